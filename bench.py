@@ -81,7 +81,17 @@ def parse():
                     help="the timed regions' delivery consumer as the C++ thread of tests/cxx/consumer_thread.cpp instead of a python thread; the other one is "
                          "measured in a leg either way (delivered_to_host.consumers).  Same-box pairs at 20 steps: python 463 k, C++ 440 k in the timed regions "
                          "(profiles/r06_ab/ab10_consumers.txt; as a leg both reach 455-468 k): the python thread stays the default")
-    ap.add_argument("--regions", type=int, default=3, help="timed regions of --steps steps each; value = the median region")
+    ap.add_argument("--regions", type=int, default=None,
+                    help="timed regions of --steps steps each; value = the median region (default: 1, so that --steps is the number of timed "
+                         "steps; 3 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the stand-alone per-kernel pass and the roofline, the live VALU and link probes, "
+                         "three timed regions, the delivered_to_host legs with the oracle FIB check, the host-to-host leg, the SNR sweep, the "
+                         "single-ensemble legs and the CPU baseline (each --no-* option still leaves its part out).  Without it a run sets up, "
+                         "warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step decoded (FIBs + CRC flags, the logical frames of every sub-channel, "
+                         "the newest super frames) as DIR/<name>.npy in float32; the inputs are seeded, so runs with the same arguments compare")
     ap.add_argument("--short-chunk-last", action="store_true", help="experiment: a region's short chunk last instead of first (profiles/r06_ab/ab14)")
     ap.add_argument("--taper", action="store_true",
                     help="experiments: with the delivery open, issue the last 7 frames of a region as chunks of 4, 2, 1 (the final slab copy, which nothing "
@@ -102,7 +112,10 @@ def parse():
     ap.add_argument("--layout", choices=["uniform", "mixed"], default="uniform",
                     help="mixed (not the headline): every second ensemble carries a 16-service multiplex of 7 different "
                          "protection profiles instead of 18 x 64 kbit/s EEP 3-A")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.regions is None:
+        args.regions = 3 if args.full else 1
+    return args
 
 
 def hip():
@@ -827,6 +840,52 @@ def oracle_fib_check(eng, sink, subch, streams, ring_frames):
     return {"fibs_compared": tot, "fibs_equal": same, "streams": sorted(res)}
 
 
+DUMP_BYTES = 64 * 10 ** 6        # --dump-outputs writes at most this much
+
+
+def dump_outputs(eng, args, subch, dx, out_dir):
+    """--dump-outputs: what the last timed step decoded, read back from the engine's device rings through the C ABI (dabx_read_fibs /
+    _msc / _superframes: the same bytes the delivery hands a caller), as float32 .npy files.  Every stream while the files stay under
+    DUMP_BYTES, else a fixed seeded sample of streams (streams.npy names them); super frames of a smaller seeded sample.
+      fibs [S, 12, 32], fib_crc [S, 12]       the FIBs of the stream's newest frame and their CRC flags
+      msc [S, M, 4, 3 * max kbps]             the 4 logical frames (CIFs) of that frame per sub-channel, zero-padded to the widest one
+      superframes [S2, M, 110 * max kbps / 8]  the newest RS-corrected super frame per sub-channel (super_streams.npy names S2)"""
+    L = dx.load()
+    S = args.streams
+    lays = [[] if args.fic_only else layout_of(args, subch, s % args.ensembles) for s in range(S)]
+    M = max(len(l_) for l_ in lays)
+    kb = max([c.kbps for l_ in lays for c in l_] or [0])
+    per_stream = 4 * (384 + 12 + M * 4 * 3 * kb)
+    n = min(S, max(1, (DUMP_BYTES * 7 // 8) // per_stream))
+    rng = np.random.default_rng(12345)
+    streams = np.arange(S) if n == S else np.sort(rng.choice(S, n, replace=False))
+    sup = streams if len(streams) <= 32 else np.sort(rng.choice(streams, 32, replace=False))
+    fibs = np.zeros((len(streams), 12, 32), np.float32)
+    crc = np.zeros((len(streams), 12), np.float32)
+    msc = np.zeros((len(streams), M, 4, 3 * kb), np.float32)
+    sf = np.zeros((len(sup), M, 110 * kb // 8), np.float32)
+    for k, s in enumerate(streams):
+        f, c = eng.read_fibs(int(s), 1)
+        assert len(f) == 1, "stream %d has decoded no frame" % s
+        fibs[k], crc[k] = f[0], c[0]
+        for j, sc in enumerate(lays[s]):
+            buf = np.zeros(4 * 3 * sc.kbps, np.uint8)
+            got = dx.check(L.dabx_read_msc(eng._h, int(s), j, 4, buf.ctypes.data_as(C.c_void_p)))
+            msc[k, j, :got, :3 * sc.kbps] = buf[:got * 3 * sc.kbps].reshape(got, 3 * sc.kbps)
+    for k, s in enumerate(sup):
+        for j, sc in enumerate(lays[s]):
+            buf = np.zeros(110 * sc.kbps // 8, np.uint8)
+            got = dx.check(L.dabx_read_superframes(eng._h, int(s), j, 1, buf.ctypes.data_as(C.c_void_p)))
+            sf[k, j, :buf.size] = buf if got else 0
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"fibs": fibs, "fib_crc": crc, "streams": streams.astype(np.float32)}
+    if not args.fic_only:
+        arrays.update(msc=msc, superframes=sf, super_streams=sup.astype(np.float32))
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BYTES
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def load_traffic(dom):
     """HBM bytes and VALU instructions per FRAME of kernel `dom` from the committed rocprofv3 --pmc passes (tools/prof_round.sh)."""
     for name in ("r06_traffic.json", "r05_traffic.json", "r04_traffic.json", "r03_traffic_final.json", "r03_traffic.json", "r02_traffic.json", "r01_traffic.json"):
@@ -943,7 +1002,7 @@ def main():
     subch = ds.default_subchannels(18, 64)
     dx = None
     link_probe = [None]
-    if not dry and rank == 0 and n_joined == 1:
+    if not dry and rank == 0 and n_joined == 1 and args.full:
         measure_valu_peak()                          # child processes, done before this process creates its engine
         link_probe[0] = measure_link_probe()
     single = None
@@ -958,7 +1017,7 @@ def main():
         # count) an engine's streams share queues with other engines' -- a one-stream engine with the MSC on, whose frame rate is a dependency loop
         # across its streams, then runs 22 % slower (10 750 -> 8 300 frames/s), and the 512-stream engine 1.7 % (both measured:
         # profiles/r06_ab/ab12_engines_per_process.txt): neither measurement may be the other's third engine.
-        if rank == 0 and n_joined == 1 and args.layout == "uniform" and not args.no_single_legs:
+        if rank == 0 and n_joined == 1 and args.layout == "uniform" and args.full and not args.no_single_legs:
             single = single_legs_in_child(args)
         eng = dx.Engine(n_streams=args.streams, ring_frames=10, max_subch=18, out_frames=8, fic_only=args.fic_only,
                         viterbi_tie_mode=args.viterbi_tie_mode, exact_level_tracker=args.exact_level)
@@ -1023,7 +1082,8 @@ def main():
     PROF_STEPS = 7
     ms = (C.c_double * 16)(); cnt = (C.c_int64 * 16)(); names = (C.c_char_p * 16)()
     share, sa_launch, dom, nk = {}, {}, None, 0
-    if not dry:
+    profiled = not dry and args.full
+    if profiled:
         dx.check(dx.load().dabx_set_profiling(eng._h, -1))
         step(PROF_STEPS)
         eng.synchronize()
@@ -1040,13 +1100,19 @@ def main():
         eng.delivery_open(slots=4, what=args.deliver_what, copy_engine=args.deliver_copy_engine)
         sink = (CxxSink if cxx_main else DeliverySink)(eng, sample_streams)
         delivering[0] = True
+    if not profiled and not dry:
+        # Without --full the line is ONE timed region: untimed, 4 chunks of 7 steps first touch every host slab of the delivery once and bring
+        # the clocks back after the slabs' allocation (--full's first region pays that and is slower than the two after it: the median hides it)
+        step(4 * 7)
+        eng.synchronize()
+        sink_catch_up()
     step(args.warmup)
     eng.synchronize()
     sink_catch_up()
-    if not dry:
+    if profiled:
         dx.check(dx.load().dabx_set_profiling(eng._h, 2 + dom_idx))
 
-    # ---- the timed regions: args.regions (3) x EXACTLY args.steps steps, each bracketed by barrier + device synchronisation on both sides;
+    # ---- the timed regions: args.regions (1; 3 with --full) x EXACTLY args.steps steps, each bracketed by barrier + device synchronisation on both sides;
     # `value` is the MEDIAN region (one 19-ms region is a lottery ticket: 517-560 k across the pool for one library), value_min / value_max the
     # spread.  With the delivery open (default) a region ends when the consumer has taken and given back the last chunk: IQ -> bytes in host memory.
     taper = deliver_on and ("short-last" if args.short_chunk_last else args.taper)
@@ -1064,9 +1130,11 @@ def main():
         barrier()
         dt = time.perf_counter() - t0
         regions.append({"c1": c1, "c2": eng.counters(), "d1": d1, "d2": sink.totals() if sink else None, "dt": dt, "host_s": host_s})
-    if not dry:
+    if profiled:
         nk = dx.check(dx.load().dabx_get_profile(eng._h, ms, cnt, names))
         dx.check(dx.load().dabx_set_profiling(eng._h, 0))
+    if args.dump_outputs and not dry and rank == 0:
+        dump_outputs(eng, args, subch, dx, args.dump_outputs)
 
     # max over ranks of each region's elapsed time, sum over ranks of its counters (the only collectives of the path, outside the timing)
     from dabstar_amd import shard
@@ -1099,7 +1167,7 @@ def main():
     # (not_delivered), a steady leg of >= 98 steps both ways, what a receiver's host side needs (half the bytes), and the same loop with a
     # C++ consumer thread instead of the python one (consumers).
     deliv = fibchk = needs = None
-    if not dry and not args.no_deliver_leg:
+    if not dry and args.full and not args.no_deliver_leg:
         def leg(n, taper_=False):
             eng.synchronize()
             sink_catch_up()
@@ -1201,7 +1269,7 @@ def main():
                              "calibration_GBps": round(dinfo["calibration_GBps"], 2),
                              "note": "the library's own clock around every slab transfer (dabx_delivery_get_info)"},
                      scope="this rank's GPU")
-    elif sink is not None:                                 # --no-deliver-leg with the delivery in the timed regions: close it, nothing else
+    elif sink is not None:                                 # no delivered_to_host legs, the delivery in the timed regions: close it, nothing else
         delivering[0] = False
         eng.synchronize()
         sink.finish()
@@ -1213,17 +1281,17 @@ def main():
     eng = None
     h2h = None
     # (the one-GPU line carries the per-link and per-ensemble legs; an N-GPU run is the scaling measurement and stays lean)
-    if not dry and rank == 0 and n_joined == 1 and args.layout == "uniform" and not args.fic_only and not args.no_host_leg:
+    if not dry and rank == 0 and n_joined == 1 and args.layout == "uniform" and not args.fic_only and args.full and not args.no_host_leg:
         h2h = host_to_host_leg(args, subch, dx, link_probe[0])
     sweep = None
-    if (not dry and rank == 0 and n_joined == 1 and args.layout == "uniform" and not args.fic_only and not args.no_snr_sweep and
+    if (not dry and rank == 0 and n_joined == 1 and args.layout == "uniform" and not args.fic_only and args.full and not args.no_snr_sweep and
             args.streams >= 48 and not args.unlocked and not args.exact_level):
         sweep = snr_sweep_legs(torch, dev, args, rank, subch, dx)
     gc.enable()
     if rank == 0:
         value = frames / dt
         roofline = None
-        if not dry:
+        if profiled:
             kern = {names[i].decode(): (ms[i] / cnt[i]) for i in range(nk) if cnt[i]}          # average launch duration (timed region)
             launches = {names[i].decode(): int(cnt[i]) for i in range(nk) if cnt[i]}
             units = (args.streams - args.unlocked) * args.steps * len(regions) / launches[dom]      # frames one launch of that kernel processes (average over the timed regions)
@@ -1279,15 +1347,16 @@ def main():
         out = {
             "metric": "DAB Mode-I ensembles/s (2.048 MS/s IQ->MSC bytes) per GPU; FIB CRC match %",
             "value": round(value, 1), "unit": "frames/s", "n_gpus": n_joined, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(1e3 * dt / args.steps, 4),
+            "ms_per_step": round(1e3 * dt / args.steps, 6),
             # value = the median of the timed regions (each EXACTLY `steps` steps, barrier + synchronise both sides, max over ranks)
             "value_min": round(regions[order[0]]["value"], 1), "value_max": round(regions[order[-1]]["value"], 1),
-            "timed_regions": [{"value": round(R["value"], 1), "ms_per_step": round(1e3 * R["dt_max"] / args.steps, 4)} for R in regions],
+            "timed_regions": [{"value": round(R["value"], 1), "ms_per_step": round(1e3 * R["dt_max"] / args.steps, 6)} for R in regions],
             "results": ("delivered to page-locked host memory inside every timed region (config.delivered_to_host; the rate with the results left in "
                         "the device rings: delivered_to_host.not_delivered)") if deliver_on else "left in the device rings (--no-deliver)",
             # CPU time this rank spent inside dabx_commit_iq + dabx_process per step (kernel launches and event traffic, no device
-            # wait): what one of N rank processes needs from its host core per step
-            "host_us_per_step": round(1e6 * host_s / args.steps, 2),
+            # wait): what one of N rank processes needs from its host core per step.  With the delivery open it is taken from steps
+            # without it (the delivered_to_host legs): --full only
+            "host_us_per_step": None if deliver_on and not args.full else round(1e6 * host_s / args.steps, 2),
             "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f32+i32", "data": "synthetic",
             "config": {"workload": ("FIC only, " if args.fic_only else "") +
@@ -1310,9 +1379,10 @@ def main():
             if all(r["frames_per_s"] > 0 for r in reports) else None,
             "collective_backend": (("gloo" if dry else "rccl %s" % ".".join(str(v) for v in torch.cuda.nccl.version())) if dist is not None else None),
             "chain": {"algorithmic_bytes_per_frame": a_frame, "achieved_GBps": round(value / n_joined * a_frame / 1e9, 2),
-                      "frac_of_hbm_peak": round(value / n_joined * a_frame / HBM_PEAK, 6),
-                      "kernel_ms_per_step_standalone": {k: round(v, 4) for k, v in share.items()}},
+                      "frac_of_hbm_peak": round(value / n_joined * a_frame / HBM_PEAK, 6)},
         }
+        if profiled:
+            out["chain"]["kernel_ms_per_step_standalone"] = {k: round(v, 4) for k, v in share.items()}
         if h2h is not None:
             out["config"]["host_to_host"] = h2h
         if single is not None:
@@ -1349,7 +1419,7 @@ def main():
         if args.layout == "mixed":       # the byte model above is the uniform layout's: no roofline claim for this variant
             out["config"]["workload"] = out["config"]["workload"].replace("18x64 kbit/s EEP 3-A DAB+ each", "alternating 18x64 kbit/s EEP 3-A and a 16-service multiplex of 7 profiles (32..128 kbit/s, EEP 2-A/3-A/3-B)")
             out["roofline"] = None
-        if n_joined == 1 and not dry and not args.no_cpu_baseline and args.layout == "uniform":
+        if n_joined == 1 and not dry and args.full and not args.no_cpu_baseline and args.layout == "uniform":
             out["cpu_baseline"] = cpu_baseline(args, subch)
         line = json.dumps(out)
     else:

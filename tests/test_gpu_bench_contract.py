@@ -1,5 +1,5 @@
 """GPU: the one JSON line bench.py prints keeps its contract (the driver parses it): metric / value / unit, the run's own
-parameters, the `roofline` object of the dominant kernel with measured traffic and VALU figures, the `chain` view, and a
+parameters, with --full the `roofline` object of the dominant kernel with measured traffic and VALU figures, the `chain` view, and a
 receiver that actually decoded everything it was timed on."""
 import json
 import os
@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_line_keeps_its_contract():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "14", "--warmup", "2", "--no-cpu-baseline"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "14", "--warmup", "2", "--no-cpu-baseline"],
                        cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -72,3 +72,28 @@ def test_bench_line_keeps_its_contract():
     #  no longer far ahead of the full receiver)
     assert one["full"]["frames_per_s"] > 5000 and one["fic_only"]["frames_per_s"] > 0.95 * one["full"]["frames_per_s"] and one["full"]["superframes_failed"] == 0
     assert "child process" in one["measured_in"]
+
+
+def test_plain_bench_line_times_exactly_its_steps_and_dumps_the_last_one(tmp_path):
+    """Without --full: one timed region of exactly --steps steps, the headline fields, nothing of what --full adds; --dump-outputs writes
+    what the last step decoded (float32, under 64 MB): every stream's FIBs with good CRCs and the logical frames of all 18 sub-channels."""
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "14", "--warmup", "2", "--dump-outputs", str(out)],
+                       cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    j = json.loads(lines[0])
+    assert j["metric"].startswith("DAB Mode-I ensembles/s") and j["unit"] == "frames/s" and j["higher_is_better"] is True and j["dtype"] == "f32+i32"
+    assert (j["steps"], j["warmup"], len(j["timed_regions"])) == (14, 2, 1) and j["value"] == j["timed_regions"][0]["value"]
+    assert j["value"] > 50000 and abs(j["value"] * j["ms_per_step"] * 1e-3 - 512) < 2
+    assert j["streams_locked"] == 512 and j["fib_crc_pass_pct"] == 100.0 and j["superframes_failed"] == 0
+    assert j["msc_bytes"] == 512 * 14 * 4 * 18 * 192
+    assert j["roofline"] is None and "cpu_baseline" not in j and "delivered_to_host" not in j["config"] and "snr_sweep" not in j["config"]
+    import numpy as np
+    files = {f.stem: np.load(f) for f in out.glob("*.npy")}
+    assert set(files) == {"fibs", "fib_crc", "msc", "superframes", "streams", "super_streams"}
+    assert all(a.dtype == np.float32 for a in files.values()) and sum(a.nbytes for a in files.values()) <= 64 * 10 ** 6
+    assert files["fibs"].shape == (512, 12, 32) and files["fib_crc"].shape == (512, 12) and (files["fib_crc"] == 1).all()
+    assert files["msc"].shape == (512, 18, 4, 192) and files["msc"].max() > 0 and files["msc"].max() <= 255
+    assert files["superframes"].shape == (32, 18, 880) and files["superframes"].any()

@@ -20,7 +20,7 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 
 
 def _bench(*extra):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline", *extra]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", *extra]
     if "--no-deliver-leg" not in extra:
         cmd += ["--no-deliver-leg", "--no-single-legs"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)

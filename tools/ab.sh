@@ -10,7 +10,7 @@ for r in $(seq 1 $REPS); do
     IFS='|' read -r name lib envs extra <<< "$cfg"
     libenv=""
     if [ "$lib" != "-" ]; then libenv="DABX_LIB=$(realpath $lib)"; fi
-    env $libenv $envs python3 bench.py ${BENCH_ARGS:---steps 49 --warmup 14} --no-cpu-baseline $extra > $OUT/${name}_$r.json 2> $OUT/${name}_$r.err
+    env $libenv $envs python3 bench.py --full ${BENCH_ARGS:---steps 49 --warmup 14} --no-cpu-baseline $extra > $OUT/${name}_$r.json 2> $OUT/${name}_$r.err
     python3 - "$OUT/${name}_$r.json" "$name" <<'PY'
 import json, sys
 try:

@@ -2,7 +2,7 @@
 # Two PMC passes restricted to a kernel regex. Usage: tools/prof_pmc2.sh <outdir> <regex> [bench args]
 OUT=$1; FILT=$2; shift 2
 export TMPDIR=/tmp
-ARGS="--steps 8 --warmup 4 --no-cpu-baseline $*"
+ARGS="--full --steps 8 --warmup 4 --no-cpu-baseline $*"
 mkdir -p $OUT
 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_ANY SQ_WAIT_INST_ANY \
   --kernel-include-regex "$FILT" -d $OUT/p1 --output-format csv -- python3 bench.py $ARGS > $OUT/p1.log 2>&1

@@ -11,11 +11,11 @@ export DABX_PROF_COMMIT=${2:-unknown}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 # (the product form: the timed regions deliver; legs that would add other engines' kernels to the statistics are left out)
-rocprofv3 --kernel-trace --stats -d $OUT/stats --output-format csv -- python3 bench.py --no-cpu-baseline --no-deliver-leg --no-host-leg --no-single-legs --no-snr-sweep > $OUT/stats_bench.log 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/stats --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-deliver-leg --no-host-leg --no-single-legs --no-snr-sweep > $OUT/stats_bench.log 2>&1
 FILT="k_msc_vitT|k_msc_prep|k_demap_frame|k_demap_fic|k_symbols|k_dabplus|k_fic_frame|k_frame_head|k_frame_tail|k_acquire|k_deliver"
-ARGS="--steps 14 --warmup 7 --regions 1 --no-cpu-baseline --no-deliver-leg --no-host-leg --no-single-legs --no-snr-sweep"
+ARGS="--full --steps 14 --warmup 7 --regions 1 --no-cpu-baseline --no-deliver-leg --no-host-leg --no-single-legs --no-snr-sweep"
 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_ANY SQ_WAIT_INST_ANY \
   --kernel-include-regex "$FILT" -d $OUT/p1 --output-format csv -- python3 bench.py $ARGS > $OUT/p1.log 2>&1
 rocprofv3 --kernel-trace --pmc SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE \
