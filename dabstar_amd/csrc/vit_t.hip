@@ -278,8 +278,8 @@ template <int TIE> struct VtTie { static constexpr int LIMTOP = 0, REN2 = 0; };
 template <> struct VtTie<1> { static constexpr int LIMTOP = 2 * 65535, REN2 = 2 * 60000; };
 template <> struct VtTie<2> { static constexpr int LIMTOP = 2 * 32767, REN2 = 2 * 30000; };
 
-template <int C, int TIE = 0, bool CLAMP = false>
-__device__ __forceinline__ void vt_one(vt::s2 (&R)[32], const VtCycle &cy, int t, const VtDec &dec_lane, vt::s2 v2n, int &Coff)
+template <int C, int TIE = 0, bool CLAMP = false, bool RC = false>
+__device__ __forceinline__ void vt_one(vt::s2 (&R)[32], const VtCycle &cy, int t, const VtDec &dec_lane, vt::s2 v2n, int &Coff, vt::s2 ref)
 {
   // the step's four symbols: dword + byte lane each (the lanes are wave-uniform and end up in SGPR selectors); the packed
   // branch metrics come straight from those (vit_t_gen.h, bm<C>): no scalar extraction, no 32-bit sums
@@ -301,7 +301,7 @@ __device__ __forceinline__ void vt_one(vt::s2 (&R)[32], const VtCycle &cy, int t
       lim = vt::pk(l, l);
     }
   }
-  if constexpr (C == 0) { vt::bm0(w, b, v2n, M); vt::step0<TIE, CLAMP>(R, M, acc0, acc1, lim); }
+  if constexpr (C == 0) { vt::bm0(w, b, v2n, M); vt::step0<TIE, CLAMP, RC>(R, M, acc0, acc1, lim, ref); }
   else if constexpr (C == 1) { vt::bm1(w, b, v2n, M); vt::step1<TIE, CLAMP>(R, M, acc0, acc1, lim); }
   else if constexpr (C == 2) { vt::bm2(w, b, v2n, M); vt::step2<TIE, CLAMP>(R, M, acc0, acc1, lim); }
   else if constexpr (C == 3) { vt::bm3(w, b, v2n, M); vt::step3<TIE, CLAMP>(R, M, acc0, acc1, lim); }
@@ -316,20 +316,23 @@ __device__ __forceinline__ void vt_one(vt::s2 (&R)[32], const VtCycle &cy, int t
   }
 }
 
-template <int TIE, bool CLAMP>
-__device__ __forceinline__ void vt_cycle6(vt::s2 (&R)[32], const VtCycle &cy, int t0, const VtDec &dec_lane, vt::s2 v2n, int &Coff)
+// RC: the cycle's first step also re-centres the metrics on `ref` (tie mode 0 only; vt_decode)
+template <int TIE, bool CLAMP, bool RC = false>
+__device__ __forceinline__ void vt_cycle6(vt::s2 (&R)[32], const VtCycle &cy, int t0, const VtDec &dec_lane, vt::s2 v2n, int &Coff,
+                                          vt::s2 ref = vt::s2{0, 0})
 {
-  vt_one<0, TIE, CLAMP>(R, cy, t0 + 0, dec_lane, v2n, Coff);
-  vt_one<1, TIE, CLAMP>(R, cy, t0 + 1, dec_lane, v2n, Coff);
-  vt_one<2, TIE, CLAMP>(R, cy, t0 + 2, dec_lane, v2n, Coff);
-  vt_one<3, TIE, CLAMP>(R, cy, t0 + 3, dec_lane, v2n, Coff);
-  vt_one<4, TIE, CLAMP>(R, cy, t0 + 4, dec_lane, v2n, Coff);
-  vt_one<5, TIE, CLAMP>(R, cy, t0 + 5, dec_lane, v2n, Coff);
+  vt_one<0, TIE, CLAMP, RC>(R, cy, t0 + 0, dec_lane, v2n, Coff, ref);
+  vt_one<1, TIE, CLAMP>(R, cy, t0 + 1, dec_lane, v2n, Coff, ref);
+  vt_one<2, TIE, CLAMP>(R, cy, t0 + 2, dec_lane, v2n, Coff, ref);
+  vt_one<3, TIE, CLAMP>(R, cy, t0 + 3, dec_lane, v2n, Coff, ref);
+  vt_one<4, TIE, CLAMP>(R, cy, t0 + 4, dec_lane, v2n, Coff, ref);
+  vt_one<5, TIE, CLAMP>(R, cy, t0 + 5, dec_lane, v2n, Coff, ref);
 }
-template <int TIE, bool ALWAYS_CLAMP>
-__device__ __forceinline__ void vt_cycle(vt::s2 (&R)[32], const VtCycle &cy, int t0, const VtDec &dec_lane, vt::s2 v2n, int &Coff)
+template <int TIE, bool ALWAYS_CLAMP, bool RC = false>
+__device__ __forceinline__ void vt_cycle(vt::s2 (&R)[32], const VtCycle &cy, int t0, const VtDec &dec_lane, vt::s2 v2n, int &Coff,
+                                         vt::s2 ref = vt::s2{0, 0})
 {
-  if constexpr (TIE == 0) vt_cycle6<0, false>(R, cy, t0, dec_lane, v2n, Coff);
+  if constexpr (TIE == 0) vt_cycle6<0, false, RC>(R, cy, t0, dec_lane, v2n, Coff, ref);
   else {
     bool clamp = ALWAYS_CLAMP;
     if constexpr (!ALWAYS_CLAMP) {
@@ -355,26 +358,35 @@ __device__ __forceinline__ VtDec6 vt_load_dec(const VtDec &dec_lane, int t0)
   d.w3 = vt_dec_load(dec_lane, t0 + 3); d.w4 = vt_dec_load(dec_lane, t0 + 4); d.w5 = vt_dec_load(dec_lane, t0 + 5);
   return d;
 }
-// step t of class C (viterbi_spiral.cpp:114-125 in label space): the decision of label L is bit pos_c[L] of the word; it
-// replaces bit p = 5 - C of the label and is output bit t - 6 (PRBS, backend.cpp:155-158, and byte packing on the way out)
+// step t of class C (viterbi_spiral.cpp:114-125 in label space).  `acc` holds the decoded bits, newest at bit 31: its top six
+// bits are the decisions of steps t + 1 .. t + 6, which is the label in another bit order, so bk_c = VT_BK[C] maps them
+// straight to the bit position of the step's decision (tools/gen_vit_t.py, chain_back).  The decision is shifted in at the
+// top (v_alignbit_b32) and is output bit t - 6; every 32 bits the word is complete in reversed byte order (byte packing,
+// MSB first) and leaves with the PRBS (backend.cpp:155-158).  Per bit: one LDS look-up and three VALU operations.
 template <int C>
-__device__ __forceinline__ void vt_back_one(const uint2 w, int t, unsigned &L, unsigned &outw, uint32_t *out, const uint32_t *prbs,
-                                            const unsigned char *pos_c)
+__device__ __forceinline__ void vt_back_one(const uint2 w, int t, unsigned &acc, uint32_t *out, const uint32_t *prbs,
+                                            const unsigned char *bk_c)
 {
-  constexpr unsigned p = 5 - C;                                   // VT_P[C]
-  const unsigned pos = pos_c[L];
+  const unsigned pos = bk_c[acc >> 26];
   const unsigned long long ww = ((unsigned long long)w.y << 32) | w.x;
-  const unsigned bit = (unsigned)(ww >> pos) & 1u;
+  acc = __builtin_amdgcn_alignbit((unsigned)(ww >> pos), acc, 1u);
   const int qb = t - 6;
-  outw |= bit << (((qb >> 3) & 3) * 8 + 7 - (qb & 7));
-  L = (L & ~(1u << p)) | (bit << p);
   if ((qb & 31) == 0) {                                           // wave-uniform
     // PRBS word over the scalar cache (constant table): a vector load here would wait for vmcnt(0), i.e. drain the
     // prefetched decision words, every 32 steps
     const unsigned pw = ((const __attribute__((address_space(4))) uint32_t *)(const void *)prbs)[qb >> 5];
-    if (out) out[qb >> 5] = outw ^ pw;
-    outw = 0;
+    if (out) out[qb >> 5] = __builtin_bswap32(acc) ^ pw;
   }
+}
+__device__ __forceinline__ void vt_back6(const VtDec6 &d, int tc, unsigned &acc, uint32_t *out, const uint32_t *prbs,
+                                         const unsigned char (*bk)[64])
+{
+  vt_back_one<5>(d.w5, tc + 5, acc, out, prbs, bk[5]);
+  vt_back_one<4>(d.w4, tc + 4, acc, out, prbs, bk[4]);
+  vt_back_one<3>(d.w3, tc + 3, acc, out, prbs, bk[3]);
+  vt_back_one<2>(d.w2, tc + 2, acc, out, prbs, bk[2]);
+  vt_back_one<1>(d.w1, tc + 1, acc, out, prbs, bk[1]);
+  vt_back_one<0>(d.w0, tc + 0, acc, out, prbs, bk[0]);
 }
 
 // Diagnostic (tools/vit_timeline.py): when a buffer is registered through dabx_internal_set_vt_timeline every decoder wave
@@ -389,7 +401,7 @@ __device__ unsigned g_vt_timeline_n = 0;
 // packed, de-dispersed bytes go (nullptr: nothing is stored).
 template <int TIE, bool ALWAYS_CLAMP>
 __device__ __forceinline__ void vt_decode(vt_rsrc in_grp, vt_cmap cmap, int nsteps, const VtDec &dec_lane, uint32_t *out, const uint32_t *prbs,
-                                          const unsigned char (*pos_tab)[64], int lane, unsigned long long &t_forward_end, bool want_time)
+                                          const unsigned char (*bk_tab)[64], int lane, unsigned long long &t_forward_end, bool want_time)
 {
   vt::s2 R[32];
 #pragma unroll
@@ -405,56 +417,59 @@ __device__ __forceinline__ void vt_decode(vt_rsrc in_grp, vt_cmap cmap, int nste
   vt_fetch(cb, in_grp, lane, cmap, 6);
   auto recentre = [&]() {                                  // every 12 steps on the metric of label 0
     const vt::s2 ref = vt::pk(R[0].x, R[0].x);
-    if constexpr (TIE != 0) Coff += (int)R[0].x;
+    if constexpr (TIE != 0) {                              // tie modes: here (the cycle's saturation test reads the re-centred R);
+      Coff += (int)R[0].x;                                 // tie mode 0: inside the cycle's first step (vt_cycle<..., RC = true>)
 #pragma unroll
-    for (int r = 0; r < 32; r++) R[r] = R[r] - ref;
+      for (int r = 0; r < 32; r++) R[r] = R[r] - ref;
+    }
+    return ref;
   };
   vt::s2 v2n;                                                      // (2, -2), pinned in a VGPR (VOP3P takes no literal on gfx9)
   asm volatile("v_mov_b32 %0, %1" : "=v"(v2n) : "s"(0xFFFE0002u));
   int t = 0;
   for (; t + 12 <= nsteps; t += 12) {
-    recentre();
-    vt_cycle<TIE, ALWAYS_CLAMP>(R, ca, t, dec_lane, v2n, Coff);
+    const vt::s2 ref = recentre();
+    vt_cycle<TIE, ALWAYS_CLAMP, TIE == 0>(R, ca, t, dec_lane, v2n, Coff, ref);
     vt_fetch(ca, in_grp, lane, cmap, t + 12 < last ? t + 12 : last);
     vt_cycle<TIE, ALWAYS_CLAMP>(R, cb, t + 6, dec_lane, v2n, Coff);
     vt_fetch(cb, in_grp, lane, cmap, t + 18 < last ? t + 18 : last);
   }
   if (t < nsteps) {                                                // odd number of cycles
-    recentre();
-    vt_cycle<TIE, ALWAYS_CLAMP>(R, ca, t, dec_lane, v2n, Coff);
+    const vt::s2 ref = recentre();
+    vt_cycle<TIE, ALWAYS_CLAMP, TIE == 0>(R, ca, t, dec_lane, v2n, Coff, ref);
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_s_waitcnt(0);
   __syncthreads();
   if (want_time) t_forward_end = __builtin_amdgcn_s_memrealtime();
 
-  // chain-back per lane (viterbi_spiral.cpp:114-125 in label space) + PRBS (backend.cpp:155-158) + byte packing.
-  // The chain is one LDS look-up (bit position of the label's decision in the step's word) and three VALU operations per
-  // step and lane; the decision words themselves are fetched two 6-step cycles ahead of their use -- their addresses do not
-  // depend on the path, only the bit that is picked does -- so no memory latency sits on the chain.  (Kept in NAMED
-  // registers: as arrays indexed through a lambda the compiler had put one set in scratch and one in LDS, and the chain
-  // then ran at ~1150 cycles per step, a third of the kernel.)
-  unsigned L = 0, outw = 0;
-  VtDec6 cur = vt_load_dec(dec_lane, nsteps - 6);
-  VtDec6 nx1 = vt_load_dec(dec_lane, nsteps - 12);                // nsteps >= 18 for every legal profile (24 * 8 + 6 = 198 at least)
-  for (int tc = nsteps - 6; tc >= 6; tc -= 6) {
-    const int tf = tc - 12 > 6 ? tc - 12 : 6;                      // beyond the start: fetch a valid cycle again (never consumed)
-    const VtDec6 nx2 = vt_load_dec(dec_lane, tf);
-    vt_back_one<5>(cur.w5, tc + 5, L, outw, out, prbs, pos_tab[5]);
-    vt_back_one<4>(cur.w4, tc + 4, L, outw, out, prbs, pos_tab[4]);
-    vt_back_one<3>(cur.w3, tc + 3, L, outw, out, prbs, pos_tab[3]);
-    vt_back_one<2>(cur.w2, tc + 2, L, outw, out, prbs, pos_tab[2]);
-    vt_back_one<1>(cur.w1, tc + 1, L, outw, out, prbs, pos_tab[1]);
-    vt_back_one<0>(cur.w0, tc + 0, L, outw, out, prbs, pos_tab[0]);
-    cur = nx1; nx1 = nx2;
+  // chain-back per lane (viterbi_spiral.cpp:114-125 in label space) + PRBS (backend.cpp:155-158) + byte packing (vt_back_one).
+  // The chain is one LDS look-up and three VALU operations per step and lane; the decision words themselves are fetched two
+  // 6-step cycles ahead of their use -- their addresses do not depend on the path, only the bit that is picked does -- so no
+  // memory latency sits on the chain.  (Kept in NAMED registers: as arrays indexed through a lambda the compiler had put one
+  // set in scratch and one in LDS, and the chain then ran at ~1150 cycles per step, a third of the kernel.)  Three sets take
+  // turns, the loop unrolled by three, so that no set is copied into another between cycles.
+  unsigned acc = 0;
+  VtDec6 da = vt_load_dec(dec_lane, nsteps - 6), db = vt_load_dec(dec_lane, nsteps - 12), dc;   // nsteps >= 18 for every legal
+  auto ahead = [&](int tf) { return vt_load_dec(dec_lane, tf > 6 ? tf : 6); };                 // profile (24 * 8 + 6 at least);
+  int tc = nsteps - 6;                                             // beyond the start a valid cycle is fetched again (never consumed)
+  for (; tc >= 18; tc -= 18) {                                     // (one exit only: the compiler then waits for nothing at the top)
+    dc = ahead(tc - 12);
+    vt_back6(da, tc, acc, out, prbs, bk_tab);
+    da = ahead(tc - 18);
+    vt_back6(db, tc - 6, acc, out, prbs, bk_tab);
+    db = ahead(tc - 24);
+    vt_back6(dc, tc - 12, acc, out, prbs, bk_tab);
   }
+  if (tc >= 6) vt_back6(da, tc, acc, out, prbs, bk_tab);
+  if (tc >= 12) vt_back6(db, tc - 6, acc, out, prbs, bk_tab);
 }
 
 // grid = groups, 64 threads.  TIE: cfg.viterbi_tie_mode (0 canonical, 1 VITERBI_AVX2, 2 VITERBI_SSE2 arithmetic).
 template <int TIE>
 __device__ __forceinline__ void msc_vitT_body(const EngineDev &e, int cifs, const MscLaunch &ML, const uint32_t *prbs)
 {
-  __shared__ unsigned char pos_tab[6][64];
+  __shared__ unsigned char bk_tab[6][64];
   const int lane = threadIdx.x;
   unsigned long long *const tl = g_vt_timeline;
   unsigned long long tl0 = 0, tl1 = 0;
@@ -462,7 +477,7 @@ __device__ __forceinline__ void msc_vitT_body(const EngineDev &e, int cifs, cons
   // Groups are ordered longest trellis first.  All waves of a launch are resident at once (<= 4 per SIMD), so the work of
   // a SIMD is the sum over the ~4 "rounds" of 1024 blocks that landed on it: walk every second round backwards
   // (boustrophedon) so that long and short trellises pair up on the same SIMD.
-  for (int i = lane; i < 6 * 64; i += 64) pos_tab[i / 64][i % 64] = vt::VT_POS[i / 64][i % 64];
+  for (int i = lane; i < 6 * 64; i += 64) bk_tab[i / 64][i % 64] = vt::VT_BK[i / 64][i % 64];
   int gg = blockIdx.x;
   {
     constexpr int ROUND = 1024;                                    // 256 CUs x 4 SIMDs
@@ -484,7 +499,7 @@ __device__ __forceinline__ void msc_vitT_body(const EngineDev &e, int cifs, cons
   // blocks, each walking several groups) so that the front end of the following frames could co-reside were measured in round 3:
   // -9 % / -3.5 % on the chain (profiles/r03_ab/ab4_persistent_decoder_grid_cap2048_cap3072.txt): the decoder alone gets 35-50 %
   // slower and nothing that moves in next to it pays that back.
-  vt_decode<TIE, false>(in_grp, cmap, nsteps, dec_lane, out, prbs, pos_tab, lane, tl1, tl != nullptr);
+  vt_decode<TIE, false>(in_grp, cmap, nsteps, dec_lane, out, prbs, bk_tab, lane, tl1, tl != nullptr);
   if (tl && lane == 0) {
     const unsigned slot = atomicAdd(&g_vt_timeline_n, 1u);
     if (slot < g_vt_timeline_cap) {
@@ -512,14 +527,14 @@ __global__ __launch_bounds__(64) void k_msc_vitT_sse2(EngineDev e, int cifs, Msc
 template <int TIE, bool ALWAYS_CLAMP>
 __global__ __launch_bounds__(64) void k_vitT_stage(const uint32_t *symT, const uint16_t *map, int nbits, uint2 *decT, uint32_t *outw, const uint32_t *zeros)
 {
-  __shared__ unsigned char pos_tab[6][64];
+  __shared__ unsigned char bk_tab[6][64];
   const int lane = threadIdx.x, g = blockIdx.x;
-  for (int i = lane; i < 6 * 64; i += 64) pos_tab[i / 64][i % 64] = vt::VT_POS[i / 64][i % 64];
+  for (int i = lane; i < 6 * 64; i += 64) bk_tab[i / 64][i % 64] = vt::VT_BK[i / 64][i % 64];
   const int nsteps = nbits + 6, rows = nsteps + 1;
   const vt_rsrc in_grp = vt_make_rsrc(symT + (size_t)g * rows * 64, (unsigned)rows * 256u);
   unsigned long long unused = 0;
   vt_decode<TIE, ALWAYS_CLAMP>(in_grp, (vt_cmap)(const void *)map, nsteps, vt_make_dec(decT + (size_t)g * nsteps * 64, nsteps, lane),
-                               outw + ((size_t)g * 64 + lane) * (nbits / 32), zeros, pos_tab, lane, unused, false);
+                               outw + ((size_t)g * 64 + lane) * (nbits / 32), zeros, bk_tab, lane, unused, false);
 }
 
 // not part of include/dabx.h (tests/test_gpu_viterbi.py): ViterbiSpiral::deconvolve on the lane-per-trellis kernel.

@@ -72,6 +72,38 @@ def class_plan(c):
 
 PLANS = [class_plan(c) for c in range(6)]
 
+# class 0: the sign bits of the hi labels (r | 32, bytes 1 and 3 of every gather) come out inverted (model_decode)
+C0_INV = 0xFF00FF00FF00FF00
+
+
+# ---- chain-back through a window of the last six decoded bits
+# The chain-back shifts every decoded bit in at the top of a 32-bit word (acc = acc >> 1 | bit << 31, one v_alignbit_b32), so
+# before step t the top six bits v = acc >> 26 are the decisions of steps t + 1 .. t + 6 (bit 5 - j = step t + 1 + j).  The label
+# is the same six bits in class order (the decision of step t' sits at bit 5 - t' mod 6), so one table per class maps v
+# straight to the decision's bit position: VT_BK[c][v] = pos_c[label(v)].  The words come out with their bytes in reverse order
+# (one byte swap per 32 bits); nothing else is done per bit but the 64-bit shift that picks the decision.
+def bk_label(c, v):
+    L = 0
+    for j in range(6):
+        L |= ((v >> (5 - j)) & 1) << (5 - (c + 1 + j) % 6)
+    return L
+
+
+VT_BK = [[PLANS[c]["pos"][bk_label(c, v)] for v in range(64)] for c in range(6)]
+
+
+def chain_back(dec, nbits):
+    """Bits of the trellis from its decision words, as the kernel's chain-back forms them (v_alignbit_b32 window)."""
+    import numpy as np
+    out = np.zeros(nbits, np.uint8)
+    acc = 0
+    for t in range(nbits + 5, 5, -1):
+        c = t % 6
+        k = (dec[t] >> VT_BK[c][acc >> 26]) & 1
+        acc = (acc >> 1) | (k << 31)
+        out[t - 6] = k
+    return out
+
 
 # ------------------------------------------------------------------------------------------- python model
 def model_decode(soft, nbits):
@@ -89,9 +121,8 @@ def model_decode(soft, nbits):
     dec = []
     for t in range(nst):
         c = t % 6
-        if c == 0 and (t // 6) % 2 == 0:
-            ref = R[0][0]
-            R = [[wrap(a - ref), wrap(b - ref)] for a, b in R]
+        # re-centring on label 0 every 12 steps, folded into the class-0 step's constants: t1 = R + (w - ref), t2 = R + (-w - ref)
+        ref = R[0][0] if c == 0 and (t // 6) % 2 == 0 else 0
         y0, x1, x2 = xs[t, 0] + xs[t, 3], xs[t, 1], xs[t, 2]
         W = [(1 - 2 * ((q >> 2) & 1)) * y0 + (1 - 2 * ((q >> 1) & 1)) * x1 + (1 - 2 * (q & 1)) * x2 for q in range(8)]
         pl = PLANS[c]
@@ -99,14 +130,17 @@ def model_decode(soft, nbits):
         if c == 0:
             for r, q in pl["regs"]:
                 lo, hi = R[r]
-                w = W[q]
-                t1 = (wrap(lo + w), wrap(hi + w)); t2 = (wrap(lo - w), wrap(hi - w))
+                P, N = wrap(W[q] - ref), wrap(-W[q] - ref)
+                t1 = (wrap(lo + P), wrap(hi + P)); t2 = (wrap(lo + N), wrap(hi + N))
                 new = (min(t1[0], t2[1]), min(t1[1], t2[0]))
-                d_lo, d_hi = wrap(t2[1] - t1[0]), wrap(t1[1] - t2[0])
-                assert abs(lo + w) < 32768 and abs(hi + w) < 32768
-                if d_lo < 0: word |= 1 << pl["pos"][r]
-                if d_hi < 0: word |= 1 << pl["pos"][r | 32]
+                assert abs(lo - ref + W[q]) < 32768 and abs(hi - ref + W[q]) < 32768
+                # Y = (t2.hi - t1.lo, t2.lo - t1.hi - 1): Y.lo is the decision difference of label r, Y.hi the bitwise NOT of
+                # label r | 32's (t1.hi - t2.lo), so its sign bit is the decision inverted; the step XORs those bits back
+                y_lo, y_hi = wrap(t2[1] - t1[0]), wrap(t2[0] - t1[1] - 1)
+                if y_lo < 0: word |= 1 << pl["pos"][r]
+                if y_hi < 0: word |= 1 << pl["pos"][r | 32]
                 R[r] = list(new)
+            word ^= C0_INV
         else:
             for ra, rb, ql, qh in pl["pairs"]:
                 A, B = R[ra], R[rb]
@@ -119,15 +153,7 @@ def model_decode(soft, nbits):
                 R[ra] = [min(a0[h], b0[h]) for h in (0, 1)]
                 R[rb] = [min(a1[h], b1[h]) for h in (0, 1)]
         dec.append(word)
-    L = 0
-    out = np.zeros(nbits, np.uint8)
-    for t in range(nst - 1, 5, -1):
-        c = t % 6
-        k = (dec[t] >> PLANS[c]["pos"][L]) & 1
-        out[t - 6] = k
-        p = PLANS[c]["p"]
-        L = (L & ~(1 << p)) | (k << p)
-    return out
+    return chain_back(dec, nbits)
 
 
 # ---- the arithmetic of the reference's SIMD builds on the same register scheme (k_msc_vitT_tie, vit_t.hip) -------------
@@ -177,17 +203,24 @@ def model_decode_tie(soft, nbits, tie, always_clamp=False, stats=None):
 
             def decide(a, b, lab):                       # a: path through predecessor i, b: through i + 32
                 nonlocal word
-                d = (wrap(a - b) >= 0) if tie == 1 else (wrap(b - a) < 0)       # tie 1: NOT (a < b); tie 2: b < a
-                if d:
+                d = wrap(a - b) < 0 if tie == 1 else wrap(b - a) < 0       # tie 1: sign of a - b, the word inverted below
+                if d:                                                   # (NOT (a < b)); tie 2: b < a
                     word |= 1 << pl["pos"][lab]
             if j == 0:
                 for r, q in pl["regs"]:
                     lo, hi = R[r]
                     w = W[q]
                     t1 = (cl(wrap(lo + w)), cl(wrap(hi + w))); t2 = (cl(wrap(lo - w)), cl(wrap(hi - w)))
-                    decide(t1[0], t2[1], r)
-                    decide(t2[0], t1[1], r | 32)
+                    # one Y register per butterfly register (see model_decode); tie 1 takes the opposite operand order and the
+                    # whole word is inverted at the end, so there the lo labels come out inverted instead of the hi labels
+                    if tie == 1:
+                        y_lo, y_hi = wrap(t1[0] - t2[1]), wrap(t1[1] - t2[0] - 1)
+                    else:
+                        y_lo, y_hi = wrap(t2[1] - t1[0]), wrap(t2[0] - t1[1] - 1)
+                    if y_lo < 0: word |= 1 << pl["pos"][r]
+                    if y_hi < 0: word |= 1 << pl["pos"][r | 32]
                     R[r] = [min(t1[0], t2[1]), min(t1[1], t2[0])]
+                word ^= C0_INV
             else:
                 for ra, rb, ql, qh in pl["pairs"]:
                     A, B = R[ra], R[rb]
@@ -199,6 +232,8 @@ def model_decode_tie(soft, nbits, tie, always_clamp=False, stats=None):
                         decide(a1[h], b1[h], rb | (32 * h))
                     R[ra] = [min(a0[h], b0[h]) for h in (0, 1)]
                     R[rb] = [min(a1[h], b1[h]) for h in (0, 1)]
+            if tie == 1:
+                word ^= (1 << 64) - 1
             dec.append(word)
             if pre:
                 mn = min(min(a, b) for a, b in R)
@@ -207,15 +242,7 @@ def model_decode_tie(soft, nbits, tie, always_clamp=False, stats=None):
         Coff += 6120
     if stats is not None:
         stats["slow_cycles"] = n_slow; stats["cycles"] = nst // 6; stats["renorms"] = n_ren
-    L = 0
-    out = np.zeros(nbits, np.uint8)
-    for t in range(nst - 1, 5, -1):
-        c = t % 6
-        k = (dec[t] >> PLANS[c]["pos"][L]) & 1
-        out[t - 6] = k
-        p = PLANS[c]["p"]
-        L = (L & ~(1 << p)) | (k << p)
-    return out
+    return chain_back(dec, nbits)
 
 
 def selftest_tie():
@@ -351,12 +378,16 @@ def emit():
     A("{ s2 r; asm(\"v_pk_sub_i16 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0]\" : \"=v\"(r) : \"v\"(a), \"v\"(b)); return r; }")
     A("// v_perm_b32 selectors 8..11 = sign of S1.lo, S1.hi, S0.lo, S0.hi replicated over the byte (0x00 / 0xFF); 12 = 0x00")
     A("__device__ __forceinline__ unsigned sg(s2 s0, s2 s1) { return __builtin_amdgcn_perm(u(s0), u(s1), 0x0B0A0908u); }")
-    A("__device__ __forceinline__ unsigned sg_even(s2 dd, s2 ee) { return __builtin_amdgcn_perm(u(dd), u(ee), 0x0C0C090Au); }   // [dd.lo, ee.hi, 0, 0]")
-    A("__device__ __forceinline__ unsigned sg_odd(s2 dd, s2 ee) { return __builtin_amdgcn_perm(u(dd), u(ee), 0x090A0C0Cu); }    // [0, 0, dd.lo, ee.hi]")
+    A("// a decision word is 8 gathers: the first one fills every bit, the other seven insert their bits with one v_bfi_b32 each")
     A("template <int K> __device__ __forceinline__ void fold(unsigned &acc, unsigned p)")
-    A("{ constexpr unsigned M = 0x01010101u << K;   // one v_and_or_b32 per gather (hipcc splits the and/or otherwise)")
-    A("  if (K == 0) acc = p & M;")
-    A("  else asm(\"v_and_or_b32 %0, %1, %2, %0\" : \"+v\"(acc) : \"v\"(p), \"s\"(M)); }")
+    A("{ constexpr unsigned M = 0x01010101u << K;")
+    A("  if (K == 0) acc = p;")
+    A("  else asm(\"v_bfi_b32 %0, %1, %2, %0\" : \"+v\"(acc) : \"s\"(M), \"v\"(p)); }")
+    A("// class 0: (t2.hi - t1.lo, t2.lo - t1.hi - 1) -- the hi half is the bitwise NOT of (t1.hi - t2.lo)")
+    A("__device__ __forceinline__ s2 ydiff(s2 t2, s2 t1) { return sub_hl(t2, t1) - s(0x00010000u); }")
+    A("// tie mode 1 (the word is inverted afterwards): (t1.lo - t2.hi, t1.hi - t2.lo - 1)")
+    A("__device__ __forceinline__ s2 ydiff_t1(s2 t1, s2 t2) { return sub_lh(t1, t2) - s(0x00010000u); }")
+    A("constexpr unsigned C0_INV = 0x%08Xu;   // class 0: bits of the hi labels (bytes 1 and 3), stored inverted by ydiff" % (C0_INV & 0xFFFFFFFF))
     A("// ---- packed branch metrics (tools/gen_vit_t.py, BM_PLAN): VOP3P forms the compiler does not pick by itself")
     A("__device__ __forceinline__ s2 swap_add(s2 a)        // (a.lo + a.hi) in both halves")
     A("{ s2 r; asm(\"v_pk_add_u16 %0, %1, %1 op_sel:[0,1] op_sel_hi:[1,0]\" : \"=v\"(r) : \"v\"(a)); return r; }")
@@ -374,11 +405,11 @@ def emit():
     A("{ return s(__builtin_amdgcn_perm(w_hi, w_lo, 0x0C000C00u | b_lo | ((4u + b_hi) << 16))); }")
     A("constexpr unsigned K_M255 = 0xFF01FF01u, K_M255_P255 = 0x00FFFF01u, K_M510 = 0xFE02FE02u, K_M510_P510 = 0x01FEFE02u;")
     A("")
-    A("// exchange bit of each step class and decision bit position of every label (chain-back tables)")
-    A("__device__ constexpr unsigned char VT_P[6] = {%s};" % ", ".join(str(pl["p"]) for pl in PLANS))
-    A("__device__ constexpr unsigned char VT_POS[6][64] = {")
-    for pl in PLANS:
-        A("  {%s}," % ", ".join(str(x) for x in pl["pos"]))
+    A("// chain-back table: VT_BK[c][v] = bit position of the decision of a class-c step in its word, v = the six bits decoded")
+    A("// after it, newest at bit 5 (tools/gen_vit_t.py, chain_back)")
+    A("__device__ constexpr unsigned char VT_BK[6][64] = {")
+    for row in VT_BK:
+        A("  {%s}," % ", ".join(str(x) for x in row))
     A("};")
     A("")
     A("// M[i]: packed branch metrics (W[ql], W[qh]) of the step's four register-pair groups; W[q], q = c0*4 + c1*2 + c2, is")
@@ -414,26 +445,34 @@ def emit():
         # TIE: 0 = scalar body (decision = b < a, a tie keeps predecessor i); 1 = VITERBI_AVX2 (decision = NOT (a < b): a tie goes to
         # i + 32; the words are inverted at the end of the step); 2 = VITERBI_SSE2 (scalar tie rule).  CLAMP: every candidate is
         # limited to `lim` first = the saturating adds of the SIMD builds at the lane's current absolute level (vit_t.hip).
-        A("template <int TIE = 0, bool CLAMP = false>")
-        A("__device__ __forceinline__ void step%d(s2 (&R)[32], const s2 (&M)[4], unsigned &acc0, unsigned &acc1, s2 lim = s2{0, 0})" % c)
+        # RC (class 0, tie mode 0): the step also re-centres every metric on `ref` -- folded into its constants, t1 = R + (w - ref),
+        # t2 = R + (-w - ref), instead of one more v_pk_sub per register
+        A("template <int TIE = 0, bool CLAMP = false%s>" % (", bool RC = false" if c == 0 else ""))
+        A("__device__ __forceinline__ void step%d(s2 (&R)[32], const s2 (&M)[4], unsigned &acc0, unsigned &acc1, s2 lim = s2{0, 0}%s)"
+          % (c, ", s2 ref = s2{0, 0}" if c == 0 else ""))
         A("{")
         if c == 0:
             qs = [q for q, _ in order]
-            for i, q in enumerate(qs):
-                A("  const s2 M%d = M[%d];" % (q, i))
+            A("  s2 P[4], N[4];")
+            A("  if constexpr (RC) { const s2 nref = s2{0, 0} - ref; for (int i = 0; i < 4; i++) { P[i] = M[i] - ref; N[i] = nref - M[i]; } }")
             for j in range(16):
-                names = []
+                ys = []
                 for r in (2 * j, 2 * j + 1):
                     q = pl["regs"][r][1]
                     cq, flip = (q, False) if q < 4 else (7 - q, True)
+                    i = qs.index(cq)
                     # t1 = (a0, b1), t2 = (a1, b0): new = (min(a0, b0), min(b1, a1)), d0 = b0 - a0, d1 = b1 - a1
-                    A("  s2 t1_%d = R[%d] %s M%d, t2_%d = R[%d] %s M%d;" % (r, r, "-" if flip else "+", cq, r, r, "+" if flip else "-", cq))
+                    A("  s2 t1_%d, t2_%d;" % (r, r))
+                    A("  if constexpr (RC) { t1_%d = R[%d] + %s[%d]; t2_%d = R[%d] + %s[%d]; }" % (r, r, "N" if flip else "P", i, r, r, "P" if flip else "N", i))
+                    A("  else { t1_%d = R[%d] %s M[%d]; t2_%d = R[%d] %s M[%d]; }" % (r, r, "-" if flip else "+", i, r, r, "+" if flip else "-", i))
                     A("  if constexpr (CLAMP) { t1_%d = mn(t1_%d, lim); t2_%d = mn(t2_%d, lim); }" % (r, r, r, r))
                     A("  R[%d] = mn_x(t1_%d, t2_%d);" % (r, r, r))
-                    names.append((r, "sub_hl(t2_%d, t1_%d)" % (r, r), "sub_lh(t1_%d, t2_%d)" % (r, r)))
-                A("  if constexpr (TIE == 1) fold<%d>(acc%d, sg_even(%s, %s) | sg_odd(%s, %s));" %
-                  (j % 8, j // 8, names[0][2], names[0][1], names[1][2], names[1][1]))
-                A("  else fold<%d>(acc%d, sg_even(%s, %s) | sg_odd(%s, %s));" % (j % 8, j // 8, names[0][1], names[0][2], names[1][1], names[1][2]))
+                    ys.append(r)
+                # register 2j -> bytes (0, 1), 2j + 1 -> bytes (2, 3) of gather j (class_plan); tie 1 swaps the operands
+                A("  if constexpr (TIE == 1) fold<%d>(acc%d, sg(ydiff_t1(t1_%d, t2_%d), ydiff_t1(t1_%d, t2_%d)));" % (j % 8, j // 8, ys[1], ys[1], ys[0], ys[0]))
+                A("  else fold<%d>(acc%d, sg(ydiff(t2_%d, t1_%d), ydiff(t2_%d, t1_%d)));" % (j % 8, j // 8, ys[1], ys[1], ys[0], ys[0]))
+            A("  if constexpr (TIE == 1) { acc0 ^= ~C0_INV; acc1 ^= ~C0_INV; }")
+            A("  else { acc0 ^= C0_INV; acc1 ^= C0_INV; }")
         else:
             for (ql, qh), idx in combos.items():
                 A("  const s2 M%d = M[%d];" % (idx, idx))
@@ -447,7 +486,7 @@ def emit():
                 A("    if constexpr (CLAMP) { a0 = mn(a0, lim); b0 = mn(b0, lim); a1 = mn(a1, lim); b1 = mn(b1, lim); }")
                 A("    R[%d] = mn(a0, b0); R[%d] = mn(a1, b1);" % (ra, rb))
                 A("    if constexpr (TIE == 1) fold<%d>(acc%d, sg(a0 - b0, a1 - b1)); else fold<%d>(acc%d, sg(b0 - a0, b1 - a1)); }" % (k % 8, k // 8, k % 8, k // 8))
-        A("  if constexpr (TIE == 1) { acc0 = ~acc0; acc1 = ~acc1; }")
+            A("  if constexpr (TIE == 1) { acc0 = ~acc0; acc1 = ~acc1; }")
         A("}")
         A("")
     A("}}  // namespace dabx::vt")
