@@ -167,9 +167,6 @@ int launch_deliver_front(const EngineDev &e, const DeliverDev &dv, hipStream_t s
 int launch_deliver_msc(const EngineDev &e, const DeliverDev &dv, hipStream_t st, bool with_lf)
 {
   if (e.max_subch <= 0) return 0;
-#ifdef DABX_DELIVER_NOPACK             // experiment builds only: what the copy alone costs (the slot table then says "nothing")
-  return 0;
-#endif
   hipLaunchKernelGGL(k_deliver_msc, dim3(e.n_streams * e.max_subch), dim3(64), 0, st, e, dv, with_lf ? 1 : 0);
   DABX_HIP(hipGetLastError());
   return 0;
@@ -178,9 +175,7 @@ int launch_deliver_msc(const EngineDev &e, const DeliverDev &dv, hipStream_t st,
 int launch_deliver_lf(const EngineDev &e, const DeliverDev &dv, hipStream_t st)
 {
   if (e.max_subch <= 0 || !dv.lf_done) return 0;
-#ifndef DABX_DELIVER_NOPACK
   hipLaunchKernelGGL(k_deliver_lf, dim3(e.n_streams * e.max_subch), dim3(64), 0, st, e, dv);
-#endif
   DABX_HIP(hipEventRecord(dv.lf_done, st));
   DABX_HIP(hipGetLastError());
   return 0;

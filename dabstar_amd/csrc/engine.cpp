@@ -3,9 +3,6 @@
 #include "viterbi_core.h"
 #include "sdma.h"
 #include "iqfile.h"
-#ifndef DABX_CU_SPLIT_DEMAP_FRONT
-#define DABX_CU_SPLIT_DEMAP_FRONT 0
-#endif
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
@@ -469,18 +466,15 @@ static void delivery_copier(Delivery *Dp)
     size_t head_bytes = sl.bytes;
     bool lf_started = false;
     auto t_lf = t_a;
-#ifndef DABX_DELIVER_NOCOPY
     if (sl.lf_from) {
       while ((he = hipEventQuery(D.packed_lf[sl.devslab])) == hipErrorNotReady) std::this_thread::sleep_for(std::chrono::microseconds(50));
       if (he != hipSuccess) err = std::string("hipEventQuery: ") + hipGetErrorString(he);
       else if (sdma_copy(D.sdma, sl.host + sl.lf_from, D.dev[sl.devslab] + sl.lf_from, sl.bytes - sl.lf_from, true, sl.sig2)) err = dabx::last_error();
       else { lf_started = true; head_bytes = sl.lf_from; t_lf = std::chrono::steady_clock::now(); }
     }
-#endif
     while ((he = hipEventQuery(D.packed[sl.devslab])) == hipErrorNotReady) std::this_thread::sleep_for(std::chrono::microseconds(50));
     if (he != hipSuccess && err.empty()) err = std::string("hipEventQuery: ") + hipGetErrorString(he);
     const auto t_b = std::chrono::steady_clock::now();
-#ifndef DABX_DELIVER_NOCOPY            // experiment builds only (tools/build_variant.sh): what the gather kernels alone cost
     if (err.empty()) {
       if (D.copy_engine == 0) {
         if (sdma_copy(D.sdma, sl.host, D.dev[sl.devslab], head_bytes, true, sl.sig) || sdma_wait(sl.sig, head_bytes)) err = dabx::last_error();
@@ -491,7 +485,6 @@ static void delivery_copier(Delivery *Dp)
         if (he != hipSuccess) err = std::string("hipMemcpyAsync: ") + hipGetErrorString(he);
       }
     }
-#endif
     const auto t_c = std::chrono::steady_clock::now();
     std::lock_guard<std::mutex> lk(D.mu);
     {
@@ -609,31 +602,14 @@ int dabx_create(const dabx_config *cfg, dabx_engine **out)
   // front end (frame-to-frame feedback = critical path) above the batched MSC decode
   int prio_lo = 0, prio_hi = 0;
   (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);       // lo = least urgent (numerically greatest)
-#ifdef DABX_CU_SPLIT
-  // Experiment builds only (tools/build_variant.sh -DDABX_CU_SPLIT=n; docs/history/r01-r04_design_notebook.md 6 "spatial partitioning"): the front-end stream gets
-  // n of the 256 CUs, the decoder and the MSC symbols' demapper the other 256 - n.  The KFD deals the bits of a queue's CU mask
-  // round-robin to the 8 XCDs, so the first n bits are n / 8 CUs on every XCD.
-  uint32_t mask_front[8], mask_back[8];
-  for (int w = 0; w < 8; w++) {
-    mask_front[w] = mask_back[w] = 0;
-    for (int b = 0; b < 32; b++) { if (32 * w + b < DABX_CU_SPLIT) mask_front[w] |= 1u << b; else mask_back[w] |= 1u << b; }
-  }
-  H(hipExtStreamCreateWithCUMask(&e->stream, 8, mask_front));
-#else
   H(hipStreamCreateWithPriority(&e->stream, hipStreamNonBlocking, prio_hi));
-#endif
   e->ss.a = e->stream;
   if (cfg->schedule == 0) {
     // overlapped schedule (default): MSC batches on b, the MSC symbols' demapper on d (pipeline.hip, launch_front_step /
     // launch_msc_batch).  All streams live on this device: a device-scope release is all a dependency needs (the default
     // system-scope release writes the caches back for host visibility on every record)
-#ifdef DABX_CU_SPLIT
-    H(hipExtStreamCreateWithCUMask(&e->ss.b, 8, mask_back));
-    H(hipExtStreamCreateWithCUMask(&e->ss.d, 8, DABX_CU_SPLIT_DEMAP_FRONT ? mask_front : mask_back));
-#else
     H(hipStreamCreateWithPriority(&e->ss.b, hipStreamNonBlocking, prio_lo));
     H(hipStreamCreateWithPriority(&e->ss.d, hipStreamNonBlocking, prio_hi));
-#endif
     H(hipEventCreateWithFlags(&e->ss.prep_done, hipEventDisableTiming | hipEventReleaseToDevice));
     H(hipEventCreateWithFlags(&e->ss.msc_done, hipEventDisableTiming | hipEventReleaseToDevice));
     H(hipEventCreateWithFlags(&e->ss.fic_go, hipEventDisableTiming | hipEventReleaseToDevice));
@@ -641,13 +617,10 @@ int dabx_create(const dabx_config *cfg, dabx_engine **out)
     H(hipEventCreateWithFlags(&e->ss.demap_done, hipEventDisableTiming | hipEventReleaseToDevice));
     H(hipEventCreateWithFlags(&e->ss.sym_done, hipEventDisableTiming | hipEventReleaseToDevice));
     // few streams: the demapper of a frame on stream d in one launch, hand-overs by device-side sequence numbers (pipeline.h, fic_on_d /
-    // EngineDev::flag_sync).  The threshold is k_symbols' own (sym_blocks_per_stream: below 48 streams a frame's symbols are spread over more
-    // blocks because latency, not throughput, is what is left) -- and the bound under which every block of the kernels that wait for each other
-    // is resident at once.  (A/B builds: tools/build_variant.sh -DDABX_FEW_STREAMS=n.)
-#ifndef DABX_FEW_STREAMS
-#define DABX_FEW_STREAMS 48
-#endif
-    e->ss.fic_on_d = cfg->n_streams < DABX_FEW_STREAMS;
+    // EngineDev::flag_sync).  The threshold is k_symbols' own (FEW_STREAMS, sym_blocks_per_stream: below it a frame's symbols are spread over
+    // more blocks because latency, not throughput, is what is left) -- and the bound under which every block of the kernels that wait for each
+    // other is resident at once.
+    e->ss.fic_on_d = cfg->n_streams < FEW_STREAMS;
     // the ingest stream BEFORE q: the runtime deals streams to its hardware queues in order of creation, and as the fifth stream the
     // ingest stream shared one (every synchronous push 20 us = 20 % dearer at 512 streams, tools/bench_ingest.py)
     H(hipStreamCreateWithFlags(&e->ingest, hipStreamNonBlocking));

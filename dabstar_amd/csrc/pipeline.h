@@ -4,21 +4,12 @@
 
 namespace dabx {
 
-// Cache hints of the streaming accesses: a set bit makes the access __builtin_nontemporal_load / _store (the `nt` modifier: the line is not kept
-// in L2 beyond its use).  The defaults are the measured ones (same-box A/B over three sessions, profiles/r05_ab/ab10_nontemporal_hints.txt:
-// +1.9 % together); the other bits stay selectable for A/B builds (tools/build_variant.sh -DDABX_VIT_NT=0 ...).
-#ifndef DABX_VIT_NT
-#define DABX_VIT_NT 3      // k_msc_vitT: 1 = survivor-decision stores, 2 = their chain-back loads (3.6 + 3.2 GB per launch, each touched once: +1.1 %);
-#endif                     //             4 = the transposed input (slower: a dword row is read up to four times in a row)
-#ifndef DABX_SYM_NT
-#define DABX_SYM_NT 2      // k_symbols: 2 = spectra stores (read next by the demapper, 478 MB later); 1 = IQ loads (slower: the cyclic prefix is read twice)
-#endif
-#ifndef DABX_DEMAP_NT
-#define DABX_DEMAP_NT 1    // demapper: 1 = spectra loads; 2 = ring stores (no effect)
-#endif
-#ifndef DABX_PREP_NT
-#define DABX_PREP_NT 0     // k_msc_prep: 1 = ring reads (-2.4 %: 64-byte runs, the other half of the line follows), 2 = transposed stores (-0.8 %)
-#endif
+// Cache hints: two streams whose every byte is written once and read once bypass the caches (__builtin_nontemporal_load / _store, the `nt`
+// modifier: the line is not kept in L2 beyond its use): k_msc_vitT's survivor decisions (3.6 GB stored and 3.2 GB loaded back per launch:
+// +1.1 %) and the spectra, stored by k_symbols and loaded by the demapper after 478 MB of other writes: +1.9 % together
+// (profiles/r05_ab/ab10_nontemporal_hints.txt).  The hint measured slower on k_msc_vitT's transposed input (a dword row is read up to four
+// times in a row), k_symbols' IQ loads (the cyclic prefix is read twice) and k_msc_prep's ring reads and transposed stores, and made no
+// difference to the demapper's ring stores.
 #ifndef DABX_MSC_BATCH               // experiment builds only (tools/build_variant.sh -DDABX_MSC_BATCH=n, bench.py --chunk n)
 #define DABX_MSC_BATCH 7
 #endif
@@ -28,6 +19,7 @@ constexpr int MSC_BATCH_FRAMES = DABX_MSC_BATCH; // frames whose MSC CIFs are de
 constexpr int SF_SLOTS = 16;      // ring of RS-corrected super frames per sub-channel: two chunks' worth (a 7-frame MSC batch completes up to 6)
 constexpr int ACQ_NEED = 20 * TU + 50 + (TF + 1) + (TN + 50 + 21) + 64;   // worst-case samples one acquisition pass may read
 constexpr int FRAME_NEED = TF + 2 * TU;                                    // worst-case samples one in-lock frame may read
+constexpr int FEW_STREAMS = 48;   // below this many streams: k_symbols' latency shape (pipeline.hip, sym_blocks_per_stream), the few-stream schedule (EngineStreams::fic_on_d)
 
 enum StreamState : int32_t { ST_INIT = 0, ST_WAIT_SYNC = 1, ST_EVAL_SYNC = 2 };
 
@@ -138,8 +130,7 @@ struct EngineDev {
   float *dciq_state;              // [S][8] meanI, meanQ, meanII, meanQQ, meanIQ of SampleReader's DC / IQ correction (sample_reader.h:102-106)
   unsigned long long *dciq_done;  // [S] absolute index of the first sample not yet corrected
   int32_t parity;                 // step parity (host sets it per launch)
-  int32_t s0;                     // first stream of a launch that covers a GROUP of streams (k_symbols and the demapper; experiment builds with
-                                  // -DDABX_GROUPS=n issue them per group so that a group's spectra stay in the 256-MB Infinity Cache; 0 otherwise)
+  int32_t s0;                     // first stream of the k_symbols and demapper launches: 0, each launch covers every stream
   // Few streams (EngineStreams::fic_on_d): the two hand-overs between the frame chain (HIP stream a) and the demapper (d) are DEVICE-side
   // sequence numbers instead of HIP events -- an event record or wait between two kernels of a HIP stream is a 6-17 us bubble in that stream
   // (profiles/r06_single_ensemble_timeline_after.txt), and the demapper's loop is what a lone ensemble's frame rate is.  k_sym_publish (stream a,

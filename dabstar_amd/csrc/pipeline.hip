@@ -352,22 +352,11 @@ __device__ __forceinline__ int acquire_stream(EngineDev &e, int s, int tid, int 
   int n2 = 0;                            // attempt-relative index at which the dip began
   float L = 0.f, pk = 0.f;
   int margin = 0;                        // comparisons within 1e-4 of their threshold
-#ifdef DABX_ACQ_TIMING                   // experiment builds only (tools/build_variant.sh): where a block's time goes, per wave role
-  long long tm[6] = {0, 0, 0, 0, 0, 0}, t_loop = clock64();
-#define ACQ_T0 const long long t0_ = clock64();
-#define ACQ_T(k) tm[k] += clock64() - t0_;
-#else
-#define ACQ_T0
-#define ACQ_T(k)
-#endif
-  int i = 0;
-  for (;; i++) {
+  for (int i = 0;; i++) {
     if (wave == 0) {
       // the block's 64 groups of 16 samples in parallel, one per lane (level_par.h): Sc[g] = sLevel before group g, bit for bit what
       // the sample-serial walk gives (round 4 began with that walk here: 17.6 cycles per sample, 20 000 per block, the pace of the search)
-      ACQ_T0
       S = lp.block(w.a[i % 3] + 64, ACQ_CH / 16, S, w.Sc[i & 1], lane);
-      ACQ_T(0)
     } else if (wave == 1) {
       if (i > 0) {
         const int jb = i - 1;
@@ -397,20 +386,15 @@ __device__ __forceinline__ int acquire_stream(EngineDev &e, int s, int tid, int 
             // zero increments up to q (what it writes there belongs to positions already evaluated)
             const int q16 = q & ~15, g0 = q16 >> 4;
             float *db = w.d[jb & 1];
-            { ACQ_T0
             if (nb < 50 || q16 < q)                                          // the attempt's first 50 samples: level += |x| (:64-66)
               for (int p = q16 + lane; p < q16 + 128; p += 64) {
                 if (p < q) db[p] = 0.f;
                 else if (p < q + m && nb + (p - q) < 50) db[p] = rb[p];
               }
-            ACQ_T(1) }
-            { ACQ_T0
             __builtin_amdgcn_wave_barrier();
             // level before sample q16 (= before q: zero increments in between) -> w.Lc[g0], then checkpoint by checkpoint
             level_sum_block(db + q16, __builtin_amdgcn_readfirstlane((q + m - q16 + 15) >> 4), L, w.Lc + g0, lane);
             __builtin_amdgcn_wave_barrier();
-            ACQ_T(2) }
-            ACQ_T0
             // Lane t owns samples 16 t .. 16 t + 15: from the two checkpoints in front of its group it re-walks both recurrences in
             // registers and evaluates, BEFORE each sample, the two comparisons of timesyncer.cpp:58, 74 -- 16 bits per lane each
             unsigned bm = 0, em = 0, nbm = 0, nem = 0;                       // dip begins / ends here; the comparison came within 1e-4 of its threshold
@@ -473,7 +457,6 @@ __device__ __forceinline__ int acquire_stream(EngineDev &e, int s, int tid, int 
               margin += wave_sum_int(__builtin_popcount(nbq) + __builtin_popcount(ne));
               if (p3 >= 0) { lim = p3 - q; ok = 1; stop = 1; }
             } else margin += wave_sum_int(__builtin_popcount(nbm));
-            ACQ_T(3)
             L = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, L_end), p_last >> 4));   // level after the segment's last sample
           }
           q += lim;
@@ -492,10 +475,8 @@ __device__ __forceinline__ int acquire_stream(EngineDev &e, int s, int tid, int 
           }
         }
         // sample_reader.cpp:247: peakLevel over the samples consumed -- the whole block's maximum, or its first q samples at the end
-        { ACQ_T0
         if (!stop) pk = fmaxf(pk, lane < 4 ? w.bmax[jb % 3][lane] : 0.f);
         else for (int p = lane; p < q; p += 64) pk = fmaxf(pk, ab[p]);
-        ACQ_T(4) }
         if (stop) {
           const float pkw = __builtin_bit_cast(float, wave_butterfly_u32(__builtin_bit_cast(unsigned, pk), [](unsigned x, unsigned y) { return x > y ? x : y; }));
           const float s_fin = s_before(q);
@@ -503,20 +484,13 @@ __device__ __forceinline__ int acquire_stream(EngineDev &e, int s, int tid, int 
         }
       }
     } else {
-      ACQ_T0
       publish(i + 1);                                      // requested a block ago
       request(i + 2);
       if (i > 0) incs(i, tid - 128, T - 128);             // block i's magnitudes are complete since the last barrier
-      ACQ_T(5)
     }
     __syncthreads();
     if (w.done) break;
   }
-#ifdef DABX_ACQ_TIMING
-  if (s == 0 && lane == 0 && wave < 3)
-    printf("acq wave %d: %d blocks, %lld cycles in all; S walk %lld, increments %lld, level walk %lld, comparisons %lld, peak %lld, magnitudes %lld (cycles per block)\n",
-           wave, i + 1, clock64() - t_loop, tm[0] / (i + 1), tm[1] / (i + 1), tm[2] / (i + 1), tm[3] / (i + 1), tm[4] / (i + 1), tm[5] / (i + 1));
-#endif
   if (tid == 0) {
     c.rd = rd0 + w.consumed;           // frequency offset is 0 while searching: NCO phase unchanged
     c.s_level = w.s_final; c.peak_level = fmaxf(c.peak_level, w.pk);
@@ -752,10 +726,8 @@ __global__ __launch_bounds__(256, 2) void k_acquire(EngineDev e, DevTables t, in
 }
 
 // --------------------------------------------------------------------------------------------- frame head
-#ifndef DABX_HEAD_OCC
-#define DABX_HEAD_OCC 3      // 166 VGPRs, no scratch
-#endif
-__global__ __launch_bounds__(256, DABX_HEAD_OCC) void k_frame_head(EngineDev e, DevTables t)
+// 3 waves per SIMD: 166 VGPRs, no scratch
+__global__ __launch_bounds__(256, 3) void k_frame_head(EngineDev e, DevTables t)
 {
   front_prio();
   __shared__ float2 lds[FFT_LDS_FLOAT2];
@@ -868,10 +840,7 @@ __global__ __launch_bounds__(256, DABX_HEAD_OCC) void k_frame_head(EngineDev e, 
 // blocks per stream (a divisor of 75): 15 blocks of 5 symbols each fill the chip from ~50 streams up (3 resident per CU); with
 // fewer streams the symbols of a frame are spread over more blocks so that the kernel's latency, not its throughput, shrinks
 // (one stream: 75 blocks of one symbol -- the single-ensemble configurations are latency-bound on the frame's serial chain)
-#ifndef DABX_SYM_G
-#define DABX_SYM_G 15
-#endif
-__host__ __device__ constexpr int sym_blocks_per_stream(int n_streams) { return n_streams >= 48 ? DABX_SYM_G : (n_streams >= 16 ? 25 : 75); }
+__host__ __device__ constexpr int sym_blocks_per_stream(int n_streams) { return n_streams >= FEW_STREAMS ? 15 : (n_streams >= 16 ? 25 : 75); }
 // 3 waves per SIMD: 170 VGPRs without spills (bounded to 4 it spills 8 registers and runs 25 % slower)
 __global__ __launch_bounds__(256, 3) void k_symbols_persistent(EngineDev e, DevTables t)
 {
@@ -889,12 +858,7 @@ __global__ __launch_bounds__(256, 3) void k_symbols_persistent(EngineDev e, DevT
   const bool two = tid + 256 < TG;
   float2 nx[12];
   auto request = [&](int o) {
-#if DABX_SYM_NT & 1          // (A/B builds: the samples past the caches, pipeline.h)
-    typedef float sym_f2 __attribute__((ext_vector_type(2)));
-    auto at = [&](unsigned i) { unsigned a = (unsigned)o + i; if (a >= len) a -= len; const sym_f2 q = __builtin_nontemporal_load(reinterpret_cast<const sym_f2 *>(ring + a)); return make_float2(q.x, q.y); };
-#else
     auto at = [&](unsigned i) { unsigned a = (unsigned)o + i; if (a >= len) a -= len; return ring[a]; };
-#endif
     nx[0] = at(tid); nx[1] = at(TU + tid);
     nx[2] = at(two ? tid + 256 : tid); nx[3] = at(two ? TU + tid + 256 : TU + tid);
 #pragma unroll
@@ -957,30 +921,14 @@ __global__ __launch_bounds__(256, 3) void k_symbols_persistent(EngineDev e, DevT
     }
     __syncthreads();
     float2 *dst = e.spectra + (((size_t)e.parity * e.n_streams + s) * 75 + l) * K;
-#ifdef DABX_SYM_ST_AUX       // experiment builds: the spectra through raw-buffer stores with the cache-policy bits of choice (16 = sc1: write-through)
-    {
-      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(dst, 0, K * 8, 0x00020000);
-      typedef float sym_f2b __attribute__((ext_vector_type(2)));
+    // the spectra, read next by the demapper after 478 MB more have been written: past the caches (pipeline.h)
 #pragma unroll
-      for (int u = 0; u < K / 256; u++) {
-        const float2 q = lds[((tid + 256 * u) & ~15) | ((rd_lo >> (4 * u)) & 15u)];
-        sym_f2b qv; qv.x = q.x; qv.y = q.y;
-        __builtin_amdgcn_raw_buffer_store_b64(qv, rs, (tid + 256 * u) * 8, 0, DABX_SYM_ST_AUX);
-      }
-    }
-#else
-#pragma unroll
-#if DABX_SYM_NT & 2          // the spectra, read next by the demapper after 478 MB more have been written: past the caches (pipeline.h)
     for (int u = 0; u < K / 256; u++) {
       typedef float sym_f2 __attribute__((ext_vector_type(2)));
       const float2 q = lds[((tid + 256 * u) & ~15) | ((rd_lo >> (4 * u)) & 15u)];
       sym_f2 qv; qv.x = q.x; qv.y = q.y;
       __builtin_nontemporal_store(qv, reinterpret_cast<sym_f2 *>(dst + tid + 256 * u));
     }
-#else
-    for (int u = 0; u < K / 256; u++) dst[tid + 256 * u] = lds[((tid + 256 * u) & ~15) | ((rd_lo >> (4 * u)) & 15u)];
-#endif
-#endif
     if (l_next >= 75) break;
     l = l_next;
     __syncthreads();                                          // the exchange buffer and red3 are free again
@@ -1024,31 +972,15 @@ __global__ void k_sym_publish(EngineDev e)
 }
 
 // -------------------------------------------------------------------------------------------------- demap
-#ifndef DABX_DEMAP_Q                 // experiment builds (tools/build_variant.sh -DDABX_DEMAP_Q=4 -DDABX_DEMAP_OCC=3): carriers per thread
-#define DABX_DEMAP_Q 2
-#define DABX_DEMAP_OCC 6
-#endif
-constexpr int DEMAP_Q = DABX_DEMAP_Q, DEMAP_THREADS = K / DEMAP_Q, DEMAP_NP = DEMAP_Q / 2;   // carriers per thread (in pairs); 12 waves per stream
+constexpr int DEMAP_Q = 2, DEMAP_THREADS = K / DEMAP_Q, DEMAP_NP = DEMAP_Q / 2;   // carriers per thread (in pairs); 12 waves per stream
 constexpr int DEMAP_NOUT = (K2 / 4) / DEMAP_THREADS;              // output dwords per thread and symbol
 constexpr int TILE_PLANE = 196;                                   // LDS bytes per plane of the output tile (192 used)
-// cache hints of the demapper's streams (pipeline.h, DABX_DEMAP_NT): 1 = the spectra, read once, past the caches; 2 = the ring stores
+// the spectra, read once: past the caches (pipeline.h)
 __device__ __forceinline__ float2 demap_ld_spec(const float2 *p)
 {
-#if DABX_DEMAP_NT & 1
   typedef float dm_f2 __attribute__((ext_vector_type(2)));
   const dm_f2 q = __builtin_nontemporal_load(reinterpret_cast<const dm_f2 *>(p));
   return make_float2(q.x, q.y);
-#else
-  return *p;
-#endif
-}
-__device__ __forceinline__ void demap_st_ring(uint32_t *p, uint32_t v)
-{
-#if DABX_DEMAP_NT & 2
-  __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
 }
 // ESoftBitType 1..3 and the symbol conversion (SAT: the SIMD builds' saturating one, cfg.viterbi_tie_mode != 0) as compile-time
 // constants: no per-carrier branches on either
@@ -1198,7 +1130,7 @@ __device__ __forceinline__ void demap_frame_body(EngineDev &e, const DevTables &
         static_assert(K2 % 16 == 0, "a symbol is a whole number of positions in every plane");
         uint8_t *const tdi_thr = tdi + (size_t)out_plane * (CIF_BITS / 16) + 4 * out_dw;
         const size_t uoff = (size_t)((cif0 + cif) & (TDI_SLOTS - 1)) * CIF_BITS + (size_t)blk * (K2 / 16);
-        demap_st_ring(reinterpret_cast<uint32_t *>(tdi_thr + uoff), v);
+        *reinterpret_cast<uint32_t *>(tdi_thr + uoff) = v;
       }
     }
   };
@@ -1261,7 +1193,7 @@ __device__ __forceinline__ void demap_frame_body(EngineDev &e, const DevTables &
 // Built for six waves per SIMD (<= 80 VGPRs, 7 values spilled outside the loop): two 12-wave blocks share a CU instead of
 // taking turns (at 94 VGPRs only one fitted: 0.32 -> 0.24 ms per step).
 template <int SOFT_TYPE, bool SAT, bool MER>
-__global__ __launch_bounds__(DEMAP_THREADS, DABX_DEMAP_OCC) void k_demap_frame6(EngineDev e, DevTables t, int l0, int l1) { demap_frame_body<SOFT_TYPE, SAT, false, MER>(e, t, l0, l1); }
+__global__ __launch_bounds__(DEMAP_THREADS, 6) void k_demap_frame6(EngineDev e, DevTables t, int l0, int l1) { demap_frame_body<SOFT_TYPE, SAT, false, MER>(e, t, l0, l1); }
 // the FIC symbols alone (first launch of a frame in the overlapped schedule): its own kernel symbol so that rocprofv3's
 // per-kernel statistics keep the 3-symbol and the 72-symbol launches apart, as bench.py's event pairs do
 template <int SOFT_TYPE, bool SAT, bool MER>
@@ -1988,13 +1920,7 @@ int launch_front_step(const EngineDev &e_in, EngineStreams &ss, Marker &mk, bool
     if (ss.q && ss.acq_a_done) { DABX_HIP(hipEventRecord(ss.acq_a_done, st)); ss.acq_a_pending = true; }
   }
   mk.begin(1, st); hipLaunchKernelGGL(k_frame_head, dim3(e.n_streams), dim3(256), 0, st, e, *t); mk.end(1, st);
-#ifndef DABX_GROUPS
-#define DABX_GROUPS 1
-#endif
-  // Experiment builds (-DDABX_GROUPS=n): k_symbols -> k_demap_fic -> k_demap_frame6 issued per group of n_streams / n streams,
-  // back to back, all streams resident: does a group's spectra (128 streams = 118 MB) survive in the Infinity Cache between its writer and its reader?
-  const bool grouped = DABX_GROUPS > 1 && ss.d && !ss.fic_on_d && e.n_streams % DABX_GROUPS == 0 && e.n_streams / DABX_GROUPS >= 48;
-  if (!grouped) { mk.begin(2, st); hipLaunchKernelGGL(k_symbols_persistent, dim3(sym_blocks_per_stream(e.n_streams), e.n_streams), dim3(256), 0, st, e, *t); mk.end(2, st); }
+  mk.begin(2, st); hipLaunchKernelGGL(k_symbols_persistent, dim3(sym_blocks_per_stream(e.n_streams), e.n_streams), dim3(256), 0, st, e, *t); mk.end(2, st);
   // kernel instance by (ESoftBitType, symbol conversion of the canonical / SIMD builds)
 #define DABX_DEMAP_DISPATCH(KERNEL, ...)                                                                                         \
   do {                                                                                                                          \
@@ -2034,28 +1960,6 @@ int launch_front_step(const EngineDev &e_in, EngineStreams &ss, Marker &mk, bool
     // (demap_done is recorded when somebody needs it -- the MSC batch, once per 7 frames: every packet between two kernels of a HIP stream is a
     //  bubble of 6-12 us on this loop, profiles/r06_single_ensemble_timeline_after.txt)
     ss.demap_in_flight = true; ss.demap_unrecorded = true;
-#if DABX_GROUPS > 1          // experiment builds only (profiles/r06_ab/ab7_grouped_issue_negative.txt)
-  } else if (grouped) {
-    static hipEvent_t ev[16] = {nullptr};      // (one engine per process in the A/B runs)
-    const int sg = e.n_streams / DABX_GROUPS;
-    for (int g = 0; g < DABX_GROUPS; g++) {
-      EngineDev eg = e;
-      eg.s0 = g * sg;
-      if (!ev[g]) DABX_HIP(hipEventCreateWithFlags(&ev[g], hipEventDisableTiming | hipEventReleaseToDevice));
-      mk.begin(2, st); hipLaunchKernelGGL(k_symbols_persistent, dim3(sym_blocks_per_stream(e.n_streams), sg), dim3(256), 0, st, eg, *t); mk.end(2, st);
-      if (g == 0 && ss.demap_in_flight) { DABX_HIP(hipStreamWaitEvent(st, ss.demap_done, 0)); ss.demap_in_flight = false; }
-      mk.begin(10, st);
-      DABX_DEMAP_DISPATCH(k_demap_fic, dim3(sg), dim3(DEMAP_THREADS), 0, st, eg, *t);
-      mk.end(10, st);
-      DABX_HIP(hipEventRecord(ev[g], st));
-      DABX_HIP(hipStreamWaitEvent(ss.d, ev[g], 0));
-      mk.begin(3, ss.d);
-      DABX_DEMAP_DISPATCH(k_demap_frame6, dim3(sg), dim3(DEMAP_THREADS), 0, ss.d, eg, *t, 3, 75);
-      mk.end(3, ss.d);
-    }
-    DABX_HIP(hipEventRecord(ss.demap_done, ss.d));
-    ss.demap_in_flight = true;
-#endif
   } else if (ss.d) {
     if (ss.demap_in_flight) { DABX_HIP(hipStreamWaitEvent(st, ss.demap_done, 0)); ss.demap_in_flight = false; }
     mk.begin(10, st);
@@ -2126,16 +2030,16 @@ int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineSt
         fast_pairs += k.n_pairs;
       }
   }
+  // Overlapped schedule: the batch's decode and DAB+ stage run on stream b while the front end (a) goes straight on to the next
+  // frames.  Serial schedule (ss.b null): the same kernels on a.
+  hipStream_t sb = ss.b ? ss.b : ss.a;
+  if (ss.b) {
+    DABX_HIP(hipEventRecord(ss.prep_done, ss.a));
+    DABX_HIP(hipStreamWaitEvent(ss.b, ss.prep_done, 0));
+  }
   if (L.n > 0) {
-    // Overlapped schedule: time de-interleave, lane-per-trellis decode and DAB+ stage of the batch run on stream b while the
-    // front end (a) goes straight on to the next frames.  k_msc_prep reads ring slots the front end only rewrites 20 CIFs
-    // (5 frames) later; dabx_process makes the front-end stream wait for `prep_b_done` before it gets there.  Serial
-    // schedule (ss.b null): the same kernels on a.
-    hipStream_t sb = ss.b ? ss.b : ss.a;
-    if (ss.b) {
-      DABX_HIP(hipEventRecord(ss.prep_done, ss.a));
-      DABX_HIP(hipStreamWaitEvent(ss.b, ss.prep_done, 0));
-    }
+    // time de-interleave + lane-per-trellis decode.  k_msc_prep reads ring slots the front end only rewrites 20 CIFs (5 frames)
+    // later; dabx_process makes the front-end stream wait for `prep_b_done` before it gets there.
     if (fast_pairs < fast->slots_active && (rc = wait_for_demapper(ss.a))) return rc;   // the wave-per-trellis leftovers below read the ring on a
     if ((rc = wait_for_demapper(sb))) return rc;
     if ((rc = launch_msc_prep(e, cifs, L, sb, mk))) return rc;
@@ -2154,31 +2058,10 @@ int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineSt
         DABX_HIP(hipStreamWaitEvent(ss.b, ss.prep_done, 0));
       }
     }
-    // the chunk's logical frames exist: into the slab with them, their share of the transfer starts while the DAB+ stage runs (deliver.hip)
-    if (dv && (rc = launch_deliver_lf(e, *dv, sb))) return rc;
-    mk.begin(9, sb);
-    hipLaunchKernelGGL(k_dabplus, dim3(e.n_streams * e.max_subch), dim3(64), 0, sb, e, *t);
-    hipLaunchKernelGGL(k_msc_done, dim3((e.n_streams + 255) / 256), dim3(256), 0, sb, e);
-    mk.end(9, sb);
-    if (dv && (rc = launch_deliver_msc(e, *dv, sb, !dv->lf_done))) return rc;
-    if (tail) *tail = sb;
-    if (ss.b) {
-      DABX_HIP(hipEventRecord(ss.msc_done, ss.b));
-      ss.msc_in_flight = true;
-#ifdef DABX_EXCLUSIVE_MSC            // experiment builds only: the next frames' front end waits for the batch (no overlap of the decoder with the frame chain)
-      DABX_HIP(hipStreamWaitEvent(ss.a, ss.msc_done, 0));
-      ss.msc_in_flight = false;
-#endif
-    }
   } else {
     // small batches (few streams / small profile classes only): the wave-per-trellis decoder.  With the overlapped schedule on stream b as
     // well (round 6): for ONE ensemble its 0.1 ms + the DAB+ stage's 0.05 ms per 7-frame batch stood on the frame chain (23 us per frame of
     // configs[2]'s 157).  It reads the time-de-interleaver ring in place: prep_b_done says when the front end may rewrite those slots.
-    hipStream_t sb = ss.b ? ss.b : ss.a;
-    if (ss.b) {
-      DABX_HIP(hipEventRecord(ss.prep_done, ss.a));
-      DABX_HIP(hipStreamWaitEvent(ss.b, ss.prep_done, 0));
-    }
     if ((rc = wait_for_demapper(sb))) return rc;
     mk.begin(8, sb);
     hipLaunchKernelGGL(k_msc_frame, dim3((jobs + 3) / 4), dim3(256), 0, sb, e, *t, cifs, 0u);
@@ -2187,17 +2070,18 @@ int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineSt
       DABX_HIP(hipEventRecord(ss.prep_b_done, ss.b));
       ss.prep_pending = true;
     }
-    if (dv && (rc = launch_deliver_lf(e, *dv, sb))) return rc;
-    mk.begin(9, sb);
-    hipLaunchKernelGGL(k_dabplus, dim3(e.n_streams * e.max_subch), dim3(64), 0, sb, e, *t);
-    hipLaunchKernelGGL(k_msc_done, dim3((e.n_streams + 255) / 256), dim3(256), 0, sb, e);
-    mk.end(9, sb);
-    if (dv && (rc = launch_deliver_msc(e, *dv, sb, !dv->lf_done))) return rc;
-    if (tail) *tail = sb;
-    if (ss.b) {
-      DABX_HIP(hipEventRecord(ss.msc_done, ss.b));
-      ss.msc_in_flight = true;
-    }
+  }
+  // the chunk's logical frames exist: into the slab with them, their share of the transfer starts while the DAB+ stage runs (deliver.hip)
+  if (dv && (rc = launch_deliver_lf(e, *dv, sb))) return rc;
+  mk.begin(9, sb);
+  hipLaunchKernelGGL(k_dabplus, dim3(e.n_streams * e.max_subch), dim3(64), 0, sb, e, *t);
+  hipLaunchKernelGGL(k_msc_done, dim3((e.n_streams + 255) / 256), dim3(256), 0, sb, e);
+  mk.end(9, sb);
+  if (dv && (rc = launch_deliver_msc(e, *dv, sb, !dv->lf_done))) return rc;
+  if (tail) *tail = sb;
+  if (ss.b) {
+    DABX_HIP(hipEventRecord(ss.msc_done, ss.b));
+    ss.msc_in_flight = true;
   }
   ss.batch_parity ^= 1;
   DABX_HIP(hipGetLastError());

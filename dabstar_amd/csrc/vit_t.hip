@@ -37,23 +37,6 @@ __device__ __forceinline__ int msc_class_of_group(const MscLaunch &L, int g)
   return c;
 }
 
-// cache hints of k_msc_prep's streams (pipeline.h, DABX_PREP_NT; both off: measured slower)
-__device__ __forceinline__ uint32_t prep_ld(const uint32_t *p)
-{
-#if DABX_PREP_NT & 1
-  return __builtin_nontemporal_load(p);
-#else
-  return *p;
-#endif
-}
-__device__ __forceinline__ void prep_st(uint32_t *p, uint32_t v)
-{
-#if DABX_PREP_NT & 2
-  __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
-}
 constexpr int PREP_STG = PJB * 16 * (PCH / 4) / 256;             // (job, plane, dword) items per thread and chunk (32)
 __device__ __forceinline__ void prep_item(int it, int cw, bool full, int &d, int &pl, int &job)
 {
@@ -80,7 +63,7 @@ __device__ __forceinline__ void prep_request(uint32_t (&stage)[PREP_STG], int ti
       if (base) {
         const unsigned slot = (unsigned)(s_r[r] - 16 + brev) & (TDI_SLOTS - 1);      // out_r[idx] = in_{r-16+map[idx&15]}[idx], backend.cpp:129
         const int2 mv = s_mv[r];
-        v = prep_ld(reinterpret_cast<const uint32_t *>(base + (brev < mv.x ? mv.y : 0) + (size_t)slot * CIF_BITS + in_plane));
+        v = *reinterpret_cast<const uint32_t *>(base + (brev < mv.x ? mv.y : 0) + (size_t)slot * CIF_BITS + in_plane);
       }
       stage[r] = v;
     }
@@ -98,7 +81,7 @@ __device__ __forceinline__ void prep_request(uint32_t (&stage)[PREP_STG], int ti
         // out_r[idx] = in_{r-16+map[idx&15]}[idx], map = 4-bit reversal (backend.cpp:129); planar ring: plane = idx & 15
         const long long cif = s_r[job] - 16 + bitrev4(pl);
         const int2 mv = s_mv[job];
-        v = prep_ld(reinterpret_cast<const uint32_t *>(base + (bitrev4(pl) < mv.x ? mv.y : 0) + (size_t)(cif & (TDI_SLOTS - 1)) * CIF_BITS + (size_t)pl * (CIF_BITS / 16) + p0 + 4 * d));
+        v = *reinterpret_cast<const uint32_t *>(base + (bitrev4(pl) < mv.x ? mv.y : 0) + (size_t)(cif & (TDI_SLOTS - 1)) * CIF_BITS + (size_t)pl * (CIF_BITS / 16) + p0 + 4 * d);
       }
     }
     stage[r] = v;
@@ -165,10 +148,10 @@ __global__ __launch_bounds__(256) void k_msc_prep(EngineDev e, int cifs, MscLaun
       const uint32_t a = __builtin_amdgcn_perm(m1, m0, 0x05010400u), b = __builtin_amdgcn_perm(m1, m0, 0x07030602u);
       const uint32_t c = __builtin_amdgcn_perm(m3, m2, 0x05010400u), f = __builtin_amdgcn_perm(m3, m2, 0x07030602u);
       const int P = p0 + 4 * d;                                    // position P + k holds idx = 16 (P + k) + plane: dword 4 (P + k) + pg
-      prep_st(&dst[(size_t)(4 * (P + 0) + pg) * 64], __builtin_amdgcn_perm(c, a, 0x05040100u));
-      prep_st(&dst[(size_t)(4 * (P + 1) + pg) * 64], __builtin_amdgcn_perm(c, a, 0x07060302u));
-      prep_st(&dst[(size_t)(4 * (P + 2) + pg) * 64], __builtin_amdgcn_perm(f, b, 0x05040100u));
-      prep_st(&dst[(size_t)(4 * (P + 3) + pg) * 64], __builtin_amdgcn_perm(f, b, 0x07060302u));
+      dst[(size_t)(4 * (P + 0) + pg) * 64] = __builtin_amdgcn_perm(c, a, 0x05040100u);
+      dst[(size_t)(4 * (P + 1) + pg) * 64] = __builtin_amdgcn_perm(c, a, 0x07060302u);
+      dst[(size_t)(4 * (P + 2) + pg) * 64] = __builtin_amdgcn_perm(f, b, 0x05040100u);
+      dst[(size_t)(4 * (P + 3) + pg) * 64] = __builtin_amdgcn_perm(f, b, 0x07060302u);
     }
     __syncthreads();
   }
@@ -193,62 +176,26 @@ __device__ __forceinline__ vt_rsrc vt_make_rsrc(const uint32_t *base, unsigned b
 {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(base), 0, (int)bytes, 0x00020000);   // raw buffer, dword format (gfx9 / CDNA)
 }
-// The lane's column of the group's decision words.  Default: a per-lane pointer, `nt` stores and loads (pipeline.h, DABX_VIT_NT).  Experiment builds
-// (-DDABX_VIT_BUF=1 -DDABX_VIT_ST_AUX=a -DDABX_VIT_LD_AUX=b): raw-buffer accesses over the group's words -- the step's row is a
-// scalar offset -- with the cache-policy bits free to choose: aux 0 plain, 1 sc0, 2 nt, 16 sc1 (write-through / L2 bypass), 17 sc0 sc1.
-struct VtDec {
-  uint2 *p;
-#if DABX_VIT_BUF
-  vt_rsrc rs;
-  int voff;
-#endif
-};
-__device__ __forceinline__ VtDec vt_make_dec(uint2 *group_base, int nsteps, int lane)
+// The lane's column of the group's decision words: a per-lane pointer.  The words are written once and read once: `nt` stores and
+// loads, past the caches (pipeline.h).
+struct VtDec { uint2 *p; };
+__device__ __forceinline__ VtDec vt_make_dec(uint2 *group_base, int lane)
 {
   VtDec d;
   d.p = group_base + lane;
-#if DABX_VIT_BUF
-  d.rs = vt_make_rsrc(reinterpret_cast<const uint32_t *>(group_base), (unsigned)nsteps * 512u);
-  d.voff = lane * 8;
-#else
-  (void)nsteps;
-#endif
   return d;
 }
-#ifndef DABX_VIT_ST_AUX
-#define DABX_VIT_ST_AUX 2
-#define DABX_VIT_LD_AUX 2
-#endif
 typedef unsigned vt_u2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void vt_dec_store(const VtDec &d, int t, unsigned acc0, unsigned acc1)
 {
-#if DABX_VIT_BUF
-  vt_u2v v; v.x = acc0; v.y = acc1;
-  __builtin_amdgcn_raw_buffer_store_b64(v, d.rs, d.voff, t * 512, DABX_VIT_ST_AUX);
-#elif DABX_VIT_NT & 1        // decision words, written once and read once: past the caches (pipeline.h)
   vt_u2v v; v.x = acc0; v.y = acc1;
   __builtin_nontemporal_store(v, reinterpret_cast<vt_u2v *>(&d.p[(size_t)t * 64]));
-#else
-  d.p[(size_t)t * 64] = make_uint2(acc0, acc1);
-#endif
 }
 __device__ __forceinline__ uint2 vt_dec_load(const VtDec &d, int t)
 {
-#if DABX_VIT_BUF
-  const vt_u2v v = __builtin_amdgcn_raw_buffer_load_b64(d.rs, d.voff, t * 512, DABX_VIT_LD_AUX);
-  return make_uint2(v.x, v.y);
-#elif DABX_VIT_NT & 2
   const vt_u2v v = __builtin_nontemporal_load(reinterpret_cast<const vt_u2v *>(&d.p[(size_t)t * 64]));
   return make_uint2(v.x, v.y);
-#else
-  return d.p[(size_t)t * 64];
-#endif
 }
-#if DABX_VIT_NT & 4          // (A/B builds: the transposed input past the caches; aux bit 1 = nt)
-constexpr int VT_IN_AUX = 2;
-#else
-constexpr int VT_IN_AUX = 0;
-#endif
 __device__ __forceinline__ void vt_fetch(VtCycle &c, vt_rsrc in_grp, int lane, vt_cmap map, int t0)
 {
   c.sh = 0;
@@ -258,7 +205,7 @@ __device__ __forceinline__ void vt_fetch(VtCycle &c, vt_rsrc in_grp, int lane, v
     const unsigned idx[4] = {m.x & 0xFFFFu, m.x >> 16, m.y & 0xFFFFu, m.y >> 16};
 #pragma unroll
     for (int p = 0; p < 4; p++) {
-      c.w[4 * s6 + p] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(in_grp, lane * 4, (int)((idx[p] >> 2) * 256u), VT_IN_AUX);
+      c.w[4 * s6 + p] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(in_grp, lane * 4, (int)((idx[p] >> 2) * 256u), 0);
       c.sh |= (unsigned long long)(idx[p] & 3) << (2 * (4 * s6 + p));
     }
   }
@@ -490,7 +437,7 @@ __device__ __forceinline__ void msc_vitT_body(const EngineDev &e, int cifs, cons
   const MscJob q = msc_class_job(e, cl, g * 64 + lane, cifs);
   const int nsteps = cl.nbits + 6, rows = cl.n_in / 4 + 1;
   const vt_rsrc in_grp = vt_make_rsrc(cl.inT + (size_t)g * rows * 64, (unsigned)rows * 256u);
-  const VtDec dec_lane = vt_make_dec(cl.decT + (size_t)g * nsteps * 64, nsteps, lane);
+  const VtDec dec_lane = vt_make_dec(cl.decT + (size_t)g * nsteps * 64, lane);
   const vt_cmap cmap = (vt_cmap)(const void *)cl.map2;
   uint32_t *out = nullptr;
   if (q.valid)
@@ -511,12 +458,7 @@ __device__ __forceinline__ void msc_vitT_body(const EngineDev &e, int cifs, cons
     }
   }
 }
-#ifdef DABX_VIT_WAVES                 // experiment builds only (tools/build_variant.sh -DDABX_VIT_WAVES=5 -DDABX_MSC_BATCH=9): ask for a fifth wave per SIMD
-#define DABX_VIT_OCC __attribute__((amdgpu_waves_per_eu(DABX_VIT_WAVES, DABX_VIT_WAVES)))
-#else
-#define DABX_VIT_OCC
-#endif
-__global__ __launch_bounds__(64) DABX_VIT_OCC void k_msc_vitT(EngineDev e, int cifs, MscLaunch ML, const uint32_t *prbs) { msc_vitT_body<0>(e, cifs, ML, prbs); }
+__global__ __launch_bounds__(64) void k_msc_vitT(EngineDev e, int cifs, MscLaunch ML, const uint32_t *prbs) { msc_vitT_body<0>(e, cifs, ML, prbs); }
 // the same trellises decoded with the arithmetic of the reference's VITERBI_AVX2 / VITERBI_SSE2 builds (cfg.viterbi_tie_mode)
 __global__ __launch_bounds__(64) void k_msc_vitT_avx2(EngineDev e, int cifs, MscLaunch ML, const uint32_t *prbs) { msc_vitT_body<1>(e, cifs, ML, prbs); }
 __global__ __launch_bounds__(64) void k_msc_vitT_sse2(EngineDev e, int cifs, MscLaunch ML, const uint32_t *prbs) { msc_vitT_body<2>(e, cifs, ML, prbs); }
@@ -533,7 +475,7 @@ __global__ __launch_bounds__(64) void k_vitT_stage(const uint32_t *symT, const u
   const int nsteps = nbits + 6, rows = nsteps + 1;
   const vt_rsrc in_grp = vt_make_rsrc(symT + (size_t)g * rows * 64, (unsigned)rows * 256u);
   unsigned long long unused = 0;
-  vt_decode<TIE, ALWAYS_CLAMP>(in_grp, (vt_cmap)(const void *)map, nsteps, vt_make_dec(decT + (size_t)g * nsteps * 64, nsteps, lane),
+  vt_decode<TIE, ALWAYS_CLAMP>(in_grp, (vt_cmap)(const void *)map, nsteps, vt_make_dec(decT + (size_t)g * nsteps * 64, lane),
                                outw + ((size_t)g * 64 + lane) * (nbits / 32), zeros, bk_tab, lane, unused, false);
 }
 

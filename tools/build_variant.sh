@@ -1,6 +1,6 @@
 #!/bin/bash
 # Builds an experiment variant of libdabx.so next to the product library, for same-box A/B runs (tools/ab.sh):
-#   tools/build_variant.sh <name> [extra hipcc flags, e.g. -DDABX_VIT_GRID_CAP=2048]   ->  tools/_build/ab/libdabx_<name>.so
+#   tools/build_variant.sh <name> [extra hipcc flags, e.g. -DDABX_MSC_BATCH=6]   ->  tools/_build/ab/libdabx_<name>.so
 NAME=$1; shift
 mkdir -p tools/_build/ab /tmp/dabx_variant_$NAME
 for f in dabstar_amd/csrc/*.hip dabstar_amd/csrc/*.cpp; do
