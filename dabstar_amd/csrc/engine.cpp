@@ -29,6 +29,8 @@ void dabx_internal_fibdec_skip(dabx_fibdec *d, long long n_fibs);     // fib.cpp
 int launch_dciq(const EngineDev &e, int mode, hipStream_t st);
 int launch_level_exact(const EngineDev &e, hipStream_t st);
 int launch_stage_msc_block(const EngineDev &e, const int16_t *soft_dev, int blk, bool closes_cif, hipStream_t st);
+int launch_msc_inject(const EngineDev &e, int stream, const int16_t *soft_dev, int n_cifs, int first, hipStream_t st);
+int launch_msc_advance(const EngineDev &e, const int32_t *counts_dev, hipStream_t st);
 extern const char *const kStepKernelNames[11];
 int launch_commit(const EngineDev &e, int stream, unsigned long long n, hipStream_t st);
 int launch_convert_iq(const void *src, int fmt, float2 *ring, int ring_len, unsigned long long wr0, size_t n, hipStream_t st);
@@ -2158,6 +2160,75 @@ int dabx_fic_restart(dabx_fic *f)
   if (int rc = dabx_fic_reset_decode_success_ratio(f)) return rc;
   f->running = true;
   return 0;
+}
+
+}  // extern "C"
+
+// ---- test entries of the batched MSC decoder (tests/test_gpu_msc_decoder.py; not part of include/dabx.h) ---------------------------
+// Soft bits go straight into the time-de-interleaver ring and k_msc_prep / k_msc_vitT (or k_msc_frame) decode them exactly as
+// dabx_process launches them: no IQ, no front-end kernel.  Between two decodes the ring holds the 16 CIFs of history in front of a
+// stream's CIF counter and at most one batch of new CIFs behind it: that is what `first + n_cifs` is checked against, so that no
+// call can overwrite history the next batch reads (TDI_SLOTS = 64 >= 16 + 4 * MSC_BATCH_FRAMES).
+extern "C" {
+
+// soft: [n_cifs][55296] int16, the whole CIFs cif_no + first .. cif_no + first + n_cifs - 1 of `stream` (cif_no: the stream's CIF counter,
+// which only dabx_internal_msc_decode moves), converted with the engine's viterbi_tie_mode as the demapper's output is.
+int dabx_internal_msc_inject(dabx_engine *e, int stream, const int16_t *soft, int n_cifs, int first)
+{
+  constexpr int HOLD = 4 * MSC_BATCH_FRAMES;
+  if (!e || !soft || stream < 0 || stream >= e->dev.n_streams || n_cifs < 1 || n_cifs > HOLD || first < 0 || first > HOLD - n_cifs || !e->dev.tdi) {
+    set_error("dabx_internal_msc_inject: bad argument (stream %d, CIFs %d + %d of at most %d)", stream, first, n_cifs, HOLD);
+    return DABX_E_ARG;
+  }
+  if (int rc = use_device(e)) return rc;
+  if (int rc = sync_all(e)) return rc;
+  int16_t *soft_dev = nullptr;
+  const size_t bytes = (size_t)n_cifs * CIF_BITS * sizeof(int16_t);
+  DABX_HIP(hipMalloc(&soft_dev, bytes));
+  int rc = 0;
+  if (hipMemcpy(soft_dev, soft, bytes, hipMemcpyHostToDevice) != hipSuccess) { set_error("dabx_internal_msc_inject: copy failed"); rc = DABX_E_HIP; }
+  if (!rc) rc = launch_msc_inject(e->dev, stream, soft_dev, n_cifs, first, e->stream);
+  if (hipStreamSynchronize(e->stream) != hipSuccess && !rc) { set_error("dabx_internal_msc_inject: HIP error"); rc = DABX_E_HIP; }
+  (void)hipFree(soft_dev);
+  return rc;
+}
+
+// cifs_per_stream: [n_streams], how many of the injected CIFs every stream counts as received (0 .. batch_cifs); then one MSC batch of
+// batch_cifs CIFs, launched as dabx_process launches it, and a full synchronisation.  Results: dabx_read_msc, dabx_get_subch_stats.
+int dabx_internal_msc_decode(dabx_engine *e, const int32_t *cifs_per_stream, int batch_cifs)
+{
+  if (!e || !cifs_per_stream || batch_cifs < 1 || batch_cifs > 4 * MSC_BATCH_FRAMES) {
+    set_error("dabx_internal_msc_decode: bad argument (batch of %d CIFs, at most %d)", batch_cifs, 4 * MSC_BATCH_FRAMES);
+    return DABX_E_ARG;
+  }
+  for (int s = 0; s < e->dev.n_streams; s++)
+    if (cifs_per_stream[s] < 0 || cifs_per_stream[s] > batch_cifs) {
+      set_error("dabx_internal_msc_decode: %d CIFs for stream %d in a batch of %d", (int)cifs_per_stream[s], s, batch_cifs);
+      return DABX_E_ARG;
+    }
+  if (e->dl.open || e->pending_frames != 0) {
+    set_error("dabx_internal_msc_decode: the engine has a delivery open or front-end frames pending");
+    return DABX_E_STATE;
+  }
+  if (int rc = use_device(e)) return rc;
+  if (int rc = sync_all(e)) return rc;
+  if (e->classes_dirty) {
+    if (int rc = e->build_msc_classes()) return rc;
+    e->classes_dirty = false;
+  }
+  int32_t *counts_dev = nullptr;
+  const size_t bytes = sizeof(int32_t) * (size_t)e->dev.n_streams;
+  DABX_HIP(hipMalloc(&counts_dev, bytes));
+  int rc = 0;
+  if (hipMemcpy(counts_dev, cifs_per_stream, bytes, hipMemcpyHostToDevice) != hipSuccess) { set_error("dabx_internal_msc_decode: copy failed"); rc = DABX_E_HIP; }
+  if (!rc) rc = launch_msc_advance(e->dev, counts_dev, e->stream);
+  if (!rc) {
+    e->dev.snap = e->snap_buf[e->ss.batch_parity];
+    rc = launch_msc_batch(e->dev, batch_cifs, e->have_fast ? &e->fast : nullptr, e->ss, e->mk);
+  }
+  const int rc2 = sync_all(e);
+  (void)hipFree(counts_dev);
+  return rc ? rc : rc2;
 }
 
 }  // extern "C"

@@ -2129,6 +2129,35 @@ int launch_stage_msc_block(const EngineDev &e, const int16_t *soft_dev, int blk,
   return 0;
 }
 
+// Test entries dabx_internal_msc_inject / dabx_internal_msc_decode (engine.cpp; not part of include/dabx.h): whole CIFs of soft bits go
+// into one stream's ring as k_stage_msc_block puts one symbol of stream 0 there -- CIFs cif_no + first .. of that stream, not yet
+// counted --, and the CIF counters then advance by a count per stream: what the front end does for a frame, without a front end.
+__global__ void k_msc_inject(EngineDev e, int s, const int16_t *soft, int n_cifs, int first)
+{
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)n_cifs * CIF_BITS) return;
+  const int c = (int)(i / CIF_BITS), bit = (int)(i - (size_t)c * CIF_BITS);
+  uint8_t *tdi = e.tdi + (size_t)s * TDI_SLOTS * CIF_BITS;
+  tdi[tdi_off(e.ctl[s].cif_no + first + c, bit)] = soft_to_sym_mode(soft[i], e.tie_mode);       // tdi_off < TDI_SLOTS * CIF_BITS for every CIF number
+}
+__global__ void k_msc_advance(EngineDev e, const int32_t *counts)
+{
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s < e.n_streams) e.ctl[s].cif_no += counts[s];
+}
+int launch_msc_inject(const EngineDev &e, int stream, const int16_t *soft_dev, int n_cifs, int first, hipStream_t st)
+{
+  hipLaunchKernelGGL(k_msc_inject, dim3((unsigned)(((size_t)n_cifs * CIF_BITS + 255) / 256)), dim3(256), 0, st, e, stream, soft_dev, n_cifs, first);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+int launch_msc_advance(const EngineDev &e, const int32_t *counts_dev, hipStream_t st)
+{
+  hipLaunchKernelGGL(k_msc_advance, dim3((e.n_streams + 255) / 256), dim3(256), 0, st, e, counts_dev);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+
 __global__ void k_commit(unsigned long long *wr, int n_streams, int stream, unsigned long long n)
 {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -103,6 +103,24 @@ def viterbi_lane_per_trellis(soft, nbits, tie_mode=0, always_clamp=False):
     return out
 
 
+def msc_inject(engine, stream, soft, first=0):
+    """Internal test entry (not part of include/dabx.h): soft [n_cifs, 55296] int16 becomes the whole CIFs cif_no + first .. of
+    `stream` in the engine's time-de-interleaver ring, converted as the demapper's output is (viterbi_tie_mode).  The stream's
+    CIF counter only moves in msc_decode; first + n_cifs may not exceed one batch (28 CIFs)."""
+    soft = np.ascontiguousarray(soft, np.int16).reshape(-1, 55296)
+    check(load().dabx_internal_msc_inject(engine._h, int(stream), _p(soft), soft.shape[0], int(first)))
+
+
+def msc_decode(engine, cifs_per_stream, batch_cifs):
+    """Internal test entry: every stream counts cifs_per_stream[s] (0 .. batch_cifs) of its injected CIFs as received, then one MSC
+    batch of batch_cifs CIFs runs exactly as dabx_process launches it (k_msc_prep + k_msc_vitT and / or k_msc_frame, DAB+ stage).
+    Results: Engine.read_msc / Engine.subch_stats."""
+    counts = np.ascontiguousarray(cifs_per_stream, np.int32).reshape(-1)
+    if counts.size != engine.n_streams:
+        raise ValueError("msc_decode needs one CIF count per stream")
+    check(load().dabx_internal_msc_decode(engine._h, _p(counts), int(batch_cifs)))
+
+
 def profile_input_bits(kbps, prot_level, short_form=0):
     return check(load().dabx_profile_input_bits(kbps, prot_level, short_form))
 

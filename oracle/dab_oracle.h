@@ -150,6 +150,8 @@ typedef struct {
 } ora_backend;
 int  ora_backend_init(ora_backend *b, const ora_subch_desc *d);
 void ora_backend_free(ora_backend *b);
+ora_backend *ora_backend_new(const ora_subch_desc *d);      /* heap constructor / destructor: a back end without a receiver */
+void ora_backend_delete(ora_backend *b);
 /* backend/backend.cpp:129-161 ; in = CIF soft bits of this sub-channel (frag i16) */
 void ora_backend_process(ora_backend *b, const int16_t *in);
 const uint8_t *ora_backend_msc_bytes(const ora_backend *b, size_t *len);

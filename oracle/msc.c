@@ -47,6 +47,22 @@ void ora_backend_free(ora_backend *b)
   memset(b, 0, sizeof(*b));
 }
 
+/* one back end on the heap, on its own (tests: a sub-channel's slice of every CIF goes straight into ora_backend_process) */
+ora_backend *ora_backend_new(const ora_subch_desc *d)
+{
+  ora_backend *b = (ora_backend *)malloc(sizeof(ora_backend));
+  if (!b) return NULL;
+  if (ora_backend_init(b, d) != 0) { ora_backend_free(b); free(b); return NULL; }
+  return b;
+}
+
+void ora_backend_delete(ora_backend *b)
+{
+  if (!b) return;
+  ora_backend_free(b);
+  free(b);
+}
+
 /* mp4processor.cpp:184-241 */
 static int process_rs_frame(ora_backend *b, int base)
 {

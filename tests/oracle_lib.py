@@ -97,6 +97,10 @@ def oracle():
         f.restype = C.POINTER(C.c_uint8)
         f.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
     L.ora_backend_stats.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
+    L.ora_backend_new.restype = C.c_void_p
+    L.ora_backend_new.argtypes = [C.POINTER(SubchDesc)]
+    L.ora_backend_delete.argtypes = [C.c_void_p]
+    L.ora_backend_process.argtypes = [C.c_void_p, _i16p]
     L.ora_parse_fibs.argtypes = [_u8p, _u8p, C.c_int, C.POINTER(SubchDesc), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]
     L.ora_rx_move_subch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_long]
     L.ora_level_walk.argtypes = [_c64p, C.c_size_t, C.c_float]
@@ -272,6 +276,45 @@ def backend_stats(rx, i):
     out = (C.c_long * 8)()
     oracle().ora_backend_stats(oracle().ora_rx_backend(rx, i), out)
     return dict(zip(["cif_out", "sf_ok", "sf_fail", "rs_corr", "rs_fail", "fc_corr", "au_ok", "au_bad"], list(out)))
+
+
+class OraBackend:
+    """oracle/msc.c on its own (Backend::_process_segment): 16-CIF time de-interleaver, ora_deconvolve, PRBS, logical frames.
+    push() takes the sub-channel's slice [cu_start * 64, (cu_start + cu_size) * 64) of one CIF."""
+
+    def __init__(self, cu_size, kbps, prot_level, short_form, cu_start=0, subch_id=0):
+        self.cu_size, self.kbps = cu_size, kbps
+        self._h = oracle().ora_backend_new(C.byref(SubchDesc(subch_id, cu_start, cu_size, kbps, prot_level, short_form)))
+        if not self._h:
+            raise ValueError("ora_backend_new refused %r" % ((cu_size, kbps, prot_level, short_form),))
+
+    def push(self, cif_slice):
+        v = np.ascontiguousarray(cif_slice, np.int16).reshape(-1)
+        assert v.size == self.cu_size * 64
+        oracle().ora_backend_process(self._h, v)
+
+    def msc_frames(self):
+        """Logical frames so far: [cifs_decoded, 3 * kbps] uint8."""
+        n = C.c_size_t(0)
+        p = oracle().ora_backend_msc_bytes(self._h, C.byref(n))
+        a = np.ctypeslib.as_array(p, (n.value,)).copy() if n.value else np.zeros(0, np.uint8)
+        return a.reshape(-1, 3 * self.kbps)
+
+    def stats(self):
+        out = (C.c_long * 8)()
+        oracle().ora_backend_stats(self._h, out)
+        return dict(zip(["cif_out", "sf_ok", "sf_fail", "rs_corr", "rs_fail", "fc_corr", "au_ok", "au_bad"], list(out)))
+
+    def close(self):
+        if self._h:
+            oracle().ora_backend_delete(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def make_descs(subch):
