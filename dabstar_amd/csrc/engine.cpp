@@ -33,7 +33,7 @@ int launch_msc_inject(const EngineDev &e, int stream, const int16_t *soft_dev, i
 int launch_msc_advance(const EngineDev &e, const int32_t *counts_dev, hipStream_t st);
 extern const char *const kStepKernelNames[11];
 int launch_commit(const EngineDev &e, int stream, unsigned long long n, hipStream_t st);
-int launch_convert_iq(const void *src, int fmt, float2 *ring, int ring_len, unsigned long long wr0, size_t n, hipStream_t st);
+int launch_convert_iq(const void *src, int fmt, void *ring, int ring_fmt, int ring_len, unsigned long long wr0, size_t n, hipStream_t st);
 int launch_fic_only(const EngineDev &e, hipStream_t st, int first, int count);
 int launch_i16_to_sym(const int16_t *soft, uint8_t *sym, size_t n, hipStream_t st);
 }  // namespace dabx
@@ -99,7 +99,7 @@ struct Ingest {
   int16_t *tab_int = nullptr; float *tab_frac = nullptr;
 };
 
-struct dabx_engine {
+struct dabx_engine : dabx::EngineHead {          // (iqfile.h: the ring format, where iqfile.cpp can read it)
   dabx_config cfg{};
   EngineDev dev{};
   hipStream_t stream = nullptr;                // == ss.a (front end)
@@ -155,10 +155,13 @@ struct dabx_engine {
   int delivery_finish(int slot, int devslab, hipStream_t tail);    // ... its slot gather is queued on `tail`: the one copy
   void delivery_abort(int slot, int devslab);                      // ... or it cannot be: both slabs go back
 
-  template <class T> int alloc(T **p, size_t count, bool zero = true)
+  // stream s's ring: its first element, whatever the element is (EngineDev::ring_fmt)
+  void *ring_of(int s) const { return static_cast<char *>(dev.iq) + (size_t)s * dev.ring_len * ring_bytes_per_sample(dev.ring_fmt); }
+  template <class T> int alloc(T **p, size_t count, bool zero = true) { return alloc_bytes(p, count * sizeof(T), zero); }
+  template <class T> int alloc_bytes(T **p, size_t n_bytes, bool zero = true)
   {
     void *q = nullptr;
-    const size_t bytes = std::max<size_t>(count * sizeof(T), 16);
+    const size_t bytes = std::max<size_t>(n_bytes, 16);
     DABX_HIP(hipMalloc(&q, bytes));
     if (zero) DABX_HIP(hipMemsetAsync(q, 0, bytes, stream));
     allocs.push_back(q);
@@ -584,7 +587,48 @@ void dabx_default_config(dabx_config *c)
   c->soft_bit_type = 1;                // glob_enums.h:49-56 (SOFTDEC1)
 }
 
-int dabx_create(const dabx_config *cfg, dabx_engine **out)
+static int create_impl(const dabx_config *cfg, int ring_fmt, dabx_engine **out);
+int dabx_create(const dabx_config *cfg, dabx_engine **out) { return create_impl(cfg, RING_CF32, out); }
+int dabx_create_ex(const dabx_config *cfg, const dabx_create_ext *ext, dabx_engine **out)
+{
+  if (!ext) return create_impl(cfg, RING_CF32, out);
+  if (ext->size < offsetof(dabx_create_ext, reserved)) {
+    set_error("dabx_create_ex: ext->size %u does not cover ring_format (sizeof(dabx_create_ext) is %zu)", ext->size, sizeof(dabx_create_ext));
+    return DABX_E_ARG;
+  }
+  if (ext->ring_format < DABX_RING_CF32 || ext->ring_format > DABX_RING_U8) {
+    set_error("dabx_create_ex: ring_format %d (DABX_RING_CF32 0, DABX_RING_S16 1, DABX_RING_U8 2)", ext->ring_format);
+    return DABX_E_ARG;
+  }
+  if (ext->ring_format != DABX_RING_CF32 && cfg && cfg->dc_iq_correction) {
+    set_error("dabx_create_ex: dc_iq_correction %d rewrites samples in place and its output is not a code: not with a DABX_RING_%s ring",
+              cfg->dc_iq_correction, ext->ring_format == DABX_RING_S16 ? "S16" : "U8");
+    return DABX_E_ARG;
+  }
+  // the native instantiations of the ring-reading kernels address an element by a 32-bit byte offset from its stream's ring (pipeline.hip, ring_elem)
+  if (ext->ring_format != DABX_RING_CF32 && cfg && (unsigned long long)cfg->ring_frames * TF * ring_bytes_per_sample(ext->ring_format) >= (1ull << 32)) {
+    set_error("dabx_create_ex: ring_frames %d: a stream's native ring stays below 4 GiB", cfg->ring_frames);
+    return DABX_E_ARG;
+  }
+  return create_impl(cfg, ext->ring_format, out);
+}
+int dabx_get_ring_format(dabx_engine *e, int32_t *ring_format, int32_t *bytes_per_sample)
+{
+  if (!e) { set_error("dabx_get_ring_format: bad argument"); return DABX_E_ARG; }
+  if (ring_format) *ring_format = e->dev.ring_fmt;
+  if (bytes_per_sample) *bytes_per_sample = ring_bytes_per_sample(e->dev.ring_fmt);
+  return 0;
+}
+// a push / slab of fmt into this engine's ring?  (a native ring takes its own codes only: they are copied, never converted)
+static int ring_takes(const dabx_engine *e, int fmt, const char *who)
+{
+  if (e->dev.ring_fmt == RING_CF32 || fmt == e->dev.ring_fmt) return 0;
+  static const char *const name[3] = {"cf32", "int16", "uint8"};
+  set_error("%s: fmt %d (%s) into a DABX_RING_%s ring: a native ring takes its own codes only", who, fmt, name[fmt], e->dev.ring_fmt == RING_S16 ? "S16" : "U8");
+  return DABX_E_ARG;
+}
+
+static int create_impl(const dabx_config *cfg, int ring_fmt, dabx_engine **out)
 {
   if (!cfg || !out || cfg->n_streams <= 0 || cfg->ring_frames < 2 || cfg->max_subch < 0 || cfg->max_subch > MAX_SUBCH ||
       cfg->out_frames < 1 || cfg->soft_bit_type < 1 || cfg->soft_bit_type > 3 || cfg->dc_iq_correction < 0 || cfg->dc_iq_correction > 2 ||
@@ -644,6 +688,7 @@ int dabx_create(const dabx_config *cfg, dabx_engine **out)
   EngineDev &d = e->dev;
   d.n_streams = S; d.max_subch = cfg->max_subch; d.out_frames = cfg->out_frames;
   d.ring_len = cfg->ring_frames * TF;
+  d.ring_fmt = e->ring_fmt = ring_fmt;
   d.threshold = cfg->sync_threshold; d.strongest = cfg->sync_strongest;
   d.fic_only = cfg->fic_only; d.capture_soft = cfg->capture_soft; d.tie_mode = cfg->viterbi_tie_mode;
   d.exact_level = cfg->exact_level_tracker == 1;
@@ -651,7 +696,7 @@ int dabx_create(const dabx_config *cfg, dabx_engine **out)
   const DevTables *t;
   if ((rc = get_tables(&t))) { dabx_destroy(e); return rc; }
 #define A(x) if ((rc = (x))) { dabx_destroy(e); return rc; }
-  A(e->alloc(&d.iq, (size_t)S * d.ring_len, false));
+  A(e->alloc_bytes(&d.iq, (size_t)S * d.ring_len * ring_bytes_per_sample(ring_fmt), false));
   A(e->alloc(&d.wr, S));
   A(e->alloc(&d.ctl, S));
   A(e->alloc(&d.spectra, (size_t)2 * S * 75 * K, false));
@@ -904,7 +949,7 @@ int dabx_set_subchannels_at(dabx_engine *e, int stream, const dabx_subch_desc *d
 int dabx_iq_ring_dev(dabx_engine *e, int stream, void **ring, size_t *cap)
 {
   if (!e || stream < 0 || stream >= e->dev.n_streams || !ring) return DABX_E_ARG;
-  *ring = e->dev.iq + (size_t)stream * e->dev.ring_len;
+  *ring = e->ring_of(stream);
   if (cap) *cap = (size_t)e->dev.ring_len;
   return 0;
 }
@@ -992,6 +1037,7 @@ int dabx_push_iq(dabx_engine *e, int stream, const void *iq, int fmt, size_t n)
     set_error("dabx_push_iq: bad argument");
     return DABX_E_ARG;
   }
+  if (int rc = ring_takes(e, fmt, "dabx_push_iq")) return rc;
   if (n == 0) return 0;
   if (int rc = use_device(e)) return rc;
   if (int rc = push_room(e, stream, n, "dabx_push_iq")) return rc;
@@ -1007,7 +1053,7 @@ int dabx_push_iq(dabx_engine *e, int stream, const void *iq, int fmt, size_t n)
   // beyond the committed write index, which no queued kernel reads; only the commit is ordered into the front-end stream
   announce_write(e, stream, e->wr_host[stream] + n);
   DABX_HIP(hipMemcpyAsync(e->stage, iq, bytes, hipMemcpyHostToDevice, e->ingest));
-  int rc = launch_convert_iq(e->stage, fmt, e->dev.iq + (size_t)stream * e->dev.ring_len, e->dev.ring_len, e->wr_host[stream], n, e->ingest);
+  int rc = launch_convert_iq(e->stage, fmt, e->ring_of(stream), e->dev.ring_fmt, e->dev.ring_len, e->wr_host[stream], n, e->ingest);
   if (rc) return rc;
   DABX_HIP(hipEventRecord(e->ingest_done, e->ingest));
   DABX_HIP(hipStreamWaitEvent(e->stream, e->ingest_done, 0));
@@ -1026,6 +1072,7 @@ int dabx_push_iq_async(dabx_engine *e, int stream, const void *iq, int fmt, size
     set_error("dabx_push_iq_async: bad argument");
     return DABX_E_ARG;
   }
+  if (int rc = ring_takes(e, fmt, "dabx_push_iq_async")) return rc;
   if (n == 0) return 0;
   if (int rc = use_device(e)) return rc;
   if (int rc = push_room(e, stream, n, "dabx_push_iq_async")) return rc;
@@ -1044,7 +1091,7 @@ int dabx_push_iq_async(dabx_engine *e, int stream, const void *iq, int fmt, size
   hipStream_t ing = (k & 1) ? e->ingest2 : e->ingest;
   announce_write(e, stream, e->wr_host[stream] + n);
   DABX_HIP(hipMemcpyAsync(e->aslot[k], iq, bytes, hipMemcpyHostToDevice, ing));
-  int rc = launch_convert_iq(e->aslot[k], fmt, e->dev.iq + (size_t)stream * e->dev.ring_len, e->dev.ring_len, e->wr_host[stream], n, ing);
+  int rc = launch_convert_iq(e->aslot[k], fmt, e->ring_of(stream), e->dev.ring_fmt, e->dev.ring_len, e->wr_host[stream], n, ing);
   if (rc) return rc;
   DABX_HIP(hipEventRecord(e->aslot_done[k], ing));
   DABX_HIP(hipStreamWaitEvent(e->stream, e->aslot_done[k], 0));      // the commit (and every frame after it) sees the samples
@@ -1082,13 +1129,25 @@ int dabx_read_iq(dabx_engine *e, int stream, uint64_t first, size_t n, float *iq
   const unsigned long long wr = e->wr_host[stream];
   if (first + n > wr || wr - first > (unsigned long long)e->dev.ring_len) { set_error("dabx_read_iq: samples not in the ring"); return DABX_E_STATE; }
   if (int rc = sync_all(e)) return rc;
-  const float2 *ring = e->dev.iq + (size_t)stream * e->dev.ring_len;
+  // a native ring: its codes are copied, and become floats here by the very map the kernels apply (ring_fmt.h: exact on host and device)
+  const size_t bps = (size_t)ring_bytes_per_sample(e->dev.ring_fmt);
+  const char *ring = static_cast<const char *>(e->ring_of(stream));
+  std::vector<char> codes(e->dev.ring_fmt == RING_CF32 ? 0 : n * bps);
+  char *dst = e->dev.ring_fmt == RING_CF32 ? reinterpret_cast<char *>(iq_out) : codes.data();
   size_t done = 0;
   while (done < n) {
     const size_t o = (size_t)((first + done) % (unsigned long long)e->dev.ring_len);
     const size_t take = std::min(n - done, (size_t)e->dev.ring_len - o);
-    DABX_HIP(hipMemcpy(iq_out + 2 * done, ring + o, take * sizeof(float2), hipMemcpyDeviceToHost));
+    DABX_HIP(hipMemcpy(dst + done * bps, ring + o * bps, take * bps, hipMemcpyDeviceToHost));
     done += take;
+  }
+  float2 *out2 = reinterpret_cast<float2 *>(iq_out);
+  if (e->dev.ring_fmt == RING_S16) {
+    const uint32_t *c = reinterpret_cast<const uint32_t *>(codes.data());
+    for (size_t i = 0; i < n; i++) out2[i] = RingFmt<RING_S16>::cvt(c[i]);
+  } else if (e->dev.ring_fmt == RING_U8) {
+    const uint16_t *c = reinterpret_cast<const uint16_t *>(codes.data());
+    for (size_t i = 0; i < n; i++) out2[i] = RingFmt<RING_U8>::cvt(c[i]);
   }
   return 0;
 }
@@ -1100,7 +1159,7 @@ int dabx_internal_ring_info(dabx_engine *e, int stream, float2 **ring, int *ring
   if (int rc = sync_all(e)) return rc;
   StreamCtl c;
   DABX_HIP(hipMemcpy(&c, e->dev.ctl + stream, sizeof(StreamCtl), hipMemcpyDeviceToHost));
-  *ring = e->dev.iq + (size_t)stream * e->dev.ring_len; *ring_len = e->dev.ring_len;
+  *ring = static_cast<float2 *>(e->ring_of(stream)); *ring_len = e->dev.ring_len;   // (untyped in a native ring: EngineHead::ring_fmt, IqDecode::ring_fmt)
   *wr = e->wr_host[stream]; *rd = c.rd; *st = e->stream;
   return 0;
 }
@@ -1549,6 +1608,7 @@ static int ingest_open_impl(dabx_engine *e, const dabx_ingest_config *cfg, const
     return DABX_E_ARG;
   }
   if (e->ing.open) { set_error("dabx_ingest_open: already open"); return DABX_E_STATE; }
+  if (!formats) { if (int rc = ring_takes(e, cfg ? cfg->fmt : 0, "dabx_ingest_open")) return rc; }
   if (int rc = use_device(e)) return rc;
   Ingest &I = e->ing;
   I.fmt = cfg ? cfg->fmt : 0;
@@ -1568,7 +1628,7 @@ static int ingest_open_impl(dabx_engine *e, const dabx_ingest_config *cfg, const
     std::map<std::pair<int, int>, int> tab_of;
     size_t need = 0;
     for (int s = 0; s < S_; s++) {
-      if ((rc = iq_check_format(&formats[s], &I.dec[(size_t)s]))) { ingest_free(e); return rc; }
+      if ((rc = iq_check_format(&formats[s], &I.dec[(size_t)s])) || (rc = iq_native_ring(&formats[s], &I.dec[(size_t)s], e->dev.ring_fmt))) { ingest_free(e); return rc; }
       const int rate = formats[s].sample_rate;
       if (rate != INPUT_RATE) {
         const auto key = std::make_pair((int)formats[s].family, rate);
@@ -1742,7 +1802,7 @@ static int ingest_commit_general(dabx_engine *e, int k)
   DABX_HIP(hipMemcpyAsync(I.jobs_dev, I.jobs_host, sizeof(IngestJob) * (size_t)S, hipMemcpyHostToDevice, e->ingest));
   DABX_HIP(hipMemcpyAsync(I.counts_dev, I.counts_host, sizeof(unsigned) * (size_t)S, hipMemcpyHostToDevice, e->ingest));
   IngestMulti m{};
-  m.slab = sl.dev; m.jobs = I.jobs_dev; m.iq = e->dev.iq; m.ring_len = e->dev.ring_len; m.work = I.work; m.work_pitch = I.work_pitch;
+  m.slab = sl.dev; m.jobs = I.jobs_dev; m.iq = static_cast<float2 *>(e->dev.iq); m.ring_len = e->dev.ring_len; m.work = I.work; m.work_pitch = I.work_pitch;
   m.carry = I.carry; m.carry_pitch = I.carry_pitch; m.tab_int = I.tab_int; m.tab_frac = I.tab_frac;
   if (int rc = launch_ingest_multi(m, S, max_n, max_out, e->ingest)) return rc;
   DABX_HIP(hipEventRecord(e->ingest_done, e->ingest));

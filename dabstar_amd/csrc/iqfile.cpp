@@ -2,6 +2,7 @@
 // resampler tables, and the streaming feed that moves payload bytes through iqfile.hip into a stream's IQ ring.
 // Reference behaviour: devices/filereaders/{raw_files,wav_files,xml_filereader}; see include/dabx.h for the rules.
 #include "iqfile.h"
+#include "ring_fmt.h"
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -41,6 +42,7 @@ static int check_format(const dabx_iq_format *f, IqDecode *d)
     d->int_scale = f->family == DABX_FAMILY_UFF ? 1.0f / (float)sc : ldexpf(1.0f, 1 - bits);
   }
   d->quirk_block = 0; d->quirk_i24 = 0; d->quirk_sign7f = 0;
+  d->ring_fmt = RING_CF32;
   if (f->reference_quirks && f->family == DABX_FAMILY_UFF) {
     // like the reference's reader, deliver whole 1-ms read blocks only (readSamples, xml_reader.cpp:224-227)
     d->quirk_block = (int16_t)(f->sample_rate / 1000);
@@ -55,6 +57,33 @@ static int check_format(const dabx_iq_format *f, IqDecode *d)
       return DABX_E_ARG;
     }
   }
+  return 0;
+}
+
+int dabx::iq_native_ring(const dabx_iq_format *f, IqDecode *d, int ring_fmt)
+{
+  d->ring_fmt = RING_CF32;
+  if (ring_fmt == RING_CF32) return 0;
+  static const char *const fam[3] = {"RAW", "WAV", "UFF"}, *const con[6] = {"uint8", "int8", "int16", "int24", "int32", "float32"};
+  const char *ring = ring_fmt == RING_S16 ? "S16" : "U8";
+  const char *why = nullptr;
+  if (f->sample_rate != INPUT_RATE) why = "it is resampled to 2.048 MS/s, and the interpolation produces floats";
+  else if (f->reference_quirks) why = "reference_quirks rewrites samples";
+  else if (ring_fmt == RING_U8) {
+    // the ring's map is raw_reader.cpp:66-70's (x - 127.38) / 128; libsndfile's uint8 is (x - 128) / 128
+    if (f->container != DABX_C_U8) why = "its samples are not uint8 codes";
+    else if (f->family == DABX_FAMILY_WAV) why = "a WAV file's uint8 means (x - 128) / 128, the ring's codes mean (x - 127.38) / 128";
+  } else {
+    const int bits = f->family == DABX_FAMILY_UFF ? f->bits : 16;
+    if (f->container != DABX_C_I16) why = "its samples are not int16 codes";
+    else if (bits != 16) why = "its int16 container does not carry 16 bits (the ring's codes mean x / 32768)";
+  }
+  if (why) {
+    set_error("iq format %s / %s at %d S/s cannot feed a DABX_RING_%s ring: %s (use a cf32 ring, dabx_create)", fam[f->family], con[f->container],
+              f->sample_rate, ring, why);
+    return DABX_E_ARG;
+  }
+  d->ring_fmt = ring_fmt;
   return 0;
 }
 
@@ -488,6 +517,8 @@ int dabx_feed_open(dabx_engine *e, int stream, const dabx_iq_format *fmt, dabx_f
   dabx_feed *f = new dabx_feed();
   f->eng = e; f->stream = stream; f->st = st;
   if ((rc = feed_setup(f, fmt))) { delete f; return rc; }
+  // a native ring takes the payload's codes as they are, or not at all (`ring` is its untyped base then)
+  if ((rc = iq_native_ring(fmt, &f->dec, reinterpret_cast<const EngineHead *>(e)->ring_fmt))) { delete f; return rc; }
   *out = f;
   return 0;
 }

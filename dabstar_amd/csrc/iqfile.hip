@@ -4,6 +4,7 @@
 //   k_resample_1ms  linear interpolation of 1-ms blocks to 2048 samples (wav_reader.cpp:190-206, xml_reader.cpp:237-244)
 #include "dabx_internal.h"
 #include "iqfile.h"
+#include "ring_fmt.h"
 #include <algorithm>
 
 namespace dabx {
@@ -70,6 +71,20 @@ __device__ __forceinline__ float2 decode_sample(const uint8_t *src, const IqDeco
   return make_float2(a, b);
 }
 
+// A native ring (IqDecode::ring_fmt, admitted by iq_native_ring: uint8 pairs of the 127.38 map, or 16-bit int16 pairs): sample i's codes
+// as the ring keeps them -- I in the low half, Q in the high half, int16 in machine byte order -- at element o of the ring at `base`
+__device__ __forceinline__ void store_native(const uint8_t *src, const IqDecode &d, size_t i, void *base, size_t o)
+{
+  const uint8_t *p = src + i * (size_t)(2 * d.bytes);
+  if (d.ring_fmt == RING_U8) {
+    const uint32_t a = p[0], b = p[1];
+    reinterpret_cast<uint16_t *>(base)[o] = (uint16_t)(d.swap_iq ? (b | (a << 8)) : (a | (b << 8)));
+  } else {
+    const uint32_t a = d.big_endian ? ld_be(p, 2) : ld_le(p, 2), b = d.big_endian ? ld_be(p + 2, 2) : ld_le(p + 2, 2);
+    reinterpret_cast<uint32_t *>(base)[o] = d.swap_iq ? (b | (a << 16)) : (a | (b << 16));
+  }
+}
+
 // ---- bulk ingest, general form: every stream its own container, rate and length, ONE slab, two launches (include/dabx.h "Bulk ingest") ----
 // grid (x, S).  Pass 1: the stream's payload -> cf32, straight into its ring (2.048 MS/s) or behind the carried samples in its work row.
 __global__ __launch_bounds__(256) void k_ingest_decode_multi(IngestMulti m)
@@ -82,6 +97,11 @@ __global__ __launch_bounds__(256) void k_ingest_decode_multi(IngestMulti m)
   float2 *work = m.work + (size_t)s * m.work_pitch;
   const size_t stride = (size_t)gridDim.x * blockDim.x, t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j.M) for (size_t i = t0; i < j.carry_n; i += stride) work[i] = m.carry[(size_t)s * m.carry_pitch + i];
+  if (j.dec.ring_fmt != RING_CF32) {                         // (never a resampling stream: refused when the ingest was opened)
+    for (size_t i = t0; i < j.n; i += stride)
+      store_native(src, j.dec, i, m.iq, (size_t)s * m.ring_len + (size_t)((j.dst0 + i) % (unsigned long long)m.ring_len));
+    return;
+  }
   for (size_t i = t0; i < j.n; i += stride) {
     const float2 v = decode_sample(src, j.dec, i);
     if (j.M) work[j.carry_n + i] = v;
@@ -123,6 +143,7 @@ __global__ __launch_bounds__(256) void k_decode_iq(const uint8_t *src, IqDecode 
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const size_t o = dst_len ? (size_t)((dst0 + i) % (unsigned long long)dst_len) : (size_t)(dst0 + i);
+  if (d.ring_fmt != RING_CF32) { store_native(src, d, i, dst, o); return; }
   dst[o] = decode_sample(src, d, i);
 }
 

@@ -1,6 +1,7 @@
 // pipeline.h -- device-resident state of the stream-batched receiver (engine.hip / pipeline.hip).
 #pragma once
 #include "dabx_internal.h"
+#include "ring_fmt.h"
 
 namespace dabx {
 
@@ -118,7 +119,8 @@ struct EngineDev {
   int32_t msc_stride;             // bytes per logical-frame slot (3 * max kbps)
   int32_t sf_stride;              // bytes per super-frame slot (110 * max kbps / 8)
   int32_t vit_stride;             // decision-scratch words per trellis (max over FIC and all sub-channels)
-  float2 *iq;                     // [S][ring_len]
+  void *iq;                       // [S][ring_len] elements of ring_fmt (ring_fmt.h): float2, or the recording's own int16 / uint8 pairs
+  int32_t ring_fmt;               // RING_CF32 / RING_S16 / RING_U8: the launchers of the ring-reading kernels pick the instantiation by it
   unsigned long long *wr;         // [S] absolute index one past the last committed sample
   StreamCtl *ctl;                 // [S]
   DemapDev demap;

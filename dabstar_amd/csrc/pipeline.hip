@@ -41,17 +41,51 @@ template <class T> __device__ __forceinline__ T uniform_load(const T *p)
   return __builtin_bit_cast(T, raw);
 }
 
-struct RingView {
-  const float2 *p;
+// The ring-reading kernels are templates on the ring's element (RF = EngineDev::ring_fmt, ring_fmt.h), as the demapper's are on the soft-bit
+// type: the launchers switch, no sample loop branches on the format.  RF = RING_CF32 is the code these kernels have always been.  In the
+// native instantiations whatever is requested ahead of its use stays a CODE in its register (one VGPR per sample instead of two) and
+// becomes a float2 where it is consumed.
+template <int RF> __device__ __forceinline__ const typename RingFmt<RF>::Elem *stream_ring(const EngineDev &e, int s)
+{
+  return reinterpret_cast<const typename RingFmt<RF>::Elem *>(e.iq) + (size_t)s * e.ring_len;
+}
+// Element i of a stream's ring.  Native rings: the byte offset in 32 bits (dabx_create_ex keeps a stream's ring below 4 GiB), so that the load
+// takes the ring's base from scalar registers and ONE address register per sample; cf32: the plain indexed load it has always been.
+template <int RF> __device__ __forceinline__ typename RingFmt<RF>::Elem ring_elem(const typename RingFmt<RF>::Elem *ring, unsigned i)
+{
+  if (RF == RING_CF32) return ring[i];
+  return *reinterpret_cast<const typename RingFmt<RF>::Elem *>(reinterpret_cast<const char *>(ring) + i * (unsigned)sizeof(typename RingFmt<RF>::Elem));
+}
+// A code prefetched a block ahead stays a code until HERE (left alone, the compiler takes a uint8 pair apart right behind its load and carries
+// two registers per sample through the block after all); nothing for cf32
+template <int RF> __device__ __forceinline__ typename RingFmt<RF>::Elem ring_held(typename RingFmt<RF>::Elem c)
+{
+  if constexpr (RF != RING_CF32) {
+    unsigned c32 = (unsigned)c;
+    asm volatile("" : "+v"(c32));
+    return (typename RingFmt<RF>::Elem)c32;
+  } else return c;
+}
+// the value of a prefetched element, zero if the sample was not there (bit `bit` of `ok`; the cf32 filler is that zero already)
+template <int RF> __device__ __forceinline__ float2 ring_value(typename RingFmt<RF>::Elem c, unsigned ok, int bit)
+{
+  const float2 v = RingFmt<RF>::cvt(c);
+  if (RF != RING_CF32 && !((ok >> bit) & 1u)) return make_float2(0.f, 0.f);
+  return v;
+}
+template <int RF> struct RingView {
+  typedef typename RingFmt<RF>::Elem Elem;
+  const Elem *p;
   unsigned len, base;
-  __device__ RingView(const float2 *ring, int ring_len, unsigned long long abs_base)
+  __device__ RingView(const Elem *ring, int ring_len, unsigned long long abs_base)
       : p(ring), len((unsigned)ring_len), base((unsigned)(abs_base % (unsigned long long)ring_len)) {}
-  __device__ float2 at(unsigned i) const     // i < len
+  __device__ Elem code(unsigned i) const     // i < len
   {
     unsigned o = base + i;
     if (o >= len) o -= len;
-    return p[o];
+    return ring_elem<RF>(p, o);
   }
+  __device__ float2 at(unsigned i) const { return RingFmt<RF>::cvt(code(i)); }
 };
 
 // ------------------------------------------------------------------------------------- DC / IQ correction
@@ -96,7 +130,7 @@ __global__ __launch_bounds__(256) void k_dciq(EngineDev e, int mode /* 1 DC, 2 D
   const int s = blockIdx.x, tid = threadIdx.x;
   const unsigned long long from = e.dciq_done[s], to = e.wr[s];
   if (from >= to) return;
-  float2 *ring = e.iq + (size_t)s * e.ring_len;
+  float2 *ring = reinterpret_cast<float2 *>(e.iq) + (size_t)s * e.ring_len;   // (cf32 rings only: dabx_create_ex refuses the correction on codes)
   float *st = e.dciq_state + (size_t)s * 8;
   float meanI = st[0], meanQ = st[1], meanII = st[2], meanQQ = st[3], meanIQ = st[4];     // tile start states (all threads)
   constexpr float ALPHA = 1.0f / (float)INPUT_RATE;
@@ -244,6 +278,7 @@ __device__ __forceinline__ float block_max_nonneg(float v, float *red, int tid)
 // One pass of the search for stream s (whole block, 256 threads).  The caller owns the stream (it is not in ST_EVAL_SYNC and
 // no demapper launch of it is in flight).  wr = the committed-sample count this kernel works with.
 // Returns -1: nothing done (too few samples), 0: searched, no end of a null symbol yet, 1: a null symbol ended at c.rd.
+template <int RF>
 __device__ __forceinline__ int acquire_stream(EngineDev &e, int s, int tid, int st, unsigned long long wr,
                                               unsigned long long budget_samples, AcqLds &w)
 {
@@ -262,7 +297,8 @@ __device__ __forceinline__ int acquire_stream(EngineDev &e, int s, int tid, int 
     for (int i = tid; i < TU; i += T) e.tii_acc[(size_t)s * TU + i] = make_float2(0.f, 0.f);
     if (tid == 0) { e.tii_cnt[2 * s] = 0; e.tii_cnt[2 * s + 1]++; }
   }
-  const float2 *ring = e.iq + (size_t)s * e.ring_len;
+  typedef RingFmt<RF> Fmt;
+  const typename Fmt::Elem *ring = stream_ring<RF>(e, s);
   const unsigned len = (unsigned)e.ring_len, base = (unsigned)(rd0 % (unsigned long long)e.ring_len);
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;   // wave-uniform: the roles below branch on the scalar unit
   // The search reads with frequency offset 0: currentPhase stays where the last frame left it and every sample is multiplied by the
@@ -280,7 +316,7 @@ __device__ __forceinline__ int acquire_stream(EngineDev &e, int s, int tid, int 
   // ... in two halves for the waves that fetch while the others walk: request(j) puts the samples of block j into registers (8 per
   // thread of waves 2-3), publish(j) turns them into the two magnitudes -- a whole block later, so that the HBM latency of the loads
   // (several microseconds next to the frame chain's traffic) lies behind a block's walk instead of in front of every eight samples
-  float2 raw[ACQ_CH / 128];
+  typename Fmt::Elem raw[ACQ_CH / 128];
   auto request = [&](int j) {
     const unsigned long long p0 = (unsigned long long)j * ACQ_CH;
     const unsigned o0 = (unsigned)((base + p0) % len);     // one 64-bit modulo per block, then add + conditional subtract
@@ -289,16 +325,18 @@ __device__ __forceinline__ int acquire_stream(EngineDev &e, int s, int tid, int 
       const int q = (tid - 128) + 128 * u;
       unsigned o = o0 + (unsigned)q;
       if (o >= len) o -= len;
-      raw[u] = p0 + (unsigned)q < avail ? ring[o] : make_float2(0.f, 0.f);
+      raw[u] = p0 + (unsigned)q < avail ? ring_elem<RF>(ring, o) : Fmt::filler();
     }
   };
   auto publish = [&](int j) {
     float *dst = w.a[j % 3], *dsr = w.r[j % 3];
     float mx = 0.f;
+    const unsigned long long p0 = (unsigned long long)j * ACQ_CH;
 #pragma unroll
     for (int u = 0; u < ACQ_CH / 128; u++) {
       const int q = (tid - 128) + 128 * u;
-      const float2 v = raw[u];
+      float2 v = Fmt::cvt(ring_held<RF>(raw[u]));
+      if (RF != RING_CF32 && !(p0 + (unsigned)q < avail)) v = make_float2(0.f, 0.f);   // (a zero VALUE has no code: the filler is not it)
       const float a = sqrtf(v.x * v.x + v.y * v.y);
       const float2 m = cmul(v, osc);
       dst[64 + q] = a; dsr[64 + q] = sqrtf(m.x * m.x + m.y * m.y);
@@ -319,7 +357,7 @@ __device__ __forceinline__ int acquire_stream(EngineDev &e, int s, int tid, int 
       if (p0 + (unsigned)q < avail) {
         unsigned o = o0 + (unsigned)q;
         if (o >= len) o -= len;
-        const float2 v = ring[o];
+        const float2 v = Fmt::cvt(ring_elem<RF>(ring, o));
         a = sqrtf(v.x * v.x + v.y * v.y);
         const float2 m = cmul(v, osc);
         ar = sqrtf(m.x * m.x + m.y * m.y);
@@ -508,15 +546,20 @@ __device__ __forceinline__ int acquire_stream(EngineDev &e, int s, int tid, int 
 // went through SampleReader's level tracker (sample_reader.cpp:245-248) -- run it exactly, sample by sample: right after
 // start-up the level is still far from settled (it starts at 0.1) and the null-dip detector of the next attempt compares
 // against it.  buf: >= T_u floats of LDS (16-byte aligned), red: >= 8.  The caller changes c.state.
-__device__ __forceinline__ void sync_failed(EngineDev &e, int s, int tid, const RingView &rv, unsigned long long rd, int phase0, int f,
+template <int RF>
+__device__ __forceinline__ void sync_failed(EngineDev &e, int s, int tid, const RingView<RF> &rv, unsigned long long rd, int phase0, int f,
                                             float *buf, float *red, bool track_level)
 {
   StreamCtl &c = e.ctl[s];
   float pk = 0.f;
   if (track_level) {                                       // (not the frame chain with cfg.exact_level_tracker: k_level_exact walks everything it reads)
+    // (native rings: the offsets of the window are made anew here -- otherwise the ones the caller's correlation loaded from, one register each,
+    //  are kept alive across the whole correlation for this rare path)
+    int t_ = tid;
+    if (RF != RING_CF32) asm volatile("" : "+v"(t_));
 #pragma unroll
     for (int u = 0; u < 8; u++) {
-      const float2 x = rv.at(tid + 256 * u);
+      const float2 x = rv.at(t_ + 256 * u);
       const float a = sqrtf(x.x * x.x + x.y * x.y);
       buf[tid + 256 * u] = a;
       pk = fmaxf(pk, a);
@@ -544,13 +587,14 @@ __device__ __forceinline__ void sync_failed(EngineDev &e, int s, int tid, const 
 // not (a long time in lock with a short ring, or a zero-copy producer whose writes the library does not see), the level continues from
 // the chunk-wise value over the samples read since (the T_u window of the failed correlation), as it did before round 4, and the
 // event is counted (dabx_stats.level_unanchored_events; level_rewalk_events counts the exact ones).
+template <int RF>
 __device__ __forceinline__ void level_from_anchor(EngineDev &e, int s, int tid, AcqLds &w)
 {
   constexpr int T = 256;
   StreamCtl &c = e.ctl[s];
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const unsigned long long p1 = c.rd, len64 = (unsigned long long)e.ring_len;
-  const float2 *ring = e.iq + (size_t)s * e.ring_len;
+  const typename RingFmt<RF>::Elem *ring = stream_ring<RF>(e, s);
   const unsigned len = (unsigned)e.ring_len;
   LevelPar lp;
   if (wave <= 1) lp.init(lane);
@@ -603,7 +647,7 @@ __device__ __forceinline__ void level_from_anchor(EngineDev &e, int s, int tid, 
         if (b0 + (unsigned)q < n) {
           unsigned o = o0 + (unsigned)q;
           if (o >= len) o -= len;
-          const float2 v = ring[o];
+          const float2 v = RingFmt<RF>::cvt(ring_elem<RF>(ring, o));
           a = sqrtf(v.x * v.x + v.y * v.y);
         }
         dst[q] = a;
@@ -663,6 +707,7 @@ __device__ __forceinline__ void level_from_anchor(EngineDev &e, int s, int tid, 
 // failed correlation straight back to the search like the reference (one candidate per step starved streams in deep fades:
 // false dips every few thousand samples -- fuzz seed 5001).  A candidate that correlates is left at ST_EVAL_SYNC with the read
 // cursor in front of it: k_frame_head repeats the correlation (same samples, same threshold, same result) and decodes the frame.
+template <int RF>
 __global__ __launch_bounds__(256, 2) void k_acquire(EngineDev e, DevTables t, int budget_frames)
 {
   __shared__ AcqLds w;
@@ -690,12 +735,12 @@ __global__ __launch_bounds__(256, 2) void k_acquire(EngineDev e, DevTables t, in
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
   int st = w.flag[1], new_state = -1;
   const unsigned long long wr = s_wr, rd_start = c.rd, budget = (unsigned long long)budget_frames * TF;
-  const float2 *ring = e.iq + (size_t)s * e.ring_len;
-  if (e.anchor_level && c.lvl_anchor_pos != c.rd) level_from_anchor(e, s, tid, w);
+  const typename RingFmt<RF>::Elem *ring = stream_ring<RF>(e, s);
+  if (e.anchor_level && c.lvl_anchor_pos != c.rd) level_from_anchor<RF>(e, s, tid, w);
   for (;;) {
     const unsigned long long used = c.rd - rd_start;
     if (used >= budget) break;
-    const int r = acquire_stream(e, s, tid, st, wr, budget - used, w);
+    const int r = acquire_stream<RF>(e, s, tid, st, wr, budget - used, w);
     if (r < 0) break;
     st = new_state = ST_WAIT_SYNC;
     if (r == 0) break;
@@ -705,14 +750,14 @@ __global__ __launch_bounds__(256, 2) void k_acquire(EngineDev e, DevTables t, in
     const int phase0 = c.nco_phase, f = (int)roundf(c.f_bb);
     Nco nco;
     nco.init(phase0, f, tid);
-    const RingView rv(ring, e.ring_len, rd);
+    const RingView<RF> rv(ring, e.ring_len, rd);
     float2 v[8];
 #pragma unroll
     for (int u = 0; u < 8; u++) { v[u] = nco.mix(rv.at(tid + 256 * u)); nco.step(); }
     const int start = prs_correlate_block(v, c.sync_thr, e.strongest, t, lds, peak, red, tid);   // dab_processor.cpp:394
     __syncthreads();
     if (start >= 0) break;
-    sync_failed(e, s, tid, rv, rd, phase0, f, peak, red, true);
+    sync_failed<RF>(e, s, tid, rv, rd, phase0, f, peak, red, true);
     new_state = ST_WAIT_SYNC;
     if (wr - c.rd < (unsigned long long)(ACQ_NEED + FRAME_NEED)) break;
   }
@@ -727,7 +772,9 @@ __global__ __launch_bounds__(256, 2) void k_acquire(EngineDev e, DevTables t, in
 
 // --------------------------------------------------------------------------------------------- frame head
 // 3 waves per SIMD: 166 VGPRs, no scratch
-__global__ __launch_bounds__(256, 3) void k_frame_head(EngineDev e, DevTables t)
+// (126 VGPRs: four waves per SIMD.  The cf32 code reaches that under its bound of three; the native instantiations are held to it)
+template <int RF>
+__global__ __launch_bounds__(256, RF == RING_CF32 ? 3 : 4) void k_frame_head(EngineDev e, DevTables t)
 {
   front_prio();
   __shared__ float2 lds[FFT_LDS_FLOAT2];
@@ -737,7 +784,7 @@ __global__ __launch_bounds__(256, 3) void k_frame_head(EngineDev e, DevTables t)
   __shared__ int s_state;
   const int s = blockIdx.x, tid = threadIdx.x;
   StreamCtl &c = e.ctl[s];
-  const float2 *ring = e.iq + (size_t)s * e.ring_len;
+  const typename RingFmt<RF>::Elem *ring = stream_ring<RF>(e, s);
   // first kernel of a step: "no frame yet"
   if (tid < 76) e.sym_off[(size_t)s * 76 + tid] = -1;
   if (tid == 0) {
@@ -755,7 +802,7 @@ __global__ __launch_bounds__(256, 3) void k_frame_head(EngineDev e, DevTables t)
   float2 v[8];
   Nco nco;
   nco.init(phase0, f, tid);
-  const RingView rv(ring, e.ring_len, rd);
+  const RingView<RF> rv(ring, e.ring_len, rd);
   float abs_a = 0.f, abs_b = 0.f;                          // level tracker: sum |x| of what this frame head reads
 #pragma unroll
   for (int u = 0; u < 8; u++) { const float2 x = rv.at(tid + 256 * u); abs_a += cabsf_level(x); v[u] = nco.mix(x); nco.step(); }
@@ -765,7 +812,7 @@ __global__ __launch_bounds__(256, 3) void k_frame_head(EngineDev e, DevTables t)
     // :396-400 -> WAIT_FOR_TIME_SYNC_MARKER: the stream goes over to k_acquire
     // (the level over the T_u samples just read: here from the chunk-wise value in the round-3 mode only; k_level_exact or k_acquire's
     //  re-walk from the anchor see to it otherwise)
-    sync_failed(e, s, tid, rv, rd, phase0, f, peak, red, !e.exact_level && !e.anchor_level);
+    sync_failed<RF>(e, s, tid, rv, rd, phase0, f, peak, red, !e.exact_level && !e.anchor_level);
     __threadfence();
     __syncthreads();
     if (tid == 0) {
@@ -842,6 +889,7 @@ __global__ __launch_bounds__(256, 3) void k_frame_head(EngineDev e, DevTables t)
 // (one stream: 75 blocks of one symbol -- the single-ensemble configurations are latency-bound on the frame's serial chain)
 __host__ __device__ constexpr int sym_blocks_per_stream(int n_streams) { return n_streams >= FEW_STREAMS ? 15 : (n_streams >= 16 ? 25 : 75); }
 // 3 waves per SIMD: 170 VGPRs without spills (bounded to 4 it spills 8 registers and runs 25 % slower)
+template <int RF>
 __global__ __launch_bounds__(256, 3) void k_symbols_persistent(EngineDev e, DevTables t)
 {
   front_prio();
@@ -853,12 +901,25 @@ __global__ __launch_bounds__(256, 3) void k_symbols_persistent(EngineDev e, DevT
   double2 nco_base = uniform_load(e.nco_sym + (size_t)s * 76 + l);
   const double2 nco_step = uniform_load(e.nco_sym + (size_t)s * 76 + 75);
   if (off < 0) return;                                       // no frame for this stream in this step (all 75 entries are -1 then)
-  const float2 *ring = e.iq + (size_t)s * e.ring_len;
+  typedef RingFmt<RF> Fmt;
+  const typename Fmt::Elem *ring = stream_ring<RF>(e, s);
   const unsigned len = (unsigned)e.ring_len;
   const bool two = tid + 256 < TG;
-  float2 nx[12];
+  typename Fmt::Elem nx[12];                                 // (codes in a native ring: 12 registers instead of 24)
   auto request = [&](int o) {
-    auto at = [&](unsigned i) { unsigned a = (unsigned)o + i; if (a >= len) a -= len; return ring[a]; };
+    auto at = [&](unsigned i) { unsigned a = (unsigned)o + i; if (a >= len) a -= len; return ring_elem<RF>(ring, a); };
+    // (native rings: the sample indices are made from the thread index anew per request -- three instructions -- instead of living in registers
+    //  across the transform, where this kernel has none to spare)
+    if (RF != RING_CF32) {
+      int t_ = tid;
+      asm volatile("" : "+v"(t_));
+      const bool two_ = t_ + 256 < TG;
+      nx[0] = at(t_); nx[1] = at(TU + t_);
+      nx[2] = at(two_ ? t_ + 256 : t_); nx[3] = at(two_ ? TU + t_ + 256 : TU + t_);
+#pragma unroll
+      for (int u = 0; u < 8; u++) nx[4 + u] = at(TG + t_ + 256 * u);
+      return;
+    }
     nx[0] = at(tid); nx[1] = at(TU + tid);
     nx[2] = at(two ? tid + 256 : tid); nx[3] = at(two ? TU + tid + 256 : TU + tid);
 #pragma unroll
@@ -875,10 +936,11 @@ __global__ __launch_bounds__(256, 3) void k_symbols_persistent(EngineDev e, DevT
   const unsigned kkw[4] = {kk4.x, kk4.y, kk4.z, kk4.w};
   const unsigned rd_lo = t.carrier_slot_rd[tid];
   for (;;) {
-    const float2 cb0 = nx[0], ca0 = nx[1], cb1 = nx[2], ca1 = nx[3];
+    // (a native ring: the codes become floats HERE, so that from the next request on the prefetch registers are free for its codes)
+    float2 cb0 = Fmt::cvt(nx[0]), ca0 = Fmt::cvt(nx[1]), cb1 = Fmt::cvt(nx[2]), ca1 = Fmt::cvt(nx[3]);
     float2 v[8];
 #pragma unroll
-    for (int u = 0; u < 8; u++) v[u] = nx[4 + u];
+    for (int u = 0; u < 8; u++) v[u] = Fmt::cvt(nx[4 + u]);
     const double2 base_now = nco_base;
     const int l_next = l + (int)gridDim.x;
     if (l_next < 75) {                                       // block-uniform
@@ -916,7 +978,9 @@ __global__ __launch_bounds__(256, 3) void k_symbols_persistent(EngineDev e, DevT
     }
 #pragma unroll
     for (int u = 0; u < 8; u++) {
-      const int kk = (int)(int16_t)(kkw[u >> 1] >> (16 * (u & 1)));
+      unsigned kw = kkw[u >> 1];
+      if (RF != RING_CF32) asm volatile("" : "+v"(kw));       // (native rings: the eight slots stay packed in their four registers between symbols)
+      const int kk = (int)(int16_t)(kw >> (16 * (u & 1)));
       if (kk >= 0) lds[kk] = v[u];
     }
     __syncthreads();
@@ -1332,6 +1396,7 @@ __global__ __launch_bounds__(256) void k_fic_frame(EngineDev e, DevTables t, int
 }
 
 // --------------------------------------------------------------------------------------------- frame tail
+template <int RF>
 __global__ __launch_bounds__(256) void k_frame_tail(EngineDev e, DevTables t)
 {
   front_prio();
@@ -1348,18 +1413,19 @@ __global__ __launch_bounds__(256) void k_frame_tail(EngineDev e, DevTables t)
   if (tid < 75) { cpp = e.cp_part[(size_t)s * 75 + tid]; absp = e.abs_part[(size_t)s * 76 + tid]; }
   // The null symbol's samples do not depend on the fine-CFO update below, only their mixing does: requested here, behind the
   // two loads above, so that their HBM latency runs behind the reductions (they used to be the first thing after the barrier).
-  const float2 *ring = e.iq + (size_t)s * e.ring_len;
+  typedef RingFmt<RF> Fmt;
+  const typename Fmt::Elem *ring = stream_ring<RF>(e, s);
   const unsigned long long base = c.sym0_pos + TU + 75ull * TS;
-  const RingView rv(ring, e.ring_len, base);
-  float2 xr[8];
+  const RingView<RF> rv(ring, e.ring_len, base);
+  typename Fmt::Elem xr[8];
 #pragma unroll
-  for (int u = 0; u < 8; u++) xr[u] = rv.at(TG + tid + 256 * u);
+  for (int u = 0; u < 8; u++) xr[u] = rv.code(TG + tid + 256 * u);
   constexpr int N_REST = (TN - TU + 255) / 256;            // the rest of the T_n samples read (guard interval and tail of the null symbol)
-  float2 xq[N_REST];
+  typename Fmt::Elem xq[N_REST];
 #pragma unroll
   for (int k = 0; k < N_REST; k++) {                       // unconditional (index clamped; the sum below skips the surplus): no branch, no wait between the requests
     const int i = min(tid + 256 * k, TN - TU - 1);
-    xq[k] = rv.at(i < TG ? i : i + TU);
+    xq[k] = rv.code(i < TG ? i : i + TU);
   }
   asm volatile("" ::: "memory");                           // keep the order of the requests
   float cre = cpp.x, cim = cpp.y, sym_w = 0.f;
@@ -1391,13 +1457,13 @@ __global__ __launch_bounds__(256) void k_frame_tail(EngineDev e, DevTables t)
   float an = 0.f;                                          // sum of this thread's |x|: transform samples first, then the rest
 #pragma unroll
   for (int u = 0; u < 8; u++) {
-    const float2 x = xr[u];
+    const float2 x = Fmt::cvt(xr[u]);
     an += cabsf_level(x);
     v[u] = nco.mix(x);
     nco.step();
   }
 #pragma unroll
-  for (int k = 0; k < N_REST; k++) if (tid + 256 * k < TN - TU) an += cabsf_level(xq[k]);
+  for (int k = 0; k < N_REST; k++) if (tid + 256 * k < TN - TU) an += cabsf_level(Fmt::cvt(xq[k]));
   an = block_sum(an, red, tid);
   fft2048<false>(v, lds, t.twiddle, tid);
   const bool is_tii = (c.cif_count & 7) >= 4;              // :274
@@ -1476,6 +1542,7 @@ __global__ __launch_bounds__(256) void k_frame_tail(EngineDev e, DevTables t)
 // per sample, 196 104 + start_index samples per frame: one wave per stream computes |x| for 1024 samples at a time into LDS
 // (all lanes) and then walks them (every lane redundantly: LDS broadcast reads, no divergence).  About 1.5 ms per frame,
 // more than the rest of the receiver together -- which is why the default advances the tracker chunk-wise (k_frame_tail).
+template <int RF>
 __global__ __launch_bounds__(128) void k_level_exact(EngineDev e)
 {
   front_prio();                          // (wave priority 0 / 1 / 3 and the HIP stream's priority make no difference to what the tracker costs
@@ -1497,9 +1564,11 @@ __global__ __launch_bounds__(128) void k_level_exact(EngineDev e)
   const unsigned long long rd1 = __hip_atomic_load(&c.rd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (rd1 <= rd0) return;
   const unsigned long long n = rd1 - rd0;
-  const float2 *ring = e.iq + (size_t)s * e.ring_len;
+  typedef RingFmt<RF> Fmt;
+  const typename Fmt::Elem *ring = stream_ring<RF>(e, s);
   const unsigned len = (unsigned)e.ring_len;
-  float2 raw[CH / 64];
+  typename Fmt::Elem raw[CH / 64];
+  unsigned raw_ok = 0;                                       // native rings: which of them are samples
   __shared__ float s_pk;
   auto request = [&](unsigned long long p0) {               // samples [p0, p0 + CH) into registers (zeros beyond n)
     const unsigned o0 = (unsigned)((rd0 + p0) % len);
@@ -1507,14 +1576,17 @@ __global__ __launch_bounds__(128) void k_level_exact(EngineDev e)
     for (int q = 0; q < CH / 64; q++) {
       const unsigned i = lane + 64 * q;
       unsigned o = o0 + i; if (o >= len) o -= len;
-      raw[q] = p0 + i < n ? ring[o] : make_float2(0.f, 0.f);
+      const bool in = p0 + i < n;
+      raw[q] = in ? ring_elem<RF>(ring, o) : Fmt::filler();
+      if (RF != RING_CF32) raw_ok = (raw_ok & ~(1u << q)) | ((unsigned)in << q);
     }
   };
   float pk = 0.f;                                            // peakLevel is a maximum: taken by the wave that makes the magnitudes
   auto publish = [&](float *dst) {
 #pragma unroll
     for (int q = 0; q < CH / 64; q++) {
-      const float a = sqrtf(raw[q].x * raw[q].x + raw[q].y * raw[q].y);
+      const float2 v = ring_value<RF>(raw[q], raw_ok, q);
+      const float a = sqrtf(v.x * v.x + v.y * v.y);
       dst[lane + 64 * q] = a;
       pk = fmaxf(pk, a);
     }
@@ -1544,9 +1616,16 @@ __global__ __launch_bounds__(128) void k_level_exact(EngineDev e)
   __syncthreads();
   if (tid == 0) { c.s_level = lv; c.peak_level = fmaxf(c.peak_level, s_pk); e.level_pos[s] = rd1; }
 }
+// a ring-reading kernel in the instantiation of the engine's ring (EngineDev::ring_fmt)
+#define DABX_LAUNCH_RING(e_, kernel, ...)                                            \
+  do {                                                                               \
+    if ((e_).ring_fmt == RING_S16) hipLaunchKernelGGL(kernel<RING_S16>, __VA_ARGS__); \
+    else if ((e_).ring_fmt == RING_U8) hipLaunchKernelGGL(kernel<RING_U8>, __VA_ARGS__); \
+    else hipLaunchKernelGGL(kernel<RING_CF32>, __VA_ARGS__);                         \
+  } while (0)
 int launch_level_exact(const EngineDev &e, hipStream_t st)
 {
-  hipLaunchKernelGGL(k_level_exact, dim3(e.n_streams), dim3(128), 0, st, e);
+  DABX_LAUNCH_RING(e, k_level_exact, dim3(e.n_streams), dim3(128), 0, st, e);
   DABX_HIP(hipGetLastError());
   return 0;
 }
@@ -1907,20 +1986,20 @@ int launch_front_step(const EngineDev &e_in, EngineStreams &ss, Marker &mk, bool
       if (e.exact_level) {
         // the tracker of step n walks the frame of step n - 1 while the chain demodulates frame n: behind that chain's tail, not before
         if (ss.tail_recorded) DABX_HIP(hipStreamWaitEvent(ss.q, ss.tail_done, 0));
-        hipLaunchKernelGGL(k_level_exact, dim3(e.n_streams), dim3(128), 0, ss.q, e);
+        DABX_LAUNCH_RING(e, k_level_exact, dim3(e.n_streams), dim3(128), 0, ss.q, e);
       }
-      if (go) { mk.begin(0, ss.q); hipLaunchKernelGGL(k_acquire, dim3(e.n_streams), dim3(256), 0, ss.q, e, *t, 1); mk.end(0, ss.q); }
+      if (go) { mk.begin(0, ss.q); DABX_LAUNCH_RING(e, k_acquire, dim3(e.n_streams), dim3(256), 0, ss.q, e, *t, 1); mk.end(0, ss.q); }
       DABX_HIP(hipEventRecord(ss.acq_done, ss.q));
       ss.acq_in_flight = true;
     }
   } else {
     if (ss.acq_in_flight) { DABX_HIP(hipStreamWaitEvent(st, ss.acq_done, 0)); ss.acq_in_flight = false; }   // a pass of an earlier, asynchronous call
-    if (e.exact_level) hipLaunchKernelGGL(k_level_exact, dim3(e.n_streams), dim3(128), 0, st, e);
-    mk.begin(0, st); hipLaunchKernelGGL(k_acquire, dim3(e.n_streams), dim3(256), 0, st, e, *t, 1); mk.end(0, st);
+    if (e.exact_level) DABX_LAUNCH_RING(e, k_level_exact, dim3(e.n_streams), dim3(128), 0, st, e);
+    mk.begin(0, st); DABX_LAUNCH_RING(e, k_acquire, dim3(e.n_streams), dim3(256), 0, st, e, *t, 1); mk.end(0, st);
     if (ss.q && ss.acq_a_done) { DABX_HIP(hipEventRecord(ss.acq_a_done, st)); ss.acq_a_pending = true; }
   }
-  mk.begin(1, st); hipLaunchKernelGGL(k_frame_head, dim3(e.n_streams), dim3(256), 0, st, e, *t); mk.end(1, st);
-  mk.begin(2, st); hipLaunchKernelGGL(k_symbols_persistent, dim3(sym_blocks_per_stream(e.n_streams), e.n_streams), dim3(256), 0, st, e, *t); mk.end(2, st);
+  mk.begin(1, st); DABX_LAUNCH_RING(e, k_frame_head, dim3(e.n_streams), dim3(256), 0, st, e, *t); mk.end(1, st);
+  mk.begin(2, st); DABX_LAUNCH_RING(e, k_symbols_persistent, dim3(sym_blocks_per_stream(e.n_streams), e.n_streams), dim3(256), 0, st, e, *t); mk.end(2, st);
   // kernel instance by (ESoftBitType, symbol conversion of the canonical / SIMD builds)
 #define DABX_DEMAP_DISPATCH(KERNEL, ...)                                                                                         \
   do {                                                                                                                          \
@@ -1974,7 +2053,7 @@ int launch_front_step(const EngineDev &e_in, EngineStreams &ss, Marker &mk, bool
     mk.begin(3, st); demap(st, 0, 75); mk.end(3, st);
   }
   mk.begin(4, st); hipLaunchKernelGGL(k_fic_frame, dim3(e.n_streams), dim3(256), 0, st, e, *t, 0, 4); mk.end(4, st);
-  mk.begin(5, st); hipLaunchKernelGGL(k_frame_tail, dim3(e.n_streams), dim3(256), 0, st, e, *t); mk.end(5, st);
+  mk.begin(5, st); DABX_LAUNCH_RING(e, k_frame_tail, dim3(e.n_streams), dim3(256), 0, st, e, *t); mk.end(5, st);
   if (e.exact_level && ss.tail_done) { DABX_HIP(hipEventRecord(ss.tail_done, st)); ss.tail_recorded = true; }
   DABX_HIP(hipGetLastError());
   return 0;
@@ -2170,30 +2249,43 @@ int launch_commit(const EngineDev &e, int stream, unsigned long long n, hipStrea
   return 0;
 }
 
-// host IQ formats -> cf32 ring (raw_reader.cpp:66-70, wav_reader.cpp:164)
-__global__ void k_convert_iq(const void *src, int fmt, float2 *ring, int ring_len, unsigned long long wr0, size_t n)
+// host IQ formats -> cf32 ring (raw_reader.cpp:66-70, wav_reader.cpp:164), or -- ring_fmt = fmt != 0 -- the codes as they are into a native ring
+__global__ void k_convert_iq(const void *src, int fmt, void *ring_base, int ring_fmt, int ring_len, unsigned long long wr0, size_t n)
 {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  const size_t o = (size_t)((wr0 + i) % (unsigned long long)ring_len);
+  if (ring_fmt == RING_S16) { reinterpret_cast<uint32_t *>(ring_base)[o] = reinterpret_cast<const uint32_t *>(src)[i]; return; }
+  if (ring_fmt == RING_U8) { reinterpret_cast<uint16_t *>(ring_base)[o] = reinterpret_cast<const uint16_t *>(src)[i]; return; }
+  float2 *ring = reinterpret_cast<float2 *>(ring_base);
   float2 v;
   if (fmt == 0) v = reinterpret_cast<const float2 *>(src)[i];
   else if (fmt == 1) { const short2 q = reinterpret_cast<const short2 *>(src)[i]; v = make_float2(q.x / 32768.0f, q.y / 32768.0f); }
   else { const uchar2 q = reinterpret_cast<const uchar2 *>(src)[i]; v = make_float2((q.x - 127.38f) / 128.0f, (q.y - 127.38f) / 128.0f); }
-  ring[(size_t)((wr0 + i) % (unsigned long long)ring_len)] = v;
+  ring[o] = v;
 }
-int launch_convert_iq(const void *src, int fmt, float2 *ring, int ring_len, unsigned long long wr0, size_t n, hipStream_t st)
+// ring: the stream's own ring (its first element); ring_fmt != RING_CF32 requires fmt == ring_fmt (checked by the callers, engine.cpp)
+int launch_convert_iq(const void *src, int fmt, void *ring, int ring_fmt, int ring_len, unsigned long long wr0, size_t n, hipStream_t st)
 {
-  hipLaunchKernelGGL(k_convert_iq, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, fmt, ring, ring_len, wr0, n);
+  hipLaunchKernelGGL(k_convert_iq, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, fmt, ring, ring_fmt, ring_len, wr0, n);
   DABX_HIP(hipGetLastError());
   return 0;
 }
 
 // bulk ingest (engine.cpp, dabx_ingest_commit): [S][n] samples of fmt in `src` -> every stream's ring behind its committed index
-__global__ __launch_bounds__(256) void k_ingest_convert(const void *src, int fmt, float2 *iq, int ring_len, const unsigned long long *wr, size_t n)
+__global__ __launch_bounds__(256) void k_ingest_convert(const void *src, int fmt, void *iq, int ring_fmt, int ring_len, const unsigned long long *wr, size_t n)
 {
   const int s = blockIdx.y;
   const unsigned long long wr0 = wr[s];
-  float2 *ring = iq + (size_t)s * ring_len;
+  if (ring_fmt != RING_CF32) {                               // a native ring (fmt == ring_fmt): the slab's codes are scattered as they are
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+      const size_t j = (size_t)s * n + i, o = (size_t)s * ring_len + (size_t)((wr0 + i) % (unsigned long long)ring_len);
+      if (ring_fmt == RING_S16) reinterpret_cast<uint32_t *>(iq)[o] = reinterpret_cast<const uint32_t *>(src)[j];
+      else reinterpret_cast<uint16_t *>(iq)[o] = reinterpret_cast<const uint16_t *>(src)[j];
+    }
+    return;
+  }
+  float2 *ring = reinterpret_cast<float2 *>(iq) + (size_t)s * ring_len;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     const size_t j = (size_t)s * n + i;
     float2 v;
@@ -2206,7 +2298,7 @@ __global__ __launch_bounds__(256) void k_ingest_convert(const void *src, int fmt
 int launch_ingest_convert(const EngineDev &e, const void *src, int fmt, size_t n, hipStream_t st)
 {
   const unsigned bx = (unsigned)std::min<size_t>((n + 255) / 256, 2048);
-  hipLaunchKernelGGL(k_ingest_convert, dim3(bx, e.n_streams), dim3(256), 0, st, src, fmt, e.iq, e.ring_len, e.wr, n);
+  hipLaunchKernelGGL(k_ingest_convert, dim3(bx, e.n_streams), dim3(256), 0, st, src, fmt, e.iq, e.ring_fmt, e.ring_len, e.wr, n);
   DABX_HIP(hipGetLastError());
   return 0;
 }

@@ -427,13 +427,27 @@ COUNTER_NAMES = ["frames", "samples", "fib_ok", "fib_total", "sync_lost", "strea
 TF = 196608
 
 
+class CreateExt(C.Structure):
+    """dabx_create_ext (include/dabx.h)."""
+    _fields_ = [("size", C.c_uint32), ("ring_format", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+RING_CF32, RING_S16, RING_U8 = 0, 1, 2
+RING_FORMATS = {"cf32": RING_CF32, "s16": RING_S16, "u8": RING_U8}
+
+
 class Engine:
-    """Stream-batched receiver (device-side DabProcessor::run for n_streams ensembles)."""
+    """Stream-batched receiver (device-side DabProcessor::run for n_streams ensembles).
+
+    ring_format: the IQ ring's element -- 0 / "cf32" (default), 1 / "s16", 2 / "u8" (DABX_RING_*): a native ring keeps the recording's own
+    codes, takes pushes of its own dtype only and decodes the very same bits."""
 
     def __init__(self, n_streams=1, ring_frames=4, max_subch=18, out_frames=4, fic_only=False, capture_soft=False,
                  sync_threshold=3.0, soft_bit_type=1, sync_strongest=False, viterbi_tie_mode=0, dc_iq_correction=0,
-                 schedule=0, msc_fast_min_jobs=0, msc_class_min_jobs=0, exact_level_tracker=False, acquire_mode=0):
+                 schedule=0, msc_fast_min_jobs=0, msc_class_min_jobs=0, exact_level_tracker=False, acquire_mode=0, ring_format=0):
         L = load()
+        if isinstance(ring_format, str):
+            ring_format = RING_FORMATS[ring_format.lower()]
         cfg = Config()
         L.dabx_default_config(C.byref(cfg))
         cfg.n_streams, cfg.ring_frames, cfg.max_subch, cfg.out_frames = n_streams, ring_frames, max_subch, out_frames
@@ -447,7 +461,11 @@ class Engine:
         self.cfg = cfg
         self.n_streams = n_streams
         self._h = C.c_void_p()
-        check(L.dabx_create(C.byref(cfg), C.byref(self._h)))
+        if int(ring_format) == RING_CF32:
+            check(L.dabx_create(C.byref(cfg), C.byref(self._h)))
+        else:
+            ext = CreateExt(size=C.sizeof(CreateExt), ring_format=int(ring_format))
+            check(L.dabx_create_ex(C.byref(cfg), C.byref(ext), C.byref(self._h)))
         self.subch = []
 
     def close(self):
@@ -491,6 +509,12 @@ class Engine:
         out = np.zeros(n, np.complex64)
         check(load().dabx_read_iq(self._h, stream, C.c_uint64(first), C.c_size_t(n), _p(out)))
         return out
+
+    def ring_format(self):
+        """(DABX_RING_* of the engine's IQ ring, bytes per sample): (0, 8), (1, 4) or (2, 2)."""
+        fmt, bps = C.c_int32(), C.c_int32()
+        check(load().dabx_get_ring_format(self._h, C.byref(fmt), C.byref(bps)))
+        return fmt.value, bps.value
 
     def ring_ptr(self, stream):
         p, cap = C.c_void_p(), C.c_size_t()

@@ -318,6 +318,34 @@ typedef struct {
 void dabx_default_config(dabx_config *cfg);
 int  dabx_create(const dabx_config *cfg, dabx_engine **out);
 void dabx_destroy(dabx_engine *e);
+/* The element of the IQ ring.  The reference's file devices turn the recording's codes into floats as they read them -- uint8 pairs
+ * ((x - 127.38) / 128, raw_reader.cpp:66-70), int16 pairs (x / 32768, wav_reader.cpp:164) -- and SampleReader sees cf32 only; so does a
+ * DABX_RING_CF32 engine (dabx_create), 8 bytes per sample.  A NATIVE ring keeps the codes themselves, 4 (S16) or 2 (U8) bytes per sample,
+ * and the kernels that read the ring apply the same map at the load: both maps are exact in float, every decoded bit, every statistic
+ * and dabx_read_iq are those of a cf32 engine fed the same codes.
+ *   DABX_RING_S16  interleaved I, Q int16 in the machine's byte order, value (float)c / 32768
+ *   DABX_RING_U8   interleaved I, Q uint8, value ((float)c - 127.38f) / 128.0f
+ * What a native ring refuses (DABX_E_ARG, nothing written, dabx_last_error names the format and the ring):
+ *   - dabx_push_iq / dabx_push_iq_async / dabx_ingest_open with a fmt other than the ring's (cf32 included): codes are copied, never
+ *     converted;
+ *   - file feeds and dabx_ingest_open_formats streams whose samples are not the ring's codes: any rate but 2.048 MS/s (the 1-ms
+ *     interpolation produces floats), reference_quirks, int24 / int32 / float / int8 containers, int16 with Bits != 16, and in a U8
+ *     ring the WAV family's uint8, whose map is (x - 128) / 128.  Accepted: RAW / UFF uint8 in a U8 ring; 16-bit int16 of either byte
+ *     order and either I/Q order in an S16 ring (stored in machine order, I first);
+ *   - dabx_config.dc_iq_correction != 0 at create: it rewrites samples in place and its output is not a code;
+ *   - a ring of 4 GiB or more per stream (ring_frames > 5461 for S16).
+ * The per-symbol handles (dabx_fic_*, dabx_msc_*) create cf32 engines. */
+enum { DABX_RING_CF32 = 0, DABX_RING_S16 = 1, DABX_RING_U8 = 2 };   /* numbered like dabx_push_iq's fmt */
+typedef struct {
+  uint32_t size;            /* sizeof(dabx_create_ext) of the caller; fields beyond it take their defaults */
+  int32_t  ring_format;     /* DABX_RING_* */
+  int32_t  reserved[6];     /* zero */
+} dabx_create_ext;
+/* dabx_create with extensions (dabx_config and DABX_ABI_VERSION stay as they are).  ext == NULL: exactly dabx_create.  DABX_E_ARG: ext->size
+ * smaller than the first two fields, an unknown ring_format, a native ring with dc_iq_correction. */
+int  dabx_create_ex(const dabx_config *cfg, const dabx_create_ext *ext, dabx_engine **out);
+/* The engine's ring element and its size: (0, 8), (1, 4) or (2, 2).  Either pointer may be NULL. */
+int  dabx_get_ring_format(dabx_engine *e, int32_t *ring_format, int32_t *bytes_per_sample);
 /* MscHandler::set_channel / stop_service equivalent for stream (or all streams when stream < 0): d[j] describes slot j
  * (kbps == 0: empty slot).  A slot whose description is unchanged keeps decoding without interruption, and so does one whose
  * sub-channel only moves to other capacity units (same SubChId, size, bit rate, protection: a multiplex reconfiguration; its
@@ -335,7 +363,8 @@ int  dabx_set_subchannels(dabx_engine *e, int stream, const dabx_subch_desc *d, 
 /* Host IQ -> device ring (IDeviceHandler::getSamples contract, common/device_handler_if.h:47-48).
  * fmt: 0 = cf32, 1 = int16 IQ (/32768, wav_reader.cpp:164), 2 = uint8 IQ ((x-127.38)/128, raw_reader.cpp:66-70).
  * Returns when the caller's buffer is free again; copy and conversion run on their own HIP stream next to frames still
- * being decoded (the receiver is drained only if the ring looks full). */
+ * being decoded (the receiver is drained only if the ring looks full).
+ * Native ring (dabx_create_ex): fmt must be the ring's format -- the codes are copied; any other fmt is DABX_E_ARG, nothing is written. */
 int  dabx_push_iq(dabx_engine *e, int stream, const void *iq, int fmt, size_t n_samples);   /* DABX_E_STATE: would overwrite unread samples */
 /* The same without waiting for the copy: the caller keeps `iq` alive and unchanged until dabx_push_wait returns.  Meant
  * for producers that cycle through a few page-locked buffers (hipHostMalloc, or their own memory passed once through
@@ -345,7 +374,8 @@ int  dabx_push_iq_async(dabx_engine *e, int stream, const void *iq, int fmt, siz
 int  dabx_push_wait(dabx_engine *e);
 int  dabx_host_register(void *p, size_t bytes);     /* hipHostRegister: page-lock a producer's buffer */
 int  dabx_host_unregister(void *p);
-/* Device-resident producers: ring base (cf32, capacity ring_frames*T_F) and commit of n new samples. */
+/* Device-resident producers: ring base (capacity ring_frames*T_F SAMPLES) and commit of n new samples.  The ring is in the engine's own
+ * element -- cf32 after dabx_create, int16 / uint8 pairs in a native ring: dabx_get_ring_format gives the bytes per sample. */
 int  dabx_iq_ring_dev(dabx_engine *e, int stream, void **ring, size_t *capacity_samples);
 int  dabx_commit_iq(dabx_engine *e, int stream /* <0: all */, size_t n_samples);
 /* Optional, for device-resident producers that want the level tracker's anchor kept (dabx_config.exact_level_tracker = 0): the library
@@ -356,7 +386,7 @@ int  dabx_commit_iq(dabx_engine *e, int stream /* <0: all */, size_t n_samples);
  * is filled once and only read again (periodic test signals). */
 int  dabx_announce_write(dabx_engine *e, int stream /* <0: all */, size_t n_samples);
 /* Host copy of ring samples [first, first + n) counted from the first sample ever committed (scopes, tests);
- * they must still be in the ring. */
+ * they must still be in the ring.  Always cf32: from a native ring, the values its codes stand for. */
 int  dabx_read_iq(dabx_engine *e, int stream, uint64_t first, size_t n, float *iq_out);
 /* Advance every stream by up to max_frames frames (bounded by available samples); returns the number of
  * batch steps executed.  Asynchronous on the engine's HIP stream unless sync != 0. */
@@ -580,7 +610,8 @@ long long dabx_delivery_slab_bytes(dabx_engine *e);
  * The raw_reader.cpp:66-70 / wav_reader.cpp:164 sample maps (fmt 2 / 1) run on the device: only 2 / 4 bytes per sample cross the link. */
 typedef struct {
   int32_t host_slabs;       /* page-locked input slabs, >= 1 (0 = default 2) */
-  int32_t fmt;              /* 0 cf32, 1 int16 IQ, 2 uint8 IQ: as dabx_push_iq */
+  int32_t fmt;              /* 0 cf32, 1 int16 IQ, 2 uint8 IQ: as dabx_push_iq (a native ring, dabx_create_ex: its own format only -- the commit
+                               scatters the slab's codes into the rings, no cf32 is written) */
   int32_t max_frames;       /* samples per stream a slab holds, in frames of T_F (0 = default DABX_CHUNK_FRAMES) */
   int32_t copy_engine;      /* as dabx_delivery_config.copy_engine */
   int32_t reserved[4];
@@ -592,7 +623,8 @@ int  dabx_ingest_open(dabx_engine *e, const dabx_ingest_config *cfg);
  * data_bytes are ignored; cfg->fmt too).  A slab is n_streams regions of dabx_ingest_pitch() bytes; the host puts the next payload bytes
  * of stream s at byte s * pitch and says how many (n_bytes[s]: whole samples -- a reader keeps an odd tail for its next slab --, 0 = the
  * recording has ended or is not ready).  Still ONE SDMA transfer per slab, TWO kernel launches per commit whatever the number of streams
- * and formats, and the results are byte-identical to n_streams dabx_feed_bytes calls (tests/test_gpu_ingest.py). */
+ * and formats, and the results are byte-identical to n_streams dabx_feed_bytes calls (tests/test_gpu_ingest.py).
+ * With a native ring (dabx_create_ex) every stream's format must be one whose samples ARE the ring's codes; DABX_E_ARG otherwise. */
 struct dabx_iq_format_s;                                                      /* "Recorded-IQ files" below */
 int  dabx_ingest_open_formats(dabx_engine *e, const dabx_ingest_config *cfg, const struct dabx_iq_format_s *formats /* [n_streams] */);
 long long dabx_ingest_pitch(dabx_engine *e);                                  /* bytes per stream region of a slab */

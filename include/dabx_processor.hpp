@@ -63,13 +63,18 @@ public:
   std::function<void(long long first_cif)> on_configuration_change;
   bool follow_reconfigurations = true;
 
-  explicit Processor(const Params &p = Params()) : params_(p)
+  // ring_format: DABX_RING_* -- a front end that delivers int16 or uint8 pairs keeps them as they are in the ring (dabx_create_ex); it then
+  // hands over that type only.  Default: cf32, as before.
+  explicit Processor(const Params &p = Params(), int ring_format = DABX_RING_CF32) : params_(p)
   {
     dabx_config cfg;
     dabx_default_config(&cfg);
     cfg.n_streams = 1; cfg.ring_frames = p.ring_frames; cfg.max_subch = p.max_services; cfg.out_frames = p.fib_ring_frames;
     cfg.sync_threshold = p.threshold; cfg.soft_bit_type = p.soft_bit_type; cfg.sync_strongest = p.sync_on_strongest_peak ? 1 : 0;
-    if (dabx_create(&cfg, &eng_) < 0) throw std::runtime_error(std::string("dabx_create: ") + dabx_last_error());
+    dabx_create_ext ext{};
+    ext.size = sizeof(ext); ext.ring_format = ring_format;
+    if ((ring_format == DABX_RING_CF32 ? dabx_create(&cfg, &eng_) : dabx_create_ex(&cfg, &ext, &eng_)) < 0)
+      throw std::runtime_error(std::string("dabx_create: ") + dabx_last_error());
     slots_.assign((size_t)p.max_services, dabx_subch_desc{});
     delivered_.assign((size_t)p.max_services, 0);
     sf_delivered_.assign((size_t)p.max_services, 0);
