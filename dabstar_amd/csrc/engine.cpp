@@ -24,7 +24,6 @@ int launch_front_step(const EngineDev &e, EngineStreams &ss, Marker &mk, bool as
 int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineStreams &ss, Marker &mk, const DeliverDev *dv = nullptr,
                      hipStream_t *tail = nullptr);
 int launch_deliver_front(const EngineDev &e, const DeliverDev &dv, hipStream_t st);
-int launch_ingest_convert(const EngineDev &e, const void *src, int fmt, size_t n, hipStream_t st);
 void dabx_internal_fibdec_skip(dabx_fibdec *d, long long n_fibs);     // fib.cpp: FIBs the decoder never saw (they had left the ring)
 int launch_dciq(const EngineDev &e, int mode, hipStream_t st);
 int launch_level_exact(const EngineDev &e, hipStream_t st);
@@ -33,7 +32,6 @@ int launch_msc_inject(const EngineDev &e, int stream, const int16_t *soft_dev, i
 int launch_msc_advance(const EngineDev &e, const int32_t *counts_dev, hipStream_t st);
 extern const char *const kStepKernelNames[11];
 int launch_commit(const EngineDev &e, int stream, unsigned long long n, hipStream_t st);
-int launch_convert_iq(const void *src, int fmt, void *ring, int ring_fmt, int ring_len, unsigned long long wr0, size_t n, hipStream_t st);
 int launch_fic_only(const EngineDev &e, hipStream_t st, int first, int count);
 int launch_i16_to_sym(const int16_t *soft, uint8_t *sym, size_t n, hipStream_t st);
 }  // namespace dabx
@@ -74,26 +72,30 @@ struct Delivery {
   dabx_chunk_header hdr{};
 };
 
-// Bulk ingest (include/dabx.h "Bulk ingest"): page-locked input slabs, their device twins, one SDMA transfer per slab.
+// Bulk ingest (include/dabx.h "Bulk ingest"): page-locked input slabs, their device twins, one SDMA transfer per slab.  Both forms are S
+// jobs for iqfile.hip's table writer: dabx_ingest_open gives every stream the same decode and a dense slab, dabx_ingest_open_formats
+// every stream its own container, rate, length and region.
 struct Ingest {
   bool open = false;
-  int fmt = 0, copy_engine = 0, max_frames = 0;
+  int copy_engine = 0, max_frames = 0;
   size_t capacity = 0;                           // bytes per slab
-  struct Slab { uint8_t *host = nullptr, *dev = nullptr; uint64_t sig = 0; size_t n = 0; bool in_flight = false; };
+  struct Slab {
+    uint8_t *host = nullptr, *dev = nullptr; uint64_t sig = 0; bool in_flight = false;
+    size_t bytes = 0, pitch = 0;                 // what was submitted: bytes transferred, bytes from one stream's payload to the next
+    std::vector<size_t> n_bytes;                 // [S] payload bytes per stream
+    // the commit's table, [S] jobs and behind them [S] sample counts: page-locked staging / device.  One per slab: dabx_ingest_submit
+    // drains the ingest stream, so by the slab's next commit the upload of this one has left the staging copy
+    IqJob *jobs_host = nullptr, *jobs_dev = nullptr;      // (in Ingest::tables_host / tables_dev)
+    hipEvent_t counts_read = nullptr;            // per-stream form: the commit kernel that reads the device table's counts has run (front-end stream)
+  };
   std::vector<Slab> slabs;
   Sdma sdma;
   hipStream_t cs = nullptr;                      // copy_engine 1 only
-  hipEvent_t committed = nullptr;                // the previous ingest commit has run on the front-end stream (the converter reads the committed indices)
-  bool committed_recorded = false;
-  hipEvent_t front = nullptr;                    // where the front-end stream stood when a conversion was queued (commits of other entry points in between)
-  // general form (dabx_ingest_open_formats): every stream its own container, rate and length
-  bool general = false;
-  size_t pitch = 0;                              // bytes per stream region of a slab
+  uint8_t *tables_host = nullptr, *tables_dev = nullptr;
+  bool general = false;                          // dabx_ingest_open_formats
+  size_t pitch = 0;                              // ... bytes per stream region of a slab
   std::vector<IqDecode> dec;                     // [S]
   std::vector<int> M, tab, carry_n;              // [S] input samples per ms (0 = 2.048 MS/s), table index, samples carried between slabs
-  std::vector<std::vector<size_t>> n_bytes;      // [slab][S] payload bytes submitted
-  IngestJob *jobs_host = nullptr, *jobs_dev = nullptr;     // [S] page-locked staging / device
-  unsigned *counts_host = nullptr, *counts_dev = nullptr;  // [S] samples committed per stream by this commit
   float2 *work = nullptr, *carry = nullptr;
   size_t work_pitch = 0, carry_pitch = 0;
   int16_t *tab_int = nullptr; float *tab_frac = nullptr;
@@ -551,21 +553,16 @@ static void ingest_free(dabx_engine *e)
 {
   Ingest &I = e->ing;
   for (auto &sl : I.slabs) {
-    if (sl.in_flight && I.copy_engine == 0) (void)sdma_wait(sl.sig, 0);
+    if (sl.in_flight && sl.bytes && I.copy_engine == 0) (void)sdma_wait(sl.sig, 0);
     if (sl.host) (void)hipHostFree(sl.host);
     if (sl.dev) (void)hipFree(sl.dev);
+    if (sl.counts_read) (void)hipEventDestroy(sl.counts_read);
     sdma_signal_destroy(sl.sig);
   }
-  I.slabs.clear();
   if (I.cs) { (void)hipStreamSynchronize(I.cs); (void)hipStreamDestroy(I.cs); }
-  if (I.committed) (void)hipEventDestroy(I.committed);
-  if (I.front) (void)hipEventDestroy(I.front);
-  for (void *q : {(void *)I.jobs_dev, (void *)I.counts_dev, (void *)I.work, (void *)I.carry, (void *)I.tab_int, (void *)I.tab_frac}) if (q) (void)hipFree(q);
-  if (I.jobs_host) (void)hipHostFree(I.jobs_host);
-  if (I.counts_host) (void)hipHostFree(I.counts_host);
-  I.jobs_host = nullptr; I.jobs_dev = nullptr; I.counts_host = nullptr; I.counts_dev = nullptr; I.work = I.carry = nullptr; I.tab_int = nullptr; I.tab_frac = nullptr;
-  I.general = false; I.dec.clear(); I.M.clear(); I.tab.clear(); I.carry_n.clear(); I.n_bytes.clear();
-  I.cs = nullptr; I.committed = nullptr; I.front = nullptr; I.committed_recorded = false; I.open = false; I.capacity = 0;
+  for (void *q : {(void *)I.tables_dev, (void *)I.work, (void *)I.carry, (void *)I.tab_int, (void *)I.tab_frac}) if (q) (void)hipFree(q);
+  if (I.tables_host) (void)hipHostFree(I.tables_host);
+  I = Ingest{};
 }
 
 static int need_device_e()
@@ -1031,72 +1028,56 @@ static int push_room(dabx_engine *e, int stream, size_t n, const char *who)
   return 0;
 }
 
-int dabx_push_iq(dabx_engine *e, int stream, const void *iq, int fmt, size_t n)
+// Both pushes: copy + conversion on an ingest stream, next to whatever the receiver streams are computing: the samples land beyond the
+// committed write index, which no queued kernel reads; only the commit is ordered into the front-end stream.
+//   synchronous   the engine's one staging buffer (grown on demand), and the call waits: the caller's buffer is free again.
+//   async         a small pool of device staging slots, each guarded by the event of its last conversion kernel, on two streams in turn
+static int push_impl(dabx_engine *e, int stream, const void *iq, int fmt, size_t n, bool async, const char *who)
 {
   if (!e || stream < 0 || stream >= e->dev.n_streams || !iq || fmt < 0 || fmt > 2 || n > (size_t)e->dev.ring_len) {
-    set_error("dabx_push_iq: bad argument");
+    set_error("%s: bad argument", who);
     return DABX_E_ARG;
   }
-  if (int rc = ring_takes(e, fmt, "dabx_push_iq")) return rc;
+  if (int rc = ring_takes(e, fmt, who)) return rc;
   if (n == 0) return 0;
   if (int rc = use_device(e)) return rc;
-  if (int rc = push_room(e, stream, n, "dabx_push_iq")) return rc;
-  static const int bps[3] = {8, 4, 2};
-  const size_t bytes = n * bps[fmt];
-  if (bytes > e->stage_cap) {                   // one staging buffer per engine, grown on demand
-    if (e->stage) DABX_HIP(hipFree(e->stage));
-    e->stage = nullptr; e->stage_cap = 0;
-    DABX_HIP(hipMalloc(&e->stage, bytes));
-    e->stage_cap = bytes;
+  if (int rc = push_room(e, stream, n, who)) return rc;
+  IqJob j{};
+  if (int rc = iq_push_decode(fmt, e->dev.ring_fmt, &j.dec)) return rc;
+  const size_t bytes = n * (size_t)(2 * j.dec.bytes);
+  void **buf = &e->stage; size_t *cap = &e->stage_cap; hipEvent_t *done = &e->ingest_done; hipStream_t st = e->ingest;
+  if (async) {
+    const int k = (int)(e->async_pushes++ % dabx_engine::ASYNC_SLOTS);
+    buf = &e->aslot[k]; cap = &e->aslot_cap[k]; done = &e->aslot_done[k];
+    if (!*done) DABX_HIP(hipEventCreateWithFlags(done, hipEventDisableTiming));
+    else DABX_HIP(hipEventSynchronize(*done));                         // the slot's previous conversion has read it
+    if (!e->ingest2) DABX_HIP(hipStreamCreateWithFlags(&e->ingest2, hipStreamNonBlocking));
+    if (k & 1) st = e->ingest2;
   }
-  // copy + conversion on the ingest stream, next to whatever the receiver streams are computing: the samples land
-  // beyond the committed write index, which no queued kernel reads; only the commit is ordered into the front-end stream
+  if (bytes > *cap) {
+    if (*buf) DABX_HIP(hipFree(*buf));
+    *buf = nullptr; *cap = 0;
+    DABX_HIP(hipMalloc(buf, bytes));
+    *cap = bytes;
+  }
   announce_write(e, stream, e->wr_host[stream] + n);
-  DABX_HIP(hipMemcpyAsync(e->stage, iq, bytes, hipMemcpyHostToDevice, e->ingest));
-  int rc = launch_convert_iq(e->stage, fmt, e->ring_of(stream), e->dev.ring_fmt, e->dev.ring_len, e->wr_host[stream], n, e->ingest);
-  if (rc) return rc;
-  DABX_HIP(hipEventRecord(e->ingest_done, e->ingest));
-  DABX_HIP(hipStreamWaitEvent(e->stream, e->ingest_done, 0));
-  rc = commit_impl(e, stream, n);
-  DABX_HIP(hipStreamSynchronize(e->ingest));   // the caller's buffer and the staging buffer are free again
+  DABX_HIP(hipMemcpyAsync(*buf, iq, bytes, hipMemcpyHostToDevice, st));
+  IqIo io{};
+  io.src = static_cast<const uint8_t *>(*buf); io.dst = e->ring_of(stream); io.dst_len = e->dev.ring_len;
+  j.n = (unsigned)n; j.dst0 = e->wr_host[stream];
+  if (int rc = launch_iq_job(io, j, st)) return rc;
+  DABX_HIP(hipEventRecord(*done, st));
+  DABX_HIP(hipStreamWaitEvent(e->stream, *done, 0));                   // the commit (and every frame after it) sees the samples
+  const int rc = commit_impl(e, stream, n);
+  if (!async) DABX_HIP(hipStreamSynchronize(st));                      // the caller's buffer and the staging buffer are free again
   return rc;
 }
-
+int dabx_push_iq(dabx_engine *e, int stream, const void *iq, int fmt, size_t n) { return push_impl(e, stream, iq, fmt, n, false, "dabx_push_iq"); }
 // The same without waiting for the copy: for producers that keep their buffers alive and unchanged until dabx_push_wait --
 // a file reader cycling through a few pinned buffers (hipHostMalloc / dabx_host_register).  From pinned memory the copies
 // of consecutive calls run back to back as DMA at PCIe rate while the host already issues the next ones; from pageable
 // memory the HIP runtime stages the copy itself and the call degrades gracefully to the synchronous behaviour.
-int dabx_push_iq_async(dabx_engine *e, int stream, const void *iq, int fmt, size_t n)
-{
-  if (!e || stream < 0 || stream >= e->dev.n_streams || !iq || fmt < 0 || fmt > 2 || n > (size_t)e->dev.ring_len) {
-    set_error("dabx_push_iq_async: bad argument");
-    return DABX_E_ARG;
-  }
-  if (int rc = ring_takes(e, fmt, "dabx_push_iq_async")) return rc;
-  if (n == 0) return 0;
-  if (int rc = use_device(e)) return rc;
-  if (int rc = push_room(e, stream, n, "dabx_push_iq_async")) return rc;
-  static const int bps[3] = {8, 4, 2};
-  const size_t bytes = n * bps[fmt];
-  const int k = (int)(e->async_pushes++ % dabx_engine::ASYNC_SLOTS);
-  if (!e->aslot_done[k]) DABX_HIP(hipEventCreateWithFlags(&e->aslot_done[k], hipEventDisableTiming));
-  else DABX_HIP(hipEventSynchronize(e->aslot_done[k]));              // the slot's previous conversion has read it
-  if (bytes > e->aslot_cap[k]) {
-    if (e->aslot[k]) DABX_HIP(hipFree(e->aslot[k]));
-    e->aslot[k] = nullptr; e->aslot_cap[k] = 0;
-    DABX_HIP(hipMalloc(&e->aslot[k], bytes));
-    e->aslot_cap[k] = bytes;
-  }
-  if (!e->ingest2) DABX_HIP(hipStreamCreateWithFlags(&e->ingest2, hipStreamNonBlocking));
-  hipStream_t ing = (k & 1) ? e->ingest2 : e->ingest;
-  announce_write(e, stream, e->wr_host[stream] + n);
-  DABX_HIP(hipMemcpyAsync(e->aslot[k], iq, bytes, hipMemcpyHostToDevice, ing));
-  int rc = launch_convert_iq(e->aslot[k], fmt, e->ring_of(stream), e->dev.ring_fmt, e->dev.ring_len, e->wr_host[stream], n, ing);
-  if (rc) return rc;
-  DABX_HIP(hipEventRecord(e->aslot_done[k], ing));
-  DABX_HIP(hipStreamWaitEvent(e->stream, e->aslot_done[k], 0));      // the commit (and every frame after it) sees the samples
-  return commit_impl(e, stream, n);
-}
+int dabx_push_iq_async(dabx_engine *e, int stream, const void *iq, int fmt, size_t n) { return push_impl(e, stream, iq, fmt, n, true, "dabx_push_iq_async"); }
 
 int dabx_push_wait(dabx_engine *e)
 {
@@ -1611,20 +1592,17 @@ static int ingest_open_impl(dabx_engine *e, const dabx_ingest_config *cfg, const
   if (!formats) { if (int rc = ring_takes(e, cfg ? cfg->fmt : 0, "dabx_ingest_open")) return rc; }
   if (int rc = use_device(e)) return rc;
   Ingest &I = e->ing;
-  I.fmt = cfg ? cfg->fmt : 0;
   I.copy_engine = cfg ? cfg->copy_engine : 0;
   I.max_frames = cfg && cfg->max_frames ? cfg->max_frames : DL_FRAMES;
   if ((long long)I.max_frames * TF > e->dev.ring_len) { set_error("dabx_ingest_open: a slab of %d frames does not fit the ring (%d frames)", I.max_frames, e->dev.ring_len / TF); return DABX_E_ARG; }
-  static const int bps[3] = {8, 4, 2};
-  I.capacity = (size_t)e->dev.n_streams * I.max_frames * TF * bps[I.fmt];
   int rc;
   const int S_ = e->dev.n_streams;
+  I.dec.assign((size_t)S_, IqDecode{}); I.M.assign((size_t)S_, 0); I.tab.assign((size_t)S_, 0); I.carry_n.assign((size_t)S_, 0);
   std::vector<int16_t> tabs_i; std::vector<float> tabs_f;
   int m_max = 0;
   if (formats) {
     // every stream's own recording: the region of a slab that holds max_frames frames' worth of ITS payload (+ one read block) sets the pitch
     I.general = true;
-    I.dec.assign((size_t)S_, IqDecode{}); I.M.assign((size_t)S_, 0); I.tab.assign((size_t)S_, 0); I.carry_n.assign((size_t)S_, 0);
     std::map<std::pair<int, int>, int> tab_of;
     size_t need = 0;
     for (int s = 0; s < S_; s++) {
@@ -1648,19 +1626,17 @@ static int ingest_open_impl(dabx_engine *e, const dabx_ingest_config *cfg, const
     }
     I.pitch = align_up(need, 256);
     I.capacity = I.pitch * (size_t)S_;
+  } else {
+    // every stream the same push format: a slab is dense, [S][n] samples
+    if ((rc = iq_push_decode(cfg ? cfg->fmt : 0, e->dev.ring_fmt, &I.dec[0]))) { ingest_free(e); return rc; }
+    I.dec.assign((size_t)S_, I.dec[0]);
+    I.capacity = (size_t)S_ * I.max_frames * TF * (size_t)(2 * I.dec[0].bytes);
   }
   if (I.copy_engine == 0 && (rc = sdma_open(e->device, &I.sdma))) { ingest_free(e); return rc; }      // (the per-stream tables above go with it)
 #define H(x) do { hipError_t err__ = (x); if (err__ != hipSuccess) { set_error("HIP error %d (%s) at %s:%d", (int)err__, hipGetErrorString(err__), __FILE__, __LINE__); ingest_free(e); return DABX_E_HIP; } } while (0)
   if (I.copy_engine == 1) H(hipStreamCreateWithFlags(&I.cs, hipStreamNonBlocking));
-  H(hipEventCreateWithFlags(&I.committed, hipEventDisableTiming | hipEventReleaseToDevice));
-  H(hipEventCreateWithFlags(&I.front, hipEventDisableTiming | hipEventReleaseToDevice));
   I.slabs.resize((size_t)(cfg && cfg->host_slabs ? cfg->host_slabs : 2));
   if (I.general) {
-    I.n_bytes.assign(I.slabs.size(), std::vector<size_t>((size_t)S_, 0));
-    H(hipHostMalloc((void **)&I.jobs_host, sizeof(IngestJob) * (size_t)S_, hipHostMallocDefault));
-    H(hipHostMalloc((void **)&I.counts_host, sizeof(unsigned) * (size_t)S_, hipHostMallocDefault));
-    H(hipMalloc((void **)&I.jobs_dev, sizeof(IngestJob) * (size_t)S_));
-    H(hipMalloc((void **)&I.counts_dev, sizeof(unsigned) * (size_t)S_));
     if (m_max) {
       // [carry | decoded samples of one slab] per resampling stream, and the carry between slabs (<= M + 1 samples)
       size_t max_in = 0;
@@ -1679,7 +1655,16 @@ static int ingest_open_impl(dabx_engine *e, const dabx_ingest_config *cfg, const
   for (auto &sl : I.slabs) {
     H(hipHostMalloc((void **)&sl.host, I.capacity, hipHostMallocDefault));
     H(hipMalloc((void **)&sl.dev, I.capacity));
+    if (I.general) H(hipEventCreateWithFlags(&sl.counts_read, hipEventDisableTiming));
     if (I.copy_engine == 0 && (rc = sdma_signal_create(&sl.sig))) { ingest_free(e); return rc; }
+  }
+  // (the tables behind the slabs: the slabs' own allocations follow each other as they always have)
+  const size_t table = (sizeof(IqJob) + sizeof(unsigned)) * (size_t)S_;
+  H(hipHostMalloc((void **)&I.tables_host, table * I.slabs.size(), hipHostMallocDefault));
+  H(hipMalloc((void **)&I.tables_dev, table * I.slabs.size()));
+  for (size_t k = 0; k < I.slabs.size(); k++) {
+    I.slabs[k].jobs_host = reinterpret_cast<IqJob *>(I.tables_host + k * table);
+    I.slabs[k].jobs_dev = reinterpret_cast<IqJob *>(I.tables_dev + k * table);
   }
 #undef H
   if (I.copy_engine == 0 && I.capacity >= ((size_t)16 << 20) && (rc = sdma_calibrate(I.sdma, I.slabs[0].host, I.slabs[0].dev, false, I.slabs[0].sig, nullptr))) {
@@ -1708,6 +1693,27 @@ int dabx_ingest_slab(dabx_engine *e, int k, void **host, size_t *capacity_bytes)
   return 0;
 }
 
+// slab k takes n_bytes[s] payload bytes per stream, `pitch` bytes apart: ONE transfer, up to the last byte any stream uses (the regions of
+// streams that end early travel as they are)
+static int ingest_submit(dabx_engine *e, int k, const std::vector<size_t> &n_bytes, size_t pitch, const char *who)
+{
+  Ingest &I = e->ing;
+  if (int rc = use_device(e)) return rc;
+  Ingest::Slab &sl = I.slabs[(size_t)k];
+  if (sl.in_flight) { set_error("%s: slab %d has a transfer that was not committed", who, k); return DABX_E_STATE; }
+  size_t last = 0;
+  for (size_t s = 0; s < n_bytes.size(); s++) if (n_bytes[s]) last = s * pitch + n_bytes[s];
+  // (the device twin is free: its converter ran on the ingest stream before the commit that cleared in_flight was queued, and a slab is
+  //  only reused after its commit -- by then, with two slabs, a whole chunk later)
+  DABX_HIP(hipStreamSynchronize(e->ingest));
+  if (last) {
+    if (I.copy_engine == 0) { if (int rc = sdma_copy(I.sdma, sl.dev, sl.host, last, false, sl.sig)) return rc; }
+    else DABX_HIP(hipMemcpyAsync(sl.dev, sl.host, last, hipMemcpyHostToDevice, I.cs));
+  }
+  sl.n_bytes = n_bytes; sl.pitch = pitch; sl.bytes = last; sl.in_flight = true;
+  return 0;
+}
+
 int dabx_ingest_submit(dabx_engine *e, int k, size_t n)
 {
   if (!e) return DABX_E_ARG;
@@ -1715,18 +1721,8 @@ int dabx_ingest_submit(dabx_engine *e, int k, size_t n)
   if (!I.open || k < 0 || k >= (int)I.slabs.size()) { set_error("dabx_ingest_submit: no such slab"); return DABX_E_STATE; }
   if (I.general) { set_error("dabx_ingest_submit: this ingest was opened with per-stream formats (dabx_ingest_submit_bytes)"); return DABX_E_STATE; }
   if (n == 0 || n > (size_t)I.max_frames * TF) { set_error("dabx_ingest_submit: %zu samples per stream, the slabs hold %d frames", n, I.max_frames); return DABX_E_ARG; }
-  if (int rc = use_device(e)) return rc;
-  Ingest::Slab &sl = I.slabs[(size_t)k];
-  if (sl.in_flight) { set_error("dabx_ingest_submit: slab %d has a transfer that was not committed", k); return DABX_E_STATE; }
-  static const int bps[3] = {8, 4, 2};
-  const size_t bytes = (size_t)e->dev.n_streams * n * bps[I.fmt];
-  // (the device twin is free: its converter ran on the ingest stream before the commit that cleared in_flight was queued, and a slab is
-  //  only reused after its commit -- by then, with two slabs, a whole chunk later)
-  DABX_HIP(hipStreamSynchronize(e->ingest));
-  if (I.copy_engine == 0) { if (int rc = sdma_copy(I.sdma, sl.dev, sl.host, bytes, false, sl.sig)) return rc; }
-  else DABX_HIP(hipMemcpyAsync(sl.dev, sl.host, bytes, hipMemcpyHostToDevice, I.cs));
-  sl.n = n; sl.in_flight = true;
-  return 0;
+  const size_t bytes = n * (size_t)(2 * I.dec[0].bytes);
+  return ingest_submit(e, k, std::vector<size_t>((size_t)e->dev.n_streams, bytes), bytes, "dabx_ingest_submit");
 }
 
 int dabx_ingest_submit_bytes(dabx_engine *e, int k, const size_t *n_bytes)
@@ -1734,10 +1730,6 @@ int dabx_ingest_submit_bytes(dabx_engine *e, int k, const size_t *n_bytes)
   if (!e || !n_bytes) return DABX_E_ARG;
   Ingest &I = e->ing;
   if (!I.open || !I.general || k < 0 || k >= (int)I.slabs.size()) { set_error("dabx_ingest_submit_bytes: no such slab of an ingest opened with dabx_ingest_open_formats"); return DABX_E_STATE; }
-  if (int rc = use_device(e)) return rc;
-  Ingest::Slab &sl = I.slabs[(size_t)k];
-  if (sl.in_flight) { set_error("dabx_ingest_submit_bytes: slab %d has a transfer that was not committed", k); return DABX_E_STATE; }
-  size_t last = 0;
   for (int s = 0; s < e->dev.n_streams; s++) {
     const IqDecode &d = I.dec[(size_t)s];
     const size_t unit = (size_t)(2 * d.bytes) * (d.quirk_block ? (size_t)d.quirk_block : 1);
@@ -1746,77 +1738,11 @@ int dabx_ingest_submit_bytes(dabx_engine *e, int k, const size_t *n_bytes)
                 d.quirk_block ? " and whole 1-ms read blocks" : "");
       return DABX_E_ARG;
     }
-    if (n_bytes[s]) last = (size_t)s * I.pitch + n_bytes[s];
   }
-  I.n_bytes[(size_t)k].assign(n_bytes, n_bytes + e->dev.n_streams);
-  DABX_HIP(hipStreamSynchronize(e->ingest));
-  // ONE transfer, up to the last byte any stream uses (the regions of streams that end early travel as they are)
-  if (last) {
-    if (I.copy_engine == 0) { if (int rc = sdma_copy(I.sdma, sl.dev, sl.host, last, false, sl.sig)) return rc; }
-    else DABX_HIP(hipMemcpyAsync(sl.dev, sl.host, last, hipMemcpyHostToDevice, I.cs));
-  }
-  sl.n = last; sl.in_flight = true;
-  return 0;
+  return ingest_submit(e, k, std::vector<size_t>(n_bytes, n_bytes + e->dev.n_streams), I.pitch, "dabx_ingest_submit_bytes");
 }
 
-// general form: per stream its own decode, resampling state and sample count; two launches for all streams together
-static int ingest_commit_general(dabx_engine *e, int k)
-{
-  Ingest &I = e->ing;
-  Ingest::Slab &sl = I.slabs[(size_t)k];
-  const int S = e->dev.n_streams;
-  const std::vector<size_t> &nb = I.n_bytes[(size_t)k];
-  std::vector<IngestJob> jobs((size_t)S);
-  unsigned max_n = 0, max_out = 0;
-  // the page-locked staging records (jobs_host, counts_host) are written below: the previous commit's asynchronous copies of them -- two
-  // commits may follow each other without a submit in between -- have to be through first
-  DABX_HIP(hipStreamSynchronize(e->ingest));
-  for (int s = 0; s < S; s++) {
-    IngestJob &j = jobs[(size_t)s];
-    j = IngestJob{};
-    j.dec = I.dec[(size_t)s];
-    j.src_off = (unsigned long long)s * I.pitch;
-    j.n = (unsigned)(nb[(size_t)s] / (size_t)(2 * j.dec.bytes));
-    j.M = (unsigned)I.M[(size_t)s]; j.tab = (unsigned)I.tab[(size_t)s]; j.carry_n = (unsigned)I.carry_n[(size_t)s];
-    unsigned produced = j.n;
-    if (j.M && j.n) {                                  // feed_push's bookkeeping (iqfile.cpp): block c needs V[c M .. c M + M]
-      const unsigned len = j.carry_n + j.n;
-      j.blocks = len >= j.M + 1 ? (len - 1) / j.M : 0;
-      j.keep = len - j.blocks * j.M;
-      produced = j.blocks * 2048;
-      max_out = std::max(max_out, produced);
-    }
-    I.counts_host[s] = j.n ? produced : 0;
-    max_n = std::max(max_n, j.n);
-    if (int rc = push_room(e, s, I.counts_host[s], "dabx_ingest_commit")) return rc;   // (the transfer stays pending: process, then commit again)
-  }
-  if (sl.n) {
-    if (I.copy_engine == 0) { if (int rc = sdma_wait(sl.sig, 0)) return rc; }
-    else DABX_HIP(hipStreamSynchronize(I.cs));
-  }
-  for (int s = 0; s < S; s++) {
-    jobs[(size_t)s].dst0 = e->wr_host[s];               // the host's own count of committed samples: no device-side index is read
-    announce_write(e, s, e->wr_host[s] + I.counts_host[s]);
-  }
-  memcpy(I.jobs_host, jobs.data(), sizeof(IngestJob) * (size_t)S);
-  DABX_HIP(hipMemcpyAsync(I.jobs_dev, I.jobs_host, sizeof(IngestJob) * (size_t)S, hipMemcpyHostToDevice, e->ingest));
-  DABX_HIP(hipMemcpyAsync(I.counts_dev, I.counts_host, sizeof(unsigned) * (size_t)S, hipMemcpyHostToDevice, e->ingest));
-  IngestMulti m{};
-  m.slab = sl.dev; m.jobs = I.jobs_dev; m.iq = static_cast<float2 *>(e->dev.iq); m.ring_len = e->dev.ring_len; m.work = I.work; m.work_pitch = I.work_pitch;
-  m.carry = I.carry; m.carry_pitch = I.carry_pitch; m.tab_int = I.tab_int; m.tab_frac = I.tab_frac;
-  if (int rc = launch_ingest_multi(m, S, max_n, max_out, e->ingest)) return rc;
-  DABX_HIP(hipEventRecord(e->ingest_done, e->ingest));
-  DABX_HIP(hipStreamWaitEvent(e->stream, e->ingest_done, 0));
-  for (int s = 0; s < S; s++) {
-    e->wr_host[s] += I.counts_host[s];
-    if (jobs[(size_t)s].M && jobs[(size_t)s].n) I.carry_n[(size_t)s] = (int)jobs[(size_t)s].keep;
-  }
-  if (int rc = launch_commit_counts(e->dev.wr, I.counts_dev, S, e->stream)) return rc;
-  if (e->cfg.dc_iq_correction) { if (int rc = launch_dciq(e->dev, e->cfg.dc_iq_correction, e->stream)) return rc; }
-  sl.in_flight = false;
-  return 0;
-}
-
+// One job per stream -- its decode, its resampling state, its sample count -- and at most two launches for all streams together
 int dabx_ingest_commit(dabx_engine *e, int k)
 {
   if (!e) return DABX_E_ARG;
@@ -1825,24 +1751,52 @@ int dabx_ingest_commit(dabx_engine *e, int k)
   if (int rc = use_device(e)) return rc;
   Ingest::Slab &sl = I.slabs[(size_t)k];
   if (!sl.in_flight) { set_error("dabx_ingest_commit: slab %d was not submitted", k); return DABX_E_STATE; }
-  if (I.general) return ingest_commit_general(e, k);
-  for (int s = 0; s < e->dev.n_streams; s++)
-    if (int rc = push_room(e, s, sl.n, "dabx_ingest_commit")) return rc;          // (the transfer stays pending: process, then commit again)
-  if (I.copy_engine == 0) { if (int rc = sdma_wait(sl.sig, 0)) return rc; }
-  else DABX_HIP(hipStreamSynchronize(I.cs));
-  for (int s = 0; s < e->dev.n_streams; s++) announce_write(e, s, e->wr_host[s] + sl.n);
-  // the converter reads the committed indices on the device: behind EVERYTHING the front-end stream has been given so far -- the previous
-  // ingest commit, and a dabx_push_iq / dabx_commit_iq of another entry point in between (their index updates run on that stream too)
-  DABX_HIP(hipEventRecord(I.front, e->stream));
-  DABX_HIP(hipStreamWaitEvent(e->ingest, I.front, 0));
-  if (int rc = launch_ingest_convert(e->dev, sl.dev, I.fmt, sl.n, e->ingest)) return rc;
+  const int S = e->dev.n_streams;
+  IqJob *jobs = sl.jobs_host;
+  unsigned *counts = reinterpret_cast<unsigned *>(jobs + S);
+  unsigned max_n = 0, max_out = 0;
+  bool resamples = false;
+  for (int s = 0; s < S; s++) {
+    IqJob &j = jobs[s];
+    j = IqJob{};
+    j.dec = I.dec[(size_t)s];
+    j.src_off = (unsigned long long)s * sl.pitch;
+    j.n = (unsigned)(sl.n_bytes[(size_t)s] / (size_t)(2 * j.dec.bytes));
+    j.M = (unsigned)I.M[(size_t)s]; j.tab = (unsigned)I.tab[(size_t)s]; j.carry_n = (unsigned)I.carry_n[(size_t)s];
+    counts[s] = iq_plan(&j);
+    max_n = std::max(max_n, j.n);
+    if (j.M && j.n) { resamples = true; max_out = std::max(max_out, counts[s]); }
+    if (int rc = push_room(e, s, counts[s], "dabx_ingest_commit")) return rc;   // (the transfer stays pending: process, then commit again)
+  }
+  if (sl.bytes) {
+    if (I.copy_engine == 0) { if (int rc = sdma_wait(sl.sig, 0)) return rc; }
+    else DABX_HIP(hipStreamSynchronize(I.cs));
+  }
+  for (int s = 0; s < S; s++) {
+    jobs[s].dst0 = e->wr_host[s];                       // the host's own count of committed samples: no device-side index is read
+    announce_write(e, s, e->wr_host[s] + counts[s]);
+  }
+  // The samples land beyond the committed indices, push_room has made the room: the writer waits for nothing on the front-end stream.
+  // The device table does, in the per-stream form: k_commit_counts of this slab's PREVIOUS commit reads its counts on the front-end
+  // stream, possibly still queued there behind steps.  counts_read was recorded right behind that kernel, and the upload below is
+  // ordered behind counts_read in the ingest stream: the table is not rewritten before the kernel has run.  (The writer kernels read
+  // the table on the ingest stream itself, in order.  The uniform form commits its count by value.)
+  if (I.general) DABX_HIP(hipStreamWaitEvent(e->ingest, sl.counts_read, 0));
+  DABX_HIP(hipMemcpyAsync(sl.jobs_dev, jobs, (sizeof(IqJob) + sizeof(unsigned)) * (size_t)S, hipMemcpyHostToDevice, e->ingest));
+  IqIo io{};
+  io.src = sl.dev; io.dst = e->dev.iq; io.dst_len = e->dev.ring_len; io.work = I.work; io.work_pitch = I.work_pitch;
+  io.carry = I.carry; io.carry_pitch = I.carry_pitch; io.tab_int = I.tab_int; io.tab_frac = I.tab_frac;
+  if (int rc = launch_iq_jobs(io, sl.jobs_dev, S, max_n, max_out, resamples, e->ingest)) return rc;
   DABX_HIP(hipEventRecord(e->ingest_done, e->ingest));
   DABX_HIP(hipStreamWaitEvent(e->stream, e->ingest_done, 0));
-  const int rc = commit_impl(e, -1, sl.n);
-  DABX_HIP(hipEventRecord(I.committed, e->stream));
-  I.committed_recorded = true;
+  for (int s = 0; s < S; s++) if (jobs[s].M) I.carry_n[(size_t)s] = (int)jobs[s].keep;
   sl.in_flight = false;
-  return rc;
+  if (!I.general) return commit_impl(e, -1, counts[0]);
+  for (int s = 0; s < S; s++) e->wr_host[s] += counts[s];
+  if (int rc = launch_commit_counts(e->dev.wr, reinterpret_cast<const unsigned *>(sl.jobs_dev + S), S, e->stream)) return rc;
+  DABX_HIP(hipEventRecord(sl.counts_read, e->stream));
+  if (e->cfg.dc_iq_correction) return launch_dciq(e->dev, e->cfg.dc_iq_correction, e->stream);
+  return 0;
 }
 
 int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)

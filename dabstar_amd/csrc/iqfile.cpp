@@ -87,6 +87,17 @@ int dabx::iq_native_ring(const dabx_iq_format *f, IqDecode *d, int ring_fmt)
   return 0;
 }
 
+int dabx::iq_push_decode(int fmt, int ring_fmt, IqDecode *d)
+{
+  dabx_iq_format f{};
+  f.sample_rate = INPUT_RATE;
+  f.family = fmt == 2 ? DABX_FAMILY_RAW : DABX_FAMILY_WAV;
+  f.container = fmt == 2 ? DABX_C_U8 : (fmt == 1 ? DABX_C_I16 : DABX_C_F32);
+  f.bits = fmt == 2 ? 8 : (fmt == 1 ? 16 : 32);
+  if (int rc = check_format(&f, d)) return rc;
+  return iq_native_ring(&f, d, ring_fmt);
+}
+
 int dabx_iq_sample_bytes(const dabx_iq_format *fmt)
 {
   const int b = fmt ? channel_bytes(fmt->container) : 0;
@@ -431,8 +442,9 @@ static long long bound_samples(const dabx_feed *f, size_t n_bytes)
 {
   size_t n = (n_bytes + f->odd.size()) / (size_t)(2 * f->dec.bytes);
   if (f->dec.quirk_block) n -= n % (size_t)f->dec.quirk_block;
-  if (!f->resample) return (long long)n;
-  return (long long)(((size_t)f->carry_n + n) / (size_t)f->M) * 2048;
+  IqJob j{};
+  j.n = (unsigned)n; j.carry_n = (unsigned)f->carry_n; j.M = (unsigned)f->M;
+  return (long long)iq_plan(&j);
 }
 long long dabx_feed_bound(const dabx_feed *f, size_t n_bytes) { return f ? bound_samples(f, n_bytes) : DABX_E_ARG; }
 
@@ -453,21 +465,25 @@ static long long feed_push(dabx_feed *f, const uint8_t *bytes, size_t n_bytes)
   f->odd.assign(src + n * sb, src + total);
   if (n == 0) return 0;
 
-  float2 *dst; int dst_len; unsigned long long dst0;
+  if (n > 0x7FFFFFFFu) { set_error("dabx_feed_bytes: %zu samples in one call", n); return DABX_E_ARG; }
+  IqJob j{};
+  j.n = (unsigned)n; j.carry_n = (unsigned)f->carry_n; j.M = (unsigned)f->M; j.dec = f->dec;
+  const long long produced = (long long)iq_plan(&j);
+  IqIo io{};
   if (f->eng) {
-    float2 *ring; int ring_len; unsigned long long wr, rd;
-    int rc = dabx_internal_ring_info(f->eng, f->stream, &ring, &ring_len, &wr, &rd, &f->st);
+    float2 *ring; unsigned long long wr, rd;
+    int rc = dabx_internal_ring_info(f->eng, f->stream, &ring, &io.dst_len, &wr, &rd, &f->st);
     if (rc) return rc;
-    const long long out_n = f->resample ? (long long)(((size_t)f->carry_n + n) / (size_t)f->M) * 2048 : (long long)n;
-    if ((long long)(wr - rd) + out_n > ring_len) {
+    if ((long long)(wr - rd) + produced > io.dst_len) {
       f->odd.clear();
       if (!joined.empty()) f->odd.assign(joined.begin(), joined.begin() + (joined.size() - n_bytes));   // as before the call
-      set_error("dabx_feed_bytes: ring of stream %d has room for %lld samples, %lld offered", f->stream, (long long)ring_len - (long long)(wr - rd), out_n);
+      set_error("dabx_feed_bytes: ring of stream %d has room for %lld samples, %lld offered", f->stream, (long long)io.dst_len - (long long)(wr - rd), produced);
       return DABX_E_STATE;
     }
-    dst = ring; dst_len = ring_len; dst0 = wr;
+    io.dst = ring; j.dst0 = wr;
   } else {
-    dst = f->lin; dst_len = 0; dst0 = f->lin_n;
+    if (f->lin_n + (size_t)produced > f->lin_cap) { set_error("dabx_convert_iq_bytes: output buffer too small"); return DABX_E_ARG; }
+    io.dst = f->lin; j.dst0 = f->lin_n;
   }
   if (n * sb > f->stage_cap) {
     if (f->stage) DABX_HIP(hipFree(f->stage));
@@ -475,32 +491,17 @@ static long long feed_push(dabx_feed *f, const uint8_t *bytes, size_t n_bytes)
     DABX_HIP(hipMalloc((void **)&f->stage, n * sb));
     f->stage_cap = n * sb;
   }
-  DABX_HIP(hipMemcpyAsync(f->stage, src, n * sb, hipMemcpyHostToDevice, f->st));
-  long long produced;
-  int rc;
-  if (!f->resample) {
-    if (!f->eng && f->lin_n + n > f->lin_cap) { set_error("dabx_convert_iq_bytes: output buffer too small"); return DABX_E_ARG; }
-    if ((rc = launch_decode_iq(f->stage, f->dec, dst, dst0, dst_len, n, f->st))) return rc;
-    produced = (long long)n;
-  } else {
-    const size_t len = (size_t)f->carry_n + n;
-    if (len > f->work_cap) {
-      if (f->work) DABX_HIP(hipFree(f->work));
-      f->work = nullptr; f->work_cap = 0;
-      DABX_HIP(hipMalloc((void **)&f->work, len * sizeof(float2)));
-      f->work_cap = len;
-    }
-    if (f->carry_n) DABX_HIP(hipMemcpyAsync(f->work, f->carry, (size_t)f->carry_n * sizeof(float2), hipMemcpyDeviceToDevice, f->st));
-    if ((rc = launch_decode_iq(f->stage, f->dec, f->work, (unsigned long long)f->carry_n, 0, n, f->st))) return rc;
-    // block c needs V[c M .. c M + M]
-    const size_t blocks = len >= (size_t)f->M + 1 ? (len - 1) / (size_t)f->M : 0;
-    produced = (long long)blocks * 2048;
-    if (!f->eng && f->lin_n + (size_t)produced > f->lin_cap) { set_error("dabx_convert_iq_bytes: output buffer too small"); return DABX_E_ARG; }
-    if ((rc = launch_resample_1ms(f->work, f->M, f->tab_int, f->tab_frac, dst, dst0, dst_len, (size_t)produced, f->st))) return rc;
-    const size_t keep = len - blocks * (size_t)f->M;          // 1 .. M samples (0 only before the first WAV sample)
-    if (keep) DABX_HIP(hipMemcpyAsync(f->carry, f->work + blocks * (size_t)f->M, keep * sizeof(float2), hipMemcpyDeviceToDevice, f->st));
-    f->carry_n = (int)keep;
+  if ((size_t)j.carry_n + n > f->work_cap && f->resample) {     // [carry | decoded]
+    if (f->work) DABX_HIP(hipFree(f->work));
+    f->work = nullptr; f->work_cap = 0;
+    DABX_HIP(hipMalloc((void **)&f->work, ((size_t)j.carry_n + n) * sizeof(float2)));
+    f->work_cap = (size_t)j.carry_n + n;
   }
+  DABX_HIP(hipMemcpyAsync(f->stage, src, n * sb, hipMemcpyHostToDevice, f->st));
+  io.src = f->stage; io.work = f->work; io.carry = f->carry; io.tab_int = f->tab_int; io.tab_frac = f->tab_frac;
+  int rc = launch_iq_job(io, j, f->st);
+  if (rc) return rc;
+  if (f->resample) f->carry_n = (int)j.keep;
   if (f->eng) {
     if (produced && (rc = dabx_internal_commit(f->eng, f->stream, (size_t)produced))) return rc;
   } else f->lin_n += (size_t)produced;

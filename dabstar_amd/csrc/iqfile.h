@@ -16,10 +16,6 @@ struct IqDecode {      // by-value kernel argument
   // which admits just the containers whose codes ARE the ring's.
   int ring_fmt;
 };
-int launch_decode_iq(const uint8_t *src, const IqDecode &d, float2 *dst, unsigned long long dst0, int dst_len, size_t n, hipStream_t st);
-int launch_resample_1ms(const float2 *V, int M, const int16_t *tab_int, const float *tab_frac, float2 *dst, unsigned long long dst0,
-                        int dst_len, size_t n_out, hipStream_t st);
-
 // iqfile.cpp: format check and the readers' interpolation tables (wav_reader.cpp:67-82, xml_reader.cpp:237-244), shared with the bulk ingest
 int iq_check_format(const dabx_iq_format *f, IqDecode *d);
 // d (from iq_check_format) is to feed a ring of ring_fmt: sets d->ring_fmt, or refuses (DABX_E_ARG, message with the format and the ring) what
@@ -27,28 +23,43 @@ int iq_check_format(const dabx_iq_format *f, IqDecode *d);
 int iq_native_ring(const dabx_iq_format *f, IqDecode *d, int ring_fmt);
 void iq_resample_tables(int family, int rate, int *M, int16_t *tab_int /* [2048] */, float *tab_frac /* [2048] */);
 
-// Bulk ingest, general form (engine.cpp, dabx_ingest_open_formats): what one stream's share of a slab is and where it goes.  One record per
-// stream and commit, uploaded in front of the two kernels below.
-struct IngestJob {
-  unsigned long long src_off;     // byte offset of the stream's payload in the device slab
-  unsigned long long dst0;        // absolute ring index of the first sample written (the committed index, host mirror)
-  unsigned n;                     // complete input samples in the slab (0: the stream takes no part)
-  unsigned carry_n;               // samples carried over from the previous slab (resampling streams: <= M + 1)
-  unsigned M;                     // input samples per millisecond (rate / 1000); 0: the recording is at 2.048 MS/s, no resampling
-  unsigned blocks;                // 1-ms blocks this commit resamples: 2048 output samples each
-  unsigned keep;                  // samples of [carry | decoded] kept for the next slab
-  unsigned tab;                   // index of the stream's interpolation tables
+// The three formats of dabx_push_iq / dabx_ingest_config.fmt as decode records for a ring of ring_fmt (which ring_takes, engine.cpp, has admitted):
+// 0 cf32 -> WAV / float32, 1 int16 -> WAV / int16, 2 uint8 -> RAW / uint8, all little-endian at 2.048 MS/s
+int iq_push_decode(int fmt, int ring_fmt, IqDecode *d);
+
+// THE way IQ samples get into a ring (iqfile.hip): one job is `n` samples of one payload for one destination.  Pushes, the file feed and
+// dabx_convert_iq_bytes hand one over by value; a bulk-ingest commit uploads one per stream, in front of the kernels that read them.
+struct IqJob {
+  unsigned long long src_off;     // byte offset of the payload in IqIo::src: on a sample boundary of the allocation
+  unsigned long long dst0;        // index of the first sample written (a ring: the absolute index, i.e. the committed count's host mirror)
+  unsigned n;                     // complete input samples (0: the stream takes no part)
+  unsigned carry_n;               // samples carried over from the previous job (resampling: <= M + 1)
+  unsigned M;                     // input samples per millisecond (rate / 1000); 0: the payload is at 2.048 MS/s, no resampling
+  unsigned blocks;                // 1-ms blocks this job resamples, 2048 output samples each  } iq_plan
+  unsigned keep;                  // samples of [carry | decoded] kept for the next job        }
+  unsigned tab;                   // index of the interpolation tables
   IqDecode dec;
 };
-struct IngestMulti {              // by-value kernel argument
-  const uint8_t *slab;
-  const IngestJob *jobs;          // [S] device
-  float2 *iq; int ring_len;       // EngineDev::iq: the untyped base of a native ring when the jobs' dec.ring_fmt says so
-  float2 *work; size_t work_pitch;    // [S][work_pitch] carry + decoded samples of the resampling streams
+// blocks, keep of a job from its carry_n, n, M; returns the samples it produces.  Block c reads V[c M .. c M + M] of V = [carry | decoded]
+inline unsigned iq_plan(IqJob *j)
+{
+  j->blocks = j->keep = 0;
+  if (!j->M) return j->n;
+  const unsigned len = j->carry_n + j->n;
+  j->blocks = len ? (len - 1) / j->M : 0;
+  j->keep = len - j->blocks * j->M;            // 1 .. M samples (0 only before the first WAV sample)
+  return j->blocks * 2048;
+}
+struct IqIo {                     // by-value kernel argument: what the jobs of one launch share.  Stream s (0 for a job by value) has row s of each
+  const uint8_t *src;
+  void *dst; int dst_len;         // [S][dst_len] elements of the jobs' dec.ring_fmt, written at (dst0 + i) % dst_len; dst_len 0: a linear buffer
+  float2 *work; size_t work_pitch;    // [S][work_pitch] carry + decoded samples of a resampling job
   float2 *carry; size_t carry_pitch;  // [S][carry_pitch]
   const int16_t *tab_int; const float *tab_frac;   // [n_tabs][2048]
 };
-int launch_ingest_multi(const IngestMulti &m, int n_streams, unsigned max_n, unsigned max_out, hipStream_t st);
+int launch_iq_job(const IqIo &io, const IqJob &j, hipStream_t st);
+// jobs_dev [n_streams]; max_n / max_out: the largest n / blocks * 2048 among them; resamples: some job has M and n
+int launch_iq_jobs(const IqIo &io, const IqJob *jobs_dev, int n_streams, unsigned max_n, unsigned max_out, bool resamples, hipStream_t st);
 int launch_commit_counts(unsigned long long *wr, const unsigned *counts_dev, int n_streams, hipStream_t st);
 }  // namespace dabx
 

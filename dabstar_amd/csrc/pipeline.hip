@@ -2249,58 +2249,4 @@ int launch_commit(const EngineDev &e, int stream, unsigned long long n, hipStrea
   return 0;
 }
 
-// host IQ formats -> cf32 ring (raw_reader.cpp:66-70, wav_reader.cpp:164), or -- ring_fmt = fmt != 0 -- the codes as they are into a native ring
-__global__ void k_convert_iq(const void *src, int fmt, void *ring_base, int ring_fmt, int ring_len, unsigned long long wr0, size_t n)
-{
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const size_t o = (size_t)((wr0 + i) % (unsigned long long)ring_len);
-  if (ring_fmt == RING_S16) { reinterpret_cast<uint32_t *>(ring_base)[o] = reinterpret_cast<const uint32_t *>(src)[i]; return; }
-  if (ring_fmt == RING_U8) { reinterpret_cast<uint16_t *>(ring_base)[o] = reinterpret_cast<const uint16_t *>(src)[i]; return; }
-  float2 *ring = reinterpret_cast<float2 *>(ring_base);
-  float2 v;
-  if (fmt == 0) v = reinterpret_cast<const float2 *>(src)[i];
-  else if (fmt == 1) { const short2 q = reinterpret_cast<const short2 *>(src)[i]; v = make_float2(q.x / 32768.0f, q.y / 32768.0f); }
-  else { const uchar2 q = reinterpret_cast<const uchar2 *>(src)[i]; v = make_float2((q.x - 127.38f) / 128.0f, (q.y - 127.38f) / 128.0f); }
-  ring[o] = v;
-}
-// ring: the stream's own ring (its first element); ring_fmt != RING_CF32 requires fmt == ring_fmt (checked by the callers, engine.cpp)
-int launch_convert_iq(const void *src, int fmt, void *ring, int ring_fmt, int ring_len, unsigned long long wr0, size_t n, hipStream_t st)
-{
-  hipLaunchKernelGGL(k_convert_iq, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, fmt, ring, ring_fmt, ring_len, wr0, n);
-  DABX_HIP(hipGetLastError());
-  return 0;
-}
-
-// bulk ingest (engine.cpp, dabx_ingest_commit): [S][n] samples of fmt in `src` -> every stream's ring behind its committed index
-__global__ __launch_bounds__(256) void k_ingest_convert(const void *src, int fmt, void *iq, int ring_fmt, int ring_len, const unsigned long long *wr, size_t n)
-{
-  const int s = blockIdx.y;
-  const unsigned long long wr0 = wr[s];
-  if (ring_fmt != RING_CF32) {                               // a native ring (fmt == ring_fmt): the slab's codes are scattered as they are
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-      const size_t j = (size_t)s * n + i, o = (size_t)s * ring_len + (size_t)((wr0 + i) % (unsigned long long)ring_len);
-      if (ring_fmt == RING_S16) reinterpret_cast<uint32_t *>(iq)[o] = reinterpret_cast<const uint32_t *>(src)[j];
-      else reinterpret_cast<uint16_t *>(iq)[o] = reinterpret_cast<const uint16_t *>(src)[j];
-    }
-    return;
-  }
-  float2 *ring = reinterpret_cast<float2 *>(iq) + (size_t)s * ring_len;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t j = (size_t)s * n + i;
-    float2 v;
-    if (fmt == 0) v = reinterpret_cast<const float2 *>(src)[j];
-    else if (fmt == 1) { const short2 q = reinterpret_cast<const short2 *>(src)[j]; v = make_float2(q.x / 32768.0f, q.y / 32768.0f); }
-    else { const uchar2 q = reinterpret_cast<const uchar2 *>(src)[j]; v = make_float2((q.x - 127.38f) / 128.0f, (q.y - 127.38f) / 128.0f); }
-    ring[(size_t)((wr0 + i) % (unsigned long long)ring_len)] = v;
-  }
-}
-int launch_ingest_convert(const EngineDev &e, const void *src, int fmt, size_t n, hipStream_t st)
-{
-  const unsigned bx = (unsigned)std::min<size_t>((n + 255) / 256, 2048);
-  hipLaunchKernelGGL(k_ingest_convert, dim3(bx, e.n_streams), dim3(256), 0, st, src, fmt, e.iq, e.ring_fmt, e.ring_len, e.wr, n);
-  DABX_HIP(hipGetLastError());
-  return 0;
-}
-
 }  // namespace dabx

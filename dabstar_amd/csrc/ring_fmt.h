@@ -5,7 +5,7 @@
 // stores it:
 //   S16  interleaved I, Q int16, machine byte order      value = (float)c / 32768               (wav_reader.cpp:164)
 //   U8   interleaved I, Q uint8                          value = ((float)c - 127.38f) / 128     (raw_reader.cpp:66-70)
-// Both maps are the expressions k_convert_iq has always used, one convert, (one subtract) and one division by a power of two per
+// Both maps are the expressions the writer's decode_one (iqfile.hip) uses, one convert, (one subtract) and one division by a power of two per
 // component: every code has exactly one float, on the device and on the host alike (-fno-fast-math -ffp-contract=off), so a native
 // ring changes no bit downstream.  An element is ONE integer register -- I in the low half, Q in the high half -- loaded with its
 // own alignment (4 / 2 bytes) and nothing wider: frames start on any sample.

@@ -17,8 +17,7 @@ namespace dabx {
 static std::string g_err;
 void set_error(const char *fmt, ...) { g_err = fmt; }
 int hip_fail(hipError_t, const char *, const char *, int) { return DABX_E_HIP; }
-int launch_decode_iq(const uint8_t *, const IqDecode &, float2 *, unsigned long long, int, size_t, hipStream_t) { abort(); }
-int launch_resample_1ms(const float2 *, int, const int16_t *, const float *, float2 *, unsigned long long, int, size_t, hipStream_t) { abort(); }
+int launch_iq_job(const IqIo &, const IqJob &, hipStream_t) { abort(); }
 int host_profile_map(int, int, int, std::vector<uint16_t> &, int *) { abort(); }
 int prs_quarter_turns(int k) { return (k * 7 + 3) & 3; }      // any table will do for memory-safety purposes
 }  // namespace dabx

@@ -77,6 +77,13 @@ def test_slab_ingest_decodes_like_per_stream_pushes_and_like_the_oracle(dtype, c
         for j in range(18):
             assert np.array_equal(a.read_msc(s, j, 16), b.read_msc(s, j, 16)), (s, j)
             assert np.array_equal(a.read_superframes(s, j, 4), b.read_superframes(s, j, 4)), (s, j)
+    # the rings themselves, not only what survives the decoder: 24 frames through a 12-frame ring wrap it twice (the modulo path)
+    ring, wr = 3 * chunk * TF, n_chunks * chunk * TF
+    for s in range(S):
+        ra = a.read_iq(s, wr - ring, ring)
+        assert np.array_equal(ra.view(np.uint32), b.read_iq(s, wr - ring, ring).view(np.uint32)), s
+    want = np.ascontiguousarray(_dequantise(xs[1][: n_chunks * per], dtype))[wr - ring:wr]
+    assert np.array_equal(a.read_iq(1, wr - ring, ring).view(np.uint32), want.view(np.uint32))
     # ... and stream 1 against the oracle receiver on the samples as the device sees them
     ora = _oracle_run(np.ascontiguousarray(_dequantise(xs[1][: n_chunks * per], dtype)), subch)
     f = a.stats(1)["frames"]
@@ -192,6 +199,49 @@ def test_slab_ingest_of_recordings_at_three_rates_and_unequal_lengths():
         kk = 4 * fr - 16
         for j in range(6):
             assert np.array_equal(a.read_msc(s, j, 16), ora["msc"][j].reshape(-1, 192)[kk - 16:kk]), (s, j)
+    for fd in feeds:
+        fd.close()
+    a.ingest_close()
+    a.close(); b.close()
+
+
+def test_slab_ingest_carries_samples_over_commits_that_complete_no_block():
+    """The resampler's state between slabs: recordings at 2.5 and 1.792 MS/s submitted in slabs SHORTER than one 1-ms block, so that most
+    commits complete no block for a stream and some complete none for any -- the leftover samples have to be carried all the same.  The
+    rings equal those of per-stream dabx_feed_bytes feeds of the same bytes, bit for bit.  (The streams end at different slabs.)"""
+    rng = np.random.default_rng(7)
+    #        family, container, big-endian, swap, bits, rate, input samples
+    kinds = [(1, 2, 0, 0, 16, 2500000, 12 * 2500), (2, 5, 0, 1, 32, 1792000, 9 * 1792 + 500)]
+    S = len(kinds)
+    fmts, payloads = [], []
+    for fam, cont, be, swap, bits, rate, n in kinds:
+        pairs = (0.25 * rng.standard_normal(2 * n)).astype(np.float32)
+        raw = (np.round(pairs * 32768.0).astype("<i2") if cont == 2 else pairs.astype("<f4")).tobytes()
+        fmts.append(dx.IqFormat(fam, cont, be, swap, bits, rate, 0, len(raw)))
+        payloads.append(np.frombuffer(raw, np.uint8))
+    a = dx.Engine(n_streams=S, ring_frames=2, max_subch=6, out_frames=4)      # bulk ingest, per-stream form
+    b = dx.Engine(n_streams=S, ring_frames=2, max_subch=6, out_frames=4)      # one feed per stream
+    slabs, pitch = a.ingest_open_formats(fmts, slabs=2, max_frames=1)
+    feeds = [dx.Feed(b, s, fmts[s]) for s in range(S)]
+    sizes = [700, 300, 1100, 50, 900]                                          # samples per stream and slab: all below 1792
+    pos, total, k, idle = [0] * S, [0] * S, 0, 0
+    while any(pos[s] < len(payloads[s]) for s in range(S)):
+        nb = [min(sizes[k % len(sizes)] * fmts[s].sample_bytes(), len(payloads[s]) - pos[s]) for s in range(S)]
+        got = []
+        for s in range(S):
+            slabs[k % 2][s, :nb[s]] = payloads[s][pos[s]:pos[s] + nb[s]]
+            got.append(feeds[s].push(payloads[s][pos[s]:pos[s] + nb[s]]) if nb[s] else 0)
+            pos[s] += nb[s]; total[s] += got[s]
+        idle += not any(got)
+        a.ingest_submit_bytes(k % 2, nb)
+        a.ingest_commit(k % 2)
+        k += 1
+    assert idle >= 3 and total == [11 * 2048, 9 * 2048], (idle, total)
+    for s in range(S):
+        ra = a.read_iq(s, 0, total[s])
+        assert np.array_equal(ra.view(np.uint32), b.read_iq(s, 0, total[s]).view(np.uint32)), s
+        with pytest.raises(dx.DabxError, match="not in the ring"):
+            a.read_iq(s, 0, total[s] + 1)
     for fd in feeds:
         fd.close()
     a.ingest_close()
