@@ -300,6 +300,19 @@ class OraBackend:
         a = np.ctypeslib.as_array(p, (n.value,)).copy() if n.value else np.zeros(0, np.uint8)
         return a.reshape(-1, 3 * self.kbps)
 
+    def _bytes(self, accessor):
+        n = C.c_size_t(0)
+        p = accessor(self._h, C.byref(n))
+        return np.ctypeslib.as_array(p, (n.value,)).copy() if n.value else np.zeros(0, np.uint8)
+
+    def sf_bytes(self):
+        """The accepted DAB+ super frames so far, RS- and fire-code-corrected, 110 * kbps / 8 bytes each, one after the other."""
+        return self._bytes(oracle().ora_backend_sf_bytes)
+
+    def sfi_bytes(self):
+        """Their 32-byte records (include/dabx.h dabx_superframe_info), one after the other."""
+        return self._bytes(oracle().ora_backend_sfi_bytes)
+
     def stats(self):
         out = (C.c_long * 8)()
         oracle().ora_backend_stats(self._h, out)

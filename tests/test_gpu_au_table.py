@@ -17,6 +17,7 @@ from dabstar_amd import lib as dx
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 from tools import dab_synth as ds  # noqa: E402
 from test_gpu_engine import _oracle_run  # noqa: E402
+from dabplus_cases import _check_record_against_its_super_frame  # noqa: E402  (moved there unchanged: the DAB+ stage tests share it)
 
 pytestmark = pytest.mark.gpu
 
@@ -25,35 +26,6 @@ def _oracle_records(x, subch):
     """The oracle receiver on x: per sub-channel the 32-byte records and the super frames they describe."""
     ora = _oracle_run(x, subch)
     return [r.view(dx.SUPERFRAME_INFO) for r in ora["sfi"]], ora["sf"], ora["stats"]
-
-
-def _crc16(b):
-    crc = 0xFFFF
-    for v in bytes(b):
-        crc ^= v << 8
-        for _ in range(8):
-            crc = ((crc << 1) ^ 0x1021) & 0xFFFF if crc & 0x8000 else (crc << 1) & 0xFFFF
-    return crc ^ 0xFFFF
-
-
-def _check_record_against_its_super_frame(r, sf, kbps):
-    """What a host relies on: the record's table is the header's, the masks are the CRCs' (checked here once with a CRC of the test's own)."""
-    end = 110 * kbps // 8
-    n = int(r["num_aus"])
-    dac, sbr = (sf[2] >> 6) & 1, (sf[2] >> 5) & 1
-    assert n == {0: 4, 1: 2, 2: 6, 3: 3}[2 * dac + sbr] and r["stream_parms"] == sf[2] & 0x7F
-    st = [int(v) for v in r["au_start"][:n + 1]]
-    assert st[0] == {4: 8, 2: 5, 6: 11, 3: 6}[n] and st[n] == end and all(int(v) == 0 for v in r["au_start"][n + 1:])
-    for a in range(n):
-        ln = st[a + 1] - st[a] - 2
-        bad_len = ln > 960 or ln < 0 or st[a] + ln + 2 > end
-        assert bool(r["au_len_bad"] >> a & 1) == bad_len
-        if bad_len:
-            assert not (r["au_crc_ok"] >> a & 1)
-            continue
-        good = _crc16(sf[st[a]:st[a] + ln]) == (int(sf[st[a] + ln]) << 8 | int(sf[st[a] + ln + 1]))
-        assert bool(r["au_crc_ok"] >> a & 1) == good, a
-    assert r["au_crc_ok"] >> n == 0 and r["au_len_bad"] >> n == 0
 
 
 def test_config3_records_equal_the_oracles_and_describe_their_super_frames():
