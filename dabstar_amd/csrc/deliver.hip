@@ -6,6 +6,7 @@
 // mp4processor.cpp:149-158.  Pure HBM copies: 14 208 B of results per frame + 13 % (super frames are the logical
 // frames' bytes again, RS-corrected) -- 0.7 % of the chain's algorithmic bytes.
 #include "pipeline.h"
+#include "packet_core.h"
 
 namespace dabx {
 
@@ -154,6 +155,57 @@ __global__ __launch_bounds__(64) void k_deliver_msc(EngineDev e, DeliverDev dv, 
     reinterpret_cast<dabx_chunk_subch *>(slab + dv.hdr.off_subch)[sj] = r;
     if (live) { dv.cif_done[sj] = sc.cif_out; dv.sf_done[sj] = sc.sf_count; }
   }
+}
+
+// The data-group section (include/dabx.h, dabx_chunk_dg): one wave per packet-mode slot, behind k_deliver_msc of the chunk (same stream; the
+// table has been zeroed in front).  The groups completed since the previous chunk -- as many of the newest as are still intact in the
+// slot's rings and fit its room in the slab -- go out of the two rings: records with byte_pos counted from the slot's bytes in the slab.
+__global__ __launch_bounds__(64) void k_deliver_dg(PacketDev pk, uint8_t *slab, unsigned long long off_dg)
+{
+  const int lane = threadIdx.x;
+  PacketSlot &ps = pk.slots[blockIdx.x];
+  if (!ps.dl_rec_off) return;
+  const long long dg_count = ps.dg_count, dg_bytes = ps.dg_bytes, done = ps.dl_done;
+  const unsigned long long rec_mask = ps.rec_mask, bytes_mask = ps.bytes_mask;
+  const dabx_datagroup_info *recs = ps.recs;
+  const uint8_t *ring = ps.bytes;
+  long long first = done;
+  if (dg_count - first > (long long)ps.dl_rec_cap) first = dg_count - ps.dl_rec_cap;
+  if (dg_count - first > (long long)rec_mask + 1) first = dg_count - ((long long)rec_mask + 1);
+  // a series of up to DABX_DG_MAX_BYTES may have been written from dg_bytes on: what that range covers in the ring is gone (engine.cpp, packet_window)
+  while (first < dg_count) {
+    const long long pos = recs[(size_t)((unsigned long long)first & rec_mask)].byte_pos;
+    if (dg_bytes + DABX_DG_MAX_BYTES - pos <= (long long)bytes_mask + 1 && dg_bytes - pos <= (long long)ps.dl_bytes_cap) break;
+    first++;
+  }
+  const int n = (int)(dg_count - first);
+  const long long base = n ? recs[(size_t)((unsigned long long)first & rec_mask)].byte_pos : dg_bytes;
+  const long long n_bytes = dg_bytes - base;
+  dabx_datagroup_info *ro = reinterpret_cast<dabx_datagroup_info *>(slab + ps.dl_rec_off);
+  for (int i = lane; i < n; i += 64) {
+    dabx_datagroup_info r = recs[(size_t)((unsigned long long)(first + i) & rec_mask)];
+    r.byte_pos -= base;
+    ro[i] = r;
+  }
+  uint8_t *bo = slab + ps.dl_bytes_off;
+  for (long long k = lane; k < n_bytes; k += 64) bo[k] = ring[(size_t)((unsigned long long)(base + k) & bytes_mask)];
+  if (lane == 0) {
+    dabx_chunk_dg t;
+    t.first_dg = first; t.n_dg = n; t.dg_lost = (int)(first - done); t.rec_off = ps.dl_rec_off; t.bytes_off = ps.dl_bytes_off; t.n_bytes = n_bytes;
+    t.frames = ps.frames; t.packets = ps.packets; t.addr_match = ps.addr_match; t.continuity_err = ps.continuity_err; t.crc_bad = ps.crc_bad;
+    t.len_bad = ps.len_bad; t.walk_short = ps.walk_short; t.dg_count = dg_count; t.dg_bytes = dg_bytes; t.dg_crc_bad = ps.dg_crc_bad;
+    t.dg_overflow = ps.dg_overflow;
+    reinterpret_cast<dabx_chunk_dg *>(slab + off_dg)[(size_t)ps.s * pk.max_subch + ps.j] = t;
+    ps.dl_done = dg_count;
+  }
+}
+int launch_deliver_dg(const EngineDev &e, const DeliverDev &dv, const PacketDev &pk, hipStream_t st)
+{
+  if (!dv.hdr.off_dg || pk.n <= 0) return 0;
+  DABX_HIP(hipMemsetAsync(dv.slab + dv.hdr.off_dg, 0, sizeof(dabx_chunk_dg) * (size_t)e.n_streams * e.max_subch, st));
+  hipLaunchKernelGGL(k_deliver_dg, dim3(pk.n), dim3(64), 0, st, pk, dv.slab, (unsigned long long)dv.hdr.off_dg);
+  DABX_HIP(hipGetLastError());
+  return 0;
 }
 
 int launch_deliver_front(const EngineDev &e, const DeliverDev &dv, hipStream_t st)

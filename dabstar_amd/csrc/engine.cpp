@@ -1,5 +1,6 @@
 // engine.cpp -- host side of the stream-batched receiver and the engine-level C ABI (include/dabx.h).
 #include "pipeline.h"
+#include "packet_core.h"
 #include "viterbi_core.h"
 #include "sdma.h"
 #include "iqfile.h"
@@ -22,7 +23,7 @@
 namespace dabx {
 int launch_front_step(const EngineDev &e, EngineStreams &ss, Marker &mk, bool async_acquire, bool all_locked);
 int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineStreams &ss, Marker &mk, const DeliverDev *dv = nullptr,
-                     hipStream_t *tail = nullptr);
+                     hipStream_t *tail = nullptr, const PacketDev *pk = nullptr);
 int launch_deliver_front(const EngineDev &e, const DeliverDev &dv, hipStream_t st);
 void dabx_internal_fibdec_skip(dabx_fibdec *d, long long n_fibs);     // fib.cpp: FIBs the decoder never saw (they had left the ring)
 int launch_dciq(const EngineDev &e, int mode, hipStream_t st);
@@ -30,7 +31,7 @@ int launch_level_exact(const EngineDev &e, hipStream_t st);
 int launch_stage_msc_block(const EngineDev &e, const int16_t *soft_dev, int blk, bool closes_cif, hipStream_t st);
 int launch_msc_inject(const EngineDev &e, int stream, const int16_t *soft_dev, int n_cifs, int first, hipStream_t st);
 int launch_msc_advance(const EngineDev &e, const int32_t *counts_dev, hipStream_t st);
-extern const char *const kStepKernelNames[11];
+extern const char *const kStepKernelNames[N_STEP_KERNELS];
 int launch_commit(const EngineDev &e, int stream, unsigned long long n, hipStream_t st);
 int launch_fic_only(const EngineDev &e, hipStream_t st, int first, int count);
 int launch_i16_to_sym(const int16_t *soft, uint8_t *sym, size_t n, hipStream_t st);
@@ -70,6 +71,7 @@ struct Delivery {
   int32_t *subch_id = nullptr;
   long long *frames_done = nullptr, *cif_done = nullptr, *sf_done = nullptr;
   dabx_chunk_header hdr{};
+  bool want_dg = false;                          // DABX_DELIVER_DG, or what == 0: a data-group section while there are packet-mode slots
 };
 
 // Bulk ingest (include/dabx.h "Bulk ingest"): page-locked input slabs, their device twins, one SDMA transfer per slab.  Both forms are S
@@ -151,6 +153,17 @@ struct dabx_engine : dabx::EngineHead {          // (iqfile.h: the ring format, 
   bool level_dirty = false;                    // exact_level_tracker: steps have been issued since k_level_exact last ran behind them
   Delivery dl;
   Ingest ing;
+  // Packet-mode slots (include/dabx.h "Packet-mode data sub-channels", k_packet).  Nothing here exists until the first dabx_set_packet_mode:
+  // pkt stays empty, pkt_dev.n stays 0 and no batch launches k_packet.  pkt[sj].st mirrors the device's job-table entry of the slot; the
+  // device owns it between packet_download and packet_upload (both with the engine drained).
+  struct PacketHost { bool on = false; PacketSlot st{}; long long seen = 0, lost = 0; };
+  std::vector<PacketHost> pkt;                 // [S][max_subch], or empty
+  std::vector<int> pkt_index;                  // [S][max_subch] place in the job table, -1 = not in packet mode
+  PacketDev pkt_dev{};                         // slots = the job table on the device, n = its length
+  int pkt_cap = 0;
+  int packet_download();
+  int packet_upload();
+  void packet_drop(size_t sj);
   int build_msc_classes();
   int delivery_layout();                       // offsets of every slot's bytes in a slab for the sub-channels configured now
   int delivery_begin(DeliverDev *dv, int *slot, int *devslab);     // a chunk closes: host + device slab, front gather on stream a
@@ -339,6 +352,23 @@ int dabx_engine::delivery_layout()
       lo[3 * sj + 2] = off;
       off += (size_t)DL_SF_CAP * sizeof(dabx_superframe_info);
     }
+  // the data-group section (dabx_chunk_dg): only with packet-mode slots -- without one the slab is what it has always been.  Callers hold a
+  // fresh mirror of the job table (packet_download with the engine drained); it goes back to the device below
+  bool any_pkt = false;
+  for (auto &q : pkt) { q.st.dl_rec_off = q.st.dl_bytes_off = 0; q.st.dl_rec_cap = q.st.dl_bytes_cap = 0; any_pkt = any_pkt || q.on; }
+  if (D.want_dg && any_pkt && !d.fic_only) {
+    off = align_up(off, 16);
+    h.off_dg = off; off += S * M * sizeof(dabx_chunk_dg);
+    h.what |= DABX_DELIVER_DG;
+    for (size_t sj = 0; sj < S * M; sj++) {
+      if (!pkt[sj].on) continue;
+      PacketSlot &st = pkt[sj].st;
+      const size_t kbps = (size_t)subch_host[sj].kbps;
+      st.dl_rec_cap = (uint32_t)(4 * F * (kbps / 8)); st.dl_bytes_cap = (uint32_t)(4 * F * 3 * kbps + DABX_DG_MAX_BYTES);
+      st.dl_rec_off = off; off += (size_t)st.dl_rec_cap * sizeof(dabx_datagroup_info);
+      st.dl_bytes_off = off; off = align_up(off + st.dl_bytes_cap, 16);
+    }
+  }
   off = align_up(off, 256);
   h.off_msc = off;
   if ((D.what & (DABX_DELIVER_MSC | DABX_DELIVER_MSC_NOT_DABPLUS)) && !d.fic_only)
@@ -356,6 +386,7 @@ int dabx_engine::delivery_layout()
   }
   D.hdr = h;
   D.bytes = off;
+  if (!pkt.empty()) if (int rc = packet_upload()) return rc;
   if (S * M) {
     DABX_HIP(hipMemcpy(D.layout_off, lo.data(), sizeof(unsigned long long) * 3 * S * M, hipMemcpyHostToDevice));
     std::vector<int32_t> ids(subch_id_host.begin(), subch_id_host.begin() + S * M);
@@ -799,6 +830,8 @@ void dabx_destroy(dabx_engine *e)
     if (e->aslot[i]) (void)hipFree(e->aslot[i]);
     if (e->aslot_done[i]) (void)hipEventDestroy(e->aslot_done[i]);
   }
+  for (size_t sj = 0; sj < e->pkt.size(); sj++) e->packet_drop(sj);
+  if (e->pkt_dev.slots) (void)hipFree(e->pkt_dev.slots);
   for (void *p : e->allocs) (void)hipFree(p);
   if (e->locked_host) (void)hipHostFree(e->locked_host);
   if (e->seq_timeouts_host) (void)hipHostFree(e->seq_timeouts_host);
@@ -828,6 +861,7 @@ static int set_subchannels_impl(dabx_engine *e, int stream, const dabx_subch_des
   }
   // refresh the host mirror: the device owns the dynamic fields (cif_out, super-frame state, counters)
   DABX_HIP(hipMemcpy(e->subch_host.data(), d.subch, sizeof(SubchDev) * e->subch_host.size(), hipMemcpyDeviceToHost));
+  if ((rc = e->packet_download())) return rc;
   int max_kbps = e->max_kbps;
   std::vector<SubchDev> row(std::max(1, d.max_subch));
   for (int j = 0; j < n; j++) {
@@ -917,6 +951,10 @@ static int set_subchannels_impl(dabx_engine *e, int stream, const dabx_subch_des
     }
   }
   DABX_HIP(hipMemcpy(d.subch, e->subch_host.data(), sizeof(SubchDev) * e->subch_host.size(), hipMemcpyHostToDevice));
+  if (!e->pkt.empty()) {                // a new or changed slot loses its packet mode; one that keeps running (a move included) keeps it and its state
+    for (size_t sj : restarted) e->packet_drop(sj);
+    if ((rc = e->packet_upload())) return rc;
+  }
   if (e->dl.open) {
     // slots that start anew count their frames from 0 again; the slab layout follows the new sub-channels (engine drained above)
     const long long zero = 0;
@@ -941,6 +979,170 @@ int dabx_set_subchannels_at(dabx_engine *e, int stream, const dabx_subch_desc *d
 {
   if (at_cif < 0 || stream < 0) { set_error("dabx_set_subchannels_at: bad argument"); return DABX_E_ARG; }
   return set_subchannels_impl(e, stream, desc, n, at_cif);
+}
+
+// ---- packet-mode data sub-channels (include/dabx.h, packet_core.h, k_packet) --------------------------------------------------------
+static_assert(sizeof(dabx_chunk_dg) == 128 && sizeof(dabx_datagroup_info) == 32 && sizeof(dabx_packet_stats) == 128 && sizeof(dabx_packet_config) == 32, "include/dabx.h: packet-mode records");
+
+// the device's job table back into the host mirror (engine drained)
+int dabx_engine::packet_download()
+{
+  if (pkt_dev.n <= 0) return 0;
+  std::vector<PacketSlot> tab((size_t)pkt_dev.n);
+  DABX_HIP(hipMemcpy(tab.data(), pkt_dev.slots, sizeof(PacketSlot) * tab.size(), hipMemcpyDeviceToHost));
+  for (const PacketSlot &q : tab) pkt[(size_t)q.s * dev.max_subch + q.j].st = q;
+  return 0;
+}
+// ... and the table rebuilt from the mirror: the slots in packet mode, in (stream, slot) order
+int dabx_engine::packet_upload()
+{
+  std::vector<PacketSlot> tab;
+  std::fill(pkt_index.begin(), pkt_index.end(), -1);
+  for (size_t sj = 0; sj < pkt.size(); sj++)
+    if (pkt[sj].on) { pkt_index[sj] = (int)tab.size(); tab.push_back(pkt[sj].st); }
+  if ((int)tab.size() > pkt_cap) {
+    PacketSlot *q = nullptr;
+    const int cap = std::max<int>(2 * pkt_cap, std::max<int>(16, (int)tab.size()));
+    DABX_HIP(hipMalloc(&q, sizeof(PacketSlot) * (size_t)cap));
+    if (pkt_dev.slots) (void)hipFree(pkt_dev.slots);
+    pkt_dev.slots = q; pkt_cap = cap;
+  }
+  if (!tab.empty()) DABX_HIP(hipMemcpy(pkt_dev.slots, tab.data(), sizeof(PacketSlot) * tab.size(), hipMemcpyHostToDevice));
+  pkt_dev.n = (int)tab.size();
+  return 0;
+}
+void dabx_engine::packet_drop(size_t sj)
+{
+  if (sj >= pkt.size() || !pkt[sj].on) return;
+  (void)hipFree(pkt[sj].st.bytes);
+  (void)hipFree(pkt[sj].st.recs);
+  pkt[sj] = PacketHost{};
+}
+
+static uint32_t pow2_at_least(size_t v) { uint32_t p = 1; while (p < v) p <<= 1; return p; }
+
+int dabx_set_packet_mode(dabx_engine *e, int stream, int j, const dabx_packet_config *cfg)
+{
+  if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch) { set_error("dabx_set_packet_mode: bad argument"); return DABX_E_ARG; }
+  if (cfg && (cfg->size < 2 * sizeof(int32_t) || cfg->packet_address < 0 || cfg->packet_address > 1023)) {
+    set_error("dabx_set_packet_mode: bad configuration (size %u, packet address %d)", cfg->size, (int)cfg->packet_address);
+    return DABX_E_ARG;
+  }
+  int rc;
+  if ((rc = sync_all(e))) return rc;
+  const size_t sj = (size_t)stream * e->dev.max_subch + j;
+  SubchDev sc;
+  DABX_HIP(hipMemcpy(&sc, e->dev.subch + sj, sizeof(SubchDev), hipMemcpyDeviceToHost));
+  if (!sc.active || sc.dab_plus || sc.kbps % 8 != 0 || sc.kbps > PKT_MAX_KBPS) {
+    set_error("dabx_set_packet_mode: stream %d slot %d is %s", stream, j, !sc.active ? "not active" : sc.dab_plus ? "a DAB+ slot" : "not at a multiple of 8 kbit/s up to 384");
+    return DABX_E_ARG;
+  }
+  if (e->pkt.empty()) {
+    if (!cfg) return 0;
+    e->pkt.resize((size_t)e->dev.n_streams * e->dev.max_subch);
+    e->pkt_index.assign(e->pkt.size(), -1);
+  }
+  if ((rc = e->packet_download())) return rc;
+  e->packet_drop(sj);
+  if (cfg) {
+    // two full batches (56 logical frames) of single-packet groups: a record per 24-byte packet, their payloads, and room for the series
+    // under assembly, which lives in the byte ring in front of the completed groups (packet_core.h)
+    dabx_engine::PacketHost h;
+    h.on = true;
+    h.st.s = stream; h.st.j = j; h.st.address = cfg->packet_address; h.st.first_byte = -1; h.st.run_crc = 0xFFFFu;
+    const uint32_t n_rec = pow2_at_least((size_t)2 * 4 * MSC_BATCH_FRAMES * (sc.kbps / 8));
+    const uint32_t n_bytes = pow2_at_least((size_t)2 * 4 * MSC_BATCH_FRAMES * 3 * sc.kbps + DABX_DG_MAX_BYTES);
+    void *b = nullptr, *r = nullptr;
+    if (hipMalloc(&b, n_bytes) != hipSuccess || hipMalloc(&r, sizeof(dabx_datagroup_info) * (size_t)n_rec) != hipSuccess) {
+      if (b) (void)hipFree(b);
+      set_error("dabx_set_packet_mode: out of device memory");
+      (void)e->packet_upload();
+      return DABX_E_NOMEM;
+    }
+    h.st.bytes = static_cast<uint8_t *>(b); h.st.recs = static_cast<dabx_datagroup_info *>(r);
+    h.st.bytes_mask = n_bytes - 1; h.st.rec_mask = n_rec - 1;
+    e->pkt[sj] = h;
+  }
+  if ((rc = e->packet_upload())) return rc;
+  if (e->dl.open) {                       // the slab's data-group section follows the packet-mode slots (engine drained above)
+    e->subch_host[sj] = sc;
+    if ((rc = e->delivery_layout())) {
+      const std::string why = dabx::last_error();
+      delivery_free(e);
+      set_error("%s -- the delivery has been closed", why.c_str());
+      return rc;
+    }
+  }
+  return 0;
+}
+
+// The slot's table entry as the device holds it and the groups [*lo, dg_count) whose record and bytes are still intact; groups older than
+// that which no call has returned yet are counted as lost.  Reads the entry and, as a rule, ONE record (the oldest candidate's).
+static int packet_window(dabx_engine *e, size_t sj, PacketSlot *st, long long *lo)
+{
+  if (int rc = sync_all(e)) return rc;
+  DABX_HIP(hipMemcpy(st, e->pkt_dev.slots + e->pkt_index[sj], sizeof(PacketSlot), hipMemcpyDeviceToHost));
+  long long first = std::max<long long>(0, st->dg_count - ((long long)st->rec_mask + 1));
+  // the device may write a series of up to DABX_DG_MAX_BYTES from dg_bytes on: whatever that range covers in the ring is gone
+  const long long ring = (long long)st->bytes_mask + 1;
+  while (first < st->dg_count) {
+    dabx_datagroup_info r;
+    DABX_HIP(hipMemcpy(&r, st->recs + (size_t)(first & st->rec_mask), sizeof(r), hipMemcpyDeviceToHost));
+    if (st->dg_bytes + DABX_DG_MAX_BYTES - r.byte_pos <= ring) break;
+    first++;
+  }
+  dabx_engine::PacketHost &h = e->pkt[sj];
+  if (first > h.seen) { h.lost += first - h.seen; h.seen = first; }
+  *lo = first;
+  return 0;
+}
+
+int dabx_read_datagroups(dabx_engine *e, int stream, int j, int n, dabx_datagroup_info *info, uint8_t *bytes, size_t max_bytes)
+{
+  if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch || n <= 0 || !info) { set_error("dabx_read_datagroups: bad argument"); return DABX_E_ARG; }
+  const size_t sj = (size_t)stream * e->dev.max_subch + j;
+  if (e->pkt.empty() || !e->pkt[sj].on) return 0;
+  PacketSlot st;
+  long long lo = 0;
+  if (int rc = packet_window(e, sj, &st, &lo)) return rc;
+  long long from = std::max(lo, st.dg_count - n);
+  int have = (int)(st.dg_count - from);
+  if (have > 0) {                                             // the records [from, dg_count): one or two runs of the ring
+    const size_t ring = (size_t)st.rec_mask + 1, at = (size_t)(from & st.rec_mask), head = std::min<size_t>((size_t)have, ring - at);
+    DABX_HIP(hipMemcpy(info, st.recs + at, sizeof(dabx_datagroup_info) * head, hipMemcpyDeviceToHost));
+    if ((size_t)have > head) DABX_HIP(hipMemcpy(info + head, st.recs, sizeof(dabx_datagroup_info) * ((size_t)have - head), hipMemcpyDeviceToHost));
+    int skip = 0;                                             // the newest groups that fit
+    if (bytes) while (skip < have && (unsigned long long)(st.dg_bytes - info[skip].byte_pos) > max_bytes) skip++;
+    if (skip) { memmove(info, info + skip, sizeof(dabx_datagroup_info) * (size_t)(have - skip)); have -= skip; }
+  }
+  if (have > 0) {
+    const long long base = info[0].byte_pos, total = st.dg_bytes - base;
+    for (int i = 0; i < have; i++) info[i].byte_pos -= base;
+    if (bytes && total > 0) {
+      const size_t ring = (size_t)st.bytes_mask + 1, at = (size_t)((unsigned long long)base & st.bytes_mask);
+      const size_t head = std::min<size_t>((size_t)total, ring - at);
+      DABX_HIP(hipMemcpy(bytes, st.bytes + at, head, hipMemcpyDeviceToHost));
+      if ((size_t)total > head) DABX_HIP(hipMemcpy(bytes + head, st.bytes, (size_t)total - head, hipMemcpyDeviceToHost));
+    }
+  }
+  e->pkt[sj].seen = std::max(e->pkt[sj].seen, st.dg_count);
+  return have;
+}
+
+int dabx_get_packet_stats(dabx_engine *e, int stream, int j, dabx_packet_stats *out)
+{
+  if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch || !out) { set_error("dabx_get_packet_stats: bad argument"); return DABX_E_ARG; }
+  memset(out, 0, sizeof(*out));
+  const size_t sj = (size_t)stream * e->dev.max_subch + j;
+  if (e->pkt.empty() || !e->pkt[sj].on) return sync_all(e);
+  PacketSlot st;
+  long long lo = 0;
+  if (int rc = packet_window(e, sj, &st, &lo)) return rc;
+  out->frames = st.frames; out->packets = st.packets; out->addr_match = st.addr_match; out->continuity_err = st.continuity_err;
+  out->crc_bad = st.crc_bad; out->len_bad = st.len_bad; out->walk_short = st.walk_short; out->dg_count = st.dg_count;
+  out->dg_bytes = st.dg_bytes; out->dg_crc_bad = st.dg_crc_bad; out->dg_overflow = st.dg_overflow; out->dg_lost = e->pkt[sj].lost;
+  out->active = 1; out->packet_address = st.address;
+  return 0;
 }
 
 int dabx_iq_ring_dev(dabx_engine *e, int stream, void **ring, size_t *cap)
@@ -1196,7 +1398,8 @@ int dabx_process(dabx_engine *e, int max_frames, int sync)
       if (e->dl.open && (rc = e->delivery_begin(&dv, &dl_slot, &dl_dev))) return rc;
       e->dev.snap = e->snap_buf[e->ss.batch_parity];
       hipStream_t tail = e->stream;
-      rc = launch_msc_batch(e->dev, 4 * e->pending_frames, e->have_fast ? &e->fast : nullptr, e->ss, e->mk, e->dl.open ? &dv : nullptr, &tail);
+      rc = launch_msc_batch(e->dev, 4 * e->pending_frames, e->have_fast ? &e->fast : nullptr, e->ss, e->mk, e->dl.open ? &dv : nullptr, &tail,
+                            e->pkt_dev.n > 0 ? &e->pkt_dev : nullptr);
       if (rc) {
         if (e->dl.open) e->delivery_abort(dl_slot, dl_dev);          // the slabs of the chunk that was begun: never left IN_FLIGHT without a copy job
         e->pending_frames = 0;
@@ -1801,7 +2004,7 @@ int dabx_ingest_commit(dabx_engine *e, int k)
 
 int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
 {
-  if (!e || (cfg && (cfg->host_slabs < 0 || cfg->host_slabs == 1 || cfg->host_slabs > 64 || (cfg->what & ~15) || cfg->copy_engine < 0 || cfg->copy_engine > 1))) {
+  if (!e || (cfg && (cfg->host_slabs < 0 || cfg->host_slabs == 1 || cfg->host_slabs > 64 || (cfg->what & ~31) || cfg->copy_engine < 0 || cfg->copy_engine > 1))) {
     set_error("dabx_delivery_open: bad argument");
     return DABX_E_ARG;
   }
@@ -1810,7 +2013,8 @@ int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
   if (rc) return rc;
   Delivery &D = e->dl;
   const EngineDev &d = e->dev;
-  D.what = cfg && cfg->what ? cfg->what : (DABX_DELIVER_FIB | DABX_DELIVER_MSC | DABX_DELIVER_SF);
+  D.want_dg = !cfg || !cfg->what || (cfg->what & DABX_DELIVER_DG);
+  D.what = cfg && cfg->what ? (cfg->what & ~DABX_DELIVER_DG) : (DABX_DELIVER_FIB | DABX_DELIVER_MSC | DABX_DELIVER_SF);
   if ((D.what & DABX_DELIVER_FIB) && d.out_frames < DL_FRAMES) {
     set_error("dabx_delivery_open: the engine's FIB ring holds %d frames, a chunk up to %d: create it with dabx_config.out_frames >= %d "
               "(the FIBs of a chunk's first frames would have left the ring before they are gathered)", d.out_frames, DL_FRAMES, DL_FRAMES);
@@ -1826,6 +2030,14 @@ int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
   const size_t per_cif = 5632;
   size_t cap = sizeof(dabx_chunk_header) + S * sizeof(dabx_chunk_stream) + S * M * sizeof(dabx_chunk_subch) + S * F * (384 + 12 + sizeof(dabx_chunk_frame)) + 6 * 16 + 256;
   if (M && !d.fic_only) cap += S * ((size_t)4 * F * per_cif + (size_t)DL_SF_CAP * 5 * per_cif + 2 * 16 * M + M * DL_SF_CAP * sizeof(dabx_superframe_info));
+  // ... and the data-group section of the packet-mode slots there are now (one that is switched on later has to fit the slack)
+  if ((rc = e->packet_download())) return rc;
+  for (size_t sj = 0; sj < e->pkt.size(); sj++)
+    if (e->pkt[sj].on) {
+      e->pkt[sj].st.dl_done = e->pkt[sj].st.dg_count;              // delivery starts with what is completed from now on
+      cap += (size_t)4 * F * (e->subch_host[sj].kbps / 8) * sizeof(dabx_datagroup_info) + (size_t)4 * F * 3 * e->subch_host[sj].kbps + DABX_DG_MAX_BYTES + 16;
+    }
+  if (!e->pkt.empty()) cap += S * M * sizeof(dabx_chunk_dg) + 16;
   D.capacity = align_up(cap, 4096);
 #define H(x) do { hipError_t err__ = (x); if (err__ != hipSuccess) { set_error("HIP error %d (%s) at %s:%d", (int)err__, hipGetErrorString(err__), __FILE__, __LINE__); delivery_free(e); return DABX_E_HIP; } } while (0)
   if (D.copy_engine == 1) H(hipStreamCreateWithFlags(&D.cs, hipStreamNonBlocking));
@@ -2238,7 +2450,7 @@ int dabx_internal_msc_decode(dabx_engine *e, const int32_t *cifs_per_stream, int
   if (!rc) rc = launch_msc_advance(e->dev, counts_dev, e->stream);
   if (!rc) {
     e->dev.snap = e->snap_buf[e->ss.batch_parity];
-    rc = launch_msc_batch(e->dev, batch_cifs, e->have_fast ? &e->fast : nullptr, e->ss, e->mk);
+    rc = launch_msc_batch(e->dev, batch_cifs, e->have_fast ? &e->fast : nullptr, e->ss, e->mk, nullptr, nullptr, e->pkt_dev.n > 0 ? &e->pkt_dev : nullptr);
   }
   const int rc2 = sync_all(e);
   (void)hipFree(counts_dev);

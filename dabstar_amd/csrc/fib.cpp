@@ -1,5 +1,5 @@
 // fib.cpp -- host-side subset of the FIB/FIG parser: sub-channel organisation (FIG 0/1), service components
-// (FIG 0/2) and ensemble information (FIG 0/0: CIF counter, change flags), for the CURRENT and the NEXT multiplex
+// (FIG 0/2), service components in packet mode (FIG 0/3, fib_decoder_fig0.cpp:294-330) and ensemble information (FIG 0/0: CIF counter, change flags), for the CURRENT and the NEXT multiplex
 // configuration, with the swap of the two that fib_decoder_fig0.cpp:102-111 makes when the change flags go 3 -> 0.  SURVEY.md 8(f) rank 1: makes the engine self-configuring the way
 // EtiGenerator is (eti_handler/eti_generator.cpp:132-134, 335-380): decode every sub-channel announced in the FIC.
 // Follows decoder/fib_decoder.cpp:59-110 (FIG walk), fib_decoder_fig0.cpp:142-224 (FIG 0/1), :230-293 (FIG 0/2),
@@ -33,9 +33,11 @@ static unsigned bits(const uint8_t *b, int off, int n)   // MSB-first bit field 
 // FibConfigFig0 (fib_config_fig0.h) as far as the path needs it: the FIG 0/1 and FIG 0/2 vectors of ONE multiplex configuration.
 struct FibConfig {
   std::vector<dabx_subch_desc> subch;       // Fig0s1_BasicSubChannelOrganizationVec: in order of first appearance, first description of a SubChId wins
-  struct Comp { uint32_t sid; int idx, tmid, ascty, subch_id; };
+  struct Comp { uint32_t sid; int idx, tmid, ascty, subch_id, scid; };
   std::vector<Comp> comps;                  // Fig0s2_BasicService_ServiceCompDefVec: first definition of (SId, component index) wins
-  void reset() { subch.clear(); comps.clear(); }
+  struct Packet { int scid, caorg_flag, dg_flag, dscty, subch_id, address; };
+  std::vector<Packet> packets;              // Fig0s3_ServiceComponentPacketModeVec: first description of an SCId wins
+  void reset() { subch.clear(); comps.clear(); packets.clear(); }
   const dabx_subch_desc *find(int id) const { for (auto &q : subch) if (q.subch_id == id) return &q; return nullptr; }
 };
 
@@ -89,6 +91,7 @@ static void walk_fib(const uint8_t *fib, dabx_fibdec &t)
             FibConfig &nx = t.cfg[t.cur ^ 1];
             if (nx.subch.empty()) nx.subch = t.cfg[t.cur].subch;
             if (nx.comps.empty()) nx.comps = t.cfg[t.cur].comps;
+            if (nx.packets.empty()) nx.packets = t.cfg[t.cur].packets;
           }
           t.cur ^= 1;
           t.cfg[t.cur ^ 1].reset();
@@ -145,12 +148,27 @@ static void walk_fib(const uint8_t *fib, dabx_fibdec &t)
             bool known = false;
             for (auto &k : cfg.comps) if (k.sid == sid && k.idx == c) known = true;
             if (known) continue;
-            FibConfig::Comp k{sid, c, (int)bits(d, o, 2), -1, -1};
+            FibConfig::Comp k{sid, c, (int)bits(d, o, 2), -1, -1, -1};
             if (k.tmid == 0) { k.ascty = (int)bits(d, o + 2, 6); k.subch_id = (int)bits(d, o + 8, 6); }
             else if (k.tmid == 1) k.subch_id = (int)bits(d, o + 8, 6);
+            else if (k.tmid == 3) k.scid = (int)bits(d, o + 2, 12);                 // MSC packet data, :266-270
             cfg.comps.push_back(k);
           }
           used = o / 8;
+        }
+      } else if (ext == 3) {                                           // _subprocess_Fig0s3, :294-330
+        int used = 2;
+        while (used + 5 <= len + 1) {
+          const int o = used * 8;
+          FibConfig::Packet k{(int)bits(d, o, 12), 0, 0, 0, 0, 0};
+          const FibConfig::Packet *known = nullptr;
+          for (auto &q : cfg.packets) if (q.scid == k.scid) { known = &q; break; }
+          if (known) { used += 5 + (known->caorg_flag ? 2 : 0); continue; }           // :322-326: stepped over by the STORED entry's form
+          k.caorg_flag = (int)bits(d, o + 15, 1); k.dg_flag = (int)bits(d, o + 16, 1); k.dscty = (int)bits(d, o + 18, 6);
+          k.subch_id = (int)bits(d, o + 24, 6); k.address = (int)bits(d, o + 30, 10);
+          used += 5 + (k.caorg_flag ? 2 : 0);
+          if (used > len + 1) break;                                                   // its CAOrg field runs past the FIG
+          cfg.packets.push_back(k);
         }
       }
     }
@@ -242,6 +260,20 @@ int dabx_fibdec_subchannels(const dabx_fibdec *d, int next, dabx_subch_desc *out
 {
   if (!d || (!out && max_out > 0) || max_out < 0) return DABX_E_ARG;
   return table_out(d->cfg[next ? d->cur ^ 1 : d->cur], out, max_out);
+}
+
+int dabx_fibdec_packet_components(const dabx_fibdec *d, int next, dabx_packet_component *out, int max_out)
+{
+  if (!d || (!out && max_out > 0) || max_out < 0) return DABX_E_ARG;
+  const FibConfig &cfg = d->cfg[next ? d->cur ^ 1 : d->cur];
+  int n = 0;
+  for (const auto &k : cfg.packets) {
+    if (n >= max_out) break;
+    dabx_packet_component q{k.scid, k.subch_id, k.address, k.dscty, k.dg_flag, 0u};
+    for (const auto &c : cfg.comps) if (c.tmid == 3 && c.scid == k.scid) { q.sid = c.sid; break; }     // fib_decoder.cpp:362, 378
+    out[n++] = q;
+  }
+  return n;
 }
 
 // fibs: n x 32 bytes, crc_ok: n flags.  Returns the number of sub-channels of the CURRENT configuration written to out (in order of

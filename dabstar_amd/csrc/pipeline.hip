@@ -12,8 +12,10 @@
 //   k_frame_tail   fine CFO, null symbol, clock error, cursor bookkeeping (dab_processor.cpp:226-302)
 //   k_msc_frame    time de-interleave + depuncture + Viterbi + PRBS per (CIF, sub-channel) (backend.cpp:129-161)
 //   k_dabplus      super-frame sync, RS(120,110), fire code, AU CRCs (mp4processor.cpp:96-333)
+//   k_packet       packet-mode data sub-channels: packet walk, packet CRCs, assembly of the MSC data groups (data_processor.cpp:106-254)
 #include <type_traits>
 #include "pipeline.h"
+#include "packet_core.h"
 #include <algorithm>
 #include "ofdm_core.h"
 #include "viterbi_core.h"
@@ -1928,6 +1930,109 @@ __global__ __launch_bounds__(64, 4) void k_dabplus(EngineDev e, DevTables t)   /
   }
 }
 
+// ------------------------------------------------------------------------------------------ packet mode
+// One wave per packet-mode slot (PacketDev::slots: those slots only); walks the logical frames the decoder produced in this batch step, in
+// order, exactly the frames k_dabplus counts for the slot (it runs in front of k_dabplus, which moves cif_out on).  Per frame: the frame is
+// staged in LDS; lane g reads the length code of granule g and the packet boundaries follow from two ballots (pkt_walk: scalar), and runs the
+// CCITT register over its granule; the lanes at packet starts fold the packet CRC from their granules' registers and, for packets that pass
+// it, the register over the payload from 0 (pkt_describe: all packets of the frame in parallel, tables in LDS); the state machine (data_processor.cpp:165-253) then runs wave-uniform over header fields only --
+// the data-group CRC register is carried from packet to packet with one multiplication by x^(8 n) -- and every accepted payload is copied
+// by the whole wave to its place in the slot's byte ring.  include/dabx.h states the semantics and the two guards.
+__global__ __launch_bounds__(64) void k_packet(PacketDev pk)
+{
+  const int lane = threadIdx.x;
+  PacketSlot &ps = pk.slots[blockIdx.x];
+  const SubchDev &sc = pk.subch[(size_t)ps.s * pk.max_subch + ps.j];
+  if (!sc.active) return;
+  const BatchSnap bs = pk.snap[ps.s];
+  long long n_new = 0;                        // logical frames the decoder just produced for this sub-channel (as k_dabplus counts them)
+  for (long long r = bs.msc_done; r < bs.cif_no; r++) if (r >= sc.start_cif + 16) n_new++;
+  if (n_new == 0) return;
+  const int nbytes = 3 * sc.kbps, n_gran = sc.kbps / 8;       // <= 1152 bytes, <= 48 granules (dabx_set_packet_mode)
+  const uint8_t *ring = pk.msc_out + ((size_t)ps.s * pk.max_subch + ps.j) * MSC_SLOTS * pk.msc_stride;
+  __shared__ __attribute__((aligned(16))) uint8_t frm[3 * PKT_MAX_KBPS];
+  __shared__ uint16_t s_crc[256], s_xpow[128];               // CCITT table; x^(8 m) mod P for m = useful length <= 127
+  __shared__ unsigned s_info[64];
+  __shared__ uint16_t s_part[64];                             // the CCITT register from 0 over every granule of the frame
+  for (int i = lane; i < 256; i += 64) s_crc[i] = pk.crc_ccitt[i];
+  for (int i = lane; i < 128; i += 64) s_xpow[i] = pk.crc_xpow[i];
+  const int address = ps.address;
+  uint8_t *const dg_ring = ps.bytes;                         // (locals: the stores below must not make the loop reload them from the table)
+  dabx_datagroup_info *const dg_recs = ps.recs;
+  const unsigned long long bytes_mask = ps.bytes_mask, rec_mask = ps.rec_mask;
+  int expected = ps.expected, state = ps.state, fill = ps.fill, first_byte = ps.first_byte;
+  unsigned run_crc = ps.run_crc;
+  long long first_frame = ps.first_frame, dg_count = ps.dg_count, dg_bytes = ps.dg_bytes;
+  long long packets = 0, addr_match = 0, continuity_err = 0, crc_bad = 0, len_bad = 0, walk_short = 0, dg_crc_bad = 0, dg_overflow = 0;
+  const long long frame0 = sc.cif_out;
+  for (long long n = 0; n < n_new; n++) {
+    const long long frame = frame0 + n;      // index of the logical frame in the slot's sequence
+    __syncthreads();                          // the previous frame (and the tables) are done with
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(ring + (size_t)(frame % MSC_SLOTS) * pk.msc_stride);
+    for (int i = lane; i < nbytes / 4; i += 64) reinterpret_cast<uint32_t *>(frm)[i] = src[i];
+    __syncthreads();
+    const unsigned code = lane < n_gran ? (unsigned)(frm[lane * PKT_GRANULE] >> 6) : 0u;
+    s_part[lane] = lane < n_gran ? (uint16_t)pkt_granule_crc(frm, lane, s_crc) : (uint16_t)0;
+    bool short_walk;
+    const unsigned long long starts = pkt_walk(__ballot(code & 1u), __ballot(code & 2u), n_gran, &short_walk);
+    __syncthreads();
+    s_info[lane] = ((starts >> lane) & 1ull) ? pkt_describe(frm, lane, nbytes, address, s_crc, s_part, s_xpow) : 0u;
+    __syncthreads();
+    packets += __popcll(starts);
+    walk_short += short_walk ? 1 : 0;
+    for (unsigned long long m = starts; m; m &= m - 1) {
+      const int g = __ffsll((long long)m) - 1;
+      const unsigned inf = s_info[g];
+      if (!(inf & 1u)) continue;                                                            // :165 another address
+      addr_match++;
+      if ((int)((inf >> 3) & 3u) != expected) { continuity_err++; expected = 0; continue; }   // :170-178
+      expected = (expected + 1) & 3;                                                        // :181, before the CRC
+      if (!(inf & 2u)) { crc_bad++; continue; }                                             // :184-187
+      if (!(inf & 4u)) { len_bad++; continue; }                                             // guard: the payload would pass the end of the logical frame
+      const int fl = (int)((inf >> 5) & 3u), ulen = (int)((inf >> 7) & 0x7Fu);
+      bool start = false, append = false, emit = false;
+      if (state == 0) {                                                                     // :191-215 waiting for a start
+        if (fl == 2) { start = true; state = 1; }
+        else if (fl == 3) { start = true; emit = true; }
+        else fill = 0;
+      } else {                                                                              // :216-253 within a series
+        if (fl == 0) append = true;
+        else if (fl == 1) { append = true; emit = true; }
+        else if (fl == 2) start = true;
+        else { state = 0; fill = 0; }
+      }
+      if (append && fill + ulen > DABX_DG_MAX_BYTES) { dg_overflow++; state = 0; fill = 0; continue; }   // guard: bounded assembly
+      if (start) { fill = 0; run_crc = 0xFFFFu; first_frame = frame; first_byte = -1; }
+      if (start || append) {
+        const int from = g * PKT_GRANULE + 3;
+        for (int i = lane; i < ulen; i += 64) dg_ring[(size_t)((unsigned long long)(dg_bytes + fill + i) & bytes_mask)] = frm[from + i];
+        if (fill == 0 && ulen > 0) first_byte = frm[from];
+        run_crc = crc_mulmod(run_crc, s_xpow[ulen]) ^ (inf >> 16);
+        fill += ulen;
+      }
+      if (emit) {
+        const bool flag = first_byte >= 0 && (first_byte & 0x40);
+        const bool good = flag && fill >= 2 && run_crc == PKT_CRC_RESIDUE;
+        if (lane == 0) {
+          dabx_datagroup_info r;
+          r.byte_pos = dg_bytes; r.first_frame = first_frame; r.last_frame = frame; r.length = (uint16_t)fill;
+          r.crc_flag = flag ? 1 : 0; r.crc_ok = good ? 1 : 0; r.reserved = 0;
+          dg_recs[(size_t)((unsigned long long)dg_count & rec_mask)] = r;
+        }
+        dg_crc_bad += (flag && !good) ? 1 : 0;
+        dg_count++; dg_bytes += fill;
+        fill = 0; state = 0;
+      }
+    }
+  }
+  if (lane == 0) {
+    ps.expected = expected; ps.state = state; ps.fill = fill; ps.first_byte = first_byte; ps.run_crc = run_crc;
+    ps.first_frame = first_frame; ps.dg_count = dg_count; ps.dg_bytes = dg_bytes;
+    ps.frames += n_new; ps.packets += packets; ps.addr_match += addr_match; ps.continuity_err += continuity_err; ps.crc_bad += crc_bad;
+    ps.len_bad += len_bad; ps.walk_short += walk_short; ps.dg_crc_bad += dg_crc_bad; ps.dg_overflow += dg_overflow;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------- launchers
 __global__ void k_msc_snap(EngineDev e, int cifs)
 {
@@ -1943,10 +2048,10 @@ __global__ void k_msc_done(EngineDev e)
   if (s < e.n_streams) e.ctl[s].msc_done_cif = e.snap[s].cif_no;
 }
 
-extern const char *const kStepKernelNames[11];
+extern const char *const kStepKernelNames[N_STEP_KERNELS];
 // "k_demap_fic": the first k_demap_frame launch of a frame (symbols 1..3) when the FIC is decoded on its own stream
-const char *const kStepKernelNames[11] = {"k_acquire", "k_frame_head", "k_symbols", "k_demap_frame", "k_fic_frame",
-                                          "k_frame_tail", "k_msc_prep", "k_msc_vitT", "k_msc_frame", "k_dabplus", "k_demap_fic"};
+const char *const kStepKernelNames[N_STEP_KERNELS] = {"k_acquire", "k_frame_head", "k_symbols", "k_demap_frame", "k_fic_frame", "k_frame_tail",
+                                                      "k_msc_prep", "k_msc_vitT", "k_msc_frame", "k_dabplus", "k_demap_fic", "k_packet"};
 
 // Front end of one batch step (everything with frame-to-frame feedback).
 // Overlapped schedule (ss.d set): the FIC lives in symbols 1..3 -- those are demapped first on the front-end stream a, then
@@ -2066,9 +2171,13 @@ int launch_msc_vitT(const EngineDev &e, int cifs, const MscLaunch &L, hipStream_
 // `e.snap` must point at the snapshot buffer of this batch.
 int launch_deliver_msc(const EngineDev &e, const DeliverDev &dv, hipStream_t st, bool with_lf);
 int launch_deliver_lf(const EngineDev &e, const DeliverDev &dv, hipStream_t st);
+int launch_deliver_dg(const EngineDev &e, const DeliverDev &dv, const PacketDev &pk, hipStream_t st);
 // `dv` (optional): the chunk's slot gather (deliver.hip) goes behind the DAB+ stage on the stream that ran it, before the batch's
 // completion event; *tail (optional) = the stream whose work completes the batch.
-int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineStreams &ss, Marker &mk, const DeliverDev *dv, hipStream_t *tail)
+// `pk` (optional): the engine has packet-mode slots -- k_packet walks their new logical frames, in front of k_dabplus (which moves the
+// slots' frame counters on); null = no launch.
+int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineStreams &ss, Marker &mk, const DeliverDev *dv, hipStream_t *tail,
+                     const PacketDev *pk)
 {
   const DevTables *t;
   int rc = get_tables(&t);
@@ -2152,11 +2261,21 @@ int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineSt
   }
   // the chunk's logical frames exist: into the slab with them, their share of the transfer starts while the DAB+ stage runs (deliver.hip)
   if (dv && (rc = launch_deliver_lf(e, *dv, sb))) return rc;
+  PacketDev p{};
+  if (pk && pk->n > 0) {
+    p = *pk;
+    p.max_subch = e.max_subch; p.msc_stride = e.msc_stride; p.subch = e.subch; p.snap = e.snap; p.msc_out = e.msc_out;
+    p.crc_ccitt = t->crc_ccitt; p.crc_xpow = t->crc_xpow;
+    mk.begin(11, sb);
+    hipLaunchKernelGGL(k_packet, dim3(p.n), dim3(64), 0, sb, p);
+    mk.end(11, sb);
+  }
   mk.begin(9, sb);
   hipLaunchKernelGGL(k_dabplus, dim3(e.n_streams * e.max_subch), dim3(64), 0, sb, e, *t);
   hipLaunchKernelGGL(k_msc_done, dim3((e.n_streams + 255) / 256), dim3(256), 0, sb, e);
   mk.end(9, sb);
   if (dv && (rc = launch_deliver_msc(e, *dv, sb, !dv->lf_done))) return rc;
+  if (dv && p.n > 0 && (rc = launch_deliver_dg(e, *dv, p, sb))) return rc;      // the slab's data-group section (head part, like the gather in front)
   if (tail) *tail = sb;
   if (ss.b) {
     DABX_HIP(hipEventRecord(ss.msc_done, ss.b));

@@ -60,6 +60,11 @@ def load(build_if_missing=True):
         L.dabx_delivery_slab_bytes.argtypes = [C.c_void_p]
         L.dabx_delivery_wait_free.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.dabx_delivery_slab_bytes.restype = C.c_longlong
+    if hasattr(L, "dabx_set_packet_mode"):           # packet-mode data sub-channels
+        L.dabx_set_packet_mode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.dabx_read_datagroups.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.dabx_get_packet_stats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.dabx_fibdec_packet_components.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     if hasattr(L, "dabx_announce_write"):            # (absent from libraries older than the level anchor: tools/ab.sh runs those through this binding too)
         L.dabx_announce_write.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
     _LIB = L
@@ -339,11 +344,11 @@ class Stats(C.Structure):
 # ---- bulk delivery (include/dabx.h "Bulk delivery"): the slab's records as numpy dtypes -----------------------------
 CHUNK_FRAMES = 7
 CHUNK_MAGIC = 0x43584244
-DELIVER_FIB, DELIVER_MSC, DELIVER_SF, DELIVER_MSC_NOT_DABPLUS = 1, 2, 4, 8
+DELIVER_FIB, DELIVER_MSC, DELIVER_SF, DELIVER_MSC_NOT_DABPLUS, DELIVER_DG = 1, 2, 4, 8, 16
 CHUNK_HEADER = np.dtype([("magic", "<u4"), ("abi", "<u4"), ("seq", "<u8"), ("n_streams", "<i4"), ("max_subch", "<i4"),
                          ("max_frames", "<i4"), ("what", "<i4"), ("bytes", "<u8"), ("off_stream", "<u8"), ("off_subch", "<u8"),
                          ("off_fib", "<u8"), ("off_crc", "<u8"), ("off_frame", "<u8"), ("off_msc", "<u8"), ("off_sf", "<u8"),
-                         ("reserved", "<u8", 4)])
+                         ("off_dg", "<u8"), ("reserved", "<u8", 3)])
 CHUNK_STREAM = np.dtype([("first_frame", "<i8"), ("n_frames", "<i4"), ("frames_lost", "<i4"), ("state", "<i4"),
                          ("fic_ratio_percent", "<i4"), ("cif_count", "<i4"), ("snr_db_est", "<f4"), ("freq_offs_bb_hz", "<f4"),
                          ("clock_err_hz", "<f4"), ("signal_level", "<f4"), ("fic_ber_bits", "<i4"), ("fic_ber_errors", "<i4"),
@@ -359,6 +364,25 @@ SUPERFRAME_INFO = np.dtype([("num_aus", "u1"), ("au_crc_ok", "u1"), ("au_len_bad
                             ("rs_corrected", "<u2"), ("rs_failed", "u1"), ("fc_corrected", "u1"), ("reserved", "<u2"), ("first_frame", "<i8")])
 assert CHUNK_HEADER.itemsize == 128 and CHUNK_STREAM.itemsize == 72 and CHUNK_FRAME.itemsize == 16 and CHUNK_SUBCH.itemsize == 144
 assert SUPERFRAME_INFO.itemsize == 32
+# packet-mode data sub-channels (include/dabx.h): dabx_datagroup_info, one record per completed MSC data group, and dabx_packet_stats
+DG_MAX_BYTES = 16384
+DG_RING_MAX_BYTES = 131072                   # the largest byte ring of a slot (384 kbit/s: 56 logical frames + DG_MAX_BYTES, as a power of two)
+DATAGROUP_INFO = np.dtype([("byte_pos", "<i8"), ("first_frame", "<i8"), ("last_frame", "<i8"), ("length", "<u2"), ("crc_flag", "u1"),
+                           ("crc_ok", "u1"), ("reserved", "<u4")])
+PACKET_COUNTERS = ("frames", "packets", "addr_match", "continuity_err", "crc_bad", "len_bad", "walk_short", "dg_count", "dg_bytes",
+                   "dg_crc_bad", "dg_overflow")
+PACKET_STATS = np.dtype([(k, "<i8") for k in PACKET_COUNTERS + ("dg_lost",)] + [("active", "<i4"), ("packet_address", "<i4"), ("reserved", "<i8", 3)])
+PACKET_COMPONENT = np.dtype([("scid", "<i4"), ("subch_id", "<i4"), ("packet_address", "<i4"), ("dscty", "<i4"), ("dg_flag", "<i4"), ("sid", "<u4")])
+# the slab's data-group section (dabx_chunk_dg): one row per (stream, slot), all zero for a slot that is not in packet mode
+CHUNK_DG = np.dtype([("first_dg", "<i8"), ("n_dg", "<i4"), ("dg_lost", "<i4"), ("rec_off", "<u8"), ("bytes_off", "<u8"), ("n_bytes", "<i8")] +
+                    [(k, "<i8") for k in PACKET_COUNTERS])
+assert CHUNK_DG.itemsize == 128
+assert DATAGROUP_INFO.itemsize == 32 and PACKET_STATS.itemsize == 128 and PACKET_COMPONENT.itemsize == 24
+
+
+class PacketConfig(C.Structure):
+    """dabx_packet_config."""
+    _fields_ = [("size", C.c_uint32), ("packet_address", C.c_int32), ("reserved", C.c_int32 * 6)]
 
 
 class DeliveryConfig(C.Structure):
@@ -396,6 +420,9 @@ class Chunk:
             self.fibs = self.raw[int(h["off_fib"]):int(h["off_fib"]) + S * F * 384].reshape(S, F, 12, 32)
             self.crc = self.raw[int(h["off_crc"]):int(h["off_crc"]) + S * F * 12].reshape(S, F, 12)
             self.frames = self.raw[int(h["off_frame"]):int(h["off_frame"]) + S * F * 16].view(CHUNK_FRAME).reshape(S, F)
+        self.dg = None                          # the data-group section: [S, M] CHUNK_DG, or None when the slab has none
+        if int(h["off_dg"]):
+            self.dg = self.raw[int(h["off_dg"]):int(h["off_dg"]) + S * M * 128].view(CHUNK_DG).reshape(S, M)
 
     def msc(self, s, j):
         """Logical frames of slot (s, j) in this chunk: [n_cifs, 3 * kbps] uint8 (a view)."""
@@ -415,6 +442,15 @@ class Chunk:
         r = self.subch[s, j]
         o = int(r["sfi_off"])
         return self.raw[o:o + int(r["n_sf"]) * 32].view(SUPERFRAME_INFO)
+
+    def datagroups(self, s, j):
+        """MSC data groups of packet-mode slot (s, j) in this chunk: ([n_dg] DATAGROUP_INFO, their n_bytes bytes), views; group i is
+        bytes[byte_pos[i] : byte_pos[i] + length[i]].  Empty when the slab has no data-group section or the slot is not in packet mode."""
+        if self.dg is None or not int(self.dg[s, j]["rec_off"]):
+            return np.zeros(0, DATAGROUP_INFO), np.zeros(0, np.uint8)
+        r = self.dg[s, j]
+        ro, bo = int(r["rec_off"]), int(r["bytes_off"])
+        return self.raw[ro:ro + int(r["n_dg"]) * 32].view(DATAGROUP_INFO), self.raw[bo:bo + int(r["n_bytes"])]
 
     def release(self):
         if self._eng is not None:
@@ -616,6 +652,35 @@ class Engine:
         out = np.zeros(n, SUPERFRAME_INFO)
         k = check(load().dabx_read_superframe_info(self._h, stream, j, n, _p(out)))
         return out[:k]
+
+    def set_packet_mode(self, stream, j, packet_address):
+        """Slot j of `stream` becomes a packet-mode data sub-channel with this packet address (dabx_set_packet_mode); None switches it
+        back to plain logical frames."""
+        L = load()
+        if packet_address is None:
+            check(L.dabx_set_packet_mode(self._h, int(stream), int(j), None))
+        else:
+            cfg = PacketConfig(size=C.sizeof(PacketConfig), packet_address=int(packet_address))
+            check(L.dabx_set_packet_mode(self._h, int(stream), int(j), C.byref(cfg)))
+
+    def read_datagroups(self, stream, j, n=64, max_bytes=None):
+        """(records [k] DATAGROUP_INFO, bytes uint8) of the newest k <= n completed data groups of slot j, oldest first; group i is
+        bytes[byte_pos[i] : byte_pos[i] + length[i]]."""
+        L = load()
+        info = np.zeros(max(1, n), DATAGROUP_INFO)
+        if max_bytes is None:
+            max_bytes = DG_RING_MAX_BYTES                 # no slot's byte ring holds more
+        buf = np.zeros(max(1, int(max_bytes)), np.uint8)
+        k = check(L.dabx_read_datagroups(self._h, int(stream), int(j), int(n), _p(info), _p(buf), int(max_bytes)))
+        info = info[:k]
+        return info, buf[:int(info["length"].sum())].copy()
+
+    def packet_stats(self, stream, j):
+        """dabx_packet_stats of slot j as a dict."""
+        L = load()
+        out = np.zeros(1, PACKET_STATS)
+        check(L.dabx_get_packet_stats(self._h, int(stream), int(j), _p(out)))
+        return {k: int(out[0][k]) for k in PACKET_STATS.names if k != "reserved"}
 
     def read_soft(self, stream):
         out = np.zeros((75, 3072), np.int16)
@@ -832,6 +897,13 @@ class FibDecoder:
         out = (SubchDesc * max_out)()
         n = check(load().dabx_fibdec_subchannels(self._h, int(next), out, max_out))
         return [out[i] for i in range(n)]
+
+    def packet_components(self, next=False, max_out=64):
+        """FIG 0/3 (+ the SId of the FIG 0/2 TMId-3 component that names the SCId): [n] PACKET_COMPONENT."""
+        L = load()
+        out = np.zeros(max(1, max_out), PACKET_COMPONENT)
+        n = check(L.dabx_fibdec_packet_components(self._h, int(next), _p(out), max_out))
+        return out[:n]
 
     def reset(self):
         check(load().dabx_fibdec_reset(self._h))

@@ -220,6 +220,21 @@ int  dabx_fibdec_process(dabx_fibdec *d, const uint8_t *fibs, const uint8_t *crc
 int  dabx_fibdec_get_info(const dabx_fibdec *d, dabx_fibdec_info *out);
 /* sub-channel table of the current (next = 0) or the next (next = 1) configuration, like dabx_parse_fibs */
 int  dabx_fibdec_subchannels(const dabx_fibdec *d, int next, struct dabx_subch_desc_s *out, int max_out);
+/* Service components in packet mode (FIG 0/3, fib_decoder_fig0.cpp:294-330) of the current (next = 0) or the next configuration, in order of
+ * first appearance; the first description of an SCId wins (:303-321).  What a host needs to bind a packet-mode sub-channel
+ * (dabx_set_packet_mode): the sub-channel, the packet address, the data service component type and the DG flag (0 = data groups are used:
+ * the one combination DataProcessor::add_to_frame does NOT walk as packets is dscty 5 with dg_flag 1, data_processor.cpp:111).  sid is the SId
+ * of the FIG 0/2 service whose TMId-3 component names this SCId, as fib_decoder.cpp:362-411 joins the two; 0 while no such FIG 0/2 has been
+ * seen.  Returns the number of components written. */
+typedef struct {
+  int32_t  scid;             /* 12 bits */
+  int32_t  subch_id;
+  int32_t  packet_address;   /* 10 bits */
+  int32_t  dscty;
+  int32_t  dg_flag;
+  uint32_t sid;
+} dabx_packet_component;
+int  dabx_fibdec_packet_components(const dabx_fibdec *d, int next, dabx_packet_component *out, int max_out);
 
 /* ===================================================================================== engine level
  * Stream-batched receiver: the device-side equivalent of DabProcessor::run
@@ -489,6 +504,70 @@ int  dabx_get_subch_stats(dabx_engine *e, int stream, int subch_idx, dabx_subch_
 /* Sum of the counters over all streams of this engine (the values one RCCL all-reduce combines). */
 int  dabx_get_counters(dabx_engine *e, int64_t out[16]);
 /* ------------------------------------------------------------------------------------------------------------
+ * Packet-mode data sub-channels: DataProcessor (base/backend/data/data_processor.cpp:106-254), the third FrameProcessor of the
+ * reference's back end, on the device (k_packet, behind the MSC decoder of every batch, one wave per packet-mode slot).  For every
+ * logical frame of the slot, in order: the packet walk (:123-150: packet length (bits 0..1 + 1) * 24 bytes, stop when fewer bytes remain),
+ * per packet the address filter, the continuity index -- a mismatch sets the expected index to 0 and drops the packet (:170-178); the
+ * expected index advances before the CRC is looked at (:181) --, check_CRC_bits over the whole packet (:184), and the assembly of the MSC
+ * data groups from first / intermediate / last / single packets (:191-253; a single packet inside a series abandons the series and is
+ * NOT emitted, :248-252).  The payload of a packet is its `useful length` bytes from byte 3; groups are kept as packed bytes.
+ * Two guards, where the reference is undefined or unbounded:
+ *   - useful length > packet length - 5: the reference copies `useful length` bytes from byte 3 whatever follows (:199, :224).  While those
+ *     bytes lie inside the logical frame the device does the same; when they would pass the end of the logical frame (the reference reads
+ *     out of bounds) the packet is dropped like one with a failed CRC, the assembly state unchanged, and counted in len_bad;
+ *   - a series is bounded at DABX_DG_MAX_BYTES (the largest legal MSC data group is below 8.3 KB; the reference's mSeriesVec grows without
+ *     limit): an append that would exceed it abandons the series (back to "waiting for a start") and is counted in dg_overflow.
+ * Every completed group goes, bytes and one dabx_datagroup_info record, into per-slot rings sized from the bit rate (two full batches, 56
+ * logical frames, of single-packet groups fit); the assembly state lives on the device and survives batch boundaries.  A host hands
+ * bytes[byte_pos .. byte_pos + length) to its data handler and looks at crc_ok: it walks no packet and runs no CRC.
+ * Out of scope: packet-mode FEC (EN 300 401 5.3.5), the TDC asynchronous stream (:257-278), the data handlers themselves. */
+#define DABX_DG_MAX_BYTES 16384
+typedef struct {
+  uint32_t size;             /* sizeof(dabx_packet_config) of the caller */
+  int32_t  packet_address;   /* 0 .. 1023: DataProcessor::mPacketAddress (FIG 0/3, dabx_packet_component.packet_address) */
+  int32_t  reserved[6];      /* zero */
+} dabx_packet_config;
+typedef struct dabx_datagroup_info_s {
+  int64_t  byte_pos;         /* position of the group's first byte in the slot's sequence of data-group bytes */
+  int64_t  first_frame;      /* logical-frame index, as in dabx_superframe_info, of the packet that started the group */
+  int64_t  last_frame;       /* ... of the packet that completed it */
+  uint16_t length;           /* bytes */
+  uint8_t  crc_flag;         /* bit 6 of byte 0 of the group: a data-group CRC is present (what ip_datahandler.cpp:48 reads); 0 for an empty group */
+  uint8_t  crc_ok;           /* crc_flag set, length >= 2 and the CCITT check over the whole group passed (ip_datahandler.cpp:59); 0 otherwise */
+  uint32_t reserved;
+} dabx_datagroup_info;       /* 32 bytes, little-endian, no holes */
+typedef struct {
+  int64_t frames;            /* logical frames walked */
+  int64_t packets;           /* packets the walk handed on (_handle_packet calls) */
+  int64_t addr_match;        /* ... whose address was the slot's */
+  int64_t continuity_err;    /* ... dropped for their continuity index */
+  int64_t crc_bad;           /* ... dropped for their CRC */
+  int64_t len_bad;           /* ... dropped because their useful length reaches beyond the logical frame (guard) */
+  int64_t walk_short;        /* frames whose walk ended at a length code that overruns the frame (:129-133) */
+  int64_t dg_count;          /* groups completed */
+  int64_t dg_bytes;          /* ... and their bytes */
+  int64_t dg_crc_bad;        /* ... of them, with the CRC flag set and crc_ok == 0 */
+  int64_t dg_overflow;       /* series abandoned at DABX_DG_MAX_BYTES (guard) */
+  int64_t dg_lost;           /* groups that had left the rings before a dabx_read_datagroups call could return them */
+  int32_t active;            /* 1: the slot is in packet mode (all else is zero otherwise) */
+  int32_t packet_address;
+  int64_t reserved[3];
+} dabx_packet_stats;         /* 128 bytes */
+/* Switches slot subch_idx of `stream` to packet mode (cfg != NULL) or back to plain logical frames (NULL).  Only an active slot with
+ * dab_plus == 0 and a bit rate that is a multiple of 8 up to 384 kbit/s; DABX_E_ARG otherwise.  The slot's logical frames are produced and
+ * delivered exactly as before; the walk starts with the next logical frame decoded.  Calling it again for a slot in packet mode restarts
+ * the assembly with the new address and empty rings.  The setting and the assembly state stay with the slot wherever dabx_set_subchannels
+ * says it "keeps decoding without interruption", a move to other capacity units included; a new or changed slot loses them.  An engine
+ * without a packet-mode slot allocates and launches nothing for this stage.  Drains the engine. */
+int  dabx_set_packet_mode(dabx_engine *e, int stream, int subch_idx, const dabx_packet_config *cfg);
+/* The newest n completed groups still in the rings, oldest first: their records into info[], their bytes back to back into bytes[];
+ * byte_pos is rebased to the returned buffer (info[0].byte_pos == 0).  When the bytes of n groups exceed max_bytes the newest groups that
+ * fit are returned (bytes == NULL: records only, byte_pos rebased all the same).  Returns the number of groups.  Groups older than
+ * the ones returned count as seen; groups that left the rings unseen are counted in dabx_packet_stats.dg_lost.  Drains the engine like
+ * the other dabx_read_* calls. */
+int  dabx_read_datagroups(dabx_engine *e, int stream, int subch_idx, int n, dabx_datagroup_info *info, uint8_t *bytes, size_t max_bytes);
+int  dabx_get_packet_stats(dabx_engine *e, int stream, int subch_idx, dabx_packet_stats *out);
+/* ------------------------------------------------------------------------------------------------------------
  * Bulk delivery of the results to the host.  The reference hands every FIB to IFibDecoder::process_FIB
  * (base/decoder/fib_decoder_if.h:81, called from fic_decoder.cpp:234-261) and every logical frame to
  * FrameProcessor::add_to_frame (base/backend/frame_processor.h:43-46, called from backend.cpp:160) the moment it exists;
@@ -520,7 +599,11 @@ enum { DABX_DELIVER_FIB = 1, DABX_DELIVER_MSC = 2, DABX_DELIVER_SF = 4,
        /* logical frames only of the slots that are NOT DAB+ (instead of DABX_DELIVER_MSC): for a DAB+ service the logical frames' consumer,
           Mp4Processor, runs on the device and the host's input is the super frame -- FIB | SF | this = what a receiver's host side needs,
           half the bytes of "everything" for a DAB+ multiplex */
-       DABX_DELIVER_MSC_NOT_DABPLUS = 8 };
+       DABX_DELIVER_MSC_NOT_DABPLUS = 8,
+       /* the MSC data groups of the packet-mode slots (dabx_set_packet_mode): with this bit, or with what == 0, AND at least one packet-mode
+          slot the slab gains a data-group section (dabx_chunk_dg below) and dabx_chunk_header.what shows the bit; without a packet-mode slot
+          a slab is byte for byte what it is without the bit, dabx_delivery_slab_bytes included */
+       DABX_DELIVER_DG = 16 };
 typedef struct {
   int32_t host_slabs;       /* page-locked host slabs, >= 2 (0 = default 4) */
   int32_t what;             /* DABX_DELIVER_* mask, 0 = everything */
@@ -535,7 +618,8 @@ typedef struct {
   int32_t  n_streams, max_subch, max_frames /* DABX_CHUNK_FRAMES */, what;
   uint64_t bytes;           /* size of the slab as copied */
   uint64_t off_stream, off_subch, off_fib, off_crc, off_frame, off_msc, off_sf;
-  uint64_t reserved[4];
+  uint64_t off_dg;          /* the data-group section: dabx_chunk_dg[n_streams * max_subch]; 0 = the slab has none */
+  uint64_t reserved[3];
 } dabx_chunk_header;        /* 128 bytes */
 typedef struct {
   int64_t first_frame;      /* index, since the stream was opened, of the first frame in the chunk */
@@ -568,6 +652,21 @@ typedef struct {
   int64_t sf_ok, sf_fail, rs_corrected, rs_failed, fc_corrected, au_ok, au_bad;      /* cumulative, as dabx_subch_stats */
   uint64_t sfi_off;         /* n_sf dabx_superframe_info records, row i for super-frame row i (ABI 6) */
 } dabx_chunk_subch;         /* 144 bytes */
+/* The data-group section (DABX_DELIVER_DG): one dabx_chunk_dg per (stream, slot) from off_dg, all zero for a slot that is not in packet
+ * mode; behind the table, per packet-mode slot, room for one record per possible packet of a chunk (4 * max_frames * kbps / 8
+ * dabx_datagroup_info from rec_off) and for the chunk's logical-frame bytes plus DABX_DG_MAX_BYTES (from bytes_off): fixed by the
+ * configuration like the rest of the slab.  It lies in the slab's head part, in front of off_msc, and is gathered behind k_deliver_msc.
+ * The chunk carries the n_dg groups first_dg .. first_dg + n_dg - 1 of the slot's sequence, completed since the previous chunk: group i is
+ * the n-th record's bytes_off + byte_pos .. + length (byte_pos counts from bytes_off; in the slot's own sequence the chunk's first byte
+ * is byte dg_bytes - n_bytes).  dg_lost: groups completed since the previous chunk that are not in this one (they had left the slot's rings,
+ * or -- useful lengths beyond the packets -- did not fit the room).  The counters are cumulative, as dabx_packet_stats. */
+typedef struct {
+  int64_t  first_dg;
+  int32_t  n_dg, dg_lost;
+  uint64_t rec_off, bytes_off;
+  int64_t  n_bytes;
+  int64_t  frames, packets, addr_match, continuity_err, crc_bad, len_bad, walk_short, dg_count, dg_bytes, dg_crc_bad, dg_overflow;
+} dabx_chunk_dg;            /* 128 bytes */
 typedef struct {
   uint64_t seq;
   const void *data;         /* the host slab: valid until dabx_delivery_release(seq) */

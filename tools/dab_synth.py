@@ -342,7 +342,10 @@ def _ofdm_frames(tx_bits: np.ndarray, n_frames: int, cyclic: bool, cif_start: in
 
 
 def build_ensemble(n_frames: int = 10, subch: list | None = None, seed: int = 0, cyclic: bool = True,
-                   cif_start: int = 0, tii: list | None = None) -> Ensemble:
+                   cif_start: int = 0, tii: list | None = None, payloads: dict | None = None) -> Ensemble:
+    """payloads (optional): {index into subch: [4 * n_frames, 3 * kbps] uint8}, the logical frames of that sub-channel (a packet-mode data
+    sub-channel, say) instead of the generated ones.  The generated bytes of every other sub-channel are those of the same call without
+    it: the random stream is drawn for the replaced sub-channels too."""
     subch = default_subchannels() if subch is None else subch
     rng = np.random.default_rng(seed)
     n_cif = 4 * n_frames
@@ -357,6 +360,9 @@ def build_ensemble(n_frames: int = 10, subch: list | None = None, seed: int = 0,
         n_sf = (n_cif + 4) // 5
         sfs = [build_superframe(c.kbps, rng) if c.dab_plus else rng.integers(0, 256, 15 * c.kbps).astype(np.uint8) for _ in range(n_sf)]
         stream = np.concatenate(sfs)[: n_cif * nb].reshape(n_cif, nb)
+        if payloads is not None and len(msc_bytes) in payloads:
+            stream = np.ascontiguousarray(payloads[len(msc_bytes)], np.uint8)
+            assert stream.shape == (n_cif, nb), (stream.shape, n_cif, nb)
         msc_bytes.append(stream.copy())
         superframes.append(np.stack([s[: 110 * (c.kbps // 8)] for s in sfs[: n_cif // 5]]) if n_cif >= 5 else np.zeros((0, 0), np.uint8))
         mask = (eep_mask(c.kbps, c.prot_level) if c.mask is None else np.asarray(c.mask)).astype(bool)
@@ -424,6 +430,31 @@ def fig02_bytes(chs, cn: int = 0) -> bytes:
     return bytes([len(body)]) + bytes(body)
 
 
+def fig02_packet_bytes(services, cn: int = 0, pd: int = 0) -> bytes:
+    """FIG 0/2 (EN 300 401 6.3.1) for services whose components are in packet mode: services = [(SId, [SCId, ...])], every component
+    TMId 3 with its 12-bit SCId.  pd = 1: 32-bit SIds (data services)."""
+    body = bytearray([(cn << 7) | (pd << 5) | 0x02])
+    for sid, scids in services:
+        body += sid.to_bytes(4 if pd else 2, "big") + bytes([len(scids) & 0xF])
+        for i, scid in enumerate(scids):
+            comp = (3 << 14) | ((scid & 0xFFF) << 2) | ((1 if i == 0 else 0) << 1)
+            body += bytes([comp >> 8, comp & 0xFF])
+    return bytes([len(body)]) + bytes(body)
+
+
+def fig03_bytes(comps, cn: int = 0, pd: int = 0) -> bytes:
+    """FIG 0/3 (EN 300 401 6.3.2), service components in packet mode: comps = [(SCId, SubChId, packet address, DSCTy, DG flag, CAOrg or
+    None)]; a CAOrg value sets the CAOrg flag and appends the 16-bit field."""
+    body = bytearray([(cn << 7) | (pd << 5) | 0x03])
+    for scid, subch_id, address, dscty, dg_flag, caorg in comps:
+        w = ((scid & 0xFFF) << 28) | ((1 if caorg is not None else 0) << 24) | ((dg_flag & 1) << 23) | ((dscty & 0x3F) << 16) | \
+            ((subch_id & 0x3F) << 10) | (address & 0x3FF)
+        body += w.to_bytes(5, "big")
+        if caorg is not None:
+            body += (caorg & 0xFFFF).to_bytes(2, "big")
+    return bytes([len(body)]) + bytes(body)
+
+
 def pack_fibs(figs: list) -> np.ndarray:
     """FIGs (header included, in order) into the three FIBs of one CIF: end marker, padding, CRC.  96 bytes."""
     fibs, cur = [], b""
@@ -479,13 +510,15 @@ def _same_desc(x, y):
 
 
 def build_reconfigured_ensemble(n_frames: int, subch_a: list, subch_b: list, switch_frame: int, announce_frames: int = 8,
-                                seed: int = 0, cif_start: int = 0, switch_cif_in_frame: int = 0) -> ReconfEnsemble:
+                                seed: int = 0, cif_start: int = 0, switch_cif_in_frame: int = 0, payloads: dict | None = None) -> ReconfEnsemble:
     """A multiplex reconfiguration (EN 300 401 6.5) at CIF switch_cif_in_frame (0..3) of frame switch_frame: layout A before, layout B from then on,
     announced for announce_frames frames in advance (FIG 0/0 change flags 3 + OccurrenceChange, the next configuration's FIG 0/1
     and 0/2 with C/N = 1); afterwards the flags are 0 and B is the current configuration.  Sub-channels described identically in
     A and B run through (same convolutional interleaver, no gap), and so does one that only moves to other capacity units (its bits are
     sent at the new address from the switch on); one that ends has its last 15 logical frames cut off in
-    the air (their later interleaver branches fall on CUs that belong to B); one that begins starts its interleaver at the switch."""
+    the air (their later interleaver branches fall on CUs that belong to B); one that begins starts its interleaver at the switch.
+    payloads (optional): {SubChId of a sub-channel of layout A: [4 * n_frames, 3 * kbps] uint8}, its logical frames instead of the generated ones
+    (the random stream is drawn all the same)."""
     rng = np.random.default_rng(seed)
     n_cif, N = 4 * n_frames, 4 * switch_frame + switch_cif_in_frame
     through = [c for c in subch_a if any(_same_desc(c, d) for d in subch_b)]
@@ -509,6 +542,9 @@ def build_reconfigured_ensemble(n_frames: int, subch_a: list, subch_b: list, swi
         n_sf = (n + 4) // 5
         sfs = [build_superframe(c.kbps, rng) if c.dab_plus else rng.integers(0, 256, 15 * c.kbps).astype(np.uint8) for _ in range(n_sf)]
         stream = np.concatenate(sfs)[: n * nb].reshape(n, nb)
+        if payloads is not None and first == 0 and c.subch_id in payloads:
+            stream = np.ascontiguousarray(payloads[c.subch_id], np.uint8)[first:last]
+            assert stream.shape == (n, nb), (stream.shape, n, nb)
         mask = (eep_mask(c.kbps, c.prot_level) if c.mask is None else np.asarray(c.mask)).astype(bool)
         disp = prbs(24 * c.kbps)
         out = rng.integers(0, 2, (n_cif, 64 * c.cu_size), dtype=np.uint8)          # what is not payload is random
