@@ -7,6 +7,7 @@
 // frames' bytes again, RS-corrected) -- 0.7 % of the chain's algorithmic bytes.
 #include "pipeline.h"
 #include "packet_core.h"
+#include "pad_core.h"
 
 namespace dabx {
 
@@ -204,6 +205,57 @@ int launch_deliver_dg(const EngineDev &e, const DeliverDev &dv, const PacketDev 
   if (!dv.hdr.off_dg || pk.n <= 0) return 0;
   DABX_HIP(hipMemsetAsync(dv.slab + dv.hdr.off_dg, 0, sizeof(dabx_chunk_dg) * (size_t)e.n_streams * e.max_subch, st));
   hipLaunchKernelGGL(k_deliver_dg, dim3(pk.n), dim3(64), 0, st, pk, dv.slab, (unsigned long long)dv.hdr.off_dg);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+
+// The PAD section (include/dabx.h, dabx_chunk_pad): one wave per PAD slot, behind k_deliver_dg of the chunk, the twin of k_deliver_dg.  The
+// items emitted since the previous chunk -- as many of the newest as are still intact in the slot's rings and fit its room in the slab --
+// go out of the two rings: records with byte_pos counted from the slot's bytes in the slab.
+__global__ __launch_bounds__(64) void k_deliver_pad(PadDev pd, uint8_t *slab, unsigned long long off_pad)
+{
+  const int lane = threadIdx.x;
+  PadSlot &ps = pd.slots[blockIdx.x];
+  if (!ps.dl_item_off) return;
+  const long long count = ps.item_count, n_all = ps.item_bytes, done = ps.dl_done;
+  const unsigned long long item_mask = ps.item_mask, bytes_mask = ps.bytes_mask;
+  const dabx_pad_item *items = ps.items;
+  const uint8_t *ring = ps.bytes;
+  long long first = done;
+  if (count - first > (long long)ps.dl_item_cap) first = count - ps.dl_item_cap;
+  if (count - first > (long long)item_mask + 1) first = count - ((long long)item_mask + 1);
+  // the group under assembly may have been written up to PAD_ASM_ROOM bytes from item_bytes on: what that range covers in the ring is gone
+  while (first < count) {
+    const long long pos = items[(size_t)((unsigned long long)first & item_mask)].byte_pos;
+    if (n_all + PAD_ASM_ROOM - pos <= (long long)bytes_mask + 1 && n_all - pos <= (long long)ps.dl_bytes_cap) break;
+    first++;
+  }
+  const int n = (int)(count - first);
+  const long long base = n ? items[(size_t)((unsigned long long)first & item_mask)].byte_pos : n_all;
+  const long long n_bytes = n_all - base;
+  dabx_pad_item *ro = reinterpret_cast<dabx_pad_item *>(slab + ps.dl_item_off);
+  for (int i = lane; i < n; i += 64) {
+    dabx_pad_item r = items[(size_t)((unsigned long long)(first + i) & item_mask)];
+    r.byte_pos -= base;
+    ro[i] = r;
+  }
+  uint8_t *bo = slab + ps.dl_bytes_off;
+  for (long long k = lane; k < n_bytes; k += 64) bo[k] = ring[(size_t)((unsigned long long)(base + k) & bytes_mask)];
+  if (lane == 0) {
+    dabx_chunk_pad t;
+    t.first_item = first; t.n_items = n; t.items_lost = (int)(first - done); t.item_off = ps.dl_item_off; t.bytes_off = ps.dl_bytes_off; t.n_bytes = n_bytes;
+    t.superframes = ps.c.superframes; t.aus = ps.c.aus; t.pad_aus = ps.c.pad_aus; t.pad_bad = ps.c.pad_bad; t.labels = ps.c.labels;
+    t.label_bytes = ps.c.label_bytes; t.groups = ps.c.groups; t.group_bytes = ps.c.group_bytes; t.dg_crc_bad = ps.c.dg_crc_bad;
+    t.dl_overflow = ps.c.dl_overflow; t.li_bad = ps.c.li_bad;
+    reinterpret_cast<dabx_chunk_pad *>(slab + off_pad)[(size_t)ps.s * pd.max_subch + ps.j] = t;
+    ps.dl_done = count;
+  }
+}
+int launch_deliver_pad(const EngineDev &e, const DeliverDev &dv, const PadDev &pd, hipStream_t st)
+{
+  if (!dv.hdr.off_pad || pd.n <= 0) return 0;
+  DABX_HIP(hipMemsetAsync(dv.slab + dv.hdr.off_pad, 0, sizeof(dabx_chunk_pad) * (size_t)e.n_streams * e.max_subch, st));
+  hipLaunchKernelGGL(k_deliver_pad, dim3(pd.n), dim3(64), 0, st, pd, dv.slab, (unsigned long long)dv.hdr.off_pad);
   DABX_HIP(hipGetLastError());
   return 0;
 }

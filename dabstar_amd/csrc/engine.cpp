@@ -1,6 +1,7 @@
 // engine.cpp -- host side of the stream-batched receiver and the engine-level C ABI (include/dabx.h).
 #include "pipeline.h"
 #include "packet_core.h"
+#include "pad_core.h"
 #include "viterbi_core.h"
 #include "sdma.h"
 #include "iqfile.h"
@@ -23,7 +24,7 @@
 namespace dabx {
 int launch_front_step(const EngineDev &e, EngineStreams &ss, Marker &mk, bool async_acquire, bool all_locked);
 int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineStreams &ss, Marker &mk, const DeliverDev *dv = nullptr,
-                     hipStream_t *tail = nullptr, const PacketDev *pk = nullptr);
+                     hipStream_t *tail = nullptr, const PacketDev *pk = nullptr, const PadDev *pad = nullptr);
 int launch_deliver_front(const EngineDev &e, const DeliverDev &dv, hipStream_t st);
 void dabx_internal_fibdec_skip(dabx_fibdec *d, long long n_fibs);     // fib.cpp: FIBs the decoder never saw (they had left the ring)
 int launch_dciq(const EngineDev &e, int mode, hipStream_t st);
@@ -71,6 +72,7 @@ struct Delivery {
   int32_t *subch_id = nullptr;
   long long *frames_done = nullptr, *cif_done = nullptr, *sf_done = nullptr;
   dabx_chunk_header hdr{};
+  bool want_pad = false;                         // DABX_DELIVER_PAD, or what == 0: a PAD section while there are PAD slots
   bool want_dg = false;                          // DABX_DELIVER_DG, or what == 0: a data-group section while there are packet-mode slots
 };
 
@@ -164,6 +166,15 @@ struct dabx_engine : dabx::EngineHead {          // (iqfile.h: the ring format, 
   int packet_download();
   int packet_upload();
   void packet_drop(size_t sj);
+  // PAD slots (include/dabx.h "Programme-associated data", k_pad): the same arrangement.  Nothing exists until the first dabx_set_pad_mode.
+  struct PadHost { bool on = false; PadSlot st{}; long long seen = 0, lost = 0; };
+  std::vector<PadHost> pad;                    // [S][max_subch], or empty
+  std::vector<int> pad_index;                  // [S][max_subch] place in the job table, -1 = no PAD decoding
+  PadDev pad_dev{};
+  int pad_cap = 0;
+  int pad_download();
+  int pad_upload();
+  void pad_drop(size_t sj);
   int build_msc_classes();
   int delivery_layout();                       // offsets of every slot's bytes in a slab for the sub-channels configured now
   int delivery_begin(DeliverDev *dv, int *slot, int *devslab);     // a chunk closes: host + device slab, front gather on stream a
@@ -369,6 +380,21 @@ int dabx_engine::delivery_layout()
       st.dl_bytes_off = off; off = align_up(off + st.dl_bytes_cap, 16);
     }
   }
+  // the PAD section (dabx_chunk_pad): only with PAD slots, behind the data-group section; its room per slot is pad_core.h's per-batch bound
+  bool any_pad = false;
+  for (auto &q : pad) { q.st.dl_item_off = q.st.dl_bytes_off = 0; q.st.dl_item_cap = q.st.dl_bytes_cap = 0; any_pad = any_pad || q.on; }
+  if (D.want_pad && any_pad && !d.fic_only) {
+    off = align_up(off, 16);
+    h.off_pad = off; off += S * M * sizeof(dabx_chunk_pad);
+    h.what |= DABX_DELIVER_PAD;
+    for (size_t sj = 0; sj < S * M; sj++) {
+      if (!pad[sj].on) continue;
+      PadSlot &st = pad[sj].st;
+      st.dl_item_cap = PAD_DL_ITEM_CAP; st.dl_bytes_cap = PAD_DL_BYTES_CAP;
+      st.dl_item_off = off; off += (size_t)st.dl_item_cap * sizeof(dabx_pad_item);
+      st.dl_bytes_off = off; off = align_up(off + st.dl_bytes_cap, 16);
+    }
+  }
   off = align_up(off, 256);
   h.off_msc = off;
   if ((D.what & (DABX_DELIVER_MSC | DABX_DELIVER_MSC_NOT_DABPLUS)) && !d.fic_only)
@@ -387,6 +413,7 @@ int dabx_engine::delivery_layout()
   D.hdr = h;
   D.bytes = off;
   if (!pkt.empty()) if (int rc = packet_upload()) return rc;
+  if (!pad.empty()) if (int rc = pad_upload()) return rc;
   if (S * M) {
     DABX_HIP(hipMemcpy(D.layout_off, lo.data(), sizeof(unsigned long long) * 3 * S * M, hipMemcpyHostToDevice));
     std::vector<int32_t> ids(subch_id_host.begin(), subch_id_host.begin() + S * M);
@@ -832,6 +859,8 @@ void dabx_destroy(dabx_engine *e)
   }
   for (size_t sj = 0; sj < e->pkt.size(); sj++) e->packet_drop(sj);
   if (e->pkt_dev.slots) (void)hipFree(e->pkt_dev.slots);
+  for (size_t sj = 0; sj < e->pad.size(); sj++) e->pad_drop(sj);
+  if (e->pad_dev.slots) (void)hipFree(e->pad_dev.slots);
   for (void *p : e->allocs) (void)hipFree(p);
   if (e->locked_host) (void)hipHostFree(e->locked_host);
   if (e->seq_timeouts_host) (void)hipHostFree(e->seq_timeouts_host);
@@ -862,6 +891,7 @@ static int set_subchannels_impl(dabx_engine *e, int stream, const dabx_subch_des
   // refresh the host mirror: the device owns the dynamic fields (cif_out, super-frame state, counters)
   DABX_HIP(hipMemcpy(e->subch_host.data(), d.subch, sizeof(SubchDev) * e->subch_host.size(), hipMemcpyDeviceToHost));
   if ((rc = e->packet_download())) return rc;
+  if ((rc = e->pad_download())) return rc;
   int max_kbps = e->max_kbps;
   std::vector<SubchDev> row(std::max(1, d.max_subch));
   for (int j = 0; j < n; j++) {
@@ -954,6 +984,10 @@ static int set_subchannels_impl(dabx_engine *e, int stream, const dabx_subch_des
   if (!e->pkt.empty()) {                // a new or changed slot loses its packet mode; one that keeps running (a move included) keeps it and its state
     for (size_t sj : restarted) e->packet_drop(sj);
     if ((rc = e->packet_upload())) return rc;
+  }
+  if (!e->pad.empty()) {                // ... and so does PAD decoding
+    for (size_t sj : restarted) e->pad_drop(sj);
+    if ((rc = e->pad_upload())) return rc;
   }
   if (e->dl.open) {
     // slots that start anew count their frames from 0 again; the slab layout follows the new sub-channels (engine drained above)
@@ -1066,6 +1100,7 @@ int dabx_set_packet_mode(dabx_engine *e, int stream, int j, const dabx_packet_co
   if ((rc = e->packet_upload())) return rc;
   if (e->dl.open) {                       // the slab's data-group section follows the packet-mode slots (engine drained above)
     e->subch_host[sj] = sc;
+    if ((rc = e->pad_download())) return rc;      // delivery_layout writes both job tables back from their mirrors
     if ((rc = e->delivery_layout())) {
       const std::string why = dabx::last_error();
       delivery_free(e);
@@ -1142,6 +1177,164 @@ int dabx_get_packet_stats(dabx_engine *e, int stream, int j, dabx_packet_stats *
   out->crc_bad = st.crc_bad; out->len_bad = st.len_bad; out->walk_short = st.walk_short; out->dg_count = st.dg_count;
   out->dg_bytes = st.dg_bytes; out->dg_crc_bad = st.dg_crc_bad; out->dg_overflow = st.dg_overflow; out->dg_lost = e->pkt[sj].lost;
   out->active = 1; out->packet_address = st.address;
+  return 0;
+}
+
+// ---- programme-associated data (include/dabx.h, pad_core.h, k_pad): the host side is that of the packet-mode slots ---------------------
+static_assert(sizeof(dabx_chunk_pad) == 128 && sizeof(dabx_pad_item) == 32 && sizeof(dabx_pad_stats) == 128 && sizeof(dabx_pad_config) == 32, "include/dabx.h: PAD records");
+
+int dabx_engine::pad_download()
+{
+  if (pad_dev.n <= 0) return 0;
+  std::vector<PadSlot> tab((size_t)pad_dev.n);
+  DABX_HIP(hipMemcpy(tab.data(), pad_dev.slots, sizeof(PadSlot) * tab.size(), hipMemcpyDeviceToHost));
+  for (const PadSlot &q : tab) pad[(size_t)q.s * dev.max_subch + q.j].st = q;
+  return 0;
+}
+int dabx_engine::pad_upload()
+{
+  std::vector<PadSlot> tab;
+  std::fill(pad_index.begin(), pad_index.end(), -1);
+  for (size_t sj = 0; sj < pad.size(); sj++)
+    if (pad[sj].on) { pad_index[sj] = (int)tab.size(); tab.push_back(pad[sj].st); }
+  if ((int)tab.size() > pad_cap) {
+    PadSlot *q = nullptr;
+    const int cap = std::max<int>(2 * pad_cap, std::max<int>(16, (int)tab.size()));
+    DABX_HIP(hipMalloc(&q, sizeof(PadSlot) * (size_t)cap));
+    if (pad_dev.slots) (void)hipFree(pad_dev.slots);
+    pad_dev.slots = q; pad_cap = cap;
+  }
+  if (!tab.empty()) DABX_HIP(hipMemcpy(pad_dev.slots, tab.data(), sizeof(PadSlot) * tab.size(), hipMemcpyHostToDevice));
+  pad_dev.n = (int)tab.size();
+  return 0;
+}
+void dabx_engine::pad_drop(size_t sj)
+{
+  if (sj >= pad.size() || !pad[sj].on) return;
+  (void)hipFree(pad[sj].st.bytes);
+  (void)hipFree(pad[sj].st.items);
+  pad[sj] = PadHost{};
+}
+
+int dabx_set_pad_mode(dabx_engine *e, int stream, int j, const dabx_pad_config *cfg)
+{
+  if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch) { set_error("dabx_set_pad_mode: bad argument"); return DABX_E_ARG; }
+  if (cfg && cfg->size < sizeof(uint32_t)) { set_error("dabx_set_pad_mode: bad configuration (size %u)", cfg->size); return DABX_E_ARG; }
+  int rc;
+  if ((rc = sync_all(e))) return rc;
+  const size_t sj = (size_t)stream * e->dev.max_subch + j;
+  SubchDev sc;
+  DABX_HIP(hipMemcpy(&sc, e->dev.subch + sj, sizeof(SubchDev), hipMemcpyDeviceToHost));
+  if (!sc.active || sc.dab_plus != 1 || !e->dev.sf_info) {
+    set_error("dabx_set_pad_mode: stream %d slot %d is %s", stream, j, !sc.active ? "not active" : "not a DAB+ slot");
+    return DABX_E_ARG;
+  }
+  if (e->pad.empty()) {
+    if (!cfg) return 0;
+    e->pad.resize((size_t)e->dev.n_streams * e->dev.max_subch);
+    e->pad_index.assign(e->pad.size(), -1);
+  }
+  if ((rc = e->pad_download())) return rc;
+  e->pad_drop(sj);
+  if (cfg) {
+    dabx_engine::PadHost h;
+    h.on = true;
+    h.st.s = stream; h.st.j = j; h.st.sf_seen = sc.sf_count;           // the walk starts with the next super frame completed
+    h.st.h.xpad_length = -1; h.st.h.segment_number = -1; h.st.h.segment_no = -1;       // pad_handler.h:74, :79, :83
+    void *b = nullptr, *r = nullptr;
+    if (hipMalloc(&b, PAD_BYTE_RING) != hipSuccess || hipMalloc(&r, sizeof(dabx_pad_item) * (size_t)PAD_ITEM_RING) != hipSuccess) {
+      if (b) (void)hipFree(b);
+      set_error("dabx_set_pad_mode: out of device memory");
+      (void)e->pad_upload();
+      return DABX_E_NOMEM;
+    }
+    h.st.bytes = static_cast<uint8_t *>(b); h.st.items = static_cast<dabx_pad_item *>(r);
+    h.st.bytes_mask = PAD_BYTE_RING - 1; h.st.item_mask = PAD_ITEM_RING - 1;
+    e->pad[sj] = h;
+  }
+  if ((rc = e->pad_upload())) return rc;
+  if (e->dl.open) {                       // the slab's PAD section follows the PAD slots (engine drained above)
+    e->subch_host[sj] = sc;
+    if ((rc = e->packet_download())) return rc;
+    if ((rc = e->delivery_layout())) {
+      const std::string why = dabx::last_error();
+      delivery_free(e);
+      set_error("%s -- the delivery has been closed", why.c_str());
+      return rc;
+    }
+  }
+  return 0;
+}
+
+// The slot's table entry as the device holds it and the items [*lo, item_count) whose record and bytes are still intact; older ones that
+// no call has returned yet are counted as lost.
+static int pad_window(dabx_engine *e, size_t sj, PadSlot *st, long long *lo)
+{
+  if (int rc = sync_all(e)) return rc;
+  DABX_HIP(hipMemcpy(st, e->pad_dev.slots + e->pad_index[sj], sizeof(PadSlot), hipMemcpyDeviceToHost));
+  long long first = std::max<long long>(0, st->item_count - ((long long)st->item_mask + 1));
+  // the device may write the group under assembly up to PAD_ASM_ROOM bytes from item_bytes on: whatever that range covers in the ring is gone
+  const long long ring = (long long)st->bytes_mask + 1;
+  while (first < st->item_count) {
+    dabx_pad_item r;
+    DABX_HIP(hipMemcpy(&r, st->items + (size_t)(first & st->item_mask), sizeof(r), hipMemcpyDeviceToHost));
+    if (st->item_bytes + PAD_ASM_ROOM - r.byte_pos <= ring) break;
+    first++;
+  }
+  dabx_engine::PadHost &h = e->pad[sj];
+  if (first > h.seen) { h.lost += first - h.seen; h.seen = first; }
+  *lo = first;
+  return 0;
+}
+
+int dabx_read_pad_items(dabx_engine *e, int stream, int j, int n, dabx_pad_item *info, uint8_t *bytes, size_t max_bytes)
+{
+  if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch || n <= 0 || !info) { set_error("dabx_read_pad_items: bad argument"); return DABX_E_ARG; }
+  const size_t sj = (size_t)stream * e->dev.max_subch + j;
+  if (e->pad.empty() || !e->pad[sj].on) return 0;
+  PadSlot st;
+  long long lo = 0;
+  if (int rc = pad_window(e, sj, &st, &lo)) return rc;
+  long long from = std::max(lo, st.item_count - n);
+  int have = (int)(st.item_count - from);
+  if (have > 0) {                                             // the records [from, item_count): one or two runs of the ring
+    const size_t ring = (size_t)st.item_mask + 1, at = (size_t)(from & st.item_mask), head = std::min<size_t>((size_t)have, ring - at);
+    DABX_HIP(hipMemcpy(info, st.items + at, sizeof(dabx_pad_item) * head, hipMemcpyDeviceToHost));
+    if ((size_t)have > head) DABX_HIP(hipMemcpy(info + head, st.items, sizeof(dabx_pad_item) * ((size_t)have - head), hipMemcpyDeviceToHost));
+    int skip = 0;                                             // the newest items that fit
+    if (bytes) while (skip < have && (unsigned long long)(st.item_bytes - info[skip].byte_pos) > max_bytes) skip++;
+    if (skip) { memmove(info, info + skip, sizeof(dabx_pad_item) * (size_t)(have - skip)); have -= skip; }
+  }
+  if (have > 0) {
+    const long long base = info[0].byte_pos, total = st.item_bytes - base;
+    for (int i = 0; i < have; i++) info[i].byte_pos -= base;
+    if (bytes && total > 0) {
+      const size_t ring = (size_t)st.bytes_mask + 1, at = (size_t)((unsigned long long)base & st.bytes_mask);
+      const size_t head = std::min<size_t>((size_t)total, ring - at);
+      DABX_HIP(hipMemcpy(bytes, st.bytes + at, head, hipMemcpyDeviceToHost));
+      if ((size_t)total > head) DABX_HIP(hipMemcpy(bytes + head, st.bytes, (size_t)total - head, hipMemcpyDeviceToHost));
+    }
+  }
+  e->pad[sj].seen = std::max(e->pad[sj].seen, st.item_count);
+  return have;
+}
+
+int dabx_get_pad_stats(dabx_engine *e, int stream, int j, dabx_pad_stats *out)
+{
+  if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch || !out) { set_error("dabx_get_pad_stats: bad argument"); return DABX_E_ARG; }
+  memset(out, 0, sizeof(*out));
+  const size_t sj = (size_t)stream * e->dev.max_subch + j;
+  if (e->pad.empty() || !e->pad[sj].on) return sync_all(e);
+  PadSlot st;
+  long long lo = 0;
+  if (int rc = pad_window(e, sj, &st, &lo)) return rc;
+  const PadCounters &c = st.c;
+  auto i32 = [](long long v) { return (int32_t)std::min<long long>(v, INT32_MAX); };
+  out->superframes = c.superframes; out->aus = c.aus; out->pad_aus = c.pad_aus; out->fpad_other = c.fpad_other; out->xpad_short = c.xpad_short;
+  out->xpad_variable = c.xpad_variable; out->xpad_other = c.xpad_other; out->pad_bad = c.pad_bad; out->labels = c.labels;
+  out->label_bytes = c.label_bytes; out->groups = c.groups; out->group_bytes = c.group_bytes; out->items_lost = e->pad[sj].lost;
+  out->li_bad = i32(c.li_bad); out->dl_overflow = i32(c.dl_overflow); out->dg_crc_bad = i32(c.dg_crc_bad); out->dg_small = i32(c.dg_small);
+  out->active = 1;
   return 0;
 }
 
@@ -1399,7 +1592,7 @@ int dabx_process(dabx_engine *e, int max_frames, int sync)
       e->dev.snap = e->snap_buf[e->ss.batch_parity];
       hipStream_t tail = e->stream;
       rc = launch_msc_batch(e->dev, 4 * e->pending_frames, e->have_fast ? &e->fast : nullptr, e->ss, e->mk, e->dl.open ? &dv : nullptr, &tail,
-                            e->pkt_dev.n > 0 ? &e->pkt_dev : nullptr);
+                            e->pkt_dev.n > 0 ? &e->pkt_dev : nullptr, e->pad_dev.n > 0 ? &e->pad_dev : nullptr);
       if (rc) {
         if (e->dl.open) e->delivery_abort(dl_slot, dl_dev);          // the slabs of the chunk that was begun: never left IN_FLIGHT without a copy job
         e->pending_frames = 0;
@@ -2004,7 +2197,7 @@ int dabx_ingest_commit(dabx_engine *e, int k)
 
 int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
 {
-  if (!e || (cfg && (cfg->host_slabs < 0 || cfg->host_slabs == 1 || cfg->host_slabs > 64 || (cfg->what & ~31) || cfg->copy_engine < 0 || cfg->copy_engine > 1))) {
+  if (!e || (cfg && (cfg->host_slabs < 0 || cfg->host_slabs == 1 || cfg->host_slabs > 64 || (cfg->what & ~63) || cfg->copy_engine < 0 || cfg->copy_engine > 1))) {
     set_error("dabx_delivery_open: bad argument");
     return DABX_E_ARG;
   }
@@ -2014,7 +2207,8 @@ int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
   Delivery &D = e->dl;
   const EngineDev &d = e->dev;
   D.want_dg = !cfg || !cfg->what || (cfg->what & DABX_DELIVER_DG);
-  D.what = cfg && cfg->what ? (cfg->what & ~DABX_DELIVER_DG) : (DABX_DELIVER_FIB | DABX_DELIVER_MSC | DABX_DELIVER_SF);
+  D.want_pad = !cfg || !cfg->what || (cfg->what & DABX_DELIVER_PAD);
+  D.what = cfg && cfg->what ? (cfg->what & ~(DABX_DELIVER_DG | DABX_DELIVER_PAD)) : (DABX_DELIVER_FIB | DABX_DELIVER_MSC | DABX_DELIVER_SF);
   if ((D.what & DABX_DELIVER_FIB) && d.out_frames < DL_FRAMES) {
     set_error("dabx_delivery_open: the engine's FIB ring holds %d frames, a chunk up to %d: create it with dabx_config.out_frames >= %d "
               "(the FIBs of a chunk's first frames would have left the ring before they are gathered)", d.out_frames, DL_FRAMES, DL_FRAMES);
@@ -2038,6 +2232,14 @@ int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
       cap += (size_t)4 * F * (e->subch_host[sj].kbps / 8) * sizeof(dabx_datagroup_info) + (size_t)4 * F * 3 * e->subch_host[sj].kbps + DABX_DG_MAX_BYTES + 16;
     }
   if (!e->pkt.empty()) cap += S * M * sizeof(dabx_chunk_dg) + 16;
+  // ... and the PAD section of the PAD slots there are now
+  if ((rc = e->pad_download())) return rc;
+  for (size_t sj = 0; sj < e->pad.size(); sj++)
+    if (e->pad[sj].on) {
+      e->pad[sj].st.dl_done = e->pad[sj].st.item_count;
+      cap += (size_t)PAD_DL_ITEM_CAP * sizeof(dabx_pad_item) + PAD_DL_BYTES_CAP + 16;
+    }
+  if (!e->pad.empty()) cap += S * M * sizeof(dabx_chunk_pad) + 16;
   D.capacity = align_up(cap, 4096);
 #define H(x) do { hipError_t err__ = (x); if (err__ != hipSuccess) { set_error("HIP error %d (%s) at %s:%d", (int)err__, hipGetErrorString(err__), __FILE__, __LINE__); delivery_free(e); return DABX_E_HIP; } } while (0)
   if (D.copy_engine == 1) H(hipStreamCreateWithFlags(&D.cs, hipStreamNonBlocking));
@@ -2450,7 +2652,8 @@ int dabx_internal_msc_decode(dabx_engine *e, const int32_t *cifs_per_stream, int
   if (!rc) rc = launch_msc_advance(e->dev, counts_dev, e->stream);
   if (!rc) {
     e->dev.snap = e->snap_buf[e->ss.batch_parity];
-    rc = launch_msc_batch(e->dev, batch_cifs, e->have_fast ? &e->fast : nullptr, e->ss, e->mk, nullptr, nullptr, e->pkt_dev.n > 0 ? &e->pkt_dev : nullptr);
+    rc = launch_msc_batch(e->dev, batch_cifs, e->have_fast ? &e->fast : nullptr, e->ss, e->mk, nullptr, nullptr, e->pkt_dev.n > 0 ? &e->pkt_dev : nullptr,
+                          e->pad_dev.n > 0 ? &e->pad_dev : nullptr);
   }
   const int rc2 = sync_all(e);
   (void)hipFree(counts_dev);

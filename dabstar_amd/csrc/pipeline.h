@@ -231,7 +231,7 @@ struct EngineStreams {
 };
 
 // ---- profiling hook: HIP events around every kernel launch of a batch step ------------------------------------
-constexpr int N_STEP_KERNELS = 12;
+constexpr int N_STEP_KERNELS = 13;
 struct Marker {
   bool on = false;
   bool serial = false;            // the host waits for every instrumented kernel: one kernel on the chip at a time = stand-alone durations

@@ -13,9 +13,11 @@
 //   k_msc_frame    time de-interleave + depuncture + Viterbi + PRBS per (CIF, sub-channel) (backend.cpp:129-161)
 //   k_dabplus      super-frame sync, RS(120,110), fire code, AU CRCs (mp4processor.cpp:96-333)
 //   k_packet       packet-mode data sub-channels: packet walk, packet CRCs, assembly of the MSC data groups (data_processor.cpp:106-254)
+//   k_pad          PAD of the DAB+ access units: dynamic labels and X-PAD MSC data groups (mp4processor.cpp:345-353, pad_handler.cpp:67-547)
 #include <type_traits>
 #include "pipeline.h"
 #include "packet_core.h"
+#include "pad_core.h"
 #include <algorithm>
 #include "ofdm_core.h"
 #include "viterbi_core.h"
@@ -2033,6 +2035,70 @@ __global__ __launch_bounds__(64) void k_packet(PacketDev pk)
   }
 }
 
+// --------------------------------------------------------------------------------------------------- PAD
+// One wave per PAD-enabled DAB+ slot (PadDev::slots: those slots only), behind k_dabplus: walks the super frames k_dabplus has completed
+// since the slot's last visit (SubchDev::sf_count against PadSlot::sf_seen: a batch adds at most 6, the rings hold SF_SLOTS) out of the
+// super-frame ring and their dabx_superframe_info records, and of every access unit that passed its CRC the data stream element
+// (mp4processor.cpp:345-353).  The PAD bytes (<= 255) are staged REVERSED in LDS, so that PadHandler's iBuffer[iLast - k] is xp[k] and a
+// sub-field is a forward run of bytes; the state machine (pad_core.h: pad_handler.cpp:67-519 line by line) runs wave-uniform on header
+// bytes, the whole wave copies sub-fields straight to their place in the slot's byte ring -- the group under assembly lives where the
+// completed group will be -- and the data-group CRC at completion is folded from per-lane slices.  The dynamic label's text and the
+// short X-PAD's bytes are in LDS for the launch.  include/dabx.h states the semantics and the guards G1..G4.
+__global__ __launch_bounds__(64) void k_pad(PadDev pd)
+{
+  const int lane = threadIdx.x;
+  PadSlot &ps = pd.slots[blockIdx.x];
+  const size_t sj = (size_t)ps.s * pd.max_subch + ps.j;
+  const SubchDev &sc = pd.subch[sj];
+  if (!sc.active || !sc.dab_plus) return;
+  const long long have = sc.sf_count;
+  long long seen = ps.sf_seen;
+  if (have <= seen) return;
+  if (have - seen > SF_SLOTS) seen = have - SF_SLOTS;         // (cannot happen: the stage runs behind every batch)
+  const int end = 110 * (sc.kbps / 8);
+  __shared__ uint8_t rb[256];                                  // the AU's PAD reversed: rb[k] = buffer[count - 1 - k]
+  __shared__ uint8_t s_text[DABX_DL_MAX_BYTES], s_short[16];
+  __shared__ uint16_t s_crc[256];
+  __shared__ __attribute__((aligned(16))) uint16_t s_xpow[1024];
+  for (int i = lane; i < 256; i += 64) { s_crc[i] = pd.crc_ccitt[i]; s_text[i] = ps.dl_text[i]; }
+  for (int i = lane; i < 128; i += 64) reinterpret_cast<uint4 *>(s_xpow)[i] = reinterpret_cast<const uint4 *>(pd.crc_xpow)[i];
+  if (lane < 16) s_short[lane] = ps.short_data[lane];
+  PadWave w;
+  w.h = ps.h; w.c = ps.c;
+  w.ring = ps.bytes; w.items = ps.items; w.bytes_mask = ps.bytes_mask; w.item_mask = ps.item_mask;
+  w.n_items = ps.item_count; w.n_bytes = ps.item_bytes;
+  w.lane = lane; w.text = s_text; w.shortd = s_short; w.s_crc = s_crc; w.s_xpow = s_xpow;
+  __syncthreads();
+  for (long long sf = seen; sf < have; sf++) {
+    const size_t slot = sj * SF_SLOTS + (size_t)(sf % SF_SLOTS);
+    const dabx_superframe_info *inf = pd.sf_info + slot;
+    const uint8_t *sfb = pd.sf_out + slot * pd.sf_stride;
+    const int n_au = min((int)inf->num_aus, 6);
+    const unsigned take = (unsigned)inf->au_crc_ok & ~(unsigned)inf->au_len_bad;
+    w.frame = inf->first_frame;
+    w.c.superframes++;
+    for (int a = 0; a < n_au; a++) {                           // mp4processor.cpp:320
+      if (!((take >> a) & 1u)) continue;                       // :325, :333
+      w.c.aus++;
+      const int st = inf->au_start[a];
+      if (st >= end || ((sfb[st] >> 5) & 7) != 4) continue;    // :345
+      w.c.pad_aus++;
+      if (st + 2 > end) { w.c.pad_bad++; continue; }           // G1
+      const int count = sfb[st + 1];                           // :347
+      if (count < 2 || st + 2 + count > end) { w.c.pad_bad++; continue; }      // G1
+      __syncthreads();                                         // the previous AU's bytes are done with
+      for (int k = lane; k < count; k += 64) rb[k] = sfb[st + 2 + count - 1 - k];      // :349-351
+      __syncthreads();
+      w.au = a;
+      pad_process(w, rb, count);                               // :352
+    }
+  }
+  __syncthreads();
+  for (int i = lane; i < DABX_DL_MAX_BYTES; i += 64) ps.dl_text[i] = s_text[i];
+  if (lane < 16) ps.short_data[lane] = s_short[lane];
+  if (lane == 0) { ps.h = w.h; ps.c = w.c; ps.item_count = w.n_items; ps.item_bytes = w.n_bytes; ps.sf_seen = have; }
+}
+
 // ---------------------------------------------------------------------------------------------- launchers
 __global__ void k_msc_snap(EngineDev e, int cifs)
 {
@@ -2051,7 +2117,7 @@ __global__ void k_msc_done(EngineDev e)
 extern const char *const kStepKernelNames[N_STEP_KERNELS];
 // "k_demap_fic": the first k_demap_frame launch of a frame (symbols 1..3) when the FIC is decoded on its own stream
 const char *const kStepKernelNames[N_STEP_KERNELS] = {"k_acquire", "k_frame_head", "k_symbols", "k_demap_frame", "k_fic_frame", "k_frame_tail",
-                                                      "k_msc_prep", "k_msc_vitT", "k_msc_frame", "k_dabplus", "k_demap_fic", "k_packet"};
+                                                      "k_msc_prep", "k_msc_vitT", "k_msc_frame", "k_dabplus", "k_demap_fic", "k_packet", "k_pad"};
 
 // Front end of one batch step (everything with frame-to-frame feedback).
 // Overlapped schedule (ss.d set): the FIC lives in symbols 1..3 -- those are demapped first on the front-end stream a, then
@@ -2172,12 +2238,14 @@ int launch_msc_vitT(const EngineDev &e, int cifs, const MscLaunch &L, hipStream_
 int launch_deliver_msc(const EngineDev &e, const DeliverDev &dv, hipStream_t st, bool with_lf);
 int launch_deliver_lf(const EngineDev &e, const DeliverDev &dv, hipStream_t st);
 int launch_deliver_dg(const EngineDev &e, const DeliverDev &dv, const PacketDev &pk, hipStream_t st);
+int launch_deliver_pad(const EngineDev &e, const DeliverDev &dv, const PadDev &pd, hipStream_t st);
 // `dv` (optional): the chunk's slot gather (deliver.hip) goes behind the DAB+ stage on the stream that ran it, before the batch's
 // completion event; *tail (optional) = the stream whose work completes the batch.
 // `pk` (optional): the engine has packet-mode slots -- k_packet walks their new logical frames, in front of k_dabplus (which moves the
 // slots' frame counters on); null = no launch.
+// `pad` (optional): the engine has PAD slots -- k_pad walks the super frames k_dabplus has just completed for them; null = no launch.
 int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineStreams &ss, Marker &mk, const DeliverDev *dv, hipStream_t *tail,
-                     const PacketDev *pk)
+                     const PacketDev *pk, const PadDev *pad)
 {
   const DevTables *t;
   int rc = get_tables(&t);
@@ -2274,8 +2342,18 @@ int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineSt
   hipLaunchKernelGGL(k_dabplus, dim3(e.n_streams * e.max_subch), dim3(64), 0, sb, e, *t);
   hipLaunchKernelGGL(k_msc_done, dim3((e.n_streams + 255) / 256), dim3(256), 0, sb, e);
   mk.end(9, sb);
+  PadDev q{};
+  if (pad && pad->n > 0) {
+    q = *pad;
+    q.max_subch = e.max_subch; q.sf_stride = e.sf_stride; q.subch = e.subch; q.sf_out = e.sf_out; q.sf_info = e.sf_info;
+    q.crc_ccitt = t->crc_ccitt; q.crc_xpow = t->crc_xpow;
+    mk.begin(12, sb);
+    hipLaunchKernelGGL(k_pad, dim3(q.n), dim3(64), 0, sb, q);
+    mk.end(12, sb);
+  }
   if (dv && (rc = launch_deliver_msc(e, *dv, sb, !dv->lf_done))) return rc;
   if (dv && p.n > 0 && (rc = launch_deliver_dg(e, *dv, p, sb))) return rc;      // the slab's data-group section (head part, like the gather in front)
+  if (dv && q.n > 0 && (rc = launch_deliver_pad(e, *dv, q, sb))) return rc;     // ... and its PAD section
   if (tail) *tail = sb;
   if (ss.b) {
     DABX_HIP(hipEventRecord(ss.msc_done, ss.b));

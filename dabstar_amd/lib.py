@@ -65,6 +65,10 @@ def load(build_if_missing=True):
         L.dabx_read_datagroups.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
         L.dabx_get_packet_stats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.dabx_fibdec_packet_components.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    if hasattr(L, "dabx_set_pad_mode"):              # programme-associated data of DAB+ slots
+        L.dabx_set_pad_mode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.dabx_read_pad_items.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.dabx_get_pad_stats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     if hasattr(L, "dabx_announce_write"):            # (absent from libraries older than the level anchor: tools/ab.sh runs those through this binding too)
         L.dabx_announce_write.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
     _LIB = L
@@ -344,11 +348,11 @@ class Stats(C.Structure):
 # ---- bulk delivery (include/dabx.h "Bulk delivery"): the slab's records as numpy dtypes -----------------------------
 CHUNK_FRAMES = 7
 CHUNK_MAGIC = 0x43584244
-DELIVER_FIB, DELIVER_MSC, DELIVER_SF, DELIVER_MSC_NOT_DABPLUS, DELIVER_DG = 1, 2, 4, 8, 16
+DELIVER_FIB, DELIVER_MSC, DELIVER_SF, DELIVER_MSC_NOT_DABPLUS, DELIVER_DG, DELIVER_PAD = 1, 2, 4, 8, 16, 32
 CHUNK_HEADER = np.dtype([("magic", "<u4"), ("abi", "<u4"), ("seq", "<u8"), ("n_streams", "<i4"), ("max_subch", "<i4"),
                          ("max_frames", "<i4"), ("what", "<i4"), ("bytes", "<u8"), ("off_stream", "<u8"), ("off_subch", "<u8"),
                          ("off_fib", "<u8"), ("off_crc", "<u8"), ("off_frame", "<u8"), ("off_msc", "<u8"), ("off_sf", "<u8"),
-                         ("off_dg", "<u8"), ("reserved", "<u8", 3)])
+                         ("off_dg", "<u8"), ("off_pad", "<u8"), ("reserved", "<u8", 2)])
 CHUNK_STREAM = np.dtype([("first_frame", "<i8"), ("n_frames", "<i4"), ("frames_lost", "<i4"), ("state", "<i4"),
                          ("fic_ratio_percent", "<i4"), ("cif_count", "<i4"), ("snr_db_est", "<f4"), ("freq_offs_bb_hz", "<f4"),
                          ("clock_err_hz", "<f4"), ("signal_level", "<f4"), ("fic_ber_bits", "<i4"), ("fic_ber_errors", "<i4"),
@@ -378,6 +382,25 @@ CHUNK_DG = np.dtype([("first_dg", "<i8"), ("n_dg", "<i4"), ("dg_lost", "<i4"), (
                     [(k, "<i8") for k in PACKET_COUNTERS])
 assert CHUNK_DG.itemsize == 128
 assert DATAGROUP_INFO.itemsize == 32 and PACKET_STATS.itemsize == 128 and PACKET_COMPONENT.itemsize == 24
+# programme-associated data (include/dabx.h): dabx_pad_item, one record per dynamic label / X-PAD MSC data group, and dabx_pad_stats
+DL_MAX_BYTES = 256
+PAD_LABEL, PAD_DATAGROUP = 1, 2
+PAD_RING_BYTES = 131072                      # a PAD slot's byte ring
+PAD_ITEM = np.dtype([("byte_pos", "<i8"), ("frame", "<i8"), ("length", "<u2"), ("kind", "u1"), ("au", "u1"), ("charset", "u1"),
+                     ("crc_flag", "u1"), ("crc_ok", "u1"), ("reserved", "u1", 9)])
+PAD_COUNTERS = ("superframes", "aus", "pad_aus", "fpad_other", "xpad_short", "xpad_variable", "xpad_other", "pad_bad", "labels", "label_bytes",
+                "groups", "group_bytes", "li_bad", "dl_overflow", "dg_crc_bad", "dg_small")
+PAD_STATS = np.dtype([(k, "<i8") for k in PAD_COUNTERS[:12] + ("items_lost",)] + [(k, "<i4") for k in PAD_COUNTERS[12:] + ("active", "reserved")])
+# the slab's PAD section (dabx_chunk_pad): one row per (stream, slot), all zero for a slot without PAD decoding
+CHUNK_PAD = np.dtype([("first_item", "<i8"), ("n_items", "<i4"), ("items_lost", "<i4"), ("item_off", "<u8"), ("bytes_off", "<u8"), ("n_bytes", "<i8")] +
+                     [(k, "<i8") for k in ("superframes", "aus", "pad_aus", "pad_bad", "labels", "label_bytes", "groups", "group_bytes", "dg_crc_bad",
+                                           "dl_overflow", "li_bad")])
+assert PAD_ITEM.itemsize == 32 and PAD_STATS.itemsize == 128 and CHUNK_PAD.itemsize == 128
+
+
+class PadConfig(C.Structure):
+    """dabx_pad_config."""
+    _fields_ = [("size", C.c_uint32), ("reserved", C.c_int32 * 7)]
 
 
 class PacketConfig(C.Structure):
@@ -423,6 +446,9 @@ class Chunk:
         self.dg = None                          # the data-group section: [S, M] CHUNK_DG, or None when the slab has none
         if int(h["off_dg"]):
             self.dg = self.raw[int(h["off_dg"]):int(h["off_dg"]) + S * M * 128].view(CHUNK_DG).reshape(S, M)
+        self.pad = None                         # the PAD section: [S, M] CHUNK_PAD, or None when the slab has none
+        if int(h["off_pad"]):
+            self.pad = self.raw[int(h["off_pad"]):int(h["off_pad"]) + S * M * 128].view(CHUNK_PAD).reshape(S, M)
 
     def msc(self, s, j):
         """Logical frames of slot (s, j) in this chunk: [n_cifs, 3 * kbps] uint8 (a view)."""
@@ -451,6 +477,15 @@ class Chunk:
         r = self.dg[s, j]
         ro, bo = int(r["rec_off"]), int(r["bytes_off"])
         return self.raw[ro:ro + int(r["n_dg"]) * 32].view(DATAGROUP_INFO), self.raw[bo:bo + int(r["n_bytes"])]
+
+    def pad_items(self, s, j):
+        """PAD items of slot (s, j) in this chunk: ([n_items] PAD_ITEM, their n_bytes bytes), views; item i is
+        bytes[byte_pos[i] : byte_pos[i] + length[i]].  Empty when the slab has no PAD section or the slot has no PAD decoding."""
+        if self.pad is None or not int(self.pad[s, j]["item_off"]):
+            return np.zeros(0, PAD_ITEM), np.zeros(0, np.uint8)
+        r = self.pad[s, j]
+        ro, bo = int(r["item_off"]), int(r["bytes_off"])
+        return self.raw[ro:ro + int(r["n_items"]) * 32].view(PAD_ITEM), self.raw[bo:bo + int(r["n_bytes"])]
 
     def release(self):
         if self._eng is not None:
@@ -681,6 +716,34 @@ class Engine:
         out = np.zeros(1, PACKET_STATS)
         check(L.dabx_get_packet_stats(self._h, int(stream), int(j), _p(out)))
         return {k: int(out[0][k]) for k in PACKET_STATS.names if k != "reserved"}
+
+    def set_pad_mode(self, stream, j, on=True):
+        """Switches the PAD decoding of DAB+ slot j of `stream` on (restarting it when it is on already) or off (dabx_set_pad_mode)."""
+        L = load()
+        if not on:
+            check(L.dabx_set_pad_mode(self._h, int(stream), int(j), None))
+        else:
+            cfg = PadConfig(size=C.sizeof(PadConfig))
+            check(L.dabx_set_pad_mode(self._h, int(stream), int(j), C.byref(cfg)))
+
+    def read_pad_items(self, stream, j, n=512, max_bytes=None):
+        """(records [k] PAD_ITEM, bytes uint8) of the newest k <= n PAD items of slot j, oldest first, dynamic labels and X-PAD MSC data
+        groups in emission order; item i is bytes[byte_pos[i] : byte_pos[i] + length[i]]."""
+        L = load()
+        info = np.zeros(max(1, n), PAD_ITEM)
+        if max_bytes is None:
+            max_bytes = PAD_RING_BYTES
+        buf = np.zeros(max(1, int(max_bytes)), np.uint8)
+        k = check(L.dabx_read_pad_items(self._h, int(stream), int(j), int(n), _p(info), _p(buf), int(max_bytes)))
+        info = info[:k]
+        return info, buf[:int(info["length"].sum())].copy()
+
+    def pad_stats(self, stream, j):
+        """dabx_pad_stats of slot j as a dict."""
+        L = load()
+        out = np.zeros(1, PAD_STATS)
+        check(L.dabx_get_pad_stats(self._h, int(stream), int(j), _p(out)))
+        return {k: int(out[0][k]) for k in PAD_STATS.names if k != "reserved"}
 
     def read_soft(self, stream):
         out = np.zeros((75, 3072), np.int16)

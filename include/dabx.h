@@ -568,6 +568,86 @@ int  dabx_set_packet_mode(dabx_engine *e, int stream, int subch_idx, const dabx_
 int  dabx_read_datagroups(dabx_engine *e, int stream, int subch_idx, int n, dabx_datagroup_info *info, uint8_t *bytes, size_t max_bytes);
 int  dabx_get_packet_stats(dabx_engine *e, int stream, int subch_idx, dabx_packet_stats *out);
 /* ------------------------------------------------------------------------------------------------------------
+ * Programme-associated data of DAB+ access units: the one piece of Mp4Processor::_process_super_frame that is neither audio decoding nor
+ * GUI, on the device (k_pad, behind k_dabplus on the MSC batch's stream, one wave per PAD-enabled slot).  For every access unit of an
+ * accepted super frame that passed its CRC (au_crc_ok set, au_len_bad clear), in AU order, super frames in order
+ * (base/backend/audio/mp4processor.cpp:320-353): when its first syntactic element is a data stream element (id 4, :345), count = AU[1],
+ * the PAD is AU[2 .. 2 + count), its last two bytes are the F-PAD (:347-352) and the rest the X-PAD, stored reversed, which goes through
+ * PadHandler::process_PAD (base/backend/data/pad_handler.cpp:67-97): F-PAD type and X-PAD indicator dispatch, the short X-PAD with and
+ * without contents indicator (:111-200), the variable X-PAD with and without (:208-330; mXPadLength counts the CI bytes and the end
+ * marker too, :268-273, and that is how long a no-CI continuation is taken to be, :224), the dynamic label (:335-455), the data-group
+ * length indicator with its CRC (:291-300) and the assembly of the X-PAD MSC data groups (:460-519).  Two hand-over points:
+ *   - every `emit signal_show_label` (:144, :193, :416, :452) is one DABX_PAD_LABEL item: the bytes of mDynamicLabelTextUnConverted at that
+ *     moment and mCharSet; the conversion to_QString_using_charset stays with the host;
+ *   - every _build_MSC_segment call (:478, :514) with size = min(iData.size(), mDataGroupLength) >= 2 (:528-534) is one DABX_PAD_DATAGROUP
+ *     item: iData[0 .. size), crc_flag = bit 6 of byte 0 (the CrcFlag bit-field, :524, :539), crc_ok = check_crc_bytes(iData, size - 2)
+ *     (:541).  A group with a bad CRC is delivered with crc_ok == 0 and counted (the reference drops it, :543); the MOT parsing from :553 on
+ *     stays with the host.
+ * The state in between (pad_handler.h:68-86) lives on the device per slot and survives batch boundaries.  Four guards, where the
+ * reference is undefined or unbounded; each is counted:
+ *   G1 (mp4processor.cpp:347-352): the reference reads AU[2 .. 2 + count), buffer[count - 1] and buffer[count - 2] whatever they are.
+ *      count < 2, or a byte it reads beyond the end of the super frame (au_start[a] + 2 + count > 110 * kbps / 8, or au_start[a] + 2 itself
+ *      beyond it): the AU's PAD is skipped, state unchanged, counted in pad_bad.  Bytes inside the super frame but beyond the AU are read
+ *      as the reference reads them.
+ *   G2 (pad_handler.cpp:119-122, :151): a short X-PAD (X-PAD indicator 1) with fewer than 4 X-PAD bytes (iLast < 3) indexes below 0:
+ *      skipped, state unchanged, pad_bad.
+ *   G3 (:254-262, :284-287): a variable X-PAD whose CI list (up to four bytes, ending early at application type 0) would be read below
+ *      index 0 is skipped before any state is touched, pad_bad.  A sub-field whose `length` bytes would reach below index 0 stops the walk
+ *      in front of that sub-field: mXPadLength is set as the reference sets it, mLastAppType is as the previous sub-field left it, pad_bad.
+ *      (The no-CI form has the reference's own check, :219.)
+ *   G4 (:163, :183; applied to every append, :407 and :446 too): mDynamicLabelTextUnConverted is bounded at DABX_DL_MAX_BYTES (the legal
+ *      maximum is 8 segments of 16 bytes): an append that would exceed it is dropped whole, text unchanged, counted in dl_overflow.
+ * The data-group buffer needs no guard: mMscDataGroupBuffer is handed on as soon as it reaches mDataGroupLength <= 16 383 (:512), so it
+ * never holds more than 16 382 bytes plus one sub-field (at most 196 bytes, a no-CI continuation of mXPadLength bytes).
+ * Out of scope: MotObject / MotHandler, the charset conversion, DL Plus, F-PAD types other than 0, PAD of MP2 frames. */
+#define DABX_DL_MAX_BYTES 256
+enum { DABX_PAD_LABEL = 1, DABX_PAD_DATAGROUP = 2 };
+typedef struct {
+  uint32_t size;             /* sizeof(dabx_pad_config) of the caller */
+  int32_t  reserved[7];      /* zero */
+} dabx_pad_config;
+typedef struct dabx_pad_item_s {
+  int64_t  byte_pos;         /* position of the item's first byte in the slot's sequence of item bytes */
+  int64_t  frame;            /* dabx_superframe_info.first_frame of the super frame whose access unit completed the item */
+  uint16_t length;           /* bytes */
+  uint8_t  kind;             /* DABX_PAD_LABEL or DABX_PAD_DATAGROUP */
+  uint8_t  au;               /* ... and that access unit's index in the super frame */
+  uint8_t  charset;          /* labels: mCharSet (pad_handler.cpp:122, :353) */
+  uint8_t  crc_flag;         /* groups: bit 6 of byte 0 (:539) */
+  uint8_t  crc_ok;           /* groups: check_crc_bytes(iData, length - 2) (:541) */
+  uint8_t  reserved[9];
+} dabx_pad_item;             /* 32 bytes, little-endian, no holes */
+typedef struct {
+  int64_t superframes;       /* super frames walked */
+  int64_t aus;               /* access units taken (au_crc_ok set, au_len_bad clear) */
+  int64_t pad_aus;           /* ... that start with a data stream element (id 4, mp4processor.cpp:345) */
+  int64_t fpad_other;        /* ... whose F-PAD type is not 0 (pad_handler.cpp:71) */
+  int64_t xpad_short, xpad_variable, xpad_other;      /* X-PAD indicator 1 / 2 / 0 or 3 (:81-96), counted in front of the guards */
+  int64_t pad_bad;           /* guards G1, G2, G3 */
+  int64_t labels, label_bytes;      /* DABX_PAD_LABEL items and their bytes */
+  int64_t groups, group_bytes;      /* DABX_PAD_DATAGROUP items and their bytes */
+  int64_t items_lost;        /* items that had left the rings before a dabx_read_pad_items call could return them */
+  int32_t li_bad;            /* data-group length indicators refused: CRC, or a length other than 4 (:292-299) */
+  int32_t dl_overflow;       /* guard G4 */
+  int32_t dg_crc_bad;        /* groups with crc_flag set and crc_ok == 0 */
+  int32_t dg_small;          /* _build_MSC_segment calls with size < 2 (:530) */
+  int32_t active;            /* 1: PAD decoding is on for the slot (all else is zero otherwise) */
+  int32_t reserved;
+} dabx_pad_stats;            /* 128 bytes */
+/* Switches PAD decoding of slot subch_idx of `stream` on (cfg != NULL) or off (NULL).  Only an active slot with dab_plus == 1; DABX_E_ARG
+ * otherwise.  The slot's logical frames, super frames and records are produced and delivered exactly as before; the walk starts with the
+ * next super frame completed.  Calling it again for a PAD slot restarts the state with empty rings.  The setting and the state stay with
+ * the slot wherever dabx_set_subchannels says it "keeps decoding without interruption", a move to other capacity units included; a new or
+ * changed slot loses them.  An engine without a PAD slot allocates and launches nothing for this stage.  Drains the engine. */
+int  dabx_set_pad_mode(dabx_engine *e, int stream, int subch_idx, const dabx_pad_config *cfg);
+/* The newest n items still in the rings, oldest first, labels and groups in emission order: their records into info[], their bytes back
+ * to back into bytes[]; byte_pos is rebased to the returned buffer (info[0].byte_pos == 0).  When the bytes of n items exceed max_bytes
+ * the newest items that fit are returned (bytes == NULL: records only).  Returns the number of items.  Items older than the ones returned
+ * count as seen; items that left the rings unseen are counted in dabx_pad_stats.items_lost.  The rings hold what two full batches can
+ * emit (512 items, 128 KiB; pad_core.h has the derivation).  Drains the engine like the other dabx_read_* calls. */
+int  dabx_read_pad_items(dabx_engine *e, int stream, int subch_idx, int n, dabx_pad_item *info, uint8_t *bytes, size_t max_bytes);
+int  dabx_get_pad_stats(dabx_engine *e, int stream, int subch_idx, dabx_pad_stats *out);
+/* ------------------------------------------------------------------------------------------------------------
  * Bulk delivery of the results to the host.  The reference hands every FIB to IFibDecoder::process_FIB
  * (base/decoder/fib_decoder_if.h:81, called from fic_decoder.cpp:234-261) and every logical frame to
  * FrameProcessor::add_to_frame (base/backend/frame_processor.h:43-46, called from backend.cpp:160) the moment it exists;
@@ -603,7 +683,11 @@ enum { DABX_DELIVER_FIB = 1, DABX_DELIVER_MSC = 2, DABX_DELIVER_SF = 4,
        /* the MSC data groups of the packet-mode slots (dabx_set_packet_mode): with this bit, or with what == 0, AND at least one packet-mode
           slot the slab gains a data-group section (dabx_chunk_dg below) and dabx_chunk_header.what shows the bit; without a packet-mode slot
           a slab is byte for byte what it is without the bit, dabx_delivery_slab_bytes included */
-       DABX_DELIVER_DG = 16 };
+       DABX_DELIVER_DG = 16,
+       /* the PAD items of the PAD-enabled slots (dabx_set_pad_mode): with this bit, or with what == 0, AND at least one PAD slot the slab
+          gains a PAD section (dabx_chunk_pad below) and dabx_chunk_header.what shows the bit; without a PAD slot a slab is byte for byte
+          what it is without the bit, dabx_delivery_slab_bytes included */
+       DABX_DELIVER_PAD = 32 };
 typedef struct {
   int32_t host_slabs;       /* page-locked host slabs, >= 2 (0 = default 4) */
   int32_t what;             /* DABX_DELIVER_* mask, 0 = everything */
@@ -619,7 +703,8 @@ typedef struct {
   uint64_t bytes;           /* size of the slab as copied */
   uint64_t off_stream, off_subch, off_fib, off_crc, off_frame, off_msc, off_sf;
   uint64_t off_dg;          /* the data-group section: dabx_chunk_dg[n_streams * max_subch]; 0 = the slab has none */
-  uint64_t reserved[3];
+  uint64_t off_pad;         /* the PAD section: dabx_chunk_pad[n_streams * max_subch]; 0 = the slab has none */
+  uint64_t reserved[2];
 } dabx_chunk_header;        /* 128 bytes */
 typedef struct {
   int64_t first_frame;      /* index, since the stream was opened, of the first frame in the chunk */
@@ -667,6 +752,22 @@ typedef struct {
   int64_t  n_bytes;
   int64_t  frames, packets, addr_match, continuity_err, crc_bad, len_bad, walk_short, dg_count, dg_bytes, dg_crc_bad, dg_overflow;
 } dabx_chunk_dg;            /* 128 bytes */
+/* The PAD section (DABX_DELIVER_PAD): one dabx_chunk_pad per (stream, slot) from off_pad, all zero for a slot without PAD decoding; behind
+ * the table, per PAD slot, room for 144 dabx_pad_item from item_off and 144 * DABX_DL_MAX_BYTES + 16 896 bytes from bytes_off, fixed by
+ * the configuration: a chunk is one batch, which completes at most 6 super frames of at most 6 access units whose X-PAD has at most 4
+ * sub-fields, each emitting at most one item; a label is at most DABX_DL_MAX_BYTES, and the groups of a chunk are together at most what
+ * was under assembly (below 16 896 bytes) plus less than a label per sub-field.  The section lies in the slab's head part, behind the
+ * data-group section and in front of off_msc, and is gathered behind k_deliver_dg (k_deliver_pad).  The chunk carries the n_items items
+ * first_item .. first_item + n_items - 1 of the slot's sequence, emitted since the previous chunk: item i is bytes_off + byte_pos ..
+ * + length (byte_pos counts from bytes_off).  items_lost: items emitted since the previous chunk that are not in this one (always 0 with
+ * this room).  The counters are cumulative, as dabx_pad_stats. */
+typedef struct {
+  int64_t  first_item;
+  int32_t  n_items, items_lost;
+  uint64_t item_off, bytes_off;
+  int64_t  n_bytes;
+  int64_t  superframes, aus, pad_aus, pad_bad, labels, label_bytes, groups, group_bytes, dg_crc_bad, dl_overflow, li_bad;
+} dabx_chunk_pad;           /* 128 bytes */
 typedef struct {
   uint64_t seq;
   const void *data;         /* the host slab: valid until dabx_delivery_release(seq) */
