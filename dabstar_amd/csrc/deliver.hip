@@ -159,45 +159,20 @@ __global__ __launch_bounds__(64) void k_deliver_msc(EngineDev e, DeliverDev dv, 
 }
 
 // The data-group section (include/dabx.h, dabx_chunk_dg): one wave per packet-mode slot, behind k_deliver_msc of the chunk (same stream; the
-// table has been zeroed in front).  The groups completed since the previous chunk -- as many of the newest as are still intact in the
-// slot's rings and fit its room in the slab -- go out of the two rings: records with byte_pos counted from the slot's bytes in the slab.
+// table has been zeroed in front).  The groups completed since the previous chunk go out of the slot's rings (out_ring.h, out_ring_gather).
 __global__ __launch_bounds__(64) void k_deliver_dg(PacketDev pk, uint8_t *slab, unsigned long long off_dg)
 {
-  const int lane = threadIdx.x;
   PacketSlot &ps = pk.slots[blockIdx.x];
-  if (!ps.dl_rec_off) return;
-  const long long dg_count = ps.dg_count, dg_bytes = ps.dg_bytes, done = ps.dl_done;
-  const unsigned long long rec_mask = ps.rec_mask, bytes_mask = ps.bytes_mask;
-  const dabx_datagroup_info *recs = ps.recs;
-  const uint8_t *ring = ps.bytes;
-  long long first = done;
-  if (dg_count - first > (long long)ps.dl_rec_cap) first = dg_count - ps.dl_rec_cap;
-  if (dg_count - first > (long long)rec_mask + 1) first = dg_count - ((long long)rec_mask + 1);
-  // a series of up to DABX_DG_MAX_BYTES may have been written from dg_bytes on: what that range covers in the ring is gone (engine.cpp, packet_window)
-  while (first < dg_count) {
-    const long long pos = recs[(size_t)((unsigned long long)first & rec_mask)].byte_pos;
-    if (dg_bytes + DABX_DG_MAX_BYTES - pos <= (long long)bytes_mask + 1 && dg_bytes - pos <= (long long)ps.dl_bytes_cap) break;
-    first++;
-  }
-  const int n = (int)(dg_count - first);
-  const long long base = n ? recs[(size_t)((unsigned long long)first & rec_mask)].byte_pos : dg_bytes;
-  const long long n_bytes = dg_bytes - base;
-  dabx_datagroup_info *ro = reinterpret_cast<dabx_datagroup_info *>(slab + ps.dl_rec_off);
-  for (int i = lane; i < n; i += 64) {
-    dabx_datagroup_info r = recs[(size_t)((unsigned long long)(first + i) & rec_mask)];
-    r.byte_pos -= base;
-    ro[i] = r;
-  }
-  uint8_t *bo = slab + ps.dl_bytes_off;
-  for (long long k = lane; k < n_bytes; k += 64) bo[k] = ring[(size_t)((unsigned long long)(base + k) & bytes_mask)];
-  if (lane == 0) {
+  if (!ps.out.dl_rec_off) return;
+  const OutGather g = out_ring_gather(ps.out, slab, threadIdx.x);
+  if (threadIdx.x == 0) {
     dabx_chunk_dg t;
-    t.first_dg = first; t.n_dg = n; t.dg_lost = (int)(first - done); t.rec_off = ps.dl_rec_off; t.bytes_off = ps.dl_bytes_off; t.n_bytes = n_bytes;
+    t.first_dg = g.first; t.n_dg = g.n; t.dg_lost = (int)(g.first - g.done); t.rec_off = ps.out.dl_rec_off; t.bytes_off = ps.out.dl_bytes_off; t.n_bytes = g.n_bytes;
     t.frames = ps.frames; t.packets = ps.packets; t.addr_match = ps.addr_match; t.continuity_err = ps.continuity_err; t.crc_bad = ps.crc_bad;
-    t.len_bad = ps.len_bad; t.walk_short = ps.walk_short; t.dg_count = dg_count; t.dg_bytes = dg_bytes; t.dg_crc_bad = ps.dg_crc_bad;
+    t.len_bad = ps.len_bad; t.walk_short = ps.walk_short; t.dg_count = ps.out.count; t.dg_bytes = ps.out.n_bytes; t.dg_crc_bad = ps.dg_crc_bad;
     t.dg_overflow = ps.dg_overflow;
     reinterpret_cast<dabx_chunk_dg *>(slab + off_dg)[(size_t)ps.s * pk.max_subch + ps.j] = t;
-    ps.dl_done = dg_count;
+    ps.out.dl_done = ps.out.count;
   }
 }
 int launch_deliver_dg(const EngineDev &e, const DeliverDev &dv, const PacketDev &pk, hipStream_t st)
@@ -209,46 +184,20 @@ int launch_deliver_dg(const EngineDev &e, const DeliverDev &dv, const PacketDev 
   return 0;
 }
 
-// The PAD section (include/dabx.h, dabx_chunk_pad): one wave per PAD slot, behind k_deliver_dg of the chunk, the twin of k_deliver_dg.  The
-// items emitted since the previous chunk -- as many of the newest as are still intact in the slot's rings and fit its room in the slab --
-// go out of the two rings: records with byte_pos counted from the slot's bytes in the slab.
+// The PAD section (include/dabx.h, dabx_chunk_pad): one wave per PAD slot, behind k_deliver_dg of the chunk, in the same way.
 __global__ __launch_bounds__(64) void k_deliver_pad(PadDev pd, uint8_t *slab, unsigned long long off_pad)
 {
-  const int lane = threadIdx.x;
   PadSlot &ps = pd.slots[blockIdx.x];
-  if (!ps.dl_item_off) return;
-  const long long count = ps.item_count, n_all = ps.item_bytes, done = ps.dl_done;
-  const unsigned long long item_mask = ps.item_mask, bytes_mask = ps.bytes_mask;
-  const dabx_pad_item *items = ps.items;
-  const uint8_t *ring = ps.bytes;
-  long long first = done;
-  if (count - first > (long long)ps.dl_item_cap) first = count - ps.dl_item_cap;
-  if (count - first > (long long)item_mask + 1) first = count - ((long long)item_mask + 1);
-  // the group under assembly may have been written up to PAD_ASM_ROOM bytes from item_bytes on: what that range covers in the ring is gone
-  while (first < count) {
-    const long long pos = items[(size_t)((unsigned long long)first & item_mask)].byte_pos;
-    if (n_all + PAD_ASM_ROOM - pos <= (long long)bytes_mask + 1 && n_all - pos <= (long long)ps.dl_bytes_cap) break;
-    first++;
-  }
-  const int n = (int)(count - first);
-  const long long base = n ? items[(size_t)((unsigned long long)first & item_mask)].byte_pos : n_all;
-  const long long n_bytes = n_all - base;
-  dabx_pad_item *ro = reinterpret_cast<dabx_pad_item *>(slab + ps.dl_item_off);
-  for (int i = lane; i < n; i += 64) {
-    dabx_pad_item r = items[(size_t)((unsigned long long)(first + i) & item_mask)];
-    r.byte_pos -= base;
-    ro[i] = r;
-  }
-  uint8_t *bo = slab + ps.dl_bytes_off;
-  for (long long k = lane; k < n_bytes; k += 64) bo[k] = ring[(size_t)((unsigned long long)(base + k) & bytes_mask)];
-  if (lane == 0) {
+  if (!ps.out.dl_rec_off) return;
+  const OutGather g = out_ring_gather(ps.out, slab, threadIdx.x);
+  if (threadIdx.x == 0) {
     dabx_chunk_pad t;
-    t.first_item = first; t.n_items = n; t.items_lost = (int)(first - done); t.item_off = ps.dl_item_off; t.bytes_off = ps.dl_bytes_off; t.n_bytes = n_bytes;
+    t.first_item = g.first; t.n_items = g.n; t.items_lost = (int)(g.first - g.done); t.item_off = ps.out.dl_rec_off; t.bytes_off = ps.out.dl_bytes_off; t.n_bytes = g.n_bytes;
     t.superframes = ps.c.superframes; t.aus = ps.c.aus; t.pad_aus = ps.c.pad_aus; t.pad_bad = ps.c.pad_bad; t.labels = ps.c.labels;
     t.label_bytes = ps.c.label_bytes; t.groups = ps.c.groups; t.group_bytes = ps.c.group_bytes; t.dg_crc_bad = ps.c.dg_crc_bad;
     t.dl_overflow = ps.c.dl_overflow; t.li_bad = ps.c.li_bad;
     reinterpret_cast<dabx_chunk_pad *>(slab + off_pad)[(size_t)ps.s * pd.max_subch + ps.j] = t;
-    ps.dl_done = count;
+    ps.out.dl_done = ps.out.count;
   }
 }
 int launch_deliver_pad(const EngineDev &e, const DeliverDev &dv, const PadDev &pd, hipStream_t st)

@@ -19,6 +19,7 @@
 #include <string>
 #include <thread>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 namespace dabx {
@@ -105,6 +106,57 @@ struct Ingest {
   int16_t *tab_int = nullptr; float *tab_frac = nullptr;
 };
 
+// The job table of a stage that runs on some slots only (k_packet: PacketSlot / PacketDev, k_pad: PadSlot / PadDev).  Nothing of it exists
+// until the stage's dabx_set_*_mode first switches a slot on: host stays empty, dev.n stays 0 and no batch launches the kernel.
+// host[sj].st mirrors the device's table entry of the slot; the device owns it between download and upload (both with the engine drained).
+template <class Slot, class Dev> struct JobTable {
+  struct Host { bool on = false; Slot st{}; long long seen = 0, lost = 0; };     // seen: items a read call has returned or passed, lost: those it found gone
+  std::vector<Host> host;                      // [S][max_subch], or empty
+  std::vector<int> index;                      // [S][max_subch] place in the table, -1 = not a slot of this stage
+  Dev dev{};                                   // slots = the table on the device, n = its length
+  int cap = 0;
+  bool on(size_t sj) const { return !host.empty() && host[sj].on; }
+  // the device's table back into the mirror
+  int download(int max_subch)
+  {
+    if (dev.n <= 0) return 0;
+    std::vector<Slot> tab((size_t)dev.n);
+    DABX_HIP(hipMemcpy(tab.data(), dev.slots, sizeof(Slot) * tab.size(), hipMemcpyDeviceToHost));
+    for (const Slot &q : tab) host[(size_t)q.s * max_subch + q.j].st = q;
+    return 0;
+  }
+  // ... and the table rebuilt from the mirror: the stage's slots, in (stream, slot) order
+  int upload()
+  {
+    std::vector<Slot> tab;
+    std::fill(index.begin(), index.end(), -1);
+    for (size_t sj = 0; sj < host.size(); sj++)
+      if (host[sj].on) { index[sj] = (int)tab.size(); tab.push_back(host[sj].st); }
+    if ((int)tab.size() > cap) {
+      Slot *q = nullptr;
+      const int n = std::max<int>(2 * cap, std::max<int>(16, (int)tab.size()));
+      DABX_HIP(hipMalloc(&q, sizeof(Slot) * (size_t)n));
+      if (dev.slots) (void)hipFree(dev.slots);
+      dev.slots = q; cap = n;
+    }
+    if (!tab.empty()) DABX_HIP(hipMemcpy(dev.slots, tab.data(), sizeof(Slot) * tab.size(), hipMemcpyHostToDevice));
+    dev.n = (int)tab.size();
+    return 0;
+  }
+  void drop(size_t sj)                         // the slot leaves the stage: its rings are freed
+  {
+    if (sj >= host.size() || !host[sj].on) return;
+    (void)hipFree(host[sj].st.out.bytes);
+    (void)hipFree(host[sj].st.out.recs);
+    host[sj] = Host{};
+  }
+  void destroy()
+  {
+    for (size_t sj = 0; sj < host.size(); sj++) drop(sj);
+    if (dev.slots) (void)hipFree(dev.slots);
+  }
+};
+
 struct dabx_engine : dabx::EngineHead {          // (iqfile.h: the ring format, where iqfile.cpp can read it)
   dabx_config cfg{};
   EngineDev dev{};
@@ -155,26 +207,8 @@ struct dabx_engine : dabx::EngineHead {          // (iqfile.h: the ring format, 
   bool level_dirty = false;                    // exact_level_tracker: steps have been issued since k_level_exact last ran behind them
   Delivery dl;
   Ingest ing;
-  // Packet-mode slots (include/dabx.h "Packet-mode data sub-channels", k_packet).  Nothing here exists until the first dabx_set_packet_mode:
-  // pkt stays empty, pkt_dev.n stays 0 and no batch launches k_packet.  pkt[sj].st mirrors the device's job-table entry of the slot; the
-  // device owns it between packet_download and packet_upload (both with the engine drained).
-  struct PacketHost { bool on = false; PacketSlot st{}; long long seen = 0, lost = 0; };
-  std::vector<PacketHost> pkt;                 // [S][max_subch], or empty
-  std::vector<int> pkt_index;                  // [S][max_subch] place in the job table, -1 = not in packet mode
-  PacketDev pkt_dev{};                         // slots = the job table on the device, n = its length
-  int pkt_cap = 0;
-  int packet_download();
-  int packet_upload();
-  void packet_drop(size_t sj);
-  // PAD slots (include/dabx.h "Programme-associated data", k_pad): the same arrangement.  Nothing exists until the first dabx_set_pad_mode.
-  struct PadHost { bool on = false; PadSlot st{}; long long seen = 0, lost = 0; };
-  std::vector<PadHost> pad;                    // [S][max_subch], or empty
-  std::vector<int> pad_index;                  // [S][max_subch] place in the job table, -1 = no PAD decoding
-  PadDev pad_dev{};
-  int pad_cap = 0;
-  int pad_download();
-  int pad_upload();
-  void pad_drop(size_t sj);
+  JobTable<PacketSlot, PacketDev> pkt;         // packet-mode slots (include/dabx.h "Packet-mode data sub-channels", k_packet)
+  JobTable<PadSlot, PadDev> pad;               // PAD slots (include/dabx.h "Programme-associated data", k_pad)
   int build_msc_classes();
   int delivery_layout();                       // offsets of every slot's bytes in a slab for the sub-channels configured now
   int delivery_begin(DeliverDev *dv, int *slot, int *devslab);     // a chunk closes: host + device slab, front gather on stream a
@@ -332,6 +366,33 @@ static constexpr int DL_SF_CAP = (4 * DL_FRAMES + 4) / 5;          // super fram
 static_assert(DL_FRAMES == DABX_CHUNK_FRAMES, "include/dabx.h: DABX_CHUNK_FRAMES is the library's MSC batch");
 #endif
 
+// One section of the slab's head part for the slots of a job table: its table of S * M records at *off_table, then every slot's records and
+// bytes, as much as one batch can emit (the caps of its ring).  Without such a slot, or unwanted: no section, the slots' offsets stay 0.
+template <class Tab> static size_t layout_section(Tab &tab, bool want, size_t off, size_t table_bytes, uint64_t *off_table)
+{
+  bool any = false;
+  for (auto &q : tab.host) { q.st.out.dl_rec_off = q.st.out.dl_bytes_off = 0; any = any || q.on; }
+  if (!want || !any) return off;
+  off = align_up(off, 16);
+  *off_table = off; off += table_bytes;
+  for (auto &q : tab.host) {
+    if (!q.on) continue;
+    auto &r = q.st.out;
+    r.dl_rec_off = off; off += (size_t)r.dl_rec_cap * sizeof(*r.recs);
+    r.dl_bytes_off = off; off = align_up(off + r.dl_bytes_cap, 16);
+  }
+  return off;
+}
+// ... and for dabx_delivery_open: the room that section needs for the slots there are now (one that is switched on later has to fit the
+// slack); delivery starts with what they emit from now on
+template <class Tab> static size_t section_capacity(Tab &tab, size_t table_bytes)
+{
+  size_t cap = tab.host.empty() ? 0 : table_bytes + 16;
+  for (auto &q : tab.host)
+    if (q.on) { q.st.out.dl_done = q.st.out.count; cap += (size_t)q.st.out.dl_rec_cap * sizeof(*q.st.out.recs) + q.st.out.dl_bytes_cap + 16; }
+  return cap;
+}
+
 // Where every slot's bytes lie in a slab with the sub-channels configured now: table part (header, stream and slot records, FIBs,
 // CRC flags, frame records), then the logical frames of all slots, then the super frames of all slots.  Uploaded to the device;
 // called with the engine drained (dabx_delivery_open, dabx_set_subchannels*).
@@ -363,38 +424,12 @@ int dabx_engine::delivery_layout()
       lo[3 * sj + 2] = off;
       off += (size_t)DL_SF_CAP * sizeof(dabx_superframe_info);
     }
-  // the data-group section (dabx_chunk_dg): only with packet-mode slots -- without one the slab is what it has always been.  Callers hold a
-  // fresh mirror of the job table (packet_download with the engine drained); it goes back to the device below
-  bool any_pkt = false;
-  for (auto &q : pkt) { q.st.dl_rec_off = q.st.dl_bytes_off = 0; q.st.dl_rec_cap = q.st.dl_bytes_cap = 0; any_pkt = any_pkt || q.on; }
-  if (D.want_dg && any_pkt && !d.fic_only) {
-    off = align_up(off, 16);
-    h.off_dg = off; off += S * M * sizeof(dabx_chunk_dg);
-    h.what |= DABX_DELIVER_DG;
-    for (size_t sj = 0; sj < S * M; sj++) {
-      if (!pkt[sj].on) continue;
-      PacketSlot &st = pkt[sj].st;
-      const size_t kbps = (size_t)subch_host[sj].kbps;
-      st.dl_rec_cap = (uint32_t)(4 * F * (kbps / 8)); st.dl_bytes_cap = (uint32_t)(4 * F * 3 * kbps + DABX_DG_MAX_BYTES);
-      st.dl_rec_off = off; off += (size_t)st.dl_rec_cap * sizeof(dabx_datagroup_info);
-      st.dl_bytes_off = off; off = align_up(off + st.dl_bytes_cap, 16);
-    }
-  }
-  // the PAD section (dabx_chunk_pad): only with PAD slots, behind the data-group section; its room per slot is pad_core.h's per-batch bound
-  bool any_pad = false;
-  for (auto &q : pad) { q.st.dl_item_off = q.st.dl_bytes_off = 0; q.st.dl_item_cap = q.st.dl_bytes_cap = 0; any_pad = any_pad || q.on; }
-  if (D.want_pad && any_pad && !d.fic_only) {
-    off = align_up(off, 16);
-    h.off_pad = off; off += S * M * sizeof(dabx_chunk_pad);
-    h.what |= DABX_DELIVER_PAD;
-    for (size_t sj = 0; sj < S * M; sj++) {
-      if (!pad[sj].on) continue;
-      PadSlot &st = pad[sj].st;
-      st.dl_item_cap = PAD_DL_ITEM_CAP; st.dl_bytes_cap = PAD_DL_BYTES_CAP;
-      st.dl_item_off = off; off += (size_t)st.dl_item_cap * sizeof(dabx_pad_item);
-      st.dl_bytes_off = off; off = align_up(off + st.dl_bytes_cap, 16);
-    }
-  }
+  // the data-group section (dabx_chunk_dg) and behind it the PAD section (dabx_chunk_pad): only with such slots -- without one the slab is
+  // what it has always been.  Callers hold fresh mirrors of the job tables (download with the engine drained); they go back to the device below
+  off = layout_section(pkt, D.want_dg && !d.fic_only, off, S * M * sizeof(dabx_chunk_dg), &h.off_dg);
+  if (h.off_dg) h.what |= DABX_DELIVER_DG;
+  off = layout_section(pad, D.want_pad && !d.fic_only, off, S * M * sizeof(dabx_chunk_pad), &h.off_pad);
+  if (h.off_pad) h.what |= DABX_DELIVER_PAD;
   off = align_up(off, 256);
   h.off_msc = off;
   if ((D.what & (DABX_DELIVER_MSC | DABX_DELIVER_MSC_NOT_DABPLUS)) && !d.fic_only)
@@ -412,8 +447,8 @@ int dabx_engine::delivery_layout()
   }
   D.hdr = h;
   D.bytes = off;
-  if (!pkt.empty()) if (int rc = packet_upload()) return rc;
-  if (!pad.empty()) if (int rc = pad_upload()) return rc;
+  if (!pkt.host.empty()) if (int rc = pkt.upload()) return rc;
+  if (!pad.host.empty()) if (int rc = pad.upload()) return rc;
   if (S * M) {
     DABX_HIP(hipMemcpy(D.layout_off, lo.data(), sizeof(unsigned long long) * 3 * S * M, hipMemcpyHostToDevice));
     std::vector<int32_t> ids(subch_id_host.begin(), subch_id_host.begin() + S * M);
@@ -621,6 +656,91 @@ static void ingest_free(dabx_engine *e)
   for (void *q : {(void *)I.tables_dev, (void *)I.work, (void *)I.carry, (void *)I.tab_int, (void *)I.tab_frac}) if (q) (void)hipFree(q);
   if (I.tables_host) (void)hipHostFree(I.tables_host);
   I = Ingest{};
+}
+
+// ---- slots with output rings (out_ring.h): what the packet-mode and the PAD entry points below share -------------------------------------
+static uint32_t pow2_at_least(size_t v) { uint32_t p = 1; while (p < v) p <<= 1; return p; }
+
+// The rings of a slot that is switched on (n_bytes, n_rec: powers of two) and what one chunk of the bulk delivery has room for
+template <class Rec> static bool out_ring_create(OutRing<Rec> *r, uint32_t n_bytes, uint32_t n_rec, uint32_t asm_room, uint32_t dl_rec_cap, uint32_t dl_bytes_cap)
+{
+  void *b = nullptr, *q = nullptr;
+  if (hipMalloc(&b, n_bytes) != hipSuccess || hipMalloc(&q, sizeof(Rec) * (size_t)n_rec) != hipSuccess) {
+    if (b) (void)hipFree(b);
+    return false;
+  }
+  r->bytes = static_cast<uint8_t *>(b); r->recs = static_cast<Rec *>(q);
+  r->bytes_mask = n_bytes - 1; r->rec_mask = n_rec - 1; r->asm_room = asm_room;
+  r->dl_rec_cap = dl_rec_cap; r->dl_bytes_cap = dl_bytes_cap;
+  return true;
+}
+
+// The tail of dabx_set_packet_mode / dabx_set_pad_mode (engine drained): the slab of an open delivery follows the stage's slots.
+// delivery_layout writes BOTH job tables back from their mirrors, so the other stage's is refreshed first.
+template <class Tab> static int relayout_open_delivery(dabx_engine *e, size_t sj, const SubchDev &sc, Tab &other)
+{
+  if (!e->dl.open) return 0;
+  e->subch_host[sj] = sc;
+  if (int rc = other.download(e->dev.max_subch)) return rc;
+  if (int rc = e->delivery_layout()) {
+    const std::string why = dabx::last_error();
+    delivery_free(e);
+    set_error("%s -- the delivery has been closed", why.c_str());
+    return rc;
+  }
+  return 0;
+}
+
+// The slot's table entry as the device holds it and the items [*lo, count) whose record and bytes are still intact (out_ring.h); older ones
+// that no call has returned yet are counted as lost.  Reads the entry and, as a rule, ONE record (the oldest candidate's).
+template <class Slot, class Dev> static int ring_window(dabx_engine *e, JobTable<Slot, Dev> &tab, size_t sj, Slot *st, long long *lo)
+{
+  if (int rc = sync_all(e)) return rc;
+  DABX_HIP(hipMemcpy(st, tab.dev.slots + tab.index[sj], sizeof(Slot), hipMemcpyDeviceToHost));
+  const auto &r = st->out;
+  long long first = out_ring_oldest(r);
+  while (first < r.count) {
+    std::remove_reference_t<decltype(*r.recs)> q;
+    DABX_HIP(hipMemcpy(&q, r.recs + (size_t)(first & r.rec_mask), sizeof(q), hipMemcpyDeviceToHost));
+    if (out_ring_intact(r, q.byte_pos)) break;
+    first++;
+  }
+  auto &h = tab.host[sj];
+  if (first > h.seen) { h.lost += first - h.seen; h.seen = first; }
+  *lo = first;
+  return 0;
+}
+
+// dabx_read_datagroups / dabx_read_pad_items behind their argument checks: the newest n intact items, of these the newest that fit max_bytes
+template <class Slot, class Dev, class Rec> static int ring_read(dabx_engine *e, JobTable<Slot, Dev> &tab, size_t sj, int n, Rec *info, uint8_t *bytes, size_t max_bytes)
+{
+  if (!tab.on(sj)) return 0;
+  Slot st;
+  long long lo = 0;
+  if (int rc = ring_window(e, tab, sj, &st, &lo)) return rc;
+  const OutRing<Rec> &r = st.out;
+  long long from = std::max(lo, r.count - n);
+  int have = (int)(r.count - from);
+  if (have > 0) {                                             // the records [from, count): one or two runs of the ring
+    const size_t ring = (size_t)r.rec_mask + 1, at = (size_t)(from & r.rec_mask), head = std::min<size_t>((size_t)have, ring - at);
+    DABX_HIP(hipMemcpy(info, r.recs + at, sizeof(Rec) * head, hipMemcpyDeviceToHost));
+    if ((size_t)have > head) DABX_HIP(hipMemcpy(info + head, r.recs, sizeof(Rec) * ((size_t)have - head), hipMemcpyDeviceToHost));
+    int skip = 0;                                             // the newest items that fit
+    if (bytes) while (skip < have && (unsigned long long)(r.n_bytes - info[skip].byte_pos) > max_bytes) skip++;
+    if (skip) { memmove(info, info + skip, sizeof(Rec) * (size_t)(have - skip)); have -= skip; }
+  }
+  if (have > 0) {
+    const long long base = info[0].byte_pos, total = r.n_bytes - base;
+    for (int i = 0; i < have; i++) info[i].byte_pos -= base;
+    if (bytes && total > 0) {
+      const size_t ring = (size_t)r.bytes_mask + 1, at = (size_t)((unsigned long long)base & r.bytes_mask);
+      const size_t head = std::min<size_t>((size_t)total, ring - at);
+      DABX_HIP(hipMemcpy(bytes, r.bytes + at, head, hipMemcpyDeviceToHost));
+      if ((size_t)total > head) DABX_HIP(hipMemcpy(bytes + head, r.bytes, (size_t)total - head, hipMemcpyDeviceToHost));
+    }
+  }
+  tab.host[sj].seen = std::max(tab.host[sj].seen, r.count);
+  return have;
 }
 
 static int need_device_e()
@@ -857,10 +977,8 @@ void dabx_destroy(dabx_engine *e)
     if (e->aslot[i]) (void)hipFree(e->aslot[i]);
     if (e->aslot_done[i]) (void)hipEventDestroy(e->aslot_done[i]);
   }
-  for (size_t sj = 0; sj < e->pkt.size(); sj++) e->packet_drop(sj);
-  if (e->pkt_dev.slots) (void)hipFree(e->pkt_dev.slots);
-  for (size_t sj = 0; sj < e->pad.size(); sj++) e->pad_drop(sj);
-  if (e->pad_dev.slots) (void)hipFree(e->pad_dev.slots);
+  e->pkt.destroy();
+  e->pad.destroy();
   for (void *p : e->allocs) (void)hipFree(p);
   if (e->locked_host) (void)hipHostFree(e->locked_host);
   if (e->seq_timeouts_host) (void)hipHostFree(e->seq_timeouts_host);
@@ -890,8 +1008,8 @@ static int set_subchannels_impl(dabx_engine *e, int stream, const dabx_subch_des
   }
   // refresh the host mirror: the device owns the dynamic fields (cif_out, super-frame state, counters)
   DABX_HIP(hipMemcpy(e->subch_host.data(), d.subch, sizeof(SubchDev) * e->subch_host.size(), hipMemcpyDeviceToHost));
-  if ((rc = e->packet_download())) return rc;
-  if ((rc = e->pad_download())) return rc;
+  if ((rc = e->pkt.download(d.max_subch))) return rc;
+  if ((rc = e->pad.download(d.max_subch))) return rc;
   int max_kbps = e->max_kbps;
   std::vector<SubchDev> row(std::max(1, d.max_subch));
   for (int j = 0; j < n; j++) {
@@ -981,13 +1099,13 @@ static int set_subchannels_impl(dabx_engine *e, int stream, const dabx_subch_des
     }
   }
   DABX_HIP(hipMemcpy(d.subch, e->subch_host.data(), sizeof(SubchDev) * e->subch_host.size(), hipMemcpyHostToDevice));
-  if (!e->pkt.empty()) {                // a new or changed slot loses its packet mode; one that keeps running (a move included) keeps it and its state
-    for (size_t sj : restarted) e->packet_drop(sj);
-    if ((rc = e->packet_upload())) return rc;
+  if (!e->pkt.host.empty()) {           // a new or changed slot loses its packet mode; one that keeps running (a move included) keeps it and its state
+    for (size_t sj : restarted) e->pkt.drop(sj);
+    if ((rc = e->pkt.upload())) return rc;
   }
-  if (!e->pad.empty()) {                // ... and so does PAD decoding
-    for (size_t sj : restarted) e->pad_drop(sj);
-    if ((rc = e->pad_upload())) return rc;
+  if (!e->pad.host.empty()) {           // ... and so does PAD decoding
+    for (size_t sj : restarted) e->pad.drop(sj);
+    if ((rc = e->pad.upload())) return rc;
   }
   if (e->dl.open) {
     // slots that start anew count their frames from 0 again; the slab layout follows the new sub-channels (engine drained above)
@@ -1015,45 +1133,9 @@ int dabx_set_subchannels_at(dabx_engine *e, int stream, const dabx_subch_desc *d
   return set_subchannels_impl(e, stream, desc, n, at_cif);
 }
 
-// ---- packet-mode data sub-channels (include/dabx.h, packet_core.h, k_packet) --------------------------------------------------------
+// ---- slots with output rings: packet-mode data sub-channels (packet_core.h, k_packet) and programme-associated data (pad_core.h, k_pad) ----
 static_assert(sizeof(dabx_chunk_dg) == 128 && sizeof(dabx_datagroup_info) == 32 && sizeof(dabx_packet_stats) == 128 && sizeof(dabx_packet_config) == 32, "include/dabx.h: packet-mode records");
-
-// the device's job table back into the host mirror (engine drained)
-int dabx_engine::packet_download()
-{
-  if (pkt_dev.n <= 0) return 0;
-  std::vector<PacketSlot> tab((size_t)pkt_dev.n);
-  DABX_HIP(hipMemcpy(tab.data(), pkt_dev.slots, sizeof(PacketSlot) * tab.size(), hipMemcpyDeviceToHost));
-  for (const PacketSlot &q : tab) pkt[(size_t)q.s * dev.max_subch + q.j].st = q;
-  return 0;
-}
-// ... and the table rebuilt from the mirror: the slots in packet mode, in (stream, slot) order
-int dabx_engine::packet_upload()
-{
-  std::vector<PacketSlot> tab;
-  std::fill(pkt_index.begin(), pkt_index.end(), -1);
-  for (size_t sj = 0; sj < pkt.size(); sj++)
-    if (pkt[sj].on) { pkt_index[sj] = (int)tab.size(); tab.push_back(pkt[sj].st); }
-  if ((int)tab.size() > pkt_cap) {
-    PacketSlot *q = nullptr;
-    const int cap = std::max<int>(2 * pkt_cap, std::max<int>(16, (int)tab.size()));
-    DABX_HIP(hipMalloc(&q, sizeof(PacketSlot) * (size_t)cap));
-    if (pkt_dev.slots) (void)hipFree(pkt_dev.slots);
-    pkt_dev.slots = q; pkt_cap = cap;
-  }
-  if (!tab.empty()) DABX_HIP(hipMemcpy(pkt_dev.slots, tab.data(), sizeof(PacketSlot) * tab.size(), hipMemcpyHostToDevice));
-  pkt_dev.n = (int)tab.size();
-  return 0;
-}
-void dabx_engine::packet_drop(size_t sj)
-{
-  if (sj >= pkt.size() || !pkt[sj].on) return;
-  (void)hipFree(pkt[sj].st.bytes);
-  (void)hipFree(pkt[sj].st.recs);
-  pkt[sj] = PacketHost{};
-}
-
-static uint32_t pow2_at_least(size_t v) { uint32_t p = 1; while (p < v) p <<= 1; return p; }
+static_assert(sizeof(dabx_chunk_pad) == 128 && sizeof(dabx_pad_item) == 32 && sizeof(dabx_pad_stats) == 128 && sizeof(dabx_pad_config) == 32, "include/dabx.h: PAD records");
 
 int dabx_set_packet_mode(dabx_engine *e, int stream, int j, const dabx_packet_config *cfg)
 {
@@ -1071,97 +1153,37 @@ int dabx_set_packet_mode(dabx_engine *e, int stream, int j, const dabx_packet_co
     set_error("dabx_set_packet_mode: stream %d slot %d is %s", stream, j, !sc.active ? "not active" : sc.dab_plus ? "a DAB+ slot" : "not at a multiple of 8 kbit/s up to 384");
     return DABX_E_ARG;
   }
-  if (e->pkt.empty()) {
+  auto &tab = e->pkt;
+  if (tab.host.empty()) {
     if (!cfg) return 0;
-    e->pkt.resize((size_t)e->dev.n_streams * e->dev.max_subch);
-    e->pkt_index.assign(e->pkt.size(), -1);
+    tab.host.resize((size_t)e->dev.n_streams * e->dev.max_subch);
+    tab.index.assign(tab.host.size(), -1);
   }
-  if ((rc = e->packet_download())) return rc;
-  e->packet_drop(sj);
+  if ((rc = tab.download(e->dev.max_subch))) return rc;
+  tab.drop(sj);
   if (cfg) {
     // two full batches (56 logical frames) of single-packet groups: a record per 24-byte packet, their payloads, and room for the series
-    // under assembly, which lives in the byte ring in front of the completed groups (packet_core.h)
-    dabx_engine::PacketHost h;
+    // under assembly, which lives in the byte ring in front of the completed groups (packet_core.h); a chunk: one batch of them
+    decltype(e->pkt)::Host h;
     h.on = true;
     h.st.s = stream; h.st.j = j; h.st.address = cfg->packet_address; h.st.first_byte = -1; h.st.run_crc = 0xFFFFu;
-    const uint32_t n_rec = pow2_at_least((size_t)2 * 4 * MSC_BATCH_FRAMES * (sc.kbps / 8));
-    const uint32_t n_bytes = pow2_at_least((size_t)2 * 4 * MSC_BATCH_FRAMES * 3 * sc.kbps + DABX_DG_MAX_BYTES);
-    void *b = nullptr, *r = nullptr;
-    if (hipMalloc(&b, n_bytes) != hipSuccess || hipMalloc(&r, sizeof(dabx_datagroup_info) * (size_t)n_rec) != hipSuccess) {
-      if (b) (void)hipFree(b);
+    const size_t recs = (size_t)4 * MSC_BATCH_FRAMES * (sc.kbps / 8), bytes = (size_t)4 * MSC_BATCH_FRAMES * 3 * sc.kbps;
+    if (!out_ring_create(&h.st.out, pow2_at_least(2 * bytes + DABX_DG_MAX_BYTES), pow2_at_least(2 * recs), DABX_DG_MAX_BYTES, (uint32_t)recs,
+                         (uint32_t)(bytes + DABX_DG_MAX_BYTES))) {
       set_error("dabx_set_packet_mode: out of device memory");
-      (void)e->packet_upload();
+      (void)tab.upload();
       return DABX_E_NOMEM;
     }
-    h.st.bytes = static_cast<uint8_t *>(b); h.st.recs = static_cast<dabx_datagroup_info *>(r);
-    h.st.bytes_mask = n_bytes - 1; h.st.rec_mask = n_rec - 1;
-    e->pkt[sj] = h;
+    tab.host[sj] = h;
   }
-  if ((rc = e->packet_upload())) return rc;
-  if (e->dl.open) {                       // the slab's data-group section follows the packet-mode slots (engine drained above)
-    e->subch_host[sj] = sc;
-    if ((rc = e->pad_download())) return rc;      // delivery_layout writes both job tables back from their mirrors
-    if ((rc = e->delivery_layout())) {
-      const std::string why = dabx::last_error();
-      delivery_free(e);
-      set_error("%s -- the delivery has been closed", why.c_str());
-      return rc;
-    }
-  }
-  return 0;
-}
-
-// The slot's table entry as the device holds it and the groups [*lo, dg_count) whose record and bytes are still intact; groups older than
-// that which no call has returned yet are counted as lost.  Reads the entry and, as a rule, ONE record (the oldest candidate's).
-static int packet_window(dabx_engine *e, size_t sj, PacketSlot *st, long long *lo)
-{
-  if (int rc = sync_all(e)) return rc;
-  DABX_HIP(hipMemcpy(st, e->pkt_dev.slots + e->pkt_index[sj], sizeof(PacketSlot), hipMemcpyDeviceToHost));
-  long long first = std::max<long long>(0, st->dg_count - ((long long)st->rec_mask + 1));
-  // the device may write a series of up to DABX_DG_MAX_BYTES from dg_bytes on: whatever that range covers in the ring is gone
-  const long long ring = (long long)st->bytes_mask + 1;
-  while (first < st->dg_count) {
-    dabx_datagroup_info r;
-    DABX_HIP(hipMemcpy(&r, st->recs + (size_t)(first & st->rec_mask), sizeof(r), hipMemcpyDeviceToHost));
-    if (st->dg_bytes + DABX_DG_MAX_BYTES - r.byte_pos <= ring) break;
-    first++;
-  }
-  dabx_engine::PacketHost &h = e->pkt[sj];
-  if (first > h.seen) { h.lost += first - h.seen; h.seen = first; }
-  *lo = first;
-  return 0;
+  if ((rc = tab.upload())) return rc;
+  return relayout_open_delivery(e, sj, sc, e->pad);
 }
 
 int dabx_read_datagroups(dabx_engine *e, int stream, int j, int n, dabx_datagroup_info *info, uint8_t *bytes, size_t max_bytes)
 {
   if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch || n <= 0 || !info) { set_error("dabx_read_datagroups: bad argument"); return DABX_E_ARG; }
-  const size_t sj = (size_t)stream * e->dev.max_subch + j;
-  if (e->pkt.empty() || !e->pkt[sj].on) return 0;
-  PacketSlot st;
-  long long lo = 0;
-  if (int rc = packet_window(e, sj, &st, &lo)) return rc;
-  long long from = std::max(lo, st.dg_count - n);
-  int have = (int)(st.dg_count - from);
-  if (have > 0) {                                             // the records [from, dg_count): one or two runs of the ring
-    const size_t ring = (size_t)st.rec_mask + 1, at = (size_t)(from & st.rec_mask), head = std::min<size_t>((size_t)have, ring - at);
-    DABX_HIP(hipMemcpy(info, st.recs + at, sizeof(dabx_datagroup_info) * head, hipMemcpyDeviceToHost));
-    if ((size_t)have > head) DABX_HIP(hipMemcpy(info + head, st.recs, sizeof(dabx_datagroup_info) * ((size_t)have - head), hipMemcpyDeviceToHost));
-    int skip = 0;                                             // the newest groups that fit
-    if (bytes) while (skip < have && (unsigned long long)(st.dg_bytes - info[skip].byte_pos) > max_bytes) skip++;
-    if (skip) { memmove(info, info + skip, sizeof(dabx_datagroup_info) * (size_t)(have - skip)); have -= skip; }
-  }
-  if (have > 0) {
-    const long long base = info[0].byte_pos, total = st.dg_bytes - base;
-    for (int i = 0; i < have; i++) info[i].byte_pos -= base;
-    if (bytes && total > 0) {
-      const size_t ring = (size_t)st.bytes_mask + 1, at = (size_t)((unsigned long long)base & st.bytes_mask);
-      const size_t head = std::min<size_t>((size_t)total, ring - at);
-      DABX_HIP(hipMemcpy(bytes, st.bytes + at, head, hipMemcpyDeviceToHost));
-      if ((size_t)total > head) DABX_HIP(hipMemcpy(bytes + head, st.bytes, (size_t)total - head, hipMemcpyDeviceToHost));
-    }
-  }
-  e->pkt[sj].seen = std::max(e->pkt[sj].seen, st.dg_count);
-  return have;
+  return ring_read(e, e->pkt, (size_t)stream * e->dev.max_subch + j, n, info, bytes, max_bytes);
 }
 
 int dabx_get_packet_stats(dabx_engine *e, int stream, int j, dabx_packet_stats *out)
@@ -1169,51 +1191,15 @@ int dabx_get_packet_stats(dabx_engine *e, int stream, int j, dabx_packet_stats *
   if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch || !out) { set_error("dabx_get_packet_stats: bad argument"); return DABX_E_ARG; }
   memset(out, 0, sizeof(*out));
   const size_t sj = (size_t)stream * e->dev.max_subch + j;
-  if (e->pkt.empty() || !e->pkt[sj].on) return sync_all(e);
+  if (!e->pkt.on(sj)) return sync_all(e);
   PacketSlot st;
   long long lo = 0;
-  if (int rc = packet_window(e, sj, &st, &lo)) return rc;
+  if (int rc = ring_window(e, e->pkt, sj, &st, &lo)) return rc;
   out->frames = st.frames; out->packets = st.packets; out->addr_match = st.addr_match; out->continuity_err = st.continuity_err;
-  out->crc_bad = st.crc_bad; out->len_bad = st.len_bad; out->walk_short = st.walk_short; out->dg_count = st.dg_count;
-  out->dg_bytes = st.dg_bytes; out->dg_crc_bad = st.dg_crc_bad; out->dg_overflow = st.dg_overflow; out->dg_lost = e->pkt[sj].lost;
+  out->crc_bad = st.crc_bad; out->len_bad = st.len_bad; out->walk_short = st.walk_short; out->dg_count = st.out.count;
+  out->dg_bytes = st.out.n_bytes; out->dg_crc_bad = st.dg_crc_bad; out->dg_overflow = st.dg_overflow; out->dg_lost = e->pkt.host[sj].lost;
   out->active = 1; out->packet_address = st.address;
   return 0;
-}
-
-// ---- programme-associated data (include/dabx.h, pad_core.h, k_pad): the host side is that of the packet-mode slots ---------------------
-static_assert(sizeof(dabx_chunk_pad) == 128 && sizeof(dabx_pad_item) == 32 && sizeof(dabx_pad_stats) == 128 && sizeof(dabx_pad_config) == 32, "include/dabx.h: PAD records");
-
-int dabx_engine::pad_download()
-{
-  if (pad_dev.n <= 0) return 0;
-  std::vector<PadSlot> tab((size_t)pad_dev.n);
-  DABX_HIP(hipMemcpy(tab.data(), pad_dev.slots, sizeof(PadSlot) * tab.size(), hipMemcpyDeviceToHost));
-  for (const PadSlot &q : tab) pad[(size_t)q.s * dev.max_subch + q.j].st = q;
-  return 0;
-}
-int dabx_engine::pad_upload()
-{
-  std::vector<PadSlot> tab;
-  std::fill(pad_index.begin(), pad_index.end(), -1);
-  for (size_t sj = 0; sj < pad.size(); sj++)
-    if (pad[sj].on) { pad_index[sj] = (int)tab.size(); tab.push_back(pad[sj].st); }
-  if ((int)tab.size() > pad_cap) {
-    PadSlot *q = nullptr;
-    const int cap = std::max<int>(2 * pad_cap, std::max<int>(16, (int)tab.size()));
-    DABX_HIP(hipMalloc(&q, sizeof(PadSlot) * (size_t)cap));
-    if (pad_dev.slots) (void)hipFree(pad_dev.slots);
-    pad_dev.slots = q; pad_cap = cap;
-  }
-  if (!tab.empty()) DABX_HIP(hipMemcpy(pad_dev.slots, tab.data(), sizeof(PadSlot) * tab.size(), hipMemcpyHostToDevice));
-  pad_dev.n = (int)tab.size();
-  return 0;
-}
-void dabx_engine::pad_drop(size_t sj)
-{
-  if (sj >= pad.size() || !pad[sj].on) return;
-  (void)hipFree(pad[sj].st.bytes);
-  (void)hipFree(pad[sj].st.items);
-  pad[sj] = PadHost{};
 }
 
 int dabx_set_pad_mode(dabx_engine *e, int stream, int j, const dabx_pad_config *cfg)
@@ -1229,94 +1215,34 @@ int dabx_set_pad_mode(dabx_engine *e, int stream, int j, const dabx_pad_config *
     set_error("dabx_set_pad_mode: stream %d slot %d is %s", stream, j, !sc.active ? "not active" : "not a DAB+ slot");
     return DABX_E_ARG;
   }
-  if (e->pad.empty()) {
+  auto &tab = e->pad;
+  if (tab.host.empty()) {
     if (!cfg) return 0;
-    e->pad.resize((size_t)e->dev.n_streams * e->dev.max_subch);
-    e->pad_index.assign(e->pad.size(), -1);
+    tab.host.resize((size_t)e->dev.n_streams * e->dev.max_subch);
+    tab.index.assign(tab.host.size(), -1);
   }
-  if ((rc = e->pad_download())) return rc;
-  e->pad_drop(sj);
+  if ((rc = tab.download(e->dev.max_subch))) return rc;
+  tab.drop(sj);
   if (cfg) {
-    dabx_engine::PadHost h;
+    decltype(e->pad)::Host h;
     h.on = true;
     h.st.s = stream; h.st.j = j; h.st.sf_seen = sc.sf_count;           // the walk starts with the next super frame completed
     h.st.h.xpad_length = -1; h.st.h.segment_number = -1; h.st.h.segment_no = -1;       // pad_handler.h:74, :79, :83
-    void *b = nullptr, *r = nullptr;
-    if (hipMalloc(&b, PAD_BYTE_RING) != hipSuccess || hipMalloc(&r, sizeof(dabx_pad_item) * (size_t)PAD_ITEM_RING) != hipSuccess) {
-      if (b) (void)hipFree(b);
+    if (!out_ring_create(&h.st.out, PAD_BYTE_RING, PAD_ITEM_RING, PAD_ASM_ROOM, PAD_DL_ITEM_CAP, PAD_DL_BYTES_CAP)) {      // (pad_core.h has the derivations)
       set_error("dabx_set_pad_mode: out of device memory");
-      (void)e->pad_upload();
+      (void)tab.upload();
       return DABX_E_NOMEM;
     }
-    h.st.bytes = static_cast<uint8_t *>(b); h.st.items = static_cast<dabx_pad_item *>(r);
-    h.st.bytes_mask = PAD_BYTE_RING - 1; h.st.item_mask = PAD_ITEM_RING - 1;
-    e->pad[sj] = h;
+    tab.host[sj] = h;
   }
-  if ((rc = e->pad_upload())) return rc;
-  if (e->dl.open) {                       // the slab's PAD section follows the PAD slots (engine drained above)
-    e->subch_host[sj] = sc;
-    if ((rc = e->packet_download())) return rc;
-    if ((rc = e->delivery_layout())) {
-      const std::string why = dabx::last_error();
-      delivery_free(e);
-      set_error("%s -- the delivery has been closed", why.c_str());
-      return rc;
-    }
-  }
-  return 0;
-}
-
-// The slot's table entry as the device holds it and the items [*lo, item_count) whose record and bytes are still intact; older ones that
-// no call has returned yet are counted as lost.
-static int pad_window(dabx_engine *e, size_t sj, PadSlot *st, long long *lo)
-{
-  if (int rc = sync_all(e)) return rc;
-  DABX_HIP(hipMemcpy(st, e->pad_dev.slots + e->pad_index[sj], sizeof(PadSlot), hipMemcpyDeviceToHost));
-  long long first = std::max<long long>(0, st->item_count - ((long long)st->item_mask + 1));
-  // the device may write the group under assembly up to PAD_ASM_ROOM bytes from item_bytes on: whatever that range covers in the ring is gone
-  const long long ring = (long long)st->bytes_mask + 1;
-  while (first < st->item_count) {
-    dabx_pad_item r;
-    DABX_HIP(hipMemcpy(&r, st->items + (size_t)(first & st->item_mask), sizeof(r), hipMemcpyDeviceToHost));
-    if (st->item_bytes + PAD_ASM_ROOM - r.byte_pos <= ring) break;
-    first++;
-  }
-  dabx_engine::PadHost &h = e->pad[sj];
-  if (first > h.seen) { h.lost += first - h.seen; h.seen = first; }
-  *lo = first;
-  return 0;
+  if ((rc = tab.upload())) return rc;
+  return relayout_open_delivery(e, sj, sc, e->pkt);
 }
 
 int dabx_read_pad_items(dabx_engine *e, int stream, int j, int n, dabx_pad_item *info, uint8_t *bytes, size_t max_bytes)
 {
   if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch || n <= 0 || !info) { set_error("dabx_read_pad_items: bad argument"); return DABX_E_ARG; }
-  const size_t sj = (size_t)stream * e->dev.max_subch + j;
-  if (e->pad.empty() || !e->pad[sj].on) return 0;
-  PadSlot st;
-  long long lo = 0;
-  if (int rc = pad_window(e, sj, &st, &lo)) return rc;
-  long long from = std::max(lo, st.item_count - n);
-  int have = (int)(st.item_count - from);
-  if (have > 0) {                                             // the records [from, item_count): one or two runs of the ring
-    const size_t ring = (size_t)st.item_mask + 1, at = (size_t)(from & st.item_mask), head = std::min<size_t>((size_t)have, ring - at);
-    DABX_HIP(hipMemcpy(info, st.items + at, sizeof(dabx_pad_item) * head, hipMemcpyDeviceToHost));
-    if ((size_t)have > head) DABX_HIP(hipMemcpy(info + head, st.items, sizeof(dabx_pad_item) * ((size_t)have - head), hipMemcpyDeviceToHost));
-    int skip = 0;                                             // the newest items that fit
-    if (bytes) while (skip < have && (unsigned long long)(st.item_bytes - info[skip].byte_pos) > max_bytes) skip++;
-    if (skip) { memmove(info, info + skip, sizeof(dabx_pad_item) * (size_t)(have - skip)); have -= skip; }
-  }
-  if (have > 0) {
-    const long long base = info[0].byte_pos, total = st.item_bytes - base;
-    for (int i = 0; i < have; i++) info[i].byte_pos -= base;
-    if (bytes && total > 0) {
-      const size_t ring = (size_t)st.bytes_mask + 1, at = (size_t)((unsigned long long)base & st.bytes_mask);
-      const size_t head = std::min<size_t>((size_t)total, ring - at);
-      DABX_HIP(hipMemcpy(bytes, st.bytes + at, head, hipMemcpyDeviceToHost));
-      if ((size_t)total > head) DABX_HIP(hipMemcpy(bytes + head, st.bytes, (size_t)total - head, hipMemcpyDeviceToHost));
-    }
-  }
-  e->pad[sj].seen = std::max(e->pad[sj].seen, st.item_count);
-  return have;
+  return ring_read(e, e->pad, (size_t)stream * e->dev.max_subch + j, n, info, bytes, max_bytes);
 }
 
 int dabx_get_pad_stats(dabx_engine *e, int stream, int j, dabx_pad_stats *out)
@@ -1324,15 +1250,15 @@ int dabx_get_pad_stats(dabx_engine *e, int stream, int j, dabx_pad_stats *out)
   if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch || !out) { set_error("dabx_get_pad_stats: bad argument"); return DABX_E_ARG; }
   memset(out, 0, sizeof(*out));
   const size_t sj = (size_t)stream * e->dev.max_subch + j;
-  if (e->pad.empty() || !e->pad[sj].on) return sync_all(e);
+  if (!e->pad.on(sj)) return sync_all(e);
   PadSlot st;
   long long lo = 0;
-  if (int rc = pad_window(e, sj, &st, &lo)) return rc;
+  if (int rc = ring_window(e, e->pad, sj, &st, &lo)) return rc;
   const PadCounters &c = st.c;
   auto i32 = [](long long v) { return (int32_t)std::min<long long>(v, INT32_MAX); };
   out->superframes = c.superframes; out->aus = c.aus; out->pad_aus = c.pad_aus; out->fpad_other = c.fpad_other; out->xpad_short = c.xpad_short;
   out->xpad_variable = c.xpad_variable; out->xpad_other = c.xpad_other; out->pad_bad = c.pad_bad; out->labels = c.labels;
-  out->label_bytes = c.label_bytes; out->groups = c.groups; out->group_bytes = c.group_bytes; out->items_lost = e->pad[sj].lost;
+  out->label_bytes = c.label_bytes; out->groups = c.groups; out->group_bytes = c.group_bytes; out->items_lost = e->pad.host[sj].lost;
   out->li_bad = i32(c.li_bad); out->dl_overflow = i32(c.dl_overflow); out->dg_crc_bad = i32(c.dg_crc_bad); out->dg_small = i32(c.dg_small);
   out->active = 1;
   return 0;
@@ -1592,7 +1518,7 @@ int dabx_process(dabx_engine *e, int max_frames, int sync)
       e->dev.snap = e->snap_buf[e->ss.batch_parity];
       hipStream_t tail = e->stream;
       rc = launch_msc_batch(e->dev, 4 * e->pending_frames, e->have_fast ? &e->fast : nullptr, e->ss, e->mk, e->dl.open ? &dv : nullptr, &tail,
-                            e->pkt_dev.n > 0 ? &e->pkt_dev : nullptr, e->pad_dev.n > 0 ? &e->pad_dev : nullptr);
+                            e->pkt.dev.n > 0 ? &e->pkt.dev : nullptr, e->pad.dev.n > 0 ? &e->pad.dev : nullptr);
       if (rc) {
         if (e->dl.open) e->delivery_abort(dl_slot, dl_dev);          // the slabs of the chunk that was begun: never left IN_FLIGHT without a copy job
         e->pending_frames = 0;
@@ -2224,22 +2150,9 @@ int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
   const size_t per_cif = 5632;
   size_t cap = sizeof(dabx_chunk_header) + S * sizeof(dabx_chunk_stream) + S * M * sizeof(dabx_chunk_subch) + S * F * (384 + 12 + sizeof(dabx_chunk_frame)) + 6 * 16 + 256;
   if (M && !d.fic_only) cap += S * ((size_t)4 * F * per_cif + (size_t)DL_SF_CAP * 5 * per_cif + 2 * 16 * M + M * DL_SF_CAP * sizeof(dabx_superframe_info));
-  // ... and the data-group section of the packet-mode slots there are now (one that is switched on later has to fit the slack)
-  if ((rc = e->packet_download())) return rc;
-  for (size_t sj = 0; sj < e->pkt.size(); sj++)
-    if (e->pkt[sj].on) {
-      e->pkt[sj].st.dl_done = e->pkt[sj].st.dg_count;              // delivery starts with what is completed from now on
-      cap += (size_t)4 * F * (e->subch_host[sj].kbps / 8) * sizeof(dabx_datagroup_info) + (size_t)4 * F * 3 * e->subch_host[sj].kbps + DABX_DG_MAX_BYTES + 16;
-    }
-  if (!e->pkt.empty()) cap += S * M * sizeof(dabx_chunk_dg) + 16;
-  // ... and the PAD section of the PAD slots there are now
-  if ((rc = e->pad_download())) return rc;
-  for (size_t sj = 0; sj < e->pad.size(); sj++)
-    if (e->pad[sj].on) {
-      e->pad[sj].st.dl_done = e->pad[sj].st.item_count;
-      cap += (size_t)PAD_DL_ITEM_CAP * sizeof(dabx_pad_item) + PAD_DL_BYTES_CAP + 16;
-    }
-  if (!e->pad.empty()) cap += S * M * sizeof(dabx_chunk_pad) + 16;
+  // ... and the data-group and the PAD section
+  if ((rc = e->pkt.download(d.max_subch)) || (rc = e->pad.download(d.max_subch))) return rc;
+  cap += section_capacity(e->pkt, S * M * sizeof(dabx_chunk_dg)) + section_capacity(e->pad, S * M * sizeof(dabx_chunk_pad));
   D.capacity = align_up(cap, 4096);
 #define H(x) do { hipError_t err__ = (x); if (err__ != hipSuccess) { set_error("HIP error %d (%s) at %s:%d", (int)err__, hipGetErrorString(err__), __FILE__, __LINE__); delivery_free(e); return DABX_E_HIP; } } while (0)
   if (D.copy_engine == 1) H(hipStreamCreateWithFlags(&D.cs, hipStreamNonBlocking));
@@ -2652,8 +2565,8 @@ int dabx_internal_msc_decode(dabx_engine *e, const int32_t *cifs_per_stream, int
   if (!rc) rc = launch_msc_advance(e->dev, counts_dev, e->stream);
   if (!rc) {
     e->dev.snap = e->snap_buf[e->ss.batch_parity];
-    rc = launch_msc_batch(e->dev, batch_cifs, e->have_fast ? &e->fast : nullptr, e->ss, e->mk, nullptr, nullptr, e->pkt_dev.n > 0 ? &e->pkt_dev : nullptr,
-                          e->pad_dev.n > 0 ? &e->pad_dev : nullptr);
+    rc = launch_msc_batch(e->dev, batch_cifs, e->have_fast ? &e->fast : nullptr, e->ss, e->mk, nullptr, nullptr, e->pkt.dev.n > 0 ? &e->pkt.dev : nullptr,
+                          e->pad.dev.n > 0 ? &e->pad.dev : nullptr);
   }
   const int rc2 = sync_all(e);
   (void)hipFree(counts_dev);

@@ -3,6 +3,7 @@
 // assembly of the MSC data groups.  include/dabx.h "Packet-mode data sub-channels" states the semantics and the two guards.
 #pragma once
 #include "pipeline.h"
+#include "out_ring.h"
 #ifdef __HIPCC__
 #include "fec_core.h"
 #endif
@@ -10,17 +11,14 @@
 namespace dabx {
 
 // One packet-mode slot: DataProcessor's members (data_processor.h: mPacketAddress, mExpectedIndex, mPacketState, mSeriesVec), the slot's
-// two rings and its counters.  The job table of k_packet is an array of these, packet-mode slots only, in HBM; the kernel's own arrays,
-// none of them part of EngineDev / SubchDev.
+// output rings (out_ring.h: one record per completed group) and its counters.  The job table of k_packet is an array of these, packet-mode
+// slots only, in HBM; the kernel's own arrays, none of them part of EngineDev / SubchDev.
 //
-// The series under assembly is kept IN the byte ring, at the place the completed group will have: bytes [dg_bytes, dg_bytes + fill) of the
-// slot's data-group byte sequence (ring index = position & bytes_mask).  Completing the group moves dg_bytes on, abandoning the series
-// leaves it: no second buffer, no copy.  A reader therefore trusts a group only while dg_bytes + DABX_DG_MAX_BYTES - byte_pos still fits the
-// ring (engine.cpp, packet_window).
+// The series under assembly is kept IN the byte ring, at the place the completed group will have: bytes [out.n_bytes, out.n_bytes + fill) of
+// the slot's data-group byte sequence.  Completing the group moves n_bytes on, abandoning the series leaves it: no second buffer, no copy.
+// The ring's asm_room is DABX_DG_MAX_BYTES, the bound of a series.
 struct PacketSlot {
-  uint8_t *bytes;                 // [bytes_mask + 1] data-group bytes
-  dabx_datagroup_info *recs;      // [rec_mask + 1] record of group i at i & rec_mask
-  uint32_t bytes_mask, rec_mask;  // ring sizes - 1 (powers of two)
+  OutRing<dabx_datagroup_info> out;
   int32_t s, j;                   // stream, slot
   int32_t address;                // mPacketAddress
   int32_t expected;               // mExpectedIndex
@@ -29,11 +27,7 @@ struct PacketSlot {
   int32_t first_byte;             // byte 0 of the series, -1 while it is empty (the data-group CRC flag is its bit 6)
   uint32_t run_crc;               // CCITT register (start value 0xFFFF) over the series so far
   long long first_frame;          // logical frame of the packet that started the series
-  long long frames, packets, addr_match, continuity_err, crc_bad, len_bad, walk_short, dg_count, dg_bytes, dg_crc_bad, dg_overflow;
-  // bulk delivery (deliver.hip, k_deliver_dg): groups delivered so far, and the slot's room in a slab (0 = the slab has no data-group section)
-  long long dl_done;
-  unsigned long long dl_rec_off, dl_bytes_off;
-  uint32_t dl_rec_cap, dl_bytes_cap;
+  long long frames, packets, addr_match, continuity_err, crc_bad, len_bad, walk_short, dg_crc_bad, dg_overflow;      // (dg_count, dg_bytes: out.count, out.n_bytes)
 };
 
 // k_packet's argument, by value: the job table and what the kernel reads of the engine (the MSC batch's snapshot, the slots' descriptions

@@ -5,6 +5,7 @@
 // parser).  include/dabx.h "Programme-associated data" states the semantics and the four guards G1..G4.
 #pragma once
 #include "pipeline.h"
+#include "out_ring.h"
 #ifdef __HIPCC__
 #include "fec_core.h"
 #include "wave_ops.h"
@@ -36,7 +37,7 @@ struct PadCounters {              // dabx_pad_stats
             groups, group_bytes, dg_crc_bad, dg_small;
 };
 
-// The largest span of the byte ring the device may write beyond item_bytes before it moves item_bytes on: the group under assembly -- fewer
+// The largest span of the byte ring the device may write beyond n_bytes before it moves n_bytes on (the ring's asm_room): the group under assembly -- fewer
 // than mDataGroupLength <= 16 383 bytes before an append, at most 196 more after it (a no-CI continuation is mXPadLength bytes long, :224)
 // -- moved up once by a label of at most DABX_DL_MAX_BYTES that is emitted while the group is open.  16 382 + 196 + 256 < 16 896.
 constexpr int PAD_ASM_ROOM = 16896;
@@ -53,25 +54,17 @@ constexpr uint32_t PAD_DL_ITEM_CAP = 144;
 constexpr uint32_t PAD_DL_BYTES_CAP = 144 * DABX_DL_MAX_BYTES + PAD_ASM_ROOM;
 
 // One PAD-enabled DAB+ slot.  The job table of k_pad is an array of these, PAD slots only, in HBM; none of it is part of EngineDev /
-// SubchDev.  Labels and groups share the two rings in emission order: item i at i & item_mask, its bytes at byte_pos & bytes_mask.
-// The group under assembly is kept IN the byte ring where the completed group will be: bytes [item_bytes, item_bytes + fill) (as
-// packet_core.h keeps its series).  A label emitted while a group is open moves those bytes up by the label's length first.  A reader
-// trusts an item only while item_bytes + PAD_ASM_ROOM - byte_pos still fits the ring (engine.cpp, pad_window).
+// SubchDev.  Labels and groups share the slot's output rings (out_ring.h) in emission order.  The group under assembly is kept IN the byte
+// ring where the completed group will be: bytes [out.n_bytes, out.n_bytes + fill) (as packet_core.h keeps its series).  A label emitted
+// while a group is open moves those bytes up by the label's length first.  The ring's asm_room is PAD_ASM_ROOM.
 struct PadSlot {
-  uint8_t *bytes;                 // [bytes_mask + 1]
-  dabx_pad_item *items;           // [item_mask + 1]
-  uint32_t bytes_mask, item_mask;
+  OutRing<dabx_pad_item> out;
   int32_t s, j;                   // stream, slot
   long long sf_seen;              // super frames of the slot (SubchDev::sf_count) walked so far
   PadState h;
   uint8_t short_data[16];         // mShortPadData: one byte from :151 and at most mStillToGo <= 15 more
   uint8_t dl_text[DABX_DL_MAX_BYTES];
   PadCounters c;
-  long long item_count, item_bytes;
-  // bulk delivery (deliver.hip, k_deliver_pad): items delivered so far, and the slot's room in a slab (0 = the slab has no PAD section)
-  long long dl_done;
-  unsigned long long dl_item_off, dl_bytes_off;
-  uint32_t dl_item_cap, dl_bytes_cap;
 };
 
 // k_pad's argument, by value: the job table and what the kernel reads of the engine (launch_msc_batch fills those in).
@@ -118,7 +111,7 @@ __device__ __forceinline__ unsigned pad_xpow(const uint16_t *s_xpow, int m)
   return r;
 }
 
-// check_crc_bytes(iData, size - 2) (crc.cpp:89-96) over the `size` >= 2 bytes at item_bytes of the byte ring.  Not one lane walking up to
+// check_crc_bytes(iData, size - 2) (crc.cpp:89-96) over the `size` >= 2 bytes at n_bytes of the byte ring.  Not one lane walking up to
 // 16 KB: every lane runs the register from 0 over its own slice, the slice registers are moved to the end of the message with x^(8 n) and
 // folded (the register is linear in the message); the 0xFFFF start value is one more term.  All lanes active.
 __device__ __forceinline__ bool pad_ring_check_crc(const PadWave &w, int size)
@@ -176,7 +169,7 @@ __device__ __forceinline__ void pad_emit_label(PadWave &w)
   w.c.labels++; w.c.label_bytes += len;
 }
 
-// _build_MSC_segment (:522-547) on the n bytes at item_bytes of the ring, up to the hand-over: the MOT parsing from :553 on is the host's
+// _build_MSC_segment (:522-547) on the n bytes at n_bytes of the ring, up to the hand-over: the MOT parsing from :553 on is the host's
 __device__ __forceinline__ void pad_build_msc(PadWave &w, int n)
 {
   const int size = min(n, w.h.dg_length);                        // :528

@@ -1959,12 +1959,12 @@ __global__ __launch_bounds__(64) void k_packet(PacketDev pk)
   for (int i = lane; i < 256; i += 64) s_crc[i] = pk.crc_ccitt[i];
   for (int i = lane; i < 128; i += 64) s_xpow[i] = pk.crc_xpow[i];
   const int address = ps.address;
-  uint8_t *const dg_ring = ps.bytes;                         // (locals: the stores below must not make the loop reload them from the table)
-  dabx_datagroup_info *const dg_recs = ps.recs;
-  const unsigned long long bytes_mask = ps.bytes_mask, rec_mask = ps.rec_mask;
+  uint8_t *const dg_ring = ps.out.bytes;                         // (locals: the stores below must not make the loop reload them from the table)
+  dabx_datagroup_info *const dg_recs = ps.out.recs;
+  const unsigned long long bytes_mask = ps.out.bytes_mask, rec_mask = ps.out.rec_mask;
   int expected = ps.expected, state = ps.state, fill = ps.fill, first_byte = ps.first_byte;
   unsigned run_crc = ps.run_crc;
-  long long first_frame = ps.first_frame, dg_count = ps.dg_count, dg_bytes = ps.dg_bytes;
+  long long first_frame = ps.first_frame, dg_count = ps.out.count, dg_bytes = ps.out.n_bytes;
   long long packets = 0, addr_match = 0, continuity_err = 0, crc_bad = 0, len_bad = 0, walk_short = 0, dg_crc_bad = 0, dg_overflow = 0;
   const long long frame0 = sc.cif_out;
   for (long long n = 0; n < n_new; n++) {
@@ -2029,7 +2029,7 @@ __global__ __launch_bounds__(64) void k_packet(PacketDev pk)
   }
   if (lane == 0) {
     ps.expected = expected; ps.state = state; ps.fill = fill; ps.first_byte = first_byte; ps.run_crc = run_crc;
-    ps.first_frame = first_frame; ps.dg_count = dg_count; ps.dg_bytes = dg_bytes;
+    ps.first_frame = first_frame; ps.out.count = dg_count; ps.out.n_bytes = dg_bytes;
     ps.frames += n_new; ps.packets += packets; ps.addr_match += addr_match; ps.continuity_err += continuity_err; ps.crc_bad += crc_bad;
     ps.len_bad += len_bad; ps.walk_short += walk_short; ps.dg_crc_bad += dg_crc_bad; ps.dg_overflow += dg_overflow;
   }
@@ -2065,8 +2065,8 @@ __global__ __launch_bounds__(64) void k_pad(PadDev pd)
   if (lane < 16) s_short[lane] = ps.short_data[lane];
   PadWave w;
   w.h = ps.h; w.c = ps.c;
-  w.ring = ps.bytes; w.items = ps.items; w.bytes_mask = ps.bytes_mask; w.item_mask = ps.item_mask;
-  w.n_items = ps.item_count; w.n_bytes = ps.item_bytes;
+  w.ring = ps.out.bytes; w.items = ps.out.recs; w.bytes_mask = ps.out.bytes_mask; w.item_mask = ps.out.rec_mask;
+  w.n_items = ps.out.count; w.n_bytes = ps.out.n_bytes;
   w.lane = lane; w.text = s_text; w.shortd = s_short; w.s_crc = s_crc; w.s_xpow = s_xpow;
   __syncthreads();
   for (long long sf = seen; sf < have; sf++) {
@@ -2096,7 +2096,7 @@ __global__ __launch_bounds__(64) void k_pad(PadDev pd)
   __syncthreads();
   for (int i = lane; i < DABX_DL_MAX_BYTES; i += 64) ps.dl_text[i] = s_text[i];
   if (lane < 16) ps.short_data[lane] = s_short[lane];
-  if (lane == 0) { ps.h = w.h; ps.c = w.c; ps.item_count = w.n_items; ps.item_bytes = w.n_bytes; ps.sf_seen = have; }
+  if (lane == 0) { ps.h = w.h; ps.c = w.c; ps.out.count = w.n_items; ps.out.n_bytes = w.n_bytes; ps.sf_seen = have; }
 }
 
 // ---------------------------------------------------------------------------------------------- launchers

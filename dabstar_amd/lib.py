@@ -469,23 +469,23 @@ class Chunk:
         o = int(r["sfi_off"])
         return self.raw[o:o + int(r["n_sf"]) * 32].view(SUPERFRAME_INFO)
 
+    def _ring_items(self, table, rec_off, count, dtype, s, j):
+        """(records, bytes) of slot (s, j) in a section of the slab whose table record names them rec_off / count / bytes_off / n_bytes."""
+        if table is None or not int(table[s, j][rec_off]):
+            return np.zeros(0, dtype), np.zeros(0, np.uint8)
+        r = table[s, j]
+        ro, bo = int(r[rec_off]), int(r["bytes_off"])
+        return self.raw[ro:ro + int(r[count]) * 32].view(dtype), self.raw[bo:bo + int(r["n_bytes"])]
+
     def datagroups(self, s, j):
         """MSC data groups of packet-mode slot (s, j) in this chunk: ([n_dg] DATAGROUP_INFO, their n_bytes bytes), views; group i is
         bytes[byte_pos[i] : byte_pos[i] + length[i]].  Empty when the slab has no data-group section or the slot is not in packet mode."""
-        if self.dg is None or not int(self.dg[s, j]["rec_off"]):
-            return np.zeros(0, DATAGROUP_INFO), np.zeros(0, np.uint8)
-        r = self.dg[s, j]
-        ro, bo = int(r["rec_off"]), int(r["bytes_off"])
-        return self.raw[ro:ro + int(r["n_dg"]) * 32].view(DATAGROUP_INFO), self.raw[bo:bo + int(r["n_bytes"])]
+        return self._ring_items(self.dg, "rec_off", "n_dg", DATAGROUP_INFO, s, j)
 
     def pad_items(self, s, j):
         """PAD items of slot (s, j) in this chunk: ([n_items] PAD_ITEM, their n_bytes bytes), views; item i is
         bytes[byte_pos[i] : byte_pos[i] + length[i]].  Empty when the slab has no PAD section or the slot has no PAD decoding."""
-        if self.pad is None or not int(self.pad[s, j]["item_off"]):
-            return np.zeros(0, PAD_ITEM), np.zeros(0, np.uint8)
-        r = self.pad[s, j]
-        ro, bo = int(r["item_off"]), int(r["bytes_off"])
-        return self.raw[ro:ro + int(r["n_items"]) * 32].view(PAD_ITEM), self.raw[bo:bo + int(r["n_bytes"])]
+        return self._ring_items(self.pad, "item_off", "n_items", PAD_ITEM, s, j)
 
     def release(self):
         if self._eng is not None:
@@ -698,17 +698,22 @@ class Engine:
             cfg = PacketConfig(size=C.sizeof(PacketConfig), packet_address=int(packet_address))
             check(L.dabx_set_packet_mode(self._h, int(stream), int(j), C.byref(cfg)))
 
-    def read_datagroups(self, stream, j, n=64, max_bytes=None):
-        """(records [k] DATAGROUP_INFO, bytes uint8) of the newest k <= n completed data groups of slot j, oldest first; group i is
-        bytes[byte_pos[i] : byte_pos[i] + length[i]]."""
-        L = load()
-        info = np.zeros(max(1, n), DATAGROUP_INFO)
+    def _read_ring(self, call, dtype, ring_bytes, stream, j, n, max_bytes, with_bytes):
+        """dabx_read_datagroups / dabx_read_pad_items: (records [k], bytes); with_bytes = False passes bytes = NULL (records only, no bytes)."""
+        info = np.zeros(max(1, n), dtype)
+        if not with_bytes:
+            return info[:check(call(self._h, int(stream), int(j), int(n), _p(info), None, 0))], np.zeros(0, np.uint8)
         if max_bytes is None:
-            max_bytes = DG_RING_MAX_BYTES                 # no slot's byte ring holds more
+            max_bytes = ring_bytes                        # no slot's byte ring holds more
         buf = np.zeros(max(1, int(max_bytes)), np.uint8)
-        k = check(L.dabx_read_datagroups(self._h, int(stream), int(j), int(n), _p(info), _p(buf), int(max_bytes)))
+        k = check(call(self._h, int(stream), int(j), int(n), _p(info), _p(buf), int(max_bytes)))
         info = info[:k]
         return info, buf[:int(info["length"].sum())].copy()
+
+    def read_datagroups(self, stream, j, n=64, max_bytes=None, with_bytes=True):
+        """(records [k] DATAGROUP_INFO, bytes uint8) of the newest k <= n completed data groups of slot j, oldest first; group i is
+        bytes[byte_pos[i] : byte_pos[i] + length[i]].  with_bytes = False: the records alone."""
+        return self._read_ring(load().dabx_read_datagroups, DATAGROUP_INFO, DG_RING_MAX_BYTES, stream, j, n, max_bytes, with_bytes)
 
     def packet_stats(self, stream, j):
         """dabx_packet_stats of slot j as a dict."""
@@ -726,17 +731,10 @@ class Engine:
             cfg = PadConfig(size=C.sizeof(PadConfig))
             check(L.dabx_set_pad_mode(self._h, int(stream), int(j), C.byref(cfg)))
 
-    def read_pad_items(self, stream, j, n=512, max_bytes=None):
+    def read_pad_items(self, stream, j, n=512, max_bytes=None, with_bytes=True):
         """(records [k] PAD_ITEM, bytes uint8) of the newest k <= n PAD items of slot j, oldest first, dynamic labels and X-PAD MSC data
-        groups in emission order; item i is bytes[byte_pos[i] : byte_pos[i] + length[i]]."""
-        L = load()
-        info = np.zeros(max(1, n), PAD_ITEM)
-        if max_bytes is None:
-            max_bytes = PAD_RING_BYTES
-        buf = np.zeros(max(1, int(max_bytes)), np.uint8)
-        k = check(L.dabx_read_pad_items(self._h, int(stream), int(j), int(n), _p(info), _p(buf), int(max_bytes)))
-        info = info[:k]
-        return info, buf[:int(info["length"].sum())].copy()
+        groups in emission order; item i is bytes[byte_pos[i] : byte_pos[i] + length[i]].  with_bytes = False: the records alone."""
+        return self._read_ring(load().dabx_read_pad_items, PAD_ITEM, PAD_RING_BYTES, stream, j, n, max_bytes, with_bytes)
 
     def pad_stats(self, stream, j):
         """dabx_pad_stats of slot j as a dict."""

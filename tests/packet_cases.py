@@ -378,6 +378,44 @@ def scenario(kbps, seed, n_frames=N_FRAMES):
     return _cache[key]
 
 
+# ---- a reader that comes late: scenarios that overrun a slot's rings before the first read --------------------------------------------------
+# name: (kbps, data-group lengths [lo, hi], CRC flag).  Address A only, everything valid: the model's rows are simply all the groups.
+LATE_READER = {
+    "A": (8, (1, 19), False),                # one single-packet group per 24-byte frame: 112 groups against a record ring of 64
+    "B": (64, (200, 400), True),             # ~17 KB in a byte ring of 32 768, of which DABX_DG_MAX_BYTES are the series' room
+    "C": (256, (300, 900), False),           # ~76 KB through a byte ring of 65 536: the surviving window crosses the ring's end
+}
+
+
+def late_reader_scenario(name, n_frames=N_FRAMES):
+    """(kbps, logical frames [n_frames, 3 kbps]) of LATE_READER[name]: dense groups until the frames are full (the last may stay open)."""
+    key = ("late", name, n_frames)
+    if key not in _cache:
+        kbps, (lo, hi), flag = LATE_READER[name]
+        w = Writer(kbps, np.random.default_rng([kbps, 4711]))
+        while len(w.frames) < n_frames:
+            w.emit(w.group(int(w.rng.integers(lo, hi + 1)), flag, dense=True))
+        _cache[key] = np.frombuffer(b"".join(w.frames[:n_frames]), np.uint8).reshape(n_frames, 3 * kbps).copy()
+    return LATE_READER[name][0], _cache[key]
+
+
+def ring_sizes(kbps):
+    """(records, bytes) of a packet-mode slot's rings (dabx_set_packet_mode): powers of two that hold two batches and the series' room."""
+    pow2 = lambda v: 1 << (v - 1).bit_length()      # noqa: E731
+    return pow2(2 * BATCH * (kbps // 8)), pow2(2 * BATCH * 3 * kbps + DG_MAX_BYTES)
+
+
+def intact_window(byte_pos, n_bytes, ring_records, ring_bytes, asm_room=DG_MAX_BYTES):
+    """The rule of a slot's output rings (dabstar_amd/csrc/out_ring.h), restated: of items with byte positions byte_pos and n_bytes bytes in
+    all, (first by the record ring alone, first still intact).  An item is trusted while the record ring still holds its record and
+    n_bytes + asm_room - byte_pos fits the byte ring -- the device may have written that far beyond n_bytes."""
+    by_records = max(0, len(byte_pos) - ring_records)
+    first = by_records
+    while first < len(byte_pos) and n_bytes + asm_room - int(byte_pos[first]) > ring_bytes:
+        first += 1
+    return by_records, first
+
+
 # ---- the sets the tests use --------------------------------------------------------------------------------------------------------------
 PROT = 3                                     # EEP 4-A, as tests/dabplus_cases.py
 # (kbps, kind) per slot: "pkt" a packet-mode slot, "dab+" a DAB+ slot, "plain" a slot left in plain logical frames that carries a packet

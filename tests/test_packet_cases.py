@@ -141,6 +141,30 @@ def test_groups_span_the_batch_boundaries_of_the_boundary_schedule_and_idle_batc
     assert spans > 20 and idle_spans > 0, (spans, idle_spans)
 
 
+def test_the_late_reader_scenarios_overrun_the_rings_the_way_each_is_meant_to():
+    """The model and the documented window rule alone on the three scenarios of test_gpu_ring_reads.py: A loses groups to the record ring, B
+    to the byte ring alone, C to the byte ring with the surviving bytes across the ring's end.  A change of seed cannot hollow that test out."""
+    seen = {}
+    for name in pc.LATE_READER:
+        kbps, frames = pc.late_reader_scenario(name)
+        m = pc.run_model(frames, pc.ADDRESS_A)
+        r, n_bytes = m.records(), m.counters["dg_bytes"]
+        c = m.counters
+        assert c["frames"] == pc.N_FRAMES and c["packets"] == c["addr_match"] and len(r) == c["dg_count"], (name, c)         # everything is valid
+        assert not any(c[k] for k in ("continuity_err", "crc_bad", "len_bad", "walk_short", "dg_crc_bad", "dg_overflow")), (name, c)
+        n_rec, n_ring = pc.ring_sizes(kbps)
+        by_records, first = pc.intact_window(r["byte_pos"], n_bytes, n_rec, n_ring)
+        base = int(r["byte_pos"][first])
+        seen[name] = (len(r), n_bytes, n_rec, n_ring, by_records, first, base % n_ring + (n_bytes - base) > n_ring)
+    print(seen)
+    n, _, n_rec, _, by_records, first, _ = seen["A"]
+    assert (n, n_rec, by_records, first) == (112, 64, 48, 48) and first % n_rec + (n - first) > n_rec      # the records come in two runs
+    n, _, n_rec, _, by_records, first, _ = seen["B"]
+    assert n < n_rec and by_records == 0 and 0 < first < n
+    n, n_bytes, n_rec, n_ring, by_records, first, crosses = seen["C"]
+    assert n < n_rec and by_records == 0 and 0 < first < n and n_bytes > n_ring and crosses
+
+
 def test_packet_crc_of_the_model_is_the_references_check_crc_bits():
     if not ol.have_ref():
         pytest.skip("oracle/_ref is not built")
