@@ -3,6 +3,7 @@
 #include "packet_core.h"
 #include "pad_core.h"
 #include "viterbi_core.h"
+#include "fig00.h"
 #include "sdma.h"
 #include "iqfile.h"
 #include <algorithm>
@@ -33,6 +34,8 @@ int launch_level_exact(const EngineDev &e, hipStream_t st);
 int launch_stage_msc_block(const EngineDev &e, const int16_t *soft_dev, int blk, bool closes_cif, hipStream_t st);
 int launch_msc_inject(const EngineDev &e, int stream, const int16_t *soft_dev, int n_cifs, int first, hipStream_t st);
 int launch_msc_advance(const EngineDev &e, const int32_t *counts_dev, hipStream_t st);
+int launch_fic_inject(const EngineDev &e, int stream, const int16_t *soft_dev, hipStream_t st);
+int launch_fic_decode(const EngineDev &e, const int32_t *present_dev, hipStream_t st);
 extern const char *const kStepKernelNames[N_STEP_KERNELS];
 int launch_commit(const EngineDev &e, int stream, unsigned long long n, hipStream_t st);
 int launch_fic_only(const EngineDev &e, hipStream_t st, int first, int count);
@@ -1677,7 +1680,7 @@ int dabx_read_eti(dabx_engine *e, int stream, int max_frames, uint8_t *out, int3
       const size_t slot = (size_t)stream * d.out_frames + (size_t)(G % d.out_frames);
       DABX_HIP(hipMemcpy(fb.data(), d.fib_out + slot * 384, 384, hipMemcpyDeviceToHost));
       DABX_HIP(hipMemcpy(fc.data(), d.fib_crc + slot * 12, 12, hipMemcpyDeviceToHost));
-      for (int i = 0; i < 12; i++) if (fc[i]) fib_cif_count(fb.data() + 32 * i, &cur.hi, &cur.lo);
+      for (int i = 0; i < 12; i++) if (fc[i]) fib_fig00_counter(fb.data() + 32 * i, &cur.hi, &cur.lo);   // k_fic_frame's own walk: == dabx_stats.cif_count
       if (G == F) { fibs = fb; fib_frame = F; }
       cur.fib_frames_seen++;
     }
@@ -2570,6 +2573,56 @@ int dabx_internal_msc_decode(dabx_engine *e, const int32_t *cifs_per_stream, int
   }
   const int rc2 = sync_all(e);
   (void)hipFree(counts_dev);
+  return rc ? rc : rc2;
+}
+
+// ---- test entries of the FIC stage (tests/test_gpu_fic_stage.py; not part of include/dabx.h) ----------------------------------------
+// soft: [9216] int16, the FIC soft bits of the next frame of `stream` (OFDM symbols 1..3), converted with the engine's viterbi_tie_mode
+// as the demapper's output is.  Nothing is decoded or counted before dabx_internal_fic_decode.
+int dabx_internal_fic_inject(dabx_engine *e, int stream, const int16_t *soft)
+{
+  if (!e || !soft || stream < 0 || stream >= e->dev.n_streams || !e->dev.fic_sym) {
+    set_error("dabx_internal_fic_inject: bad argument (stream %d)", stream);
+    return DABX_E_ARG;
+  }
+  if (int rc = use_device(e)) return rc;
+  if (int rc = sync_all(e)) return rc;
+  int16_t *soft_dev = nullptr;
+  const size_t bytes = (size_t)3 * K2 * sizeof(int16_t);
+  DABX_HIP(hipMalloc(&soft_dev, bytes));
+  int rc = 0;
+  if (hipMemcpy(soft_dev, soft, bytes, hipMemcpyHostToDevice) != hipSuccess) { set_error("dabx_internal_fic_inject: copy failed"); rc = DABX_E_HIP; }
+  if (!rc) rc = launch_fic_inject(e->dev, stream, soft_dev, e->stream);
+  if (hipStreamSynchronize(e->stream) != hipSuccess && !rc) { set_error("dabx_internal_fic_inject: HIP error"); rc = DABX_E_HIP; }
+  (void)hipFree(soft_dev);
+  return rc;
+}
+
+// present: [n_streams], 1 = the stream has a frame (frame_ok), 0 = it has none: k_fic_frame must leave everything of that stream as it
+// is.  One launch of k_fic_frame over all streams (first = 0, count = 4, no sequence-number wait), then the present streams count the
+// frame (the slot ring of out_frames turns), and a full synchronisation.  Results: dabx_read_fibs, dabx_get_stats.
+int dabx_internal_fic_decode(dabx_engine *e, const int32_t *present)
+{
+  if (!e || !present || !e->dev.fic_sym) { set_error("dabx_internal_fic_decode: bad argument"); return DABX_E_ARG; }
+  for (int s = 0; s < e->dev.n_streams; s++)
+    if (present[s] != 0 && present[s] != 1) {
+      set_error("dabx_internal_fic_decode: present[%d] = %d (0 or 1)", s, (int)present[s]);
+      return DABX_E_ARG;
+    }
+  if (e->dl.open || e->pending_frames != 0) {
+    set_error("dabx_internal_fic_decode: the engine has a delivery open or front-end frames pending");
+    return DABX_E_STATE;
+  }
+  if (int rc = use_device(e)) return rc;
+  if (int rc = sync_all(e)) return rc;
+  int32_t *present_dev = nullptr;
+  const size_t bytes = sizeof(int32_t) * (size_t)e->dev.n_streams;
+  DABX_HIP(hipMalloc(&present_dev, bytes));
+  int rc = 0;
+  if (hipMemcpy(present_dev, present, bytes, hipMemcpyHostToDevice) != hipSuccess) { set_error("dabx_internal_fic_decode: copy failed"); rc = DABX_E_HIP; }
+  if (!rc) rc = launch_fic_decode(e->dev, present_dev, e->stream);
+  const int rc2 = sync_all(e);
+  (void)hipFree(present_dev);
   return rc ? rc : rc2;
 }
 

@@ -6,6 +6,7 @@
 // fib_table.h:44-117 (short-form table) and fib_decoder.cpp:547-557, 673-691 (getters).  Tiny, branchy, per-FIB:
 // stays on the host ("OUT OF SCOPE for GPU").
 #include "dabx_internal.h"
+#include "fig00.h"
 #include <cstring>
 #include <vector>
 
@@ -190,22 +191,15 @@ static int table_out(const FibConfig &cfg, dabx_subch_desc *out, int max_out)
   return n;
 }
 
-// FIG 0/0 of one FIB -> CIF counter halves (mCifCount_hi / _lo, fib_decoder_fig0.cpp:89-101); false if the FIB has none
-bool fib_cif_count(const uint8_t *fib, int *hi, int *lo)
-{
-  bool found = false;
-  int p = 0;
-  while (p < 30) {
-    const int type = fib[p] >> 5, len = fib[p] & 0x1F;
-    if (type == 7 && len == 0x1F) break;
-    if (p + 1 + len > 30) break;
-    if (type == 0 && len >= 5 && (fib[p + 1] & 0x1F) == 0) { *hi = fib[p + 4] & 0x1F; *lo = fib[p + 5]; found = true; }
-    p += len + 1;
-  }
-  return found;
-}
-
 }  // namespace dabx
+
+// Host only, not part of include/dabx.h (tests/test_fic_cases.py): the counter the library reads out of one FIB of 32 bytes whose CRC is
+// taken as good.  Returns 1 with *hi / *lo set, 0 if the FIB carries no FIG 0/0 (*hi / *lo untouched).
+extern "C" int dabx_internal_fib_cif_count(const uint8_t *fib32, int *hi, int *lo)
+{
+  if (!fib32 || !hi || !lo) return DABX_E_ARG;
+  return dabx::fib_fig00_counter(fib32, hi, lo) ? 1 : 0;
+}
 
 using namespace dabx;
 

@@ -24,6 +24,7 @@
 #include "fec_core.h"
 #include "acq_walk.h"
 #include "level_par.h"
+#include "fig00.h"
 
 namespace dabx {
 
@@ -1362,16 +1363,8 @@ __global__ __launch_bounds__(256) void k_fic_frame(EngineDev e, DevTables t, int
     crc_ok[fibi] = good;
     e.fib_crc[((size_t)s * e.out_frames + slot) * 12 + fibi] = good;
     int cif = -1;
-    if (good) {
-      int p = 0;                            // fib_decoder.cpp:59-110
-      while (p < 30) {
-        const int type = b[p] >> 5, len = b[p] & 0x1F;
-        if (type == 7 && len == 0x1F) break;
-        if (type == 0 && p + 5 < 32 && (b[p + 1] & 0x1F) == 0)                       // FIG 0/0, fib_decoder_fig0.cpp:89-101
-          cif = (b[p + 4] & 0x1F) * 250 + b[p + 5];
-        p += len + 1;
-      }
-    }
+    int hi, lo;
+    if (good && fib_fig00_counter(b, &hi, &lo)) cif = hi * 250 + lo;      // fig00.h: the walk the ETI frames' counter comes from too
     fib_cif[fibi] = cif;
   }
   for (int i = threadIdx.x; i < 24 * count; i += 256) reinterpret_cast<uint32_t *>(fo)[24 * first + i] = fibw[first + i / 24][i % 24];
@@ -2430,6 +2423,45 @@ int launch_msc_inject(const EngineDev &e, int stream, const int16_t *soft_dev, i
 int launch_msc_advance(const EngineDev &e, const int32_t *counts_dev, hipStream_t st)
 {
   hipLaunchKernelGGL(k_msc_advance, dim3((e.n_streams + 255) / 256), dim3(256), 0, st, e, counts_dev);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+
+// Test entries dabx_internal_fic_inject / dabx_internal_fic_decode (engine.cpp; not part of include/dabx.h): a frame's 9216 FIC soft bits go
+// into one stream's fic_sym as the demapper's first launch puts them there, k_fic_frame decodes all streams as the many-stream schedule
+// launches it (first = 0, count = 4, no sequence-number wait), and the streams that had a frame count it, as k_frame_tail does.
+__global__ void k_fic_inject(EngineDev e, int s, const int16_t *soft)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < 3 * K2) e.fic_sym[(size_t)s * 3 * K2 + i] = soft_to_sym_mode(soft[i], e.tie_mode);
+}
+__global__ void k_fic_present(EngineDev e, const int32_t *present)
+{
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s < e.n_streams) e.ctl[s].frame_ok = present[s] ? 1 : 0;
+}
+__global__ void k_fic_advance(EngineDev e, const int32_t *present)
+{
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s < e.n_streams && present[s]) e.ctl[s].frames += 1;
+}
+int launch_fic_inject(const EngineDev &e, int stream, const int16_t *soft_dev, hipStream_t st)
+{
+  hipLaunchKernelGGL(k_fic_inject, dim3(3 * K2 / 256), dim3(256), 0, st, e, stream, soft_dev);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+int launch_fic_decode(const EngineDev &e_in, const int32_t *present_dev, hipStream_t st)
+{
+  const DevTables *t;
+  int rc = get_tables(&t);
+  if (rc) return rc;
+  EngineDev e = e_in;
+  e.flag_sync = 0;                                          // the hand-over by sequence number belongs to a front end this call does not run
+  const dim3 grid((e.n_streams + 255) / 256);
+  hipLaunchKernelGGL(k_fic_present, grid, dim3(256), 0, st, e, present_dev);
+  hipLaunchKernelGGL(k_fic_frame, dim3(e.n_streams), dim3(256), 0, st, e, *t, 0, 4);
+  hipLaunchKernelGGL(k_fic_advance, grid, dim3(256), 0, st, e, present_dev);
   DABX_HIP(hipGetLastError());
   return 0;
 }

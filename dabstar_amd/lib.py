@@ -130,6 +130,34 @@ def msc_decode(engine, cifs_per_stream, batch_cifs):
     check(load().dabx_internal_msc_decode(engine._h, _p(counts), int(batch_cifs)))
 
 
+def fic_inject(engine, stream, soft):
+    """Internal test entry (not part of include/dabx.h): soft [9216] int16 becomes the FIC symbols of the next frame of `stream`,
+    converted as the demapper's output is (viterbi_tie_mode).  Nothing is decoded before fic_decode_frame."""
+    soft = np.ascontiguousarray(soft, np.int16).reshape(-1)
+    if soft.size != 9216:
+        raise ValueError("fic_inject needs the 9216 soft bits of one frame's FIC")
+    check(load().dabx_internal_fic_inject(engine._h, int(stream), _p(soft)))
+
+
+def fic_decode_frame(engine, present):
+    """Internal test entry: k_fic_frame over all streams as the many-stream schedule launches it; present[s] = 0 means stream s has
+    no frame (nothing of it may change), the others count the frame.  Results: Engine.read_fibs / Engine.stats."""
+    present = np.ascontiguousarray(present, np.int32).reshape(-1)
+    if present.size != engine.n_streams:
+        raise ValueError("fic_decode_frame needs one flag per stream")
+    check(load().dabx_internal_fic_decode(engine._h, _p(present)))
+
+
+def fib_cif_count(fib32):
+    """Internal, host only: (CIFCountHi, CIFCountLo) the library's FIG 0/0 walk reads out of one FIB of 32 bytes (CRC taken as good),
+    or None -- the walk of k_fic_frame and of the ETI writer (csrc/fig00.h)."""
+    fib32 = np.ascontiguousarray(fib32, np.uint8).reshape(-1)
+    if fib32.size != 32:
+        raise ValueError("a FIB has 32 bytes")
+    hi, lo = C.c_int(-1), C.c_int(-1)
+    return (hi.value, lo.value) if check(load().dabx_internal_fib_cif_count(_p(fib32), C.byref(hi), C.byref(lo))) else None
+
+
 def profile_input_bits(kbps, prot_level, short_form=0):
     return check(load().dabx_profile_input_bits(kbps, prot_level, short_form))
 

@@ -99,7 +99,8 @@ int  dabx_fic_get_decode_ratio_percent(dabx_fic *f);        /* get_fic_decode_ra
 int  dabx_fic_reset_decode_success_ratio(dabx_fic *f);      /* fic_decoder.h:53 */
 int  dabx_fic_stop(dabx_fic *f);                            /* stop(): process_block becomes a no-op, .cpp:182-185, 264-268 */
 int  dabx_fic_restart(dabx_fic *f);                         /* restart(): ratio = 0, running, .cpp:270-275 */
-/* FibDecoder::get_cif_count as the FIG 0/0 walk of the decoded FIBs left it (fib_decoder_fig0.cpp:89-101): hi * 250 + lo */
+/* FibDecoder::get_cif_count as the FIG 0/0 walk of the decoded FIBs left it (fib_decoder_fig0.cpp:89-101): hi * 250 + lo; 0 before the
+ * first FIG 0/0.  The rule and its limits: dabx_stats.cif_count. */
 int  dabx_fic_get_cif_count(dabx_fic *f);
 /* The channel BER of the FIC (ViterbiSpiral::calculate_BER, viterbi_spiral.cpp:128-164, driven from fic_decoder.cpp:199-210): the decoded
  * bits re-encoded and compared with the signs of the 2304 transmitted soft bits of every block; both counters are halved after every
@@ -308,6 +309,15 @@ typedef struct {
   float   freq_offs_bb_hz, clock_err_hz;
   float   snr_db_est;        /* OfdmDecoder's LCD SNR (ofdm_decoder.cpp:326-343) after the newest frame's last symbol */
   int32_t last_start_index, cif_count;
+  /* cif_count: CIFCountHi * 250 + CIFCountLo of the last FIG 0/0 in the last FIB with a good CRC that carries one (mCifCount); 0 before the
+   * first.  The rule is the reference's walk (fib_decoder.cpp:74-100, fib_decoder_fig0.cpp:95-101): FIG after FIG by the header's length
+   * field, stopped by the end marker alone, no length checked anywhere -- every FIG of type 0 with extension 0 sets the counter from the
+   * bytes 4 and 5 behind its header, whatever its length field says (with the header at byte 25 or 26 those are the FIB's CRC bytes).  The
+   * ETI frames of dabx_read_eti carry the same counter (one walk for both).  Three limits:
+   *  - a FIG 0/0 header at byte 27 or later of the FIB is ignored (the reference reads bits of whatever follows the FIB in its buffer);
+   *  - the reference's break after a FIG 0/1 with impossible content (mRestartFibDecoding) is not modelled: a FIG 0/0 behind it counts;
+   *  - dabx_fibdec / dabx_parse_fibs walk more strictly (they stop at a FIG that runs past byte 30 and take a FIG 0/0 of length >= 5
+   *    only): on a non-conformant FIB with a good CRC dabx_fibdec_info.cif_count can differ from this one. */
   int64_t fib_ok, fib_total, sf_ok, sf_fail, rs_corrected, rs_failed, au_ok, au_bad, cifs_decoded;
   float   signal_level;      /* SampleReader::sLevel (sample_reader.h:70,95; .cpp:245-248) after the newest frame */
   float   peak_level;        /* SampleReader::peakLevel (.cpp:247); tracked out of lock and, with exact_level_tracker, in lock */
@@ -322,7 +332,9 @@ typedef struct {
   /* -- ABI 5 -- */
   int64_t fic_ber_bits;      /* FicDecoder::mFicBits / mFicErrors (fic_decoder.h:74-75): transmitted FIC bits compared with the re-encoded */
   int64_t fic_ber_errors;    /* decoder output and those that differed (ViterbiSpiral::calculate_BER, viterbi_spiral.cpp:128-164), both halved
-                                every 40 FIC blocks (fic_decoder.cpp:201-210); the channel BER the reference displays is errors / bits */
+                                every 40 FIC blocks (fic_decoder.cpp:201-210); the channel BER the reference displays is errors / bits.
+                                The hard decision is taken on the Viterbi symbol: with viterbi_tie_mode 0 a soft bit >= 32641 counts as
+                                negative, because the scalar build's `soft + 127` wraps there (viterbi_scalar.h:34-40) */
   /* -- ABI 6 (in the place of the first reserved word: the record's size is unchanged) -- */
   float   mer_db_est;        /* OfdmDecoder's LCD MER (ofdm_decoder.cpp:204-208, 331-340) after the newest frame's last symbol; 0 unless
                                 dabx_set_lcd_statistics switched its per-carrier IIR on */
