@@ -661,6 +661,14 @@ static void ingest_free(dabx_engine *e)
   I = Ingest{};
 }
 
+// PadDev::n_mp2 follows the table: called behind every e->pad.upload()
+static void pad_count_sources(dabx_engine *e)
+{
+  int n = 0;
+  for (const auto &h : e->pad.host) n += h.on && h.st.source == DABX_PAD_SOURCE_MP2 ? 1 : 0;
+  e->pad.dev.n_mp2 = n;
+}
+
 // ---- slots with output rings (out_ring.h): what the packet-mode and the PAD entry points below share -------------------------------------
 static uint32_t pow2_at_least(size_t v) { uint32_t p = 1; while (p < v) p <<= 1; return p; }
 
@@ -1109,6 +1117,7 @@ static int set_subchannels_impl(dabx_engine *e, int stream, const dabx_subch_des
   if (!e->pad.host.empty()) {           // ... and so does PAD decoding
     for (size_t sj : restarted) e->pad.drop(sj);
     if ((rc = e->pad.upload())) return rc;
+    pad_count_sources(e);
   }
   if (e->dl.open) {
     // slots that start anew count their frames from 0 again; the slab layout follows the new sub-channels (engine drained above)
@@ -1139,6 +1148,7 @@ int dabx_set_subchannels_at(dabx_engine *e, int stream, const dabx_subch_desc *d
 // ---- slots with output rings: packet-mode data sub-channels (packet_core.h, k_packet) and programme-associated data (pad_core.h, k_pad) ----
 static_assert(sizeof(dabx_chunk_dg) == 128 && sizeof(dabx_datagroup_info) == 32 && sizeof(dabx_packet_stats) == 128 && sizeof(dabx_packet_config) == 32, "include/dabx.h: packet-mode records");
 static_assert(sizeof(dabx_chunk_pad) == 128 && sizeof(dabx_pad_item) == 32 && sizeof(dabx_pad_stats) == 128 && sizeof(dabx_pad_config) == 32, "include/dabx.h: PAD records");
+static_assert(sizeof(dabx_mp2_sync_stats) == 64 && offsetof(dabx_pad_config, source) == 4, "include/dabx.h: PAD of MP2 frames");
 
 int dabx_set_packet_mode(dabx_engine *e, int stream, int j, const dabx_packet_config *cfg)
 {
@@ -1156,6 +1166,7 @@ int dabx_set_packet_mode(dabx_engine *e, int stream, int j, const dabx_packet_co
     set_error("dabx_set_packet_mode: stream %d slot %d is %s", stream, j, !sc.active ? "not active" : sc.dab_plus ? "a DAB+ slot" : "not at a multiple of 8 kbit/s up to 384");
     return DABX_E_ARG;
   }
+  if (cfg && e->pad.on(sj)) { set_error("dabx_set_packet_mode: stream %d slot %d has PAD decoding on", stream, j); return DABX_E_ARG; }
   auto &tab = e->pkt;
   if (tab.host.empty()) {
     if (!cfg) return 0;
@@ -1214,7 +1225,15 @@ int dabx_set_pad_mode(dabx_engine *e, int stream, int j, const dabx_pad_config *
   const size_t sj = (size_t)stream * e->dev.max_subch + j;
   SubchDev sc;
   DABX_HIP(hipMemcpy(&sc, e->dev.subch + sj, sizeof(SubchDev), hipMemcpyDeviceToHost));
-  if (!sc.active || sc.dab_plus != 1 || !e->dev.sf_info) {
+  const int source = cfg && cfg->size >= 2 * sizeof(uint32_t) ? cfg->source : DABX_PAD_SOURCE_DABPLUS;
+  if (source != DABX_PAD_SOURCE_DABPLUS && source != DABX_PAD_SOURCE_MP2) { set_error("dabx_set_pad_mode: unknown source %d", source); return DABX_E_ARG; }
+  if (source == DABX_PAD_SOURCE_MP2) {
+    if (!sc.active || sc.dab_plus || e->pkt.on(sj) || sc.kbps % 8 != 0 || sc.kbps > PKT_MAX_KBPS) {
+      set_error("dabx_set_pad_mode: source MP2: stream %d slot %d is %s", stream, j, !sc.active ? "not active" : sc.dab_plus ? "a DAB+ slot" :
+                e->pkt.on(sj) ? "in packet mode" : "not at a multiple of 8 kbit/s up to 384");
+      return DABX_E_ARG;
+    }
+  } else if (!(cfg == nullptr && e->pad.on(sj)) && (!sc.active || sc.dab_plus != 1 || !e->dev.sf_info)) {      // (NULL also switches an MP2 source slot off)
     set_error("dabx_set_pad_mode: stream %d slot %d is %s", stream, j, !sc.active ? "not active" : "not a DAB+ slot");
     return DABX_E_ARG;
   }
@@ -1231,15 +1250,35 @@ int dabx_set_pad_mode(dabx_engine *e, int stream, int j, const dabx_pad_config *
     h.on = true;
     h.st.s = stream; h.st.j = j; h.st.sf_seen = sc.sf_count;           // the walk starts with the next super frame completed
     h.st.h.xpad_length = -1; h.st.h.segment_number = -1; h.st.h.segment_no = -1;       // pad_handler.h:74, :79, :83
+    h.st.source = source;
+    h.st.m.sample_rate = 48000; h.st.m.last_sync_bit = -1;             // mp2processor.cpp:236-240: SearchingForSync, both counts 0
     if (!out_ring_create(&h.st.out, PAD_BYTE_RING, PAD_ITEM_RING, PAD_ASM_ROOM, PAD_DL_ITEM_CAP, PAD_DL_BYTES_CAP)) {      // (pad_core.h has the derivations)
       set_error("dabx_set_pad_mode: out of device memory");
       (void)tab.upload();
+      pad_count_sources(e);
       return DABX_E_NOMEM;
     }
     tab.host[sj] = h;
   }
   if ((rc = tab.upload())) return rc;
+  pad_count_sources(e);
   return relayout_open_delivery(e, sj, sc, e->pkt);
+}
+
+int dabx_get_mp2_sync_stats(dabx_engine *e, int stream, int j, dabx_mp2_sync_stats *out)
+{
+  if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch || !out) { set_error("dabx_get_mp2_sync_stats: bad argument"); return DABX_E_ARG; }
+  memset(out, 0, sizeof(*out));
+  const size_t sj = (size_t)stream * e->dev.max_subch + j;
+  if (!e->pad.on(sj) || e->pad.host[sj].st.source != DABX_PAD_SOURCE_MP2) return sync_all(e);
+  if (int rc = sync_all(e)) return rc;
+  PadSlot st;
+  DABX_HIP(hipMemcpy(&st, e->pad.dev.slots + e->pad.index[sj], sizeof(PadSlot), hipMemcpyDeviceToHost));
+  const Mp2State &m = st.m;
+  out->syncs = m.syncs; out->frames = m.frames; out->hdr_refused = m.hdr_refused; out->rate_unsupported = m.rate_unsupported;
+  out->sample_rate = m.sample_rate; out->state = m.state; out->bit_count = m.bit_count; out->header_count = m.header_count;
+  out->last_sync_bit = m.last_sync_bit; out->active = 1;
+  return 0;
 }
 
 int dabx_read_pad_items(dabx_engine *e, int stream, int j, int n, dabx_pad_item *info, uint8_t *bytes, size_t max_bytes)

@@ -1,8 +1,10 @@
-// pad_core.h -- programme-associated data of DAB+ access units: the per-slot state, the argument of k_pad (pipeline.hip) and its device
-// helpers.  mp4processor.cpp:345-353 (the data stream element of an access unit) and PadHandler (base/backend/data/pad_handler.cpp:67-547):
+// pad_core.h -- programme-associated data of DAB+ access units and of DAB (MP2) audio frames: the per-slot state, the argument of k_pad and
+// k_pad_mp2 (pipeline.hip) and their device helpers.  mp4processor.cpp:345-353 (the data stream element of an access unit) and PadHandler (base/backend/data/pad_handler.cpp:67-547):
 // F-PAD dispatch, short and variable X-PAD, the dynamic label, the data-group length indicator and the assembly of the X-PAD MSC data
 // groups, up to the two hand-over points (the label's bytes in front of the charset conversion, the data group in front of the MOT
-// parser).  include/dabx.h "Programme-associated data" states the semantics and the four guards G1..G4.
+// parser).  include/dabx.h "Programme-associated data" states the semantics and the four guards G1..G4.  For a DAB (MP2) slot the front of
+// the walk is Mp2Processor's (base/backend/audio/mp2processor.cpp:250-285, :611-747): MP2 frame sync over the logical frames' bits and the
+// PAD at the end of the logical frame in which an MP2 frame completes; Mp2State and the mp2_* helpers below.
 #pragma once
 #include "pipeline.h"
 #include "out_ring.h"
@@ -46,14 +48,32 @@ constexpr int PAD_ASM_ROOM = 16896;
 // sub-field emits at most one item (one signal_show_label or one _build_MSC_segment call): 6 * 6 * 4 = 144 items per batch, 288 -> 512.
 // Bytes: a label item is at most DABX_DL_MAX_BYTES; the data-group items of a batch are together at most the bytes that were under
 // assembly (< PAD_ASM_ROOM) plus <= 48 per sub-field (< a label's 256): 2 * 144 * 256 + PAD_ASM_ROOM + PAD_ASM_ROOM = 107 520 -> 131 072.
+// An MP2 source slot (k_pad_mp2) stays inside the same bound: a batch walks at most 28 logical frames, a logical frame completes at most one
+// MP2 frame (mp2processor.cpp:691: lf is at least the logical frame's bits) and so hands on at most one X-PAD of at most 4 sub-fields:
+// 28 * 4 = 112 <= 144 items, and the bytes follow as above.
 constexpr uint32_t PAD_ITEM_RING = 512;
 constexpr uint32_t PAD_BYTE_RING = 131072;
+static_assert(4 * MSC_BATCH_FRAMES * 4 <= 144, "pad_core.h: the items of an MP2 source slot per batch");
 static_assert(2 * 144 <= PAD_ITEM_RING && 2 * 144 * DABX_DL_MAX_BYTES + 2 * PAD_ASM_ROOM <= PAD_BYTE_RING, "pad_core.h: ring sizes");
 // Per chunk of the bulk delivery (one batch): 144 items, 144 * 256 + PAD_ASM_ROOM bytes.
 constexpr uint32_t PAD_DL_ITEM_CAP = 144;
 constexpr uint32_t PAD_DL_BYTES_CAP = 144 * DABX_DL_MAX_BYTES + PAD_ASM_ROOM;
 
-// One PAD-enabled DAB+ slot.  The job table of k_pad is an array of these, PAD slots only, in HBM; none of it is part of EngineDev /
+// Mp2Processor's sync members (mp2processor.h:85-90, mp2processor.cpp:236-240) and what dabx_mp2_sync_stats counts.  Of MP2frame only the
+// 24 header bits are ever read for our purpose (_get_mp2_sample_rate, :271-285): the first 12 are the sync word's ones, the other 12 are
+// collected in `header` while the state is GetSampleRate (a header may straddle a logical-frame boundary).
+enum { MP2_SEARCHING = 0, MP2_GET_RATE = 1, MP2_GET_DATA = 2 };          // ESyncState, dabx_mp2_sync_stats.state
+struct Mp2State {
+  int32_t state;                  // MP2SyncState
+  int32_t header_count;           // MP2headerCount: the run of ones in front of the next bit (< 12)
+  int32_t bit_count;              // MP2bitCount
+  int32_t sample_rate;            // sampleRate: 48 000 at the start, sticky (:250-264)
+  int32_t header;                 // bits 12 .. MP2bitCount - 1 of MP2frame while state == MP2_GET_RATE
+  int32_t last_sync_bit;          // bit index in its logical frame of the 12th one of the last sync word, -1: none yet
+  long long syncs, frames, hdr_refused, rate_unsupported;
+};
+
+// One PAD-enabled slot.  The job table of k_pad and k_pad_mp2 is an array of these, PAD slots only, in HBM; none of it is part of EngineDev /
 // SubchDev.  Labels and groups share the slot's output rings (out_ring.h) in emission order.  The group under assembly is kept IN the byte
 // ring where the completed group will be: bytes [out.n_bytes, out.n_bytes + fill) (as packet_core.h keeps its series).  A label emitted
 // while a group is open moves those bytes up by the label's length first.  The ring's asm_room is PAD_ASM_ROOM.
@@ -65,9 +85,12 @@ struct PadSlot {
   uint8_t short_data[16];         // mShortPadData: one byte from :151 and at most mStillToGo <= 15 more
   uint8_t dl_text[DABX_DL_MAX_BYTES];
   PadCounters c;
+  // behind everything k_pad reads: the slot's source (DABX_PAD_SOURCE_*) and the front of k_pad_mp2's walk
+  int32_t source, reserved;
+  Mp2State m;
 };
 
-// k_pad's argument, by value: the job table and what the kernel reads of the engine (launch_msc_batch fills those in).
+// k_pad's and k_pad_mp2's argument, by value: the job table and what the kernel reads of the engine (launch_msc_batch fills those in).
 struct PadDev {
   PadSlot *slots;
   int32_t n;                      // PAD slots = blocks of one wave
@@ -76,6 +99,10 @@ struct PadDev {
   const uint8_t *sf_out;
   const dabx_superframe_info *sf_info;
   const uint16_t *crc_ccitt, *crc_xpow;
+  // k_pad_mp2: slots with source MP2 among the n (the kernel is launched only when there is one), and the logical frames of the batch
+  int32_t n_mp2, msc_stride;
+  const BatchSnap *snap;
+  const uint8_t *msc_out;
 };
 
 #ifdef __HIPCC__
@@ -377,6 +404,67 @@ __device__ __forceinline__ void pad_process(PadWave &w, const uint8_t *rb, int c
     break;
   default: w.c.xpad_other++; break;                              // :83-85
   }
+}
+// ---- the front of k_pad_mp2's walk: Mp2Processor::add_to_frame (mp2processor.cpp:678-747) without a bit-serial loop ----------------------
+// The logical frame is staged in LDS as bytes; bit i of the frame (iBits[i]) is bit 7 - (i & 7) of byte i >> 3, so a 32-bit word read
+// big-endian holds bits 32 w .. 32 w + 31 from its top bit down.
+__device__ __forceinline__ unsigned mp2_word_be(const uint8_t *frm, int w) { return __builtin_bswap32(reinterpret_cast<const uint32_t *>(frm)[w]); }
+
+// :715-733 for the bits [pos, nbits) at once: the first bit index at which MP2headerCount reaches 12, given the `run` ones counted in front
+// of pos (run < 12); -1: none, and *run_out = the count behind the last bit.  Lane l of pass k tests word pos / 32 + 64 k + l together with
+// the word in front of it (a run of 12 may end in the first bits of a word); bits in front of pos are replaced by `run` ones behind a zero.
+// The first hit of a pass comes from a ballot, so a sync word within 2048 bits of pos -- bit 0 in steady state -- costs one pass.
+__device__ __forceinline__ int mp2_find_sync(const uint8_t *frm, int nbits, int pos, int run, int lane, int *run_out)
+{
+  const int n_words = nbits >> 5;                                // 24 kbps bits: a multiple of 32 for every multiple of 8 kbit/s
+  for (int w0 = pos >> 5; w0 < n_words; w0 += 64) {
+    const int w = w0 + lane;
+    unsigned long long v = 0;
+    if (w < n_words) v = ((unsigned long long)(w > 0 ? mp2_word_be(frm, w - 1) : 0u) << 32) | mp2_word_be(frm, w);
+    const int first = 32 * (w - 1);                              // the frame's bit index of v's top bit
+    if (first < pos) {                                           // the top pos - first bits of v (1 .. 63, w >= pos / 32) lie in front of pos
+      const int cut = pos - first;
+      v = (v & (~0ull >> cut)) | (((1ull << run) - 1ull) << (64 - cut));     // (ones beyond the top bit fall away)
+    }
+    unsigned long long m = v & (v >> 1);                         // bit q: v[q .. q + 1] are ones
+    m &= m >> 2;                                                 // ... v[q .. q + 3]
+    const unsigned long long m8 = m & (m >> 4);                  // ... v[q .. q + 7]
+    const unsigned hit = (unsigned)(m8 & (m >> 8));              // ... v[q .. q + 11], for the bits of word w: a run of 12 ends there
+    const unsigned long long who = __ballot(hit != 0u);
+    if (who) {
+      const int l = __ffsll((long long)who) - 1;
+      const unsigned h = pad_u(__shfl(hit, l));
+      return 32 * (w0 + l) + __clz(h);
+    }
+  }
+  // no sync word: the run of ones at the end of the frame (at most 11, or the search would have ended), counted from pos on
+  int r = 0;
+  for (int i = nbits - 1; i >= pos && r < 12; i--) {             // wave-uniform, at most 12 steps
+    if (!((pad_u(frm[i >> 3]) >> (7 - (i & 7))) & 1u)) { *run_out = r; return -1; }
+    r++;
+  }
+  *run_out = r + run;                                            // every bit from pos on is a one (fewer than 12 - run of them)
+  return -1;
+}
+
+// the n <= 12 bits from bit `pos` on, first bit on top (:737)
+__device__ __forceinline__ unsigned mp2_bits(const uint8_t *frm, int nbytes, int pos, int n)
+{
+  const int b = pos >> 3;
+  const unsigned v = (pad_u(frm[b]) << 16) | (b + 1 < nbytes ? pad_u(frm[b + 1]) << 8 : 0u) | (b + 2 < nbytes ? pad_u(frm[b + 2]) : 0u);
+  return (v >> (24 - (pos & 7) - n)) & ((1u << n) - 1u);
+}
+
+// :740: _set_sample_rate(_get_mp2_sample_rate(MP2frame)) on MP2frame[0 .. 2] = 0xFF, 0xF0 | header >> 8, header & 0xFF
+__device__ __forceinline__ void mp2_header(Mp2State &m)
+{
+  const int b1 = 0xF0 | (m.header >> 8), b2 = m.header & 0xFF;
+  const bool refused = (b1 & 0xF6) != 0xF4 || (b2 - 0x10) >= 0xE0;         // :277-282 (in int: only bit-rate index 15 is "invalid", index 0 passes)
+  const int at = (((b1 & 0x08) >> 1) ^ 4) + ((b2 >> 2) & 3);     // :283-284 sample_rates = 44100, 48000, 32000, 0, 22050, 24000, 16000, 0
+  const int rate = refused ? 0 : at == 1 ? 48000 : at == 5 ? 24000 : 1;    // (1: any of the rates _set_sample_rate refuses, :257-261, 0 included)
+  m.hdr_refused += refused ? 1 : 0;                              // (sums, not branches: the counters stay in registers)
+  m.rate_unsupported += rate == 1 ? 1 : 0;                       // a refused header's 0 ends at :257-261 too: sampleRate stays
+  if (rate == 48000 || rate == 24000) m.sample_rate = rate;      // :252-263
 }
 #endif
 

@@ -14,6 +14,7 @@
 //   k_dabplus      super-frame sync, RS(120,110), fire code, AU CRCs (mp4processor.cpp:96-333)
 //   k_packet       packet-mode data sub-channels: packet walk, packet CRCs, assembly of the MSC data groups (data_processor.cpp:106-254)
 //   k_pad          PAD of the DAB+ access units: dynamic labels and X-PAD MSC data groups (mp4processor.cpp:345-353, pad_handler.cpp:67-547)
+//   k_pad_mp2      PAD of DAB (MP2) audio frames: MP2 frame sync over the logical frames and the same PadHandler (mp2processor.cpp:611-747)
 #include <type_traits>
 #include "pipeline.h"
 #include "packet_core.h"
@@ -2092,6 +2093,94 @@ __global__ __launch_bounds__(64) void k_pad(PadDev pd)
   if (lane == 0) { ps.h = w.h; ps.c = w.c; ps.out.count = w.n_items; ps.out.n_bytes = w.n_bytes; ps.sf_seen = have; }
 }
 
+// One wave per PAD slot whose source is the MP2 frames of a DAB audio sub-channel (PadSlot::source; the blocks of the other slots of the
+// table return at once, as k_pad's do for these), behind k_dabplus, which has moved the slots' frame counters on: walks the logical frames
+// the decoder produced in this batch step, the frames k_packet walks (BatchSnap, start_cif + 16) in its numbering.  Per frame: the frame
+// is staged in LDS and Mp2Processor::add_to_frame (mp2processor.cpp:678-747) runs over its 24 kbps bits as a handful of wave-uniform phase
+// changes -- at most one completed MP2 frame (:691: lf is at least a logical frame's bits) and two searches -- the search for the 12 ones
+// being one wave-wide pass (mp2_find_sync).  When an MP2 frame completes, _process_pad_data (:611-674) takes the PAD from the end of the
+// CURRENT logical frame (:695): F-PAD in the last two bytes, the X-PAD in front of the ScF-CRC, staged reversed as k_pad stages it and
+// handed to the same pad_process.  Only the newest 254 X-PAD bytes are staged: PadHandler reads at most 196 below iLast.
+__global__ __launch_bounds__(64) void k_pad_mp2(PadDev pd)
+{
+  const int lane = threadIdx.x;
+  PadSlot &ps = pd.slots[blockIdx.x];
+  if (ps.source != DABX_PAD_SOURCE_MP2) return;
+  const size_t sj = (size_t)ps.s * pd.max_subch + ps.j;
+  const SubchDev &sc = pd.subch[sj];
+  if (!sc.active || sc.dab_plus) return;
+  const BatchSnap bs = pd.snap[ps.s];
+  long long n_new = 0;                        // logical frames the decoder just produced for this sub-channel (as k_dabplus counted them)
+  for (long long r = bs.msc_done; r < bs.cif_no; r++) if (r >= sc.start_cif + 16) n_new++;
+  if (n_new == 0) return;
+  const int nbytes = 3 * sc.kbps, nbits = 8 * nbytes;          // <= 1152 bytes (dabx_set_pad_mode); MP2framesize = 24 * bitRate (:236)
+  const int v_len = nbytes - (sc.kbps >= 56 ? 4 : 2) - 2;       // :613-621
+  const int n_stage = min(v_len, 254);
+  const uint8_t *ring = pd.msc_out + sj * MSC_SLOTS * pd.msc_stride;
+  __shared__ __attribute__((aligned(16))) uint8_t frm[3 * PKT_MAX_KBPS];
+  __shared__ uint8_t rb[256];                                  // rb[0] = L0, rb[1] = L1, rb[2 + k] = frame[vLen - 1 - k]
+  __shared__ uint8_t s_text[DABX_DL_MAX_BYTES], s_short[16];
+  __shared__ uint16_t s_crc[256];
+  __shared__ __attribute__((aligned(16))) uint16_t s_xpow[1024];
+  for (int i = lane; i < 256; i += 64) { s_crc[i] = pd.crc_ccitt[i]; s_text[i] = ps.dl_text[i]; }
+  for (int i = lane; i < 128; i += 64) reinterpret_cast<uint4 *>(s_xpow)[i] = reinterpret_cast<const uint4 *>(pd.crc_xpow)[i];
+  if (lane < 16) s_short[lane] = ps.short_data[lane];
+  PadWave w;
+  w.h = ps.h; w.c = ps.c;
+  w.ring = ps.out.bytes; w.items = ps.out.recs; w.bytes_mask = ps.out.bytes_mask; w.item_mask = ps.out.rec_mask;
+  w.n_items = ps.out.count; w.n_bytes = ps.out.n_bytes;
+  w.lane = lane; w.au = 0; w.text = s_text; w.shortd = s_short; w.s_crc = s_crc; w.s_xpow = s_xpow;
+  Mp2State m = ps.m;
+  const long long frame0 = sc.cif_out - n_new;
+  for (long long n = 0; n < n_new; n++) {
+    w.frame = frame0 + n;                     // index of the logical frame in the slot's sequence
+    __syncthreads();                          // the previous frame (and the tables) are done with
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(ring + (size_t)(w.frame % MSC_SLOTS) * pd.msc_stride);
+    for (int i = lane; i < nbytes / 4; i += 64) reinterpret_cast<uint32_t *>(frm)[i] = src[i];
+    __syncthreads();
+    w.c.superframes++;                        // (dabx_pad_stats of an MP2 source slot: logical frames walked)
+    int pos = 0;                              // :685 i
+    while (pos < nbits) {
+      if (m.state == MP2_GET_DATA) {                             // :687-714
+        const int lf = m.sample_rate == 48000 ? nbits : 2 * nbits;      // :680, :741
+        const int need = lf - m.bit_count;                       // (>= 1: a frame that completes leaves the state)
+        if (need > nbits - pos) { m.bit_count += nbits - pos; break; }
+        pos += need;                                             // :691 the MP2 frame is complete with bit pos - 1
+        m.frames++;
+        w.c.aus++; w.c.pad_aus++;                                // :695 _process_pad_data(iBits): the PAD at the end of THIS logical frame
+        const unsigned l1 = pad_u(frm[nbytes - 2]);              // :624
+        const int count = (((l1 >> 4) & 3) == 1 ? 4 : n_stage) + 2;     // :649-657; F-PAD type and the indicators 0 and 3: pad_process (:629-645)
+        __syncthreads();                                         // the previous PAD's bytes are done with
+        if (lane < 2) rb[lane] = frm[nbytes - 1 - lane];         // :623-624 L0, L1
+        for (int k = lane; k < n_stage; k += 64) rb[2 + k] = frm[v_len - 1 - k];     // :660-673 pPadData[vLengthBytes - 1 - k]
+        __syncthreads();
+        pad_process(w, rb, count);                               // :673 process_PAD(pPadData, vLengthBytes - 1, L1, L0)
+        m.state = MP2_SEARCHING; m.header_count = 0; m.bit_count = 0;   // :710-712
+      } else if (m.state == MP2_SEARCHING) {                     // :715-734
+        int run;
+        const int p = mp2_find_sync(frm, nbits, pos, m.header_count, lane, &run);
+        if (p < 0) { m.header_count = run; break; }              // :720, :732 to the end of the frame
+        m.syncs++; m.last_sync_bit = p;
+        m.header_count = 12; m.bit_count = 12; m.header = 0;     // :720-726
+        m.state = MP2_GET_RATE;                                  // :727
+        pos = p + 1;
+      } else {                                                   // :735-744
+        const int k = min(24 - m.bit_count, nbits - pos);
+        m.header = (m.header << k) | (int)mp2_bits(frm, nbytes, pos, k);       // :737
+        m.bit_count += k; pos += k;
+        if (m.bit_count == 24) {                                 // :738
+          mp2_header(m);                                         // :740
+          m.state = MP2_GET_DATA;                                // :742
+        }
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = lane; i < DABX_DL_MAX_BYTES; i += 64) ps.dl_text[i] = s_text[i];
+  if (lane < 16) ps.short_data[lane] = s_short[lane];
+  if (lane == 0) { ps.h = w.h; ps.c = w.c; ps.out.count = w.n_items; ps.out.n_bytes = w.n_bytes; ps.m = m; }
+}
+
 // ---------------------------------------------------------------------------------------------- launchers
 __global__ void k_msc_snap(EngineDev e, int cifs)
 {
@@ -2236,7 +2325,8 @@ int launch_deliver_pad(const EngineDev &e, const DeliverDev &dv, const PadDev &p
 // completion event; *tail (optional) = the stream whose work completes the batch.
 // `pk` (optional): the engine has packet-mode slots -- k_packet walks their new logical frames, in front of k_dabplus (which moves the
 // slots' frame counters on); null = no launch.
-// `pad` (optional): the engine has PAD slots -- k_pad walks the super frames k_dabplus has just completed for them; null = no launch.
+// `pad` (optional): the engine has PAD slots -- k_pad walks the super frames k_dabplus has just completed for the DAB+ ones, k_pad_mp2 the
+// batch's logical frames of those whose source is MP2 (pad->n_mp2 of the pad->n), each launched only when it has a slot; null = no launch.
 int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineStreams &ss, Marker &mk, const DeliverDev *dv, hipStream_t *tail,
                      const PacketDev *pk, const PadDev *pad)
 {
@@ -2340,8 +2430,10 @@ int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineSt
     q = *pad;
     q.max_subch = e.max_subch; q.sf_stride = e.sf_stride; q.subch = e.subch; q.sf_out = e.sf_out; q.sf_info = e.sf_info;
     q.crc_ccitt = t->crc_ccitt; q.crc_xpow = t->crc_xpow;
+    q.msc_stride = e.msc_stride; q.snap = e.snap; q.msc_out = e.msc_out;
     mk.begin(12, sb);
-    hipLaunchKernelGGL(k_pad, dim3(q.n), dim3(64), 0, sb, q);
+    if (q.n > q.n_mp2) hipLaunchKernelGGL(k_pad, dim3(q.n), dim3(64), 0, sb, q);
+    if (q.n_mp2 > 0) hipLaunchKernelGGL(k_pad_mp2, dim3(q.n), dim3(64), 0, sb, q);
     mk.end(12, sb);
   }
   if (dv && (rc = launch_deliver_msc(e, *dv, sb, !dv->lf_done))) return rc;

@@ -69,6 +69,8 @@ def load(build_if_missing=True):
         L.dabx_set_pad_mode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.dabx_read_pad_items.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
         L.dabx_get_pad_stats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    if hasattr(L, "dabx_get_mp2_sync_stats"):        # ... and of DAB (MP2) audio slots
+        L.dabx_get_mp2_sync_stats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     if hasattr(L, "dabx_announce_write"):            # (absent from libraries older than the level anchor: tools/ab.sh runs those through this binding too)
         L.dabx_announce_write.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
     _LIB = L
@@ -424,11 +426,17 @@ CHUNK_PAD = np.dtype([("first_item", "<i8"), ("n_items", "<i4"), ("items_lost", 
                      [(k, "<i8") for k in ("superframes", "aus", "pad_aus", "pad_bad", "labels", "label_bytes", "groups", "group_bytes", "dg_crc_bad",
                                            "dl_overflow", "li_bad")])
 assert PAD_ITEM.itemsize == 32 and PAD_STATS.itemsize == 128 and CHUNK_PAD.itemsize == 128
+# PAD of DAB (MP2) audio frames: DABX_PAD_SOURCE_* and dabx_mp2_sync_stats (where Mp2Processor's frame sync of the slot stands)
+PAD_SOURCES = {"dabplus": 0, "mp2": 1}
+MP2_SEARCHING, MP2_GET_RATE, MP2_GET_DATA = 0, 1, 2
+MP2_SYNC_STATS = np.dtype([(k, "<i8") for k in ("syncs", "frames", "hdr_refused", "rate_unsupported")] +
+                          [(k, "<i4") for k in ("sample_rate", "state", "bit_count", "header_count", "last_sync_bit", "active")] + [("reserved", "<i4", 2)])
+assert MP2_SYNC_STATS.itemsize == 64
 
 
 class PadConfig(C.Structure):
     """dabx_pad_config."""
-    _fields_ = [("size", C.c_uint32), ("reserved", C.c_int32 * 7)]
+    _fields_ = [("size", C.c_uint32), ("source", C.c_int32), ("reserved", C.c_int32 * 6)]
 
 
 class PacketConfig(C.Structure):
@@ -750,13 +758,14 @@ class Engine:
         check(L.dabx_get_packet_stats(self._h, int(stream), int(j), _p(out)))
         return {k: int(out[0][k]) for k in PACKET_STATS.names if k != "reserved"}
 
-    def set_pad_mode(self, stream, j, on=True):
-        """Switches the PAD decoding of DAB+ slot j of `stream` on (restarting it when it is on already) or off (dabx_set_pad_mode)."""
+    def set_pad_mode(self, stream, j, on=True, source="dabplus"):
+        """Switches the PAD decoding of slot j of `stream` on (restarting it when it is on already) or off (dabx_set_pad_mode).  source:
+        "dabplus", the access units of a DAB+ slot, or "mp2", the MP2 frames of a DAB audio slot (an integer is passed on as it is)."""
         L = load()
         if not on:
             check(L.dabx_set_pad_mode(self._h, int(stream), int(j), None))
         else:
-            cfg = PadConfig(size=C.sizeof(PadConfig))
+            cfg = PadConfig(size=C.sizeof(PadConfig), source=PAD_SOURCES[source] if isinstance(source, str) else int(source))
             check(L.dabx_set_pad_mode(self._h, int(stream), int(j), C.byref(cfg)))
 
     def read_pad_items(self, stream, j, n=512, max_bytes=None, with_bytes=True):
@@ -770,6 +779,12 @@ class Engine:
         out = np.zeros(1, PAD_STATS)
         check(L.dabx_get_pad_stats(self._h, int(stream), int(j), _p(out)))
         return {k: int(out[0][k]) for k in PAD_STATS.names if k != "reserved"}
+
+    def mp2_sync_stats(self, stream, j):
+        """dabx_mp2_sync_stats of slot j as a dict (all zero unless the slot is a PAD slot with source "mp2")."""
+        out = np.zeros(1, MP2_SYNC_STATS)
+        check(load().dabx_get_mp2_sync_stats(self._h, int(stream), int(j), _p(out)))
+        return {k: int(out[0][k]) for k in MP2_SYNC_STATS.names if k != "reserved"}
 
     def read_soft(self, stream):
         out = np.zeros((75, 3072), np.int16)

@@ -611,27 +611,51 @@ int  dabx_get_packet_stats(dabx_engine *e, int stream, int subch_idx, dabx_packe
  *      maximum is 8 segments of 16 bytes): an append that would exceed it is dropped whole, text unchanged, counted in dl_overflow.
  * The data-group buffer needs no guard: mMscDataGroupBuffer is handed on as soon as it reaches mDataGroupLength <= 16 383 (:512), so it
  * never holds more than 16 382 bytes plus one sub-field (at most 196 bytes, a no-CI continuation of mXPadLength bytes).
- * Out of scope: MotObject / MotHandler, the charset conversion, DL Plus, F-PAD types other than 0, PAD of MP2 frames. */
+ *
+ * PAD of DAB (MP2) audio frames (source DABX_PAD_SOURCE_MP2): for a classic DAB audio sub-channel the same PadHandler is fed by the one
+ * piece of Mp2Processor that is neither audio decoding nor GUI (base/backend/audio/mp2processor.cpp:611-747 with :250-285), on the device
+ * (k_pad_mp2, beside k_pad on the MSC batch's stream, one wave per such slot).  Mp2Processor::add_to_frame (:678-747) runs over the bits of
+ * every logical frame (24 * kbps of them, MP2framesize): SearchingForSync counts ones until the 12th (:715-733; the run may straddle a
+ * logical-frame boundary), GetSampleRate collects 12 more header bits (:735-744; they may straddle one too), GetData counts bits until
+ * MP2bitCount reaches lf = MP2framesize at 48 kHz, twice that at 24 kHz (:680, :741), and then searches again.  Quirks kept:
+ *   - the header check (:277-279) evaluates (iFrame[2] - 0x10) >= 0xE0 in int: only bit-rate index 15 is refused, index 0 passes; a
+ *     refused header and the rates 44 100, 32 000, 22 050, 16 000 and 0 leave sampleRate as it was (:257-261; it starts at 48 000);
+ *   - when an MP2 frame completes (:691), _process_pad_data takes the PAD from the end of the CURRENT logical frame, wherever in it the MP2
+ *     frame ended (:695); at 24 kHz that is every second logical frame.
+ * _process_pad_data (:611-674): vLen = 3 * kbps - (kbps >= 56 ? 4 : 2) - 2 bytes in front of the ScF-CRC and the F-PAD; L0 is the logical
+ * frame's last byte, L1 the one in front of it; F-PAD type != 0 and X-PAD indicator 0 and 3 return (counted as for DAB+); indicator 1 hands
+ * on the four bytes frame[vLen - 4 .. vLen) with iLast = 3, indicator 2 frame[0 .. vLen) with iLast = vLen - 1.  The device stages the
+ * newest min(vLen, 254) of them: PadHandler reads at most 196 bytes below iLast (four contents indicators, sub-fields of together at
+ * most 4 * 48 bytes, or a no-CI continuation of mXPadLength <= 196 bytes), so no decision changes.  Guards G1 and G2 have no counterpart
+ * (vLen >= 20 and the short form always has its four bytes); G3 and the check of :219 do bite at small rates, G4 is as above.
+ * Parity of this path with the reference is unpinned: mp2processor.cpp cannot be compiled without the GUI's headers, so the tests compare
+ * the device with a line-by-line restatement (tests/mp2_pad_cases.py), not with the reference's object code.
+ * Out of scope: MotObject / MotHandler, the charset conversion, DL Plus, F-PAD types other than 0, MP2 audio decoding, handing out
+ * assembled MP2 frames. */
 #define DABX_DL_MAX_BYTES 256
 enum { DABX_PAD_LABEL = 1, DABX_PAD_DATAGROUP = 2 };
+enum { DABX_PAD_SOURCE_DABPLUS = 0,    /* the access units of a DAB+ slot (dab_plus == 1) */
+       DABX_PAD_SOURCE_MP2 = 1 };      /* the MP2 frames of a DAB audio slot (dab_plus == 0, not in packet mode, a multiple of 8 kbit/s up to 384) */
 typedef struct {
   uint32_t size;             /* sizeof(dabx_pad_config) of the caller */
-  int32_t  reserved[7];      /* zero */
+  int32_t  source;           /* DABX_PAD_SOURCE_*; read only when size >= 8 (a shorter configuration means DABX_PAD_SOURCE_DABPLUS) */
+  int32_t  reserved[6];      /* zero */
 } dabx_pad_config;
 typedef struct dabx_pad_item_s {
   int64_t  byte_pos;         /* position of the item's first byte in the slot's sequence of item bytes */
-  int64_t  frame;            /* dabx_superframe_info.first_frame of the super frame whose access unit completed the item */
+  int64_t  frame;            /* dabx_superframe_info.first_frame of the super frame whose access unit completed the item; MP2 source: the
+                                index of the logical frame that supplied the PAD, in the numbering of dabx_datagroup_info.last_frame */
   uint16_t length;           /* bytes */
   uint8_t  kind;             /* DABX_PAD_LABEL or DABX_PAD_DATAGROUP */
-  uint8_t  au;               /* ... and that access unit's index in the super frame */
+  uint8_t  au;               /* ... and that access unit's index in the super frame (MP2 source: 0) */
   uint8_t  charset;          /* labels: mCharSet (pad_handler.cpp:122, :353) */
   uint8_t  crc_flag;         /* groups: bit 6 of byte 0 (:539) */
   uint8_t  crc_ok;           /* groups: check_crc_bytes(iData, length - 2) (:541) */
   uint8_t  reserved[9];
 } dabx_pad_item;             /* 32 bytes, little-endian, no holes */
 typedef struct {
-  int64_t superframes;       /* super frames walked */
-  int64_t aus;               /* access units taken (au_crc_ok set, au_len_bad clear) */
+  int64_t superframes;       /* super frames walked (MP2 source: logical frames walked) */
+  int64_t aus;               /* access units taken (au_crc_ok set, au_len_bad clear) (MP2 source: _process_pad_data calls, as pad_aus) */
   int64_t pad_aus;           /* ... that start with a data stream element (id 4, mp4processor.cpp:345) */
   int64_t fpad_other;        /* ... whose F-PAD type is not 0 (pad_handler.cpp:71) */
   int64_t xpad_short, xpad_variable, xpad_other;      /* X-PAD indicator 1 / 2 / 0 or 3 (:81-96), counted in front of the guards */
@@ -646,8 +670,9 @@ typedef struct {
   int32_t active;            /* 1: PAD decoding is on for the slot (all else is zero otherwise) */
   int32_t reserved;
 } dabx_pad_stats;            /* 128 bytes */
-/* Switches PAD decoding of slot subch_idx of `stream` on (cfg != NULL) or off (NULL).  Only an active slot with dab_plus == 1; DABX_E_ARG
- * otherwise.  The slot's logical frames, super frames and records are produced and delivered exactly as before; the walk starts with the
+/* Switches PAD decoding of slot subch_idx of `stream` on (cfg != NULL) or off (NULL).  Source DABX_PAD_SOURCE_DABPLUS: only an active
+ * slot with dab_plus == 1; source DABX_PAD_SOURCE_MP2: only an active slot with dab_plus == 0 that is not in packet mode; DABX_E_ARG
+ * otherwise, and for an unknown source.  NULL: a slot whose PAD decoding is on, or a DAB+ slot.  The slot's logical frames, super frames and records are produced and delivered exactly as before; the walk starts with the
  * next super frame completed.  Calling it again for a PAD slot restarts the state with empty rings.  The setting and the state stay with
  * the slot wherever dabx_set_subchannels says it "keeps decoding without interruption", a move to other capacity units included; a new or
  * changed slot loses them.  An engine without a PAD slot allocates and launches nothing for this stage.  Drains the engine. */
@@ -659,6 +684,23 @@ int  dabx_set_pad_mode(dabx_engine *e, int stream, int subch_idx, const dabx_pad
  * emit (512 items, 128 KiB; pad_core.h has the derivation).  Drains the engine like the other dabx_read_* calls. */
 int  dabx_read_pad_items(dabx_engine *e, int stream, int subch_idx, int n, dabx_pad_item *info, uint8_t *bytes, size_t max_bytes);
 int  dabx_get_pad_stats(dabx_engine *e, int stream, int subch_idx, dabx_pad_stats *out);
+/* Where Mp2Processor's frame sync of a PAD slot with source DABX_PAD_SOURCE_MP2 stands: a host MP2 decoder learns from it where the MP2
+ * frames start in the logical frames it reads.  All zero for any other slot.  Drains the engine. */
+typedef struct {
+  int64_t syncs;             /* sync words found: 12 ones in a row (mp2processor.cpp:720) */
+  int64_t frames;            /* MP2 frames completed (:691) = _process_pad_data calls */
+  int64_t hdr_refused;       /* headers _get_mp2_sample_rate refused (:277-279): ID / layer bits, or bit-rate index 15 */
+  int64_t rate_unsupported;  /* headers that passed with a rate _set_sample_rate refuses (:257-261): 44 100, 32 000, 22 050, 16 000, 0 */
+  int32_t sample_rate;       /* sampleRate: 48 000 or 24 000 */
+  int32_t state;             /* MP2SyncState: 0 SearchingForSync, 1 GetSampleRate, 2 GetData */
+  int32_t bit_count;         /* MP2bitCount */
+  int32_t header_count;      /* MP2headerCount */
+  int32_t last_sync_bit;     /* bit index in its logical frame of the 12th one of the last sync word (the MP2 frame starts 11 bits in
+                                front of it); -1: none yet */
+  int32_t active;            /* 1: the slot is a PAD slot with source DABX_PAD_SOURCE_MP2 (all else is zero otherwise) */
+  int32_t reserved[2];
+} dabx_mp2_sync_stats;       /* 64 bytes */
+int  dabx_get_mp2_sync_stats(dabx_engine *e, int stream, int subch_idx, dabx_mp2_sync_stats *out);
 /* ------------------------------------------------------------------------------------------------------------
  * Bulk delivery of the results to the host.  The reference hands every FIB to IFibDecoder::process_FIB
  * (base/decoder/fib_decoder_if.h:81, called from fic_decoder.cpp:234-261) and every logical frame to
