@@ -59,14 +59,14 @@ __global__ __launch_bounds__(128) void k_deliver_front(EngineDev e, DeliverDev d
 }
 
 // Which logical frames of slot sj the chunk carries.  Called BEFORE the DAB+ stage (k_deliver_lf: cif_out has not been moved on yet, the
-// batch's new frames are counted from its snapshot exactly as k_dabplus counts them) and after it (k_deliver_msc: pre = false).
+// batch's new frames are counted from its snapshot, msc_new_frames as in k_dabplus) and after it (k_deliver_msc: pre = false).
 struct LfRange { long long first; int n, lost; };
 __device__ __forceinline__ LfRange deliver_lf_range(const EngineDev &e, const DeliverDev &dv, int sj, const SubchDev &sc, bool pre)
 {
   long long cif_out = sc.cif_out;
   if (pre) {
     const BatchSnap bs = e.snap[sj / e.max_subch];
-    for (long long r = bs.msc_done; r < bs.cif_no; r++) if (r >= sc.start_cif + 16) cif_out++;
+    cif_out += msc_new_frames(bs.msc_done, bs.cif_no, sc.start_cif).n;
   }
   const int cap_cifs = 4 * dv.hdr.max_frames;
   const long long have = cif_out - dv.cif_done[sj];

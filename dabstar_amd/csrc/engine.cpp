@@ -1692,7 +1692,7 @@ int dabx_read_eti(dabx_engine *e, int stream, int max_frames, uint8_t *out, int3
   for (int j = 0; j < d.max_subch; j++) if (row[j].active) act.push_back(j);
   // CIFs [lo_cif, hi_cif) are complete in both rings
   long long hi_cif = act.empty() ? c.cif_no : c.msc_done_cif, lo_cif = std::max(0ll, (c.frames - d.out_frames) * 4);
-  for (int j : act) lo_cif = std::max(lo_cif, row[j].start_cif + 16 + std::max(0ll, row[j].cif_out - MSC_SLOTS));
+  for (int j : act) lo_cif = std::max(lo_cif, msc_first_cif(row[j].start_cif) + std::max(0ll, row[j].cif_out - MSC_SLOTS));   // the oldest logical frame still in the ring
   dabx_engine::EtiCursor &cur = e->eti[stream];
   if (cur.next_cif < 0) { cur.next_cif = lo_cif; cur.fib_frames_seen = lo_cif / 4; }
   if (cur.next_cif < lo_cif) {

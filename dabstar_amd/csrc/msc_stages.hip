@@ -1,0 +1,553 @@
+// msc_stages.hip -- the slot stages behind the MSC decoder of a batch: one wave per (stream, sub-channel) slot walks what the decoder -- or
+// the stage in front -- has just produced for the slot.  launch_msc_batch (pipeline.hip) runs them on the batch's stream in this order:
+//
+//   k_packet       packet-mode data sub-channels: packet walk, packet CRCs, assembly of the MSC data groups (data_processor.cpp:106-254)
+//   k_dabplus      super-frame sync, RS(120,110), fire code, AU CRCs (mp4processor.cpp:96-333); moves the slots' frame counters on
+//   k_pad          PAD of the DAB+ access units: dynamic labels and X-PAD MSC data groups (mp4processor.cpp:345-353, pad_handler.cpp:67-547)
+//   k_pad_mp2      PAD of DAB (MP2) audio frames: MP2 frame sync over the logical frames and the same PadHandler (mp2processor.cpp:611-747)
+//
+// Which logical frames of a slot are new in a batch is msc_new_frames (pipeline.h), for every stage and for the delivery (deliver.hip).
+#include "pipeline.h"
+#include "packet_core.h"
+#include "pad_core.h"
+#include "fec_core.h"
+#include "wave_ops.h"
+
+namespace dabx {
+
+// ------------------------------------------------------------------------------------------------- DAB+
+// One wave per (stream, sub-channel); walks the logical frames produced in this batch step.
+// The 5-frame window is staged in LDS once per super frame.  RS code word j is the byte sequence
+// window[j + k R], k < 120 (mp4processor.cpp:193-201) and its corrected data bytes go back to the same
+// positions of mOutVec (:225-228), so the super frame is simply window[0 .. 110 R) corrected in place.
+// Syndromes of all R code words x 10 roots are evaluated lane-parallel (Horner over LDS); the full
+// Berlekamp-Massey / Chien / Forney decoder runs only for code words whose syndromes are not all zero.
+__global__ __launch_bounds__(64, 4) void k_dabplus(EngineDev e, DevTables t)   // <= 128 VGPRs: four waves per SIMD (it took 129)
+{
+  const int job = blockIdx.x, lane = threadIdx.x;
+  const int s = job / e.max_subch, j = job % e.max_subch;
+  SubchDev &sc = e.subch[(size_t)s * e.max_subch + j];
+  if (!sc.active) return;
+  const BatchSnap bs = e.snap[s];
+  const long long n_new = msc_new_frames(bs.msc_done, bs.cif_no, sc.start_cif).n;   // logical frames the decoder just produced for this sub-channel
+  if (n_new == 0) return;
+  const int R = sc.kbps / 8, nbytes = 3 * sc.kbps;         // nbytes = 24 R
+  const uint8_t *ring = e.msc_out + ((size_t)s * e.max_subch + j) * MSC_SLOTS * e.msc_stride;
+  long long cif_out = sc.cif_out;
+  int blocks_in_buf = sc.blocks_in_buf, sf_sync = sc.sf_sync;
+  long long sf_count = sc.sf_count, sf_ok = 0, sf_fail = 0, rs_corr = 0, rs_fail = 0, fc_corr = 0, au_ok = 0, au_bad = 0;
+  __shared__ __attribute__((aligned(16))) uint8_t win[120 * 48 + 16];   // 5 logical frames (<= 384 kbit/s)
+  __shared__ uint8_t gexp[512], glog[256];
+  __shared__ uint16_t s_crc[256], s_fc[256];                // CCITT and fire-code CRC tables (serial look-up chains: keep them in LDS)
+  __shared__ __attribute__((aligned(16))) uint16_t s_xpow[1024];   // x^(8 m) mod P, m <= 960: two look-ups per access unit sat behind an L2 round trip each
+  __shared__ unsigned syn_or[48];                           // != 0: some syndrome of the code word is non-zero
+  __shared__ __attribute__((aligned(4))) unsigned syn_w[48][3];   // the code word's ten syndromes (bytes 0..9 of the three words): the full decoder starts from them
+  __shared__ uint8_t s_lam[48][12], s_deg[48], s_root[48][RS_NR];  // per dirty code word: locator (index form) + degree -> roots found by the wave-wide Chien search
+  __shared__ int s_rootn[48];
+  __shared__ uint8_t hdr0[12];
+  __shared__ int s_flag;
+  __shared__ int s_au[8];
+  if (sc.dab_plus) {
+    for (int i = lane; i < 512; i += 64) gexp[i] = t.gf_exp[i];
+    for (int i = lane; i < 256; i += 64) { glog[i] = t.gf_log[i]; s_crc[i] = t.crc_ccitt[i]; s_fc[i] = t.fc_crctab[i]; }
+    for (int i = lane; i < 128; i += 64) reinterpret_cast<uint4 *>(s_xpow)[i] = reinterpret_cast<const uint4 *>(t.crc_xpow)[i];
+  }
+  unsigned syn_ex[2][3];                      // (r (119 - k)) mod 255 for r = 0..9 as bytes, k = lane + 64 h: the syndrome sums' exponents
+#pragma unroll
+  for (int h = 0; h < 2; h++) {
+    const int m = 119 - (lane + 64 * h);
+    int ex = 0;
+    syn_ex[h][0] = syn_ex[h][1] = syn_ex[h][2] = 0;
+#pragma unroll
+    for (int r = 0; r < 10; r++) {
+      syn_ex[h][r >> 2] |= (unsigned)ex << (8 * (r & 3));
+      ex += m;
+      if (ex >= 255) ex -= 255;
+    }
+  }
+  __syncthreads();
+  for (long long n = 0; n < n_new; n++) {
+    const long long newest = cif_out;        // index of the logical frame just added
+    cif_out++;
+    if (!sc.dab_plus) continue;
+    blocks_in_buf++;                         // mp4processor.cpp:113
+    if (blocks_in_buf < 5) continue;
+    const long long oldest = newest - 4;
+    if (sf_sync == 0) {                      // :132-142: fire code over the first 11 bytes of the oldest frame
+      const uint8_t *f0 = ring + (size_t)(oldest % MSC_SLOTS) * e.msc_stride;
+      const bool ok = firecode_syndrome([&](int i) { return f0[i]; }, s_fc) == 0;
+      if (ok) sf_sync = 4; else { blocks_in_buf = 4; continue; }
+    }
+    blocks_in_buf = 0;                       // :147
+    // ---- stage the window (coalesced 4-byte loads) and the GF tables
+    __syncthreads();
+    {                                         // the five frames' loads of a chunk in flight together (they were five memory latencies in a row)
+      const uint32_t *src[5];
+#pragma unroll
+      for (int f = 0; f < 5; f++) src[f] = reinterpret_cast<const uint32_t *>(ring + (size_t)((oldest + f) % MSC_SLOTS) * e.msc_stride);
+      for (int i = lane; i < nbytes / 4; i += 64) {
+        uint32_t w[5];
+#pragma unroll
+        for (int f = 0; f < 5; f++) w[f] = src[f][i];
+#pragma unroll
+        for (int f = 0; f < 5; f++) reinterpret_cast<uint32_t *>(win + f * nbytes)[i] = w[f];
+      }
+    }
+    if (lane < 12) hdr0[lane] = 0;
+    __syncthreads();
+    if (lane < 11) hdr0[lane] = win[lane];
+    // ---- syndromes S_r(j) = XOR_k c_k alpha^(r (119 - k)), r < 10: the Horner recursion of reed_solomon.cpp:254-290 written
+    //      as a sum, lanes over the byte index k (no 120-step dependent look-up chain); only "all ten are zero" is needed
+    //      here, the full decoder below recomputes them for the code words that are not clean
+    // one code word's partial sums of this lane: ten 8-bit sums packed into three words
+    auto syn_partial = [&](int j, unsigned &a0, unsigned &a1, unsigned &a2) {
+      a0 = a1 = a2 = 0;
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+        const int k = lane + 64 * h;
+        const int b = k < 120 ? win[j + k * R] : 0;
+        if (b) {
+          const int lg = glog[b];
+#pragma unroll
+          for (int r = 0; r < 10; r++) {                      // exponents r (119 - k) mod 255: per-lane constants (syn_ex), no running sum on the look-up chain
+            const unsigned v = gexp[lg + (int)((syn_ex[h][r >> 2] >> (8 * (r & 3))) & 0xFFu)];
+            if (r < 4) a0 ^= v << (8 * r); else if (r < 8) a1 ^= v << (8 * (r - 4)); else a2 ^= v << (8 * (r - 8));
+          }
+        }
+      }
+    };
+    int cw = 0;
+    for (; cw + 1 < R; cw += 2) {                               // two code words at a time: their look-up and reduction chains interleave
+      unsigned a0, a1, a2, b0, b1, b2;
+      syn_partial(cw, a0, a1, a2);
+      syn_partial(cw + 1, b0, b1, b2);
+      a0 = wave_xor(a0); b0 = wave_xor(b0); a1 = wave_xor(a1); b1 = wave_xor(b1); a2 = wave_xor(a2); b2 = wave_xor(b2);
+      if (lane == 0) {
+        syn_or[cw] = a0 | a1 | a2; syn_or[cw + 1] = b0 | b1 | b2;
+        syn_w[cw][0] = a0; syn_w[cw][1] = a1; syn_w[cw][2] = a2; syn_w[cw + 1][0] = b0; syn_w[cw + 1][1] = b1; syn_w[cw + 1][2] = b2;
+      }
+    }
+    if (cw < R) {
+      unsigned a0, a1, a2;
+      syn_partial(cw, a0, a1, a2);
+      a0 = wave_xor(a0); a1 = wave_xor(a1); a2 = wave_xor(a2);
+      if (lane == 0) { syn_or[cw] = a0 | a1 | a2; syn_w[cw][0] = a0; syn_w[cw][1] = a1; syn_w[cw][2] = a2; }
+    }
+    __syncthreads();
+    // ---- full decoder only where needed.  Berlekamp-Massey and Forney: one lane per dirty code word, from the syndromes summed above (byte r of
+    //      syn_w[code word]: no second, 1200-step pass over the 120 bytes on one lane).  The Chien search over all 255 positions, the longest part
+    //      (255 x deg dependent table look-ups per lane), is made by the WHOLE wave for one dirty code word after the other: 4 positions per lane, the
+    //      roots collected in the order the serial loop finds them (ballot + prefix count).  At 5 dB, where most super frames have dirty code words,
+    //      the kernel went 0.178 -> 0.117 (syndromes) -> see docs/history/r06.md ms per step; at 8 dB and above nothing of this runs.
+    int my_ret = 0;
+    const bool dirty = lane < R && syn_or[lane];
+    const Gf gf{gexp, glog};
+    uint8_t lam[RS_NR + 1];
+    int deg_lambda = 0;
+    if (__builtin_amdgcn_ballot_w64(dirty)) {                  // wave-uniform: clean super frames skip all of it
+      if (dirty) {
+        rs_berlekamp_massey(reinterpret_cast<const uint8_t *>(syn_w[lane]), gf, lam, deg_lambda);
+#pragma unroll
+        for (int i = 0; i <= RS_NR; i++) s_lam[lane][i] = lam[i];
+        s_deg[lane] = (uint8_t)deg_lambda;
+      }
+      __syncthreads();
+      unsigned long long dm = __builtin_amdgcn_ballot_w64(dirty);
+      while (dm) {
+        const int c = __builtin_ctzll(dm);
+        dm &= dm - 1;
+        const int dg = s_deg[c];
+        int count = 0;
+#pragma unroll
+        for (int pass = 0; pass < 4; pass++) {
+          const int i = 64 * pass + lane + 1;
+          const bool root = i <= RS_NN && rs_chien_at(s_lam[c], dg, gexp, i) == 0;
+          const unsigned long long b = __builtin_amdgcn_ballot_w64(root);
+          const int idx = count + __builtin_popcountll(b & ((1ull << lane) - 1ull));
+          if (root && idx < RS_NR) s_root[c][idx] = (uint8_t)i;
+          count += __builtin_popcountll(b);
+        }
+        if (lane == 0) s_rootn[c] = count;
+      }
+      __syncthreads();
+      if (dirty)
+        my_ret = s_rootn[lane] != deg_lambda ? -1
+                                             : rs_forney(CwStrided{win + lane, R}, gf, reinterpret_cast<const uint8_t *>(syn_w[lane]), lam, deg_lambda, s_root[lane], s_rootn[lane]);
+    }
+    int corr = my_ret > 0 ? my_ret : 0, fail = my_ret < 0 ? 1 : 0;
+    corr = wave_sum_int(corr); fail = wave_sum_int(fail);
+    rs_corr += corr; rs_fail += fail;
+    __syncthreads();
+    if (lane == 0) {
+      uint8_t hdr[12];
+      for (int i = 0; i < 12; i++) hdr[i] = win[i];
+      const bool ok = firecode_check_and_correct(hdr, s_fc, t.fc_syndrome);   // :230-240
+      int flag = ok ? 1 : 0;
+      if (ok) {
+        bool changed = false;
+        for (int i = 0; i < 11; i++) changed = changed || (hdr[i] != hdr0[i]);
+        if (changed) flag |= 2;
+        for (int i = 0; i < 12; i++) win[i] = hdr[i];
+        // AU table, mp4processor.cpp:256-306
+        const int dac = (hdr[2] >> 6) & 1, sbr = (hdr[2] >> 5) & 1, end = 110 * R;
+        int n_au;
+        switch (2 * dac + sbr) {
+        case 0: n_au = 4; s_au[0] = 8; s_au[1] = hdr[3] * 16 + (hdr[4] >> 4); s_au[2] = (hdr[4] & 0xf) * 256 + hdr[5];
+                s_au[3] = hdr[6] * 16 + (hdr[7] >> 4); s_au[4] = end; break;
+        case 1: n_au = 2; s_au[0] = 5; s_au[1] = hdr[3] * 16 + (hdr[4] >> 4); s_au[2] = end; break;
+        case 2: n_au = 6; s_au[0] = 11; s_au[1] = hdr[3] * 16 + (hdr[4] >> 4); s_au[2] = (hdr[4] & 0xf) * 256 + hdr[5];
+                s_au[3] = hdr[6] * 16 + (hdr[7] >> 4); s_au[4] = (hdr[7] & 0xf) * 256 + hdr[8];
+                s_au[5] = hdr[9] * 16 + (hdr[10] >> 4); s_au[6] = end; break;
+        default: n_au = 3; s_au[0] = 6; s_au[1] = hdr[3] * 16 + (hdr[4] >> 4); s_au[2] = (hdr[4] & 0xf) * 256 + hdr[5];
+                s_au[3] = end; break;
+        }
+        s_au[7] = n_au;
+      }
+      s_flag = flag;
+    }
+    __syncthreads();
+    const int flag = s_flag;
+    if (flag & 1) {                          // :149-158
+      if (flag & 2) fc_corr++;
+      sf_sync = 4; sf_ok++;
+      const int n_au = s_au[7];
+      // :318-333 AU CRCs.  The CRC register is linear in the message: every lane runs the table recursion over its own
+      // slice from state 0, the slice results are moved to the end of the AU by multiplying with x^(8 n) mod P
+      // (crc_xpow, in LDS) and XOR-ed together; the 0xFFFF start value rides on the first two bytes -- calc_crc (crc.cpp:75-86)
+      // without a several-hundred-step look-up chain on one lane.
+      int good = 0, bad = 0;
+      unsigned crc_mask = 0, len_mask = 0;     // per access unit: passed its CRC / failed the length check (dabx_superframe_info)
+      for (int a = 0; a < n_au; a++) {
+        const int st = s_au[a], len = s_au[a + 1] - st - 2;
+        if (len > 960 || len < 0 || st + len + 2 > 110 * R) { bad++; len_mask |= 1u << a; continue; }
+        const int per = (len + 63) >> 6, from = lane * per, to = min(len, from + per);
+        const unsigned xp_slice = s_xpow[from < to ? len - to : 0];
+        // The 0xFFFF start value of a 16-bit CRC is the same as complementing the first two message bytes and starting from 0
+        // (the register only ever shifts the start value through those two steps): the lanes that own bytes 0 and 1 do that, and
+        // the second crc_mulmod that lane 0 ran for the start value's contribution -- with the other 63 lanes waiting -- is gone.
+        const unsigned first2 = len >= 2 ? 0xFFu : 0u;
+        unsigned crc = 0;
+        for (int i = from; i < to; i++) crc = (s_crc[(win[st + i] ^ (i < 2 ? first2 : 0u) ^ (crc >> 8)) & 0xFF] ^ (crc << 8)) & 0xFFFFu;
+        unsigned acc = from < to ? crc_mulmod(crc, xp_slice) : 0u;
+        if (len < 2 && lane == 0) acc ^= crc_mulmod(0xFFFFu, s_xpow[len]);      // a message shorter than the register: the start value's contribution as it was
+        acc = wave_xor(acc);
+        const unsigned want = ((unsigned)win[st + len] << 8) | win[st + len + 1];
+        if (((~acc) & 0xFFFFu) == want) { good++; crc_mask |= 1u << a; } else bad++;
+      }
+      au_ok += good; au_bad += bad;
+      if (lane == 0 && e.sf_info) {            // what _process_super_frame knows when it hands the access units on (mp4processor.cpp:256-333)
+        dabx_superframe_info r;
+        r.num_aus = (uint8_t)n_au; r.au_crc_ok = (uint8_t)crc_mask; r.au_len_bad = (uint8_t)len_mask; r.stream_parms = (uint8_t)(win[2] & 0x7F);
+#pragma unroll
+        for (int a = 0; a < 7; a++) r.au_start[a] = a <= n_au ? (uint16_t)s_au[a] : (uint16_t)0;
+        r.rs_corrected = (uint16_t)corr; r.rs_failed = (uint8_t)fail; r.fc_corrected = (flag & 2) ? 1 : 0; r.reserved = 0;
+        r.first_frame = oldest;
+        e.sf_info[((size_t)s * e.max_subch + j) * SF_SLOTS + (size_t)(sf_count % SF_SLOTS)] = r;
+      }
+      uint8_t *sfo = e.sf_out + (((size_t)s * e.max_subch + j) * SF_SLOTS + (size_t)(sf_count % SF_SLOTS)) * e.sf_stride;
+      for (int i = lane; i < (110 * R + 3) / 4; i += 64)
+        reinterpret_cast<uint32_t *>(sfo)[i] = reinterpret_cast<const uint32_t *>(win)[i];
+      sf_count++;
+    } else {                                 // :159-169
+      sf_sync--;
+      if (sf_sync == 0) { blocks_in_buf = 4; sf_fail++; }
+    }
+  }
+  if (lane == 0) {
+    sc.cif_out = cif_out; sc.blocks_in_buf = blocks_in_buf; sc.sf_sync = sf_sync; sc.sf_count = sf_count;
+    sc.sf_ok += sf_ok; sc.sf_fail += sf_fail; sc.rs_corr += rs_corr; sc.rs_fail += rs_fail;
+    sc.fc_corr += fc_corr; sc.au_ok += au_ok; sc.au_bad += au_bad;
+  }
+}
+
+// ------------------------------------------------------------------------------------------ packet mode
+// One wave per packet-mode slot (PacketDev::slots: those slots only); walks the logical frames the decoder produced in this batch step
+// (msc_new_frames, pipeline.h), in order, numbered from the slot's cif_out (it runs in front of k_dabplus, which moves cif_out on).  Per frame: the frame is
+// staged in LDS; lane g reads the length code of granule g and the packet boundaries follow from two ballots (pkt_walk: scalar), and runs the
+// CCITT register over its granule; the lanes at packet starts fold the packet CRC from their granules' registers and, for packets that pass
+// it, the register over the payload from 0 (pkt_describe: all packets of the frame in parallel, tables in LDS); the state machine (data_processor.cpp:165-253) then runs wave-uniform over header fields only --
+// the data-group CRC register is carried from packet to packet with one multiplication by x^(8 n) -- and every accepted payload is copied
+// by the whole wave to its place in the slot's byte ring.  include/dabx.h states the semantics and the two guards.
+__global__ __launch_bounds__(64) void k_packet(PacketDev pk)
+{
+  const int lane = threadIdx.x;
+  PacketSlot &ps = pk.slots[blockIdx.x];
+  const SubchDev &sc = pk.subch[(size_t)ps.s * pk.max_subch + ps.j];
+  if (!sc.active) return;
+  const BatchSnap bs = pk.snap[ps.s];
+  const long long n_new = msc_new_frames(bs.msc_done, bs.cif_no, sc.start_cif).n;   // logical frames the decoder just produced for this sub-channel
+  if (n_new == 0) return;
+  const int nbytes = 3 * sc.kbps, n_gran = sc.kbps / 8;       // <= 1152 bytes, <= 48 granules (dabx_set_packet_mode)
+  const uint8_t *ring = pk.msc_out + ((size_t)ps.s * pk.max_subch + ps.j) * MSC_SLOTS * pk.msc_stride;
+  __shared__ __attribute__((aligned(16))) uint8_t frm[3 * PKT_MAX_KBPS];
+  __shared__ uint16_t s_crc[256], s_xpow[128];               // CCITT table; x^(8 m) mod P for m = useful length <= 127
+  __shared__ unsigned s_info[64];
+  __shared__ uint16_t s_part[64];                             // the CCITT register from 0 over every granule of the frame
+  for (int i = lane; i < 256; i += 64) s_crc[i] = pk.crc_ccitt[i];
+  for (int i = lane; i < 128; i += 64) s_xpow[i] = pk.crc_xpow[i];
+  const int address = ps.address;
+  uint8_t *const dg_ring = ps.out.bytes;                         // (locals: the stores below must not make the loop reload them from the table)
+  dabx_datagroup_info *const dg_recs = ps.out.recs;
+  const unsigned long long bytes_mask = ps.out.bytes_mask, rec_mask = ps.out.rec_mask;
+  int expected = ps.expected, state = ps.state, fill = ps.fill, first_byte = ps.first_byte;
+  unsigned run_crc = ps.run_crc;
+  long long first_frame = ps.first_frame, dg_count = ps.out.count, dg_bytes = ps.out.n_bytes;
+  long long packets = 0, addr_match = 0, continuity_err = 0, crc_bad = 0, len_bad = 0, walk_short = 0, dg_crc_bad = 0, dg_overflow = 0;
+  const long long frame0 = sc.cif_out;
+  for (long long n = 0; n < n_new; n++) {
+    const long long frame = frame0 + n;      // index of the logical frame in the slot's sequence
+    slot_stage_frame(frm, ring, pk.msc_stride, frame, nbytes, lane);
+    const unsigned code = lane < n_gran ? (unsigned)(frm[lane * PKT_GRANULE] >> 6) : 0u;
+    s_part[lane] = lane < n_gran ? (uint16_t)pkt_granule_crc(frm, lane, s_crc) : (uint16_t)0;
+    bool short_walk;
+    const unsigned long long starts = pkt_walk(__ballot(code & 1u), __ballot(code & 2u), n_gran, &short_walk);
+    __syncthreads();
+    s_info[lane] = ((starts >> lane) & 1ull) ? pkt_describe(frm, lane, nbytes, address, s_crc, s_part, s_xpow) : 0u;
+    __syncthreads();
+    packets += __popcll(starts);
+    walk_short += short_walk ? 1 : 0;
+    for (unsigned long long m = starts; m; m &= m - 1) {
+      const int g = __ffsll((long long)m) - 1;
+      const unsigned inf = s_info[g];
+      if (!(inf & 1u)) continue;                                                            // :165 another address
+      addr_match++;
+      if ((int)((inf >> 3) & 3u) != expected) { continuity_err++; expected = 0; continue; }   // :170-178
+      expected = (expected + 1) & 3;                                                        // :181, before the CRC
+      if (!(inf & 2u)) { crc_bad++; continue; }                                             // :184-187
+      if (!(inf & 4u)) { len_bad++; continue; }                                             // guard: the payload would pass the end of the logical frame
+      const int fl = (int)((inf >> 5) & 3u), ulen = (int)((inf >> 7) & 0x7Fu);
+      bool start = false, append = false, emit = false;
+      if (state == 0) {                                                                     // :191-215 waiting for a start
+        if (fl == 2) { start = true; state = 1; }
+        else if (fl == 3) { start = true; emit = true; }
+        else fill = 0;
+      } else {                                                                              // :216-253 within a series
+        if (fl == 0) append = true;
+        else if (fl == 1) { append = true; emit = true; }
+        else if (fl == 2) start = true;
+        else { state = 0; fill = 0; }
+      }
+      if (append && fill + ulen > DABX_DG_MAX_BYTES) { dg_overflow++; state = 0; fill = 0; continue; }   // guard: bounded assembly
+      if (start) { fill = 0; run_crc = 0xFFFFu; first_frame = frame; first_byte = -1; }
+      if (start || append) {
+        const int from = g * PKT_GRANULE + 3;
+        for (int i = lane; i < ulen; i += 64) dg_ring[(size_t)((unsigned long long)(dg_bytes + fill + i) & bytes_mask)] = frm[from + i];
+        if (fill == 0 && ulen > 0) first_byte = frm[from];
+        run_crc = crc_mulmod(run_crc, s_xpow[ulen]) ^ (inf >> 16);
+        fill += ulen;
+      }
+      if (emit) {
+        const bool flag = first_byte >= 0 && (first_byte & 0x40);
+        const bool good = flag && fill >= 2 && run_crc == PKT_CRC_RESIDUE;
+        if (lane == 0) {
+          dabx_datagroup_info r;
+          r.byte_pos = dg_bytes; r.first_frame = first_frame; r.last_frame = frame; r.length = (uint16_t)fill;
+          r.crc_flag = flag ? 1 : 0; r.crc_ok = good ? 1 : 0; r.reserved = 0;
+          dg_recs[(size_t)((unsigned long long)dg_count & rec_mask)] = r;
+        }
+        dg_crc_bad += (flag && !good) ? 1 : 0;
+        dg_count++; dg_bytes += fill;
+        fill = 0; state = 0;
+      }
+    }
+  }
+  if (lane == 0) {
+    ps.expected = expected; ps.state = state; ps.fill = fill; ps.first_byte = first_byte; ps.run_crc = run_crc;
+    ps.first_frame = first_frame; ps.out.count = dg_count; ps.out.n_bytes = dg_bytes;
+    ps.frames += n_new; ps.packets += packets; ps.addr_match += addr_match; ps.continuity_err += continuity_err; ps.crc_bad += crc_bad;
+    ps.len_bad += len_bad; ps.walk_short += walk_short; ps.dg_crc_bad += dg_crc_bad; ps.dg_overflow += dg_overflow;
+  }
+}
+
+// --------------------------------------------------------------------------------------------------- PAD
+// One wave per PAD-enabled DAB+ slot (PadDev::slots: those slots only), behind k_dabplus: walks the super frames k_dabplus has completed
+// since the slot's last visit (SubchDev::sf_count against PadSlot::sf_seen: a batch adds at most 6, the rings hold SF_SLOTS) out of the
+// super-frame ring and their dabx_superframe_info records, and of every access unit that passed its CRC the data stream element
+// (mp4processor.cpp:345-353).  The PAD bytes (<= 255) are staged REVERSED in LDS, so that PadHandler's iBuffer[iLast - k] is xp[k] and a
+// sub-field is a forward run of bytes; the state machine (pad_core.h: pad_handler.cpp:67-519 line by line) runs wave-uniform on header
+// bytes, the whole wave copies sub-fields straight to their place in the slot's byte ring -- the group under assembly lives where the
+// completed group will be -- and the data-group CRC at completion is folded from per-lane slices.  The dynamic label's text and the
+// short X-PAD's bytes are in LDS for the launch.  include/dabx.h states the semantics and the guards G1..G4.
+__global__ __launch_bounds__(64) void k_pad(PadDev pd)
+{
+  const int lane = threadIdx.x;
+  PadSlot &ps = pd.slots[blockIdx.x];
+  const size_t sj = (size_t)ps.s * pd.max_subch + ps.j;
+  const SubchDev &sc = pd.subch[sj];
+  if (!sc.active || !sc.dab_plus) return;
+  const long long have = sc.sf_count;
+  long long seen = ps.sf_seen;
+  if (have <= seen) return;
+  if (have - seen > SF_SLOTS) seen = have - SF_SLOTS;         // (cannot happen: the stage runs behind every batch)
+  const int end = 110 * (sc.kbps / 8);
+  __shared__ PadLds lds;                                       // lds.rb: the AU's PAD reversed, rb[k] = buffer[count - 1 - k]
+  PadWave w;
+  pad_wave_open(w, ps, pd, lds, lane);
+  __syncthreads();
+  for (long long sf = seen; sf < have; sf++) {
+    const size_t slot = sj * SF_SLOTS + (size_t)(sf % SF_SLOTS);
+    const dabx_superframe_info *inf = pd.sf_info + slot;
+    const uint8_t *sfb = pd.sf_out + slot * pd.sf_stride;
+    const int n_au = min((int)inf->num_aus, 6);
+    const unsigned take = (unsigned)inf->au_crc_ok & ~(unsigned)inf->au_len_bad;
+    w.frame = inf->first_frame;
+    w.c.superframes++;
+    for (int a = 0; a < n_au; a++) {                           // mp4processor.cpp:320
+      if (!((take >> a) & 1u)) continue;                       // :325, :333
+      w.c.aus++;
+      const int st = inf->au_start[a];
+      if (st >= end || ((sfb[st] >> 5) & 7) != 4) continue;    // :345
+      w.c.pad_aus++;
+      if (st + 2 > end) { w.c.pad_bad++; continue; }           // G1
+      const int count = sfb[st + 1];                           // :347
+      if (count < 2 || st + 2 + count > end) { w.c.pad_bad++; continue; }      // G1
+      __syncthreads();                                         // the previous AU's bytes are done with
+      for (int k = lane; k < count; k += 64) lds.rb[k] = sfb[st + 2 + count - 1 - k];      // :349-351
+      __syncthreads();
+      w.au = a;
+      pad_process(w, lds.rb, count);                           // :352
+    }
+  }
+  pad_wave_close(w, ps, lds, lane);
+  if (lane == 0) ps.sf_seen = have;
+}
+
+// One wave per PAD slot whose source is the MP2 frames of a DAB audio sub-channel (PadSlot::source; the blocks of the other slots of the
+// table return at once, as k_pad's do for these), behind k_dabplus, which has moved the slots' frame counters on: walks the logical frames
+// the decoder produced in this batch step, the frames k_packet walks (msc_new_frames, pipeline.h) in its numbering.  Per frame: the frame
+// is staged in LDS and Mp2Processor::add_to_frame (mp2processor.cpp:678-747) runs over its 24 kbps bits as a handful of wave-uniform phase
+// changes -- at most one completed MP2 frame (:691: lf is at least a logical frame's bits) and two searches -- the search for the 12 ones
+// being one wave-wide pass (mp2_find_sync).  When an MP2 frame completes, _process_pad_data (:611-674) takes the PAD from the end of the
+// CURRENT logical frame (:695): F-PAD in the last two bytes, the X-PAD in front of the ScF-CRC, staged reversed as k_pad stages it and
+// handed to the same pad_process.  Only the newest 254 X-PAD bytes are staged: PadHandler reads at most 196 below iLast.
+__global__ __launch_bounds__(64) void k_pad_mp2(PadDev pd)
+{
+  const int lane = threadIdx.x;
+  PadSlot &ps = pd.slots[blockIdx.x];
+  if (ps.source != DABX_PAD_SOURCE_MP2) return;
+  const size_t sj = (size_t)ps.s * pd.max_subch + ps.j;
+  const SubchDev &sc = pd.subch[sj];
+  if (!sc.active || sc.dab_plus) return;
+  const BatchSnap bs = pd.snap[ps.s];
+  const long long n_new = msc_new_frames(bs.msc_done, bs.cif_no, sc.start_cif).n;   // logical frames the decoder just produced for this sub-channel
+  if (n_new == 0) return;
+  const int nbytes = 3 * sc.kbps, nbits = 8 * nbytes;          // <= 1152 bytes (dabx_set_pad_mode); MP2framesize = 24 * bitRate (:236)
+  const int v_len = nbytes - (sc.kbps >= 56 ? 4 : 2) - 2;       // :613-621
+  const int n_stage = min(v_len, 254);
+  const uint8_t *ring = pd.msc_out + sj * MSC_SLOTS * pd.msc_stride;
+  __shared__ __attribute__((aligned(16))) uint8_t frm[3 * PKT_MAX_KBPS];
+  __shared__ PadLds lds;                                       // lds.rb: rb[0] = L0, rb[1] = L1, rb[2 + k] = frame[vLen - 1 - k]
+  PadWave w;
+  pad_wave_open(w, ps, pd, lds, lane);
+  Mp2State m = ps.m;
+  const long long frame0 = sc.cif_out - n_new;
+  for (long long n = 0; n < n_new; n++) {
+    w.frame = frame0 + n;                     // index of the logical frame in the slot's sequence
+    slot_stage_frame(frm, ring, pd.msc_stride, w.frame, nbytes, lane);
+    w.c.superframes++;                        // (dabx_pad_stats of an MP2 source slot: logical frames walked)
+    int pos = 0;                              // :685 i
+    while (pos < nbits) {
+      if (m.state == MP2_GET_DATA) {                             // :687-714
+        const int lf = m.sample_rate == 48000 ? nbits : 2 * nbits;      // :680, :741
+        const int need = lf - m.bit_count;                       // (>= 1: a frame that completes leaves the state)
+        if (need > nbits - pos) { m.bit_count += nbits - pos; break; }
+        pos += need;                                             // :691 the MP2 frame is complete with bit pos - 1
+        m.frames++;
+        w.c.aus++; w.c.pad_aus++;                                // :695 _process_pad_data(iBits): the PAD at the end of THIS logical frame
+        const unsigned l1 = pad_u(frm[nbytes - 2]);              // :624
+        const int count = (((l1 >> 4) & 3) == 1 ? 4 : n_stage) + 2;     // :649-657; F-PAD type and the indicators 0 and 3: pad_process (:629-645)
+        __syncthreads();                                         // the previous PAD's bytes are done with
+        if (lane < 2) lds.rb[lane] = frm[nbytes - 1 - lane];     // :623-624 L0, L1
+        for (int k = lane; k < n_stage; k += 64) lds.rb[2 + k] = frm[v_len - 1 - k]; // :660-673 pPadData[vLengthBytes - 1 - k]
+        __syncthreads();
+        pad_process(w, lds.rb, count);                           // :673 process_PAD(pPadData, vLengthBytes - 1, L1, L0)
+        m.state = MP2_SEARCHING; m.header_count = 0; m.bit_count = 0;   // :710-712
+      } else if (m.state == MP2_SEARCHING) {                     // :715-734
+        int run;
+        const int p = mp2_find_sync(frm, nbits, pos, m.header_count, lane, &run);
+        if (p < 0) { m.header_count = run; break; }              // :720, :732 to the end of the frame
+        m.syncs++; m.last_sync_bit = p;
+        m.header_count = 12; m.bit_count = 12; m.header = 0;     // :720-726
+        m.state = MP2_GET_RATE;                                  // :727
+        pos = p + 1;
+      } else {                                                   // :735-744
+        const int k = min(24 - m.bit_count, nbits - pos);
+        m.header = (m.header << k) | (int)mp2_bits(frm, nbytes, pos, k);       // :737
+        m.bit_count += k; pos += k;
+        if (m.bit_count == 24) {                                 // :738
+          mp2_header(m);                                         // :740
+          m.state = MP2_GET_DATA;                                // :742
+        }
+      }
+    }
+  }
+  pad_wave_close(w, ps, lds, lane);
+  if (lane == 0) ps.m = m;
+}
+
+// ---------------------------------------------------------------------------------------------- launchers
+// One per stage, on the stream launch_msc_batch gives them.  The packet and PAD launchers take the engine's job table (null or n = 0: the
+// engine has no such slot, no launch), fill in what the kernel reads of the engine and leave the argument they launched with in *used for
+// the delivery's gather of the same slots (deliver.hip); used->n = 0 says that nothing ran.
+__global__ void k_msc_done(EngineDev e)
+{
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s < e.n_streams) e.ctl[s].msc_done_cif = e.snap[s].cif_no;
+}
+
+// every slot of the engine; closes the batch: msc_done_cif moves up to the snapshot's cif_no
+int launch_dabplus_stage(const EngineDev &e, hipStream_t st, Marker &mk)
+{
+  const DevTables *t;
+  int rc = get_tables(&t);
+  if (rc) return rc;
+  mk.begin(9, st);
+  hipLaunchKernelGGL(k_dabplus, dim3(e.n_streams * e.max_subch), dim3(64), 0, st, e, *t);
+  hipLaunchKernelGGL(k_msc_done, dim3((e.n_streams + 255) / 256), dim3(256), 0, st, e);
+  mk.end(9, st);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+
+// in front of k_dabplus, which moves the slots' frame counters on
+int launch_packet_stage(const EngineDev &e, const PacketDev *pk, hipStream_t st, Marker &mk, PacketDev *used)
+{
+  *used = PacketDev{};
+  if (!pk || pk->n <= 0) return 0;
+  const DevTables *t;
+  int rc = get_tables(&t);
+  if (rc) return rc;
+  PacketDev p = *pk;
+  p.max_subch = e.max_subch; p.msc_stride = e.msc_stride; p.subch = e.subch; p.snap = e.snap; p.msc_out = e.msc_out;
+  p.crc_ccitt = t->crc_ccitt; p.crc_xpow = t->crc_xpow;
+  mk.begin(11, st);
+  hipLaunchKernelGGL(k_packet, dim3(p.n), dim3(64), 0, st, p);
+  mk.end(11, st);
+  DABX_HIP(hipGetLastError());
+  *used = p;
+  return 0;
+}
+
+// behind k_dabplus: k_pad walks the super frames it has just completed for the DAB+ slots, k_pad_mp2 the batch's logical frames of the slots
+// whose source is MP2 (pad->n_mp2 of the pad->n), each launched only when it has a slot, both inside marker 12
+int launch_pad_stage(const EngineDev &e, const PadDev *pad, hipStream_t st, Marker &mk, PadDev *used)
+{
+  *used = PadDev{};
+  if (!pad || pad->n <= 0) return 0;
+  const DevTables *t;
+  int rc = get_tables(&t);
+  if (rc) return rc;
+  PadDev q = *pad;
+  q.max_subch = e.max_subch; q.sf_stride = e.sf_stride; q.subch = e.subch; q.sf_out = e.sf_out; q.sf_info = e.sf_info;
+  q.crc_ccitt = t->crc_ccitt; q.crc_xpow = t->crc_xpow;
+  q.msc_stride = e.msc_stride; q.snap = e.snap; q.msc_out = e.msc_out;
+  mk.begin(12, st);
+  if (q.n > q.n_mp2) hipLaunchKernelGGL(k_pad, dim3(q.n), dim3(64), 0, st, q);
+  if (q.n_mp2 > 0) hipLaunchKernelGGL(k_pad_mp2, dim3(q.n), dim3(64), 0, st, q);
+  mk.end(12, st);
+  DABX_HIP(hipGetLastError());
+  *used = q;
+  return 0;
+}
+
+}  // namespace dabx

@@ -1,4 +1,4 @@
-// packet_core.h -- packet-mode data sub-channels: the per-slot state, the argument of k_packet (pipeline.hip) and its device helpers.
+// packet_core.h -- packet-mode data sub-channels: the per-slot state, the argument of k_packet (msc_stages.hip) and its device helpers.
 // DataProcessor (base/backend/data/data_processor.cpp:106-254): packet walk, address filter, continuity index, packet CRC and the
 // assembly of the MSC data groups.  include/dabx.h "Packet-mode data sub-channels" states the semantics and the two guards.
 #pragma once
@@ -31,7 +31,7 @@ struct PacketSlot {
 };
 
 // k_packet's argument, by value: the job table and what the kernel reads of the engine (the MSC batch's snapshot, the slots' descriptions
-// and the ring of logical frames; launch_msc_batch fills those in).
+// and the ring of logical frames; launch_packet_stage fills those in).
 struct PacketDev {
   PacketSlot *slots;
   int32_t n;                      // packet-mode slots = blocks of one wave
@@ -47,6 +47,17 @@ constexpr int PKT_GRANULE = 24;
 constexpr unsigned PKT_CRC_RESIDUE = 0x1D0Fu;          // the CCITT register (start 0xFFFF) after a message followed by its complemented CRC
 
 #ifdef __HIPCC__
+// Stages logical frame f of a slot in LDS for its wave (k_packet, k_pad_mp2): `ring` = the slot's MSC_SLOTS frames in msc_out, nbytes = 3 kbps
+// <= 3 * PKT_MAX_KBPS, a multiple of 4.  The barrier in front says the previous frame (and whatever else the wave put into LDS) is done with,
+// the one behind that the frame is there.
+__device__ __forceinline__ void slot_stage_frame(uint8_t *frm, const uint8_t *ring, int msc_stride, long long f, int nbytes, int lane)
+{
+  __syncthreads();
+  const uint32_t *src = reinterpret_cast<const uint32_t *>(ring + (size_t)(f % MSC_SLOTS) * msc_stride);
+  for (int i = lane; i < nbytes / 4; i += 64) reinterpret_cast<uint32_t *>(frm)[i] = src[i];
+  __syncthreads();
+}
+
 // the packets of one logical frame (data_processor.cpp:123-150) from the length codes of its granules: bit g of the result = a packet starts
 // at granule g.  b0 / b1 = the two bits of every granule's first byte's length code as lane masks; wave-uniform, scalar work.  *walk_short:
 // the walk ended at a packet that needs more bytes than remain (:129-133).

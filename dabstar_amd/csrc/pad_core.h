@@ -1,5 +1,5 @@
 // pad_core.h -- programme-associated data of DAB+ access units and of DAB (MP2) audio frames: the per-slot state, the argument of k_pad and
-// k_pad_mp2 (pipeline.hip) and their device helpers.  mp4processor.cpp:345-353 (the data stream element of an access unit) and PadHandler (base/backend/data/pad_handler.cpp:67-547):
+// k_pad_mp2 (msc_stages.hip) and their device helpers.  mp4processor.cpp:345-353 (the data stream element of an access unit) and PadHandler (base/backend/data/pad_handler.cpp:67-547):
 // F-PAD dispatch, short and variable X-PAD, the dynamic label, the data-group length indicator and the assembly of the X-PAD MSC data
 // groups, up to the two hand-over points (the label's bytes in front of the charset conversion, the data group in front of the MOT
 // parser).  include/dabx.h "Programme-associated data" states the semantics and the four guards G1..G4.  For a DAB (MP2) slot the front of
@@ -90,7 +90,7 @@ struct PadSlot {
   Mp2State m;
 };
 
-// k_pad's and k_pad_mp2's argument, by value: the job table and what the kernel reads of the engine (launch_msc_batch fills those in).
+// k_pad's and k_pad_mp2's argument, by value: the job table and what the kernel reads of the engine (launch_pad_stage fills those in).
 struct PadDev {
   PadSlot *slots;
   int32_t n;                      // PAD slots = blocks of one wave
@@ -120,6 +120,35 @@ struct PadWave {
   uint8_t *text, *shortd;         // LDS: dl_text, short_data
   const uint16_t *s_crc, *s_xpow; // LDS: CCITT table, x^(8 m) mod P for m < 1024
 };
+
+// The wave's LDS, declared __shared__ by the kernel: the PAD bytes being walked and the slot's tables for the launch.
+struct PadLds {
+  __attribute__((aligned(16))) uint16_t xpow[1024];              // x^(8 m) mod P
+  uint16_t crc[256];                                             // CCITT table
+  uint8_t rb[256];                                               // the PAD reversed: rb[0] = L0, rb[1] = L1, rb[2 + k] = the X-PAD from its end (pad_process)
+  uint8_t text[DABX_DL_MAX_BYTES], shortd[16];                   // PadSlot::dl_text, short_data
+};
+// Opens the slot for the launch: tables and the slot's label text and short X-PAD bytes into LDS (the caller's next barrier publishes them),
+// PadHandler's state and the output rings' cursors into registers.  pad_wave_close puts back what the launch changed; whatever else a
+// kernel keeps per slot (k_pad: sf_seen, k_pad_mp2: m) is its own to store.
+__device__ __forceinline__ void pad_wave_open(PadWave &w, const PadSlot &ps, const PadDev &pd, PadLds &lds, int lane)
+{
+  static_assert(DABX_DL_MAX_BYTES == 256, "pad_core.h: the label text is loaded beside the 256-entry CCITT table");
+  for (int i = lane; i < 256; i += 64) { lds.crc[i] = pd.crc_ccitt[i]; lds.text[i] = ps.dl_text[i]; }
+  for (int i = lane; i < 128; i += 64) reinterpret_cast<uint4 *>(lds.xpow)[i] = reinterpret_cast<const uint4 *>(pd.crc_xpow)[i];
+  if (lane < 16) lds.shortd[lane] = ps.short_data[lane];
+  w.h = ps.h; w.c = ps.c;
+  w.ring = ps.out.bytes; w.items = ps.out.recs; w.bytes_mask = ps.out.bytes_mask; w.item_mask = ps.out.rec_mask;
+  w.n_items = ps.out.count; w.n_bytes = ps.out.n_bytes;
+  w.lane = lane; w.au = 0; w.text = lds.text; w.shortd = lds.shortd; w.s_crc = lds.crc; w.s_xpow = lds.xpow;
+}
+__device__ __forceinline__ void pad_wave_close(const PadWave &w, PadSlot &ps, const PadLds &lds, int lane)
+{
+  __syncthreads();
+  for (int i = lane; i < DABX_DL_MAX_BYTES; i += 64) ps.dl_text[i] = lds.text[i];
+  if (lane < 16) ps.short_data[lane] = lds.shortd[lane];
+  if (lane == 0) { ps.h = w.h; ps.c = w.c; ps.out.count = w.n_items; ps.out.n_bytes = w.n_bytes; }
+}
 
 __device__ __forceinline__ unsigned pad_u(unsigned v) { return (unsigned)__builtin_amdgcn_readfirstlane((int)v); }
 __device__ __forceinline__ unsigned pad_crc_step(unsigned c, unsigned b, const uint16_t *s_crc) { return (s_crc[(b ^ (c >> 8)) & 0xFF] ^ (c << 8)) & 0xFFFFu; }

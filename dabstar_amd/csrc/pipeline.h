@@ -1,4 +1,4 @@
-// pipeline.h -- device-resident state of the stream-batched receiver (engine.hip / pipeline.hip).
+// pipeline.h -- device-resident state of the stream-batched receiver (engine.cpp / pipeline.hip / msc_stages.hip).
 #pragma once
 #include "dabx_internal.h"
 #include "ring_fmt.h"
@@ -266,7 +266,41 @@ struct MscJob {
   long long out_idx;    // index of the logical frame in the sub-channel's output ring
 };
 
+// ---- the new-frames rule: which CIFs of a batch give a slot a logical frame ------------------------------------
+// A slot configured at CIF start_cif has its time de-interleaver filled 16 CIFs later (backend.cpp:146-150): logical frame i of the slot
+// belongs to CIF msc_first_cif(start_cif) + i.
+constexpr __host__ __device__ long long msc_first_cif(long long start_cif) { return start_cif + 16; }
+// Of the CIFs [msc_done, cif_no) of a batch snapshot (BatchSnap), the slot gets a logical frame for r0 .. r0 + n - 1.  Everything that walks
+// the batch's logical frames of a slot behind the decoder -- k_dabplus, k_packet, k_pad_mp2 (msc_stages.hip), deliver_lf_range
+// (deliver.hip) -- counts them with this function.
+struct NewFrames { long long r0, n; };
+constexpr __host__ __device__ NewFrames msc_new_frames(long long msc_done, long long cif_no, long long start_cif)
+{
+  const long long r0 = msc_done > msc_first_cif(start_cif) ? msc_done : msc_first_cif(start_cif);
+  return NewFrames{r0, cif_no > r0 ? cif_no - r0 : 0};
+}
+// the rule CIF by CIF against the closed form, for the asserts below: a wrong edit of either stops the build
+constexpr bool msc_new_frames_holds(long long msc_done, long long cif_no, long long start_cif)
+{
+  long long n = 0, first = -1;
+  for (long long r = msc_done; r < cif_no; r++)
+    if (r >= msc_first_cif(start_cif)) { if (n == 0) first = r; n++; }
+  const NewFrames q = msc_new_frames(msc_done, cif_no, start_cif);
+  return q.n == n && (n == 0 || q.r0 == first);
+}
+static_assert(msc_new_frames_holds(100, 128, 120) && msc_new_frames(100, 128, 120).n == 0, "pipeline.h: batch wholly before start_cif + 16");
+static_assert(msc_new_frames_holds(100, 128, 97) && msc_new_frames(100, 128, 97).n == 15, "pipeline.h: start_cif + 16 in the middle of the batch");
+static_assert(msc_new_frames_holds(100, 128, 84) && msc_new_frames(100, 128, 84).n == 28, "pipeline.h: start_cif + 16 at the batch's first CIF");
+static_assert(msc_new_frames_holds(100, 128, 111) && msc_new_frames(100, 128, 111).n == 1, "pipeline.h: start_cif + 16 at the batch's last CIF");
+static_assert(msc_new_frames_holds(100, 128, 112) && msc_new_frames(100, 128, 112).n == 0, "pipeline.h: start_cif + 16 one past the batch");
+static_assert(msc_new_frames_holds(128, 128, 0) && msc_new_frames(128, 128, 0).n == 0, "pipeline.h: empty batch");
+static_assert(msc_new_frames_holds(128, 128, 120) && msc_new_frames(128, 128, 120).n == 0, "pipeline.h: empty batch in front of start_cif + 16");
+static_assert(msc_new_frames_holds(100, 128, 0) && msc_new_frames(100, 128, 0).r0 == 100 && msc_new_frames(100, 128, 0).n == 28, "pipeline.h: slot older than the batch");
+
 #ifdef __HIPCC__
+// msc_job and msc_class_job below state the same rule per job -- is CIF msc_done + k one of the slot's new frames, and which logical frame of
+// the slot is it -- in their own arithmetic, twice: k_msc_prep and k_msc_vitT, the two hottest kernels, change their register allocation
+// with any other spelling of these lines, a common helper included (docs/history/slot_stages.md).
 __device__ __forceinline__ MscJob msc_job(const EngineDev &e, int J, int cifs)
 {
   MscJob q;
@@ -280,7 +314,7 @@ __device__ __forceinline__ MscJob msc_job(const EngineDev &e, int J, int cifs)
   const BatchSnap c = e.snap[q.s];
   const SubchDev &sc = e.subch[(size_t)q.s * e.max_subch + q.j];
   q.r = c.msc_done + q.k;
-  const long long valid_from = sc.start_cif + 16;                 // de-interleaver filled, backend.cpp:146-150
+  const long long valid_from = sc.start_cif + 16;                 // msc_first_cif: de-interleaver filled, backend.cpp:146-150
   q.valid = sc.active && q.r < c.cif_no && q.r >= valid_from;
   q.out_idx = sc.cif_out + (q.r - (c.msc_done > valid_from ? c.msc_done : valid_from));
   return q;
