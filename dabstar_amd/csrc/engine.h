@@ -1,0 +1,228 @@
+// engine.h -- internal: struct dabx_engine with its delivery, ingest and job-table parts, and what the engine*.cpp files share.
+#pragma once
+#include "pipeline.h"
+#include "packet_core.h"
+#include "pad_core.h"
+#include "sdma.h"
+#include "iqfile.h"
+#include <algorithm>
+#include <condition_variable>
+#include <deque>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+using namespace dabx;                          // (a header of engine.cpp and the engine_*.cpp files only)
+
+static constexpr int DL_FRAMES = MSC_BATCH_FRAMES;                 // a chunk = what one MSC batch decodes (the default slab of the bulk ingest too)
+
+// Bulk delivery (include/dabx.h): host slabs (page-locked) the chunks land in, device slabs they are packed into, and the copier --
+// a thread of the library that waits (polling every 50 us) for a chunk's gather kernels and then moves the slab with ONE SDMA
+// transfer (sdma.h: the HIP runtime's own device-to-host copy is a shader copy that stalls the receiver's kernels while it runs).
+struct Delivery {
+  bool open = false;
+  int what = 0;
+  int copy_engine = 0;                           // dabx_delivery_config.copy_engine: 0 SDMA through the HSA runtime, 1 hipMemcpyAsync
+  static constexpr int NDEV = 3;                 // device slabs: chunk n + 3 is packed into the slab of chunk n once its copy has left
+  uint8_t *dev[NDEV] = {nullptr, nullptr, nullptr};
+  hipEvent_t packed[NDEV] = {nullptr, nullptr, nullptr};    // the chunk's gather kernels have finished (system-scope release; the copier polls them)
+  hipEvent_t packed_lf[NDEV] = {nullptr, nullptr, nullptr}; // ... its logical frames (the slab's tail, [off_msc, bytes)) are in the slab: that share of the
+                                                            // transfer starts while the DAB+ stage still runs (round 6)
+  bool dev_busy[NDEV] = {false, false, false};   // packed into or being copied from (guarded by mu)
+  hipStream_t cs = nullptr;                      // copy_engine 1 only
+  Sdma sdma;
+  size_t capacity = 0, bytes = 0;                // bytes allocated per slab / bytes the current layout uses (= what is copied)
+  enum { FREE = 0, IN_FLIGHT = 1, LANDED = 2, HELD = 3 };
+  struct Slot { uint8_t *host = nullptr; uint64_t sig = 0, sig2 = 0; int state = FREE; uint64_t seq = 0; size_t bytes = 0, lf_from = 0; int devslab = 0; };
+  std::vector<Slot> slots;
+  std::deque<int> queue;                         // slots in flight or landed, oldest first (what dabx_delivery_next hands out)
+  std::deque<int> jobs;                          // slots whose copy the copier still has to make
+  std::mutex mu;                                 // everything above: the engine's thread, the copier and ONE consumer thread
+  std::condition_variable cv;                    // any state change
+  std::thread copier;
+  bool quit = false;
+  int device = 0;
+  std::string copier_error;
+  uint64_t next_seq = 0, landed = 0, bytes_copied = 0;
+  double copy_s = 0, copy_s_max = 0, gather_wait_s = 0, calib_gbps = 0;
+  unsigned long long *layout_off = nullptr;      // device tables (DeliverDev)
+  int32_t *subch_id = nullptr;
+  long long *frames_done = nullptr, *cif_done = nullptr, *sf_done = nullptr;
+  dabx_chunk_header hdr{};
+  bool want_pad = false;                         // DABX_DELIVER_PAD, or what == 0: a PAD section while there are PAD slots
+  bool want_dg = false;                          // DABX_DELIVER_DG, or what == 0: a data-group section while there are packet-mode slots
+};
+
+// Bulk ingest (include/dabx.h "Bulk ingest"): page-locked input slabs, their device twins, one SDMA transfer per slab.  Both forms are S
+// jobs for iqfile.hip's table writer: dabx_ingest_open gives every stream the same decode and a dense slab, dabx_ingest_open_formats
+// every stream its own container, rate, length and region.
+struct Ingest {
+  bool open = false;
+  int copy_engine = 0, max_frames = 0;
+  size_t capacity = 0;                           // bytes per slab
+  struct Slab {
+    uint8_t *host = nullptr, *dev = nullptr; uint64_t sig = 0; bool in_flight = false;
+    size_t bytes = 0, pitch = 0;                 // what was submitted: bytes transferred, bytes from one stream's payload to the next
+    std::vector<size_t> n_bytes;                 // [S] payload bytes per stream
+    // the commit's table, [S] jobs and behind them [S] sample counts: page-locked staging / device.  One per slab: dabx_ingest_submit
+    // drains the ingest stream, so by the slab's next commit the upload of this one has left the staging copy
+    IqJob *jobs_host = nullptr, *jobs_dev = nullptr;      // (in Ingest::tables_host / tables_dev)
+    hipEvent_t counts_read = nullptr;            // per-stream form: the commit kernel that reads the device table's counts has run (front-end stream)
+  };
+  std::vector<Slab> slabs;
+  Sdma sdma;
+  hipStream_t cs = nullptr;                      // copy_engine 1 only
+  uint8_t *tables_host = nullptr, *tables_dev = nullptr;
+  bool general = false;                          // dabx_ingest_open_formats
+  size_t pitch = 0;                              // ... bytes per stream region of a slab
+  std::vector<IqDecode> dec;                     // [S]
+  std::vector<int> M, tab, carry_n;              // [S] input samples per ms (0 = 2.048 MS/s), table index, samples carried between slabs
+  float2 *work = nullptr, *carry = nullptr;
+  size_t work_pitch = 0, carry_pitch = 0;
+  int16_t *tab_int = nullptr; float *tab_frac = nullptr;
+};
+
+// The job table of a stage that runs on some slots only (k_packet: PacketSlot / PacketDev, k_pad: PadSlot / PadDev).  Nothing of it exists
+// until the stage's dabx_set_*_mode first switches a slot on: host stays empty, dev.n stays 0 and no batch launches the kernel.
+// host[sj].st mirrors the device's table entry of the slot; the device owns it between download and upload (both with the engine drained).
+template <class Slot, class Dev> struct JobTable {
+  struct Host { bool on = false; Slot st{}; long long seen = 0, lost = 0; };     // seen: items a read call has returned or passed, lost: those it found gone
+  std::vector<Host> host;                      // [S][max_subch], or empty
+  std::vector<int> index;                      // [S][max_subch] place in the table, -1 = not a slot of this stage
+  Dev dev{};                                   // slots = the table on the device, n = its length
+  int cap = 0;
+  bool on(size_t sj) const { return !host.empty() && host[sj].on; }
+  // the device's table back into the mirror
+  int download(int max_subch)
+  {
+    if (dev.n <= 0) return 0;
+    std::vector<Slot> tab((size_t)dev.n);
+    DABX_HIP(hipMemcpy(tab.data(), dev.slots, sizeof(Slot) * tab.size(), hipMemcpyDeviceToHost));
+    for (const Slot &q : tab) host[(size_t)q.s * max_subch + q.j].st = q;
+    return 0;
+  }
+  // ... and the table rebuilt from the mirror: the stage's slots, in (stream, slot) order
+  int upload()
+  {
+    std::vector<Slot> tab;
+    std::fill(index.begin(), index.end(), -1);
+    for (size_t sj = 0; sj < host.size(); sj++)
+      if (host[sj].on) { index[sj] = (int)tab.size(); tab.push_back(host[sj].st); }
+    if ((int)tab.size() > cap) {
+      Slot *q = nullptr;
+      const int n = std::max<int>(2 * cap, std::max<int>(16, (int)tab.size()));
+      DABX_HIP(hipMalloc(&q, sizeof(Slot) * (size_t)n));
+      if (dev.slots) (void)hipFree(dev.slots);
+      dev.slots = q; cap = n;
+    }
+    if (!tab.empty()) DABX_HIP(hipMemcpy(dev.slots, tab.data(), sizeof(Slot) * tab.size(), hipMemcpyHostToDevice));
+    dev.n = (int)tab.size();
+    return 0;
+  }
+  void drop(size_t sj)                         // the slot leaves the stage: its rings are freed
+  {
+    if (sj >= host.size() || !host[sj].on) return;
+    (void)hipFree(host[sj].st.out.bytes);
+    (void)hipFree(host[sj].st.out.recs);
+    host[sj] = Host{};
+  }
+  void destroy()
+  {
+    for (size_t sj = 0; sj < host.size(); sj++) drop(sj);
+    if (dev.slots) (void)hipFree(dev.slots);
+  }
+};
+
+struct dabx_engine : dabx::EngineHead {          // (iqfile.h: the ring format, where iqfile.cpp can read it)
+  dabx_config cfg{};
+  EngineDev dev{};
+  hipStream_t stream = nullptr;                // == ss.a (front end)
+  EngineStreams ss;
+  BatchSnap *snap_buf[2] = {nullptr, nullptr};
+  int device = 0;
+  std::vector<unsigned long long> wr_host;     // host mirror of committed samples
+  std::vector<SubchDev> subch_host;            // [S][max_subch]
+  std::vector<int> subch_id_host;              // [S][max_subch] SubChId (host only: ETI STC field)
+  struct EtiCursor { long long next_cif = -1; int hi = -1, lo = -1; long long fib_frames_seen = 0; };
+  std::vector<EtiCursor> eti;                  // [S]
+  std::vector<dabx_fibdec *> fibdec;           // [S] FIB decoders (current / next configuration), created on first dabx_follow_fic
+  std::vector<long long> fib_frames_fed;       // [S] frames whose FIBs the decoder has seen
+  bool fig_reference_quirks = false;           // dabx_set_fig_reference_quirks: the engine's own FIB decoders swap like the reference (flags 3 only)
+  std::vector<dabx_tii *> tii;                 // [S] detectors, created on first dabx_read_tii
+  std::vector<int> tii_epoch;                  // [S] reset epoch seen by the detector
+  std::vector<void *> allocs;
+  void *stage = nullptr;                       // host -> device staging of dabx_push_iq
+  size_t stage_cap = 0;
+  // dabx_push_iq_async: a small pool of device staging slots, each guarded by the event of its last conversion kernel, so
+  // that consecutive pushes from pinned host memory queue back to back on the ingest stream (DMA at PCIe rate, no host wait)
+  static constexpr int ASYNC_SLOTS = 8;
+  void *aslot[ASYNC_SLOTS] = {nullptr};
+  size_t aslot_cap[ASYNC_SLOTS] = {0};
+  hipEvent_t aslot_done[ASYNC_SLOTS] = {nullptr};
+  unsigned long long async_pushes = 0;
+  hipStream_t ingest = nullptr;                // dabx_push_iq: copy + format conversion, concurrent with the receiver streams
+  hipStream_t ingest2 = nullptr;               // dabx_push_iq_async alternates between the two: the DMA of push k + 1 runs under the conversion of push k
+  hipEvent_t ingest_done = nullptr;
+  std::vector<unsigned long long> rd_seen;     // [S] read index of every stream when last looked at (lower bound)
+  std::vector<StreamCtl> ctl_peek;
+  int max_kbps = 0;
+  bool buffers_ready = false;
+  Marker mk;
+  double prof_ms[N_STEP_KERNELS] = {0};
+  long long prof_n[N_STEP_KERNELS] = {0};
+  int pending_frames = 0;                      // front-end steps whose CIFs still await the MSC decoder
+  bool have_fast = false;
+  MscFast fast{};
+
+  std::vector<void *> fast_allocs;             // buffers of the current MSC classes (replaced on reconfiguration)
+  bool classes_dirty = false;
+  std::vector<char> announcing;                // per stream: the zero-copy producer uses dabx_announce_write
+  unsigned long long *horizon_host = nullptr;  // hipHostMalloc'ed, EngineDev::wr_horizon: what pushes may have overwritten (written BEFORE a copy is issued)
+  int32_t *locked_host = nullptr;              // hipHostMalloc'ed: number of streams in lock, kept by the device (EngineDev::locked_count)
+  int32_t *seq_timeouts_host = nullptr;        // hipHostMalloc'ed: device-side waits that gave up (EngineDev::seq_timeouts)
+  bool level_dirty = false;                    // exact_level_tracker: steps have been issued since k_level_exact last ran behind them
+  Delivery dl;
+  Ingest ing;
+  JobTable<PacketSlot, PacketDev> pkt;         // packet-mode slots (include/dabx.h "Packet-mode data sub-channels", k_packet)
+  JobTable<PadSlot, PadDev> pad;               // PAD slots (include/dabx.h "Programme-associated data", k_pad)
+  int build_msc_classes();
+  int delivery_layout();                       // offsets of every slot's bytes in a slab for the sub-channels configured now
+  int delivery_begin(DeliverDev *dv, int *slot, int *devslab);     // a chunk closes: host + device slab, front gather on stream a
+  int delivery_finish(int slot, int devslab, hipStream_t tail);    // ... its slot gather is queued on `tail`: the one copy
+  void delivery_abort(int slot, int devslab);                      // ... or it cannot be: both slabs go back
+
+  // stream s's ring: its first element, whatever the element is (EngineDev::ring_fmt)
+  void *ring_of(int s) const { return static_cast<char *>(dev.iq) + (size_t)s * dev.ring_len * ring_bytes_per_sample(dev.ring_fmt); }
+  template <class T> int alloc(T **p, size_t count, bool zero = true) { return alloc_bytes(p, count * sizeof(T), zero); }
+  template <class T> int alloc_bytes(T **p, size_t n_bytes, bool zero = true)
+  {
+    void *q = nullptr;
+    const size_t bytes = std::max<size_t>(n_bytes, 16);
+    DABX_HIP(hipMalloc(&q, bytes));
+    if (zero) DABX_HIP(hipMemsetAsync(q, 0, bytes, stream));
+    allocs.push_back(q);
+    *p = reinterpret_cast<T *>(q);
+    return 0;
+  }
+};
+
+// ---- helpers of more than one engine*.cpp file, each defined in the file that owns its subsystem -------------------------------------
+namespace dabx {
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// engine.cpp
+int need_device_e();
+int use_device(const dabx_engine *e);
+int sync_all(dabx_engine *e, bool chain_only = false);
+int ring_takes(const dabx_engine *e, int fmt, const char *who);
+void announce_write(dabx_engine *e, int stream, unsigned long long upto);
+int commit_impl(dabx_engine *e, int stream, size_t n);
+int push_room(dabx_engine *e, int stream, size_t n, const char *who);
+// engine_delivery.cpp
+int delivery_drain(dabx_engine *e);
+void delivery_free(dabx_engine *e);
+// engine_ingest.cpp
+void ingest_free(dabx_engine *e);
+// engine_slots.cpp
+void pad_count_sources(dabx_engine *e);
+}  // namespace dabx

@@ -1,0 +1,270 @@
+// engine_slots.cpp -- the slots with output rings, packet mode and PAD: what their entry points share and dabx_set_*_mode, dabx_read_*,
+// dabx_get_*_stats.
+#include "engine.h"
+#include <algorithm>
+#include <cstddef>
+#include <cstring>
+#include <string>
+#include <type_traits>
+
+namespace dabx {
+
+// PadDev::n_mp2 follows the table: called behind every e->pad.upload()
+void pad_count_sources(dabx_engine *e)
+{
+  int n = 0;
+  for (const auto &h : e->pad.host) n += h.on && h.st.source == DABX_PAD_SOURCE_MP2 ? 1 : 0;
+  e->pad.dev.n_mp2 = n;
+}
+
+}  // namespace dabx
+
+// ---- slots with output rings (out_ring.h): what the packet-mode and the PAD entry points below share -------------------------------------
+static uint32_t pow2_at_least(size_t v) { uint32_t p = 1; while (p < v) p <<= 1; return p; }
+
+// The rings of a slot that is switched on (n_bytes, n_rec: powers of two) and what one chunk of the bulk delivery has room for
+template <class Rec> static bool out_ring_create(OutRing<Rec> *r, uint32_t n_bytes, uint32_t n_rec, uint32_t asm_room, uint32_t dl_rec_cap, uint32_t dl_bytes_cap)
+{
+  void *b = nullptr, *q = nullptr;
+  if (hipMalloc(&b, n_bytes) != hipSuccess || hipMalloc(&q, sizeof(Rec) * (size_t)n_rec) != hipSuccess) {
+    if (b) (void)hipFree(b);
+    return false;
+  }
+  r->bytes = static_cast<uint8_t *>(b); r->recs = static_cast<Rec *>(q);
+  r->bytes_mask = n_bytes - 1; r->rec_mask = n_rec - 1; r->asm_room = asm_room;
+  r->dl_rec_cap = dl_rec_cap; r->dl_bytes_cap = dl_bytes_cap;
+  return true;
+}
+
+// The tail of dabx_set_packet_mode / dabx_set_pad_mode (engine drained): the slab of an open delivery follows the stage's slots.
+// delivery_layout writes BOTH job tables back from their mirrors, so the other stage's is refreshed first.
+template <class Tab> static int relayout_open_delivery(dabx_engine *e, size_t sj, const SubchDev &sc, Tab &other)
+{
+  if (!e->dl.open) return 0;
+  e->subch_host[sj] = sc;
+  if (int rc = other.download(e->dev.max_subch)) return rc;
+  if (int rc = e->delivery_layout()) {
+    const std::string why = dabx::last_error();
+    delivery_free(e);
+    set_error("%s -- the delivery has been closed", why.c_str());
+    return rc;
+  }
+  return 0;
+}
+
+// The slot's table entry as the device holds it and the items [*lo, count) whose record and bytes are still intact (out_ring.h); older ones
+// that no call has returned yet are counted as lost.  Reads the entry and, as a rule, ONE record (the oldest candidate's).
+template <class Slot, class Dev> static int ring_window(dabx_engine *e, JobTable<Slot, Dev> &tab, size_t sj, Slot *st, long long *lo)
+{
+  if (int rc = sync_all(e)) return rc;
+  DABX_HIP(hipMemcpy(st, tab.dev.slots + tab.index[sj], sizeof(Slot), hipMemcpyDeviceToHost));
+  const auto &r = st->out;
+  long long first = out_ring_oldest(r);
+  while (first < r.count) {
+    std::remove_reference_t<decltype(*r.recs)> q;
+    DABX_HIP(hipMemcpy(&q, r.recs + (size_t)(first & r.rec_mask), sizeof(q), hipMemcpyDeviceToHost));
+    if (out_ring_intact(r, q.byte_pos)) break;
+    first++;
+  }
+  auto &h = tab.host[sj];
+  if (first > h.seen) { h.lost += first - h.seen; h.seen = first; }
+  *lo = first;
+  return 0;
+}
+
+// dabx_read_datagroups / dabx_read_pad_items behind their argument checks: the newest n intact items, of these the newest that fit max_bytes
+template <class Slot, class Dev, class Rec> static int ring_read(dabx_engine *e, JobTable<Slot, Dev> &tab, size_t sj, int n, Rec *info, uint8_t *bytes, size_t max_bytes)
+{
+  if (!tab.on(sj)) return 0;
+  Slot st;
+  long long lo = 0;
+  if (int rc = ring_window(e, tab, sj, &st, &lo)) return rc;
+  const OutRing<Rec> &r = st.out;
+  long long from = std::max(lo, r.count - n);
+  int have = (int)(r.count - from);
+  if (have > 0) {                                             // the records [from, count): one or two runs of the ring
+    const size_t ring = (size_t)r.rec_mask + 1, at = (size_t)(from & r.rec_mask), head = std::min<size_t>((size_t)have, ring - at);
+    DABX_HIP(hipMemcpy(info, r.recs + at, sizeof(Rec) * head, hipMemcpyDeviceToHost));
+    if ((size_t)have > head) DABX_HIP(hipMemcpy(info + head, r.recs, sizeof(Rec) * ((size_t)have - head), hipMemcpyDeviceToHost));
+    int skip = 0;                                             // the newest items that fit
+    if (bytes) while (skip < have && (unsigned long long)(r.n_bytes - info[skip].byte_pos) > max_bytes) skip++;
+    if (skip) { memmove(info, info + skip, sizeof(Rec) * (size_t)(have - skip)); have -= skip; }
+  }
+  if (have > 0) {
+    const long long base = info[0].byte_pos, total = r.n_bytes - base;
+    for (int i = 0; i < have; i++) info[i].byte_pos -= base;
+    if (bytes && total > 0) {
+      const size_t ring = (size_t)r.bytes_mask + 1, at = (size_t)((unsigned long long)base & r.bytes_mask);
+      const size_t head = std::min<size_t>((size_t)total, ring - at);
+      DABX_HIP(hipMemcpy(bytes, r.bytes + at, head, hipMemcpyDeviceToHost));
+      if ((size_t)total > head) DABX_HIP(hipMemcpy(bytes + head, r.bytes, (size_t)total - head, hipMemcpyDeviceToHost));
+    }
+  }
+  tab.host[sj].seen = std::max(tab.host[sj].seen, r.count);
+  return have;
+}
+
+// ---- slots with output rings: packet-mode data sub-channels (packet_core.h, k_packet) and programme-associated data (pad_core.h, k_pad) ----
+static_assert(sizeof(dabx_chunk_dg) == 128 && sizeof(dabx_datagroup_info) == 32 && sizeof(dabx_packet_stats) == 128 && sizeof(dabx_packet_config) == 32, "include/dabx.h: packet-mode records");
+static_assert(sizeof(dabx_chunk_pad) == 128 && sizeof(dabx_pad_item) == 32 && sizeof(dabx_pad_stats) == 128 && sizeof(dabx_pad_config) == 32, "include/dabx.h: PAD records");
+static_assert(sizeof(dabx_mp2_sync_stats) == 64 && offsetof(dabx_pad_config, source) == 4, "include/dabx.h: PAD of MP2 frames");
+
+extern "C" {
+
+int dabx_set_packet_mode(dabx_engine *e, int stream, int j, const dabx_packet_config *cfg)
+{
+  if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch) { set_error("dabx_set_packet_mode: bad argument"); return DABX_E_ARG; }
+  if (cfg && (cfg->size < 2 * sizeof(int32_t) || cfg->packet_address < 0 || cfg->packet_address > 1023)) {
+    set_error("dabx_set_packet_mode: bad configuration (size %u, packet address %d)", cfg->size, (int)cfg->packet_address);
+    return DABX_E_ARG;
+  }
+  int rc;
+  if ((rc = sync_all(e))) return rc;
+  const size_t sj = (size_t)stream * e->dev.max_subch + j;
+  SubchDev sc;
+  DABX_HIP(hipMemcpy(&sc, e->dev.subch + sj, sizeof(SubchDev), hipMemcpyDeviceToHost));
+  if (!sc.active || sc.dab_plus || sc.kbps % 8 != 0 || sc.kbps > PKT_MAX_KBPS) {
+    set_error("dabx_set_packet_mode: stream %d slot %d is %s", stream, j, !sc.active ? "not active" : sc.dab_plus ? "a DAB+ slot" : "not at a multiple of 8 kbit/s up to 384");
+    return DABX_E_ARG;
+  }
+  if (cfg && e->pad.on(sj)) { set_error("dabx_set_packet_mode: stream %d slot %d has PAD decoding on", stream, j); return DABX_E_ARG; }
+  auto &tab = e->pkt;
+  if (tab.host.empty()) {
+    if (!cfg) return 0;
+    tab.host.resize((size_t)e->dev.n_streams * e->dev.max_subch);
+    tab.index.assign(tab.host.size(), -1);
+  }
+  if ((rc = tab.download(e->dev.max_subch))) return rc;
+  tab.drop(sj);
+  if (cfg) {
+    // two full batches (56 logical frames) of single-packet groups: a record per 24-byte packet, their payloads, and room for the series
+    // under assembly, which lives in the byte ring in front of the completed groups (packet_core.h); a chunk: one batch of them
+    decltype(e->pkt)::Host h;
+    h.on = true;
+    h.st.s = stream; h.st.j = j; h.st.address = cfg->packet_address; h.st.first_byte = -1; h.st.run_crc = 0xFFFFu;
+    const size_t recs = (size_t)4 * MSC_BATCH_FRAMES * (sc.kbps / 8), bytes = (size_t)4 * MSC_BATCH_FRAMES * 3 * sc.kbps;
+    if (!out_ring_create(&h.st.out, pow2_at_least(2 * bytes + DABX_DG_MAX_BYTES), pow2_at_least(2 * recs), DABX_DG_MAX_BYTES, (uint32_t)recs,
+                         (uint32_t)(bytes + DABX_DG_MAX_BYTES))) {
+      set_error("dabx_set_packet_mode: out of device memory");
+      (void)tab.upload();
+      return DABX_E_NOMEM;
+    }
+    tab.host[sj] = h;
+  }
+  if ((rc = tab.upload())) return rc;
+  return relayout_open_delivery(e, sj, sc, e->pad);
+}
+
+int dabx_read_datagroups(dabx_engine *e, int stream, int j, int n, dabx_datagroup_info *info, uint8_t *bytes, size_t max_bytes)
+{
+  if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch || n <= 0 || !info) { set_error("dabx_read_datagroups: bad argument"); return DABX_E_ARG; }
+  return ring_read(e, e->pkt, (size_t)stream * e->dev.max_subch + j, n, info, bytes, max_bytes);
+}
+
+int dabx_get_packet_stats(dabx_engine *e, int stream, int j, dabx_packet_stats *out)
+{
+  if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch || !out) { set_error("dabx_get_packet_stats: bad argument"); return DABX_E_ARG; }
+  memset(out, 0, sizeof(*out));
+  const size_t sj = (size_t)stream * e->dev.max_subch + j;
+  if (!e->pkt.on(sj)) return sync_all(e);
+  PacketSlot st;
+  long long lo = 0;
+  if (int rc = ring_window(e, e->pkt, sj, &st, &lo)) return rc;
+  out->frames = st.frames; out->packets = st.packets; out->addr_match = st.addr_match; out->continuity_err = st.continuity_err;
+  out->crc_bad = st.crc_bad; out->len_bad = st.len_bad; out->walk_short = st.walk_short; out->dg_count = st.out.count;
+  out->dg_bytes = st.out.n_bytes; out->dg_crc_bad = st.dg_crc_bad; out->dg_overflow = st.dg_overflow; out->dg_lost = e->pkt.host[sj].lost;
+  out->active = 1; out->packet_address = st.address;
+  return 0;
+}
+
+int dabx_set_pad_mode(dabx_engine *e, int stream, int j, const dabx_pad_config *cfg)
+{
+  if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch) { set_error("dabx_set_pad_mode: bad argument"); return DABX_E_ARG; }
+  if (cfg && cfg->size < sizeof(uint32_t)) { set_error("dabx_set_pad_mode: bad configuration (size %u)", cfg->size); return DABX_E_ARG; }
+  int rc;
+  if ((rc = sync_all(e))) return rc;
+  const size_t sj = (size_t)stream * e->dev.max_subch + j;
+  SubchDev sc;
+  DABX_HIP(hipMemcpy(&sc, e->dev.subch + sj, sizeof(SubchDev), hipMemcpyDeviceToHost));
+  const int source = cfg && cfg->size >= 2 * sizeof(uint32_t) ? cfg->source : DABX_PAD_SOURCE_DABPLUS;
+  if (source != DABX_PAD_SOURCE_DABPLUS && source != DABX_PAD_SOURCE_MP2) { set_error("dabx_set_pad_mode: unknown source %d", source); return DABX_E_ARG; }
+  if (source == DABX_PAD_SOURCE_MP2) {
+    if (!sc.active || sc.dab_plus || e->pkt.on(sj) || sc.kbps % 8 != 0 || sc.kbps > PKT_MAX_KBPS) {
+      set_error("dabx_set_pad_mode: source MP2: stream %d slot %d is %s", stream, j, !sc.active ? "not active" : sc.dab_plus ? "a DAB+ slot" :
+                e->pkt.on(sj) ? "in packet mode" : "not at a multiple of 8 kbit/s up to 384");
+      return DABX_E_ARG;
+    }
+  } else if (!(cfg == nullptr && e->pad.on(sj)) && (!sc.active || sc.dab_plus != 1 || !e->dev.sf_info)) {      // (NULL also switches an MP2 source slot off)
+    set_error("dabx_set_pad_mode: stream %d slot %d is %s", stream, j, !sc.active ? "not active" : "not a DAB+ slot");
+    return DABX_E_ARG;
+  }
+  auto &tab = e->pad;
+  if (tab.host.empty()) {
+    if (!cfg) return 0;
+    tab.host.resize((size_t)e->dev.n_streams * e->dev.max_subch);
+    tab.index.assign(tab.host.size(), -1);
+  }
+  if ((rc = tab.download(e->dev.max_subch))) return rc;
+  tab.drop(sj);
+  if (cfg) {
+    decltype(e->pad)::Host h;
+    h.on = true;
+    h.st.s = stream; h.st.j = j; h.st.sf_seen = sc.sf_count;           // the walk starts with the next super frame completed
+    h.st.h.xpad_length = -1; h.st.h.segment_number = -1; h.st.h.segment_no = -1;       // pad_handler.h:74, :79, :83
+    h.st.source = source;
+    h.st.m.sample_rate = 48000; h.st.m.last_sync_bit = -1;             // mp2processor.cpp:236-240: SearchingForSync, both counts 0
+    if (!out_ring_create(&h.st.out, PAD_BYTE_RING, PAD_ITEM_RING, PAD_ASM_ROOM, PAD_DL_ITEM_CAP, PAD_DL_BYTES_CAP)) {      // (pad_core.h has the derivations)
+      set_error("dabx_set_pad_mode: out of device memory");
+      (void)tab.upload();
+      pad_count_sources(e);
+      return DABX_E_NOMEM;
+    }
+    tab.host[sj] = h;
+  }
+  if ((rc = tab.upload())) return rc;
+  pad_count_sources(e);
+  return relayout_open_delivery(e, sj, sc, e->pkt);
+}
+
+int dabx_get_mp2_sync_stats(dabx_engine *e, int stream, int j, dabx_mp2_sync_stats *out)
+{
+  if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch || !out) { set_error("dabx_get_mp2_sync_stats: bad argument"); return DABX_E_ARG; }
+  memset(out, 0, sizeof(*out));
+  const size_t sj = (size_t)stream * e->dev.max_subch + j;
+  if (!e->pad.on(sj) || e->pad.host[sj].st.source != DABX_PAD_SOURCE_MP2) return sync_all(e);
+  if (int rc = sync_all(e)) return rc;
+  PadSlot st;
+  DABX_HIP(hipMemcpy(&st, e->pad.dev.slots + e->pad.index[sj], sizeof(PadSlot), hipMemcpyDeviceToHost));
+  const Mp2State &m = st.m;
+  out->syncs = m.syncs; out->frames = m.frames; out->hdr_refused = m.hdr_refused; out->rate_unsupported = m.rate_unsupported;
+  out->sample_rate = m.sample_rate; out->state = m.state; out->bit_count = m.bit_count; out->header_count = m.header_count;
+  out->last_sync_bit = m.last_sync_bit; out->active = 1;
+  return 0;
+}
+
+int dabx_read_pad_items(dabx_engine *e, int stream, int j, int n, dabx_pad_item *info, uint8_t *bytes, size_t max_bytes)
+{
+  if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch || n <= 0 || !info) { set_error("dabx_read_pad_items: bad argument"); return DABX_E_ARG; }
+  return ring_read(e, e->pad, (size_t)stream * e->dev.max_subch + j, n, info, bytes, max_bytes);
+}
+
+int dabx_get_pad_stats(dabx_engine *e, int stream, int j, dabx_pad_stats *out)
+{
+  if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch || !out) { set_error("dabx_get_pad_stats: bad argument"); return DABX_E_ARG; }
+  memset(out, 0, sizeof(*out));
+  const size_t sj = (size_t)stream * e->dev.max_subch + j;
+  if (!e->pad.on(sj)) return sync_all(e);
+  PadSlot st;
+  long long lo = 0;
+  if (int rc = ring_window(e, e->pad, sj, &st, &lo)) return rc;
+  const PadCounters &c = st.c;
+  auto i32 = [](long long v) { return (int32_t)std::min<long long>(v, INT32_MAX); };
+  out->superframes = c.superframes; out->aus = c.aus; out->pad_aus = c.pad_aus; out->fpad_other = c.fpad_other; out->xpad_short = c.xpad_short;
+  out->xpad_variable = c.xpad_variable; out->xpad_other = c.xpad_other; out->pad_bad = c.pad_bad; out->labels = c.labels;
+  out->label_bytes = c.label_bytes; out->groups = c.groups; out->group_bytes = c.group_bytes; out->items_lost = e->pad.host[sj].lost;
+  out->li_bad = i32(c.li_bad); out->dl_overflow = i32(c.dl_overflow); out->dg_crc_bad = i32(c.dg_crc_bad); out->dg_small = i32(c.dg_small);
+  out->active = 1;
+  return 0;
+}
+
+}  // extern "C"

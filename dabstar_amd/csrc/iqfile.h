@@ -63,7 +63,7 @@ int launch_iq_jobs(const IqIo &io, const IqJob *jobs_dev, int n_streams, unsigne
 int launch_commit_counts(unsigned long long *wr, const unsigned *counts_dev, int n_streams, hipStream_t st);
 }  // namespace dabx
 
-// Head of every dabx_engine (engine.cpp: its first base): what this file's host side reads of an engine without calling into it
+// Head of every dabx_engine (engine.h: its first base): what this file's host side reads of an engine without calling into it
 namespace dabx { struct EngineHead { int32_t ring_fmt = 0; }; }
 extern "C" int dabx_internal_commit(dabx_engine *e, int stream, size_t n);   // commit of samples iqfile.cpp wrote itself (announces them first)
 extern "C" int dabx_internal_ring_info(dabx_engine *e, int stream, float2 **ring, int *ring_len, unsigned long long *wr,

@@ -2,7 +2,7 @@
 // and X-PAD data groups): a ring of 32-byte records and a ring of bytes, both in emission order -- item i has its record at i & rec_mask and
 // its bytes from byte_pos & bytes_mask on.  The item under assembly lives IN the byte ring, where the completed item will be: bytes
 // [n_bytes, n_bytes + fill), so the device may have written up to asm_room bytes beyond n_bytes, and whatever that range covers in the
-// ring is gone.  A reader -- dabx_read_datagroups / dabx_read_pad_items (engine.cpp) and the slab gather (deliver.hip) -- therefore trusts
+// ring is gone.  A reader -- dabx_read_datagroups / dabx_read_pad_items (engine_slots.cpp) and the slab gather (deliver.hip) -- therefore trusts
 // item i only while its record is still in the record ring (out_ring_oldest) and its bytes are (out_ring_intact).  This is the only place
 // that states the rule.
 #pragma once

@@ -1,4 +1,4 @@
-// pipeline.h -- device-resident state of the stream-batched receiver (engine.cpp / pipeline.hip / msc_stages.hip).
+// pipeline.h -- device-resident state of the stream-batched receiver (engine.h and the engine*.cpp files / pipeline.hip / msc_stages.hip).
 #pragma once
 #include "dabx_internal.h"
 #include "ring_fmt.h"
@@ -343,5 +343,39 @@ __device__ __forceinline__ size_t tdi_off(long long cif, int i)
   return (size_t)(cif & (TDI_SLOTS - 1)) * CIF_BITS + (size_t)(i & 15) * (CIF_BITS / 16) + (size_t)(i >> 4);
 }
 #endif
+
+// ---- launchers (asynchronous on their streams) and tables of the engine, by the file that defines them: declared here and nowhere else ----
+struct PacketDev;                 // packet_core.h
+struct PadDev;                    // pad_core.h
+// pipeline.hip
+extern const char *const kStepKernelNames[N_STEP_KERNELS];
+int launch_front_step(const EngineDev &e, EngineStreams &ss, Marker &mk, bool async_acquire, bool all_locked);
+int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineStreams &ss, Marker &mk, const DeliverDev *dv = nullptr,
+                     hipStream_t *tail = nullptr, const PacketDev *pk = nullptr, const PadDev *pad = nullptr);
+int launch_dciq(const EngineDev &e, int mode, hipStream_t st);
+int launch_level_exact(const EngineDev &e, hipStream_t st);
+int launch_commit(const EngineDev &e, int stream, unsigned long long n, hipStream_t st);
+int launch_fic_only(const EngineDev &e, hipStream_t st, int first, int count);
+int launch_i16_to_sym(const int16_t *soft, uint8_t *sym, size_t n, hipStream_t st);
+int launch_stage_msc_block(const EngineDev &e, const int16_t *soft_dev, int blk, bool closes_cif, hipStream_t st);
+int launch_msc_inject(const EngineDev &e, int stream, const int16_t *soft_dev, int n_cifs, int first, hipStream_t st);
+int launch_msc_advance(const EngineDev &e, const int32_t *counts_dev, hipStream_t st);
+int launch_fic_inject(const EngineDev &e, int stream, const int16_t *soft_dev, hipStream_t st);
+int launch_fic_decode(const EngineDev &e, const int32_t *present_dev, hipStream_t st);
+// vit_t.hip
+int launch_msc_prep(const EngineDev &e, int cifs, const MscLaunch &L, hipStream_t st, Marker &mk);
+int launch_msc_vitT(const EngineDev &e, int cifs, const MscLaunch &L, hipStream_t st, Marker &mk);
+// deliver.hip
+int launch_deliver_front(const EngineDev &e, const DeliverDev &dv, hipStream_t st);
+int launch_deliver_msc(const EngineDev &e, const DeliverDev &dv, hipStream_t st, bool with_lf);
+int launch_deliver_lf(const EngineDev &e, const DeliverDev &dv, hipStream_t st);
+int launch_deliver_dg(const EngineDev &e, const DeliverDev &dv, const PacketDev &pk, hipStream_t st);
+int launch_deliver_pad(const EngineDev &e, const DeliverDev &dv, const PadDev &pd, hipStream_t st);
+// msc_stages.hip
+int launch_dabplus_stage(const EngineDev &e, hipStream_t st, Marker &mk);
+int launch_packet_stage(const EngineDev &e, const PacketDev *pk, hipStream_t st, Marker &mk, PacketDev *used);
+int launch_pad_stage(const EngineDev &e, const PadDev *pad, hipStream_t st, Marker &mk, PadDev *used);
+// fib.cpp
+void dabx_internal_fibdec_skip(dabx_fibdec *d, long long n_fibs);     // FIBs the decoder never saw (they had left the ring)
 
 }  // namespace dabx

@@ -12,7 +12,9 @@
 //   k_frame_tail   fine CFO, null symbol, clock error, cursor bookkeeping (dab_processor.cpp:226-302)
 //   k_msc_frame    time de-interleave + depuncture + Viterbi + PRBS per (CIF, sub-channel) (backend.cpp:129-161)
 // The launchers and the test-entry kernels are at the end.  Elsewhere: the lane-per-trellis MSC decoder k_msc_prep / k_msc_vitT (vit_t.hip), the
-// slot stages behind the decoder k_packet / k_dabplus / k_pad / k_pad_mp2 (msc_stages.hip), the delivery gathers (deliver.hip).
+// slot stages behind the decoder k_packet / k_dabplus / k_pad / k_pad_mp2 (msc_stages.hip), the delivery gathers (deliver.hip).  Every launcher
+// of these files is declared at the end of pipeline.h.  The host side that calls them: engine.cpp (create, push, dabx_process, reads),
+// engine_delivery.cpp, engine_ingest.cpp, engine_slots.cpp (packet mode, PAD), engine_facade.cpp (dabx_fic_*, dabx_msc_*, test entries).
 #include <type_traits>
 #include "pipeline.h"
 #include "packet_core.h"
@@ -1688,7 +1690,6 @@ __global__ void k_msc_snap(EngineDev e, int cifs)
   e.snap[s] = BatchSnap{done > cif_no - cifs ? done : cif_no - cifs, cif_no};
 }
 
-extern const char *const kStepKernelNames[N_STEP_KERNELS];
 // "k_demap_fic": the first k_demap_frame launch of a frame (symbols 1..3) when the FIC is decoded on its own stream
 const char *const kStepKernelNames[N_STEP_KERNELS] = {"k_acquire", "k_frame_head", "k_symbols", "k_demap_frame", "k_fic_frame", "k_frame_tail",
                                                       "k_msc_prep", "k_msc_vitT", "k_msc_frame", "k_dabplus", "k_demap_fic", "k_packet", "k_pad"};
@@ -1803,18 +1804,6 @@ int launch_front_step(const EngineDev &e_in, EngineStreams &ss, Marker &mk, bool
   DABX_HIP(hipGetLastError());
   return 0;
 }
-
-int launch_msc_prep(const EngineDev &e, int cifs, const MscLaunch &L, hipStream_t st, Marker &mk);
-int launch_msc_vitT(const EngineDev &e, int cifs, const MscLaunch &L, hipStream_t st, Marker &mk);
-
-int launch_deliver_msc(const EngineDev &e, const DeliverDev &dv, hipStream_t st, bool with_lf);
-int launch_deliver_lf(const EngineDev &e, const DeliverDev &dv, hipStream_t st);
-int launch_deliver_dg(const EngineDev &e, const DeliverDev &dv, const PacketDev &pk, hipStream_t st);
-int launch_deliver_pad(const EngineDev &e, const DeliverDev &dv, const PadDev &pd, hipStream_t st);
-// msc_stages.hip
-int launch_dabplus_stage(const EngineDev &e, hipStream_t st, Marker &mk);
-int launch_packet_stage(const EngineDev &e, const PacketDev *pk, hipStream_t st, Marker &mk, PacketDev *used);
-int launch_pad_stage(const EngineDev &e, const PadDev *pad, hipStream_t st, Marker &mk, PadDev *used);
 
 // MSC decode of the newest `cifs` CIFs (4 per front-end step, <= 4 * MSC_BATCH_FRAMES; 1 for the per-symbol stage entry) + the slot stages.
 // `e.snap` must point at the snapshot buffer of this batch.
@@ -1965,7 +1954,7 @@ int launch_stage_msc_block(const EngineDev &e, const int16_t *soft_dev, int blk,
   return 0;
 }
 
-// Test entries dabx_internal_msc_inject / dabx_internal_msc_decode (engine.cpp; not part of include/dabx.h): whole CIFs of soft bits go
+// Test entries dabx_internal_msc_inject / dabx_internal_msc_decode (engine_facade.cpp; not part of include/dabx.h): whole CIFs of soft bits go
 // into one stream's ring as k_stage_msc_block puts one symbol of stream 0 there -- CIFs cif_no + first .. of that stream, not yet
 // counted --, and the CIF counters then advance by a count per stream: what the front end does for a frame, without a front end.
 __global__ void k_msc_inject(EngineDev e, int s, const int16_t *soft, int n_cifs, int first)
@@ -1994,7 +1983,7 @@ int launch_msc_advance(const EngineDev &e, const int32_t *counts_dev, hipStream_
   return 0;
 }
 
-// Test entries dabx_internal_fic_inject / dabx_internal_fic_decode (engine.cpp; not part of include/dabx.h): a frame's 9216 FIC soft bits go
+// Test entries dabx_internal_fic_inject / dabx_internal_fic_decode (engine_facade.cpp; not part of include/dabx.h): a frame's 9216 FIC soft bits go
 // into one stream's fic_sym as the demapper's first launch puts them there, k_fic_frame decodes all streams as the many-stream schedule
 // launches it (first = 0, count = 4, no sequence-number wait), and the streams that had a frame count it, as k_frame_tail does.
 __global__ void k_fic_inject(EngineDev e, int s, const int16_t *soft)

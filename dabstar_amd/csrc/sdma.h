@@ -2,7 +2,7 @@
 // (hsa_amd_memory_async_copy).  Why not hipMemcpyAsync: on this ROCm (7.2) the HIP runtime moves device <-> page-locked host buffers
 // with a shader copy (__amd_rocclr_copyBuffer).  It reaches the link's rate, but while it runs the receiver's kernels stand still:
 // a 96-MiB copy next to an HBM-bound kernel doubles that kernel's time, the same bytes on an SDMA engine cost it 0.5 %
-// (tools/copy_interference.hip, profiles/r05_copy_interference.json).  The delivery's one copy per chunk (engine.cpp) goes this way.
+// (tools/copy_interference.hip, profiles/r05_copy_interference.json).  The delivery's one copy per chunk (engine_delivery.cpp) goes this way.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
