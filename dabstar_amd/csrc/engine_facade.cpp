@@ -1,5 +1,5 @@
-// engine_facade.cpp -- dabx_fic_decode, the per-symbol facades dabx_fic_* and dabx_msc_*, and the dabx_internal_* test entries of the FIC
-// and MSC stages.
+// engine_facade.cpp -- dabx_fic_decode, the per-symbol facades dabx_fic_* and dabx_msc_*, and the dabx_internal_* test entries of the demapper,
+// the FIC and the MSC stages.
 #include "engine.h"
 #include "viterbi_core.h"
 #include <cstring>
@@ -293,6 +293,67 @@ int dabx_internal_fic_decode(dabx_engine *e, const int32_t *present)
   int rc = 0;
   if (hipMemcpy(present_dev, present, bytes, hipMemcpyHostToDevice) != hipSuccess) { set_error("dabx_internal_fic_decode: copy failed"); rc = DABX_E_HIP; }
   if (!rc) rc = launch_fic_decode(e->dev, present_dev, e->stream);
+  const int rc2 = sync_all(e);
+  (void)hipFree(present_dev);
+  return rc ? rc : rc2;
+}
+
+// ---- test entries of the engine's demapper (tests/test_gpu_demap_stage.py; not part of include/dabx.h) -------------------------------
+// spectra: [76][2048] cf32 in FFT bin order, symbols 0..75 of the next frame of `stream`: symbol 0 becomes the stream's phase reference,
+// symbols 1..75 go into the engine's spectra buffer of the next step's parity, in carrier order, as k_symbols_persistent stores them.
+// null_fft: [2048] cf32 or NULL: advances the noise-power buffer that np_sel selects (the library's own update, null_power_next).
+// clock_err and np_sel (0 or 1) go into the stream's control record.  Nothing is demapped before dabx_internal_demap_frame.
+int dabx_internal_demap_inject(dabx_engine *e, int stream, const float *spectra, const float *null_fft, float clock_err, int np_sel)
+{
+  if (!e || !spectra || stream < 0 || stream >= e->dev.n_streams || (np_sel != 0 && np_sel != 1) || !e->dev.spectra) {
+    set_error("dabx_internal_demap_inject: bad argument (stream %d, np_sel %d)", stream, np_sel);
+    return DABX_E_ARG;
+  }
+  if (int rc = use_device(e)) return rc;
+  if (int rc = sync_all(e)) return rc;
+  float2 *buf = nullptr;
+  const size_t n_spec = (size_t)76 * TU, n_all = n_spec + TU;
+  DABX_HIP(hipMalloc(&buf, n_all * sizeof(float2)));
+  int rc = 0;
+  if (hipMemcpy(buf, spectra, n_spec * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess) { set_error("dabx_internal_demap_inject: copy failed"); rc = DABX_E_HIP; }
+  if (!rc && null_fft && hipMemcpy(buf + n_spec, null_fft, TU * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess) {
+    set_error("dabx_internal_demap_inject: copy failed");
+    rc = DABX_E_HIP;
+  }
+  if (!rc) rc = launch_demap_inject(e->dev, (int)(e->ss.step_count & 1u), stream, buf, null_fft ? buf + n_spec : nullptr, clock_err, np_sel, e->stream);
+  if (hipStreamSynchronize(e->stream) != hipSuccess && !rc) { set_error("dabx_internal_demap_inject: HIP error"); rc = DABX_E_HIP; }
+  (void)hipFree(buf);
+  return rc;
+}
+
+// present: [n_streams], 1 = the stream has a frame (frame_ok), 0 = it has none: the demapper must leave everything of that stream as it is.
+// schedule 0: one k_demap_frame6(0, 75); 1: k_demap_fic, then k_demap_frame6(3, 75); 2: k_demap_whole -- the launches of launch_front_step's
+// three schedules, picked by soft-bit type, tie mode and LCD statistics through the same dispatch, without the sequence-number hand-over;
+// then a full synchronisation.  Neither the CIF counter nor the frame count moves: dabx_internal_fic_decode and dabx_internal_msc_decode do
+// that afterwards.  Results: dabx_read_soft (capture_soft), dabx_get_stats, and what those two decode.
+int dabx_internal_demap_frame(dabx_engine *e, const int32_t *present, int schedule)
+{
+  if (!e || !present || schedule < 0 || schedule > 2 || !e->dev.spectra || !e->dev.fic_sym || !e->dev.tdi) {
+    set_error("dabx_internal_demap_frame: bad argument (schedule %d)", schedule);
+    return DABX_E_ARG;
+  }
+  for (int s = 0; s < e->dev.n_streams; s++)
+    if (present[s] != 0 && present[s] != 1) {
+      set_error("dabx_internal_demap_frame: present[%d] = %d (0 or 1)", s, (int)present[s]);
+      return DABX_E_ARG;
+    }
+  if (e->dl.open || e->pending_frames != 0) {
+    set_error("dabx_internal_demap_frame: the engine has a delivery open or front-end frames pending");
+    return DABX_E_STATE;
+  }
+  if (int rc = use_device(e)) return rc;
+  if (int rc = sync_all(e)) return rc;
+  int32_t *present_dev = nullptr;
+  const size_t bytes = sizeof(int32_t) * (size_t)e->dev.n_streams;
+  DABX_HIP(hipMalloc(&present_dev, bytes));
+  int rc = 0;
+  if (hipMemcpy(present_dev, present, bytes, hipMemcpyHostToDevice) != hipSuccess) { set_error("dabx_internal_demap_frame: copy failed"); rc = DABX_E_HIP; }
+  if (!rc) rc = launch_demap_frame(e->dev, e->ss.step_count, present_dev, schedule, e->stream);
   const int rc2 = sync_all(e);
   (void)hipFree(present_dev);
   return rc ? rc : rc2;

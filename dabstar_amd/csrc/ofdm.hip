@@ -91,20 +91,15 @@ __global__ void k_demap_store_ref(DemapDev d, const float2 *fft)   // ofdm_decod
   if (i < (size_t)d.batch * TU) d.phase_ref[i] = fft[i];
 }
 
-// store_null_symbol_without_tii, ofdm_decoder.cpp:114-130: IIR alpha 0.05 on the 1536 used bins
-__device__ __forceinline__ void null_power_update(float *np, float2 x)
-{
-  const float kMinNoisePower = (1.0f / 32767.0f) * (1.0f / 32767.0f);
-  const float power = x.x * x.x + x.y * x.y + kMinNoisePower;
-  *np += 0.05f * (power - *np);
-}
+// store_null_symbol_without_tii, ofdm_decoder.cpp:114-130: the 1536 used bins (ofdm_core.h, null_power_next)
 __global__ void k_demap_store_null(DemapDev d, const float2 *fft)
 {
   const int s = blockIdx.x;
   for (int i = threadIdx.x; i < K; i += blockDim.x) {
     const int idx = i - K / 2;
     const int bin = idx < 0 ? idx + TU : idx + 1;
-    null_power_update(&d.null_power[(size_t)s * TU + bin], fft[(size_t)s * TU + bin]);
+    float *np = &d.null_power[(size_t)s * TU + bin];
+    *np = null_power_next(*np, fft[(size_t)s * TU + bin]);
   }
 }
 

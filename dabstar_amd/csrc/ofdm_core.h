@@ -232,6 +232,15 @@ __device__ inline int coarse_cfo_block(const float2 X[8], const DevTables &t, fl
   return s_hz;
 }
 
+// ---- noise power per used bin: store_null_symbol_without_tii (ofdm_decoder.cpp:114-130), IIR alpha 0.05 -- the one update behind
+// k_demap_store_null, k_frame_tail and the demapper's test entry (k_demap_inject)
+__device__ __forceinline__ float null_power_next(float np, float2 x)
+{
+  const float kMinNoisePower = (1.0f / 32767.0f) * (1.0f / 32767.0f);
+  const float power = x.x * x.x + x.y * x.y + kMinNoisePower;
+  return np + 0.05f * (power - np);
+}
+
 // ---- D-QPSK soft-bit demapper: OfdmDecoder::decode_symbol (base/ofdm/ofdm_decoder.cpp:147-355) -------
 struct DemapCarrier {        // per-carrier state kept in registers across the 75 symbols of a frame
   float2 prev;               // mPhaseReference[bin]

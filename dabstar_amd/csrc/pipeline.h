@@ -362,6 +362,8 @@ int launch_msc_inject(const EngineDev &e, int stream, const int16_t *soft_dev, i
 int launch_msc_advance(const EngineDev &e, const int32_t *counts_dev, hipStream_t st);
 int launch_fic_inject(const EngineDev &e, int stream, const int16_t *soft_dev, hipStream_t st);
 int launch_fic_decode(const EngineDev &e, const int32_t *present_dev, hipStream_t st);
+int launch_demap_inject(const EngineDev &e, int parity, int stream, const float2 *spec_dev, const float2 *null_dev, float clock_err, int np_sel, hipStream_t st);
+int launch_demap_frame(const EngineDev &e, unsigned step_count, const int32_t *present_dev, int schedule, hipStream_t st);
 // vit_t.hip
 int launch_msc_prep(const EngineDev &e, int cifs, const MscLaunch &L, hipStream_t st, Marker &mk);
 int launch_msc_vitT(const EngineDev &e, int cifs, const MscLaunch &L, hipStream_t st, Marker &mk);

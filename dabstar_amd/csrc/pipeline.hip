@@ -1477,7 +1477,6 @@ __global__ __launch_bounds__(256) void k_frame_tail(EngineDev e, DevTables t)
   // THIS frame does not read (its MSC symbols may still be in flight on another HIP stream); a TII frame carries the values
   // over unchanged.  np_sel is flipped below.
   {
-    const float kMinNoisePower = (1.0f / 32767.0f) * (1.0f / 32767.0f);
     const float *np_cur = c.np_sel ? e.demap.null_power2 : e.demap.null_power;
     float *np_new = c.np_sel ? e.demap.null_power : e.demap.null_power2;
 #pragma unroll
@@ -1485,10 +1484,7 @@ __global__ __launch_bounds__(256) void k_frame_tail(EngineDev e, DevTables t)
       const int bin = tid + 256 * u;
       if ((bin >= 1 && bin <= K / 2) || bin >= TU - K / 2) {
         float np = np_cur[(size_t)s * TU + bin];
-        if (!is_tii) {
-          const float power = v[u].x * v[u].x + v[u].y * v[u].y + kMinNoisePower;
-          np += 0.05f * (power - np);
-        }
+        if (!is_tii) np = null_power_next(np, v[u]);
         np_new[(size_t)s * TU + bin] = np;
       }
     }
@@ -2018,6 +2014,65 @@ int launch_fic_decode(const EngineDev &e_in, const int32_t *present_dev, hipStre
   hipLaunchKernelGGL(k_fic_present, grid, dim3(256), 0, st, e, present_dev);
   hipLaunchKernelGGL(k_fic_frame, dim3(e.n_streams), dim3(256), 0, st, e, *t, 0, 4);
   hipLaunchKernelGGL(k_fic_advance, grid, dim3(256), 0, st, e, present_dev);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+
+// Test entries dabx_internal_demap_inject / dabx_internal_demap_frame (engine_facade.cpp; not part of include/dabx.h): the spectra of one frame
+// go where the front end leaves them for the demapper -- symbol 0 (FFT bin order) becomes the stream's phase reference, symbols 1..75 go into
+// e.spectra of parity e.parity in carrier order, as k_symbols_persistent stores them --, clock_err and np_sel into the stream's control
+// record; a null spectrum advances the noise-power buffer np_sel selects by null_power_next (ofdm_core.h), in place.  Then the demapper is
+// launched as launch_front_step launches it for each of its three schedules, without the sequence-number hand-over.
+// Grid: 76 blocks (one per symbol) + 1 (the null spectrum and the scalars).
+__global__ __launch_bounds__(256) void k_demap_inject(EngineDev e, DevTables t, int s, const float2 *spec, const float2 *null_fft, float clock_err, int np_sel)
+{
+  const int l = blockIdx.x, tid = threadIdx.x;
+  if (l == 0) {
+    for (int i = tid; i < TU; i += 256) e.demap.phase_ref[(size_t)s * TU + i] = spec[i];
+  } else if (l <= 75) {
+    float2 *dst = e.spectra + (((size_t)e.parity * e.n_streams + s) * 75 + (l - 1)) * K;
+    for (int k = tid; k < K; k += 256) dst[k] = spec[(size_t)l * TU + t.perm_bin[k]];
+  } else {
+    if (null_fft) {
+      float *np = (np_sel ? e.demap.null_power2 : e.demap.null_power) + (size_t)s * TU;
+      for (int k = tid; k < K; k += 256) { const int bin = t.perm_bin[k]; np[bin] = null_power_next(np[bin], null_fft[bin]); }
+    }
+    if (tid == 0) { e.ctl[s].clock_err = clock_err; e.ctl[s].np_sel = np_sel; }
+  }
+}
+int launch_demap_inject(const EngineDev &e_in, int parity, int stream, const float2 *spec_dev, const float2 *null_dev, float clock_err, int np_sel, hipStream_t st)
+{
+  const DevTables *t;
+  int rc = get_tables(&t);
+  if (rc) return rc;
+  EngineDev e = e_in;
+  e.parity = parity;
+  hipLaunchKernelGGL(k_demap_inject, dim3(77), dim3(256), 0, st, e, *t, stream, spec_dev, null_dev, clock_err, np_sel);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+// schedule 0: one k_demap_frame6(0, 75) (serial schedule); 1: k_demap_fic, then k_demap_frame6(3, 75) (overlapped, 48 and more streams);
+// 2: k_demap_whole (few streams).  All on `st`, flag_sync = 0: no launch waits for a sequence number nobody publishes.  k_demap_whole
+// itself still publishes behind the FIC symbols, whatever flag_sync says: step_seq is therefore set to step_count, the number of the last
+// real step -- what fic_seq holds already; the next real step waits for step_count + 1, which this store does not satisfy.
+int launch_demap_frame(const EngineDev &e_in, unsigned step_count, const int32_t *present_dev, int schedule, hipStream_t st)
+{
+  const DevTables *t;
+  int rc = get_tables(&t);
+  if (rc) return rc;
+  EngineDev e = e_in;
+  e.parity = (int)(step_count & 1u);                      // the spectra buffer the next step would use (launch_demap_inject wrote it)
+  e.step_seq = step_count;
+  e.flag_sync = 0;
+  hipLaunchKernelGGL(k_fic_present, dim3((e.n_streams + 255) / 256), dim3(256), 0, st, e, present_dev);
+  if (schedule == 0) {
+    DABX_DEMAP_DISPATCH(k_demap_frame6, dim3(e.n_streams), dim3(DEMAP_THREADS), 0, st, e, *t, 0, 75);
+  } else if (schedule == 1) {
+    DABX_DEMAP_DISPATCH(k_demap_fic, dim3(e.n_streams), dim3(DEMAP_THREADS), 0, st, e, *t);
+    DABX_DEMAP_DISPATCH(k_demap_frame6, dim3(e.n_streams), dim3(DEMAP_THREADS), 0, st, e, *t, 3, 75);
+  } else {
+    DABX_DEMAP_DISPATCH(k_demap_whole, dim3(e.n_streams), dim3(DEMAP_THREADS), 0, st, e, *t);
+  }
   DABX_HIP(hipGetLastError());
   return 0;
 }

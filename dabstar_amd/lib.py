@@ -150,6 +150,34 @@ def fic_decode_frame(engine, present):
     check(load().dabx_internal_fic_decode(engine._h, _p(present)))
 
 
+def demap_inject(engine, stream, spectra, null_fft=None, clock_err=0.0, np_sel=0):
+    """Internal test entry (not part of include/dabx.h): spectra [76, 2048] complex64 in FFT bin order become the next frame of `stream`
+    as the front end leaves it for the demapper -- symbol 0 the phase reference, symbols 1..75 the engine's spectra in carrier order --,
+    clock_err and np_sel go into the stream's control record, and null_fft [2048] (optional) advances the noise-power buffer np_sel
+    selects.  Nothing is demapped before demap_frame."""
+    spectra = np.ascontiguousarray(spectra, np.complex64)
+    if spectra.shape != (76, 2048):
+        raise ValueError("demap_inject needs the 76 spectra of one frame")
+    if null_fft is not None:
+        null_fft = np.ascontiguousarray(null_fft, np.complex64).reshape(-1)
+        if null_fft.size != 2048:
+            raise ValueError("demap_inject: a null spectrum has 2048 bins")
+    L = load()
+    L.dabx_internal_demap_inject.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_int]
+    check(L.dabx_internal_demap_inject(engine._h, int(stream), _p(spectra), None if null_fft is None else _p(null_fft), float(clock_err), int(np_sel)))
+
+
+def demap_frame(engine, present, schedule):
+    """Internal test entry: the engine's demapper over all streams, launched as the front end launches it -- schedule 0: one
+    k_demap_frame6(0, 75); 1: k_demap_fic, then k_demap_frame6(3, 75); 2: k_demap_whole -- in the instance the engine's soft-bit type,
+    tie mode and LCD statistics select.  present[s] = 0: stream s has no frame (nothing of it may change).  Neither the CIF counter nor
+    the frame count moves (fic_decode_frame / msc_decode do that).  Results: Engine.read_soft, Engine.stats."""
+    present = np.ascontiguousarray(present, np.int32).reshape(-1)
+    if present.size != engine.n_streams:
+        raise ValueError("demap_frame needs one flag per stream")
+    check(load().dabx_internal_demap_frame(engine._h, _p(present), int(schedule)))
+
+
 def fib_cif_count(fib32):
     """Internal, host only: (CIFCountHi, CIFCountLo) the library's FIG 0/0 walk reads out of one FIB of 32 bytes (CRC taken as good),
     or None -- the walk of k_fic_frame and of the ETI writer (csrc/fig00.h)."""

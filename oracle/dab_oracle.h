@@ -196,6 +196,9 @@ void ora_demap_reset(ora_demap *d);                                  /* ofdm_dec
 void ora_demap_store_ref(ora_demap *d, const ora_cf32 *fft);         /* ofdm_decoder.cpp:132-145 */
 void ora_demap_store_null(ora_demap *d, const ora_cf32 *fft);        /* ofdm_decoder.cpp:114-130 */
 void ora_demap_symbol(ora_demap *d, const ora_cf32 *fft, float clock_err, int16_t out[ORA_2K]); /* :147-355 */
+void ora_demap_symbol_products(ora_demap *d, const ora_cf32 *fft, float clock_err, int16_t out[ORA_2K],
+                               float prod[ORA_2K]);                  /* the same + the float products in front of the (i16) casts */
+float *ora_demap_state(ora_demap *d, int which);                     /* 0 integ, 1 mean_power, 2 mean_sigma_sq [K]; 3 mean_null_power [Tu] */
 float ora_demap_snr_db(const ora_demap *d);                       /* :326-343, :358-371 (SNR of the LCD statistics) */
 const int16_t *ora_interleave_map(void);                          /* the 16-entry time-de-interleaver map, backend.cpp:129 / eti_generator.cpp:22 */
 float ora_demap_mean_value(const ora_demap *d);

@@ -173,8 +173,11 @@ void ora_demap_store_null(ora_demap *d, const ora_cf32 *fft)
   }
 }
 
-/* ofdm_decoder.cpp:147-355 (soft-bit relevant part; display paths omitted) */
-void ora_demap_symbol(ora_demap *d, const ora_cf32 *fft, float clock_err, int16_t out[ORA_2K])
+/* ofdm_decoder.cpp:147-355 (soft-bit relevant part; display paths omitted).  prod (optional, tests): the float products
+ * r1.re * w2 [0, K) and r1.im * w2 [K, 2K) that the (i16) casts of :254-255 are applied to -- the same values, stored, nothing
+ * else changes. */
+static inline __attribute__((always_inline)) void demap_symbol(ora_demap *d, const ora_cf32 *fft, float clock_err, int16_t out[ORA_2K],
+                                                               float *prod)
 {
   float sum = 0.0f;
   const float ALPHA = 0.005f;
@@ -241,12 +244,19 @@ void ora_demap_symbol(ora_demap *d, const ora_cf32 *fft, float clock_err, int16_
     /* :254-255 */
     out[k] = cvt_i16(r1.re * w2);
     out[ORA_K + k] = cvt_i16(r1.im * w2);
+    if (prod) { prod[k] = r1.re * w2; prod[ORA_K + k] = r1.im * w2; }
     if (!(fabsf(r1.re * w2) < 32768.0f)) d->overflow_count++;
     if (!(fabsf(r1.im * w2) < 32768.0f)) d->overflow_count++;
     sum += cabs_f(r1);                                 /* :256 */
   }
   d->mean_value = sum / (float)ORA_K;                  /* :294 */
   memcpy(d->phase_ref, fft, sizeof(d->phase_ref));     /* :354 */
+}
+
+void ora_demap_symbol(ora_demap *d, const ora_cf32 *fft, float clock_err, int16_t out[ORA_2K]) { demap_symbol(d, fft, clock_err, out, NULL); }
+void ora_demap_symbol_products(ora_demap *d, const ora_cf32 *fft, float clock_err, int16_t out[ORA_2K], float prod[ORA_2K])
+{
+  demap_symbol(d, fft, clock_err, out, prod);
 }
 
 /* ofdm_decoder.cpp:326-343 (LCD statistics) with _compute_noise_Power, :358-371 */
@@ -279,3 +289,9 @@ void ora_phaseref_set_strongest(ora_phaseref *p, int on) { p->strongest = on; }
 void ora_demap_set_type(ora_demap *d, int type) { d->soft_bit_type = type; }
 float ora_demap_mean_value(const ora_demap *d) { return d->mean_value; }                     /* mMeanValue: SLcdData::TestData1, :344 */
 const float *ora_demap_std_dev_sq(const ora_demap *d) { return d->std_dev_sq; }             /* mStdDevSqPhaseVector (tests) */
+/* the per-carrier state (tests; writable: a test may hold two noise-power buffers and hand over the current one):
+ * 0 mIntegAbsPhaseVector [K], 1 mMeanPowerVector [K], 2 mMeanSigmaSqVector [K], 3 mMeanNullPowerWithoutTII [Tu, FFT bin order] */
+float *ora_demap_state(ora_demap *d, int which)
+{
+  return which == 0 ? d->integ_abs_phase : which == 1 ? d->mean_power : which == 2 ? d->mean_sigma_sq : which == 3 ? d->mean_null_power : NULL;
+}

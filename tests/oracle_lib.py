@@ -51,7 +51,24 @@ def oracle():
     global _ora
     if _ora is not None:
         return _ora
-    L = C.CDLL(build_oracle())
+    _ora = _prototypes(C.CDLL(build_oracle()))
+    return _ora
+
+
+_ora_fm = None
+
+
+def oracle_fastmath():
+    """The same sources built with the reference's float flags (-O3 -ffast-math -fsingle-precision-constant, `make -C oracle fastmath`):
+    what its shipped CPU path may do with the floats.  Never a checker; tests/test_demap_cases.py measures its distance from oracle()."""
+    global _ora_fm
+    if _ora_fm is None:
+        subprocess.check_call(["make", "-C", ORA_DIR, "fastmath"], stdout=subprocess.DEVNULL)
+        _ora_fm = _prototypes(C.CDLL(os.path.join(ORA_DIR, "_build", "liboracle_fastmath.so")))
+    return _ora_fm
+
+
+def _prototypes(L):
     L.ora_pi_codes.restype = C.POINTER(C.c_int8)
     L.ora_pi_codes.argtypes = [C.c_int]
     L.ora_freq_interleaver.argtypes = [_i16p]
@@ -134,12 +151,14 @@ def oracle():
     L.ora_demap_store_ref.argtypes = [C.c_void_p, _c64p]
     L.ora_demap_store_null.argtypes = [C.c_void_p, _c64p]
     L.ora_demap_symbol.argtypes = [C.c_void_p, _c64p, C.c_float, _i16p]
+    L.ora_demap_symbol_products.argtypes = [C.c_void_p, _c64p, C.c_float, _i16p, _f32p]
+    L.ora_demap_state.argtypes = [C.c_void_p, C.c_int]
+    L.ora_demap_state.restype = C.POINTER(C.c_float)
     L.ora_phaseref_new.restype = C.c_void_p
     L.ora_phaseref_free.argtypes = [C.c_void_p]
     L.ora_phaseref_set_strongest.argtypes = [C.c_void_p, C.c_int]
     L.ora_phaseref_correlate.argtypes = [C.c_void_p, _c64p, C.c_float]
     L.ora_phaseref_coarse_cfo.argtypes = [C.c_void_p, _c64p]
-    _ora = L
     return L
 
 
