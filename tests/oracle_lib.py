@@ -159,6 +159,9 @@ def _prototypes(L):
     L.ora_phaseref_set_strongest.argtypes = [C.c_void_p, C.c_int]
     L.ora_phaseref_correlate.argtypes = [C.c_void_p, _c64p, C.c_float]
     L.ora_phaseref_coarse_cfo.argtypes = [C.c_void_p, _c64p]
+    # oracle/fec.c builds its fire-code syndrome table on first use, "first writer wins" per syndrome; two threads of
+    # dabplus_cases.oracle_results that meet in that first use can leave a wrong table behind.  Built here, before any thread.
+    L.ora_firecode_syndrome_table()
     return L
 
 
@@ -352,6 +355,66 @@ class OraBackend:
 def make_descs(subch):
     return (SubchDesc * len(subch))(*[SubchDesc(c.subch_id, c.cu_start, c.cu_size, c.kbps, c.prot_level, c.short_form)
                                       for c in subch])
+
+
+def oracle_run(x, subch, want_soft=False, config=None):
+    """The oracle receiver on IQ x: per frame the FIBs, CRC flags and receiver scalars, per sub-channel the back end's results."""
+    L = oracle()
+    rx = L.ora_rx_create(make_descs(subch), len(subch))
+    if config:
+        L.ora_rx_configure(rx, *config)
+    L.ora_rx_enable_soft_capture(rx, int(want_soft))
+    n = L.ora_rx_run(rx, x, len(x), 10000)
+    cap = L.ora_rx_get_capture(rx).contents
+    res = dict(n=n, fibs=np.ctypeslib.as_array(cap.fibs, (n, 12, 32)).copy(),
+               crc=np.ctypeslib.as_array(cap.fib_crc, (n, 12)).copy(),
+               start=np.ctypeslib.as_array(cap.start_idx, (n,)).copy(),
+               fbb=np.ctypeslib.as_array(cap.fbb, (n,)).copy(),
+               fbb_end=np.ctypeslib.as_array(cap.fbb_end, (n,)).copy(), clock_err=np.ctypeslib.as_array(cap.clock_err, (n,)).copy(),
+               fic_ratio=np.ctypeslib.as_array(cap.fic_ratio, (n,)).copy(), snr_db=np.ctypeslib.as_array(cap.snr_db, (n,)).copy(),
+               mer_db=np.ctypeslib.as_array(cap.mer_db, (n,)).copy(),
+               s_level=np.ctypeslib.as_array(cap.s_level, (n,)).copy(), peak_level=np.ctypeslib.as_array(cap.peak_level, (n,)).copy(),
+               sym0=np.ctypeslib.as_array(cap.sym0_pos, (n,)).copy(),
+               ber_bits=np.ctypeslib.as_array(cap.fic_ber_bits, (n,)).copy(), ber_errors=np.ctypeslib.as_array(cap.fic_ber_errors, (n,)).copy(),
+               msc=[backend_bytes(rx, i, "msc") for i in range(len(subch))],
+               sf=[backend_bytes(rx, i, "sf") for i in range(len(subch))],
+               sfi=[backend_bytes(rx, i, "sfi") for i in range(len(subch))],
+               stats=[backend_stats(rx, i) for i in range(len(subch))])
+    if want_soft:
+        res["soft"] = np.ctypeslib.as_array(cap.soft, (n, 75, 3072)).copy()
+    L.ora_rx_destroy(rx)
+    return res
+
+
+def oracle_run_with_move(x, subch, move=None):
+    """move = (back end, new first capacity unit, CIF): that sub-channel is handed its slice from the new address from that CIF on"""
+    L = oracle()
+    rx = L.ora_rx_create(make_descs(subch), len(subch))
+    if move:
+        L.ora_rx_move_subch(rx, *move)
+    n = L.ora_rx_run(rx, x, len(x), 10000)
+    cap = L.ora_rx_get_capture(rx).contents
+    res = dict(n=n, fibs=np.ctypeslib.as_array(cap.fibs, (n, 12, 32)).copy(), crc=np.ctypeslib.as_array(cap.fib_crc, (n, 12)).copy(),
+               msc=[backend_bytes(rx, i, "msc").reshape(-1, 3 * subch[i].kbps) for i in range(len(subch))],
+               sf=[backend_bytes(rx, i, "sf") for i in range(len(subch))])
+    L.ora_rx_destroy(rx)
+    return res
+
+
+class FicBer(C.Structure):
+    """dabx_fic_ber (include/dabx.h), as dabx_fic_get_ber fills it."""
+    _fields_ = [("bits", C.c_int32), ("errors", C.c_int32), ("status_bits", C.c_int32), ("status_errors", C.c_int32),
+                ("blocks", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+def ora_eti_frame(hi, lo, minor, subch, fic96, msc):
+    """oracle/eti.c: (the 6144-byte ETI(NI) frame of one CIF, the bytes of it that are used)."""
+    arr = (SubchDesc * max(1, len(subch)))(*[SubchDesc(s.subch_id, s.cu_start, s.cu_size, s.kbps, s.prot_level, s.short_form) for s in subch])
+    bufs = [np.ascontiguousarray(m, np.uint8) for m in msc]
+    ptrs = (C.c_void_p * max(1, len(bufs)))(*[b.ctypes.data for b in bufs])
+    out = np.zeros(6144, np.uint8)
+    used = oracle().ora_eti_frame(hi, lo, minor, arr, len(subch), np.ascontiguousarray(fic96, np.uint8), ptrs, out)
+    return out, used
 
 
 class OraFibDecoder:

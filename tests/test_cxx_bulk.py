@@ -34,7 +34,7 @@ def test_bulk_host_builds_with_gxx_and_refuses_to_run_without_a_gpu(tmp_path):
 @pytest.mark.gpu
 def test_cxx_host_loop_with_a_consumer_thread_delivers_the_oracles_output(tmp_path):
     from tools import dab_synth as ds
-    from test_gpu_engine import _oracle_run
+    from oracle_lib import oracle_run
     exe = _build()
     subch = [ds.SubCh(1, 0, 48, 64, 2, 0), ds.SubCh(5, 60, 96, 128, 2, 0), ds.SubCh(9, 200, 84, 112, 2, 0), ds.SubCh(12, 400, 24, 32, 2, 0, dab_plus=0)]
     S, n_frames = 3, 28
@@ -58,7 +58,7 @@ def test_cxx_host_loop_with_a_consumer_thread_delivers_the_oracles_output(tmp_pa
     total_frames = aus = 0
     for s in range(S):
         x = ((qs[s].astype(np.float32) - np.float32(127.38)) / np.float32(128.0)).view(np.complex64)
-        ora = _oracle_run(np.ascontiguousarray(x), subch)
+        ora = oracle_run(np.ascontiguousarray(x), subch)
         rec = np.fromfile(out + ".s%d.fibs" % s, np.uint8).reshape(-1, 396)
         f = len(rec)
         total_frames += f

@@ -1,6 +1,5 @@
 """ETI(NI) frame assembly (host, CPU): dabx_eti_frame vs the oracle restatement of EtiGenerator::_init_eti + assembly,
 plus the structural rules of the container (ETS 300 799: FSYNC alternation, FL, header CRC, EOF CRC)."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -16,15 +15,6 @@ def _crc(b):
         for _ in range(8):
             crc = ((crc << 1) ^ 0x1021) & 0xFFFF if crc & 0x8000 else (crc << 1) & 0xFFFF
     return crc ^ 0xFFFF
-
-
-def _ora_frame(hi, lo, minor, subch, fic96, msc):
-    arr = (ol.SubchDesc * max(1, len(subch)))(*[ol.SubchDesc(s.subch_id, s.cu_start, s.cu_size, s.kbps, s.prot_level, s.short_form) for s in subch])
-    bufs = [np.ascontiguousarray(m, np.uint8) for m in msc]
-    ptrs = (C.c_void_p * max(1, len(bufs)))(*[b.ctypes.data for b in bufs])
-    out = np.zeros(6144, np.uint8)
-    used = ol.oracle().ora_eti_frame(hi, lo, minor, arr, len(subch), np.ascontiguousarray(fic96, np.uint8), ptrs, out)
-    return out, used
 
 
 def _random_case(rng, n):
@@ -46,7 +36,7 @@ def test_frames_match_the_oracle_for_random_ensembles():
             subch, fic, msc = _random_case(rng, n)
             hi, lo, minor = int(rng.integers(0, 21)), int(rng.integers(0, 250)), int(rng.integers(0, 4))
             got, used = dx.eti_frame(hi, lo, minor, subch, fic, msc)
-            want, used_o = _ora_frame(hi, lo, minor, subch, fic, msc)
+            want, used_o = ol.ora_eti_frame(hi, lo, minor, subch, fic, msc)
             assert used == used_o and np.array_equal(got, want)
 
 

@@ -16,7 +16,7 @@ from dabstar_amd import lib as dx
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 from tools import dab_synth as ds  # noqa: E402
-from test_gpu_engine import _oracle_run  # noqa: E402
+from oracle_lib import oracle_run  # noqa: E402
 from dabplus_cases import _check_record_against_its_super_frame  # noqa: E402  (moved there unchanged: the DAB+ stage tests share it)
 
 pytestmark = pytest.mark.gpu
@@ -24,7 +24,7 @@ pytestmark = pytest.mark.gpu
 
 def _oracle_records(x, subch):
     """The oracle receiver on x: per sub-channel the 32-byte records and the super frames they describe."""
-    ora = _oracle_run(x, subch)
+    ora = oracle_run(x, subch)
     return [r.view(dx.SUPERFRAME_INFO) for r in ora["sfi"]], ora["sf"], ora["stats"]
 
 

@@ -16,31 +16,16 @@ The device keeps the newest 16 super frames per slot and a batch completes at mo
 The end-of-frame guard `au_start + len + 2 > end` (an AU whose length passes the 0 .. 960 check but which would end behind the super
 frame) is the oracle's and the kernel's; mp4processor.cpp:311 has no such test and would read past the super frame there.  The guard is
 kept and compared; the reference's out-of-bounds read is not reproduced."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import dabplus_cases as dc
 from dabstar_amd import lib as dx
+from stage_driver import SF_COUNTERS, drive, engine, kernel_launches
 
 pytestmark = pytest.mark.gpu
 
-H, B = dc.HISTORY, dc.BATCH
-COUNTERS = (("cifs_decoded", "cif_out"), ("sf_ok", "sf_ok"), ("sf_fail", "sf_fail"), ("rs_corrected", "rs_corr"), ("rs_failed", "rs_fail"),
-            ("fc_corrected", "fc_corr"), ("au_ok", "au_ok"), ("au_bad", "au_bad"))
-
-
-def _engine(n_streams, max_subch, fast_min=1, class_min=1):
-    eng = dx.Engine(n_streams=n_streams, ring_frames=2, max_subch=max_subch, out_frames=1, msc_fast_min_jobs=fast_min, msc_class_min_jobs=class_min)
-    dx.check(dx.load().dabx_set_profiling(eng._h, 1))
-    return eng
-
-
-def _kernel_launches(eng):
-    ms = (C.c_double * 16)(); cnt = (C.c_int64 * 16)(); names = (C.c_char_p * 16)()
-    nk = dx.check(dx.load().dabx_get_profile(eng._h, ms, cnt, names))
-    return {names[i].decode(): int(cnt[i]) for i in range(nk)}
+B = dc.BATCH
 
 
 def _state(eng, lay, s):
@@ -55,51 +40,14 @@ def _state(eng, lay, s):
 
 
 def _drive(eng, lays, cifs, schedule):
-    """16 CIFs of history for every stream, then one MSC batch per row of `schedule` ([batch][stream] CIF counts).  After every batch the
-    new logical frames, super frames and records of every slot are read and appended; a stream that received nothing must hold byte for
-    byte what it held.  Returns ({(s, j): {"frames", "sf", "sfi", "stats"}}, per stream the batches that completed no super frame)."""
-    S = len(lays)
-    for s in range(S):
-        eng.set_subchannels(lays[s], stream=s)                 # SubCh.dab_plus of every slot decides
-        dx.msc_inject(eng, s, cifs[s][:H])
-    dx.msc_decode(eng, [H] * S, H)
-    got = {(s, j): {"frames": [], "sf": [], "sfi": [], "seen": 0} for s in range(S) for j, sc in enumerate(lays[s]) if sc.kbps}
-    at, idle = [H] * S, [0] * S
-    for counts in schedule:
-        before = {s: _state(eng, lays[s], s) for s in range(S) if counts[s] == 0}
-        for s in range(S):
-            if counts[s]:
-                dx.msc_inject(eng, s, cifs[s][at[s]:at[s] + counts[s]])
-        dx.msc_decode(eng, counts, B)
-        for s in range(S):
-            if counts[s] == 0:
-                assert _state(eng, lays[s], s) == before[s], "stream %d received nothing in this batch and changed" % s
-                continue
-            at[s] += counts[s]
-            eng.subch = list(lays[s])
-            completed = 0
-            for j, sc in enumerate(lays[s]):
-                if not sc.kbps:
-                    continue
-                g = got[(s, j)]
-                fr = eng.read_msc(s, j, counts[s])
-                assert fr.shape[0] == counts[s], (sc.kbps, s, j, fr.shape)
-                g["frames"].append(fr)
-                new = eng.subch_stats(s, j)["sf_count"] - g["seen"]
-                assert 0 <= new <= 6, (sc.kbps, s, j, new)                         # 28 + 4 frames hold at most 6 windows: nothing left the ring of 16 unread
-                if new:
-                    sf, sfi = eng.read_superframes(s, j, new), eng.read_superframe_info(s, j, new)
-                    assert sf.shape[0] == new == len(sfi), (sc.kbps, s, j, new)
-                    g["sf"].append(sf); g["sfi"].append(sfi)
-                g["seen"] += new
-                completed += new if sc.dab_plus else 0
-            idle[s] += completed == 0
-    for (s, j), g in got.items():
-        R = lays[s][j].kbps // 8
-        g["frames"] = np.concatenate(g["frames"])
-        g["sf"] = np.concatenate(g["sf"]) if g["sf"] else np.zeros((0, 110 * R), np.uint8)
-        g["sfi"] = np.concatenate(g["sfi"]) if g["sfi"] else np.zeros(0, dx.SUPERFRAME_INFO)
-        g["stats"] = eng.subch_stats(s, j)
+    """stage_driver.drive on per stream (layout, CIFs): after every batch the new logical frames, super frames and records of every slot
+    are read and appended; a stream that received nothing must hold byte for byte what it held.  Returns ({(s, j): {"frames", "sf", "sfi",
+    "stats"}}, per stream the batches that completed no super frame)."""
+    got = drive(eng, [(lays[s], None, cifs[s]) for s in range(len(lays))], schedule, lambda eng, s: None, {}, lambda eng, s: _state(eng, lays[s], s))
+    idle = []
+    for s in range(len(lays)):
+        per_slot = [g["sf_new"] for (i, j), g in got.items() if i == s and lays[s][j].dab_plus]
+        idle.append(sum(not any(batch) for batch in zip(*per_slot)))
     return got, idle
 
 
@@ -125,14 +73,14 @@ def _mismatches(got, lays, want):
             if not np.array_equal(g["sf"][i], o["sf"][i]):
                 d = np.flatnonzero(g["sf"][i] != o["sf"][i])
                 bad.append(where + "%d bytes differ, the first at %s (code words %s)" % (len(d), d[:8].tolist(), sorted(set((d % (sc.kbps // 8)).tolist()))[:8]))
-        for mine, theirs in COUNTERS:
+        for mine, theirs in SF_COUNTERS:
             if g["stats"][mine] != o["stats"][theirs]:
                 bad.append(tag + "%s = %d, the oracle's %d" % (mine, g["stats"][mine], o["stats"][theirs]))
     return bad
 
 
 def _totals(got, lays):
-    t = dict.fromkeys([m for m, _ in COUNTERS] + ["sf_count"], 0)
+    t = dict.fromkeys([m for m, _ in SF_COUNTERS] + ["sf_count"], 0)
     for (s, j), g in got.items():
         if lays[s][j].dab_plus:
             for k in t:
@@ -164,10 +112,10 @@ def test_every_bit_rate_on_adversarial_super_frames_equals_the_oracle():
     for layout in dc.every_rate_layouts():
         lays = [layout] * S
         cifs, want = _case(0, lays)
-        eng = _engine(S, len(layout))
+        eng = engine(S, len(layout))
         try:
             got, _idle = _drive(eng, lays, cifs, _full_batches(S))
-            launches = _kernel_launches(eng)
+            launches = kernel_launches(eng)
             assert launches["k_dabplus"] == dc.N_BATCHES + 1 == launches["k_msc_vitT"] and launches["k_msc_frame"] == 0, launches
         finally:
             eng.close()
@@ -192,10 +140,10 @@ def test_super_frames_across_batch_boundaries_and_streams_that_receive_nothing()
     lays = [layout] * S
     cifs, want = _case(1, lays)
     schedule = dc.boundary_schedule()
-    eng = _engine(S, len(layout))
+    eng = engine(S, len(layout))
     try:
         got, idle = _drive(eng, lays, cifs, schedule)
-        launches = _kernel_launches(eng)
+        launches = kernel_launches(eng)
         assert launches["k_dabplus"] == len(schedule) + 1, launches
     finally:
         eng.close()
@@ -215,10 +163,10 @@ def test_both_decoders_feed_the_stage_the_same():
     cifs, want = _case(1, lays)
     runs = []
     for fast_min, class_min in ((1 << 30, 0), (0, 0), (1, 1)):
-        eng = _engine(S, len(layout), fast_min=fast_min, class_min=class_min)
+        eng = engine(S, len(layout), fast_min=fast_min, class_min=class_min)
         try:
             got, _idle = _drive(eng, lays, cifs, _full_batches(S))
-            launches = _kernel_launches(eng)
+            launches = kernel_launches(eng)
             assert launches["k_dabplus"] == dc.N_BATCHES + 1, launches
             if fast_min == 1 << 30:
                 assert launches["k_msc_vitT"] == 0 and launches["k_msc_frame"] == dc.N_BATCHES + 1, launches
@@ -243,7 +191,7 @@ def test_a_slot_that_is_not_dab_plus_and_one_that_is_not_configured_next_to_dab_
     lays = dc.neighbour_layouts()
     assert lays[0][1].kbps == 0 and lays[0][2].kbps and not lays[0][2].dab_plus and all(c.dab_plus for c in lays[1])
     cifs, want = _case(2, lays)
-    eng = _engine(2, 4)
+    eng = engine(2, 4)
     try:
         got, _idle = _drive(eng, lays, cifs, _full_batches(2))
         idle_slot = eng.subch_stats(0, 1)

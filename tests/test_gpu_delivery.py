@@ -16,7 +16,7 @@ from dabstar_amd import lib as dx
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 from tools import dab_synth as ds  # noqa: E402
-from test_gpu_engine import _oracle_run  # noqa: E402
+from oracle_lib import oracle_run  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -82,7 +82,7 @@ def test_chunks_carry_the_complete_output_of_every_stream():
     for seed, snr, cfo, toff in chans:
         ens = ds.build_ensemble(10, subch, seed=seed)
         x = ds.channel(ens.iq, snr_db=snr, cfo_hz=cfo, timing_offset=toff, seed=seed, n_out=n_total)
-        xs.append(x); oras.append(_oracle_run(x, subch))
+        xs.append(x); oras.append(oracle_run(x, subch))
     S = len(chans)
     eng = dx.Engine(n_streams=S, ring_frames=46, max_subch=18, out_frames=8)
     eng.set_subchannels(subch)
@@ -156,7 +156,7 @@ def test_consumer_thread_and_partial_deliveries():
     subch = ds.default_subchannels(18, 64)
     ens = ds.build_ensemble(10, subch, seed=7)
     x = ds.channel(ens.iq, snr_db=18.0, cfo_hz=-420.0, timing_offset=99999, seed=7, n_out=40 * ds.TF)
-    ora = _oracle_run(x, subch)
+    ora = oracle_run(x, subch)
     short = dx.Engine(n_streams=1, ring_frames=4, max_subch=1, out_frames=4, fic_only=True)      # a FIB ring shorter than a chunk is refused ...
     with pytest.raises(dx.DabxError, match="out_frames >= 7"):
         short.delivery_open(slots=2, what=dx.DELIVER_FIB)
@@ -209,7 +209,7 @@ def test_delivery_follows_a_reconfiguration():
     subch = ds.default_subchannels(18, 64)
     ens = ds.build_ensemble(10, subch, seed=11)
     x = ds.channel(ens.iq, snr_db=20.0, cfo_hz=150.0, timing_offset=4000, seed=11, n_out=40 * ds.TF)
-    ora = _oracle_run(x, subch)
+    ora = oracle_run(x, subch)
     eng = dx.Engine(n_streams=1, ring_frames=41, max_subch=18, out_frames=8)
     first = subch[:6]
     eng.set_subchannels(first)
@@ -244,7 +244,7 @@ def test_what_a_receivers_host_side_needs():
     subch = [ds.SubCh(1, 0, 48, 64, 2, 0), ds.SubCh(5, 60, 96, 128, 2, 0), ds.SubCh(9, 200, 84, 112, 2, 0), ds.SubCh(12, 400, 24, 32, 2, 0, dab_plus=0)]
     ens = ds.build_ensemble(10, subch, seed=91)
     x = ds.channel(ens.iq, snr_db=21.0, cfo_hz=77.0, timing_offset=2222, seed=91, n_out=30 * ds.TF)
-    ora = _oracle_run(x, subch)
+    ora = oracle_run(x, subch)
     eng = dx.Engine(n_streams=1, ring_frames=31, max_subch=4, out_frames=8)
     eng.set_subchannels(subch)
     eng.delivery_open(slots=2, what=dx.DELIVER_FIB | dx.DELIVER_SF | dx.DELIVER_MSC_NOT_DABPLUS)

@@ -202,9 +202,9 @@ def test_the_test_entries_refuse_what_they_cannot_do():
 def test_the_entries_work_in_the_hipmodule_form():
     """One row and schedule of the engine test, and the refusals, with the binding pointed at hipmodule/libdabx.so: k_demap_inject and the
     demapper instances are found in the code objects and launched through hipModuleLaunchKernel."""
-    from test_gpu_hipmodule import _env
+    from hipmodule_env import hipmodule_env
     p = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider",
-                        "tests/test_gpu_demap_stage.py", "-k", "gen3_tie0_mer1-fic_then_frame6 or refuse"], cwd=ROOT, env=_env(), capture_output=True,
+                        "tests/test_gpu_demap_stage.py", "-k", "gen3_tie0_mer1-fic_then_frame6 or refuse"], cwd=ROOT, env=hipmodule_env(), capture_output=True,
                        text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-3000:]
     assert "2 passed" in p.stdout and "failed" not in p.stdout, p.stdout[-500:]

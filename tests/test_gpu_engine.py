@@ -10,40 +10,13 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
+from stage_driver import kernel_launches
 from dabstar_amd import lib as dx
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 from tools import dab_synth as ds  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-
-def _oracle_run(x, subch, want_soft=False, config=None):
-    L = ol.oracle()
-    rx = L.ora_rx_create(ol.make_descs(subch), len(subch))
-    if config:
-        L.ora_rx_configure(rx, *config)
-    L.ora_rx_enable_soft_capture(rx, int(want_soft))
-    n = L.ora_rx_run(rx, x, len(x), 10000)
-    cap = L.ora_rx_get_capture(rx).contents
-    res = dict(n=n, fibs=np.ctypeslib.as_array(cap.fibs, (n, 12, 32)).copy(),
-               crc=np.ctypeslib.as_array(cap.fib_crc, (n, 12)).copy(),
-               start=np.ctypeslib.as_array(cap.start_idx, (n,)).copy(),
-               fbb=np.ctypeslib.as_array(cap.fbb, (n,)).copy(),
-               fbb_end=np.ctypeslib.as_array(cap.fbb_end, (n,)).copy(), clock_err=np.ctypeslib.as_array(cap.clock_err, (n,)).copy(),
-               fic_ratio=np.ctypeslib.as_array(cap.fic_ratio, (n,)).copy(), snr_db=np.ctypeslib.as_array(cap.snr_db, (n,)).copy(),
-               mer_db=np.ctypeslib.as_array(cap.mer_db, (n,)).copy(),
-               s_level=np.ctypeslib.as_array(cap.s_level, (n,)).copy(), peak_level=np.ctypeslib.as_array(cap.peak_level, (n,)).copy(),
-               sym0=np.ctypeslib.as_array(cap.sym0_pos, (n,)).copy(),
-               ber_bits=np.ctypeslib.as_array(cap.fic_ber_bits, (n,)).copy(), ber_errors=np.ctypeslib.as_array(cap.fic_ber_errors, (n,)).copy(),
-               msc=[ol.backend_bytes(rx, i, "msc") for i in range(len(subch))],
-               sf=[ol.backend_bytes(rx, i, "sf") for i in range(len(subch))],
-               sfi=[ol.backend_bytes(rx, i, "sfi") for i in range(len(subch))],
-               stats=[ol.backend_stats(rx, i) for i in range(len(subch))])
-    if want_soft:
-        res["soft"] = np.ctypeslib.as_array(cap.soft, (n, 75, 3072)).copy()
-    L.ora_rx_destroy(rx)
-    return res
 
 
 def _engine_run(x, subch, n_frames, lcd=False, **kw):
@@ -99,7 +72,7 @@ def test_fic_and_msc_bit_exact_vs_oracle(seed, snr, cfo, toff):
     ens = ds.build_ensemble(10, subch, seed=seed)
     n_total = 28 * ds.TF
     x = ds.channel(ens.iq, snr_db=snr, cfo_hz=cfo, timing_offset=toff, seed=seed, n_out=n_total)
-    ora = _oracle_run(x, subch)
+    ora = ol.oracle_run(x, subch)
     eng, fibs, crc, msc, starts, fbbs = _engine_run(x, subch, ora["n"], lcd=seed in (2, 4))
     n = min(len(fibs), ora["n"])
     assert n >= ora["n"] - 1 and n >= 20
@@ -153,7 +126,7 @@ def test_mobile_channels_follow_the_oracle(profile, doppler, snr, ppm, drift):
     ens = ds.build_ensemble(10, subch, seed=33)
     x = ds.channel_mobile(ens.iq, profile, doppler_hz=doppler, snr_db=snr, cfo_hz=-520.0, timing_offset=9000, seed=33,
                           n_out=30 * ds.TF, clock_ppm=ppm, clock_drift_ppm_per_s=drift)
-    ora = _oracle_run(x, subch)
+    ora = ol.oracle_run(x, subch)
     eng = dx.Engine(n_streams=1, ring_frames=len(x) // ds.TF + 1, max_subch=18, out_frames=4)
     eng.set_subchannels(subch)
     if profile == "TU6":
@@ -211,7 +184,7 @@ def test_input_level_extremes_follow_the_oracle(gain):
     subch = ds.default_subchannels(6, 64)
     ens = ds.build_ensemble(10, subch, seed=15)
     x = (ds.channel(ens.iq, snr_db=17.0, cfo_hz=610.0, timing_offset=33333, seed=15, n_out=22 * ds.TF) * np.float32(gain)).astype(np.complex64)
-    ora = _oracle_run(x, subch)
+    ora = ol.oracle_run(x, subch)
     # the level tracker starts at 0.1 (sample_reader.h:95): a weak input spends its first frames in failed acquisition
     # attempts while the level decays, each of them one engine step
     eng, fibs, crc, msc, starts, fbbs = _engine_run(x, subch, ora["n"] + 12)
@@ -238,7 +211,7 @@ def test_multipath_channel_follows_the_oracle(strongest):
     y[210:] += np.complex64(0.35 * np.exp(-1j * 2.3)) * x[:-210]
     y = y.astype(np.complex64)
     cfg = (3.0, strongest, 1)
-    ora = _oracle_run(y, subch, config=cfg)
+    ora = ol.oracle_run(y, subch, config=cfg)
     eng, fibs, crc, msc, starts, fbbs = _engine_run(y, subch, ora["n"], sync_threshold=cfg[0], sync_strongest=bool(strongest))
     n = min(len(fibs), ora["n"])
     assert n >= ora["n"] - 1 and n >= 18
@@ -288,7 +261,7 @@ def test_soft_bits_within_tolerance_and_transmitted_data_recovered():
     subch = ds.default_subchannels(18, 64)
     ens = ds.build_ensemble(10, subch, seed=7)
     x = ds.channel(ens.iq, snr_db=20.0, cfo_hz=-433.0, timing_offset=1000, seed=7, n_out=14 * ds.TF)
-    ora = _oracle_run(x, subch, want_soft=True)
+    ora = ol.oracle_run(x, subch, want_soft=True)
     eng = dx.Engine(n_streams=1, ring_frames=15, max_subch=18, capture_soft=True)
     eng.set_subchannels(subch)
     eng.push_iq(0, x)
@@ -382,7 +355,7 @@ def test_lcd_mer_in_the_many_stream_schedule_and_in_the_delivered_record():
     n_streams, n_frames = 48, 12
     xs = {s: ds.channel(ens.iq, snr_db=14.0 + 0.25 * s, cfo_hz=-800.0 + 30.0 * s, timing_offset=1000 + 4099 * s, seed=500 + s,
                         n_out=(n_frames + 2) * ds.TF) for s in (0, 17, 47)}
-    ora = {s: _oracle_run(xs[s], []) for s in xs}
+    ora = {s: ol.oracle_run(xs[s], []) for s in xs}
     eng = dx.Engine(n_streams=n_streams, ring_frames=n_frames + 3, max_subch=1, out_frames=8, fic_only=True)
     assert eng.stats(0)["mer_db_est"] == 0.0
     eng.set_lcd_statistics(1)
@@ -414,12 +387,6 @@ def test_lcd_mer_in_the_many_stream_schedule_and_in_the_delivered_record():
     eng.close()
 
 
-def _kernel_launches(eng):
-    ms = (C.c_double * 16)(); cnt = (C.c_int64 * 16)(); names = (C.c_char_p * 16)()
-    nk = dx.check(dx.load().dabx_get_profile(eng._h, ms, cnt, names))
-    return {names[i].decode(): int(cnt[i]) for i in range(nk)}
-
-
 @pytest.mark.parametrize("class_min", [1, 256])
 def test_profile_classes_decode_mixed_and_per_stream_layouts_lane_per_trellis(class_min):
     """Lane-per-trellis MSC decoder on a population of DIFFERENT ensembles: the sub-channels of all streams are grouped
@@ -440,7 +407,7 @@ def test_profile_classes_decode_mixed_and_per_stream_layouts_lane_per_trellis(cl
         eng.push_iq(s, xs[s])
     dx.check(dx.load().dabx_set_profiling(eng._h, 1))
     eng.process(n_frames)
-    launches = _kernel_launches(eng)
+    launches = kernel_launches(eng)
     dx.check(dx.load().dabx_set_profiling(eng._h, 0))
     assert launches["k_msc_vitT"] >= 4 and launches["k_msc_prep"] == launches["k_msc_vitT"]
     assert (launches["k_msc_frame"] == 0) == (class_min == 1), launches
@@ -495,7 +462,7 @@ def test_more_profiles_than_decoder_classes():
         eng.push_iq(s, xs[s])
     dx.check(dx.load().dabx_set_profiling(eng._h, 1))
     eng.process(n_frames)
-    launches = _kernel_launches(eng)
+    launches = kernel_launches(eng)
     dx.check(dx.load().dabx_set_profiling(eng._h, 0))
     assert launches["k_msc_vitT"] >= 4 and launches["k_msc_frame"] == launches["k_msc_vitT"], launches
     for s in range(n_streams):
@@ -565,7 +532,7 @@ def test_subchannels_discovered_from_the_decoded_fic_then_decoded():
     eng.process(12)                 # 7 + 5 frames: the de-interleaver warm-up ends inside the first MSC batch
     st = eng.stats(0)
     assert st["sf_fail"] == 0 and st["sf_ok"] >= 18 and st["fib_ok"] >= st["fib_total"] - 24   # two settling frames, as in the oracle
-    ref = _oracle_run(x, subch)
+    ref = ol.oracle_run(x, subch)
     for j in (0, 5, 17):
         sf = eng.read_superframes(0, j, 4)
         assert len(sf) == 4                                   # (48 - 16) logical frames -> 4..6 windows, ring read of 4
@@ -579,11 +546,10 @@ def test_subchannels_discovered_from_the_decoded_fic_then_decoded():
 def test_eti_frames_carry_the_fic_and_the_logical_frames_of_each_cif():
     """dabx_read_eti (eti_generator.cpp:169-199): every emitted frame == the oracle's ETI assembly of that CIF's FIBs,
     FIG 0/0 counter and the oracle receiver's MSC bytes; frames are consecutive across calls."""
-    import test_eti as te
     subch = ds.default_subchannels(18, 64)
     ens = ds.build_ensemble(10, subch, seed=12, cif_start=240)          # CIF counter wraps 249 -> 0 inside the run
     x = ds.channel(ens.iq, snr_db=22.0, cfo_hz=77.0, timing_offset=2222, seed=4, n_out=22 * ds.TF)
-    ora = _oracle_run(x, subch)
+    ora = ol.oracle_run(x, subch)
     eng = dx.Engine(n_streams=1, ring_frames=23, max_subch=18, out_frames=8)
     eng.set_subchannels(subch)
     eng.push_iq(0, x)
@@ -607,7 +573,7 @@ def test_eti_frames_carry_the_fic_and_the_logical_frames_of_each_cif():
             if ora["crc"][F][3 * g]:
                 hi, lo = int(ora["fibs"][F][3 * g][4] & 0x1F), int(ora["fibs"][F][3 * g][5])
         msc = [ora["msc"][j].reshape(-1, 192)[r - 16] for j in range(18)]
-        want, _ = te._ora_frame(hi, lo, k, descs, fib[96 * k:96 * k + 96], msc)
+        want, _ = ol.ora_eti_frame(hi, lo, k, descs, fib[96 * k:96 * k + 96], msc)
         assert np.array_equal(f, want), i
         fct.append(int(f[4]))
     assert len(set(fct)) >= 30 and min(fct) < 10 and max(fct) > 240    # FCT ran through the 249 -> 0 wrap
@@ -618,11 +584,10 @@ def test_sixty_four_subchannels_discovered_decoded_and_packed_into_eti():
     """The most sub-channels an ensemble can carry (SubChId is 6 bits): 64 x 8 kbit/s EEP 3-A DAB+.  Discovery from the FIC
     (the FIG 0/1 / 0/2 description is spread over several FIBs and frames), decode of all 64 slots, per-slot counters and
     ETI frames with 64 stream-characterisation entries -- all equal to the oracle's."""
-    import test_eti as te
     subch = [ds.SubCh(i, 6 * i, 6, 8, 2, 0) for i in range(64)]
     ens = ds.build_ensemble(10, subch, seed=88)
     x = ds.channel(ens.iq, snr_db=18.0, cfo_hz=-120.0, timing_offset=1234, seed=88, n_out=22 * ds.TF)
-    ora = _oracle_run(x, subch)
+    ora = ol.oracle_run(x, subch)
     eng = dx.Engine(n_streams=1, ring_frames=23, max_subch=64, out_frames=8)
     eng.push_iq(0, x)
     eng.process(6)
@@ -656,7 +621,7 @@ def test_sixty_four_subchannels_discovered_decoded_and_packed_into_eti():
             if ora["crc"][F][3 * g]:
                 hi, lo = int(ora["fibs"][F][3 * g][4] & 0x1F), int(ora["fibs"][F][3 * g][5])
         msc = [ora["msc"][j].reshape(-1, 24)[r - 16] for j in range(64)]
-        want, _ = te._ora_frame(hi, lo, q, descs, fib[96 * q:96 * q + 96], msc)
+        want, _ = ol.ora_eti_frame(hi, lo, q, descs, fib[96 * q:96 * q + 96], msc)
         assert np.array_equal(frames[i], want), i
     eng.close()
 
@@ -677,7 +642,7 @@ def test_mixed_ensemble_uep_eep_a_b_bit_exact_and_discoverable():
     subch = _mixed_subchannels()
     ens = ds.build_ensemble(10, subch, seed=77)
     x = ds.channel(ens.iq, snr_db=16.0, cfo_hz=-840.0, timing_offset=91000, seed=6, n_out=24 * ds.TF)
-    ora = _oracle_run(x, subch)
+    ora = ol.oracle_run(x, subch)
     eng = dx.Engine(n_streams=1, ring_frames=25, max_subch=8, out_frames=4)
     eng.push_iq(0, x)
     eng.process(5)
@@ -713,7 +678,7 @@ def test_adding_a_service_does_not_disturb_running_ones():
     subch = ds.default_subchannels(18, 64)
     ens = ds.build_ensemble(10, subch, seed=52)
     x = ds.channel(ens.iq, snr_db=21.0, cfo_hz=150.0, timing_offset=1234, seed=3, n_out=24 * ds.TF)
-    ora = _oracle_run(x, subch)
+    ora = ol.oracle_run(x, subch)
     A, B = subch[4], subch[13]
     mk = lambda c: dx.SubchDesc(c.subch_id, c.cu_start, c.cu_size, c.kbps, c.prot_level, c.short_form, 1, 0)   # noqa: E731
     empty = dx.SubchDesc(0, 0, 0, 0, 0, 0, 0, 0)
@@ -795,7 +760,7 @@ def test_loss_of_lock_and_reacquisition_follow_the_oracle(gap_kind, acquire_mode
         x[a:b] = ((rng.standard_normal(b - a) + 1j * rng.standard_normal(b - a)) * 0.2).astype(np.complex64)
     else:                                                   # the transmitter jumps: 0.37 frame of samples vanish
         x = np.concatenate([x[:a], x[a + int(0.37 * ds.TF):]])
-    ora = _oracle_run(x, subch)
+    ora = ol.oracle_run(x, subch)
     eng = dx.Engine(n_streams=1, ring_frames=len(x) // ds.TF + 1, max_subch=18, out_frames=4, acquire_mode=acquire_mode)
     eng.set_subchannels(subch)
     if acquire_mode == 1:
@@ -851,7 +816,7 @@ def test_exact_level_tracker_is_bit_identical_to_the_oracle(gain):
     x = ds.channel(ens.iq, snr_db=16.0, cfo_hz=911.0, timing_offset=77777, gain=gain, seed=17, n_out=30 * ds.TF).copy()
     a, b = int(10.6 * ds.TF), int(12.2 * ds.TF)
     x[a:b] = 0                                                     # silence: the PRS correlation fails, back to the null-dip search
-    ora = _oracle_run(x, subch)
+    ora = ol.oracle_run(x, subch)
 
     def run(exact):
         eng = dx.Engine(n_streams=1, ring_frames=len(x) // ds.TF + 1, max_subch=4, out_frames=4, exact_level_tracker=exact)
@@ -907,7 +872,7 @@ def test_search_after_a_lost_lock_starts_from_the_references_level(gain):
     x = ds.channel(ens.iq, snr_db=16.0, cfo_hz=911.0, timing_offset=77777, gain=gain, seed=17, n_out=30 * ds.TF).copy()
     a, b = int(10.6 * ds.TF), int(14.4 * ds.TF)                   # a drop-out long enough for steps that search and find nothing
     x[a:b] = 0
-    ora = _oracle_run(x, subch)
+    ora = ol.oracle_run(x, subch)
 
     def run(mode):
         eng = dx.Engine(n_streams=1, ring_frames=len(x) // ds.TF + 1, max_subch=4, out_frames=4, exact_level_tracker=mode)
@@ -952,7 +917,7 @@ def test_level_anchor_that_has_left_the_ring_is_counted():
     ens = ds.build_ensemble(10, subch, seed=171)
     x = ds.channel(ens.iq, snr_db=16.0, cfo_hz=911.0, timing_offset=77777, gain=0.25, seed=17, n_out=30 * ds.TF).copy()
     x[int(10.6 * ds.TF):int(12.2 * ds.TF)] = 0
-    ora = _oracle_run(x, subch)
+    ora = ol.oracle_run(x, subch)
     eng = dx.Engine(n_streams=1, ring_frames=4, max_subch=4, out_frames=4)
     eng.set_subchannels(subch)
     starts, pushed = [], 0
@@ -1024,7 +989,7 @@ def test_zero_copy_producers_keep_the_level_anchor_by_announcing_their_writes(an
     x = ds.channel(ens.iq, snr_db=16.0, cfo_hz=911.0, timing_offset=77777, gain=0.25, seed=17, n_out=30 * ds.TF).copy()
     x[int(10.6 * ds.TF):int(14.4 * ds.TF)] = 0
     x = np.ascontiguousarray(x, np.complex64)
-    ora = _oracle_run(x, subch)
+    ora = ol.oracle_run(x, subch)
     eng = dx.Engine(n_streams=1, ring_frames=len(x) // ds.TF + 1, max_subch=4, out_frames=4)
     eng.set_subchannels(subch)
     ptr, cap = eng.ring_ptr(0)
@@ -1063,10 +1028,10 @@ def test_failed_sync_attempts_do_not_starve_a_stream():
     which goes straight back to the null-dip search (dab_processor.cpp:154-160, 396-400): the engine retries inside the step
     until a frame of samples is consumed.  (One attempt per step consumed 3.7 frames in 62 steps.)  The walk itself is the
     oracle's: same start indices, same FIBs."""
-    import test_gpu_fuzz as F
+    import fuzz_cases as F
     layouts, cases, xs, _ = F.draw_streams(5001, only=18)
     x, subch = xs[18], layouts[cases[18][0]]
-    ora = _oracle_run(x, subch, config=(4.0, 1, 2))
+    ora = ol.oracle_run(x, subch, config=(4.0, 1, 2))
     assert ora["n"] >= 14 and ora["start"][0] > 0
     eng = dx.Engine(n_streams=1, ring_frames=len(x) // ds.TF + 1, max_subch=len(subch), out_frames=4, sync_threshold=4.0, sync_strongest=True, soft_bit_type=2)
     eng.set_subchannels(subch)
@@ -1156,7 +1121,7 @@ def test_receiver_options_follow_the_oracle(threshold, strongest, soft_type):
     subch = ds.default_subchannels(18, 64)
     ens = ds.build_ensemble(10, subch, seed=90 + soft_type)
     x = ds.channel(ens.iq, snr_db=16.0, cfo_hz=700.0, timing_offset=66000, seed=11, n_out=22 * ds.TF)
-    ora = _oracle_run(x, subch, want_soft=True, config=(threshold, strongest, soft_type))
+    ora = ol.oracle_run(x, subch, want_soft=True, config=(threshold, strongest, soft_type))
     eng, fibs, crc, msc, starts, fbbs = _engine_run(x, subch, ora["n"], sync_threshold=threshold, sync_strongest=bool(strongest),
                                                     soft_bit_type=soft_type, capture_soft=True)
     n = min(len(fibs), ora["n"])
@@ -1185,7 +1150,7 @@ def test_sample_clock_offset_is_tracked_like_the_oracle(ppm):
     i0 = np.floor(t).astype(np.int64)
     fr = (t - i0).astype(np.float32)
     x = (x0[i0] * (1 - fr) + x0[i0 + 1] * fr).astype(np.complex64)
-    ora = _oracle_run(x, subch)
+    ora = ol.oracle_run(x, subch)
     eng, fibs, crc, msc, starts, fbbs = _engine_run(x, subch, ora["n"])
     n = min(len(fibs), ora["n"])
     assert n >= ora["n"] - 1 and n >= 22
@@ -1217,7 +1182,7 @@ def test_low_snr_error_paths_follow_the_oracle(snr):
     # the recording ends 30 000 samples into a frame: too short for the oracle to finish another CIF, so both sides have
     # decoded exactly the same CIFs and every counter is comparable
     x = ds.channel(ens.iq, snr_db=snr, cfo_hz=333.0, timing_offset=20000, seed=17, n_out=25 * ds.TF + 20000 + 30000)
-    ora = _oracle_run(x, subch)
+    ora = ol.oracle_run(x, subch)
     eng, fibs, crc, msc, starts, fbbs = _engine_run(x, subch, ora["n"])
     n = min(len(fibs), ora["n"])
     assert len(fibs) == ora["n"] and n >= 18
@@ -1265,7 +1230,7 @@ def test_largest_and_smallest_subchannels():
     subch = [ds.SubCh(1, 0, 240, 320, 2, 0), ds.SubCh(2, 300, 12, 8, 0, 0)]
     ens = ds.build_ensemble(10, subch, seed=131)
     x = ds.channel(ens.iq, snr_db=15.0, cfo_hz=410.0, timing_offset=7777, seed=19, n_out=23 * ds.TF + 50000)
-    ora = _oracle_run(x, subch)
+    ora = ol.oracle_run(x, subch)
     eng, fibs, crc, msc, starts, fbbs = _engine_run(x, subch, ora["n"])
     n = min(len(fibs), ora["n"])
     assert len(fibs) == ora["n"] and n >= 20
@@ -1293,7 +1258,7 @@ def test_maximum_dab_plus_rate_384_kbit_with_rs_corrections():
     subch = [ds.SubCh(1, 0, 288, 384, 2, 0), ds.SubCh(2, 400, 48, 64, 2, 0)]
     ens = ds.build_ensemble(10, subch, seed=133)
     x = ds.channel(ens.iq, snr_db=9.5, cfo_hz=-377.0, timing_offset=7777, seed=23, n_out=23 * ds.TF + 50000)
-    ora = _oracle_run(x, subch)
+    ora = ol.oracle_run(x, subch)
     eng, fibs, crc, msc, starts, fbbs = _engine_run(x, subch, ora["n"])
     n = min(len(fibs), ora["n"])
     assert len(fibs) == ora["n"] and n >= 20
@@ -1325,7 +1290,7 @@ def test_growing_the_largest_bit_rate_keeps_every_running_service_and_stream():
     ens_a, ens_b = ds.build_ensemble(10, sub_a, seed=71), ds.build_ensemble(10, sub_b, seed=72)
     xa = ds.channel(ens_a.iq, snr_db=19.0, cfo_hz=333.0, timing_offset=4321, seed=71, n_out=25 * ds.TF)
     xb = ds.channel(ens_b.iq, snr_db=18.0, cfo_hz=-712.0, timing_offset=99999, seed=72, n_out=25 * ds.TF)
-    ora_a, ora_b = _oracle_run(xa, sub_a), _oracle_run(xb, sub_b)
+    ora_a, ora_b = ol.oracle_run(xa, sub_a), ol.oracle_run(xb, sub_b)
     mk = lambda c: dx.SubchDesc(c.subch_id, c.cu_start, c.cu_size, c.kbps, c.prot_level, c.short_form, 1, 0)   # noqa: E731
     eng = dx.Engine(n_streams=2, ring_frames=26, max_subch=2, out_frames=8)
     eng.set_subchannels([mk(c) for c in sub_a], stream=0)               # largest rate so far: 64 kbit/s
@@ -1356,7 +1321,6 @@ def test_growing_the_largest_bit_rate_keeps_every_running_service_and_stream():
     eti_after = np.concatenate([eti_mid, eti_after])
     assert len(eti_after) == 12 * 4
     both = np.concatenate([eti_before, eti_after])
-    import test_eti as te
     descs = [mk(c) for c in sub_a]
     for i in (0, len(eti_before) - 1, len(eti_before), len(eti_before) + 1, len(both) - 1):   # either side of the change == oracle assembly
         r = 16 + i
@@ -1367,7 +1331,7 @@ def test_growing_the_largest_bit_rate_keeps_every_running_service_and_stream():
             if ora_a["crc"][F][3 * g]:
                 hi, lo = int(ora_a["fibs"][F][3 * g][4] & 0x1F), int(ora_a["fibs"][F][3 * g][5])
         msc = [ora_a["msc"][j].reshape(-1, 192)[r - 16] for j in range(2)]
-        want, _ = te._ora_frame(hi, lo, k, descs, fib[96 * k:96 * k + 96], msc)
+        want, _ = ol.ora_eti_frame(hi, lo, k, descs, fib[96 * k:96 * k + 96], msc)
         assert np.array_equal(both[i], want), i
     eng.subch = list(sub_b)
     for j, c in enumerate(sub_b):                                       # stream 1: started at its own CIF, bytes == oracle
@@ -1414,7 +1378,7 @@ def test_simd_viterbi_arithmetic_on_the_lane_per_trellis_decoder(mode, snr):
         eng.push_iq(s, xs[s])
     dx.check(dx.load().dabx_set_profiling(eng._h, 1))
     eng.process(n_frames)
-    launches = _kernel_launches(eng)
+    launches = kernel_launches(eng)
     dx.check(dx.load().dabx_set_profiling(eng._h, 0))
     assert launches["k_msc_vitT"] >= 4 and launches["k_msc_frame"] == 0, launches
     for s in (0, 3, 5):
@@ -1445,10 +1409,10 @@ def test_avx2_viterbi_build_of_the_reference_is_selectable_for_the_whole_receive
     ens = ds.build_ensemble(10, subch, seed=77)
     x = ds.channel(ens.iq, snr_db=4.3, cfo_hz=-150.0, timing_offset=31000, seed=77, n_out=24 * ds.TF)
     L = ol.oracle()
-    canon = _oracle_run(x, subch)
+    canon = ol.oracle_run(x, subch)
     L.ora_set_viterbi_mode(mode)
     try:
-        ora = _oracle_run(x, subch)
+        ora = ol.oracle_run(x, subch)
     finally:
         L.ora_set_viterbi_mode(0)
     eng = dx.Engine(n_streams=1, ring_frames=25, max_subch=18, out_frames=4, viterbi_tie_mode=mode)
@@ -1538,7 +1502,7 @@ def test_repeated_drop_outs_under_asynchronous_pushes_follow_the_oracle():
     for k in (9.6, 18.6, 27.6, 36.6):
         x[int(k * ds.TF):int((k + 1.7) * ds.TF)] = 0
     x = np.ascontiguousarray(x, np.complex64)
-    ora = _oracle_run(x, subch)
+    ora = ol.oracle_run(x, subch)
     ring = 6
     eng = dx.Engine(n_streams=1, ring_frames=ring, max_subch=4, out_frames=8)
     eng.set_subchannels(subch)

@@ -16,14 +16,8 @@ from dabstar_amd import lib as dx
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 from tools import dab_synth as ds  # noqa: E402
-from test_gpu_engine import _oracle_run  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-
-class FicBer(C.Structure):
-    _fields_ = [("bits", C.c_int32), ("errors", C.c_int32), ("status_bits", C.c_int32), ("status_errors", C.c_int32),
-                ("blocks", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
 @pytest.mark.parametrize("snr,tie", [(9.0, 0), (7.5, 0), (8.0, 1), (20.0, 0)])
@@ -35,7 +29,7 @@ def test_engine_ber_counters_equal_the_oracles_frame_by_frame(snr, tie):
     L = ol.oracle()
     L.ora_set_viterbi_mode(tie)
     try:
-        ora = _oracle_run(x, subch)
+        ora = ol.oracle_run(x, subch)
     finally:
         L.ora_set_viterbi_mode(0)
     eng = dx.Engine(n_streams=1, ring_frames=48, max_subch=1, fic_only=True, viterbi_tie_mode=tie)
@@ -91,7 +85,7 @@ def test_per_symbol_handle_reports_the_status_pair_of_the_40th_block():
             if blocks == 40:
                 status = (bits, errors)
                 blocks, errors, bits = 0, errors // 2, bits // 2
-        out = FicBer()
+        out = ol.FicBer()
         dx.check(L.dabx_fic_get_ber(h, C.byref(out)))
         assert (out.bits, out.errors, out.blocks) == (bits, errors, blocks), frame
         assert (out.status_bits, out.status_errors) == status, frame

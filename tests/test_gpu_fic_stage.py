@@ -14,7 +14,7 @@ import pytest
 
 import fic_cases as fc
 from dabstar_amd import lib as dx
-from test_gpu_fic_ber import FicBer
+from oracle_lib import FicBer
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
@@ -170,8 +170,8 @@ def test_the_test_entries_refuse_what_they_cannot_do():
 def test_the_entries_work_in_the_hipmodule_form():
     """The same engine test (tie mode 1) with the binding pointed at hipmodule/libdabx.so: k_fic_inject and its companions are found in
     the code objects and launched through hipModuleLaunchKernel."""
-    from test_gpu_hipmodule import _env
+    from hipmodule_env import hipmodule_env
     p = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider",
-                        "tests/test_gpu_fic_stage.py", "-k", "tie_mode_1 or refuse"], cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=600)
+                        "tests/test_gpu_fic_stage.py", "-k", "tie_mode_1 or refuse"], cwd=ROOT, env=hipmodule_env(), capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-3000:]
     assert "2 passed" in p.stdout and "failed" not in p.stdout, p.stdout[-500:]

@@ -9,22 +9,13 @@ import sys
 
 import pytest
 
+from hipmodule_env import MOD_DIR, ROOT, hipmodule_env
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-MOD_DIR = os.path.join(ROOT, "dabstar_amd", "hipmodule")
-
-
-def _env():
-    lib = os.path.join(MOD_DIR, "libdabx.so")
-    if not os.path.exists(lib) or not any(f.endswith(".hsaco") for f in os.listdir(MOD_DIR)):
-        subprocess.run([sys.executable, "-m", "dabstar_amd.build", "--hipmodule"], check=True, cwd=ROOT, capture_output=True)
-    env = dict(os.environ, DABX_LIB=lib)
-    env["LD_LIBRARY_PATH"] = MOD_DIR + os.pathsep + env.get("LD_LIBRARY_PATH", "")
-    return env
 
 
 def test_the_library_has_no_device_code_of_its_own():
-    env = _env()
+    env = hipmodule_env()
     out = subprocess.run(["readelf", "-S", "-W", env["DABX_LIB"]], capture_output=True, text=True, check=True).stdout
     assert ".hip_fatbin" not in out                                    # the default build keeps its code objects there
     assert sorted(f for f in os.listdir(MOD_DIR) if f.endswith(".hsaco")) == [
@@ -36,13 +27,13 @@ def test_the_library_has_no_device_code_of_its_own():
 def test_smoke_through_hipmodule_launches():
     code = ("import ctypes, __graft_entry__ as g; from dabstar_amd import lib as dx; "
             "assert dx.load().dabx_internal_hipmodule() == 1; g.smoke()")
-    p = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=600)
+    p = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=hipmodule_env(), capture_output=True, text=True, timeout=600)
     assert p.returncode == 0 and "smoke ok" in p.stdout, (p.stdout[-1000:], p.stderr[-2000:])
 
 
 def test_shims_stage_entries_and_an_engine_run_in_hipmodule_form():
     p = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider",
                         "tests/test_shims.py", "tests/test_gpu_stages.py", "tests/test_gpu_viterbi.py", "tests/test_gpu_config3.py"],
-                       cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=1200)
+                       cwd=ROOT, env=hipmodule_env(), capture_output=True, text=True, timeout=1200)
     assert p.returncode == 0, p.stdout[-3000:]
     assert " passed" in p.stdout and "failed" not in p.stdout, p.stdout[-500:]

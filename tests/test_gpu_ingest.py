@@ -11,7 +11,7 @@ from dabstar_amd import lib as dx
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 from tools import dab_synth as ds  # noqa: E402
-from test_gpu_engine import _oracle_run  # noqa: E402
+from oracle_lib import oracle_run  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 TF = ds.TF
@@ -85,7 +85,7 @@ def test_slab_ingest_decodes_like_per_stream_pushes_and_like_the_oracle(dtype, c
     want = np.ascontiguousarray(_dequantise(xs[1][: n_chunks * per], dtype))[wr - ring:wr]
     assert np.array_equal(a.read_iq(1, wr - ring, ring).view(np.uint32), want.view(np.uint32))
     # ... and stream 1 against the oracle receiver on the samples as the device sees them
-    ora = _oracle_run(np.ascontiguousarray(_dequantise(xs[1][: n_chunks * per], dtype)), subch)
+    ora = oracle_run(np.ascontiguousarray(_dequantise(xs[1][: n_chunks * per], dtype)), subch)
     f = a.stats(1)["frames"]
     fa, ca = a.read_fibs(1, 8)
     assert f <= ora["n"] and np.array_equal(fa, ora["fibs"][f - 8:f]) and np.array_equal(ca, ora["crc"][f - 8:f])
@@ -192,7 +192,7 @@ def test_slab_ingest_of_recordings_at_three_rates_and_unequal_lengths():
         cap = used.size + 4096
         x = np.zeros(cap, np.complex64)
         n = ol.oracle().ora_iq_convert(f.family, f.container, f.big_endian, f.swap_iq, f.bits, f.sample_rate, used, used.size, x.ctypes.data, cap)
-        ora = _oracle_run(np.ascontiguousarray(x[:n]), subch)
+        ora = oracle_run(np.ascontiguousarray(x[:n]), subch)
         fr = a.stats(s)["frames"]
         fa, ca = a.read_fibs(s, 8)
         assert fr <= ora["n"] and np.array_equal(fa, ora["fibs"][fr - 8:fr]) and np.array_equal(ca, ora["crc"][fr - 8:fr]), s

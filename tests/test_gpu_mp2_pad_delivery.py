@@ -18,8 +18,8 @@ from dabstar_amd import lib as dx
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 from tools import dab_synth as ds  # noqa: E402
-from test_gpu_engine import _oracle_run  # noqa: E402
-from test_gpu_pad_delivery import CHUNK_COUNTERS, Sink  # noqa: E402
+from delivery_sink import CHUNK_COUNTERS, PAD, assert_tail_is_what_the_reader_returns, run  # noqa: E402
+from oracle_lib import oracle_run  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -41,34 +41,15 @@ def test_the_section_carries_every_item_of_both_sources_and_equals_the_per_slot_
     pay = {DABPLUS[0]: np.concatenate([a[-16:], a[:4 * N_TX - 16]]), MP2[0]: np.concatenate([b[-16:], b[:-16]])}
     ens = ds.build_ensemble(N_TX, subch, seed=12, payloads=pay)
     x = ds.channel(ens.iq, snr_db=22.0, cfo_hz=217.0, timing_offset=5555, seed=12, n_out=(N_TX + 1) * ds.TF)
-    ora = _oracle_run(x, subch)
-    M = len(subch)
-    eng = dx.Engine(n_streams=STREAMS, ring_frames=N_TX + 2, max_subch=M, out_frames=8)
-    try:
-        eng.set_subchannels(subch)
-        for s in range(STREAMS):
-            eng.set_pad_mode(s, DABPLUS[0])
-            eng.set_pad_mode(s, MP2[0], source="mp2")
-        eng.delivery_open(slots=4, what=0)
-        for s in range(STREAMS):
-            eng.push_iq(s, x)
-        sink = Sink(eng, STREAMS, M)
-        sink.start()
-        try:
-            for m in (3, 7, 1, 14, 4):
-                eng.process(m, sync=False)
-                sink.expect((m + 6) // 7)
-            eng.synchronize()
-        finally:
-            sink.finish()
-        assert sink.error is None and eng.delivery_next(wait=False) is None
-        direct = {(s, j): (eng.pad_stats(s, j), eng.read_pad_items(s, j, 512), eng.subch_stats(s, j), eng.mp2_sync_stats(s, j))
-                  for s in range(STREAMS) for j in (DABPLUS[0], MP2[0])}
-        frames = [eng.stats(s)["frames"] for s in range(STREAMS)]
-        eng.delivery_close()
-    finally:
-        eng.close()
-    assert all(sink.off_pad) and all(w == 7 | dx.DELIVER_PAD for w in sink.whats)
+    ora = oracle_run(x, subch)
+    def switch_on(eng, s):
+        eng.set_pad_mode(s, DABPLUS[0])
+        eng.set_pad_mode(s, MP2[0], source="mp2")
+        return [DABPLUS[0], MP2[0]]
+
+    sink, direct, frames, _ = run(x, subch, 0, PAD, STREAMS, N_TX + 2, switch_on,
+                                  lambda eng, s, j: (eng.pad_stats(s, j), eng.read_pad_items(s, j, 512), eng.subch_stats(s, j), eng.mp2_sync_stats(s, j)))
+    assert all(sink.off) and all(w == 7 | dx.DELIVER_PAD for w in sink.whats)
     for s in range(STREAMS):
         assert frames[s] >= 26, frames
         for j, kbps, _ in (DABPLUS, MP2):
@@ -92,8 +73,4 @@ def test_the_section_carries_every_item_of_both_sources_and_equals_the_per_slot_
             assert all(st[k] == int(sink.last[(s, j)][k]) for k in CHUNK_COUNTERS), (s, j, st, sink.last[(s, j)])
             assert st["items_lost"] == 0 and st["active"] == 1
             # ... and they are what the per-slot reader returns (its byte_pos counts from its own first item)
-            k = len(r2)
-            assert k == min(len(rec), 512) > 0
-            tail = rec[-k:].copy()
-            tail["byte_pos"] -= tail["byte_pos"][0]
-            assert r2.tobytes() == tail.tobytes() and np.array_equal(b2, by[len(by) - len(b2):])
+            assert_tail_is_what_the_reader_returns(rec, by, r2, b2, 512)

@@ -17,22 +17,11 @@ import mp2_pad_cases as mc
 import packet_cases as pkc
 import pad_cases as pc
 from dabstar_amd import lib as dx
+from stage_driver import PAD_ITEMS, Follower, drive, engine, kernel_launches, mp2_batch_mismatches, mp2_final_mismatches, packet_follower
 
 pytestmark = pytest.mark.gpu
 
 H, B = dc.HISTORY, dc.BATCH
-
-
-def _engine(n_streams, max_subch, fast_min=1, class_min=1):
-    eng = dx.Engine(n_streams=n_streams, ring_frames=2, max_subch=max_subch, out_frames=1, msc_fast_min_jobs=fast_min, msc_class_min_jobs=class_min)
-    dx.check(dx.load().dabx_set_profiling(eng._h, 1))
-    return eng
-
-
-def _kernel_launches(eng):
-    ms = (C.c_double * 16)(); cnt = (C.c_int64 * 16)(); names = (C.c_char_p * 16)()
-    nk = dx.check(dx.load().dabx_get_profile(eng._h, ms, cnt, names))
-    return {names[i].decode(): int(cnt[i]) for i in range(nk)}
 
 
 def _slots(s, *kinds):
@@ -48,135 +37,44 @@ def _state(eng, i, s):
     return out
 
 
-def _check_mp2_slot(eng, i, j, m, n, g, tag):
-    """Slot (i, j) after n logical frames against the model's snapshot: the new items and bytes, dabx_pad_stats, dabx_mp2_sync_stats."""
-    bad = []
-    items, n_bytes, counters, sync = m.snaps[n]
-    st, sy = eng.pad_stats(i, j), eng.mp2_sync_stats(i, j)
-    for k in pc.PAD_COUNTERS:
-        if st[k] != counters[k]:
-            bad.append(tag + "after %d frames %s = %d, the model's %d" % (n, k, st[k], counters[k]))
-    if st["items_lost"] != 0 or st["active"] != 1:
-        bad.append(tag + "after %d frames items_lost / active: %s" % (n, st))
-    for k in mc.SYNC_FIELDS:
-        if sy[k] != sync[k]:
-            bad.append(tag + "after %d frames sync %s = %d, the model's %d" % (n, k, sy[k], sync[k]))
-    new = st["labels"] + st["groups"] - g["item_seen"]
-    assert 0 <= new <= 112, (tag, new)                              # pad_core.h: 28 logical frames x 4 sub-fields
-    if new:
-        rec, by = eng.read_pad_items(i, j, new)
-        assert len(rec) == new and rec["byte_pos"][0] == 0, (tag, new, len(rec))
-        rec = rec.copy()
-        rec["byte_pos"] += g["byte_seen"]
-        g["rec"].append(rec); g["bytes"].append(by)
-        want = m.pad.records()[g["item_seen"]:items]
-        if rec.tobytes() != want.tobytes():
-            d = [k for k in range(min(len(rec), len(want))) if rec[k].tobytes() != want[k].tobytes()][:3]
-            bad.append(tag + "after %d frames %d new items, the model has %d; first differences %s" % (n, len(rec), len(want), [(k, rec[k].tolist(), want[k].tolist()) for k in d]))
-        if not np.array_equal(by, m.pad.all_bytes()[g["byte_seen"]:n_bytes]):
-            bad.append(tag + "after %d frames the new items' bytes differ (%d, the model has %d)" % (n, len(by), n_bytes - g["byte_seen"]))
-    g["item_seen"] += new
-    g["byte_seen"] = st["label_bytes"] + st["group_bytes"]
-    return bad
+def _switch_on(eng, i, s, mp2):
+    for j, (kbps, kind) in enumerate(mc.kinds(s)):
+        if kind == "pad":
+            eng.set_pad_mode(i, j)
+        elif kind == "mp2" and mp2:
+            eng.set_pad_mode(i, j, source="mp2")
+        elif kind == "pkt":
+            eng.set_packet_mode(i, j, mc.PACKET_ADDRESS)
+
+
+def _follower(kbps, kind):
+    if kind == "pkt":
+        return packet_follower(kbps)
+    return Follower(PAD_ITEMS, 112 if kind == "mp2" else 144)      # pad_core.h: 28 logical frames, or 6 super frames x 6 AUs, x 4 sub-fields
 
 
 def _drive(eng, streams, schedule, mp2=True):
-    """Configures streams (indices into mc.STAGE_STREAMS), 16 CIFs of history, then one MSC batch per row of `schedule`.  After every batch
-    the MP2 slots are compared with the model, the new logical frames of every slot, the new items of the DAB+ PAD slots and the new data
-    groups of the packet slot are read and appended; a stream that received nothing must hold byte for byte what it held.  mp2 = False:
-    the same streams with their MP2 slots left as plain slots."""
+    """stage_driver.drive on streams (indices into mc.STAGE_STREAMS).  After every batch the MP2 slots are compared with the model, the new
+    logical frames of every slot, the new items of the DAB+ PAD slots and the new data groups of the packet slot are read and appended; a
+    stream that received nothing must hold byte for byte what it held.  mp2 = False: the same streams with their MP2 slots left as plain
+    slots."""
     cases = [mc.stream_case(s) for s in streams]
-    S = len(streams)
-    got, bad = {}, []
-    for i, s in enumerate(streams):
-        layout, _, cifs, _ = cases[i]
-        eng.set_subchannels(layout, stream=i)
-        for j, (kbps, kind) in enumerate(mc.kinds(s)):
-            if kind == "pad":
-                eng.set_pad_mode(i, j)
-            elif kind == "mp2" and mp2:
-                eng.set_pad_mode(i, j, source="mp2")
-            elif kind == "pkt":
-                eng.set_packet_mode(i, j, mc.PACKET_ADDRESS)
-            got[(i, j)] = {"frames": [], "rec": [], "bytes": [], "item_seen": 0, "byte_seen": 0, "dg": [], "dg_bytes": [], "dg_seen": 0}
-        dx.msc_inject(eng, i, cifs[:H])
-    dx.msc_decode(eng, [H] * S, H)
-    at = [H] * S
-    for counts in schedule:
-        before = {i: _state(eng, i, streams[i]) for i in range(S) if counts[i] == 0}
-        for i in range(S):
-            if counts[i]:
-                dx.msc_inject(eng, i, cases[i][2][at[i]:at[i] + counts[i]])
-        dx.msc_decode(eng, counts, B)
-        for i, s in enumerate(streams):
-            if counts[i] == 0:
-                assert _state(eng, i, s) == before[i], "stream %d received nothing in this batch and changed" % i
-                continue
-            at[i] += counts[i]
-            eng.subch = list(cases[i][0])
-            for j, (kbps, kind) in enumerate(mc.kinds(s)):
-                g = got[(i, j)]
-                fr = eng.read_msc(i, j, counts[i])
-                assert fr.shape[0] == counts[i], (i, j, fr.shape)
-                g["frames"].append(fr)
-                tag = "stream %d slot %d (%d kbit/s, %s): " % (i, j, kbps, kind)
-                if kind == "mp2" and mp2:
-                    bad += _check_mp2_slot(eng, i, j, mc.slot_model(s, j), at[i] - H, g, tag)
-                elif kind == "pad":
-                    st = eng.pad_stats(i, j)
-                    new = st["labels"] + st["groups"] - g["item_seen"]
-                    if new:
-                        rec, by = eng.read_pad_items(i, j, new)
-                        assert len(rec) == new
-                        rec = rec.copy()
-                        rec["byte_pos"] += g["byte_seen"]
-                        g["rec"].append(rec); g["bytes"].append(by)
-                    g["item_seen"] += new
-                    g["byte_seen"] = st["label_bytes"] + st["group_bytes"]
-                elif kind == "pkt":
-                    new = eng.packet_stats(i, j)["dg_count"] - g["dg_seen"]
-                    if new:
-                        rec, by = eng.read_datagroups(i, j, new)
-                        assert len(rec) == new
-                        g["dg"].append(rec["length"].copy()); g["dg_bytes"].append(by)
-                    g["dg_seen"] += new
-    for (i, j), g in got.items():
-        g["frames"] = np.concatenate(g["frames"])
-        g["rec"] = np.concatenate(g["rec"]) if g["rec"] else np.zeros(0, dx.PAD_ITEM)
-        g["bytes"] = np.concatenate(g["bytes"]) if g["bytes"] else np.zeros(0, np.uint8)
-        g["dg"] = np.concatenate(g["dg"]) if g["dg"] else np.zeros(0, np.uint16)
-        g["dg_bytes"] = np.concatenate(g["dg_bytes"]) if g["dg_bytes"] else np.zeros(0, np.uint8)
-        g["pstats"], g["sync"], g["kstats"] = eng.pad_stats(i, j), eng.mp2_sync_stats(i, j), eng.packet_stats(i, j)
-    return got, cases, bad
-
-
-def _final_mismatches(got, cases, streams, mp2=True):
-    """The whole run of every slot: logical frames against the oracle back end, MP2 slots against the model, DAB+ PAD slots against
-    pad_cases' model on the oracle's super frames, the other slots show no PAD results."""
+    followers = {(i, j): _follower(kbps, kind) for i, s in enumerate(streams) for j, (kbps, kind) in enumerate(mc.kinds(s))
+                 if kind in ("pad", "pkt") or (kind == "mp2" and mp2)}
     bad = []
-    for (i, j), g in sorted(got.items()):
-        s = streams[i]
-        kbps, kind = mc.kinds(s)[j]
-        tag = "stream %d slot %d (%d kbit/s, %s): " % (i, j, kbps, kind)
-        o = cases[i][3][j]
-        if not np.array_equal(g["frames"], o["frames"]) or not np.array_equal(g["frames"], cases[i][1][j]):
-            bad.append(tag + "logical frames differ from the oracle's or the intended ones")
-        if kind == "mp2" and mp2:
-            m = mc.slot_model(s, j)
-            if g["rec"].tobytes() != m.pad.records().tobytes() or not np.array_equal(g["bytes"], m.pad.all_bytes()):
-                bad.append(tag + "the items of the whole run differ from the model's (%d, the model has %d)" % (len(g["rec"]), len(m.pad.rows)))
-            if g["sync"] != m.sync_stats():
-                bad.append(tag + "sync stats %s, the model's %s" % (g["sync"], m.sync_stats()))
-        elif kind == "pad":
-            m = pc.run_model(o["sf"], o["sfi"])
-            if g["rec"].tobytes() != m.records().tobytes() or not np.array_equal(g["bytes"], m.all_bytes()) or \
-               any(g["pstats"][k] != m.counters[k] for k in pc.PAD_COUNTERS) or g["pstats"]["items_lost"] != 0:
-                bad.append(tag + "the DAB+ PAD slot differs from pad_cases' model")
-            if any(g["sync"].values()):
-                bad.append(tag + "a DAB+ PAD slot shows MP2 sync stats: %s" % g["sync"])
-        elif any(g["pstats"].values()) or any(g["sync"].values()) or len(g["rec"]):
-            bad.append(tag + "no PAD decoding and shows PAD results: %s %s" % (g["pstats"], g["sync"]))
-    return bad
+
+    def after_batch(i, n, taken):
+        for j, (kbps, kind) in enumerate(mc.kinds(streams[i])):
+            if kind == "mp2" and mp2:
+                tag = "stream %d slot %d (%d kbit/s, %s): " % (i, j, kbps, kind)
+                bad.extend(mp2_batch_mismatches(tag, mc.slot_model(streams[i], j), n, taken[j], eng.mp2_sync_stats(i, j)))
+
+    got = drive(eng, cases, schedule, lambda eng, i: _switch_on(eng, i, streams[i], mp2), followers, lambda eng, i: _state(eng, i, streams[i]), after_batch)
+    for (i, j), g in got.items():
+        g["pstats"], g["sync"], g["kstats"] = eng.pad_stats(i, j), eng.mp2_sync_stats(i, j), eng.packet_stats(i, j)
+        if mc.kinds(streams[i])[j][1] == "pkt":                     # the packet slot's groups are no PAD items
+            g["dg"], g["dg_bytes"], g["rec"], g["bytes"] = g["rec"], g["bytes"], g["rec"][:0], g["bytes"][:0]
+    return got, cases, bad
 
 
 _runs = {}
@@ -186,15 +84,15 @@ def test_every_mp2_slot_equals_the_model_after_every_batch_behind_the_lane_per_t
     """Full batches of 28 CIFs, k_msc_prep + k_msc_vitT as the only decoder.  The stage (k_pad and k_pad_mp2 inside one marker) ran once per
     batch."""
     streams = list(range(len(mc.STAGE_STREAMS)))
-    eng = _engine(len(streams), 5)
+    eng = engine(len(streams), 5)
     try:
         got, cases, bad = _drive(eng, streams, [[B] * len(streams)] * mc.N_BATCHES)
-        launches = _kernel_launches(eng)
+        launches = kernel_launches(eng)
     finally:
         eng.close()
     print(launches)
     assert launches["k_pad"] == mc.N_BATCHES + 1 == launches["k_dabplus"] == launches["k_msc_vitT"] and launches["k_msc_frame"] == 0, launches
-    bad += _final_mismatches(got, cases, streams)
+    bad += mp2_final_mismatches(got, cases, streams)
     assert not bad, "%d differences:\n%s" % (len(bad), "\n".join(bad[:25]))
     total = {k: sum(g["pstats"][k] for (i, j), g in got.items() if mc.kinds(streams[i])[j][1] == "mp2") for k in pc.PAD_COUNTERS}
     assert all(v > 0 for v in total.values()), total                # every counter was exercised on the device by the MP2 slots alone
@@ -207,15 +105,15 @@ def test_sync_and_items_across_batch_boundaries_and_idle_batches_behind_the_wave
     the only decoder here; the results are also byte for byte those of the full-batch run."""
     streams = list(range(len(mc.STAGE_STREAMS)))
     schedule = mc.boundary_schedule(len(streams))
-    eng = _engine(len(streams), 5, fast_min=1 << 30, class_min=0)
+    eng = engine(len(streams), 5, fast_min=1 << 30, class_min=0)
     try:
         got, cases, bad = _drive(eng, streams, schedule)
-        launches = _kernel_launches(eng)
+        launches = kernel_launches(eng)
     finally:
         eng.close()
     print(launches)
     assert launches["k_pad"] == len(schedule) + 1 == launches["k_msc_frame"] and launches["k_msc_vitT"] == 0, launches
-    bad += _final_mismatches(got, cases, streams)
+    bad += mp2_final_mismatches(got, cases, streams)
     assert not bad, "%d differences:\n%s" % (len(bad), "\n".join(bad[:25]))
     if "full" in _runs:
         for key, g in got.items():
@@ -231,12 +129,12 @@ def test_the_dabplus_pad_slots_and_the_packet_slot_give_what_they_give_without_a
         if mp2 and "full" in _runs:
             runs.append({k: g for k, g in _runs["full"].items() if k[0] in streams})
             continue
-        eng = _engine(len(streams), 5)
+        eng = engine(len(streams), 5)
         try:
             got, cases, bad = _drive(eng, streams, [[B] * len(streams)] * mc.N_BATCHES, mp2=mp2)
         finally:
             eng.close()
-        bad += _final_mismatches(got, cases, streams, mp2=mp2)
+        bad += mp2_final_mismatches(got, cases, streams, mp2=mp2)
         assert not bad, "\n".join(bad[:25])
         runs.append(got)
     n_pad = n_pkt = 0
@@ -248,7 +146,7 @@ def test_the_dabplus_pad_slots_and_the_packet_slot_give_what_they_give_without_a
             assert a["rec"].tobytes() == b["rec"].tobytes() and np.array_equal(a["bytes"], b["bytes"]) and a["pstats"] == b["pstats"] and len(a["rec"]) > 0, (i, j)
             n_pad += 1
         elif kind == "pkt":
-            assert np.array_equal(a["dg"], b["dg"]) and np.array_equal(a["dg_bytes"], b["dg_bytes"]) and a["kstats"] == b["kstats"] and len(a["dg"]) > 0, (i, j)
+            assert a["dg"].tobytes() == b["dg"].tobytes() and np.array_equal(a["dg_bytes"], b["dg_bytes"]) and a["kstats"] == b["kstats"] and len(a["dg"]) > 0, (i, j)
             n_pkt += 1
         elif kind == "mp2":
             assert not any(b["pstats"].values()) and not any(b["sync"].values()) and len(b["rec"]) == 0, (i, j, b["pstats"])
@@ -266,7 +164,7 @@ def test_mp2_pad_on_off_and_on_again_leaves_the_logical_frames_the_oracles_and_t
     assert mc.kinds(s)[j] == (128, "mp2")
     results = []
     for mode in ("never", "mp2 only", "toggled"):
-        eng = _engine(1, len(layout))
+        eng = engine(1, len(layout))
         try:
             eng.set_subchannels(layout, stream=0)
             dx.msc_inject(eng, 0, cifs[:H])
@@ -286,7 +184,7 @@ def test_mp2_pad_on_off_and_on_again_leaves_the_logical_frames_the_oracles_and_t
                     assert eng.pad_stats(0, j)["active"] == 0 and not any(eng.mp2_sync_stats(0, j).values()) and len(eng.read_pad_items(0, j, 8)[0]) == 0
             for k in range(len(layout)):
                 assert np.array_equal(np.concatenate(got[k]), want[k]["frames"]), (mode, k)
-            results.append((eng.pad_stats(0, j), eng.mp2_sync_stats(0, j), eng.read_pad_items(0, j, 512), _kernel_launches(eng)))
+            results.append((eng.pad_stats(0, j), eng.mp2_sync_stats(0, j), eng.read_pad_items(0, j, 512), kernel_launches(eng)))
         finally:
             eng.close()
     st, sy, (rec, by), launches = results[0]
@@ -320,19 +218,19 @@ def test_an_mp2_slot_that_moves_to_other_capacity_units_in_the_middle_of_the_lon
     assert done - 80 < b_move * B < done - 5, (done, b_move)          # the group takes 86 logical frames: the move falls inside it
     move = H + b_move * B
     cifs = np.concatenate([c_old[:move], c_new[move:]])
-    eng = _engine(1, 2)
+    eng = engine(1, 2)
     try:
         eng.set_subchannels(old, stream=0)
         eng.set_pad_mode(0, 1, source="mp2")
         dx.msc_inject(eng, 0, cifs[:H])
         dx.msc_decode(eng, [H], H)
-        g, bad = {"rec": [], "bytes": [], "item_seen": 0, "byte_seen": 0}, []
+        ring, bad = Follower(PAD_ITEMS, 112), []
         for b in range(mc.N_BATCHES):
             if b == b_move:
                 eng.set_subchannels(new, stream=0)
             dx.msc_inject(eng, 0, cifs[H + B * b:H + B * (b + 1)])
             dx.msc_decode(eng, [B], B)
-            bad += _check_mp2_slot(eng, 0, 1, m, B * (b + 1), g, "batch %d: " % b)
+            bad += mp2_batch_mismatches("batch %d: " % b, m, B * (b + 1), ring.take(eng, 0, 1), eng.mp2_sync_stats(0, 1))
         eng.subch = list(new)
         last = eng.read_msc(0, 1, B)
         changed = dc.dabplus_layout([(64, mc.PROT, 0), (kbps, 2, 0)], dab_plus=[0, 0])
@@ -341,7 +239,7 @@ def test_an_mp2_slot_that_moves_to_other_capacity_units_in_the_middle_of_the_lon
     finally:
         eng.close()
     assert not bad, "\n".join(bad[:25])
-    assert np.array_equal(last, frames[-B:]) and g["item_seen"] == len(m.pad.rows) and np.array_equal(np.concatenate(g["bytes"]), m.pad.all_bytes())
+    assert np.array_equal(last, frames[-B:]) and ring.seen == len(m.pad.rows) and np.array_equal(ring.result()[1], m.pad.all_bytes())
     assert not any(after.values()) and not any(after_sync.values()), (after, after_sync)
 
 
@@ -350,7 +248,7 @@ def test_the_refusals():
     DAB+ on a plain slot is refused as before; a slot whose PAD decoding is on cannot become a packet-mode slot; a configuration too short to
     hold `source` means DAB+."""
     layout = mc.stage_layout(0)                                       # 8 mp2, 384 mp2, 64 DAB+, 16 pkt, 56 mp2
-    eng = _engine(1, 6)
+    eng = engine(1, 6)
     L = dx.load()
     try:
         eng.set_subchannels(layout, stream=0)

@@ -6,31 +6,17 @@ entries, no IQ, no front end), so the decoder sees exact ties, saturated and out
 decode -- input on which a Viterbi decoder does NOT correct a fault in its own input path, unlike the >= 15 dB demapper output of
 the engine tests.  Generators, layouts and the coverage facts: tests/msc_cases.py, proven on the CPU in tests/test_msc_cases.py.
 Every comparison is np.array_equal on logical-frame bytes and on cifs_decoded; the oracle is the only reference."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import msc_cases as mc
 from dabstar_amd import lib as dx
+from stage_driver import engine, kernel_launches
 
 pytestmark = pytest.mark.gpu
 
 H, B = mc.HISTORY, mc.BATCH
 E_ARG = -2                          # DABX_E_ARG (include/dabx.h)
-
-
-def _engine(n_streams, max_subch, tie_mode=0, fast_min=1, class_min=1):
-    eng = dx.Engine(n_streams=n_streams, ring_frames=2, max_subch=max_subch, out_frames=1, viterbi_tie_mode=tie_mode,
-                    msc_fast_min_jobs=fast_min, msc_class_min_jobs=class_min)
-    dx.check(dx.load().dabx_set_profiling(eng._h, 1))
-    return eng
-
-
-def _kernel_launches(eng):
-    ms = (C.c_double * 16)(); cnt = (C.c_int64 * 16)(); names = (C.c_char_p * 16)()
-    nk = dx.check(dx.load().dabx_get_profile(eng._h, ms, cnt, names))
-    return {names[i].decode(): int(cnt[i]) for i in range(nk)}
 
 
 def _history_then_one_batch(eng, cifs):
@@ -66,11 +52,11 @@ def _run_layout(layout, n_streams, seed, tie_mode=0, expect_vitT=True):
     """One engine, the layout on every stream, every stream its own data: (mismatches, per stream the input-class names and
     the CIFs).  Asserts which decoder ran."""
     data = [mc.stream_cifs(layout, s, H + B, seed) for s in range(n_streams)]
-    eng = _engine(n_streams, len(layout), tie_mode)
+    eng = engine(n_streams, len(layout), tie_mode=tie_mode)
     try:
         eng.set_subchannels(layout, dab_plus=False)
         _history_then_one_batch(eng, [d[0] for d in data])
-        launches = _kernel_launches(eng)
+        launches = kernel_launches(eng)
         if expect_vitT:      # every slot is a lane-per-trellis class: nothing may fall back to the wave-per-trellis kernel
             assert launches["k_msc_vitT"] == 2 and launches["k_msc_prep"] == 2 and launches["k_msc_frame"] == 0, launches
         else:                # the padded UEP rows: k_msc_frame is the only kernel that takes them
@@ -158,7 +144,7 @@ def test_lanes_with_nothing_to_decode_leave_the_outputs_alone():
     total = [H + counts[0][s] + counts[1][s] for s in range(S)]
     data = [mc.stream_cifs(lays[s], s, total[s], 3000) for s in range(S)]
     want = [mc.oracle_frames(lays[s], data[s][0]) for s in range(S)]
-    eng = _engine(S, len(layout))
+    eng = engine(S, len(layout))
     try:
         for s in range(S):
             eng.set_subchannels(lays[s], stream=s, dab_plus=False)
@@ -192,7 +178,7 @@ def test_lanes_with_nothing_to_decode_leave_the_outputs_alone():
             assert np.array_equal(snapshots[0][(3, j)][0], snapshots[1][(3, j)][0]) and snapshots[0][(3, j)][1] == snapshots[1][(3, j)][1]
         # the slot that is not configured stays empty
         assert eng.subch_stats(4, 1)["active"] == 0 and eng.subch_stats(4, 1)["cifs_decoded"] == 0
-        launches = _kernel_launches(eng)
+        launches = kernel_launches(eng)
         assert launches["k_msc_vitT"] == 3 and launches["k_msc_prep"] == 3 and launches["k_msc_frame"] == 0, launches
     finally:
         eng.close()
@@ -213,7 +199,7 @@ def test_more_than_one_round_of_decoder_groups():
     for s in (0, S // 2, S - 1):
         rounds = {((len(layout) - 1) * per_class + (k * S + s) // 64) // 1024 for k in range(B)}
         assert rounds == {0, 1}
-    eng = _engine(S, len(layout))
+    eng = engine(S, len(layout))
     try:
         eng.set_subchannels(layout, dab_plus=False)
         keep = []
@@ -225,7 +211,7 @@ def test_more_than_one_round_of_decoder_groups():
         for s in range(S):
             dx.msc_inject(eng, s, keep[s][0][H:])
         dx.msc_decode(eng, [B] * S, B)
-        launches = _kernel_launches(eng)
+        launches = kernel_launches(eng)
         assert launches["k_msc_vitT"] == 2 and launches["k_msc_frame"] == 0, launches
         bad = []
         for s in range(S):
@@ -249,12 +235,12 @@ def test_both_decoders_share_a_batch_and_agree():
     want = [mc.oracle_frames(lays[s], data[s][0]) for s in range(S)]
     outputs = []
     for fast_min, class_min, vitT, frame in ((1, 84, True, True), (1, 1, True, False), (1 << 30, 1, False, True)):
-        eng = _engine(S, len(full), fast_min=fast_min, class_min=class_min)
+        eng = engine(S, len(full), fast_min=fast_min, class_min=class_min)
         try:
             for s in range(S):
                 eng.set_subchannels(lays[s], stream=s, dab_plus=False)
             _history_then_one_batch(eng, [d[0] for d in data])
-            launches = _kernel_launches(eng)
+            launches = kernel_launches(eng)
             assert (launches["k_msc_vitT"] > 0) == vitT and (launches["k_msc_frame"] > 0) == frame, launches
             bad = []
             for s in range(S):
@@ -269,7 +255,7 @@ def test_both_decoders_share_a_batch_and_agree():
 
 
 def test_the_injection_entries_refuse_what_would_leave_the_ring():
-    eng = _engine(2, 2)
+    eng = engine(2, 2)
     try:
         eng.set_subchannels(mc.layout_of([(8, 1, 0), (16, 2, 0)]), dab_plus=False)
         soft = np.zeros((B + 1, mc.CIF_BITS), np.int16)

@@ -7,32 +7,17 @@ model that the scenarios reach every branch and both guards).  Four streams, two
 384 kbit/s, two packet addresses on the same kind of traffic.  After every batch the new records, bytes and counters of every packet slot are
 read; at the end everything is compared with the model EXACTLY -- records by .tobytes(), bytes by np.array_equal, counters by == -- and the
 logical frames of every slot and the super frames, records and counters of the DAB+ slots beside them with the oracle back end's."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import dabplus_cases as dc
 import packet_cases as pc
 from dabstar_amd import lib as dx
+from stage_driver import drive, engine, kernel_launches, packet_follower, packet_mismatches
 
 pytestmark = pytest.mark.gpu
 
 H, B = dc.HISTORY, dc.BATCH
-SF_COUNTERS = (("cifs_decoded", "cif_out"), ("sf_ok", "sf_ok"), ("sf_fail", "sf_fail"), ("rs_corrected", "rs_corr"), ("rs_failed", "rs_fail"),
-               ("fc_corrected", "fc_corr"), ("au_ok", "au_ok"), ("au_bad", "au_bad"))
-
-
-def _engine(n_streams, max_subch, fast_min=1, class_min=1):
-    eng = dx.Engine(n_streams=n_streams, ring_frames=2, max_subch=max_subch, out_frames=1, msc_fast_min_jobs=fast_min, msc_class_min_jobs=class_min)
-    dx.check(dx.load().dabx_set_profiling(eng._h, 1))
-    return eng
-
-
-def _kernel_launches(eng):
-    ms = (C.c_double * 16)(); cnt = (C.c_int64 * 16)(); names = (C.c_char_p * 16)()
-    nk = dx.check(dx.load().dabx_get_profile(eng._h, ms, cnt, names))
-    return {names[i].decode(): int(cnt[i]) for i in range(nk)}
 
 
 def _packet_slots(s):
@@ -40,113 +25,29 @@ def _packet_slots(s):
     return [(j, kbps, address) for j, (kbps, kind) in enumerate(pc.STAGE_LAYOUTS[lay]) if kind == "pkt"]
 
 
-def _packet_state(eng, s):
+def _packet_state(eng, i, s):
     out = []
     for j, _, _ in _packet_slots(s):
-        rec, by = eng.read_datagroups(s, j, 4)
-        out.append((sorted(eng.packet_stats(s, j).items()), rec.tobytes(), by.tobytes()))
+        rec, by = eng.read_datagroups(i, j, 4)
+        out.append((sorted(eng.packet_stats(i, j).items()), rec.tobytes(), by.tobytes()))
     return out
 
 
 def _drive(eng, streams, schedule):
-    """Configures streams (indices into pc.STAGE_STREAMS), 16 CIFs of history, then one MSC batch per row of `schedule`.  After every batch
+    """stage_driver.drive on streams (indices into pc.STAGE_STREAMS) with their packet slots switched on and followed: after every batch
     the new logical frames of every slot, the new super frames of the DAB+ slots and the new groups of the packet slots are read and
     appended; a stream that received nothing must hold byte for byte what it held."""
     cases = [pc.stream_case(s) for s in streams]
-    S = len(streams)
-    got = {}
-    for i, s in enumerate(streams):
-        layout, _, cifs, _ = cases[i]
-        eng.set_subchannels(layout, stream=i)
-        for j, kbps, address in _packet_slots(s):
+
+    def switch_on(eng, i):
+        for j, _, address in _packet_slots(streams[i]):
             eng.set_packet_mode(i, j, address)
-        dx.msc_inject(eng, i, cifs[:H])
-        for j, sc in enumerate(layout):
-            got[(i, j)] = {"frames": [], "sf": [], "sfi": [], "seen": 0, "rec": [], "bytes": [], "dg_seen": 0, "byte_seen": 0}
-    dx.msc_decode(eng, [H] * S, H)
-    at = [H] * S
-    for counts in schedule:
-        before = {i: _packet_state(eng, streams[i]) for i in range(S) if counts[i] == 0}
-        for i in range(S):
-            if counts[i]:
-                dx.msc_inject(eng, i, cases[i][2][at[i]:at[i] + counts[i]])
-        dx.msc_decode(eng, counts, B)
-        for i, s in enumerate(streams):
-            if counts[i] == 0:
-                assert _packet_state(eng, s) == before[i], "stream %d received nothing in this batch and changed" % i
-                continue
-            at[i] += counts[i]
-            layout = cases[i][0]
-            eng.subch = list(layout)
-            for j, sc in enumerate(layout):
-                g = got[(i, j)]
-                fr = eng.read_msc(i, j, counts[i])
-                assert fr.shape[0] == counts[i], (i, j, fr.shape)
-                g["frames"].append(fr)
-                new = eng.subch_stats(i, j)["sf_count"] - g["seen"]
-                if new:
-                    g["sf"].append(eng.read_superframes(i, j, new)); g["sfi"].append(eng.read_superframe_info(i, j, new))
-                g["seen"] += new
-            for j, kbps, _ in _packet_slots(s):
-                g = got[(i, j)]
-                st = eng.packet_stats(i, j)
-                new = st["dg_count"] - g["dg_seen"]
-                assert 0 <= new <= B * (kbps // 8), (i, j, new)
-                if new:
-                    rec, by = eng.read_datagroups(i, j, new, max_bytes=B * (kbps // 8) * 127 + dx.DG_MAX_BYTES)
-                    assert len(rec) == new and rec["byte_pos"][0] == 0 and len(by) == st["dg_bytes"] - g["byte_seen"], (i, j, new, len(rec), len(by))
-                    rec = rec.copy()
-                    rec["byte_pos"] += g["byte_seen"]
-                    g["rec"].append(rec); g["bytes"].append(by)
-                g["dg_seen"] += new
-                g["byte_seen"] = st["dg_bytes"]
+
+    followers = {(i, j): packet_follower(kbps) for i, s in enumerate(streams) for j, kbps, _ in _packet_slots(s)}
+    got = drive(eng, cases, schedule, switch_on, followers, lambda eng, i: _packet_state(eng, i, streams[i]))
     for (i, j), g in got.items():
-        sc = cases[i][0][j]
-        g["frames"] = np.concatenate(g["frames"])
-        g["sf"] = np.concatenate(g["sf"]) if g["sf"] else np.zeros((0, 110 * sc.kbps // 8), np.uint8)
-        g["sfi"] = np.concatenate(g["sfi"]) if g["sfi"] else np.zeros(0, dx.SUPERFRAME_INFO)
-        g["rec"] = np.concatenate(g["rec"]) if g["rec"] else np.zeros(0, dx.DATAGROUP_INFO)
-        g["bytes"] = np.concatenate(g["bytes"]) if g["bytes"] else np.zeros(0, np.uint8)
-        g["stats"] = eng.subch_stats(i, j)
         g["pstats"] = eng.packet_stats(i, j)
     return got, cases
-
-
-def _mismatches(got, cases, streams):
-    """Every difference between the device and the model / the oracle as a line that names the stream, the slot and the bit rate."""
-    bad = []
-    for (i, j), g in sorted(got.items()):
-        s = streams[i]
-        layout, frames, _, want = cases[i]
-        kbps, kind = pc.STAGE_LAYOUTS[pc.STAGE_STREAMS[s][0]][j]
-        tag = "stream %d slot %d (%d kbit/s, %s): " % (i, j, kbps, kind)
-        o = want[j]
-        # the soft bits decode to the intended frames, on the oracle and on the device; DAB+ results equal the oracle back end's
-        if not np.array_equal(o["frames"], frames[j]):
-            bad.append(tag + "the oracle's logical frames are not the intended ones")
-        if not np.array_equal(g["frames"], o["frames"]):
-            bad.append(tag + "logical frames differ from the oracle's")
-        if g["sfi"].tobytes() != o["sfi"].tobytes() or not np.array_equal(g["sf"], o["sf"]):
-            bad.append(tag + "super frames or their records differ from the oracle's (%d, the oracle has %d)" % (len(g["sfi"]), len(o["sfi"])))
-        for mine, theirs in SF_COUNTERS:
-            if g["stats"][mine] != o["stats"][theirs]:
-                bad.append(tag + "%s = %d, the oracle's %d" % (mine, g["stats"][mine], o["stats"][theirs]))
-        if kind != "pkt":
-            if g["pstats"]["active"] or any(g["pstats"].values()) or len(g["rec"]):
-                bad.append(tag + "not in packet mode and shows packet results: %s" % g["pstats"])
-            continue
-        m = pc.run_model(frames[j], pc.STAGE_STREAMS[s][1])
-        if g["rec"].tobytes() != m.records().tobytes():
-            d = [k for k in range(min(len(g["rec"]), len(m.rows))) if g["rec"][k].tobytes() != m.records()[k].tobytes()][:3]
-            bad.append(tag + "%d records, the model has %d; first differences %s" % (len(g["rec"]), len(m.rows), [(k, g["rec"][k].tolist(), m.rows[k]) for k in d]))
-        if not np.array_equal(g["bytes"], m.all_bytes()):
-            bad.append(tag + "data-group bytes differ (%d, the model has %d)" % (len(g["bytes"]), len(m.all_bytes())))
-        for k in pc.PACKET_COUNTERS:
-            if g["pstats"][k] != m.counters[k]:
-                bad.append(tag + "%s = %d, the model's %d" % (k, g["pstats"][k], m.counters[k]))
-        if g["pstats"]["dg_lost"] != 0 or g["pstats"]["active"] != 1 or g["pstats"]["packet_address"] != pc.STAGE_STREAMS[s][1]:
-            bad.append(tag + "dg_lost / active / packet_address: %s" % g["pstats"])
-    return bad
 
 
 def _totals(got):
@@ -163,15 +64,15 @@ _runs = {}
 def test_every_stream_and_slot_equals_the_model_behind_the_lane_per_trellis_decoder():
     """Full batches of 28 CIFs, k_msc_prep + k_msc_vitT as the only decoder.  k_packet ran once per batch."""
     streams = list(range(len(pc.STAGE_STREAMS)))
-    eng = _engine(len(streams), 5)
+    eng = engine(len(streams), 5)
     try:
         got, cases = _drive(eng, streams, [[B] * len(streams)] * pc.N_BATCHES)
-        launches = _kernel_launches(eng)
+        launches = kernel_launches(eng)
     finally:
         eng.close()
     print(launches, _totals(got))
     assert launches["k_packet"] == pc.N_BATCHES + 1 == launches["k_dabplus"] == launches["k_msc_vitT"] and launches["k_msc_frame"] == 0, launches
-    bad = _mismatches(got, cases, streams)
+    bad = packet_mismatches(got, cases, streams)
     assert not bad, "%d differences:\n%s" % (len(bad), "\n".join(bad[:25]))
     assert all(v > 0 for v in _totals(got).values()), _totals(got)          # both guards and every counter were exercised on the device
     _runs["full"] = got
@@ -184,15 +85,15 @@ def test_groups_across_batch_boundaries_and_idle_batches_behind_the_wave_per_tre
     results are also byte for byte those of the full-batch run behind the other decoder."""
     streams = list(range(len(pc.STAGE_STREAMS)))
     schedule = pc.boundary_schedule(len(streams))
-    eng = _engine(len(streams), 5, fast_min=1 << 30, class_min=0)
+    eng = engine(len(streams), 5, fast_min=1 << 30, class_min=0)
     try:
         got, cases = _drive(eng, streams, schedule)
-        launches = _kernel_launches(eng)
+        launches = kernel_launches(eng)
     finally:
         eng.close()
     print(launches)
     assert launches["k_packet"] == len(schedule) + 1 == launches["k_msc_frame"] and launches["k_msc_vitT"] == 0, launches
-    bad = _mismatches(got, cases, streams)
+    bad = packet_mismatches(got, cases, streams)
     assert not bad, "%d differences:\n%s" % (len(bad), "\n".join(bad[:25]))
     if "full" in _runs:
         for key, g in got.items():
@@ -210,7 +111,7 @@ def test_packet_mode_on_and_off_leaves_the_logical_frames_untouched_and_no_packe
     assert pc.STAGE_LAYOUTS[pc.STAGE_STREAMS[s][0]][j] == (kbps, "pkt")
     results = []
     for toggle in (False, True):
-        eng = _engine(1, len(layout))
+        eng = engine(1, len(layout))
         try:
             eng.set_subchannels(layout, stream=0)
             dx.msc_inject(eng, 0, cifs[:H])
@@ -226,7 +127,7 @@ def test_packet_mode_on_and_off_leaves_the_logical_frames_untouched_and_no_packe
                 if toggle and b == 1:
                     assert eng.packet_stats(0, j)["active"] == 0 and len(eng.read_datagroups(0, j, 8)[0]) == 0
             st, (rec, by) = eng.packet_stats(0, j), eng.read_datagroups(0, j, 4096, max_bytes=1 << 20)
-            launches = _kernel_launches(eng)
+            launches = kernel_launches(eng)
         finally:
             eng.close()
         for b in range(3):
@@ -259,7 +160,7 @@ def test_a_slot_that_moves_to_other_capacity_units_keeps_its_assembly_and_a_chan
     m = pc.run_model(frames, address)
     r = m.records()
     assert ((r["first_frame"] < 2 * B) & (r["last_frame"] >= 2 * B)).any()          # a group is under way at the move
-    eng = _engine(1, 2)
+    eng = engine(1, 2)
     try:
         eng.set_subchannels(old, stream=0)
         eng.set_packet_mode(0, 1, address)
@@ -288,7 +189,7 @@ def test_a_slot_that_moves_to_other_capacity_units_keeps_its_assembly_and_a_chan
 
 def test_set_packet_mode_refuses_what_it_cannot_walk():
     layout = pc.stage_layout(0)
-    eng = _engine(1, 6)
+    eng = engine(1, 6)
     try:
         eng.set_subchannels(layout, stream=0)
         for j, address in ((1, 5), (5, 5), (0, 1024), (0, -1), (6, 5)):           # a DAB+ slot, a slot that is not configured, addresses out of range, no such slot

@@ -7,8 +7,6 @@ that the scenarios reach every branch and each side of every guard).  Four strea
 slots, a packet-mode slot and a plain slot at 8 .. 192 kbit/s.  After every batch the new items, bytes and counters of every PAD slot are
 read; at the end everything is compared with the model EXACTLY -- records by .tobytes(), bytes by np.array_equal, counters by == -- and the
 logical frames, super frames, records and counters of every slot with the oracle back end's."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -16,24 +14,11 @@ import dabplus_cases as dc
 import packet_cases as pkc
 import pad_cases as pc
 from dabstar_amd import lib as dx
+from stage_driver import PAD_ITEMS, Follower, drive, engine, kernel_launches, oracle_mismatches, pad_mismatches
 
 pytestmark = pytest.mark.gpu
 
 H, B = dc.HISTORY, dc.BATCH
-SF_COUNTERS = (("cifs_decoded", "cif_out"), ("sf_ok", "sf_ok"), ("sf_fail", "sf_fail"), ("rs_corrected", "rs_corr"), ("rs_failed", "rs_fail"),
-               ("fc_corrected", "fc_corr"), ("au_ok", "au_ok"), ("au_bad", "au_bad"))
-
-
-def _engine(n_streams, max_subch, fast_min=1, class_min=1):
-    eng = dx.Engine(n_streams=n_streams, ring_frames=2, max_subch=max_subch, out_frames=1, msc_fast_min_jobs=fast_min, msc_class_min_jobs=class_min)
-    dx.check(dx.load().dabx_set_profiling(eng._h, 1))
-    return eng
-
-
-def _kernel_launches(eng):
-    ms = (C.c_double * 16)(); cnt = (C.c_int64 * 16)(); names = (C.c_char_p * 16)()
-    nk = dx.check(dx.load().dabx_get_profile(eng._h, ms, cnt, names))
-    return {names[i].decode(): int(cnt[i]) for i in range(nk)}
 
 
 def _kinds(s):
@@ -52,115 +37,24 @@ def _pad_state(eng, i, s):
     return out
 
 
+def _switch_on(eng, i, s):
+    for j, (kbps, kind) in enumerate(_kinds(s)):
+        if kind == "pad":
+            eng.set_pad_mode(i, j)
+        elif kind == "pkt":
+            eng.set_packet_mode(i, j, pc.PACKET_ADDRESS)
+
+
 def _drive(eng, streams, schedule):
-    """Configures streams (indices into pc.STAGE_STREAMS), 16 CIFs of history, then one MSC batch per row of `schedule`.  After every batch
-    the new logical frames and super frames of every slot and the new items of the PAD slots are read and appended; a stream that
-    received nothing must hold byte for byte what it held."""
+    """stage_driver.drive on streams (indices into pc.STAGE_STREAMS) with their PAD slots followed: after every batch the new logical
+    frames and super frames of every slot and the new items of the PAD slots are read and appended; a stream that received nothing must
+    hold byte for byte what it held."""
     cases = [pc.stream_case(s) for s in streams]
-    S = len(streams)
-    got = {}
-    for i, s in enumerate(streams):
-        layout, _, cifs, _ = cases[i]
-        eng.set_subchannels(layout, stream=i)
-        for j, (kbps, kind) in enumerate(_kinds(s)):
-            if kind == "pad":
-                eng.set_pad_mode(i, j)
-            elif kind == "pkt":
-                eng.set_packet_mode(i, j, pc.PACKET_ADDRESS)
-            got[(i, j)] = {"frames": [], "sf": [], "sfi": [], "seen": 0, "rec": [], "bytes": [], "item_seen": 0, "byte_seen": 0}
-        dx.msc_inject(eng, i, cifs[:H])
-    dx.msc_decode(eng, [H] * S, H)
-    at = [H] * S
-    for counts in schedule:
-        before = {i: _pad_state(eng, i, streams[i]) for i in range(S) if counts[i] == 0}
-        for i in range(S):
-            if counts[i]:
-                dx.msc_inject(eng, i, cases[i][2][at[i]:at[i] + counts[i]])
-        dx.msc_decode(eng, counts, B)
-        for i, s in enumerate(streams):
-            if counts[i] == 0:
-                assert _pad_state(eng, i, s) == before[i], "stream %d received nothing in this batch and changed" % i
-                continue
-            at[i] += counts[i]
-            layout = cases[i][0]
-            eng.subch = list(layout)
-            for j, sc in enumerate(layout):
-                g = got[(i, j)]
-                fr = eng.read_msc(i, j, counts[i])
-                assert fr.shape[0] == counts[i], (i, j, fr.shape)
-                g["frames"].append(fr)
-                new = eng.subch_stats(i, j)["sf_count"] - g["seen"]
-                assert 0 <= new <= 6
-                if new:
-                    g["sf"].append(eng.read_superframes(i, j, new)); g["sfi"].append(eng.read_superframe_info(i, j, new))
-                g["seen"] += new
-            for j in _pad_slots(s):
-                g = got[(i, j)]
-                st = eng.pad_stats(i, j)
-                new = st["labels"] + st["groups"] - g["item_seen"]
-                assert 0 <= new <= 144, (i, j, new)                       # pad_core.h: 6 super frames x 6 AUs x 4 sub-fields
-                if new:
-                    rec, by = eng.read_pad_items(i, j, new)
-                    total = st["label_bytes"] + st["group_bytes"]
-                    assert len(rec) == new and rec["byte_pos"][0] == 0 and len(by) == total - g["byte_seen"], (i, j, new, len(rec), len(by))
-                    rec = rec.copy()
-                    rec["byte_pos"] += g["byte_seen"]
-                    g["rec"].append(rec); g["bytes"].append(by)
-                g["item_seen"] += new
-                g["byte_seen"] = st["label_bytes"] + st["group_bytes"]
+    followers = {(i, j): Follower(PAD_ITEMS, 144) for i, s in enumerate(streams) for j in _pad_slots(s)}       # pad_core.h: 6 super frames x 6 AUs x 4 sub-fields
+    got = drive(eng, cases, schedule, lambda eng, i: _switch_on(eng, i, streams[i]), followers, lambda eng, i: _pad_state(eng, i, streams[i]))
     for (i, j), g in got.items():
-        sc = cases[i][0][j]
-        g["frames"] = np.concatenate(g["frames"])
-        g["sf"] = np.concatenate(g["sf"]) if g["sf"] else np.zeros((0, 110 * sc.kbps // 8), np.uint8)
-        g["sfi"] = np.concatenate(g["sfi"]) if g["sfi"] else np.zeros(0, dx.SUPERFRAME_INFO)
-        g["rec"] = np.concatenate(g["rec"]) if g["rec"] else np.zeros(0, dx.PAD_ITEM)
-        g["bytes"] = np.concatenate(g["bytes"]) if g["bytes"] else np.zeros(0, np.uint8)
-        g["stats"] = eng.subch_stats(i, j)
         g["pstats"] = eng.pad_stats(i, j)
     return got, cases
-
-
-def _oracle_mismatches(tag, g, o, frames):
-    bad = []
-    if not np.array_equal(o["frames"], frames):
-        bad.append(tag + "the oracle's logical frames are not the intended ones")
-    if not np.array_equal(g["frames"], o["frames"]):
-        bad.append(tag + "logical frames differ from the oracle's")
-    if g["sfi"].tobytes() != o["sfi"].tobytes() or not np.array_equal(g["sf"], o["sf"]):
-        bad.append(tag + "super frames or their records differ from the oracle's (%d, the oracle has %d)" % (len(g["sfi"]), len(o["sfi"])))
-    for mine, theirs in SF_COUNTERS:
-        if g["stats"][mine] != o["stats"][theirs]:
-            bad.append(tag + "%s = %d, the oracle's %d" % (mine, g["stats"][mine], o["stats"][theirs]))
-    return bad
-
-
-def _mismatches(got, cases, streams):
-    """Every difference between the device and the model / the oracle as a line that names the stream, the slot and the bit rate."""
-    bad = []
-    for (i, j), g in sorted(got.items()):
-        s = streams[i]
-        layout, frames, _, want = cases[i]
-        kbps, kind = _kinds(s)[j]
-        tag = "stream %d slot %d (%d kbit/s, %s): " % (i, j, kbps, kind)
-        bad += _oracle_mismatches(tag, g, want[j], frames[j])
-        if kind != "pad":
-            if any(g["pstats"].values()) or len(g["rec"]):
-                bad.append(tag + "no PAD decoding and shows PAD results: %s" % g["pstats"])
-            continue
-        m = pc.slot_model(s, j)
-        if g["rec"].tobytes() != m.records().tobytes():
-            d = [k for k in range(min(len(g["rec"]), len(m.rows))) if g["rec"][k].tobytes() != m.records()[k].tobytes()][:3]
-            bad.append(tag + "%d items, the model has %d; first differences %s" % (len(g["rec"]), len(m.rows), [(k, g["rec"][k].tolist(), m.rows[k]) for k in d]))
-        if not np.array_equal(g["bytes"], m.all_bytes()):
-            n = min(len(g["bytes"]), len(m.all_bytes()))
-            first = int(np.argmax(g["bytes"][:n] != m.all_bytes()[:n])) if n and (g["bytes"][:n] != m.all_bytes()[:n]).any() else n
-            bad.append(tag + "item bytes differ (%d, the model has %d; first difference at %d)" % (len(g["bytes"]), len(m.all_bytes()), first))
-        for k in pc.PAD_COUNTERS:
-            if g["pstats"][k] != m.counters[k]:
-                bad.append(tag + "%s = %d, the model's %d" % (k, g["pstats"][k], m.counters[k]))
-        if g["pstats"]["items_lost"] != 0 or g["pstats"]["active"] != 1:
-            bad.append(tag + "items_lost / active: %s" % g["pstats"])
-    return bad
 
 
 def _totals(got):
@@ -177,15 +71,15 @@ _runs = {}
 def test_every_stream_and_slot_equals_the_model_behind_the_lane_per_trellis_decoder():
     """Full batches of 28 CIFs, k_msc_prep + k_msc_vitT as the only decoder.  k_pad ran once per batch."""
     streams = list(range(len(pc.STAGE_STREAMS)))
-    eng = _engine(len(streams), 5)
+    eng = engine(len(streams), 5)
     try:
         got, cases = _drive(eng, streams, [[B] * len(streams)] * pc.N_BATCHES)
-        launches = _kernel_launches(eng)
+        launches = kernel_launches(eng)
     finally:
         eng.close()
     print(launches, _totals(got))
     assert launches["k_pad"] == pc.N_BATCHES + 1 == launches["k_dabplus"] == launches["k_msc_vitT"] and launches["k_msc_frame"] == 0, launches
-    bad = _mismatches(got, cases, streams)
+    bad = pad_mismatches(got, cases, streams)
     assert not bad, "%d differences:\n%s" % (len(bad), "\n".join(bad[:25]))
     assert all(v > 0 for v in _totals(got).values()), _totals(got)          # every guard and every counter was exercised on the device
     _runs["full"] = got
@@ -197,15 +91,15 @@ def test_items_across_batch_boundaries_and_idle_batches_behind_the_wave_per_trel
     carried from launch to launch.  k_msc_frame is the only decoder here; the results are also byte for byte those of the full-batch run."""
     streams = list(range(len(pc.STAGE_STREAMS)))
     schedule = pc.boundary_schedule(len(streams))
-    eng = _engine(len(streams), 5, fast_min=1 << 30, class_min=0)
+    eng = engine(len(streams), 5, fast_min=1 << 30, class_min=0)
     try:
         got, cases = _drive(eng, streams, schedule)
-        launches = _kernel_launches(eng)
+        launches = kernel_launches(eng)
     finally:
         eng.close()
     print(launches)
     assert launches["k_pad"] == len(schedule) + 1 == launches["k_msc_frame"] and launches["k_msc_vitT"] == 0, launches
-    bad = _mismatches(got, cases, streams)
+    bad = pad_mismatches(got, cases, streams)
     assert not bad, "%d differences:\n%s" % (len(bad), "\n".join(bad[:25]))
     if "full" in _runs:
         for key, g in got.items():
@@ -222,7 +116,7 @@ def test_pad_on_off_and_on_again_leaves_every_result_the_oracles_and_no_pad_slot
     assert _kinds(s)[j] == (64, "pad")
     results = []
     for toggle in (False, True):
-        eng = _engine(1, len(layout))
+        eng = engine(1, len(layout))
         try:
             eng.set_subchannels(layout, stream=0)
             dx.msc_inject(eng, 0, cifs[:H])
@@ -253,10 +147,10 @@ def test_pad_on_off_and_on_again_leaves_every_result_the_oracles_and_no_pad_slot
                 g["sfi"] = np.concatenate(g["sfi"]) if g["sfi"] else np.zeros(0, dx.SUPERFRAME_INFO)
                 g["stats"] = eng.subch_stats(0, k)
             st, (rec, by) = eng.pad_stats(0, j), eng.read_pad_items(0, j, 512)
-            launches = _kernel_launches(eng)
+            launches = kernel_launches(eng)
         finally:
             eng.close()
-        bad = [line for k, g in got.items() for line in _oracle_mismatches("PAD %s, slot %d: " % ("toggled" if toggle else "never on", k), g, want[k], frames[k])]
+        bad = [line for k, g in got.items() for line in oracle_mismatches("PAD %s, slot %d: " % ("toggled" if toggle else "never on", k), g, want[k], frames[k])]
         assert not bad, "\n".join(bad)
         results.append((st, rec, by, launches, sf_at_start))
     st, rec, by, launches, _ = results[0]
@@ -288,25 +182,20 @@ def test_a_slot_that_moves_to_other_capacity_units_in_the_middle_of_a_group_lose
     assert done - 70 < b_move * B < done - 5, (done, b_move)
     move = H + b_move * B                                             # the CIF from which the sub-channel is at its new place
     cifs = np.concatenate([c_old[:move], c_new[move:]])
-    eng = _engine(1, 2)
+    eng = engine(1, 2)
     try:
         eng.set_subchannels(old, stream=0)
         eng.set_pad_mode(0, 1)
         dx.msc_inject(eng, 0, cifs[:H])
         dx.msc_decode(eng, [H], H)
-        recs, chunks, seen = [], [], 0
+        ring = Follower(PAD_ITEMS, 144)
         for b in range(pc.N_BATCHES):
             if b == b_move:
                 eng.set_subchannels(new, stream=0)
             dx.msc_inject(eng, 0, cifs[H + B * b:H + B * (b + 1)])
             dx.msc_decode(eng, [B], B)
-            st = eng.pad_stats(0, 1)
-            n = st["labels"] + st["groups"] - seen
-            if n:
-                rec, by = eng.read_pad_items(0, 1, n)
-                assert len(rec) == n
-                recs.append(rec["length"].copy()); chunks.append(by)
-            seen += n
+            st = ring.take(eng, 0, 1)[0]
+        rec, by = ring.result()
         eng.subch = list(new)
         last = eng.read_msc(0, 1, B)
         changed = dc.dabplus_layout([(64, pc.PROT, 0), (kbps, 2, 0)], dab_plus=[0, 1])
@@ -316,14 +205,14 @@ def test_a_slot_that_moves_to_other_capacity_units_in_the_middle_of_a_group_lose
         eng.close()
     assert np.array_equal(last, frames[-B:])
     assert st["labels"] + st["groups"] == len(m.rows) and st["items_lost"] == 0, (st, len(m.rows))
-    assert np.array_equal(np.concatenate(recs), r["length"]) and np.array_equal(np.concatenate(chunks), m.all_bytes())
+    assert np.array_equal(rec["length"], r["length"]) and np.array_equal(by, m.all_bytes())
     assert all(st[k] == m.counters[k] for k in pc.PAD_COUNTERS), (st, m.counters)
     assert after["active"] == 0 and not any(after.values()), after
 
 
 def test_set_pad_mode_refuses_an_inactive_a_non_dabplus_and_a_packet_mode_slot():
     layout = pc.stage_layout(0)
-    eng = _engine(1, 6)
+    eng = engine(1, 6)
     try:
         eng.set_subchannels(layout, stream=0)
         eng.set_packet_mode(0, 3, pc.PACKET_ADDRESS)

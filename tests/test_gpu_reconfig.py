@@ -21,21 +21,6 @@ from tools import dab_synth as ds  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 
-def _oracle(x, subch, move=None):
-    """move = (back end, new first capacity unit, CIF): that sub-channel is handed its slice from the new address from that CIF on"""
-    L = ol.oracle()
-    rx = L.ora_rx_create(ol.make_descs(subch), len(subch))
-    if move:
-        L.ora_rx_move_subch(rx, *move)
-    n = L.ora_rx_run(rx, x, len(x), 10000)
-    cap = L.ora_rx_get_capture(rx).contents
-    res = dict(n=n, fibs=np.ctypeslib.as_array(cap.fibs, (n, 12, 32)).copy(), crc=np.ctypeslib.as_array(cap.fib_crc, (n, 12)).copy(),
-               msc=[ol.backend_bytes(rx, i, "msc").reshape(-1, 3 * subch[i].kbps) for i in range(len(subch))],
-               sf=[ol.backend_bytes(rx, i, "sf") for i in range(len(subch))])
-    L.ora_rx_destroy(rx)
-    return res
-
-
 @pytest.mark.parametrize("cif_in_frame,reference_rule", [(0, False), (2, False), (0, True)])
 def test_reconfiguration_is_followed_at_the_announced_cif(cif_in_frame, reference_rule):
     """cif_in_frame = 2: the configuration changes in the MIDDLE of a transmission frame (its third CIF).  dabx_set_subchannels_at is
@@ -50,12 +35,12 @@ def test_reconfiguration_is_followed_at_the_announced_cif(cif_in_frame, referenc
     n_frames, switch_frame = 27, 12
     ens = ds.build_reconfigured_ensemble(n_frames, a, b, switch_frame, announce_frames=7, seed=5, switch_cif_in_frame=cif_in_frame)
     x = ds.channel(ens.iq, snr_db=20.0, cfo_hz=310.0, timing_offset=3000, seed=5, cyclic=False)
-    ora_a, ora_b = _oracle(x, a), _oracle(x, b)
+    ora_a, ora_b = ol.oracle_run_with_move(x, a), ol.oracle_run_with_move(x, b)
     assert ora_a["n"] == ora_b["n"] >= n_frames - 2 and ora_a["crc"][2:].all()      # (the first two frames: start-up of the CFO loop)
     # the sub-channel that only moves: one Backend that is handed its slice from the new address from the switch CIF on (the receivers
     # count CIFs from their first frame: transmitted CIF = counted CIF + the counter of the first FIG 0/0 - its position)
     c0_ora = dx.parse_fibs(ora_a["fibs"][2][:1], np.ones(1, np.uint8))[1] - 8
-    ora_m = _oracle(x, a, move=(3, 400, ens.switch_cif - c0_ora))
+    ora_m = ol.oracle_run_with_move(x, a, move=(3, 400, ens.switch_cif - c0_ora))
 
     eng = dx.Engine(n_streams=1, ring_frames=n_frames + 2, max_subch=6, out_frames=4)
     eng.set_subchannels(a)

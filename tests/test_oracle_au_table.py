@@ -10,8 +10,8 @@ import pytest
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 from tools import dab_synth as ds  # noqa: E402
 from dabstar_amd import lib as dx  # noqa: E402
-from test_gpu_engine import _oracle_run  # noqa: E402
-from test_gpu_au_table import _check_record_against_its_super_frame  # noqa: E402
+from oracle_lib import oracle_run  # noqa: E402
+from dabplus_cases import _check_record_against_its_super_frame  # noqa: E402
 
 
 @pytest.mark.parametrize("snr", [20.0, 4.0])
@@ -19,7 +19,7 @@ def test_oracle_records_describe_their_super_frames(snr):
     subch = ds.default_subchannels(2, 64)
     ens = ds.build_ensemble(10, subch, seed=1)
     x = ds.channel(ens.iq, snr_db=snr, cfo_hz=-730.0, timing_offset=123456, seed=1, n_out=16 * ds.TF)
-    ora = _oracle_run(x, subch)
+    ora = oracle_run(x, subch)
     bad = 0
     for j in range(2):
         r = ora["sfi"][j].view(dx.SUPERFRAME_INFO)
