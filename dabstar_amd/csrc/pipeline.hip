@@ -506,7 +506,10 @@ __device__ __forceinline__ int acquire_stream(EngineDev &e, int s, int tid, int 
           q += lim;
           if (ok) break;
           nb += m;
-          if (nb == last) {
+          // (a dip that began anywhere in this segment has moved the time-out -- also in the segment cut at the NO_DIP time-out, up to 1023
+          //  positions in front of T_F + 50: if its end lies behind the cut, the attempt goes on looking for it; n2 + T_n + 71 cannot be
+          //  reached inside the segment the begin was found in)
+          if (nb == (phase == 3 ? n2 + TN + 71 : last)) {
             if (phase == 0) { phase = 1; nb = 0; L = 0.f; }
             else {
               // NO_DIP_FOUND / NO_END_OF_DIP_FOUND: dab_processor.cpp:154-160 tries again at once.  The same here while the next

@@ -213,6 +213,7 @@ typedef struct {
 } ora_phaseref;
 void ora_phaseref_init(ora_phaseref *p);
 int  ora_phaseref_correlate(ora_phaseref *p, const ora_cf32 *v, float threshold); /* :87-213 */
+int  ora_phaseref_correlate_ratio(ora_phaseref *p, const ora_cf32 *v, float threshold, float *ratio);   /* + max(peak[i0..i1)) / mean */
 int  ora_phaseref_coarse_cfo(ora_phaseref *p, const ora_cf32 *fft_sym0);          /* :223-280 */
 
 ora_demap *ora_demap_new(void);
@@ -261,6 +262,27 @@ void ora_rx_enable_soft_capture(ora_receiver *r, int on);
 const ora_rx_capture *ora_rx_get_capture(ora_receiver *r);
 int ora_rx_run_spectra(ora_receiver *r, const ora_cf32 *spectra, const ora_cf32 *nulls, const float *clock_err, int n_frames);   /* per-symbol class calls on given FFT outputs */
 int ora_rx_take_tii(ora_receiver *r, ora_cf32 *out2048);   /* TII null-symbol sum + count since the last call */
+/* Event trace of ora_rx_run's state machine (tests/acquire_cases.py): one record per event, in order.
+ *   SEEDED       the 20 T_u reads in front of the first search are done (dab_processor.cpp:139-142)
+ *   NO_DIP       time_sync gave up looking for the begin of a dip (timesyncer.cpp:68-71)      NO_END  ... for its end (:82-85)
+ *   DIP_END      time_sync found the end of a null symbol (:88)
+ *   CORR_FAILED  the phase-reference correlation of the T_u samples behind it (or behind a frame) found no peak (dab_processor.cpp:396-400)
+ *   CORR_OK      ... found one (recorded before the rest of symbol 0 is read)                 FRAME_DONE  the frame's null symbol is read
+ * pos = samples read when the event happened; s_level / peak_level = SampleReader's as bit patterns at that moment; dip_begin = the
+ * attempt-relative sample BEFORE which `level / 50 > 0.55 sLevel` first failed, dip_len = samples read until `level / 50 < 0.75 sLevel`
+ * failed (-1 where there is none); margin = running count of the comparisons of time_sync that came within 1e-4 (relative) of their
+ * threshold, |mean - thr| <= 1e-4f * thr in float: the begin comparisons up to and including the one that ends the loop, then the end
+ * comparisons from the same sample on (what dabx_stats.level_margin_events counts); ratio = max(peak[i0..i1)) / mean of a correlation. */
+enum { ORA_EV_SEEDED = 0, ORA_EV_NO_DIP = 1, ORA_EV_NO_END = 2, ORA_EV_DIP_END = 3, ORA_EV_CORR_FAILED = 4, ORA_EV_CORR_OK = 5, ORA_EV_FRAME_DONE = 6 };
+typedef struct {
+  int32_t kind, dip_begin, dip_len, margin;
+  int64_t pos;
+  uint32_t s_level_bits, peak_level_bits;
+  float ratio; int32_t reserved;
+} ora_trace_event;
+void ora_rx_enable_trace(ora_receiver *r, int max_events);
+int ora_rx_get_trace(ora_receiver *r, const ora_trace_event **out);   /* number of events recorded by the last ora_rx_run */
+void ora_set_search_variant(int k);   /* test only, process-wide: 0 the restatement, 1..7 off-by-one variants of time_sync (receiver.c) */
 ora_backend *ora_rx_backend(ora_receiver *r, int i);
 ora_fic *ora_rx_fic(ora_receiver *r);
 

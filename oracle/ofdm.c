@@ -76,7 +76,9 @@ void ora_phaseref_init(ora_phaseref *p)
 }
 
 /* phasereference.cpp:87-213 */
-int ora_phaseref_correlate(ora_phaseref *p, const ora_cf32 *v, float threshold)
+int ora_phaseref_correlate(ora_phaseref *p, const ora_cf32 *v, float threshold) { return ora_phaseref_correlate_ratio(p, v, threshold, NULL); }
+/* the same; *ratio = max(peak[i0..i1)) / mean, what the decision compares with the threshold (0 / 0 where the window is all zeros) */
+int ora_phaseref_correlate_ratio(ora_phaseref *p, const ora_cf32 *v, float threshold, float *ratio)
 {
   ora_cf32 a[ORA_TU], b[ORA_TU];
   float peak[ORA_TU];
@@ -89,10 +91,15 @@ int ora_phaseref_correlate(ora_phaseref *p, const ora_cf32 *v, float threshold)
   float sum = 0;
   for (int i = 0; i < ORA_TU; i++) { peak[i] = cabs_f(a[i]); sum += peak[i]; }   /* :116-122 */
   sum /= (float)ORA_TU;
+  const int gap = 10, i0 = ORA_TG - 250, i1 = ORA_TG + 500;                     /* :136-139 */
+  if (ratio) {
+    float mx = 0;
+    for (int i = i0; i < i1; ++i) if (peak[i] > mx) mx = peak[i];
+    *ratio = mx / sum;
+  }
   if (sum == 0) return -1;
   int max_index = -1, first = -1;
   float max_l = -1000;
-  const int gap = 10, i0 = ORA_TG - 250, i1 = ORA_TG + 500;                     /* :136-139 */
   for (int i = i0; i < i1; ++i) {
     if (peak[i] / sum > threshold) {
       int found = 1;

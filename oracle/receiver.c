@@ -29,7 +29,40 @@ struct ora_receiver {
   ora_cf32 tii_acc[ORA_TU]; int tii_count;
   /* capture */
   ora_rx_capture cap; int cap_alloc; int want_soft;
+  /* event trace of the state machine (ora_rx_enable_trace): test bookkeeping, never read by the receiver itself */
+  ora_trace_event *trace; int trace_max, trace_n;
+  int margin;                        /* comparisons of time_sync within 1e-4 (relative) of their threshold so far */
+  int dip_begin, dip_len;            /* of the last time_sync: attempt-relative sample at which the dip began, samples read until it ended (-1: none) */
+  float last_level;                  /* the moving sum as the last time_sync left it (search variant 6 only) */
+  float corr_ratio;                  /* of the last correlation: max(peak[i0..i1)) / mean */
+  int last_correction;               /* of the last frame: what the coarse search returned (0 where it did not run) */
 };
+
+/* Test-only, process-wide: named off-by-one variants of time_sync (0 = the restatement).  tests/test_acquire_cases.py uses them to
+ * prove that its inputs tell each of them from the restatement; no checker runs with anything but 0. */
+static int g_search_variant = 0;
+void ora_set_search_variant(int k) { g_search_variant = k; }
+
+static void trace_event(ora_receiver *r, int kind)
+{
+  if (!r->trace || r->trace_n >= r->trace_max) return;
+  ora_trace_event *e = &r->trace[r->trace_n++];
+  const int dip = kind == ORA_EV_NO_DIP || kind == ORA_EV_NO_END || kind == ORA_EV_DIP_END;
+  const int corr = kind == ORA_EV_CORR_FAILED || kind == ORA_EV_CORR_OK;
+  memset(e, 0, sizeof(*e));
+  e->kind = kind; e->pos = (int64_t)r->pos;
+  memcpy(&e->s_level_bits, &r->s_level, 4); memcpy(&e->peak_level_bits, &r->peak_level, 4);
+  e->dip_begin = dip ? r->dip_begin : -1; e->dip_len = dip ? r->dip_len : -1;
+  e->margin = r->margin;
+  e->ratio = corr ? r->corr_ratio : (kind == ORA_EV_FRAME_DONE ? (float)r->last_correction : 0.0f);
+}
+void ora_rx_enable_trace(ora_receiver *r, int max_events)
+{
+  free(r->trace);
+  r->trace = max_events > 0 ? (ora_trace_event *)calloc((size_t)max_events, sizeof(ora_trace_event)) : NULL;
+  r->trace_max = max_events > 0 ? max_events : 0; r->trace_n = 0;
+}
+int ora_rx_get_trace(ora_receiver *r, const ora_trace_event **out) { if (out) *out = r->trace; return r->trace_n; }
 
 static ora_cf32 *g_osc = NULL;   /* sample_reader.cpp:44-50 : 2 048 000-entry oscillator table */
 static void build_osc(void)
@@ -120,35 +153,66 @@ float ora_level_walk(const ora_cf32 *x, size_t n, float s0)
   return s;
 }
 
-/* timesyncer.cpp:40-90 ; returns 1 established, 0 otherwise, -1 eof */
+/* a comparison of time_sync that a relative error of 1e-4 in sLevel could have turned (dabx_stats.level_margin_events counts the same) */
+static int near_thr(float mean, float thr) { return fabsf(mean - thr) <= 1e-4f * thr; }
+
+/* timesyncer.cpp:40-90 ; returns 1 established, 0 otherwise, -1 eof.
+ * g_search_variant (test only, see above): 1 a dip is accepted from sample 49 on, 2 `> T_F` read as `>= T_F`, 3 `> T_n + 70` as `>= T_n + 70`,
+ * 4 the end is searched from the sample after the begin, 5 `>` / `<` become `>=` / `<=`, 6 the moving sum starts from where the last
+ * attempt left it, 7 the envelope is taken before the oscillator product. */
 static int time_sync(ora_receiver *r)
 {
   enum { SEARCH = 50, BUFSZ = 4096, MASK = BUFSZ - 1 };
-  float env[BUFSZ], level = 0;
+  const int var = g_search_variant;
+  float env[BUFSZ], level = var == 6 ? r->last_level : 0;
   int idx = 0;
   ora_cf32 s;
-  for (int i = 0; i < SEARCH; i++) {
+  const int seed = var == 1 ? SEARCH - 1 : SEARCH;
+  if (var == 1) memset(env, 0, sizeof(env));
+  r->dip_begin = r->dip_len = -1;
+#define ORA_ENV(s_) (var == 7 ? sqrtf(r->iq[r->pos - 1].re * r->iq[r->pos - 1].re + r->iq[r->pos - 1].im * r->iq[r->pos - 1].im) \
+                              : sqrtf((s_).re * (s_).re + (s_).im * (s_).im))
+  for (int i = 0; i < seed; i++) {
     if (!get_samples(r, &s, 1, 0)) return -1;
-    env[idx] = sqrtf(s.re * s.re + s.im * s.im);
+    env[idx] = ORA_ENV(s);
     level += env[idx];
     ++idx;
   }
   int counter = 0;
-  while (level / SEARCH > 0.55f * r->s_level) {
+  for (;;) {
+    const float mean = level / SEARCH, thr = 0.55f * r->s_level;
+    r->margin += near_thr(mean, thr);
+    if (!(var == 5 ? mean >= thr : mean > thr)) break;
     if (!get_samples(r, &s, 1, 0)) return -1;
-    env[idx] = sqrtf(s.re * s.re + s.im * s.im);
+    env[idx] = ORA_ENV(s);
     level += env[idx] - env[(unsigned)(idx - SEARCH) & MASK];
     idx = (idx + 1) & MASK;
-    if (++counter > ORA_TF) return 0;
+    ++counter;
+    if (var == 2 ? counter >= ORA_TF : counter > ORA_TF) { r->last_level = level; return 0; }
   }
+  r->dip_begin = seed + counter;
   counter = 0;
-  while (level / SEARCH < 0.75f * r->s_level) {
+  if (var == 4) {
     if (!get_samples(r, &s, 1, 0)) return -1;
-    env[idx] = sqrtf(s.re * s.re + s.im * s.im);
+    env[idx] = ORA_ENV(s);
+    level += env[idx] - env[(unsigned)(idx - SEARCH) & MASK];
+    idx = (idx + 1) & MASK;                /* (not counted: the comparison at the begin sample itself can never end the dip -- the mean is at most
+                                              0.55 sLevel there --, so the variant shows only in the time-out, one sample later) */
+  }
+  for (;;) {
+    const float mean = level / SEARCH, thr = 0.75f * r->s_level;
+    r->margin += near_thr(mean, thr);
+    if (!(var == 5 ? mean <= thr : mean < thr)) break;
+    if (!get_samples(r, &s, 1, 0)) return -1;
+    env[idx] = ORA_ENV(s);
     level += env[idx] - env[(unsigned)(idx - SEARCH) & MASK];
     idx = (idx + 1) & MASK;
-    if (++counter > ORA_TN + SEARCH + 20) return 0;
+    ++counter;
+    if (var == 3 ? counter >= ORA_TN + SEARCH + 20 : counter > ORA_TN + SEARCH + 20) { r->last_level = level; return 0; }
   }
+#undef ORA_ENV
+  r->dip_len = counter;
+  r->last_level = level;
   return 1;
 }
 
@@ -190,6 +254,7 @@ void ora_rx_destroy(ora_receiver *r)
   free(r->cap.fbb_end); free(r->cap.clock_err); free(r->cap.fic_ratio); free(r->cap.snr_db); free(r->cap.fic_overflow); free(r->cap.msc_overflow);
   free(r->cap.s_level); free(r->cap.peak_level); free(r->cap.fic_ber_bits); free(r->cap.fic_ber_errors);
   free(r->cap.mer_db);
+  free(r->trace);
   free(r);
 }
 
@@ -269,6 +334,7 @@ static int process_rest_of_frame(ora_receiver *r, int *sample_count, int frame_n
     r->freq_offs_bb = r->freq_offs_sync;
   }
   r->cap.fbb[frame_no] = r->freq_offs_bb;
+  r->last_correction = correction;
 
   /* _process_ofdm_symbols_1_to_L, :304-367 */
   float fc_re = 0, fc_im = 0;
@@ -332,6 +398,8 @@ int ora_rx_run(ora_receiver *r, const ora_cf32 *iq, size_t n_samples, int max_fr
   r->freq_offs_bb = 0; r->freq_offs_sync = 0; r->fic.success_ratio = 0;   /* :119-124 */
   for (int i = 0; i < 20; i++)                                   /* :139-142 */
     if (!get_samples(r, r->buf, ORA_TU, 0)) return 0;
+  r->trace_n = 0; r->margin = 0; r->last_level = 0;
+  trace_event(r, ORA_EV_SEEDED);
   while (!r->eof && frames < max_frames) {
     switch (state) {
     case WAIT_SYNC: {                                            /* :146-160 */
@@ -340,13 +408,15 @@ int ora_rx_run(ora_receiver *r, const ora_cf32 *iq, size_t n_samples, int max_fr
       sample_count = 0; sync_thr = r->threshold;
       const int ok = time_sync(r);
       if (ok < 0) return frames;
+      trace_event(r, ok ? ORA_EV_DIP_END : (r->dip_begin < 0 ? ORA_EV_NO_DIP : ORA_EV_NO_END));
       state = ok ? EVAL_SYNC : WAIT_SYNC;
       r->clock_err = 0.0f;
       break;
     }
     case EVAL_SYNC: {                                            /* :389-414 */
       if (!get_samples(r, r->buf, ORA_TU, r->freq_offs_bb)) return frames;
-      const int start = ora_phaseref_correlate(&r->pr, r->buf, sync_thr);
+      const int start = ora_phaseref_correlate_ratio(&r->pr, r->buf, sync_thr, &r->corr_ratio);
+      trace_event(r, start < 0 ? ORA_EV_CORR_FAILED : ORA_EV_CORR_OK);
       if (start < 0) { state = WAIT_SYNC; break; }
       const int next = ORA_TU - start;
       memmove(r->buf, &r->buf[start], sizeof(ora_cf32) * (size_t)next);
@@ -371,6 +441,7 @@ int ora_rx_run(ora_receiver *r, const ora_cf32 *iq, size_t n_samples, int max_fr
       }
       frames++;
       r->cap.n_frames = frames;
+      trace_event(r, ORA_EV_FRAME_DONE);
       state = EVAL_SYNC;
       sync_thr = 2 * r->threshold;
       break;

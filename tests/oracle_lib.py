@@ -35,6 +35,23 @@ class RxCapture(C.Structure):
                 ("mer_db", C.POINTER(C.c_float))]
 
 
+class TraceEvent(C.Structure):
+    """ora_trace_event (oracle/dab_oracle.h): one event of ora_rx_run's state machine."""
+    _fields_ = [("kind", C.c_int32), ("dip_begin", C.c_int32), ("dip_len", C.c_int32), ("margin", C.c_int32), ("pos", C.c_int64),
+                ("s_level_bits", C.c_uint32), ("peak_level_bits", C.c_uint32), ("ratio", C.c_float), ("reserved", C.c_int32)]
+
+
+TRACE_DTYPE = np.dtype([("kind", "<i4"), ("dip_begin", "<i4"), ("dip_len", "<i4"), ("margin", "<i4"), ("pos", "<i8"),
+                        ("s_level_bits", "<u4"), ("peak_level_bits", "<u4"), ("ratio", "<f4"), ("reserved", "<i4")])
+assert TRACE_DTYPE.itemsize == C.sizeof(TraceEvent) == 40
+EV_SEEDED, EV_NO_DIP, EV_NO_END, EV_DIP_END, EV_CORR_FAILED, EV_CORR_OK, EV_FRAME_DONE = range(7)
+EV_NAMES = ("SEEDED", "NO_DIP", "NO_END", "DIP_END", "CORR_FAILED", "CORR_OK", "FRAME_DONE")
+# ora_set_search_variant: the named off-by-one variants of time_sync (oracle/receiver.c)
+SEARCH_VARIANTS = {1: "a dip is accepted from sample 49", 2: "> T_F read as >= T_F", 3: "> T_n + 70 read as >= T_n + 70",
+                   4: "the end is searched from the sample after the begin", 5: "> and < become >= and <=",
+                   6: "the level restarts from its old value", 7: "the envelope is taken before the oscillator product"}
+
+
 def build_oracle():
     if not os.path.exists(ORA_SO) or any(
             os.path.getmtime(os.path.join(ORA_DIR, f)) > os.path.getmtime(ORA_SO)
@@ -108,6 +125,9 @@ def _prototypes(L):
     L.ora_rx_get_capture.restype = C.POINTER(RxCapture)
     L.ora_rx_take_tii.argtypes = [C.c_void_p, _c64p]
     L.ora_rx_get_capture.argtypes = [C.c_void_p]
+    L.ora_rx_enable_trace.argtypes = [C.c_void_p, C.c_int]
+    L.ora_rx_get_trace.argtypes = [C.c_void_p, C.POINTER(C.POINTER(TraceEvent))]
+    L.ora_set_search_variant.argtypes = [C.c_int]
     L.ora_rx_backend.restype = C.c_void_p
     L.ora_rx_backend.argtypes = [C.c_void_p, C.c_int]
     for f in (L.ora_backend_msc_bytes, L.ora_backend_sf_bytes, L.ora_backend_sfi_bytes):
@@ -357,14 +377,46 @@ def make_descs(subch):
                                       for c in subch])
 
 
-def oracle_run(x, subch, want_soft=False, config=None):
-    """The oracle receiver on IQ x: per frame the FIBs, CRC flags and receiver scalars, per sub-channel the back end's results."""
+def rx_trace(rx):
+    """The events the receiver's last ora_rx_run recorded (ora_rx_enable_trace), as a TRACE_DTYPE array."""
+    p = C.POINTER(TraceEvent)()
+    n = oracle().ora_rx_get_trace(rx, C.byref(p))
+    if not n:
+        return np.zeros(0, TRACE_DTYPE)
+    return np.frombuffer(C.string_at(p, n * C.sizeof(TraceEvent)), TRACE_DTYPE).copy()
+
+
+def oracle_trace(x, threshold=3.0, strongest=0, variant=0, max_events=1 << 16):
+    """The event trace of the oracle receiver on IQ x without back ends (the search and the frame chain's walk do not depend on them).
+    variant != 0 runs one of SEARCH_VARIANTS -- a process-wide switch, so never from two threads at once."""
+    L = oracle()
+    x = np.ascontiguousarray(x, np.complex64)
+    rx = L.ora_rx_create(make_descs([]), 0)
+    L.ora_rx_configure(rx, threshold, strongest, 1)
+    L.ora_rx_enable_trace(rx, max_events)
+    L.ora_set_search_variant(variant)
+    try:
+        L.ora_rx_run(rx, x, len(x), 10000)
+    finally:
+        L.ora_set_search_variant(0)
+    tr = rx_trace(rx)
+    L.ora_rx_destroy(rx)
+    assert len(tr) < max_events
+    return tr
+
+
+def oracle_run(x, subch, want_soft=False, config=None, trace=0):
+    """The oracle receiver on IQ x: per frame the FIBs, CRC flags and receiver scalars, per sub-channel the back end's results.
+    trace = n: also res["trace"], up to n events of its state machine."""
     L = oracle()
     rx = L.ora_rx_create(make_descs(subch), len(subch))
     if config:
         L.ora_rx_configure(rx, *config)
     L.ora_rx_enable_soft_capture(rx, int(want_soft))
+    if trace:
+        L.ora_rx_enable_trace(rx, trace)
     n = L.ora_rx_run(rx, x, len(x), 10000)
+    tr = rx_trace(rx) if trace else None
     cap = L.ora_rx_get_capture(rx).contents
     res = dict(n=n, fibs=np.ctypeslib.as_array(cap.fibs, (n, 12, 32)).copy(),
                crc=np.ctypeslib.as_array(cap.fib_crc, (n, 12)).copy(),
@@ -382,6 +434,8 @@ def oracle_run(x, subch, want_soft=False, config=None):
                stats=[backend_stats(rx, i) for i in range(len(subch))])
     if want_soft:
         res["soft"] = np.ctypeslib.as_array(cap.soft, (n, 75, 3072)).copy()
+    if trace:
+        res["trace"] = tr
     L.ora_rx_destroy(rx)
     return res
 
