@@ -8,6 +8,7 @@
 #include "pipeline.h"
 #include "packet_core.h"
 #include "pad_core.h"
+#include "mot_core.h"
 
 namespace dabx {
 
@@ -205,6 +206,31 @@ int launch_deliver_pad(const EngineDev &e, const DeliverDev &dv, const PadDev &p
   if (!dv.hdr.off_pad || pd.n <= 0) return 0;
   DABX_HIP(hipMemsetAsync(dv.slab + dv.hdr.off_pad, 0, sizeof(dabx_chunk_pad) * (size_t)e.n_streams * e.max_subch, st));
   hipLaunchKernelGGL(k_deliver_pad, dim3(pd.n), dim3(64), 0, st, pd, dv.slab, (unsigned long long)dv.hdr.off_pad);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+
+// The MOT section (include/dabx.h, dabx_chunk_mot): one wave per MOT slot, behind k_deliver_pad of the chunk, in the same way.
+__global__ __launch_bounds__(64) void k_deliver_mot(MotDev md, uint8_t *slab, unsigned long long off_mot)
+{
+  MotSlot &ms = md.slots[blockIdx.x];
+  if (!ms.out.dl_rec_off) return;
+  const OutGather g = out_ring_gather(ms.out, slab, threadIdx.x);
+  if (threadIdx.x == 0) {
+    dabx_chunk_mot t;
+    t.first_object = g.first; t.n_objects = g.n; t.objects_lost = (int)(g.first - g.done); t.rec_off = ms.out.dl_rec_off; t.bytes_off = ms.out.dl_bytes_off; t.n_bytes = g.n_bytes;
+    t.objects = ms.out.count; t.object_bytes = ms.out.n_bytes; t.groups = ms.c.groups; t.headers = ms.c.headers; t.segments = ms.c.segments;
+    t.crc_bad = ms.c.crc_bad; t.grp_short = ms.c.grp_short; t.hdr_bad = ms.c.hdr_bad; t.obj_overflow = ms.c.obj_overflow; t.resets = ms.c.resets;
+    t.progress_events = ms.c.progress_events;
+    reinterpret_cast<dabx_chunk_mot *>(slab + off_mot)[(size_t)ms.s * md.max_subch + ms.j] = t;
+    ms.out.dl_done = ms.out.count;
+  }
+}
+int launch_deliver_mot(const EngineDev &e, const DeliverDev &dv, const MotDev &md, hipStream_t st)
+{
+  if (!dv.hdr.off_mot || md.n <= 0) return 0;
+  DABX_HIP(hipMemsetAsync(dv.slab + dv.hdr.off_mot, 0, sizeof(dabx_chunk_mot) * (size_t)e.n_streams * e.max_subch, st));
+  hipLaunchKernelGGL(k_deliver_mot, dim3(md.n), dim3(64), 0, st, md, dv.slab, (unsigned long long)dv.hdr.off_mot);
   DABX_HIP(hipGetLastError());
   return 0;
 }

@@ -375,6 +375,7 @@ void dabx_destroy(dabx_engine *e)
   }
   e->pkt.destroy();
   e->pad.destroy();
+  e->mot.destroy();
   for (void *p : e->allocs) (void)hipFree(p);
   if (e->locked_host) (void)hipHostFree(e->locked_host);
   if (e->seq_timeouts_host) (void)hipHostFree(e->seq_timeouts_host);
@@ -406,6 +407,7 @@ static int set_subchannels_impl(dabx_engine *e, int stream, const dabx_subch_des
   DABX_HIP(hipMemcpy(e->subch_host.data(), d.subch, sizeof(SubchDev) * e->subch_host.size(), hipMemcpyDeviceToHost));
   if ((rc = e->pkt.download(d.max_subch))) return rc;
   if ((rc = e->pad.download(d.max_subch))) return rc;
+  if ((rc = e->mot.download(d.max_subch))) return rc;
   int max_kbps = e->max_kbps;
   std::vector<SubchDev> row(std::max(1, d.max_subch));
   for (int j = 0; j < n; j++) {
@@ -503,6 +505,10 @@ static int set_subchannels_impl(dabx_engine *e, int stream, const dabx_subch_des
     for (size_t sj : restarted) e->pad.drop(sj);
     if ((rc = e->pad.upload())) return rc;
     pad_count_sources(e);
+  }
+  if (!e->mot.host.empty()) {           // ... and the MOT decoding behind it
+    for (size_t sj : restarted) e->mot.drop(sj);
+    if ((rc = mot_follow_pad(e))) return rc;
   }
   if (e->dl.open) {
     // slots that start anew count their frames from 0 again; the slab layout follows the new sub-channels (engine drained above)
@@ -793,7 +799,7 @@ int dabx_process(dabx_engine *e, int max_frames, int sync)
       e->dev.snap = e->snap_buf[e->ss.batch_parity];
       hipStream_t tail = e->stream;
       rc = launch_msc_batch(e->dev, 4 * e->pending_frames, e->have_fast ? &e->fast : nullptr, e->ss, e->mk, e->dl.open ? &dv : nullptr, &tail,
-                            e->pkt.dev.n > 0 ? &e->pkt.dev : nullptr, e->pad.dev.n > 0 ? &e->pad.dev : nullptr);
+                            e->pkt.dev.n > 0 ? &e->pkt.dev : nullptr, e->pad.dev.n > 0 ? &e->pad.dev : nullptr, e->mot.dev.n > 0 ? &e->mot.dev : nullptr);
       if (rc) {
         if (e->dl.open) e->delivery_abort(dl_slot, dl_dev);          // the slabs of the chunk that was begun: never left IN_FLIGHT without a copy job
         e->pending_frames = 0;

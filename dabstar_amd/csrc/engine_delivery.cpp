@@ -2,6 +2,7 @@
 #include "engine.h"
 #include <algorithm>
 #include <chrono>
+#include <cstddef>
 #include <cstring>
 #include <string>
 #include <thread>
@@ -9,7 +10,7 @@
 
 // ---- bulk delivery (include/dabx.h "Bulk delivery", deliver.hip) -------------------------------------------------------
 // the slab's records are ABI: hosts and the python binding (dabstar_amd/lib.py, CHUNK_*) parse them by these sizes
-static_assert(sizeof(dabx_chunk_header) == 128 && sizeof(dabx_chunk_stream) == 72 && sizeof(dabx_chunk_frame) == 16 && sizeof(dabx_chunk_subch) == 144 &&
+static_assert(sizeof(dabx_chunk_header) == 128 && sizeof(dabx_chunk_stream) == 72 && sizeof(dabx_chunk_frame) == 16 && sizeof(dabx_chunk_subch) == 144 && offsetof(dabx_chunk_header, off_mot) == 112 &&
               sizeof(dabx_superframe_info) == 32,
               "include/dabx.h: chunk record layout");
 static constexpr int DL_SF_CAP = (4 * DL_FRAMES + 4) / 5;          // super frames one chunk can complete (4 CIFs may be waiting from before)
@@ -81,6 +82,8 @@ int dabx_engine::delivery_layout()
   if (h.off_dg) h.what |= DABX_DELIVER_DG;
   off = layout_section(pad, D.want_pad && !d.fic_only, off, S * M * sizeof(dabx_chunk_pad), &h.off_pad);
   if (h.off_pad) h.what |= DABX_DELIVER_PAD;
+  off = layout_section(mot, D.want_mot && !d.fic_only, off, S * M * sizeof(dabx_chunk_mot), &h.off_mot);     // ... and behind that the MOT section (dabx_chunk_mot)
+  if (h.off_mot) h.what |= DABX_DELIVER_MOT;
   off = align_up(off, 256);
   h.off_msc = off;
   if ((D.what & (DABX_DELIVER_MSC | DABX_DELIVER_MSC_NOT_DABPLUS)) && !d.fic_only)
@@ -100,6 +103,7 @@ int dabx_engine::delivery_layout()
   D.bytes = off;
   if (!pkt.host.empty()) if (int rc = pkt.upload()) return rc;
   if (!pad.host.empty()) if (int rc = pad.upload()) return rc;
+  if (!mot.host.empty()) if (int rc = mot.upload()) return rc;
   if (S * M) {
     DABX_HIP(hipMemcpy(D.layout_off, lo.data(), sizeof(unsigned long long) * 3 * S * M, hipMemcpyHostToDevice));
     std::vector<int32_t> ids(subch_id_host.begin(), subch_id_host.begin() + S * M);
@@ -301,7 +305,7 @@ extern "C" {
 
 int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
 {
-  if (!e || (cfg && (cfg->host_slabs < 0 || cfg->host_slabs == 1 || cfg->host_slabs > 64 || (cfg->what & ~63) || cfg->copy_engine < 0 || cfg->copy_engine > 1))) {
+  if (!e || (cfg && (cfg->host_slabs < 0 || cfg->host_slabs == 1 || cfg->host_slabs > 64 || (cfg->what & ~127) || cfg->copy_engine < 0 || cfg->copy_engine > 1))) {
     set_error("dabx_delivery_open: bad argument");
     return DABX_E_ARG;
   }
@@ -312,7 +316,8 @@ int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
   const EngineDev &d = e->dev;
   D.want_dg = !cfg || !cfg->what || (cfg->what & DABX_DELIVER_DG);
   D.want_pad = !cfg || !cfg->what || (cfg->what & DABX_DELIVER_PAD);
-  D.what = cfg && cfg->what ? (cfg->what & ~(DABX_DELIVER_DG | DABX_DELIVER_PAD)) : (DABX_DELIVER_FIB | DABX_DELIVER_MSC | DABX_DELIVER_SF);
+  D.want_mot = !cfg || !cfg->what || (cfg->what & DABX_DELIVER_MOT);
+  D.what = cfg && cfg->what ? (cfg->what & ~(DABX_DELIVER_DG | DABX_DELIVER_PAD | DABX_DELIVER_MOT)) : (DABX_DELIVER_FIB | DABX_DELIVER_MSC | DABX_DELIVER_SF);
   if ((D.what & DABX_DELIVER_FIB) && d.out_frames < DL_FRAMES) {
     set_error("dabx_delivery_open: the engine's FIB ring holds %d frames, a chunk up to %d: create it with dabx_config.out_frames >= %d "
               "(the FIBs of a chunk's first frames would have left the ring before they are gathered)", d.out_frames, DL_FRAMES, DL_FRAMES);
@@ -328,9 +333,10 @@ int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
   const size_t per_cif = 5632;
   size_t cap = sizeof(dabx_chunk_header) + S * sizeof(dabx_chunk_stream) + S * M * sizeof(dabx_chunk_subch) + S * F * (384 + 12 + sizeof(dabx_chunk_frame)) + 6 * 16 + 256;
   if (M && !d.fic_only) cap += S * ((size_t)4 * F * per_cif + (size_t)DL_SF_CAP * 5 * per_cif + 2 * 16 * M + M * DL_SF_CAP * sizeof(dabx_superframe_info));
-  // ... and the data-group and the PAD section
-  if ((rc = e->pkt.download(d.max_subch)) || (rc = e->pad.download(d.max_subch))) return rc;
-  cap += section_capacity(e->pkt, S * M * sizeof(dabx_chunk_dg)) + section_capacity(e->pad, S * M * sizeof(dabx_chunk_pad));
+  // ... and the data-group, the PAD and the MOT section
+  if ((rc = e->pkt.download(d.max_subch)) || (rc = e->pad.download(d.max_subch)) || (rc = e->mot.download(d.max_subch))) return rc;
+  cap += section_capacity(e->pkt, S * M * sizeof(dabx_chunk_dg)) + section_capacity(e->pad, S * M * sizeof(dabx_chunk_pad)) +
+         section_capacity(e->mot, S * M * sizeof(dabx_chunk_mot));
   D.capacity = align_up(cap, 4096);
 #define H(x) do { hipError_t err__ = (x); if (err__ != hipSuccess) { set_error("HIP error %d (%s) at %s:%d", (int)err__, hipGetErrorString(err__), __FILE__, __LINE__); delivery_free(e); return DABX_E_HIP; } } while (0)
   if (D.copy_engine == 1) H(hipStreamCreateWithFlags(&D.cs, hipStreamNonBlocking));

@@ -1,5 +1,5 @@
-// engine_slots.cpp -- the slots with output rings, packet mode and PAD: what their entry points share and dabx_set_*_mode, dabx_read_*,
-// dabx_get_*_stats.
+// engine_slots.cpp -- the slots with output rings, packet mode, PAD and the MOT objects of the X-PAD: what their entry points share and
+// dabx_set_*_mode, dabx_read_*, dabx_get_*_stats.
 #include "engine.h"
 #include <algorithm>
 #include <cstddef>
@@ -17,16 +17,33 @@ void pad_count_sources(dabx_engine *e)
   e->pad.dev.n_mp2 = n;
 }
 
+// The MOT job table follows the PAD job table: called behind every e->pad.upload() that may have changed the PAD slots, with a fresh mirror
+// of the MOT table (download with the engine drained).  A MOT slot whose PAD decoding is gone leaves the stage; the others learn their PAD
+// slot's place in the rebuilt table.
+int mot_follow_pad(dabx_engine *e)
+{
+  auto &tab = e->mot;
+  if (tab.host.empty()) return 0;
+  for (size_t sj = 0; sj < tab.host.size(); sj++) {
+    if (!tab.host[sj].on) continue;
+    if (!e->pad.on(sj)) tab.drop(sj);
+    else tab.host[sj].st.pad_index = e->pad.index[sj];
+  }
+  return tab.upload();
+}
+
 }  // namespace dabx
 
 // ---- slots with output rings (out_ring.h): what the packet-mode and the PAD entry points below share -------------------------------------
 static uint32_t pow2_at_least(size_t v) { uint32_t p = 1; while (p < v) p <<= 1; return p; }
 
 // The rings of a slot that is switched on (n_bytes, n_rec: powers of two) and what one chunk of the bulk delivery has room for
-template <class Rec> static bool out_ring_create(OutRing<Rec> *r, uint32_t n_bytes, uint32_t n_rec, uint32_t asm_room, uint32_t dl_rec_cap, uint32_t dl_bytes_cap)
+// (extra: bytes the stage keeps behind the byte ring in the same allocation, freed with it)
+template <class Rec> static bool out_ring_create(OutRing<Rec> *r, uint32_t n_bytes, uint32_t n_rec, uint32_t asm_room, uint32_t dl_rec_cap, uint32_t dl_bytes_cap,
+                                                 size_t extra = 0)
 {
   void *b = nullptr, *q = nullptr;
-  if (hipMalloc(&b, n_bytes) != hipSuccess || hipMalloc(&q, sizeof(Rec) * (size_t)n_rec) != hipSuccess) {
+  if (hipMalloc(&b, (size_t)n_bytes + extra) != hipSuccess || hipMalloc(&q, sizeof(Rec) * (size_t)n_rec) != hipSuccess) {
     if (b) (void)hipFree(b);
     return false;
   }
@@ -36,13 +53,15 @@ template <class Rec> static bool out_ring_create(OutRing<Rec> *r, uint32_t n_byt
   return true;
 }
 
-// The tail of dabx_set_packet_mode / dabx_set_pad_mode (engine drained): the slab of an open delivery follows the stage's slots.
-// delivery_layout writes BOTH job tables back from their mirrors, so the other stage's is refreshed first.
-template <class Tab> static int relayout_open_delivery(dabx_engine *e, size_t sj, const SubchDev &sc, Tab &other)
+// The tail of dabx_set_packet_mode / dabx_set_pad_mode / dabx_set_mot_mode (engine drained): the slab of an open delivery follows the
+// stage's slots.  delivery_layout writes ALL job tables back from their mirrors, so the other stages' are refreshed first.
+template <class... Tabs> static int relayout_open_delivery(dabx_engine *e, size_t sj, const SubchDev &sc, Tabs &...others)
 {
   if (!e->dl.open) return 0;
   e->subch_host[sj] = sc;
-  if (int rc = other.download(e->dev.max_subch)) return rc;
+  int rc_dl = 0;
+  ((rc_dl = rc_dl ? rc_dl : others.download(e->dev.max_subch)), ...);
+  if (rc_dl) return rc_dl;
   if (int rc = e->delivery_layout()) {
     const std::string why = dabx::last_error();
     delivery_free(e);
@@ -107,6 +126,7 @@ template <class Slot, class Dev, class Rec> static int ring_read(dabx_engine *e,
 // ---- slots with output rings: packet-mode data sub-channels (packet_core.h, k_packet) and programme-associated data (pad_core.h, k_pad) ----
 static_assert(sizeof(dabx_chunk_dg) == 128 && sizeof(dabx_datagroup_info) == 32 && sizeof(dabx_packet_stats) == 128 && sizeof(dabx_packet_config) == 32, "include/dabx.h: packet-mode records");
 static_assert(sizeof(dabx_chunk_pad) == 128 && sizeof(dabx_pad_item) == 32 && sizeof(dabx_pad_stats) == 128 && sizeof(dabx_pad_config) == 32, "include/dabx.h: PAD records");
+static_assert(sizeof(dabx_chunk_mot) == 128 && sizeof(dabx_mot_object) == 32 && sizeof(dabx_mot_stats) == 128 && sizeof(dabx_mot_config) == 32, "include/dabx.h: MOT records");
 static_assert(sizeof(dabx_mp2_sync_stats) == 64 && offsetof(dabx_pad_config, source) == 4, "include/dabx.h: PAD of MP2 frames");
 
 extern "C" {
@@ -152,7 +172,7 @@ int dabx_set_packet_mode(dabx_engine *e, int stream, int j, const dabx_packet_co
     tab.host[sj] = h;
   }
   if ((rc = tab.upload())) return rc;
-  return relayout_open_delivery(e, sj, sc, e->pad);
+  return relayout_open_delivery(e, sj, sc, e->pad, e->mot);
 }
 
 int dabx_read_datagroups(dabx_engine *e, int stream, int j, int n, dabx_datagroup_info *info, uint8_t *bytes, size_t max_bytes)
@@ -204,8 +224,9 @@ int dabx_set_pad_mode(dabx_engine *e, int stream, int j, const dabx_pad_config *
     tab.host.resize((size_t)e->dev.n_streams * e->dev.max_subch);
     tab.index.assign(tab.host.size(), -1);
   }
-  if ((rc = tab.download(e->dev.max_subch))) return rc;
+  if ((rc = tab.download(e->dev.max_subch)) || (rc = e->mot.download(e->dev.max_subch))) return rc;
   tab.drop(sj);
+  e->mot.drop(sj);                                                     // PAD restarts with empty rings: nothing for k_mot to follow
   if (cfg) {
     decltype(e->pad)::Host h;
     h.on = true;
@@ -217,13 +238,15 @@ int dabx_set_pad_mode(dabx_engine *e, int stream, int j, const dabx_pad_config *
       set_error("dabx_set_pad_mode: out of device memory");
       (void)tab.upload();
       pad_count_sources(e);
+      (void)mot_follow_pad(e);
       return DABX_E_NOMEM;
     }
     tab.host[sj] = h;
   }
   if ((rc = tab.upload())) return rc;
   pad_count_sources(e);
-  return relayout_open_delivery(e, sj, sc, e->pkt);
+  if ((rc = mot_follow_pad(e))) return rc;
+  return relayout_open_delivery(e, sj, sc, e->pkt, e->mot);
 }
 
 int dabx_get_mp2_sync_stats(dabx_engine *e, int stream, int j, dabx_mp2_sync_stats *out)
@@ -264,6 +287,85 @@ int dabx_get_pad_stats(dabx_engine *e, int stream, int j, dabx_pad_stats *out)
   out->label_bytes = c.label_bytes; out->groups = c.groups; out->group_bytes = c.group_bytes; out->items_lost = e->pad.host[sj].lost;
   out->li_bad = i32(c.li_bad); out->dl_overflow = i32(c.dl_overflow); out->dg_crc_bad = i32(c.dg_crc_bad); out->dg_small = i32(c.dg_small);
   out->active = 1;
+  return 0;
+}
+
+// ---- MOT objects of the X-PAD (mot_core.h, k_mot) ----------------------------------------------------------------------------------------
+int dabx_set_mot_mode(dabx_engine *e, int stream, int j, const dabx_mot_config *cfg)
+{
+  if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch) { set_error("dabx_set_mot_mode: bad argument"); return DABX_E_ARG; }
+  if (cfg && cfg->size < sizeof(uint32_t)) { set_error("dabx_set_mot_mode: bad configuration (size %u)", cfg->size); return DABX_E_ARG; }
+  const uint32_t max_bytes = cfg && cfg->size >= 2 * sizeof(uint32_t) && cfg->max_object_bytes ? cfg->max_object_bytes : MOT_OBJECT_BYTES_DEFAULT;
+  if (max_bytes < MOT_OBJECT_BYTES_MIN || max_bytes > MOT_OBJECT_BYTES_MAX) {
+    set_error("dabx_set_mot_mode: max_object_bytes %u is not within %u .. %u", max_bytes, MOT_OBJECT_BYTES_MIN, MOT_OBJECT_BYTES_MAX);
+    return DABX_E_ARG;
+  }
+  int rc;
+  if ((rc = sync_all(e))) return rc;
+  const size_t sj = (size_t)stream * e->dev.max_subch + j;
+  if (cfg && !e->pad.on(sj)) { set_error("dabx_set_mot_mode: stream %d slot %d has no PAD decoding (dabx_set_pad_mode)", stream, j); return DABX_E_ARG; }
+  SubchDev sc;
+  DABX_HIP(hipMemcpy(&sc, e->dev.subch + sj, sizeof(SubchDev), hipMemcpyDeviceToHost));
+  auto &tab = e->mot;
+  if (tab.host.empty()) {
+    if (!cfg) return 0;
+    tab.host.resize((size_t)e->dev.n_streams * e->dev.max_subch);
+    tab.index.assign(tab.host.size(), -1);
+  }
+  if ((rc = tab.download(e->dev.max_subch))) return rc;
+  tab.drop(sj);
+  if (cfg) {
+    decltype(e->mot)::Host h;
+    h.on = true;
+    h.st.s = stream; h.st.j = j; h.st.pad_index = e->pad.index[sj]; h.st.max_object_bytes = max_bytes;
+    PadSlot ps;                                                        // the walk starts with the next PAD item emitted
+    DABX_HIP(hipMemcpy(&ps, e->pad.dev.slots + e->pad.index[sj], sizeof(PadSlot), hipMemcpyDeviceToHost));
+    h.st.items_seen = ps.out.count;
+    h.st.h.transport_id = -1; h.st.h.num_segments = -1; h.st.h.max_seg = -1;      // mot_object.h:82-83
+    const uint32_t ring = mot_byte_ring(max_bytes);                    // (mot_core.h has the derivations)
+    if (!out_ring_create(&h.st.out, ring, MOT_REC_RING, 0, MOT_DL_REC_CAP, 2 * max_bytes, mot_extra_bytes(max_bytes))) {
+      set_error("dabx_set_mot_mode: out of device memory");
+      (void)tab.upload();
+      return DABX_E_NOMEM;
+    }
+    h.st.arena = h.st.out.bytes + ring;
+    h.st.name = h.st.arena + (((size_t)max_bytes + 7) & ~(size_t)7);
+    h.st.table = reinterpret_cast<MotSeg *>(h.st.name + MOT_NAME_ROOM);
+    tab.host[sj] = h;
+    if (hipMemset(h.st.table, 0xFF, sizeof(MotSeg) * MOT_MAX_SEGMENTS) != hipSuccess) {       // every segment number absent (MOT_ABSENT)
+      tab.drop(sj);
+      (void)tab.upload();
+      set_error("dabx_set_mot_mode: clearing the segment table failed");
+      return DABX_E_HIP;
+    }
+  }
+  if ((rc = tab.upload())) return rc;
+  return relayout_open_delivery(e, sj, sc, e->pkt, e->pad);
+}
+
+int dabx_read_mot_objects(dabx_engine *e, int stream, int j, int n, dabx_mot_object *info, uint8_t *bytes, size_t max_bytes)
+{
+  if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch || n <= 0 || !info) { set_error("dabx_read_mot_objects: bad argument"); return DABX_E_ARG; }
+  return ring_read(e, e->mot, (size_t)stream * e->dev.max_subch + j, n, info, bytes, max_bytes);
+}
+
+int dabx_get_mot_stats(dabx_engine *e, int stream, int j, dabx_mot_stats *out)
+{
+  if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch || !out) { set_error("dabx_get_mot_stats: bad argument"); return DABX_E_ARG; }
+  memset(out, 0, sizeof(*out));
+  const size_t sj = (size_t)stream * e->dev.max_subch + j;
+  if (!e->mot.on(sj)) return sync_all(e);
+  MotSlot st;
+  long long lo = 0;
+  if (int rc = ring_window(e, e->mot, sj, &st, &lo)) return rc;
+  const MotCounters &c = st.c;
+  auto i32 = [](long long v) { return (int32_t)std::min<long long>(v, INT32_MAX); };
+  out->objects = st.out.count; out->object_bytes = st.out.n_bytes; out->objects_lost = e->mot.host[sj].lost;
+  out->groups = c.groups; out->headers = c.headers; out->segments = c.segments;
+  out->crc_bad = i32(c.crc_bad); out->type_other = i32(c.type_other); out->no_tid = i32(c.no_tid); out->grp_short = i32(c.grp_short);
+  out->hdr_bad = i32(c.hdr_bad); out->seg_number_bad = i32(c.seg_number_bad); out->seg_duplicate = i32(c.seg_duplicate); out->resets = i32(c.resets);
+  out->obj_overflow = i32(c.obj_overflow); out->pad_overrun = i32(c.pad_overrun); out->progress_events = i32(c.progress_events);
+  out->progress_pct = st.h.progress_pct; out->transport_id = st.h.transport_id; out->segments_stored = st.h.n_stored; out->active = 1;
   return 0;
 }
 

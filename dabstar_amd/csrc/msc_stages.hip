@@ -5,11 +5,13 @@
 //   k_dabplus      super-frame sync, RS(120,110), fire code, AU CRCs (mp4processor.cpp:96-333); moves the slots' frame counters on
 //   k_pad          PAD of the DAB+ access units: dynamic labels and X-PAD MSC data groups (mp4processor.cpp:345-353, pad_handler.cpp:67-547)
 //   k_pad_mp2      PAD of DAB (MP2) audio frames: MP2 frame sync over the logical frames and the same PadHandler (mp2processor.cpp:611-747)
+//   k_mot          MOT objects out of the X-PAD data groups the two PAD kernels have just emitted (pad_handler.cpp:553-622, mot_object.cpp:71-323)
 //
 // Which logical frames of a slot are new in a batch is msc_new_frames (pipeline.h), for every stage and for the delivery (deliver.hip).
 #include "pipeline.h"
 #include "packet_core.h"
 #include "pad_core.h"
+#include "mot_core.h"
 #include "fec_core.h"
 #include "wave_ops.h"
 
@@ -485,6 +487,52 @@ __global__ __launch_bounds__(64) void k_pad_mp2(PadDev pd)
   if (lane == 0) ps.m = m;
 }
 
+// --------------------------------------------------------------------------------------------------- MOT
+// One wave per MOT-enabled PAD slot (MotDev::slots: those slots only), behind k_pad and k_pad_mp2: walks the items the slot's PAD kernel has
+// emitted since this slot's last visit (PadSlot::out.count against MotSlot::items_seen) out of the PAD rings and takes the
+// DABX_PAD_DATAGROUP items through the tail of _build_MSC_segment and the handler's MotObject (mot_core.h: pad_handler.cpp:539-622 and
+// mot_object.cpp:71-323 line by line).  The PAD rings hold what two batches emit, so every item of this batch is intact; the rule is
+// checked all the same (out_ring_oldest, out_ring_intact) and a violation is counted in pad_overrun instead of read.  Header fields are
+// wave-uniform and the state machine is scalar; the whole wave copies a body segment into the slot's arena and a header segment into LDS,
+// completeness is a ballot over the segment table, and an emit gathers the stored segments in key order straight into the byte ring.
+// include/dabx.h "MOT objects of the X-PAD" states the semantics and the guards M1..M3.
+__global__ __launch_bounds__(64) void k_mot(MotDev md)
+{
+  const int lane = threadIdx.x;
+  MotSlot &ms = md.slots[blockIdx.x];
+  if (ms.pad_index < 0 || ms.pad_index >= md.n_pad) return;
+  const PadSlot &ps = md.pad_slots[ms.pad_index];
+  const long long count = ps.out.count;
+  long long seen = ms.items_seen;
+  if (count <= seen) return;
+  __shared__ __attribute__((aligned(16))) uint8_t s_hdr[MOT_NAME_ROOM];
+  MotWave w;
+  w.h = ms.h; w.c = ms.c;
+  w.pad_ring = ps.out.bytes; w.pad_mask = ps.out.bytes_mask;
+  w.arena = ms.arena; w.name = ms.name; w.table = ms.table;
+  w.ring = ms.out.bytes; w.recs = ms.out.recs; w.bytes_mask = ms.out.bytes_mask; w.rec_mask = ms.out.rec_mask;
+  w.n_recs = ms.out.count; w.n_bytes = ms.out.n_bytes;
+  w.max_object_bytes = ms.max_object_bytes;
+  w.lane = lane; w.hdr = s_hdr; w.frame = 0; w.au = 0;
+  const dabx_pad_item *items = ps.out.recs;
+  const unsigned long long item_mask = ps.out.rec_mask;
+  const long long oldest = out_ring_oldest(ps.out);
+  if (seen < oldest) { w.c.pad_overrun += oldest - seen; seen = oldest; }      // (cannot happen: the stage runs behind every batch)
+  for (long long i = seen; i < count; i++) {
+    const unsigned long long *r = reinterpret_cast<const unsigned long long *>(items + (size_t)((unsigned long long)i & item_mask));
+    const unsigned long long r2 = r[2];                          // length, kind, au, charset, crc_flag, crc_ok (pad_put_item)
+    const unsigned lo = pad_u((unsigned)r2), hi = pad_u((unsigned)(r2 >> 32));
+    if (((lo >> 16) & 0xFFu) != DABX_PAD_DATAGROUP) continue;
+    const long long pos = (long long)(((unsigned long long)pad_u((unsigned)(r[0] >> 32)) << 32) | pad_u((unsigned)r[0]));
+    if (!out_ring_intact(ps.out, pos)) { w.c.pad_overrun++; continue; }
+    w.frame = (long long)(((unsigned long long)pad_u((unsigned)(r[1] >> 32)) << 32) | pad_u((unsigned)r[1]));
+    w.au = (int)((lo >> 24) & 0xFFu);
+    mot_group(w, pos, (int)(lo & 0xFFFFu), ((hi >> 8) & 1u) != 0, ((hi >> 16) & 1u) != 0);
+  }
+  __syncthreads();
+  if (lane == 0) { ms.h = w.h; ms.c = w.c; ms.out.count = w.n_recs; ms.out.n_bytes = w.n_bytes; ms.items_seen = count; }
+}
+
 // ---------------------------------------------------------------------------------------------- launchers
 // One per stage, on the stream launch_msc_batch gives them.  The packet and PAD launchers take the engine's job table (null or n = 0: the
 // engine has no such slot, no launch), fill in what the kernel reads of the engine and leave the argument they launched with in *used for
@@ -545,6 +593,21 @@ int launch_pad_stage(const EngineDev &e, const PadDev *pad, hipStream_t st, Mark
   if (q.n > q.n_mp2) hipLaunchKernelGGL(k_pad, dim3(q.n), dim3(64), 0, st, q);
   if (q.n_mp2 > 0) hipLaunchKernelGGL(k_pad_mp2, dim3(q.n), dim3(64), 0, st, q);
   mk.end(12, st);
+  DABX_HIP(hipGetLastError());
+  *used = q;
+  return 0;
+}
+
+// behind the PAD stage: k_mot reads the PAD rings as that launch left them (`pad`: the argument launch_pad_stage launched with)
+int launch_mot_stage(const EngineDev &e, const MotDev *mot, const PadDev &pad, hipStream_t st, Marker &mk, MotDev *used)
+{
+  *used = MotDev{};
+  if (!mot || mot->n <= 0 || pad.n <= 0) return 0;
+  MotDev q = *mot;
+  q.max_subch = e.max_subch; q.pad_slots = pad.slots; q.n_pad = pad.n;
+  mk.begin(13, st);
+  hipLaunchKernelGGL(k_mot, dim3(q.n), dim3(64), 0, st, q);
+  mk.end(13, st);
   DABX_HIP(hipGetLastError());
   *used = q;
   return 0;

@@ -69,6 +69,10 @@ def load(build_if_missing=True):
         L.dabx_set_pad_mode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.dabx_read_pad_items.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
         L.dabx_get_pad_stats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    if hasattr(L, "dabx_set_mot_mode"):              # MOT objects of the X-PAD
+        L.dabx_set_mot_mode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.dabx_read_mot_objects.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.dabx_get_mot_stats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     if hasattr(L, "dabx_get_mp2_sync_stats"):        # ... and of DAB (MP2) audio slots
         L.dabx_get_mp2_sync_stats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     if hasattr(L, "dabx_announce_write"):            # (absent from libraries older than the level anchor: tools/ab.sh runs those through this binding too)
@@ -406,11 +410,11 @@ class Stats(C.Structure):
 # ---- bulk delivery (include/dabx.h "Bulk delivery"): the slab's records as numpy dtypes -----------------------------
 CHUNK_FRAMES = 7
 CHUNK_MAGIC = 0x43584244
-DELIVER_FIB, DELIVER_MSC, DELIVER_SF, DELIVER_MSC_NOT_DABPLUS, DELIVER_DG, DELIVER_PAD = 1, 2, 4, 8, 16, 32
+DELIVER_FIB, DELIVER_MSC, DELIVER_SF, DELIVER_MSC_NOT_DABPLUS, DELIVER_DG, DELIVER_PAD, DELIVER_MOT = 1, 2, 4, 8, 16, 32, 64
 CHUNK_HEADER = np.dtype([("magic", "<u4"), ("abi", "<u4"), ("seq", "<u8"), ("n_streams", "<i4"), ("max_subch", "<i4"),
                          ("max_frames", "<i4"), ("what", "<i4"), ("bytes", "<u8"), ("off_stream", "<u8"), ("off_subch", "<u8"),
                          ("off_fib", "<u8"), ("off_crc", "<u8"), ("off_frame", "<u8"), ("off_msc", "<u8"), ("off_sf", "<u8"),
-                         ("off_dg", "<u8"), ("off_pad", "<u8"), ("reserved", "<u8", 2)])
+                         ("off_dg", "<u8"), ("off_pad", "<u8"), ("off_mot", "<u8"), ("reserved", "<u8", 1)])
 CHUNK_STREAM = np.dtype([("first_frame", "<i8"), ("n_frames", "<i4"), ("frames_lost", "<i4"), ("state", "<i4"),
                          ("fic_ratio_percent", "<i4"), ("cif_count", "<i4"), ("snr_db_est", "<f4"), ("freq_offs_bb_hz", "<f4"),
                          ("clock_err_hz", "<f4"), ("signal_level", "<f4"), ("fic_ber_bits", "<i4"), ("fic_ber_errors", "<i4"),
@@ -460,6 +464,28 @@ MP2_SEARCHING, MP2_GET_RATE, MP2_GET_DATA = 0, 1, 2
 MP2_SYNC_STATS = np.dtype([(k, "<i8") for k in ("syncs", "frames", "hdr_refused", "rate_unsupported")] +
                           [(k, "<i4") for k in ("sample_rate", "state", "bit_count", "header_count", "last_sync_bit", "active")] + [("reserved", "<i4", 2)])
 assert MP2_SYNC_STATS.itemsize == 64
+
+
+# MOT objects of the X-PAD (include/dabx.h): dabx_mot_object, one record per signal_new_mot_object, dabx_mot_stats and the slab's MOT
+# section (dabx_chunk_mot): one row per (stream, slot), all zero for a slot without MOT decoding
+MOT_OBJECT_BYTES_DEFAULT = 65536
+MOT_NAME_ROOM = 8192
+MOT_OBJECT = np.dtype([("byte_pos", "<i8"), ("frame", "<i8"), ("body_len", "<u4"), ("body_size", "<u4"), ("transport_id", "<u2"),
+                       ("content_type", "<u2"), ("name_len", "<u2"), ("au", "u1"), ("repeat", "u1")])
+MOT_COUNTERS = ("objects", "object_bytes", "groups", "headers", "segments", "crc_bad", "type_other", "no_tid", "grp_short", "hdr_bad",
+                "seg_number_bad", "seg_duplicate", "resets", "obj_overflow", "pad_overrun", "progress_events", "progress_pct", "transport_id",
+                "segments_stored")
+MOT_STATS = np.dtype([(k, "<i8") for k in ("objects", "object_bytes", "objects_lost", "groups", "headers", "segments")] +
+                     [(k, "<i4") for k in MOT_COUNTERS[5:] + ("active",)] + [("reserved", "<i4", 5)])
+CHUNK_MOT = np.dtype([("first_object", "<i8"), ("n_objects", "<i4"), ("objects_lost", "<i4"), ("rec_off", "<u8"), ("bytes_off", "<u8"), ("n_bytes", "<i8")] +
+                     [(k, "<i8") for k in ("objects", "object_bytes", "groups", "headers", "segments", "crc_bad", "grp_short", "hdr_bad", "obj_overflow",
+                                           "resets", "progress_events")])
+assert MOT_OBJECT.itemsize == 32 and MOT_STATS.itemsize == 128 and CHUNK_MOT.itemsize == 128
+
+
+class MotConfig(C.Structure):
+    """dabx_mot_config."""
+    _fields_ = [("size", C.c_uint32), ("max_object_bytes", C.c_uint32), ("reserved", C.c_int32 * 6)]
 
 
 class PadConfig(C.Structure):
@@ -513,6 +539,9 @@ class Chunk:
         self.pad = None                         # the PAD section: [S, M] CHUNK_PAD, or None when the slab has none
         if int(h["off_pad"]):
             self.pad = self.raw[int(h["off_pad"]):int(h["off_pad"]) + S * M * 128].view(CHUNK_PAD).reshape(S, M)
+        self.mot = None                         # the MOT section: [S, M] CHUNK_MOT, or None when the slab has none
+        if int(h["off_mot"]):
+            self.mot = self.raw[int(h["off_mot"]):int(h["off_mot"]) + S * M * 128].view(CHUNK_MOT).reshape(S, M)
 
     def msc(self, s, j):
         """Logical frames of slot (s, j) in this chunk: [n_cifs, 3 * kbps] uint8 (a view)."""
@@ -550,6 +579,12 @@ class Chunk:
         """PAD items of slot (s, j) in this chunk: ([n_items] PAD_ITEM, their n_bytes bytes), views; item i is
         bytes[byte_pos[i] : byte_pos[i] + length[i]].  Empty when the slab has no PAD section or the slot has no PAD decoding."""
         return self._ring_items(self.pad, "item_off", "n_items", PAD_ITEM, s, j)
+
+    def mot_objects(self, s, j):
+        """MOT objects of slot (s, j) in this chunk: ([n_objects] MOT_OBJECT, their n_bytes bytes), views; object i is
+        bytes[byte_pos[i] : byte_pos[i] + body_len[i] + name_len[i]], body first.  Empty when the slab has no MOT section or the slot has no
+        MOT decoding."""
+        return self._ring_items(self.mot, "rec_off", "n_objects", MOT_OBJECT, s, j)
 
     def release(self):
         if self._eng is not None:
@@ -807,6 +842,37 @@ class Engine:
         out = np.zeros(1, PAD_STATS)
         check(L.dabx_get_pad_stats(self._h, int(stream), int(j), _p(out)))
         return {k: int(out[0][k]) for k in PAD_STATS.names if k != "reserved"}
+
+    def set_mot_mode(self, stream, j, on=True, max_object_bytes=0):
+        """Switches the MOT decoding of PAD slot j of `stream` on (restarting it when it is on already) or off (dabx_set_mot_mode).
+        max_object_bytes: the bound of an object's stored segments, 0 = 65 536."""
+        L = load()
+        if not on:
+            check(L.dabx_set_mot_mode(self._h, int(stream), int(j), None))
+        else:
+            cfg = MotConfig(size=C.sizeof(MotConfig), max_object_bytes=int(max_object_bytes))
+            check(L.dabx_set_mot_mode(self._h, int(stream), int(j), C.byref(cfg)))
+
+    def read_mot_objects(self, stream, j, n=256, max_bytes=None, with_bytes=True):
+        """(records [k] MOT_OBJECT, bytes uint8) of the newest k <= n MOT objects of slot j that are still in its rings, oldest first;
+        object i is bytes[byte_pos[i] : byte_pos[i] + body_len[i] + name_len[i]], the body and then the name.  with_bytes = False: the
+        records alone.  max_bytes None: as much as `n` objects of the default size can have."""
+        call = load().dabx_read_mot_objects
+        info = np.zeros(max(1, n), MOT_OBJECT)
+        if not with_bytes:
+            return info[:check(call(self._h, int(stream), int(j), int(n), _p(info), None, 0))], np.zeros(0, np.uint8)
+        if max_bytes is None:
+            max_bytes = 2 * (MOT_OBJECT_BYTES_DEFAULT + MOT_NAME_ROOM)
+        buf = np.zeros(max(1, int(max_bytes)), np.uint8)
+        k = check(call(self._h, int(stream), int(j), int(n), _p(info), _p(buf), int(max_bytes)))
+        info = info[:k]
+        return info, buf[:int(info["body_len"].sum()) + int(info["name_len"].sum())].copy()
+
+    def mot_stats(self, stream, j):
+        """dabx_mot_stats of slot j as a dict (all zero unless MOT decoding is on for the slot)."""
+        out = np.zeros(1, MOT_STATS)
+        check(load().dabx_get_mot_stats(self._h, int(stream), int(j), _p(out)))
+        return {k: int(out[0][k]) for k in MOT_STATS.names if k != "reserved"}
 
     def mp2_sync_stats(self, stream, j):
         """dabx_mp2_sync_stats of slot j as a dict (all zero unless the slot is a PAD slot with source "mp2")."""

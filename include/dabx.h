@@ -594,7 +594,7 @@ int  dabx_get_packet_stats(dabx_engine *e, int stream, int subch_idx, dabx_packe
  *   - every _build_MSC_segment call (:478, :514) with size = min(iData.size(), mDataGroupLength) >= 2 (:528-534) is one DABX_PAD_DATAGROUP
  *     item: iData[0 .. size), crc_flag = bit 6 of byte 0 (the CrcFlag bit-field, :524, :539), crc_ok = check_crc_bytes(iData, size - 2)
  *     (:541).  A group with a bad CRC is delivered with crc_ok == 0 and counted (the reference drops it, :543); the MOT parsing from :553 on
- *     stays with the host.
+ *     is the host's, or k_mot's ("MOT objects of the X-PAD" below).
  * The state in between (pad_handler.h:68-86) lives on the device per slot and survives batch boundaries.  Four guards, where the
  * reference is undefined or unbounded; each is counted:
  *   G1 (mp4processor.cpp:347-352): the reference reads AU[2 .. 2 + count), buffer[count - 1] and buffer[count - 2] whatever they are.
@@ -630,8 +630,8 @@ int  dabx_get_packet_stats(dabx_engine *e, int stream, int subch_idx, dabx_packe
  * (vLen >= 20 and the short form always has its four bytes); G3 and the check of :219 do bite at small rates, G4 is as above.
  * Parity of this path with the reference is unpinned: mp2processor.cpp cannot be compiled without the GUI's headers, so the tests compare
  * the device with a line-by-line restatement (tests/mp2_pad_cases.py), not with the reference's object code.
- * Out of scope: MotObject / MotHandler, the charset conversion, DL Plus, F-PAD types other than 0, MP2 audio decoding, handing out
- * assembled MP2 frames. */
+ * Out of scope: MotHandler (the handler's one MotObject is "MOT objects of the X-PAD" below), the charset conversion, DL Plus, F-PAD types
+ * other than 0, MP2 audio decoding, handing out assembled MP2 frames. */
 #define DABX_DL_MAX_BYTES 256
 enum { DABX_PAD_LABEL = 1, DABX_PAD_DATAGROUP = 2 };
 enum { DABX_PAD_SOURCE_DABPLUS = 0,    /* the access units of a DAB+ slot (dab_plus == 1) */
@@ -702,6 +702,104 @@ typedef struct {
 } dabx_mp2_sync_stats;       /* 64 bytes */
 int  dabx_get_mp2_sync_stats(dabx_engine *e, int stream, int subch_idx, dabx_mp2_sync_stats *out);
 /* ------------------------------------------------------------------------------------------------------------
+ * MOT objects of the X-PAD: what PadHandler does with a data group behind the hand-over of dabx_pad_item -- the tail of
+ * _build_MSC_segment (base/backend/data/pad_handler.cpp:539-622) and the handler's one MotObject (pad_handler.cpp:54: no directory
+ * element, a PAD element; base/backend/data/mot/mot_object.cpp:71-323) -- on the device (k_mot, behind k_pad / k_pad_mp2 on the MSC
+ * batch's stream, one wave per MOT-enabled PAD slot, for both PAD sources).  Every `emit signal_new_mot_object` (:300) is one
+ * dabx_mot_object plus its bytes: the finished slideshow picture with its name and content type.  Per DABX_PAD_DATAGROUP item, in emission
+ * order; the item's `length` is the reference's `size` (:528):
+ *   1 crc_flag && !crc_ok: return (:539-545, crc_bad).  No flag: go on (:548-551).
+ *   2 DataGroupType (byte 0, bits 0-3) other than 3 / 4: return (:556-560, type_other).
+ *   3 index = ExtensionFlag (bit 7) ? 4 : 2.  SegmentFlag (bit 5): lastFlag and the 15-bit segment number, index += 2 (:567-573); without it
+ *     the number is -1.  UserAccessFlag (bit 4): lengthIndicator = low nibble, the transport id from the two bytes behind the length byte
+ *     whenever bit 4 of that byte is set, WHATEVER lengthIndicator says (:583-588); index moves by 1 + lengthIndicator only (:589).  No
+ *     transport id: return (:593-597, no_tid).
+ *   4 segmentSize = 13 bits at index, the segment starts at index + 2 (:605-616).
+ *   5 type 3, set_header (mot_object.cpp:71-115): a transport-id change resets the object first (:75-79, resets); the 7-byte header core
+ *     (:84-95); the extension walk `while pointer < headerSize` (:99-104, :210-238): PLI 0 / 1 / 2 advance by 1 / 2 / 5, PLI 3 has the 7- or
+ *     15-bit length.  ContentName (0x0C) replaces the name with bytes [pointer + 1, pointer + length) (:181-189).  Parameters 0x02-0x08,
+ *     0x0A, 0x0B and 0x0F do NOT advance the pointer by their length (:191-201): the bytes of their value are walked as parameters.  Kept.
+ *     Then _check_if_complete and the emit (:111-114).
+ *   6 type 4, add_body_segment (:117-175): a number < 0 or >= 8192: return (:119-123, seg_number_bad); a transport-id change resets the
+ *     object, header core included (:125-130); a number already stored: return (:139-143, seg_duplicate); else the segment is stored and
+ *     the sum grows; a last flag sets mNumOfSegments = number + 1, a later one overwrites it (:145-148); signal_pad_mot_progress for base
+ *     type image with bodySize > 0, clamped at 100 (:160-169: progress_pct, progress_events); _check_if_complete (:240-278: header core
+ *     seen, number of segments known, stored count >= that number, every index below it present) and the emit (:281-301): ALL stored
+ *     segments in key order, those numbered at or above mNumOfSegments too.
+ *   7 Nothing is cleared after an emit; only a transport-id change resets (:313-323).  Every repeated header of a complete object
+ *     therefore emits it again (:111-114): `repeat` counts that.
+ * Three guards, where the reference reads outside the bytes it was given or grows without bound; each is counted:
+ *   M1 (pad_handler.cpp:569-616): a header field, the segmentation header or the segment itself (index + 2 + segmentSize) would reach
+ *      beyond the item's `length` bytes: the group is ignored, state unchanged, grp_short.  Bytes inside the item, the two CRC bytes
+ *      included, are read as the reference reads them.  The reference's buffer can be longer than `size` (mMscDataGroupBuffer beyond
+ *      mDataGroupLength, :528), where its reads are defined; the item does not carry those bytes, so the guard covers that case too.
+ *   M2 (mot_object.cpp:84-87, :212-230, :185): a type-3 segment shorter than the 7 bytes of the header core is ignored, state unchanged.  An
+ *      extension read -- the parameter byte, its length bytes, a name byte -- at an index >= segmentSize ends the walk: that parameter is
+ *      not applied and the completeness check follows.  A header longer than its segment (a segmented header) ends there too.  hdr_bad.
+ *   M3 (:135-137): a body segment that would take the stored sum beyond max_object_bytes resets the object; the transport id just set
+ *      stays.  obj_overflow.  (The reference's map grows without limit.)
+ * The name needs no guard: it lies inside a header segment, fewer than 8192 bytes.
+ * Parity of this path with the reference's object code is unpinned: mot_object.cpp cannot be compiled without the GUI's headers
+ * (dabradio.h), so the tests compare the device with a line-by-line restatement (tests/mot_cases.py).
+ * Out of scope: MotHandler / MotDirectory (the packet-mode carousel with its object cache and directory mode; the reference prints "This
+ * is not working well yet" for that constructor), image decoding, the charset of the object name, and the default name "trid_<n>",
+ * which the host forms from transport_id when name_len == 0 (:293-297). */
+typedef struct {
+  uint32_t size;             /* sizeof(dabx_mot_config) of the caller */
+  uint32_t max_object_bytes; /* guard M3; 0 = 65 536; below 256 or above 4 MiB: DABX_E_ARG.  Read only when size >= 8 */
+  int32_t  reserved[6];      /* zero */
+} dabx_mot_config;           /* 32 bytes */
+typedef struct dabx_mot_object_s {
+  int64_t  byte_pos;         /* position of the object's first byte in the slot's sequence of object bytes */
+  int64_t  frame;            /* dabx_pad_item.frame of the item whose group completed the object */
+  uint32_t body_len;         /* bytes handed on: the sum of all stored segments (mot_object.cpp:286-291) */
+  uint32_t body_size;        /* the header core's bodySize (:84) */
+  uint16_t transport_id;
+  uint16_t content_type;     /* get_content_type(): ((contentType << 8) & 0x3f00) | (contentSubType & 0xff), mot_object.h:71-75 */
+  uint16_t name_len;         /* 0: the host forms "trid_<transport_id>" */
+  uint8_t  au;               /* dabx_pad_item.au of that item */
+  uint8_t  repeat;           /* emissions of this object since the last reset(), minus one, saturating at 255: a host skips repeat != 0
+                                without comparing bytes */
+} dabx_mot_object;           /* 32 bytes, little-endian, no holes; the object's bytes: body_len of body (the stored segments in key order),
+                                then name_len of name */
+typedef struct {
+  int64_t objects, object_bytes;    /* dabx_mot_object records emitted and their bytes */
+  int64_t objects_lost;      /* objects that had left the rings before a dabx_read_mot_objects call could return them */
+  int64_t groups;            /* DABX_PAD_DATAGROUP items walked */
+  int64_t headers;           /* set_header calls that read a header core */
+  int64_t segments;          /* body segments stored (:135-137) */
+  int32_t crc_bad;           /* 1 */
+  int32_t type_other;        /* 2 */
+  int32_t no_tid;            /* 3 */
+  int32_t grp_short;         /* guard M1 */
+  int32_t hdr_bad;           /* guard M2 */
+  int32_t seg_number_bad;    /* 6: :119-123 */
+  int32_t seg_duplicate;     /* 6: :139-143 */
+  int32_t resets;            /* reset() calls: transport-id changes (the first id after -1 included) and guard M3 */
+  int32_t obj_overflow;      /* guard M3 */
+  int32_t pad_overrun;       /* PAD items that had left the PAD rings before k_mot reached them (the rings hold two batches: always 0) */
+  int32_t progress_events;   /* signal_pad_mot_progress (:168) */
+  int32_t progress_pct;      /* ... and its last value */
+  int32_t transport_id;      /* mTransportId, -1 at the start */
+  int32_t segments_stored;   /* mMotMap.size() */
+  int32_t active;            /* 1: MOT decoding is on for the slot (all else is zero otherwise) */
+  int32_t reserved[5];
+} dabx_mot_stats;            /* 128 bytes */
+/* Switches the MOT decoding of slot subch_idx of `stream` on (cfg != NULL) or off (NULL).  On only for a slot whose PAD decoding is on, of
+ * either source; DABX_E_ARG otherwise.  It starts with an empty object at the next PAD item emitted; calling it again restarts it.
+ * Calling dabx_set_pad_mode for the slot, on or off, ends its MOT decoding: PAD restarts with empty rings.  The setting and the state stay
+ * with the slot wherever dabx_set_subchannels says it "keeps decoding without interruption", a move to other capacity units included; a
+ * new or changed slot loses them.  The PAD items of the slot are produced and delivered exactly as before.  An engine without a MOT slot
+ * allocates and launches nothing for this stage.  Drains the engine. */
+int  dabx_set_mot_mode(dabx_engine *e, int stream, int subch_idx, const dabx_mot_config *cfg);
+/* The newest n objects still intact in the rings, oldest first: their records into info[], their bytes back to back into bytes[];
+ * byte_pos is rebased to the returned buffer (info[0].byte_pos == 0).  When the bytes of n objects exceed max_bytes the newest objects that
+ * fit are returned (bytes == NULL: records only).  Returns the number of objects.  Older unseen ones that left the rings are counted in
+ * dabx_mot_stats.objects_lost.  The rings hold 256 records and at least two largest objects (max_object_bytes + 8 192 bytes each, as a
+ * power of two).  Drains the engine like the other dabx_read_* calls. */
+int  dabx_read_mot_objects(dabx_engine *e, int stream, int subch_idx, int n, dabx_mot_object *info, uint8_t *bytes, size_t max_bytes);
+int  dabx_get_mot_stats(dabx_engine *e, int stream, int subch_idx, dabx_mot_stats *out);
+/* ------------------------------------------------------------------------------------------------------------
  * Bulk delivery of the results to the host.  The reference hands every FIB to IFibDecoder::process_FIB
  * (base/decoder/fib_decoder_if.h:81, called from fic_decoder.cpp:234-261) and every logical frame to
  * FrameProcessor::add_to_frame (base/backend/frame_processor.h:43-46, called from backend.cpp:160) the moment it exists;
@@ -741,7 +839,11 @@ enum { DABX_DELIVER_FIB = 1, DABX_DELIVER_MSC = 2, DABX_DELIVER_SF = 4,
        /* the PAD items of the PAD-enabled slots (dabx_set_pad_mode): with this bit, or with what == 0, AND at least one PAD slot the slab
           gains a PAD section (dabx_chunk_pad below) and dabx_chunk_header.what shows the bit; without a PAD slot a slab is byte for byte
           what it is without the bit, dabx_delivery_slab_bytes included */
-       DABX_DELIVER_PAD = 32 };
+       DABX_DELIVER_PAD = 32,
+       /* the MOT objects of the MOT-enabled PAD slots (dabx_set_mot_mode): with this bit, or with what == 0, AND at least one MOT slot the
+          slab gains a MOT section (dabx_chunk_mot below) and dabx_chunk_header.what shows the bit; without a MOT slot a slab is byte for
+          byte what it is without the bit, dabx_delivery_slab_bytes included */
+       DABX_DELIVER_MOT = 64 };
 typedef struct {
   int32_t host_slabs;       /* page-locked host slabs, >= 2 (0 = default 4) */
   int32_t what;             /* DABX_DELIVER_* mask, 0 = everything */
@@ -758,7 +860,8 @@ typedef struct {
   uint64_t off_stream, off_subch, off_fib, off_crc, off_frame, off_msc, off_sf;
   uint64_t off_dg;          /* the data-group section: dabx_chunk_dg[n_streams * max_subch]; 0 = the slab has none */
   uint64_t off_pad;         /* the PAD section: dabx_chunk_pad[n_streams * max_subch]; 0 = the slab has none */
-  uint64_t reserved[2];
+  uint64_t off_mot;         /* the MOT section: dabx_chunk_mot[n_streams * max_subch]; 0 = the slab has none */
+  uint64_t reserved[1];
 } dabx_chunk_header;        /* 128 bytes */
 typedef struct {
   int64_t first_frame;      /* index, since the stream was opened, of the first frame in the chunk */
@@ -822,6 +925,21 @@ typedef struct {
   int64_t  n_bytes;
   int64_t  superframes, aus, pad_aus, pad_bad, labels, label_bytes, groups, group_bytes, dg_crc_bad, dl_overflow, li_bad;
 } dabx_chunk_pad;           /* 128 bytes */
+/* The MOT section (DABX_DELIVER_MOT): one dabx_chunk_mot per (stream, slot) from off_mot, all zero for a slot without MOT decoding; behind
+ * the table, per MOT slot, room for 16 dabx_mot_object from rec_off and 2 * max_object_bytes bytes from bytes_off, fixed by the
+ * configuration.  The section lies in the slab's head part, behind the PAD section and in front of off_msc, and is gathered behind
+ * k_deliver_pad (k_deliver_mot).  The chunk carries the n_objects objects first_object .. first_object + n_objects - 1 of the slot's
+ * sequence, emitted since the previous chunk: object i is bytes_off + byte_pos .. + body_len + name_len (byte_pos counts from bytes_off).
+ * objects_lost: objects emitted since the previous chunk that are not in this one -- more than 16, more bytes than the room, or gone from
+ * the slot's rings; those still in the rings stay readable through dabx_read_mot_objects.  The counters are cumulative, as
+ * dabx_mot_stats. */
+typedef struct {
+  int64_t  first_object;
+  int32_t  n_objects, objects_lost;
+  uint64_t rec_off, bytes_off;
+  int64_t  n_bytes;
+  int64_t  objects, object_bytes, groups, headers, segments, crc_bad, grp_short, hdr_bad, obj_overflow, resets, progress_events;
+} dabx_chunk_mot;           /* 128 bytes */
 typedef struct {
   uint64_t seq;
   const void *data;         /* the host slab: valid until dabx_delivery_release(seq) */
