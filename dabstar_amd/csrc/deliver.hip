@@ -9,6 +9,7 @@
 #include "packet_core.h"
 #include "pad_core.h"
 #include "mot_core.h"
+#include "carousel_core.h"
 
 namespace dabx {
 
@@ -231,6 +232,32 @@ int launch_deliver_mot(const EngineDev &e, const DeliverDev &dv, const MotDev &m
   if (!dv.hdr.off_mot || md.n <= 0) return 0;
   DABX_HIP(hipMemsetAsync(dv.slab + dv.hdr.off_mot, 0, sizeof(dabx_chunk_mot) * (size_t)e.n_streams * e.max_subch, st));
   hipLaunchKernelGGL(k_deliver_mot, dim3(md.n), dim3(64), 0, st, md, dv.slab, (unsigned long long)dv.hdr.off_mot);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+
+// ... and the rows of the carousel slots (a slot is a PAD slot or a packet slot, never both), by a second launch over their job table.
+// clear_table: no k_deliver_mot ran for this chunk, the table is zeroed here.
+__global__ __launch_bounds__(64) void k_deliver_carousel(CarouselDev cd, uint8_t *slab, unsigned long long off_mot)
+{
+  CarouselSlot &cs = cd.slots[blockIdx.x];
+  if (!cs.out.dl_rec_off) return;
+  const OutGather g = out_ring_gather(cs.out, slab, threadIdx.x);
+  if (threadIdx.x == 0) {
+    dabx_chunk_mot t;
+    t.first_object = g.first; t.n_objects = g.n; t.objects_lost = (int)(g.first - g.done); t.rec_off = cs.out.dl_rec_off; t.bytes_off = cs.out.dl_bytes_off; t.n_bytes = g.n_bytes;
+    t.objects = cs.out.count; t.object_bytes = cs.out.n_bytes; t.groups = cs.x.groups; t.headers = cs.c.headers; t.segments = cs.c.segments;
+    t.crc_bad = cs.c.crc_bad; t.grp_short = cs.c.grp_short; t.hdr_bad = cs.c.hdr_bad; t.obj_overflow = cs.c.obj_overflow; t.resets = cs.c.resets;
+    t.progress_events = 0;
+    reinterpret_cast<dabx_chunk_mot *>(slab + off_mot)[(size_t)cs.s * cd.max_subch + cs.j] = t;
+    cs.out.dl_done = cs.out.count;
+  }
+}
+int launch_deliver_carousel(const EngineDev &e, const DeliverDev &dv, const CarouselDev &cd, hipStream_t st, bool clear_table)
+{
+  if (!dv.hdr.off_mot || cd.n <= 0) return 0;
+  if (clear_table) DABX_HIP(hipMemsetAsync(dv.slab + dv.hdr.off_mot, 0, sizeof(dabx_chunk_mot) * (size_t)e.n_streams * e.max_subch, st));
+  hipLaunchKernelGGL(k_deliver_carousel, dim3(cd.n), dim3(64), 0, st, cd, dv.slab, (unsigned long long)dv.hdr.off_mot);
   DABX_HIP(hipGetLastError());
   return 0;
 }

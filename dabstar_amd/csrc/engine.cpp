@@ -376,6 +376,7 @@ void dabx_destroy(dabx_engine *e)
   e->pkt.destroy();
   e->pad.destroy();
   e->mot.destroy();
+  e->car.destroy();
   for (void *p : e->allocs) (void)hipFree(p);
   if (e->locked_host) (void)hipHostFree(e->locked_host);
   if (e->seq_timeouts_host) (void)hipHostFree(e->seq_timeouts_host);
@@ -408,6 +409,7 @@ static int set_subchannels_impl(dabx_engine *e, int stream, const dabx_subch_des
   if ((rc = e->pkt.download(d.max_subch))) return rc;
   if ((rc = e->pad.download(d.max_subch))) return rc;
   if ((rc = e->mot.download(d.max_subch))) return rc;
+  if ((rc = e->car.download(d.max_subch))) return rc;
   int max_kbps = e->max_kbps;
   std::vector<SubchDev> row(std::max(1, d.max_subch));
   for (int j = 0; j < n; j++) {
@@ -500,6 +502,10 @@ static int set_subchannels_impl(dabx_engine *e, int stream, const dabx_subch_des
   if (!e->pkt.host.empty()) {           // a new or changed slot loses its packet mode; one that keeps running (a move included) keeps it and its state
     for (size_t sj : restarted) e->pkt.drop(sj);
     if ((rc = e->pkt.upload())) return rc;
+  }
+  if (!e->car.host.empty()) {           // ... and the carousel decoding behind it
+    for (size_t sj : restarted) e->car.drop(sj);
+    if ((rc = carousel_follow_packet(e))) return rc;
   }
   if (!e->pad.host.empty()) {           // ... and so does PAD decoding
     for (size_t sj : restarted) e->pad.drop(sj);
@@ -799,7 +805,8 @@ int dabx_process(dabx_engine *e, int max_frames, int sync)
       e->dev.snap = e->snap_buf[e->ss.batch_parity];
       hipStream_t tail = e->stream;
       rc = launch_msc_batch(e->dev, 4 * e->pending_frames, e->have_fast ? &e->fast : nullptr, e->ss, e->mk, e->dl.open ? &dv : nullptr, &tail,
-                            e->pkt.dev.n > 0 ? &e->pkt.dev : nullptr, e->pad.dev.n > 0 ? &e->pad.dev : nullptr, e->mot.dev.n > 0 ? &e->mot.dev : nullptr);
+                            e->pkt.dev.n > 0 ? &e->pkt.dev : nullptr, e->pad.dev.n > 0 ? &e->pad.dev : nullptr, e->mot.dev.n > 0 ? &e->mot.dev : nullptr,
+                            e->car.dev.n > 0 ? &e->car.dev : nullptr);
       if (rc) {
         if (e->dl.open) e->delivery_abort(dl_slot, dl_dev);          // the slabs of the chunk that was begun: never left IN_FLIGHT without a copy job
         e->pending_frames = 0;

@@ -4,6 +4,7 @@
 #include "packet_core.h"
 #include "pad_core.h"
 #include "mot_core.h"
+#include "carousel_core.h"
 #include "sdma.h"
 #include "iqfile.h"
 #include <algorithm>
@@ -52,7 +53,7 @@ struct Delivery {
   long long *frames_done = nullptr, *cif_done = nullptr, *sf_done = nullptr;
   dabx_chunk_header hdr{};
   bool want_pad = false;                         // DABX_DELIVER_PAD, or what == 0: a PAD section while there are PAD slots
-  bool want_mot = false;                         // DABX_DELIVER_MOT, or what == 0: a MOT section while there are MOT slots
+  bool want_mot = false;                         // DABX_DELIVER_MOT, or what == 0: a MOT section while there are MOT or carousel slots
   bool want_dg = false;                          // DABX_DELIVER_DG, or what == 0: a data-group section while there are packet-mode slots
 };
 
@@ -85,7 +86,7 @@ struct Ingest {
   int16_t *tab_int = nullptr; float *tab_frac = nullptr;
 };
 
-// The job table of a stage that runs on some slots only (k_packet: PacketSlot / PacketDev, k_pad: PadSlot / PadDev, k_mot: MotSlot / MotDev).  Nothing of it exists
+// The job table of a stage that runs on some slots only (k_packet: PacketSlot / PacketDev, k_pad: PadSlot / PadDev, k_mot: MotSlot / MotDev, k_carousel: CarouselSlot / CarouselDev).  Nothing of it exists
 // until the stage's dabx_set_*_mode first switches a slot on: host stays empty, dev.n stays 0 and no batch launches the kernel.
 // host[sj].st mirrors the device's table entry of the slot; the device owns it between download and upload (both with the engine drained).
 template <class Slot, class Dev> struct JobTable {
@@ -189,6 +190,7 @@ struct dabx_engine : dabx::EngineHead {          // (iqfile.h: the ring format, 
   JobTable<PacketSlot, PacketDev> pkt;         // packet-mode slots (include/dabx.h "Packet-mode data sub-channels", k_packet)
   JobTable<PadSlot, PadDev> pad;               // PAD slots (include/dabx.h "Programme-associated data", k_pad)
   JobTable<MotSlot, MotDev> mot;               // MOT slots (include/dabx.h "MOT objects of the X-PAD", k_mot): PAD slots all of them
+  JobTable<CarouselSlot, CarouselDev> car;     // carousel slots (include/dabx.h "MOT objects of a packet-mode carousel", k_carousel): packet-mode slots all of them
   int build_msc_classes();
   int delivery_layout();                       // offsets of every slot's bytes in a slab for the sub-channels configured now
   int delivery_begin(DeliverDev *dv, int *slot, int *devslab);     // a chunk closes: host + device slab, front gather on stream a
@@ -229,4 +231,5 @@ void ingest_free(dabx_engine *e);
 // engine_slots.cpp
 void pad_count_sources(dabx_engine *e);
 int mot_follow_pad(dabx_engine *e);
+int carousel_follow_packet(dabx_engine *e);
 }  // namespace dabx

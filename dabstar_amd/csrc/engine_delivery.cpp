@@ -26,7 +26,7 @@ template <class Tab> static size_t layout_section(Tab &tab, bool want, size_t of
   for (auto &q : tab.host) { q.st.out.dl_rec_off = q.st.out.dl_bytes_off = 0; any = any || q.on; }
   if (!want || !any) return off;
   off = align_up(off, 16);
-  *off_table = off; off += table_bytes;
+  if (!*off_table) { *off_table = off; off += table_bytes; }      // (the carousel slots share the MOT section's table)
   for (auto &q : tab.host) {
     if (!q.on) continue;
     auto &r = q.st.out;
@@ -83,6 +83,7 @@ int dabx_engine::delivery_layout()
   off = layout_section(pad, D.want_pad && !d.fic_only, off, S * M * sizeof(dabx_chunk_pad), &h.off_pad);
   if (h.off_pad) h.what |= DABX_DELIVER_PAD;
   off = layout_section(mot, D.want_mot && !d.fic_only, off, S * M * sizeof(dabx_chunk_mot), &h.off_mot);     // ... and behind that the MOT section (dabx_chunk_mot)
+  off = layout_section(car, D.want_mot && !d.fic_only, off, S * M * sizeof(dabx_chunk_mot), &h.off_mot);     // ... with the rooms of the carousel slots
   if (h.off_mot) h.what |= DABX_DELIVER_MOT;
   off = align_up(off, 256);
   h.off_msc = off;
@@ -104,6 +105,7 @@ int dabx_engine::delivery_layout()
   if (!pkt.host.empty()) if (int rc = pkt.upload()) return rc;
   if (!pad.host.empty()) if (int rc = pad.upload()) return rc;
   if (!mot.host.empty()) if (int rc = mot.upload()) return rc;
+  if (!car.host.empty()) if (int rc = car.upload()) return rc;
   if (S * M) {
     DABX_HIP(hipMemcpy(D.layout_off, lo.data(), sizeof(unsigned long long) * 3 * S * M, hipMemcpyHostToDevice));
     std::vector<int32_t> ids(subch_id_host.begin(), subch_id_host.begin() + S * M);
@@ -334,9 +336,10 @@ int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
   size_t cap = sizeof(dabx_chunk_header) + S * sizeof(dabx_chunk_stream) + S * M * sizeof(dabx_chunk_subch) + S * F * (384 + 12 + sizeof(dabx_chunk_frame)) + 6 * 16 + 256;
   if (M && !d.fic_only) cap += S * ((size_t)4 * F * per_cif + (size_t)DL_SF_CAP * 5 * per_cif + 2 * 16 * M + M * DL_SF_CAP * sizeof(dabx_superframe_info));
   // ... and the data-group, the PAD and the MOT section
-  if ((rc = e->pkt.download(d.max_subch)) || (rc = e->pad.download(d.max_subch)) || (rc = e->mot.download(d.max_subch))) return rc;
+  if ((rc = e->pkt.download(d.max_subch)) || (rc = e->pad.download(d.max_subch)) || (rc = e->mot.download(d.max_subch)) ||
+      (rc = e->car.download(d.max_subch))) return rc;
   cap += section_capacity(e->pkt, S * M * sizeof(dabx_chunk_dg)) + section_capacity(e->pad, S * M * sizeof(dabx_chunk_pad)) +
-         section_capacity(e->mot, S * M * sizeof(dabx_chunk_mot));
+         section_capacity(e->mot, S * M * sizeof(dabx_chunk_mot)) + section_capacity(e->car, S * M * sizeof(dabx_chunk_mot));
   D.capacity = align_up(cap, 4096);
 #define H(x) do { hipError_t err__ = (x); if (err__ != hipSuccess) { set_error("HIP error %d (%s) at %s:%d", (int)err__, hipGetErrorString(err__), __FILE__, __LINE__); delivery_free(e); return DABX_E_HIP; } } while (0)
   if (D.copy_engine == 1) H(hipStreamCreateWithFlags(&D.cs, hipStreamNonBlocking));

@@ -1,4 +1,4 @@
-// engine_slots.cpp -- the slots with output rings, packet mode, PAD and the MOT objects of the X-PAD: what their entry points share and
+// engine_slots.cpp -- the slots with output rings, packet mode, PAD and the MOT objects of the X-PAD and of a carousel: what their entry points share and
 // dabx_set_*_mode, dabx_read_*, dabx_get_*_stats.
 #include "engine.h"
 #include <algorithm>
@@ -28,6 +28,19 @@ int mot_follow_pad(dabx_engine *e)
     if (!tab.host[sj].on) continue;
     if (!e->pad.on(sj)) tab.drop(sj);
     else tab.host[sj].st.pad_index = e->pad.index[sj];
+  }
+  return tab.upload();
+}
+
+// ... and the carousel job table the packet job table, in the same way (behind every e->pkt.upload())
+int carousel_follow_packet(dabx_engine *e)
+{
+  auto &tab = e->car;
+  if (tab.host.empty()) return 0;
+  for (size_t sj = 0; sj < tab.host.size(); sj++) {
+    if (!tab.host[sj].on) continue;
+    if (!e->pkt.on(sj)) tab.drop(sj);
+    else tab.host[sj].st.pkt_index = e->pkt.index[sj];
   }
   return tab.upload();
 }
@@ -127,6 +140,7 @@ template <class Slot, class Dev, class Rec> static int ring_read(dabx_engine *e,
 static_assert(sizeof(dabx_chunk_dg) == 128 && sizeof(dabx_datagroup_info) == 32 && sizeof(dabx_packet_stats) == 128 && sizeof(dabx_packet_config) == 32, "include/dabx.h: packet-mode records");
 static_assert(sizeof(dabx_chunk_pad) == 128 && sizeof(dabx_pad_item) == 32 && sizeof(dabx_pad_stats) == 128 && sizeof(dabx_pad_config) == 32, "include/dabx.h: PAD records");
 static_assert(sizeof(dabx_chunk_mot) == 128 && sizeof(dabx_mot_object) == 32 && sizeof(dabx_mot_stats) == 128 && sizeof(dabx_mot_config) == 32, "include/dabx.h: MOT records");
+static_assert(sizeof(dabx_carousel_stats) == 128 && sizeof(dabx_carousel_config) == 32, "include/dabx.h: carousel records");
 static_assert(sizeof(dabx_mp2_sync_stats) == 64 && offsetof(dabx_pad_config, source) == 4, "include/dabx.h: PAD of MP2 frames");
 
 extern "C" {
@@ -154,8 +168,9 @@ int dabx_set_packet_mode(dabx_engine *e, int stream, int j, const dabx_packet_co
     tab.host.resize((size_t)e->dev.n_streams * e->dev.max_subch);
     tab.index.assign(tab.host.size(), -1);
   }
-  if ((rc = tab.download(e->dev.max_subch))) return rc;
+  if ((rc = tab.download(e->dev.max_subch)) || (rc = e->car.download(e->dev.max_subch))) return rc;
   tab.drop(sj);
+  e->car.drop(sj);                                                     // the packet stage restarts with empty rings: nothing for k_carousel to follow
   if (cfg) {
     // two full batches (56 logical frames) of single-packet groups: a record per 24-byte packet, their payloads, and room for the series
     // under assembly, which lives in the byte ring in front of the completed groups (packet_core.h); a chunk: one batch of them
@@ -167,12 +182,14 @@ int dabx_set_packet_mode(dabx_engine *e, int stream, int j, const dabx_packet_co
                          (uint32_t)(bytes + DABX_DG_MAX_BYTES))) {
       set_error("dabx_set_packet_mode: out of device memory");
       (void)tab.upload();
+      (void)carousel_follow_packet(e);
       return DABX_E_NOMEM;
     }
     tab.host[sj] = h;
   }
   if ((rc = tab.upload())) return rc;
-  return relayout_open_delivery(e, sj, sc, e->pad, e->mot);
+  if ((rc = carousel_follow_packet(e))) return rc;
+  return relayout_open_delivery(e, sj, sc, e->pad, e->mot, e->car);
 }
 
 int dabx_read_datagroups(dabx_engine *e, int stream, int j, int n, dabx_datagroup_info *info, uint8_t *bytes, size_t max_bytes)
@@ -246,7 +263,7 @@ int dabx_set_pad_mode(dabx_engine *e, int stream, int j, const dabx_pad_config *
   if ((rc = tab.upload())) return rc;
   pad_count_sources(e);
   if ((rc = mot_follow_pad(e))) return rc;
-  return relayout_open_delivery(e, sj, sc, e->pkt, e->mot);
+  return relayout_open_delivery(e, sj, sc, e->pkt, e->mot, e->car);
 }
 
 int dabx_get_mp2_sync_stats(dabx_engine *e, int stream, int j, dabx_mp2_sync_stats *out)
@@ -340,13 +357,15 @@ int dabx_set_mot_mode(dabx_engine *e, int stream, int j, const dabx_mot_config *
     }
   }
   if ((rc = tab.upload())) return rc;
-  return relayout_open_delivery(e, sj, sc, e->pkt, e->pad);
+  return relayout_open_delivery(e, sj, sc, e->pkt, e->pad, e->car);
 }
 
 int dabx_read_mot_objects(dabx_engine *e, int stream, int j, int n, dabx_mot_object *info, uint8_t *bytes, size_t max_bytes)
 {
   if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch || n <= 0 || !info) { set_error("dabx_read_mot_objects: bad argument"); return DABX_E_ARG; }
-  return ring_read(e, e->mot, (size_t)stream * e->dev.max_subch + j, n, info, bytes, max_bytes);
+  const size_t sj = (size_t)stream * e->dev.max_subch + j;
+  if (e->car.on(sj)) return ring_read(e, e->car, sj, n, info, bytes, max_bytes);      // (a slot is a PAD slot or a packet slot, never both)
+  return ring_read(e, e->mot, sj, n, info, bytes, max_bytes);
 }
 
 int dabx_get_mot_stats(dabx_engine *e, int stream, int j, dabx_mot_stats *out)
@@ -366,6 +385,98 @@ int dabx_get_mot_stats(dabx_engine *e, int stream, int j, dabx_mot_stats *out)
   out->hdr_bad = i32(c.hdr_bad); out->seg_number_bad = i32(c.seg_number_bad); out->seg_duplicate = i32(c.seg_duplicate); out->resets = i32(c.resets);
   out->obj_overflow = i32(c.obj_overflow); out->pad_overrun = i32(c.pad_overrun); out->progress_events = i32(c.progress_events);
   out->progress_pct = st.h.progress_pct; out->transport_id = st.h.transport_id; out->segments_stored = st.h.n_stored; out->active = 1;
+  return 0;
+}
+
+// ---- MOT objects of a packet-mode carousel (carousel_core.h, k_carousel) -----------------------------------------------------------------
+int dabx_set_carousel_mode(dabx_engine *e, int stream, int j, const dabx_carousel_config *cfg)
+{
+  if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch) { set_error("dabx_set_carousel_mode: bad argument"); return DABX_E_ARG; }
+  if (cfg && cfg->size < sizeof(uint32_t)) { set_error("dabx_set_carousel_mode: bad configuration (size %u)", cfg->size); return DABX_E_ARG; }
+  auto field = [&](size_t at, uint32_t v, uint32_t dflt) { return cfg && cfg->size >= at + sizeof(uint32_t) && v ? v : dflt; };
+  const uint32_t max_bytes = field(4, cfg ? cfg->max_object_bytes : 0, MOT_OBJECT_BYTES_DEFAULT);
+  const uint32_t max_objects = field(8, cfg ? cfg->max_dir_objects : 0, CAR_DIR_OBJECTS_DEFAULT);
+  const uint32_t max_dir = field(12, cfg ? cfg->max_dir_bytes : 0, CAR_DIR_BYTES_DEFAULT);
+  if (max_bytes < MOT_OBJECT_BYTES_MIN || max_bytes > MOT_OBJECT_BYTES_MAX || max_objects > CAR_DIR_OBJECTS_MAX || max_dir < CAR_DIR_BYTES_MIN || max_dir > CAR_DIR_BYTES_MAX) {
+    set_error("dabx_set_carousel_mode: max_object_bytes %u is not within %u .. %u, max_dir_objects %u is above %u or max_dir_bytes %u is not within %u .. %u",
+              max_bytes, MOT_OBJECT_BYTES_MIN, MOT_OBJECT_BYTES_MAX, max_objects, CAR_DIR_OBJECTS_MAX, max_dir, CAR_DIR_BYTES_MIN, CAR_DIR_BYTES_MAX);
+    return DABX_E_ARG;
+  }
+  int rc;
+  if ((rc = sync_all(e))) return rc;
+  const size_t sj = (size_t)stream * e->dev.max_subch + j;
+  if (cfg && !e->pkt.on(sj)) { set_error("dabx_set_carousel_mode: stream %d slot %d is not in packet mode (dabx_set_packet_mode)", stream, j); return DABX_E_ARG; }
+  SubchDev sc;
+  DABX_HIP(hipMemcpy(&sc, e->dev.subch + sj, sizeof(SubchDev), hipMemcpyDeviceToHost));
+  auto &tab = e->car;
+  if (tab.host.empty()) {
+    if (!cfg) return 0;
+    tab.host.resize((size_t)e->dev.n_streams * e->dev.max_subch);
+    tab.index.assign(tab.host.size(), -1);
+  }
+  if ((rc = tab.download(e->dev.max_subch))) return rc;
+  tab.drop(sj);
+  if (cfg) {
+    decltype(e->car)::Host h;
+    h.on = true;
+    CarouselSlot &st = h.st;
+    st.s = stream; st.j = j; st.pkt_index = e->pkt.index[sj];
+    st.max_object_bytes = max_bytes; st.max_dir_objects = max_objects; st.max_dir_bytes = max_dir;
+    PacketSlot ps;                                                     // the walk starts with the next data group completed
+    DABX_HIP(hipMemcpy(&ps, e->pkt.dev.slots + e->pkt.index[sj], sizeof(PacketSlot), hipMemcpyDeviceToHost));
+    st.groups_seen = ps.out.count;
+    for (CarEntry &q : st.cache) q = CarEntry{-1, 0};                  // mot_handler.cpp:42-46
+    const uint32_t ring = mot_byte_ring(max_bytes);                    // (mot_core.h has the derivations)
+    const size_t extra = car_extra_bytes(max_bytes, max_objects, max_dir), n_obj = CAR_CACHE + max_objects;
+    if (!out_ring_create(&st.out, ring, MOT_REC_RING, 0, MOT_DL_REC_CAP, 2 * max_bytes, extra)) {
+      set_error("dabx_set_carousel_mode: out of device memory");
+      (void)tab.upload();
+      return DABX_E_NOMEM;
+    }
+    st.stores = st.out.bytes + ring;
+    st.store_bytes = mot_extra_bytes(max_bytes);
+    st.dir = st.stores + n_obj * st.store_bytes;
+    st.marked = reinterpret_cast<uint32_t *>(st.dir + car_align8(max_dir));
+    st.comp = st.marked + CAR_DIR_SEGMENTS / 32;
+    st.obj = reinterpret_cast<MotState *>(reinterpret_cast<uint8_t *>(st.comp) + car_align8(4 * (size_t)max_objects));
+    tab.host[sj] = h;
+    MotState fresh{};
+    fresh.transport_id = -1; fresh.num_segments = -1; fresh.max_seg = -1;          // mot_object.h:82-83
+    const std::vector<MotState> objs(n_obj, fresh);
+    // every segment number of every store absent (MOT_ABSENT); no directory, no mark, no component in use
+    if (hipMemset(st.stores, 0xFF, n_obj * st.store_bytes) != hipSuccess ||
+        hipMemset(st.dir, 0, (size_t)(reinterpret_cast<uint8_t *>(st.obj) - st.dir)) != hipSuccess ||
+        hipMemcpy(st.obj, objs.data(), sizeof(MotState) * n_obj, hipMemcpyHostToDevice) != hipSuccess) {
+      tab.drop(sj);
+      (void)tab.upload();
+      set_error("dabx_set_carousel_mode: clearing the object stores failed");
+      return DABX_E_HIP;
+    }
+  }
+  if ((rc = tab.upload())) return rc;
+  return relayout_open_delivery(e, sj, sc, e->pkt, e->pad, e->mot);
+}
+
+int dabx_get_carousel_stats(dabx_engine *e, int stream, int j, dabx_carousel_stats *out)
+{
+  if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch || !out) { set_error("dabx_get_carousel_stats: bad argument"); return DABX_E_ARG; }
+  memset(out, 0, sizeof(*out));
+  const size_t sj = (size_t)stream * e->dev.max_subch + j;
+  if (!e->car.on(sj)) return sync_all(e);
+  CarouselSlot st;
+  long long lo = 0;
+  if (int rc = ring_window(e, e->car, sj, &st, &lo)) return rc;
+  const MotCounters &c = st.c;
+  const CarCounters &x = st.x;
+  auto i32 = [](long long v) { return (int32_t)std::min<long long>(v, INT32_MAX); };
+  out->objects = st.out.count; out->object_bytes = st.out.n_bytes; out->objects_lost = e->car.host[sj].lost;
+  out->groups = i32(x.groups); out->headers = i32(c.headers); out->segments = i32(c.segments);
+  out->crc_bad = i32(c.crc_bad); out->type_other = i32(c.type_other); out->no_tid = i32(c.no_tid); out->grp_short = i32(c.grp_short);
+  out->hdr_bad = i32(c.hdr_bad); out->seg_number_bad = i32(c.seg_number_bad); out->seg_duplicate = i32(c.seg_duplicate); out->resets = i32(c.resets);
+  out->obj_overflow = i32(c.obj_overflow); out->hdr_known = i32(x.hdr_known); out->hdr_not_first = i32(x.hdr_not_first); out->from_body = i32(x.from_body);
+  out->evictions = i32(x.evictions); out->dirs_begun = i32(x.dirs_begun); out->dirs_repeated = i32(x.dirs_repeated); out->dirs_refused = i32(x.dirs_refused);
+  out->dir_segments = i32(x.dir_segments); out->dir_objects = i32(x.dir_objects); out->dir_short = i32(x.dir_short); out->dir_seg_bad = i32(x.dir_seg_bad);
+  out->dir_cut = i32(x.dir_cut); out->dg_overrun = i32(x.dg_overrun); out->active = 1;
   return 0;
 }
 

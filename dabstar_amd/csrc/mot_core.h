@@ -225,7 +225,9 @@ __device__ __forceinline__ void mot_set_header(MotWave &w, long long pos, int se
   if (mot_complete(w)) mot_emit(w);                              // :111-114
 }
 
-// add_body_segment (:117-175) on the segsize bytes at `seg` of the group
+// add_body_segment (:117-175) on the segsize bytes at `seg` of the group.  PAD_ELEMENT: mIsPadElement (:160); false for the objects of a
+// packet-mode carousel (carousel_core.h), which signal no progress
+template <bool PAD_ELEMENT = true>
 __device__ __forceinline__ void mot_add_body(MotWave &w, long long pos, int seg, int number, int segsize, bool last, int tid)
 {
   if (number < 0 || number >= MOT_MAX_SEGMENTS) { w.c.seg_number_bad++; return; }      // :119-123
@@ -243,7 +245,7 @@ __device__ __forceinline__ void mot_add_body(MotWave &w, long long pos, int seg,
   if (number > w.h.max_seg) w.h.max_seg = number;
   w.c.segments++;
   if (last) w.h.num_segments = number + 1;                       // :145-148
-  if (w.h.body_size > 0 && w.h.content_type == 2) {              // :160 a PAD element, base type image ((contentType << 8 & 0x3f00) >> 8 == MOTBaseTypeImage)
+  if (PAD_ELEMENT && w.h.body_size > 0 && w.h.content_type == 2) { // :160 a PAD element, base type image ((contentType << 8 & 0x3f00) >> 8 == MOTBaseTypeImage)
     int pct = (int)(100ll * w.h.sum / w.h.body_size);            // :162 (the reference's i32 product cannot overflow below 21 MiB; M3 bounds the sum at 4 MiB)
     if (pct > 100) pct = 100;                                    // :163-167
     w.h.progress_pct = pct;                                      // :168

@@ -6,12 +6,15 @@
 //   k_pad          PAD of the DAB+ access units: dynamic labels and X-PAD MSC data groups (mp4processor.cpp:345-353, pad_handler.cpp:67-547)
 //   k_pad_mp2      PAD of DAB (MP2) audio frames: MP2 frame sync over the logical frames and the same PadHandler (mp2processor.cpp:611-747)
 //   k_mot          MOT objects out of the X-PAD data groups the two PAD kernels have just emitted (pad_handler.cpp:553-622, mot_object.cpp:71-323)
+//   k_carousel     MOT objects out of the MSC data groups k_packet has just completed: MotHandler and MotDirectory (mot_handler.cpp:69-259,
+//                  mot_dir.cpp:28-156); launched right behind k_packet
 //
 // Which logical frames of a slot are new in a batch is msc_new_frames (pipeline.h), for every stage and for the delivery (deliver.hip).
 #include "pipeline.h"
 #include "packet_core.h"
 #include "pad_core.h"
 #include "mot_core.h"
+#include "carousel_core.h"
 #include "fec_core.h"
 #include "wave_ops.h"
 
@@ -533,6 +536,53 @@ __global__ __launch_bounds__(64) void k_mot(MotDev md)
   if (lane == 0) { ms.h = w.h; ms.c = w.c; ms.out.count = w.n_recs; ms.out.n_bytes = w.n_bytes; ms.items_seen = count; }
 }
 
+// ---------------------------------------------------------------------------------------------- carousel
+// One wave per carousel-enabled packet-mode slot (CarouselDev::slots: those slots only), behind k_packet: walks the data groups k_packet has
+// completed since this slot's last visit (PacketSlot::out.count against CarouselSlot::groups_seen) out of the packet slot's rings and takes
+// them through MotHandler::add_MSC_data_group, its cache, MotDirectory and the MotObject of the store each group belongs to
+// (carousel_core.h: mot_handler.cpp:69-259 and mot_dir.cpp:28-156 line by line; mot_core.h for the object).  The packet rings hold what two
+// batches emit, so every group of this batch is intact; the rule is checked all the same (out_ring_oldest, out_ring_intact) and a violation
+// is counted in dg_overrun instead of read.  Header fields are wave-uniform and the state machine is scalar; the wave as a whole looks an
+// id up in the cache (one compare and a ballot) and in the directory (64 components per pass), copies segments and directory segments,
+// checks the 512 marks and the segment table with ballots and gathers an emit into the byte ring.
+// include/dabx.h "MOT objects of a packet-mode carousel" states the semantics and the guards C1..C3, D1..D4.
+__global__ __launch_bounds__(64) void k_carousel(CarouselDev cd)
+{
+  const int lane = threadIdx.x;
+  CarouselSlot &cs = cd.slots[blockIdx.x];
+  if (cs.pkt_index < 0 || cs.pkt_index >= cd.n_pkt) return;
+  const PacketSlot &ps = cd.pkt_slots[cs.pkt_index];
+  const long long count = ps.out.count;
+  long long seen = cs.groups_seen;
+  if (count <= seen) return;
+  __shared__ __attribute__((aligned(16))) uint8_t s_hdr[MOT_NAME_ROOM];
+  CarWave cw;
+  MotWave &w = cw.w;
+  cw.cs = &cs; cw.d = cs.d; cw.x = cs.x; cw.open = 0;
+  cw.pkt_ring = ps.out.bytes; cw.pkt_mask = ps.out.bytes_mask;
+  w.h = MotState{}; w.c = cs.c;
+  w.pad_ring = cw.pkt_ring; w.pad_mask = cw.pkt_mask;
+  w.arena = cs.stores; w.name = cs.stores; w.table = nullptr;    // (car_open sets them)
+  w.ring = cs.out.bytes; w.recs = cs.out.recs; w.bytes_mask = cs.out.bytes_mask; w.rec_mask = cs.out.rec_mask;
+  w.n_recs = cs.out.count; w.n_bytes = cs.out.n_bytes;
+  w.max_object_bytes = cs.max_object_bytes;
+  w.lane = lane; w.hdr = s_hdr; w.frame = 0; w.au = 0;
+  const dabx_datagroup_info *recs = ps.out.recs;
+  const unsigned long long rec_mask = ps.out.rec_mask;
+  const long long oldest = out_ring_oldest(ps.out);
+  if (seen < oldest) { cw.x.dg_overrun += oldest - seen; seen = oldest; }      // (cannot happen: the stage runs behind every batch)
+  for (long long i = seen; i < count; i++) {
+    const unsigned long long *r = reinterpret_cast<const unsigned long long *>(recs + (size_t)((unsigned long long)i & rec_mask));
+    const long long pos = (long long)(((unsigned long long)pad_u((unsigned)(r[0] >> 32)) << 32) | pad_u((unsigned)r[0]));
+    if (!out_ring_intact(ps.out, pos)) { cw.x.dg_overrun++; continue; }
+    w.frame = (long long)(((unsigned long long)pad_u((unsigned)(r[2] >> 32)) << 32) | pad_u((unsigned)r[2]));      // last_frame
+    const unsigned lo = pad_u((unsigned)r[3]);                   // length, crc_flag, crc_ok
+    car_group(cw, pos, (int)(lo & 0xFFFFu), ((lo >> 16) & 0xFFu) != 0, ((lo >> 24) & 0xFFu) != 0);
+  }
+  __syncthreads();
+  if (lane == 0) { cs.d = cw.d; cs.c = w.c; cs.x = cw.x; cs.out.count = w.n_recs; cs.out.n_bytes = w.n_bytes; cs.groups_seen = count; }
+}
+
 // ---------------------------------------------------------------------------------------------- launchers
 // One per stage, on the stream launch_msc_batch gives them.  The packet and PAD launchers take the engine's job table (null or n = 0: the
 // engine has no such slot, no launch), fill in what the kernel reads of the engine and leave the argument they launched with in *used for
@@ -573,6 +623,21 @@ int launch_packet_stage(const EngineDev &e, const PacketDev *pk, hipStream_t st,
   mk.end(11, st);
   DABX_HIP(hipGetLastError());
   *used = p;
+  return 0;
+}
+
+// behind k_packet: k_carousel reads the packet rings as that launch left them (`pk`: the argument launch_packet_stage launched with)
+int launch_carousel_stage(const EngineDev &e, const CarouselDev *car, const PacketDev &pk, hipStream_t st, Marker &mk, CarouselDev *used)
+{
+  *used = CarouselDev{};
+  if (!car || car->n <= 0 || pk.n <= 0) return 0;
+  CarouselDev q = *car;
+  q.max_subch = e.max_subch; q.pkt_slots = pk.slots; q.n_pkt = pk.n;
+  mk.begin(14, st);
+  hipLaunchKernelGGL(k_carousel, dim3(q.n), dim3(64), 0, st, q);
+  mk.end(14, st);
+  DABX_HIP(hipGetLastError());
+  *used = q;
   return 0;
 }
 

@@ -231,7 +231,7 @@ struct EngineStreams {
 };
 
 // ---- profiling hook: HIP events around every kernel launch of a batch step ------------------------------------
-constexpr int N_STEP_KERNELS = 14;
+constexpr int N_STEP_KERNELS = 15;
 struct Marker {
   bool on = false;
   bool serial = false;            // the host waits for every instrumented kernel: one kernel on the chip at a time = stand-alone durations
@@ -348,11 +348,13 @@ __device__ __forceinline__ size_t tdi_off(long long cif, int i)
 struct PacketDev;                 // packet_core.h
 struct PadDev;                    // pad_core.h
 struct MotDev;                    // mot_core.h
+struct CarouselDev;               // carousel_core.h
 // pipeline.hip
 extern const char *const kStepKernelNames[N_STEP_KERNELS];
 int launch_front_step(const EngineDev &e, EngineStreams &ss, Marker &mk, bool async_acquire, bool all_locked);
 int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineStreams &ss, Marker &mk, const DeliverDev *dv = nullptr,
-                     hipStream_t *tail = nullptr, const PacketDev *pk = nullptr, const PadDev *pad = nullptr, const MotDev *mot = nullptr);
+                     hipStream_t *tail = nullptr, const PacketDev *pk = nullptr, const PadDev *pad = nullptr, const MotDev *mot = nullptr,
+                     const CarouselDev *car = nullptr);
 int launch_dciq(const EngineDev &e, int mode, hipStream_t st);
 int launch_level_exact(const EngineDev &e, hipStream_t st);
 int launch_commit(const EngineDev &e, int stream, unsigned long long n, hipStream_t st);
@@ -375,11 +377,13 @@ int launch_deliver_lf(const EngineDev &e, const DeliverDev &dv, hipStream_t st);
 int launch_deliver_dg(const EngineDev &e, const DeliverDev &dv, const PacketDev &pk, hipStream_t st);
 int launch_deliver_pad(const EngineDev &e, const DeliverDev &dv, const PadDev &pd, hipStream_t st);
 int launch_deliver_mot(const EngineDev &e, const DeliverDev &dv, const MotDev &md, hipStream_t st);
+int launch_deliver_carousel(const EngineDev &e, const DeliverDev &dv, const CarouselDev &cd, hipStream_t st, bool clear_table);
 // msc_stages.hip
 int launch_dabplus_stage(const EngineDev &e, hipStream_t st, Marker &mk);
 int launch_packet_stage(const EngineDev &e, const PacketDev *pk, hipStream_t st, Marker &mk, PacketDev *used);
 int launch_pad_stage(const EngineDev &e, const PadDev *pad, hipStream_t st, Marker &mk, PadDev *used);
 int launch_mot_stage(const EngineDev &e, const MotDev *mot, const PadDev &pad, hipStream_t st, Marker &mk, MotDev *used);
+int launch_carousel_stage(const EngineDev &e, const CarouselDev *car, const PacketDev &pk, hipStream_t st, Marker &mk, CarouselDev *used);
 // fib.cpp
 void dabx_internal_fibdec_skip(dabx_fibdec *d, long long n_fibs);     // FIBs the decoder never saw (they had left the ring)
 

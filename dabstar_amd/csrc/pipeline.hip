@@ -12,7 +12,7 @@
 //   k_frame_tail   fine CFO, null symbol, clock error, cursor bookkeeping (dab_processor.cpp:226-302)
 //   k_msc_frame    time de-interleave + depuncture + Viterbi + PRBS per (CIF, sub-channel) (backend.cpp:129-161)
 // The launchers and the test-entry kernels are at the end.  Elsewhere: the lane-per-trellis MSC decoder k_msc_prep / k_msc_vitT (vit_t.hip), the
-// slot stages behind the decoder k_packet / k_dabplus / k_pad / k_pad_mp2 / k_mot (msc_stages.hip), the delivery gathers (deliver.hip).  Every launcher
+// slot stages behind the decoder k_packet / k_carousel / k_dabplus / k_pad / k_pad_mp2 / k_mot (msc_stages.hip), the delivery gathers (deliver.hip).  Every launcher
 // of these files is declared at the end of pipeline.h.  The host side that calls them: engine.cpp (create, push, dabx_process, reads),
 // engine_delivery.cpp, engine_ingest.cpp, engine_slots.cpp (packet mode, PAD), engine_facade.cpp (dabx_fic_*, dabx_msc_*, test entries).
 #include <type_traits>
@@ -20,6 +20,7 @@
 #include "packet_core.h"
 #include "pad_core.h"
 #include "mot_core.h"
+#include "carousel_core.h"
 #include <algorithm>
 #include "ofdm_core.h"
 #include "viterbi_core.h"
@@ -1692,7 +1693,8 @@ __global__ void k_msc_snap(EngineDev e, int cifs)
 
 // "k_demap_fic": the first k_demap_frame launch of a frame (symbols 1..3) when the FIC is decoded on its own stream
 const char *const kStepKernelNames[N_STEP_KERNELS] = {"k_acquire", "k_frame_head", "k_symbols", "k_demap_frame", "k_fic_frame", "k_frame_tail",
-                                                      "k_msc_prep", "k_msc_vitT", "k_msc_frame", "k_dabplus", "k_demap_fic", "k_packet", "k_pad", "k_mot"};
+                                                      "k_msc_prep", "k_msc_vitT", "k_msc_frame", "k_dabplus", "k_demap_fic", "k_packet", "k_pad", "k_mot",
+                                                      "k_carousel"};
 
 // Front end of one batch step (everything with frame-to-frame feedback).
 // Overlapped schedule (ss.d set): the FIC lives in symbols 1..3 -- those are demapped first on the front-end stream a, then
@@ -1809,10 +1811,10 @@ int launch_front_step(const EngineDev &e_in, EngineStreams &ss, Marker &mk, bool
 // `e.snap` must point at the snapshot buffer of this batch.
 // `dv` (optional): the chunk's slot gather (deliver.hip) goes behind the DAB+ stage on the stream that ran it, before the batch's
 // completion event; *tail (optional) = the stream whose work completes the batch.
-// `pk`, `pad`, `mot` (optional): the engine's packet-mode / PAD / MOT slots, for the slot stages (msc_stages.hip) and the gathers of what
+// `pk`, `pad`, `mot`, `car` (optional): the engine's packet-mode / PAD / MOT / carousel slots, for the slot stages (msc_stages.hip) and the gathers of what
 // they emitted.
 int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineStreams &ss, Marker &mk, const DeliverDev *dv, hipStream_t *tail,
-                     const PacketDev *pk, const PadDev *pad, const MotDev *mot)
+                     const PacketDev *pk, const PadDev *pad, const MotDev *mot, const CarouselDev *car)
 {
   const DevTables *t;
   int rc = get_tables(&t);
@@ -1899,7 +1901,9 @@ int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineSt
   PacketDev p;                                           // the stages' arguments as launched, n = 0: no such slot
   PadDev q;
   MotDev m;
+  CarouselDev c;
   if ((rc = launch_packet_stage(e, pk, sb, mk, &p))) return rc;
+  if ((rc = launch_carousel_stage(e, car, p, sb, mk, &c))) return rc;
   if ((rc = launch_dabplus_stage(e, sb, mk))) return rc;
   if ((rc = launch_pad_stage(e, pad, sb, mk, &q))) return rc;
   if ((rc = launch_mot_stage(e, mot, q, sb, mk, &m))) return rc;
@@ -1907,6 +1911,7 @@ int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineSt
   if (dv && p.n > 0 && (rc = launch_deliver_dg(e, *dv, p, sb))) return rc;      // the slab's data-group section (head part, like the gather in front)
   if (dv && q.n > 0 && (rc = launch_deliver_pad(e, *dv, q, sb))) return rc;     // ... and its PAD section
   if (dv && m.n > 0 && (rc = launch_deliver_mot(e, *dv, m, sb))) return rc;     // ... and its MOT section
+  if (dv && c.n > 0 && (rc = launch_deliver_carousel(e, *dv, c, sb, m.n <= 0))) return rc;      // ... the carousel slots' rows of it
   if (tail) *tail = sb;
   if (ss.b) {
     DABX_HIP(hipEventRecord(ss.msc_done, ss.b));

@@ -73,6 +73,9 @@ def load(build_if_missing=True):
         L.dabx_set_mot_mode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.dabx_read_mot_objects.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
         L.dabx_get_mot_stats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    if hasattr(L, "dabx_set_carousel_mode"):         # MOT objects of a packet-mode carousel
+        L.dabx_set_carousel_mode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.dabx_get_carousel_stats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     if hasattr(L, "dabx_get_mp2_sync_stats"):        # ... and of DAB (MP2) audio slots
         L.dabx_get_mp2_sync_stats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     if hasattr(L, "dabx_announce_write"):            # (absent from libraries older than the level anchor: tools/ab.sh runs those through this binding too)
@@ -483,6 +486,26 @@ CHUNK_MOT = np.dtype([("first_object", "<i8"), ("n_objects", "<i4"), ("objects_l
 assert MOT_OBJECT.itemsize == 32 and MOT_STATS.itemsize == 128 and CHUNK_MOT.itemsize == 128
 
 
+# MOT objects of a packet-mode carousel (include/dabx.h): the records are MOT_OBJECT -- `frame` is the last_frame of the data group that
+# completed the object and `au` carries flags --, dabx_carousel_stats, and the slot's row of the slab's MOT section is a CHUNK_MOT
+MOT_FLAG_DIR_ELEMENT = 1
+CAROUSEL_DIR_OBJECTS_DEFAULT = 49
+CAROUSEL_DIR_BYTES_DEFAULT = 65536
+CAROUSEL_COUNTERS = ("objects", "object_bytes", "groups", "headers", "segments", "crc_bad", "type_other", "no_tid", "grp_short", "hdr_bad",
+                     "seg_number_bad", "seg_duplicate", "resets", "obj_overflow", "hdr_known", "hdr_not_first", "from_body", "evictions",
+                     "dirs_begun", "dirs_repeated", "dirs_refused", "dir_segments", "dir_objects", "dir_short", "dir_seg_bad", "dir_cut",
+                     "dg_overrun")
+CAROUSEL_STATS = np.dtype([(k, "<i8") for k in ("objects", "object_bytes", "objects_lost")] +
+                          [(k, "<i4") for k in CAROUSEL_COUNTERS[2:] + ("active",)])
+assert CAROUSEL_STATS.itemsize == 128
+
+
+class CarouselConfig(C.Structure):
+    """dabx_carousel_config."""
+    _fields_ = [("size", C.c_uint32), ("max_object_bytes", C.c_uint32), ("max_dir_objects", C.c_uint32), ("max_dir_bytes", C.c_uint32),
+                ("reserved", C.c_int32 * 4)]
+
+
 class MotConfig(C.Structure):
     """dabx_mot_config."""
     _fields_ = [("size", C.c_uint32), ("max_object_bytes", C.c_uint32), ("reserved", C.c_int32 * 6)]
@@ -873,6 +896,25 @@ class Engine:
         out = np.zeros(1, MOT_STATS)
         check(load().dabx_get_mot_stats(self._h, int(stream), int(j), _p(out)))
         return {k: int(out[0][k]) for k in MOT_STATS.names if k != "reserved"}
+
+    def set_carousel_mode(self, stream, j, on=True, max_object_bytes=0, max_dir_objects=0, max_dir_bytes=0):
+        """Switches the carousel decoding (MotHandler / MotDirectory) of packet-mode slot j of `stream` on (restarting it when it is on
+        already) or off (dabx_set_carousel_mode).  max_object_bytes: the bound of an object's stored segments, 0 = 65 536;
+        max_dir_objects: the most objects a directory may announce, 0 = 49; max_dir_bytes: the largest directory, 0 = 65 536.  The objects
+        are read with read_mot_objects."""
+        L = load()
+        if not on:
+            check(L.dabx_set_carousel_mode(self._h, int(stream), int(j), None))
+        else:
+            cfg = CarouselConfig(size=C.sizeof(CarouselConfig), max_object_bytes=int(max_object_bytes), max_dir_objects=int(max_dir_objects),
+                                 max_dir_bytes=int(max_dir_bytes))
+            check(L.dabx_set_carousel_mode(self._h, int(stream), int(j), C.byref(cfg)))
+
+    def carousel_stats(self, stream, j):
+        """dabx_carousel_stats of slot j as a dict (all zero unless carousel decoding is on for the slot)."""
+        out = np.zeros(1, CAROUSEL_STATS)
+        check(load().dabx_get_carousel_stats(self._h, int(stream), int(j), _p(out)))
+        return {k: int(out[0][k]) for k in CAROUSEL_STATS.names}
 
     def mp2_sync_stats(self, stream, j):
         """dabx_mp2_sync_stats of slot j as a dict (all zero unless the slot is a PAD slot with source "mp2")."""

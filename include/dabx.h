@@ -630,7 +630,8 @@ int  dabx_get_packet_stats(dabx_engine *e, int stream, int subch_idx, dabx_packe
  * (vLen >= 20 and the short form always has its four bytes); G3 and the check of :219 do bite at small rates, G4 is as above.
  * Parity of this path with the reference is unpinned: mp2processor.cpp cannot be compiled without the GUI's headers, so the tests compare
  * the device with a line-by-line restatement (tests/mp2_pad_cases.py), not with the reference's object code.
- * Out of scope: MotHandler (the handler's one MotObject is "MOT objects of the X-PAD" below), the charset conversion, DL Plus, F-PAD types
+ * Out of scope: MotHandler of the X-PAD (the handler's one MotObject is "MOT objects of the X-PAD" below; the packet-mode MotHandler is
+ * "MOT objects of a packet-mode carousel"), the charset conversion, DL Plus, F-PAD types
  * other than 0, MP2 audio decoding, handing out assembled MP2 frames. */
 #define DABX_DL_MAX_BYTES 256
 enum { DABX_PAD_LABEL = 1, DABX_PAD_DATAGROUP = 2 };
@@ -741,8 +742,7 @@ int  dabx_get_mp2_sync_stats(dabx_engine *e, int stream, int subch_idx, dabx_mp2
  * The name needs no guard: it lies inside a header segment, fewer than 8192 bytes.
  * Parity of this path with the reference's object code is unpinned: mot_object.cpp cannot be compiled without the GUI's headers
  * (dabradio.h), so the tests compare the device with a line-by-line restatement (tests/mot_cases.py).
- * Out of scope: MotHandler / MotDirectory (the packet-mode carousel with its object cache and directory mode; the reference prints "This
- * is not working well yet" for that constructor), image decoding, the charset of the object name, and the default name "trid_<n>",
+ * Out of scope: image decoding, the charset of the object name, and the default name "trid_<n>",
  * which the host forms from transport_id when name_len == 0 (:293-297). */
 typedef struct {
   uint32_t size;             /* sizeof(dabx_mot_config) of the caller */
@@ -757,7 +757,7 @@ typedef struct dabx_mot_object_s {
   uint16_t transport_id;
   uint16_t content_type;     /* get_content_type(): ((contentType << 8) & 0x3f00) | (contentSubType & 0xff), mot_object.h:71-75 */
   uint16_t name_len;         /* 0: the host forms "trid_<transport_id>" */
-  uint8_t  au;               /* dabx_pad_item.au of that item */
+  uint8_t  au;               /* dabx_pad_item.au of that item (a carousel slot: flags, DABX_MOT_FLAG_DIR_ELEMENT) */
   uint8_t  repeat;           /* emissions of this object since the last reset(), minus one, saturating at 255: a host skips repeat != 0
                                 without comparing bytes */
 } dabx_mot_object;           /* 32 bytes, little-endian, no holes; the object's bytes: body_len of body (the stored segments in key order),
@@ -800,6 +800,113 @@ int  dabx_set_mot_mode(dabx_engine *e, int stream, int subch_idx, const dabx_mot
 int  dabx_read_mot_objects(dabx_engine *e, int stream, int subch_idx, int n, dabx_mot_object *info, uint8_t *bytes, size_t max_bytes);
 int  dabx_get_mot_stats(dabx_engine *e, int stream, int subch_idx, dabx_mot_stats *out);
 /* ------------------------------------------------------------------------------------------------------------
+ * MOT objects of a packet-mode carousel: what DataProcessor does with the MSC data groups of a packet-mode sub-channel with DSCTy 60
+ * (data_processor.cpp:92-95, :209, :236; the DSCTy is dabx_packet_component's) behind the hand-over of dabx_datagroup_info --
+ * MotHandler::add_MSC_data_group with its object cache (base/backend/data/mot/mot_handler.cpp:69-259, mh:), MotDirectory
+ * (base/backend/data/mot/mot_dir.cpp:28-156, md:) and a MotObject per transport id (mot_object.cpp:71-323, mo:, as in "MOT objects of the
+ * X-PAD" but no PAD element: no progress signal, mo:160) -- on the device (k_carousel, behind k_packet on the MSC batch's stream, one wave
+ * per carousel-enabled packet-mode slot).  Every `emit signal_new_mot_object` (mo:300) is one dabx_mot_object plus its bytes.  Per
+ * dabx_datagroup_info, in emission order:
+ *   1 an empty group: return (mh:86-89).  crc_flag && !crc_ok: return (mh:91-94, crc_bad; the record's verdict, the CRC is not run again).
+ *   2 next = ExtensionFlag ? 4 : 2 bytes.  SegmentFlag: lastFlag and the 15-bit segment number, next += 2 (mh:101-106); without it the number
+ *     is 0.  UserAccessFlag: lengthInd = low nibble, the transport id from the two bytes behind the length byte whenever bit 4 of that byte
+ *     is set, WHATEVER lengthInd says (mh:110-116); next moves by 1 + lengthInd only (mh:112, :117).  No transport id: return (mh:122-125,
+ *     no_tid).
+ *   3 the payload is everything behind next, minus the two CRC bytes when the flag is set (mh:120); segmentSize = its first 13 bits, the
+ *     segment starts 2 bytes in (mh:139).
+ *   4 the cache (mh:211-259): 15 entries.  getHandle looks an id up in the cache first and then in the directory's components; setHandle
+ *     takes the first free entry, and when none is free it evicts the entry with the lowest order number (evictions) -- that object is gone.
+ *   5 type 3 (mh:142-154): looked at only when the segment number is 0 (hdr_not_first otherwise); IGNORED when a handle for the id exists,
+ *     in the cache or in the directory (mh:145-149, hdr_known) -- a header never replaces a header; else a new object, set_header
+ *     (mo:71-115) on the segment, a cache entry.
+ *   6 type 4 (mh:156-170): for an id without a handle the object is made with set_header run over the BODY segment's bytes (mh:159-164,
+ *     from_body) and put into the cache; such an object keeps that header for good, since 5 ignores every later header.  Then
+ *     add_body_segment (mo:117-175) and the emit when complete, as in "MOT objects of the X-PAD" 6.
+ *   7 type 6 (mh:172-204), segment number 0: the same transport id as the directory's: return (dirs_repeated); else the directory and
+ *     every object in it are deleted and a new MotDirectory is made from dirSize (30 bits), numObjects (16 bits) and the segment (md:28-57,
+ *     dirs_begun): the segment goes to offset 0, and the directory is analysed at once when segmentSize >= dirSize.  Other segment numbers:
+ *     dropped when there is no directory of that id (mh:198-201) or the segment is marked already (md:102); else a last flag sets
+ *     num_dirSegments, the segment is marked and copied to segmentNumber * dir_segmentSize -- the size of segment 0 -- (md:104-108,
+ *     dir_segments), and the directory is analysed when every segment below num_dirSegments is marked (md:112-118).  Nothing prevents a
+ *     second analysis when a further segment arrives.
+ *   8 analyse_theDirectory (md:124-152): base = 11, the 16-bit extension length is skipped, then for each of numObjects entries: a
+ *     transport id of 0 ends the walk; else a MotObject as a directory element with set_header on the entry's bytes, base += 2 +
+ *     headerSize, and setHandle puts it into the first component not in use (md:78-88, dir_objects).  A second analysis therefore
+ *     registers nothing once all components are in use -- and registers entries AGAIN, behind the first ones, when the first walk ended
+ *     early.  Kept.  (An object that finds no component is never seen again: only its headerSize is read.)
+ *   9 any other type: return (mh:206-207, type_other).  Nothing is cleared after an emit.
+ * Guards, where the reference reads outside the bytes it was given or grows without bound; each is counted:
+ *   C1 (mh:103-115, :139, :151-167): a header field beyond the group, a payload shorter than 2 bytes or 2 + segmentSize beyond the payload:
+ *      the group is ignored, state unchanged, grp_short (an empty group counts here too).  Checked in front of the dispatch of 5..9.
+ *   C2 (mo:84-87, :212-230, :185): a type-3 or created-from-body segment shorter than the 7 bytes of the header core: the group is ignored
+ *      and no handle is made.  An extension read at an index >= segmentSize ends the walk, as M2.  For a directory entry, whose
+ *      set_header gets no size at all (md:145), the bound is the directory's end, and 8 192 bytes (headerSize has 13 bits).  hdr_bad.
+ *   C3: M3 as it is (mo:135-137), obj_overflow.
+ *   D1 (mh:188-189, md:127): segment 0 of a directory is shorter than the 13 bytes its fields and the analysis read: ignored, the old
+ *      directory stays.  dir_short.
+ *   D2 (md:46-47): dirSize > max_dir_bytes or numObjects > max_dir_objects: the directory is refused, the state is as if there were none of
+ *      that id; the old one is still deleted, as mh:183-184 does.  dirs_refused.
+ *   D3 (md:102, :107-108, :52): a directory segment number >= 512 (marked[512]) or a copy that would pass dirSize: the segment is dropped
+ *      and not marked, its last flag not looked at.  dir_seg_bad.  The constructor's copy of segment 0 is clipped to dirSize.
+ *   D4 (md:127, :133, :139-146): the analysis would read the extension length, an entry's id or its header core at or beyond dirSize: the
+ *      walk ends there.  dir_cut.
+ * Memory per carousel slot, B = max_object_bytes rounded up to 8, D = max_dir_objects, Y = max_dir_bytes rounded up to 8: one allocation of
+ *   ring(B) + (15 + D) * (B + 8 192 + 65 536 + 56) + Y + 64 + 4 * D (rounded up to 8) bytes, ring(B) = 2 * (B + 8 192) as a power of two,
+ * plus 256 * 32 bytes of records: every object has an arena, 8 KiB of name room and the 8 192-entry segment table, so the reference's
+ * segment-number range is kept whole.  The defaults take 9.3 MB.
+ * Parity of this path with the reference's object code is unpinned: mot_handler.cpp cannot be compiled without the GUI's headers
+ * (dabradio.h), so the tests compare the device with a line-by-line restatement (tests/carousel_cases.py).
+ * Out of scope: the SPI/EPG decoders, image decoding, the charset of the object name, the default name "trid_<n>", the Journaline, TDC
+ * and IP handlers, packet-mode FEC. */
+#define DABX_MOT_FLAG_DIR_ELEMENT 1   /* dabx_mot_object.au of a carousel slot, bit 0: the dirElement argument of signal_new_mot_object */
+typedef struct {
+  uint32_t size;             /* sizeof(dabx_carousel_config) of the caller */
+  uint32_t max_object_bytes; /* guard C3; 0 = 65 536; below 256 or above 4 MiB: DABX_E_ARG.  Read only when size >= 8 */
+  uint32_t max_dir_objects;  /* guard D2; 0 = 49; above 1 009: DABX_E_ARG.  Read only when size >= 12 */
+  uint32_t max_dir_bytes;    /* guard D2; 0 = 65 536; below 256 or above 1 MiB: DABX_E_ARG.  Read only when size >= 16 */
+  int32_t  reserved[4];      /* zero */
+} dabx_carousel_config;      /* 32 bytes */
+typedef struct {
+  int64_t objects, object_bytes;    /* dabx_mot_object records emitted and their bytes */
+  int64_t objects_lost;      /* objects that had left the rings before a dabx_read_mot_objects call could return them */
+  int32_t groups;            /* data groups walked */
+  int32_t headers;           /* set_header calls that read a header core */
+  int32_t segments;          /* body segments stored (mo:135-137) */
+  int32_t crc_bad;           /* 1 */
+  int32_t type_other;        /* 9 */
+  int32_t no_tid;            /* 2 */
+  int32_t grp_short;         /* guard C1, and the empty groups of 1 */
+  int32_t hdr_bad;           /* guard C2 */
+  int32_t seg_number_bad;    /* mo:119-123 */
+  int32_t seg_duplicate;     /* mo:139-143 */
+  int32_t resets;            /* reset() calls: one per object made (mo:75-79 in the constructor) and guard C3 */
+  int32_t obj_overflow;      /* guard C3 */
+  int32_t hdr_known;         /* 5: a type-3 group for an id that has a handle */
+  int32_t hdr_not_first;     /* 5: a type-3 group with a segment number other than 0 */
+  int32_t from_body;         /* 6: objects made from a body segment */
+  int32_t evictions;         /* 4 */
+  int32_t dirs_begun;        /* 7: directories made */
+  int32_t dirs_repeated;     /* 7: segment 0 of the directory there is */
+  int32_t dirs_refused;      /* guard D2 */
+  int32_t dir_segments;      /* 7: directory segments stored, segment 0 included */
+  int32_t dir_objects;       /* 8: objects registered in a component */
+  int32_t dir_short;         /* guard D1 */
+  int32_t dir_seg_bad;       /* guard D3 */
+  int32_t dir_cut;           /* guard D4 */
+  int32_t dg_overrun;        /* data groups that had left the packet rings before k_carousel reached them (the rings hold two batches: always 0) */
+  int32_t active;            /* 1: carousel decoding is on for the slot (all else is zero otherwise) */
+} dabx_carousel_stats;       /* 128 bytes */
+/* Switches the carousel decoding of slot subch_idx of `stream` on (cfg != NULL) or off (NULL).  On only for a slot in packet mode
+ * (dabx_set_packet_mode); DABX_E_ARG otherwise.  It starts with an empty cache and no directory at the next data group completed; calling
+ * it again restarts it.  Calling dabx_set_packet_mode for the slot, on or off, ends its carousel decoding: the packet stage restarts with
+ * empty rings.  The setting and the state stay with the slot wherever dabx_set_subchannels says it "keeps decoding without interruption", a
+ * move to other capacity units included; a new or changed slot loses them.  The data groups of the slot are produced and delivered
+ * exactly as before.  The objects are dabx_mot_object records, read with dabx_read_mot_objects (a slot is a PAD slot or a packet slot, never
+ * both); for a carousel slot `frame` is dabx_datagroup_info.last_frame of the group that completed the object and the byte `au` carries
+ * flags: DABX_MOT_FLAG_DIR_ELEMENT.  An engine without a carousel slot allocates and launches nothing for this stage.  Drains the engine. */
+int  dabx_set_carousel_mode(dabx_engine *e, int stream, int subch_idx, const dabx_carousel_config *cfg);
+int  dabx_get_carousel_stats(dabx_engine *e, int stream, int subch_idx, dabx_carousel_stats *out);
+/* ------------------------------------------------------------------------------------------------------------
  * Bulk delivery of the results to the host.  The reference hands every FIB to IFibDecoder::process_FIB
  * (base/decoder/fib_decoder_if.h:81, called from fic_decoder.cpp:234-261) and every logical frame to
  * FrameProcessor::add_to_frame (base/backend/frame_processor.h:43-46, called from backend.cpp:160) the moment it exists;
@@ -840,8 +947,8 @@ enum { DABX_DELIVER_FIB = 1, DABX_DELIVER_MSC = 2, DABX_DELIVER_SF = 4,
           gains a PAD section (dabx_chunk_pad below) and dabx_chunk_header.what shows the bit; without a PAD slot a slab is byte for byte
           what it is without the bit, dabx_delivery_slab_bytes included */
        DABX_DELIVER_PAD = 32,
-       /* the MOT objects of the MOT-enabled PAD slots (dabx_set_mot_mode): with this bit, or with what == 0, AND at least one MOT slot the
-          slab gains a MOT section (dabx_chunk_mot below) and dabx_chunk_header.what shows the bit; without a MOT slot a slab is byte for
+       /* the MOT objects of the MOT-enabled PAD slots (dabx_set_mot_mode) and of the carousel slots (dabx_set_carousel_mode): with this bit,
+          or with what == 0, AND at least one MOT or carousel slot the slab gains a MOT section (dabx_chunk_mot below) and dabx_chunk_header.what shows the bit; without a MOT slot a slab is byte for
           byte what it is without the bit, dabx_delivery_slab_bytes included */
        DABX_DELIVER_MOT = 64 };
 typedef struct {
@@ -932,7 +1039,8 @@ typedef struct {
  * sequence, emitted since the previous chunk: object i is bytes_off + byte_pos .. + body_len + name_len (byte_pos counts from bytes_off).
  * objects_lost: objects emitted since the previous chunk that are not in this one -- more than 16, more bytes than the room, or gone from
  * the slot's rings; those still in the rings stay readable through dabx_read_mot_objects.  The counters are cumulative, as
- * dabx_mot_stats. */
+ * dabx_mot_stats.  A carousel slot (dabx_set_carousel_mode) has its row and its room in the same section, behind the rooms of the MOT slots,
+ * filled by a second gather launch (k_deliver_carousel); its counters are those of dabx_carousel_stats and progress_events is 0. */
 typedef struct {
   int64_t  first_object;
   int32_t  n_objects, objects_lost;
