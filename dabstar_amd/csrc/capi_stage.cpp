@@ -1,6 +1,7 @@
 // capi_stage.cpp -- stage-level C ABI (host-pointer entry points mirroring single reference functions).
 #include <algorithm>
 #include "dabx_internal.h"
+#include "eti_core.h"
 #include <cstring>
 
 namespace dabx { const char *last_error(); }
@@ -137,6 +138,49 @@ int dabx_crc16_check(const uint8_t *msgs, int stride, int len, int batch, uint8_
   if ((rc = launch_crc16_check(dm.as<uint8_t>(), stride, len, batch, dok.as<uint8_t>(), 0))) return rc;
   DABX_HIP(hipStreamSynchronize(0));
   return dok.to_host(ok, (size_t)batch);
+}
+
+// ETI(NI) frames on the device: eti_build_frame (eti_core.h), the body of the delivery's ETI stage, one wave per frame
+int dabx_eti_frames_device(int n, const int32_t *cif_hi, const int32_t *cif_lo, const int32_t *minor, const dabx_subch_desc *sc, int n_subch,
+                           const uint8_t *fic96, const uint8_t *msc, uint8_t *out, int32_t *used)
+{
+  if (n <= 0 || !cif_hi || !cif_lo || !minor || n_subch < 0 || n_subch > 64 || (n_subch && (!sc || !msc)) || !fic96 || !out || !used) {
+    set_error("dabx_eti_frames_device: bad argument");
+    return DABX_E_ARG;
+  }
+  for (int f = 0; f < n; f++)
+    if (cif_hi[f] < 0 || cif_lo[f] < 0 || minor[f] < 0 || minor[f] > 3) { set_error("dabx_eti_frames_device: bad counter of frame %d", f); return DABX_E_ARG; }
+  std::vector<uint32_t> stc((size_t)std::max(1, n_subch));
+  std::vector<int32_t> ndw(stc.size()), off(stc.size());
+  int sum_kbps = 0;
+  for (int i = 0; i < n_subch; i++) {
+    const dabx_subch_desc &q = sc[i];
+    const bool lvl_ok = q.short_form ? (q.prot_level >= 1 && q.prot_level <= 5) : (q.prot_level >= 0 && q.prot_level <= 7);
+    if (!lvl_ok || q.subch_id < 0 || q.subch_id > 63 || q.cu_start < 0 || q.cu_start > 863 || q.kbps <= 0 || q.kbps > 1023 || q.kbps % 8) {
+      set_error("dabx_eti_frames_device: sub-channel %d is not a legal description (kbps a multiple of 8)", i);
+      return DABX_E_ARG;
+    }
+    stc[(size_t)i] = eti_stc_word(q.subch_id, q.cu_start, q.kbps, q.prot_level, q.short_form);
+    ndw[(size_t)i] = 3 * q.kbps / 4; off[(size_t)i] = 3 * sum_kbps / 4;
+    sum_kbps += q.kbps;
+  }
+  if (eti_used_bytes(n_subch, sum_kbps) > DABX_ETI_FRAME_BYTES) {
+    set_error("dabx_eti_frames_device: %d bytes of sub-channel data do not fit an ETI frame", 96 + 3 * sum_kbps);
+    return DABX_E_ARG;
+  }
+  int rc = need_device();
+  if (rc) return rc;
+  const size_t N = (size_t)n, row = (size_t)3 * sum_kbps;
+  DevBuf dhi, dlo, dmi, dstc, dndw, doff, dfic, dmsc, dout, dused;
+  if ((rc = dhi.from_host(cif_hi, 4 * N)) || (rc = dlo.from_host(cif_lo, 4 * N)) || (rc = dmi.from_host(minor, 4 * N)) ||
+      (rc = dstc.from_host(stc.data(), 4 * stc.size())) || (rc = dndw.from_host(ndw.data(), 4 * ndw.size())) ||
+      (rc = doff.from_host(off.data(), 4 * off.size())) || (rc = dfic.from_host(fic96, 96 * N)) ||
+      (rc = row ? dmsc.from_host(msc, row * N) : dmsc.alloc(4)) || (rc = dout.alloc((size_t)DABX_ETI_FRAME_BYTES * N)) || (rc = dused.alloc(4 * N))) return rc;
+  if ((rc = launch_eti_frames(n, dhi.as<int32_t>(), dlo.as<int32_t>(), dmi.as<int32_t>(), n_subch, dstc.as<uint32_t>(), dndw.as<int32_t>(),
+                              doff.as<int32_t>(), (int)(row / 4), dfic.as<uint32_t>(), dmsc.as<uint32_t>(), dout.as<uint32_t>(), dused.as<int32_t>(), 0))) return rc;
+  DABX_HIP(hipStreamSynchronize(0));
+  if ((rc = dout.to_host(out, (size_t)DABX_ETI_FRAME_BYTES * N))) return rc;
+  return dused.to_host(used, 4 * N);
 }
 
 int dabx_fft2048(const dabx_cf32 *in, int batch, int inverse, dabx_cf32 *out)

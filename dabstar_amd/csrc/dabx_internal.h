@@ -91,5 +91,9 @@ int launch_demap_store_null(DemapDev &d, const float2 *fft, hipStream_t st);
 int launch_demap_symbols(DemapDev &d, const float2 *fft, int n_sym, const float *clock_err, int16_t *soft, hipStream_t st);
 int launch_demap_snr(DemapDev &d, float *snr_db_dev, hipStream_t st);
 int launch_demap_lcd(DemapDev &d, float *out3_dev /* [B][3]: SNR dB, MER dB, mMeanValue */, hipStream_t st);
+// deliver.hip: n ETI frames of one layout, a wave each (eti_core.h).  stc / ndw / off [n_subch]: eti_stc_word, 3 * kbps / 4 and the dword
+// offset of the sub-channel in a frame's msc row of sum_dw dwords; fic [n][24], msc [n][sum_dw], out [n][1536], used [n]
+int launch_eti_frames(int n, const int32_t *cif_hi, const int32_t *cif_lo, const int32_t *minor, int n_subch, const uint32_t *stc, const int32_t *ndw,
+                      const int32_t *off, int sum_dw, const uint32_t *fic, const uint32_t *msc, uint32_t *out, int32_t *used, hipStream_t st);
 
 }  // namespace dabx

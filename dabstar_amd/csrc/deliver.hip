@@ -10,6 +10,8 @@
 #include "pad_core.h"
 #include "mot_core.h"
 #include "carousel_core.h"
+#include "eti_core.h"
+#include "fig00.h"
 
 namespace dabx {
 
@@ -283,6 +285,183 @@ int launch_deliver_lf(const EngineDev &e, const DeliverDev &dv, hipStream_t st)
   if (e.max_subch <= 0 || !dv.lf_done) return 0;
   hipLaunchKernelGGL(k_deliver_lf, dim3(e.n_streams * e.max_subch), dim3(64), 0, st, e, dv);
   DABX_HIP(hipEventRecord(dv.lf_done, st));
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---- the ETI stage (include/dabx.h, dabx_chunk_eti; pipeline.h, EtiDev): the stream of frames dabx_read_eti defines, built on the device ----
+// Front half, grid = n_streams, 128 threads, front-end stream, beside k_deliver_front: the FIBs of the chunk's frames into the chunk's
+// staging, and the FIG 0/0 counter walked over those whose CRC is good (fib_fig00_counter, one FIB per thread; thread 0 strings them together).
+__global__ __launch_bounds__(128) void k_eti_front(EngineDev e, EtiDev t)
+{
+  constexpr int F = MSC_BATCH_FRAMES;
+  __shared__ int32_t found[12 * F], fhi[12 * F], flo[12 * F];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  const StreamCtl &c = e.ctl[s];
+  const EtiFront cur = t.front[s];
+  EtiStage &st = t.stage[s];
+  const long long frames = c.frames, have = frames - cur.fib_frames;
+  const int n = have < 0 ? 0 : (int)(have < F ? have : F);           // (older frames have left the chunk: their FIBs are not walked, as in dabx_read_eti)
+  const long long first = frames - n;
+  for (int i = tid; i < n * 96; i += 128) {
+    const int f = i / 96, w = i - 96 * f;
+    const size_t slot = (size_t)s * e.out_frames + (size_t)((first + f) % e.out_frames);
+    st.fib[f][w] = reinterpret_cast<const uint32_t *>(e.fib_out + slot * 384)[w];
+  }
+  for (int q = tid; q < 12 * n; q += 128) {
+    const int f = q / 12, i = q - 12 * f;
+    const size_t slot = (size_t)s * e.out_frames + (size_t)((first + f) % e.out_frames);
+    int hi = -1, lo = -1;
+    found[q] = e.fib_crc[slot * 12 + i] && fib_fig00_counter(e.fib_out + slot * 384 + 32 * i, &hi, &lo);
+    fhi[q] = hi; flo[q] = lo;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int hi = cur.hi, lo = cur.lo;
+    for (int f = 0; f < n; f++) {
+      for (int i = 0; i < 12; i++) if (found[12 * f + i]) { hi = fhi[12 * f + i]; lo = flo[12 * f + i]; }
+      st.hi[f] = hi; st.lo[f] = lo;
+    }
+    st.first_frame = first; st.n_frames = n; st.hi_cif = c.cif_no; st.end_hi = hi; st.end_lo = lo; st.pad_ = 0; st.fib_frames = frames;
+    t.front[s] = EtiFront{frames, hi, lo};
+  }
+}
+
+// Which CIFs of stream s the chunk turns into rows: [first_cif, first_cif + n_eti), and why the others of [next_cif, hi_cif) are not.
+// In CIF order: lost (gone from a ring, or more than the rows' room), waiting (a de-interleaver not filled, no FIG 0/0 yet), then the rows
+// -- or none of them, refused, when the layout does not fit a frame.  Computed by every wave that needs it, all lanes.
+struct EtiPlan { long long first_cif, hi_cif; int n_eti, lost, waiting, refused, n_subch; };
+__device__ __forceinline__ long long wave_max_ll(long long v)
+{
+  for (int d = 32; d > 0; d >>= 1) { const long long o = __shfl_xor(v, d); v = o > v ? o : v; }
+  return v;
+}
+__device__ __forceinline__ EtiPlan eti_plan(const EngineDev &e, const EtiDev &t, int s, int lane, bool pre)
+{
+  const EtiStage &st = t.stage[s];
+  const long long next = t.next_cif[s], hi_cif = st.hi_cif > next ? st.hi_cif : next;
+  long long wait_lo = 0, over_lo = 0;
+  int n_act = 0, sum_kbps = 0;
+  for (int j0 = 0; j0 < e.max_subch; j0 += 64) {
+    const int j = j0 + lane;
+    long long w = 0, o = 0;
+    int a = 0, k = 0;
+    if (j < e.max_subch && e.msc_out) {
+      const SubchDev &sc = e.subch[(size_t)s * e.max_subch + j];
+      if (sc.active) {
+        a = 1; k = sc.kbps; w = msc_first_cif(sc.start_cif);
+        long long cif_out = sc.cif_out;
+        if (pre) { const BatchSnap bs = e.snap[s]; cif_out += msc_new_frames(bs.msc_done, bs.cif_no, sc.start_cif).n; }
+        if (cif_out > MSC_SLOTS) o = w + cif_out - MSC_SLOTS;          // the oldest logical frame still in the slot's ring
+      }
+    }
+    n_act += wave_sum_int(a); sum_kbps += wave_sum_int(k);
+    w = wave_max_ll(w); o = wave_max_ll(o);
+    wait_lo = w > wait_lo ? w : wait_lo; over_lo = o > over_lo ? o : over_lo;
+  }
+  const int cap = 4 * t.max_frames;
+  long long lost_lo = next;
+  if (over_lo > lost_lo) lost_lo = over_lo;
+  if (4 * st.first_frame > lost_lo) lost_lo = 4 * st.first_frame;                  // the FIBs of older frames were not staged
+  if (hi_cif - cap > lost_lo) lost_lo = hi_cif - cap;
+  if (hi_cif > 4 * (st.first_frame + st.n_frames) || lost_lo > hi_cif) lost_lo = hi_cif;
+  long long ctr_lo = hi_cif;                                                       // eti_generator.cpp:156-160: no frame before the first FIG 0/0
+  for (int i = st.n_frames - 1; i >= 0; i--) if (st.hi[i] >= 0 && st.lo[i] >= 0) ctr_lo = 4 * (st.first_frame + i);
+  long long emit_lo = lost_lo;
+  if (wait_lo > emit_lo) emit_lo = wait_lo;
+  if (ctr_lo > emit_lo) emit_lo = ctr_lo;
+  if (emit_lo > hi_cif) emit_lo = hi_cif;
+  const bool refused = n_act > 64 || eti_used_bytes(n_act, sum_kbps) > DABX_ETI_FRAME_BYTES;
+  EtiPlan p;
+  p.hi_cif = hi_cif; p.lost = (int)(lost_lo - next); p.waiting = (int)(emit_lo - lost_lo);
+  p.refused = refused ? (int)(hi_cif - emit_lo) : 0;
+  p.n_eti = refused ? 0 : (int)(hi_cif - emit_lo);
+  p.first_cif = hi_cif - p.n_eti; p.n_subch = n_act;
+  return p;
+}
+
+// grid = (4 * max_frames, n_streams), one wave each: row k of stream s, behind the batch's Viterbi decode (pre != 0: in front of its DAB+ stage,
+// SubchDev::cif_out not moved on yet).  The FIC of CIF r with the logical frame r - start_cif - 16 of every active slot, in slot order.
+__global__ __launch_bounds__(64) void k_eti_rows(EngineDev e, EtiDev t, int pre)
+{
+  __shared__ EtiSlot slots[64];
+  const int k = blockIdx.x, s = blockIdx.y, lane = threadIdx.x;
+  const EtiPlan p = eti_plan(e, t, s, lane, pre != 0);
+  if (k >= p.n_eti) return;
+  const long long r = p.first_cif + k;
+  int base = 0;
+  for (int j0 = 0; j0 < e.max_subch; j0 += 64) {
+    const int j = j0 + lane;
+    const size_t sj = (size_t)s * e.max_subch + (j < e.max_subch ? j : 0);
+    const bool a = j < e.max_subch && e.msc_out && e.subch[sj].active;
+    const unsigned long long m = __ballot(a);
+    if (a) {
+      const SubchDev &sc = e.subch[sj];
+      const long long lf = r - sc.start_cif - 16;
+      EtiSlot q;
+      q.src = reinterpret_cast<const uint32_t *>(e.msc_out + (sj * MSC_SLOTS + (size_t)(lf % MSC_SLOTS)) * e.msc_stride);
+      q.stc = eti_stc_word(t.subch_id[sj], r < sc.move_cif ? sc.prev_cu_start : sc.cu_start, sc.kbps, sc.prot_level, sc.short_form);
+      q.ndw = 3 * sc.kbps / 4;
+      slots[base + __popcll(m & ((1ull << lane) - 1ull))] = q;
+    }
+    base += __popcll(m);
+  }
+  __syncthreads();
+  const EtiStage &st = t.stage[s];
+  const int fi = (int)(r / 4 - st.first_frame);
+  uint32_t *row = reinterpret_cast<uint32_t *>(t.slab + t.rows_off + ((size_t)s * 4 * t.max_frames + k) * DABX_ETI_FRAME_BYTES);
+  eti_build_frame(st.hi[fi], st.lo[fi], (int)(r & 3), p.n_subch, slots, st.fib[fi] + 24 * (int)(r & 3), row, lane);
+}
+
+// grid = n_streams, one wave each, behind k_eti_rows: the stream's record, and the cursor moves on
+__global__ __launch_bounds__(64) void k_eti_close(EngineDev e, EtiDev t, int pre)
+{
+  const int s = blockIdx.x, lane = threadIdx.x;
+  const EtiPlan p = eti_plan(e, t, s, lane, pre != 0);
+  if (lane != 0) return;
+  const EtiStage &st = t.stage[s];
+  dabx_chunk_eti r{};
+  r.first_cif = p.first_cif; r.n_eti = p.n_eti; r.cifs_lost = p.lost; r.cifs_waiting = p.waiting; r.cifs_refused = p.refused;
+  r.cif_hi = st.end_hi; r.cif_lo = st.end_lo; r.fib_frames = st.fib_frames;
+  r.rows_off = t.rows_off + (size_t)s * 4 * t.max_frames * DABX_ETI_FRAME_BYTES;
+  reinterpret_cast<dabx_chunk_eti *>(t.slab + t.off_eti)[s] = r;
+  t.next_cif[s] = p.hi_cif;
+}
+
+int launch_eti_front(const EngineDev &e, const EtiDev &t, hipStream_t st, Marker &mk)
+{
+  mk.begin(15, st);
+  hipLaunchKernelGGL(k_eti_front, dim3(e.n_streams), dim3(128), 0, st, e, t);
+  mk.end(15, st);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+int launch_eti_back(const EngineDev &e, const EtiDev &t, hipStream_t st, Marker &mk, bool pre)
+{
+  mk.begin(15, st);
+  hipLaunchKernelGGL(k_eti_rows, dim3(4 * t.max_frames, e.n_streams), dim3(64), 0, st, e, t, pre ? 1 : 0);
+  hipLaunchKernelGGL(k_eti_close, dim3(e.n_streams), dim3(64), 0, st, e, t, pre ? 1 : 0);
+  mk.end(15, st);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+
+// dabx_eti_frames_device (capi_stage.cpp): n frames of one layout through the same body, a wave each
+__global__ __launch_bounds__(64) void k_eti_frames(const int32_t *cif_hi, const int32_t *cif_lo, const int32_t *minor, int n_subch, const uint32_t *stc,
+                                                   const int32_t *ndw, const int32_t *off, int sum_dw, const uint32_t *fic, const uint32_t *msc,
+                                                   uint32_t *out, int32_t *used)
+{
+  __shared__ EtiSlot slots[64];
+  const int f = blockIdx.x, lane = threadIdx.x;
+  if (lane < n_subch) slots[lane] = EtiSlot{msc + (size_t)f * sum_dw + off[lane], stc[lane], ndw[lane]};
+  __syncthreads();
+  const int u = eti_build_frame(cif_hi[f], cif_lo[f], minor[f], n_subch, slots, fic + (size_t)f * 24, out + (size_t)f * 1536, lane);
+  if (lane == 0) used[f] = u;
+}
+int launch_eti_frames(int n, const int32_t *cif_hi, const int32_t *cif_lo, const int32_t *minor, int n_subch, const uint32_t *stc, const int32_t *ndw,
+                      const int32_t *off, int sum_dw, const uint32_t *fic, const uint32_t *msc, uint32_t *out, int32_t *used, hipStream_t st)
+{
+  hipLaunchKernelGGL(k_eti_frames, dim3(n), dim3(64), 0, st, cif_hi, cif_lo, minor, n_subch, stc, ndw, off, sum_dw, fic, msc, out, used);
   DABX_HIP(hipGetLastError());
   return 0;
 }

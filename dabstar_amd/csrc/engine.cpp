@@ -522,6 +522,10 @@ static int set_subchannels_impl(dabx_engine *e, int stream, const dabx_subch_des
     for (size_t sj : restarted) {
       DABX_HIP(hipMemcpy(e->dl.cif_done + sj, &zero, sizeof(zero), hipMemcpyHostToDevice));
       DABX_HIP(hipMemcpy(e->dl.sf_done + sj, &zero, sizeof(zero), hipMemcpyHostToDevice));
+      if (e->dl.eti()) {           // ... and the ETI stage forgets the stream's counter, as dabx_read_eti's cursor does above
+        const int32_t unknown[2] = {-1, -1};
+        DABX_HIP(hipMemcpy(&e->dl.eti_front[sj / (size_t)d.max_subch].hi, unknown, sizeof(unknown), hipMemcpyHostToDevice));
+      }
     }
     if ((rc = e->delivery_layout())) {             // the new sub-channels do not fit the slabs: no gather may run with a stale layout
       const std::string why = dabx::last_error();
@@ -804,9 +808,11 @@ int dabx_process(dabx_engine *e, int max_frames, int sync)
       if (e->dl.open && (rc = e->delivery_begin(&dv, &dl_slot, &dl_dev))) return rc;
       e->dev.snap = e->snap_buf[e->ss.batch_parity];
       hipStream_t tail = e->stream;
+      const bool with_eti = e->dl.open && e->dl.eti();
+      const EtiDev eti = with_eti ? e->dl.eti_dev(dl_dev) : EtiDev{};
       rc = launch_msc_batch(e->dev, 4 * e->pending_frames, e->have_fast ? &e->fast : nullptr, e->ss, e->mk, e->dl.open ? &dv : nullptr, &tail,
                             e->pkt.dev.n > 0 ? &e->pkt.dev : nullptr, e->pad.dev.n > 0 ? &e->pad.dev : nullptr, e->mot.dev.n > 0 ? &e->mot.dev : nullptr,
-                            e->car.dev.n > 0 ? &e->car.dev : nullptr);
+                            e->car.dev.n > 0 ? &e->car.dev : nullptr, with_eti ? &eti : nullptr);
       if (rc) {
         if (e->dl.open) e->delivery_abort(dl_slot, dl_dev);          // the slabs of the chunk that was begun: never left IN_FLIGHT without a copy job
         e->pending_frames = 0;

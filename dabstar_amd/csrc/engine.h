@@ -55,6 +55,16 @@ struct Delivery {
   bool want_pad = false;                         // DABX_DELIVER_PAD, or what == 0: a PAD section while there are PAD slots
   bool want_mot = false;                         // DABX_DELIVER_MOT, or what == 0: a MOT section while there are MOT or carousel slots
   bool want_dg = false;                          // DABX_DELIVER_DG, or what == 0: a data-group section while there are packet-mode slots
+  // DABX_DELIVER_ETI (pipeline.h, EtiDev): the stage's cursor, one staging buffer per device slab, where the rows lie in a slab; all null / 0 without the bit
+  EtiFront *eti_front = nullptr;
+  long long *eti_next = nullptr;
+  EtiStage *eti_stage[NDEV] = {nullptr, nullptr, nullptr};
+  size_t eti_rows_off = 0;
+  bool eti() const { return (what & DABX_DELIVER_ETI) != 0; }
+  EtiDev eti_dev(int devslab) const
+  {
+    return EtiDev{eti_front, eti_next, eti_stage[devslab], dev[devslab], subch_id, hdr.off_eti, eti_rows_off, hdr.max_frames, 0};
+  }
 };
 
 // Bulk ingest (include/dabx.h "Bulk ingest"): page-locked input slabs, their device twins, one SDMA transfer per slab.  Both forms are S

@@ -11,7 +11,7 @@
 // ---- bulk delivery (include/dabx.h "Bulk delivery", deliver.hip) -------------------------------------------------------
 // the slab's records are ABI: hosts and the python binding (dabstar_amd/lib.py, CHUNK_*) parse them by these sizes
 static_assert(sizeof(dabx_chunk_header) == 128 && sizeof(dabx_chunk_stream) == 72 && sizeof(dabx_chunk_frame) == 16 && sizeof(dabx_chunk_subch) == 144 && offsetof(dabx_chunk_header, off_mot) == 112 &&
-              sizeof(dabx_superframe_info) == 32,
+              sizeof(dabx_superframe_info) == 32 && sizeof(dabx_chunk_eti) == 64 && offsetof(dabx_chunk_header, off_eti) == 120,
               "include/dabx.h: chunk record layout");
 static constexpr int DL_SF_CAP = (4 * DL_FRAMES + 4) / 5;          // super frames one chunk can complete (4 CIFs may be waiting from before)
 #if DABX_MSC_BATCH == 7
@@ -85,6 +85,7 @@ int dabx_engine::delivery_layout()
   off = layout_section(mot, D.want_mot && !d.fic_only, off, S * M * sizeof(dabx_chunk_mot), &h.off_mot);     // ... and behind that the MOT section (dabx_chunk_mot)
   off = layout_section(car, D.want_mot && !d.fic_only, off, S * M * sizeof(dabx_chunk_mot), &h.off_mot);     // ... with the rooms of the carousel slots
   if (h.off_mot) h.what |= DABX_DELIVER_MOT;
+  if (D.eti()) { off = align_up(off, 16); h.off_eti = off; off += S * sizeof(dabx_chunk_eti); }     // the ETI section's table (its rows: the slab's end)
   off = align_up(off, 256);
   h.off_msc = off;
   if ((D.what & (DABX_DELIVER_MSC | DABX_DELIVER_MSC_NOT_DABPLUS)) && !d.fic_only)
@@ -94,6 +95,8 @@ int dabx_engine::delivery_layout()
       lo[3 * sj] = off;
       off = align_up(off + (size_t)4 * F * 3 * sc.kbps, 16);
     }
+  D.eti_rows_off = 0;
+  if (D.eti()) { off = align_up(off, 256); D.eti_rows_off = off; off += S * 4 * F * DABX_ETI_FRAME_BYTES; }     // part of the tail: gathered with the logical frames
   h.bytes = off;
   if (off > D.capacity) {
     set_error("delivery: the configured sub-channels need %zu bytes per chunk, the slabs hold %zu (sub-channels of a stream that together "
@@ -154,7 +157,9 @@ int dabx_engine::delivery_begin(DeliverDev *dv, int *slot, int *devslab)
     D.slots[(size_t)h].lf_from = split ? lf_from : 0;
   }
   *slot = h;
-  const int rc = launch_deliver_front(dev, *dv, stream);
+  int rc = launch_deliver_front(dev, *dv, stream);
+  // the ETI stage's front half: the FIB ring is the front end's, which rewrites it while the chunk's MSC batch is decoded
+  if (!rc && D.eti()) rc = launch_eti_front(dev, D.eti_dev(*devslab), stream, mk);
   if (rc) {                                                        // nothing was queued: give the slabs back
     std::lock_guard<std::mutex> lk(D.mu);
     D.dev_busy[*devslab] = false;
@@ -292,8 +297,11 @@ void delivery_free(dabx_engine *e)
     if (D.packed_lf[k]) (void)hipEventDestroy(D.packed_lf[k]);
     D.dev[k] = nullptr; D.packed[k] = nullptr; D.packed_lf[k] = nullptr; D.dev_busy[k] = false;
   }
-  for (void *q : {(void *)D.layout_off, (void *)D.subch_id, (void *)D.frames_done, (void *)D.cif_done, (void *)D.sf_done}) if (q) (void)hipFree(q);
+  for (void *q : {(void *)D.layout_off, (void *)D.subch_id, (void *)D.frames_done, (void *)D.cif_done, (void *)D.sf_done, (void *)D.eti_front,
+                  (void *)D.eti_next, (void *)D.eti_stage[0], (void *)D.eti_stage[1], (void *)D.eti_stage[2]}) if (q) (void)hipFree(q);
   D.layout_off = nullptr; D.subch_id = nullptr; D.frames_done = D.cif_done = D.sf_done = nullptr;
+  D.eti_front = nullptr; D.eti_next = nullptr; D.eti_rows_off = 0;
+  for (int k = 0; k < Delivery::NDEV; k++) D.eti_stage[k] = nullptr;
   if (D.cs) (void)hipStreamDestroy(D.cs);
   D.cs = nullptr;
   D.copier_error.clear();
@@ -307,7 +315,7 @@ extern "C" {
 
 int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
 {
-  if (!e || (cfg && (cfg->host_slabs < 0 || cfg->host_slabs == 1 || cfg->host_slabs > 64 || (cfg->what & ~127) || cfg->copy_engine < 0 || cfg->copy_engine > 1))) {
+  if (!e || (cfg && (cfg->host_slabs < 0 || cfg->host_slabs == 1 || cfg->host_slabs > 64 || (cfg->what & ~255) || cfg->copy_engine < 0 || cfg->copy_engine > 1))) {
     set_error("dabx_delivery_open: bad argument");
     return DABX_E_ARG;
   }
@@ -325,6 +333,11 @@ int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
               "(the FIBs of a chunk's first frames would have left the ring before they are gathered)", d.out_frames, DL_FRAMES, DL_FRAMES);
     return DABX_E_STATE;
   }
+  if (D.eti() && (d.fic_only || d.out_frames < DL_FRAMES)) {       // the ETI stage reads the chunk's FIBs at chunk close, like the FIB gather
+    if (d.fic_only) set_error("dabx_delivery_open: DABX_DELIVER_ETI on an engine that was created FIC-only");
+    else set_error("dabx_delivery_open: DABX_DELIVER_ETI needs dabx_config.out_frames >= %d, the engine's FIB ring holds %d frames", DL_FRAMES, d.out_frames);
+    return DABX_E_STATE;
+  }
   D.copy_engine = cfg ? cfg->copy_engine : 0;
   D.device = e->device;
   if (D.copy_engine == 0 && (rc = sdma_open(e->device, &D.sdma))) return rc;
@@ -340,6 +353,7 @@ int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
       (rc = e->car.download(d.max_subch))) return rc;
   cap += section_capacity(e->pkt, S * M * sizeof(dabx_chunk_dg)) + section_capacity(e->pad, S * M * sizeof(dabx_chunk_pad)) +
          section_capacity(e->mot, S * M * sizeof(dabx_chunk_mot)) + section_capacity(e->car, S * M * sizeof(dabx_chunk_mot));
+  if (D.eti()) cap += 16 + S * sizeof(dabx_chunk_eti) + 256 + S * 4 * F * DABX_ETI_FRAME_BYTES;      // ... and the ETI section: its table and 4 F rows per stream
   D.capacity = align_up(cap, 4096);
 #define H(x) do { hipError_t err__ = (x); if (err__ != hipSuccess) { set_error("HIP error %d (%s) at %s:%d", (int)err__, hipGetErrorString(err__), __FILE__, __LINE__); delivery_free(e); return DABX_E_HIP; } } while (0)
   if (D.copy_engine == 1) H(hipStreamCreateWithFlags(&D.cs, hipStreamNonBlocking));
@@ -373,6 +387,20 @@ int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
     H(hipMemcpy(D.frames_done, fr.data(), sizeof(long long) * S, hipMemcpyHostToDevice));
     H(hipMemcpy(D.cif_done, cd.data(), sizeof(long long) * cd.size(), hipMemcpyHostToDevice));
     H(hipMemcpy(D.sf_done, sd.data(), sizeof(long long) * sd.size(), hipMemcpyHostToDevice));
+    if (D.eti()) {
+      // the ETI stage's cursor: the CIFs decoded from now on, the counter unknown until a delivered frame carries a FIG 0/0
+      std::vector<EtiFront> ef(S);
+      std::vector<long long> nc(S);
+      for (size_t s_ = 0; s_ < S; s_++) { ef[s_] = EtiFront{ctl[s_].frames, -1, -1}; nc[s_] = ctl[s_].cif_no; }
+      H(hipMalloc((void **)&D.eti_front, sizeof(EtiFront) * S));
+      H(hipMalloc((void **)&D.eti_next, sizeof(long long) * S));
+      H(hipMemcpy(D.eti_front, ef.data(), sizeof(EtiFront) * S, hipMemcpyHostToDevice));
+      H(hipMemcpy(D.eti_next, nc.data(), sizeof(long long) * S, hipMemcpyHostToDevice));
+      for (int k = 0; k < Delivery::NDEV; k++) {
+        H(hipMalloc((void **)&D.eti_stage[k], sizeof(EtiStage) * S));
+        H(hipMemset(D.eti_stage[k], 0, sizeof(EtiStage) * S));
+      }
+    }
   }
 #undef H
   if ((rc = e->delivery_layout())) { delivery_free(e); return rc; }

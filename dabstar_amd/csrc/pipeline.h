@@ -181,6 +181,29 @@ struct DeliverDev {
   hipEvent_t lf_done;
 };
 
+// ---- the ETI stage of the delivery (deliver.hip k_eti_*, include/dabx.h dabx_chunk_eti): ETI(NI) frames assembled on the device (eti_core.h).
+// The stage's cursor per stream has a front-end half and a batch half, because the two run on different HIP streams: k_eti_front (front-end
+// stream, at chunk close, where k_deliver_front runs) owns the FIB ring -- it walks the FIG 0/0 counter over the chunk's frames and stages
+// their FIBs, since the front end may be rewriting the ring by the time the chunk's logical frames exist --, k_eti_rows / k_eti_close
+// (behind the batch's Viterbi decode) own next_cif.  One EtiStage per stream and device slab: a chunk's staging lives as long as its slab.
+struct EtiFront { long long fib_frames; int32_t hi, lo; };   // frames whose FIBs have been walked; CIFCountHi / Lo after them (-1: no FIG 0/0 yet)
+struct EtiStage {
+  long long first_frame, hi_cif;                             // the staged frames' first; ctl.cif_no at chunk close (== the batch's snapshot)
+  int32_t n_frames, end_hi, end_lo, pad_;
+  int32_t hi[MSC_BATCH_FRAMES], lo[MSC_BATCH_FRAMES];        // the counter after all 12 FIBs of staged frame i
+  uint32_t fib[MSC_BATCH_FRAMES][96];
+  long long fib_frames;
+};
+struct EtiDev {
+  EtiFront *front;                        // [S]
+  long long *next_cif;                    // [S] the next CIF the stage looks at
+  EtiStage *stage;                        // [S] of this chunk's device slab
+  uint8_t *slab;
+  const int32_t *subch_id;                // [S * max_subch], Delivery::subch_id
+  unsigned long long off_eti, rows_off;   // the table dabx_chunk_eti[S]; stream s's rows from rows_off + s * 4 * max_frames * 6144
+  int32_t max_frames, pad_;
+};
+
 // ---- lane-per-trellis path of the MSC decoder (vit_t.hip) ------------------------------------------------------
 // The sub-channels of ALL streams are grouped into classes of equal protection profile (same depuncture map and
 // trellis length): the 64 lanes of a decoder wave then share the map and step count whatever ensemble they come from.
@@ -231,7 +254,7 @@ struct EngineStreams {
 };
 
 // ---- profiling hook: HIP events around every kernel launch of a batch step ------------------------------------
-constexpr int N_STEP_KERNELS = 15;
+constexpr int N_STEP_KERNELS = 16;
 struct Marker {
   bool on = false;
   bool serial = false;            // the host waits for every instrumented kernel: one kernel on the chip at a time = stand-alone durations
@@ -354,7 +377,7 @@ extern const char *const kStepKernelNames[N_STEP_KERNELS];
 int launch_front_step(const EngineDev &e, EngineStreams &ss, Marker &mk, bool async_acquire, bool all_locked);
 int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineStreams &ss, Marker &mk, const DeliverDev *dv = nullptr,
                      hipStream_t *tail = nullptr, const PacketDev *pk = nullptr, const PadDev *pad = nullptr, const MotDev *mot = nullptr,
-                     const CarouselDev *car = nullptr);
+                     const CarouselDev *car = nullptr, const EtiDev *eti = nullptr);
 int launch_dciq(const EngineDev &e, int mode, hipStream_t st);
 int launch_level_exact(const EngineDev &e, hipStream_t st);
 int launch_commit(const EngineDev &e, int stream, unsigned long long n, hipStream_t st);
@@ -378,6 +401,8 @@ int launch_deliver_dg(const EngineDev &e, const DeliverDev &dv, const PacketDev 
 int launch_deliver_pad(const EngineDev &e, const DeliverDev &dv, const PadDev &pd, hipStream_t st);
 int launch_deliver_mot(const EngineDev &e, const DeliverDev &dv, const MotDev &md, hipStream_t st);
 int launch_deliver_carousel(const EngineDev &e, const DeliverDev &dv, const CarouselDev &cd, hipStream_t st, bool clear_table);
+int launch_eti_front(const EngineDev &e, const EtiDev &t, hipStream_t st, Marker &mk);              // at chunk close, front-end stream
+int launch_eti_back(const EngineDev &e, const EtiDev &t, hipStream_t st, Marker &mk, bool pre);     // behind the batch's decode; pre: in front of its DAB+ stage
 // msc_stages.hip
 int launch_dabplus_stage(const EngineDev &e, hipStream_t st, Marker &mk);
 int launch_packet_stage(const EngineDev &e, const PacketDev *pk, hipStream_t st, Marker &mk, PacketDev *used);

@@ -1694,7 +1694,7 @@ __global__ void k_msc_snap(EngineDev e, int cifs)
 // "k_demap_fic": the first k_demap_frame launch of a frame (symbols 1..3) when the FIC is decoded on its own stream
 const char *const kStepKernelNames[N_STEP_KERNELS] = {"k_acquire", "k_frame_head", "k_symbols", "k_demap_frame", "k_fic_frame", "k_frame_tail",
                                                       "k_msc_prep", "k_msc_vitT", "k_msc_frame", "k_dabplus", "k_demap_fic", "k_packet", "k_pad", "k_mot",
-                                                      "k_carousel"};
+                                                      "k_carousel", "k_eti"};
 
 // Front end of one batch step (everything with frame-to-frame feedback).
 // Overlapped schedule (ss.d set): the FIC lives in symbols 1..3 -- those are demapped first on the front-end stream a, then
@@ -1814,7 +1814,7 @@ int launch_front_step(const EngineDev &e_in, EngineStreams &ss, Marker &mk, bool
 // `pk`, `pad`, `mot`, `car` (optional): the engine's packet-mode / PAD / MOT / carousel slots, for the slot stages (msc_stages.hip) and the gathers of what
 // they emitted.
 int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineStreams &ss, Marker &mk, const DeliverDev *dv, hipStream_t *tail,
-                     const PacketDev *pk, const PadDev *pad, const MotDev *mot, const CarouselDev *car)
+                     const PacketDev *pk, const PadDev *pad, const MotDev *mot, const CarouselDev *car, const EtiDev *eti)
 {
   const DevTables *t;
   int rc = get_tables(&t);
@@ -1822,6 +1822,7 @@ int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineSt
   if (tail) *tail = ss.a;
   if (e.fic_only || e.max_subch <= 0 || !e.msc_out) {
     if (dv && (rc = launch_deliver_msc(e, *dv, ss.a, true))) return rc;    // the slot table says "nothing" for every slot
+    if (dv && eti && (rc = launch_eti_back(e, *eti, ss.a, mk, false))) return rc;     // FIC-only frames (an engine without a sub-channel)
     return 0;
   }
   const int jobs = e.n_streams * cifs * e.max_subch;
@@ -1897,6 +1898,8 @@ int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineSt
     }
   }
   // the chunk's logical frames exist: into the slab with them, their share of the transfer starts while the DAB+ stage runs (deliver.hip)
+  // ... and the ETI rows, which depend on nothing but the logical frames: they lie in the slab's tail and travel with it
+  if (dv && eti && dv->lf_done && (rc = launch_eti_back(e, *eti, sb, mk, true))) return rc;
   if (dv && (rc = launch_deliver_lf(e, *dv, sb))) return rc;
   PacketDev p;                                           // the stages' arguments as launched, n = 0: no such slot
   PadDev q;
@@ -1908,6 +1911,7 @@ int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineSt
   if ((rc = launch_pad_stage(e, pad, sb, mk, &q))) return rc;
   if ((rc = launch_mot_stage(e, mot, q, sb, mk, &m))) return rc;
   if (dv && (rc = launch_deliver_msc(e, *dv, sb, !dv->lf_done))) return rc;
+  if (dv && eti && !dv->lf_done && (rc = launch_eti_back(e, *eti, sb, mk, false))) return rc;      // (one transfer behind everything: here)
   if (dv && p.n > 0 && (rc = launch_deliver_dg(e, *dv, p, sb))) return rc;      // the slab's data-group section (head part, like the gather in front)
   if (dv && q.n > 0 && (rc = launch_deliver_pad(e, *dv, q, sb))) return rc;     // ... and its PAD section
   if (dv && m.n > 0 && (rc = launch_deliver_mot(e, *dv, m, sb))) return rc;     // ... and its MOT section

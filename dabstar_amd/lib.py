@@ -417,7 +417,13 @@ DELIVER_FIB, DELIVER_MSC, DELIVER_SF, DELIVER_MSC_NOT_DABPLUS, DELIVER_DG, DELIV
 CHUNK_HEADER = np.dtype([("magic", "<u4"), ("abi", "<u4"), ("seq", "<u8"), ("n_streams", "<i4"), ("max_subch", "<i4"),
                          ("max_frames", "<i4"), ("what", "<i4"), ("bytes", "<u8"), ("off_stream", "<u8"), ("off_subch", "<u8"),
                          ("off_fib", "<u8"), ("off_crc", "<u8"), ("off_frame", "<u8"), ("off_msc", "<u8"), ("off_sf", "<u8"),
-                         ("off_dg", "<u8"), ("off_pad", "<u8"), ("off_mot", "<u8"), ("reserved", "<u8", 1)])
+                         ("off_dg", "<u8"), ("off_pad", "<u8"), ("off_mot", "<u8"), ("off_eti", "<u8")])
+# the ETI section (DELIVER_ETI, opt-in: not part of what == 0): one record per stream, rows of ETI_FRAME_BYTES at rows_off
+DELIVER_ETI = 128
+ETI_FRAME_BYTES = 6144
+CHUNK_ETI = np.dtype([("first_cif", "<i8"), ("n_eti", "<i4"), ("cifs_lost", "<i4"), ("cifs_waiting", "<i4"), ("cifs_refused", "<i4"),
+                      ("cif_hi", "<i4"), ("cif_lo", "<i4"), ("rows_off", "<u8"), ("fib_frames", "<i8"), ("reserved", "<u8", 2)])
+assert CHUNK_ETI.itemsize == 64
 CHUNK_STREAM = np.dtype([("first_frame", "<i8"), ("n_frames", "<i4"), ("frames_lost", "<i4"), ("state", "<i4"),
                          ("fic_ratio_percent", "<i4"), ("cif_count", "<i4"), ("snr_db_est", "<f4"), ("freq_offs_bb_hz", "<f4"),
                          ("clock_err_hz", "<f4"), ("signal_level", "<f4"), ("fic_ber_bits", "<i4"), ("fic_ber_errors", "<i4"),
@@ -565,6 +571,18 @@ class Chunk:
         self.mot = None                         # the MOT section: [S, M] CHUNK_MOT, or None when the slab has none
         if int(h["off_mot"]):
             self.mot = self.raw[int(h["off_mot"]):int(h["off_mot"]) + S * M * 128].view(CHUNK_MOT).reshape(S, M)
+        self.eti_table = None                   # the ETI section: [S] CHUNK_ETI, or None when the slab has none
+        if int(h["off_eti"]):
+            self.eti_table = self.raw[int(h["off_eti"]):int(h["off_eti"]) + S * 64].view(CHUNK_ETI)
+
+    def eti(self, stream):
+        """ETI(NI) frames of `stream` in this chunk: (its CHUNK_ETI record, [n_eti, 6144] uint8), views; the rows are contiguous and in CIF
+        order -- rows.tobytes() is a piece of a raw ETI(NI) stream.  (None, empty) when the slab has no ETI section."""
+        if self.eti_table is None:
+            return None, np.zeros((0, ETI_FRAME_BYTES), np.uint8)
+        r = self.eti_table[stream]
+        o, n = int(r["rows_off"]), int(r["n_eti"])
+        return r, self.raw[o:o + n * ETI_FRAME_BYTES].reshape(n, ETI_FRAME_BYTES)
 
     def msc(self, s, j):
         """Logical frames of slot (s, j) in this chunk: [n_cifs, 3 * kbps] uint8 (a view)."""
@@ -1018,6 +1036,26 @@ def eti_frame(cif_hi, cif_lo, minor, subch, fic96, msc):
     fic96 = np.ascontiguousarray(fic96, np.uint8)
     out = np.zeros(6144, np.uint8)
     used = check(load().dabx_eti_frame(cif_hi, cif_lo, minor, arr, len(subch), _p(fic96), ptrs, _p(out)))
+    return out, used
+
+
+def eti_frames_device(cif_hi, cif_lo, minor, subch, fic96, msc):
+    """The same assembly on the device, n frames of one layout (a wavefront each, the kernel body of the delivery's ETI stage): cif_hi /
+    cif_lo / minor [n], subch = SubchDesc list, fic96 [n, 96], msc [n, sum of 3 * kbps] -> ([n, 6144] uint8, used [n] int32)."""
+    hi = np.ascontiguousarray(cif_hi, np.int32).reshape(-1)
+    lo = np.ascontiguousarray(cif_lo, np.int32).reshape(-1)
+    mi = np.ascontiguousarray(minor, np.int32).reshape(-1)
+    n = hi.size
+    if lo.size != n or mi.size != n:
+        raise ValueError("eti_frames_device needs one (cif_hi, cif_lo, minor) per frame")
+    arr = (SubchDesc * max(1, len(subch)))(*subch)
+    fic96 = np.ascontiguousarray(fic96, np.uint8).reshape(n, 96)
+    msc = np.ascontiguousarray(msc, np.uint8).reshape(n, -1)
+    out = np.zeros((n, ETI_FRAME_BYTES), np.uint8)
+    used = np.zeros(n, np.int32)
+    L = load()
+    L.dabx_eti_frames_device.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    check(L.dabx_eti_frames_device(n, _p(hi), _p(lo), _p(mi), arr, len(subch), _p(fic96), _p(msc) if msc.size else None, _p(out), _p(used)))
     return out, used
 
 

@@ -915,7 +915,8 @@ int  dabx_get_carousel_stats(dabx_engine *e, int stream, int subch_idx, dabx_car
  * DABX_CHUNK_FRAMES frames of every stream; a dabx_process call closes its last chunk -- is gathered on the device into ONE
  * contiguous slab and copied with ONE asynchronous DMA (an SDMA engine) into a page-locked host slab, next to the decode of the following chunk.
  * No call of the receiver waits for it, nothing is copied per stream or per CIF.  dabx_read_fibs / _msc / _superframes /
- * _eti remain as the convenience form for single streams (they drain the engine and copy from the device rings).
+ * _eti remain as the convenience form for single streams (they drain the engine and copy from the device rings); the ETI frames have
+ * their bulk form too, DABX_DELIVER_ETI below.
  *
  * A slab starts with a dabx_chunk_header; all dabx_chunk_* offsets are bytes from the slab's first byte:
  *   stream table  dabx_chunk_stream[n_streams]              which frames of the stream the chunk holds + the stream's scalars
@@ -950,7 +951,12 @@ enum { DABX_DELIVER_FIB = 1, DABX_DELIVER_MSC = 2, DABX_DELIVER_SF = 4,
        /* the MOT objects of the MOT-enabled PAD slots (dabx_set_mot_mode) and of the carousel slots (dabx_set_carousel_mode): with this bit,
           or with what == 0, AND at least one MOT or carousel slot the slab gains a MOT section (dabx_chunk_mot below) and dabx_chunk_header.what shows the bit; without a MOT slot a slab is byte for
           byte what it is without the bit, dabx_delivery_slab_bytes included */
-       DABX_DELIVER_MOT = 64 };
+       DABX_DELIVER_MOT = 64,
+       /* ETI(NI) frames of every stream, assembled on the device (the ETI section, dabx_chunk_eti below).  Opt-in: what == 0 does NOT
+          include it, and without the bit a slab, dabx_delivery_slab_bytes and the kernels launched are exactly what they are without it.
+          One ETI stream per ensemble carries the whole FIC and MSC: a consumer of ETI needs no other bit.  Needs dabx_config.out_frames
+          >= DABX_CHUNK_FRAMES, like the FIBs; an engine created FIC-only refuses it (DABX_E_STATE, as dabx_read_eti) */
+       DABX_DELIVER_ETI = 128 };
 typedef struct {
   int32_t host_slabs;       /* page-locked host slabs, >= 2 (0 = default 4) */
   int32_t what;             /* DABX_DELIVER_* mask, 0 = everything */
@@ -968,7 +974,7 @@ typedef struct {
   uint64_t off_dg;          /* the data-group section: dabx_chunk_dg[n_streams * max_subch]; 0 = the slab has none */
   uint64_t off_pad;         /* the PAD section: dabx_chunk_pad[n_streams * max_subch]; 0 = the slab has none */
   uint64_t off_mot;         /* the MOT section: dabx_chunk_mot[n_streams * max_subch]; 0 = the slab has none */
-  uint64_t reserved[1];
+  uint64_t off_eti;         /* the ETI section: dabx_chunk_eti[n_streams]; 0 = the slab has none */
 } dabx_chunk_header;        /* 128 bytes */
 typedef struct {
   int64_t first_frame;      /* index, since the stream was opened, of the first frame in the chunk */
@@ -1048,6 +1054,30 @@ typedef struct {
   int64_t  n_bytes;
   int64_t  objects, object_bytes, groups, headers, segments, crc_bad, grp_short, hdr_bad, obj_overflow, resets, progress_events;
 } dabx_chunk_mot;           /* 128 bytes */
+/* The ETI section (DABX_DELIVER_ETI): one dabx_chunk_eti per stream from off_eti -- in the slab's head part, at the next multiple of 16
+ * behind the MOT section, 64 * n_streams bytes -- and, at the next multiple of 256 behind the logical frames (the very end of the slab),
+ * room for 4 * DABX_CHUNK_FRAMES rows of DABX_ETI_FRAME_BYTES (6144) bytes per stream: n_streams * 4 * DABX_CHUNK_FRAMES * 6144 bytes, fixed by
+ * the configuration.  Stream s's rows start at rows_off = (start of the rows) + s * 4 * DABX_CHUNK_FRAMES * 6144; its n_eti rows are contiguous,
+ * compacted and in CIF order: rows_off .. + n_eti * 6144 can go to a file or a pipe as it is, as a raw ETI(NI) stream.  With DABX_DELIVER_ETI alone
+ * a slab is the header, the stream table, the slot table (each rounded up to 16 bytes), the ETI table, and from the next multiple of 256 the rows.
+ * The frames are those of dabx_read_eti, byte for byte (row i is CIF first_cif + i in the sense of its counter: the FIC of that CIF with
+ * the logical frame that completes with it of every active sub-channel in slot order, a moved sub-channel with its old start address
+ * before the move, the frame counter as FIG 0/0 gave it after the frame's 12 FIBs), from a cursor of the stage's own in device memory: the two do
+ * not disturb each other.  A delivery opened on a running stream starts with the CIFs decoded from then on and with the counter unknown:
+ * rows begin with the first delivered frame that carries a FIG 0/0, exactly as a first dabx_read_eti call on empty rings would begin.
+ * A sub-channel that is added or replaced (not one that only moves) makes the stage forget the counter in the same way, as it resets dabx_read_eti's cursor.
+ * Every CIF decoded since the previous chunk is a row or counted: cifs_lost (it had left a ring before the chunk was packed, or exceeded the
+ * rows' room; always 0 so far), cifs_waiting (the reference makes no frame for it either: a sub-channel's de-interleaver is not filled yet, or no FIG
+ * 0/0 has been seen, eti_generator.cpp:156-160), cifs_refused (the configured sub-channels do not fit a frame: dabx_eti_frame's DABX_E_ARG).
+ * A stream out of lock delivers n_eti = 0.  The rows are gathered behind the chunk's Viterbi decode and travel with the slab's tail (k_eti). */
+typedef struct {
+  int64_t  first_cif;       /* CIF of row 0; first_cif + n_eti is the next chunk's first_cif */
+  int32_t  n_eti, cifs_lost, cifs_waiting, cifs_refused;
+  int32_t  cif_hi, cif_lo;  /* CIFCountHi / Lo after the chunk's last frame (-1: no FIG 0/0 yet) */
+  uint64_t rows_off;
+  int64_t  fib_frames;      /* frames of the stream whose FIBs the stage has walked for the counter */
+  uint64_t reserved[2];
+} dabx_chunk_eti;           /* 64 bytes */
 typedef struct {
   uint64_t seq;
   const void *data;         /* the host slab: valid until dabx_delivery_release(seq) */
@@ -1189,6 +1219,12 @@ void dabx_feed_close(dabx_feed *f);
 #define DABX_ETI_FRAME_BYTES 6144
 int  dabx_eti_frame(int cif_hi, int cif_lo, int minor, const dabx_subch_desc *sc, int n_subch, const uint8_t *fic96,
                     const uint8_t *const *msc, uint8_t *out /* 6144 */);
+/* The same assembly on the device (stage level, host pointers): n frames of ONE layout, one wavefront per frame, through the kernel body of
+ * the delivery's ETI stage (DABX_DELIVER_ETI).  cif_hi / cif_lo / minor [n]; fic96 [n][96]; msc [n][sum of 3 * kbps]: a frame's sub-channel
+ * bytes one behind the other in sc's order; out [n][6144]; used [n] = dabx_eti_frame's return value per frame.  Refuses (DABX_E_ARG) what
+ * dabx_eti_frame refuses, and a kbps that is not a multiple of 8 (no sub-channel of the standard has one; the copy runs in dwords). */
+int  dabx_eti_frames_device(int n, const int32_t *cif_hi, const int32_t *cif_lo, const int32_t *minor, const dabx_subch_desc *sc, int n_subch,
+                            const uint8_t *fic96, const uint8_t *msc, uint8_t *out, int32_t *used);
 /* ETI frames of `stream` for the CIFs decoded since the previous call (at most max_frames, oldest first), assembled
  * from the engine's FIB and logical-frame rings for the configured sub-channels.  Like the reference the FIC of a
  * CIF is paired with the (time-de-interleaved) MSC data that completes with that CIF; frames start once every
