@@ -359,6 +359,58 @@ int dabx_internal_demap_frame(dabx_engine *e, const int32_t *present, int schedu
   return rc ? rc : rc2;
 }
 
+// ---- test entry of the frame chain (tests/test_gpu_front_stage.py; not part of include/dabx.h) ----------------------------------------
+// What k_frame_head, k_symbols_persistent and k_frame_tail of the LAST step left for `stream` of a drained engine, copied out with plain
+// hipMemcpy behind a full synchronisation (no kernel).  sc: the record below; phase_ref [2048] cf32 in bin order; spectra [75][1536] cf32 in
+// carrier order, from the buffer of the parity that step used; cp_part [75] cf32; abs_part [75]; null_power [2][2048] (DemapDev::null_power,
+// then null_power2; sc->np_sel tells which is current); tii_acc [2048] cf32 (left alone when the engine has no TII sum: sc->has_tii = 0).
+// Any of the array pointers may be NULL.
+struct dabx_front_scalars {
+  int32_t frame_ok, np_sel, start_index, correction, f_frame, phase_sym1, nco_phase, has_tii;
+  long long frames;
+  unsigned long long sym0_pos, rd;
+  float f_sync, f_bb, phase_offs, clock_err;
+  int32_t tii_cnt[2], parity, pad_;
+};
+static_assert(sizeof(dabx_front_scalars) == 88, "dabx_front_scalars: dabstar_amd/lib.py reads it as a packed record of 88 bytes");
+
+int dabx_internal_front_read(dabx_engine *e, int stream, dabx_front_scalars *sc, float *phase_ref, float *spectra, float *cp_part, float *abs_part,
+                             float *null_power, float *tii_acc)
+{
+  if (!e || !sc || stream < 0 || stream >= e->dev.n_streams || !e->dev.spectra || !e->dev.cp_part || !e->dev.abs_part || !e->dev.demap.phase_ref) {
+    set_error("dabx_internal_front_read: bad argument (stream %d)", stream);
+    return DABX_E_ARG;
+  }
+  if (e->dl.open || e->pending_frames != 0) {
+    set_error("dabx_internal_front_read: the engine has a delivery open or front-end frames pending");
+    return DABX_E_STATE;
+  }
+  if (int rc = use_device(e)) return rc;
+  if (int rc = sync_all(e)) return rc;
+  const EngineDev &d = e->dev;
+  const size_t s = (size_t)stream;
+  StreamCtl c;
+  DABX_HIP(hipMemcpy(&c, d.ctl + s, sizeof(StreamCtl), hipMemcpyDeviceToHost));
+  memset(sc, 0, sizeof(*sc));
+  sc->frame_ok = c.frame_ok; sc->np_sel = c.np_sel; sc->start_index = c.start_index; sc->correction = c.correction; sc->f_frame = c.f_frame;
+  sc->phase_sym1 = c.phase_sym1; sc->nco_phase = c.nco_phase; sc->frames = c.frames; sc->sym0_pos = c.sym0_pos; sc->rd = c.rd;
+  sc->f_sync = c.f_sync; sc->f_bb = c.f_bb; sc->phase_offs = c.phase_offs; sc->clock_err = c.clock_err;
+  sc->parity = e->ss.step_count ? (int)((e->ss.step_count - 1) & 1u) : 0;            // launch_front_step: parity = step_count++ & 1
+  sc->has_tii = d.tii_acc && d.tii_cnt;
+  if (sc->has_tii) DABX_HIP(hipMemcpy(sc->tii_cnt, d.tii_cnt + 2 * s, 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (phase_ref) DABX_HIP(hipMemcpy(phase_ref, d.demap.phase_ref + s * TU, TU * sizeof(float2), hipMemcpyDeviceToHost));
+  if (spectra)
+    DABX_HIP(hipMemcpy(spectra, d.spectra + ((size_t)sc->parity * d.n_streams + s) * 75 * K, (size_t)75 * K * sizeof(float2), hipMemcpyDeviceToHost));
+  if (cp_part) DABX_HIP(hipMemcpy(cp_part, d.cp_part + s * 75, 75 * sizeof(float2), hipMemcpyDeviceToHost));
+  if (abs_part) DABX_HIP(hipMemcpy(abs_part, d.abs_part + s * 76, 75 * sizeof(float), hipMemcpyDeviceToHost));
+  if (null_power) {
+    DABX_HIP(hipMemcpy(null_power, d.demap.null_power + s * TU, TU * sizeof(float), hipMemcpyDeviceToHost));
+    DABX_HIP(hipMemcpy(null_power + TU, d.demap.null_power2 + s * TU, TU * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  if (tii_acc && sc->has_tii) DABX_HIP(hipMemcpy(tii_acc, d.tii_acc + s * TU, TU * sizeof(float2), hipMemcpyDeviceToHost));
+  return 0;
+}
+
 }  // extern "C"
 
 struct dabx_msc {

@@ -843,7 +843,15 @@ __global__ __launch_bounds__(256, RF == RING_CF32 ? 3 : 4) void k_frame_head(Eng
   block_sum2(abs_a, abs_b, red, tid);
   fft2048<false>(v, lds, t.twiddle, tid);                 // dab_processor.cpp:199-201
 #pragma unroll
-  for (int u = 0; u < 8; u++) e.demap.phase_ref[(size_t)s * TU + tid + 256 * u] = v[u];   // store_reference_symbol_0
+  for (int u = 0; u < 8; u++) {                           // store_reference_symbol_0
+    // A bin the float transform cancels to exactly (0, 0) -- a used carrier that sees only rounding noise, as 33 of them do in the first
+    // frame of a noise-free signal 33 carriers off -- would make the demapper divide 0 by |0|: a NaN in the symbol's block-wide mean and in
+    // the carrier's running means, which no later frame gets rid of.  The reference's double transform leaves rounding noise there; the
+    // smallest such value (2^-60: its square is a normal float, its weight in the soft bits nil) stands in for it.
+    float2 r = v[u];
+    if (r.x == 0.0f && r.y == 0.0f) r.x = 0x1p-60f;
+    e.demap.phase_ref[(size_t)s * TU + tid + 256 * u] = r;
+  }
 
   int correction = 0;
   float f_sync = c.f_sync, f_bb = c.f_bb, clock_err = c.clock_err;
@@ -1442,7 +1450,10 @@ __global__ __launch_bounds__(256) void k_frame_tail(EngineDev e, DevTables t)
     double sr, cr;
     sincospi(-2.0 * (double)(((long long)f * TU) % INPUT_RATE) / (double)INPUT_RATE, &sr, &cr);
     const float rr = cre * (float)cr - cim * (float)sr, ri = cre * (float)sr + cim * (float)cr;
-    float ph = atan2f(ri, rr);
+    // (a correlation of exactly zero: the reference's sum of mixed zeros is (+0, +0) and its atan2f gives 0, whereas the rotation above makes
+    //  (-0, +0) of it where cos < 0 < sin -- f mod 1000 in (500, 750), or in (-500, -250) for a negative f -- and atan2f(+0, -0) = pi would be
+    //  a full clamp step)
+    float ph = (cre == 0.0f && cim == 0.0f) ? 0.0f : atan2f(ri, rr);
     const float lim = 20.0f * 0.01745329251994329577f;
     if (ph > lim) ph = lim; else if (ph < -lim) ph = -lim;
     c.phase_offs = ph;

@@ -185,6 +185,38 @@ def demap_frame(engine, present, schedule):
     check(load().dabx_internal_demap_frame(engine._h, _p(present), int(schedule)))
 
 
+FRONT_SCALARS = np.dtype([("frame_ok", "<i4"), ("np_sel", "<i4"), ("start_index", "<i4"), ("correction", "<i4"), ("f_frame", "<i4"),
+                          ("phase_sym1", "<i4"), ("nco_phase", "<i4"), ("has_tii", "<i4"), ("frames", "<i8"), ("sym0_pos", "<u8"), ("rd", "<u8"),
+                          ("f_sync", "<f4"), ("f_bb", "<f4"), ("phase_offs", "<f4"), ("clock_err", "<f4"), ("tii_cnt", "<i4", (2,)),
+                          ("parity", "<i4"), ("pad_", "<i4")])     # dabx_front_scalars (csrc/engine_facade.cpp)
+assert FRONT_SCALARS.itemsize == 88
+
+
+def front_read(engine, stream, spectra=True):
+    """Internal test entry (not part of include/dabx.h): what the frame chain (k_frame_head, k_symbols_persistent, k_frame_tail) of the
+    last step left for `stream` of a drained engine, copied out without any kernel.  A dict of the control record's scalars (frame_ok,
+    frames, sym0_pos, start_index, correction, f_frame, phase_sym1, nco_phase, f_sync, f_bb, phase_offs, clock_err, np_sel, rd, parity,
+    tii_cnt) and phase_ref [2048] complex64 in bin order, spectra [75, 1536] complex64 in carrier order (spectra=False: left out),
+    cp_part [75] complex64, abs_part [75] float32, null_power [2, 2048] float32 (both buffers; np_sel tells which is current) and
+    tii_acc [2048] complex64 (None when the engine keeps no TII sum)."""
+    sc = np.zeros(1, FRONT_SCALARS)
+    phase_ref = np.zeros(2048, np.complex64)
+    spec = np.zeros((75, 1536), np.complex64) if spectra else None
+    cp_part = np.zeros(75, np.complex64)
+    abs_part = np.zeros(75, np.float32)
+    null_power = np.zeros((2, 2048), np.float32)
+    tii_acc = np.zeros(2048, np.complex64)
+    L = load()
+    L.dabx_internal_front_read.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
+    check(L.dabx_internal_front_read(engine._h, int(stream), _p(sc), _p(phase_ref), None if spec is None else _p(spec), _p(cp_part), _p(abs_part),
+                                     _p(null_power), _p(tii_acc)))
+    out = {k: (sc[k][0].copy() if k == "tii_cnt" else sc[k][0].item()) for k in FRONT_SCALARS.names if k != "pad_"}
+    out["f_bb"], out["f_sync"], out["clock_err"], out["phase_offs"] = (np.float32(sc[k][0]) for k in ("f_bb", "f_sync", "clock_err", "phase_offs"))
+    out.update(phase_ref=phase_ref, spectra=spec, cp_part=cp_part, abs_part=abs_part, null_power=null_power,
+               tii_acc=tii_acc if out["has_tii"] else None)
+    return out
+
+
 def fib_cif_count(fib32):
     """Internal, host only: (CIFCountHi, CIFCountLo) the library's FIG 0/0 walk reads out of one FIB of 32 bytes (CRC taken as good),
     or None -- the walk of k_fic_frame and of the ETI writer (csrc/fig00.h)."""

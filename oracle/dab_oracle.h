@@ -257,8 +257,17 @@ typedef struct {
   int32_t *fic_ber_bits;   /* n_frames : FicDecoder::mFicBits / mFicErrors after the frame's four FIC blocks (fic_decoder.cpp:199-210) */
   int32_t *fic_ber_errors;
   float   *mer_db;        /* n_frames : MER of the LCD statistics after symbol 75, ofdm_decoder.cpp:331-340 */
+  /* the front capture (NULL unless ora_rx_enable_front_capture): what the frame chain itself computes, tests/front_cases.py */
+  int32_t *front_phase_sym1;  /* n_frames : SampleReader's oscillator phase (cur_phase) before the first sample of symbol 1 ... */
+  int32_t *front_phase_end;   /* n_frames : ... and after the null symbol's last */
+  int32_t *front_f_sym;       /* n_frames : the integer frequency of symbols 1..75, round(fbb), sample_reader.cpp:211 ... */
+  int32_t *front_f_null;      /* n_frames : ... and of the null symbol, round(fbb_end) */
+  float   *front_fc;          /* n_frames * 2 : the cyclic-prefix correlation (re, im) summed over symbols 1..75, dab_processor.cpp:330-333 */
+  int32_t *front_is_tii;      /* n_frames : the null symbol went into the TII sum, :274 */
+  ora_cf32 *front_spectra;    /* level 2 only: n_frames * 77 * 2048 : FFT outputs of symbols 0..75 and ([76]) of the null symbol, bin order */
 } ora_rx_capture;
 void ora_rx_enable_soft_capture(ora_receiver *r, int on);
+void ora_rx_enable_front_capture(ora_receiver *r, int level);   /* before ora_rx_run: 0 off (default), 1 the scalars, 2 the spectra too (10 MB per 8 frames) */
 const ora_rx_capture *ora_rx_get_capture(ora_receiver *r);
 int ora_rx_run_spectra(ora_receiver *r, const ora_cf32 *spectra, const ora_cf32 *nulls, const float *clock_err, int n_frames);   /* per-symbol class calls on given FFT outputs */
 int ora_rx_take_tii(ora_receiver *r, ora_cf32 *out2048);   /* TII null-symbol sum + count since the last call */

@@ -29,6 +29,7 @@ struct ora_receiver {
   ora_cf32 tii_acc[ORA_TU]; int tii_count;
   /* capture */
   ora_rx_capture cap; int cap_alloc; int want_soft;
+  int want_front;                    /* ora_rx_enable_front_capture: 1 the frame chain's scalars, 2 its spectra too */
   /* event trace of the state machine (ora_rx_enable_trace): test bookkeeping, never read by the receiver itself */
   ora_trace_event *trace; int trace_max, trace_n;
   int margin;                        /* comparisons of time_sync within 1e-4 (relative) of their threshold so far */
@@ -254,11 +255,14 @@ void ora_rx_destroy(ora_receiver *r)
   free(r->cap.fbb_end); free(r->cap.clock_err); free(r->cap.fic_ratio); free(r->cap.snr_db); free(r->cap.fic_overflow); free(r->cap.msc_overflow);
   free(r->cap.s_level); free(r->cap.peak_level); free(r->cap.fic_ber_bits); free(r->cap.fic_ber_errors);
   free(r->cap.mer_db);
+  free(r->cap.front_phase_sym1); free(r->cap.front_phase_end); free(r->cap.front_f_sym); free(r->cap.front_f_null);
+  free(r->cap.front_fc); free(r->cap.front_is_tii); free(r->cap.front_spectra);
   free(r->trace);
   free(r);
 }
 
 void ora_rx_enable_soft_capture(ora_receiver *r, int on) { r->want_soft = on; }
+void ora_rx_enable_front_capture(ora_receiver *r, int level) { r->want_front = level < 0 ? 0 : (level > 2 ? 2 : level); }
 const ora_rx_capture *ora_rx_get_capture(ora_receiver *r) { return &r->cap; }
 ora_backend *ora_rx_backend(ora_receiver *r, int i) { return (i >= 0 && i < r->n_back) ? &r->back[i] : NULL; }
 ora_fic *ora_rx_fic(ora_receiver *r) { return &r->fic; }
@@ -285,6 +289,15 @@ static void cap_reserve(ora_receiver *r, int n)
   r->cap.fic_ber_bits = (int32_t *)realloc(r->cap.fic_ber_bits, sizeof(int32_t) * (size_t)na);
   r->cap.fic_ber_errors = (int32_t *)realloc(r->cap.fic_ber_errors, sizeof(int32_t) * (size_t)na);
   if (r->want_soft) r->cap.soft = (int16_t *)realloc(r->cap.soft, sizeof(int16_t) * (size_t)na * 75 * ORA_2K);
+  if (r->want_front) {
+    r->cap.front_phase_sym1 = (int32_t *)realloc(r->cap.front_phase_sym1, sizeof(int32_t) * (size_t)na);
+    r->cap.front_phase_end = (int32_t *)realloc(r->cap.front_phase_end, sizeof(int32_t) * (size_t)na);
+    r->cap.front_f_sym = (int32_t *)realloc(r->cap.front_f_sym, sizeof(int32_t) * (size_t)na);
+    r->cap.front_f_null = (int32_t *)realloc(r->cap.front_f_null, sizeof(int32_t) * (size_t)na);
+    r->cap.front_fc = (float *)realloc(r->cap.front_fc, sizeof(float) * 2 * (size_t)na);
+    r->cap.front_is_tii = (int32_t *)realloc(r->cap.front_is_tii, sizeof(int32_t) * (size_t)na);
+    if (r->want_front > 1) r->cap.front_spectra = (ora_cf32 *)realloc(r->cap.front_spectra, sizeof(ora_cf32) * (size_t)na * 77 * ORA_TU);
+  }
   r->cap_alloc = na;
 }
 
@@ -322,6 +335,8 @@ static int process_rest_of_frame(ora_receiver *r, int *sample_count, int frame_n
   memcpy(fin, r->buf, sizeof(fin));
   ora_fft2048(fin, fout, 0);
   ora_demap_store_ref(&r->dm, fout);                              /* :199-202 */
+  ora_cf32 *const fspec = r->want_front > 1 ? &r->cap.front_spectra[(size_t)frame_no * 77 * ORA_TU] : NULL;
+  if (fspec) memcpy(fspec, fout, sizeof(fout));
 
   int correction = 0;
   if (r->fic.success_ratio * 10 < 30) {                           /* :205-224 */
@@ -339,6 +354,10 @@ static int process_rest_of_frame(ora_receiver *r, int *sample_count, int frame_n
   /* _process_ofdm_symbols_1_to_L, :304-367 */
   float fc_re = 0, fc_im = 0;
   r->cap.fic_overflow[frame_no] = r->cap.msc_overflow[frame_no] = 0;
+  if (r->want_front) {                                            /* the oscillator as symbol 1's first sample finds it, and its step */
+    r->cap.front_phase_sym1[frame_no] = r->cur_phase;
+    r->cap.front_f_sym[frame_no] = (int32_t)roundf(r->freq_offs_bb);
+  }
   for (int sym = 1; sym < ORA_L; sym++) {
     if (!get_samples(r, r->buf, ORA_TS, r->freq_offs_bb)) return 0;
     *sample_count += ORA_TS;
@@ -349,6 +368,7 @@ static int process_rest_of_frame(ora_receiver *r, int *sample_count, int frame_n
     }
     memcpy(fin, &r->buf[ORA_TG], sizeof(fin));
     ora_fft2048(fin, fout, 0);
+    if (fspec) memcpy(&fspec[(size_t)sym * ORA_TU], fout, sizeof(fout));
     const long long ovf0 = r->dm.overflow_count;
     ora_demap_symbol(&r->dm, fout, r->clock_err, r->bits);        /* :342 */
     if (sym <= 3) r->cap.fic_overflow[frame_no] += (int32_t)(r->dm.overflow_count - ovf0);
@@ -359,6 +379,7 @@ static int process_rest_of_frame(ora_receiver *r, int *sample_count, int frame_n
   }
   r->cap.snr_db[frame_no] = ora_demap_snr_db(&r->dm);
   r->cap.mer_db[frame_no] = ora_demap_mer_db(&r->dm);
+  if (r->want_front) { r->cap.front_fc[2 * frame_no] = fc_re; r->cap.front_fc[2 * frame_no + 1] = fc_im; }
   r->phase_offs_cp = atan2f(fc_im, fc_re);                        /* :366 */
 
   limit_sym(&r->phase_offs_cp, 20.0f * (float)(M_PI / 180.0));    /* :240-242 */
@@ -371,6 +392,12 @@ static int process_rest_of_frame(ora_receiver *r, int *sample_count, int frame_n
   const int is_tii = (r->fic.cif_count & 7) >= 4;
   memcpy(fin, &r->buf[ORA_TG], sizeof(fin));
   ora_fft2048(fin, fout, 0);
+  if (fspec) memcpy(&fspec[(size_t)76 * ORA_TU], fout, sizeof(fout));
+  if (r->want_front) {
+    r->cap.front_phase_end[frame_no] = r->cur_phase;
+    r->cap.front_f_null[frame_no] = (int32_t)roundf(r->freq_offs_bb);
+    r->cap.front_is_tii[frame_no] = is_tii;
+  }
   if (!is_tii) ora_demap_store_null(&r->dm, fout);
   else {                                                          /* :282-300 add_to_tii_buffer */
     for (int i = 0; i < ORA_TU; i++) { r->tii_acc[i].re += fout[i].re; r->tii_acc[i].im += fout[i].im; }

@@ -32,7 +32,10 @@ class RxCapture(C.Structure):
                 ("snr_db", C.POINTER(C.c_float)), ("fic_overflow", C.POINTER(C.c_int32)), ("msc_overflow", C.POINTER(C.c_int32)),
                 ("s_level", C.POINTER(C.c_float)), ("peak_level", C.POINTER(C.c_float)),
                 ("fic_ber_bits", C.POINTER(C.c_int32)), ("fic_ber_errors", C.POINTER(C.c_int32)),
-                ("mer_db", C.POINTER(C.c_float))]
+                ("mer_db", C.POINTER(C.c_float)),
+                ("front_phase_sym1", C.POINTER(C.c_int32)), ("front_phase_end", C.POINTER(C.c_int32)),
+                ("front_f_sym", C.POINTER(C.c_int32)), ("front_f_null", C.POINTER(C.c_int32)), ("front_fc", C.POINTER(C.c_float)),
+                ("front_is_tii", C.POINTER(C.c_int32)), ("front_spectra", C.POINTER(C.c_float))]
 
 
 class TraceEvent(C.Structure):
@@ -118,6 +121,7 @@ def _prototypes(L):
     L.ora_rx_configure.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_int]
     L.ora_rx_run.argtypes = [C.c_void_p, _c64p, C.c_size_t, C.c_int]
     L.ora_rx_enable_soft_capture.argtypes = [C.c_void_p, C.c_int]
+    L.ora_rx_enable_front_capture.argtypes = [C.c_void_p, C.c_int]
     L.ora_rx_set_dc_iq.argtypes = [C.c_void_p, C.c_int]
     L.ora_dciq_buffer.argtypes = [_c64p, C.c_size_t, C.c_int, np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")]
     L.ora_dciq_buffer_f64.argtypes = [_c64p, C.c_size_t, C.c_int, np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")]
@@ -405,14 +409,17 @@ def oracle_trace(x, threshold=3.0, strongest=0, variant=0, max_events=1 << 16):
     return tr
 
 
-def oracle_run(x, subch, want_soft=False, config=None, trace=0):
+def oracle_run(x, subch, want_soft=False, config=None, trace=0, front=0, front_frames=None):
     """The oracle receiver on IQ x: per frame the FIBs, CRC flags and receiver scalars, per sub-channel the back end's results.
-    trace = n: also res["trace"], up to n events of its state machine."""
+    trace = n: also res["trace"], up to n events of its state machine.  front = 1: also the frame chain's own scalars (phase_sym1,
+    phase_end, f_sym, f_null, fc, is_tii); front = 2: and res["spectra"] = {frame: [77, 2048] complex64} (symbols 0..75, the null
+    symbol) of the frames in front_frames (default: all)."""
     L = oracle()
     rx = L.ora_rx_create(make_descs(subch), len(subch))
     if config:
         L.ora_rx_configure(rx, *config)
     L.ora_rx_enable_soft_capture(rx, int(want_soft))
+    L.ora_rx_enable_front_capture(rx, int(front))
     if trace:
         L.ora_rx_enable_trace(rx, trace)
     n = L.ora_rx_run(rx, x, len(x), 10000)
@@ -436,6 +443,13 @@ def oracle_run(x, subch, want_soft=False, config=None, trace=0):
         res["soft"] = np.ctypeslib.as_array(cap.soft, (n, 75, 3072)).copy()
     if trace:
         res["trace"] = tr
+    if front:
+        for k, p, w in (("phase_sym1", cap.front_phase_sym1, 1), ("phase_end", cap.front_phase_end, 1), ("f_sym", cap.front_f_sym, 1),
+                        ("f_null", cap.front_f_null, 1), ("fc", cap.front_fc, 2), ("is_tii", cap.front_is_tii, 1)):
+            res[k] = np.ctypeslib.as_array(p, (n, w) if w > 1 else (n,)).copy() if n else np.zeros((0, w) if w > 1 else (0,))
+    if front > 1:
+        spec = np.ctypeslib.as_array(cap.front_spectra, (n, 77, 2048, 2)) if n else None
+        res["spectra"] = {f: spec[f].copy().view(np.complex64)[..., 0] for f in (range(n) if front_frames is None else front_frames) if f < n}
     L.ora_rx_destroy(rx)
     return res
 

@@ -16,6 +16,15 @@ def test_library_exports_every_declared_symbol():
     assert L.dabx_abi_version() == 6
 
 
+def test_library_exports_the_internal_test_entries():
+    """The stage tests' entries (not part of include/dabx.h, mirrored in dabstar_amd/lib.py) are exported all the same."""
+    L = dx.load()
+    names = ["dabx_internal_msc_inject", "dabx_internal_msc_decode", "dabx_internal_fic_inject", "dabx_internal_fic_decode",
+             "dabx_internal_demap_inject", "dabx_internal_demap_frame", "dabx_internal_front_read"]
+    assert not [n for n in names if not hasattr(L, n)]
+    assert not [n for n in names if n in dx.declared_symbols()]
+
+
 def test_fails_loudly_without_device():
     import numpy as np
     L = dx.load()
