@@ -2,6 +2,7 @@
 #include <algorithm>
 #include "dabx_internal.h"
 #include "eti_core.h"
+#include "tii_core.h"
 #include <cstring>
 
 namespace dabx { const char *last_error(); }
@@ -181,6 +182,34 @@ int dabx_eti_frames_device(int n, const int32_t *cif_hi, const int32_t *cif_lo, 
   DABX_HIP(hipStreamSynchronize(0));
   if ((rc = dout.to_host(out, (size_t)DABX_ETI_FRAME_BYTES * N))) return rc;
   return dused.to_host(used, 4 * N);
+}
+
+// The TII detector on the device: tii_detect (tii_core.h), the body of the engine's k_tii, one block per detector
+int dabx_tii_process_device(int n, const float *sums, float *pairs, const dabx_tii_config *cfg, dabx_tii_result *out, int32_t *n_results, int32_t *n_found)
+{
+  if (n <= 0 || !sums || !pairs || !cfg || !out || !n_results || !n_found) { set_error("dabx_tii_process_device: bad argument"); return DABX_E_ARG; }
+  int rc = need_device();
+  if (rc) return rc;
+  const size_t N = (size_t)n;
+  std::vector<TiiCfgDev> c(N);
+  for (size_t d = 0; d < N; d++) {
+    const int thr = cfg[d].threshold_db ? cfg[d].threshold_db : 8;
+    c[d] = TiiCfgDev{cfg[d].enable ? 1 : 0, 1, thr, cfg[d].collisions ? 1 : 0, cfg[d].collision_sub_id, 0, tii_factor(thr), 0};
+  }
+  uint8_t tab[TII_PAIRS + 72];
+  tii_tables_host(tab, tab + TII_PAIRS);
+  // (the outputs travel both ways: a detector with enable = 0 leaves its rows as the caller has them)
+  DevBuf dsum, dpairs, dcfg, dtab, dout, dnr, dnf;
+  if ((rc = dsum.from_host(sums, sizeof(float2) * TU * N)) || (rc = dpairs.from_host(pairs, sizeof(float2) * TII_PAIRS * N)) ||
+      (rc = dcfg.from_host(c.data(), sizeof(TiiCfgDev) * N)) || (rc = dtab.from_host(tab, sizeof(tab))) ||
+      (rc = dout.from_host(out, sizeof(dabx_tii_result) * DABX_TII_MAX_RESULTS * N)) || (rc = dnr.from_host(n_results, 4 * N)) ||
+      (rc = dnf.from_host(n_found, 4 * N))) return rc;
+  if ((rc = launch_tii_batch(n, dsum.as<float2>(), dpairs.as<float2>(), dcfg.as<TiiCfgDev>(), dtab.as<uint8_t>(), dtab.as<uint8_t>() + TII_PAIRS,
+                             dout.as<dabx_tii_result>(), dnr.as<int32_t>(), dnf.as<int32_t>(), 0))) return rc;
+  DABX_HIP(hipStreamSynchronize(0));
+  if ((rc = dpairs.to_host(pairs, sizeof(float2) * TII_PAIRS * N)) || (rc = dout.to_host(out, sizeof(dabx_tii_result) * DABX_TII_MAX_RESULTS * N)) ||
+      (rc = dnr.to_host(n_results, 4 * N))) return rc;
+  return dnf.to_host(n_found, 4 * N);
 }
 
 int dabx_fft2048(const dabx_cf32 *in, int batch, int inverse, dabx_cf32 *out)

@@ -11,6 +11,7 @@
 #include "mot_core.h"
 #include "carousel_core.h"
 #include "eti_core.h"
+#include "tii_core.h"
 #include "fig00.h"
 
 namespace dabx {
@@ -271,6 +272,40 @@ int launch_deliver_front(const EngineDev &e, const DeliverDev &dv, hipStream_t s
   return 0;
 }
 
+// The TII section (include/dabx.h, dabx_chunk_tii; pipeline.h, TiiDeliverDev).  grid = n_streams, 128 threads, front-end stream, behind
+// k_deliver_front -- so behind the k_tii of the chunk's last frame: the events the stream's detector has completed since the previous chunk,
+// the newest 4 of them (a chunk's frames cannot complete more), out of the detector's ring.  Block 0 writes the header's extension.
+__global__ __launch_bounds__(128) void k_deliver_tii(EngineDev e, TiiDeliverDev td)
+{
+  const int s = blockIdx.x, tid = threadIdx.x;
+  constexpr int CAP = 4, SLOT_DW = DABX_TII_EVENT_SLOT_BYTES / 4;
+  if (s == 0 && tid == 0) *reinterpret_cast<dabx_chunk_header_ext *>(td.slab + sizeof(dabx_chunk_header)) = td.ext;
+  const long long total = td.ring ? td.events[(size_t)s * td.cnt_stride] : 0, have = total - td.done[s];
+  int n = (int)(have < CAP ? have : CAP);
+  if (n < 0) n = 0;
+  const long long first = total - n;
+  const unsigned long long ev_off = td.ext.off_tii + (unsigned long long)e.n_streams * sizeof(dabx_chunk_tii) + (unsigned long long)s * CAP * DABX_TII_EVENT_SLOT_BYTES;
+  if (tid == 0) {
+    dabx_chunk_tii r;
+    r.first_event = first; r.n_events = n; r.events_lost = (int)(have > n ? have - n : 0); r.ev_off = ev_off; r.events_total = total;
+    reinterpret_cast<dabx_chunk_tii *>(td.slab + td.ext.off_tii)[s] = r;
+  }
+  uint32_t *o = reinterpret_cast<uint32_t *>(td.slab + ev_off);
+  for (int i = tid; i < n * SLOT_DW; i += 128) {
+    const int k = i / SLOT_DW, wd = i - k * SLOT_DW;
+    o[i] = reinterpret_cast<const uint32_t *>(td.ring + ((size_t)s * TII_RING + (size_t)((first + k) % TII_RING)) * DABX_TII_EVENT_SLOT_BYTES)[wd];
+  }
+  __syncthreads();
+  if (tid == 0) td.done[s] = total;
+}
+
+int launch_deliver_tii(const EngineDev &e, const TiiDeliverDev &td, hipStream_t st)
+{
+  hipLaunchKernelGGL(k_deliver_tii, dim3(e.n_streams), dim3(128), 0, st, e, td);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+
 // with_lf: no launch_deliver_lf went in front (the logical frames are gathered here too)
 int launch_deliver_msc(const EngineDev &e, const DeliverDev &dv, hipStream_t st, bool with_lf)
 {
@@ -462,6 +497,72 @@ int launch_eti_frames(int n, const int32_t *cif_hi, const int32_t *cif_lo, const
                       const int32_t *off, int sum_dw, const uint32_t *fic, const uint32_t *msc, uint32_t *out, int32_t *used, hipStream_t st)
 {
   hipLaunchKernelGGL(k_eti_frames, dim3(n), dim3(64), 0, st, cif_hi, cif_lo, minor, n_subch, stc, ndw, off, sum_dw, fic, msc, out, used);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---- the TII detector on the device (tii_core.h): k_tii, the engine's stage behind the frame tail (include/dabx.h, dabx_set_tii_mode), and
+// k_tii_batch, the same device function on crafted sums (dabx_tii_process_device) ----
+// grid = n_streams, 256 threads, front-end stream, behind k_frame_tail of the same step: the next frame's accumulation cannot start before
+// this kernel has finished.  A block has work only in the step whose TII null symbol brought its stream's sum to min_frames -- when
+// DabProcessor runs process_tii_data (dab_processor.cpp:287-300).  A stream that is out of lock has no frame in the step (frame_ok = 0); its
+// sum and count belong to the search (k_acquire), which may be running on its own HIP stream, and are not looked at.
+__global__ __launch_bounds__(256) void k_tii(EngineDev e, TiiDev t)
+{
+  __shared__ TiiLds w;
+  const int s = blockIdx.x, tid = threadIdx.x;
+  const TiiCfgDev cfg = t.cfg[s];
+  if (!cfg.enable) return;
+  const StreamCtl &c = e.ctl[s];
+  if (!c.frame_ok || (c.cif_count & 7) < 4) return;          // no frame in this step, or its null symbol was not a TII one (:274)
+  const int in_sum = e.tii_cnt[2 * s], epoch = e.tii_cnt[2 * s + 1];
+  if (in_sum < cfg.min_frames) return;
+  float2 *pairs = t.pairs + (size_t)s * TII_PAIRS;
+  const bool reset = epoch != cfg.epoch_seen;                 // the lock was lost since the detector last ran: TiiDetector::reset clears both buffers (:149-153)
+  if (reset) for (int i = tid; i < TII_PAIRS; i += 256) pairs[i] = make_float2(0.f, 0.f);   // (each thread clears the pairs it advances below)
+  const TiiCounters n = t.cnt[s];
+  uint8_t *slot = t.ring + ((size_t)s * TII_RING + (size_t)(n.events % TII_RING)) * TII_SLOT_BYTES;
+  dabx_tii_result *res = reinterpret_cast<dabx_tii_result *>(slot + sizeof(dabx_tii_event));
+  const int found = tii_detect(e.tii_acc + (size_t)s * TU, pairs, cfg, t.turn, t.pattern, res, w, tid);
+  const int stored = found < DABX_TII_MAX_RESULTS ? found : DABX_TII_MAX_RESULTS;
+  if (tid >= stored && tid < DABX_TII_MAX_RESULTS) {          // the rest of the slot: zeros, whatever an older event left there
+    uint32_t *z = reinterpret_cast<uint32_t *>(res + tid);
+    z[0] = z[1] = z[2] = z[3] = 0;
+  }
+  if (tid == 0) {
+    dabx_tii_event ev;
+    ev.frame = c.frames - 1;                                  // (the tail has counted the frame)
+    ev.n_results = stored; ev.n_found = found; ev.frames_in_sum = in_sum; ev.epoch = epoch; ev.threshold_db = cfg.threshold_db; ev.reserved = 0;
+    *reinterpret_cast<dabx_tii_event *>(slot) = ev;
+    e.tii_cnt[2 * s] = 0;                                     // mTiiCounter = 0
+    if (reset) t.cfg[s].epoch_seen = epoch;
+    t.cnt[s] = TiiCounters{n.events + 1, n.results + stored, n.truncated + (found > stored ? 1 : 0), n.resets + (reset ? 1 : 0)};
+  }
+}
+
+int launch_tii(const EngineDev &e, const TiiDev &t, hipStream_t st)
+{
+  hipLaunchKernelGGL(k_tii, dim3(e.n_streams), dim3(256), 0, st, e, t);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+
+// grid = n detectors, 256 threads
+__global__ __launch_bounds__(256) void k_tii_batch(float2 *sums, float2 *pairs, const TiiCfgDev *cfg, const uint8_t *turn, const uint8_t *pattern,
+                                                   dabx_tii_result *out, int32_t *n_results, int32_t *n_found)
+{
+  __shared__ TiiLds w;
+  const int d = blockIdx.x, tid = threadIdx.x;
+  const TiiCfgDev c = cfg[d];
+  if (!c.enable) return;
+  const int found = tii_detect(sums + (size_t)d * TU, pairs + (size_t)d * TII_PAIRS, c, turn, pattern, out + (size_t)d * DABX_TII_MAX_RESULTS, w, tid);
+  if (tid == 0) { n_found[d] = found; n_results[d] = found < DABX_TII_MAX_RESULTS ? found : DABX_TII_MAX_RESULTS; }
+}
+
+int launch_tii_batch(int n, float2 *sums, float2 *pairs, const TiiCfgDev *cfg, const uint8_t *turn, const uint8_t *pattern, dabx_tii_result *out,
+                     int32_t *n_results, int32_t *n_found, hipStream_t st)
+{
+  hipLaunchKernelGGL(k_tii_batch, dim3(n), dim3(256), 0, st, sums, pairs, cfg, turn, pattern, out, n_results, n_found);
   DABX_HIP(hipGetLastError());
   return 0;
 }

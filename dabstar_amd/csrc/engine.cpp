@@ -364,6 +364,7 @@ void dabx_destroy(dabx_engine *e)
   delivery_free(e);
   ingest_free(e);
   for (dabx_tii *t : e->tii) dabx_tii_destroy(t);
+  tii_stage_free(e);
   for (dabx_fibdec *f : e->fibdec) dabx_fibdec_destroy(f);
   if (e->ingest) { (void)hipStreamSynchronize(e->ingest); (void)hipStreamDestroy(e->ingest); }
   if (e->ingest2) { (void)hipStreamSynchronize(e->ingest2); (void)hipStreamDestroy(e->ingest2); }
@@ -801,6 +802,11 @@ int dabx_process(dabx_engine *e, int max_frames, int sync)
     const bool all_locked = e->locked_host && __atomic_load_n(e->locked_host, __ATOMIC_RELAXED) == e->dev.n_streams;
     int rc = launch_front_step(e->dev, e->ss, e->mk, async_acquire, all_locked);
     if (rc) return rc;
+    // the TII detectors of the streams that have the mode on (deliver.hip): behind the frame tail, in front of the next frame's accumulation
+    if (e->tiis.n_on > 0) {
+      if ((rc = launch_tii(e->dev, e->tiis.dev, e->stream))) return rc;
+      e->tiis.launches++;
+    }
     e->level_dirty = true;
     if (++e->pending_frames == MSC_BATCH_FRAMES || i == max_frames - 1) {
       DeliverDev dv{};
@@ -1002,6 +1008,10 @@ int dabx_read_tii(dabx_engine *e, int stream, int min_frames, int threshold_db, 
 {
   if (!e || stream < 0 || stream >= e->dev.n_streams || (!out && max_out > 0) || max_out < 0) return DABX_E_ARG;
   if (!e->dev.tii_acc) { set_error("dabx_read_tii: engine has no TII accumulator"); return DABX_E_STATE; }
+  if (e->tiis.exists() && e->tiis.cfg[(size_t)stream].enable) {
+    set_error("dabx_read_tii: stream %d runs its detector on the device (dabx_set_tii_mode), which owns the sum: dabx_read_tii_events", stream);
+    return DABX_E_STATE;
+  }
   if (int rc = sync_all(e)) return rc;
   int32_t cnt[2];
   DABX_HIP(hipMemcpy(cnt, e->dev.tii_cnt + 2 * stream, sizeof(cnt), hipMemcpyDeviceToHost));

@@ -5,6 +5,7 @@
 #include "pad_core.h"
 #include "mot_core.h"
 #include "carousel_core.h"
+#include "tii_core.h"
 #include "sdma.h"
 #include "iqfile.h"
 #include <algorithm>
@@ -60,6 +61,10 @@ struct Delivery {
   long long *eti_next = nullptr;
   EtiStage *eti_stage[NDEV] = {nullptr, nullptr, nullptr};
   size_t eti_rows_off = 0;
+  // DABX_DELIVER_TII (deliver.hip, k_deliver_tii): the header's extension as it goes into a slab, the section's cursor per stream; zeros / null without the bit
+  dabx_chunk_header_ext ext{};
+  long long *tii_done = nullptr;
+  bool tii() const { return (what & DABX_DELIVER_TII) != 0; }
   bool eti() const { return (what & DABX_DELIVER_ETI) != 0; }
   EtiDev eti_dev(int devslab) const
   {
@@ -147,6 +152,18 @@ template <class Slot, class Dev> struct JobTable {
   }
 };
 
+// The TII stage (include/dabx.h dabx_set_tii_mode, deliver.hip k_tii).  Nothing of it exists until the mode is first switched on: dev stays all
+// null, n_on stays 0 and no step launches the kernel.
+struct TiiStage {
+  TiiDev dev{};
+  uint8_t *tables = nullptr;                   // turn [768] + pattern [72]
+  int n_on = 0;                                // streams with the mode on
+  std::vector<TiiCfgDev> cfg;                  // [S] mirror of dev.cfg but for epoch_seen, which the device owns
+  std::vector<long long> seen;                 // [S] events dabx_read_tii_events has returned or passed
+  long long launches = 0;
+  bool exists() const { return dev.pairs != nullptr; }
+};
+
 struct dabx_engine : dabx::EngineHead {          // (iqfile.h: the ring format, where iqfile.cpp can read it)
   dabx_config cfg{};
   EngineDev dev{};
@@ -164,6 +181,7 @@ struct dabx_engine : dabx::EngineHead {          // (iqfile.h: the ring format, 
   bool fig_reference_quirks = false;           // dabx_set_fig_reference_quirks: the engine's own FIB decoders swap like the reference (flags 3 only)
   std::vector<dabx_tii *> tii;                 // [S] detectors, created on first dabx_read_tii
   std::vector<int> tii_epoch;                  // [S] reset epoch seen by the detector
+  TiiStage tiis;                               // the detectors on the device
   std::vector<void *> allocs;
   void *stage = nullptr;                       // host -> device staging of dabx_push_iq
   size_t stage_cap = 0;
@@ -238,6 +256,8 @@ int delivery_drain(dabx_engine *e);
 void delivery_free(dabx_engine *e);
 // engine_ingest.cpp
 void ingest_free(dabx_engine *e);
+// engine_tii.cpp
+void tii_stage_free(dabx_engine *e);
 // engine_slots.cpp
 void pad_count_sources(dabx_engine *e);
 int mot_follow_pad(dabx_engine *e);

@@ -11,7 +11,8 @@
 // ---- bulk delivery (include/dabx.h "Bulk delivery", deliver.hip) -------------------------------------------------------
 // the slab's records are ABI: hosts and the python binding (dabstar_amd/lib.py, CHUNK_*) parse them by these sizes
 static_assert(sizeof(dabx_chunk_header) == 128 && sizeof(dabx_chunk_stream) == 72 && sizeof(dabx_chunk_frame) == 16 && sizeof(dabx_chunk_subch) == 144 && offsetof(dabx_chunk_header, off_mot) == 112 &&
-              sizeof(dabx_superframe_info) == 32 && sizeof(dabx_chunk_eti) == 64 && offsetof(dabx_chunk_header, off_eti) == 120,
+              sizeof(dabx_superframe_info) == 32 && sizeof(dabx_chunk_eti) == 64 && offsetof(dabx_chunk_header, off_eti) == 120 &&
+              sizeof(dabx_chunk_header_ext) == 64 && sizeof(dabx_chunk_tii) == 32 && sizeof(dabx_tii_event) == 32 && sizeof(dabx_tii_result) == 16,
               "include/dabx.h: chunk record layout");
 static constexpr int DL_SF_CAP = (4 * DL_FRAMES + 4) / 5;          // super frames one chunk can complete (4 CIFs may be waiting from before)
 #if DABX_MSC_BATCH == 7
@@ -57,6 +58,8 @@ int dabx_engine::delivery_layout()
   h.magic = DABX_CHUNK_MAGIC; h.abi = DABX_ABI_VERSION;
   h.n_streams = d.n_streams; h.max_subch = d.max_subch; h.max_frames = DL_FRAMES; h.what = D.what;
   size_t off = sizeof(dabx_chunk_header);
+  dabx_chunk_header_ext x{};
+  if (D.what & ~255) { x.magic = DABX_CHUNK_EXT_MAGIC; x.bytes = sizeof(x); off += sizeof(x); }     // a bit the header has no word for: its extension follows it
   h.off_stream = off; off = align_up(off + S * sizeof(dabx_chunk_stream), 16);
   h.off_subch = off; off = align_up(off + S * M * sizeof(dabx_chunk_subch), 16);
   const bool fib = (D.what & DABX_DELIVER_FIB) != 0;
@@ -86,6 +89,8 @@ int dabx_engine::delivery_layout()
   off = layout_section(car, D.want_mot && !d.fic_only, off, S * M * sizeof(dabx_chunk_mot), &h.off_mot);     // ... with the rooms of the carousel slots
   if (h.off_mot) h.what |= DABX_DELIVER_MOT;
   if (D.eti()) { off = align_up(off, 16); h.off_eti = off; off += S * sizeof(dabx_chunk_eti); }     // the ETI section's table (its rows: the slab's end)
+  // the TII section: its table and 4 event slots per stream
+  if (D.tii()) { off = align_up(off, 16); x.off_tii = off; off += S * (sizeof(dabx_chunk_tii) + 4 * (size_t)DABX_TII_EVENT_SLOT_BYTES); }
   off = align_up(off, 256);
   h.off_msc = off;
   if ((D.what & (DABX_DELIVER_MSC | DABX_DELIVER_MSC_NOT_DABPLUS)) && !d.fic_only)
@@ -104,6 +109,7 @@ int dabx_engine::delivery_layout()
     return DABX_E_NOMEM;
   }
   D.hdr = h;
+  D.ext = x;
   D.bytes = off;
   if (!pkt.host.empty()) if (int rc = pkt.upload()) return rc;
   if (!pad.host.empty()) if (int rc = pad.upload()) return rc;
@@ -160,6 +166,10 @@ int dabx_engine::delivery_begin(DeliverDev *dv, int *slot, int *devslab)
   int rc = launch_deliver_front(dev, *dv, stream);
   // the ETI stage's front half: the FIB ring is the front end's, which rewrites it while the chunk's MSC batch is decoded
   if (!rc && D.eti()) rc = launch_eti_front(dev, D.eti_dev(*devslab), stream, mk);
+  // the TII section: behind the k_tii of the chunk's last frame, which the front-end stream has run by now
+  if (!rc && D.tii())
+    rc = launch_deliver_tii(dev, TiiDeliverDev{D.dev[*devslab], D.ext, D.tii_done, tiis.dev.ring, tiis.exists() ? &tiis.dev.cnt->events : nullptr,
+                                               (int32_t)(sizeof(TiiCounters) / sizeof(long long)), 0}, stream);
   if (rc) {                                                        // nothing was queued: give the slabs back
     std::lock_guard<std::mutex> lk(D.mu);
     D.dev_busy[*devslab] = false;
@@ -298,7 +308,8 @@ void delivery_free(dabx_engine *e)
     D.dev[k] = nullptr; D.packed[k] = nullptr; D.packed_lf[k] = nullptr; D.dev_busy[k] = false;
   }
   for (void *q : {(void *)D.layout_off, (void *)D.subch_id, (void *)D.frames_done, (void *)D.cif_done, (void *)D.sf_done, (void *)D.eti_front,
-                  (void *)D.eti_next, (void *)D.eti_stage[0], (void *)D.eti_stage[1], (void *)D.eti_stage[2]}) if (q) (void)hipFree(q);
+                  (void *)D.eti_next, (void *)D.eti_stage[0], (void *)D.eti_stage[1], (void *)D.eti_stage[2], (void *)D.tii_done}) if (q) (void)hipFree(q);
+  D.tii_done = nullptr; D.ext = dabx_chunk_header_ext{};
   D.layout_off = nullptr; D.subch_id = nullptr; D.frames_done = D.cif_done = D.sf_done = nullptr;
   D.eti_front = nullptr; D.eti_next = nullptr; D.eti_rows_off = 0;
   for (int k = 0; k < Delivery::NDEV; k++) D.eti_stage[k] = nullptr;
@@ -315,8 +326,14 @@ extern "C" {
 
 int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
 {
-  if (!e || (cfg && (cfg->host_slabs < 0 || cfg->host_slabs == 1 || cfg->host_slabs > 64 || (cfg->what & ~255) || cfg->copy_engine < 0 || cfg->copy_engine > 1))) {
+  if (!e || (cfg && (cfg->host_slabs < 0 || cfg->host_slabs == 1 || cfg->host_slabs > 64 || (cfg->what & ~511) || cfg->copy_engine < 0 || cfg->copy_engine > 1))) {
     set_error("dabx_delivery_open: bad argument");
+    return DABX_E_ARG;
+  }
+  // DABX_DELIVER_TII adds its section to a delivery of something else.  Alone it names nothing a chunk is made of: the mask 256 stays the
+  // bad argument it was before the bit existed (a host that probes for bits it does not know sees no change)
+  if (cfg && cfg->what == DABX_DELIVER_TII) {
+    set_error("dabx_delivery_open: DABX_DELIVER_TII needs at least one other DABX_DELIVER_* bit beside it");
     return DABX_E_ARG;
   }
   if (e->dl.open) { set_error("dabx_delivery_open: already open"); return DABX_E_STATE; }
@@ -354,6 +371,7 @@ int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
   cap += section_capacity(e->pkt, S * M * sizeof(dabx_chunk_dg)) + section_capacity(e->pad, S * M * sizeof(dabx_chunk_pad)) +
          section_capacity(e->mot, S * M * sizeof(dabx_chunk_mot)) + section_capacity(e->car, S * M * sizeof(dabx_chunk_mot));
   if (D.eti()) cap += 16 + S * sizeof(dabx_chunk_eti) + 256 + S * 4 * F * DABX_ETI_FRAME_BYTES;      // ... and the ETI section: its table and 4 F rows per stream
+  if (D.tii()) cap += sizeof(dabx_chunk_header_ext) + 16 + S * (sizeof(dabx_chunk_tii) + 4 * (size_t)DABX_TII_EVENT_SLOT_BYTES);   // ... and the TII section
   D.capacity = align_up(cap, 4096);
 #define H(x) do { hipError_t err__ = (x); if (err__ != hipSuccess) { set_error("HIP error %d (%s) at %s:%d", (int)err__, hipGetErrorString(err__), __FILE__, __LINE__); delivery_free(e); return DABX_E_HIP; } } while (0)
   if (D.copy_engine == 1) H(hipStreamCreateWithFlags(&D.cs, hipStreamNonBlocking));
@@ -400,6 +418,17 @@ int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
         H(hipMalloc((void **)&D.eti_stage[k], sizeof(EtiStage) * S));
         H(hipMemset(D.eti_stage[k], 0, sizeof(EtiStage) * S));
       }
+    }
+    if (D.tii()) {
+      // the TII section's cursor: the events completed from now on
+      std::vector<long long> td(S, 0);
+      if (e->tiis.exists()) {
+        std::vector<TiiCounters> tc(S);
+        H(hipMemcpy(tc.data(), e->tiis.dev.cnt, sizeof(TiiCounters) * S, hipMemcpyDeviceToHost));
+        for (size_t s_ = 0; s_ < S; s_++) td[s_] = tc[s_].events;
+      }
+      H(hipMalloc((void **)&D.tii_done, sizeof(long long) * S));
+      H(hipMemcpy(D.tii_done, td.data(), sizeof(long long) * S, hipMemcpyHostToDevice));
     }
   }
 #undef H

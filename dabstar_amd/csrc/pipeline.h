@@ -204,6 +204,17 @@ struct EtiDev {
   int32_t max_frames, pad_;
 };
 
+// ---- the TII section of the delivery (deliver.hip k_deliver_tii, include/dabx.h dabx_chunk_tii): the events the detectors (deliver.hip, k_tii) have
+// completed since the previous chunk, out of their rings into the slab's head part; gathered at chunk close on the front-end stream
+struct TiiDeliverDev {
+  uint8_t *slab;
+  dabx_chunk_header_ext ext;              // as it goes into the slab
+  long long *done;                        // [S] events of the stream delivered or passed so far
+  const uint8_t *ring;                    // TiiDev::ring and ::cnt (tii_core.h), null while the engine has no TII stage: every stream delivers no event
+  const long long *events;                // &cnt[0].events, a TiiCounters apart
+  int32_t cnt_stride, pad_;               // ... in long longs
+};
+
 // ---- lane-per-trellis path of the MSC decoder (vit_t.hip) ------------------------------------------------------
 // The sub-channels of ALL streams are grouped into classes of equal protection profile (same depuncture map and
 // trellis length): the 64 lanes of a decoder wave then share the map and step count whatever ensemble they come from.
@@ -401,6 +412,7 @@ int launch_deliver_dg(const EngineDev &e, const DeliverDev &dv, const PacketDev 
 int launch_deliver_pad(const EngineDev &e, const DeliverDev &dv, const PadDev &pd, hipStream_t st);
 int launch_deliver_mot(const EngineDev &e, const DeliverDev &dv, const MotDev &md, hipStream_t st);
 int launch_deliver_carousel(const EngineDev &e, const DeliverDev &dv, const CarouselDev &cd, hipStream_t st, bool clear_table);
+int launch_deliver_tii(const EngineDev &e, const TiiDeliverDev &td, hipStream_t st);                // at chunk close, front-end stream, behind launch_deliver_front
 int launch_eti_front(const EngineDev &e, const EtiDev &t, hipStream_t st, Marker &mk);              // at chunk close, front-end stream
 int launch_eti_back(const EngineDev &e, const EtiDev &t, hipStream_t st, Marker &mk, bool pre);     // behind the batch's decode; pre: in front of its DAB+ stage
 // msc_stages.hip

@@ -6,6 +6,7 @@
 // (EN 300 401 table 43) and the phase turn of pair (k, k+1) is the phase-reference difference phi_k - phi_k+1.
 // Pinned against the reference's object code: tests/test_tii.py (oracle/_ref, golden fixture).
 #include "dabx_internal.h"
+#include "tii_core.h"
 #include <algorithm>
 #include <math.h>
 
@@ -44,6 +45,25 @@ struct dabx_tii {
   int coll_sub_id = 0;
 };
 
+// the two tables and the threshold factor for the device's detector (tii_core.h): made here, where the host detector's are
+namespace dabx {
+void tii_tables_host(uint8_t *turn, uint8_t *pattern)
+{
+  int n = 0;
+  for (int v = 0; v < 256 && n < 70; v++) if (__builtin_popcount(v) == 4) pattern[n++] = (uint8_t)v;
+  pattern[70] = pattern[71] = 0;
+  for (int i = 0; i < K / 2; i++) {
+    const int k = -K / 2 + 2 * i, c0 = k < 0 ? k : k + 1;
+    turn[i] = (uint8_t)((prs_quarter_turns(c0) - prs_quarter_turns(c0 + 1)) & 3);
+  }
+}
+float tii_factor(int threshold_db)
+{
+  volatile float ten = 10.0f;                               // as in dabx_tii_process: keeps powf from being rewritten as exp10f
+  return powf(ten, (float)threshold_db / 10.0f);
+}
+}  // namespace dabx
+
 static inline int pair_bin(int i) { const int k = -K / 2 + 2 * i; return k < 0 ? k + TU : k + 1; }   // fft_shift_skip_dc
 
 static cf quarter_turn(cf v, int q)      // tii_detector.cpp:282-297
@@ -62,12 +82,9 @@ int dabx_tii_create(dabx_tii **out)
 {
   if (!out) return DABX_E_ARG;
   dabx_tii *t = new dabx_tii();
-  int n = 0;
-  for (int v = 0; v < 256 && n < 70; v++) if (__builtin_popcount(v) == 4) t->pattern[n++] = (uint8_t)v;
-  for (int i = 0; i < K / 2; i++) {
-    const int k = -K / 2 + 2 * i, c0 = k < 0 ? k : k + 1;
-    t->turn[i] = (uint8_t)((prs_quarter_turns(c0) - prs_quarter_turns(c0 + 1)) & 3);
-  }
+  uint8_t pattern[72];
+  tii_tables_host(t->turn, pattern);
+  std::copy(pattern, pattern + 70, t->pattern);
   *out = t;
   return 0;
 }

@@ -381,6 +381,16 @@ class TiiResult(C.Structure):
         return (self.main_id, self.sub_id, self.strength, self.phase_deg, self.non_etsi_phase)
 
 
+class TiiConfig(C.Structure):
+    _fields_ = [("enable", C.c_int32), ("min_frames", C.c_int32), ("threshold_db", C.c_int32), ("collisions", C.c_int32),
+                ("collision_sub_id", C.c_int32), ("reserved", C.c_int32 * 3)]          # dabx_tii_config
+
+
+def _tii_tuples(res):
+    """TII_RESULT records -> the tuples TiiResult.as_tuple gives"""
+    return [(int(r["main_id"]), int(r["sub_id"]), float(r["strength"]), float(r["phase_deg"]), int(r["non_etsi_phase"])) for r in res]
+
+
 class Tii:
     """Host-side TII detector (dabx_tii_*): TiiDetector of the reference."""
 
@@ -456,6 +466,20 @@ ETI_FRAME_BYTES = 6144
 CHUNK_ETI = np.dtype([("first_cif", "<i8"), ("n_eti", "<i4"), ("cifs_lost", "<i4"), ("cifs_waiting", "<i4"), ("cifs_refused", "<i4"),
                       ("cif_hi", "<i4"), ("cif_lo", "<i4"), ("rows_off", "<u8"), ("fib_frames", "<i8"), ("reserved", "<u8", 2)])
 assert CHUNK_ETI.itemsize == 64
+# the TII section (DELIVER_TII, opt-in like DELIVER_ETI): announced by the header's extension, which follows the header when `what` has a
+# bit >= 256; one CHUNK_TII per stream, then 4 event slots per stream (a TII_EVENT + TII_MAX_RESULTS TII_RESULT records each)
+DELIVER_TII = 256
+TII_MAX_RESULTS = 32
+CHUNK_EXT_MAGIC = 0x45584244                     # "DBXE"
+CHUNK_HEADER_EXT = np.dtype([("magic", "<u4"), ("bytes", "<u4"), ("off_tii", "<u8"), ("reserved", "<u8", 6)])
+CHUNK_TII = np.dtype([("first_event", "<i8"), ("n_events", "<i4"), ("events_lost", "<i4"), ("ev_off", "<u8"), ("events_total", "<i8")])
+TII_EVENT = np.dtype([("frame", "<i8"), ("n_results", "<i4"), ("n_found", "<i4"), ("frames_in_sum", "<i4"), ("epoch", "<i4"),
+                      ("threshold_db", "<i4"), ("reserved", "<i4")])
+TII_RESULT = np.dtype({"names": ["main_id", "sub_id", "strength", "phase_deg", "non_etsi_phase"], "formats": ["u1", "u1", "<f4", "<f4", "<i4"],
+                       "offsets": [0, 1, 4, 8, 12], "itemsize": 16})          # dabx_tii_result, == TiiResult
+TII_STATS = np.dtype([("events", "<i8"), ("results", "<i8"), ("truncated", "<i8"), ("resets", "<i8"), ("launches", "<i8"), ("reserved", "<i8", 3)])
+TII_EVENT_SLOT_BYTES = 32 + 16 * TII_MAX_RESULTS
+assert (CHUNK_HEADER_EXT.itemsize, CHUNK_TII.itemsize, TII_EVENT.itemsize, TII_RESULT.itemsize, TII_STATS.itemsize) == (64, 32, 32, 16, 64)
 CHUNK_STREAM = np.dtype([("first_frame", "<i8"), ("n_frames", "<i4"), ("frames_lost", "<i4"), ("state", "<i4"),
                          ("fic_ratio_percent", "<i4"), ("cif_count", "<i4"), ("snr_db_est", "<f4"), ("freq_offs_bb_hz", "<f4"),
                          ("clock_err_hz", "<f4"), ("signal_level", "<f4"), ("fic_ber_bits", "<i4"), ("fic_ber_errors", "<i4"),
@@ -603,9 +627,31 @@ class Chunk:
         self.mot = None                         # the MOT section: [S, M] CHUNK_MOT, or None when the slab has none
         if int(h["off_mot"]):
             self.mot = self.raw[int(h["off_mot"]):int(h["off_mot"]) + S * M * 128].view(CHUNK_MOT).reshape(S, M)
+        self.header_ext = None                  # the header's extension (CHUNK_HEADER_EXT) when `what` has a bit >= 256, else None
+        self.tii_table = None                   # the TII section: [S] CHUNK_TII, or None when the slab has none
+        if int(h["what"]) & ~255:
+            self.header_ext = self.raw[128:192].view(CHUNK_HEADER_EXT)[0]
+            if int(self.header_ext["magic"]) != CHUNK_EXT_MAGIC or int(self.header_ext["bytes"]) < 64:
+                raise DabxError("chunk %d: bad header extension" % self.seq)
+            if int(self.header_ext["off_tii"]):
+                o = int(self.header_ext["off_tii"])
+                self.tii_table = self.raw[o:o + S * 32].view(CHUNK_TII)
         self.eti_table = None                   # the ETI section: [S] CHUNK_ETI, or None when the slab has none
         if int(h["off_eti"]):
             self.eti_table = self.raw[int(h["off_eti"]):int(h["off_eti"]) + S * 64].view(CHUNK_ETI)
+
+    def tii(self, stream):
+        """TII events of `stream` in this chunk, oldest first: a list of (TII_EVENT record, its results[:n_results] as TII_RESULT records),
+        views.  Empty when the slab has no TII section."""
+        if self.tii_table is None:
+            return []
+        r = self.tii_table[stream]
+        out = []
+        for k in range(int(r["n_events"])):
+            o = int(r["ev_off"]) + k * TII_EVENT_SLOT_BYTES
+            ev = self.raw[o:o + 32].view(TII_EVENT)[0]
+            out.append((ev, self.raw[o + 32:o + 32 + 16 * int(ev["n_results"])].view(TII_RESULT)))
+        return out
 
     def eti(self, stream):
         """ETI(NI) frames of `stream` in this chunk: (its CHUNK_ETI record, [n_eti, 6144] uint8), views; the rows are contiguous and in CIF
@@ -835,6 +881,32 @@ class Engine:
         n = check(load().dabx_read_tii(self._h, stream, min_frames, threshold_db, int(collisions), collision_sub_id, out, max_out,
                                        C.byref(acc)))
         return [out[i].as_tuple() for i in range(n)], acc.value
+
+    def set_tii_mode(self, stream, min_frames=5, threshold_db=8, collisions=False, sub_id=0, enable=True):
+        """The stream's TII detector on the device (dabx_set_tii_mode; stream = -1: all streams): an event whenever `min_frames` TII null
+        symbols are in the sum, read with read_tii_events or delivered in bulk (DELIVER_TII)."""
+        cfg = TiiConfig(enable=int(bool(enable)), min_frames=min_frames, threshold_db=threshold_db, collisions=int(bool(collisions)),
+                        collision_sub_id=sub_id)
+        L = load()
+        L.dabx_set_tii_mode.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        check(L.dabx_set_tii_mode(self._h, stream, C.byref(cfg)))
+
+    def read_tii_events(self, stream, max_events=8):
+        """The events completed since the previous call: ([(TII_EVENT record, results[:n_results] as TII_RESULT records)], events lost)."""
+        ev = np.zeros(max_events, TII_EVENT)
+        res = np.zeros((max_events, TII_MAX_RESULTS), TII_RESULT)
+        lost = C.c_int32(0)
+        L = load()
+        L.dabx_read_tii_events.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        n = check(L.dabx_read_tii_events(self._h, stream, max_events, _p(ev), _p(res), C.byref(lost)))
+        return [(ev[k], res[k, :int(ev[k]["n_results"])]) for k in range(n)], lost.value
+
+    def tii_stats(self, stream):
+        st = np.zeros(1, TII_STATS)
+        L = load()
+        L.dabx_get_tii_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        check(L.dabx_get_tii_stats(self._h, stream, _p(st)))
+        return {k: int(st[k][0]) for k in TII_STATS.names if k != "reserved"}
 
     def read_eti(self, stream, max_frames=32):
         out = np.zeros((max_frames, 6144), np.uint8)
@@ -1089,6 +1161,28 @@ def eti_frames_device(cif_hi, cif_lo, minor, subch, fic96, msc):
     L.dabx_eti_frames_device.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     check(L.dabx_eti_frames_device(n, _p(hi), _p(lo), _p(mi), arr, len(subch), _p(fic96), _p(msc) if msc.size else None, _p(out), _p(used)))
     return out, used
+
+
+def tii_process_device(sums, pairs, cfgs, out=None, n_results=None, n_found=None):
+    """The TII detector on the device, n independent detectors in one call (a block each, the device function of the engine's k_tii): sums
+    [n, 2048] complex64, pairs [n, 768] complex64 (the detectors' state: a copy is advanced and returned), cfgs = n dicts / TiiConfig
+    (threshold_db, collisions, collision_sub_id, enable) -> (pairs, results [n, 32] TII_RESULT, n_results [n], n_found [n]).  out /
+    n_results / n_found: what a detector with enable = 0 leaves in its rows."""
+    sums = np.ascontiguousarray(sums, np.complex64).reshape(-1, 2048)
+    n = sums.shape[0]
+    pairs = np.array(pairs, np.complex64).reshape(n, 768)
+    arr = (TiiConfig * max(1, n))(*[c if isinstance(c, TiiConfig) else TiiConfig(**dict({"enable": 1}, **c)) for c in cfgs])
+    if len(cfgs) != n:
+        raise ValueError("tii_process_device needs one configuration per detector")
+    res = np.zeros((n, TII_MAX_RESULTS), TII_RESULT)
+    if out is not None:
+        res[...] = np.asarray(out, TII_RESULT).reshape(n, TII_MAX_RESULTS)
+    nr = np.zeros(n, np.int32) if n_results is None else np.array(n_results, np.int32).reshape(n)
+    nf = np.zeros(n, np.int32) if n_found is None else np.array(n_found, np.int32).reshape(n)
+    L = load()
+    L.dabx_tii_process_device.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    check(L.dabx_tii_process_device(n, _p(sums), _p(pairs), arr, _p(res), _p(nr), _p(nf)))
+    return pairs, res, nr, nf
 
 
 def host_register(a):

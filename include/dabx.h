@@ -956,7 +956,13 @@ enum { DABX_DELIVER_FIB = 1, DABX_DELIVER_MSC = 2, DABX_DELIVER_SF = 4,
           include it, and without the bit a slab, dabx_delivery_slab_bytes and the kernels launched are exactly what they are without it.
           One ETI stream per ensemble carries the whole FIC and MSC: a consumer of ETI needs no other bit.  Needs dabx_config.out_frames
           >= DABX_CHUNK_FRAMES, like the FIBs; an engine created FIC-only refuses it (DABX_E_STATE, as dabx_read_eti) */
-       DABX_DELIVER_ETI = 128 };
+       DABX_DELIVER_ETI = 128,
+       /* the TII events of every stream whose detector runs on the device (dabx_set_tii_mode; the TII section, dabx_chunk_tii below).  Opt-in
+          like DABX_DELIVER_ETI: what == 0 does NOT include it, and without the bit a slab, dabx_delivery_slab_bytes and the kernels launched
+          are exactly what they are without it.  With the bit the header is followed by a dabx_chunk_header_ext, which announces the section.
+          The bit adds to a delivery of something else (FIBs, logical frames, ...): what == DABX_DELIVER_TII alone is DABX_E_ARG, as the
+          mask 256 was before the bit existed */
+       DABX_DELIVER_TII = 256 };
 typedef struct {
   int32_t host_slabs;       /* page-locked host slabs, >= 2 (0 = default 4) */
   int32_t what;             /* DABX_DELIVER_* mask, 0 = everything */
@@ -976,6 +982,15 @@ typedef struct {
   uint64_t off_mot;         /* the MOT section: dabx_chunk_mot[n_streams * max_subch]; 0 = the slab has none */
   uint64_t off_eti;         /* the ETI section: dabx_chunk_eti[n_streams]; 0 = the slab has none */
 } dabx_chunk_header;        /* 128 bytes */
+/* The header's extension: present when, and only when, dabx_chunk_header.what carries a bit >= 256.  It follows the header at byte 128,
+ * and the stream table then starts at 192 (off_stream says so: every table of a slab is found through the header's offsets). */
+#define DABX_CHUNK_EXT_MAGIC 0x45584244u   /* "DBXE" */
+typedef struct {
+  uint32_t magic;           /* DABX_CHUNK_EXT_MAGIC */
+  uint32_t bytes;           /* 64 */
+  uint64_t off_tii;         /* the TII section: dabx_chunk_tii[n_streams]; 0 = the slab has none */
+  uint64_t reserved[6];
+} dabx_chunk_header_ext;    /* 64 bytes */
 typedef struct {
   int64_t first_frame;      /* index, since the stream was opened, of the first frame in the chunk */
   int32_t n_frames;         /* frames of this stream in the chunk, 0..max_frames (a stream out of lock delivers none) */
@@ -1078,6 +1093,19 @@ typedef struct {
   int64_t  fib_frames;      /* frames of the stream whose FIBs the stage has walked for the counter */
   uint64_t reserved[2];
 } dabx_chunk_eti;           /* 64 bytes */
+/* The TII section (DABX_DELIVER_TII): one dabx_chunk_tii per stream from dabx_chunk_header_ext.off_tii -- in the slab's head part, at the
+ * next multiple of 16 behind the ETI table (or where that would be) -- followed by room for 4 event slots per stream, n_streams * 4 * (32 + 32 * 16)
+ * bytes, fixed by the configuration: a chunk of DABX_CHUNK_FRAMES frames holds at most 4 TII null symbols, so at most 4 events even with
+ * min_frames = 1.  An event slot is a dabx_tii_event followed by DABX_TII_MAX_RESULTS dabx_tii_result records (of which n_results are
+ * valid), DABX_TII_EVENT_SLOT_BYTES in all; stream s's n_events slots lie one behind the other from ev_off, oldest first.  Every event a
+ * stream's detector completed since the previous chunk is in the chunk or counted in events_lost.  Gathered on the front-end stream when
+ * the chunk closes (k_deliver_tii): the events are front-end results like the FIBs. */
+typedef struct {
+  int64_t  first_event;     /* number, since the stream's mode was first switched on, of the first event in the chunk */
+  int32_t  n_events, events_lost;
+  uint64_t ev_off;
+  int64_t  events_total;    /* events the stream's detector has completed so far: first_event + n_events */
+} dabx_chunk_tii;           /* 32 bytes */
 typedef struct {
   uint64_t seq;
   const void *data;         /* the host slab: valid until dabx_delivery_release(seq) */
@@ -1233,10 +1261,11 @@ int  dabx_eti_frames_device(int n, const int32_t *cif_hi, const int32_t *cif_lo,
 int  dabx_read_eti(dabx_engine *e, int stream, int max_frames, uint8_t *out, int32_t *lost_cifs);
 
 /* ------------------------------------------------------------------------------------------------------------
- * TII: TiiDetector, base/ofdm/tii_detector.h:26-37, .cpp:149-240.  Host only: the engine
- * accumulates the FFT of every TII null symbol ((CIF count & 7) >= 4, dab_processor.cpp:273-300) on the device;
- * dabx_read_tii hands the sum to the stream's detector once `min_frames` of them are in (DabProcessor's
- * tiiFramesToCount) and returns the transmitters found, strongest first. */
+ * TII: TiiDetector, base/ofdm/tii_detector.h:26-37, .cpp:149-240.  The engine accumulates the FFT of every TII
+ * null symbol ((CIF count & 7) >= 4, dab_processor.cpp:273-300) on the device.  Two ways to the transmitters, per stream one or the other:
+ * on the host -- dabx_read_tii hands the sum to the stream's host detector (dabx_tii_*) once `min_frames` of them are in (DabProcessor's
+ * tiiFramesToCount) and returns the transmitters found, strongest first -- or on the device: dabx_set_tii_mode below runs the same detector
+ * behind the frame tail, at the reference's cadence, and its events are read in bulk (DABX_DELIVER_TII) or by dabx_read_tii_events. */
 typedef struct {
   uint8_t main_id, sub_id;   /* STiiResult */
   float strength, phase_deg;
@@ -1254,6 +1283,55 @@ int  dabx_tii_process(dabx_tii *t, int threshold_db, dabx_tii_result *out, int m
  * dab_processor.cpp:150-152. */
 int  dabx_read_tii(dabx_engine *e, int stream, int min_frames, int threshold_db, int collisions, int collision_sub_id,
                    dabx_tii_result *out, int max_out, int32_t *frames_accumulated);
+
+/* The detector on the device (csrc/tii_core.h, k_tii): dabx_tii_process line for line, one 256-thread block per stream, launched behind
+ * every frame tail while at least one stream has the mode on.  A stream with the mode on that is in lock runs its detector in the step
+ * whose TII null symbol brings the count of the sum to min_frames -- exactly when DabProcessor runs process_tii_data
+ * (dab_processor.cpp:287-300) --, writes one event (also when no transmitter is found: n_results = 0), and clears sum and count.  Every float
+ * sum and product is taken in dabx_tii_process's order; only |z| ((float)sqrt in double) and arg (the device library's atan2f) may differ
+ * from the host's libm in the last bits, ids, flags and order differ only where a decision of the detector lies within those bits.
+ * Results of equal strength keep the order in which the detector made them.  A loss of lock clears the detector's state, like dabx_read_tii.
+ * dabx_read_tii on a stream whose mode is on is refused (DABX_E_STATE): the two would take each other's sum. */
+#define DABX_TII_MAX_RESULTS 32
+typedef struct {
+  int32_t enable;
+  int32_t min_frames;        /* tiiFramesToCount; 0 = 5 (dabradio.cpp:85-93) */
+  int32_t threshold_db;      /* 0 = 8 (configuration.cpp:62-77) */
+  int32_t collisions, collision_sub_id;      /* set_detect_collisions, set_subid_for_collision_search */
+  int32_t reserved[3];
+} dabx_tii_config;           /* 32 bytes */
+typedef struct {
+  int64_t frame;             /* the stream's frame (index since it was opened) whose null symbol completed the sum */
+  int32_t n_results;         /* records stored behind the event: min(n_found, DABX_TII_MAX_RESULTS), the strongest */
+  int32_t n_found;           /* transmitters the detector found */
+  int32_t frames_in_sum;     /* TII null symbols in the sum */
+  int32_t epoch;             /* detector-reset epoch: moves with every loss of lock */
+  int32_t threshold_db;
+  int32_t reserved;
+} dabx_tii_event;            /* 32 bytes */
+#define DABX_TII_EVENT_SLOT_BYTES (32 + 16 * DABX_TII_MAX_RESULTS)
+typedef struct {
+  int64_t events;            /* events written */
+  int64_t results;           /* records stored in them */
+  int64_t truncated;         /* events with n_found > n_results */
+  int64_t resets;            /* times the detector's state was cleared after a loss of lock */
+  int64_t launches;          /* k_tii launches of the engine (the kernel has no row in the profile table) */
+  int64_t reserved[3];
+} dabx_tii_stats;            /* 64 bytes */
+/* stream = -1: all streams.  cfg = NULL: defaults, enabled.  Switching a stream's mode on clears its detector state.  The first enable
+ * allocates the stage; an engine that never enables the mode allocates and launches nothing for it.  Drains the engine. */
+int  dabx_set_tii_mode(dabx_engine *e, int stream, const dabx_tii_config *cfg);
+/* The events `stream` completed since the previous call, oldest first, at most max_events: ev [max_events], res [max_events][32] (optional).
+ * The device keeps the last 8 per stream; *lost (optional) counts those that had left.  Drains the engine; a cursor of its own, the
+ * delivery's is another.  Returns the number of events. */
+int  dabx_read_tii_events(dabx_engine *e, int stream, int max_events, dabx_tii_event *ev, dabx_tii_result *res, int32_t *lost);
+/* Any engine; all zeros without the mode (launches is the engine's, the same for every stream). */
+int  dabx_get_tii_stats(dabx_engine *e, int stream, dabx_tii_stats *out);
+/* The detector on crafted sums (stage level, host pointers, no engine): n independent detectors, one block each, through the device
+ * function of k_tii.  sums [n][2048] cf32; pairs [n][768] cf32 is the detectors' state, in and out, so a caller can run rounds;
+ * cfg [n] (min_frames is not looked at; enable = 0: that detector's pairs and outputs are left as they are); out [n][32]. */
+int  dabx_tii_process_device(int n, const float *sums, float *pairs, const dabx_tii_config *cfg, dabx_tii_result *out,
+                             int32_t *n_results, int32_t *n_found);
 
 #ifdef __cplusplus
 }
