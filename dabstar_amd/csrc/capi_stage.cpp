@@ -3,6 +3,7 @@
 #include "dabx_internal.h"
 #include "eti_core.h"
 #include "tii_core.h"
+#include "mp2_core.h"
 #include <cstring>
 
 namespace dabx { const char *last_error(); }
@@ -35,6 +36,19 @@ int dabx_abi_version(void) { return DABX_ABI_VERSION; }
 // 0: the kernels are in this library's fat binary (default build); 1 in the hipModule form (csrc/hipmodule/hipmodule_rt.cpp)
 int dabx_internal_hipmodule(void) { return 0; }
 #endif
+// Test entry of the MP2 audio stage (tests/test_mp2_audio_cases.py; not part of include/dabx.h): _mp2_decode_frame behind its counters on
+// the HOST, through the kernel's own pieces lane after lane (mp2_core.h, mp2a_decode_host).  frame: MP2frame as the device keeps it,
+// 6 kbps bytes; hist: [2][16][64] int32, the V rows of the 16 newest sub-blocks per channel, oldest first, in and out; pcm: [2304] int16.
+// Returns the frame size, 0 where the decoder returns 0 (*status: 1 = :397-402, 2 = :412-421); *over: guard G1.  Needs no device.
+int dabx_internal_mp2_decode_host(const uint8_t *frame, int kbps, int32_t *hist, int16_t *pcm, int32_t *status, int32_t *over)
+{
+  if (!frame || !hist || !pcm || !status || !over || kbps < 8 || kbps > MP2A_MAX_KBPS || kbps % 8 != 0) { set_error("dabx_internal_mp2_decode_host: bad argument"); return DABX_E_ARG; }
+  int st = 0, ov = 0;
+  const int size = mp2a_decode_host(frame, 6 * kbps, 48 * kbps, hist, pcm, &st, &ov);
+  *status = st; *over = ov;
+  return size;
+}
+
 int dabx_device_count(void) { int n = 0; return hipGetDeviceCount(&n) == hipSuccess ? n : 0; }
 int dabx_set_device(int device)
 {

@@ -10,6 +10,7 @@
 #include "pad_core.h"
 #include "mot_core.h"
 #include "carousel_core.h"
+#include "mp2_core.h"
 #include "eti_core.h"
 #include "tii_core.h"
 #include "fig00.h"
@@ -261,6 +262,44 @@ int launch_deliver_carousel(const EngineDev &e, const DeliverDev &dv, const Caro
   if (!dv.hdr.off_mot || cd.n <= 0) return 0;
   if (clear_table) DABX_HIP(hipMemsetAsync(dv.slab + dv.hdr.off_mot, 0, sizeof(dabx_chunk_mot) * (size_t)e.n_streams * e.max_subch, st));
   hipLaunchKernelGGL(k_deliver_carousel, dim3(cd.n), dim3(64), 0, st, cd, dv.slab, (unsigned long long)dv.hdr.off_mot);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+
+// The MP2 audio section (include/dabx.h, dabx_chunk_mp2_audio): one wave per slot with the mode on, behind the other sections' gathers of the
+// chunk, in the same way.
+__global__ __launch_bounds__(64) void k_deliver_mp2_audio(Mp2AudioDev ad, uint8_t *slab, unsigned long long off_mp2_audio)
+{
+  Mp2AudioSlot &as = ad.slots[blockIdx.x];
+  if (!as.out.dl_rec_off) return;
+  const OutGather g = out_ring_gather(as.out, slab, threadIdx.x);
+  if (threadIdx.x == 0) {
+    dabx_chunk_mp2_audio t;
+    t.first_frame = g.first; t.n_frames = g.n; t.frames_lost = (int)(g.first - g.done); t.rec_off = as.out.dl_rec_off; t.bytes_off = as.out.dl_bytes_off; t.n_bytes = g.n_bytes;
+    t.decode_calls = as.a.decode_calls; t.frames_out = as.a.frames_out; t.bad_header = as.a.bad_header; t.refused = as.a.refused; t.overread = as.a.overread;
+    t.sample_rate = as.m.sample_rate; t.voffs = as.a.voffs; t.number_of_frames = as.a.number_of_frames; t.error_frames = as.a.error_frames;
+    t.reserved[0] = t.reserved[1] = 0;
+    reinterpret_cast<dabx_chunk_mp2_audio *>(slab + off_mp2_audio)[(size_t)as.s * ad.max_subch + as.j] = t;
+    as.out.dl_done = as.out.count;
+  }
+}
+int launch_deliver_mp2_audio(const EngineDev &e, const DeliverDev &dv, const Mp2AudioDev &ad, unsigned long long off_mp2_audio, hipStream_t st)
+{
+  if (!off_mp2_audio || ad.n <= 0) return 0;
+  DABX_HIP(hipMemsetAsync(dv.slab + off_mp2_audio, 0, sizeof(dabx_chunk_mp2_audio) * (size_t)e.n_streams * e.max_subch, st));
+  hipLaunchKernelGGL(k_deliver_mp2_audio, dim3(ad.n), dim3(64), 0, st, ad, dv.slab, off_mp2_audio);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+
+// The header's extension of a slab that has one but no TII section (k_deliver_tii writes it otherwise)
+__global__ void k_deliver_ext(dabx_chunk_header_ext ext, uint8_t *slab)
+{
+  if (blockIdx.x == 0 && threadIdx.x == 0) *reinterpret_cast<dabx_chunk_header_ext *>(slab + sizeof(dabx_chunk_header)) = ext;
+}
+int launch_deliver_ext(const dabx_chunk_header_ext &ext, uint8_t *slab, hipStream_t st)
+{
+  hipLaunchKernelGGL(k_deliver_ext, dim3(1), dim3(64), 0, st, ext, slab);
   DABX_HIP(hipGetLastError());
   return 0;
 }

@@ -5,6 +5,7 @@
 #include "pad_core.h"
 #include "mot_core.h"
 #include "carousel_core.h"
+#include "mp2_core.h"
 #include "tii_core.h"
 #include "sdma.h"
 #include "iqfile.h"
@@ -65,6 +66,7 @@ struct Delivery {
   dabx_chunk_header_ext ext{};
   long long *tii_done = nullptr;
   bool tii() const { return (what & DABX_DELIVER_TII) != 0; }
+  bool mp2_audio() const { return (what & DABX_DELIVER_MP2_AUDIO) != 0; }      // the MP2 audio section (deliver.hip, k_deliver_mp2_audio), while a slot has the mode on
   bool eti() const { return (what & DABX_DELIVER_ETI) != 0; }
   EtiDev eti_dev(int devslab) const
   {
@@ -219,6 +221,8 @@ struct dabx_engine : dabx::EngineHead {          // (iqfile.h: the ring format, 
   JobTable<PadSlot, PadDev> pad;               // PAD slots (include/dabx.h "Programme-associated data", k_pad)
   JobTable<MotSlot, MotDev> mot;               // MOT slots (include/dabx.h "MOT objects of the X-PAD", k_mot): PAD slots all of them
   JobTable<CarouselSlot, CarouselDev> car;     // carousel slots (include/dabx.h "MOT objects of a packet-mode carousel", k_carousel): packet-mode slots all of them
+  JobTable<Mp2AudioSlot, Mp2AudioDev> mpa;     // MP2 audio slots (include/dabx.h "MP2 audio", k_mp2_audio)
+  long long mpa_launches = 0;                  // k_mp2_audio launches (dabx_mp2_audio_stats.launches)
   int build_msc_classes();
   int delivery_layout();                       // offsets of every slot's bytes in a slab for the sub-channels configured now
   int delivery_begin(DeliverDev *dv, int *slot, int *devslab);     // a chunk closes: host + device slab, front gather on stream a

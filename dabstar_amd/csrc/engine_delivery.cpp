@@ -12,7 +12,8 @@
 // the slab's records are ABI: hosts and the python binding (dabstar_amd/lib.py, CHUNK_*) parse them by these sizes
 static_assert(sizeof(dabx_chunk_header) == 128 && sizeof(dabx_chunk_stream) == 72 && sizeof(dabx_chunk_frame) == 16 && sizeof(dabx_chunk_subch) == 144 && offsetof(dabx_chunk_header, off_mot) == 112 &&
               sizeof(dabx_superframe_info) == 32 && sizeof(dabx_chunk_eti) == 64 && offsetof(dabx_chunk_header, off_eti) == 120 &&
-              sizeof(dabx_chunk_header_ext) == 64 && sizeof(dabx_chunk_tii) == 32 && sizeof(dabx_tii_event) == 32 && sizeof(dabx_tii_result) == 16,
+              sizeof(dabx_chunk_header_ext) == 64 && sizeof(dabx_chunk_tii) == 32 && sizeof(dabx_tii_event) == 32 && sizeof(dabx_tii_result) == 16 &&
+              sizeof(dabx_chunk_mp2_audio) == 128 && offsetof(dabx_chunk_header_ext, off_mp2_audio) == 16,
               "include/dabx.h: chunk record layout");
 static constexpr int DL_SF_CAP = (4 * DL_FRAMES + 4) / 5;          // super frames one chunk can complete (4 CIFs may be waiting from before)
 #if DABX_MSC_BATCH == 7
@@ -91,6 +92,8 @@ int dabx_engine::delivery_layout()
   if (D.eti()) { off = align_up(off, 16); h.off_eti = off; off += S * sizeof(dabx_chunk_eti); }     // the ETI section's table (its rows: the slab's end)
   // the TII section: its table and 4 event slots per stream
   if (D.tii()) { off = align_up(off, 16); x.off_tii = off; off += S * (sizeof(dabx_chunk_tii) + 4 * (size_t)DABX_TII_EVENT_SLOT_BYTES); }
+  // the MP2 audio section (dabx_chunk_mp2_audio): with the bit and a slot that has the mode on
+  off = layout_section(mpa, D.mp2_audio() && !d.fic_only, off, S * M * sizeof(dabx_chunk_mp2_audio), &x.off_mp2_audio);
   off = align_up(off, 256);
   h.off_msc = off;
   if ((D.what & (DABX_DELIVER_MSC | DABX_DELIVER_MSC_NOT_DABPLUS)) && !d.fic_only)
@@ -115,6 +118,7 @@ int dabx_engine::delivery_layout()
   if (!pad.host.empty()) if (int rc = pad.upload()) return rc;
   if (!mot.host.empty()) if (int rc = mot.upload()) return rc;
   if (!car.host.empty()) if (int rc = car.upload()) return rc;
+  if (!mpa.host.empty()) if (int rc = mpa.upload()) return rc;
   if (S * M) {
     DABX_HIP(hipMemcpy(D.layout_off, lo.data(), sizeof(unsigned long long) * 3 * S * M, hipMemcpyHostToDevice));
     std::vector<int32_t> ids(subch_id_host.begin(), subch_id_host.begin() + S * M);
@@ -154,6 +158,7 @@ int dabx_engine::delivery_begin(DeliverDev *dv, int *slot, int *devslab)
   dv->slab = D.dev[*devslab]; dv->layout_off = D.layout_off; dv->subch_id = D.subch_id;
   dv->frames_done = D.frames_done; dv->cif_done = D.cif_done; dv->sf_done = D.sf_done;
   dv->hdr = D.hdr; dv->hdr.seq = seq;
+  dv->off_mp2_audio = D.ext.off_mp2_audio;
   // two transfers when the slab has a tail of logical frames worth a transfer of its own (SDMA path)
   const size_t lf_from = (size_t)D.hdr.off_msc;
   const bool split = D.copy_engine == 0 && D.bytes > lf_from && D.bytes - lf_from >= ((size_t)1 << 20) && !dev.fic_only && dev.max_subch > 0 && dev.msc_out;
@@ -170,6 +175,7 @@ int dabx_engine::delivery_begin(DeliverDev *dv, int *slot, int *devslab)
   if (!rc && D.tii())
     rc = launch_deliver_tii(dev, TiiDeliverDev{D.dev[*devslab], D.ext, D.tii_done, tiis.dev.ring, tiis.exists() ? &tiis.dev.cnt->events : nullptr,
                                                (int32_t)(sizeof(TiiCounters) / sizeof(long long)), 0}, stream);
+  else if (!rc && D.ext.magic) rc = launch_deliver_ext(D.ext, D.dev[*devslab], stream);      // (k_deliver_tii writes the header's extension otherwise)
   if (rc) {                                                        // nothing was queued: give the slabs back
     std::lock_guard<std::mutex> lk(D.mu);
     D.dev_busy[*devslab] = false;
@@ -326,7 +332,7 @@ extern "C" {
 
 int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
 {
-  if (!e || (cfg && (cfg->host_slabs < 0 || cfg->host_slabs == 1 || cfg->host_slabs > 64 || (cfg->what & ~511) || cfg->copy_engine < 0 || cfg->copy_engine > 1))) {
+  if (!e || (cfg && (cfg->host_slabs < 0 || cfg->host_slabs == 1 || cfg->host_slabs > 64 || (cfg->what & ~1023) || cfg->copy_engine < 0 || cfg->copy_engine > 1))) {
     set_error("dabx_delivery_open: bad argument");
     return DABX_E_ARG;
   }
@@ -334,6 +340,11 @@ int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
   // bad argument it was before the bit existed (a host that probes for bits it does not know sees no change)
   if (cfg && cfg->what == DABX_DELIVER_TII) {
     set_error("dabx_delivery_open: DABX_DELIVER_TII needs at least one other DABX_DELIVER_* bit beside it");
+    return DABX_E_ARG;
+  }
+  // ... and so does DABX_DELIVER_MP2_AUDIO, alone or with DABX_DELIVER_TII: neither names anything a chunk is made of
+  if (cfg && (cfg->what & DABX_DELIVER_MP2_AUDIO) && !(cfg->what & ~(DABX_DELIVER_MP2_AUDIO | DABX_DELIVER_TII))) {
+    set_error("dabx_delivery_open: DABX_DELIVER_MP2_AUDIO needs at least one DABX_DELIVER_* bit below 256 beside it");
     return DABX_E_ARG;
   }
   if (e->dl.open) { set_error("dabx_delivery_open: already open"); return DABX_E_STATE; }
@@ -367,11 +378,12 @@ int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
   if (M && !d.fic_only) cap += S * ((size_t)4 * F * per_cif + (size_t)DL_SF_CAP * 5 * per_cif + 2 * 16 * M + M * DL_SF_CAP * sizeof(dabx_superframe_info));
   // ... and the data-group, the PAD and the MOT section
   if ((rc = e->pkt.download(d.max_subch)) || (rc = e->pad.download(d.max_subch)) || (rc = e->mot.download(d.max_subch)) ||
-      (rc = e->car.download(d.max_subch))) return rc;
+      (rc = e->car.download(d.max_subch)) || (rc = e->mpa.download(d.max_subch))) return rc;
   cap += section_capacity(e->pkt, S * M * sizeof(dabx_chunk_dg)) + section_capacity(e->pad, S * M * sizeof(dabx_chunk_pad)) +
          section_capacity(e->mot, S * M * sizeof(dabx_chunk_mot)) + section_capacity(e->car, S * M * sizeof(dabx_chunk_mot));
   if (D.eti()) cap += 16 + S * sizeof(dabx_chunk_eti) + 256 + S * 4 * F * DABX_ETI_FRAME_BYTES;      // ... and the ETI section: its table and 4 F rows per stream
   if (D.tii()) cap += sizeof(dabx_chunk_header_ext) + 16 + S * (sizeof(dabx_chunk_tii) + 4 * (size_t)DABX_TII_EVENT_SLOT_BYTES);   // ... and the TII section
+  if (D.mp2_audio()) cap += (D.tii() ? 0 : sizeof(dabx_chunk_header_ext)) + section_capacity(e->mpa, S * M * sizeof(dabx_chunk_mp2_audio));   // ... and the MP2 audio section
   D.capacity = align_up(cap, 4096);
 #define H(x) do { hipError_t err__ = (x); if (err__ != hipSuccess) { set_error("HIP error %d (%s) at %s:%d", (int)err__, hipGetErrorString(err__), __FILE__, __LINE__); delivery_free(e); return DABX_E_HIP; } } while (0)
   if (D.copy_engine == 1) H(hipStreamCreateWithFlags(&D.cs, hipStreamNonBlocking));

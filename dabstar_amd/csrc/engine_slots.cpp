@@ -142,6 +142,8 @@ static_assert(sizeof(dabx_chunk_pad) == 128 && sizeof(dabx_pad_item) == 32 && si
 static_assert(sizeof(dabx_chunk_mot) == 128 && sizeof(dabx_mot_object) == 32 && sizeof(dabx_mot_stats) == 128 && sizeof(dabx_mot_config) == 32, "include/dabx.h: MOT records");
 static_assert(sizeof(dabx_carousel_stats) == 128 && sizeof(dabx_carousel_config) == 32, "include/dabx.h: carousel records");
 static_assert(sizeof(dabx_mp2_sync_stats) == 64 && offsetof(dabx_pad_config, source) == 4, "include/dabx.h: PAD of MP2 frames");
+static_assert(sizeof(dabx_mp2_audio_frame) == 32 && sizeof(dabx_mp2_audio_stats) == 64 && sizeof(dabx_mp2_audio_config) == 32 && offsetof(dabx_mp2_audio_frame, flags) == 28,
+              "include/dabx.h: MP2 audio records");
 
 extern "C" {
 
@@ -162,6 +164,7 @@ int dabx_set_packet_mode(dabx_engine *e, int stream, int j, const dabx_packet_co
     return DABX_E_ARG;
   }
   if (cfg && e->pad.on(sj)) { set_error("dabx_set_packet_mode: stream %d slot %d has PAD decoding on", stream, j); return DABX_E_ARG; }
+  if (cfg && e->mpa.on(sj)) { set_error("dabx_set_packet_mode: stream %d slot %d has MP2 audio decoding on", stream, j); return DABX_E_ARG; }
   auto &tab = e->pkt;
   if (tab.host.empty()) {
     if (!cfg) return 0;
@@ -189,7 +192,7 @@ int dabx_set_packet_mode(dabx_engine *e, int stream, int j, const dabx_packet_co
   }
   if ((rc = tab.upload())) return rc;
   if ((rc = carousel_follow_packet(e))) return rc;
-  return relayout_open_delivery(e, sj, sc, e->pad, e->mot, e->car);
+  return relayout_open_delivery(e, sj, sc, e->pad, e->mot, e->car, e->mpa);
 }
 
 int dabx_read_datagroups(dabx_engine *e, int stream, int j, int n, dabx_datagroup_info *info, uint8_t *bytes, size_t max_bytes)
@@ -263,7 +266,7 @@ int dabx_set_pad_mode(dabx_engine *e, int stream, int j, const dabx_pad_config *
   if ((rc = tab.upload())) return rc;
   pad_count_sources(e);
   if ((rc = mot_follow_pad(e))) return rc;
-  return relayout_open_delivery(e, sj, sc, e->pkt, e->mot, e->car);
+  return relayout_open_delivery(e, sj, sc, e->pkt, e->mot, e->car, e->mpa);
 }
 
 int dabx_get_mp2_sync_stats(dabx_engine *e, int stream, int j, dabx_mp2_sync_stats *out)
@@ -304,6 +307,76 @@ int dabx_get_pad_stats(dabx_engine *e, int stream, int j, dabx_pad_stats *out)
   out->label_bytes = c.label_bytes; out->groups = c.groups; out->group_bytes = c.group_bytes; out->items_lost = e->pad.host[sj].lost;
   out->li_bad = i32(c.li_bad); out->dl_overflow = i32(c.dl_overflow); out->dg_crc_bad = i32(c.dg_crc_bad); out->dg_small = i32(c.dg_small);
   out->active = 1;
+  return 0;
+}
+
+// ---- MP2 audio (mp2_core.h, k_mp2_audio) -------------------------------------------------------------------------------------------------
+int dabx_set_mp2_audio_mode(dabx_engine *e, int stream, int j, const dabx_mp2_audio_config *cfg)
+{
+  if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch) { set_error("dabx_set_mp2_audio_mode: bad argument"); return DABX_E_ARG; }
+  if (cfg && cfg->size < sizeof(uint32_t)) { set_error("dabx_set_mp2_audio_mode: bad configuration (size %u)", cfg->size); return DABX_E_ARG; }
+  int rc;
+  if ((rc = sync_all(e))) return rc;
+  const size_t sj = (size_t)stream * e->dev.max_subch + j;
+  SubchDev sc;
+  DABX_HIP(hipMemcpy(&sc, e->dev.subch + sj, sizeof(SubchDev), hipMemcpyDeviceToHost));
+  if (!(cfg == nullptr && e->mpa.on(sj)) && (!sc.active || sc.dab_plus || e->pkt.on(sj) || sc.kbps % 8 != 0 || sc.kbps > MP2A_MAX_KBPS)) {      // the rules of DABX_PAD_SOURCE_MP2
+    set_error("dabx_set_mp2_audio_mode: stream %d slot %d is %s", stream, j, !sc.active ? "not active" : sc.dab_plus ? "a DAB+ slot" :
+              e->pkt.on(sj) ? "in packet mode" : "not at a multiple of 8 kbit/s up to 384");
+    return DABX_E_ARG;
+  }
+  auto &tab = e->mpa;
+  if (tab.host.empty()) {
+    if (!cfg) return 0;
+    tab.host.resize((size_t)e->dev.n_streams * e->dev.max_subch);
+    tab.index.assign(tab.host.size(), -1);
+  }
+  if ((rc = tab.download(e->dev.max_subch))) return rc;
+  tab.drop(sj);
+  if (cfg) {
+    decltype(e->mpa)::Host h;
+    h.on = true;
+    h.st.s = stream; h.st.j = j;
+    h.st.m.sample_rate = 48000; h.st.m.last_sync_bit = -1;             // mp2processor.cpp:234-242: SearchingForSync, every count and Voffs 0
+    if (!out_ring_create(&h.st.out, MP2A_BYTE_RING, MP2A_REC_RING, MP2A_PCM_BYTES, MP2A_DL_REC_CAP, MP2A_DL_BYTES_CAP, MP2A_EXTRA_BYTES)) {      // (mp2_core.h has the derivations)
+      set_error("dabx_set_mp2_audio_mode: out of device memory");
+      (void)tab.upload();
+      return DABX_E_NOMEM;
+    }
+    h.st.hist = reinterpret_cast<int32_t *>(h.st.out.bytes + MP2A_BYTE_RING);
+    h.st.mp2frame = reinterpret_cast<uint8_t *>(h.st.hist + 2 * MP2A_HIST_ROWS * 64);
+    tab.host[sj] = h;
+    if (hipMemset(h.st.hist, 0, MP2A_EXTRA_BYTES) != hipSuccess) {     // V and MP2frame zero (:215-221, :237)
+      tab.drop(sj);
+      (void)tab.upload();
+      set_error("dabx_set_mp2_audio_mode: clearing the decoder state failed");
+      return DABX_E_HIP;
+    }
+  }
+  if ((rc = tab.upload())) return rc;
+  return relayout_open_delivery(e, sj, sc, e->pkt, e->pad, e->mot, e->car);
+}
+
+int dabx_read_mp2_audio(dabx_engine *e, int stream, int j, int n, dabx_mp2_audio_frame *recs, uint8_t *pcm, size_t max_bytes)
+{
+  if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch || n <= 0 || !recs) { set_error("dabx_read_mp2_audio: bad argument"); return DABX_E_ARG; }
+  return ring_read(e, e->mpa, (size_t)stream * e->dev.max_subch + j, n, recs, pcm, max_bytes);
+}
+
+int dabx_get_mp2_audio_stats(dabx_engine *e, int stream, int j, dabx_mp2_audio_stats *out)
+{
+  if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch || !out) { set_error("dabx_get_mp2_audio_stats: bad argument"); return DABX_E_ARG; }
+  memset(out, 0, sizeof(*out));
+  out->launches = e->mpa_launches;
+  const size_t sj = (size_t)stream * e->dev.max_subch + j;
+  if (!e->mpa.on(sj)) return sync_all(e);
+  Mp2AudioSlot st;
+  long long lo = 0;
+  if (int rc = ring_window(e, e->mpa, sj, &st, &lo)) return rc;
+  const Mp2AudioState &a = st.a;
+  out->decode_calls = a.decode_calls; out->frames_out = a.frames_out; out->bad_header = a.bad_header; out->refused = a.refused; out->overread = a.overread;
+  out->sample_rate = st.m.sample_rate; out->frames_lost = (int32_t)std::min<long long>(e->mpa.host[sj].lost, INT32_MAX);
+  out->number_of_frames = (int16_t)a.number_of_frames; out->error_frames = (int16_t)a.error_frames; out->voffs = (int16_t)a.voffs; out->active = 1;
   return 0;
 }
 
@@ -357,7 +430,7 @@ int dabx_set_mot_mode(dabx_engine *e, int stream, int j, const dabx_mot_config *
     }
   }
   if ((rc = tab.upload())) return rc;
-  return relayout_open_delivery(e, sj, sc, e->pkt, e->pad, e->car);
+  return relayout_open_delivery(e, sj, sc, e->pkt, e->pad, e->car, e->mpa);
 }
 
 int dabx_read_mot_objects(dabx_engine *e, int stream, int j, int n, dabx_mot_object *info, uint8_t *bytes, size_t max_bytes)
@@ -454,7 +527,7 @@ int dabx_set_carousel_mode(dabx_engine *e, int stream, int j, const dabx_carouse
     }
   }
   if ((rc = tab.upload())) return rc;
-  return relayout_open_delivery(e, sj, sc, e->pkt, e->pad, e->mot);
+  return relayout_open_delivery(e, sj, sc, e->pkt, e->pad, e->mot, e->mpa);
 }
 
 int dabx_get_carousel_stats(dabx_engine *e, int stream, int j, dabx_carousel_stats *out)

@@ -5,6 +5,7 @@
 //   k_dabplus      super-frame sync, RS(120,110), fire code, AU CRCs (mp4processor.cpp:96-333); moves the slots' frame counters on
 //   k_pad          PAD of the DAB+ access units: dynamic labels and X-PAD MSC data groups (mp4processor.cpp:345-353, pad_handler.cpp:67-547)
 //   k_pad_mp2      PAD of DAB (MP2) audio frames: MP2 frame sync over the logical frames and the same PadHandler (mp2processor.cpp:611-747)
+//   k_mp2_audio    MP2 audio of DAB audio slots: frame assembly and the MP2 decoder, 1152 stereo samples per MP2 frame (mp2processor.cpp:292-609, :678-763)
 //   k_mot          MOT objects out of the X-PAD data groups the two PAD kernels have just emitted (pad_handler.cpp:553-622, mot_object.cpp:71-323)
 //   k_carousel     MOT objects out of the MSC data groups k_packet has just completed: MotHandler and MotDirectory (mot_handler.cpp:69-259,
 //                  mot_dir.cpp:28-156); launched right behind k_packet
@@ -15,6 +16,7 @@
 #include "pad_core.h"
 #include "mot_core.h"
 #include "carousel_core.h"
+#include "mp2_core.h"
 #include "fec_core.h"
 #include "wave_ops.h"
 
@@ -490,6 +492,206 @@ __global__ __launch_bounds__(64) void k_pad_mp2(PadDev pd)
   if (lane == 0) ps.m = m;
 }
 
+// --------------------------------------------------------------------------------------------- MP2 audio
+// One block of 256 threads per slot whose MP2 audio is decoded (Mp2AudioDev::slots: those slots only), behind k_dabplus, beside the PAD
+// stage: walks the logical frames the decoder produced in this batch step as k_pad_mp2 does -- the same sync walk (pad_core.h) on state of
+// its own, every wave running its wave-uniform steps in step with the others -- but keeps every bit of GetSampleRate and GetData in MP2frame
+// (mp2processor.cpp:689, :725, :737; in LDS for the launch, 6 kbps bytes in HBM between launches, never cleared): a run of bits goes from
+// the staged logical frame to its bit offset in MP2frame as one funnel shift per destination byte (mp2a_copy_bits).  When an MP2 frame
+// completes, _mp2_decode_frame (:377-609, mp2_core.h) runs on it:
+//   parse     every wave the same: lane 2 sb + ch reads its allocation, scfsi and scale factors at positions that are wave prefix sums
+//             (mp2a_scan), then wave w reads and requantises the sample triples of granules w, w + 4, w + 8 into smp[ch][sub-block][sb];
+//   matrix    all 2 x 36 x 64 values of V at once: wave w takes (sub-block, channel) pairs w, w + 4, ..., lane i holds row i of N in
+//             registers and reads the 32 samples as broadcasts; the rows go behind the channel's 16 history rows in LDS;
+//   window    lane (ch << 5 | j) holds its 16 taps of D in registers and reads 16 values of V per output sample, straight into the
+//             slot's byte ring; then the newest 16 rows become the history.
+// LDS: frm 1152 + mp2f 2320 + smp 2 x (36 x 32 + 16) x 4 + v 2 x 52 x 64 x 4 = 39 440 bytes; tests/test_mp2_audio_lds.py states the bank
+// behaviour of every access.  include/dabx.h "MP2 audio" states the semantics and guard G1.
+struct Mp2AudioLds {
+  __attribute__((aligned(16))) uint8_t frm[3 * MP2A_MAX_KBPS];            // the logical frame being walked
+  __attribute__((aligned(16))) uint8_t mp2f[MP2A_FRAME_ROOM + 16];        // MP2frame
+  __attribute__((aligned(16))) int smp[2][MP2A_SUBBLOCKS * 32 + 16];      // sample[ch][sub-block][sb]; + 16: the channels' lanes of a store on different banks
+  __attribute__((aligned(16))) int v[2][(MP2A_HIST_ROWS + MP2A_SUBBLOCKS) * 64];      // V rows of a channel, oldest first: 16 of history, then the frame's 36
+};
+
+// exclusive prefix sum over the wave's 64 lanes; *total: the sum
+__device__ __forceinline__ int mp2a_scan(int v, int lane, int *total)
+{
+  int incl = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int up = __shfl_up(incl, d);
+    if (lane >= d) incl += up;
+  }
+  *total = __shfl(incl, 63);
+  return incl - v;
+}
+
+// bits [sbit, sbit + k) of src (n_src bytes) to bits [dbit, dbit + k) of dst, bit i of an array being bit 7 - (i & 7) of byte i >> 3
+// (_add_bit_to_mp2, :749-763, k times): one thread per destination byte takes the 16 source bits its byte lies in and merges the part of
+// the byte the run covers.  The barrier in front says that whatever wrote dst before is done (the first and last byte are shared with the
+// neighbouring runs); callers put one behind before dst is read.
+__device__ __forceinline__ void mp2a_copy_bits(uint8_t *dst, int dbit, const uint8_t *src, int n_src, int sbit, int k, int tid)
+{
+  __syncthreads();
+  const int first = dbit >> 3, last = (dbit + k - 1) >> 3;
+  for (int b = first + tid; b <= last; b += 256) {
+    const int lo = max(dbit, 8 * b) - 8 * b, hi = min(dbit + k, 8 * b + 8) - 8 * b;      // the byte's bits [lo, hi), from the top
+    const int s0 = sbit + 8 * b - dbit;                              // the source bit of the byte's top bit (>= -7)
+    const int sb = s0 >> 3, sh = s0 & 7;
+    const unsigned w = ((sb >= 0 && sb < n_src ? (unsigned)src[sb] : 0u) << 8) | (sb + 1 >= 0 && sb + 1 < n_src ? (unsigned)src[sb + 1] : 0u);
+    const unsigned val = (w >> (8 - sh)) & 0xFFu, mask = (0xFFu >> lo) & (0xFF00u >> hi) & 0xFFu;
+    dst[b] = (uint8_t)((dst[b] & ~mask) | (val & mask));
+  }
+}
+
+__global__ __launch_bounds__(256) void k_mp2_audio(Mp2AudioDev ad)
+{
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  Mp2AudioSlot &as = ad.slots[blockIdx.x];
+  const size_t sj = (size_t)as.s * ad.max_subch + as.j;
+  const SubchDev &sc = ad.subch[sj];
+  if (!sc.active || sc.dab_plus || sc.kbps > MP2A_MAX_KBPS) return;
+  const BatchSnap bs = ad.snap[as.s];
+  const long long n_new = msc_new_frames(bs.msc_done, bs.cif_no, sc.start_cif).n;   // logical frames the decoder just produced for this sub-channel
+  if (n_new == 0) return;
+  const int nbytes = 3 * sc.kbps, nbits = 8 * nbytes;          // <= 1152 bytes (dabx_set_mp2_audio_mode); MP2framesize = 24 * bitRate (:236)
+  const int cap = 6 * sc.kbps, limit = 48 * sc.kbps;            // MP2frame as kept / as the reference sizes it (:237)
+  const uint8_t *ring = ad.msc_out + sj * MSC_SLOTS * ad.msc_stride;
+  __shared__ Mp2AudioLds lds;
+  uint8_t *const pcm_ring = as.out.bytes;
+  dabx_mp2_audio_frame *const recs = as.out.recs;
+  const unsigned long long bytes_mask = as.out.bytes_mask, rec_mask = as.out.rec_mask;
+  long long n_recs = as.out.count, n_bytes = as.out.n_bytes;
+  int32_t *const hist = as.hist;
+  uint8_t *const mp2frame = as.mp2frame;
+  for (int i = tid; i < (MP2A_FRAME_ROOM + 16) / 4; i += 256) reinterpret_cast<uint32_t *>(lds.mp2f)[i] = 4 * i < cap ? reinterpret_cast<const uint32_t *>(mp2frame)[i] : 0u;
+  for (int i = tid; i < 2 * MP2A_HIST_ROWS * 64; i += 256) lds.v[i >> 10][i & 1023] = hist[i];
+  int n_row[32], d_tap[16];                   // row `lane` of N; the window taps of output sample lane & 31
+#pragma unroll
+  for (int j = 0; j < 32; j++) n_row[j] = MP2_N[lane][j];
+#pragma unroll
+  for (int i = 0; i < 8; i++) { d_tap[2 * i] = MP2_D[64 * i + (lane & 31)]; d_tap[2 * i + 1] = MP2_D[64 * i + 32 + (lane & 31)]; }
+  Mp2State m = as.m;
+  Mp2AudioState a = as.a;
+  const long long frame0 = sc.cif_out - n_new;
+  for (long long n = 0; n < n_new; n++) {
+    const long long frame = frame0 + n;       // index of the logical frame in the slot's sequence
+    __syncthreads();
+    {
+      const uint32_t *src = reinterpret_cast<const uint32_t *>(ring + (size_t)(frame % MSC_SLOTS) * ad.msc_stride);
+      for (int i = tid; i < nbytes / 4; i += 256) reinterpret_cast<uint32_t *>(lds.frm)[i] = src[i];
+    }
+    __syncthreads();
+    int pos = 0;                              // :685 i
+    while (pos < nbits) {
+      if (m.state == MP2_GET_DATA) {                             // :687-714
+        const int lf = m.sample_rate == 48000 ? nbits : 2 * nbits;      // :680, :741
+        const int k = min(lf - m.bit_count, nbits - pos);
+        mp2a_copy_bits(lds.mp2f, m.bit_count, lds.frm, nbytes, pos, k, tid);      // :689
+        m.bit_count += k; pos += k;
+        if (m.bit_count < lf) break;                             // (the logical frame is used up)
+        m.frames++;                                              // :691 the MP2 frame is complete
+        __syncthreads();
+        // ---- _mp2_decode_frame (:377-609)
+        a.decode_calls++;
+        a.number_of_frames++;                                    // :388-394
+        if (a.number_of_frames >= 25) { a.number_of_frames = 0; a.error_frames = 0; }
+        const Mp2Header h = mp2a_header(pad_u(lds.mp2f[0]), pad_u(lds.mp2f[1]), pad_u(lds.mp2f[2]), pad_u(lds.mp2f[3]));
+        if (h.status == 1) { a.error_frames++; a.bad_header++; }           // :397-403
+        else if (h.status == 2) a.refused++;                     // :412-421
+        else {
+          const int sb = lane >> 1, ch = lane & 1;
+          int at = h.pos, total;
+          // allocation (:482-487): a lane from `bound` on whose channel is 1 has its neighbour's
+          const int w_alloc = mp2a_alloc_bits(h, lane);
+          unsigned av = mp2a_bits(lds.mp2f, cap, at + mp2a_scan(w_alloc, lane, &total), w_alloc);
+          at += total;
+          const unsigned av0 = (unsigned)__shfl((int)av, lane & ~1);
+          const int q = mp2a_quantiser(h, sb, w_alloc || !ch ? av : av0);
+          // scfsi (:491-499) and scale factors (:502-535).  Channel 1 of a mono frame reads none: its samples are channel 0's (below)
+          const bool has_scf = q != 0 && ch < h.nch;
+          const int w_sel = has_scf ? 2 : 0;
+          const unsigned sel = mp2a_bits(lds.mp2f, cap, at + mp2a_scan(w_sel, lane, &total), w_sel);
+          at += total;
+          const int n_scf = has_scf ? mp2a_scf_count(sel) : 0;
+          const int p_scf = at + mp2a_scan(6 * n_scf, lane, &total);
+          at += total;
+          const int v0 = (int)mp2a_bits(lds.mp2f, cap, p_scf, n_scf > 0 ? 6 : 0), v1 = (int)mp2a_bits(lds.mp2f, cap, p_scf + 6, n_scf > 1 ? 6 : 0),
+                    v2 = (int)mp2a_bits(lds.mp2f, cap, p_scf + 12, n_scf > 2 ? 6 : 0);
+          // samples (:538-556): every granule has the same size, so granule g of this lane starts at at + g * gran + off
+          const bool reads = w_alloc != 0 && q != 0;
+          int gran;
+          const int off = mp2a_scan(reads ? mp2a_sample_bits(q) : 0, lane, &gran);
+          for (int g = wave; g < 12; g += 4) {
+            int s[3] = {0, 0, 0};
+            if (reads) mp2a_read_samples(lds.mp2f, cap, at + g * gran + off, q, mp2a_scf_of(sel, g >> 2, v0, v1, v2), s);
+#pragma unroll
+            for (int idx = 0; idx < 3; idx++) {
+              const int s0 = __shfl(s[idx], lane & ~1);          // :548-550: channel 0's sample, already scaled with channel 0's factor
+              lds.smp[ch][(3 * g + idx) * 32 + sb] = w_alloc || !ch ? s[idx] : s0;
+            }
+          }
+          const bool over = mp2a_refill_pos(at + 12 * gran) > limit;       // guard G1
+          __syncthreads();
+          // matrixing (:567-575)
+          for (int p = wave; p < 2 * MP2A_SUBBLOCKS; p += 4) {
+            const int k2 = p >> 1, c = p & 1;
+            lds.v[c][(MP2A_HIST_ROWS + k2) * 64 + lane] = mp2a_matrix(n_row, &lds.smp[c][k2 * 32]);
+          }
+          __syncthreads();
+          // window and output (:578-601): opPcm[(sub-block << 6) | (j << 1) | ch]
+          for (int k2 = wave; k2 < MP2A_SUBBLOCKS; k2 += 4) {
+            const int c = lane >> 5, j = lane & 31;
+            const int sum = mp2a_window(lds.v[c], MP2A_HIST_ROWS + k2, j, d_tap);
+            *reinterpret_cast<int16_t *>(pcm_ring + (size_t)((unsigned long long)(n_bytes + 2 * ((k2 << 6) | (j << 1) | c)) & bytes_mask)) = (int16_t)sum;
+          }
+          __syncthreads();
+          int keep[8];                                           // the newest 16 rows of both channels become the history
+#pragma unroll
+          for (int i = 0; i < 8; i++) { const int e = tid + 256 * i; keep[i] = lds.v[e >> 10][MP2A_SUBBLOCKS * 64 + (e & 1023)]; }
+#pragma unroll
+          for (int i = 0; i < 8; i++) { const int e = tid + 256 * i; lds.v[e >> 10][e & 1023] = keep[i]; }
+          a.voffs = (a.voffs - MP2A_SUBBLOCKS * 64) & 1023;      // :562, 36 times
+          if (tid == 0) {                     // the 32 bytes of a dabx_mp2_audio_frame as four little-endian words
+            unsigned long long *o = reinterpret_cast<unsigned long long *>(recs + (size_t)((unsigned long long)n_recs & rec_mask));
+            o[0] = (unsigned long long)n_bytes; o[1] = (unsigned long long)frame;
+            o[2] = (unsigned long long)(unsigned)m.sample_rate | ((unsigned long long)(unsigned)h.frame_size << 32);
+            o[3] = (unsigned long long)lds.mp2f[1] | ((unsigned long long)lds.mp2f[2] << 8) | ((unsigned long long)lds.mp2f[3] << 16) |
+                   ((unsigned long long)(h.stereo ? 1 : 0) << 24) | ((unsigned long long)(over ? 1 : 0) << 32);
+          }
+          a.frames_out++; a.overread += over ? 1 : 0;
+          n_recs++; n_bytes += MP2A_PCM_BYTES;
+        }
+        m.state = MP2_SEARCHING; m.header_count = 0; m.bit_count = 0;   // :710-712
+      } else if (m.state == MP2_SEARCHING) {                     // :715-734
+        int run;
+        const int p = mp2_find_sync(lds.frm, nbits, pos, m.header_count, lane, &run);
+        if (p < 0) { m.header_count = run; break; }              // :720, :732 to the end of the frame
+        m.syncs++; m.last_sync_bit = p;
+        __syncthreads();
+        if (tid == 0) { lds.mp2f[0] = 0xFF; lds.mp2f[1] |= 0xF0; }      // :722-726 twelve ones
+        m.header_count = 12; m.bit_count = 12; m.header = 0;
+        m.state = MP2_GET_RATE;                                  // :727
+        pos = p + 1;
+      } else {                                                   // :735-744
+        const int k = min(24 - m.bit_count, nbits - pos);
+        mp2a_copy_bits(lds.mp2f, m.bit_count, lds.frm, nbytes, pos, k, tid);      // :737
+        m.header = (m.header << k) | (int)mp2_bits(lds.frm, nbytes, pos, k);
+        m.bit_count += k; pos += k;
+        if (m.bit_count == 24) {                                 // :738
+          mp2_header(m);                                         // :740
+          m.state = MP2_GET_DATA;                                // :742
+        }
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < cap / 4; i += 256) reinterpret_cast<uint32_t *>(mp2frame)[i] = reinterpret_cast<const uint32_t *>(lds.mp2f)[i];
+  for (int i = tid; i < 2 * MP2A_HIST_ROWS * 64; i += 256) hist[i] = lds.v[i >> 10][i & 1023];
+  if (tid == 0) { as.m = m; as.a = a; as.out.count = n_recs; as.out.n_bytes = n_bytes; }
+}
+
 // --------------------------------------------------------------------------------------------------- MOT
 // One wave per MOT-enabled PAD slot (MotDev::slots: those slots only), behind k_pad and k_pad_mp2: walks the items the slot's PAD kernel has
 // emitted since this slot's last visit (PadSlot::out.count against MotSlot::items_seen) out of the PAD rings and takes the
@@ -658,6 +860,20 @@ int launch_pad_stage(const EngineDev &e, const PadDev *pad, hipStream_t st, Mark
   if (q.n > q.n_mp2) hipLaunchKernelGGL(k_pad, dim3(q.n), dim3(64), 0, st, q);
   if (q.n_mp2 > 0) hipLaunchKernelGGL(k_pad_mp2, dim3(q.n), dim3(64), 0, st, q);
   mk.end(12, st);
+  DABX_HIP(hipGetLastError());
+  *used = q;
+  return 0;
+}
+
+// behind k_dabplus, beside the PAD stage: k_mp2_audio walks the batch's logical frames of the slots whose MP2 audio is decoded.  No marker:
+// the profile table has no row for it (dabx_mp2_audio_stats.launches counts; tools/bench_mp2_audio.py times it)
+int launch_mp2_audio_stage(const EngineDev &e, const Mp2AudioDev *ma, hipStream_t st, Mp2AudioDev *used)
+{
+  *used = Mp2AudioDev{};
+  if (!ma || ma->n <= 0) return 0;
+  Mp2AudioDev q = *ma;
+  q.max_subch = e.max_subch; q.msc_stride = e.msc_stride; q.subch = e.subch; q.snap = e.snap; q.msc_out = e.msc_out;
+  hipLaunchKernelGGL(k_mp2_audio, dim3(q.n), dim3(256), 0, st, q);
   DABX_HIP(hipGetLastError());
   *used = q;
   return 0;

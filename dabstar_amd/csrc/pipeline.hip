@@ -21,6 +21,7 @@
 #include "pad_core.h"
 #include "mot_core.h"
 #include "carousel_core.h"
+#include "mp2_core.h"
 #include <algorithm>
 #include "ofdm_core.h"
 #include "viterbi_core.h"
@@ -1825,7 +1826,8 @@ int launch_front_step(const EngineDev &e_in, EngineStreams &ss, Marker &mk, bool
 // `pk`, `pad`, `mot`, `car` (optional): the engine's packet-mode / PAD / MOT / carousel slots, for the slot stages (msc_stages.hip) and the gathers of what
 // they emitted.
 int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineStreams &ss, Marker &mk, const DeliverDev *dv, hipStream_t *tail,
-                     const PacketDev *pk, const PadDev *pad, const MotDev *mot, const CarouselDev *car, const EtiDev *eti)
+                     const PacketDev *pk, const PadDev *pad, const MotDev *mot, const CarouselDev *car, const EtiDev *eti, const Mp2AudioDev *mp2a,
+                     long long *mp2a_launches)
 {
   const DevTables *t;
   int rc = get_tables(&t);
@@ -1916,17 +1918,21 @@ int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineSt
   PadDev q;
   MotDev m;
   CarouselDev c;
+  Mp2AudioDev au;
   if ((rc = launch_packet_stage(e, pk, sb, mk, &p))) return rc;
   if ((rc = launch_carousel_stage(e, car, p, sb, mk, &c))) return rc;
   if ((rc = launch_dabplus_stage(e, sb, mk))) return rc;
   if ((rc = launch_pad_stage(e, pad, sb, mk, &q))) return rc;
   if ((rc = launch_mot_stage(e, mot, q, sb, mk, &m))) return rc;
+  if ((rc = launch_mp2_audio_stage(e, mp2a, sb, &au))) return rc;     // MP2 audio of the slots that have the mode on: launched only when there is one
+  if (au.n > 0 && mp2a_launches) ++*mp2a_launches;
   if (dv && (rc = launch_deliver_msc(e, *dv, sb, !dv->lf_done))) return rc;
   if (dv && eti && !dv->lf_done && (rc = launch_eti_back(e, *eti, sb, mk, false))) return rc;      // (one transfer behind everything: here)
   if (dv && p.n > 0 && (rc = launch_deliver_dg(e, *dv, p, sb))) return rc;      // the slab's data-group section (head part, like the gather in front)
   if (dv && q.n > 0 && (rc = launch_deliver_pad(e, *dv, q, sb))) return rc;     // ... and its PAD section
   if (dv && m.n > 0 && (rc = launch_deliver_mot(e, *dv, m, sb))) return rc;     // ... and its MOT section
   if (dv && c.n > 0 && (rc = launch_deliver_carousel(e, *dv, c, sb, m.n <= 0))) return rc;      // ... the carousel slots' rows of it
+  if (dv && au.n > 0 && (rc = launch_deliver_mp2_audio(e, *dv, au, dv->off_mp2_audio, sb))) return rc;      // ... and its MP2 audio section
   if (tail) *tail = sb;
   if (ss.b) {
     DABX_HIP(hipEventRecord(ss.msc_done, ss.b));

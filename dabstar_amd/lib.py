@@ -78,6 +78,10 @@ def load(build_if_missing=True):
         L.dabx_get_carousel_stats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     if hasattr(L, "dabx_get_mp2_sync_stats"):        # ... and of DAB (MP2) audio slots
         L.dabx_get_mp2_sync_stats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    if hasattr(L, "dabx_set_mp2_audio_mode"):        # MP2 audio of DAB audio slots
+        L.dabx_set_mp2_audio_mode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.dabx_read_mp2_audio.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.dabx_get_mp2_audio_stats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     if hasattr(L, "dabx_announce_write"):            # (absent from libraries older than the level anchor: tools/ab.sh runs those through this binding too)
         L.dabx_announce_write.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
     _LIB = L
@@ -471,7 +475,7 @@ assert CHUNK_ETI.itemsize == 64
 DELIVER_TII = 256
 TII_MAX_RESULTS = 32
 CHUNK_EXT_MAGIC = 0x45584244                     # "DBXE"
-CHUNK_HEADER_EXT = np.dtype([("magic", "<u4"), ("bytes", "<u4"), ("off_tii", "<u8"), ("reserved", "<u8", 6)])
+CHUNK_HEADER_EXT = np.dtype([("magic", "<u4"), ("bytes", "<u4"), ("off_tii", "<u8"), ("off_mp2_audio", "<u8"), ("reserved", "<u8", 5)])
 CHUNK_TII = np.dtype([("first_event", "<i8"), ("n_events", "<i4"), ("events_lost", "<i4"), ("ev_off", "<u8"), ("events_total", "<i8")])
 TII_EVENT = np.dtype([("frame", "<i8"), ("n_results", "<i4"), ("n_found", "<i4"), ("frames_in_sum", "<i4"), ("epoch", "<i4"),
                       ("threshold_db", "<i4"), ("reserved", "<i4")])
@@ -529,6 +533,26 @@ MP2_SEARCHING, MP2_GET_RATE, MP2_GET_DATA = 0, 1, 2
 MP2_SYNC_STATS = np.dtype([(k, "<i8") for k in ("syncs", "frames", "hdr_refused", "rate_unsupported")] +
                           [(k, "<i4") for k in ("sample_rate", "state", "bit_count", "header_count", "last_sync_bit", "active")] + [("reserved", "<i4", 2)])
 assert MP2_SYNC_STATS.itemsize == 64
+# MP2 audio (include/dabx.h "MP2 audio"): dabx_mp2_audio_frame, one record per decoded MP2 frame with MP2_PCM_BYTES of PCM (1152 samples,
+# interleaved L/R int16), dabx_mp2_audio_stats, and the slab's MP2 audio section (DELIVER_MP2_AUDIO, opt-in like DELIVER_ETI; announced by
+# the header's extension): one CHUNK_MP2_AUDIO per (stream, slot), all zero for a slot without the mode
+DELIVER_MP2_AUDIO = 512
+MP2_PCM_BYTES = 4608
+MP2_AUDIO_RING_BYTES = 512 * 1024
+MP2_AUDIO_OVERREAD = 1                       # dabx_mp2_audio_frame.flags
+MP2_AUDIO_FRAME = np.dtype([("byte_pos", "<i8"), ("frame", "<i8"), ("sample_rate", "<i4"), ("frame_size", "<i4"), ("header", "u1", 3),
+                            ("stereo", "u1"), ("flags", "u1"), ("reserved", "u1", 3)])
+MP2_AUDIO_STATS = np.dtype([(k, "<i8") for k in ("decode_calls", "frames_out", "bad_header", "refused", "overread", "launches")] +
+                           [("sample_rate", "<i4"), ("frames_lost", "<i4")] + [(k, "<i2") for k in ("number_of_frames", "error_frames", "voffs", "active")])
+CHUNK_MP2_AUDIO = np.dtype([("first_frame", "<i8"), ("n_frames", "<i4"), ("frames_lost", "<i4"), ("rec_off", "<u8"), ("bytes_off", "<u8"), ("n_bytes", "<i8")] +
+                           [(k, "<i8") for k in ("decode_calls", "frames_out", "bad_header", "refused", "overread", "sample_rate", "voffs", "number_of_frames",
+                                                 "error_frames")] + [("reserved", "<i8", 2)])
+assert MP2_AUDIO_FRAME.itemsize == 32 and MP2_AUDIO_STATS.itemsize == 64 and CHUNK_MP2_AUDIO.itemsize == 128
+
+
+class Mp2AudioConfig(C.Structure):
+    """dabx_mp2_audio_config."""
+    _fields_ = [("size", C.c_uint32), ("reserved", C.c_int32 * 7)]
 
 
 # MOT objects of the X-PAD (include/dabx.h): dabx_mot_object, one record per signal_new_mot_object, dabx_mot_stats and the slab's MOT
@@ -629,6 +653,7 @@ class Chunk:
             self.mot = self.raw[int(h["off_mot"]):int(h["off_mot"]) + S * M * 128].view(CHUNK_MOT).reshape(S, M)
         self.header_ext = None                  # the header's extension (CHUNK_HEADER_EXT) when `what` has a bit >= 256, else None
         self.tii_table = None                   # the TII section: [S] CHUNK_TII, or None when the slab has none
+        self.mp2_audio_table = None             # the MP2 audio section: [S, M] CHUNK_MP2_AUDIO, or None when the slab has none
         if int(h["what"]) & ~255:
             self.header_ext = self.raw[128:192].view(CHUNK_HEADER_EXT)[0]
             if int(self.header_ext["magic"]) != CHUNK_EXT_MAGIC or int(self.header_ext["bytes"]) < 64:
@@ -636,6 +661,9 @@ class Chunk:
             if int(self.header_ext["off_tii"]):
                 o = int(self.header_ext["off_tii"])
                 self.tii_table = self.raw[o:o + S * 32].view(CHUNK_TII)
+            if int(self.header_ext["off_mp2_audio"]):
+                o = int(self.header_ext["off_mp2_audio"])
+                self.mp2_audio_table = self.raw[o:o + S * M * 128].view(CHUNK_MP2_AUDIO).reshape(S, M)
         self.eti_table = None                   # the ETI section: [S] CHUNK_ETI, or None when the slab has none
         if int(h["off_eti"]):
             self.eti_table = self.raw[int(h["off_eti"]):int(h["off_eti"]) + S * 64].view(CHUNK_ETI)
@@ -704,6 +732,12 @@ class Chunk:
         bytes[byte_pos[i] : byte_pos[i] + body_len[i] + name_len[i]], body first.  Empty when the slab has no MOT section or the slot has no
         MOT decoding."""
         return self._ring_items(self.mot, "rec_off", "n_objects", MOT_OBJECT, s, j)
+
+    def mp2_audio(self, s, j):
+        """Decoded MP2 frames of slot (s, j) in this chunk: ([n_frames] MP2_AUDIO_FRAME, their n_bytes = 4608 n_frames bytes of PCM), views;
+        frame i's samples are bytes[4608 i : 4608 (i + 1)].view(int16).reshape(1152, 2), left and right.  Empty when the slab has no MP2
+        audio section or the slot has not the mode on."""
+        return self._ring_items(self.mp2_audio_table, "rec_off", "n_frames", MP2_AUDIO_FRAME, s, j)
 
     def release(self):
         if self._eng is not None:
@@ -1037,6 +1071,37 @@ class Engine:
         out = np.zeros(1, CAROUSEL_STATS)
         check(load().dabx_get_carousel_stats(self._h, int(stream), int(j), _p(out)))
         return {k: int(out[0][k]) for k in CAROUSEL_STATS.names}
+
+    def set_mp2_audio_mode(self, stream, j, on=True):
+        """Switches the MP2 audio decoding of DAB audio slot j of `stream` on (restarting it, as a fresh Mp2Processor, when it is on already)
+        or off (dabx_set_mp2_audio_mode).  Independent of the slot's PAD mode."""
+        L = load()
+        if not on:
+            check(L.dabx_set_mp2_audio_mode(self._h, int(stream), int(j), None))
+        else:
+            cfg = Mp2AudioConfig(size=C.sizeof(Mp2AudioConfig))
+            check(L.dabx_set_mp2_audio_mode(self._h, int(stream), int(j), C.byref(cfg)))
+
+    def read_mp2_audio(self, stream, j, n=64, max_bytes=None, with_bytes=True):
+        """(records [k] MP2_AUDIO_FRAME, bytes uint8 [k * 4608]) of the newest k <= n decoded MP2 frames of slot j, oldest first; frame i's
+        PCM is bytes[4608 i : 4608 (i + 1)].view(int16).reshape(1152, 2), left and right.  with_bytes = False: the records alone."""
+        call = load().dabx_read_mp2_audio
+        info = np.zeros(max(1, n), MP2_AUDIO_FRAME)
+        if not with_bytes:
+            return info[:check(call(self._h, int(stream), int(j), int(n), _p(info), None, 0))], np.zeros(0, np.uint8)
+        if max_bytes is None:
+            max_bytes = min(MP2_AUDIO_RING_BYTES, n * MP2_PCM_BYTES)
+        buf = np.zeros(max(1, int(max_bytes)), np.uint8)
+        k = check(call(self._h, int(stream), int(j), int(n), _p(info), _p(buf), int(max_bytes)))
+        return info[:k], buf[:k * MP2_PCM_BYTES].copy()
+
+    def mp2_audio_stats(self, stream, j):
+        """dabx_mp2_audio_stats of slot j as a dict (all zero but `launches` unless the mode is on); pcm_bytes = 4608 * frames_out."""
+        out = np.zeros(1, MP2_AUDIO_STATS)
+        check(load().dabx_get_mp2_audio_stats(self._h, int(stream), int(j), _p(out)))
+        st = {k: int(out[0][k]) for k in MP2_AUDIO_STATS.names}
+        st["pcm_bytes"] = MP2_PCM_BYTES * st["frames_out"]
+        return st
 
     def mp2_sync_stats(self, stream, j):
         """dabx_mp2_sync_stats of slot j as a dict (all zero unless the slot is a PAD slot with source "mp2")."""

@@ -632,7 +632,7 @@ int  dabx_get_packet_stats(dabx_engine *e, int stream, int subch_idx, dabx_packe
  * the device with a line-by-line restatement (tests/mp2_pad_cases.py), not with the reference's object code.
  * Out of scope: MotHandler of the X-PAD (the handler's one MotObject is "MOT objects of the X-PAD" below; the packet-mode MotHandler is
  * "MOT objects of a packet-mode carousel"), the charset conversion, DL Plus, F-PAD types
- * other than 0, MP2 audio decoding, handing out assembled MP2 frames. */
+ * other than 0, handing out assembled MP2 frames.  (MP2 audio decoding is "MP2 audio" at the end of this file.) */
 #define DABX_DL_MAX_BYTES 256
 enum { DABX_PAD_LABEL = 1, DABX_PAD_DATAGROUP = 2 };
 enum { DABX_PAD_SOURCE_DABPLUS = 0,    /* the access units of a DAB+ slot (dab_plus == 1) */
@@ -962,7 +962,12 @@ enum { DABX_DELIVER_FIB = 1, DABX_DELIVER_MSC = 2, DABX_DELIVER_SF = 4,
           are exactly what they are without it.  With the bit the header is followed by a dabx_chunk_header_ext, which announces the section.
           The bit adds to a delivery of something else (FIBs, logical frames, ...): what == DABX_DELIVER_TII alone is DABX_E_ARG, as the
           mask 256 was before the bit existed */
-       DABX_DELIVER_TII = 256 };
+       DABX_DELIVER_TII = 256,
+       /* the PCM of every slot whose MP2 audio is decoded on the device (dabx_set_mp2_audio_mode; the MP2 audio section, dabx_chunk_mp2_audio
+          below).  Opt-in exactly like DABX_DELIVER_ETI and DABX_DELIVER_TII: what == 0 does NOT include it, the bit alone is DABX_E_ARG, and
+          without the bit a slab, dabx_delivery_slab_bytes and the kernels launched are exactly what they are without it.  With the bit the
+          header is followed by a dabx_chunk_header_ext; the section exists while at least one slot has the mode on */
+       DABX_DELIVER_MP2_AUDIO = 512 };
 typedef struct {
   int32_t host_slabs;       /* page-locked host slabs, >= 2 (0 = default 4) */
   int32_t what;             /* DABX_DELIVER_* mask, 0 = everything */
@@ -989,7 +994,8 @@ typedef struct {
   uint32_t magic;           /* DABX_CHUNK_EXT_MAGIC */
   uint32_t bytes;           /* 64 */
   uint64_t off_tii;         /* the TII section: dabx_chunk_tii[n_streams]; 0 = the slab has none */
-  uint64_t reserved[6];
+  uint64_t off_mp2_audio;   /* the MP2 audio section: dabx_chunk_mp2_audio[n_streams * max_subch]; 0 = the slab has none */
+  uint64_t reserved[5];
 } dabx_chunk_header_ext;    /* 64 bytes */
 typedef struct {
   int64_t first_frame;      /* index, since the stream was opened, of the first frame in the chunk */
@@ -1332,6 +1338,83 @@ int  dabx_get_tii_stats(dabx_engine *e, int stream, dabx_tii_stats *out);
  * cfg [n] (min_frames is not looked at; enable = 0: that detector's pairs and outputs are left as they are); out [n][32]. */
 int  dabx_tii_process_device(int n, const float *sums, float *pairs, const dabx_tii_config *cfg, dabx_tii_result *out,
                              int32_t *n_results, int32_t *n_found);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * MP2 audio: the MP2 decoder of a DAB (MPEG-1/2 Audio Layer II) audio sub-channel on the device -- Mp2Processor's frame assembly and
+ * _mp2_decode_frame (base/backend/audio/mp2processor.cpp:197-243, :292-609, :678-763; kjmp2), k_mp2_audio: one 256-thread block per
+ * slot with the mode on, behind k_dabplus on the MSC batch's stream, beside the PAD stage.  The decoder is pure 32-bit integer
+ * arithmetic, so the device gives the reference's samples exactly: 1152 stereo int16 samples per MP2 frame for which _mp2_decode_frame
+ * returns > 0, interleaved L/R as opPcm holds them (a mono frame has the same sample in both channels).
+ * The sync walk is that of the PAD stage's MP2 source ("Programme-associated data" above) on state of its own, so the two are
+ * independent: either, both or neither may be on for a slot.  Every bit of GetSampleRate and GetData goes into MP2frame (:689, :725,
+ * :737), kept per slot on the device: 6 * kbps bytes, all that is ever written; bytes are never cleared between frames, so a 48 kHz
+ * frame behind a 24 kHz one leaves stale bytes behind it, which the parser can read.  Quirks kept: grouped code words beyond nlevels^3
+ * (:325-329), scale factor 63 (:311), a 44.1 / 32 kHz header decoded with its own tables at the sticky rate, bound > sblimit (:478), the
+ * sample of channel 0 copied to channel 1 from `bound` on whatever channel 1's scale factors say (:548-550), the header check in int
+ * arithmetic (bit-rate index 0 passes :399 and is refused at :412), two's-complement wrap-around of U[i] * D[i] (:587: codes beyond
+ * the quantiser's range reach it; codes within it stay below 2^31).
+ * Guard G1: frame_pos may run past MP2frame (48 * kbps bytes): the longest parse reads 4500 bytes with quantiser tables A / B and 1690
+ * with the LSR table (the window's refill reads up to two bytes more), so below 96 kbit/s a crafted header reaches it.  The device reads
+ * bytes >= 6 * kbps as zero -- what the reference holds up to 48 * kbps --; a frame whose refill reads a byte at or beyond 48 * kbps is
+ * counted in `overread`, flagged in its record, and decoded over zeros.
+ * Parity with the reference's object code is unpinned, as for the rest of Mp2Processor (mp2processor.cpp needs the GUI's headers): the
+ * tests compare the device with a line-by-line restatement (tests/mp2_audio_cases.py).
+ * Out of scope: resampling and playback, the "MP2 dump" ring (frameBuffer; frame_size and the header bytes are in the record), the
+ * signal_* cadence of :703-707. */
+#define DABX_MP2_PCM_BYTES 4608        /* 1152 samples x 2 channels x int16 */
+typedef struct {
+  uint32_t size;             /* sizeof(dabx_mp2_audio_config) of the caller */
+  int32_t  reserved[7];      /* zero */
+} dabx_mp2_audio_config;     /* 32 bytes */
+typedef struct dabx_mp2_audio_frame_s {
+  int64_t  byte_pos;         /* position of the frame's first PCM byte in the slot's sequence of PCM bytes (a multiple of 4608) */
+  int64_t  frame;            /* the logical frame in which the MP2 frame completed, in the numbering of dabx_pad_item.frame */
+  int32_t  sample_rate;      /* sampleRate when the frame was decoded: the sticky 48 000 / 24 000 of :250-264 */
+  int32_t  frame_size;       /* what _mp2_decode_frame returned (:454) */
+  uint8_t  header[3];        /* MP2frame[1 .. 3] */
+  uint8_t  stereo;           /* signal_is_stereo's argument (:444) */
+  uint8_t  flags;            /* bit 0: the frame was over-read (guard G1) */
+  uint8_t  reserved[3];
+} dabx_mp2_audio_frame;      /* 32 bytes, little-endian, no holes */
+typedef struct {
+  int64_t decode_calls;      /* _mp2_decode_frame calls (:388) = MP2 frames completed */
+  int64_t frames_out;        /* ... that returned > 0: records and PCM frames written */
+  int64_t bad_header;        /* ... that returned at :397-402 (the only place errorFrames moves) */
+  int64_t refused;           /* ... that returned at :412-421: free format (bit-rate index 0), sampling frequency 3 */
+  int64_t overread;          /* frames_out with flags bit 0 (guard G1) */
+  int64_t launches;          /* k_mp2_audio launches of the engine (the kernel has no row in the profile table) */
+  int32_t sample_rate;       /* sampleRate */
+  int32_t frames_lost;       /* frames that had left the rings before a dabx_read_mp2_audio call could return them */
+  int16_t number_of_frames, error_frames;      /* the live window of :388-394 */
+  int16_t voffs;             /* Voffs */
+  int16_t active;            /* 1: the mode is on for the slot (all else but launches is zero otherwise) */
+} dabx_mp2_audio_stats;      /* 64 bytes */
+/* Switches MP2 audio decoding of slot subch_idx of `stream` on (cfg != NULL) or off (NULL).  On: only an active slot with dab_plus == 0
+ * that is not in packet mode, at a multiple of 8 kbit/s up to 384 -- the rules of DABX_PAD_SOURCE_MP2 --, DABX_E_ARG otherwise.  A slot
+ * that is switched on starts as a fresh Mp2Processor: searching for sync, sampleRate 48 000, V and MP2frame zero, Voffs 0, empty rings;
+ * the walk starts with the next logical frame decoded.  The setting and the state stay with the slot wherever dabx_set_subchannels says
+ * it "keeps decoding without interruption", a move to other capacity units included; a new or changed slot loses them.  A slot with the
+ * mode on cannot become a packet-mode slot.  An engine without such a slot allocates and launches nothing for this stage.  Drains the
+ * engine. */
+int  dabx_set_mp2_audio_mode(dabx_engine *e, int stream, int subch_idx, const dabx_mp2_audio_config *cfg);
+/* The newest n frames still in the rings, oldest first: their records into recs[], their PCM back to back into pcm[], 4608 bytes each;
+ * byte_pos is rebased to the returned buffer.  When n frames exceed max_bytes the newest that fit are returned (pcm == NULL: records
+ * only).  Returns the number of frames.  The rings hold two batches: 64 records, 512 KiB.  Drains the engine. */
+int  dabx_read_mp2_audio(dabx_engine *e, int stream, int subch_idx, int n, dabx_mp2_audio_frame *recs, uint8_t *pcm, size_t max_bytes);
+int  dabx_get_mp2_audio_stats(dabx_engine *e, int stream, int subch_idx, dabx_mp2_audio_stats *out);
+/* The MP2 audio section (DABX_DELIVER_MP2_AUDIO): one dabx_chunk_mp2_audio per (stream, slot) from dabx_chunk_header_ext.off_mp2_audio,
+ * all zero for a slot without the mode; behind the table every such slot has room for DABX_CHUNK_FRAMES * 4 records and as many times
+ * 4608 bytes -- a logical frame completes at most one MP2 frame -- fixed by the configuration.  Record i's PCM is the 4608 bytes at
+ * bytes_off + byte_pos.  Gathered behind the batch's stages like the PAD section. */
+typedef struct {
+  int64_t  first_frame;      /* number, since the mode was switched on, of the first record in the chunk */
+  int32_t  n_frames, frames_lost;
+  uint64_t rec_off, bytes_off;
+  int64_t  n_bytes;          /* n_frames * 4608 */
+  int64_t  decode_calls, frames_out, bad_header, refused, overread;      /* dabx_mp2_audio_stats after the chunk's batch */
+  int64_t  sample_rate, voffs, number_of_frames, error_frames;
+  int64_t  reserved[2];
+} dabx_chunk_mp2_audio;      /* 128 bytes */
 
 #ifdef __cplusplus
 }

@@ -222,6 +222,15 @@ public:
     for (const auto &s : slots_) if (s.kbps && s.subch_id == subChId) return true;
     return false;
   }
+  // The MP2 decoder of a running DAB (not DAB+) audio service on the device (dabx_set_mp2_audio_mode): false when the service does not
+  // run or the engine refuses (a DAB+ or packet-mode slot).  The PCM is read with dabx_read_mp2_audio(engine(), 0, slot, ...)
+  bool set_mp2_audio_decoding(int subChId, bool on)
+  {
+    const dabx_mp2_audio_config cfg{sizeof(dabx_mp2_audio_config), {0}};
+    for (size_t j = 0; j < slots_.size(); j++)
+      if (slots_[j].kbps && slots_[j].subch_id == subChId) return dabx_set_mp2_audio_mode(eng_, 0, (int)j, on ? &cfg : nullptr) == 0;
+    return false;
+  }
   // "decode everything the FIC announces" -- what EtiGenerator does on its own (eti_generator.cpp:132-134)
   int set_all_channels()
   {
