@@ -412,6 +412,25 @@ int dabx_internal_front_read(dabx_engine *e, int stream, dabx_front_scalars *sc,
   return 0;
 }
 
+// ---- test entry of the DC / IQ correction (tests/test_gpu_dciq_stage.py; not part of include/dabx.h) -----------------------------------
+// What k_dciq carries from launch to launch for `stream`: state = meanI, meanQ, meanII, meanQQ, meanIQ (EngineDev::dciq_state, the first
+// five of the stream's eight floats) and *done = the absolute index of the first sample not yet corrected (EngineDev::dciq_done), copied
+// out with plain hipMemcpy behind a full synchronisation (no kernel).  An engine without the correction has the initial values.
+int dabx_internal_dciq_read(dabx_engine *e, int stream, float *state, uint64_t *done)
+{
+  if (!e || !state || !done || stream < 0 || stream >= e->dev.n_streams || !e->dev.dciq_state || !e->dev.dciq_done) {
+    set_error("dabx_internal_dciq_read: bad argument (stream %d)", stream);
+    return DABX_E_ARG;
+  }
+  if (int rc = use_device(e)) return rc;
+  if (int rc = sync_all(e)) return rc;
+  unsigned long long upto = 0;
+  DABX_HIP(hipMemcpy(state, e->dev.dciq_state + (size_t)stream * 8, 5 * sizeof(float), hipMemcpyDeviceToHost));
+  DABX_HIP(hipMemcpy(&upto, e->dev.dciq_done + stream, sizeof(upto), hipMemcpyDeviceToHost));
+  *done = (uint64_t)upto;
+  return 0;
+}
+
 }  // extern "C"
 
 struct dabx_msc {

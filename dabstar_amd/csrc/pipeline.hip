@@ -107,7 +107,10 @@ template <int RF> struct RingView {
 // maps of its 16 consecutive samples, a block scan gives every thread its start state, and the thread then runs the
 // reference's float recurrence over its 16 samples from there -- three dependent levels (means -> second moments -> QQ).
 // Not bit-identical to the 196 608-step serial recurrence (start states differ in the last ulps; each filter forgets rounding
-// noise with its own 1-s time constant), equal within 1e-5 of full scale (tests/test_gpu_engine.py).
+// noise with its own 1-s time constant).  Measured against the same filters with double states (tests/test_gpu_dciq_stage.py, bounds
+// per case from tests/dciq_cases.py): outputs within 2.3e-7 of full scale DC only, 2.4e-6 with the IQ correction, carried means within
+// 1.3e-5 of their own value; bit for bit the float32 restatement of this tile algorithm in tests/dciq_cases.py.  The receiver test
+// (tests/test_gpu_engine.py, test_dc_and_iq_imbalance_correction_follows_the_oracle) allows 4e-6 on its signal.
 // The maps are kept as y -> y - e y + b with e = 1 - a: a itself (1 - 4.9e-7 per sample) has no exact float, its rounding
 // would change the filter's time constant by up to 6 %; e and b are small numbers and compose exactly enough.
 struct Affine { float a /* e = 1 - slope */, b; };

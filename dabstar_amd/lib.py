@@ -221,6 +221,17 @@ def front_read(engine, stream, spectra=True):
     return out
 
 
+def dciq_read(engine, stream):
+    """Internal test entry (not part of include/dabx.h): what k_dciq carries from launch to launch for `stream`, copied out without any
+    kernel -> (state [5] float32: meanI, meanQ, meanII, meanQQ, meanIQ; done: the absolute index of the first sample not yet corrected)."""
+    state = np.zeros(5, np.float32)
+    done = C.c_uint64(0)
+    L = load()
+    L.dabx_internal_dciq_read.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    check(L.dabx_internal_dciq_read(engine._h, int(stream), _p(state), C.byref(done)))
+    return state, int(done.value)
+
+
 def fib_cif_count(fib32):
     """Internal, host only: (CIFCountHi, CIFCountLo) the library's FIG 0/0 walk reads out of one FIB of 32 bytes (CRC taken as good),
     or None -- the walk of k_fic_frame and of the ETI writer (csrc/fig00.h)."""

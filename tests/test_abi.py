@@ -20,7 +20,7 @@ def test_library_exports_the_internal_test_entries():
     """The stage tests' entries (not part of include/dabx.h, mirrored in dabstar_amd/lib.py) are exported all the same."""
     L = dx.load()
     names = ["dabx_internal_msc_inject", "dabx_internal_msc_decode", "dabx_internal_fic_inject", "dabx_internal_fic_decode",
-             "dabx_internal_demap_inject", "dabx_internal_demap_frame", "dabx_internal_front_read"]
+             "dabx_internal_demap_inject", "dabx_internal_demap_frame", "dabx_internal_front_read", "dabx_internal_dciq_read"]
     assert not [n for n in names if not hasattr(L, n)]
     assert not [n for n in names if n in dx.declared_symbols()]
 
