@@ -4,6 +4,7 @@
 #include "eti_core.h"
 #include "tii_core.h"
 #include "mp2_core.h"
+#include "aac_core.h"
 #include <cstring>
 
 namespace dabx { const char *last_error(); }
@@ -47,6 +48,15 @@ int dabx_internal_mp2_decode_host(const uint8_t *frame, int kbps, int32_t *hist,
   const int size = mp2a_decode_host(frame, 6 * kbps, 48 * kbps, hist, pcm, &st, &ov);
   *status = st; *over = ov;
   return size;
+}
+
+// Test entry of the AAC stream stage (tests/test_aac_stream_cases.py; not part of include/dabx.h): the LOAS frame of ONE access unit on the
+// HOST, through the kernel's own header and copy pieces lane after lane (aac_core.h, aac_frame_host).  au: the L <= 960 payload bytes;
+// stream_parms as dabx_superframe_info holds them; out: room for DABX_AAC_MAX_FRAME_BYTES.  Returns the frame's size.  Needs no device.
+int dabx_internal_aac_frame_host(const uint8_t *au, int L, int stream_parms, uint8_t *out)
+{
+  if ((!au && L > 0) || !out || L < 0 || L > AAC_MAX_AU_BYTES || stream_parms < 0 || stream_parms > 0x7F) { set_error("dabx_internal_aac_frame_host: bad argument"); return DABX_E_ARG; }
+  return aac_frame_host(au, L, (unsigned)stream_parms, out);
 }
 
 int dabx_device_count(void) { int n = 0; return hipGetDeviceCount(&n) == hipSuccess ? n : 0; }

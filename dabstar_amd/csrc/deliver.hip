@@ -11,6 +11,7 @@
 #include "mot_core.h"
 #include "carousel_core.h"
 #include "mp2_core.h"
+#include "aac_core.h"
 #include "eti_core.h"
 #include "tii_core.h"
 #include "fig00.h"
@@ -288,6 +289,31 @@ int launch_deliver_mp2_audio(const EngineDev &e, const DeliverDev &dv, const Mp2
   if (!off_mp2_audio || ad.n <= 0) return 0;
   DABX_HIP(hipMemsetAsync(dv.slab + off_mp2_audio, 0, sizeof(dabx_chunk_mp2_audio) * (size_t)e.n_streams * e.max_subch, st));
   hipLaunchKernelGGL(k_deliver_mp2_audio, dim3(ad.n), dim3(64), 0, st, ad, dv.slab, off_mp2_audio);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+
+// The AAC section (include/dabx.h, dabx_chunk_aac): one wave per slot with the mode on, behind the other sections' gathers of the chunk, in
+// the same way.
+__global__ __launch_bounds__(64) void k_deliver_aac(AacStreamDev ad, uint8_t *slab, unsigned long long off_aac)
+{
+  AacStreamSlot &as = ad.slots[blockIdx.x];
+  if (!as.out.dl_rec_off) return;
+  const OutGather g = out_ring_gather(as.out, slab, threadIdx.x);
+  if (threadIdx.x == 0) {
+    dabx_chunk_aac t;
+    t.first_frame = g.first; t.n_frames = g.n; t.frames_lost = (int)(g.first - g.done); t.rec_off = as.out.dl_rec_off; t.bytes_off = as.out.dl_bytes_off; t.n_bytes = g.n_bytes;
+    t.superframes = as.superframes; t.records = as.records; t.frames = as.frames; t.frame_bytes = as.frame_bytes; t.lost_len = as.lost_len; t.lost_crc = as.lost_crc;
+    for (int i = 0; i < 5; i++) t.reserved[i] = 0;
+    reinterpret_cast<dabx_chunk_aac *>(slab + off_aac)[(size_t)as.s * ad.max_subch + as.j] = t;
+    as.out.dl_done = as.out.count;
+  }
+}
+int launch_deliver_aac(const EngineDev &e, const DeliverDev &dv, const AacStreamDev &ad, unsigned long long off_aac, hipStream_t st)
+{
+  if (!off_aac || ad.n <= 0) return 0;
+  DABX_HIP(hipMemsetAsync(dv.slab + off_aac, 0, sizeof(dabx_chunk_aac) * (size_t)e.n_streams * e.max_subch, st));
+  hipLaunchKernelGGL(k_deliver_aac, dim3(ad.n), dim3(64), 0, st, ad, dv.slab, off_aac);
   DABX_HIP(hipGetLastError());
   return 0;
 }

@@ -377,6 +377,7 @@ void dabx_destroy(dabx_engine *e)
   e->pkt.destroy();
   e->pad.destroy();
   e->mpa.destroy();
+  e->aac.destroy();
   e->mot.destroy();
   e->car.destroy();
   for (void *p : e->allocs) (void)hipFree(p);
@@ -413,6 +414,7 @@ static int set_subchannels_impl(dabx_engine *e, int stream, const dabx_subch_des
   if ((rc = e->mot.download(d.max_subch))) return rc;
   if ((rc = e->car.download(d.max_subch))) return rc;
   if ((rc = e->mpa.download(d.max_subch))) return rc;
+  if ((rc = e->aac.download(d.max_subch))) return rc;
   int max_kbps = e->max_kbps;
   std::vector<SubchDev> row(std::max(1, d.max_subch));
   for (int j = 0; j < n; j++) {
@@ -522,6 +524,10 @@ static int set_subchannels_impl(dabx_engine *e, int stream, const dabx_subch_des
   if (!e->mpa.host.empty()) {           // ... and MP2 audio decoding, as PAD decoding
     for (size_t sj : restarted) e->mpa.drop(sj);
     if ((rc = e->mpa.upload())) return rc;
+  }
+  if (!e->aac.host.empty()) {           // ... and the LOAS framing, as PAD decoding
+    for (size_t sj : restarted) e->aac.drop(sj);
+    if ((rc = e->aac.upload())) return rc;
   }
   if (e->dl.open) {
     // slots that start anew count their frames from 0 again; the slab layout follows the new sub-channels (engine drained above)
@@ -824,7 +830,8 @@ int dabx_process(dabx_engine *e, int max_frames, int sync)
       const EtiDev eti = with_eti ? e->dl.eti_dev(dl_dev) : EtiDev{};
       rc = launch_msc_batch(e->dev, 4 * e->pending_frames, e->have_fast ? &e->fast : nullptr, e->ss, e->mk, e->dl.open ? &dv : nullptr, &tail,
                             e->pkt.dev.n > 0 ? &e->pkt.dev : nullptr, e->pad.dev.n > 0 ? &e->pad.dev : nullptr, e->mot.dev.n > 0 ? &e->mot.dev : nullptr,
-                            e->car.dev.n > 0 ? &e->car.dev : nullptr, with_eti ? &eti : nullptr, e->mpa.dev.n > 0 ? &e->mpa.dev : nullptr, &e->mpa_launches);
+                            e->car.dev.n > 0 ? &e->car.dev : nullptr, with_eti ? &eti : nullptr, e->mpa.dev.n > 0 ? &e->mpa.dev : nullptr, &e->mpa_launches,
+                            e->aac.dev.n > 0 ? &e->aac.dev : nullptr, &e->aac_launches);
       if (rc) {
         if (e->dl.open) e->delivery_abort(dl_slot, dl_dev);          // the slabs of the chunk that was begun: never left IN_FLIGHT without a copy job
         e->pending_frames = 0;

@@ -6,6 +6,7 @@
 #include "mot_core.h"
 #include "carousel_core.h"
 #include "mp2_core.h"
+#include "aac_core.h"
 #include "tii_core.h"
 #include "sdma.h"
 #include "iqfile.h"
@@ -67,6 +68,7 @@ struct Delivery {
   long long *tii_done = nullptr;
   bool tii() const { return (what & DABX_DELIVER_TII) != 0; }
   bool mp2_audio() const { return (what & DABX_DELIVER_MP2_AUDIO) != 0; }      // the MP2 audio section (deliver.hip, k_deliver_mp2_audio), while a slot has the mode on
+  bool aac() const { return (what & DABX_DELIVER_AAC) != 0; }      // the AAC section (deliver.hip, k_deliver_aac), while a slot has the mode on
   bool eti() const { return (what & DABX_DELIVER_ETI) != 0; }
   EtiDev eti_dev(int devslab) const
   {
@@ -223,6 +225,8 @@ struct dabx_engine : dabx::EngineHead {          // (iqfile.h: the ring format, 
   JobTable<CarouselSlot, CarouselDev> car;     // carousel slots (include/dabx.h "MOT objects of a packet-mode carousel", k_carousel): packet-mode slots all of them
   JobTable<Mp2AudioSlot, Mp2AudioDev> mpa;     // MP2 audio slots (include/dabx.h "MP2 audio", k_mp2_audio)
   long long mpa_launches = 0;                  // k_mp2_audio launches (dabx_mp2_audio_stats.launches)
+  JobTable<AacStreamSlot, AacStreamDev> aac;   // AAC stream slots (include/dabx.h "AAC stream", k_aac_stream): DAB+ slots all of them
+  long long aac_launches = 0;                  // k_aac_stream launches (dabx_aac_stream_stats.launches)
   int build_msc_classes();
   int delivery_layout();                       // offsets of every slot's bytes in a slab for the sub-channels configured now
   int delivery_begin(DeliverDev *dv, int *slot, int *devslab);     // a chunk closes: host + device slab, front gather on stream a

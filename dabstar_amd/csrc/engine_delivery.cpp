@@ -13,7 +13,8 @@
 static_assert(sizeof(dabx_chunk_header) == 128 && sizeof(dabx_chunk_stream) == 72 && sizeof(dabx_chunk_frame) == 16 && sizeof(dabx_chunk_subch) == 144 && offsetof(dabx_chunk_header, off_mot) == 112 &&
               sizeof(dabx_superframe_info) == 32 && sizeof(dabx_chunk_eti) == 64 && offsetof(dabx_chunk_header, off_eti) == 120 &&
               sizeof(dabx_chunk_header_ext) == 64 && sizeof(dabx_chunk_tii) == 32 && sizeof(dabx_tii_event) == 32 && sizeof(dabx_tii_result) == 16 &&
-              sizeof(dabx_chunk_mp2_audio) == 128 && offsetof(dabx_chunk_header_ext, off_mp2_audio) == 16,
+              sizeof(dabx_chunk_mp2_audio) == 128 && offsetof(dabx_chunk_header_ext, off_mp2_audio) == 16 &&
+              sizeof(dabx_chunk_aac) == 128 && offsetof(dabx_chunk_header_ext, off_aac) == 24,
               "include/dabx.h: chunk record layout");
 static constexpr int DL_SF_CAP = (4 * DL_FRAMES + 4) / 5;          // super frames one chunk can complete (4 CIFs may be waiting from before)
 #if DABX_MSC_BATCH == 7
@@ -94,6 +95,8 @@ int dabx_engine::delivery_layout()
   if (D.tii()) { off = align_up(off, 16); x.off_tii = off; off += S * (sizeof(dabx_chunk_tii) + 4 * (size_t)DABX_TII_EVENT_SLOT_BYTES); }
   // the MP2 audio section (dabx_chunk_mp2_audio): with the bit and a slot that has the mode on
   off = layout_section(mpa, D.mp2_audio() && !d.fic_only, off, S * M * sizeof(dabx_chunk_mp2_audio), &x.off_mp2_audio);
+  // ... and the AAC section (dabx_chunk_aac), in the same way
+  off = layout_section(aac, D.aac() && !d.fic_only, off, S * M * sizeof(dabx_chunk_aac), &x.off_aac);
   off = align_up(off, 256);
   h.off_msc = off;
   if ((D.what & (DABX_DELIVER_MSC | DABX_DELIVER_MSC_NOT_DABPLUS)) && !d.fic_only)
@@ -119,6 +122,7 @@ int dabx_engine::delivery_layout()
   if (!mot.host.empty()) if (int rc = mot.upload()) return rc;
   if (!car.host.empty()) if (int rc = car.upload()) return rc;
   if (!mpa.host.empty()) if (int rc = mpa.upload()) return rc;
+  if (!aac.host.empty()) if (int rc = aac.upload()) return rc;
   if (S * M) {
     DABX_HIP(hipMemcpy(D.layout_off, lo.data(), sizeof(unsigned long long) * 3 * S * M, hipMemcpyHostToDevice));
     std::vector<int32_t> ids(subch_id_host.begin(), subch_id_host.begin() + S * M);
@@ -159,6 +163,7 @@ int dabx_engine::delivery_begin(DeliverDev *dv, int *slot, int *devslab)
   dv->frames_done = D.frames_done; dv->cif_done = D.cif_done; dv->sf_done = D.sf_done;
   dv->hdr = D.hdr; dv->hdr.seq = seq;
   dv->off_mp2_audio = D.ext.off_mp2_audio;
+  dv->off_aac = D.ext.off_aac;
   // two transfers when the slab has a tail of logical frames worth a transfer of its own (SDMA path)
   const size_t lf_from = (size_t)D.hdr.off_msc;
   const bool split = D.copy_engine == 0 && D.bytes > lf_from && D.bytes - lf_from >= ((size_t)1 << 20) && !dev.fic_only && dev.max_subch > 0 && dev.msc_out;
@@ -332,7 +337,7 @@ extern "C" {
 
 int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
 {
-  if (!e || (cfg && (cfg->host_slabs < 0 || cfg->host_slabs == 1 || cfg->host_slabs > 64 || (cfg->what & ~1023) || cfg->copy_engine < 0 || cfg->copy_engine > 1))) {
+  if (!e || (cfg && (cfg->host_slabs < 0 || cfg->host_slabs == 1 || cfg->host_slabs > 64 || (cfg->what & ~(1023 | DABX_DELIVER_AAC)) || cfg->copy_engine < 0 || cfg->copy_engine > 1))) {
     set_error("dabx_delivery_open: bad argument");
     return DABX_E_ARG;
   }
@@ -345,6 +350,11 @@ int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
   // ... and so does DABX_DELIVER_MP2_AUDIO, alone or with DABX_DELIVER_TII: neither names anything a chunk is made of
   if (cfg && (cfg->what & DABX_DELIVER_MP2_AUDIO) && !(cfg->what & ~(DABX_DELIVER_MP2_AUDIO | DABX_DELIVER_TII))) {
     set_error("dabx_delivery_open: DABX_DELIVER_MP2_AUDIO needs at least one DABX_DELIVER_* bit below 256 beside it");
+    return DABX_E_ARG;
+  }
+  // ... and DABX_DELIVER_AAC, alone or with only those two
+  if (cfg && (cfg->what & DABX_DELIVER_AAC) && !(cfg->what & ~(DABX_DELIVER_AAC | DABX_DELIVER_MP2_AUDIO | DABX_DELIVER_TII))) {
+    set_error("dabx_delivery_open: DABX_DELIVER_AAC needs at least one DABX_DELIVER_* bit below 256 beside it");
     return DABX_E_ARG;
   }
   if (e->dl.open) { set_error("dabx_delivery_open: already open"); return DABX_E_STATE; }
@@ -378,12 +388,13 @@ int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
   if (M && !d.fic_only) cap += S * ((size_t)4 * F * per_cif + (size_t)DL_SF_CAP * 5 * per_cif + 2 * 16 * M + M * DL_SF_CAP * sizeof(dabx_superframe_info));
   // ... and the data-group, the PAD and the MOT section
   if ((rc = e->pkt.download(d.max_subch)) || (rc = e->pad.download(d.max_subch)) || (rc = e->mot.download(d.max_subch)) ||
-      (rc = e->car.download(d.max_subch)) || (rc = e->mpa.download(d.max_subch))) return rc;
+      (rc = e->car.download(d.max_subch)) || (rc = e->mpa.download(d.max_subch)) || (rc = e->aac.download(d.max_subch))) return rc;
   cap += section_capacity(e->pkt, S * M * sizeof(dabx_chunk_dg)) + section_capacity(e->pad, S * M * sizeof(dabx_chunk_pad)) +
          section_capacity(e->mot, S * M * sizeof(dabx_chunk_mot)) + section_capacity(e->car, S * M * sizeof(dabx_chunk_mot));
   if (D.eti()) cap += 16 + S * sizeof(dabx_chunk_eti) + 256 + S * 4 * F * DABX_ETI_FRAME_BYTES;      // ... and the ETI section: its table and 4 F rows per stream
   if (D.tii()) cap += sizeof(dabx_chunk_header_ext) + 16 + S * (sizeof(dabx_chunk_tii) + 4 * (size_t)DABX_TII_EVENT_SLOT_BYTES);   // ... and the TII section
   if (D.mp2_audio()) cap += (D.tii() ? 0 : sizeof(dabx_chunk_header_ext)) + section_capacity(e->mpa, S * M * sizeof(dabx_chunk_mp2_audio));   // ... and the MP2 audio section
+  if (D.aac()) cap += (D.tii() || D.mp2_audio() ? 0 : sizeof(dabx_chunk_header_ext)) + section_capacity(e->aac, S * M * sizeof(dabx_chunk_aac));   // ... and the AAC section
   D.capacity = align_up(cap, 4096);
 #define H(x) do { hipError_t err__ = (x); if (err__ != hipSuccess) { set_error("HIP error %d (%s) at %s:%d", (int)err__, hipGetErrorString(err__), __FILE__, __LINE__); delivery_free(e); return DABX_E_HIP; } } while (0)
   if (D.copy_engine == 1) H(hipStreamCreateWithFlags(&D.cs, hipStreamNonBlocking));

@@ -144,6 +144,8 @@ static_assert(sizeof(dabx_carousel_stats) == 128 && sizeof(dabx_carousel_config)
 static_assert(sizeof(dabx_mp2_sync_stats) == 64 && offsetof(dabx_pad_config, source) == 4, "include/dabx.h: PAD of MP2 frames");
 static_assert(sizeof(dabx_mp2_audio_frame) == 32 && sizeof(dabx_mp2_audio_stats) == 64 && sizeof(dabx_mp2_audio_config) == 32 && offsetof(dabx_mp2_audio_frame, flags) == 28,
               "include/dabx.h: MP2 audio records");
+static_assert(sizeof(dabx_aac_frame) == 32 && sizeof(dabx_aac_stream_stats) == 64 && sizeof(dabx_aac_stream_config) == 32 && offsetof(dabx_aac_frame, flags) == 23 &&
+              offsetof(dabx_aac_frame, length) == 16, "include/dabx.h: AAC stream records");
 
 extern "C" {
 
@@ -165,6 +167,7 @@ int dabx_set_packet_mode(dabx_engine *e, int stream, int j, const dabx_packet_co
   }
   if (cfg && e->pad.on(sj)) { set_error("dabx_set_packet_mode: stream %d slot %d has PAD decoding on", stream, j); return DABX_E_ARG; }
   if (cfg && e->mpa.on(sj)) { set_error("dabx_set_packet_mode: stream %d slot %d has MP2 audio decoding on", stream, j); return DABX_E_ARG; }
+  if (cfg && e->aac.on(sj)) { set_error("dabx_set_packet_mode: stream %d slot %d has the AAC stream mode on", stream, j); return DABX_E_ARG; }
   auto &tab = e->pkt;
   if (tab.host.empty()) {
     if (!cfg) return 0;
@@ -192,7 +195,7 @@ int dabx_set_packet_mode(dabx_engine *e, int stream, int j, const dabx_packet_co
   }
   if ((rc = tab.upload())) return rc;
   if ((rc = carousel_follow_packet(e))) return rc;
-  return relayout_open_delivery(e, sj, sc, e->pad, e->mot, e->car, e->mpa);
+  return relayout_open_delivery(e, sj, sc, e->pad, e->mot, e->car, e->mpa, e->aac);
 }
 
 int dabx_read_datagroups(dabx_engine *e, int stream, int j, int n, dabx_datagroup_info *info, uint8_t *bytes, size_t max_bytes)
@@ -266,7 +269,7 @@ int dabx_set_pad_mode(dabx_engine *e, int stream, int j, const dabx_pad_config *
   if ((rc = tab.upload())) return rc;
   pad_count_sources(e);
   if ((rc = mot_follow_pad(e))) return rc;
-  return relayout_open_delivery(e, sj, sc, e->pkt, e->mot, e->car, e->mpa);
+  return relayout_open_delivery(e, sj, sc, e->pkt, e->mot, e->car, e->mpa, e->aac);
 }
 
 int dabx_get_mp2_sync_stats(dabx_engine *e, int stream, int j, dabx_mp2_sync_stats *out)
@@ -354,7 +357,7 @@ int dabx_set_mp2_audio_mode(dabx_engine *e, int stream, int j, const dabx_mp2_au
     }
   }
   if ((rc = tab.upload())) return rc;
-  return relayout_open_delivery(e, sj, sc, e->pkt, e->pad, e->mot, e->car);
+  return relayout_open_delivery(e, sj, sc, e->pkt, e->pad, e->mot, e->car, e->aac);
 }
 
 int dabx_read_mp2_audio(dabx_engine *e, int stream, int j, int n, dabx_mp2_audio_frame *recs, uint8_t *pcm, size_t max_bytes)
@@ -377,6 +380,67 @@ int dabx_get_mp2_audio_stats(dabx_engine *e, int stream, int j, dabx_mp2_audio_s
   out->decode_calls = a.decode_calls; out->frames_out = a.frames_out; out->bad_header = a.bad_header; out->refused = a.refused; out->overread = a.overread;
   out->sample_rate = st.m.sample_rate; out->frames_lost = (int32_t)std::min<long long>(e->mpa.host[sj].lost, INT32_MAX);
   out->number_of_frames = (int16_t)a.number_of_frames; out->error_frames = (int16_t)a.error_frames; out->voffs = (int16_t)a.voffs; out->active = 1;
+  return 0;
+}
+
+// ---- AAC stream (aac_core.h, k_aac_stream) ------------------------------------------------------------------------------------------------
+int dabx_set_aac_stream_mode(dabx_engine *e, int stream, int j, const dabx_aac_stream_config *cfg)
+{
+  if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch) { set_error("dabx_set_aac_stream_mode: bad argument"); return DABX_E_ARG; }
+  if (cfg && cfg->size < sizeof(dabx_aac_stream_config)) { set_error("dabx_set_aac_stream_mode: bad configuration (size %u)", cfg->size); return DABX_E_ARG; }
+  if (cfg && cfg->format != 0) { set_error("dabx_set_aac_stream_mode: unknown format %d (0 = LOAS)", cfg->format); return DABX_E_ARG; }
+  if (cfg) for (int r : cfg->reserved) if (r) { set_error("dabx_set_aac_stream_mode: a reserved word is not 0"); return DABX_E_ARG; }
+  int rc;
+  if ((rc = sync_all(e))) return rc;
+  const size_t sj = (size_t)stream * e->dev.max_subch + j;
+  SubchDev sc;
+  DABX_HIP(hipMemcpy(&sc, e->dev.subch + sj, sizeof(SubchDev), hipMemcpyDeviceToHost));
+  if (!(cfg == nullptr && e->aac.on(sj)) && (!sc.active || sc.dab_plus != 1 || e->pkt.on(sj) || !e->dev.sf_info)) {
+    set_error("dabx_set_aac_stream_mode: stream %d slot %d is %s", stream, j, !sc.active ? "not active" : e->pkt.on(sj) ? "in packet mode" : "not a DAB+ slot");
+    return DABX_E_ARG;
+  }
+  auto &tab = e->aac;
+  if (tab.host.empty()) {
+    if (!cfg) return 0;
+    tab.host.resize((size_t)e->dev.n_streams * e->dev.max_subch);
+    tab.index.assign(tab.host.size(), -1);
+  }
+  if ((rc = tab.download(e->dev.max_subch))) return rc;
+  tab.drop(sj);
+  if (cfg) {
+    decltype(e->aac)::Host h;
+    h.on = true;
+    h.st.s = stream; h.st.j = j; h.st.sf_seen = sc.sf_count;           // the walk starts with the next super frame completed
+    const uint32_t batch = aac_batch_bytes(sc.kbps);                   // (aac_core.h has the derivation)
+    if (!out_ring_create(&h.st.out, pow2_at_least(2 * (size_t)batch), AAC_REC_RING, AAC_MAX_FRAME_BYTES, AAC_DL_REC_CAP, batch)) {
+      set_error("dabx_set_aac_stream_mode: out of device memory");
+      (void)tab.upload();
+      return DABX_E_NOMEM;
+    }
+    tab.host[sj] = h;
+  }
+  if ((rc = tab.upload())) return rc;
+  return relayout_open_delivery(e, sj, sc, e->pkt, e->pad, e->mot, e->car, e->mpa);
+}
+
+int dabx_read_aac_frames(dabx_engine *e, int stream, int j, int n, dabx_aac_frame *recs, uint8_t *bytes, size_t max_bytes)
+{
+  if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch || n <= 0 || !recs) { set_error("dabx_read_aac_frames: bad argument"); return DABX_E_ARG; }
+  return ring_read(e, e->aac, (size_t)stream * e->dev.max_subch + j, n, recs, bytes, max_bytes);
+}
+
+int dabx_get_aac_stream_stats(dabx_engine *e, int stream, int j, dabx_aac_stream_stats *out)
+{
+  if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch || !out) { set_error("dabx_get_aac_stream_stats: bad argument"); return DABX_E_ARG; }
+  memset(out, 0, sizeof(*out));
+  out->launches = e->aac_launches;
+  const size_t sj = (size_t)stream * e->dev.max_subch + j;
+  if (!e->aac.on(sj)) return sync_all(e);
+  AacStreamSlot st;
+  long long lo = 0;
+  if (int rc = ring_window(e, e->aac, sj, &st, &lo)) return rc;
+  out->superframes = st.superframes; out->records = st.records; out->frames = st.frames; out->frame_bytes = st.frame_bytes;
+  out->lost_len = st.lost_len; out->lost_crc = st.lost_crc; out->lost = e->aac.host[sj].lost;
   return 0;
 }
 
@@ -430,7 +494,7 @@ int dabx_set_mot_mode(dabx_engine *e, int stream, int j, const dabx_mot_config *
     }
   }
   if ((rc = tab.upload())) return rc;
-  return relayout_open_delivery(e, sj, sc, e->pkt, e->pad, e->car, e->mpa);
+  return relayout_open_delivery(e, sj, sc, e->pkt, e->pad, e->car, e->mpa, e->aac);
 }
 
 int dabx_read_mot_objects(dabx_engine *e, int stream, int j, int n, dabx_mot_object *info, uint8_t *bytes, size_t max_bytes)
@@ -527,7 +591,7 @@ int dabx_set_carousel_mode(dabx_engine *e, int stream, int j, const dabx_carouse
     }
   }
   if ((rc = tab.upload())) return rc;
-  return relayout_open_delivery(e, sj, sc, e->pkt, e->pad, e->mot, e->mpa);
+  return relayout_open_delivery(e, sj, sc, e->pkt, e->pad, e->mot, e->mpa, e->aac);
 }
 
 int dabx_get_carousel_stats(dabx_engine *e, int stream, int j, dabx_carousel_stats *out)

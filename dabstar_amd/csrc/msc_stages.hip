@@ -6,6 +6,7 @@
 //   k_pad          PAD of the DAB+ access units: dynamic labels and X-PAD MSC data groups (mp4processor.cpp:345-353, pad_handler.cpp:67-547)
 //   k_pad_mp2      PAD of DAB (MP2) audio frames: MP2 frame sync over the logical frames and the same PadHandler (mp2processor.cpp:611-747)
 //   k_mp2_audio    MP2 audio of DAB audio slots: frame assembly and the MP2 decoder, 1152 stereo samples per MP2 frame (mp2processor.cpp:292-609, :678-763)
+//   k_aac_stream   LOAS/LATM frames of the DAB+ access units that passed their CRC, one record per access unit (mp4processor.cpp:320-391, :395-445)
 //   k_mot          MOT objects out of the X-PAD data groups the two PAD kernels have just emitted (pad_handler.cpp:553-622, mot_object.cpp:71-323)
 //   k_carousel     MOT objects out of the MSC data groups k_packet has just completed: MotHandler and MotDirectory (mot_handler.cpp:69-259,
 //                  mot_dir.cpp:28-156); launched right behind k_packet
@@ -17,6 +18,7 @@
 #include "mot_core.h"
 #include "carousel_core.h"
 #include "mp2_core.h"
+#include "aac_core.h"
 #include "fec_core.h"
 #include "wave_ops.h"
 
@@ -692,6 +694,79 @@ __global__ __launch_bounds__(256) void k_mp2_audio(Mp2AudioDev ad)
   if (tid == 0) { as.m = m; as.a = a; as.out.count = n_recs; as.out.n_bytes = n_bytes; }
 }
 
+// ------------------------------------------------------------------------------------------- AAC stream
+// One wave per DAB+ slot whose access units are framed (AacStreamDev::slots: those slots only), behind k_dabplus, beside the PAD stage:
+// walks the super frames k_dabplus has completed since the slot's last visit as k_pad does (SubchDev::sf_count against
+// AacStreamSlot::sf_seen) and their dabx_superframe_info records -- no CRC runs here.  Per super frame, staged in LDS with dword loads:
+// lane a < num_aus computes L, the verdict and the LOAS frame's length of access unit a (aac_core.h, aac_au: mp4processor.cpp:320-333,
+// :377), a prefix sum over the lanes gives every access unit its byte_pos, lanes 0 .. num_aus - 1 store the records, and the frames are
+// written straight to their place in the slot's byte ring, a byte per lane: the header from one of two templates (aac_header), everything
+// behind it a copy shifted by 5 or 6 bits (aac_frame_byte).  A length-good access unit lies inside the super frame (k_dabplus's length
+// check), so every LDS read does.  LDS: 5280 bytes.  include/dabx.h "AAC stream" states the semantics; there is no guard on the output's
+// size.
+__global__ __launch_bounds__(64) void k_aac_stream(AacStreamDev ad)
+{
+  const int lane = threadIdx.x;
+  AacStreamSlot &as = ad.slots[blockIdx.x];
+  const size_t sj = (size_t)as.s * ad.max_subch + as.j;
+  const SubchDev &sc = ad.subch[sj];
+  if (!sc.active || !sc.dab_plus || sc.kbps > 384) return;
+  const long long have = sc.sf_count;
+  long long seen = as.sf_seen;
+  if (have <= seen) return;
+  if (have - seen > SF_SLOTS) seen = have - SF_SLOTS;         // (cannot happen: the stage runs behind every batch)
+  const int end = 110 * (sc.kbps / 8);
+  __shared__ __attribute__((aligned(16))) uint8_t sfb[110 * 48];
+  uint8_t *const ring = as.out.bytes;                            // (locals: the stores below must not make the loop reload them from the table)
+  dabx_aac_frame *const recs = as.out.recs;
+  const unsigned long long bytes_mask = as.out.bytes_mask, rec_mask = as.out.rec_mask;
+  long long n_recs = as.out.count, n_bytes = as.out.n_bytes;
+  long long frames = 0, lost_len = 0, lost_crc = 0;
+  const long long recs0 = n_recs, bytes0 = n_bytes;
+  for (long long sf = seen; sf < have; sf++) {
+    const size_t slot = sj * SF_SLOTS + (size_t)(sf % SF_SLOTS);
+    const dabx_superframe_info *inf = ad.sf_info + slot;
+    __syncthreads();                                             // the previous super frame's bytes are done with
+    {
+      const uint32_t *src = reinterpret_cast<const uint32_t *>(ad.sf_out + slot * ad.sf_stride);
+      for (int i = lane; i < (end + 3) / 4; i += 64) reinterpret_cast<uint32_t *>(sfb)[i] = src[i];
+    }
+    __syncthreads();
+    const int n_au = min((int)inf->num_aus, 6);
+    const unsigned parms = inf->stream_parms;
+    const int sbr = (parms >> 5) & 1;
+    AacAu u{0, 0, 0};
+    if (lane < n_au) u = aac_au(*inf, lane);                     // mp4processor.cpp:320-333
+    const int incl = row_prefix_sum_int(u.length);               // (lanes 0 .. 5: one row of 16)
+    const int off = incl - u.length, total = __shfl(incl, 15);
+    if (lane < n_au) {                           // the 32 bytes of a dabx_aac_frame as four little-endian words
+      unsigned long long *o = reinterpret_cast<unsigned long long *>(recs + (size_t)((unsigned long long)(n_recs + lane) & rec_mask));
+      o[0] = (unsigned long long)(n_bytes + off); o[1] = (unsigned long long)inf->first_frame;
+      o[2] = (unsigned long long)(u.length & 0xFFFF) | ((unsigned long long)(u.L & 0xFFFF) << 16) | ((unsigned long long)lane << 32) |
+             ((unsigned long long)n_au << 40) | ((unsigned long long)parms << 48) | ((unsigned long long)u.flags << 56);
+      o[3] = 0;
+    }
+    frames += __popcll(__ballot(lane < n_au && u.flags == 0));
+    lost_len += __popcll(__ballot(lane < n_au && u.flags == DABX_AAC_LOST_LEN));
+    lost_crc += __popcll(__ballot(lane < n_au && u.flags == DABX_AAC_LOST_CRC));
+    for (int a = 0; a < n_au; a++) {
+      const int len = __shfl(u.length, a);
+      if (len == 0) continue;                                    // :325-331, :377-382: the reference conceals
+      const int L = __shfl(u.L, a);
+      const long long at = n_bytes + __shfl(off, a);
+      const uint8_t *au = sfb + inf->au_start[a];
+      const AacHeader h = aac_header(parms, len);                // :399-432
+      for (int i = lane; i < len; i += 64) ring[(size_t)((unsigned long long)(at + i) & bytes_mask)] = (uint8_t)aac_frame_byte(h, sbr, L, au, i);
+    }
+    n_recs += n_au; n_bytes += total;
+  }
+  if (lane == 0) {
+    as.sf_seen = have; as.out.count = n_recs; as.out.n_bytes = n_bytes;
+    as.superframes += have - seen; as.records += n_recs - recs0; as.frames += frames; as.frame_bytes += n_bytes - bytes0;
+    as.lost_len += lost_len; as.lost_crc += lost_crc;
+  }
+}
+
 // --------------------------------------------------------------------------------------------------- MOT
 // One wave per MOT-enabled PAD slot (MotDev::slots: those slots only), behind k_pad and k_pad_mp2: walks the items the slot's PAD kernel has
 // emitted since this slot's last visit (PadSlot::out.count against MotSlot::items_seen) out of the PAD rings and takes the
@@ -874,6 +949,20 @@ int launch_mp2_audio_stage(const EngineDev &e, const Mp2AudioDev *ma, hipStream_
   Mp2AudioDev q = *ma;
   q.max_subch = e.max_subch; q.msc_stride = e.msc_stride; q.subch = e.subch; q.snap = e.snap; q.msc_out = e.msc_out;
   hipLaunchKernelGGL(k_mp2_audio, dim3(q.n), dim3(256), 0, st, q);
+  DABX_HIP(hipGetLastError());
+  *used = q;
+  return 0;
+}
+
+// behind k_dabplus, beside the PAD stage: k_aac_stream walks the super frames just completed of the slots whose access units are framed.
+// No marker: the profile table has no row for it (dabx_aac_stream_stats.launches counts; tools/bench_aac_stream.py times it)
+int launch_aac_stream_stage(const EngineDev &e, const AacStreamDev *aa, hipStream_t st, AacStreamDev *used)
+{
+  *used = AacStreamDev{};
+  if (!aa || aa->n <= 0 || !e.sf_info) return 0;
+  AacStreamDev q = *aa;
+  q.max_subch = e.max_subch; q.sf_stride = e.sf_stride; q.subch = e.subch; q.sf_out = e.sf_out; q.sf_info = e.sf_info;
+  hipLaunchKernelGGL(k_aac_stream, dim3(q.n), dim3(64), 0, st, q);
   DABX_HIP(hipGetLastError());
   *used = q;
   return 0;

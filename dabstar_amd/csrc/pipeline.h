@@ -177,6 +177,7 @@ struct DeliverDev {
   long long *cif_done, *sf_done;          // [S * max_subch] logical / super frames of the slot delivered so far
   dabx_chunk_header hdr;                  // as it goes into the slab
   unsigned long long off_mp2_audio;       // dabx_chunk_header_ext.off_mp2_audio of the slab (0: it has no MP2 audio section)
+  unsigned long long off_aac;             // dabx_chunk_header_ext.off_aac of the slab (0: it has no AAC section)
   // host side only: recorded behind k_deliver_lf (the chunk's logical frames are in the slab: their share of the transfer may start while the
   // DAB+ stage still runs); null = one transfer behind everything
   hipEvent_t lf_done;
@@ -385,12 +386,14 @@ struct PadDev;                    // pad_core.h
 struct MotDev;                    // mot_core.h
 struct CarouselDev;               // carousel_core.h
 struct Mp2AudioDev;               // mp2_core.h
+struct AacStreamDev;              // aac_core.h
 // pipeline.hip
 extern const char *const kStepKernelNames[N_STEP_KERNELS];
 int launch_front_step(const EngineDev &e, EngineStreams &ss, Marker &mk, bool async_acquire, bool all_locked);
 int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineStreams &ss, Marker &mk, const DeliverDev *dv = nullptr,
                      hipStream_t *tail = nullptr, const PacketDev *pk = nullptr, const PadDev *pad = nullptr, const MotDev *mot = nullptr,
-                     const CarouselDev *car = nullptr, const EtiDev *eti = nullptr, const Mp2AudioDev *mp2a = nullptr, long long *mp2a_launches = nullptr);
+                     const CarouselDev *car = nullptr, const EtiDev *eti = nullptr, const Mp2AudioDev *mp2a = nullptr, long long *mp2a_launches = nullptr,
+                     const AacStreamDev *aac = nullptr, long long *aac_launches = nullptr);
 int launch_dciq(const EngineDev &e, int mode, hipStream_t st);
 int launch_level_exact(const EngineDev &e, hipStream_t st);
 int launch_commit(const EngineDev &e, int stream, unsigned long long n, hipStream_t st);
@@ -415,6 +418,7 @@ int launch_deliver_pad(const EngineDev &e, const DeliverDev &dv, const PadDev &p
 int launch_deliver_mot(const EngineDev &e, const DeliverDev &dv, const MotDev &md, hipStream_t st);
 int launch_deliver_carousel(const EngineDev &e, const DeliverDev &dv, const CarouselDev &cd, hipStream_t st, bool clear_table);
 int launch_deliver_mp2_audio(const EngineDev &e, const DeliverDev &dv, const Mp2AudioDev &ad, unsigned long long off_mp2_audio, hipStream_t st);
+int launch_deliver_aac(const EngineDev &e, const DeliverDev &dv, const AacStreamDev &ad, unsigned long long off_aac, hipStream_t st);
 int launch_deliver_ext(const dabx_chunk_header_ext &ext, uint8_t *slab, hipStream_t st);           // at chunk close, front-end stream: the header's extension of a slab without a TII section
 int launch_deliver_tii(const EngineDev &e, const TiiDeliverDev &td, hipStream_t st);                // at chunk close, front-end stream, behind launch_deliver_front
 int launch_eti_front(const EngineDev &e, const EtiDev &t, hipStream_t st, Marker &mk);              // at chunk close, front-end stream
@@ -425,6 +429,7 @@ int launch_packet_stage(const EngineDev &e, const PacketDev *pk, hipStream_t st,
 int launch_pad_stage(const EngineDev &e, const PadDev *pad, hipStream_t st, Marker &mk, PadDev *used);
 int launch_mot_stage(const EngineDev &e, const MotDev *mot, const PadDev &pad, hipStream_t st, Marker &mk, MotDev *used);
 int launch_mp2_audio_stage(const EngineDev &e, const Mp2AudioDev *ma, hipStream_t st, Mp2AudioDev *used);
+int launch_aac_stream_stage(const EngineDev &e, const AacStreamDev *aa, hipStream_t st, AacStreamDev *used);
 int launch_carousel_stage(const EngineDev &e, const CarouselDev *car, const PacketDev &pk, hipStream_t st, Marker &mk, CarouselDev *used);
 // fib.cpp
 void dabx_internal_fibdec_skip(dabx_fibdec *d, long long n_fibs);     // FIBs the decoder never saw (they had left the ring)

@@ -22,6 +22,7 @@
 #include "mot_core.h"
 #include "carousel_core.h"
 #include "mp2_core.h"
+#include "aac_core.h"
 #include <algorithm>
 #include "ofdm_core.h"
 #include "viterbi_core.h"
@@ -1830,7 +1831,7 @@ int launch_front_step(const EngineDev &e_in, EngineStreams &ss, Marker &mk, bool
 // they emitted.
 int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineStreams &ss, Marker &mk, const DeliverDev *dv, hipStream_t *tail,
                      const PacketDev *pk, const PadDev *pad, const MotDev *mot, const CarouselDev *car, const EtiDev *eti, const Mp2AudioDev *mp2a,
-                     long long *mp2a_launches)
+                     long long *mp2a_launches, const AacStreamDev *aac, long long *aac_launches)
 {
   const DevTables *t;
   int rc = get_tables(&t);
@@ -1922,6 +1923,7 @@ int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineSt
   MotDev m;
   CarouselDev c;
   Mp2AudioDev au;
+  AacStreamDev ac;
   if ((rc = launch_packet_stage(e, pk, sb, mk, &p))) return rc;
   if ((rc = launch_carousel_stage(e, car, p, sb, mk, &c))) return rc;
   if ((rc = launch_dabplus_stage(e, sb, mk))) return rc;
@@ -1929,6 +1931,8 @@ int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineSt
   if ((rc = launch_mot_stage(e, mot, q, sb, mk, &m))) return rc;
   if ((rc = launch_mp2_audio_stage(e, mp2a, sb, &au))) return rc;     // MP2 audio of the slots that have the mode on: launched only when there is one
   if (au.n > 0 && mp2a_launches) ++*mp2a_launches;
+  if ((rc = launch_aac_stream_stage(e, aac, sb, &ac))) return rc;     // LOAS frames of the slots that have the mode on: launched only when there is one
+  if (ac.n > 0 && aac_launches) ++*aac_launches;
   if (dv && (rc = launch_deliver_msc(e, *dv, sb, !dv->lf_done))) return rc;
   if (dv && eti && !dv->lf_done && (rc = launch_eti_back(e, *eti, sb, mk, false))) return rc;      // (one transfer behind everything: here)
   if (dv && p.n > 0 && (rc = launch_deliver_dg(e, *dv, p, sb))) return rc;      // the slab's data-group section (head part, like the gather in front)
@@ -1936,6 +1940,7 @@ int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineSt
   if (dv && m.n > 0 && (rc = launch_deliver_mot(e, *dv, m, sb))) return rc;     // ... and its MOT section
   if (dv && c.n > 0 && (rc = launch_deliver_carousel(e, *dv, c, sb, m.n <= 0))) return rc;      // ... the carousel slots' rows of it
   if (dv && au.n > 0 && (rc = launch_deliver_mp2_audio(e, *dv, au, dv->off_mp2_audio, sb))) return rc;      // ... and its MP2 audio section
+  if (dv && ac.n > 0 && (rc = launch_deliver_aac(e, *dv, ac, dv->off_aac, sb))) return rc;      // ... and its AAC section
   if (tail) *tail = sb;
   if (ss.b) {
     DABX_HIP(hipEventRecord(ss.msc_done, ss.b));

@@ -46,4 +46,15 @@ __device__ __forceinline__ int wave_min_int(int v)
   return (int)wave_butterfly_u32((unsigned)v, [](unsigned a, unsigned b) { return (unsigned)((int)a < (int)b ? (int)a : (int)b); });
 }
 
+// Inclusive prefix sum within every row of 16 lanes (lane i: the sum over lanes 16 * (i / 16) .. i), in the VALU: DPP row_shr:1, 2, 4, 8 with
+// zeros shifted in.  Every lane must be active.
+__device__ __forceinline__ int row_prefix_sum_int(int v)
+{
+  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, true);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, true);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, true);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, true);
+  return v;
+}
+
 }  // namespace dabx

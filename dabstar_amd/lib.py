@@ -82,6 +82,11 @@ def load(build_if_missing=True):
         L.dabx_set_mp2_audio_mode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.dabx_read_mp2_audio.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
         L.dabx_get_mp2_audio_stats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    if hasattr(L, "dabx_set_aac_stream_mode"):       # LOAS stream of DAB+ slots
+        L.dabx_set_aac_stream_mode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.dabx_read_aac_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.dabx_get_aac_stream_stats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.dabx_internal_aac_frame_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     if hasattr(L, "dabx_announce_write"):            # (absent from libraries older than the level anchor: tools/ab.sh runs those through this binding too)
         L.dabx_announce_write.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
     _LIB = L
@@ -486,7 +491,7 @@ assert CHUNK_ETI.itemsize == 64
 DELIVER_TII = 256
 TII_MAX_RESULTS = 32
 CHUNK_EXT_MAGIC = 0x45584244                     # "DBXE"
-CHUNK_HEADER_EXT = np.dtype([("magic", "<u4"), ("bytes", "<u4"), ("off_tii", "<u8"), ("off_mp2_audio", "<u8"), ("reserved", "<u8", 5)])
+CHUNK_HEADER_EXT = np.dtype([("magic", "<u4"), ("bytes", "<u4"), ("off_tii", "<u8"), ("off_mp2_audio", "<u8"), ("off_aac", "<u8"), ("reserved", "<u8", 4)])
 CHUNK_TII = np.dtype([("first_event", "<i8"), ("n_events", "<i4"), ("events_lost", "<i4"), ("ev_off", "<u8"), ("events_total", "<i8")])
 TII_EVENT = np.dtype([("frame", "<i8"), ("n_results", "<i4"), ("n_found", "<i4"), ("frames_in_sum", "<i4"), ("epoch", "<i4"),
                       ("threshold_db", "<i4"), ("reserved", "<i4")])
@@ -564,6 +569,43 @@ assert MP2_AUDIO_FRAME.itemsize == 32 and MP2_AUDIO_STATS.itemsize == 64 and CHU
 class Mp2AudioConfig(C.Structure):
     """dabx_mp2_audio_config."""
     _fields_ = [("size", C.c_uint32), ("reserved", C.c_int32 * 7)]
+
+
+# AAC stream (include/dabx.h "AAC stream"): dabx_aac_frame, one record per access unit of a DAB+ slot -- a LOAS/LATM frame of `length` bytes
+# or, with length 0, a lost one (AAC_LOST_LEN / AAC_LOST_CRC: where the reference conceals) --, dabx_aac_stream_stats, and the slab's AAC
+# section (DELIVER_AAC = 2048, opt-in like DELIVER_ETI; 1024 stays refused; announced by the header's extension): one CHUNK_AAC per
+# (stream, slot), all zero for a slot without the mode
+DELIVER_AAC = 2048
+AAC_LOST_LEN, AAC_LOST_CRC = 1, 2            # dabx_aac_frame.flags
+AAC_MAX_FRAME_BYTES = 974
+AAC_FRAME = np.dtype([("byte_pos", "<i8"), ("first_frame", "<i8"), ("length", "<u2"), ("au_len", "<u2"), ("au", "u1"), ("num_aus", "u1"),
+                      ("stream_parms", "u1"), ("flags", "u1"), ("reserved", "u1", 8)])
+AAC_STREAM_STATS = np.dtype([(k, "<i8") for k in ("superframes", "records", "frames", "frame_bytes", "lost_len", "lost_crc", "launches", "lost")])
+CHUNK_AAC = np.dtype([("first_frame", "<i8"), ("n_frames", "<i4"), ("frames_lost", "<i4"), ("rec_off", "<u8"), ("bytes_off", "<u8"), ("n_bytes", "<i8")] +
+                     [(k, "<i8") for k in ("superframes", "records", "frames", "frame_bytes", "lost_len", "lost_crc")] + [("reserved", "<i8", 5)])
+assert AAC_FRAME.itemsize == 32 and AAC_STREAM_STATS.itemsize == 64 and CHUNK_AAC.itemsize == 128
+
+
+class AacStreamConfig(C.Structure):
+    """dabx_aac_stream_config."""
+    _fields_ = [("size", C.c_uint32), ("format", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+def aac_ring_bytes(kbps):
+    """Size of the byte ring of an AAC stream slot: the next power of two >= two batches of in-order super frames."""
+    n = 1
+    while n < 2 * 6 * (110 * (kbps // 8) + 72):
+        n <<= 1
+    return n
+
+
+def aac_frame_host(au, stream_parms):
+    """The LOAS frame (uint8 array) of one access unit of len(au) <= 960 bytes, built on the host by the pieces of k_aac_stream lane after
+    lane (dabx_internal_aac_frame_host: a test entry, not part of include/dabx.h).  Needs no device."""
+    au = np.ascontiguousarray(au, np.uint8)
+    out = np.zeros(AAC_MAX_FRAME_BYTES, np.uint8)
+    n = check(load().dabx_internal_aac_frame_host(_p(au) if len(au) else None, len(au), int(stream_parms), _p(out)))
+    return out[:n].copy()
 
 
 # MOT objects of the X-PAD (include/dabx.h): dabx_mot_object, one record per signal_new_mot_object, dabx_mot_stats and the slab's MOT
@@ -665,6 +707,7 @@ class Chunk:
         self.header_ext = None                  # the header's extension (CHUNK_HEADER_EXT) when `what` has a bit >= 256, else None
         self.tii_table = None                   # the TII section: [S] CHUNK_TII, or None when the slab has none
         self.mp2_audio_table = None             # the MP2 audio section: [S, M] CHUNK_MP2_AUDIO, or None when the slab has none
+        self.aac_table = None                   # the AAC section: [S, M] CHUNK_AAC, or None when the slab has none
         if int(h["what"]) & ~255:
             self.header_ext = self.raw[128:192].view(CHUNK_HEADER_EXT)[0]
             if int(self.header_ext["magic"]) != CHUNK_EXT_MAGIC or int(self.header_ext["bytes"]) < 64:
@@ -675,6 +718,9 @@ class Chunk:
             if int(self.header_ext["off_mp2_audio"]):
                 o = int(self.header_ext["off_mp2_audio"])
                 self.mp2_audio_table = self.raw[o:o + S * M * 128].view(CHUNK_MP2_AUDIO).reshape(S, M)
+            if int(self.header_ext["off_aac"]):
+                o = int(self.header_ext["off_aac"])
+                self.aac_table = self.raw[o:o + S * M * 128].view(CHUNK_AAC).reshape(S, M)
         self.eti_table = None                   # the ETI section: [S] CHUNK_ETI, or None when the slab has none
         if int(h["off_eti"]):
             self.eti_table = self.raw[int(h["off_eti"]):int(h["off_eti"]) + S * 64].view(CHUNK_ETI)
@@ -749,6 +795,13 @@ class Chunk:
         frame i's samples are bytes[4608 i : 4608 (i + 1)].view(int16).reshape(1152, 2), left and right.  Empty when the slab has no MP2
         audio section or the slot has not the mode on."""
         return self._ring_items(self.mp2_audio_table, "rec_off", "n_frames", MP2_AUDIO_FRAME, s, j)
+
+    def aac(self, s, j):
+        """The LOAS stream of slot (s, j) in this chunk: (its CHUNK_AAC record or None, [n_frames] AAC_FRAME, their n_bytes bytes), views;
+        record i's frame is bytes[byte_pos[i] : byte_pos[i] + length[i]] and the bytes are the slot's stream as it is.  None and empty when
+        the slab has no AAC section or the slot has not the mode on."""
+        rec, by = self._ring_items(self.aac_table, "rec_off", "n_frames", AAC_FRAME, s, j)
+        return (self.aac_table[s, j] if self.aac_table is not None and int(self.aac_table[s, j]["rec_off"]) else None), rec, by
 
     def release(self):
         if self._eng is not None:
@@ -1113,6 +1166,34 @@ class Engine:
         st = {k: int(out[0][k]) for k in MP2_AUDIO_STATS.names}
         st["pcm_bytes"] = MP2_PCM_BYTES * st["frames_out"]
         return st
+
+    def set_aac_stream_mode(self, stream, j, on=True):
+        """Switches the LOAS framing of DAB+ slot j of `stream` on (restarting it with empty rings when it is on already) or off
+        (dabx_set_aac_stream_mode).  Independent of the slot's PAD and MOT modes."""
+        L = load()
+        if not on:
+            check(L.dabx_set_aac_stream_mode(self._h, int(stream), int(j), None))
+        else:
+            cfg = AacStreamConfig(size=C.sizeof(AacStreamConfig), format=0)
+            check(L.dabx_set_aac_stream_mode(self._h, int(stream), int(j), C.byref(cfg)))
+
+    def read_aac_frames(self, stream, j, n=128, max_bytes=None):
+        """(records [k] AAC_FRAME, bytes uint8) of the newest k <= n access units of slot j, oldest first; record i's LOAS frame is
+        bytes[byte_pos[i] : byte_pos[i] + length[i]] (length 0: a lost access unit), and `bytes` is that stretch of the slot's stream."""
+        info = np.zeros(max(1, n), AAC_FRAME)
+        if max_bytes is None:
+            max_bytes = n * AAC_MAX_FRAME_BYTES
+        buf = np.zeros(max(1, int(max_bytes)), np.uint8)
+        k = check(load().dabx_read_aac_frames(self._h, int(stream), int(j), int(n), _p(info), _p(buf), int(max_bytes)))
+        info = info[:k]
+        total = int(info["byte_pos"][-1]) + int(info["length"][-1]) if k else 0
+        return info, buf[:total].copy()
+
+    def aac_stream_stats(self, stream, j):
+        """dabx_aac_stream_stats of slot j as a dict (all zero but `launches` unless the mode is on)."""
+        out = np.zeros(1, AAC_STREAM_STATS)
+        check(load().dabx_get_aac_stream_stats(self._h, int(stream), int(j), _p(out)))
+        return {k: int(out[0][k]) for k in AAC_STREAM_STATS.names}
 
     def mp2_sync_stats(self, stream, j):
         """dabx_mp2_sync_stats of slot j as a dict (all zero unless the slot is a PAD slot with source "mp2")."""

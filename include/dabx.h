@@ -967,7 +967,14 @@ enum { DABX_DELIVER_FIB = 1, DABX_DELIVER_MSC = 2, DABX_DELIVER_SF = 4,
           below).  Opt-in exactly like DABX_DELIVER_ETI and DABX_DELIVER_TII: what == 0 does NOT include it, the bit alone is DABX_E_ARG, and
           without the bit a slab, dabx_delivery_slab_bytes and the kernels launched are exactly what they are without it.  With the bit the
           header is followed by a dabx_chunk_header_ext; the section exists while at least one slot has the mode on */
-       DABX_DELIVER_MP2_AUDIO = 512 };
+       DABX_DELIVER_MP2_AUDIO = 512,
+       /* the LOAS/LATM stream of every DAB+ slot whose access units are framed on the device (dabx_set_aac_stream_mode; the AAC section,
+          dabx_chunk_aac below).  Opt-in exactly like DABX_DELIVER_ETI, DABX_DELIVER_TII and DABX_DELIVER_MP2_AUDIO: what == 0 does NOT include
+          it, the bit alone or with only those two is DABX_E_ARG, and without the bit a slab, dabx_delivery_slab_bytes and the kernels
+          launched are exactly what they are without it.  With the bit the header is followed by a dabx_chunk_header_ext; the section exists
+          while at least one slot has the mode on.  The value is 2048, not 1024: the mask 1024 has always been refused with DABX_E_ARG and
+          callers rely on that (tests/test_gpu_mp2_audio_delivery.py), so 1024 stays refused */
+       DABX_DELIVER_AAC = 2048 };
 typedef struct {
   int32_t host_slabs;       /* page-locked host slabs, >= 2 (0 = default 4) */
   int32_t what;             /* DABX_DELIVER_* mask, 0 = everything */
@@ -995,7 +1002,8 @@ typedef struct {
   uint32_t bytes;           /* 64 */
   uint64_t off_tii;         /* the TII section: dabx_chunk_tii[n_streams]; 0 = the slab has none */
   uint64_t off_mp2_audio;   /* the MP2 audio section: dabx_chunk_mp2_audio[n_streams * max_subch]; 0 = the slab has none */
-  uint64_t reserved[5];
+  uint64_t off_aac;         /* the AAC section: dabx_chunk_aac[n_streams * max_subch]; 0 = the slab has none */
+  uint64_t reserved[4];
 } dabx_chunk_header_ext;    /* 64 bytes */
 typedef struct {
   int64_t first_frame;      /* index, since the stream was opened, of the first frame in the chunk */
@@ -1415,6 +1423,85 @@ typedef struct {
   int64_t  sample_rate, voffs, number_of_frames, error_frames;
   int64_t  reserved[2];
 } dabx_chunk_mp2_audio;      /* 128 bytes */
+
+/* ------------------------------------------------------------------------------------------------------------
+ * AAC stream: the LOAS/LATM stream of a DAB+ audio sub-channel on the device -- the access-unit walk of Mp4Processor::_process_super_frame
+ * and _build_aac_stream over BitWriter (base/backend/audio/mp4processor.cpp:320-391, :395-445, bit_writer.cpp:29-59), k_aac_stream: one
+ * 64-thread block per slot with the mode on, behind k_dabplus on the MSC batch's stream, beside the PAD stage.  It walks the super
+ * frames k_dabplus has completed since the slot's last visit and takes k_dabplus's verdicts (dabx_superframe_info): it re-runs no CRC.
+ * Per access unit a = 0 .. num_aus - 1, in order, ONE record:
+ *   au_len_bad bit set (:325-331)                   length 0, flags DABX_AAC_LOST_LEN -- where the reference conceals
+ *   length good, au_crc_ok bit clear (:377-382)     length 0, flags DABX_AAC_LOST_CRC -- where the reference conceals
+ *   otherwise (:333-341)                            one LOAS frame of the L = au_start[a + 1] - au_start[a] - 2 payload bytes at au_start[a]
+ * so the records are the reference's sequence of "frame / conceal" events.  The bytes of a slot's frames follow each other without
+ * padding, each frame on a byte boundary: what mpFrameBuffer receives (:341, the "AAC dump") and what convert_mp4_to_pcm of the fdk-aac
+ * build is handed (:357); written to a file they play in any AAC player.  LOAS because it is the only container that can say "960-sample
+ * transform" (ADTS cannot).
+ * The frame (:399-441): 11-bit sync word 0x2B7, 13-bit audioMuxLengthBytes = size - 3 (bit_writer.cpp:54-59), StreamMuxConfig with
+ *   CoreSrIndex = dac ? (sbr ? 6 : 3) : (sbr ? 8 : 5), CoreChConfig = aacChannelMode ? 2 : 1, ExtensionSrIndex = dac ? 3 : 5
+ * (:266-269; psFlag and mpegSurround do not enter), PayloadLengthInfo of L / 255 bytes 0xFF and one byte L % 255, the payload.  The header
+ * is 69 bits without SBR and 78 with, so the payload lies 5 / 6 bits off the byte grid and the last byte ends in 3 / 2 zero bits; a frame
+ * is 10 + L / 255 + L bytes without SBR, 11 + L / 255 + L with.  L = 0 is legal (one length byte 0, no payload); L runs to 960.
+ * Unbounded output: for a super frame whose AU table is in order the access units partition it and each adds at most 12 bytes net, so it
+ * emits at most 110 * kbps / 8 + 72 bytes.  A crafted table with starts out of order can hold overlapping access units that each pass
+ * their CRC; the reference emits them all, and so does the device: there is no guard.  Such a stream simply emits more bytes; the rings
+ * lose oldest-first, counted in `lost` and in the chunk's frames_lost, as the sibling rings do.
+ * Parity with the reference's object code is unpinned (mp4processor.cpp needs the GUI's headers): the tests compare the device with a
+ * bit-serial, line-cited restatement (tests/aac_stream_cases.py).
+ * Out of scope: AAC decoding itself, the raw-AU path of the faad build (:359-364), resampling and playback, the signal_* cadence of
+ * :384-389. */
+enum { DABX_AAC_LOST_LEN = 1, DABX_AAC_LOST_CRC = 2 };      /* dabx_aac_frame.flags */
+#define DABX_AAC_MAX_FRAME_BYTES 974   /* 11 + 960 / 255 + 960 */
+typedef struct {
+  uint32_t size;             /* sizeof(dabx_aac_stream_config) of the caller */
+  int32_t  format;           /* 0: LOAS/LATM; anything else is DABX_E_ARG */
+  int32_t  reserved[6];      /* zero */
+} dabx_aac_stream_config;    /* 32 bytes */
+typedef struct dabx_aac_frame_s {
+  int64_t  byte_pos;         /* position of the frame's first byte in the slot's sequence of LOAS bytes */
+  int64_t  first_frame;      /* dabx_superframe_info.first_frame of the access unit's super frame */
+  uint16_t length;           /* bytes of the LOAS frame; 0 for a lost access unit */
+  uint16_t au_len;           /* L; for DABX_AAC_LOST_LEN the 16 low bits of the computed value */
+  uint8_t  au, num_aus;      /* the access unit's index in its super frame, and how many that has */
+  uint8_t  stream_parms;     /* dabx_superframe_info.stream_parms */
+  uint8_t  flags;            /* 0, DABX_AAC_LOST_LEN or DABX_AAC_LOST_CRC */
+  uint8_t  reserved[8];
+} dabx_aac_frame;            /* 32 bytes, little-endian, no holes */
+typedef struct {
+  int64_t superframes;       /* super frames walked */
+  int64_t records;           /* access units visited = records written */
+  int64_t frames;            /* ... of these LOAS frames */
+  int64_t frame_bytes;       /* bytes of all LOAS frames */
+  int64_t lost_len, lost_crc;      /* records with DABX_AAC_LOST_LEN / DABX_AAC_LOST_CRC */
+  int64_t launches;          /* k_aac_stream launches of the engine (the kernel has no row in the profile table) */
+  int64_t lost;              /* records that had left the rings before a dabx_read_aac_frames call could return them */
+} dabx_aac_stream_stats;     /* 64 bytes */
+/* Switches the LOAS framing of slot subch_idx of `stream` on (cfg != NULL) or off (NULL).  On: only an active DAB+ slot (dab_plus == 1)
+ * that is not in packet mode, cfg->format 0 and the reserved words 0; DABX_E_ARG otherwise.  A slot that is switched on starts with empty
+ * rings and all counts 0; the walk starts with the next super frame completed.  Independent of the slot's PAD and MOT modes.  The
+ * setting stays with the slot wherever dabx_set_subchannels says it "keeps decoding without interruption", a move included; a new or
+ * changed slot loses it, as it loses PAD decoding.  A slot with the mode on cannot become a packet-mode slot.  An engine without such a
+ * slot allocates and launches nothing for this stage.  Drains the engine. */
+int  dabx_set_aac_stream_mode(dabx_engine *e, int stream, int subch_idx, const dabx_aac_stream_config *cfg);
+/* The newest n records still in the rings, oldest first: into recs[], their LOAS frames back to back into bytes[]; byte_pos is rebased
+ * to the returned buffer.  When they exceed max_bytes the newest that fit are returned (bytes == NULL: records only).  Returns the number
+ * of records.  The rings hold two batches of in-order super frames: 128 records and the next power of two >= 2 * 6 * (110 * kbps / 8 + 72)
+ * bytes.  Drains the engine. */
+int  dabx_read_aac_frames(dabx_engine *e, int stream, int subch_idx, int n, dabx_aac_frame *recs, uint8_t *bytes, size_t max_bytes);
+int  dabx_get_aac_stream_stats(dabx_engine *e, int stream, int subch_idx, dabx_aac_stream_stats *out);
+/* The AAC section (DABX_DELIVER_AAC): one dabx_chunk_aac per (stream, slot) from dabx_chunk_header_ext.off_aac, all zero for a slot
+ * without the mode; behind the table every such slot has room for 36 records (a chunk closes at most 6 super frames of at most 6
+ * access units) and for 6 * (110 * kbps / 8 + 72) bytes -- enough for every chunk of super frames whose AU tables are in order; of more
+ * the newest that fit are delivered and the rest counted in frames_lost.  Record i's frame is the `length` bytes at bytes_off + byte_pos.
+ * Gathered behind the batch's stages like the MP2 audio section. */
+typedef struct {
+  int64_t  first_frame;      /* number, since the mode was switched on, of the first record in the chunk */
+  int32_t  n_frames, frames_lost;      /* records in the chunk; records between the previous chunk's and these that were not delivered */
+  uint64_t rec_off, bytes_off;
+  int64_t  n_bytes;
+  int64_t  superframes, records, frames, frame_bytes, lost_len, lost_crc;      /* dabx_aac_stream_stats after the chunk's batch */
+  int64_t  reserved[5];
+} dabx_chunk_aac;            /* 128 bytes */
 
 #ifdef __cplusplus
 }

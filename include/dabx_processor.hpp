@@ -231,6 +231,15 @@ public:
       if (slots_[j].kbps && slots_[j].subch_id == subChId) return dabx_set_mp2_audio_mode(eng_, 0, (int)j, on ? &cfg : nullptr) == 0;
     return false;
   }
+  // The LOAS/LATM stream of a running DAB+ audio service on the device (dabx_set_aac_stream_mode): false when the service does not run or
+  // the engine refuses (a slot that is not DAB+, or in packet mode).  The frames are read with dabx_read_aac_frames(engine(), 0, slot, ...)
+  bool set_aac_stream(int subChId, bool on)
+  {
+    const dabx_aac_stream_config cfg{sizeof(dabx_aac_stream_config), 0, {0}};
+    for (size_t j = 0; j < slots_.size(); j++)
+      if (slots_[j].kbps && slots_[j].subch_id == subChId) return dabx_set_aac_stream_mode(eng_, 0, (int)j, on ? &cfg : nullptr) == 0;
+    return false;
+  }
   // "decode everything the FIC announces" -- what EtiGenerator does on its own (eti_generator.cpp:132-134)
   int set_all_channels()
   {
