@@ -14,6 +14,7 @@
 #include "aac_core.h"
 #include "eti_core.h"
 #include "tii_core.h"
+#include "scope_core.h"
 #include "fig00.h"
 
 namespace dabx {
@@ -367,6 +368,41 @@ __global__ __launch_bounds__(128) void k_deliver_tii(EngineDev e, TiiDeliverDev 
 int launch_deliver_tii(const EngineDev &e, const TiiDeliverDev &td, hipStream_t st)
 {
   hipLaunchKernelGGL(k_deliver_tii, dim3(e.n_streams), dim3(128), 0, st, e, td);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+
+// The scope section (include/dabx.h, dabx_chunk_scope; pipeline.h, ScopeDeliverDev).  grid = n_streams, 256 threads, front-end stream, behind
+// k_deliver_front -- so behind the k_scope of the chunk's last frame, whichever HIP stream ran it (the frame's FIC decoder waits for the
+// demapper launch behind k_scope): the records the stream has written since the previous chunk, the newest DABX_CHUNK_FRAMES of them (a
+// chunk's frames cannot show more), out of the stage's ring.  A stream without room in the slab (rec_off 0) delivers none.
+__global__ __launch_bounds__(256) void k_deliver_scope(EngineDev e, ScopeDeliverDev sd)
+{
+  const int s = blockIdx.x, tid = threadIdx.x;
+  constexpr int CAP = DABX_CHUNK_FRAMES < SCOPE_RING ? DABX_CHUNK_FRAMES : SCOPE_RING, SLOT_Q = SCOPE_SLOT_BYTES / 16;
+  static_assert(SCOPE_SLOT_BYTES % 16 == 0, "a record slot is copied in 16-byte words");
+  const unsigned long long rec_off = sd.rec_off[s];
+  const long long total = sd.ring ? sd.shows[(size_t)s * sd.st_stride] : 0, have = rec_off ? total - sd.done[s] : 0;
+  int n = (int)(have < CAP ? have : CAP);
+  if (n < 0) n = 0;
+  const long long first = total - n;
+  if (tid == 0) {
+    dabx_chunk_scope r;
+    r.first_record = first; r.n_records = n; r.records_lost = (int)(have > n ? have - n : 0); r.rec_off = rec_off; r.records_total = total;
+    reinterpret_cast<dabx_chunk_scope *>(sd.slab + sd.off_scope)[s] = r;
+  }
+  uint4 *o = reinterpret_cast<uint4 *>(sd.slab + rec_off);
+  for (int i = tid; i < n * SLOT_Q; i += 256) {
+    const int k = i / SLOT_Q, wd = i - k * SLOT_Q;
+    o[i] = reinterpret_cast<const uint4 *>(sd.ring + ((size_t)s * SCOPE_RING + (size_t)((first + k) % SCOPE_RING)) * SCOPE_SLOT_BYTES)[wd];
+  }
+  __syncthreads();
+  if (tid == 0) sd.done[s] = total;
+}
+
+int launch_deliver_scope(const EngineDev &e, const ScopeDeliverDev &sd, hipStream_t st)
+{
+  hipLaunchKernelGGL(k_deliver_scope, dim3(e.n_streams), dim3(256), 0, st, e, sd);
   DABX_HIP(hipGetLastError());
   return 0;
 }

@@ -365,6 +365,7 @@ void dabx_destroy(dabx_engine *e)
   ingest_free(e);
   for (dabx_tii *t : e->tii) dabx_tii_destroy(t);
   tii_stage_free(e);
+  scope_stage_free(e);
   for (dabx_fibdec *f : e->fibdec) dabx_fibdec_destroy(f);
   if (e->ingest) { (void)hipStreamSynchronize(e->ingest); (void)hipStreamDestroy(e->ingest); }
   if (e->ingest2) { (void)hipStreamSynchronize(e->ingest2); (void)hipStreamDestroy(e->ingest2); }
@@ -812,8 +813,10 @@ int dabx_process(dabx_engine *e, int max_frames, int sync)
       e->ss.prep_pending = false;
     }
     const bool all_locked = e->locked_host && __atomic_load_n(e->locked_host, __ATOMIC_RELAXED) == e->dev.n_streams;
-    int rc = launch_front_step(e->dev, e->ss, e->mk, async_acquire, all_locked);
+    // (the scope stage's k_scope goes in front of the frame's first demapper launch, only while a stream has the mode on)
+    int rc = launch_front_step(e->dev, e->ss, e->mk, async_acquire, all_locked, e->scope.n_on > 0 ? &e->scope.dev : nullptr);
     if (rc) return rc;
+    if (e->scope.n_on > 0) e->scope.launches++;
     // the TII detectors of the streams that have the mode on (deliver.hip): behind the frame tail, in front of the next frame's accumulation
     if (e->tiis.n_on > 0) {
       if ((rc = launch_tii(e->dev, e->tiis.dev, e->stream))) return rc;

@@ -8,6 +8,7 @@
 #include "mp2_core.h"
 #include "aac_core.h"
 #include "tii_core.h"
+#include "scope_core.h"
 #include "sdma.h"
 #include "iqfile.h"
 #include <algorithm>
@@ -66,6 +67,12 @@ struct Delivery {
   // DABX_DELIVER_TII (deliver.hip, k_deliver_tii): the header's extension as it goes into a slab, the section's cursor per stream; zeros / null without the bit
   dabx_chunk_header_ext ext{};
   long long *tii_done = nullptr;
+  // DABX_DELIVER_SCOPE (deliver.hip, k_deliver_scope): the section's cursor per stream, where each stream's record slots lie in a slab (device
+  // and host; 0 = the stream's mode was off when the delivery was opened: no room); null / empty without the bit
+  long long *scope_done = nullptr;
+  unsigned long long *scope_off = nullptr;
+  std::vector<char> scope_room;                  // [S] the stream had the mode on when the delivery was opened
+  bool scope() const { return (what & DABX_DELIVER_SCOPE) != 0; }
   bool tii() const { return (what & DABX_DELIVER_TII) != 0; }
   bool mp2_audio() const { return (what & DABX_DELIVER_MP2_AUDIO) != 0; }      // the MP2 audio section (deliver.hip, k_deliver_mp2_audio), while a slot has the mode on
   bool aac() const { return (what & DABX_DELIVER_AAC) != 0; }      // the AAC section (deliver.hip, k_deliver_aac), while a slot has the mode on
@@ -168,7 +175,20 @@ struct TiiStage {
   bool exists() const { return dev.pairs != nullptr; }
 };
 
-struct dabx_engine : dabx::EngineHead {          // (iqfile.h: the ring format, where iqfile.cpp can read it)
+// The scope stage (include/dabx.h dabx_set_scope_mode, pipeline.hip k_scope).  Nothing of it exists until the mode is first switched on: dev
+// stays all null, n_on stays 0 and no step launches the kernel.
+struct ScopeStage {
+  ScopeDev dev{};
+  int32_t *list = nullptr;                     // [S] device: the first n_on entries are the streams with the mode on (ScopeDev::list)
+  ScopeCfgDev *cfg_dev = nullptr;              // [S] (ScopeDev::cfg)
+  int n_on = 0;
+  std::vector<ScopeCfgDev> cfg;                // [S] mirror of cfg_dev
+  std::vector<long long> seen, lost;           // [S] records dabx_read_scope has returned or passed / found gone
+  long long launches = 0;
+  bool exists() const { return dev.ring != nullptr; }
+};
+
+struct dabx_engine : dabx::EngineHead {         // (iqfile.h: the ring format, where iqfile.cpp can read it)
   dabx_config cfg{};
   EngineDev dev{};
   hipStream_t stream = nullptr;                // == ss.a (front end)
@@ -186,6 +206,7 @@ struct dabx_engine : dabx::EngineHead {          // (iqfile.h: the ring format, 
   std::vector<dabx_tii *> tii;                 // [S] detectors, created on first dabx_read_tii
   std::vector<int> tii_epoch;                  // [S] reset epoch seen by the detector
   TiiStage tiis;                               // the detectors on the device
+  ScopeStage scope;                            // the IQ scope and carrier plots on the device
   std::vector<void *> allocs;
   void *stage = nullptr;                       // host -> device staging of dabx_push_iq
   size_t stage_cap = 0;
@@ -266,6 +287,8 @@ void delivery_free(dabx_engine *e);
 void ingest_free(dabx_engine *e);
 // engine_tii.cpp
 void tii_stage_free(dabx_engine *e);
+// engine_scope.cpp
+void scope_stage_free(dabx_engine *e);
 // engine_slots.cpp
 void pad_count_sources(dabx_engine *e);
 int mot_follow_pad(dabx_engine *e);

@@ -97,6 +97,14 @@ int dabx_engine::delivery_layout()
   off = layout_section(mpa, D.mp2_audio() && !d.fic_only, off, S * M * sizeof(dabx_chunk_mp2_audio), &x.off_mp2_audio);
   // ... and the AAC section (dabx_chunk_aac), in the same way
   off = layout_section(aac, D.aac() && !d.fic_only, off, S * M * sizeof(dabx_chunk_aac), &x.off_aac);
+  // the scope section: its table, then DL_FRAMES record slots for every stream that had the mode on when the delivery was opened
+  if (D.scope()) {
+    off = align_up(off, 16); x.off_scope = off; off += S * sizeof(dabx_chunk_scope);
+    std::vector<unsigned long long> so(S, 0);
+    for (size_t s_ = 0; s_ < S; s_++)
+      if (D.scope_room[s_]) { so[s_] = off; off += (size_t)DL_FRAMES * SCOPE_SLOT_BYTES; }
+    DABX_HIP(hipMemcpy(D.scope_off, so.data(), sizeof(unsigned long long) * S, hipMemcpyHostToDevice));
+  }
   off = align_up(off, 256);
   h.off_msc = off;
   if ((D.what & (DABX_DELIVER_MSC | DABX_DELIVER_MSC_NOT_DABPLUS)) && !d.fic_only)
@@ -181,6 +189,10 @@ int dabx_engine::delivery_begin(DeliverDev *dv, int *slot, int *devslab)
     rc = launch_deliver_tii(dev, TiiDeliverDev{D.dev[*devslab], D.ext, D.tii_done, tiis.dev.ring, tiis.exists() ? &tiis.dev.cnt->events : nullptr,
                                                (int32_t)(sizeof(TiiCounters) / sizeof(long long)), 0}, stream);
   else if (!rc && D.ext.magic) rc = launch_deliver_ext(D.ext, D.dev[*devslab], stream);      // (k_deliver_tii writes the header's extension otherwise)
+  // the scope section: behind the k_scope of the chunk's last frame (deliver.hip, k_deliver_scope)
+  if (!rc && D.scope())
+    rc = launch_deliver_scope(dev, ScopeDeliverDev{D.dev[*devslab], D.ext.off_scope, D.scope_off, D.scope_done, scope.dev.ring,
+                                                   scope.exists() ? &scope.dev.st->shows : nullptr, (int32_t)(sizeof(ScopeState) / sizeof(long long)), 0}, stream);
   if (rc) {                                                        // nothing was queued: give the slabs back
     std::lock_guard<std::mutex> lk(D.mu);
     D.dev_busy[*devslab] = false;
@@ -319,8 +331,10 @@ void delivery_free(dabx_engine *e)
     D.dev[k] = nullptr; D.packed[k] = nullptr; D.packed_lf[k] = nullptr; D.dev_busy[k] = false;
   }
   for (void *q : {(void *)D.layout_off, (void *)D.subch_id, (void *)D.frames_done, (void *)D.cif_done, (void *)D.sf_done, (void *)D.eti_front,
-                  (void *)D.eti_next, (void *)D.eti_stage[0], (void *)D.eti_stage[1], (void *)D.eti_stage[2], (void *)D.tii_done}) if (q) (void)hipFree(q);
+                  (void *)D.eti_next, (void *)D.eti_stage[0], (void *)D.eti_stage[1], (void *)D.eti_stage[2], (void *)D.tii_done, (void *)D.scope_done,
+                  (void *)D.scope_off}) if (q) (void)hipFree(q);
   D.tii_done = nullptr; D.ext = dabx_chunk_header_ext{};
+  D.scope_done = nullptr; D.scope_off = nullptr; D.scope_room.clear();
   D.layout_off = nullptr; D.subch_id = nullptr; D.frames_done = D.cif_done = D.sf_done = nullptr;
   D.eti_front = nullptr; D.eti_next = nullptr; D.eti_rows_off = 0;
   for (int k = 0; k < Delivery::NDEV; k++) D.eti_stage[k] = nullptr;
@@ -337,7 +351,7 @@ extern "C" {
 
 int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
 {
-  if (!e || (cfg && (cfg->host_slabs < 0 || cfg->host_slabs == 1 || cfg->host_slabs > 64 || (cfg->what & ~(1023 | DABX_DELIVER_AAC)) || cfg->copy_engine < 0 || cfg->copy_engine > 1))) {
+  if (!e || (cfg && (cfg->host_slabs < 0 || cfg->host_slabs == 1 || cfg->host_slabs > 64 || (cfg->what & ~(1023 | DABX_DELIVER_AAC | DABX_DELIVER_SCOPE)) || cfg->copy_engine < 0 || cfg->copy_engine > 1))) {
     set_error("dabx_delivery_open: bad argument");
     return DABX_E_ARG;
   }
@@ -355,6 +369,12 @@ int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
   // ... and DABX_DELIVER_AAC, alone or with only those two
   if (cfg && (cfg->what & DABX_DELIVER_AAC) && !(cfg->what & ~(DABX_DELIVER_AAC | DABX_DELIVER_MP2_AUDIO | DABX_DELIVER_TII))) {
     set_error("dabx_delivery_open: DABX_DELIVER_AAC needs at least one DABX_DELIVER_* bit below 256 beside it");
+    return DABX_E_ARG;
+  }
+  // ... and DABX_DELIVER_SCOPE, alone or with only the other opt-in bits
+  if (cfg && (cfg->what & DABX_DELIVER_SCOPE) &&
+      !(cfg->what & ~(DABX_DELIVER_SCOPE | DABX_DELIVER_AAC | DABX_DELIVER_MP2_AUDIO | DABX_DELIVER_TII | DABX_DELIVER_ETI))) {
+    set_error("dabx_delivery_open: DABX_DELIVER_SCOPE needs at least one DABX_DELIVER_* bit below 128 beside it");
     return DABX_E_ARG;
   }
   if (e->dl.open) { set_error("dabx_delivery_open: already open"); return DABX_E_STATE; }
@@ -395,6 +415,13 @@ int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
   if (D.tii()) cap += sizeof(dabx_chunk_header_ext) + 16 + S * (sizeof(dabx_chunk_tii) + 4 * (size_t)DABX_TII_EVENT_SLOT_BYTES);   // ... and the TII section
   if (D.mp2_audio()) cap += (D.tii() ? 0 : sizeof(dabx_chunk_header_ext)) + section_capacity(e->mpa, S * M * sizeof(dabx_chunk_mp2_audio));   // ... and the MP2 audio section
   if (D.aac()) cap += (D.tii() || D.mp2_audio() ? 0 : sizeof(dabx_chunk_header_ext)) + section_capacity(e->aac, S * M * sizeof(dabx_chunk_aac));   // ... and the AAC section
+  D.scope_room.assign(D.scope() ? S : 0, 0);
+  if (D.scope()) {                                                  // ... and the scope section: its table and DL_FRAMES record slots per stream with the mode on
+    size_t n_on = 0;
+    if (e->scope.exists())
+      for (size_t s_ = 0; s_ < S; s_++) { D.scope_room[s_] = (char)(e->scope.cfg[s_].enable != 0); n_on += D.scope_room[s_] ? 1 : 0; }
+    cap += (D.tii() || D.mp2_audio() || D.aac() ? 0 : sizeof(dabx_chunk_header_ext)) + 16 + S * sizeof(dabx_chunk_scope) + n_on * (size_t)DL_FRAMES * SCOPE_SLOT_BYTES;
+  }
   D.capacity = align_up(cap, 4096);
 #define H(x) do { hipError_t err__ = (x); if (err__ != hipSuccess) { set_error("HIP error %d (%s) at %s:%d", (int)err__, hipGetErrorString(err__), __FILE__, __LINE__); delivery_free(e); return DABX_E_HIP; } } while (0)
   if (D.copy_engine == 1) H(hipStreamCreateWithFlags(&D.cs, hipStreamNonBlocking));
@@ -452,6 +479,18 @@ int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
       }
       H(hipMalloc((void **)&D.tii_done, sizeof(long long) * S));
       H(hipMemcpy(D.tii_done, td.data(), sizeof(long long) * S, hipMemcpyHostToDevice));
+    }
+    if (D.scope()) {
+      // the scope section's cursor: the records written from now on
+      std::vector<long long> sd(S, 0);
+      if (e->scope.exists()) {
+        std::vector<ScopeState> st(S);
+        H(hipMemcpy(st.data(), e->scope.dev.st, sizeof(ScopeState) * S, hipMemcpyDeviceToHost));
+        for (size_t s_ = 0; s_ < S; s_++) sd[s_] = st[s_].shows;
+      }
+      H(hipMalloc((void **)&D.scope_done, sizeof(long long) * S));
+      H(hipMemcpy(D.scope_done, sd.data(), sizeof(long long) * S, hipMemcpyHostToDevice));
+      H(hipMalloc((void **)&D.scope_off, sizeof(unsigned long long) * S));
     }
   }
 #undef H

@@ -354,7 +354,9 @@ int dabx_internal_demap_frame(dabx_engine *e, const int32_t *present, int schedu
   DABX_HIP(hipMalloc(&present_dev, bytes));
   int rc = 0;
   if (hipMemcpy(present_dev, present, bytes, hipMemcpyHostToDevice) != hipSuccess) { set_error("dabx_internal_demap_frame: copy failed"); rc = DABX_E_HIP; }
-  if (!rc) rc = launch_demap_frame(e->dev, e->ss.step_count, present_dev, schedule, e->stream);
+  const bool scope_on = e->scope.n_on > 0;
+  if (!rc) rc = launch_demap_frame(e->dev, e->ss.step_count, present_dev, schedule, e->stream, scope_on ? &e->scope.dev : nullptr);
+  if (!rc && scope_on) e->scope.launches++;
   const int rc2 = sync_all(e);
   (void)hipFree(present_dev);
   return rc ? rc : rc2;

@@ -217,6 +217,18 @@ struct TiiDeliverDev {
   int32_t cnt_stride, pad_;               // ... in long longs
 };
 
+// ---- the scope section of the delivery (deliver.hip k_deliver_scope, include/dabx.h dabx_chunk_scope): the records k_scope (pipeline.hip) has
+// written since the previous chunk, out of their rings into the slab's head part; gathered at chunk close on the front-end stream
+struct ScopeDeliverDev {
+  uint8_t *slab;
+  unsigned long long off_scope;           // dabx_chunk_header_ext.off_scope of the slab
+  const unsigned long long *rec_off;      // [S] where the stream's record slots lie in a slab, 0 = it has no room (mode off when the delivery was opened)
+  long long *done;                        // [S] records of the stream delivered or passed so far
+  const uint8_t *ring;                    // ScopeDev::ring (scope_core.h), null while the engine has no scope stage: every stream delivers no record
+  const long long *shows;                 // &st[0].shows, a ScopeState apart
+  int32_t st_stride, pad_;                // ... in long longs
+};
+
 // ---- lane-per-trellis path of the MSC decoder (vit_t.hip) ------------------------------------------------------
 // The sub-channels of ALL streams are grouped into classes of equal protection profile (same depuncture map and
 // trellis length): the 64 lanes of a decoder wave then share the map and step count whatever ensemble they come from.
@@ -387,9 +399,10 @@ struct MotDev;                    // mot_core.h
 struct CarouselDev;               // carousel_core.h
 struct Mp2AudioDev;               // mp2_core.h
 struct AacStreamDev;              // aac_core.h
+struct ScopeDev;                  // scope_core.h
 // pipeline.hip
 extern const char *const kStepKernelNames[N_STEP_KERNELS];
-int launch_front_step(const EngineDev &e, EngineStreams &ss, Marker &mk, bool async_acquire, bool all_locked);
+int launch_front_step(const EngineDev &e, EngineStreams &ss, Marker &mk, bool async_acquire, bool all_locked, const ScopeDev *scope = nullptr);
 int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineStreams &ss, Marker &mk, const DeliverDev *dv = nullptr,
                      hipStream_t *tail = nullptr, const PacketDev *pk = nullptr, const PadDev *pad = nullptr, const MotDev *mot = nullptr,
                      const CarouselDev *car = nullptr, const EtiDev *eti = nullptr, const Mp2AudioDev *mp2a = nullptr, long long *mp2a_launches = nullptr,
@@ -405,7 +418,7 @@ int launch_msc_advance(const EngineDev &e, const int32_t *counts_dev, hipStream_
 int launch_fic_inject(const EngineDev &e, int stream, const int16_t *soft_dev, hipStream_t st);
 int launch_fic_decode(const EngineDev &e, const int32_t *present_dev, hipStream_t st);
 int launch_demap_inject(const EngineDev &e, int parity, int stream, const float2 *spec_dev, const float2 *null_dev, float clock_err, int np_sel, hipStream_t st);
-int launch_demap_frame(const EngineDev &e, unsigned step_count, const int32_t *present_dev, int schedule, hipStream_t st);
+int launch_demap_frame(const EngineDev &e, unsigned step_count, const int32_t *present_dev, int schedule, hipStream_t st, const ScopeDev *scope = nullptr);
 // vit_t.hip
 int launch_msc_prep(const EngineDev &e, int cifs, const MscLaunch &L, hipStream_t st, Marker &mk);
 int launch_msc_vitT(const EngineDev &e, int cifs, const MscLaunch &L, hipStream_t st, Marker &mk);
@@ -421,6 +434,7 @@ int launch_deliver_mp2_audio(const EngineDev &e, const DeliverDev &dv, const Mp2
 int launch_deliver_aac(const EngineDev &e, const DeliverDev &dv, const AacStreamDev &ad, unsigned long long off_aac, hipStream_t st);
 int launch_deliver_ext(const dabx_chunk_header_ext &ext, uint8_t *slab, hipStream_t st);           // at chunk close, front-end stream: the header's extension of a slab without a TII section
 int launch_deliver_tii(const EngineDev &e, const TiiDeliverDev &td, hipStream_t st);                // at chunk close, front-end stream, behind launch_deliver_front
+int launch_deliver_scope(const EngineDev &e, const ScopeDeliverDev &sd, hipStream_t st);            // at chunk close, front-end stream, behind the header's extension
 int launch_eti_front(const EngineDev &e, const EtiDev &t, hipStream_t st, Marker &mk);              // at chunk close, front-end stream
 int launch_eti_back(const EngineDev &e, const EtiDev &t, hipStream_t st, Marker &mk, bool pre);     // behind the batch's decode; pre: in front of its DAB+ stage
 // msc_stages.hip

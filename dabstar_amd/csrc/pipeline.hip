@@ -25,6 +25,7 @@
 #include "aac_core.h"
 #include <algorithm>
 #include "ofdm_core.h"
+#include "scope_core.h"
 #include "viterbi_core.h"
 #include "fec_core.h"
 #include "acq_walk.h"
@@ -1290,8 +1291,186 @@ __global__ __launch_bounds__(DEMAP_THREADS) void k_demap_fic(EngineDev e, DevTab
 template <int SOFT_TYPE, bool SAT, bool MER>
 __global__ __launch_bounds__(DEMAP_THREADS) void k_demap_whole(EngineDev e, DevTables t) { demap_frame_body<SOFT_TYPE, SAT, true, MER>(e, t, 0, 75); }
 
+// -------------------------------------------------------------------------------------------------- scope
+// The IQ scope and the carrier plot of OfdmDecoder (ofdm_decoder.cpp:258-291, 303-324; scope_core.h; docs/history/scope.md).  One block per
+// stream with the mode on (sc.list), launched directly in front of the frame's first demapper launch on the same HIP stream: it reads what
+// that launch is about to read -- the stream's scalars, the per-carrier state as the previous frame left it, the phase reference, the
+// frame's spectra -- and writes none of it.  A frame that shows symbol l replays the demapper's recurrences over symbols 1 .. l - 1 with
+// demap_pair itself (soft bits dropped), then evaluates symbol l with scope_pair.  Same carrier <-> thread mapping as demap_frame_body.
+template <int SOFT_TYPE>
+__global__ __launch_bounds__(DEMAP_THREADS) void k_scope(EngineDev e, DevTables t, ScopeDev sc)
+{
+  static_assert(DEMAP_Q == 2 && DEMAP_THREADS / 64 == 12, "one DemapPair per thread: carriers tid and tid + 768; twelve wave partials");
+  __shared__ __attribute__((aligned(16))) float red[32];
+  __shared__ float ph[K];                                  // PRS_PHASE_UNWRAP: the wrapped phases in realCarrRelIdx order
+  const int s = sc.list[blockIdx.x], tid = threadIdx.x;
+  const StreamCtl &c = e.ctl[s];
+  if (e.flag_sync) seq_wait(e.sym_seq + s, e.step_seq, e.seq_timeouts);   // as the demapper's first launch: k_symbols of this step is through
+  if (!c.frame_ok) return;                                 // no decode_symbol call: neither counter moves
+  const ScopeCfgDev cfg = sc.cfg[s];
+  ScopeState q = sc.st[s];
+  const int cadence = scope_counters_frame(q);
+  const int shown = cfg.symbol ? cfg.symbol : cadence;     // 1-based OFDM symbol, 0 = this frame shows nothing
+  __syncthreads();                                         // every thread has read the counters
+  if (tid == 0) {
+    ScopeState n = q;
+    n.shows += shown ? 1 : 0;
+    sc.st[s] = n;
+  }
+  if (!shown) return;
+  const int L = shown - 1;                                 // 0-based, as demap_frame_body counts
+  const DemapDev &d = e.demap;
+  const float *null_power = c.np_sel ? d.null_power2 : d.null_power;
+  const float2 *spectra = e.spectra + ((size_t)e.parity * e.n_streams + s) * 75 * K;
+  const bool mer = d.track_mer != 0;
+  int kk[2], bin[2], rel[2];
+  DemapPair cr;
+  v2f rel_f, wk, pacc = (v2f)(0.0f), sd;
+#pragma unroll
+  for (int h = 0; h < 2; h++) {
+    const int k = tid + DEMAP_THREADS * h;
+    kk[h] = k; bin[h] = t.perm_bin[k]; rel[h] = t.perm_rel[k];
+    rel_f[h] = (float)(K / 2 - rel[h]);
+    const float2 pr = d.phase_ref[(size_t)s * TU + bin[h]];
+    cr.prev_re[h] = pr.x; cr.prev_im[h] = pr.y;
+    cr.integ[h] = d.integ[(size_t)s * K + k];
+    cr.mean_power[h] = d.mean_power[(size_t)s * K + k];
+    cr.mean_sigma_sq[h] = d.mean_sigma[(size_t)s * K + k];
+    cr.null_power[h] = null_power[(size_t)s * TU + bin[h]];
+    wk[h] = mpa_weight(k);
+    sd[h] = d.std_dev[(size_t)s * K + k];
+  }
+  const float2 prs0[2] = {make_float2(cr.prev_re[0], cr.prev_im[0]), make_float2(cr.prev_re[1], cr.prev_im[1])};   // symbol 0 of this frame (:137-144)
+  const float ce = c.clock_err;
+  float part = 0.f;
+  for (int l = 0; l < L; l++) {
+    const float2 x0 = demap_ld_spec(spectra + (size_t)l * K + kk[0]), x1 = demap_ld_spec(spectra + (size_t)l * K + kk[1]);
+    int16_t sr[2], si[2];
+    v2f pw;
+    const v2f mag = demap_pair<SOFT_TYPE>(cr, (v2f){x0.x, x1.x}, (v2f){x0.y, x1.y}, rel_f, ce, 0.0f, sr, si, pw, mer ? &sd : nullptr);
+    part = mag.x + mag.y;
+    pacc = pacc * mpa_decay() + pw;
+  }
+  // mMeanValue and mMeanPowerOvrAll in front of the shown symbol: the block sum of |r1| of the symbol before it, in the demapper's own order
+  // of additions, and the demapper's closed form over the replayed symbols
+  float mean_value = d.mean_value[s], mpa = d.mean_power_all[s];
+  if (L > 0) {
+    const float pw_sum = wave_sum(part);
+    float wsum = wave_sum(wk.x * pacc.x + wk.y * pacc.y);
+    if ((tid & 63) == 0) { red[tid >> 6] = pw_sum; red[16 + (tid >> 6)] = wsum; }
+    __syncthreads();
+    const v2f *rp2 = reinterpret_cast<const v2f *>(red);
+    const v2f a = ((rp2[0] + rp2[1]) + (rp2[2] + rp2[3])) + (rp2[4] + rp2[5]);
+    mean_value = (a.x + a.y) * (1.0f / (float)K);
+    wsum = 0.f;
+    for (int w = 0; w < DEMAP_THREADS / 64; w++) wsum += red[16 + w];
+    mpa = mpa * mpa_decay_n(L) + wsum;
+    __syncthreads();
+  }
+  const float w2 = demap_w2(mean_value, SOFT_TYPE);
+  const float inv_sqrt_mp = mpa > 0.0f ? 1.0f / sqrtf(mpa) : 1.0f;      // :162
+  ScopePairOut o;
+  {
+    const float2 x0 = demap_ld_spec(spectra + (size_t)L * K + kk[0]), x1 = demap_ld_spec(spectra + (size_t)L * K + kk[1]);
+    scope_pair<SOFT_TYPE>(cr, (v2f){x0.x, x1.x}, (v2f){x0.y, x1.y}, rel_f, ce, sd, mer, o);
+  }
+  uint8_t *slot = sc.ring + ((size_t)s * SCOPE_RING + (size_t)(q.shows % SCOPE_RING)) * SCOPE_SLOT_BYTES;
+  float2 *iq_out = reinterpret_cast<float2 *>(slot + 32);
+  float *carr_out = reinterpret_cast<float *>(slot + 32 + K * 8);
+  if (tid == 0) {
+    dabx_scope_record r;
+    r.frame = c.frames; r.symbol = shown; r.iq_type = (uint8_t)cfg.iq_type; r.carrier_type = (uint8_t)cfg.carrier_type;
+    r.soft_bit_type = (uint8_t)SOFT_TYPE; r.reserved0 = 0; r.mean_value = mean_value; r.mean_power_all = mpa; r.reserved[0] = r.reserved[1] = 0;
+    *reinterpret_cast<dabx_scope_record *>(slot) = r;
+  }
+  // mIqVector, by nomCarrIdx (:260-267)
+#pragma unroll
+  for (int h = 0; h < 2; h++) {
+    float2 v;
+    if (cfg.iq_type == 0) v = make_float2(o.b_re[h] / o.mean_level[h], o.b_im[h] / o.mean_level[h]);
+    else if (cfg.iq_type == 1) v = make_float2(o.b_re[h] * inv_sqrt_mp, o.b_im[h] * inv_sqrt_mp);
+    else v = make_float2(o.raw_re[h] * inv_sqrt_mp, o.raw_im[h] * inv_sqrt_mp);
+    iq_out[kk[h]] = v;
+  }
+  // mCarrVector, by realCarrRelIdx (:269-290)
+  const int ct = cfg.carrier_type;
+  v2f cv = (v2f)(0.0f);
+  if (ct == SC_REL_POWER || ct == SC_NULL_OVR_POW) {
+    // mMeanPowerOvrAll moves inside the carrier loop (:214): carrier k sees x_k = (1-a)^(k+1) x_0 + a (1-a)^k sum_{j<=k} (1-a)^(-j) p_j -- an
+    // inclusive prefix sum over the carriers in nominal order, the first 768 of them in thread order and then the second 768
+    const float LN1A = -3.2552135e-6f, A = 0.005f / (float)K;
+    const float y0 = o.power[0] * __expf(-(float)kk[0] * LN1A), y1 = o.power[1] * __expf(-(float)kk[1] * LN1A);
+    const float p0 = block_scan_incl(y0, red, tid);
+    const float half = block_last(p0, red, tid);
+    const float p1 = half + block_scan_incl(y1, red, tid);
+    const float pp[2] = {p0, p1};
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+      const float xk = __expf((float)(kk[h] + 1) * LN1A) * mpa + A * __expf((float)kk[h] * LN1A) * pp[h];
+      cv[h] = scope_log10_times_10((ct == SC_REL_POWER ? cr.mean_power[h] : cr.null_power[h]) / xk);
+    }
+  } else {
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+      float v;
+      switch (ct) {
+      case SC_SB_WEIGHT: {
+        float w = (fabsf(o.r1_re[h]) + fabsf(o.r1_im[h])) / 2.0f * (-w2);
+        if (w < 0.0f) w = 0.0f; else if (w > 127.0f) w = 127.0f;            // limit_min_max (glob_defs.h:75-85): a NaN stays
+        v = 100.0f / 127.0f * w;
+      } break;
+      case SC_EVM_PER: v = 100.0f * sqrtf(cr.mean_sigma_sq[h]) / o.mean_level[h]; break;
+      case SC_EVM_DB: v = scope_log10_times_10(cr.mean_sigma_sq[h] / cr.mean_power[h]); break;
+      case SC_STD_DEV: v = scope_deg(sqrtf(o.std_dev_sq[h])); break;
+      case SC_PHASE_ERROR: v = scope_deg(o.phase_err[h]); break;
+      case SC_PRS_PHASE:
+      case SC_PRS_PHASE_UNWRAP: {
+        const float2 r = t.prs_ref[bin[h]], z = prs0[h];                    // z * conj(r), :142
+        v = scope_deg(atan2f(z.y * r.x - z.x * r.y, z.x * r.x + z.y * r.y));
+      } break;
+      case SC_FOUR_QUAD_PHASE: v = scope_deg(atan2f(o.b_im[h], o.b_re[h])); break;
+      default: v = scope_log10_times_10(cr.mean_power[h] / cr.null_power[h]); break;   // SC_SNR
+      }
+      cv[h] = v;
+    }
+  }
+  if (ct != SC_PRS_PHASE_UNWRAP) {
+    carr_out[rel[0]] = cv.x; carr_out[rel[1]] = cv.y;
+    return;
+  }
+  // :305-318, serial in the reference: the prefix sum of the wrapped first differences over realCarrRelIdx, element 0 the phase itself
+  ph[rel[0]] = cv.x; ph[rel[1]] = cv.y;
+  __syncthreads();
+  float df[2];
+#pragma unroll
+  for (int h = 0; h < 2; h++) {
+    const int i = tid + DEMAP_THREADS * h;
+    float v = ph[i];
+    if (i > 0) {
+      v -= ph[i - 1];
+      if (v > 180.0f) v -= 360.0f; else if (v < -180.0f) v += 360.0f;
+    }
+    df[h] = v;
+  }
+  const float u0 = block_scan_incl(df[0], red, tid);
+  const float half = block_last(u0, red, tid);
+  const float u1 = half + block_scan_incl(df[1], red, tid);
+  carr_out[tid] = u0; carr_out[tid + DEMAP_THREADS] = u1;
+}
+
+// in front of the frame's first demapper launch, on its HIP stream; sc null or empty: nothing is launched
+static int launch_scope(const EngineDev &e, const DevTables &t, const ScopeDev *sc, hipStream_t st)
+{
+  if (!sc || sc->n <= 0) return 0;
+  const int g = e.demap.soft_type == 3 ? 3 : e.demap.soft_type == 2 ? 2 : 1;
+  if (g == 3) hipLaunchKernelGGL((k_scope<3>), dim3(sc->n), dim3(DEMAP_THREADS), 0, st, e, t, *sc);
+  else if (g == 2) hipLaunchKernelGGL((k_scope<2>), dim3(sc->n), dim3(DEMAP_THREADS), 0, st, e, t, *sc);
+  else hipLaunchKernelGGL((k_scope<1>), dim3(sc->n), dim3(DEMAP_THREADS), 0, st, e, t, *sc);
+  return 0;
+}
+
 // ---------------------------------------------------------------------------------------------------- FIC
-struct SrcFic {                       // 2304 Viterbi symbols of one FIC + depuncture map (viterbi_core.h: key / raw / syms)
+struct SrcFic {                     // 2304 Viterbi symbols of one FIC + depuncture map (viterbi_core.h: key / raw / syms)
   const uint8_t *sym;
   const uint16_t *map;
   typedef ushort4 Key;
@@ -1718,7 +1897,7 @@ const char *const kStepKernelNames[N_STEP_KERNELS] = {"k_acquire", "k_frame_head
 // chain) and the frame tail follow on a, while the 72 MSC symbols are demapped on stream d: nothing on the chain of the NEXT
 // frame needs them, so a goes on to frame n + 1 while d is busy; the next frame's first demapper launch (and the MSC batch)
 // wait for d.  Serial schedule (cfg.schedule = 1, ss.d null): every kernel on a in program order.
-int launch_front_step(const EngineDev &e_in, EngineStreams &ss, Marker &mk, bool async_acquire, bool all_locked)
+int launch_front_step(const EngineDev &e_in, EngineStreams &ss, Marker &mk, bool async_acquire, bool all_locked, const ScopeDev *scope)
 {
   const DevTables *t;
   int rc = get_tables(&t);
@@ -1797,6 +1976,7 @@ int launch_front_step(const EngineDev &e_in, EngineStreams &ss, Marker &mk, bool
     // the two hand-overs (k_symbols -> k_demap_fic, k_demap_fic -> k_fic_frame) are device-side sequence numbers: no packet between the two
     // demapper launches on d, none in front of them (EngineDev::flag_sync)
     hipLaunchKernelGGL(k_sym_publish, dim3((e.n_streams + 63) / 64), dim3(64), 0, st, e);
+    if ((rc = launch_scope(e, *t, scope, ss.d))) return rc;     // (takes k_demap_whole's own wait for k_symbols)
     mk.begin(3, ss.d);
     DABX_DEMAP_DISPATCH(k_demap_whole, dim3(e.n_streams), dim3(DEMAP_THREADS), 0, ss.d, e, *t);
     mk.end(3, ss.d);
@@ -1805,6 +1985,7 @@ int launch_front_step(const EngineDev &e_in, EngineStreams &ss, Marker &mk, bool
     ss.demap_in_flight = true; ss.demap_unrecorded = true;
   } else if (ss.d) {
     if (ss.demap_in_flight) { DABX_HIP(hipStreamWaitEvent(st, ss.demap_done, 0)); ss.demap_in_flight = false; }
+    if ((rc = launch_scope(e, *t, scope, st))) return rc;
     mk.begin(10, st);
     DABX_DEMAP_DISPATCH(k_demap_fic, dim3(e.n_streams), dim3(DEMAP_THREADS), 0, st, e, *t);
     mk.end(10, st);
@@ -1814,6 +1995,7 @@ int launch_front_step(const EngineDev &e_in, EngineStreams &ss, Marker &mk, bool
     DABX_HIP(hipEventRecord(ss.demap_done, ss.d));
     ss.demap_in_flight = true;
   } else {
+    if ((rc = launch_scope(e, *t, scope, st))) return rc;
     mk.begin(3, st); demap(st, 0, 75); mk.end(3, st);
   }
   mk.begin(4, st); hipLaunchKernelGGL(k_fic_frame, dim3(e.n_streams), dim3(256), 0, st, e, *t, 0, 4); mk.end(4, st);
@@ -2097,7 +2279,7 @@ int launch_demap_inject(const EngineDev &e_in, int parity, int stream, const flo
 // 2: k_demap_whole (few streams).  All on `st`, flag_sync = 0: no launch waits for a sequence number nobody publishes.  k_demap_whole
 // itself still publishes behind the FIC symbols, whatever flag_sync says: step_seq is therefore set to step_count, the number of the last
 // real step -- what fic_seq holds already; the next real step waits for step_count + 1, which this store does not satisfy.
-int launch_demap_frame(const EngineDev &e_in, unsigned step_count, const int32_t *present_dev, int schedule, hipStream_t st)
+int launch_demap_frame(const EngineDev &e_in, unsigned step_count, const int32_t *present_dev, int schedule, hipStream_t st, const ScopeDev *scope)
 {
   const DevTables *t;
   int rc = get_tables(&t);
@@ -2107,6 +2289,7 @@ int launch_demap_frame(const EngineDev &e_in, unsigned step_count, const int32_t
   e.step_seq = step_count;
   e.flag_sync = 0;
   hipLaunchKernelGGL(k_fic_present, dim3((e.n_streams + 255) / 256), dim3(256), 0, st, e, present_dev);
+  if ((rc = launch_scope(e, *t, scope, st))) return rc;     // in front of the first demapper launch of each of the three schedules
   if (schedule == 0) {
     DABX_DEMAP_DISPATCH(k_demap_frame6, dim3(e.n_streams), dim3(DEMAP_THREADS), 0, st, e, *t, 0, 75);
   } else if (schedule == 1) {

@@ -491,7 +491,8 @@ assert CHUNK_ETI.itemsize == 64
 DELIVER_TII = 256
 TII_MAX_RESULTS = 32
 CHUNK_EXT_MAGIC = 0x45584244                     # "DBXE"
-CHUNK_HEADER_EXT = np.dtype([("magic", "<u4"), ("bytes", "<u4"), ("off_tii", "<u8"), ("off_mp2_audio", "<u8"), ("off_aac", "<u8"), ("reserved", "<u8", 4)])
+CHUNK_HEADER_EXT = np.dtype([("magic", "<u4"), ("bytes", "<u4"), ("off_tii", "<u8"), ("off_mp2_audio", "<u8"), ("off_aac", "<u8"), ("off_scope", "<u8"),
+                             ("reserved", "<u8", 3)])
 CHUNK_TII = np.dtype([("first_event", "<i8"), ("n_events", "<i4"), ("events_lost", "<i4"), ("ev_off", "<u8"), ("events_total", "<i8")])
 TII_EVENT = np.dtype([("frame", "<i8"), ("n_results", "<i4"), ("n_found", "<i4"), ("frames_in_sum", "<i4"), ("epoch", "<i4"),
                       ("threshold_db", "<i4"), ("reserved", "<i4")])
@@ -584,6 +585,30 @@ AAC_STREAM_STATS = np.dtype([(k, "<i8") for k in ("superframes", "records", "fra
 CHUNK_AAC = np.dtype([("first_frame", "<i8"), ("n_frames", "<i4"), ("frames_lost", "<i4"), ("rec_off", "<u8"), ("bytes_off", "<u8"), ("n_bytes", "<i8")] +
                      [(k, "<i8") for k in ("superframes", "records", "frames", "frame_bytes", "lost_len", "lost_crc")] + [("reserved", "<i8", 5)])
 assert AAC_FRAME.itemsize == 32 and AAC_STREAM_STATS.itemsize == 64 and CHUNK_AAC.itemsize == 128
+
+
+# IQ scope and carrier plots (include/dabx.h "IQ scope and carrier plots"): dabx_scope_record, one per shown symbol, with the IQ vector
+# [1536] complex64 by nomCarrIdx and the carrier vector [1536] float32 by realCarrRelIdx behind it; dabx_scope_stats
+SCOPE_CARRIERS = 1536
+SCOPE_RECORD = np.dtype([("frame", "<i8"), ("symbol", "<i4"), ("iq_type", "u1"), ("carrier_type", "u1"), ("soft_bit_type", "u1"), ("reserved0", "u1"),
+                         ("mean_value", "<f4"), ("mean_power_all", "<f4"), ("reserved", "<i4", 2)])
+SCOPE_STATS = np.dtype([("shows", "<i8"), ("lost", "<i8"), ("launches", "<i8"), ("reserved", "<i8", 5)])
+SCOPE_SLOT_BYTES = 32 + SCOPE_CARRIERS * 8 + SCOPE_CARRIERS * 4
+# the slab's scope section (DELIVER_SCOPE = 8192, opt-in like DELIVER_ETI; 1024 and 4096 stay refused; announced by the header's extension):
+# one CHUNK_SCOPE per stream, then CHUNK_FRAMES record slots for every stream that had the mode on when the delivery was opened
+DELIVER_SCOPE = 8192
+CHUNK_SCOPE = np.dtype([("first_record", "<i8"), ("n_records", "<i4"), ("records_lost", "<i4"), ("rec_off", "<u8"), ("records_total", "<i8")])
+assert CHUNK_SCOPE.itemsize == 32
+# EIqPlotType / ECarrierPlotType (glob_enums.h); the types the library refuses are left out
+SCOPE_IQ_TYPES = {"PHASE_CORR_CARR_NORMED": 0, "PHASE_CORR_MEAN_NORMED": 1, "RAW_MEAN_NORMED": 2}
+SCOPE_CARRIER_TYPES = {"SB_WEIGHT": 0, "EVM_PER": 1, "EVM_DB": 2, "STD_DEV": 3, "PHASE_ERROR": 4, "PRS_PHASE": 5, "PRS_PHASE_UNWRAP": 6,
+                       "FOUR_QUAD_PHASE": 7, "REL_POWER": 8, "SNR": 9, "NULL_OVR_POW": 13}
+assert SCOPE_RECORD.itemsize == 32 and SCOPE_STATS.itemsize == 64
+
+
+class ScopeConfig(C.Structure):
+    """dabx_scope_config."""
+    _fields_ = [("enable", C.c_int32), ("iq_type", C.c_int32), ("carrier_type", C.c_int32), ("symbol", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
 class AacStreamConfig(C.Structure):
@@ -708,6 +733,7 @@ class Chunk:
         self.tii_table = None                   # the TII section: [S] CHUNK_TII, or None when the slab has none
         self.mp2_audio_table = None             # the MP2 audio section: [S, M] CHUNK_MP2_AUDIO, or None when the slab has none
         self.aac_table = None                   # the AAC section: [S, M] CHUNK_AAC, or None when the slab has none
+        self.scope_table = None                 # the scope section: [S] CHUNK_SCOPE, or None when the slab has none
         if int(h["what"]) & ~255:
             self.header_ext = self.raw[128:192].view(CHUNK_HEADER_EXT)[0]
             if int(self.header_ext["magic"]) != CHUNK_EXT_MAGIC or int(self.header_ext["bytes"]) < 64:
@@ -721,7 +747,10 @@ class Chunk:
             if int(self.header_ext["off_aac"]):
                 o = int(self.header_ext["off_aac"])
                 self.aac_table = self.raw[o:o + S * M * 128].view(CHUNK_AAC).reshape(S, M)
-        self.eti_table = None                   # the ETI section: [S] CHUNK_ETI, or None when the slab has none
+            if int(self.header_ext["off_scope"]):
+                o = int(self.header_ext["off_scope"])
+                self.scope_table = self.raw[o:o + S * 32].view(CHUNK_SCOPE)
+        self.eti_table = None                  # the ETI section: [S] CHUNK_ETI, or None when the slab has none
         if int(h["off_eti"]):
             self.eti_table = self.raw[int(h["off_eti"]):int(h["off_eti"]) + S * 64].view(CHUNK_ETI)
 
@@ -736,6 +765,19 @@ class Chunk:
             o = int(r["ev_off"]) + k * TII_EVENT_SLOT_BYTES
             ev = self.raw[o:o + 32].view(TII_EVENT)[0]
             out.append((ev, self.raw[o + 32:o + 32 + 16 * int(ev["n_results"])].view(TII_RESULT)))
+        return out
+
+    def scope(self, stream):
+        """Scope records of `stream` in this chunk, oldest first: a list of (SCOPE_RECORD record, iq [1536] complex64, carr [1536] float32),
+        views.  Empty when the slab has no scope section or the stream had the mode off when the delivery was opened."""
+        if self.scope_table is None:
+            return []
+        r = self.scope_table[stream]
+        out = []
+        for k in range(int(r["n_records"])):
+            o = int(r["rec_off"]) + k * SCOPE_SLOT_BYTES
+            out.append((self.raw[o:o + 32].view(SCOPE_RECORD)[0], self.raw[o + 32:o + 32 + SCOPE_CARRIERS * 8].view(np.complex64),
+                        self.raw[o + 32 + SCOPE_CARRIERS * 8:o + SCOPE_SLOT_BYTES].view(np.float32)))
         return out
 
     def eti(self, stream):
@@ -1005,6 +1047,32 @@ class Engine:
         L.dabx_get_tii_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         check(L.dabx_get_tii_stats(self._h, stream, _p(st)))
         return {k: int(st[k][0]) for k in TII_STATS.names if k != "reserved"}
+
+    def set_scope_mode(self, stream, iq_type=0, carrier_type=0, symbol=0, enable=True):
+        """The stream's IQ scope and carrier plot on the device (dabx_set_scope_mode; stream = -1: all streams): a record whenever the
+        reference would show a symbol (symbol = 0), or for OFDM symbol `symbol` (1..75) of every decoded frame; read with read_scope."""
+        cfg = ScopeConfig(enable=int(bool(enable)), iq_type=iq_type, carrier_type=carrier_type, symbol=symbol)
+        L = load()
+        L.dabx_set_scope_mode.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        check(L.dabx_set_scope_mode(self._h, stream, C.byref(cfg)))
+
+    def read_scope(self, stream, max_records=8):
+        """The records completed since the previous call: ([(SCOPE_RECORD record, iq [1536] complex64, carr [1536] float32)], records lost)."""
+        recs = np.zeros(max_records, SCOPE_RECORD)
+        iq = np.zeros((max_records, SCOPE_CARRIERS), np.complex64)
+        carr = np.zeros((max_records, SCOPE_CARRIERS), np.float32)
+        lost = C.c_int32(0)
+        L = load()
+        L.dabx_read_scope.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        n = check(L.dabx_read_scope(self._h, stream, max_records, _p(recs), _p(iq), _p(carr), C.byref(lost)))
+        return [(recs[k], iq[k], carr[k]) for k in range(n)], lost.value
+
+    def scope_stats(self, stream):
+        st = np.zeros(1, SCOPE_STATS)
+        L = load()
+        L.dabx_get_scope_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        check(L.dabx_get_scope_stats(self._h, stream, _p(st)))
+        return {k: int(st[k][0]) for k in SCOPE_STATS.names if k != "reserved"}
 
     def read_eti(self, stream, max_frames=32):
         out = np.zeros((max_frames, 6144), np.uint8)

@@ -974,7 +974,14 @@ enum { DABX_DELIVER_FIB = 1, DABX_DELIVER_MSC = 2, DABX_DELIVER_SF = 4,
           launched are exactly what they are without it.  With the bit the header is followed by a dabx_chunk_header_ext; the section exists
           while at least one slot has the mode on.  The value is 2048, not 1024: the mask 1024 has always been refused with DABX_E_ARG and
           callers rely on that (tests/test_gpu_mp2_audio_delivery.py), so 1024 stays refused */
-       DABX_DELIVER_AAC = 2048 };
+       DABX_DELIVER_AAC = 2048,
+       /* the scope records of every stream whose IQ scope runs on the device (dabx_set_scope_mode; the scope section, dabx_chunk_scope
+          below).  Opt-in exactly like the four bits above: what == 0 does NOT include it, the bit alone or with only DABX_DELIVER_ETI, _TII,
+          _MP2_AUDIO and _AAC beside it is DABX_E_ARG, and without the bit a slab, dabx_delivery_slab_bytes and the kernels launched are
+          exactly what they are without it.  With the bit the header is followed by a dabx_chunk_header_ext.  The value is 8192, not 1024
+          and not 4096: both masks have always been refused with DABX_E_ARG and callers rely on that
+          (tests/test_gpu_aac_stream_delivery.py), so both stay refused */
+       DABX_DELIVER_SCOPE = 8192 };
 typedef struct {
   int32_t host_slabs;       /* page-locked host slabs, >= 2 (0 = default 4) */
   int32_t what;             /* DABX_DELIVER_* mask, 0 = everything */
@@ -1003,7 +1010,8 @@ typedef struct {
   uint64_t off_tii;         /* the TII section: dabx_chunk_tii[n_streams]; 0 = the slab has none */
   uint64_t off_mp2_audio;   /* the MP2 audio section: dabx_chunk_mp2_audio[n_streams * max_subch]; 0 = the slab has none */
   uint64_t off_aac;         /* the AAC section: dabx_chunk_aac[n_streams * max_subch]; 0 = the slab has none */
-  uint64_t reserved[4];
+  uint64_t off_scope;       /* the scope section: dabx_chunk_scope[n_streams]; 0 = the slab has none */
+  uint64_t reserved[3];
 } dabx_chunk_header_ext;    /* 64 bytes */
 typedef struct {
   int64_t first_frame;      /* index, since the stream was opened, of the first frame in the chunk */
@@ -1120,6 +1128,19 @@ typedef struct {
   uint64_t ev_off;
   int64_t  events_total;    /* events the stream's detector has completed so far: first_event + n_events */
 } dabx_chunk_tii;           /* 32 bytes */
+/* The scope section (DABX_DELIVER_SCOPE; "IQ scope and carrier plots" below): one dabx_chunk_scope per stream from
+ * dabx_chunk_header_ext.off_scope, in the slab's head part behind the AAC section (or where that would be), followed by room for
+ * DABX_CHUNK_FRAMES record slots for each stream that has the mode on WHEN THE DELIVERY IS OPENED (a chunk's frames cannot show more; a
+ * stream switched on later has no room and delivers none: rec_off = 0).  A record slot is a dabx_scope_record, the IQ vector [1536] cf32
+ * and the carrier vector [1536] f32, DABX_SCOPE_SLOT_BYTES in all, byte for byte what dabx_read_scope returns; stream s's n_records slots
+ * lie one behind the other from rec_off, oldest first.  Every record a stream wrote since the previous chunk is in the chunk or counted in
+ * records_lost.  Gathered on the front-end stream when the chunk closes (k_deliver_scope), with a cursor of its own. */
+typedef struct {
+  int64_t  first_record;    /* number, since the stream's mode was first switched on, of the first record in the chunk */
+  int32_t  n_records, records_lost;
+  uint64_t rec_off;         /* 0 = the stream has no room in this delivery */
+  int64_t  records_total;   /* records the stream has written so far: first_record + n_records */
+} dabx_chunk_scope;         /* 32 bytes */
 typedef struct {
   uint64_t seq;
   const void *data;         /* the host slab: valid until dabx_delivery_release(seq) */
@@ -1348,7 +1369,63 @@ int  dabx_tii_process_device(int n, const float *sums, float *pairs, const dabx_
                              int32_t *n_results, int32_t *n_found);
 
 /* ------------------------------------------------------------------------------------------------------------
- * MP2 audio: the MP2 decoder of a DAB (MPEG-1/2 Audio Layer II) audio sub-channel on the device -- Mp2Processor's frame assembly and
+ * IQ scope and carrier plots: what OfdmDecoder hands its user on a shown symbol -- the constellation mIqVector and the per-carrier plot
+ * mCarrVector (base/ofdm/ofdm_decoder.cpp:258-291, 303-324) --, computed on the device from the state the engine's demapper keeps
+ * (csrc/scope_core.h, k_scope: one 768-thread block per stream with the mode on, directly in front of the frame's first demapper launch;
+ * docs/history/scope.md).  The demapper kernels are not touched: k_scope replays the frame's demapper recurrences up to the shown symbol.
+ * Which symbol (cfg.symbol): 0 follows the reference's two counters (mShowCntIqScope > 76 on symbol mNextShownOfdmSymbIdx, which the
+ * statistics counter (> 380) moves on by one, 75 wrapping to 1; :154-157, :323, :349-351; neither is touched by reset()) -- from a fresh
+ * engine decoded frames 3, 5, 7 at symbol 1, then frame 9 at symbol 2, and so on; 1..75 shows that symbol of every decoded frame (the two
+ * counters run on underneath as they would with 0).  The counters are the stream's, kept on the device, advanced only by frames the
+ * stream decodes while its mode is on; changing the types of an enabled stream keeps them.
+ * iq_type: EIqPlotType 0..2 (glob_enums.h: PHASE_CORR_CARR_NORMED, PHASE_CORR_MEAN_NORMED, RAW_MEAN_NORMED).  3 and 4 (the DC-offset plots)
+ * are refused with DABX_E_ARG: they need the DC bin and mDcAdc, which the stored spectra do not carry.
+ * carrier_type: ECarrierPlotType 0..9 (SB_WEIGHT, EVM_PER, EVM_DB, STD_DEV, PHASE_ERROR, PRS_PHASE, PRS_PHASE_UNWRAP, FOUR_QUAD_PHASE,
+ * REL_POWER, SNR) and 13 (NULL_OVR_POW).  10..12 (the three NULL_* level plots) are refused with DABX_E_ARG: they need a per-bin IIR over
+ * null-symbol spectra that nothing keeps.  STD_DEV needs dabx_set_lcd_statistics(on) (the phase-deviation IIR, :204-208): DABX_E_STATE
+ * without it.  REL_POWER and NULL_OVR_POW use mMeanPowerOvrAll as it stands after carriers 0..k of the shown symbol (:214 lies inside the
+ * carrier loop), the two mean-normed IQ plots as it stood in front of the symbol (:162).
+ * The IQ vector is indexed by nomCarrIdx, the carrier vector by realCarrRelIdx, as the reference fills them. */
+typedef struct {
+  int32_t enable;
+  int32_t iq_type;           /* EIqPlotType 0..2 */
+  int32_t carrier_type;      /* ECarrierPlotType 0..9, 13 */
+  int32_t symbol;            /* 0 = the reference's cadence, 1..75 = this OFDM symbol of every decoded frame */
+  int32_t reserved[4];
+} dabx_scope_config;         /* 32 bytes */
+typedef struct {
+  int64_t frame;             /* the stream's frame (index since it was opened) the symbol belongs to */
+  int32_t symbol;            /* 1..75 */
+  uint8_t iq_type, carrier_type, soft_bit_type /* ESoftBitType 1..3 the demapper ran with */, reserved0;
+  float   mean_value;        /* mMeanValue in front of the symbol (:234-250) */
+  float   mean_power_all;    /* mMeanPowerOvrAll in front of the symbol (:162) */
+  int32_t reserved[2];
+} dabx_scope_record;         /* 32 bytes */
+#define DABX_SCOPE_CARRIERS 1536
+#define DABX_SCOPE_SLOT_BYTES (32 + DABX_SCOPE_CARRIERS * 8 + DABX_SCOPE_CARRIERS * 4)   /* record, IQ vector (cf32), carrier vector (f32) */
+typedef struct {
+  int64_t shows;             /* records written for the stream */
+  int64_t lost;              /* records dabx_read_scope found gone from the ring of 8 */
+  int64_t launches;          /* k_scope launches of the engine (the kernel has no row in the profile table) */
+  int64_t reserved[5];
+} dabx_scope_stats;          /* 64 bytes */
+/* ofdm_decoder.h:86-88, set_select_iq_plot_type / set_select_carrier_plot_type.  stream = -1: all streams.  cfg = NULL: defaults (types 0,
+ * the reference's cadence), enabled.  The first enable allocates the stage; an engine that never enables the mode allocates and launches
+ * nothing for it, and with no stream enabled the launch sequence is what it is without the mode.  Drains the engine. */
+int  dabx_set_scope_mode(dabx_engine *e, int stream, const dabx_scope_config *cfg);
+/* ofdm_decoder.cpp:320-322 (the two ring buffers and signal_slot_show_iq).  The records `stream` completed since the previous call, oldest
+ * first, at most max_records: recs [max], iq [max][1536] cf32, carr [max][1536] f32 (either vector optional).  The device keeps the last 8
+ * per stream; *lost (optional) counts those that had left.  Drains the engine; a cursor of its own.  Returns the number of records. */
+int  dabx_read_scope(dabx_engine *e, int stream, int max_records, dabx_scope_record *recs, float *iq, float *carr, int32_t *lost);
+/* Any engine; all zeros without the mode (launches is the engine's, the same for every stream).  (:323: every show counts.) */
+int  dabx_get_scope_stats(dabx_engine *e, int stream, dabx_scope_stats *out);
+/* ofdm_decoder.cpp:154-157, :323, :349-351 on the host, no engine and no device: the two counters over the 75 decode_symbol calls of one
+ * decoded frame -- the very function k_scope runs.  counters = { mShowCntIqScope, mShowCntStatistics, mNextShownOfdmSymbIdx }, in and out
+ * (a fresh decoder: 0, 0, 1).  Returns the symbol shown in that frame, 0 = none. */
+int  dabx_scope_cadence_frame(int32_t counters[3]);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * MP2 audio:the MP2 decoder of a DAB (MPEG-1/2 Audio Layer II) audio sub-channel on the device -- Mp2Processor's frame assembly and
  * _mp2_decode_frame (base/backend/audio/mp2processor.cpp:197-243, :292-609, :678-763; kjmp2), k_mp2_audio: one 256-thread block per
  * slot with the mode on, behind k_dabplus on the MSC batch's stream, beside the PAD stage.  The decoder is pure 32-bit integer
  * arithmetic, so the device gives the reference's samples exactly: 1152 stereo int16 samples per MP2 frame for which _mp2_decode_frame
