@@ -178,8 +178,16 @@ __device__ inline int prs_correlate_block(float2 v[8], float threshold, int stro
   return s_res;
 }
 
+// (int)(float) as x86-64 compiles it: cvttss2si gives "integer indefinite" 0x80000000 for NaN and for anything outside the int range
+__device__ __forceinline__ int cvt_i32_x86(float x)
+{
+  if (!(fabsf(x) < 2147483648.0f)) return (int)0x80000000u;
+  return (int)x;
+}
+
 // ---- coarse CFO: PhaseReference::estimate_carrier_offset_from_sync_symbol_0 (:223-280) -----------------
-// X = FFT of symbol 0 in the strided register layout.  Returns Hz (int) or IDX_NOT_FOUND (100000).
+// X = FFT of symbol 0 in the strided register layout.  Returns Hz (int) or IDX_NOT_FOUND (100000); INT_MIN where the estimate is
+// not finite (every magnitude 0, or some of them inf), which the reference's callers take as "found".
 __device__ inline int coarse_cfo_block(const float2 X[8], const DevTables &t, float2 *lds, float *mag /* >= 160 floats LDS */,
                                        int tid)
 {
@@ -202,17 +210,20 @@ __device__ inline int coarse_cfo_block(const float2 X[8], const DevTables &t, fl
 #pragma unroll
   for (int u = 0; u < 8; u++) v[u] = cmul(v[u], t.prs_arg_conj[tid + 256 * u]);
   fft2048<false>(v, lds, t.twiddle, tid);
-  // |.| of bins -70..70 -> mag[0..140]
+  // |.| of bins -71..71 -> mag[0..142].  Where no bin of the window is > 0 the index stays IDX_NOT_FOUND and the reference interpolates
+  // over the bins (Tu + IDX_NOT_FOUND + i - 1) % Tu = 1695..1697 -> mag[144..146]
+  constexpr int IDX_NOT_FOUND = 100000, NF0 = (TU + IDX_NOT_FOUND - 1) % TU;
 #pragma unroll
   for (int u = 0; u < 8; u++) {
     const int i = tid + 256 * u;
     if (i <= 71) mag[71 + i] = cabsf_(v[u]);            // bins 0..71 (71 only feeds the interpolation)
     if (i >= TU - 71) mag[71 + i - TU] = cabsf_(v[u]);   // bins -71..-1
+    if (u == NF0 / 256 && i >= NF0 && i < NF0 + 3) mag[144 + i - NF0] = cabsf_(v[u]);
   }
   __syncthreads();
   __shared__ int s_hz;
   if (tid == 0) {
-    int index = 100000;
+    int index = IDX_NOT_FOUND;
     float mx = 0.f, avg = 0.f;
     for (int i = -70; i <= 70; ++i) {
       const float val = mag[71 + i];
@@ -220,12 +231,13 @@ __device__ inline int coarse_cfo_block(const float2 X[8], const DevTables &t, fl
       avg += val;
     }
     avg /= 141.0f;
-    if (mx < avg * 5) s_hz = 100000;
+    if (mx < avg * 5) s_hz = IDX_NOT_FOUND;
     else {
-      const float p0 = mag[71 + index - 1], p1 = mag[71 + index], p2 = mag[71 + index + 1];
+      const int at = index == IDX_NOT_FOUND ? 145 : 71 + index;
+      const float p0 = mag[at - 1], p1 = mag[at], p2 = mag[at + 1];
       const float psum = (0.0f + p0) + p1 + p2;
       const float offset = (float)index + (p2 - p0) / psum;
-      s_hz = (int)(offset * 1000.0f);
+      s_hz = cvt_i32_x86(offset * 1000.0f);
     }
   }
   __syncthreads();
