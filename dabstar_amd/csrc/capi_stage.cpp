@@ -236,6 +236,22 @@ int dabx_tii_process_device(int n, const float *sums, float *pairs, const dabx_t
   return dnf.to_host(n_found, 4 * N);
 }
 
+// cir_viewer.cpp:66-95 on crafted rows: the row function of k_cir (cir_core.h, cir_row_block), one block per row
+int dabx_cir_rows_device(const float *iq, int n_rows, float *y)
+{
+  if (!iq || !y || n_rows <= 0 || n_rows > 65535) { set_error("dabx_cir_rows_device: bad argument"); return DABX_E_ARG; }
+  int rc = need_device();
+  if (rc) return rc;
+  DevBuf din, dout;
+  const size_t nb = sizeof(float2) * TU * (size_t)n_rows;
+  if ((rc = din.alloc(nb)) || (rc = dout.alloc(sizeof(float) * (size_t)n_rows))) return rc;
+  DABX_HIP(hipMemcpy(din.p, iq, nb, hipMemcpyHostToDevice));
+  if ((rc = launch_cir_rows_test(din.as<float2>(), n_rows, dout.as<float>(), 0))) return rc;
+  DABX_HIP(hipDeviceSynchronize());
+  DABX_HIP(hipMemcpy(y, dout.p, sizeof(float) * (size_t)n_rows, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int dabx_fft2048(const dabx_cf32 *in, int batch, int inverse, dabx_cf32 *out)
 {
   if (!in || !out || batch <= 0) { set_error("dabx_fft2048: bad argument"); return DABX_E_ARG; }

@@ -82,6 +82,7 @@ int launch_firecode(uint8_t *x, int batch, int correct, uint8_t *ok, hipStream_t
 int launch_crc16_check(const uint8_t *msgs, int stride, int len, int batch, uint8_t *ok, hipStream_t st);
 // ofdm.hip
 int launch_fft2048(const float2 *in, int batch, int inverse, float2 *out, hipStream_t st);
+int launch_cir_rows_test(const float2 *in, int n_rows, float *y, hipStream_t st);   // pipeline.hip: dabx_cir_rows_device
 int launch_prs_correlate(const float2 *v, int batch, float threshold, int strongest, int32_t *start, hipStream_t st);
 int launch_coarse_cfo(const float2 *fft, int batch, int32_t *hz, hipStream_t st);
 int launch_demap_reset(DemapDev &d, hipStream_t st);

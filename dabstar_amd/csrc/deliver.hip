@@ -15,6 +15,7 @@
 #include "eti_core.h"
 #include "tii_core.h"
 #include "scope_core.h"
+#include "cir_core.h"
 #include "fig00.h"
 
 namespace dabx {
@@ -403,6 +404,40 @@ __global__ __launch_bounds__(256) void k_deliver_scope(EngineDev e, ScopeDeliver
 int launch_deliver_scope(const EngineDev &e, const ScopeDeliverDev &sd, hipStream_t st)
 {
   hipLaunchKernelGGL(k_deliver_scope, dim3(e.n_streams), dim3(256), 0, st, e, sd);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+
+// The CIR section (include/dabx.h, dabx_chunk_cir; pipeline.h, CirDeliverDev).  grid = n_streams, 256 threads, front-end stream, behind k_deliver_front -- so behind the k_cir_finish and
+// k_cir_corr of the chunk's last frame, which run on that stream: the records of both kinds the stream has completed since the previous
+// chunk, the newest DABX_CIR_CHUNK_RECORDS of them, out of the stage's ring.  A stream without room in the slab (rec_off 0) delivers none.
+__global__ __launch_bounds__(256) void k_deliver_cir(CirDeliverDev sd)
+{
+  const int s = blockIdx.x, tid = threadIdx.x;
+  constexpr int CAP = DABX_CIR_CHUNK_RECORDS < CIR_RING ? DABX_CIR_CHUNK_RECORDS : CIR_RING, SLOT_Q = CIR_SLOT_BYTES / 16;
+  static_assert(CIR_SLOT_BYTES % 16 == 0, "a record slot is copied in 16-byte words");
+  const unsigned long long rec_off = sd.rec_off[s];
+  const long long total = sd.ring ? sd.shows[(size_t)s * sd.st_stride] : 0, have = rec_off ? total - sd.done[s] : 0;
+  int n = (int)(have < CAP ? have : CAP);
+  if (n < 0) n = 0;
+  const long long first = total - n;
+  if (tid == 0) {
+    dabx_chunk_cir r;
+    r.first_record = first; r.n_records = n; r.records_lost = (int)(have > n ? have - n : 0); r.rec_off = rec_off; r.records_total = total;
+    reinterpret_cast<dabx_chunk_cir *>(sd.slab + sd.off_cir)[s] = r;
+  }
+  uint4 *o = reinterpret_cast<uint4 *>(sd.slab + rec_off);
+  for (int i = tid; i < n * SLOT_Q; i += 256) {
+    const int k = i / SLOT_Q, wd = i - k * SLOT_Q;
+    o[i] = reinterpret_cast<const uint4 *>(sd.ring + ((size_t)s * CIR_RING + (size_t)((first + k) % CIR_RING)) * CIR_SLOT_BYTES)[wd];
+  }
+  __syncthreads();
+  if (tid == 0) sd.done[s] = total;
+}
+
+int launch_deliver_cir(int n_streams, const CirDeliverDev &sd, hipStream_t st)
+{
+  hipLaunchKernelGGL(k_deliver_cir, dim3(n_streams), dim3(256), 0, st, sd);
   DABX_HIP(hipGetLastError());
   return 0;
 }

@@ -9,6 +9,7 @@
 #include "aac_core.h"
 #include "tii_core.h"
 #include "scope_core.h"
+#include "cir_core.h"
 #include "sdma.h"
 #include "iqfile.h"
 #include <algorithm>
@@ -73,6 +74,11 @@ struct Delivery {
   unsigned long long *scope_off = nullptr;
   std::vector<char> scope_room;                  // [S] the stream had the mode on when the delivery was opened
   bool scope() const { return (what & DABX_DELIVER_SCOPE) != 0; }
+  // DABX_DELIVER_CIR (deliver.hip, k_deliver_cir): the same three for the CIR section
+  long long *cir_done = nullptr;
+  unsigned long long *cir_off = nullptr;
+  std::vector<char> cir_room;
+  bool cir() const { return (what & DABX_DELIVER_CIR) != 0; }
   bool tii() const { return (what & DABX_DELIVER_TII) != 0; }
   bool mp2_audio() const { return (what & DABX_DELIVER_MP2_AUDIO) != 0; }      // the MP2 audio section (deliver.hip, k_deliver_mp2_audio), while a slot has the mode on
   bool aac() const { return (what & DABX_DELIVER_AAC) != 0; }      // the AAC section (deliver.hip, k_deliver_aac), while a slot has the mode on
@@ -188,6 +194,21 @@ struct ScopeStage {
   bool exists() const { return dev.ring != nullptr; }
 };
 
+// The CIR / correlation plot stage (include/dabx.h dabx_set_cir_mode, pipeline.hip k_cir, k_cir_finish, k_cir_corr).  Nothing of it exists until
+// the mode is first switched on: dev stays all null, n_on stays 0 and no step launches a kernel of it.
+struct CirStage {
+  CirDev dev{};
+  int32_t *list = nullptr;                     // [S] device: the first n_on entries are the streams with the mode on (CirDev::list)
+  CirCfgDev *cfg_dev = nullptr;                // [S] (CirDev::cfg)
+  int n_on = 0, n_corr = 0;                    // streams with the mode on / with the correlation plot on
+  std::vector<CirCfgDev> cfg;                  // [S] mirror of cfg_dev
+  std::vector<CirState> walk;                  // [S] the host's own window / row bookkeeping (base, win, rows_done): the same function over the same
+                                               //     wr as the device's, so that a step launches as many blocks per stream as rows are due
+  std::vector<long long> seen, lost;           // [S] records dabx_read_cir has returned or passed / found gone
+  long long launches = 0;
+  bool exists() const { return dev.ring != nullptr; }
+};
+
 struct dabx_engine : dabx::EngineHead {         // (iqfile.h: the ring format, where iqfile.cpp can read it)
   dabx_config cfg{};
   EngineDev dev{};
@@ -207,6 +228,7 @@ struct dabx_engine : dabx::EngineHead {         // (iqfile.h: the ring format, w
   std::vector<int> tii_epoch;                  // [S] reset epoch seen by the detector
   TiiStage tiis;                               // the detectors on the device
   ScopeStage scope;                            // the IQ scope and carrier plots on the device
+  CirStage cir;                                // the channel impulse response and the correlation plot on the device
   std::vector<void *> allocs;
   void *stage = nullptr;                       // host -> device staging of dabx_push_iq
   size_t stage_cap = 0;
@@ -289,6 +311,9 @@ void ingest_free(dabx_engine *e);
 void tii_stage_free(dabx_engine *e);
 // engine_scope.cpp
 void scope_stage_free(dabx_engine *e);
+// engine_cir.cpp
+void cir_stage_free(dabx_engine *e);
+int cir_step_cap(dabx_engine *e, bool advance);   // the rows due per stream in the step about to be launched, at most; advance: the host's bookkeeping moves on
 // engine_slots.cpp
 void pad_count_sources(dabx_engine *e);
 int mot_follow_pad(dabx_engine *e);

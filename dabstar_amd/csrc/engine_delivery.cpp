@@ -105,6 +105,14 @@ int dabx_engine::delivery_layout()
       if (D.scope_room[s_]) { so[s_] = off; off += (size_t)DL_FRAMES * SCOPE_SLOT_BYTES; }
     DABX_HIP(hipMemcpy(D.scope_off, so.data(), sizeof(unsigned long long) * S, hipMemcpyHostToDevice));
   }
+  // the CIR section: its table, then DABX_CIR_CHUNK_RECORDS record slots for every stream that had the mode on when the delivery was opened
+  if (D.cir()) {
+    off = align_up(off, 16); x.off_cir = off; off += S * sizeof(dabx_chunk_cir);
+    std::vector<unsigned long long> so(S, 0);
+    for (size_t s_ = 0; s_ < S; s_++)
+      if (D.cir_room[s_]) { so[s_] = off; off += (size_t)DABX_CIR_CHUNK_RECORDS * CIR_SLOT_BYTES; }
+    DABX_HIP(hipMemcpy(D.cir_off, so.data(), sizeof(unsigned long long) * S, hipMemcpyHostToDevice));
+  }
   off = align_up(off, 256);
   h.off_msc = off;
   if ((D.what & (DABX_DELIVER_MSC | DABX_DELIVER_MSC_NOT_DABPLUS)) && !d.fic_only)
@@ -193,6 +201,10 @@ int dabx_engine::delivery_begin(DeliverDev *dv, int *slot, int *devslab)
   if (!rc && D.scope())
     rc = launch_deliver_scope(dev, ScopeDeliverDev{D.dev[*devslab], D.ext.off_scope, D.scope_off, D.scope_done, scope.dev.ring,
                                                    scope.exists() ? &scope.dev.st->shows : nullptr, (int32_t)(sizeof(ScopeState) / sizeof(long long)), 0}, stream);
+  // the CIR section: behind the k_cir_finish and k_cir_corr of the chunk's last frame, which the front-end stream has run (deliver.hip, k_deliver_cir)
+  if (!rc && D.cir())
+    rc = launch_deliver_cir(dev.n_streams, CirDeliverDev{D.dev[*devslab], D.ext.off_cir, D.cir_off, D.cir_done, cir.dev.ring,
+                                                 cir.exists() ? &cir.dev.st->shows : nullptr, (int32_t)(sizeof(CirState) / sizeof(long long)), 0}, stream);
   if (rc) {                                                        // nothing was queued: give the slabs back
     std::lock_guard<std::mutex> lk(D.mu);
     D.dev_busy[*devslab] = false;
@@ -332,9 +344,10 @@ void delivery_free(dabx_engine *e)
   }
   for (void *q : {(void *)D.layout_off, (void *)D.subch_id, (void *)D.frames_done, (void *)D.cif_done, (void *)D.sf_done, (void *)D.eti_front,
                   (void *)D.eti_next, (void *)D.eti_stage[0], (void *)D.eti_stage[1], (void *)D.eti_stage[2], (void *)D.tii_done, (void *)D.scope_done,
-                  (void *)D.scope_off}) if (q) (void)hipFree(q);
+                  (void *)D.scope_off, (void *)D.cir_done, (void *)D.cir_off}) if (q) (void)hipFree(q);
   D.tii_done = nullptr; D.ext = dabx_chunk_header_ext{};
   D.scope_done = nullptr; D.scope_off = nullptr; D.scope_room.clear();
+  D.cir_done = nullptr; D.cir_off = nullptr; D.cir_room.clear();
   D.layout_off = nullptr; D.subch_id = nullptr; D.frames_done = D.cif_done = D.sf_done = nullptr;
   D.eti_front = nullptr; D.eti_next = nullptr; D.eti_rows_off = 0;
   for (int k = 0; k < Delivery::NDEV; k++) D.eti_stage[k] = nullptr;
@@ -351,7 +364,7 @@ extern "C" {
 
 int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
 {
-  if (!e || (cfg && (cfg->host_slabs < 0 || cfg->host_slabs == 1 || cfg->host_slabs > 64 || (cfg->what & ~(1023 | DABX_DELIVER_AAC | DABX_DELIVER_SCOPE)) || cfg->copy_engine < 0 || cfg->copy_engine > 1))) {
+  if (!e || (cfg && (cfg->host_slabs < 0 || cfg->host_slabs == 1 || cfg->host_slabs > 64 || (cfg->what & ~(1023 | DABX_DELIVER_AAC | DABX_DELIVER_SCOPE | DABX_DELIVER_CIR)) || cfg->copy_engine < 0 || cfg->copy_engine > 1))) {
     set_error("dabx_delivery_open: bad argument");
     return DABX_E_ARG;
   }
@@ -375,6 +388,12 @@ int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
   if (cfg && (cfg->what & DABX_DELIVER_SCOPE) &&
       !(cfg->what & ~(DABX_DELIVER_SCOPE | DABX_DELIVER_AAC | DABX_DELIVER_MP2_AUDIO | DABX_DELIVER_TII | DABX_DELIVER_ETI))) {
     set_error("dabx_delivery_open: DABX_DELIVER_SCOPE needs at least one DABX_DELIVER_* bit below 128 beside it");
+    return DABX_E_ARG;
+  }
+  // ... and DABX_DELIVER_CIR, in the same way
+  if (cfg && (cfg->what & DABX_DELIVER_CIR) &&
+      !(cfg->what & ~(DABX_DELIVER_CIR | DABX_DELIVER_SCOPE | DABX_DELIVER_AAC | DABX_DELIVER_MP2_AUDIO | DABX_DELIVER_TII | DABX_DELIVER_ETI))) {
+    set_error("dabx_delivery_open: DABX_DELIVER_CIR needs at least one DABX_DELIVER_* bit below 128 beside it");
     return DABX_E_ARG;
   }
   if (e->dl.open) { set_error("dabx_delivery_open: already open"); return DABX_E_STATE; }
@@ -421,6 +440,13 @@ int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
     if (e->scope.exists())
       for (size_t s_ = 0; s_ < S; s_++) { D.scope_room[s_] = (char)(e->scope.cfg[s_].enable != 0); n_on += D.scope_room[s_] ? 1 : 0; }
     cap += (D.tii() || D.mp2_audio() || D.aac() ? 0 : sizeof(dabx_chunk_header_ext)) + 16 + S * sizeof(dabx_chunk_scope) + n_on * (size_t)DL_FRAMES * SCOPE_SLOT_BYTES;
+  }
+  D.cir_room.assign(D.cir() ? S : 0, 0);
+  if (D.cir()) {                                                    // ... and the CIR section: its table and DABX_CIR_CHUNK_RECORDS record slots per stream with the mode on
+    size_t n_on = 0;
+    if (e->cir.exists())
+      for (size_t s_ = 0; s_ < S; s_++) { D.cir_room[s_] = (char)(e->cir.cfg[s_].enable != 0); n_on += D.cir_room[s_] ? 1 : 0; }
+    cap += (D.tii() || D.mp2_audio() || D.aac() || D.scope() ? 0 : sizeof(dabx_chunk_header_ext)) + 16 + S * sizeof(dabx_chunk_cir) + n_on * (size_t)DABX_CIR_CHUNK_RECORDS * CIR_SLOT_BYTES;
   }
   D.capacity = align_up(cap, 4096);
 #define H(x) do { hipError_t err__ = (x); if (err__ != hipSuccess) { set_error("HIP error %d (%s) at %s:%d", (int)err__, hipGetErrorString(err__), __FILE__, __LINE__); delivery_free(e); return DABX_E_HIP; } } while (0)
@@ -491,6 +517,18 @@ int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
       H(hipMalloc((void **)&D.scope_done, sizeof(long long) * S));
       H(hipMemcpy(D.scope_done, sd.data(), sizeof(long long) * S, hipMemcpyHostToDevice));
       H(hipMalloc((void **)&D.scope_off, sizeof(unsigned long long) * S));
+    }
+    if (D.cir()) {
+      // the CIR section's cursor: the records completed from now on
+      std::vector<long long> cdn(S, 0);
+      if (e->cir.exists()) {
+        std::vector<CirState> st(S);
+        H(hipMemcpy(st.data(), e->cir.dev.st, sizeof(CirState) * S, hipMemcpyDeviceToHost));
+        for (size_t s_ = 0; s_ < S; s_++) cdn[s_] = st[s_].shows;
+      }
+      H(hipMalloc((void **)&D.cir_done, sizeof(long long) * S));
+      H(hipMemcpy(D.cir_done, cdn.data(), sizeof(long long) * S, hipMemcpyHostToDevice));
+      H(hipMalloc((void **)&D.cir_off, sizeof(unsigned long long) * S));
     }
   }
 #undef H

@@ -127,8 +127,8 @@ __device__ __forceinline__ int nco_advance(int phase0, int f, long long n)   // 
 // ---- PRS correlator: PhaseReference::correlate_with_phase_ref_and_find_max_peak ----------------------
 // (base/ofdm/phasereference.cpp:87-213).  v = T_u samples in the strided register layout of fft_core.h.
 // Returns the start index (first local maximum above threshold * mean in [254, 1004)) or -1.
-__device__ inline int prs_correlate_block(float2 v[8], float threshold, int strongest, const DevTables &t, float2 *lds,
-                                          float *peak /* [2048] LDS */, float *red, int tid)
+// The part the correlation plot (cir_core.h, k_cir_corr) needs too: mCorrPeakValues into peak[], returns sum / T_u (:90-126).
+__device__ __forceinline__ float prs_correlate_peaks(float2 v[8], const DevTables &t, float2 *lds, float *peak /* [2048] LDS */, float *red, int tid)
 {
   fft2048<false>(v, lds, t.twiddle, tid);
 #pragma unroll
@@ -139,6 +139,12 @@ __device__ inline int prs_correlate_block(float2 v[8], float threshold, int stro
   for (int u = 0; u < 8; u++) { const float a = cabsf_(v[u]); peak[tid + 256 * u] = a; part += a; }   // :116-122
   float sum = block_sum(part, red, tid) / (float)TU;
   __syncthreads();
+  return sum;
+}
+__device__ inline int prs_correlate_block(float2 v[8], float threshold, int strongest, const DevTables &t, float2 *lds,
+                                          float *peak /* [2048] LDS */, float *red, int tid)
+{
+  const float sum = prs_correlate_peaks(v, t, lds, peak, red, tid);
   if (sum == 0.f) return -1;
   constexpr int i0 = TG - 250, i1 = TG + 500, gap = 10;   // :136-139
   int *ired = reinterpret_cast<int *>(red);

@@ -26,6 +26,7 @@
 #include <algorithm>
 #include "ofdm_core.h"
 #include "scope_core.h"
+#include "cir_core.h"
 #include "viterbi_core.h"
 #include "fec_core.h"
 #include "acq_walk.h"
@@ -1886,6 +1887,226 @@ __global__ void k_msc_snap(EngineDev e, int cifs)
   e.snap[s] = BatchSnap{done > cif_no - cifs ? done : cif_no - cifs, cif_no};
 }
 
+// ---------------------------------------------------------------------------------------------------- CIR
+// The channel impulse response plot of CirViewer::show_cir (cir_viewer.cpp:54-107; cir_core.h; docs/history/cir.md), computed row by row as
+// the window's samples are committed instead of 385 rows at once every sixth frame.  At the head of a front-end step, on the front-end
+// stream behind an in-step k_acquire (and the k_dciq of the commits) and in front of k_frame_head: grid (ceil(cap / CIR_ROWS_PER_BLOCK), streams
+// with the mode on).  Block x of a stream computes rows rows_done + 4 x .. + 3 of the stream's current window as far as they are due (cir_rows_due: all
+// 2048 samples of a row committed) -- the samples k_frame_head reads in front of its NCO, RingFmt<RF>::cvt of the ring -- and stores its value into the
+// stream's row buffer.  `cap` is the host's own count of the rows due (the same function over its mirror of wr), so no block is idle in
+// steady state and a step with nothing due launches nothing; a cap below what is due only leaves rows to the next step.  k_cir_finish
+// (behind it, one block per stream) moves the bookkeeping on by the same count and, with row 384, writes the record.
+// A row is only read while the trust rule holds (cir_row_trusted), looked at before and after the loads; otherwise it is -1.
+template <int RF>
+__global__ __launch_bounds__(256) void k_cir(EngineDev e, DevTables t, CirDev cd, int cap)
+{
+  __shared__ float2 lds[FFT_LDS_FLOAT2];
+  __shared__ float red[8];
+  __shared__ unsigned long long s_look[2];
+  __shared__ float s_y[CIR_ROWS_PER_BLOCK];
+  const int s = cd.list[blockIdx.y], tid = threadIdx.x;
+  if (!cd.cfg[s].cir) return;
+  const CirState q = cd.st[s];
+  const int due = cir_rows_due(q.base, q.win, q.rows_done, e.wr[s], cap);
+  const int r0 = (int)blockIdx.x * CIR_ROWS_PER_BLOCK;     // this block's rows: rows_done + r0 .. + CIR_ROWS_PER_BLOCK - 1, as far as they are due
+  if (r0 >= due) return;
+  const int nr = due - r0 < CIR_ROWS_PER_BLOCK ? due - r0 : CIR_ROWS_PER_BLOCK;
+  const StreamCtl &c = e.ctl[s];
+  const unsigned long long len = (unsigned long long)e.ring_len;
+  // one thread looks -- the read position, and the write horizon in host memory --, once in front of the block's rows and once behind them;
+  // every row is judged by both looks
+  auto look = [&]() {
+    __syncthreads();
+    if (tid == 0) {
+      s_look[0] = __hip_atomic_load(&c.rd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      s_look[1] = __hip_atomic_load(&e.wr_horizon[s], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    __syncthreads();
+  };
+  look();
+  const unsigned long long rd0 = s_look[0], hz0 = s_look[1];
+#pragma unroll 1
+  for (int r = 0; r < nr; r++) {
+    const unsigned long long first = cir_row_first(q.base, q.win, q.rows_done + r0 + r);
+    float y = -1.0f;
+    if (cir_row_trusted(first, rd0, hz0, len)) {           // (block-uniform) a row that is not trusted is not loaded at all
+      const RingView<RF> rv(stream_ring<RF>(e, s), e.ring_len, first);
+      float2 v[8];
+#pragma unroll
+      for (int u = 0; u < 8; u++) v[u] = rv.at(tid + 256 * u);
+      y = cir_row_block(v, t, lds, red, tid);              // (its barriers stand behind every thread's loads)
+    }
+    if (tid == 0) s_y[r] = y;
+  }
+  look();
+  if (tid < nr) {
+    const unsigned long long first = cir_row_first(q.base, q.win, q.rows_done + r0 + tid);
+    cd.acc[(size_t)s * CIR_ROWS + q.rows_done + r0 + tid] = cir_row_trusted(first, s_look[0], s_look[1], len) ? s_y[tid] : -1.0f;
+  }
+}
+
+__global__ __launch_bounds__(64) void k_cir_finish(EngineDev e, CirDev cd, int cap)
+{
+  const int s = cd.list[blockIdx.x], lane = threadIdx.x;
+  if (!cd.cfg[s].cir) return;
+  CirState q = cd.st[s];
+  const int due = cir_rows_due(q.base, q.win, q.rows_done, e.wr[s], cap);
+  if (due == 0) return;
+  const unsigned long long w0 = cir_row_first(q.base, q.win, 0);
+  if (!cir_rows_advance(q.win, q.rows_done, due)) {
+    if (lane == 0) cd.st[s].rows_done = q.rows_done;
+    return;
+  }
+  uint8_t *slot = cd.ring + ((size_t)s * CIR_RING + (size_t)(q.shows % CIR_RING)) * CIR_SLOT_BYTES;
+  float *val = reinterpret_cast<float *>(slot + 32);
+  const float *acc = cd.acc + (size_t)s * CIR_ROWS;
+  int bad = 0;
+  for (int i = lane; i < CIR_CORR_LAGS; i += 64) {
+    const float a = i < CIR_ROWS ? acc[i] : 0.0f;
+    bad += (i < CIR_ROWS && a == -1.0f) ? 1 : 0;
+    val[i] = a;
+  }
+  int16_t *idx = reinterpret_cast<int16_t *>(slot + 32 + CIR_CORR_LAGS * 4);
+  for (int i = lane; i < CIR_INDEX_ROOM; i += 64) idx[i] = 0;
+  bad = wave_sum_int(bad);
+  if (lane == 0) {
+    dabx_cir_record r;
+    r.kind = DABX_CIR_KIND_CIR; r.n_values = CIR_ROWS; r.n_indices = 0; r.rows_untrusted = bad;
+    r.frame = e.ctl[s].frames; r.first_sample = (int64_t)w0; r.threshold = 0.0f; r.reserved[0] = r.reserved[1] = r.reserved[2] = 0;
+    *reinterpret_cast<dabx_cir_record *>(slot) = r;
+    q.shows++; q.shows_kind[0]++; q.rows_untrusted += bad;
+    cd.st[s] = q;
+  }
+}
+
+// The correlation plot of PhaseReference::correlate_with_phase_ref_and_find_max_peak (phasereference.cpp:110-195; include/dabx.h).  One
+// block per stream with the mode on, directly in front of k_frame_head on the same HIP stream, with the search in step (dabx_process): the
+// state, rd, NCO phase, frequency and threshold it reads are the ones the head is about to read, and it writes none of them.  It passes
+// the head's two guards, correlates the head's window with the head's device function (prs_correlate_peaks) and runs the reference's
+// display state machine on the result.
+template <int RF>
+__global__ __launch_bounds__(256) void k_cir_corr(EngineDev e, DevTables t, CirDev cd)
+{
+  __shared__ float2 lds[FFT_LDS_FLOAT2];
+  __shared__ __attribute__((aligned(16))) float peak[TU];
+  __shared__ float red[8];
+  __shared__ unsigned long long mask[12];
+  __shared__ int16_t s_idx[CIR_INDEX_ROOM];
+  __shared__ int s_n;
+  const int s = cd.list[blockIdx.x], tid = threadIdx.x;
+  if (!cd.cfg[s].correlation) return;
+  const StreamCtl &c = e.ctl[s];
+  if (tid == 0) s_n = __hip_atomic_load(&c.state, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);   // one thread looks, everyone follows
+  __syncthreads();
+  if (s_n != ST_EVAL_SYNC) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  if (e.wr[s] - c.rd < (unsigned long long)FRAME_NEED) return;
+  const unsigned long long rd = c.rd;
+  const int phase0 = c.nco_phase;
+  const int f = (int)roundf(c.f_bb);
+  const float thr = c.sync_thr;
+  float2 v[8];
+  Nco nco;
+  nco.init(phase0, f, tid);
+  const RingView<RF> rv(stream_ring<RF>(e, s), e.ring_len, rd);
+#pragma unroll
+  for (int u = 0; u < 8; u++) { v[u] = nco.mix(rv.at(tid + 256 * u)); nco.step(); }
+  const float sum = prs_correlate_peaks(v, t, lds, peak, red, tid);
+  float *mean = cd.mean + (size_t)s * TU;
+  float m[8];
+#pragma unroll
+  for (int u = 0; u < 8; u++) { m[u] = mean[tid + 256 * u] + peak[tid + 256 * u]; mean[tid + 256 * u] = m[u]; }   // :121, on every call
+  if (sum == 0.f) return;                                  // :128
+  // which positions the walk of :143-169 accepts if it comes to them: a wave's 64 positions per ballot, twelve words for the 750
+  constexpr int i0 = TG - 250, i1 = TG + 500, gap = 10;
+#pragma unroll
+  for (int q = 0; q < 3; q++) {
+    const int i = i0 + 256 * q + tid;
+    bool ok = false;
+    if (i < i1) {
+      const float p = peak[i];
+      ok = p / sum > thr;
+      for (int j = 1; j < gap && i + j < i1; ++j) ok = ok && !(peak[i + j] > p);
+    }
+    const unsigned long long b = __ballot(ok);
+    if ((tid & 63) == 0) mask[4 * q + (tid >> 6)] = b;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int n = 0;
+    for (int p = 0; p < i1 - i0; ++p)
+      if (((mask[p >> 6] >> (p & 63)) & 1ull) && n < CIR_INDEX_ROOM) { s_idx[n++] = (int16_t)(i0 + p); p += gap; }   // :159, :166
+    s_n = n;
+  }
+  __syncthreads();
+  const int n_idx = s_n;
+  if (n_idx == 0) return;                                  // :171: maxL is still -1000
+  CirState q = cd.st[s];
+  __syncthreads();                                         // every thread has read the counter
+  if (q.corr_counter + 1 <= 5) {                           // :179-181
+    if (tid == 0) cd.st[s].corr_counter = q.corr_counter + 1;
+    return;
+  }
+  uint8_t *slot = cd.ring + ((size_t)s * CIR_RING + (size_t)(q.shows % CIR_RING)) * CIR_SLOT_BYTES;
+  float *val = reinterpret_cast<float *>(slot + 32);
+#pragma unroll
+  for (int u = 0; u < 8; u++) {                            // :188; nothing clears the mean behind the show
+    const float a = m[u] / 6.0f;
+    mean[tid + 256 * u] = a; val[tid + 256 * u] = a;
+  }
+  int16_t *idx = reinterpret_cast<int16_t *>(slot + 32 + CIR_CORR_LAGS * 4);
+  if (tid < CIR_INDEX_ROOM) idx[tid] = tid < n_idx ? s_idx[tid] : (int16_t)0;
+  if (tid == 0) {
+    dabx_cir_record r;
+    r.frame = c.frames; r.first_sample = (int64_t)rd; r.threshold = sum * thr; r.rows_untrusted = 0;   // :192
+    r.n_values = CIR_CORR_LAGS; r.n_indices = (int16_t)n_idx; r.kind = DABX_CIR_KIND_CORRELATION;
+    r.reserved[0] = r.reserved[1] = r.reserved[2] = 0;
+    *reinterpret_cast<dabx_cir_record *>(slot) = r;
+    q.corr_counter = 0;                                    // :193
+    q.shows++; q.shows_kind[1]++;
+    cd.st[s] = q;
+  }
+}
+
+// test entry (dabx_cir_rows_device): cir_row_block on crafted rows, one block per row
+__global__ __launch_bounds__(256) void k_cir_rows_test(const float2 *in, float *y, DevTables t)
+{
+  __shared__ float2 lds[FFT_LDS_FLOAT2];
+  __shared__ float red[8];
+  const int tid = threadIdx.x;
+  const float2 *src = in + (size_t)blockIdx.x * TU;
+  float2 v[8];
+#pragma unroll
+  for (int u = 0; u < 8; u++) v[u] = src[tid + 256 * u];
+  const float r = cir_row_block(v, t, lds, red, tid);
+  if (tid == 0) y[blockIdx.x] = r;
+}
+
+int launch_cir_rows_test(const float2 *in, int n_rows, float *y, hipStream_t st)
+{
+  const DevTables *t;
+  if (int rc = get_tables(&t)) return rc;
+  hipLaunchKernelGGL(k_cir_rows_test, dim3(n_rows), dim3(256), 0, st, in, y, *t);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+
+static int launch_cir(const EngineDev &e, const DevTables &t, const CirDev *cd, int cap, hipStream_t st)
+{
+  if (!cd || cd->n <= 0 || cap <= 0) return 0;
+  DABX_LAUNCH_RING(e, k_cir, dim3((cap + CIR_ROWS_PER_BLOCK - 1) / CIR_ROWS_PER_BLOCK, cd->n), dim3(256), 0, st, e, t, *cd, cap);
+  hipLaunchKernelGGL(k_cir_finish, dim3(cd->n), dim3(64), 0, st, e, *cd, cap);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+static int launch_cir_corr(const EngineDev &e, const DevTables &t, const CirDev *cd, hipStream_t st)
+{
+  if (!cd || cd->n <= 0 || !cd->n_corr) return 0;
+  DABX_LAUNCH_RING(e, k_cir_corr, dim3(cd->n), dim3(256), 0, st, e, t, *cd);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+
 // "k_demap_fic": the first k_demap_frame launch of a frame (symbols 1..3) when the FIC is decoded on its own stream
 const char *const kStepKernelNames[N_STEP_KERNELS] = {"k_acquire", "k_frame_head", "k_symbols", "k_demap_frame", "k_fic_frame", "k_frame_tail",
                                                       "k_msc_prep", "k_msc_vitT", "k_msc_frame", "k_dabplus", "k_demap_fic", "k_packet", "k_pad", "k_mot",
@@ -1897,7 +2118,7 @@ const char *const kStepKernelNames[N_STEP_KERNELS] = {"k_acquire", "k_frame_head
 // chain) and the frame tail follow on a, while the 72 MSC symbols are demapped on stream d: nothing on the chain of the NEXT
 // frame needs them, so a goes on to frame n + 1 while d is busy; the next frame's first demapper launch (and the MSC batch)
 // wait for d.  Serial schedule (cfg.schedule = 1, ss.d null): every kernel on a in program order.
-int launch_front_step(const EngineDev &e_in, EngineStreams &ss, Marker &mk, bool async_acquire, bool all_locked, const ScopeDev *scope)
+int launch_front_step(const EngineDev &e_in, EngineStreams &ss, Marker &mk, bool async_acquire, bool all_locked, const ScopeDev *scope, const CirDev *cir, int cir_cap)
 {
   const DevTables *t;
   int rc = get_tables(&t);
@@ -1941,6 +2162,9 @@ int launch_front_step(const EngineDev &e_in, EngineStreams &ss, Marker &mk, bool
     mk.begin(0, st); DABX_LAUNCH_RING(e, k_acquire, dim3(e.n_streams), dim3(256), 0, st, e, *t, 1); mk.end(0, st);
     if (ss.q && ss.acq_a_done) { DABX_HIP(hipEventRecord(ss.acq_a_done, st)); ss.acq_a_pending = true; }
   }
+  // the CIR rows that have become due (dabx_set_cir_mode): only while a stream has the mode on and the host counts a row due
+  if ((rc = launch_cir(e, *t, cir, cir_cap, st))) return rc;
+  if ((rc = launch_cir_corr(e, *t, cir, st))) return rc;     // the correlation plot, directly in front of the head whose correlation it repeats
   mk.begin(1, st); DABX_LAUNCH_RING(e, k_frame_head, dim3(e.n_streams), dim3(256), 0, st, e, *t); mk.end(1, st);
   mk.begin(2, st); DABX_LAUNCH_RING(e, k_symbols_persistent, dim3(sym_blocks_per_stream(e.n_streams), e.n_streams), dim3(256), 0, st, e, *t); mk.end(2, st);
   // kernel instance by (ESoftBitType, symbol conversion of the canonical / SIMD builds)

@@ -492,7 +492,7 @@ DELIVER_TII = 256
 TII_MAX_RESULTS = 32
 CHUNK_EXT_MAGIC = 0x45584244                     # "DBXE"
 CHUNK_HEADER_EXT = np.dtype([("magic", "<u4"), ("bytes", "<u4"), ("off_tii", "<u8"), ("off_mp2_audio", "<u8"), ("off_aac", "<u8"), ("off_scope", "<u8"),
-                             ("reserved", "<u8", 3)])
+                             ("off_cir", "<u8"), ("reserved", "<u8", 2)])
 CHUNK_TII = np.dtype([("first_event", "<i8"), ("n_events", "<i4"), ("events_lost", "<i4"), ("ev_off", "<u8"), ("events_total", "<i8")])
 TII_EVENT = np.dtype([("frame", "<i8"), ("n_results", "<i4"), ("n_found", "<i4"), ("frames_in_sum", "<i4"), ("epoch", "<i4"),
                       ("threshold_db", "<i4"), ("reserved", "<i4")])
@@ -604,6 +604,33 @@ SCOPE_IQ_TYPES = {"PHASE_CORR_CARR_NORMED": 0, "PHASE_CORR_MEAN_NORMED": 1, "RAW
 SCOPE_CARRIER_TYPES = {"SB_WEIGHT": 0, "EVM_PER": 1, "EVM_DB": 2, "STD_DEV": 3, "PHASE_ERROR": 4, "PRS_PHASE": 5, "PRS_PHASE_UNWRAP": 6,
                        "FOUR_QUAD_PHASE": 7, "REL_POWER": 8, "SNR": 9, "NULL_OVR_POW": 13}
 assert SCOPE_RECORD.itemsize == 32 and SCOPE_STATS.itemsize == 64
+
+
+# Channel impulse response and correlation plot (include/dabx.h "Channel impulse response and correlation plot"): dabx_cir_record, one per
+# completed CIR window (kind 0: 385 values) or correlation show (kind 1: 2048 values, up to 69 indices), with the values [2048] float32 and the
+# indices [72] int16 behind it; dabx_cir_stats
+CIR_KIND_CIR, CIR_KIND_CORRELATION = 0, 1
+CIR_ROWS = 385
+CIR_WINDOW = 97 * 2048
+CIR_PERIOD = 6 * 196608
+CIR_CORR_LAGS = 2048
+CIR_MAX_INDICES = 69
+CIR_INDEX_ROOM = 72
+CIR_RECORD = np.dtype([("frame", "<i8"), ("first_sample", "<i8"), ("threshold", "<f4"), ("rows_untrusted", "<i4"), ("n_values", "<i2"),
+                       ("n_indices", "<i2"), ("kind", "u1"), ("reserved", "u1", 3)])
+CIR_STATS = np.dtype([("shows", "<i8", 2), ("lost", "<i8"), ("rows_untrusted", "<i8"), ("launches", "<i8"), ("reserved", "<i8", 3)])
+CIR_SLOT_BYTES = 32 + CIR_CORR_LAGS * 4 + CIR_INDEX_ROOM * 2
+# the slab's CIR section (DELIVER_CIR = 32768, opt-in like DELIVER_SCOPE; 1024, 4096 and 16384 stay refused; announced by the header's
+# extension): one CHUNK_CIR per stream, then CIR_CHUNK_RECORDS record slots for every stream that had the mode on when the delivery was opened
+DELIVER_CIR = 32768
+CIR_CHUNK_RECORDS = 4
+CHUNK_CIR = np.dtype([("first_record", "<i8"), ("n_records", "<i4"), ("records_lost", "<i4"), ("rec_off", "<u8"), ("records_total", "<i8")])
+assert CIR_RECORD.itemsize == 32 and CIR_STATS.itemsize == 64 and CHUNK_CIR.itemsize == 32
+
+
+class CirConfig(C.Structure):
+    """dabx_cir_config."""
+    _fields_ = [("enable", C.c_int32), ("cir", C.c_int32), ("correlation", C.c_int32), ("reserved", C.c_int32 * 5)]
 
 
 class ScopeConfig(C.Structure):
@@ -734,6 +761,7 @@ class Chunk:
         self.mp2_audio_table = None             # the MP2 audio section: [S, M] CHUNK_MP2_AUDIO, or None when the slab has none
         self.aac_table = None                   # the AAC section: [S, M] CHUNK_AAC, or None when the slab has none
         self.scope_table = None                 # the scope section: [S] CHUNK_SCOPE, or None when the slab has none
+        self.cir_table = None                   # the CIR section: [S] CHUNK_CIR, or None when the slab has none
         if int(h["what"]) & ~255:
             self.header_ext = self.raw[128:192].view(CHUNK_HEADER_EXT)[0]
             if int(self.header_ext["magic"]) != CHUNK_EXT_MAGIC or int(self.header_ext["bytes"]) < 64:
@@ -750,6 +778,9 @@ class Chunk:
             if int(self.header_ext["off_scope"]):
                 o = int(self.header_ext["off_scope"])
                 self.scope_table = self.raw[o:o + S * 32].view(CHUNK_SCOPE)
+            if int(self.header_ext["off_cir"]):
+                o = int(self.header_ext["off_cir"])
+                self.cir_table = self.raw[o:o + S * 32].view(CHUNK_CIR)
         self.eti_table = None                  # the ETI section: [S] CHUNK_ETI, or None when the slab has none
         if int(h["off_eti"]):
             self.eti_table = self.raw[int(h["off_eti"]):int(h["off_eti"]) + S * 64].view(CHUNK_ETI)
@@ -778,6 +809,20 @@ class Chunk:
             o = int(r["rec_off"]) + k * SCOPE_SLOT_BYTES
             out.append((self.raw[o:o + 32].view(SCOPE_RECORD)[0], self.raw[o + 32:o + 32 + SCOPE_CARRIERS * 8].view(np.complex64),
                         self.raw[o + 32 + SCOPE_CARRIERS * 8:o + SCOPE_SLOT_BYTES].view(np.float32)))
+        return out
+
+    def cir(self, stream):
+        """CIR / correlation records of `stream` in this chunk, oldest first: a list of (CIR_RECORD record, values[:n_values] float32,
+        indices[:n_indices] int16), views.  Empty when the slab has no CIR section or the stream had the mode off when the delivery was opened."""
+        if self.cir_table is None:
+            return []
+        r = self.cir_table[stream]
+        out = []
+        for k in range(int(r["n_records"])):
+            o = int(r["rec_off"]) + k * CIR_SLOT_BYTES
+            rec = self.raw[o:o + 32].view(CIR_RECORD)[0]
+            out.append((rec, self.raw[o + 32:o + 32 + 4 * int(rec["n_values"])].view(np.float32),
+                        self.raw[o + 32 + CIR_CORR_LAGS * 4:o + 32 + CIR_CORR_LAGS * 4 + 2 * int(rec["n_indices"])].view(np.int16)))
         return out
 
     def eti(self, stream):
@@ -1066,6 +1111,34 @@ class Engine:
         L.dabx_read_scope.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         n = check(L.dabx_read_scope(self._h, stream, max_records, _p(recs), _p(iq), _p(carr), C.byref(lost)))
         return [(recs[k], iq[k], carr[k]) for k in range(n)], lost.value
+
+    def set_cir_mode(self, stream, cir=True, correlation=False, enable=True):
+        """The stream's channel impulse response plot and / or correlation plot on the device (dabx_set_cir_mode; stream = -1: all streams):
+        a CIR record per window of 97 x 2048 samples every six frames' worth of samples, a correlation record whenever the reference would
+        show its plot; read with read_cir.  enable=False switches both off."""
+        cfg = CirConfig(enable=int(bool(enable)), cir=int(bool(cir)), correlation=int(bool(correlation)))
+        L = load()
+        L.dabx_set_cir_mode.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        check(L.dabx_set_cir_mode(self._h, stream, C.byref(cfg) if enable else None))
+
+    def read_cir(self, stream, max_records=4):
+        """The records completed since the previous call: ([(CIR_RECORD record, values[:n_values] float32, indices[:n_indices] int16)], records lost)."""
+        recs = np.zeros(max_records, CIR_RECORD)
+        val = np.zeros((max_records, CIR_CORR_LAGS), np.float32)
+        idx = np.zeros((max_records, CIR_INDEX_ROOM), np.int16)
+        lost = C.c_int32(0)
+        L = load()
+        L.dabx_read_cir.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        n = check(L.dabx_read_cir(self._h, stream, max_records, _p(recs), _p(val), _p(idx), C.byref(lost)))
+        return [(recs[k], val[k, :int(recs[k]["n_values"])], idx[k, :int(recs[k]["n_indices"])]) for k in range(n)], lost.value
+
+    def cir_stats(self, stream):
+        st = np.zeros(1, CIR_STATS)
+        L = load()
+        L.dabx_get_cir_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        check(L.dabx_get_cir_stats(self._h, stream, _p(st)))
+        return {"shows": [int(v) for v in st["shows"][0]], "lost": int(st["lost"][0]), "rows_untrusted": int(st["rows_untrusted"][0]),
+                "launches": int(st["launches"][0])}
 
     def scope_stats(self, stream):
         st = np.zeros(1, SCOPE_STATS)

@@ -981,7 +981,13 @@ enum { DABX_DELIVER_FIB = 1, DABX_DELIVER_MSC = 2, DABX_DELIVER_SF = 4,
           exactly what they are without it.  With the bit the header is followed by a dabx_chunk_header_ext.  The value is 8192, not 1024
           and not 4096: both masks have always been refused with DABX_E_ARG and callers rely on that
           (tests/test_gpu_aac_stream_delivery.py), so both stay refused */
-       DABX_DELIVER_SCOPE = 8192 };
+       DABX_DELIVER_SCOPE = 8192,
+       /* the CIR and correlation-plot records of every stream that has the mode on (dabx_set_cir_mode; the CIR section, dabx_chunk_cir
+          below).  Opt-in exactly like the five bits above: what == 0 does NOT include it, the bit alone or with only DABX_DELIVER_ETI, _TII,
+          _MP2_AUDIO, _AAC and _SCOPE beside it is DABX_E_ARG, and without the bit a slab, dabx_delivery_slab_bytes and the kernels launched
+          are exactly what they are without it.  With the bit the header is followed by a dabx_chunk_header_ext.  The value is 32768, not
+          1024, 4096 or 16384: those masks have always been refused with DABX_E_ARG and callers rely on that, so they stay refused */
+       DABX_DELIVER_CIR = 32768 };
 typedef struct {
   int32_t host_slabs;       /* page-locked host slabs, >= 2 (0 = default 4) */
   int32_t what;             /* DABX_DELIVER_* mask, 0 = everything */
@@ -1011,7 +1017,8 @@ typedef struct {
   uint64_t off_mp2_audio;   /* the MP2 audio section: dabx_chunk_mp2_audio[n_streams * max_subch]; 0 = the slab has none */
   uint64_t off_aac;         /* the AAC section: dabx_chunk_aac[n_streams * max_subch]; 0 = the slab has none */
   uint64_t off_scope;       /* the scope section: dabx_chunk_scope[n_streams]; 0 = the slab has none */
-  uint64_t reserved[3];
+  uint64_t off_cir;         /* the CIR section: dabx_chunk_cir[n_streams]; 0 = the slab has none (the first of three words that were reserved) */
+  uint64_t reserved[2];
 } dabx_chunk_header_ext;    /* 64 bytes */
 typedef struct {
   int64_t first_frame;      /* index, since the stream was opened, of the first frame in the chunk */
@@ -1141,6 +1148,24 @@ typedef struct {
   uint64_t rec_off;         /* 0 = the stream has no room in this delivery */
   int64_t  records_total;   /* records the stream has written so far: first_record + n_records */
 } dabx_chunk_scope;         /* 32 bytes */
+/* The CIR section (DABX_DELIVER_CIR; "Channel impulse response and correlation plot" below): one dabx_chunk_cir per stream from
+ * dabx_chunk_header_ext.off_cir, in the slab's head part behind the scope section (or where that would be), followed by room for
+ * DABX_CIR_CHUNK_RECORDS record slots for each stream that has the mode on WHEN THE DELIVERY IS OPENED (a stream switched on later has no
+ * room and delivers none: rec_off = 0).  A chunk of DABX_CHUNK_FRAMES = 7 frames completes at most 2 records of each kind: a CIR record
+ * takes six frames' worth of committed samples (1 179 648, fed a frame per step: windows complete six steps apart, so steps 1 and 7 of a
+ * chunk at the most), a correlation show takes six counted calls of one per step (again steps 1 and 7 at the most) -- 4 slots.  (A host
+ * that commits many frames before it processes them can complete a CIR window in every step; what does not fit is counted in
+ * records_lost, the newest are kept.)  A record slot is a dabx_cir_record, the values [2048] f32 and the indices [72] int16,
+ * DABX_CIR_SLOT_BYTES in all, byte for byte what dabx_read_cir returns; stream s's n_records slots lie one behind the other from rec_off,
+ * oldest first, both kinds in the order they were completed.  Every record a stream wrote since the previous chunk is in the chunk or
+ * counted in records_lost.  Gathered on the front-end stream when the chunk closes (k_deliver_cir), with a cursor of its own. */
+#define DABX_CIR_CHUNK_RECORDS 4
+typedef struct {
+  int64_t  first_record;    /* number, since the stream's mode was first switched on, of the first record in the chunk */
+  int32_t  n_records, records_lost;
+  uint64_t rec_off;         /* 0 = the stream has no room in this delivery */
+  int64_t  records_total;   /* records the stream has written so far: first_record + n_records */
+} dabx_chunk_cir;           /* 32 bytes */
 typedef struct {
   uint64_t seq;
   const void *data;         /* the host slab: valid until dabx_delivery_release(seq) */
@@ -1423,6 +1448,93 @@ int  dabx_get_scope_stats(dabx_engine *e, int stream, dabx_scope_stats *out);
  * decoded frame -- the very function k_scope runs.  counters = { mShowCntIqScope, mShowCntStatistics, mNextShownOfdmSymbIdx }, in and out
  * (a fresh decoder: 0, 0, 1).  Returns the symbol shown in that frame, 0 = none. */
 int  dabx_scope_cadence_frame(int32_t counters[3]);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Channel impulse response and correlation plot: the two displays that tell the transmitters of an SFN apart (csrc/cir_core.h, k_cir and
+ * k_cir_corr; docs/history/cir.md).  One opt-in mode, two kinds of record:
+ * kind 0, the CIR of CirViewer::show_cir (base/spectrum_viewer/cir_viewer.cpp:54-107, scalar build) over the window SampleReader captures
+ * (base/main/sample_reader.cpp:179-196, :250-265; CIR_BUFF_SIZE = 97 x 2048).  For a stream switched on at read position `base`, window n
+ * covers the absolute sample positions [base + n * 1 179 648, base + n * 1 179 648 + 198 656) -- six frames' worth of consumed samples
+ * apart, whether the stream is in lock or searching, as the reference counts them.  The samples are those the frame head reads in front
+ * of its NCO: behind the DC / IQ correction where that is on, converted from a native ring as every kernel converts them.  Row j (0..384)
+ * is the 2048 samples from the window's first + 512 j: forward transform, product with the conjugate reference table (the PRS correlator's),
+ * unnormalised backward transform, y[j] = sqrtf(max_i(re^2 + im^2)) / 26000 with max starting at 0 and a strict `>` (:86-93).  Kept: a row
+ * with a NaN anywhere gives 0 (a NaN wins no comparison), a row whose largest square overflows gives inf.  The rows are computed as their
+ * samples are committed, at the head of every front-end step -- about 64 per stream and step instead of 385 every sixth --, so a row's
+ * samples are normally unread and intact; row 384 completes the record.  A step computes rows of one window only.
+ * The trust rule: a row is only read if no push the ABI has accepted may be writing one of its ring slots -- its first sample has not
+ * been read by the receiver yet (>= rd), or nothing issued so far reaches round the ring to it (>= write horizon - ring length; a
+ * zero-copy commit without dabx_announce_write puts the horizon at ~0).  Looked at before and after the row's loads.  Otherwise
+ * y[j] = -1 and the row counts in rows_untrusted.
+ * Deviation: switching the CIR off and on again starts a new window at the stream's read position then; the reference would splice the
+ * half-filled buffer.
+ * kind 1, the correlation plot of PhaseReference::correlate_with_phase_ref_and_find_max_peak (base/ofdm/phasereference.cpp:110-195): the
+ * mean of |corr| over the 2048 lags of the sync window, the accepted peak indices mIndices of the call that shows (:143-169) and the
+ * threshold line sum * iThreshold (:192).  k_cir_corr stands directly in front of the frame head, evaluates its two guards (in lock, a
+ * frame's samples committed) and computes the same |corr| from the same samples, NCO phase and rounded frequency with the same device
+ * function.  The reference's state machine, quirks included: mean += |corr| on EVERY call, also those that return -1 (:121); sum == 0
+ * returns (:128); a call without an accepted peak returns without counting (:171); otherwise ++counter, and when counter > 5 the mean is
+ * divided by 6, shown with sum * threshold and ALL accepted indices in walk order, and counter = 0 (:179-193) -- the mean is NOT cleared
+ * (no line does), so every later show carries a sixth of the one before.  The threshold factor is the stream's: 3 after a search, doubled
+ * in lock.  At most 69 indices: the walk visits 750 positions and an accepted peak moves it on by 11 (:166 and the loop's own step).
+ * While a stream has the correlation on, the search for streams out of lock runs in step, as it does with cfg.dc_iq_correction: a search
+ * running beside the step could hand a stream to the frame head between k_cir_corr and the head, and the plot would miss a call the
+ * head made.  Deviation: the correlations the SEARCH makes of candidates that fail are not accumulated (the search kernel is not touched);
+ * a candidate that correlates is counted once, when the frame head repeats it. */
+typedef struct {
+  int32_t enable;
+  int32_t cir;               /* 0/1: kind 0 */
+  int32_t correlation;       /* 0/1: kind 1 */
+  int32_t reserved[5];       /* 0 */
+} dabx_cir_config;           /* 32 bytes */
+typedef struct {
+  int64_t frame;             /* frames the stream had decoded when the record was completed */
+  int64_t first_sample;      /* kind 0: the window's first absolute sample position; kind 1: the sync window's (the read position of the call that showed) */
+  float   threshold;         /* kind 1: sum * iThreshold of the call that showed (:192); kind 0: 0 */
+  int32_t rows_untrusted;    /* kind 0: rows given up for the trust rule (their value is -1) */
+  int16_t n_values;          /* 385 (kind 0) or 2048 (kind 1) */
+  int16_t n_indices;         /* kind 1: accepted peaks, 0..69 */
+  uint8_t kind;              /* DABX_CIR_KIND_* */
+  uint8_t reserved[3];
+} dabx_cir_record;           /* 32 bytes */
+#define DABX_CIR_KIND_CIR 0
+#define DABX_CIR_KIND_CORRELATION 1
+#define DABX_CIR_ROWS 385                /* (97 * 2048 - 2048) / 512 + 1 */
+#define DABX_CIR_WINDOW 198656           /* 97 * 2048 */
+#define DABX_CIR_PERIOD 1179648          /* 6 * 196 608 */
+#define DABX_CIR_CORR_LAGS 2048
+#define DABX_CIR_MAX_INDICES 69          /* ceil(750 / 11) */
+#define DABX_CIR_INDEX_ROOM 72           /* the index list's int16 slots in a record slot */
+#define DABX_CIR_SLOT_BYTES (32 + DABX_CIR_CORR_LAGS * 4 + DABX_CIR_INDEX_ROOM * 2)   /* record, values [2048] f32, indices [72] int16 */
+typedef struct {
+  int64_t shows[2];          /* records completed, per kind */
+  int64_t lost;              /* records dabx_read_cir found gone from the ring of 4 */
+  int64_t rows_untrusted;    /* CIR rows given up for the trust rule, all windows */
+  int64_t launches;          /* steps of the engine that launched a kernel of the stage */
+  int64_t reserved[3];
+} dabx_cir_stats;            /* 64 bytes */
+/* stream = -1: all streams.  cfg = NULL or enable = 0: off.  The first enable allocates the stage; an engine that never enables the mode
+ * allocates and launches nothing for it, and with no stream enabled the launch sequence is what it is without the mode.  Switching a
+ * stream's CIR on (from off) puts `base` at its read position; switching its correlation on (from off) clears its mean and counter.
+ * Drains the engine. */
+int  dabx_set_cir_mode(dabx_engine *e, int stream, const dabx_cir_config *cfg);
+/* The records `stream` completed since the previous call, oldest first, both kinds in the order they were completed, at most max_records:
+ * recs [max], values [max][2048] f32 (the first n_values of a row count, the rest is 0), indices [max][72] int16 (the first n_indices;
+ * either array optional).  The device keeps the last 4 per stream; *lost (optional) counts those that had left.  Drains the engine; a
+ * cursor of its own.  Returns the number of records. */
+int  dabx_read_cir(dabx_engine *e, int stream, int max_records, dabx_cir_record *recs, float *values, int16_t *indices, int32_t *lost);
+/* Any engine; all zeros without the mode (launches is the engine's, the same for every stream). */
+int  dabx_get_cir_stats(dabx_engine *e, int stream, dabx_cir_stats *out);
+/* cir_viewer.cpp:66-95 on crafted rows, no engine: the row function of k_cir on n_rows windows of 2048 cf32 samples each (iq [n][2048]
+ * interleaved re, im), y [n]. */
+int  dabx_cir_rows_device(const float *iq, int n_rows, float *y);
+/* The window / row bookkeeping k_cir and k_cir_finish run, on the host, no engine and no device.  walk = { base, window, rows_done }, in
+ * and out; wr = one past the last committed sample; cap = the most rows a step takes.  Returns the number of rows due (rows_done ..
+ * rows_done + n - 1 of `window`, each with all 2048 samples below wr), *first (optional) = the first due row's first sample, *completed
+ * (optional) = 1 if row 384 is among them; walk is moved on past them. */
+int  dabx_cir_rows_due(int64_t walk[3], uint64_t wr, int32_t cap, int64_t *first, int32_t *completed);
+/* The trust rule k_cir runs, on the host: 1 = a row whose first sample is `first` may be read. */
+int  dabx_cir_row_trusted(uint64_t first, uint64_t rd, uint64_t horizon, uint64_t ring_len);
 
 /* ------------------------------------------------------------------------------------------------------------
  * MP2 audio:the MP2 decoder of a DAB (MPEG-1/2 Audio Layer II) audio sub-channel on the device -- Mp2Processor's frame assembly and
