@@ -5,6 +5,7 @@
 #include "tii_core.h"
 #include "mp2_core.h"
 #include "aac_core.h"
+#include "spectrum_core.h"
 #include <cstring>
 
 namespace dabx { const char *last_error(); }
@@ -249,6 +250,31 @@ int dabx_cir_rows_device(const float *iq, int n_rows, float *y)
   if ((rc = launch_cir_rows_test(din.as<float2>(), n_rows, dout.as<float>(), 0))) return rc;
   DABX_HIP(hipDeviceSynchronize());
   DABX_HIP(hipMemcpy(y, dout.p, sizeof(float) * (size_t)n_rows, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// spectrum_viewer.cpp:169-218 on crafted windows: the row function of k_spectrum (spectrum_core.h, spectrum_row_block), one block walks the
+// n windows through one display buffer
+int dabx_spectrum_rows_device(const float *iq, int n, float *state, float *lin, float *db, float *ext)
+{
+  if (!iq || !state || !lin || !db || n <= 0 || n > 4096) { set_error("dabx_spectrum_rows_device: bad argument"); return DABX_E_ARG; }
+  int rc = need_device();
+  if (rc) return rc;
+  DevBuf din, dst, dlin, ddb, dext, dwin;
+  const size_t nb = sizeof(float2) * SPEC_SIZE * (size_t)n, no = sizeof(float) * SPEC_DISPLAY * (size_t)n, ns = sizeof(float) * (SPEC_DISPLAY + 4);
+  if ((rc = din.alloc(nb)) || (rc = dst.alloc(ns)) || (rc = dlin.alloc(no)) || (rc = ddb.alloc(no)) || (rc = dext.alloc(sizeof(float) * 4 * (size_t)n)) ||
+      (rc = dwin.alloc(sizeof(float) * SPEC_SIZE))) return rc;
+  std::vector<float> w(SPEC_SIZE);
+  spectrum_make_window(w.data());
+  DABX_HIP(hipMemcpy(dwin.p, w.data(), sizeof(float) * SPEC_SIZE, hipMemcpyHostToDevice));
+  DABX_HIP(hipMemcpy(din.p, iq, nb, hipMemcpyHostToDevice));
+  DABX_HIP(hipMemcpy(dst.p, state, ns, hipMemcpyHostToDevice));
+  if ((rc = launch_spectrum_rows_test(din.as<float2>(), n, dst.as<float>(), dlin.as<float>(), ddb.as<float>(), dext.as<float>(), dwin.as<float>(), 0))) return rc;
+  DABX_HIP(hipDeviceSynchronize());
+  DABX_HIP(hipMemcpy(state, dst.p, ns, hipMemcpyDeviceToHost));
+  DABX_HIP(hipMemcpy(lin, dlin.p, no, hipMemcpyDeviceToHost));
+  DABX_HIP(hipMemcpy(db, ddb.p, no, hipMemcpyDeviceToHost));
+  if (ext) DABX_HIP(hipMemcpy(ext, dext.p, sizeof(float) * 4 * (size_t)n, hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -83,6 +83,7 @@ int launch_crc16_check(const uint8_t *msgs, int stride, int len, int batch, uint
 // ofdm.hip
 int launch_fft2048(const float2 *in, int batch, int inverse, float2 *out, hipStream_t st);
 int launch_cir_rows_test(const float2 *in, int n_rows, float *y, hipStream_t st);   // pipeline.hip: dabx_cir_rows_device
+int launch_spectrum_rows_test(const float2 *in, int n, float *state, float *lin, float *db, float *ext, const float *window, hipStream_t st);   // pipeline.hip: dabx_spectrum_rows_device
 int launch_prs_correlate(const float2 *v, int batch, float threshold, int strongest, int32_t *start, hipStream_t st);
 int launch_coarse_cfo(const float2 *fft, int batch, int32_t *hz, hipStream_t st);
 int launch_demap_reset(DemapDev &d, hipStream_t st);

@@ -16,6 +16,7 @@
 #include "tii_core.h"
 #include "scope_core.h"
 #include "cir_core.h"
+#include "spectrum_core.h"
 #include "fig00.h"
 
 namespace dabx {
@@ -438,6 +439,41 @@ __global__ __launch_bounds__(256) void k_deliver_cir(CirDeliverDev sd)
 int launch_deliver_cir(int n_streams, const CirDeliverDev &sd, hipStream_t st)
 {
   hipLaunchKernelGGL(k_deliver_cir, dim3(n_streams), dim3(256), 0, st, sd);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+
+// The spectrum section (include/dabx.h, dabx_chunk_spectrum; pipeline.h, SpecDeliverDev).  grid = n_streams, 256 threads, front-end stream, behind
+// k_deliver_front -- so behind the k_spectrum of the chunk's last frame, which runs on that stream: the records the stream has completed since
+// the previous chunk, the newest DABX_SPECTRUM_CHUNK_RECORDS of them, out of the stage's ring.  A stream without room in the slab (rec_off 0)
+// delivers none.
+__global__ __launch_bounds__(256) void k_deliver_spectrum(SpecDeliverDev sd)
+{
+  const int s = blockIdx.x, tid = threadIdx.x;
+  constexpr int CAP = DABX_SPECTRUM_CHUNK_RECORDS < SPEC_RING ? DABX_SPECTRUM_CHUNK_RECORDS : SPEC_RING, SLOT_Q = SPEC_SLOT_BYTES / 16;
+  static_assert(SPEC_SLOT_BYTES % 16 == 0, "a record slot is copied in 16-byte words");
+  const unsigned long long rec_off = sd.rec_off[s];
+  const long long total = sd.ring ? sd.shows[(size_t)s * sd.st_stride] : 0, have = rec_off ? total - sd.done[s] : 0;
+  int n = (int)(have < CAP ? have : CAP);
+  if (n < 0) n = 0;
+  const long long first = total - n;
+  if (tid == 0) {
+    dabx_chunk_spectrum r;
+    r.first_record = first; r.n_records = n; r.records_lost = (int)(have > n ? have - n : 0); r.rec_off = rec_off; r.records_total = total;
+    reinterpret_cast<dabx_chunk_spectrum *>(sd.slab + sd.off_spectrum)[s] = r;
+  }
+  uint4 *o = reinterpret_cast<uint4 *>(sd.slab + rec_off);
+  for (int i = tid; i < n * SLOT_Q; i += 256) {
+    const int k = i / SLOT_Q, wd = i - k * SLOT_Q;
+    o[i] = reinterpret_cast<const uint4 *>(sd.ring + ((size_t)s * SPEC_RING + (size_t)((first + k) % SPEC_RING)) * SPEC_SLOT_BYTES)[wd];
+  }
+  __syncthreads();
+  if (tid == 0) sd.done[s] = total;
+}
+
+int launch_deliver_spectrum(int n_streams, const SpecDeliverDev &sd, hipStream_t st)
+{
+  hipLaunchKernelGGL(k_deliver_spectrum, dim3(n_streams), dim3(256), 0, st, sd);
   DABX_HIP(hipGetLastError());
   return 0;
 }

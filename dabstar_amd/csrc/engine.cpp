@@ -367,6 +367,7 @@ void dabx_destroy(dabx_engine *e)
   tii_stage_free(e);
   scope_stage_free(e);
   cir_stage_free(e);
+  spectrum_stage_free(e);
   for (dabx_fibdec *f : e->fibdec) dabx_fibdec_destroy(f);
   if (e->ingest) { (void)hipStreamSynchronize(e->ingest); (void)hipStreamDestroy(e->ingest); }
   if (e->ingest2) { (void)hipStreamSynchronize(e->ingest2); (void)hipStreamDestroy(e->ingest2); }
@@ -808,7 +809,8 @@ int dabx_process(dabx_engine *e, int max_frames, int sync)
   const bool some_locked = !e->locked_host || 2 * __atomic_load_n(e->locked_host, __ATOMIC_RELAXED) >= e->dev.n_streams;
   // (And while a stream has the correlation plot on -- dabx_set_cir_mode -- it stays in step as well: a search beside the step could hand a
   // stream to the frame head between k_cir_corr and the head, and the plot would miss a call that the head made.)
-  const bool async_acquire = !e->cfg.dc_iq_correction && e->cir.n_corr == 0 && (e->cfg.acquire_mode == 2 || (e->cfg.acquire_mode == 0 && some_locked));
+  // (... and while a stream has the spectrum on -- dabx_set_spectrum_mode: k_spectrum reads, behind the head, where the search has left the stream)
+  const bool async_acquire = !e->cfg.dc_iq_correction && e->cir.n_corr == 0 && e->spectrum.n_on == 0 && (e->cfg.acquire_mode == 2 || (e->cfg.acquire_mode == 0 && some_locked));
   for (int i = 0; i < max_frames; i++) {
     // the 5th frame after a batch starts rewriting time-de-interleaver slots the previous batch's k_msc_prep (stream b) reads
     if (e->ss.prep_pending && e->pending_frames >= 4) {
@@ -820,11 +822,12 @@ int dabx_process(dabx_engine *e, int max_frames, int sync)
     // (the CIR stage's kernels go in front of the frame head, only while a stream has the mode on and a row is due or a plot is on)
     const int cir_cap = e->cir.n_on > 0 ? cir_step_cap(e, false) : 0;
     int rc = launch_front_step(e->dev, e->ss, e->mk, async_acquire, all_locked, e->scope.n_on > 0 ? &e->scope.dev : nullptr,
-                               e->cir.n_on > 0 ? &e->cir.dev : nullptr, cir_cap);
+                               e->cir.n_on > 0 ? &e->cir.dev : nullptr, cir_cap, e->spectrum.n_on > 0 ? &e->spectrum.dev : nullptr);
     if (rc) return rc;
     if (cir_cap > 0) cir_step_cap(e, true);                // the step is launched: the host's count of rows done follows k_cir_finish's
     if (e->cir.n_on > 0 && (cir_cap > 0 || e->cir.n_corr > 0)) e->cir.launches++;
     if (e->scope.n_on > 0) e->scope.launches++;
+    if (e->spectrum.n_on > 0) e->spectrum.launches++;
     // the TII detectors of the streams that have the mode on (deliver.hip): behind the frame tail, in front of the next frame's accumulation
     if (e->tiis.n_on > 0) {
       if ((rc = launch_tii(e->dev, e->tiis.dev, e->stream))) return rc;

@@ -10,6 +10,7 @@
 #include "tii_core.h"
 #include "scope_core.h"
 #include "cir_core.h"
+#include "spectrum_core.h"
 #include "sdma.h"
 #include "iqfile.h"
 #include <algorithm>
@@ -79,6 +80,11 @@ struct Delivery {
   unsigned long long *cir_off = nullptr;
   std::vector<char> cir_room;
   bool cir() const { return (what & DABX_DELIVER_CIR) != 0; }
+  // DABX_DELIVER_SPECTRUM (deliver.hip, k_deliver_spectrum): the same three for the spectrum section
+  long long *spec_done = nullptr;
+  unsigned long long *spec_off = nullptr;
+  std::vector<char> spec_room;
+  bool spectrum() const { return (what & DABX_DELIVER_SPECTRUM) != 0; }
   bool tii() const { return (what & DABX_DELIVER_TII) != 0; }
   bool mp2_audio() const { return (what & DABX_DELIVER_MP2_AUDIO) != 0; }      // the MP2 audio section (deliver.hip, k_deliver_mp2_audio), while a slot has the mode on
   bool aac() const { return (what & DABX_DELIVER_AAC) != 0; }      // the AAC section (deliver.hip, k_deliver_aac), while a slot has the mode on
@@ -209,6 +215,20 @@ struct CirStage {
   bool exists() const { return dev.ring != nullptr; }
 };
 
+// The RF spectrum / waterfall stage (include/dabx.h dabx_set_spectrum_mode, pipeline.hip k_spectrum).  Nothing of it exists until the mode is
+// first switched on: dev stays all null, n_on stays 0 and no step launches a kernel of it.
+struct SpecStage {
+  SpecDev dev{};
+  int32_t *list = nullptr;                     // [S] device: the first n_on entries are the streams with the mode on (SpecDev::list)
+  SpecCfgDev *cfg_dev = nullptr;               // [S] (SpecDev::cfg)
+  float *window = nullptr;                     // [2048] device (SpecDev::window)
+  int n_on = 0;                                // streams with the mode on
+  std::vector<SpecCfgDev> cfg;                 // [S] mirror of cfg_dev
+  std::vector<long long> seen, lost;           // [S] records dabx_read_spectrum has returned or passed / found gone
+  long long launches = 0;
+  bool exists() const { return dev.ring != nullptr; }
+};
+
 struct dabx_engine : dabx::EngineHead {         // (iqfile.h: the ring format, where iqfile.cpp can read it)
   dabx_config cfg{};
   EngineDev dev{};
@@ -229,6 +249,7 @@ struct dabx_engine : dabx::EngineHead {         // (iqfile.h: the ring format, w
   TiiStage tiis;                               // the detectors on the device
   ScopeStage scope;                            // the IQ scope and carrier plots on the device
   CirStage cir;                                // the channel impulse response and the correlation plot on the device
+  SpecStage spectrum;                          // the RF spectrum and waterfall rows on the device
   std::vector<void *> allocs;
   void *stage = nullptr;                       // host -> device staging of dabx_push_iq
   size_t stage_cap = 0;
@@ -314,6 +335,8 @@ void scope_stage_free(dabx_engine *e);
 // engine_cir.cpp
 void cir_stage_free(dabx_engine *e);
 int cir_step_cap(dabx_engine *e, bool advance);   // the rows due per stream in the step about to be launched, at most; advance: the host's bookkeeping moves on
+// engine_spectrum.cpp
+void spectrum_stage_free(dabx_engine *e);
 // engine_slots.cpp
 void pad_count_sources(dabx_engine *e);
 int mot_follow_pad(dabx_engine *e);

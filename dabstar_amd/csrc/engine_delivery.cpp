@@ -113,6 +113,14 @@ int dabx_engine::delivery_layout()
       if (D.cir_room[s_]) { so[s_] = off; off += (size_t)DABX_CIR_CHUNK_RECORDS * CIR_SLOT_BYTES; }
     DABX_HIP(hipMemcpy(D.cir_off, so.data(), sizeof(unsigned long long) * S, hipMemcpyHostToDevice));
   }
+  // the spectrum section: its table, then DABX_SPECTRUM_CHUNK_RECORDS record slots for every stream that had the mode on when the delivery was opened
+  if (D.spectrum()) {
+    off = align_up(off, 16); x.off_spectrum = off; off += S * sizeof(dabx_chunk_spectrum);
+    std::vector<unsigned long long> so(S, 0);
+    for (size_t s_ = 0; s_ < S; s_++)
+      if (D.spec_room[s_]) { so[s_] = off; off += (size_t)DABX_SPECTRUM_CHUNK_RECORDS * SPEC_SLOT_BYTES; }
+    DABX_HIP(hipMemcpy(D.spec_off, so.data(), sizeof(unsigned long long) * S, hipMemcpyHostToDevice));
+  }
   off = align_up(off, 256);
   h.off_msc = off;
   if ((D.what & (DABX_DELIVER_MSC | DABX_DELIVER_MSC_NOT_DABPLUS)) && !d.fic_only)
@@ -205,6 +213,11 @@ int dabx_engine::delivery_begin(DeliverDev *dv, int *slot, int *devslab)
   if (!rc && D.cir())
     rc = launch_deliver_cir(dev.n_streams, CirDeliverDev{D.dev[*devslab], D.ext.off_cir, D.cir_off, D.cir_done, cir.dev.ring,
                                                  cir.exists() ? &cir.dev.st->shows : nullptr, (int32_t)(sizeof(CirState) / sizeof(long long)), 0}, stream);
+  // the spectrum section: behind the k_spectrum of the chunk's last frame, which the front-end stream has run (deliver.hip, k_deliver_spectrum)
+  if (!rc && D.spectrum())
+    rc = launch_deliver_spectrum(dev.n_streams, SpecDeliverDev{D.dev[*devslab], D.ext.off_spectrum, D.spec_off, D.spec_done, spectrum.dev.ring,
+                                                               spectrum.exists() ? &spectrum.dev.st->shows : nullptr,
+                                                               (int32_t)(sizeof(SpecState) / sizeof(long long)), 0}, stream);
   if (rc) {                                                        // nothing was queued: give the slabs back
     std::lock_guard<std::mutex> lk(D.mu);
     D.dev_busy[*devslab] = false;
@@ -344,10 +357,11 @@ void delivery_free(dabx_engine *e)
   }
   for (void *q : {(void *)D.layout_off, (void *)D.subch_id, (void *)D.frames_done, (void *)D.cif_done, (void *)D.sf_done, (void *)D.eti_front,
                   (void *)D.eti_next, (void *)D.eti_stage[0], (void *)D.eti_stage[1], (void *)D.eti_stage[2], (void *)D.tii_done, (void *)D.scope_done,
-                  (void *)D.scope_off, (void *)D.cir_done, (void *)D.cir_off}) if (q) (void)hipFree(q);
+                  (void *)D.scope_off, (void *)D.cir_done, (void *)D.cir_off, (void *)D.spec_done, (void *)D.spec_off}) if (q) (void)hipFree(q);
   D.tii_done = nullptr; D.ext = dabx_chunk_header_ext{};
   D.scope_done = nullptr; D.scope_off = nullptr; D.scope_room.clear();
   D.cir_done = nullptr; D.cir_off = nullptr; D.cir_room.clear();
+  D.spec_done = nullptr; D.spec_off = nullptr; D.spec_room.clear();
   D.layout_off = nullptr; D.subch_id = nullptr; D.frames_done = D.cif_done = D.sf_done = nullptr;
   D.eti_front = nullptr; D.eti_next = nullptr; D.eti_rows_off = 0;
   for (int k = 0; k < Delivery::NDEV; k++) D.eti_stage[k] = nullptr;
@@ -364,7 +378,7 @@ extern "C" {
 
 int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
 {
-  if (!e || (cfg && (cfg->host_slabs < 0 || cfg->host_slabs == 1 || cfg->host_slabs > 64 || (cfg->what & ~(1023 | DABX_DELIVER_AAC | DABX_DELIVER_SCOPE | DABX_DELIVER_CIR)) || cfg->copy_engine < 0 || cfg->copy_engine > 1))) {
+  if (!e || (cfg && (cfg->host_slabs < 0 || cfg->host_slabs == 1 || cfg->host_slabs > 64 || (cfg->what & ~(1023 | DABX_DELIVER_AAC | DABX_DELIVER_SCOPE | DABX_DELIVER_CIR | DABX_DELIVER_SPECTRUM)) || cfg->copy_engine < 0 || cfg->copy_engine > 1))) {
     set_error("dabx_delivery_open: bad argument");
     return DABX_E_ARG;
   }
@@ -392,8 +406,14 @@ int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
   }
   // ... and DABX_DELIVER_CIR, in the same way
   if (cfg && (cfg->what & DABX_DELIVER_CIR) &&
-      !(cfg->what & ~(DABX_DELIVER_CIR | DABX_DELIVER_SCOPE | DABX_DELIVER_AAC | DABX_DELIVER_MP2_AUDIO | DABX_DELIVER_TII | DABX_DELIVER_ETI))) {
+      !(cfg->what & ~(DABX_DELIVER_SPECTRUM | DABX_DELIVER_CIR | DABX_DELIVER_SCOPE | DABX_DELIVER_AAC | DABX_DELIVER_MP2_AUDIO | DABX_DELIVER_TII | DABX_DELIVER_ETI))) {
     set_error("dabx_delivery_open: DABX_DELIVER_CIR needs at least one DABX_DELIVER_* bit below 128 beside it");
+    return DABX_E_ARG;
+  }
+  // ... and DABX_DELIVER_SPECTRUM, in the same way
+  if (cfg && (cfg->what & DABX_DELIVER_SPECTRUM) &&
+      !(cfg->what & ~(DABX_DELIVER_SPECTRUM | DABX_DELIVER_CIR | DABX_DELIVER_SCOPE | DABX_DELIVER_AAC | DABX_DELIVER_MP2_AUDIO | DABX_DELIVER_TII | DABX_DELIVER_ETI))) {
+    set_error("dabx_delivery_open: DABX_DELIVER_SPECTRUM needs at least one DABX_DELIVER_* bit below 128 beside it");
     return DABX_E_ARG;
   }
   if (e->dl.open) { set_error("dabx_delivery_open: already open"); return DABX_E_STATE; }
@@ -447,6 +467,14 @@ int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
     if (e->cir.exists())
       for (size_t s_ = 0; s_ < S; s_++) { D.cir_room[s_] = (char)(e->cir.cfg[s_].enable != 0); n_on += D.cir_room[s_] ? 1 : 0; }
     cap += (D.tii() || D.mp2_audio() || D.aac() || D.scope() ? 0 : sizeof(dabx_chunk_header_ext)) + 16 + S * sizeof(dabx_chunk_cir) + n_on * (size_t)DABX_CIR_CHUNK_RECORDS * CIR_SLOT_BYTES;
+  }
+  D.spec_room.assign(D.spectrum() ? S : 0, 0);
+  if (D.spectrum()) {                                               // ... and the spectrum section: its table and DABX_SPECTRUM_CHUNK_RECORDS record slots per stream with the mode on
+    size_t n_on = 0;
+    if (e->spectrum.exists())
+      for (size_t s_ = 0; s_ < S; s_++) { D.spec_room[s_] = (char)(e->spectrum.cfg[s_].enable != 0); n_on += D.spec_room[s_] ? 1 : 0; }
+    cap += (D.tii() || D.mp2_audio() || D.aac() || D.scope() || D.cir() ? 0 : sizeof(dabx_chunk_header_ext)) + 16 + S * sizeof(dabx_chunk_spectrum) +
+           n_on * (size_t)DABX_SPECTRUM_CHUNK_RECORDS * SPEC_SLOT_BYTES;
   }
   D.capacity = align_up(cap, 4096);
 #define H(x) do { hipError_t err__ = (x); if (err__ != hipSuccess) { set_error("HIP error %d (%s) at %s:%d", (int)err__, hipGetErrorString(err__), __FILE__, __LINE__); delivery_free(e); return DABX_E_HIP; } } while (0)
@@ -529,6 +557,18 @@ int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
       H(hipMalloc((void **)&D.cir_done, sizeof(long long) * S));
       H(hipMemcpy(D.cir_done, cdn.data(), sizeof(long long) * S, hipMemcpyHostToDevice));
       H(hipMalloc((void **)&D.cir_off, sizeof(unsigned long long) * S));
+    }
+    if (D.spectrum()) {
+      // the spectrum section's cursor: the records completed from now on
+      std::vector<long long> cdn(S, 0);
+      if (e->spectrum.exists()) {
+        std::vector<SpecState> st(S);
+        H(hipMemcpy(st.data(), e->spectrum.dev.st, sizeof(SpecState) * S, hipMemcpyDeviceToHost));
+        for (size_t s_ = 0; s_ < S; s_++) cdn[s_] = st[s_].shows;
+      }
+      H(hipMalloc((void **)&D.spec_done, sizeof(long long) * S));
+      H(hipMemcpy(D.spec_done, cdn.data(), sizeof(long long) * S, hipMemcpyHostToDevice));
+      H(hipMalloc((void **)&D.spec_off, sizeof(unsigned long long) * S));
     }
   }
 #undef H

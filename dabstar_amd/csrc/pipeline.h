@@ -241,6 +241,18 @@ struct CirDeliverDev {
   int32_t st_stride, pad_;                // ... in long longs
 };
 
+// ---- the spectrum section of the delivery (deliver.hip k_deliver_spectrum, include/dabx.h dabx_chunk_spectrum): the records k_spectrum
+// (pipeline.hip) has completed since the previous chunk, out of the stage's ring
+struct SpecDeliverDev {
+  uint8_t *slab;
+  unsigned long long off_spectrum;        // dabx_chunk_header_ext.off_spectrum of the slab
+  const unsigned long long *rec_off;      // [S] where the stream's record slots lie in a slab, 0 = it has no room (mode off when the delivery was opened)
+  long long *done;                        // [S] records of the stream delivered or passed so far
+  const uint8_t *ring;                    // SpecDev::ring (spectrum_core.h), null while the engine has no spectrum stage: every stream delivers no record
+  const long long *shows;                 // &st[0].shows, a SpecState apart
+  int32_t st_stride, pad_;                // ... in long longs
+};
+
 // ---- lane-per-trellis path of the MSC decoder (vit_t.hip) ------------------------------------------------------
 // The sub-channels of ALL streams are grouped into classes of equal protection profile (same depuncture map and
 // trellis length): the 64 lanes of a decoder wave then share the map and step count whatever ensemble they come from.
@@ -413,10 +425,11 @@ struct Mp2AudioDev;               // mp2_core.h
 struct AacStreamDev;              // aac_core.h
 struct ScopeDev;                  // scope_core.h
 struct CirDev;                    // cir_core.h
+struct SpecDev;                   // spectrum_core.h
 // pipeline.hip
 extern const char *const kStepKernelNames[N_STEP_KERNELS];
 int launch_front_step(const EngineDev &e, EngineStreams &ss, Marker &mk, bool async_acquire, bool all_locked, const ScopeDev *scope = nullptr,
-                      const CirDev *cir = nullptr, int cir_cap = 0);
+                      const CirDev *cir = nullptr, int cir_cap = 0, const SpecDev *spec = nullptr);
 int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineStreams &ss, Marker &mk, const DeliverDev *dv = nullptr,
                      hipStream_t *tail = nullptr, const PacketDev *pk = nullptr, const PadDev *pad = nullptr, const MotDev *mot = nullptr,
                      const CarouselDev *car = nullptr, const EtiDev *eti = nullptr, const Mp2AudioDev *mp2a = nullptr, long long *mp2a_launches = nullptr,
@@ -450,6 +463,7 @@ int launch_deliver_ext(const dabx_chunk_header_ext &ext, uint8_t *slab, hipStrea
 int launch_deliver_tii(const EngineDev &e, const TiiDeliverDev &td, hipStream_t st);                // at chunk close, front-end stream, behind launch_deliver_front
 int launch_deliver_scope(const EngineDev &e, const ScopeDeliverDev &sd, hipStream_t st);            // at chunk close, front-end stream, behind the header's extension
 int launch_deliver_cir(int n_streams, const CirDeliverDev &cd, hipStream_t st);                     // ... and the CIR section behind it
+int launch_deliver_spectrum(int n_streams, const SpecDeliverDev &sd, hipStream_t st);               // ... and the spectrum section behind that
 int launch_eti_front(const EngineDev &e, const EtiDev &t, hipStream_t st, Marker &mk);              // at chunk close, front-end stream
 int launch_eti_back(const EngineDev &e, const EtiDev &t, hipStream_t st, Marker &mk, bool pre);     // behind the batch's decode; pre: in front of its DAB+ stage
 // msc_stages.hip

@@ -27,6 +27,7 @@
 #include "ofdm_core.h"
 #include "scope_core.h"
 #include "cir_core.h"
+#include "spectrum_core.h"
 #include "viterbi_core.h"
 #include "fec_core.h"
 #include "acq_walk.h"
@@ -2107,6 +2108,172 @@ static int launch_cir_corr(const EngineDev &e, const DevTables &t, const CirDev 
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------- spectrum
+// The RF spectrum and waterfall row of SpectrumViewer::show_spectrum (spectrum_viewer.cpp:141-234) and WaterfallScope::show_waterfall
+// (waterfall_scope.cpp:52-79; spectrum_core.h; docs/history/spectrum.md).  One block per stream with the mode on, on the front-end stream
+// directly behind k_frame_head, with the search in step (dabx_process): the read position, state, failed-correlation count and -- if this
+// step's head has begun a frame -- the frame's symbol-0 position are what the search and the head have just left, and the frame's samples
+// are not read yet.  A block
+//   1. evaluates the stream's window [W, W + 2048) if that is not done and its samples are committed (spectrum_row_block; the samples
+//      SampleReader captures, sample_reader.cpp:198-205, :267-272: RingFmt<RF>::cvt of the ring, behind k_dciq and in front of the NCO) into the
+//      stream's pending slot -- only while the trust rule holds (cir_row_trusted, cir_core.h), looked at before and after the loads;
+//   2. looks where the receiver stands (spectrum_look): if the window's show position E lies in what was searched since the last look or in the
+//      frame that begins, the pending slot becomes the stream's next record and the next window starts at E;
+//   3. evaluates that window at once if it is committed: in lock it starts at a symbol end of the frame the head has just begun, which the
+//      receiver has not read yet.
+// Windows of a stream are more than 512 000 samples apart and a step consumes less, so at most one show per look, in order.
+template <int RF>
+__global__ __launch_bounds__(256) void k_spectrum(EngineDev e, DevTables t, SpecDev sd)
+{
+  __shared__ __attribute__((aligned(16))) float2 lds[FFT_LDS_FLOAT2];           // (spectrum_row_block reads it back four floats at a time)
+  __shared__ float red[16];
+  __shared__ unsigned long long s_look[2], s_E;
+  __shared__ SpecState s_q;
+  __shared__ int s_inexact;
+  const int s = sd.list[blockIdx.x], tid = threadIdx.x;
+  const SpecCfgDev cfg = sd.cfg[s];
+  if (!cfg.enable) return;
+  const StreamCtl &c = e.ctl[s];
+  const unsigned long long len = (unsigned long long)e.ring_len, wr = e.wr[s];
+  uint8_t *pend = sd.pend + (size_t)s * SPEC_SLOT_BYTES;
+  float *dispg = sd.disp + (size_t)s * SPEC_DISPLAY;
+  float *pend_db = reinterpret_cast<float *>(pend + 64);
+  uint8_t *pend_row = pend + 64 + SPEC_DISPLAY * 4;
+  // one thread looks -- the read position, and the write horizon in host memory --, everyone follows
+  auto look = [&]() {
+    __syncthreads();
+    if (tid == 0) {
+      s_look[0] = __hip_atomic_load(&c.rd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      s_look[1] = __hip_atomic_load(&e.wr_horizon[s], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    __syncthreads();
+  };
+  // the pending slot of a window that is not evaluated: db, limits and row as they stand, untrusted = 1
+  auto give_up = [&]() {
+#pragma unroll
+    for (int h = 0; h < 2; h++) { pend_db[tid + 256 * h] = dispg[tid + 256 * h]; pend_row[tid + 256 * h] = 0; }
+    if (tid == 0) {
+      dabx_spectrum_record r{};
+      r.untrusted = 1;
+      *reinterpret_cast<dabx_spectrum_record *>(pend) = r;
+      const SpecLimits l = s_q.lim;
+      *reinterpret_cast<dabx_spectrum_limits_rec *>(pend + 32) = dabx_spectrum_limits_rec{l.glob_max, l.glob_min, l.loc_max, l.loc_min, 0.0f, 0.0f, {0.0f, 0.0f}};
+      s_q.computed = 2;
+    }
+  };
+  if (tid == 0) s_q = sd.st[s];
+  __syncthreads();
+#pragma unroll 1
+  for (int pass = 0; pass < 2; pass++) {
+    const unsigned long long first = s_q.W;
+    const bool todo = !s_q.computed && wr >= first + (unsigned long long)SPEC_SIZE;
+    __syncthreads();                                                              // every thread has read s_q: the look below writes it
+    if (todo) {                                                                   // (block-uniform)
+      look();
+      if (cir_row_trusted(first, s_look[0], s_look[1], len)) {                    // a window that is not trusted is not loaded at all
+        const RingView<RF> rv(stream_ring<RF>(e, s), e.ring_len, first);
+        float2 v[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) v[u] = rv.at(tid + 256 * u);
+        float lin[2], disp[2] = {dispg[tid], dispg[tid + 256]}, ext[4];
+        spectrum_row_block(v, sd.window, t, lds, red, tid, lin, disp, ext);       // (its barriers stand behind every thread's loads)
+        look();
+        if (cir_row_trusted(first, s_look[0], s_look[1], len)) {
+          SpecLimits l = s_q.lim;                                                 // (the same in every thread)
+          float y_min, y_max;
+          const int valid = spectrum_limits(ext, l, spectrum_alpha(cfg.averaging), cfg.zoom_percent, &y_min, &y_max);
+          __syncthreads();                                                        // (every thread has read s_q.lim)
+#pragma unroll
+          for (int h = 0; h < 2; h++) {
+            dispg[tid + 256 * h] = disp[h];
+            pend_db[tid + 256 * h] = disp[h];
+            pend_row[tid + 256 * h] = valid ? spectrum_pixel(disp[h], y_min, y_max - y_min) : (uint8_t)0;
+          }
+          if (tid == 0) {
+            dabx_spectrum_record r{};
+            r.row_valid = valid;
+            *reinterpret_cast<dabx_spectrum_record *>(pend) = r;
+            *reinterpret_cast<dabx_spectrum_limits_rec *>(pend + 32) = dabx_spectrum_limits_rec{l.glob_max, l.glob_min, l.loc_max, l.loc_min, y_min, y_max, {0.0f, 0.0f}};
+            s_q.lim = l; s_q.computed = 1;
+          }
+        } else give_up();
+      } else give_up();
+      __syncthreads();
+    }
+    if (pass == 1) break;
+    if (tid == 0) {
+      const int st = __hip_atomic_load(&c.state, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+      int inexact;
+      const unsigned long long W = s_q.W;
+      s_E = spectrum_look(s_q, c.rd, st, c.sync_lost, c.frame_ok, c.sym0_pos, &inexact);
+      s_inexact = inexact;
+      if (s_q.W != W) s_E = SPEC_NONE;                                            // (a stream that was put back shows nothing in this look)
+    }
+    __syncthreads();
+    const unsigned long long E = s_E;
+    if (E == SPEC_NONE) break;
+    const bool never = !s_q.computed;                                             // never evaluated (its samples were never seen committed)
+    __syncthreads();
+    if (never) give_up();
+    if (tid == 0) {                                                             // the show: the pending slot's head
+      dabx_spectrum_record *r = reinterpret_cast<dabx_spectrum_record *>(pend);
+      r->frame = c.frames; r->first_sample = (int64_t)first; r->inexact = s_inexact;
+    }
+    __syncthreads();
+    uint4 *slot = reinterpret_cast<uint4 *>(sd.ring + ((size_t)s * SPEC_RING + (size_t)(s_q.shows % SPEC_RING)) * SPEC_SLOT_BYTES);
+    if (tid < SPEC_SLOT_BYTES / 16) slot[tid] = reinterpret_cast<const uint4 *>(pend)[tid];
+    __syncthreads();
+    if (tid == 0) {
+      s_q.shows++;
+      s_q.untrusted += s_q.computed == 2 ? 1 : 0;
+      s_q.inexact += reinterpret_cast<const dabx_spectrum_record *>(pend)->inexact;
+      s_q.W = E; s_q.computed = 0;
+    }
+    __syncthreads();
+  }
+  if (tid == 0) sd.st[s] = s_q;
+}
+
+// test entry (dabx_spectrum_rows_device): spectrum_row_block on n crafted windows, one behind the other through one display buffer; one block
+__global__ __launch_bounds__(256) void k_spectrum_rows_test(const float2 *in, int n, float *state, float *lin, float *db, float *ext, const float *window, DevTables t)
+{
+  __shared__ __attribute__((aligned(16))) float2 lds[FFT_LDS_FLOAT2];
+  __shared__ float red[16];
+  const int tid = threadIdx.x;
+  float disp[2] = {state[tid], state[tid + 256]}, x[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+  for (int k = 0; k < n; k++) {
+    const float2 *src = in + (size_t)k * SPEC_SIZE;
+    float2 v[8];
+#pragma unroll
+    for (int u = 0; u < 8; u++) v[u] = src[tid + 256 * u];
+    float l[2];
+    spectrum_row_block(v, window, t, lds, red, tid, l, disp, x);
+#pragma unroll
+    for (int h = 0; h < 2; h++) { lin[(size_t)k * SPEC_DISPLAY + tid + 256 * h] = l[h]; db[(size_t)k * SPEC_DISPLAY + tid + 256 * h] = disp[h]; }
+    if (ext && tid < 4) ext[4 * k + tid] = x[tid];
+  }
+  state[tid] = disp[0]; state[tid + 256] = disp[1];
+  if (tid < 4) state[SPEC_DISPLAY + tid] = x[tid];
+}
+
+int launch_spectrum_rows_test(const float2 *in, int n, float *state, float *lin, float *db, float *ext, const float *window, hipStream_t st)
+{
+  const DevTables *t;
+  if (int rc = get_tables(&t)) return rc;
+  hipLaunchKernelGGL(k_spectrum_rows_test, dim3(1), dim3(256), 0, st, in, n, state, lin, db, ext, window, *t);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+
+static int launch_spectrum(const EngineDev &e, const DevTables &t, const SpecDev *sd, hipStream_t st)
+{
+  if (!sd || sd->n <= 0) return 0;
+  DABX_LAUNCH_RING(e, k_spectrum, dim3(sd->n), dim3(256), 0, st, e, t, *sd);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+
 // "k_demap_fic": the first k_demap_frame launch of a frame (symbols 1..3) when the FIC is decoded on its own stream
 const char *const kStepKernelNames[N_STEP_KERNELS] = {"k_acquire", "k_frame_head", "k_symbols", "k_demap_frame", "k_fic_frame", "k_frame_tail",
                                                       "k_msc_prep", "k_msc_vitT", "k_msc_frame", "k_dabplus", "k_demap_fic", "k_packet", "k_pad", "k_mot",
@@ -2118,7 +2285,8 @@ const char *const kStepKernelNames[N_STEP_KERNELS] = {"k_acquire", "k_frame_head
 // chain) and the frame tail follow on a, while the 72 MSC symbols are demapped on stream d: nothing on the chain of the NEXT
 // frame needs them, so a goes on to frame n + 1 while d is busy; the next frame's first demapper launch (and the MSC batch)
 // wait for d.  Serial schedule (cfg.schedule = 1, ss.d null): every kernel on a in program order.
-int launch_front_step(const EngineDev &e_in, EngineStreams &ss, Marker &mk, bool async_acquire, bool all_locked, const ScopeDev *scope, const CirDev *cir, int cir_cap)
+int launch_front_step(const EngineDev &e_in, EngineStreams &ss, Marker &mk, bool async_acquire, bool all_locked, const ScopeDev *scope, const CirDev *cir, int cir_cap,
+                      const SpecDev *spec)
 {
   const DevTables *t;
   int rc = get_tables(&t);
@@ -2166,6 +2334,8 @@ int launch_front_step(const EngineDev &e_in, EngineStreams &ss, Marker &mk, bool
   if ((rc = launch_cir(e, *t, cir, cir_cap, st))) return rc;
   if ((rc = launch_cir_corr(e, *t, cir, st))) return rc;     // the correlation plot, directly in front of the head whose correlation it repeats
   mk.begin(1, st); DABX_LAUNCH_RING(e, k_frame_head, dim3(e.n_streams), dim3(256), 0, st, e, *t); mk.end(1, st);
+  // the spectrum stage (dabx_set_spectrum_mode): only while a stream has the mode on; behind the head, whose frame it looks at before the receiver reads it
+  if ((rc = launch_spectrum(e, *t, spec, st))) return rc;
   mk.begin(2, st); DABX_LAUNCH_RING(e, k_symbols_persistent, dim3(sym_blocks_per_stream(e.n_streams), e.n_streams), dim3(256), 0, st, e, *t); mk.end(2, st);
   // kernel instance by (ESoftBitType, symbol conversion of the canonical / SIMD builds)
 #define DABX_DEMAP_DISPATCH(KERNEL, ...)                                                                                         \

@@ -492,7 +492,7 @@ DELIVER_TII = 256
 TII_MAX_RESULTS = 32
 CHUNK_EXT_MAGIC = 0x45584244                     # "DBXE"
 CHUNK_HEADER_EXT = np.dtype([("magic", "<u4"), ("bytes", "<u4"), ("off_tii", "<u8"), ("off_mp2_audio", "<u8"), ("off_aac", "<u8"), ("off_scope", "<u8"),
-                             ("off_cir", "<u8"), ("reserved", "<u8", 2)])
+                             ("off_cir", "<u8"), ("off_spectrum", "<u8"), ("reserved", "<u8", (1,))])
 CHUNK_TII = np.dtype([("first_event", "<i8"), ("n_events", "<i4"), ("events_lost", "<i4"), ("ev_off", "<u8"), ("events_total", "<i8")])
 TII_EVENT = np.dtype([("frame", "<i8"), ("n_results", "<i4"), ("n_found", "<i4"), ("frames_in_sum", "<i4"), ("epoch", "<i4"),
                       ("threshold_db", "<i4"), ("reserved", "<i4")])
@@ -626,6 +626,95 @@ DELIVER_CIR = 32768
 CIR_CHUNK_RECORDS = 4
 CHUNK_CIR = np.dtype([("first_record", "<i8"), ("n_records", "<i4"), ("records_lost", "<i4"), ("rec_off", "<u8"), ("records_total", "<i8")])
 assert CIR_RECORD.itemsize == 32 and CIR_STATS.itemsize == 64 and CHUNK_CIR.itemsize == 32
+
+
+# RF spectrum and waterfall (include/dabx.h "RF spectrum and waterfall"): dabx_spectrum_record, one per show, with dabx_spectrum_limits_rec, db [512]
+# float32 and row [512] uint8 behind it; dabx_spectrum_stats
+SPECTRUM_BINS = 512
+SPECTRUM_SIZE = 2048
+SPECTRUM_PERIOD = 512000
+SPECTRUM_RING = 8
+SPECTRUM_AVERAGING = {"slow": 0, "medium": 1, "fast": 2}
+SPECTRUM_RECORD = np.dtype([("frame", "<i8"), ("first_sample", "<i8"), ("untrusted", "<i4"), ("row_valid", "<i4"), ("inexact", "<i4"), ("reserved", "<i4")])
+SPECTRUM_LIMITS = np.dtype([("glob_max", "<f4"), ("glob_min", "<f4"), ("loc_max", "<f4"), ("loc_min", "<f4"), ("y_min", "<f4"), ("y_max", "<f4"),
+                            ("reserved", "<f4", 2)])
+SPECTRUM_STATS = np.dtype([("shows", "<i8"), ("untrusted", "<i8"), ("lost", "<i8"), ("launches", "<i8"), ("inexact", "<i8"), ("reserved", "<i8", 3)])
+SPECTRUM_SLOT_BYTES = 32 + 32 + SPECTRUM_BINS * 4 + SPECTRUM_BINS
+# the slab's spectrum section (DELIVER_SPECTRUM = 65536, opt-in like DELIVER_CIR; 1024, 4096 and 16384 stay refused; announced by the header's
+# extension): one CHUNK_SPECTRUM per stream, then SPECTRUM_CHUNK_RECORDS record slots for every stream that had the mode on when the delivery was opened
+DELIVER_SPECTRUM = 65536
+SPECTRUM_CHUNK_RECORDS = 6
+CHUNK_SPECTRUM = np.dtype([("first_record", "<i8"), ("n_records", "<i4"), ("records_lost", "<i4"), ("rec_off", "<u8"), ("records_total", "<i8")])
+assert SPECTRUM_RECORD.itemsize == 32 and SPECTRUM_LIMITS.itemsize == 32 and SPECTRUM_STATS.itemsize == 64 and CHUNK_SPECTRUM.itemsize == 32
+
+
+class SpectrumConfig(C.Structure):
+    """dabx_spectrum_config."""
+    _fields_ = [("enable", C.c_int32), ("averaging", C.c_int32), ("zoom_percent", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+def spectrum_rows_device(iq, state=None):
+    """spectrum_viewer.cpp:169-218 on crafted windows (dabx_spectrum_rows_device): iq [n, 2048] complex64, one behind the other through one
+    display buffer.  state = None: a fresh one (zeros), else [516] float32 from an earlier call.  -> (lin [n, 512], db [n, 512], ext [n, 4],
+    state [516]): mYValVec, mDisplayBuffer behind each window, each window's extrema {glob max, glob min, loc max, loc min}."""
+    iq = np.ascontiguousarray(iq, np.complex64).reshape(-1, SPECTRUM_SIZE)
+    n = iq.shape[0]
+    st = np.zeros(SPECTRUM_BINS + 4, np.float32) if state is None else np.array(state, np.float32).reshape(SPECTRUM_BINS + 4)
+    lin = np.zeros((n, SPECTRUM_BINS), np.float32)
+    db = np.zeros((n, SPECTRUM_BINS), np.float32)
+    ext = np.zeros((n, 4), np.float32)
+    L = load()
+    L.dabx_spectrum_rows_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    check(L.dabx_spectrum_rows_device(_p(iq), n, _p(st), _p(lin), _p(db), _p(ext)))
+    return lin, db, ext, st
+
+
+def spectrum_limits(ext, limits, averaging="medium", zoom=0):
+    """dabx_spectrum_limits, on the host: a show's extrema {glob max, glob min, loc max, loc min} into the four limits {Glob.Max, Glob.Min,
+    Loc.Max, Loc.Min} -> (limits [4] float32, (yMin, yMax), row valid)."""
+    e = np.array(ext, np.float32).reshape(4)
+    l = np.array(limits, np.float32).reshape(4)
+    y = np.zeros(2, np.float32)
+    L = load()
+    L.dabx_spectrum_limits.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    valid = check(L.dabx_spectrum_limits(_p(e), _p(l), SPECTRUM_AVERAGING.get(averaging, averaging), int(zoom), _p(y)))
+    return l, (y[0], y[1]), bool(valid)
+
+
+def spectrum_waterfall_row(db, y):
+    """dabx_spectrum_waterfall_row, on the host: the colour indices of db for the range y = (yMin, yMax)."""
+    d = np.ascontiguousarray(db, np.float32).reshape(-1)
+    yy = np.array(y, np.float32).reshape(2)
+    row = np.zeros(d.size, np.uint8)
+    L = load()
+    L.dabx_spectrum_waterfall_row.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    check(L.dabx_spectrum_waterfall_row(_p(d), d.size, _p(yy), _p(row)))
+    return row
+
+
+def spectrum_next_show(W, kind, a, b=0):
+    """dabx_spectrum_next_show, on the host: the show position E of window W inside a searched range [a, b) (kind 0) or a frame whose
+    symbol 0 ends at a (kind 1), or None."""
+    L = load()
+    L.dabx_spectrum_next_show.argtypes = [C.c_uint64, C.c_int, C.c_uint64, C.c_uint64]
+    L.dabx_spectrum_next_show.restype = C.c_int64
+    E = L.dabx_spectrum_next_show(int(W), int(kind), int(a), int(b))
+    if E < -1:
+        check(int(E))
+    return None if E < 0 else int(E)
+
+
+def spectrum_look(walk, rd, state, sync_lost, frame_ok, sym0_pos):
+    """dabx_spectrum_look, on the host: one look of k_spectrum.  walk = [W, pos, lost_seen, state_seen] -> (E or None, inexact, walk)."""
+    w = np.array(walk, np.int64).reshape(4)
+    inexact = C.c_int32(0)
+    L = load()
+    L.dabx_spectrum_look.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int64, C.c_int, C.c_uint64, C.c_void_p]
+    L.dabx_spectrum_look.restype = C.c_int64
+    E = L.dabx_spectrum_look(_p(w), int(rd), int(state), int(sync_lost), int(frame_ok), int(sym0_pos), C.byref(inexact))
+    if E < -1:
+        check(int(E))
+    return (None if E < 0 else int(E)), inexact.value, w.tolist()
 
 
 class CirConfig(C.Structure):
@@ -762,6 +851,7 @@ class Chunk:
         self.aac_table = None                   # the AAC section: [S, M] CHUNK_AAC, or None when the slab has none
         self.scope_table = None                 # the scope section: [S] CHUNK_SCOPE, or None when the slab has none
         self.cir_table = None                   # the CIR section: [S] CHUNK_CIR, or None when the slab has none
+        self.spectrum_table = None              # the spectrum section: [S] CHUNK_SPECTRUM, or None when the slab has none
         if int(h["what"]) & ~255:
             self.header_ext = self.raw[128:192].view(CHUNK_HEADER_EXT)[0]
             if int(self.header_ext["magic"]) != CHUNK_EXT_MAGIC or int(self.header_ext["bytes"]) < 64:
@@ -781,6 +871,9 @@ class Chunk:
             if int(self.header_ext["off_cir"]):
                 o = int(self.header_ext["off_cir"])
                 self.cir_table = self.raw[o:o + S * 32].view(CHUNK_CIR)
+            if int(self.header_ext["off_spectrum"]):
+                o = int(self.header_ext["off_spectrum"])
+                self.spectrum_table = self.raw[o:o + S * 32].view(CHUNK_SPECTRUM)
         self.eti_table = None                  # the ETI section: [S] CHUNK_ETI, or None when the slab has none
         if int(h["off_eti"]):
             self.eti_table = self.raw[int(h["off_eti"]):int(h["off_eti"]) + S * 64].view(CHUNK_ETI)
@@ -823,6 +916,19 @@ class Chunk:
             rec = self.raw[o:o + 32].view(CIR_RECORD)[0]
             out.append((rec, self.raw[o + 32:o + 32 + 4 * int(rec["n_values"])].view(np.float32),
                         self.raw[o + 32 + CIR_CORR_LAGS * 4:o + 32 + CIR_CORR_LAGS * 4 + 2 * int(rec["n_indices"])].view(np.int16)))
+        return out
+
+    def spectrum(self, stream):
+        """Spectrum records of `stream` in this chunk, oldest first: a list of (SPECTRUM_RECORD record, SPECTRUM_LIMITS record, db [512]
+        float32, row [512] uint8), views.  Empty when the slab has no spectrum section or the stream had the mode off when the delivery was opened."""
+        if self.spectrum_table is None:
+            return []
+        r = self.spectrum_table[stream]
+        out = []
+        for k in range(int(r["n_records"])):
+            o = int(r["rec_off"]) + k * SPECTRUM_SLOT_BYTES
+            out.append((self.raw[o:o + 32].view(SPECTRUM_RECORD)[0], self.raw[o + 32:o + 64].view(SPECTRUM_LIMITS)[0],
+                        self.raw[o + 64:o + 64 + 4 * SPECTRUM_BINS].view(np.float32), self.raw[o + 64 + 4 * SPECTRUM_BINS:o + SPECTRUM_SLOT_BYTES]))
         return out
 
     def eti(self, stream):
@@ -1139,6 +1245,35 @@ class Engine:
         check(L.dabx_get_cir_stats(self._h, stream, _p(st)))
         return {"shows": [int(v) for v in st["shows"][0]], "lost": int(st["lost"][0]), "rows_untrusted": int(st["rows_untrusted"][0]),
                 "launches": int(st["launches"][0])}
+
+    def set_spectrum_mode(self, stream, averaging="medium", zoom=0, enable=True):
+        """The stream's RF spectrum and waterfall rows on the device (dabx_set_spectrum_mode; stream = -1: all streams): a record per show of
+        SpectrumViewer::show_spectrum, more than 512 000 consumed samples apart; read with read_spectrum.  averaging: "slow" / "medium" /
+        "fast" (the filter of the display limits), zoom: 0..100 (the waterfall's scaling).  enable=False switches it off."""
+        cfg = SpectrumConfig(enable=int(bool(enable)), averaging=SPECTRUM_AVERAGING.get(averaging, averaging), zoom_percent=int(zoom))
+        L = load()
+        L.dabx_set_spectrum_mode.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        check(L.dabx_set_spectrum_mode(self._h, stream, C.byref(cfg) if enable else None))
+
+    def read_spectrum(self, stream, max_records=8):
+        """The records completed since the previous call: ([(SPECTRUM_RECORD record, SPECTRUM_LIMITS record, db [512] float32, row [512] uint8)],
+        records lost)."""
+        recs = np.zeros(max_records, SPECTRUM_RECORD)
+        lim = np.zeros(max_records, SPECTRUM_LIMITS)
+        db = np.zeros((max_records, SPECTRUM_BINS), np.float32)
+        row = np.zeros((max_records, SPECTRUM_BINS), np.uint8)
+        lost = C.c_int32(0)
+        L = load()
+        L.dabx_read_spectrum.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        n = check(L.dabx_read_spectrum(self._h, stream, max_records, _p(recs), _p(lim), _p(db), _p(row), C.byref(lost)))
+        return [(recs[k], lim[k], db[k], row[k]) for k in range(n)], lost.value
+
+    def spectrum_stats(self, stream):
+        st = np.zeros(1, SPECTRUM_STATS)
+        L = load()
+        L.dabx_get_spectrum_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        check(L.dabx_get_spectrum_stats(self._h, stream, _p(st)))
+        return {k: int(st[k][0]) for k in ("shows", "untrusted", "lost", "launches", "inexact")}
 
     def scope_stats(self, stream):
         st = np.zeros(1, SCOPE_STATS)

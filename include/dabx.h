@@ -987,7 +987,13 @@ enum { DABX_DELIVER_FIB = 1, DABX_DELIVER_MSC = 2, DABX_DELIVER_SF = 4,
           _MP2_AUDIO, _AAC and _SCOPE beside it is DABX_E_ARG, and without the bit a slab, dabx_delivery_slab_bytes and the kernels launched
           are exactly what they are without it.  With the bit the header is followed by a dabx_chunk_header_ext.  The value is 32768, not
           1024, 4096 or 16384: those masks have always been refused with DABX_E_ARG and callers rely on that, so they stay refused */
-       DABX_DELIVER_CIR = 32768 };
+       DABX_DELIVER_CIR = 32768,
+       /* the RF spectrum and waterfall records of every stream that has the mode on (dabx_set_spectrum_mode; the spectrum section,
+          dabx_chunk_spectrum below).  Opt-in exactly like the six bits above: what == 0 does NOT include it, the bit alone or with only
+          DABX_DELIVER_ETI, _TII, _MP2_AUDIO, _AAC, _SCOPE and _CIR beside it is DABX_E_ARG, and without the bit a slab,
+          dabx_delivery_slab_bytes and the kernels launched are exactly what they are without it.  With the bit the header is followed by a
+          dabx_chunk_header_ext.  1024, 4096 and 16384 stay refused with DABX_E_ARG, as ever */
+       DABX_DELIVER_SPECTRUM = 65536 };
 typedef struct {
   int32_t host_slabs;       /* page-locked host slabs, >= 2 (0 = default 4) */
   int32_t what;             /* DABX_DELIVER_* mask, 0 = everything */
@@ -1018,7 +1024,8 @@ typedef struct {
   uint64_t off_aac;         /* the AAC section: dabx_chunk_aac[n_streams * max_subch]; 0 = the slab has none */
   uint64_t off_scope;       /* the scope section: dabx_chunk_scope[n_streams]; 0 = the slab has none */
   uint64_t off_cir;         /* the CIR section: dabx_chunk_cir[n_streams]; 0 = the slab has none (the first of three words that were reserved) */
-  uint64_t reserved[2];
+  uint64_t off_spectrum;    /* the spectrum section: dabx_chunk_spectrum[n_streams]; 0 = the slab has none (the second of them) */
+  uint64_t reserved[1];
 } dabx_chunk_header_ext;    /* 64 bytes */
 typedef struct {
   int64_t first_frame;      /* index, since the stream was opened, of the first frame in the chunk */
@@ -1166,6 +1173,22 @@ typedef struct {
   uint64_t rec_off;         /* 0 = the stream has no room in this delivery */
   int64_t  records_total;   /* records the stream has written so far: first_record + n_records */
 } dabx_chunk_cir;           /* 32 bytes */
+/* The spectrum section (DABX_DELIVER_SPECTRUM; "RF spectrum and waterfall" below): one dabx_chunk_spectrum per stream from
+ * dabx_chunk_header_ext.off_spectrum, in the slab's head part behind the CIR section (or where that would be), followed by room for
+ * DABX_SPECTRUM_CHUNK_RECORDS record slots for each stream that has the mode on WHEN THE DELIVERY IS OPENED (a stream switched on later
+ * has no room and delivers none: rec_off = 0).  Shows lie more than 512 000 consumed samples apart and a step consumes at most a frame and
+ * a frame's worth of search (393 216 samples), so a chunk of DABX_CHUNK_FRAMES = 7 frames completes at most 6 records (three in lock): all
+ * of them have room, and records_lost stays 0 (the field is kept for the shape the other sections have: the newest are kept should a
+ * chunk ever complete more).  A record slot is DABX_SPECTRUM_SLOT_BYTES, byte for byte what dabx_read_spectrum returns; stream s's
+ * n_records slots lie one behind the other from rec_off, oldest first.  Every record a stream wrote since the previous chunk is in the
+ * chunk or counted in records_lost.  Gathered on the front-end stream when the chunk closes (k_deliver_spectrum), with a cursor of its own. */
+#define DABX_SPECTRUM_CHUNK_RECORDS 6
+typedef struct {
+  int64_t  first_record;    /* number, since the stream's mode was first switched on, of the first record in the chunk */
+  int32_t  n_records, records_lost;
+  uint64_t rec_off;         /* 0 = the stream has no room in this delivery */
+  int64_t  records_total;   /* records the stream has written so far: first_record + n_records */
+} dabx_chunk_spectrum;      /* 32 bytes */
 typedef struct {
   uint64_t seq;
   const void *data;         /* the host slab: valid until dabx_delivery_release(seq) */
@@ -1535,6 +1558,107 @@ int  dabx_cir_rows_device(const float *iq, int n_rows, float *y);
 int  dabx_cir_rows_due(int64_t walk[3], uint64_t wr, int32_t cap, int64_t *first, int32_t *completed);
 /* The trust rule k_cir runs, on the host: 1 = a row whose first sample is `first` may be read. */
 int  dabx_cir_row_trusted(uint64_t first, uint64_t rd, uint64_t horizon, uint64_t ring_len);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * RF spectrum and waterfall: the display that shows whether a carrier is there at all, an adjacent-channel interferer, a tilted passband
+ * or a DC spur -- in lock or not (csrc/spectrum_core.h, k_spectrum; docs/history/spectrum.md).  One opt-in mode, one record per show of
+ * SpectrumViewer::show_spectrum (base/spectrum_viewer/spectrum_viewer.cpp:141-234) with the row WaterfallScope::show_waterfall
+ * (waterfall_scope.cpp:52-79) paints from it.
+ * The capture (base/ofdm/sample_reader.cpp:198-205, :267-272, :285-296): a window is the 2048 consumed samples from W on, behind the DC / IQ
+ * correction where that is on and in front of the NCO.  It is shown at E, the first end of a get_samples call made with iShowSpec == true
+ * -- a single-sample call of the null-symbol search (:96-99) or the read of one of a frame's symbols 1..75 (dab_processor.cpp:321); not
+ * the T_u block in front of the PRS correlation, the rest of symbol 0 (:392, :409), the null symbol (:270) or the 20 T_u reads that seed
+ * the level (:141) -- with E - W > 512 000; the next window starts at E.  While searching E = W + 512 001; in lock E is one of the
+ * symbol ends sym0_end + 2552 j.
+ * The show: the flat-top window (glob_defs.h:252-266, made in double and cast to float), the forward 2048-point transform, per display
+ * bin the mean of |X| over four bins (bin i < 256 from transform bins 1024 + 4 i + j, bin 256 + i from 4 i + j), val = 20 log10f(y / 512 +
+ * 1e-6f), the IIR db += 0.2f (val - db) from 0, the global extrema over the 512 bins and the local ones over bins 64..447 (strict
+ * comparisons from -1000 / +1000), the four limits filtered with alpha = 0.01 / 0.10 / 1.00 from Glob {-30, -90} and Loc {-31, -50},
+ * _calc_spectrum_display_limits (:112-139) on Glob, and on Loc only if Glob changed.  The waterfall: yMax = (Glob.Max + 5)(1 - s) +
+ * Loc.Max s, yMin = Glob.Min (1 - s) + Loc.Min s with s = zoom_percent / 100; no row if yMax - yMin <= 0, otherwise
+ * row[i] = (int)(clamp((db[i] - yMin) / (yMax - yMin), 0, 1) * 255).
+ * k_spectrum stands directly behind the frame head of every front-end step while a stream has the mode on.  It evaluates a window as
+ * soon as its 2048 samples are committed -- under the trust rule of the CIR stage (dabx_cir_row_trusted, the same function), looked at
+ * before and after the loads -- and keeps the result until the schedule says it is shown.  A window that starts at a symbol end of the
+ * frame the head has just begun is read before the receiver reads it; one that starts in a searched range lies behind the read position
+ * and is read only if nothing issued reaches round the ring to it.  A window that is not trusted is not evaluated: its record has
+ * untrusted = 1, db, limits and row as they stood, and the IIR state does not move.
+ * Deviations: the first window starts at the read position at which the mode is switched on (the reference's buffer fills from its last
+ * reset); |X| is sqrtf(re^2 + im^2), not std::abs, which differs only where the squares leave the float range; a NaN db gives row index 0
+ * (the reference's cast of a NaN is undefined); the schedule is taken from what the existing kernels leave -- read position, state, the
+ * frame's symbol-0 position, the count of failed correlations -- so the position of a search candidate whose correlation failed is not
+ * known: a show whose sample W + 512 000 may lie inside such a candidate's T_u block is placed as if it did not, up to 2048 samples
+ * early, and has inexact = 1; while a stream has the mode on the search runs in step, as with cfg.dc_iq_correction.  The x axis, the
+ * colour table and the painting stay with the host; so does the digital level bar. */
+typedef struct {
+  int32_t enable;
+  int32_t averaging;         /* DABX_SPECTRUM_AVR_*: the filter of the four limits, 0 slow (0.01), 1 medium (0.10), 2 fast (1.00) */
+  int32_t zoom_percent;      /* 0..100: the waterfall's scaling slider */
+  int32_t reserved[5];       /* 0 */
+} dabx_spectrum_config;      /* 32 bytes */
+#define DABX_SPECTRUM_AVR_SLOW 0
+#define DABX_SPECTRUM_AVR_MEDIUM 1
+#define DABX_SPECTRUM_AVR_FAST 2
+typedef struct {
+  int64_t frame;             /* frames the stream had decoded at the show */
+  int64_t first_sample;      /* W: the window's first absolute sample position */
+  int32_t untrusted;         /* 1: the window was not evaluated (the trust rule) */
+  int32_t row_valid;         /* 1: `row` is a waterfall row; 0: yMax - yMin <= 0, or untrusted */
+  int32_t inexact;           /* 1: the show position may be up to 2048 samples early (above) */
+  int32_t reserved;
+} dabx_spectrum_record;      /* 32 bytes */
+typedef struct {
+  float glob_max, glob_min, loc_max, loc_min;    /* mSpecViewLimits behind the show */
+  float y_min, y_max;        /* the waterfall's range for the stream's zoom */
+  float reserved[2];
+} dabx_spectrum_limits_rec;  /* 32 bytes: directly behind the record */
+#define DABX_SPECTRUM_BINS 512
+#define DABX_SPECTRUM_SIZE 2048
+#define DABX_SPECTRUM_PERIOD 512000      /* INPUT_RATE / 4 */
+#define DABX_SPECTRUM_RING 8
+#define DABX_SPECTRUM_SLOT_BYTES (32 + 32 + DABX_SPECTRUM_BINS * 4 + DABX_SPECTRUM_BINS)   /* record, limits, db [512] f32, row [512] u8 */
+typedef struct {
+  int64_t shows;             /* records completed */
+  int64_t untrusted;         /* ... of them not evaluated for the trust rule */
+  int64_t lost;              /* records dabx_read_spectrum found gone from the ring of 8 */
+  int64_t launches;          /* steps of the engine that launched the stage's kernel */
+  int64_t inexact;           /* records with inexact = 1 */
+  int64_t reserved[3];
+} dabx_spectrum_stats;       /* 64 bytes */
+/* stream = -1: all streams.  cfg = NULL or enable = 0: off.  The first enable allocates the stage and uploads the window table; an engine
+ * that never enables the mode allocates and launches nothing for it, and with no stream enabled the launch sequence is what it is without
+ * the mode.  Switching a stream on (from off) puts W at its read position and the IIR and the limits at their initial values; changing
+ * averaging or zoom_percent on a running stream keeps the state.  Drains the engine. */
+int  dabx_set_spectrum_mode(dabx_engine *e, int stream, const dabx_spectrum_config *cfg);
+/* The records `stream` completed since the previous call, oldest first, at most max_records: recs [max], limits [max], db [max][512] f32,
+ * row [max][512] u8 (the last three optional).  The device keeps the last 8 per stream; *lost (optional) counts those that had left.
+ * Drains the engine; a cursor of its own.  Returns the number of records. */
+int  dabx_read_spectrum(dabx_engine *e, int stream, int max_records, dabx_spectrum_record *recs, dabx_spectrum_limits_rec *limits, float *db,
+                        uint8_t *row, int32_t *lost);
+/* Any engine; all zeros without the mode (launches is the engine's, the same for every stream). */
+int  dabx_get_spectrum_stats(dabx_engine *e, int stream, dabx_spectrum_stats *out);
+/* spectrum_viewer.cpp:169-218 on crafted windows, no engine: the row function of k_spectrum on n windows of 2048 cf32 samples each
+ * (iq [n][2048] interleaved re, im), one behind the other through ONE display buffer: state [512 + 4] in and out = mDisplayBuffer and the
+ * four extrema {glob max, glob min, loc max, loc min} of the last window (in: ignored); lin [n][512] = mYValVec of each window (the
+ * un-averaged linear values), db [n][512] = mDisplayBuffer behind each window, ext [n][4] (optional) = each window's extrema. */
+int  dabx_spectrum_rows_device(const float *iq, int n, float *state, float *lin, float *db, float *ext);
+/* spectrum_viewer.cpp:220-230 and waterfall_scope.cpp:57-60, the function k_spectrum runs, on the host, no engine and no device:
+ * ext [4] = a show's extrema {glob max, glob min, loc max, loc min}; limits [4] in and out = {Glob.Max, Glob.Min, Loc.Max, Loc.Min};
+ * averaging 0..2, zoom_percent 0..100; y [2] out = {yMin, yMax}.  Returns 1 if the waterfall has a row, 0 if not. */
+int  dabx_spectrum_limits(const float ext[4], float limits[4], int averaging, int zoom_percent, float y[2]);
+/* waterfall_scope.cpp:73-74 on the host: row [n] from db [n] for a range {yMin, yMax} with yMax - yMin > 0. */
+int  dabx_spectrum_waterfall_row(const float *db, int n, const float y[2], uint8_t *row);
+/* The capture schedule k_spectrum runs, on the host: the smallest end E of a show-enabled call with E - W > 512 000 inside one piece of
+ * the receiver's walk, or -1 ("not in here").  kind 0: the searched range [a, b) (single-sample calls, ends a + 1 .. b); kind 1: a frame
+ * whose symbol 0 ends at a (one past its last sample; ends a + 2552 j, j = 1..75; b is ignored). */
+int64_t dabx_spectrum_next_show(uint64_t W, int kind, uint64_t a, uint64_t b);
+/* One look of k_spectrum at a stream, on the host (csrc/spectrum_core.h, spectrum_look): what a front-end step did to the stream, from
+ * what the existing kernels leave behind the frame head.  walk = { W, pos, lost_seen, state_seen } in and out: the window's first
+ * sample, the position up to which the schedule has been evaluated, and the failed-correlation count and state (0 init, 1 searching,
+ * 2 in lock) of the look before.  rd, state, sync_lost: the stream's read position, state and failed-correlation count now; frame_ok,
+ * sym0_pos: whether this step's head has begun a frame, and where the T_u part of its symbol 0 lies.  Returns E (and moves W on to it,
+ * as the kernel does) or -1; *inexact (optional) = 1 if E lies in a searched range in which a candidate's correlation failed. */
+int64_t dabx_spectrum_look(int64_t walk[4], uint64_t rd, int state, int64_t sync_lost, int frame_ok, uint64_t sym0_pos, int32_t *inexact);
 
 /* ------------------------------------------------------------------------------------------------------------
  * MP2 audio:the MP2 decoder of a DAB (MPEG-1/2 Audio Layer II) audio sub-channel on the device -- Mp2Processor's frame assembly and
