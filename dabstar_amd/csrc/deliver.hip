@@ -17,6 +17,7 @@
 #include "scope_core.h"
 #include "cir_core.h"
 #include "spectrum_core.h"
+#include "rec_ring.h"
 #include "fig00.h"
 
 namespace dabx {
@@ -340,140 +341,58 @@ int launch_deliver_front(const EngineDev &e, const DeliverDev &dv, hipStream_t s
   return 0;
 }
 
-// The TII section (include/dabx.h, dabx_chunk_tii; pipeline.h, TiiDeliverDev).  grid = n_streams, 128 threads, front-end stream, behind
-// k_deliver_front -- so behind the k_tii of the chunk's last frame: the events the stream's detector has completed since the previous chunk,
-// the newest 4 of them (a chunk's frames cannot complete more), out of the detector's ring.  Block 0 writes the header's extension.
-__global__ __launch_bounds__(128) void k_deliver_tii(EngineDev e, TiiDeliverDev td)
+// ---- the record sections (include/dabx.h, dabx_chunk_tii / _scope / _cir / _spectrum; pipeline.h, RecDeliverDev) ----------------------------------
+// One block gathers stream s = blockIdx.x's share of a section, with NT threads: the records the stream has written since the previous chunk,
+// the newest CAP of them (what a chunk's frames can complete, and no more than the ring holds), out of the stage's record ring (rec_ring.h)
+// into the stream's slots in the slab, and the stream's row of the section's table.  A stream without room in the slab (rec_off 0) delivers none.
+template <int RING, int SLOT_BYTES, int CAP, int NT> __device__ __forceinline__ void deliver_records(const RecDeliverDev &rd)
 {
+  static_assert(SLOT_BYTES % 16 == 0 && sizeof(dabx_chunk_scope) % 16 == 0, "a record slot is copied in 16-byte words, out of and into 16-aligned slots");
+  constexpr int SLOT_Q = SLOT_BYTES / 16;
   const int s = blockIdx.x, tid = threadIdx.x;
-  constexpr int CAP = 4, SLOT_DW = DABX_TII_EVENT_SLOT_BYTES / 4;
-  if (s == 0 && tid == 0) *reinterpret_cast<dabx_chunk_header_ext *>(td.slab + sizeof(dabx_chunk_header)) = td.ext;
-  const long long total = td.ring ? td.events[(size_t)s * td.cnt_stride] : 0, have = total - td.done[s];
-  int n = (int)(have < CAP ? have : CAP);
-  if (n < 0) n = 0;
-  const long long first = total - n;
-  const unsigned long long ev_off = td.ext.off_tii + (unsigned long long)e.n_streams * sizeof(dabx_chunk_tii) + (unsigned long long)s * CAP * DABX_TII_EVENT_SLOT_BYTES;
-  if (tid == 0) {
-    dabx_chunk_tii r;
-    r.first_event = first; r.n_events = n; r.events_lost = (int)(have > n ? have - n : 0); r.ev_off = ev_off; r.events_total = total;
-    reinterpret_cast<dabx_chunk_tii *>(td.slab + td.ext.off_tii)[s] = r;
-  }
-  uint32_t *o = reinterpret_cast<uint32_t *>(td.slab + ev_off);
-  for (int i = tid; i < n * SLOT_DW; i += 128) {
-    const int k = i / SLOT_DW, wd = i - k * SLOT_DW;
-    o[i] = reinterpret_cast<const uint32_t *>(td.ring + ((size_t)s * TII_RING + (size_t)((first + k) % TII_RING)) * DABX_TII_EVENT_SLOT_BYTES)[wd];
-  }
-  __syncthreads();
-  if (tid == 0) td.done[s] = total;
-}
-
-int launch_deliver_tii(const EngineDev &e, const TiiDeliverDev &td, hipStream_t st)
-{
-  hipLaunchKernelGGL(k_deliver_tii, dim3(e.n_streams), dim3(128), 0, st, e, td);
-  DABX_HIP(hipGetLastError());
-  return 0;
-}
-
-// The scope section (include/dabx.h, dabx_chunk_scope; pipeline.h, ScopeDeliverDev).  grid = n_streams, 256 threads, front-end stream, behind
-// k_deliver_front -- so behind the k_scope of the chunk's last frame, whichever HIP stream ran it (the frame's FIC decoder waits for the
-// demapper launch behind k_scope): the records the stream has written since the previous chunk, the newest DABX_CHUNK_FRAMES of them (a
-// chunk's frames cannot show more), out of the stage's ring.  A stream without room in the slab (rec_off 0) delivers none.
-__global__ __launch_bounds__(256) void k_deliver_scope(EngineDev e, ScopeDeliverDev sd)
-{
-  const int s = blockIdx.x, tid = threadIdx.x;
-  constexpr int CAP = DABX_CHUNK_FRAMES < SCOPE_RING ? DABX_CHUNK_FRAMES : SCOPE_RING, SLOT_Q = SCOPE_SLOT_BYTES / 16;
-  static_assert(SCOPE_SLOT_BYTES % 16 == 0, "a record slot is copied in 16-byte words");
-  const unsigned long long rec_off = sd.rec_off[s];
-  const long long total = sd.ring ? sd.shows[(size_t)s * sd.st_stride] : 0, have = rec_off ? total - sd.done[s] : 0;
-  int n = (int)(have < CAP ? have : CAP);
-  if (n < 0) n = 0;
-  const long long first = total - n;
+  const unsigned long long rec_off = rd.rec_off[s];
+  const long long total = rd.ring ? rd.total[(size_t)s * rd.stride] : 0;
+  const RecWindow w = rec_window(total, rec_off ? rd.done[s] : total, CAP);
   if (tid == 0) {
     dabx_chunk_scope r;
-    r.first_record = first; r.n_records = n; r.records_lost = (int)(have > n ? have - n : 0); r.rec_off = rec_off; r.records_total = total;
-    reinterpret_cast<dabx_chunk_scope *>(sd.slab + sd.off_scope)[s] = r;
+    r.first_record = w.first; r.n_records = w.n; r.records_lost = (int)w.gone; r.rec_off = rec_off; r.records_total = total;
+    reinterpret_cast<dabx_chunk_scope *>(rd.slab + rd.off_table)[s] = r;
   }
-  uint4 *o = reinterpret_cast<uint4 *>(sd.slab + rec_off);
-  for (int i = tid; i < n * SLOT_Q; i += 256) {
+  uint4 *o = reinterpret_cast<uint4 *>(rd.slab + rec_off);
+  for (int i = tid; i < w.n * SLOT_Q; i += NT) {
     const int k = i / SLOT_Q, wd = i - k * SLOT_Q;
-    o[i] = reinterpret_cast<const uint4 *>(sd.ring + ((size_t)s * SCOPE_RING + (size_t)((first + k) % SCOPE_RING)) * SCOPE_SLOT_BYTES)[wd];
+    o[i] = reinterpret_cast<const uint4 *>(rec_slot<RING, SLOT_BYTES>(rd.ring, s, w.first + k))[wd];
   }
   __syncthreads();
-  if (tid == 0) sd.done[s] = total;
+  if (tid == 0) rd.done[s] = total;
 }
 
-int launch_deliver_scope(const EngineDev &e, const ScopeDeliverDev &sd, hipStream_t st)
+// grid = n_streams, 256 threads, front-end stream, behind k_deliver_front and the header's extension -- so behind the chunk's last k_scope
+// (whichever HIP stream ran it: the frame's FIC decoder waits for the demapper launch behind k_scope), k_cir_finish and k_cir_corr, and
+// k_spectrum, which run on that stream
+template <int RING, int SLOT_BYTES, int CHUNK_RECORDS> __global__ __launch_bounds__(256) void k_deliver_records(RecDeliverDev rd)
 {
-  hipLaunchKernelGGL(k_deliver_scope, dim3(e.n_streams), dim3(256), 0, st, e, sd);
-  DABX_HIP(hipGetLastError());
-  return 0;
+  deliver_records<RING, SLOT_BYTES, (CHUNK_RECORDS < RING ? CHUNK_RECORDS : RING), 256>(rd);
 }
 
-// The CIR section (include/dabx.h, dabx_chunk_cir; pipeline.h, CirDeliverDev).  grid = n_streams, 256 threads, front-end stream, behind k_deliver_front -- so behind the k_cir_finish and
-// k_cir_corr of the chunk's last frame, which run on that stream: the records of both kinds the stream has completed since the previous
-// chunk, the newest DABX_CIR_CHUNK_RECORDS of them, out of the stage's ring.  A stream without room in the slab (rec_off 0) delivers none.
-__global__ __launch_bounds__(256) void k_deliver_cir(CirDeliverDev sd)
+// The TII section: grid = n_streams, 128 threads, front-end stream, behind k_deliver_front -- so behind the k_tii of the chunk's last frame;
+// 4 events at the most (a chunk's frames cannot complete more), and every stream has room.  Block 0 writes the header's extension.
+__global__ __launch_bounds__(128) void k_deliver_tii(RecDeliverDev rd, dabx_chunk_header_ext ext)
 {
-  const int s = blockIdx.x, tid = threadIdx.x;
-  constexpr int CAP = DABX_CIR_CHUNK_RECORDS < CIR_RING ? DABX_CIR_CHUNK_RECORDS : CIR_RING, SLOT_Q = CIR_SLOT_BYTES / 16;
-  static_assert(CIR_SLOT_BYTES % 16 == 0, "a record slot is copied in 16-byte words");
-  const unsigned long long rec_off = sd.rec_off[s];
-  const long long total = sd.ring ? sd.shows[(size_t)s * sd.st_stride] : 0, have = rec_off ? total - sd.done[s] : 0;
-  int n = (int)(have < CAP ? have : CAP);
-  if (n < 0) n = 0;
-  const long long first = total - n;
-  if (tid == 0) {
-    dabx_chunk_cir r;
-    r.first_record = first; r.n_records = n; r.records_lost = (int)(have > n ? have - n : 0); r.rec_off = rec_off; r.records_total = total;
-    reinterpret_cast<dabx_chunk_cir *>(sd.slab + sd.off_cir)[s] = r;
+  if (blockIdx.x == 0 && threadIdx.x == 0) *reinterpret_cast<dabx_chunk_header_ext *>(rd.slab + sizeof(dabx_chunk_header)) = ext;
+  deliver_records<TII_RING, TII_SLOT_BYTES, 4, 128>(rd);
+}
+
+int launch_deliver_records(int section, int n_streams, const RecDeliverDev &rd, const dabx_chunk_header_ext &ext, hipStream_t st)
+{
+  const dim3 grid(n_streams), nt(256);
+  switch (section) {
+  case REC_TII: hipLaunchKernelGGL(k_deliver_tii, grid, dim3(128), 0, st, rd, ext); break;
+  case REC_SCOPE: hipLaunchKernelGGL((k_deliver_records<SCOPE_RING, SCOPE_SLOT_BYTES, DABX_CHUNK_FRAMES>), grid, nt, 0, st, rd); break;
+  case REC_CIR: hipLaunchKernelGGL((k_deliver_records<CIR_RING, CIR_SLOT_BYTES, DABX_CIR_CHUNK_RECORDS>), grid, nt, 0, st, rd); break;
+  case REC_SPECTRUM: hipLaunchKernelGGL((k_deliver_records<SPEC_RING, SPEC_SLOT_BYTES, DABX_SPECTRUM_CHUNK_RECORDS>), grid, nt, 0, st, rd); break;
+  default: set_error("launch_deliver_records: section %d", section); return DABX_E_ARG;
   }
-  uint4 *o = reinterpret_cast<uint4 *>(sd.slab + rec_off);
-  for (int i = tid; i < n * SLOT_Q; i += 256) {
-    const int k = i / SLOT_Q, wd = i - k * SLOT_Q;
-    o[i] = reinterpret_cast<const uint4 *>(sd.ring + ((size_t)s * CIR_RING + (size_t)((first + k) % CIR_RING)) * CIR_SLOT_BYTES)[wd];
-  }
-  __syncthreads();
-  if (tid == 0) sd.done[s] = total;
-}
-
-int launch_deliver_cir(int n_streams, const CirDeliverDev &sd, hipStream_t st)
-{
-  hipLaunchKernelGGL(k_deliver_cir, dim3(n_streams), dim3(256), 0, st, sd);
-  DABX_HIP(hipGetLastError());
-  return 0;
-}
-
-// The spectrum section (include/dabx.h, dabx_chunk_spectrum; pipeline.h, SpecDeliverDev).  grid = n_streams, 256 threads, front-end stream, behind
-// k_deliver_front -- so behind the k_spectrum of the chunk's last frame, which runs on that stream: the records the stream has completed since
-// the previous chunk, the newest DABX_SPECTRUM_CHUNK_RECORDS of them, out of the stage's ring.  A stream without room in the slab (rec_off 0)
-// delivers none.
-__global__ __launch_bounds__(256) void k_deliver_spectrum(SpecDeliverDev sd)
-{
-  const int s = blockIdx.x, tid = threadIdx.x;
-  constexpr int CAP = DABX_SPECTRUM_CHUNK_RECORDS < SPEC_RING ? DABX_SPECTRUM_CHUNK_RECORDS : SPEC_RING, SLOT_Q = SPEC_SLOT_BYTES / 16;
-  static_assert(SPEC_SLOT_BYTES % 16 == 0, "a record slot is copied in 16-byte words");
-  const unsigned long long rec_off = sd.rec_off[s];
-  const long long total = sd.ring ? sd.shows[(size_t)s * sd.st_stride] : 0, have = rec_off ? total - sd.done[s] : 0;
-  int n = (int)(have < CAP ? have : CAP);
-  if (n < 0) n = 0;
-  const long long first = total - n;
-  if (tid == 0) {
-    dabx_chunk_spectrum r;
-    r.first_record = first; r.n_records = n; r.records_lost = (int)(have > n ? have - n : 0); r.rec_off = rec_off; r.records_total = total;
-    reinterpret_cast<dabx_chunk_spectrum *>(sd.slab + sd.off_spectrum)[s] = r;
-  }
-  uint4 *o = reinterpret_cast<uint4 *>(sd.slab + rec_off);
-  for (int i = tid; i < n * SLOT_Q; i += 256) {
-    const int k = i / SLOT_Q, wd = i - k * SLOT_Q;
-    o[i] = reinterpret_cast<const uint4 *>(sd.ring + ((size_t)s * SPEC_RING + (size_t)((first + k) % SPEC_RING)) * SPEC_SLOT_BYTES)[wd];
-  }
-  __syncthreads();
-  if (tid == 0) sd.done[s] = total;
-}
-
-int launch_deliver_spectrum(int n_streams, const SpecDeliverDev &sd, hipStream_t st)
-{
-  hipLaunchKernelGGL(k_deliver_spectrum, dim3(n_streams), dim3(256), 0, st, sd);
   DABX_HIP(hipGetLastError());
   return 0;
 }

@@ -11,11 +11,13 @@
 #include "scope_core.h"
 #include "cir_core.h"
 #include "spectrum_core.h"
+#include "rec_ring.h"
 #include "sdma.h"
 #include "iqfile.h"
 #include <algorithm>
 #include <condition_variable>
 #include <deque>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -66,25 +68,23 @@ struct Delivery {
   long long *eti_next = nullptr;
   EtiStage *eti_stage[NDEV] = {nullptr, nullptr, nullptr};
   size_t eti_rows_off = 0;
-  // DABX_DELIVER_TII (deliver.hip, k_deliver_tii): the header's extension as it goes into a slab, the section's cursor per stream; zeros / null without the bit
-  dabx_chunk_header_ext ext{};
-  long long *tii_done = nullptr;
-  // DABX_DELIVER_SCOPE (deliver.hip, k_deliver_scope): the section's cursor per stream, where each stream's record slots lie in a slab (device
-  // and host; 0 = the stream's mode was off when the delivery was opened: no room); null / empty without the bit
-  long long *scope_done = nullptr;
-  unsigned long long *scope_off = nullptr;
-  std::vector<char> scope_room;                  // [S] the stream had the mode on when the delivery was opened
-  bool scope() const { return (what & DABX_DELIVER_SCOPE) != 0; }
-  // DABX_DELIVER_CIR (deliver.hip, k_deliver_cir): the same three for the CIR section
-  long long *cir_done = nullptr;
-  unsigned long long *cir_off = nullptr;
-  std::vector<char> cir_room;
-  bool cir() const { return (what & DABX_DELIVER_CIR) != 0; }
-  // DABX_DELIVER_SPECTRUM (deliver.hip, k_deliver_spectrum): the same three for the spectrum section
-  long long *spec_done = nullptr;
-  unsigned long long *spec_off = nullptr;
-  std::vector<char> spec_room;
-  bool spectrum() const { return (what & DABX_DELIVER_SPECTRUM) != 0; }
+  // The sections of fixed-size records (rec_ring.h; deliver.hip, k_deliver_tii and k_deliver_records), in the order they are gathered: a table of
+  // one 32-byte row per stream at the extension's word, behind it chunk_records slots for every stream that has room.  done / off are null
+  // and room is empty without the section's bit.
+  struct RecSection {
+    int bit;                                     // DABX_DELIVER_*
+    int chunk_records, slot_bytes;               // the most a chunk delivers per stream
+    uint64_t dabx_chunk_header_ext::*off_word;   // the word of the header's extension that announces the section
+    long long *done = nullptr;                   // [S] device: records of the stream delivered or passed so far
+    unsigned long long *off = nullptr;           // [S] device: where the stream's slots lie in a slab, 0 = it has no room
+    std::vector<char> room;                      // [S] the stream had the mode on when the delivery was opened (TII: every stream)
+  };
+  RecSection rec[N_REC_SECTIONS] = {
+    {DABX_DELIVER_TII, 4, DABX_TII_EVENT_SLOT_BYTES, &dabx_chunk_header_ext::off_tii},
+    {DABX_DELIVER_SCOPE, DL_FRAMES, SCOPE_SLOT_BYTES, &dabx_chunk_header_ext::off_scope},
+    {DABX_DELIVER_CIR, DABX_CIR_CHUNK_RECORDS, CIR_SLOT_BYTES, &dabx_chunk_header_ext::off_cir},
+    {DABX_DELIVER_SPECTRUM, DABX_SPECTRUM_CHUNK_RECORDS, SPEC_SLOT_BYTES, &dabx_chunk_header_ext::off_spectrum}};
+  dabx_chunk_header_ext ext{};                   // the header's extension as it goes into a slab; zeros without a bit >= 256
   bool tii() const { return (what & DABX_DELIVER_TII) != 0; }
   bool mp2_audio() const { return (what & DABX_DELIVER_MP2_AUDIO) != 0; }      // the MP2 audio section (deliver.hip, k_deliver_mp2_audio), while a slot has the mode on
   bool aac() const { return (what & DABX_DELIVER_AAC) != 0; }      // the AAC section (deliver.hip, k_deliver_aac), while a slot has the mode on
@@ -175,6 +175,43 @@ template <class Slot, class Dev> struct JobTable {
   }
 };
 
+// ---- what the stages with a record ring (rec_ring.h) share --------------------------------------------------------------------------------
+inline void hip_free_all(std::initializer_list<void *> ptrs) { for (void *q : ptrs) if (q) (void)hipFree(q); }
+
+// Every buffer of the table allocated and zeroed, or none of them: after a failure the pointers are null again, the error is set in the
+// name of `who` and the return is DABX_E_NOMEM (out of memory) or DABX_E_HIP.
+struct DevBuf { void **p; size_t bytes; };
+inline int alloc_zeroed(const char *who, std::initializer_list<DevBuf> bufs)
+{
+  for (const DevBuf &b : bufs) *b.p = nullptr;
+  for (const DevBuf &b : bufs) {
+    hipError_t he = hipMalloc(b.p, b.bytes);
+    if (he == hipSuccess) he = hipMemset(*b.p, 0, b.bytes);
+    if (he == hipSuccess) continue;
+    set_error("%s: HIP error %d (%s) allocating the stage", who, (int)he, hipGetErrorString(he));
+    for (const DevBuf &q : bufs) { if (*q.p) (void)hipFree(*q.p); *q.p = nullptr; }
+    return he == hipErrorOutOfMemory ? DABX_E_NOMEM : DABX_E_HIP;
+  }
+  return 0;
+}
+
+// One dabx_read_* call on a stream's ring: what the ring has overwritten since the last call is dropped and counted (*lost: this call's,
+// *lost_total: the stage's running total, where it keeps one), then up to max_records records go through copy(n, slot), oldest first.
+// total: the stream's record counter, just read from the device; seen: the records earlier calls have returned or passed.
+template <int RING, int SLOT_BYTES, class CopySlot>
+int rec_ring_read(const uint8_t *ring, int stream, long long total, long long &seen, long long *lost_total, int max_records, int32_t *lost, CopySlot copy)
+{
+  if (const long long gone = rec_window(total, seen, RING).gone) {
+    if (lost) *lost = (int32_t)std::min<long long>(gone, INT32_MAX);
+    if (lost_total) *lost_total += gone;
+    seen += gone;
+  }
+  int n = 0;
+  for (; n < max_records && seen < total; n++, seen++)
+    if (int rc = copy(n, rec_slot<RING, SLOT_BYTES>(ring, stream, seen))) return rc;
+  return n;
+}
+
 // The TII stage (include/dabx.h dabx_set_tii_mode, deliver.hip k_tii).  Nothing of it exists until the mode is first switched on: dev stays all
 // null, n_on stays 0 and no step launches the kernel.
 struct TiiStage {
@@ -187,46 +224,47 @@ struct TiiStage {
   bool exists() const { return dev.pairs != nullptr; }
 };
 
-// The scope stage (include/dabx.h dabx_set_scope_mode, pipeline.hip k_scope).  Nothing of it exists until the mode is first switched on: dev
-// stays all null, n_on stays 0 and no step launches the kernel.
-struct ScopeStage {
-  ScopeDev dev{};
-  int32_t *list = nullptr;                     // [S] device: the first n_on entries are the streams with the mode on (ScopeDev::list)
-  ScopeCfgDev *cfg_dev = nullptr;              // [S] (ScopeDev::cfg)
+// What the scope, the CIR and the spectrum stage share: the streams with the mode on as a compacted list for the stage's kernels (one block
+// each), a settings row per stream and the read-out's bookkeeping.  Nothing of a stage exists until its mode is first switched on: its dev
+// stays all null, n_on stays 0 and no step launches a kernel of it.
+template <class Cfg> struct ListedStage {
+  int32_t *list = nullptr;                     // [S] device: the first n_on entries are the streams with the mode on
+  Cfg *cfg_dev = nullptr;                      // [S] device
   int n_on = 0;
-  std::vector<ScopeCfgDev> cfg;                // [S] mirror of cfg_dev
-  std::vector<long long> seen, lost;           // [S] records dabx_read_scope has returned or passed / found gone
+  std::vector<Cfg> cfg;                        // [S] mirror of cfg_dev
+  std::vector<long long> seen, lost;           // [S] records the stage's dabx_read_* has returned or passed / found gone
   long long launches = 0;
-  bool exists() const { return dev.ring != nullptr; }
+  bool exists() const { return list != nullptr; }
+  // the settings and the list rebuilt from them, to the device (with the engine drained); *dev_n: the length the stage's kernels go by
+  int upload(int32_t *dev_n)
+  {
+    std::vector<int32_t> on;
+    for (size_t s = 0; s < cfg.size(); s++) if (cfg[s].enable) on.push_back((int32_t)s);
+    DABX_HIP(hipMemcpy(cfg_dev, cfg.data(), sizeof(Cfg) * cfg.size(), hipMemcpyHostToDevice));
+    if (!on.empty()) DABX_HIP(hipMemcpy(list, on.data(), sizeof(int32_t) * on.size(), hipMemcpyHostToDevice));
+    n_on = *dev_n = (int)on.size();
+    return 0;
+  }
+  void start(size_t S) { cfg.assign(S, Cfg{}); seen.assign(S, 0); lost.assign(S, 0); }     // (a stage that was just created)
 };
 
-// The CIR / correlation plot stage (include/dabx.h dabx_set_cir_mode, pipeline.hip k_cir, k_cir_finish, k_cir_corr).  Nothing of it exists until
-// the mode is first switched on: dev stays all null, n_on stays 0 and no step launches a kernel of it.
-struct CirStage {
+// The scope stage (include/dabx.h dabx_set_scope_mode, pipeline.hip k_scope)
+struct ScopeStage : ListedStage<ScopeCfgDev> {
+  ScopeDev dev{};
+};
+
+// The CIR / correlation plot stage (include/dabx.h dabx_set_cir_mode, pipeline.hip k_cir, k_cir_finish, k_cir_corr)
+struct CirStage : ListedStage<CirCfgDev> {
   CirDev dev{};
-  int32_t *list = nullptr;                     // [S] device: the first n_on entries are the streams with the mode on (CirDev::list)
-  CirCfgDev *cfg_dev = nullptr;                // [S] (CirDev::cfg)
-  int n_on = 0, n_corr = 0;                    // streams with the mode on / with the correlation plot on
-  std::vector<CirCfgDev> cfg;                  // [S] mirror of cfg_dev
+  int n_corr = 0;                              // streams with the correlation plot on
   std::vector<CirState> walk;                  // [S] the host's own window / row bookkeeping (base, win, rows_done): the same function over the same
                                                //     wr as the device's, so that a step launches as many blocks per stream as rows are due
-  std::vector<long long> seen, lost;           // [S] records dabx_read_cir has returned or passed / found gone
-  long long launches = 0;
-  bool exists() const { return dev.ring != nullptr; }
 };
 
-// The RF spectrum / waterfall stage (include/dabx.h dabx_set_spectrum_mode, pipeline.hip k_spectrum).  Nothing of it exists until the mode is
-// first switched on: dev stays all null, n_on stays 0 and no step launches a kernel of it.
-struct SpecStage {
+// The RF spectrum / waterfall stage (include/dabx.h dabx_set_spectrum_mode, pipeline.hip k_spectrum)
+struct SpecStage : ListedStage<SpecCfgDev> {
   SpecDev dev{};
-  int32_t *list = nullptr;                     // [S] device: the first n_on entries are the streams with the mode on (SpecDev::list)
-  SpecCfgDev *cfg_dev = nullptr;               // [S] (SpecDev::cfg)
   float *window = nullptr;                     // [2048] device (SpecDev::window)
-  int n_on = 0;                                // streams with the mode on
-  std::vector<SpecCfgDev> cfg;                 // [S] mirror of cfg_dev
-  std::vector<long long> seen, lost;           // [S] records dabx_read_spectrum has returned or passed / found gone
-  long long launches = 0;
-  bool exists() const { return dev.ring != nullptr; }
 };
 
 struct dabx_engine : dabx::EngineHead {         // (iqfile.h: the ring format, where iqfile.cpp can read it)
@@ -341,4 +379,15 @@ void spectrum_stage_free(dabx_engine *e);
 void pad_count_sources(dabx_engine *e);
 int mot_follow_pad(dabx_engine *e);
 int carousel_follow_packet(dabx_engine *e);
+
+// How the dabx_read_* and dabx_get_*_stats entries of a ListedStage begin: the engine drained, the stream's state record read from the
+// device.  0: *c holds it; 1: the stage does not exist (nothing to read: the entry returns 0); < 0: the error to return.
+template <class Stage, class State> int stage_state(dabx_engine *e, const Stage &T, int stream, State *c)
+{
+  if (int rc = use_device(e)) return rc;
+  if (int rc = sync_all(e)) return rc;
+  if (!T.exists()) return 1;
+  DABX_HIP(hipMemcpy(c, T.dev.st + stream, sizeof(*c), hipMemcpyDeviceToHost));
+  return 0;
+}
 }  // namespace dabx

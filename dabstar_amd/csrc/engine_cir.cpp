@@ -1,8 +1,8 @@
 // engine_cir.cpp -- the channel impulse response and the correlation plot on the device (include/dabx.h dabx_set_cir_mode; cir_core.h,
-// pipeline.hip k_cir / k_cir_finish / k_cir_corr): the stage's memory, its per-stream settings and compacted stream list, the host's copy of
-// the window / row bookkeeping that sizes a step's launch, the record read-out, the counters and the host-callable entries.  The records of
-// both kinds lie in one ring of CIR_RING fixed-size slots per stream, indexed by the stream's record count, read out as engine_scope.cpp
-// reads the scope's.
+// pipeline.hip k_cir / k_cir_finish / k_cir_corr): the stage's memory, what a stream's settings may be and what a fresh enable resets, the
+// host's copy of the window / row bookkeeping that sizes a step's launch, the parts of a record that dabx_read_cir copies, the counters and
+// the host-callable entries.  The records of both kinds lie in one record ring (rec_ring.h) of CIR_RING slots per stream, indexed by the
+// stream's record count.
 #include "engine.h"
 #include <cstring>
 
@@ -17,7 +17,7 @@ namespace dabx {
 void cir_stage_free(dabx_engine *e)
 {
   CirStage &T = e->cir;
-  for (void *q : {(void *)T.list, (void *)T.cfg_dev, (void *)T.dev.st, (void *)T.dev.acc, (void *)T.dev.mean, (void *)T.dev.ring}) if (q) (void)hipFree(q);
+  hip_free_all({T.list, T.cfg_dev, T.dev.st, T.dev.acc, T.dev.mean, T.dev.ring});
   T = CirStage{};
 }
 
@@ -26,23 +26,13 @@ static int cir_stage_create(dabx_engine *e)
 {
   CirStage &T = e->cir;
   const size_t S = (size_t)e->dev.n_streams;
-  const struct { void **p; size_t n; } bufs[] = {{(void **)&T.list, sizeof(int32_t) * S}, {(void **)&T.cfg_dev, sizeof(CirCfgDev) * S},
-                                                {(void **)&T.dev.st, sizeof(CirState) * S}, {(void **)&T.dev.acc, sizeof(float) * CIR_ROWS * S},
-                                                {(void **)&T.dev.mean, sizeof(float) * TU * S}, {(void **)&T.dev.ring, (size_t)CIR_RING * CIR_SLOT_BYTES * S}};
-  for (const auto &b : bufs) {
-    hipError_t he = hipMalloc(b.p, b.n);
-    if (he == hipSuccess) he = hipMemset(*b.p, 0, b.n);
-    if (he != hipSuccess) {
-      set_error("dabx_set_cir_mode: HIP error %d (%s) allocating the stage", (int)he, hipGetErrorString(he));
-      cir_stage_free(e);
-      return he == hipErrorOutOfMemory ? DABX_E_NOMEM : DABX_E_HIP;
-    }
-  }
+  if (int rc = alloc_zeroed("dabx_set_cir_mode", {{(void **)&T.list, sizeof(int32_t) * S}, {(void **)&T.cfg_dev, sizeof(CirCfgDev) * S},
+                                                  {(void **)&T.dev.st, sizeof(CirState) * S}, {(void **)&T.dev.acc, sizeof(float) * CIR_ROWS * S},
+                                                  {(void **)&T.dev.mean, sizeof(float) * TU * S}, {(void **)&T.dev.ring, (size_t)CIR_RING * CIR_SLOT_BYTES * S}}))
+    return rc;
   T.dev.list = T.list; T.dev.cfg = T.cfg_dev; T.dev.n = T.dev.n_corr = 0;
-  T.cfg.assign(S, CirCfgDev{});
+  T.start(S);
   T.walk.assign(S, CirState{});
-  T.seen.assign(S, 0);
-  T.lost.assign(S, 0);
   return 0;
 }
 
@@ -101,14 +91,11 @@ int dabx_set_cir_mode(dabx_engine *e, int stream, const dabx_cir_config *cfg)
       DABX_HIP(hipMemset(T.dev.mean + (size_t)s * TU, 0, sizeof(float) * TU));
     }
   }
-  std::vector<int32_t> list;
   int n_corr = 0;
-  for (int s = 0; s < e->dev.n_streams; s++) if (T.cfg[(size_t)s].enable) { list.push_back(s); n_corr += T.cfg[(size_t)s].correlation; }
+  for (const CirCfgDev &c : T.cfg) n_corr += c.enable ? c.correlation : 0;
   DABX_HIP(hipMemcpy(T.dev.st, st.data(), sizeof(CirState) * S, hipMemcpyHostToDevice));
-  DABX_HIP(hipMemcpy(T.cfg_dev, T.cfg.data(), sizeof(CirCfgDev) * S, hipMemcpyHostToDevice));
-  if (!list.empty()) DABX_HIP(hipMemcpy(T.list, list.data(), sizeof(int32_t) * list.size(), hipMemcpyHostToDevice));
+  if ((rc = T.upload(&T.dev.n))) return rc;
   T.walk = st;                                            // the engine is drained: the device's bookkeeping is the host's
-  T.n_on = T.dev.n = (int)list.size();
   T.n_corr = T.dev.n_corr = n_corr;
   return 0;
 }
@@ -117,40 +104,25 @@ int dabx_read_cir(dabx_engine *e, int stream, int max_records, dabx_cir_record *
 {
   if (!e || stream < 0 || stream >= e->dev.n_streams || max_records < 0 || (max_records > 0 && !recs)) { set_error("dabx_read_cir: bad argument"); return DABX_E_ARG; }
   if (lost) *lost = 0;
-  if (int rc = use_device(e)) return rc;
-  if (int rc = sync_all(e)) return rc;
   CirStage &T = e->cir;
-  if (!T.exists()) return 0;
   CirState c;
-  DABX_HIP(hipMemcpy(&c, T.dev.st + stream, sizeof(c), hipMemcpyDeviceToHost));
-  long long &seen = T.seen[(size_t)stream];
-  if (c.shows - seen > CIR_RING) {
-    const long long gone = c.shows - seen - CIR_RING;
-    if (lost) *lost = (int32_t)std::min<long long>(gone, INT32_MAX);
-    T.lost[(size_t)stream] += gone;
-    seen = c.shows - CIR_RING;
-  }
-  int n = 0;
-  while (n < max_records && seen < c.shows) {
-    const uint8_t *slot = T.dev.ring + ((size_t)stream * CIR_RING + (size_t)(seen % CIR_RING)) * CIR_SLOT_BYTES;
+  if (int rc = stage_state(e, T, stream, &c)) return std::min(rc, 0);
+  return rec_ring_read<CIR_RING, CIR_SLOT_BYTES>(T.dev.ring, stream, c.shows, T.seen[(size_t)stream], &T.lost[(size_t)stream], max_records, lost,
+                                                  [&](int n, const uint8_t *slot) {
     DABX_HIP(hipMemcpy(recs + n, slot, sizeof(dabx_cir_record), hipMemcpyDeviceToHost));
     if (values) DABX_HIP(hipMemcpy(values + (size_t)n * CIR_CORR_LAGS, slot + 32, sizeof(float) * CIR_CORR_LAGS, hipMemcpyDeviceToHost));
     if (indices) DABX_HIP(hipMemcpy(indices + (size_t)n * CIR_INDEX_ROOM, slot + 32 + CIR_CORR_LAGS * 4, sizeof(int16_t) * CIR_INDEX_ROOM, hipMemcpyDeviceToHost));
-    n++; seen++;
-  }
-  return n;
+    return 0;
+  });
 }
 
 int dabx_get_cir_stats(dabx_engine *e, int stream, dabx_cir_stats *out)
 {
   if (!e || stream < 0 || stream >= e->dev.n_streams || !out) { set_error("dabx_get_cir_stats: bad argument"); return DABX_E_ARG; }
   memset(out, 0, sizeof(*out));
-  if (int rc = use_device(e)) return rc;
-  if (int rc = sync_all(e)) return rc;
   const CirStage &T = e->cir;
-  if (!T.exists()) return 0;
   CirState c;
-  DABX_HIP(hipMemcpy(&c, T.dev.st + stream, sizeof(c), hipMemcpyDeviceToHost));
+  if (int rc = stage_state(e, T, stream, &c)) return std::min(rc, 0);
   out->shows[0] = c.shows_kind[0]; out->shows[1] = c.shows_kind[1]; out->lost = T.lost[(size_t)stream];
   out->rows_untrusted = c.rows_untrusted; out->launches = T.launches;
   return 0;

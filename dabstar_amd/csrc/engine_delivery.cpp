@@ -20,6 +20,33 @@ static constexpr int DL_SF_CAP = (4 * DL_FRAMES + 4) / 5;          // super fram
 #if DABX_MSC_BATCH == 7
 static_assert(DL_FRAMES == DABX_CHUNK_FRAMES, "include/dabx.h: DABX_CHUNK_FRAMES is the library's MSC batch");
 #endif
+// the record sections (engine.h, Delivery::rec): a row of a section's table (pipeline.h: the four are one layout); the gather copies 16-byte words
+static constexpr size_t rec_row_bytes = sizeof(dabx_chunk_scope);
+static_assert(rec_row_bytes % 16 == 0 && DABX_TII_EVENT_SLOT_BYTES % 16 == 0 && SCOPE_SLOT_BYTES % 16 == 0 && CIR_SLOT_BYTES % 16 == 0 && SPEC_SLOT_BYTES % 16 == 0,
+              "a record section's slots are 16-aligned");
+
+// What a record section gathers from (RecDeliverDev::ring, ::total, ::stride): all null / 0 while the engine has no such stage
+struct RecSource { const uint8_t *ring; const long long *total; int32_t stride; };
+static RecSource rec_source(const dabx_engine *e, int section)
+{
+  switch (section) {
+  case REC_TII: if (e->tiis.exists()) return {e->tiis.dev.ring, &e->tiis.dev.cnt->events, (int32_t)(sizeof(TiiCounters) / sizeof(long long))}; break;
+  case REC_SCOPE: if (e->scope.exists()) return {e->scope.dev.ring, &e->scope.dev.st->shows, (int32_t)(sizeof(ScopeState) / sizeof(long long))}; break;
+  case REC_CIR: if (e->cir.exists()) return {e->cir.dev.ring, &e->cir.dev.st->shows, (int32_t)(sizeof(CirState) / sizeof(long long))}; break;
+  case REC_SPECTRUM: if (e->spectrum.exists()) return {e->spectrum.dev.ring, &e->spectrum.dev.st->shows, (int32_t)(sizeof(SpecState) / sizeof(long long))}; break;
+  }
+  return {nullptr, nullptr, 0};
+}
+// ... and whether stream s gets room in the section: it has the stage's mode on (a TII event is small: every stream has room)
+static bool rec_stream_on(const dabx_engine *e, int section, size_t s)
+{
+  switch (section) {
+  case REC_SCOPE: return e->scope.exists() && e->scope.cfg[s].enable;
+  case REC_CIR: return e->cir.exists() && e->cir.cfg[s].enable;
+  case REC_SPECTRUM: return e->spectrum.exists() && e->spectrum.cfg[s].enable;
+  }
+  return true;
+}
 
 // One section of the slab's head part for the slots of a job table: its table of S * M records at *off_table, then every slot's records and
 // bytes, as much as one batch can emit (the caps of its ring).  Without such a slot, or unwanted: no section, the slots' offsets stay 0.
@@ -91,36 +118,22 @@ int dabx_engine::delivery_layout()
   off = layout_section(car, D.want_mot && !d.fic_only, off, S * M * sizeof(dabx_chunk_mot), &h.off_mot);     // ... with the rooms of the carousel slots
   if (h.off_mot) h.what |= DABX_DELIVER_MOT;
   if (D.eti()) { off = align_up(off, 16); h.off_eti = off; off += S * sizeof(dabx_chunk_eti); }     // the ETI section's table (its rows: the slab's end)
-  // the TII section: its table and 4 event slots per stream
-  if (D.tii()) { off = align_up(off, 16); x.off_tii = off; off += S * (sizeof(dabx_chunk_tii) + 4 * (size_t)DABX_TII_EVENT_SLOT_BYTES); }
+  // a record section: its table, then chunk_records slots for every stream that has room (all 16-aligned: the static_assert at rec_row_bytes)
+  auto layout_records = [&](Delivery::RecSection &r) -> int {
+    if (!(D.what & r.bit)) return 0;
+    off = align_up(off, 16); x.*r.off_word = off; off += S * rec_row_bytes;
+    std::vector<unsigned long long> so(S, 0);
+    for (size_t s_ = 0; s_ < S; s_++)
+      if (r.room[s_]) { so[s_] = off; off += (size_t)r.chunk_records * r.slot_bytes; }
+    DABX_HIP(hipMemcpy(r.off, so.data(), sizeof(unsigned long long) * S, hipMemcpyHostToDevice));
+    return 0;
+  };
+  if (int rc = layout_records(D.rec[REC_TII])) return rc;
   // the MP2 audio section (dabx_chunk_mp2_audio): with the bit and a slot that has the mode on
   off = layout_section(mpa, D.mp2_audio() && !d.fic_only, off, S * M * sizeof(dabx_chunk_mp2_audio), &x.off_mp2_audio);
   // ... and the AAC section (dabx_chunk_aac), in the same way
   off = layout_section(aac, D.aac() && !d.fic_only, off, S * M * sizeof(dabx_chunk_aac), &x.off_aac);
-  // the scope section: its table, then DL_FRAMES record slots for every stream that had the mode on when the delivery was opened
-  if (D.scope()) {
-    off = align_up(off, 16); x.off_scope = off; off += S * sizeof(dabx_chunk_scope);
-    std::vector<unsigned long long> so(S, 0);
-    for (size_t s_ = 0; s_ < S; s_++)
-      if (D.scope_room[s_]) { so[s_] = off; off += (size_t)DL_FRAMES * SCOPE_SLOT_BYTES; }
-    DABX_HIP(hipMemcpy(D.scope_off, so.data(), sizeof(unsigned long long) * S, hipMemcpyHostToDevice));
-  }
-  // the CIR section: its table, then DABX_CIR_CHUNK_RECORDS record slots for every stream that had the mode on when the delivery was opened
-  if (D.cir()) {
-    off = align_up(off, 16); x.off_cir = off; off += S * sizeof(dabx_chunk_cir);
-    std::vector<unsigned long long> so(S, 0);
-    for (size_t s_ = 0; s_ < S; s_++)
-      if (D.cir_room[s_]) { so[s_] = off; off += (size_t)DABX_CIR_CHUNK_RECORDS * CIR_SLOT_BYTES; }
-    DABX_HIP(hipMemcpy(D.cir_off, so.data(), sizeof(unsigned long long) * S, hipMemcpyHostToDevice));
-  }
-  // the spectrum section: its table, then DABX_SPECTRUM_CHUNK_RECORDS record slots for every stream that had the mode on when the delivery was opened
-  if (D.spectrum()) {
-    off = align_up(off, 16); x.off_spectrum = off; off += S * sizeof(dabx_chunk_spectrum);
-    std::vector<unsigned long long> so(S, 0);
-    for (size_t s_ = 0; s_ < S; s_++)
-      if (D.spec_room[s_]) { so[s_] = off; off += (size_t)DABX_SPECTRUM_CHUNK_RECORDS * SPEC_SLOT_BYTES; }
-    DABX_HIP(hipMemcpy(D.spec_off, so.data(), sizeof(unsigned long long) * S, hipMemcpyHostToDevice));
-  }
+  for (int i = REC_SCOPE; i < N_REC_SECTIONS; i++) if (int rc = layout_records(D.rec[i])) return rc;
   off = align_up(off, 256);
   h.off_msc = off;
   if ((D.what & (DABX_DELIVER_MSC | DABX_DELIVER_MSC_NOT_DABPLUS)) && !d.fic_only)
@@ -200,24 +213,14 @@ int dabx_engine::delivery_begin(DeliverDev *dv, int *slot, int *devslab)
   int rc = launch_deliver_front(dev, *dv, stream);
   // the ETI stage's front half: the FIB ring is the front end's, which rewrites it while the chunk's MSC batch is decoded
   if (!rc && D.eti()) rc = launch_eti_front(dev, D.eti_dev(*devslab), stream, mk);
-  // the TII section: behind the k_tii of the chunk's last frame, which the front-end stream has run by now
-  if (!rc && D.tii())
-    rc = launch_deliver_tii(dev, TiiDeliverDev{D.dev[*devslab], D.ext, D.tii_done, tiis.dev.ring, tiis.exists() ? &tiis.dev.cnt->events : nullptr,
-                                               (int32_t)(sizeof(TiiCounters) / sizeof(long long)), 0}, stream);
-  else if (!rc && D.ext.magic) rc = launch_deliver_ext(D.ext, D.dev[*devslab], stream);      // (k_deliver_tii writes the header's extension otherwise)
-  // the scope section: behind the k_scope of the chunk's last frame (deliver.hip, k_deliver_scope)
-  if (!rc && D.scope())
-    rc = launch_deliver_scope(dev, ScopeDeliverDev{D.dev[*devslab], D.ext.off_scope, D.scope_off, D.scope_done, scope.dev.ring,
-                                                   scope.exists() ? &scope.dev.st->shows : nullptr, (int32_t)(sizeof(ScopeState) / sizeof(long long)), 0}, stream);
-  // the CIR section: behind the k_cir_finish and k_cir_corr of the chunk's last frame, which the front-end stream has run (deliver.hip, k_deliver_cir)
-  if (!rc && D.cir())
-    rc = launch_deliver_cir(dev.n_streams, CirDeliverDev{D.dev[*devslab], D.ext.off_cir, D.cir_off, D.cir_done, cir.dev.ring,
-                                                 cir.exists() ? &cir.dev.st->shows : nullptr, (int32_t)(sizeof(CirState) / sizeof(long long)), 0}, stream);
-  // the spectrum section: behind the k_spectrum of the chunk's last frame, which the front-end stream has run (deliver.hip, k_deliver_spectrum)
-  if (!rc && D.spectrum())
-    rc = launch_deliver_spectrum(dev.n_streams, SpecDeliverDev{D.dev[*devslab], D.ext.off_spectrum, D.spec_off, D.spec_done, spectrum.dev.ring,
-                                                               spectrum.exists() ? &spectrum.dev.st->shows : nullptr,
-                                                               (int32_t)(sizeof(SpecState) / sizeof(long long)), 0}, stream);
+  if (!rc && D.ext.magic && !D.tii()) rc = launch_deliver_ext(D.ext, D.dev[*devslab], stream);      // (k_deliver_tii writes the header's extension otherwise)
+  // the record sections: behind the stages' kernels of the chunk's last frame, which the front-end stream has run by now
+  for (int i = 0; i < N_REC_SECTIONS && !rc; i++) {
+    const Delivery::RecSection &r = D.rec[i];
+    if (!(D.what & r.bit)) continue;
+    const RecSource src = rec_source(this, i);
+    rc = launch_deliver_records(i, dev.n_streams, RecDeliverDev{D.dev[*devslab], D.ext.*r.off_word, r.off, r.done, src.ring, src.total, src.stride, 0}, D.ext, stream);
+  }
   if (rc) {                                                        // nothing was queued: give the slabs back
     std::lock_guard<std::mutex> lk(D.mu);
     D.dev_busy[*devslab] = false;
@@ -355,13 +358,9 @@ void delivery_free(dabx_engine *e)
     if (D.packed_lf[k]) (void)hipEventDestroy(D.packed_lf[k]);
     D.dev[k] = nullptr; D.packed[k] = nullptr; D.packed_lf[k] = nullptr; D.dev_busy[k] = false;
   }
-  for (void *q : {(void *)D.layout_off, (void *)D.subch_id, (void *)D.frames_done, (void *)D.cif_done, (void *)D.sf_done, (void *)D.eti_front,
-                  (void *)D.eti_next, (void *)D.eti_stage[0], (void *)D.eti_stage[1], (void *)D.eti_stage[2], (void *)D.tii_done, (void *)D.scope_done,
-                  (void *)D.scope_off, (void *)D.cir_done, (void *)D.cir_off, (void *)D.spec_done, (void *)D.spec_off}) if (q) (void)hipFree(q);
-  D.tii_done = nullptr; D.ext = dabx_chunk_header_ext{};
-  D.scope_done = nullptr; D.scope_off = nullptr; D.scope_room.clear();
-  D.cir_done = nullptr; D.cir_off = nullptr; D.cir_room.clear();
-  D.spec_done = nullptr; D.spec_off = nullptr; D.spec_room.clear();
+  hip_free_all({D.layout_off, D.subch_id, D.frames_done, D.cif_done, D.sf_done, D.eti_front, D.eti_next, D.eti_stage[0], D.eti_stage[1], D.eti_stage[2]});
+  for (Delivery::RecSection &r : D.rec) { hip_free_all({r.done, r.off}); r.done = nullptr; r.off = nullptr; r.room.clear(); }
+  D.ext = dabx_chunk_header_ext{};
   D.layout_off = nullptr; D.subch_id = nullptr; D.frames_done = D.cif_done = D.sf_done = nullptr;
   D.eti_front = nullptr; D.eti_next = nullptr; D.eti_rows_off = 0;
   for (int k = 0; k < Delivery::NDEV; k++) D.eti_stage[k] = nullptr;
@@ -451,30 +450,17 @@ int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
   cap += section_capacity(e->pkt, S * M * sizeof(dabx_chunk_dg)) + section_capacity(e->pad, S * M * sizeof(dabx_chunk_pad)) +
          section_capacity(e->mot, S * M * sizeof(dabx_chunk_mot)) + section_capacity(e->car, S * M * sizeof(dabx_chunk_mot));
   if (D.eti()) cap += 16 + S * sizeof(dabx_chunk_eti) + 256 + S * 4 * F * DABX_ETI_FRAME_BYTES;      // ... and the ETI section: its table and 4 F rows per stream
-  if (D.tii()) cap += sizeof(dabx_chunk_header_ext) + 16 + S * (sizeof(dabx_chunk_tii) + 4 * (size_t)DABX_TII_EVENT_SLOT_BYTES);   // ... and the TII section
-  if (D.mp2_audio()) cap += (D.tii() ? 0 : sizeof(dabx_chunk_header_ext)) + section_capacity(e->mpa, S * M * sizeof(dabx_chunk_mp2_audio));   // ... and the MP2 audio section
-  if (D.aac()) cap += (D.tii() || D.mp2_audio() ? 0 : sizeof(dabx_chunk_header_ext)) + section_capacity(e->aac, S * M * sizeof(dabx_chunk_aac));   // ... and the AAC section
-  D.scope_room.assign(D.scope() ? S : 0, 0);
-  if (D.scope()) {                                                  // ... and the scope section: its table and DL_FRAMES record slots per stream with the mode on
-    size_t n_on = 0;
-    if (e->scope.exists())
-      for (size_t s_ = 0; s_ < S; s_++) { D.scope_room[s_] = (char)(e->scope.cfg[s_].enable != 0); n_on += D.scope_room[s_] ? 1 : 0; }
-    cap += (D.tii() || D.mp2_audio() || D.aac() ? 0 : sizeof(dabx_chunk_header_ext)) + 16 + S * sizeof(dabx_chunk_scope) + n_on * (size_t)DL_FRAMES * SCOPE_SLOT_BYTES;
-  }
-  D.cir_room.assign(D.cir() ? S : 0, 0);
-  if (D.cir()) {                                                    // ... and the CIR section: its table and DABX_CIR_CHUNK_RECORDS record slots per stream with the mode on
-    size_t n_on = 0;
-    if (e->cir.exists())
-      for (size_t s_ = 0; s_ < S; s_++) { D.cir_room[s_] = (char)(e->cir.cfg[s_].enable != 0); n_on += D.cir_room[s_] ? 1 : 0; }
-    cap += (D.tii() || D.mp2_audio() || D.aac() || D.scope() ? 0 : sizeof(dabx_chunk_header_ext)) + 16 + S * sizeof(dabx_chunk_cir) + n_on * (size_t)DABX_CIR_CHUNK_RECORDS * CIR_SLOT_BYTES;
-  }
-  D.spec_room.assign(D.spectrum() ? S : 0, 0);
-  if (D.spectrum()) {                                               // ... and the spectrum section: its table and DABX_SPECTRUM_CHUNK_RECORDS record slots per stream with the mode on
-    size_t n_on = 0;
-    if (e->spectrum.exists())
-      for (size_t s_ = 0; s_ < S; s_++) { D.spec_room[s_] = (char)(e->spectrum.cfg[s_].enable != 0); n_on += D.spec_room[s_] ? 1 : 0; }
-    cap += (D.tii() || D.mp2_audio() || D.aac() || D.scope() || D.cir() ? 0 : sizeof(dabx_chunk_header_ext)) + 16 + S * sizeof(dabx_chunk_spectrum) +
-           n_on * (size_t)DABX_SPECTRUM_CHUNK_RECORDS * SPEC_SLOT_BYTES;
+  if (D.what & ~255) cap += sizeof(dabx_chunk_header_ext);          // ... and the header's extension, where delivery_layout puts one
+  if (D.mp2_audio()) cap += section_capacity(e->mpa, S * M * sizeof(dabx_chunk_mp2_audio));   // ... and the MP2 audio section
+  if (D.aac()) cap += section_capacity(e->aac, S * M * sizeof(dabx_chunk_aac));               // ... and the AAC section
+  for (int i = 0; i < N_REC_SECTIONS; i++) {                        // ... and the record sections: a table and chunk_records slots per stream with room
+    Delivery::RecSection &r = D.rec[i];
+    const bool want = (D.what & r.bit) != 0;
+    r.room.assign(want ? S : 0, 0);
+    if (!want) continue;
+    size_t n_room = 0;
+    for (size_t s_ = 0; s_ < S; s_++) { r.room[s_] = (char)rec_stream_on(e, i, s_); n_room += r.room[s_] ? 1 : 0; }
+    cap += 16 + S * rec_row_bytes + n_room * (size_t)r.chunk_records * r.slot_bytes;
   }
   D.capacity = align_up(cap, 4096);
 #define H(x) do { hipError_t err__ = (x); if (err__ != hipSuccess) { set_error("HIP error %d (%s) at %s:%d", (int)err__, hipGetErrorString(err__), __FILE__, __LINE__); delivery_free(e); return DABX_E_HIP; } } while (0)
@@ -523,52 +509,20 @@ int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
         H(hipMemset(D.eti_stage[k], 0, sizeof(EtiStage) * S));
       }
     }
-    if (D.tii()) {
-      // the TII section's cursor: the events completed from now on
-      std::vector<long long> td(S, 0);
-      if (e->tiis.exists()) {
-        std::vector<TiiCounters> tc(S);
-        H(hipMemcpy(tc.data(), e->tiis.dev.cnt, sizeof(TiiCounters) * S, hipMemcpyDeviceToHost));
-        for (size_t s_ = 0; s_ < S; s_++) td[s_] = tc[s_].events;
+    for (int i = 0; i < N_REC_SECTIONS; i++) {
+      Delivery::RecSection &r = D.rec[i];
+      if (!(D.what & r.bit)) continue;
+      // the section's cursor: the records completed from now on (the counters lie src.stride long longs apart, from src.total on)
+      const RecSource src = rec_source(e, i);
+      std::vector<long long> cur(S, 0);
+      if (src.total) {
+        std::vector<long long> raw((S - 1) * (size_t)src.stride + 1);
+        H(hipMemcpy(raw.data(), src.total, sizeof(long long) * raw.size(), hipMemcpyDeviceToHost));
+        for (size_t s_ = 0; s_ < S; s_++) cur[s_] = raw[s_ * (size_t)src.stride];
       }
-      H(hipMalloc((void **)&D.tii_done, sizeof(long long) * S));
-      H(hipMemcpy(D.tii_done, td.data(), sizeof(long long) * S, hipMemcpyHostToDevice));
-    }
-    if (D.scope()) {
-      // the scope section's cursor: the records written from now on
-      std::vector<long long> sd(S, 0);
-      if (e->scope.exists()) {
-        std::vector<ScopeState> st(S);
-        H(hipMemcpy(st.data(), e->scope.dev.st, sizeof(ScopeState) * S, hipMemcpyDeviceToHost));
-        for (size_t s_ = 0; s_ < S; s_++) sd[s_] = st[s_].shows;
-      }
-      H(hipMalloc((void **)&D.scope_done, sizeof(long long) * S));
-      H(hipMemcpy(D.scope_done, sd.data(), sizeof(long long) * S, hipMemcpyHostToDevice));
-      H(hipMalloc((void **)&D.scope_off, sizeof(unsigned long long) * S));
-    }
-    if (D.cir()) {
-      // the CIR section's cursor: the records completed from now on
-      std::vector<long long> cdn(S, 0);
-      if (e->cir.exists()) {
-        std::vector<CirState> st(S);
-        H(hipMemcpy(st.data(), e->cir.dev.st, sizeof(CirState) * S, hipMemcpyDeviceToHost));
-        for (size_t s_ = 0; s_ < S; s_++) cdn[s_] = st[s_].shows;
-      }
-      H(hipMalloc((void **)&D.cir_done, sizeof(long long) * S));
-      H(hipMemcpy(D.cir_done, cdn.data(), sizeof(long long) * S, hipMemcpyHostToDevice));
-      H(hipMalloc((void **)&D.cir_off, sizeof(unsigned long long) * S));
-    }
-    if (D.spectrum()) {
-      // the spectrum section's cursor: the records completed from now on
-      std::vector<long long> cdn(S, 0);
-      if (e->spectrum.exists()) {
-        std::vector<SpecState> st(S);
-        H(hipMemcpy(st.data(), e->spectrum.dev.st, sizeof(SpecState) * S, hipMemcpyDeviceToHost));
-        for (size_t s_ = 0; s_ < S; s_++) cdn[s_] = st[s_].shows;
-      }
-      H(hipMalloc((void **)&D.spec_done, sizeof(long long) * S));
-      H(hipMemcpy(D.spec_done, cdn.data(), sizeof(long long) * S, hipMemcpyHostToDevice));
-      H(hipMalloc((void **)&D.spec_off, sizeof(unsigned long long) * S));
+      H(hipMalloc((void **)&r.done, sizeof(long long) * S));
+      H(hipMemcpy(r.done, cur.data(), sizeof(long long) * S, hipMemcpyHostToDevice));
+      H(hipMalloc((void **)&r.off, sizeof(unsigned long long) * S));
     }
   }
 #undef H

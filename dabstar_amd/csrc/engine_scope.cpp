@@ -1,7 +1,6 @@
 // engine_scope.cpp -- the IQ scope and carrier plots on the device (include/dabx.h dabx_set_scope_mode; scope_core.h, pipeline.hip k_scope):
-// the stage's memory, its per-stream settings and compacted stream list, the record read-out and the counters.  The records lie in a ring
-// of SCOPE_RING fixed-size slots per stream that k_scope indexes by the stream's show count, read out as engine_tii.cpp reads the TII
-// events (out_ring.h serves variable-length items of slot stages behind the MSC batch; a record here has one size and one writer per frame).
+// the stage's memory, what a stream's settings may be, the parts of a record that dabx_read_scope copies and the counters.  The records lie in
+// a record ring (rec_ring.h) of SCOPE_RING slots per stream that k_scope indexes by the stream's show count.
 #include "engine.h"
 #include <cstring>
 
@@ -13,7 +12,7 @@ namespace dabx {
 void scope_stage_free(dabx_engine *e)
 {
   ScopeStage &T = e->scope;
-  for (void *q : {(void *)T.list, (void *)T.cfg_dev, (void *)T.dev.st, (void *)T.dev.ring}) if (q) (void)hipFree(q);
+  hip_free_all({T.list, T.cfg_dev, T.dev.st, T.dev.ring});
   T = ScopeStage{};
 }
 
@@ -22,17 +21,9 @@ static int scope_stage_create(dabx_engine *e)
 {
   ScopeStage &T = e->scope;
   const size_t S = (size_t)e->dev.n_streams;
-  const struct { void **p; size_t n; } bufs[] = {{(void **)&T.list, sizeof(int32_t) * S}, {(void **)&T.cfg_dev, sizeof(ScopeCfgDev) * S},
-                                                {(void **)&T.dev.st, sizeof(ScopeState) * S}, {(void **)&T.dev.ring, (size_t)SCOPE_RING * SCOPE_SLOT_BYTES * S}};
-  for (const auto &b : bufs) {
-    hipError_t he = hipMalloc(b.p, b.n);
-    if (he == hipSuccess) he = hipMemset(*b.p, 0, b.n);
-    if (he != hipSuccess) {
-      set_error("dabx_set_scope_mode: HIP error %d (%s) allocating the stage", (int)he, hipGetErrorString(he));
-      scope_stage_free(e);
-      return he == hipErrorOutOfMemory ? DABX_E_NOMEM : DABX_E_HIP;
-    }
-  }
+  if (int rc = alloc_zeroed("dabx_set_scope_mode", {{(void **)&T.list, sizeof(int32_t) * S}, {(void **)&T.cfg_dev, sizeof(ScopeCfgDev) * S},
+                                                    {(void **)&T.dev.st, sizeof(ScopeState) * S}, {(void **)&T.dev.ring, (size_t)SCOPE_RING * SCOPE_SLOT_BYTES * S}}))
+    return rc;
   // mNextShownOfdmSymbIdx = 1 (ofdm_decoder.h:88), both counters 0
   std::vector<ScopeState> st(S, ScopeState{0, 0, 1, 0, 0, 0});
   if (hipMemcpy(T.dev.st, st.data(), sizeof(ScopeState) * S, hipMemcpyHostToDevice) != hipSuccess) {
@@ -41,9 +32,7 @@ static int scope_stage_create(dabx_engine *e)
     return DABX_E_HIP;
   }
   T.dev.list = T.list; T.dev.cfg = T.cfg_dev; T.dev.n = 0;
-  T.cfg.assign(S, ScopeCfgDev{});
-  T.seen.assign(S, 0);
-  T.lost.assign(S, 0);
+  T.start(S);
   return 0;
 }
 
@@ -77,40 +66,23 @@ int dabx_set_scope_mode(dabx_engine *e, int stream, const dabx_scope_config *cfg
     if (on) c = ScopeCfgDev{1, iq, ct, sym};          // (the two counters are the device's: an enabled stream keeps them)
     else c.enable = 0;
   }
-  std::vector<int32_t> list;
-  for (int s = 0; s < e->dev.n_streams; s++) if (T.cfg[(size_t)s].enable) list.push_back(s);
-  DABX_HIP(hipMemcpy(T.cfg_dev, T.cfg.data(), sizeof(ScopeCfgDev) * T.cfg.size(), hipMemcpyHostToDevice));
-  if (!list.empty()) DABX_HIP(hipMemcpy(T.list, list.data(), sizeof(int32_t) * list.size(), hipMemcpyHostToDevice));
-  T.n_on = T.dev.n = (int)list.size();
-  return 0;
+  return T.upload(&T.dev.n);
 }
 
 int dabx_read_scope(dabx_engine *e, int stream, int max_records, dabx_scope_record *recs, float *iq, float *carr, int32_t *lost)
 {
   if (!e || stream < 0 || stream >= e->dev.n_streams || max_records < 0 || (max_records > 0 && !recs)) { set_error("dabx_read_scope: bad argument"); return DABX_E_ARG; }
   if (lost) *lost = 0;
-  if (int rc = use_device(e)) return rc;
-  if (int rc = sync_all(e)) return rc;
   ScopeStage &T = e->scope;
-  if (!T.exists()) return 0;
   ScopeState c;
-  DABX_HIP(hipMemcpy(&c, T.dev.st + stream, sizeof(c), hipMemcpyDeviceToHost));
-  long long &seen = T.seen[(size_t)stream];
-  if (c.shows - seen > SCOPE_RING) {
-    const long long gone = c.shows - seen - SCOPE_RING;
-    if (lost) *lost = (int32_t)std::min<long long>(gone, INT32_MAX);
-    T.lost[(size_t)stream] += gone;
-    seen = c.shows - SCOPE_RING;
-  }
-  int n = 0;
-  while (n < max_records && seen < c.shows) {
-    const uint8_t *slot = T.dev.ring + ((size_t)stream * SCOPE_RING + (size_t)(seen % SCOPE_RING)) * SCOPE_SLOT_BYTES;
+  if (int rc = stage_state(e, T, stream, &c)) return std::min(rc, 0);
+  return rec_ring_read<SCOPE_RING, SCOPE_SLOT_BYTES>(T.dev.ring, stream, c.shows, T.seen[(size_t)stream], &T.lost[(size_t)stream], max_records, lost,
+                                                      [&](int n, const uint8_t *slot) {
     DABX_HIP(hipMemcpy(recs + n, slot, sizeof(dabx_scope_record), hipMemcpyDeviceToHost));
     if (iq) DABX_HIP(hipMemcpy(iq + (size_t)n * 2 * K, slot + 32, sizeof(float) * 2 * K, hipMemcpyDeviceToHost));
     if (carr) DABX_HIP(hipMemcpy(carr + (size_t)n * K, slot + 32 + K * 8, sizeof(float) * K, hipMemcpyDeviceToHost));
-    n++; seen++;
-  }
-  return n;
+    return 0;
+  });
 }
 
 int dabx_scope_cadence_frame(int32_t counters[3])
@@ -126,12 +98,9 @@ int dabx_get_scope_stats(dabx_engine *e, int stream, dabx_scope_stats *out)
 {
   if (!e || stream < 0 || stream >= e->dev.n_streams || !out) { set_error("dabx_get_scope_stats: bad argument"); return DABX_E_ARG; }
   memset(out, 0, sizeof(*out));
-  if (int rc = use_device(e)) return rc;
-  if (int rc = sync_all(e)) return rc;
   const ScopeStage &T = e->scope;
-  if (!T.exists()) return 0;
   ScopeState c;
-  DABX_HIP(hipMemcpy(&c, T.dev.st + stream, sizeof(c), hipMemcpyDeviceToHost));
+  if (int rc = stage_state(e, T, stream, &c)) return std::min(rc, 0);
   out->shows = c.shows; out->lost = T.lost[(size_t)stream]; out->launches = T.launches;
   return 0;
 }

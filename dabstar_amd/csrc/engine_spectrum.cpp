@@ -1,7 +1,7 @@
 // engine_spectrum.cpp -- the RF spectrum and waterfall rows on the device (include/dabx.h dabx_set_spectrum_mode; spectrum_core.h, pipeline.hip
-// k_spectrum): the stage's memory, its window table, its per-stream settings and compacted stream list, the record read-out, the counters and
-// the host-callable entries.  The records lie in a ring of SPEC_RING fixed-size slots per stream, indexed by the stream's record count, read
-// out as engine_cir.cpp reads the CIR's.
+// k_spectrum): the stage's memory, its window table, what a stream's settings may be and what a fresh enable resets, the parts of a record
+// that dabx_read_spectrum copies, the counters and the host-callable entries.  The records lie in a record ring (rec_ring.h) of SPEC_RING
+// slots per stream, indexed by the stream's record count.
 #include "engine.h"
 #include <cstring>
 
@@ -16,8 +16,7 @@ namespace dabx {
 void spectrum_stage_free(dabx_engine *e)
 {
   SpecStage &T = e->spectrum;
-  for (void *q : {(void *)T.list, (void *)T.cfg_dev, (void *)T.window, (void *)T.dev.st, (void *)T.dev.disp, (void *)T.dev.pend, (void *)T.dev.ring})
-    if (q) (void)hipFree(q);
+  hip_free_all({T.list, T.cfg_dev, T.window, T.dev.st, T.dev.disp, T.dev.pend, T.dev.ring});
   T = SpecStage{};
 }
 
@@ -27,30 +26,21 @@ static int spectrum_stage_create(dabx_engine *e)
 {
   SpecStage &T = e->spectrum;
   const size_t S = (size_t)e->dev.n_streams;
-  const struct { void **p; size_t n; } bufs[] = {{(void **)&T.list, sizeof(int32_t) * S}, {(void **)&T.cfg_dev, sizeof(SpecCfgDev) * S},
-                                                {(void **)&T.window, sizeof(float) * SPEC_SIZE}, {(void **)&T.dev.st, sizeof(SpecState) * S},
-                                                {(void **)&T.dev.disp, sizeof(float) * SPEC_DISPLAY * S}, {(void **)&T.dev.pend, (size_t)SPEC_SLOT_BYTES * S},
-                                                {(void **)&T.dev.ring, (size_t)SPEC_RING * SPEC_SLOT_BYTES * S}};
-  hipError_t he = hipSuccess;
-  for (const auto &b : bufs) {
-    he = hipMalloc(b.p, b.n);
-    if (he == hipSuccess) he = hipMemset(*b.p, 0, b.n);
-    if (he != hipSuccess) break;
-  }
-  if (he == hipSuccess) {
-    std::vector<float> w(SPEC_SIZE);
-    spectrum_make_window(w.data());
-    he = hipMemcpy(T.window, w.data(), sizeof(float) * SPEC_SIZE, hipMemcpyHostToDevice);
-  }
+  if (int rc = alloc_zeroed("dabx_set_spectrum_mode", {{(void **)&T.list, sizeof(int32_t) * S}, {(void **)&T.cfg_dev, sizeof(SpecCfgDev) * S},
+                                                       {(void **)&T.window, sizeof(float) * SPEC_SIZE}, {(void **)&T.dev.st, sizeof(SpecState) * S},
+                                                       {(void **)&T.dev.disp, sizeof(float) * SPEC_DISPLAY * S}, {(void **)&T.dev.pend, (size_t)SPEC_SLOT_BYTES * S},
+                                                       {(void **)&T.dev.ring, (size_t)SPEC_RING * SPEC_SLOT_BYTES * S}}))
+    return rc;
+  std::vector<float> w(SPEC_SIZE);
+  spectrum_make_window(w.data());
+  const hipError_t he = hipMemcpy(T.window, w.data(), sizeof(float) * SPEC_SIZE, hipMemcpyHostToDevice);
   if (he != hipSuccess) {
     set_error("dabx_set_spectrum_mode: HIP error %d (%s) allocating the stage", (int)he, hipGetErrorString(he));
     spectrum_stage_free(e);
     return he == hipErrorOutOfMemory ? DABX_E_NOMEM : DABX_E_HIP;
   }
   T.dev.list = T.list; T.dev.cfg = T.cfg_dev; T.dev.window = T.window; T.dev.n = 0;
-  T.cfg.assign(S, SpecCfgDev{});
-  T.seen.assign(S, 0);
-  T.lost.assign(S, 0);
+  T.start(S);
   return 0;
 }
 
@@ -95,13 +85,8 @@ int dabx_set_spectrum_mode(dabx_engine *e, int stream, const dabx_spectrum_confi
       DABX_HIP(hipMemset(T.dev.disp + (size_t)s * SPEC_DISPLAY, 0, sizeof(float) * SPEC_DISPLAY));
     }
   }
-  std::vector<int32_t> list;
-  for (int s = 0; s < e->dev.n_streams; s++) if (T.cfg[(size_t)s].enable) list.push_back(s);
   DABX_HIP(hipMemcpy(T.dev.st, st.data(), sizeof(SpecState) * S, hipMemcpyHostToDevice));
-  DABX_HIP(hipMemcpy(T.cfg_dev, T.cfg.data(), sizeof(SpecCfgDev) * S, hipMemcpyHostToDevice));
-  if (!list.empty()) DABX_HIP(hipMemcpy(T.list, list.data(), sizeof(int32_t) * list.size(), hipMemcpyHostToDevice));
-  T.n_on = T.dev.n = (int)list.size();
-  return 0;
+  return T.upload(&T.dev.n);
 }
 
 int dabx_read_spectrum(dabx_engine *e, int stream, int max_records, dabx_spectrum_record *recs, dabx_spectrum_limits_rec *limits, float *db,
@@ -109,41 +94,26 @@ int dabx_read_spectrum(dabx_engine *e, int stream, int max_records, dabx_spectru
 {
   if (!e || stream < 0 || stream >= e->dev.n_streams || max_records < 0 || (max_records > 0 && !recs)) { set_error("dabx_read_spectrum: bad argument"); return DABX_E_ARG; }
   if (lost) *lost = 0;
-  if (int rc = use_device(e)) return rc;
-  if (int rc = sync_all(e)) return rc;
   SpecStage &T = e->spectrum;
-  if (!T.exists()) return 0;
   SpecState c;
-  DABX_HIP(hipMemcpy(&c, T.dev.st + stream, sizeof(c), hipMemcpyDeviceToHost));
-  long long &seen = T.seen[(size_t)stream];
-  if (c.shows - seen > SPEC_RING) {
-    const long long gone = c.shows - seen - SPEC_RING;
-    if (lost) *lost = (int32_t)std::min<long long>(gone, INT32_MAX);
-    T.lost[(size_t)stream] += gone;
-    seen = c.shows - SPEC_RING;
-  }
-  int n = 0;
-  while (n < max_records && seen < c.shows) {
-    const uint8_t *slot = T.dev.ring + ((size_t)stream * SPEC_RING + (size_t)(seen % SPEC_RING)) * SPEC_SLOT_BYTES;
+  if (int rc = stage_state(e, T, stream, &c)) return std::min(rc, 0);
+  return rec_ring_read<SPEC_RING, SPEC_SLOT_BYTES>(T.dev.ring, stream, c.shows, T.seen[(size_t)stream], &T.lost[(size_t)stream], max_records, lost,
+                                                    [&](int n, const uint8_t *slot) {
     DABX_HIP(hipMemcpy(recs + n, slot, sizeof(dabx_spectrum_record), hipMemcpyDeviceToHost));
     if (limits) DABX_HIP(hipMemcpy(limits + n, slot + 32, sizeof(dabx_spectrum_limits_rec), hipMemcpyDeviceToHost));
     if (db) DABX_HIP(hipMemcpy(db + (size_t)n * SPEC_DISPLAY, slot + 64, sizeof(float) * SPEC_DISPLAY, hipMemcpyDeviceToHost));
     if (row) DABX_HIP(hipMemcpy(row + (size_t)n * SPEC_DISPLAY, slot + 64 + SPEC_DISPLAY * 4, SPEC_DISPLAY, hipMemcpyDeviceToHost));
-    n++; seen++;
-  }
-  return n;
+    return 0;
+  });
 }
 
 int dabx_get_spectrum_stats(dabx_engine *e, int stream, dabx_spectrum_stats *out)
 {
   if (!e || stream < 0 || stream >= e->dev.n_streams || !out) { set_error("dabx_get_spectrum_stats: bad argument"); return DABX_E_ARG; }
   memset(out, 0, sizeof(*out));
-  if (int rc = use_device(e)) return rc;
-  if (int rc = sync_all(e)) return rc;
   const SpecStage &T = e->spectrum;
-  if (!T.exists()) return 0;
   SpecState c;
-  DABX_HIP(hipMemcpy(&c, T.dev.st + stream, sizeof(c), hipMemcpyDeviceToHost));
+  if (int rc = stage_state(e, T, stream, &c)) return std::min(rc, 0);
   out->shows = c.shows; out->untrusted = c.untrusted; out->lost = T.lost[(size_t)stream]; out->launches = T.launches; out->inexact = c.inexact;
   return 0;
 }

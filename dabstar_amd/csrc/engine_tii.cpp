@@ -1,5 +1,6 @@
 // engine_tii.cpp -- the TII detectors on the device (include/dabx.h dabx_set_tii_mode; tii_core.h, deliver.hip k_tii): the stage's memory, its
-// per-stream settings, the event read-out and the counters.
+// per-stream settings, the parts of an event that dabx_read_tii_events copies and the counters.  The events lie in a record ring (rec_ring.h)
+// of TII_RING slots per stream, indexed by the stream's event count.
 #include "engine.h"
 #include <cstring>
 
@@ -8,7 +9,7 @@ namespace dabx {
 void tii_stage_free(dabx_engine *e)
 {
   TiiStage &T = e->tiis;
-  for (void *q : {(void *)T.dev.pairs, (void *)T.dev.cfg, (void *)T.dev.ring, (void *)T.dev.cnt, (void *)T.tables}) if (q) (void)hipFree(q);
+  hip_free_all({T.dev.pairs, T.dev.cfg, T.dev.ring, T.dev.cnt, T.tables});
   T = TiiStage{};
 }
 
@@ -19,18 +20,10 @@ static int tii_stage_create(dabx_engine *e)
   const size_t S = (size_t)e->dev.n_streams;
   uint8_t tab[TII_PAIRS + 72];
   tii_tables_host(tab, tab + TII_PAIRS);
-  const struct { void **p; size_t n; } bufs[] = {{(void **)&T.dev.pairs, sizeof(float2) * TII_PAIRS * S}, {(void **)&T.dev.cfg, sizeof(TiiCfgDev) * S},
-                                                {(void **)&T.dev.ring, (size_t)TII_RING * TII_SLOT_BYTES * S}, {(void **)&T.dev.cnt, sizeof(TiiCounters) * S},
-                                                {(void **)&T.tables, sizeof(tab)}};
-  for (const auto &b : bufs) {
-    hipError_t he = hipMalloc(b.p, b.n);
-    if (he == hipSuccess) he = hipMemset(*b.p, 0, b.n);
-    if (he != hipSuccess) {
-      set_error("dabx_set_tii_mode: HIP error %d (%s) allocating the stage", (int)he, hipGetErrorString(he));
-      tii_stage_free(e);
-      return he == hipErrorOutOfMemory ? DABX_E_NOMEM : DABX_E_HIP;
-    }
-  }
+  if (int rc = alloc_zeroed("dabx_set_tii_mode", {{(void **)&T.dev.pairs, sizeof(float2) * TII_PAIRS * S}, {(void **)&T.dev.cfg, sizeof(TiiCfgDev) * S},
+                                                  {(void **)&T.dev.ring, (size_t)TII_RING * TII_SLOT_BYTES * S}, {(void **)&T.dev.cnt, sizeof(TiiCounters) * S},
+                                                  {(void **)&T.tables, sizeof(tab)}}))
+    return rc;
   if (hipMemcpy(T.tables, tab, sizeof(tab), hipMemcpyHostToDevice) != hipSuccess) { set_error("dabx_set_tii_mode: uploading the tables failed"); tii_stage_free(e); return DABX_E_HIP; }
   T.dev.turn = T.tables; T.dev.pattern = T.tables + TII_PAIRS;
   T.cfg.assign(S, TiiCfgDev{});
@@ -95,20 +88,14 @@ int dabx_read_tii_events(dabx_engine *e, int stream, int max_events, dabx_tii_ev
   if (!T.exists()) return 0;
   TiiCounters c;
   DABX_HIP(hipMemcpy(&c, T.dev.cnt + stream, sizeof(c), hipMemcpyDeviceToHost));
-  long long &seen = T.seen[(size_t)stream];
-  if (c.events - seen > TII_RING) {
-    if (lost) *lost = (int32_t)std::min<long long>(c.events - seen - TII_RING, INT32_MAX);
-    seen = c.events - TII_RING;
-  }
-  int n = 0;
   uint8_t slot[TII_SLOT_BYTES];
-  while (n < max_events && seen < c.events) {
-    DABX_HIP(hipMemcpy(slot, T.dev.ring + ((size_t)stream * TII_RING + (size_t)(seen % TII_RING)) * TII_SLOT_BYTES, sizeof(slot), hipMemcpyDeviceToHost));
+  return rec_ring_read<TII_RING, TII_SLOT_BYTES>(T.dev.ring, stream, c.events, T.seen[(size_t)stream], nullptr, max_events, lost,
+                                                  [&](int n, const uint8_t *dev_slot) {
+    DABX_HIP(hipMemcpy(slot, dev_slot, sizeof(slot), hipMemcpyDeviceToHost));
     memcpy(ev + n, slot, sizeof(dabx_tii_event));
     if (res) memcpy(res + (size_t)n * DABX_TII_MAX_RESULTS, slot + sizeof(dabx_tii_event), sizeof(dabx_tii_result) * DABX_TII_MAX_RESULTS);
-    n++; seen++;
-  }
-  return n;
+    return 0;
+  });
 }
 
 int dabx_get_tii_stats(dabx_engine *e, int stream, dabx_tii_stats *out)

@@ -2,6 +2,7 @@
 #pragma once
 #include "dabx_internal.h"
 #include "ring_fmt.h"
+#include <cstddef>
 
 namespace dabx {
 
@@ -206,52 +207,29 @@ struct EtiDev {
   int32_t max_frames, pad_;
 };
 
-// ---- the TII section of the delivery (deliver.hip k_deliver_tii, include/dabx.h dabx_chunk_tii): the events the detectors (deliver.hip, k_tii) have
-// completed since the previous chunk, out of their rings into the slab's head part; gathered at chunk close on the front-end stream
-struct TiiDeliverDev {
+// ---- the record sections of the delivery (deliver.hip k_deliver_tii / k_deliver_records; include/dabx.h dabx_chunk_tii, dabx_chunk_scope,
+// dabx_chunk_cir, dabx_chunk_spectrum): the records a stage has written into its record ring (rec_ring.h) since the previous chunk -- the TII
+// events of k_tii (deliver.hip), the records of k_scope, of k_cir_finish and k_cir_corr, and of k_spectrum (pipeline.hip) -- out of the ring
+// into the slab's head part; gathered at chunk close on the front-end stream, in this order
+enum : int { REC_TII = 0, REC_SCOPE, REC_CIR, REC_SPECTRUM, N_REC_SECTIONS };
+struct RecDeliverDev {
   uint8_t *slab;
-  dabx_chunk_header_ext ext;              // as it goes into the slab
-  long long *done;                        // [S] events of the stream delivered or passed so far
-  const uint8_t *ring;                    // TiiDev::ring and ::cnt (tii_core.h), null while the engine has no TII stage: every stream delivers no event
-  const long long *events;                // &cnt[0].events, a TiiCounters apart
-  int32_t cnt_stride, pad_;               // ... in long longs
-};
-
-// ---- the scope section of the delivery (deliver.hip k_deliver_scope, include/dabx.h dabx_chunk_scope): the records k_scope (pipeline.hip) has
-// written since the previous chunk, out of their rings into the slab's head part; gathered at chunk close on the front-end stream
-struct ScopeDeliverDev {
-  uint8_t *slab;
-  unsigned long long off_scope;           // dabx_chunk_header_ext.off_scope of the slab
+  unsigned long long off_table;           // the section's word of dabx_chunk_header_ext: its table of one row per stream
   const unsigned long long *rec_off;      // [S] where the stream's record slots lie in a slab, 0 = it has no room (mode off when the delivery was opened)
   long long *done;                        // [S] records of the stream delivered or passed so far
-  const uint8_t *ring;                    // ScopeDev::ring (scope_core.h), null while the engine has no scope stage: every stream delivers no record
-  const long long *shows;                 // &st[0].shows, a ScopeState apart
-  int32_t st_stride, pad_;                // ... in long longs
+  const uint8_t *ring;                    // the stage's ring, null while the engine has no such stage: every stream delivers no record
+  const long long *total;                 // the first stream's record counter in the stage's state records (TiiCounters::events, *State::shows)
+  int32_t stride, pad_;                   // ... and how far apart they lie, in long longs
 };
-
-// ---- the CIR section of the delivery (deliver.hip k_deliver_cir, include/dabx.h dabx_chunk_cir): the records k_cir_finish and k_cir_corr
-// (pipeline.hip) have completed since the previous chunk, out of the stage's ring
-struct CirDeliverDev {
-  uint8_t *slab;
-  unsigned long long off_cir;             // dabx_chunk_header_ext.off_cir of the slab
-  const unsigned long long *rec_off;      // [S] where the stream's record slots lie in a slab, 0 = it has no room (mode off when the delivery was opened)
-  long long *done;                        // [S] records of the stream delivered or passed so far
-  const uint8_t *ring;                    // CirDev::ring (cir_core.h), null while the engine has no CIR stage: every stream delivers no record
-  const long long *shows;                 // &st[0].shows, a CirState apart
-  int32_t st_stride, pad_;                // ... in long longs
-};
-
-// ---- the spectrum section of the delivery (deliver.hip k_deliver_spectrum, include/dabx.h dabx_chunk_spectrum): the records k_spectrum
-// (pipeline.hip) has completed since the previous chunk, out of the stage's ring
-struct SpecDeliverDev {
-  uint8_t *slab;
-  unsigned long long off_spectrum;        // dabx_chunk_header_ext.off_spectrum of the slab
-  const unsigned long long *rec_off;      // [S] where the stream's record slots lie in a slab, 0 = it has no room (mode off when the delivery was opened)
-  long long *done;                        // [S] records of the stream delivered or passed so far
-  const uint8_t *ring;                    // SpecDev::ring (spectrum_core.h), null while the engine has no spectrum stage: every stream delivers no record
-  const long long *shows;                 // &st[0].shows, a SpecState apart
-  int32_t st_stride, pad_;                // ... in long longs
-};
+// the rows of the four tables are one layout under two sets of names: the gather writes them all as dabx_chunk_scope
+#define DABX_REC_ROW_IS(T, first, n, lost, off, total)                                                                                     \
+  static_assert(sizeof(T) == 32 && offsetof(T, first) == 0 && offsetof(T, n) == 8 && offsetof(T, lost) == 12 && offsetof(T, off) == 16 && \
+                offsetof(T, total) == 24, "include/dabx.h: the row of a record section")
+DABX_REC_ROW_IS(dabx_chunk_tii, first_event, n_events, events_lost, ev_off, events_total);
+DABX_REC_ROW_IS(dabx_chunk_scope, first_record, n_records, records_lost, rec_off, records_total);
+DABX_REC_ROW_IS(dabx_chunk_cir, first_record, n_records, records_lost, rec_off, records_total);
+DABX_REC_ROW_IS(dabx_chunk_spectrum, first_record, n_records, records_lost, rec_off, records_total);
+#undef DABX_REC_ROW_IS
 
 // ---- lane-per-trellis path of the MSC decoder (vit_t.hip) ------------------------------------------------------
 // The sub-channels of ALL streams are grouped into classes of equal protection profile (same depuncture map and
@@ -460,10 +438,8 @@ int launch_deliver_carousel(const EngineDev &e, const DeliverDev &dv, const Caro
 int launch_deliver_mp2_audio(const EngineDev &e, const DeliverDev &dv, const Mp2AudioDev &ad, unsigned long long off_mp2_audio, hipStream_t st);
 int launch_deliver_aac(const EngineDev &e, const DeliverDev &dv, const AacStreamDev &ad, unsigned long long off_aac, hipStream_t st);
 int launch_deliver_ext(const dabx_chunk_header_ext &ext, uint8_t *slab, hipStream_t st);           // at chunk close, front-end stream: the header's extension of a slab without a TII section
-int launch_deliver_tii(const EngineDev &e, const TiiDeliverDev &td, hipStream_t st);                // at chunk close, front-end stream, behind launch_deliver_front
-int launch_deliver_scope(const EngineDev &e, const ScopeDeliverDev &sd, hipStream_t st);            // at chunk close, front-end stream, behind the header's extension
-int launch_deliver_cir(int n_streams, const CirDeliverDev &cd, hipStream_t st);                     // ... and the CIR section behind it
-int launch_deliver_spectrum(int n_streams, const SpecDeliverDev &sd, hipStream_t st);               // ... and the spectrum section behind that
+// at chunk close, front-end stream, behind launch_deliver_front: record section `section` (REC_*); REC_TII writes the header's extension too
+int launch_deliver_records(int section, int n_streams, const RecDeliverDev &rd, const dabx_chunk_header_ext &ext, hipStream_t st);
 int launch_eti_front(const EngineDev &e, const EtiDev &t, hipStream_t st, Marker &mk);              // at chunk close, front-end stream
 int launch_eti_back(const EngineDev &e, const EtiDev &t, hipStream_t st, Marker &mk, bool pre);     // behind the batch's decode; pre: in front of its DAB+ stage
 // msc_stages.hip

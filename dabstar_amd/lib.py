@@ -891,28 +891,27 @@ class Chunk:
             out.append((ev, self.raw[o + 32:o + 32 + 16 * int(ev["n_results"])].view(TII_RESULT)))
         return out
 
+    @staticmethod
+    def _record_slots(table, stream, slot_bytes):
+        """Where the record slots of `stream` lie in the slab, oldest first, by its row of a scope / CIR / spectrum section's table (None: the
+        slab has no such section)."""
+        if table is None:
+            return []
+        r = table[stream]
+        return [int(r["rec_off"]) + k * slot_bytes for k in range(int(r["n_records"]))]
+
     def scope(self, stream):
         """Scope records of `stream` in this chunk, oldest first: a list of (SCOPE_RECORD record, iq [1536] complex64, carr [1536] float32),
         views.  Empty when the slab has no scope section or the stream had the mode off when the delivery was opened."""
-        if self.scope_table is None:
-            return []
-        r = self.scope_table[stream]
-        out = []
-        for k in range(int(r["n_records"])):
-            o = int(r["rec_off"]) + k * SCOPE_SLOT_BYTES
-            out.append((self.raw[o:o + 32].view(SCOPE_RECORD)[0], self.raw[o + 32:o + 32 + SCOPE_CARRIERS * 8].view(np.complex64),
-                        self.raw[o + 32 + SCOPE_CARRIERS * 8:o + SCOPE_SLOT_BYTES].view(np.float32)))
-        return out
+        return [(self.raw[o:o + 32].view(SCOPE_RECORD)[0], self.raw[o + 32:o + 32 + SCOPE_CARRIERS * 8].view(np.complex64),
+                 self.raw[o + 32 + SCOPE_CARRIERS * 8:o + SCOPE_SLOT_BYTES].view(np.float32))
+                for o in self._record_slots(self.scope_table, stream, SCOPE_SLOT_BYTES)]
 
     def cir(self, stream):
         """CIR / correlation records of `stream` in this chunk, oldest first: a list of (CIR_RECORD record, values[:n_values] float32,
         indices[:n_indices] int16), views.  Empty when the slab has no CIR section or the stream had the mode off when the delivery was opened."""
-        if self.cir_table is None:
-            return []
-        r = self.cir_table[stream]
         out = []
-        for k in range(int(r["n_records"])):
-            o = int(r["rec_off"]) + k * CIR_SLOT_BYTES
+        for o in self._record_slots(self.cir_table, stream, CIR_SLOT_BYTES):
             rec = self.raw[o:o + 32].view(CIR_RECORD)[0]
             out.append((rec, self.raw[o + 32:o + 32 + 4 * int(rec["n_values"])].view(np.float32),
                         self.raw[o + 32 + CIR_CORR_LAGS * 4:o + 32 + CIR_CORR_LAGS * 4 + 2 * int(rec["n_indices"])].view(np.int16)))
@@ -921,15 +920,9 @@ class Chunk:
     def spectrum(self, stream):
         """Spectrum records of `stream` in this chunk, oldest first: a list of (SPECTRUM_RECORD record, SPECTRUM_LIMITS record, db [512]
         float32, row [512] uint8), views.  Empty when the slab has no spectrum section or the stream had the mode off when the delivery was opened."""
-        if self.spectrum_table is None:
-            return []
-        r = self.spectrum_table[stream]
-        out = []
-        for k in range(int(r["n_records"])):
-            o = int(r["rec_off"]) + k * SPECTRUM_SLOT_BYTES
-            out.append((self.raw[o:o + 32].view(SPECTRUM_RECORD)[0], self.raw[o + 32:o + 64].view(SPECTRUM_LIMITS)[0],
-                        self.raw[o + 64:o + 64 + 4 * SPECTRUM_BINS].view(np.float32), self.raw[o + 64 + 4 * SPECTRUM_BINS:o + SPECTRUM_SLOT_BYTES]))
-        return out
+        return [(self.raw[o:o + 32].view(SPECTRUM_RECORD)[0], self.raw[o + 32:o + 64].view(SPECTRUM_LIMITS)[0],
+                 self.raw[o + 64:o + 64 + 4 * SPECTRUM_BINS].view(np.float32), self.raw[o + 64 + 4 * SPECTRUM_BINS:o + SPECTRUM_SLOT_BYTES])
+                for o in self._record_slots(self.spectrum_table, stream, SPECTRUM_SLOT_BYTES)]
 
     def eti(self, stream):
         """ETI(NI) frames of `stream` in this chunk: (its CHUNK_ETI record, [n_eti, 6144] uint8), views; the rows are contiguous and in CIF

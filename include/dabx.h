@@ -1148,7 +1148,7 @@ typedef struct {
  * stream switched on later has no room and delivers none: rec_off = 0).  A record slot is a dabx_scope_record, the IQ vector [1536] cf32
  * and the carrier vector [1536] f32, DABX_SCOPE_SLOT_BYTES in all, byte for byte what dabx_read_scope returns; stream s's n_records slots
  * lie one behind the other from rec_off, oldest first.  Every record a stream wrote since the previous chunk is in the chunk or counted in
- * records_lost.  Gathered on the front-end stream when the chunk closes (k_deliver_scope), with a cursor of its own. */
+ * records_lost.  Gathered on the front-end stream when the chunk closes (k_deliver_records), with a cursor of its own. */
 typedef struct {
   int64_t  first_record;    /* number, since the stream's mode was first switched on, of the first record in the chunk */
   int32_t  n_records, records_lost;
@@ -1165,7 +1165,7 @@ typedef struct {
  * records_lost, the newest are kept.)  A record slot is a dabx_cir_record, the values [2048] f32 and the indices [72] int16,
  * DABX_CIR_SLOT_BYTES in all, byte for byte what dabx_read_cir returns; stream s's n_records slots lie one behind the other from rec_off,
  * oldest first, both kinds in the order they were completed.  Every record a stream wrote since the previous chunk is in the chunk or
- * counted in records_lost.  Gathered on the front-end stream when the chunk closes (k_deliver_cir), with a cursor of its own. */
+ * counted in records_lost.  Gathered on the front-end stream when the chunk closes (k_deliver_records), with a cursor of its own. */
 #define DABX_CIR_CHUNK_RECORDS 4
 typedef struct {
   int64_t  first_record;    /* number, since the stream's mode was first switched on, of the first record in the chunk */
@@ -1181,7 +1181,7 @@ typedef struct {
  * of them have room, and records_lost stays 0 (the field is kept for the shape the other sections have: the newest are kept should a
  * chunk ever complete more).  A record slot is DABX_SPECTRUM_SLOT_BYTES, byte for byte what dabx_read_spectrum returns; stream s's
  * n_records slots lie one behind the other from rec_off, oldest first.  Every record a stream wrote since the previous chunk is in the
- * chunk or counted in records_lost.  Gathered on the front-end stream when the chunk closes (k_deliver_spectrum), with a cursor of its own. */
+ * chunk or counted in records_lost.  Gathered on the front-end stream when the chunk closes (k_deliver_records), with a cursor of its own. */
 #define DABX_SPECTRUM_CHUNK_RECORDS 6
 typedef struct {
   int64_t  first_record;    /* number, since the stream's mode was first switched on, of the first record in the chunk */

@@ -1,4 +1,4 @@
-"""The CIR section of the bulk delivery (DABX_DELIVER_CIR, dabx_chunk_header_ext.off_cir, dabx_chunk_cir; deliver.hip k_deliver_cir):
+"""The CIR section of the bulk delivery (DABX_DELIVER_CIR, dabx_chunk_header_ext.off_cir, dabx_chunk_cir; deliver.hip k_deliver_records):
 two streams of one FIC-only engine, stream 1 with both kinds on, dabx_process calls of 5, 7, 3 and 6 frames.  What Chunk.cir returns is
 dabx_read_cir of a twin engine without a delivery, record for record and byte for byte; every record is in a chunk or counted lost; the
 refusals hold (the bit alone, the bit with only the other opt-in bits, and 1024 / 4096 / 16384 as ever); without the bit a slab has the

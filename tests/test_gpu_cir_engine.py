@@ -324,6 +324,47 @@ def test_mode_off_everywhere_is_an_engine_without_the_stage(world):
         assert np.array_equal(plain[0][s], fibs_on[s][:len(plain[0][s])])
 
 
+def test_five_unread_correlation_shows_give_four_records_and_one_lost():
+    """The overrun of a record ring other than the scope's (csrc/rec_ring.h): CIR_RING = 4 slots, so RING + 1 correlation shows left unread
+    lose the oldest.  One stream, the correlation plot alone, cf32, a clean signal: the plot shows once per PER_SHOW counted calls
+    (mDisplayCounter > FRAMES_PER_SECOND / 2, phasereference.cpp:181; CirState::corr_counter), one call per frame in lock, so RING + 1 shows
+    take (RING + 1) * PER_SHOW frames in lock -- plus two for the search and a cut first frame and two to spare, fewer than a further show
+    would take.  Read once at the end, the records are byte for byte the newest RING of the same run read after every step."""
+    RING = 4                                                              # cir_core.h, CIR_RING
+    PER_SHOW = cc.CorrPlot.FRAMES_PER_SECOND // 2 + 1
+    n_shows = RING + 1
+    n_frames = n_shows * PER_SHOW + 4
+    assert 4 < PER_SHOW
+    ens = ds.build_ensemble(20, ds.default_subchannels(1, 64), seed=70)
+    x = echo(ds.channel(ens.iq, snr_db=25.0, cfo_hz=-120.0, timing_offset=4243, seed=6, n_out=n_frames * TF))
+
+    def go(read_every_step):
+        eng = dx.Engine(n_streams=1, ring_frames=n_frames + 2, max_subch=1, out_frames=8, fic_only=True, acquire_mode=1, ring_format="cf32")
+        try:
+            eng.push_iq(0, x)
+            eng.set_cir_mode(0, cir=False, correlation=True)
+            got = []
+            for _ in range(n_frames + 1):
+                assert eng.process(1) == 1
+                if read_every_step:
+                    recs, lost = eng.read_cir(0, 4)
+                    assert lost == 0
+                    got += [(r.tobytes(), v.tobytes(), i.tobytes()) for r, v, i in recs]
+            if read_every_step:
+                return got, eng.cir_stats(0)
+            recs, lost = eng.read_cir(0, 8)
+            return [(r.tobytes(), v.tobytes(), i.tobytes()) for r, v, i in recs], lost, eng.cir_stats(0), eng.read_cir(0, 8)
+        finally:
+            eng.close()
+    every, stats_every = go(True)
+    assert len(every) == n_shows and stats_every["shows"] == [0, n_shows] and stats_every["lost"] == 0
+    assert all(np.frombuffer(r, dx.CIR_RECORD)[0]["kind"] == dx.CIR_KIND_CORRELATION for r, _, _ in every)
+    once, lost, stats_once, again = go(False)
+    assert lost == 1 and once == every[-RING:]
+    assert stats_once["shows"] == [0, n_shows] and stats_once["lost"] == 1
+    assert again == ([], 0)
+
+
 def test_arguments():
     eng = dx.Engine(n_streams=2, ring_frames=4, max_subch=1, fic_only=True)
     try:

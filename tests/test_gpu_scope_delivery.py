@@ -1,4 +1,4 @@
-"""The scope section of the bulk delivery (DABX_DELIVER_SCOPE, dabx_chunk_header_ext.off_scope, dabx_chunk_scope; deliver.hip k_deliver_scope)
+"""The scope section of the bulk delivery (DABX_DELIVER_SCOPE, dabx_chunk_header_ext.off_scope, dabx_chunk_scope; deliver.hip k_deliver_records)
 and k_scope inside the running engine, through IQ: two streams of one FIC-only engine, stream 1 with the mode on (OFDM symbol 4 of every
 decoded frame, so a chunk of seven frames fills its seven record slots), a consumer thread beside dabx_process calls of 5, 7, 3 and 6 frames.
 The slab's records and vectors are dabx_read_scope's of the same engine, byte for byte; the few-stream schedule (k_scope on the demapper's

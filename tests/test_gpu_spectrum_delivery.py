@@ -1,5 +1,5 @@
 """The spectrum section of the bulk delivery (DABX_DELIVER_SPECTRUM, dabx_chunk_header_ext.off_spectrum, dabx_chunk_spectrum; deliver.hip
-k_deliver_spectrum): two streams of one FIC-only engine, stream 1 with the mode on, dabx_process calls of 5, 7, 3 and 6 frames.  What
+k_deliver_records): two streams of one FIC-only engine, stream 1 with the mode on, dabx_process calls of 5, 7, 3 and 6 frames.  What
 Chunk.spectrum returns is dabx_read_spectrum of a twin engine without a delivery, record for record and byte for byte; every record is in
 a chunk or counted lost; the refusals hold (the bit alone, the bit with only the other opt-in bits, and 1024 / 4096 / 16384 as ever);
 without the bit a slab is byte for byte the slab of an engine that has no spectrum stage at all, with a stream's mode on and shows being made."""

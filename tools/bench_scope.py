@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What the IQ scope on the device (dabx_set_scope_mode, k_scope) and its section of the bulk delivery (DABX_DELIVER_SCOPE, k_deliver_scope)
+"""What the IQ scope on the device (dabx_set_scope_mode, k_scope) and its section of the bulk delivery (DABX_DELIVER_SCOPE, k_deliver_records)
 cost, at bench.py's layout: --streams streams x 18 sub-channels of 64 kbit/s, rings filled as bench.py fills them, primed for 40 frames.
 One JSON line per figure; a fresh process per run.
 
