@@ -6,6 +6,7 @@
 #include "mp2_core.h"
 #include "aac_core.h"
 #include "spectrum_core.h"
+#include "fig_core.h"
 #include <cstring>
 
 namespace dabx { const char *last_error(); }
@@ -235,6 +236,66 @@ int dabx_tii_process_device(int n, const float *sums, float *pairs, const dabx_t
   if ((rc = dpairs.to_host(pairs, sizeof(float2) * TII_PAIRS * N)) || (rc = dout.to_host(out, sizeof(dabx_tii_result) * DABX_TII_MAX_RESULTS * N)) ||
       (rc = dnr.to_host(n_results, 4 * N))) return rc;
   return dnf.to_host(n_found, 4 * N);
+}
+
+// The FIG walk on the device: fig_walk_fib (fig_core.h), the body of the engine's k_fig, one wave per decoder
+int dabx_fig_walk_device(const uint8_t *fibs, const uint8_t *crc_ok, int n_decoders, int n_fibs, int reference_quirks, dabx_fibdec_info *info,
+                         int32_t *n_tab, dabx_subch_desc *subch, dabx_packet_component *packets, int32_t *n_labels, dabx_fig_label *labels,
+                         dabx_fig_stats *stats, int64_t *n_events, dabx_fig_event *events)
+{
+  if (!fibs || !crc_ok || n_decoders <= 0 || n_decoders > 65535 || n_fibs <= 0 || n_fibs > 1 << 20) { set_error("dabx_fig_walk_device: bad argument"); return DABX_E_ARG; }
+  int rc = need_device();
+  if (rc) return rc;
+  const size_t N = (size_t)n_decoders;
+  std::vector<FigDecoder> dec(N);
+  for (FigDecoder &d : dec) { memset(&d, 0, sizeof(d)); fig_state_init(d.st, reference_quirks ? 1 : 0, 0); }
+  std::vector<FigState> st(N);
+  for (size_t d = 0; d < N; d++) st[d] = dec[d].st;
+  DevBuf dfib, dcrc, dst, dlab, dring;
+  if ((rc = dfib.from_host(fibs, N * n_fibs * 32)) || (rc = dcrc.from_host(crc_ok, N * n_fibs)) || (rc = dst.from_host(st.data(), sizeof(FigState) * N)) ||
+      (rc = dlab.alloc(sizeof(dabx_fig_label) * FIG_LAB_SLOTS * N)) || (rc = dring.alloc(sizeof(dabx_fig_event) * FIG_RING * N))) return rc;
+  DABX_HIP(hipMemset(dlab.p, 0, sizeof(dabx_fig_label) * FIG_LAB_SLOTS * N));
+  DABX_HIP(hipMemset(dring.p, 0, sizeof(dabx_fig_event) * FIG_RING * N));
+  if ((rc = launch_fig_batch(dfib.as<uint8_t>(), dcrc.as<uint8_t>(), n_decoders, n_fibs, dst.as<FigState>(), dlab.as<dabx_fig_label>(), dring.as<dabx_fig_event>(), 0))) return rc;
+  DABX_HIP(hipStreamSynchronize(0));
+  if ((rc = dst.to_host(st.data(), sizeof(FigState) * N))) return rc;
+  for (size_t d = 0; d < N; d++) {
+    dec[d].st = st[d];
+    DABX_HIP(hipMemcpy(dec[d].labels, dlab.as<dabx_fig_label>() + d * FIG_LAB_SLOTS, sizeof(dec[d].labels), hipMemcpyDeviceToHost));
+    DABX_HIP(hipMemcpy(dec[d].ring, dring.as<dabx_fig_event>() + d * FIG_RING, sizeof(dec[d].ring), hipMemcpyDeviceToHost));
+    fig_present(dec[d], info ? info + d : nullptr, n_tab ? n_tab + 6 * d : nullptr, subch ? subch + 2 * FIG_MAX_SUB * d : nullptr,
+                packets ? packets + 2 * FIG_MAX_PKT * d : nullptr, n_labels ? n_labels + d : nullptr, labels ? labels + FIG_LAB_SLOTS * d : nullptr,
+                stats ? stats + d : nullptr, n_events ? n_events + d : nullptr, events ? events + FIG_RING * d : nullptr);
+  }
+  return 0;
+}
+
+// Test entries of the FIG walk (tests/test_fig_cases.py; not part of include/dabx.h): the HOST build of fig_walk_fib on a decoder the caller
+// keeps as bytes.  dabx_internal_fig_host_bytes: the size of one; _init: a fresh decoder; _walk: n_fibs FIBs of 32 bytes with their CRC
+// verdicts; _read: the decoder presented as one row of dabx_fig_walk_device's outputs.  Needs no device.
+int dabx_internal_fig_host_bytes(void) { return (int)sizeof(FigDecoder); }
+int dabx_internal_fig_host_init(void *dec, int reference_quirks)
+{
+  if (!dec) return DABX_E_ARG;
+  FigDecoder *d = static_cast<FigDecoder *>(dec);
+  memset(d, 0, sizeof(*d));
+  fig_state_init(d->st, reference_quirks ? 1 : 0, 0);
+  return 0;
+}
+int dabx_internal_fig_host_walk(void *dec, const uint8_t *fibs, const uint8_t *crc_ok, int n_fibs)
+{
+  if (!dec || !fibs || !crc_ok || n_fibs < 0) return DABX_E_ARG;
+  FigDecoder *d = static_cast<FigDecoder *>(dec);
+  const FigOut o{d->labels, d->ring};
+  for (int i = 0; i < n_fibs; i++) fig_walk_fib(d->st, fibs + (size_t)i * 32, crc_ok[i] != 0, o, 0);
+  return 0;
+}
+int dabx_internal_fig_host_read(const void *dec, dabx_fibdec_info *info, int32_t *n_tab, dabx_subch_desc *subch, dabx_packet_component *packets,
+                                int32_t *n_labels, dabx_fig_label *labels, dabx_fig_stats *stats, int64_t *n_events, dabx_fig_event *events)
+{
+  if (!dec) return DABX_E_ARG;
+  fig_present(*static_cast<const FigDecoder *>(dec), info, n_tab, subch, packets, n_labels, labels, stats, n_events, events);
+  return 0;
 }
 
 // cir_viewer.cpp:66-95 on crafted rows: the row function of k_cir (cir_core.h, cir_row_block), one block per row

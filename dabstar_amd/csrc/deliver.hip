@@ -17,6 +17,7 @@
 #include "scope_core.h"
 #include "cir_core.h"
 #include "spectrum_core.h"
+#include "fig_core.h"
 #include "rec_ring.h"
 #include "fig00.h"
 
@@ -391,6 +392,7 @@ int launch_deliver_records(int section, int n_streams, const RecDeliverDev &rd, 
   case REC_SCOPE: hipLaunchKernelGGL((k_deliver_records<SCOPE_RING, SCOPE_SLOT_BYTES, DABX_CHUNK_FRAMES>), grid, nt, 0, st, rd); break;
   case REC_CIR: hipLaunchKernelGGL((k_deliver_records<CIR_RING, CIR_SLOT_BYTES, DABX_CIR_CHUNK_RECORDS>), grid, nt, 0, st, rd); break;
   case REC_SPECTRUM: hipLaunchKernelGGL((k_deliver_records<SPEC_RING, SPEC_SLOT_BYTES, DABX_SPECTRUM_CHUNK_RECORDS>), grid, nt, 0, st, rd); break;
+  case REC_FIG: hipLaunchKernelGGL((k_deliver_records<FIG_RING, FIG_SLOT_BYTES, DABX_FIG_CHUNK_RECORDS>), grid, nt, 0, st, rd); break;
   default: set_error("launch_deliver_records: section %d", section); return DABX_E_ARG;
   }
   DABX_HIP(hipGetLastError());
@@ -654,6 +656,80 @@ int launch_tii_batch(int n, float2 *sums, float2 *pairs, const TiiCfgDev *cfg, c
                      int32_t *n_results, int32_t *n_found, hipStream_t st)
 {
   hipLaunchKernelGGL(k_tii_batch, dim3(n), dim3(256), 0, st, sums, pairs, cfg, turn, pattern, out, n_results, n_found);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---- the FIG walk on the device (fig_core.h): k_fig, the engine's stage behind the FIC decoder of the same frame (include/dabx.h,
+// dabx_set_fig_mode), and k_fig_batch, the same device function on crafted FIBs (dabx_fig_walk_device).  One wave per decoder: the decoder's
+// state comes into LDS with coalesced loads, the frame's 12 FIBs and CRC verdicts with one load per lane, the FIBs are walked in
+// transmission order, and the state goes back. ----
+struct FigLds {
+  FigState st;
+  uint32_t fib[96];                              // 12 FIBs of 32 bytes
+  uint32_t crc[3];                               // their 12 verdicts
+};
+
+__device__ inline void fig_state_move(uint32_t *dst, const uint32_t *src, int lane)
+{
+  for (int i = lane; i < (int)(sizeof(FigState) / 4); i += 64) dst[i] = src[i];
+  fig_sync();
+}
+
+// grid = n_streams, 64 threads, front-end stream, behind k_fic_frame and the frame's count (k_frame_tail, k_fic_advance) and in front of the
+// next frame's k_fic_frame: the frame's slot of fib_out is read before anything can rewrite it, and no frame is skipped.  A stream with the
+// mode off, or without a frame in this step, returns at once.
+__global__ __launch_bounds__(64) void k_fig(const StreamCtl *ctl, const uint8_t *fib_out, const uint8_t *fib_crc, int out_frames, FigDev f)
+{
+  __shared__ FigLds w;
+  const int s = blockIdx.x, lane = threadIdx.x;
+  if (!f.on[s]) return;
+  const StreamCtl &c = ctl[s];
+  if (!c.frame_ok || c.frames <= 0) return;
+  const long long frame = c.frames - 1;                      // (the frame has been counted)
+  const size_t slot = (size_t)s * out_frames + (size_t)(frame % out_frames);
+  w.fib[lane] = reinterpret_cast<const uint32_t *>(fib_out + slot * 384)[lane];
+  if (lane < 32) w.fib[64 + lane] = reinterpret_cast<const uint32_t *>(fib_out + slot * 384)[64 + lane];
+  if (lane < 3) w.crc[lane] = reinterpret_cast<const uint32_t *>(fib_crc + slot * 12)[lane];
+  fig_state_move(reinterpret_cast<uint32_t *>(&w.st), reinterpret_cast<const uint32_t *>(f.st + s), lane);
+  if (w.st.fibs < 12 * frame) w.st.fibs = 12 * frame;        // FIB k of frame n is FIB 12 n + k of the stream, as dabx_follow_fic counts
+  fig_sync();
+  const FigOut o{f.labels + (size_t)s * FIG_LAB_SLOTS, f.ring + (size_t)s * FIG_RING};
+  const uint8_t *fb = reinterpret_cast<const uint8_t *>(w.fib), *ok = reinterpret_cast<const uint8_t *>(w.crc);
+  for (int i = 0; i < 12; i++) fig_walk_fib(w.st, fb + 32 * i, fig_u(ok[i]) != 0, o, lane);
+  fig_sync();
+  fig_state_move(reinterpret_cast<uint32_t *>(f.st + s), reinterpret_cast<const uint32_t *>(&w.st), lane);
+}
+
+int launch_fig(const EngineDev &e, const FigDev &f, hipStream_t st)
+{
+  hipLaunchKernelGGL(k_fig, dim3(e.n_streams), dim3(64), 0, st, e.ctl, e.fib_out, e.fib_crc, e.out_frames, f);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+
+// grid = n decoders, 64 threads: decoder d walks fibs[d][n_fibs][32] with crc_ok[d][n_fibs] from the state st[d]
+__global__ __launch_bounds__(64) void k_fig_batch(const uint8_t *fibs, const uint8_t *crc_ok, int n_fibs, FigState *st, dabx_fig_label *labels, dabx_fig_event *ring)
+{
+  __shared__ FigLds w;
+  const int d = blockIdx.x, lane = threadIdx.x;
+  fig_state_move(reinterpret_cast<uint32_t *>(&w.st), reinterpret_cast<const uint32_t *>(st + d), lane);
+  const FigOut o{labels + (size_t)d * FIG_LAB_SLOTS, ring + (size_t)d * FIG_RING};
+  const uint8_t *fb = reinterpret_cast<const uint8_t *>(w.fib);
+  for (int i = 0; i < n_fibs; i++) {
+    const size_t k = (size_t)d * n_fibs + i;
+    if (lane < 8) w.fib[lane] = reinterpret_cast<const uint32_t *>(fibs + k * 32)[lane];
+    fig_sync();
+    fig_walk_fib(w.st, fb, fig_u(crc_ok[k]) != 0, o, lane);
+    fig_sync();
+  }
+  fig_state_move(reinterpret_cast<uint32_t *>(st + d), reinterpret_cast<const uint32_t *>(&w.st), lane);
+}
+
+int launch_fig_batch(const uint8_t *fibs, const uint8_t *crc_ok, int n_decoders, int n_fibs, FigState *st, dabx_fig_label *labels, dabx_fig_event *ring,
+                     hipStream_t stream)
+{
+  hipLaunchKernelGGL(k_fig_batch, dim3(n_decoders), dim3(64), 0, stream, fibs, crc_ok, n_fibs, st, labels, ring);
   DABX_HIP(hipGetLastError());
   return 0;
 }

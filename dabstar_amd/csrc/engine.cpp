@@ -365,6 +365,7 @@ void dabx_destroy(dabx_engine *e)
   ingest_free(e);
   for (dabx_tii *t : e->tii) dabx_tii_destroy(t);
   tii_stage_free(e);
+  fig_stage_free(e);
   scope_stage_free(e);
   cir_stage_free(e);
   spectrum_stage_free(e);
@@ -833,6 +834,8 @@ int dabx_process(dabx_engine *e, int max_frames, int sync)
       if ((rc = launch_tii(e->dev, e->tiis.dev, e->stream))) return rc;
       e->tiis.launches++;
     }
+    // the FIG walk of the streams that have the mode on (deliver.hip): behind the frame's FIC decoder and its count, in front of the next frame's
+    if ((rc = fig_step(e))) return rc;
     e->level_dirty = true;
     if (++e->pending_frames == MSC_BATCH_FRAMES || i == max_frames - 1) {
       DeliverDev dv{};
@@ -1088,6 +1091,10 @@ int dabx_follow_fic(dabx_engine *e, int stream, dabx_reconf *out)
   if (!e || stream < 0 || stream >= e->dev.n_streams || !out) return DABX_E_ARG;
   memset(out, 0, sizeof(*out));
   out->at_cif = out->last_change_cif = -1;
+  if (e->fig.on_for(stream)) {
+    set_error("dabx_follow_fic: stream %d follows the FIC on the device (dabx_set_fig_mode): dabx_fig_follow", stream);
+    return DABX_E_STATE;
+  }
   StreamCtl c;
   int rc = fetch_ctl(e, stream, &c);
   if (rc) return rc;

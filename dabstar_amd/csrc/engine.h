@@ -11,6 +11,7 @@
 #include "scope_core.h"
 #include "cir_core.h"
 #include "spectrum_core.h"
+#include "fig_core.h"
 #include "rec_ring.h"
 #include "sdma.h"
 #include "iqfile.h"
@@ -83,7 +84,8 @@ struct Delivery {
     {DABX_DELIVER_TII, 4, DABX_TII_EVENT_SLOT_BYTES, &dabx_chunk_header_ext::off_tii},
     {DABX_DELIVER_SCOPE, DL_FRAMES, SCOPE_SLOT_BYTES, &dabx_chunk_header_ext::off_scope},
     {DABX_DELIVER_CIR, DABX_CIR_CHUNK_RECORDS, CIR_SLOT_BYTES, &dabx_chunk_header_ext::off_cir},
-    {DABX_DELIVER_SPECTRUM, DABX_SPECTRUM_CHUNK_RECORDS, SPEC_SLOT_BYTES, &dabx_chunk_header_ext::off_spectrum}};
+    {DABX_DELIVER_SPECTRUM, DABX_SPECTRUM_CHUNK_RECORDS, SPEC_SLOT_BYTES, &dabx_chunk_header_ext::off_spectrum},
+    {DABX_DELIVER_FIG, DABX_FIG_CHUNK_RECORDS, FIG_SLOT_BYTES, &dabx_chunk_header_ext::off_fig}};
   dabx_chunk_header_ext ext{};                   // the header's extension as it goes into a slab; zeros without a bit >= 256
   bool tii() const { return (what & DABX_DELIVER_TII) != 0; }
   bool mp2_audio() const { return (what & DABX_DELIVER_MP2_AUDIO) != 0; }      // the MP2 audio section (deliver.hip, k_deliver_mp2_audio), while a slot has the mode on
@@ -267,6 +269,20 @@ struct SpecStage : ListedStage<SpecCfgDev> {
   float *window = nullptr;                     // [2048] device (SpecDev::window)
 };
 
+// The FIG stage (include/dabx.h dabx_set_fig_mode, deliver.hip k_fig).  Nothing of it exists until the mode is first switched on: dev stays all
+// null, n_on stays 0 and no step launches the kernel.
+struct FigStage {
+  FigDev dev{};
+  int n_on = 0;                                // streams with the mode on
+  std::vector<int32_t> on;                     // [S] mirror of dev.on
+  std::vector<long long> seen;                 // [S] events dabx_read_fig_events has returned or passed
+  long long launches = 0;
+  bool timing = false;                         // dabx_internal_fig_timing: every launch between two events of its own
+  std::vector<hipEvent_t> timed;               // ... begin, end, begin, end, ...
+  bool exists() const { return dev.st != nullptr; }
+  bool on_for(int s) const { return exists() && on[(size_t)s] != 0; }
+};
+
 struct dabx_engine : dabx::EngineHead {         // (iqfile.h: the ring format, where iqfile.cpp can read it)
   dabx_config cfg{};
   EngineDev dev{};
@@ -288,6 +304,7 @@ struct dabx_engine : dabx::EngineHead {         // (iqfile.h: the ring format, w
   ScopeStage scope;                            // the IQ scope and carrier plots on the device
   CirStage cir;                                // the channel impulse response and the correlation plot on the device
   SpecStage spectrum;                          // the RF spectrum and waterfall rows on the device
+  FigStage fig;                                // the FIG walk on the device
   std::vector<void *> allocs;
   void *stage = nullptr;                       // host -> device staging of dabx_push_iq
   size_t stage_cap = 0;
@@ -368,6 +385,9 @@ void delivery_free(dabx_engine *e);
 void ingest_free(dabx_engine *e);
 // engine_tii.cpp
 void tii_stage_free(dabx_engine *e);
+// engine_fig.cpp
+void fig_stage_free(dabx_engine *e);
+int fig_step(dabx_engine *e);                     // k_fig behind a frame's FIC decoder, while a stream has the mode on
 // engine_scope.cpp
 void scope_stage_free(dabx_engine *e);
 // engine_cir.cpp

@@ -22,7 +22,8 @@ static_assert(DL_FRAMES == DABX_CHUNK_FRAMES, "include/dabx.h: DABX_CHUNK_FRAMES
 #endif
 // the record sections (engine.h, Delivery::rec): a row of a section's table (pipeline.h: the four are one layout); the gather copies 16-byte words
 static constexpr size_t rec_row_bytes = sizeof(dabx_chunk_scope);
-static_assert(rec_row_bytes % 16 == 0 && DABX_TII_EVENT_SLOT_BYTES % 16 == 0 && SCOPE_SLOT_BYTES % 16 == 0 && CIR_SLOT_BYTES % 16 == 0 && SPEC_SLOT_BYTES % 16 == 0,
+static_assert(rec_row_bytes % 16 == 0 && DABX_TII_EVENT_SLOT_BYTES % 16 == 0 && SCOPE_SLOT_BYTES % 16 == 0 && CIR_SLOT_BYTES % 16 == 0 && SPEC_SLOT_BYTES % 16 == 0 &&
+              FIG_SLOT_BYTES % 16 == 0 && sizeof(dabx_chunk_fig) == sizeof(dabx_chunk_scope) && offsetof(FigState, cnt) % 8 == 0,
               "a record section's slots are 16-aligned");
 
 // What a record section gathers from (RecDeliverDev::ring, ::total, ::stride): all null / 0 while the engine has no such stage
@@ -34,6 +35,10 @@ static RecSource rec_source(const dabx_engine *e, int section)
   case REC_SCOPE: if (e->scope.exists()) return {e->scope.dev.ring, &e->scope.dev.st->shows, (int32_t)(sizeof(ScopeState) / sizeof(long long))}; break;
   case REC_CIR: if (e->cir.exists()) return {e->cir.dev.ring, &e->cir.dev.st->shows, (int32_t)(sizeof(CirState) / sizeof(long long))}; break;
   case REC_SPECTRUM: if (e->spectrum.exists()) return {e->spectrum.dev.ring, &e->spectrum.dev.st->shows, (int32_t)(sizeof(SpecState) / sizeof(long long))}; break;
+  case REC_FIG:
+    if (e->fig.exists())
+      return {reinterpret_cast<const uint8_t *>(e->fig.dev.ring), reinterpret_cast<const long long *>(&e->fig.dev.st->cnt.events), (int32_t)(sizeof(FigState) / sizeof(long long))};
+    break;
   }
   return {nullptr, nullptr, 0};
 }
@@ -44,6 +49,7 @@ static bool rec_stream_on(const dabx_engine *e, int section, size_t s)
   case REC_SCOPE: return e->scope.exists() && e->scope.cfg[s].enable;
   case REC_CIR: return e->cir.exists() && e->cir.cfg[s].enable;
   case REC_SPECTRUM: return e->spectrum.exists() && e->spectrum.cfg[s].enable;
+  case REC_FIG: return e->fig.on_for((int)s);
   }
   return true;
 }
@@ -377,7 +383,7 @@ extern "C" {
 
 int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
 {
-  if (!e || (cfg && (cfg->host_slabs < 0 || cfg->host_slabs == 1 || cfg->host_slabs > 64 || (cfg->what & ~(1023 | DABX_DELIVER_AAC | DABX_DELIVER_SCOPE | DABX_DELIVER_CIR | DABX_DELIVER_SPECTRUM)) || cfg->copy_engine < 0 || cfg->copy_engine > 1))) {
+  if (!e || (cfg && (cfg->host_slabs < 0 || cfg->host_slabs == 1 || cfg->host_slabs > 64 || (cfg->what & ~(1023 | DABX_DELIVER_AAC | DABX_DELIVER_SCOPE | DABX_DELIVER_CIR | DABX_DELIVER_SPECTRUM | DABX_DELIVER_FIG)) || cfg->copy_engine < 0 || cfg->copy_engine > 1))) {
     set_error("dabx_delivery_open: bad argument");
     return DABX_E_ARG;
   }
@@ -405,14 +411,20 @@ int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
   }
   // ... and DABX_DELIVER_CIR, in the same way
   if (cfg && (cfg->what & DABX_DELIVER_CIR) &&
-      !(cfg->what & ~(DABX_DELIVER_SPECTRUM | DABX_DELIVER_CIR | DABX_DELIVER_SCOPE | DABX_DELIVER_AAC | DABX_DELIVER_MP2_AUDIO | DABX_DELIVER_TII | DABX_DELIVER_ETI))) {
+      !(cfg->what & ~(DABX_DELIVER_FIG | DABX_DELIVER_SPECTRUM | DABX_DELIVER_CIR | DABX_DELIVER_SCOPE | DABX_DELIVER_AAC | DABX_DELIVER_MP2_AUDIO | DABX_DELIVER_TII | DABX_DELIVER_ETI))) {
     set_error("dabx_delivery_open: DABX_DELIVER_CIR needs at least one DABX_DELIVER_* bit below 128 beside it");
     return DABX_E_ARG;
   }
   // ... and DABX_DELIVER_SPECTRUM, in the same way
   if (cfg && (cfg->what & DABX_DELIVER_SPECTRUM) &&
-      !(cfg->what & ~(DABX_DELIVER_SPECTRUM | DABX_DELIVER_CIR | DABX_DELIVER_SCOPE | DABX_DELIVER_AAC | DABX_DELIVER_MP2_AUDIO | DABX_DELIVER_TII | DABX_DELIVER_ETI))) {
+      !(cfg->what & ~(DABX_DELIVER_FIG | DABX_DELIVER_SPECTRUM | DABX_DELIVER_CIR | DABX_DELIVER_SCOPE | DABX_DELIVER_AAC | DABX_DELIVER_MP2_AUDIO | DABX_DELIVER_TII | DABX_DELIVER_ETI))) {
     set_error("dabx_delivery_open: DABX_DELIVER_SPECTRUM needs at least one DABX_DELIVER_* bit below 128 beside it");
+    return DABX_E_ARG;
+  }
+  // ... and DABX_DELIVER_FIG, in the same way
+  if (cfg && (cfg->what & DABX_DELIVER_FIG) &&
+      !(cfg->what & ~(DABX_DELIVER_FIG | DABX_DELIVER_SPECTRUM | DABX_DELIVER_CIR | DABX_DELIVER_SCOPE | DABX_DELIVER_AAC | DABX_DELIVER_MP2_AUDIO | DABX_DELIVER_TII | DABX_DELIVER_ETI))) {
+    set_error("dabx_delivery_open: DABX_DELIVER_FIG needs at least one DABX_DELIVER_* bit below 128 beside it");
     return DABX_E_ARG;
   }
   if (e->dl.open) { set_error("dabx_delivery_open: already open"); return DABX_E_STATE; }

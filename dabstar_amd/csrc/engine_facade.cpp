@@ -294,6 +294,7 @@ int dabx_internal_fic_decode(dabx_engine *e, const int32_t *present)
   int rc = 0;
   if (hipMemcpy(present_dev, present, bytes, hipMemcpyHostToDevice) != hipSuccess) { set_error("dabx_internal_fic_decode: copy failed"); rc = DABX_E_HIP; }
   if (!rc) rc = launch_fic_decode(e->dev, present_dev, e->stream);
+  if (!rc) rc = fig_step(e);
   const int rc2 = sync_all(e);
   (void)hipFree(present_dev);
   return rc ? rc : rc2;

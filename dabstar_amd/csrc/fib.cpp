@@ -4,7 +4,9 @@
 // EtiGenerator is (eti_handler/eti_generator.cpp:132-134, 335-380): decode every sub-channel announced in the FIC.
 // Follows decoder/fib_decoder.cpp:59-110 (FIG walk), fib_decoder_fig0.cpp:142-224 (FIG 0/1), :230-293 (FIG 0/2),
 // fib_table.h:44-117 (short-form table) and fib_decoder.cpp:547-557, 673-691 (getters).  Tiny, branchy, per-FIB:
-// stays on the host ("OUT OF SCOPE for GPU").
+// stays on the host ("OUT OF SCOPE for GPU").  Per FIB it is tiny; for an engine's worth of streams the same decisions run on the
+// device as well, one wave per stream behind the FIC decoder (fig_core.h, k_fig; include/dabx.h dabx_set_fig_mode), with this file as their
+// model: tests/test_fig_cases.py holds the two against each other FIB by FIB.
 #include "dabx_internal.h"
 #include "fig00.h"
 #include <cstring>

@@ -211,7 +211,7 @@ struct EtiDev {
 // dabx_chunk_cir, dabx_chunk_spectrum): the records a stage has written into its record ring (rec_ring.h) since the previous chunk -- the TII
 // events of k_tii (deliver.hip), the records of k_scope, of k_cir_finish and k_cir_corr, and of k_spectrum (pipeline.hip) -- out of the ring
 // into the slab's head part; gathered at chunk close on the front-end stream, in this order
-enum : int { REC_TII = 0, REC_SCOPE, REC_CIR, REC_SPECTRUM, N_REC_SECTIONS };
+enum : int { REC_TII = 0, REC_SCOPE, REC_CIR, REC_SPECTRUM, REC_FIG, N_REC_SECTIONS };
 struct RecDeliverDev {
   uint8_t *slab;
   unsigned long long off_table;           // the section's word of dabx_chunk_header_ext: its table of one row per stream

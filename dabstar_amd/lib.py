@@ -491,8 +491,9 @@ assert CHUNK_ETI.itemsize == 64
 DELIVER_TII = 256
 TII_MAX_RESULTS = 32
 CHUNK_EXT_MAGIC = 0x45584244                     # "DBXE"
-CHUNK_HEADER_EXT = np.dtype([("magic", "<u4"), ("bytes", "<u4"), ("off_tii", "<u8"), ("off_mp2_audio", "<u8"), ("off_aac", "<u8"), ("off_scope", "<u8"),
-                             ("off_cir", "<u8"), ("off_spectrum", "<u8"), ("reserved", "<u8", (1,))])
+CHUNK_HEADER_EXT = np.dtype({"names": ["magic", "bytes", "off_tii", "off_mp2_audio", "off_aac", "off_scope", "off_cir", "off_spectrum", "off_fig", "reserved"],
+                             "formats": ["<u4", "<u4", "<u8", "<u8", "<u8", "<u8", "<u8", "<u8", "<u8", ("<u8", (1,))],
+                             "offsets": [0, 4, 8, 16, 24, 32, 40, 48, 56, 56], "itemsize": 64})      # (off_fig is the last reserved word: one word, both names)
 CHUNK_TII = np.dtype([("first_event", "<i8"), ("n_events", "<i4"), ("events_lost", "<i4"), ("ev_off", "<u8"), ("events_total", "<i8")])
 TII_EVENT = np.dtype([("frame", "<i8"), ("n_results", "<i4"), ("n_found", "<i4"), ("frames_in_sum", "<i4"), ("epoch", "<i4"),
                       ("threshold_db", "<i4"), ("reserved", "<i4")])
@@ -646,6 +647,127 @@ DELIVER_SPECTRUM = 65536
 SPECTRUM_CHUNK_RECORDS = 6
 CHUNK_SPECTRUM = np.dtype([("first_record", "<i8"), ("n_records", "<i4"), ("records_lost", "<i4"), ("rec_off", "<u8"), ("records_total", "<i8")])
 assert SPECTRUM_RECORD.itemsize == 32 and SPECTRUM_LIMITS.itemsize == 32 and SPECTRUM_STATS.itemsize == 64 and CHUNK_SPECTRUM.itemsize == 32
+# the FIC followed on the device (include/dabx.h, dabx_set_fig_mode): dabx_fig_label, dabx_fig_event (its payload as 8 words: fig_event_dict
+# reads them by kind), dabx_fig_stats; the slab's FIG section (DELIVER_FIG = 262144, opt-in like DELIVER_SPECTRUM; 131072 stays refused like 1024, 4096 and 16384; announced by the header's
+# extension): one CHUNK_FIG per stream, then FIG_CHUNK_RECORDS event slots for every stream that had the mode on when the delivery was opened
+DELIVER_FIG = 262144
+FIG_MAX_COMPONENTS, FIG_MAX_PACKETS, FIG_MAX_LABELS, FIG_MAX_EVENTS, FIG_CHUNK_RECORDS = 256, 64, 64, 256, 32
+FIG_ANNOUNCE, FIG_SWAP, FIG_RESTART, FIG_TABLE, FIG_LABEL_EVENT = 1, 2, 3, 4, 5
+FIG_LABEL = np.dtype([("id", "<u4"), ("char_flags", "<u2"), ("kind", "u1"), ("charset", "u1"), ("label", "u1", (16,)), ("pd", "u1"), ("scids", "u1"),
+                      ("reserved", "u1", (6,))])
+FIG_EVENT = np.dtype([("kind", "<i4"), ("epoch", "<i4"), ("frame", "<i8"), ("fib", "<i8"), ("cif", "<i8"), ("words", "<i4", (8,))])
+FIG_COUNTERS = ("fibs_good", "fibs_bad", "figs", "end_markers", "fig_overrun", "fig_other_type", "fig0_other_ext", "fig00", "subch_new", "subch_known",
+                "comp_new", "comp_known", "packet_new", "packet_known", "restarts", "swaps", "announces", "over_components", "over_packets",
+                "over_labels", "label_new", "label_known", "label_charset", "label_short", "label_other_ext", "events", "launches")
+FIG_STATS = np.dtype([(k, "<i8") for k in FIG_COUNTERS] + [("reserved", "<i8", (5,))])
+CHUNK_FIG = np.dtype([("first_record", "<i8"), ("n_records", "<i4"), ("records_lost", "<i4"), ("rec_off", "<u8"), ("records_total", "<i8")])
+assert (FIG_LABEL.itemsize, FIG_EVENT.itemsize, FIG_STATS.itemsize, CHUNK_FIG.itemsize) == (32, 64, 256, 32)
+
+
+class FigConfig(C.Structure):
+    _fields_ = [("enable", C.c_int32), ("reference_quirks", C.c_int32), ("reserved", C.c_int32 * 2)]          # dabx_fig_config
+
+
+def fig_label_dict(r):
+    """A FIG_LABEL record as plain values (label: the 16 raw bytes)."""
+    return dict(id=int(r["id"]), char_flags=int(r["char_flags"]), kind=int(r["kind"]), charset=int(r["charset"]), label=bytes(bytearray(r["label"])),
+                pd=int(r["pd"]), scids=int(r["scids"]))
+
+
+def fig_event_dict(ev):
+    """A FIG_EVENT record as plain values: the head (kind, epoch, frame, fib, cif) and the payload its kind defines."""
+    out = dict(kind=int(ev["kind"]), epoch=int(ev["epoch"]), frame=int(ev["frame"]), fib=int(ev["fib"]), cif=int(ev["cif"]))
+    w = [int(v) for v in ev["words"]]
+    if out["kind"] == FIG_ANNOUNCE:
+        out.update(flags=w[0], occurrence_change=w[1], at_cif=(w[2] & 0xFFFFFFFF) | (w[3] << 32))
+    elif out["kind"] == FIG_SWAP:
+        out.update(n_changes=w[0], n_subch=w[1], n_components=w[2], n_packets=w[3])
+    elif out["kind"] == FIG_TABLE:
+        out.update(next=w[0], n_subch=w[1], n_components=w[2], n_packets=w[3])
+    elif out["kind"] == FIG_LABEL_EVENT:
+        out.update(label=fig_label_dict(np.array(ev["words"], "<i4").view(FIG_LABEL)[0]))
+    return out
+
+
+def _subch_dict(q):
+    return {k: int(getattr(q, k)) for k in ("subch_id", "cu_start", "cu_size", "kbps", "prot_level", "short_form", "dab_plus")}
+
+
+def _fig_rows(n, info, n_tab, subch, packets, n_labels, labels, stats, n_events, events):
+    """the rows of dabx_fig_walk_device's outputs as one dict per decoder"""
+    out = []
+    for d in range(n):
+        ne = int(n_events[d])
+        out.append(dict(
+            info={k: int(getattr(info[d], k)) for k, _ in FibdecInfo._fields_ if not k.startswith("reserved")},
+            n_tab=n_tab[d].reshape(2, 3).tolist(),
+            subch=[[_subch_dict(subch[(d * 2 + k) * 64 + i]) for i in range(int(n_tab[d, 3 * k]))] for k in range(2)],
+            packets=[packets[d, k, :int(n_tab[d, 3 * k + 2])].copy() for k in range(2)],
+            labels=[fig_label_dict(r) for r in labels[d, :int(n_labels[d])]],
+            stats={k: int(stats[d][k]) for k in FIG_COUNTERS},
+            n_events=ne,
+            events=[fig_event_dict(e) for e in events[d, :min(ne, FIG_MAX_EVENTS)]]))
+    return out
+
+
+def _fig_out_buffers(n):
+    return ((FibdecInfo * n)(), np.zeros((n, 6), np.int32), (SubchDesc * (n * 2 * 64))(), np.zeros((n, 2, FIG_MAX_PACKETS), PACKET_COMPONENT),
+            np.zeros(n, np.int32), np.zeros((n, 4 * FIG_MAX_LABELS), FIG_LABEL), np.zeros(n, FIG_STATS), np.zeros(n, np.int64),
+            np.zeros((n, FIG_MAX_EVENTS), FIG_EVENT))
+
+
+def fig_walk_device(fibs, crc_ok, reference_quirks=False):
+    """The FIG walk on the device, n fresh decoders in one call (a wave each, the device function of the engine's k_fig): fibs [n, n_fibs,
+    32] uint8, crc_ok [n, n_fibs] -> one dict per decoder: info (as FibDecoder.info), n_tab [[current], [next]] x (sub-channels, components,
+    packets), subch / packets of both configurations as the getters return them, labels, stats, n_events and the newest events."""
+    fibs = np.ascontiguousarray(fibs, np.uint8)
+    if fibs.ndim != 3 or fibs.shape[2] != 32:
+        raise ValueError("fig_walk_device needs fibs [n, n_fibs, 32]")
+    n, nf = fibs.shape[0], fibs.shape[1]
+    crc_ok = np.ascontiguousarray(crc_ok, np.uint8).reshape(n, nf)
+    bufs = _fig_out_buffers(n)
+    info, n_tab, subch, packets, n_labels, labels, stats, n_events, events = bufs
+    L = load()
+    L.dabx_fig_walk_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 9
+    check(L.dabx_fig_walk_device(_p(fibs), _p(crc_ok), n, nf, int(bool(reference_quirks)), info, _p(n_tab), subch, _p(packets), _p(n_labels), _p(labels),
+                                 _p(stats), _p(n_events), _p(events)))
+    return _fig_rows(n, *bufs)
+
+
+def fig_timing(engine, on, max_launches=4096):
+    """Internal measuring entry (tools/bench_fig.py): starts (on = True) or stops timing every k_fig launch with HIP events of its own;
+    returns the milliseconds of the launches timed since the previous call, oldest first."""
+    ms = np.zeros(max_launches, np.float32)
+    L = load()
+    L.dabx_internal_fig_timing.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    n = check(L.dabx_internal_fig_timing(engine._h, int(bool(on)), _p(ms), max_launches))
+    return ms[:min(n, max_launches)].copy()
+
+
+class FigHostDecoder:
+    """Internal test entry (not part of include/dabx.h): the HOST build of the device's FIG walk (csrc/fig_core.h) on a decoder kept here as
+    bytes.  walk(fibs, crc_ok) feeds FIBs, read() presents the decoder as one row of fig_walk_device.  Needs no device."""
+
+    def __init__(self, reference_quirks=False):
+        L = load()
+        self._buf = np.zeros(L.dabx_internal_fig_host_bytes(), np.uint8)
+        L.dabx_internal_fig_host_init.argtypes = [C.c_void_p, C.c_int]
+        check(L.dabx_internal_fig_host_init(_p(self._buf), int(bool(reference_quirks))))
+
+    def walk(self, fibs, crc_ok):
+        fibs = np.ascontiguousarray(fibs, np.uint8).reshape(-1, 32)
+        crc_ok = np.ascontiguousarray(crc_ok, np.uint8).reshape(-1)
+        L = load()
+        L.dabx_internal_fig_host_walk.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        check(L.dabx_internal_fig_host_walk(_p(self._buf), _p(fibs), _p(crc_ok), fibs.shape[0]))
+
+    def read(self):
+        bufs = _fig_out_buffers(1)
+        info, n_tab, subch, packets, n_labels, labels, stats, n_events, events = bufs
+        L = load()
+        L.dabx_internal_fig_host_read.argtypes = [C.c_void_p] * 10
+        check(L.dabx_internal_fig_host_read(_p(self._buf), info, _p(n_tab), subch, _p(packets), _p(n_labels), _p(labels), _p(stats), _p(n_events), _p(events)))
+        return _fig_rows(1, *bufs)[0]
 
 
 class SpectrumConfig(C.Structure):
@@ -852,6 +974,7 @@ class Chunk:
         self.scope_table = None                 # the scope section: [S] CHUNK_SCOPE, or None when the slab has none
         self.cir_table = None                   # the CIR section: [S] CHUNK_CIR, or None when the slab has none
         self.spectrum_table = None              # the spectrum section: [S] CHUNK_SPECTRUM, or None when the slab has none
+        self.fig_table = None                   # the FIG section: [S] CHUNK_FIG, or None when the slab has none
         if int(h["what"]) & ~255:
             self.header_ext = self.raw[128:192].view(CHUNK_HEADER_EXT)[0]
             if int(self.header_ext["magic"]) != CHUNK_EXT_MAGIC or int(self.header_ext["bytes"]) < 64:
@@ -874,6 +997,9 @@ class Chunk:
             if int(self.header_ext["off_spectrum"]):
                 o = int(self.header_ext["off_spectrum"])
                 self.spectrum_table = self.raw[o:o + S * 32].view(CHUNK_SPECTRUM)
+            if int(self.header_ext["off_fig"]):
+                o = int(self.header_ext["off_fig"])
+                self.fig_table = self.raw[o:o + S * 32].view(CHUNK_FIG)
         self.eti_table = None                  # the ETI section: [S] CHUNK_ETI, or None when the slab has none
         if int(h["off_eti"]):
             self.eti_table = self.raw[int(h["off_eti"]):int(h["off_eti"]) + S * 64].view(CHUNK_ETI)
@@ -923,6 +1049,11 @@ class Chunk:
         return [(self.raw[o:o + 32].view(SPECTRUM_RECORD)[0], self.raw[o + 32:o + 64].view(SPECTRUM_LIMITS)[0],
                  self.raw[o + 64:o + 64 + 4 * SPECTRUM_BINS].view(np.float32), self.raw[o + 64 + 4 * SPECTRUM_BINS:o + SPECTRUM_SLOT_BYTES])
                 for o in self._record_slots(self.spectrum_table, stream, SPECTRUM_SLOT_BYTES)]
+
+    def fig(self, stream):
+        """FIG change events of `stream` in this chunk, oldest first: a list of dicts (fig_event_dict).  Empty when the slab has no FIG section
+        or the stream had the mode off when the delivery was opened."""
+        return [fig_event_dict(self.raw[o:o + 64].view(FIG_EVENT)[0]) for o in self._record_slots(self.fig_table, stream, 64)]
 
     def eti(self, stream):
         """ETI(NI) frames of `stream` in this chunk: (its CHUNK_ETI record, [n_eti, 6144] uint8), views; the rows are contiguous and in CIF
@@ -1191,6 +1322,67 @@ class Engine:
         L.dabx_get_tii_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         check(L.dabx_get_tii_stats(self._h, stream, _p(st)))
         return {k: int(st[k][0]) for k in TII_STATS.names if k != "reserved"}
+
+    def set_fig_mode(self, stream, enable=True, reference_quirks=False):
+        """The stream's FIC followed on the device (dabx_set_fig_mode; stream = -1: all streams): FIG 0/0-0/3 and the labels of FIG 1 go into
+        a database on the device (fig_info, fig_subchannels, fig_packet_components, fig_labels, fig_follow), changes are reported as events
+        (read_fig_events, or in bulk with DELIVER_FIG)."""
+        cfg = FigConfig(enable=int(bool(enable)), reference_quirks=int(bool(reference_quirks)))
+        L = load()
+        L.dabx_set_fig_mode.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        check(L.dabx_set_fig_mode(self._h, stream, C.byref(cfg)))
+
+    def fig_info(self, stream):
+        out = FibdecInfo()
+        L = load()
+        L.dabx_fig_info.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        check(L.dabx_fig_info(self._h, stream, C.byref(out)))
+        return {k: getattr(out, k) for k, _ in FibdecInfo._fields_ if not k.startswith("reserved")}
+
+    def fig_subchannels(self, stream, next=False, max_out=64):
+        out = (SubchDesc * max_out)()
+        L = load()
+        L.dabx_fig_subchannels.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
+        n = check(L.dabx_fig_subchannels(self._h, stream, int(next), out, max_out))
+        return [out[i] for i in range(n)]
+
+    def fig_packet_components(self, stream, next=False, max_out=FIG_MAX_PACKETS):
+        out = np.zeros(max(1, max_out), PACKET_COMPONENT)
+        L = load()
+        L.dabx_fig_packet_components.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
+        n = check(L.dabx_fig_packet_components(self._h, stream, int(next), _p(out), max_out))
+        return out[:n]
+
+    def fig_follow(self, stream):
+        out = Reconf()
+        L = load()
+        L.dabx_fig_follow.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        check(L.dabx_fig_follow(self._h, stream, C.byref(out)))
+        return {k: getattr(out, k) for k, _ in Reconf._fields_ if not k.startswith("reserved")}
+
+    def fig_labels(self, stream, max_out=4 * FIG_MAX_LABELS):
+        """Every label filed so far, in order of filing: a list of dicts (fig_label_dict)."""
+        out = np.zeros(max(1, max_out), FIG_LABEL)
+        L = load()
+        L.dabx_fig_labels.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        n = check(L.dabx_fig_labels(self._h, stream, _p(out), max_out))
+        return [fig_label_dict(r) for r in out[:n]]
+
+    def fig_stats(self, stream):
+        st = np.zeros(1, FIG_STATS)
+        L = load()
+        L.dabx_get_fig_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        check(L.dabx_get_fig_stats(self._h, stream, _p(st)))
+        return {k: int(st[k][0]) for k in FIG_COUNTERS}
+
+    def read_fig_events(self, stream, max_events=FIG_MAX_EVENTS):
+        """The events written since the previous call that the ring still holds, oldest first: ([fig_event_dict], events lost)."""
+        ev = np.zeros(max(1, max_events), FIG_EVENT)
+        lost = C.c_int32(0)
+        L = load()
+        L.dabx_read_fig_events.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        n = check(L.dabx_read_fig_events(self._h, stream, max_events, _p(ev), C.byref(lost)))
+        return [fig_event_dict(e) for e in ev[:n]], lost.value
 
     def set_scope_mode(self, stream, iq_type=0, carrier_type=0, symbol=0, enable=True):
         """The stream's IQ scope and carrier plot on the device (dabx_set_scope_mode; stream = -1: all streams): a record whenever the

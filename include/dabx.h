@@ -993,7 +993,14 @@ enum { DABX_DELIVER_FIB = 1, DABX_DELIVER_MSC = 2, DABX_DELIVER_SF = 4,
           DABX_DELIVER_ETI, _TII, _MP2_AUDIO, _AAC, _SCOPE and _CIR beside it is DABX_E_ARG, and without the bit a slab,
           dabx_delivery_slab_bytes and the kernels launched are exactly what they are without it.  With the bit the header is followed by a
           dabx_chunk_header_ext.  1024, 4096 and 16384 stay refused with DABX_E_ARG, as ever */
-       DABX_DELIVER_SPECTRUM = 65536 };
+       DABX_DELIVER_SPECTRUM = 65536,
+       /* the FIG change events of every stream that follows the FIC on the device (dabx_set_fig_mode; the FIG section, dabx_chunk_fig
+          below).  Opt-in exactly like the seven bits above: what == 0 does NOT include it, the bit alone or with only DABX_DELIVER_ETI, _TII,
+          _MP2_AUDIO, _AAC, _SCOPE, _CIR and _SPECTRUM beside it is DABX_E_ARG, and without the bit a slab, dabx_delivery_slab_bytes and the
+          kernels launched are exactly what they are without it.  With the bit the header is followed by a dabx_chunk_header_ext.  The value
+          is 262144, not 131072: the mask 131072 has always been refused with DABX_E_ARG, alone and beside other bits, and callers rely on
+          that (tests/test_gpu_spectrum_delivery.py), so 131072 stays refused, as 1024, 4096 and 16384 do */
+       DABX_DELIVER_FIG = 262144 };
 typedef struct {
   int32_t host_slabs;       /* page-locked host slabs, >= 2 (0 = default 4) */
   int32_t what;             /* DABX_DELIVER_* mask, 0 = everything */
@@ -1025,7 +1032,12 @@ typedef struct {
   uint64_t off_scope;       /* the scope section: dabx_chunk_scope[n_streams]; 0 = the slab has none */
   uint64_t off_cir;         /* the CIR section: dabx_chunk_cir[n_streams]; 0 = the slab has none (the first of three words that were reserved) */
   uint64_t off_spectrum;    /* the spectrum section: dabx_chunk_spectrum[n_streams]; 0 = the slab has none (the second of them) */
-  uint64_t reserved[1];
+  /* the FIG section: dabx_chunk_fig[n_streams]; 0 = the slab has none.  It takes the last of the reserved words, which keeps its old name
+     beside the new one (an anonymous union: C11 and C++; compilers that speak GNU C take it in C99 as well) */
+#if defined(__GNUC__)
+  __extension__
+#endif
+  union { uint64_t off_fig; uint64_t reserved[1]; };
 } dabx_chunk_header_ext;    /* 64 bytes */
 typedef struct {
   int64_t first_frame;      /* index, since the stream was opened, of the first frame in the chunk */
@@ -1189,6 +1201,21 @@ typedef struct {
   uint64_t rec_off;         /* 0 = the stream has no room in this delivery */
   int64_t  records_total;   /* records the stream has written so far: first_record + n_records */
 } dabx_chunk_spectrum;      /* 32 bytes */
+/* The FIG section (DABX_DELIVER_FIG; "The FIC followed on the device" below): one dabx_chunk_fig per stream from
+ * dabx_chunk_header_ext.off_fig, in the slab's head part behind the spectrum section (or where that would be), followed by room for
+ * DABX_FIG_CHUNK_RECORDS event slots for each stream that has the mode on WHEN THE DELIVERY IS OPENED (a stream switched on later has no
+ * room and delivers none: rec_off = 0).  A slot is a dabx_fig_event, byte for byte what dabx_read_fig_events returns; stream s's n_records
+ * slots lie one behind the other from rec_off, oldest first.  The room is sized for a real ensemble's start-up: about 18 sub-channels' worth
+ * of table and label events spread over the first second.  Of more events than that in one chunk the newest are delivered and the rest
+ * counted in records_lost: events are notifications, the database (dabx_fig_subchannels, dabx_fig_labels, ...) stays complete.  Gathered
+ * on the front-end stream when the chunk closes (k_deliver_records), with a cursor of its own. */
+#define DABX_FIG_CHUNK_RECORDS 32
+typedef struct {
+  int64_t  first_record;    /* number, since the stream's mode was switched on, of the first event in the chunk */
+  int32_t  n_records, records_lost;
+  uint64_t rec_off;         /* 0 = the stream has no room in this delivery */
+  int64_t  records_total;   /* events the stream has written so far: first_record + n_records */
+} dabx_chunk_fig;           /* 32 bytes */
 typedef struct {
   uint64_t seq;
   const void *data;         /* the host slab: valid until dabx_delivery_release(seq) */
@@ -1815,6 +1842,93 @@ typedef struct {
   int64_t  superframes, records, frames, frame_bytes, lost_len, lost_crc;      /* dabx_aac_stream_stats after the chunk's batch */
   int64_t  reserved[5];
 } dabx_chunk_aac;            /* 128 bytes */
+
+/* ------------------------------------------------------------------------------------------------------------
+ * The FIC followed on the device (csrc/fig_core.h, k_fig): what dabx_fibdec does with FIG 0/0 .. 0/3 -- walk_fib's decisions bit for bit,
+ * both swap rules -- plus the labels of FIG 1/0, 1/1, 1/4 and 1/5 (fib_decoder_fig1.cpp:49-152, fib_decoder.cpp:744-778), one wave per
+ * stream behind every decoded frame, with a per-stream database that stays on the device.  A label is filed iff its key is unknown (1/0:
+ * the one ensemble label; 1/1: SId16; 1/4: P/D + SCIdS + SId; 1/5: SId32) and its charset is 0, 6 or 15 (charsets.h:50-55); filed are the 16
+ * raw bytes, the charset, the character flag field and the identifier.  Charset conversion, the short label and FIG 1/6 stay with the host.
+ * A restart (_restart_fib_decoding, fib_decoder.cpp:131-141) clears the labels too.
+ * Where it departs from the reference:
+ *  - the tables are bounded.  64 sub-channels per configuration are all there can be (6-bit id).  The others are counted guards that a legal
+ *    ensemble cannot reach: DABX_FIG_MAX_COMPONENTS service components and DABX_FIG_MAX_PACKETS packet components per configuration,
+ *    DABX_FIG_MAX_LABELS labels per kind.  An entry that does not fit is dropped and counted (over_components, over_packets, over_labels);
+ *  - a FIG 1 whose label field (16 bytes + the flag field) does not lie inside its own FIG, by the header's length, is dropped and counted
+ *    (label_short).  The reference reads on into whatever follows.  Like walk_fib the walk stops at a FIG that runs past byte 30.
+ * The events below are lossy notifications, newest kept; the database (dabx_fig_info, _subchannels, _packet_components, _labels, _follow)
+ * is the truth. */
+#define DABX_FIG_MAX_COMPONENTS 256
+#define DABX_FIG_MAX_PACKETS 64
+#define DABX_FIG_MAX_LABELS 64
+#define DABX_FIG_MAX_EVENTS 256       /* events a stream's ring holds */
+typedef struct {
+  int32_t enable;             /* 0: off -- the stream's database is dropped, dabx_follow_fic works again */
+  int32_t reference_quirks;   /* dabx_fibdec_set_reference_quirks: swap only after change flags 3 */
+  int32_t reserved[2];
+} dabx_fig_config;
+enum { DABX_FIG_LABEL_ENSEMBLE = 0, DABX_FIG_LABEL_SERVICE = 1, DABX_FIG_LABEL_COMPONENT = 4, DABX_FIG_LABEL_DATA_SERVICE = 5 };
+typedef struct {
+  uint32_t id;                /* 1/0: EId, otherwise the SId */
+  uint16_t char_flags;        /* CharFlagField */
+  uint8_t  kind;              /* the FIG 1 extension: 0, 1, 4, 5 */
+  uint8_t  charset;           /* 0 EBU Latin, 6 UCS-2, 15 UTF-8 */
+  uint8_t  label[16];         /* as transmitted */
+  uint8_t  pd, scids;         /* 1/4 only */
+  uint8_t  reserved[6];
+} dabx_fig_label;             /* 32 bytes */
+enum { DABX_FIG_ANNOUNCE = 1, DABX_FIG_SWAP = 2, DABX_FIG_RESTART = 3, DABX_FIG_TABLE = 4, DABX_FIG_LABEL = 5 };
+typedef struct {
+  int32_t kind;               /* DABX_FIG_* */
+  int32_t epoch;              /* restarts so far (a RESTART event carries the new count) */
+  int64_t frame;              /* fib / 12 */
+  int64_t fib;                /* index of the FIB within the stream, counted like dabx_fibdec_info.fibs_processed (TABLE: the frame's last) */
+  int64_t cif;                /* 4 * (fib / 12) + (fib % 12) / 3 */
+  union {
+    struct { int32_t flags, occurrence_change; int64_t at_cif; } announce;      /* change flags 0 -> non-zero; at_cif as dabx_follow_fic */
+    struct { int32_t n_changes, n_subch, n_components, n_packets; } swap;       /* the new current configuration */
+    struct { int32_t next, n_subch, n_components, n_packets; } table;           /* at most one per frame and configuration that gained an entry */
+    dabx_fig_label label;                                                       /* a label was filed */
+    int32_t words[8];
+  } u;
+} dabx_fig_event;             /* 64 bytes */
+typedef struct {
+  int64_t fibs_good, fibs_bad;                   /* FIBs walked / counted and skipped for their CRC */
+  int64_t figs, end_markers, fig_overrun;        /* FIGs stepped through; walks ended by 0xFF; by a FIG running past byte 30 */
+  int64_t fig_other_type, fig0_other_ext;        /* FIGs of type 2..7; FIG 0 of another extension (or a FIG 0/0 shorter than 5) */
+  int64_t fig00;
+  int64_t subch_new, subch_known, comp_new, comp_known, packet_new, packet_known;
+  int64_t restarts, swaps, announces;
+  int64_t over_components, over_packets, over_labels;       /* the guards: entries dropped because the table was full */
+  int64_t label_new, label_known, label_charset, label_short, label_other_ext;
+  int64_t events;                                /* events written to the ring */
+  int64_t launches;                              /* k_fig launches of the engine */
+  int64_t reserved[5];
+} dabx_fig_stats;             /* 256 bytes */
+/* stream -1 = all.  cfg == NULL or enable != 0: on.  A stream that is switched on starts from an empty database with the FIB count of the
+ * frames decoded so far, as a dabx_follow_fic decoder would; switching off drops it.  While no stream has the mode on nothing is launched,
+ * and an engine that never enables it allocates nothing.  dabx_follow_fic on a stream with the mode on is refused (DABX_E_STATE).  Drains
+ * the engine. */
+int  dabx_set_fig_mode(dabx_engine *e, int stream, const dabx_fig_config *cfg);
+/* The database of a stream with the mode on (DABX_E_STATE otherwise), one device-to-host copy per call.  As dabx_fibdec_get_info,
+ * dabx_fibdec_subchannels (with the dab_plus join), dabx_fibdec_packet_components (with the sid join) and dabx_follow_fic (frames_missed
+ * is always 0: no frame is skipped); dabx_fig_labels returns every filed label in order of filing. */
+int  dabx_fig_info(dabx_engine *e, int stream, dabx_fibdec_info *out);
+int  dabx_fig_subchannels(dabx_engine *e, int stream, int next, dabx_subch_desc *out, int max_out);
+int  dabx_fig_packet_components(dabx_engine *e, int stream, int next, dabx_packet_component *out, int max_out);
+int  dabx_fig_follow(dabx_engine *e, int stream, dabx_reconf *out);
+int  dabx_fig_labels(dabx_engine *e, int stream, dabx_fig_label *out, int max_out);
+int  dabx_get_fig_stats(dabx_engine *e, int stream, dabx_fig_stats *out);
+/* The newest events still in the stream's ring that no earlier call has returned, oldest first, at most max_events; *lost (optional): those
+ * that had left the ring.  The rule of dabx_read_tii_events. */
+int  dabx_read_fig_events(dabx_engine *e, int stream, int max_events, dabx_fig_event *ev, int32_t *lost);
+/* The walk on crafted FIBs, without an engine: n_decoders fresh decoders, one wave each, decoder d walks fibs[d][n_fibs][32] with
+ * crc_ok[d][n_fibs].  Every output is optional (NULL) and has a row per decoder: info[d]; n_tab[d][2][3] sizes of (current, next) x
+ * (sub-channels, components, packets); subch[d][2][64] and packets[d][2][DABX_FIG_MAX_PACKETS] as the getters return them; n_labels[d] and
+ * labels[d][4 * DABX_FIG_MAX_LABELS]; stats[d]; n_events[d] = events written, events[d][DABX_FIG_MAX_EVENTS] the newest of them, oldest first. */
+int  dabx_fig_walk_device(const uint8_t *fibs, const uint8_t *crc_ok, int n_decoders, int n_fibs, int reference_quirks, dabx_fibdec_info *info,
+                          int32_t *n_tab, dabx_subch_desc *subch, dabx_packet_component *packets, int32_t *n_labels, dabx_fig_label *labels,
+                          dabx_fig_stats *stats, int64_t *n_events, dabx_fig_event *events);
 
 #ifdef __cplusplus
 }
