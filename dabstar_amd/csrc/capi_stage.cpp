@@ -238,12 +238,38 @@ int dabx_tii_process_device(int n, const float *sums, float *pairs, const dabx_t
   return dnf.to_host(n_found, 4 * N);
 }
 
-// The FIG walk on the device: fig_walk_fib (fig_core.h), the body of the engine's k_fig, one wave per decoder
-int dabx_fig_walk_device(const uint8_t *fibs, const uint8_t *crc_ok, int n_decoders, int n_fibs, int reference_quirks, dabx_fibdec_info *info,
-                         int32_t *n_tab, dabx_subch_desc *subch, dabx_packet_component *packets, int32_t *n_labels, dabx_fig_label *labels,
-                         dabx_fig_stats *stats, int64_t *n_events, dabx_fig_event *events)
+// The FIG walk on the device: fig_walk_fib (fig_core.h), the body of the engine's k_fig, one wave per decoder.  With `si` the decoders follow
+// the service information too (fig_si_core.h, k_fig_si_batch) and k_fig_directory joins both configurations of each.
+struct FigSiOuts {                               // one decoder's rows of dabx_fig_si_walk_device's SI outputs, every one optional
+  dabx_fig_si_scalars *info; dabx_fig_si_stats *stats; dabx_fig_global_def *gd; dabx_fig_user_apps_entry *ua; dabx_fig_fec_scheme *fec; dabx_fig_cluster *cl;
+  dabx_fig_language *lang; dabx_fig_programme_type *pty; int32_t *n_dir; dabx_fig_service *dir;
+  FigSiOuts row(size_t d) const
+  {
+    return FigSiOuts{info ? info + d : nullptr, stats ? stats + d : nullptr, gd ? gd + 2 * SI_MAX_GD * d : nullptr, ua ? ua + 2 * SI_MAX_UA * d : nullptr,
+                     fec ? fec + 2 * SI_MAX_FEC * d : nullptr, cl ? cl + 2 * SI_MAX_CL * d : nullptr, lang ? lang + SI_MAX_LANG * d : nullptr,
+                     pty ? pty + SI_MAX_PTY * d : nullptr, n_dir ? n_dir + 2 * d : nullptr, dir ? dir + 2 * (size_t)FIG_MAX_COMP * d : nullptr};
+  }
+};
+// the tables of one decoder (not its directory)
+static void fig_si_present(const FigState &t, const FigSiState &s, const FigSiOuts &o)
 {
-  if (!fibs || !crc_ok || n_decoders <= 0 || n_decoders > 65535 || n_fibs <= 0 || n_fibs > 1 << 20) { set_error("dabx_fig_walk_device: bad argument"); return DABX_E_ARG; }
+  if (o.info) fig_si_info(t, s, o.info);
+  if (o.stats) *o.stats = s.cnt;
+  for (int k = 0; k < 2; k++) {
+    if (o.gd) fig_si_global_defs(t, s, k, o.gd + (size_t)k * SI_MAX_GD, SI_MAX_GD);
+    if (o.ua) fig_si_user_apps(t, s, k, o.ua + (size_t)k * SI_MAX_UA, SI_MAX_UA);
+    if (o.fec) fig_si_fec(t, s, k, o.fec + (size_t)k * SI_MAX_FEC, SI_MAX_FEC);
+    if (o.cl) fig_si_clusters(t, s, k, o.cl + (size_t)k * SI_MAX_CL, SI_MAX_CL);
+  }
+  if (o.lang) fig_si_languages(s, o.lang, SI_MAX_LANG);
+  if (o.pty) fig_si_ptys(s, o.pty, SI_MAX_PTY);
+}
+
+static int fig_walk_device(const char *who, const uint8_t *fibs, const uint8_t *crc_ok, int n_decoders, int n_fibs, int reference_quirks, dabx_fibdec_info *info,
+                           int32_t *n_tab, dabx_subch_desc *subch, dabx_packet_component *packets, int32_t *n_labels, dabx_fig_label *labels,
+                           dabx_fig_stats *stats, int64_t *n_events, dabx_fig_event *events, const FigSiOuts *si)
+{
+  if (!fibs || !crc_ok || n_decoders <= 0 || n_decoders > 65535 || n_fibs <= 0 || n_fibs > 1 << 20) { set_error("%s: bad argument", who); return DABX_E_ARG; }
   int rc = need_device();
   if (rc) return rc;
   const size_t N = (size_t)n_decoders;
@@ -251,14 +277,29 @@ int dabx_fig_walk_device(const uint8_t *fibs, const uint8_t *crc_ok, int n_decod
   for (FigDecoder &d : dec) { memset(&d, 0, sizeof(d)); fig_state_init(d.st, reference_quirks ? 1 : 0, 0); }
   std::vector<FigState> st(N);
   for (size_t d = 0; d < N; d++) st[d] = dec[d].st;
-  DevBuf dfib, dcrc, dst, dlab, dring;
+  DevBuf dfib, dcrc, dst, dlab, dring, dsi, ddir, dndir;
   if ((rc = dfib.from_host(fibs, N * n_fibs * 32)) || (rc = dcrc.from_host(crc_ok, N * n_fibs)) || (rc = dst.from_host(st.data(), sizeof(FigState) * N)) ||
       (rc = dlab.alloc(sizeof(dabx_fig_label) * FIG_LAB_SLOTS * N)) || (rc = dring.alloc(sizeof(dabx_fig_event) * FIG_RING * N))) return rc;
   DABX_HIP(hipMemset(dlab.p, 0, sizeof(dabx_fig_label) * FIG_LAB_SLOTS * N));
   DABX_HIP(hipMemset(dring.p, 0, sizeof(dabx_fig_event) * FIG_RING * N));
-  if ((rc = launch_fig_batch(dfib.as<uint8_t>(), dcrc.as<uint8_t>(), n_decoders, n_fibs, dst.as<FigState>(), dlab.as<dabx_fig_label>(), dring.as<dabx_fig_event>(), 0))) return rc;
+  if (si) {
+    if ((rc = dsi.alloc(sizeof(FigSiState) * N)) || (rc = ddir.alloc(sizeof(dabx_fig_service) * 2 * FIG_MAX_COMP * N)) || (rc = dndir.alloc(sizeof(int32_t) * 2 * N))) return rc;
+    DABX_HIP(hipMemset(dsi.p, 0, sizeof(FigSiState) * N));                  // fig_si_state_init
+    DABX_HIP(hipMemset(ddir.p, 0, sizeof(dabx_fig_service) * 2 * FIG_MAX_COMP * N));
+  }
+  if ((rc = launch_fig_batch(dfib.as<uint8_t>(), dcrc.as<uint8_t>(), n_decoders, n_fibs, dst.as<FigState>(), si ? dsi.as<FigSiState>() : nullptr,
+                             dlab.as<dabx_fig_label>(), dring.as<dabx_fig_event>(), 0))) return rc;
+  for (int k = 0; si && k < 2; k++)
+    if ((rc = launch_fig_directory(dst.as<FigState>(), dsi.as<FigSiState>(), dlab.as<dabx_fig_label>(), nullptr, 0, n_decoders, k,
+                                   ddir.as<dabx_fig_service>() + (size_t)k * FIG_MAX_COMP, 2 * FIG_MAX_COMP, FIG_MAX_COMP, dndir.as<int32_t>() + k, 2, 0))) return rc;
   DABX_HIP(hipStreamSynchronize(0));
   if ((rc = dst.to_host(st.data(), sizeof(FigState) * N))) return rc;
+  std::vector<FigSiState> sis(si ? N : 0);
+  if (si) {
+    if ((rc = dsi.to_host(sis.data(), sizeof(FigSiState) * N))) return rc;
+    if (si->n_dir && (rc = dndir.to_host(si->n_dir, sizeof(int32_t) * 2 * N))) return rc;
+    if (si->dir && (rc = ddir.to_host(si->dir, sizeof(dabx_fig_service) * 2 * FIG_MAX_COMP * N))) return rc;
+  }
   for (size_t d = 0; d < N; d++) {
     dec[d].st = st[d];
     DABX_HIP(hipMemcpy(dec[d].labels, dlab.as<dabx_fig_label>() + d * FIG_LAB_SLOTS, sizeof(dec[d].labels), hipMemcpyDeviceToHost));
@@ -266,8 +307,28 @@ int dabx_fig_walk_device(const uint8_t *fibs, const uint8_t *crc_ok, int n_decod
     fig_present(dec[d], info ? info + d : nullptr, n_tab ? n_tab + 6 * d : nullptr, subch ? subch + 2 * FIG_MAX_SUB * d : nullptr,
                 packets ? packets + 2 * FIG_MAX_PKT * d : nullptr, n_labels ? n_labels + d : nullptr, labels ? labels + FIG_LAB_SLOTS * d : nullptr,
                 stats ? stats + d : nullptr, n_events ? n_events + d : nullptr, events ? events + FIG_RING * d : nullptr);
+    if (si) fig_si_present(st[d], sis[d], si->row(d));
   }
   return 0;
+}
+
+int dabx_fig_walk_device(const uint8_t *fibs, const uint8_t *crc_ok, int n_decoders, int n_fibs, int reference_quirks, dabx_fibdec_info *info,
+                         int32_t *n_tab, dabx_subch_desc *subch, dabx_packet_component *packets, int32_t *n_labels, dabx_fig_label *labels,
+                         dabx_fig_stats *stats, int64_t *n_events, dabx_fig_event *events)
+{
+  return fig_walk_device("dabx_fig_walk_device", fibs, crc_ok, n_decoders, n_fibs, reference_quirks, info, n_tab, subch, packets, n_labels, labels, stats, n_events,
+                         events, nullptr);
+}
+
+int dabx_fig_si_walk_device(const uint8_t *fibs, const uint8_t *crc_ok, int n_decoders, int n_fibs, int reference_quirks, dabx_fibdec_info *info,
+                            int32_t *n_tab, dabx_subch_desc *subch, dabx_packet_component *packets, int32_t *n_labels, dabx_fig_label *labels,
+                            dabx_fig_stats *stats, int64_t *n_events, dabx_fig_event *events, dabx_fig_si_scalars *si_info, dabx_fig_si_stats *si_stats,
+                            dabx_fig_global_def *global_defs, dabx_fig_user_apps_entry *user_apps, dabx_fig_fec_scheme *fec, dabx_fig_cluster *clusters,
+                            dabx_fig_language *languages, dabx_fig_programme_type *ptys, int32_t *n_dir, dabx_fig_service *dir)
+{
+  const FigSiOuts si{si_info, si_stats, global_defs, user_apps, fec, clusters, languages, ptys, n_dir, dir};
+  return fig_walk_device("dabx_fig_si_walk_device", fibs, crc_ok, n_decoders, n_fibs, reference_quirks, info, n_tab, subch, packets, n_labels, labels, stats,
+                         n_events, events, &si);
 }
 
 // Test entries of the FIG walk (tests/test_fig_cases.py; not part of include/dabx.h): the HOST build of fig_walk_fib on a decoder the caller
@@ -295,6 +356,48 @@ int dabx_internal_fig_host_read(const void *dec, dabx_fibdec_info *info, int32_t
 {
   if (!dec) return DABX_E_ARG;
   fig_present(*static_cast<const FigDecoder *>(dec), info, n_tab, subch, packets, n_labels, labels, stats, n_events, events);
+  return 0;
+}
+
+// ... and with the service information (tests/test_fig_si_cases.py): a FigSiHostDecoder is a FigDecoder with its FigSiState behind it; _read
+// presents it as one row of dabx_fig_si_walk_device's outputs, the directory joined by the host build of fig_dir_record.
+struct FigSiHostDecoder {
+  FigDecoder dec;
+  FigSiState si;
+};
+int dabx_internal_fig_si_host_bytes(void) { return (int)sizeof(FigSiHostDecoder); }
+int dabx_internal_fig_si_host_init(void *dec, int reference_quirks)
+{
+  if (!dec) return DABX_E_ARG;
+  FigSiHostDecoder *d = static_cast<FigSiHostDecoder *>(dec);
+  memset(d, 0, sizeof(*d));
+  fig_state_init(d->dec.st, reference_quirks ? 1 : 0, 0);
+  fig_si_state_init(d->si);
+  return 0;
+}
+int dabx_internal_fig_si_host_walk(void *dec, const uint8_t *fibs, const uint8_t *crc_ok, int n_fibs)
+{
+  if (!dec || !fibs || !crc_ok || n_fibs < 0) return DABX_E_ARG;
+  FigSiHostDecoder *d = static_cast<FigSiHostDecoder *>(dec);
+  const FigOut o{d->dec.labels, d->dec.ring, &d->si};
+  for (int i = 0; i < n_fibs; i++) fig_walk_fib(d->dec.st, fibs + (size_t)i * 32, crc_ok[i] != 0, o, 0);
+  return 0;
+}
+int dabx_internal_fig_si_host_read(const void *dec, dabx_fibdec_info *info, int32_t *n_tab, dabx_subch_desc *subch, dabx_packet_component *packets,
+                                   int32_t *n_labels, dabx_fig_label *labels, dabx_fig_stats *stats, int64_t *n_events, dabx_fig_event *events,
+                                   dabx_fig_si_scalars *si_info, dabx_fig_si_stats *si_stats, dabx_fig_global_def *global_defs, dabx_fig_user_apps_entry *user_apps,
+                                   dabx_fig_fec_scheme *fec, dabx_fig_cluster *clusters, dabx_fig_language *languages, dabx_fig_programme_type *ptys,
+                                   int32_t *n_dir, dabx_fig_service *dir)
+{
+  if (!dec) return DABX_E_ARG;
+  const FigSiHostDecoder *d = static_cast<const FigSiHostDecoder *>(dec);
+  fig_present(d->dec, info, n_tab, subch, packets, n_labels, labels, stats, n_events, events);
+  fig_si_present(d->dec.st, d->si, FigSiOuts{si_info, si_stats, global_defs, user_apps, fec, clusters, languages, ptys, n_dir, dir});
+  for (int k = 0; k < 2; k++) {
+    const int n = d->dec.st.cfg[d->dec.st.cur ^ k].n_comp;
+    if (n_dir) n_dir[k] = n;
+    for (int i = 0; dir && i < n; i++) fig_dir_record(d->dec.st, d->si, d->dec.labels, k, i, dir + (size_t)k * FIG_MAX_COMP + i);
+  }
   return 0;
 }
 

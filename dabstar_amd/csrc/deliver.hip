@@ -669,23 +669,29 @@ struct FigLds {
   uint32_t fib[96];                              // 12 FIBs of 32 bytes
   uint32_t crc[3];                               // their 12 verdicts
 };
+struct FigSiLds {                                // ... with the service information of the decoder beside it (fig_si_core.h)
+  FigLds w;
+  FigSiState si;
+};
+static_assert(sizeof(FigSiLds) < 64 * 1024, "FigState, FigSiState and the frame share the 64 KB of static LDS a workgroup can have");
 
-__device__ inline void fig_state_move(uint32_t *dst, const uint32_t *src, int lane)
+__device__ inline void fig_words_move(uint32_t *dst, const uint32_t *src, int n_words, int lane)
 {
-  for (int i = lane; i < (int)(sizeof(FigState) / 4); i += 64) dst[i] = src[i];
+  for (int i = lane; i < n_words; i += 64) dst[i] = src[i];
   fig_sync();
 }
-
-// grid = n_streams, 64 threads, front-end stream, behind k_fic_frame and the frame's count (k_frame_tail, k_fic_advance) and in front of the
-// next frame's k_fic_frame: the frame's slot of fib_out is read before anything can rewrite it, and no frame is skipped.  A stream with the
-// mode off, or without a frame in this step, returns at once.
-__global__ __launch_bounds__(64) void k_fig(const StreamCtl *ctl, const uint8_t *fib_out, const uint8_t *fib_crc, int out_frames, FigDev f)
+__device__ inline void fig_state_move(uint32_t *dst, const uint32_t *src, int lane) { fig_words_move(dst, src, (int)(sizeof(FigState) / 4), lane); }
+__device__ inline void fig_si_move(FigSiState *dst, const FigSiState *src, int lane)
 {
-  __shared__ FigLds w;
-  const int s = blockIdx.x, lane = threadIdx.x;
-  if (!f.on[s]) return;
+  fig_words_move(reinterpret_cast<uint32_t *>(dst), reinterpret_cast<const uint32_t *>(src), (int)(sizeof(FigSiState) / 4), lane);
+}
+
+// One stream's frame: the state into LDS, the 12 FIBs walked, the state back.  si: the stream's service information in LDS, loaded and
+// stored by the caller; nullptr: not followed (k_fig passes the constant, and nothing of fig_si_core.h remains in it).
+__device__ __forceinline__ void fig_frame(FigLds &w, FigSiState *si, const StreamCtl *ctl, const uint8_t *fib_out, const uint8_t *fib_crc, int out_frames, const FigDev &f,
+                                 int s, int lane)
+{
   const StreamCtl &c = ctl[s];
-  if (!c.frame_ok || c.frames <= 0) return;
   const long long frame = c.frames - 1;                      // (the frame has been counted)
   const size_t slot = (size_t)s * out_frames + (size_t)(frame % out_frames);
   w.fib[lane] = reinterpret_cast<const uint32_t *>(fib_out + slot * 384)[lane];
@@ -694,27 +700,52 @@ __global__ __launch_bounds__(64) void k_fig(const StreamCtl *ctl, const uint8_t 
   fig_state_move(reinterpret_cast<uint32_t *>(&w.st), reinterpret_cast<const uint32_t *>(f.st + s), lane);
   if (w.st.fibs < 12 * frame) w.st.fibs = 12 * frame;        // FIB k of frame n is FIB 12 n + k of the stream, as dabx_follow_fic counts
   fig_sync();
-  const FigOut o{f.labels + (size_t)s * FIG_LAB_SLOTS, f.ring + (size_t)s * FIG_RING};
+  const FigOut o{f.labels + (size_t)s * FIG_LAB_SLOTS, f.ring + (size_t)s * FIG_RING, si};
   const uint8_t *fb = reinterpret_cast<const uint8_t *>(w.fib), *ok = reinterpret_cast<const uint8_t *>(w.crc);
   for (int i = 0; i < 12; i++) fig_walk_fib(w.st, fb + 32 * i, fig_u(ok[i]) != 0, o, lane);
   fig_sync();
   fig_state_move(reinterpret_cast<uint32_t *>(f.st + s), reinterpret_cast<const uint32_t *>(&w.st), lane);
 }
 
+// grid = n_streams, 64 threads, front-end stream, behind k_fic_frame and the frame's count (k_frame_tail, k_fic_advance) and in front of the
+// next frame's k_fic_frame: the frame's slot of fib_out is read before anything can rewrite it, and no frame is skipped.  A stream with the
+// mode off, or without a frame in this step, returns at once.  k_fig: an engine none of whose streams follows the service information;
+// k_fig_si: one that has such streams -- a stream with that switch on brings its FigSiState into LDS beside FigState and writes it back.
+__global__ __launch_bounds__(64) void k_fig(const StreamCtl *ctl, const uint8_t *fib_out, const uint8_t *fib_crc, int out_frames, FigDev f)
+{
+  __shared__ FigLds w;
+  const int s = blockIdx.x, lane = threadIdx.x;
+  if (!f.on[s]) return;
+  if (!ctl[s].frame_ok || ctl[s].frames <= 0) return;
+  fig_frame(w, nullptr, ctl, fib_out, fib_crc, out_frames, f, s, lane);
+}
+
+__global__ __launch_bounds__(64) void k_fig_si(const StreamCtl *ctl, const uint8_t *fib_out, const uint8_t *fib_crc, int out_frames, FigDev f)
+{
+  __shared__ FigSiLds w;
+  const int s = blockIdx.x, lane = threadIdx.x;
+  if (!f.on[s]) return;
+  if (!ctl[s].frame_ok || ctl[s].frames <= 0) return;
+  const bool si = fig_u(f.si_on[s]) != 0;
+  if (si) fig_si_move(&w.si, f.si + s, lane);
+  fig_frame(w.w, si ? &w.si : nullptr, ctl, fib_out, fib_crc, out_frames, f, s, lane);
+  if (si) fig_si_move(f.si + s, &w.si, lane);
+}
+
 int launch_fig(const EngineDev &e, const FigDev &f, hipStream_t st)
 {
-  hipLaunchKernelGGL(k_fig, dim3(e.n_streams), dim3(64), 0, st, e.ctl, e.fib_out, e.fib_crc, e.out_frames, f);
+  if (f.si) hipLaunchKernelGGL(k_fig_si, dim3(e.n_streams), dim3(64), 0, st, e.ctl, e.fib_out, e.fib_crc, e.out_frames, f);
+  else hipLaunchKernelGGL(k_fig, dim3(e.n_streams), dim3(64), 0, st, e.ctl, e.fib_out, e.fib_crc, e.out_frames, f);
   DABX_HIP(hipGetLastError());
   return 0;
 }
 
 // grid = n decoders, 64 threads: decoder d walks fibs[d][n_fibs][32] with crc_ok[d][n_fibs] from the state st[d]
-__global__ __launch_bounds__(64) void k_fig_batch(const uint8_t *fibs, const uint8_t *crc_ok, int n_fibs, FigState *st, dabx_fig_label *labels, dabx_fig_event *ring)
+__device__ __forceinline__ void fig_batch(FigLds &w, FigSiState *si, const uint8_t *fibs, const uint8_t *crc_ok, int n_fibs, FigState *st, dabx_fig_label *labels,
+                                 dabx_fig_event *ring, int d, int lane)
 {
-  __shared__ FigLds w;
-  const int d = blockIdx.x, lane = threadIdx.x;
   fig_state_move(reinterpret_cast<uint32_t *>(&w.st), reinterpret_cast<const uint32_t *>(st + d), lane);
-  const FigOut o{labels + (size_t)d * FIG_LAB_SLOTS, ring + (size_t)d * FIG_RING};
+  const FigOut o{labels + (size_t)d * FIG_LAB_SLOTS, ring + (size_t)d * FIG_RING, si};
   const uint8_t *fb = reinterpret_cast<const uint8_t *>(w.fib);
   for (int i = 0; i < n_fibs; i++) {
     const size_t k = (size_t)d * n_fibs + i;
@@ -726,10 +757,53 @@ __global__ __launch_bounds__(64) void k_fig_batch(const uint8_t *fibs, const uin
   fig_state_move(reinterpret_cast<uint32_t *>(st + d), reinterpret_cast<const uint32_t *>(&w.st), lane);
 }
 
-int launch_fig_batch(const uint8_t *fibs, const uint8_t *crc_ok, int n_decoders, int n_fibs, FigState *st, dabx_fig_label *labels, dabx_fig_event *ring,
-                     hipStream_t stream)
+__global__ __launch_bounds__(64) void k_fig_batch(const uint8_t *fibs, const uint8_t *crc_ok, int n_fibs, FigState *st, dabx_fig_label *labels, dabx_fig_event *ring)
 {
-  hipLaunchKernelGGL(k_fig_batch, dim3(n_decoders), dim3(64), 0, stream, fibs, crc_ok, n_fibs, st, labels, ring);
+  __shared__ FigLds w;
+  fig_batch(w, nullptr, fibs, crc_ok, n_fibs, st, labels, ring, blockIdx.x, threadIdx.x);
+}
+
+__global__ __launch_bounds__(64) void k_fig_si_batch(const uint8_t *fibs, const uint8_t *crc_ok, int n_fibs, FigState *st, FigSiState *si, dabx_fig_label *labels,
+                                                     dabx_fig_event *ring)
+{
+  __shared__ FigSiLds w;
+  const int d = blockIdx.x, lane = threadIdx.x;
+  fig_si_move(&w.si, si + d, lane);
+  fig_batch(w.w, &w.si, fibs, crc_ok, n_fibs, st, labels, ring, d, lane);
+  fig_si_move(si + d, &w.si, lane);
+}
+
+int launch_fig_batch(const uint8_t *fibs, const uint8_t *crc_ok, int n_decoders, int n_fibs, FigState *st, FigSiState *si, dabx_fig_label *labels,
+                     dabx_fig_event *ring, hipStream_t stream)
+{
+  if (si) hipLaunchKernelGGL(k_fig_si_batch, dim3(n_decoders), dim3(64), 0, stream, fibs, crc_ok, n_fibs, st, si, labels, ring);
+  else hipLaunchKernelGGL(k_fig_batch, dim3(n_decoders), dim3(64), 0, stream, fibs, crc_ok, n_fibs, st, labels, ring);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---- the service directory (include/dabx.h, dabx_fig_directory): grid = decoders, one wave each, one lane per service component of the chosen
+// configuration, 64 at a step.  Block b joins decoder first + b (fig_dir_record) into out[b * out_stride ...], at most max_per records, and
+// leaves the number of components in n_out[b * n_stride].  on (optional): a decoder without service information has none. ----
+__global__ __launch_bounds__(64) void k_fig_directory(const FigState *st, const FigSiState *si, const dabx_fig_label *labels, const int32_t *on, int first, int next,
+                                                      dabx_fig_service *out, long long out_stride, int max_per, int32_t *n_out, int n_stride)
+{
+  const int b = blockIdx.x, s = first + b, lane = threadIdx.x;
+  int n = 0;
+  if (!on || on[s]) {
+    const FigState &t = st[s];
+    n = t.cfg[next ? t.cur ^ 1 : t.cur].n_comp;
+    if (n > FIG_MAX_COMP) n = FIG_MAX_COMP;                  // (a state the walk wrote never has more)
+    const int m = n < max_per ? n : max_per;
+    for (int i = lane; i < m; i += 64) fig_dir_record(t, si[s], labels + (size_t)s * FIG_LAB_SLOTS, next, i, out + (size_t)b * out_stride + i);
+  }
+  if (lane == 0) n_out[(size_t)b * n_stride] = n;
+}
+
+int launch_fig_directory(const FigState *st, const FigSiState *si, const dabx_fig_label *labels, const int32_t *on, int first, int n, int next,
+                         dabx_fig_service *out, long long out_stride, int max_per, int32_t *n_out, int n_stride, hipStream_t stream)
+{
+  hipLaunchKernelGGL(k_fig_directory, dim3(n), dim3(64), 0, stream, st, si, labels, on, first, next, out, out_stride, max_per, n_out, n_stride);
   DABX_HIP(hipGetLastError());
   return 0;
 }

@@ -275,12 +275,15 @@ struct FigStage {
   FigDev dev{};
   int n_on = 0;                                // streams with the mode on
   std::vector<int32_t> on;                     // [S] mirror of dev.on
+  std::vector<int32_t> si_on;                  // [S] mirror of dev.si_on (empty until a stream first asks for the service information)
+  int n_si = 0;                                // streams that follow it now: k_fig_si is launched while there is one, k_fig otherwise
   std::vector<long long> seen;                 // [S] events dabx_read_fig_events has returned or passed
   long long launches = 0;
   bool timing = false;                         // dabx_internal_fig_timing: every launch between two events of its own
   std::vector<hipEvent_t> timed;               // ... begin, end, begin, end, ...
   bool exists() const { return dev.st != nullptr; }
   bool on_for(int s) const { return exists() && on[(size_t)s] != 0; }
+  bool si_for(int s) const { return on_for(s) && dev.si != nullptr && si_on[(size_t)s] != 0; }
 };
 
 struct dabx_engine : dabx::EngineHead {         // (iqfile.h: the ring format, where iqfile.cpp can read it)

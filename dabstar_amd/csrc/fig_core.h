@@ -11,6 +11,10 @@
 // itself flips FigState::cur.  For the host the same functions are loops (FIG_LANES = 1, lane 0).  Label records and events go to global
 // memory from lane 0.
 //
+// The service information of FIG 0 behind 0/3 and the service directory's join are fig_si_core.h, included at the end of this file: a decoder follows them when
+// FigOut::si points at its FigSiState (k_fig_si, k_fig_si_batch; the host walk of the tests), and a walk whose FigOut::si is the constant
+// nullptr (k_fig, k_fig_batch) is compiled without them.
+//
 // Plain C++ but for those few functions: a host compiler takes it without HIP.
 #pragma once
 #include <stdint.h>
@@ -44,7 +48,7 @@ struct FigCfg {
   uint32_t sub_span[FIG_MAX_SUB];                // cu_start | cu_size << 16
   uint32_t sub_desc[FIG_MAX_SUB];                // kbps | prot_level << 12 | short_form << 16
   uint32_t comp_sid[FIG_MAX_COMP];
-  uint32_t comp_info[FIG_MAX_COMP];              // idx | tmid << 4 | ascty << 6 | subch_id << 12 | scid << 18 (what the TMId does not define: 0)
+  uint32_t comp_info[FIG_MAX_COMP];              // idx | tmid << 4 | ascty or dscty << 6 | subch_id << 12 | scid << 18 (what the TMId does not define: 0) | P/S << 30 | P/D << 31
   uint32_t pkt_scid[FIG_MAX_PKT];
   uint32_t pkt_info[FIG_MAX_PKT];                // caorg | dg << 1 | dscty << 2 | subch_id << 8 | address << 14
 };
@@ -62,9 +66,11 @@ struct FigState {
 static_assert(sizeof(FigState) % 8 == 0, "FigState is copied as dwords");
 
 // where a walk leaves what does not live in FigState
+struct FigSiState;
 struct FigOut {
   dabx_fig_label *labels;                        // [FIG_LAB_SLOTS]
   dabx_fig_event *ring;                          // [FIG_RING]
+  FigSiState *si = nullptr;                      // the decoder's service information (fig_si_core.h); nullptr: not followed
 };
 
 FIG_HD inline void fig_state_init(FigState &t, int strict, long long fibs)      // a fresh dabx_fibdec (fib.cpp) that has skipped `fibs` FIBs
@@ -151,6 +157,13 @@ FIG_HD inline void fig_emit(FigState &t, const FigOut &o, int kind, const int32_
   t.cnt.events++;
 }
 
+// The service information's side of the walk (fig_si_core.h, included at the end of this file): what the functions below call
+struct FigSiState;
+FIG_HD inline void fig_si_restart(FigSiState &s);
+FIG_HD inline void fig_si_swap(FigSiState &s, int cur, int strict, int lane);
+FIG_HD inline void fig_si_walk(FigState &t, FigSiState &s, const uint8_t *d, int len, int ext, int pd, int cn, const FigOut &o, int lane);
+FIG_HD inline void fig_si_frame_end(FigState &t, FigSiState &s, const FigOut &o, int lane);
+
 // _restart_fib_decoding (fib_decoder.cpp:131-141; dabx_fibdec::restart_decoding): both configurations, the labels and the FIG 0/0 scalars
 FIG_HD inline void fig_restart(FigState &t, const FigOut &o, int lane)
 {
@@ -158,6 +171,7 @@ FIG_HD inline void fig_restart(FigState &t, const FigOut &o, int lane)
   t.n_labels = 0; t.n_kind[0] = t.n_kind[1] = t.n_kind[2] = t.n_kind[3] = 0;
   t.cif_count = t.cif_hi = t.cif_lo = -1; t.change_flags = t.occurrence = t.prev_change_flag = 0; t.fig00_fib = -1;
   t.n_restarts++; t.cnt.restarts++;
+  if (o.si) fig_si_restart(*o.si);
   fig_emit(t, o, DABX_FIG_RESTART, nullptr, lane);
 }
 
@@ -190,6 +204,7 @@ FIG_HD inline void fig_0s0(FigState &t, const uint8_t *d, int len, const FigOut 
       if (nx.n_pkt == 0) { fig_copy(nx.pkt_scid, cu.pkt_scid, cu.n_pkt, lane); fig_copy(nx.pkt_info, cu.pkt_info, cu.n_pkt, lane); nx.n_pkt = cu.n_pkt; }
       fig_sync();
     }
+    if (o.si) fig_si_swap(*o.si, t.cur, t.strict, lane);
     t.cur ^= 1;                                                        // the swap: an index, no table moves
     fig_cfg_reset(t.cfg[t.cur ^ 1]);
     t.n_changes++; t.cnt.swaps++;
@@ -267,9 +282,8 @@ FIG_HD inline void fig_0s2(FigState &t, FigCfg &cfg, const uint8_t *d, int len, 
       if (known >= 0) { t.cnt.comp_known++; continue; }
       if (cfg.n_comp >= FIG_MAX_COMP) { t.cnt.over_components++; continue; }     // guard: the table is full
       const unsigned tmid = (unsigned)fig_u((int)fig_bits(d, ob, 2));
-      unsigned info = (unsigned)c | tmid << 4;
-      if (tmid == 0) info |= fig_bits(d, ob + 2, 6) << 6 | fig_bits(d, ob + 8, 6) << 12;
-      else if (tmid == 1) info |= fig_bits(d, ob + 8, 6) << 12;
+      unsigned info = (unsigned)c | tmid << 4 | fig_bits(d, ob + 14, 1) << 30 | (unsigned)pd << 31;
+      if (tmid == 0 || tmid == 1) info |= fig_bits(d, ob + 2, 6) << 6 | fig_bits(d, ob + 8, 6) << 12;
       else if (tmid == 3) info |= fig_bits(d, ob + 2, 12) << 18;
       const int n = cfg.n_comp;
       cfg.comp_sid[n] = sid; cfg.comp_info[n] = (unsigned)fig_u((int)info);
@@ -366,7 +380,10 @@ FIG_HD inline void fig_walk_fib(FigState &t, const uint8_t *fib, bool crc_ok, co
         else if (ext == 1) restarted = fig_0s1(t, cfg, d, len, o, lane);
         else if (ext == 2) fig_0s2(t, cfg, d, len, pd, lane);
         else if (ext == 3) fig_0s3(t, cfg, d, len, lane);
-        else t.cnt.fig0_other_ext++;
+        else {
+          t.cnt.fig0_other_ext++;
+          if (o.si) fig_si_walk(t, *o.si, d, len, ext, pd, cn, o, lane);
+        }
       } else if (type == 1) fig_1(t, d, len, o, lane);
       else if (type != 0) t.cnt.fig_other_type++;
       else t.cnt.fig0_other_ext++;
@@ -382,6 +399,7 @@ FIG_HD inline void fig_walk_fib(FigState &t, const uint8_t *fib, bool crc_ok, co
       fig_emit(t, o, DABX_FIG_TABLE, w, lane);
       c.gained = 0;
     }
+    if (o.si) fig_si_frame_end(t, *o.si, o, lane);
   }
   t.fibs++;
 }
@@ -475,14 +493,20 @@ struct FigDev {
   dabx_fig_label *labels;                        // [S][FIG_LAB_SLOTS]
   dabx_fig_event *ring;                          // [S][FIG_RING]
   int32_t *on;                                   // [S] the stream has the mode on
+  FigSiState *si;                                // [S] the service information; nullptr until a stream first asks for it (dabx_fig_config.service_info)
+  int32_t *si_on;                                // [S] the stream follows it
 };
 
 #ifdef __HIPCC__
 // deliver.hip
 struct EngineDev;
 int launch_fig(const EngineDev &e, const FigDev &f, hipStream_t st);
-int launch_fig_batch(const uint8_t *fibs, const uint8_t *crc_ok, int n_decoders, int n_fibs, FigState *st, dabx_fig_label *labels, dabx_fig_event *ring,
-                     hipStream_t stream);
+int launch_fig_batch(const uint8_t *fibs, const uint8_t *crc_ok, int n_decoders, int n_fibs, FigState *st, FigSiState *si /* nullptr: without */,
+                     dabx_fig_label *labels, dabx_fig_event *ring, hipStream_t stream);
+int launch_fig_directory(const FigState *st, const FigSiState *si, const dabx_fig_label *labels, const int32_t *on, int first, int n, int next,
+                         dabx_fig_service *out, long long out_stride, int max_per, int32_t *n_out, int n_stride, hipStream_t stream);
 #endif
 
 }  // namespace dabx
+
+#include "fig_si_core.h"

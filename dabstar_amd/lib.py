@@ -665,7 +665,7 @@ assert (FIG_LABEL.itemsize, FIG_EVENT.itemsize, FIG_STATS.itemsize, CHUNK_FIG.it
 
 
 class FigConfig(C.Structure):
-    _fields_ = [("enable", C.c_int32), ("reference_quirks", C.c_int32), ("reserved", C.c_int32 * 2)]          # dabx_fig_config
+    _fields_ = [("enable", C.c_int32), ("reference_quirks", C.c_int32), ("service_info", C.c_int32), ("reserved", C.c_int32 * 1)]    # dabx_fig_config
 
 
 def fig_label_dict(r):
@@ -686,6 +686,13 @@ def fig_event_dict(ev):
         out.update(next=w[0], n_subch=w[1], n_components=w[2], n_packets=w[3])
     elif out["kind"] == FIG_LABEL_EVENT:
         out.update(label=fig_label_dict(np.array(ev["words"], "<i4").view(FIG_LABEL)[0]))
+    elif out["kind"] == FIG_SI_TABLE:
+        out.update(next=w[0], mask=w[1], n_global_defs=w[2], n_user_apps=w[3], n_fec=w[4], n_clusters=w[5], n_cluster_sids=w[6], n_languages=w[7] & 0xFFFF,
+                   n_ptys=w[7] >> 16)
+    elif out["kind"] == FIG_TIME:
+        out.update(mjd=w[0], hour=w[1], minute=w[2], second=w[3], lto_minutes=w[4], utc_flag=w[5], lsi=w[6])
+    elif out["kind"] in (FIG_ANNOUNCE_START, FIG_ANNOUNCE_STOP):
+        out.update(cluster=w[0], flags=w[1], subch_id=w[2], n_services=w[3], next=w[4])
     return out
 
 
@@ -768,6 +775,134 @@ class FigHostDecoder:
         L.dabx_internal_fig_host_read.argtypes = [C.c_void_p] * 10
         check(L.dabx_internal_fig_host_read(_p(self._buf), info, _p(n_tab), subch, _p(packets), _p(n_labels), _p(labels), _p(stats), _p(n_events), _p(events)))
         return _fig_rows(1, *bufs)[0]
+
+
+# the service information (include/dabx.h "Service information"; csrc/fig_si_core.h): the SI event kinds, the getters' records, the counters
+# and the service directory's record
+FIG_SI_TABLE, FIG_TIME, FIG_ANNOUNCE_START, FIG_ANNOUNCE_STOP = 6, 7, 8, 9
+FIG_MAX_GLOBAL_DEFS, FIG_MAX_USER_APPS, FIG_MAX_LANGUAGES, FIG_MAX_PTYS, FIG_MAX_CLUSTERS, FIG_MAX_CLUSTER_SIDS, FIG_CLUSTER_LIST = 256, 128, 128, 128, 64, 512, 24
+FIG_SI_HAS = dict(language=1, config=2, global_def=4, lto=8, user_apps=16, fec=32, pty=64, cluster=128)
+FIG_JOIN = dict(subch=1, packet=2, global_def=4, user_apps=8, fec=16, language=32, pty=64, label=128)
+FIG_SI_INFO = np.dtype([("has_config", "<i4", (2,)), ("n_services", "<i4", (2,)), ("count", "<i4", (2,)), ("has_lto", "<i4"), ("lto_minutes", "<i4"),
+                        ("ecc", "<i4"), ("inter_table", "<i4"), ("lto_ext", "<i4"), ("time_set", "<i4"), ("mjd", "<i4"), ("hour", "<i4"), ("minute", "<i4"),
+                        ("second", "<i4"), ("lsi", "<i4"), ("utc_flag", "<i4"), ("n_global_defs", "<i4", (2,)), ("n_user_apps", "<i4", (2,)),
+                        ("n_fec", "<i4", (2,)), ("n_clusters", "<i4", (2,)), ("n_cluster_sids", "<i4", (2,)), ("n_languages", "<i4"), ("n_ptys", "<i4"),
+                        ("reserved", "<i4", (2,))])
+FIG_GLOBAL_DEF = np.dtype([("sid", "<u4"), ("scids", "i1"), ("pd", "i1"), ("ls", "i1"), ("ext", "i1"), ("subch_id", "<i2"), ("scid", "<i2")])
+FIG_USER_APPS = np.dtype([("sid", "<u4"), ("size_bits", "<u2"), ("scids", "u1"), ("pd", "u1"), ("n_apps", "u1"), ("len", "u1", (6,)), ("reserved0", "u1"),
+                          ("type", "<u2", (6,)), ("data", "u1", (6, 4)), ("reserved", "u1", (12,))])
+FIG_LANGUAGE = np.dtype([("ls", "<i4"), ("id", "<i4"), ("language", "<i4"), ("reserved", "<i4")])
+FIG_PTY = np.dtype([("sid", "<u4"), ("sd", "<i4"), ("code", "<i4"), ("reserved", "<i4")])
+FIG_FEC = np.dtype([("subch_id", "<i4"), ("scheme", "<i4")])
+FIG_CLUSTER = np.dtype([("cluster_id", "<i4"), ("flags", "<i4"), ("announcing", "<i4"), ("n_services", "<i4"), ("sid", "<u4", (FIG_CLUSTER_LIST,)),
+                        ("reserved", "<i4", (4,))])
+FIG_SI_COUNTERS = ("si_figs", "language_new", "language_known", "config_new", "config_known", "global_def_new", "global_def_known", "lto_new", "lto_known",
+                   "time_set", "user_apps_new", "user_apps_known", "user_apps_clamped", "fec_new", "fec_known", "pty_new", "pty_known", "cluster_new",
+                   "cluster_fallback", "cluster_zero", "cluster_sid_new", "cluster_sid_known", "asw_count", "asw_start", "asw_stop", "asw_unknown",
+                   "over_global_defs", "over_user_apps", "over_languages", "over_ptys", "over_cluster_sids", "outside")
+FIG_SI_STATS = np.dtype([(k, "<i8") for k in FIG_SI_COUNTERS])
+FIG_SERVICE = np.dtype([("sid", "<u4"), ("comp_idx", "i1"), ("ps", "i1"), ("tmid", "i1"), ("ty", "i1"), ("scids", "i1"), ("subch_id", "i1"), ("prot_level", "i1"),
+                        ("short_form", "i1"), ("cu_start", "<i2"), ("cu_size", "<i2"), ("kbps", "<i2"), ("packet_address", "<i2"), ("scid", "<i2"),
+                        ("language", "<i2"), ("pty", "i1"), ("fec_scheme", "i1"), ("dg_flag", "i1"), ("pd", "i1"), ("n_apps", "u1"), ("app_len", "u1", (6,)),
+                        ("reserved0", "u1"), ("app_type", "<u2", (6,)), ("app_data", "u1", (6, 4)), ("label", FIG_LABEL), ("joined", "<u4"),
+                        ("reference_defined", "<i4"), ("reserved", "<i4", (4,))])
+assert (FIG_SI_INFO.itemsize, FIG_GLOBAL_DEF.itemsize, FIG_USER_APPS.itemsize, FIG_LANGUAGE.itemsize, FIG_PTY.itemsize, FIG_FEC.itemsize, FIG_CLUSTER.itemsize,
+        FIG_SI_STATS.itemsize, FIG_SERVICE.itemsize) == (128, 12, 64, 16, 16, 8, 128, 256, 128)
+
+
+def _rec_dict(r, skip=("reserved", "reserved0")):
+    """a numpy record as plain values (arrays as lists, nested records as dicts)"""
+    out = {}
+    for k in r.dtype.names:
+        if k in skip:
+            continue
+        v = r[k]
+        out[k] = fig_label_dict(v) if k == "label" else v.tolist() if isinstance(v, np.ndarray) else int(v)
+    return out
+
+
+def fig_user_apps_dict(r):
+    """A FIG_USER_APPS record as plain values: its n_apps applications as (type, data length, the first four data bytes)."""
+    n = int(r["n_apps"])
+    return dict(sid=int(r["sid"]), scids=int(r["scids"]), pd=int(r["pd"]), size_bits=int(r["size_bits"]),
+                apps=[(int(r["type"][k]), int(r["len"][k]), bytes(bytearray(r["data"][k]))) for k in range(n)])
+
+
+def fig_service_dict(r):
+    """A FIG_SERVICE record (dabx_fig_service) as plain values: the applications as in fig_user_apps_dict, the label as fig_label_dict or None."""
+    out = _rec_dict(r, skip=("reserved", "reserved0", "app_len", "app_type", "app_data", "n_apps", "label"))
+    out["apps"] = [(int(r["app_type"][k]), int(r["app_len"][k]), bytes(bytearray(r["app_data"][k]))) for k in range(int(r["n_apps"]))]
+    out["label"] = None if int(r["label"]["kind"]) == 0xFF else fig_label_dict(r["label"])
+    return out
+
+
+def fig_cluster_dict(r):
+    n = int(r["n_services"])
+    return dict(cluster_id=int(r["cluster_id"]), flags=int(r["flags"]), announcing=int(r["announcing"]), n_services=n,
+                sids=[int(v) for v in r["sid"][:min(n, FIG_CLUSTER_LIST)]])
+
+
+def _fig_si_out_buffers(n):
+    return (np.zeros(n, FIG_SI_INFO), np.zeros(n, FIG_SI_STATS), np.zeros((n, 2, FIG_MAX_GLOBAL_DEFS), FIG_GLOBAL_DEF), np.zeros((n, 2, FIG_MAX_USER_APPS), FIG_USER_APPS),
+            np.zeros((n, 2, 64), FIG_FEC), np.zeros((n, 2, FIG_MAX_CLUSTERS), FIG_CLUSTER), np.zeros((n, FIG_MAX_LANGUAGES), FIG_LANGUAGE),
+            np.zeros((n, FIG_MAX_PTYS), FIG_PTY), np.zeros((n, 2), np.int32), np.zeros((n, 2, FIG_MAX_COMPONENTS), FIG_SERVICE))
+
+
+def _fig_si_rows(rows, si_info, si_stats, gd, ua, fec, cl, lang, pty, n_dir, dirs):
+    """the SI outputs of dabx_fig_si_walk_device added to the rows of _fig_rows: row["si"] (the tables) and row["dir"] (both directories)"""
+    for d, row in enumerate(rows):
+        i = si_info[d]
+        row["si"] = dict(
+            info=_rec_dict(i), stats={k: int(si_stats[d][k]) for k in FIG_SI_COUNTERS},
+            global_defs=[[_rec_dict(r) for r in gd[d, k, :int(i["n_global_defs"][k])]] for k in range(2)],
+            user_apps=[[fig_user_apps_dict(r) for r in ua[d, k, :int(i["n_user_apps"][k])]] for k in range(2)],
+            fec=[[(int(r["subch_id"]), int(r["scheme"])) for r in fec[d, k, :int(i["n_fec"][k])]] for k in range(2)],
+            clusters=[[fig_cluster_dict(r) for r in cl[d, k, :int(i["n_clusters"][k])]] for k in range(2)],
+            languages=[(int(r["ls"]), int(r["id"]), int(r["language"])) for r in lang[d, :int(i["n_languages"])]],
+            ptys=[(int(r["sid"]), int(r["sd"]), int(r["code"])) for r in pty[d, :int(i["n_ptys"])]])
+        row["dir"] = [[fig_service_dict(r) for r in dirs[d, k, :int(n_dir[d, k])]] for k in range(2)]
+    return rows
+
+
+def fig_si_walk_device(fibs, crc_ok, reference_quirks=False):
+    """fig_walk_device with the service information followed (dabx_fig_si_walk_device: k_fig_si_batch, then k_fig_directory on both
+    configurations): the rows of fig_walk_device, each with "si" (info, stats, global_defs / user_apps / fec / clusters of (current, next),
+    languages, ptys) and "dir" (the service directory of (current, next), fig_service_dict)."""
+    fibs = np.ascontiguousarray(fibs, np.uint8)
+    if fibs.ndim != 3 or fibs.shape[2] != 32:
+        raise ValueError("fig_si_walk_device needs fibs [n, n_fibs, 32]")
+    n, nf = fibs.shape[0], fibs.shape[1]
+    crc_ok = np.ascontiguousarray(crc_ok, np.uint8).reshape(n, nf)
+    bufs, si = _fig_out_buffers(n), _fig_si_out_buffers(n)
+    L = load()
+    L.dabx_fig_si_walk_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 19
+    check(L.dabx_fig_si_walk_device(_p(fibs), _p(crc_ok), n, nf, int(bool(reference_quirks)), *[b if isinstance(b, C.Array) else _p(b) for b in bufs + si]))
+    return _fig_si_rows(_fig_rows(n, *bufs), *si)
+
+
+class FigSiHostDecoder:
+    """Internal test entry (not part of include/dabx.h): FigHostDecoder with the service information followed (csrc/fig_si_core.h on the
+    host); read() presents the decoder as one row of fig_si_walk_device, the directory joined by the host build of the join.  No device."""
+
+    def __init__(self, reference_quirks=False):
+        L = load()
+        self._buf = np.zeros(L.dabx_internal_fig_si_host_bytes(), np.uint8)
+        L.dabx_internal_fig_si_host_init.argtypes = [C.c_void_p, C.c_int]
+        check(L.dabx_internal_fig_si_host_init(_p(self._buf), int(bool(reference_quirks))))
+
+    def walk(self, fibs, crc_ok):
+        fibs = np.ascontiguousarray(fibs, np.uint8).reshape(-1, 32)
+        crc_ok = np.ascontiguousarray(crc_ok, np.uint8).reshape(-1)
+        L = load()
+        L.dabx_internal_fig_si_host_walk.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        check(L.dabx_internal_fig_si_host_walk(_p(self._buf), _p(fibs), _p(crc_ok), fibs.shape[0]))
+
+    def read(self):
+        bufs, si = _fig_out_buffers(1), _fig_si_out_buffers(1)
+        L = load()
+        L.dabx_internal_fig_si_host_read.argtypes = [C.c_void_p] * 20
+        check(L.dabx_internal_fig_si_host_read(_p(self._buf), *[b if isinstance(b, C.Array) else _p(b) for b in bufs + si]))
+        return _fig_si_rows(_fig_rows(1, *bufs), *si)[0]
 
 
 class SpectrumConfig(C.Structure):
@@ -1323,11 +1458,12 @@ class Engine:
         check(L.dabx_get_tii_stats(self._h, stream, _p(st)))
         return {k: int(st[k][0]) for k in TII_STATS.names if k != "reserved"}
 
-    def set_fig_mode(self, stream, enable=True, reference_quirks=False):
+    def set_fig_mode(self, stream, enable=True, reference_quirks=False, service_info=False):
         """The stream's FIC followed on the device (dabx_set_fig_mode; stream = -1: all streams): FIG 0/0-0/3 and the labels of FIG 1 go into
         a database on the device (fig_info, fig_subchannels, fig_packet_components, fig_labels, fig_follow), changes are reported as events
-        (read_fig_events, or in bulk with DELIVER_FIG)."""
-        cfg = FigConfig(enable=int(bool(enable)), reference_quirks=int(bool(reference_quirks)))
+        (read_fig_events, or in bulk with DELIVER_FIG).  service_info: FIG 0/5 .. 0/19 are followed too (fig_si_info, fig_user_apps,
+        fig_global_defs, fig_languages, fig_programme_types, fig_fec_schemes, fig_clusters, fig_si_stats, fig_directory; events of kinds 6-9)."""
+        cfg = FigConfig(enable=int(bool(enable)), reference_quirks=int(bool(reference_quirks)), service_info=int(bool(service_info)))
         L = load()
         L.dabx_set_fig_mode.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         check(L.dabx_set_fig_mode(self._h, stream, C.byref(cfg)))
@@ -1374,6 +1510,66 @@ class Engine:
         L.dabx_get_fig_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         check(L.dabx_get_fig_stats(self._h, stream, _p(st)))
         return {k: int(st[k][0]) for k in FIG_COUNTERS}
+
+    def fig_si_info(self, stream):
+        """FIG 0/7 of both configurations, FIG 0/9, the newest FIG 0/10 and the SI tables' sizes (dabx_fig_si_info) as a dict."""
+        out = np.zeros(1, FIG_SI_INFO)
+        L = load()
+        L.dabx_fig_si_info.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        check(L.dabx_fig_si_info(self._h, stream, _p(out)))
+        return _rec_dict(out[0])
+
+    def _fig_si_table(self, name, dtype, cap, stream, next=None):
+        out = np.zeros(cap, dtype)
+        fn = getattr(load(), name)
+        if next is None:
+            fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+            n = check(fn(self._h, stream, _p(out), cap))
+        else:
+            fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
+            n = check(fn(self._h, stream, int(next), _p(out), cap))
+        return out[:n]
+
+    def fig_user_apps(self, stream, next=False):
+        """FIG 0/13 of the current (or next) configuration in order of filing: a list of dicts (fig_user_apps_dict)."""
+        return [fig_user_apps_dict(r) for r in self._fig_si_table("dabx_fig_user_apps", FIG_USER_APPS, FIG_MAX_USER_APPS, stream, next)]
+
+    def fig_global_defs(self, stream, next=False):
+        return [_rec_dict(r) for r in self._fig_si_table("dabx_fig_global_defs", FIG_GLOBAL_DEF, FIG_MAX_GLOBAL_DEFS, stream, next)]
+
+    def fig_fec_schemes(self, stream, next=False):
+        """FIG 0/14: [(SubChId, FEC scheme)]."""
+        return [(int(r["subch_id"]), int(r["scheme"])) for r in self._fig_si_table("dabx_fig_fec_schemes", FIG_FEC, 64, stream, next)]
+
+    def fig_clusters(self, stream, next=False):
+        return [fig_cluster_dict(r) for r in self._fig_si_table("dabx_fig_clusters", FIG_CLUSTER, FIG_MAX_CLUSTERS, stream, next)]
+
+    def fig_languages(self, stream):
+        """FIG 0/5: [(L/S, SubChId or SCId, language)]."""
+        return [(int(r["ls"]), int(r["id"]), int(r["language"])) for r in self._fig_si_table("dabx_fig_languages", FIG_LANGUAGE, FIG_MAX_LANGUAGES, stream)]
+
+    def fig_programme_types(self, stream):
+        """FIG 0/17: [(SId, S/D, international code)]."""
+        return [(int(r["sid"]), int(r["sd"]), int(r["code"])) for r in self._fig_si_table("dabx_fig_programme_types", FIG_PTY, FIG_MAX_PTYS, stream)]
+
+    def fig_si_stats(self, stream):
+        st = np.zeros(1, FIG_SI_STATS)
+        L = load()
+        L.dabx_get_fig_si_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        check(L.dabx_get_fig_si_stats(self._h, stream, _p(st)))
+        return {k: int(st[k][0]) for k in FIG_SI_COUNTERS}
+
+    def fig_directory(self, stream=-1, next=False, max_per_stream=FIG_MAX_COMPONENTS):
+        """The service directory (dabx_fig_directory: one launch, one copy): every service component of the current (or next) configuration
+        joined with its sub-channel, packet data, language, programme type, user applications and label -- a list of dicts (fig_service_dict)
+        for one stream, a list of such lists for stream = -1.  Charset conversion and the short label stay with the caller."""
+        n = self.n_streams if stream < 0 else 1
+        out, cnt = np.zeros((n, max(1, max_per_stream)), FIG_SERVICE), np.zeros(n, np.int32)
+        L = load()
+        L.dabx_fig_directory.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        check(L.dabx_fig_directory(self._h, stream, int(next), _p(out), max_per_stream, _p(cnt)))
+        rows = [[fig_service_dict(r) for r in out[s, :min(int(cnt[s]), max_per_stream)]] for s in range(n)]
+        return rows if stream < 0 else rows[0]
 
     def read_fig_events(self, stream, max_events=FIG_MAX_EVENTS):
         """The events written since the previous call that the ring still holds, oldest first: ([fig_event_dict], events lost)."""

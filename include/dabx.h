@@ -1865,7 +1865,8 @@ typedef struct {
 typedef struct {
   int32_t enable;             /* 0: off -- the stream's database is dropped, dabx_follow_fic works again */
   int32_t reference_quirks;   /* dabx_fibdec_set_reference_quirks: swap only after change flags 3 */
-  int32_t reserved[2];
+  int32_t service_info;       /* != 0: the service information of FIG 0/5 .. 0/19 is followed too ("Service information" below); 0: not */
+  int32_t reserved[1];
 } dabx_fig_config;
 enum { DABX_FIG_LABEL_ENSEMBLE = 0, DABX_FIG_LABEL_SERVICE = 1, DABX_FIG_LABEL_COMPONENT = 4, DABX_FIG_LABEL_DATA_SERVICE = 5 };
 typedef struct {
@@ -1929,6 +1930,148 @@ int  dabx_read_fig_events(dabx_engine *e, int stream, int max_events, dabx_fig_e
 int  dabx_fig_walk_device(const uint8_t *fibs, const uint8_t *crc_ok, int n_decoders, int n_fibs, int reference_quirks, dabx_fibdec_info *info,
                           int32_t *n_tab, dabx_subch_desc *subch, dabx_packet_component *packets, int32_t *n_labels, dabx_fig_label *labels,
                           dabx_fig_stats *stats, int64_t *n_events, dabx_fig_event *events);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Service information (csrc/fig_si_core.h; dabx_fig_config.service_info): the FIG 0 extensions behind 0/3 that the reference decodes
+ * (fib_decoder_fig0.cpp:333-720) -- 0/5 component language, 0/7 configuration information, 0/8 component global definition, 0/9 country / LTO,
+ * 0/10 date and time, 0/13 user applications, 0/14 FEC scheme, 0/17 programme type, 0/18 announcement support, 0/19 announcement switching --
+ * walked by the same wave at the point where the walk counts fig0_other_ext (which it still does), and the join of all tables into one
+ * record per service component (dabx_fig_directory; fib_decoder.cpp:219-290, :351-460).  With service_info = 0 nothing of this exists.
+ * Where the tables live, as in the reference: 0/7, 0/8, 0/13, 0/14 and the clusters of 0/18 / 0/19 in the configuration the C/N flag selects
+ * (_get_config_ptr); 0/5, 0/9 and 0/17 in the current one; the time of 0/10 in scalars.  Its decisions, line for line:
+ *  - the first description of a key wins (0/5 :346/:366, 0/7 :392, 0/8 :435, 0/14 :569, 0/17 :596); FIG 0/9 is read once (:456);
+ *  - FIG 0/5's long form asks "known?" through a getter whose argument is 8 bits wide (fib_config_fig0.h:242): a component with SCId >= 256
+ *    is never known and filed again by every repetition (until the cap below);
+ *  - FIG 0/13 looks its key up in the CURRENT configuration and files into the C/N one (:525, :547): with C/N = 1 every repetition files
+ *    again.  A known entry is stepped over by its stored SizeBits (:554).  NumUserApps is clamped to 6 (:532-536); the cursor then stands
+ *    inside the 7th application, stays there (ua_clamped) and what follows is read as the next entry;
+ *  - FIG 0/17 steps by 32 bits whatever its flags say, while offset < length * 8 (:590-611);
+ *  - FIG 0/18 reads a 16-bit SId whatever P/D says (:626); cluster id 0 is skipped (:635); _get_cluster (fib_decoder.cpp:722-742) searches
+ *    64 entries, takes the first free one for an unknown id and falls back to entry 0 when all are in use; _set_cluster overwrites the
+ *    flags and appends the SId if the cluster does not list it (:707-719);
+ *  - FIG 0/19 (:658-719): a cluster whose flags meet the ASw flags counts up, and announces the start when the count reaches 5; one that
+ *    counted and no longer meets them is set back to 0 and announces the stop.  An unknown cluster id gets an entry of its own here too,
+ *    with flags 0 (asw_unknown): _get_cluster never returns the null pointer that :686-689 leaves the FIG for;
+ *  - FIG 0/10 overwrites the time with every FIG (:491-506) and reports it iff a FIG 0/9 is filed (:508-513).
+ * A swap follows the configuration's: under reference_quirks the object that becomes current brings only what was filed into it, so 0/5,
+ * 0/9 and 0/17 are gone after it; under the default rule every SI table the announcement never filled is carried over, 0/5, 0/9 and 0/17
+ * always.  A restart clears every table and the time.
+ * Where it departs from the reference (all of it is here):
+ *  - the tables are bounded: DABX_FIG_MAX_GLOBAL_DEFS (one per service component), DABX_FIG_MAX_USER_APPS (64 packet components + 64
+ *    sub-channels with X-PAD applications), DABX_FIG_MAX_LANGUAGES (64 sub-channels + 64 packet components), DABX_FIG_MAX_PTYS (FIG 0/7
+ *    counts at most 63 services), 64 FEC entries and 64 clusters (all there can be), DABX_FIG_MAX_CLUSTER_SIDS (cluster, SId) pairs in all
+ *    (63 services x 7 clusters of a FIG 0/18 entry = 441).  What does not fit is dropped and counted: over_global_defs, over_user_apps,
+ *    over_languages, over_ptys, over_cluster_sids;
+ *  - an entry whose fields do not lie inside its own FIG, by the header's length, ends that FIG's walk and is counted (outside).  The
+ *    reference reads on into whatever follows;
+ *  - no timer gate: mFibLoadingState, which keeps _set_cluster and FIG 0/19 closed until Qt timers have run out (:679,
+ *    fib_decoder.cpp:695), has no counterpart; both are evaluated from the first FIB;
+ *  - of a user application the type, the data length and the first four data bytes are kept (an X-PAD application has its XPadAppTy and
+ *    DSCTy there); the reference keeps type and length;
+ *  - an announcement's start and stop are ONE event per cluster, with the number of SIds the cluster lists in n_services -- also when it
+ *    lists none (a cluster that FIG 0/19 itself made, or entry 0 answering for an id that found no room).  The reference signals once per
+ *    listed SId (:697-716) and so not at all for such a cluster: a host that wants its behaviour drops events with n_services 0;
+ *  - a reset (restart; the next configuration after a swap) clears the cluster table too; FibConfigFig0::reset leaves it;
+ *  - the directory gives a secondary audio component its SCIdS from the short-form FIG 0/8 entry of (SId, SubChId) and its FIG 1/4 label
+ *    through that; the reference lists primary audio components only. */
+#define DABX_FIG_MAX_GLOBAL_DEFS 256
+#define DABX_FIG_MAX_USER_APPS 128
+#define DABX_FIG_MAX_LANGUAGES 128
+#define DABX_FIG_MAX_PTYS 128
+#define DABX_FIG_MAX_CLUSTERS 64
+#define DABX_FIG_MAX_CLUSTER_SIDS 512
+#define DABX_FIG_CLUSTER_LIST 24      /* SIds a dabx_fig_cluster lists */
+enum { DABX_FIG_SI_TABLE = 6, DABX_FIG_TIME = 7, DABX_FIG_ANNOUNCE_START = 8, DABX_FIG_ANNOUNCE_STOP = 9 };
+/* Payloads of the SI events, in dabx_fig_event.u.words (they are written for a stream with service_info on only):
+ *  SI_TABLE        at the frame's end, per configuration that gained an SI entry in it: next, mask of DABX_FIG_SI_HAS_*, then the sizes of
+ *                  its 0/8, 0/13, 0/14, cluster and (cluster, SId) tables, and n_languages | n_ptys << 16 (current configuration only);
+ *  TIME            mjd, hour, minute, second (-1: short form), lto_minutes, utc_flag, lsi;
+ *  ANNOUNCE_START / _STOP   cluster id, ASw flags, SubChId, services in the cluster, next (the C/N flag). */
+enum { DABX_FIG_SI_HAS_LANGUAGE = 1, DABX_FIG_SI_HAS_CONFIG = 2, DABX_FIG_SI_HAS_GLOBAL_DEF = 4, DABX_FIG_SI_HAS_LTO = 8, DABX_FIG_SI_HAS_USER_APPS = 16,
+       DABX_FIG_SI_HAS_FEC = 32, DABX_FIG_SI_HAS_PTY = 64, DABX_FIG_SI_HAS_CLUSTER = 128 };
+typedef struct {
+  int32_t has_config[2], n_services[2], count[2];          /* FIG 0/7 of (current, next) */
+  int32_t has_lto, lto_minutes, ecc, inter_table, lto_ext;  /* FIG 0/9: Ensemble LTO * 30, ECC, InterTableId, Ext flag */
+  int32_t time_set, mjd, hour, minute, second, lsi, utc_flag;   /* FIG 0/10, the newest; second -1: short form */
+  int32_t n_global_defs[2], n_user_apps[2], n_fec[2], n_clusters[2], n_cluster_sids[2];
+  int32_t n_languages, n_ptys;
+  int32_t reserved[2];
+} dabx_fig_si_scalars;          /* 128 bytes */
+typedef struct {
+  uint32_t sid;
+  int8_t   scids, pd, ls, ext;
+  int16_t  subch_id, scid;    /* short form: the sub-channel (scid -1); long form: the SCId (subch_id -1) */
+} dabx_fig_global_def;        /* 12 bytes */
+typedef struct {
+  uint32_t sid;
+  uint16_t size_bits;         /* SizeBits: the entry's length behind the FIG's cursor */
+  uint8_t  scids, pd;
+  uint8_t  n_apps, len[6], reserved0;        /* UserAppDataLength of each */
+  uint16_t type[6];           /* UserAppType */
+  uint8_t  data[6][4];        /* the first four bytes of each application's data, 0 where there are fewer */
+  uint8_t  reserved[12];
+} dabx_fig_user_apps_entry;   /* 64 bytes */
+typedef struct { int32_t ls, id, language, reserved; } dabx_fig_language;           /* ls 0: id = SubChId, 1: id = SCId */
+typedef struct { uint32_t sid; int32_t sd, code, reserved; } dabx_fig_programme_type;
+typedef struct { int32_t subch_id, scheme; } dabx_fig_fec_scheme;
+typedef struct {
+  int32_t cluster_id, flags, announcing, n_services;       /* ASu flags; the FIG 0/19 count; SIds filed */
+  uint32_t sid[DABX_FIG_CLUSTER_LIST];                      /* the first of them, in order of filing */
+  int32_t reserved[4];
+} dabx_fig_cluster;           /* 128 bytes */
+typedef struct {
+  int64_t si_figs;                               /* FIG 0 of an extension the SI walk knows */
+  int64_t language_new, language_known, config_new, config_known, global_def_new, global_def_known, lto_new, lto_known;
+  int64_t time_set;                              /* FIG 0/10 read */
+  int64_t user_apps_new, user_apps_known, user_apps_clamped, fec_new, fec_known, pty_new, pty_known;
+  int64_t cluster_new, cluster_fallback, cluster_zero, cluster_sid_new, cluster_sid_known;
+  int64_t asw_count, asw_start, asw_stop, asw_unknown;
+  int64_t over_global_defs, over_user_apps, over_languages, over_ptys, over_cluster_sids;        /* the guards: dropped, table full */
+  int64_t outside;                               /* the guard: walks ended by an entry that does not lie inside its FIG */
+} dabx_fig_si_stats;          /* 256 bytes */
+enum { DABX_FIG_JOIN_SUBCH = 1, DABX_FIG_JOIN_PACKET = 2, DABX_FIG_JOIN_GLOBAL_DEF = 4, DABX_FIG_JOIN_USER_APPS = 8, DABX_FIG_JOIN_FEC = 16,
+       DABX_FIG_JOIN_LANGUAGE = 32, DABX_FIG_JOIN_PTY = 64, DABX_FIG_JOIN_LABEL = 128 };
+/* One service component with everything the tables say about it.  -1: not known (the look-up that gives it did not succeed). */
+typedef struct {
+  uint32_t sid;
+  int8_t   comp_idx, ps, tmid, ty;      /* index within its FIG 0/2 service; P/S; TMId; ASCTy (TMId 0) or DSCTy (TMId 1: FIG 0/2, TMId 3: FIG 0/3) */
+  int8_t   scids, subch_id, prot_level, short_form;
+  int16_t  cu_start, cu_size, kbps, packet_address;
+  int16_t  scid, language;
+  int8_t   pty, fec_scheme, dg_flag, pd;            /* fec_scheme 0 without a FIG 0/14 (fib_decoder.cpp:408); pd: the P/D flag of its FIG 0/2 */
+  uint8_t  n_apps, app_len[6], reserved0;
+  uint16_t app_type[6];
+  uint8_t  app_data[6][4];
+  dabx_fig_label label;                 /* kind 0xFF: none */
+  uint32_t joined;                      /* DABX_FIG_JOIN_* */
+  int32_t  reference_defined;           /* what _get_data_for_audio_service / _get_data_for_packet_service returns for it (TMId 1: 0) */
+  int32_t  reserved[4];
+} dabx_fig_service;           /* 128 bytes */
+/* The SI database of a stream with service_info on (DABX_E_STATE otherwise), one device-to-host copy per call; next: the configuration. */
+int  dabx_fig_si_info(dabx_engine *e, int stream, dabx_fig_si_scalars *out);
+int  dabx_fig_user_apps(dabx_engine *e, int stream, int next, dabx_fig_user_apps_entry *out, int max_out);
+int  dabx_fig_global_defs(dabx_engine *e, int stream, int next, dabx_fig_global_def *out, int max_out);
+int  dabx_fig_languages(dabx_engine *e, int stream, dabx_fig_language *out, int max_out);
+int  dabx_fig_programme_types(dabx_engine *e, int stream, dabx_fig_programme_type *out, int max_out);
+int  dabx_fig_fec_schemes(dabx_engine *e, int stream, int next, dabx_fig_fec_scheme *out, int max_out);
+int  dabx_fig_clusters(dabx_engine *e, int stream, int next, dabx_fig_cluster *out, int max_out);
+int  dabx_get_fig_si_stats(dabx_engine *e, int stream, dabx_fig_si_stats *out);
+/* The service directory: one launch (k_fig_directory: a wave per stream, a lane per service component of the chosen configuration) and one
+ * copy.  stream >= 0: out[max_per_stream], n_out[1]; stream -1: out[n_streams][max_per_stream], n_out[n_streams] (a stream without
+ * service_info: n_out 0).  Records in the component table's filing order; n_out counts the components, of which min(n_out, max_per_stream)
+ * are written.  The joins are fib_decoder.cpp's: audio :219-290 (a 32-bit SId is refused: reference_defined 0), packet :351-460 (the first
+ * long-form FIG 0/8 of the SId whatever its SCId, :379; language through the 8-bit getter).  Charset conversion and the short label stay
+ * with the host.  Returns 0. */
+int  dabx_fig_directory(dabx_engine *e, int stream, int next, dabx_fig_service *out, int max_per_stream, int32_t *n_out);
+/* dabx_fig_walk_device with the service information on: the outputs of that entry, then per decoder si_info[d], si_stats[d],
+ * global_defs[d][2][DABX_FIG_MAX_GLOBAL_DEFS], user_apps[d][2][DABX_FIG_MAX_USER_APPS], fec[d][2][64], clusters[d][2][64],
+ * languages[d][DABX_FIG_MAX_LANGUAGES], ptys[d][DABX_FIG_MAX_PTYS], and the directory of both configurations: n_dir[d][2],
+ * dir[d][2][DABX_FIG_MAX_COMPONENTS].  Every output is optional. */
+int  dabx_fig_si_walk_device(const uint8_t *fibs, const uint8_t *crc_ok, int n_decoders, int n_fibs, int reference_quirks, dabx_fibdec_info *info,
+                             int32_t *n_tab, dabx_subch_desc *subch, dabx_packet_component *packets, int32_t *n_labels, dabx_fig_label *labels,
+                             dabx_fig_stats *stats, int64_t *n_events, dabx_fig_event *events, dabx_fig_si_scalars *si_info, dabx_fig_si_stats *si_stats,
+                             dabx_fig_global_def *global_defs, dabx_fig_user_apps_entry *user_apps, dabx_fig_fec_scheme *fec, dabx_fig_cluster *clusters,
+                             dabx_fig_language *languages, dabx_fig_programme_type *ptys, int32_t *n_dir, dabx_fig_service *dir);
 
 #ifdef __cplusplus
 }
