@@ -7,7 +7,9 @@
 #include "aac_core.h"
 #include "spectrum_core.h"
 #include "fig_core.h"
+#include "data_core.h"
 #include <cstring>
+#include <vector>
 
 namespace dabx { const char *last_error(); }
 using namespace dabx;
@@ -399,6 +401,82 @@ int dabx_internal_fig_si_host_read(const void *dec, dabx_fibdec_info *info, int3
     for (int i = 0; dir && i < n; i++) fig_dir_record(d->dec.st, d->si, d->dec.labels, k, i, dir + (size_t)k * FIG_MAX_COMP + i);
   }
   return 0;
+}
+
+// Test entries of the data handlers (tests/test_data_handler_cases.py, tests/test_gpu_data_handler_stage.py; not part of include/dabx.h): one
+// slot's crafted data groups -- group i is bytes[groups[i].byte_pos .. + groups[i].length), with the verdicts and the last_frame of its
+// record -- through the handler (data_core.h).  _host: the host build of data_group, needs no device.  _device: k_data_batch, the body of
+// the engine's k_data_handler, one wave.  items [max_items], out_bytes [out_cap]: all items in emission order, byte_pos counted from
+// out_bytes; more items or bytes than that room: DABX_E_ARG.  Returns the number of items; *stats as dabx_get_data_stats (launches 0).
+static int data_walk_args(const char *who, int handler, int n_groups, const dabx_datagroup_info *groups, const uint8_t *bytes, size_t n_bytes, int max_items,
+                          const dabx_data_item *items, const uint8_t *out_bytes, const dabx_data_stats *stats)
+{
+  bool ok = handler >= DABX_DATA_HANDLER_TDC && handler <= DABX_DATA_HANDLER_JOURNALINE && n_groups >= 0 && (groups || !n_groups) && (bytes || !n_bytes) && max_items > 0 &&
+            max_items <= 1 << 20 && items && out_bytes && stats && n_bytes <= (size_t)1 << 30;
+  for (int i = 0; ok && i < n_groups; i++)
+    ok = groups[i].byte_pos >= 0 && (unsigned long long)groups[i].byte_pos + groups[i].length <= n_bytes && groups[i].length <= DABX_DG_MAX_BYTES;
+  if (!ok) { set_error("%s: bad argument", who); return DABX_E_ARG; }
+  return 0;
+}
+static size_t data_pow2(size_t v) { size_t p = 4; while (p < v) p <<= 1; return p; }
+
+int dabx_internal_data_walk_host(int handler, int only_new_revisions, int n_groups, const dabx_datagroup_info *groups, const uint8_t *bytes, size_t n_bytes,
+                                 int max_items, dabx_data_item *items, uint8_t *out_bytes, size_t out_cap, dabx_data_stats *stats)
+{
+  if (int rc = data_walk_args("dabx_internal_data_walk_host", handler, n_groups, groups, bytes, n_bytes, max_items, items, out_bytes, stats)) return rc;
+  const size_t n_rec = data_pow2((size_t)max_items), n_out = data_pow2(out_cap);
+  std::vector<dabx_data_item> recs(n_rec);
+  std::vector<uint8_t> ring(n_out), jl(DATA_JL_TABLE, (uint8_t)DATA_JL_NONE);
+  uint16_t crc[256], xpow[DATA_XPOW];
+  data_host_tables(crc, xpow);
+  DataWave w{};
+  DataCounters cnt{};
+  w.c = &cnt;
+  w.recs = recs.data(); w.ring = ring.data(); w.rec_mask = n_rec - 1; w.bytes_mask = n_out - 1; w.jl = jl.data(); w.crc = crc; w.xpow = xpow;
+  w.only_new = only_new_revisions ? 1 : 0;
+  for (int i = 0; i < n_groups; i++)
+    data_group(w, handler, bytes + groups[i].byte_pos, groups[i].length, groups[i].crc_flag != 0, groups[i].crc_ok != 0, groups[i].last_frame, (unsigned)i);
+  data_present(w, handler, stats);
+  if (w.n_recs > max_items || (unsigned long long)w.n_bytes > out_cap) { set_error("dabx_internal_data_walk_host: %lld items of %lld bytes do not fit the room", w.n_recs, w.n_bytes); return DABX_E_ARG; }
+  memcpy(items, recs.data(), sizeof(dabx_data_item) * (size_t)w.n_recs);
+  memcpy(out_bytes, ring.data(), (size_t)w.n_bytes);
+  return (int)w.n_recs;
+}
+
+int dabx_internal_data_walk_device(int handler, int only_new_revisions, int n_groups, const dabx_datagroup_info *groups, const uint8_t *bytes, size_t n_bytes,
+                                   int max_items, dabx_data_item *items, uint8_t *out_bytes, size_t out_cap, dabx_data_stats *stats)
+{
+  int rc = data_walk_args("dabx_internal_data_walk_device", handler, n_groups, groups, bytes, n_bytes, max_items, items, out_bytes, stats);
+  if (rc) return rc;
+  if (n_groups == 0) { set_error("dabx_internal_data_walk_device: no group"); return DABX_E_ARG; }      // (nothing to launch for)
+  if ((rc = need_device())) return rc;
+  const size_t n_rec = data_pow2((size_t)max_items), n_out = data_pow2(out_cap), n_in = data_pow2(n_bytes);
+  const bool jl = handler == DABX_DATA_HANDLER_JOURNALINE;
+  DevBuf dslot, dgrp, din, drec, dring;
+  if ((rc = dslot.alloc(sizeof(DataBatchSlot))) || (rc = dgrp.from_host(groups, sizeof(dabx_datagroup_info) * (size_t)n_groups)) || (rc = din.alloc(n_in)) ||
+      (rc = drec.alloc(sizeof(dabx_data_item) * n_rec)) || (rc = dring.alloc(n_out + (jl ? DATA_JL_TABLE : 0)))) return rc;
+  DABX_HIP(hipMemset(din.p, 0, n_in));
+  if (n_bytes) DABX_HIP(hipMemcpy(din.p, bytes, n_bytes, hipMemcpyHostToDevice));
+  if (jl) DABX_HIP(hipMemset(dring.as<uint8_t>() + n_out, DATA_JL_NONE, DATA_JL_TABLE));
+  DataBatchSlot b{};
+  b.st.out.bytes = dring.as<uint8_t>(); b.st.out.recs = drec.as<dabx_data_item>(); b.st.out.bytes_mask = (uint32_t)(n_out - 1); b.st.out.rec_mask = (uint32_t)(n_rec - 1);
+  b.st.handler = handler; b.st.only_new = only_new_revisions ? 1 : 0; b.st.jl = jl ? dring.as<uint8_t>() + n_out : nullptr;
+  b.groups = dgrp.as<dabx_datagroup_info>(); b.n_groups = n_groups;
+  DABX_HIP(hipMemcpy(dslot.p, &b, sizeof(b), hipMemcpyHostToDevice));
+  if ((rc = launch_data_batch(dslot.as<DataBatchSlot>(), 1, din.as<uint8_t>(), (unsigned long long)n_in - 1, 0))) return rc;
+  DABX_HIP(hipStreamSynchronize(0));
+  if ((rc = dslot.to_host(&b, sizeof(b)))) return rc;
+  memset(stats, 0, sizeof(*stats));
+  stats->groups = b.st.groups; stats->items = b.st.out.count; stats->bytes = b.st.out.n_bytes;
+  memcpy(&stats->dg_overrun, &b.st.c, sizeof(DataCounters));
+  stats->active = 1; stats->handler = handler;
+  if (b.st.out.count > max_items || (unsigned long long)b.st.out.n_bytes > out_cap) {
+    set_error("dabx_internal_data_walk_device: %lld items of %lld bytes do not fit the room", b.st.out.count, b.st.out.n_bytes);
+    return DABX_E_ARG;
+  }
+  if (b.st.out.count && (rc = drec.to_host(items, sizeof(dabx_data_item) * (size_t)b.st.out.count))) return rc;
+  if (b.st.out.n_bytes && (rc = dring.to_host(out_bytes, (size_t)b.st.out.n_bytes))) return rc;
+  return (int)b.st.out.count;
 }
 
 // cir_viewer.cpp:66-95 on crafted rows: the row function of k_cir (cir_core.h, cir_row_block), one block per row

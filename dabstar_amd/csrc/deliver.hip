@@ -12,6 +12,7 @@
 #include "carousel_core.h"
 #include "mp2_core.h"
 #include "aac_core.h"
+#include "data_core.h"
 #include "eti_core.h"
 #include "tii_core.h"
 #include "scope_core.h"
@@ -319,6 +320,43 @@ int launch_deliver_aac(const EngineDev &e, const DeliverDev &dv, const AacStream
   if (!off_aac || ad.n <= 0) return 0;
   DABX_HIP(hipMemsetAsync(dv.slab + off_aac, 0, sizeof(dabx_chunk_aac) * (size_t)e.n_streams * e.max_subch, st));
   hipLaunchKernelGGL(k_deliver_aac, dim3(ad.n), dim3(64), 0, st, ad, dv.slab, off_aac);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+
+// The data section (dabx_chunk_data): one wave per slot with a data handler on, behind k_data_handler -- out_ring_gather of what the slot
+// emitted since the previous chunk into its room, and its row of the table (zeroed in front: rows of slots without a handler stay zero)
+__global__ __launch_bounds__(64) void k_deliver_data(DataDev dd, uint8_t *slab, unsigned long long off_data)
+{
+  DataSlot &ds = dd.slots[blockIdx.x];
+  if (!ds.out.dl_rec_off) return;
+  const OutGather g = out_ring_gather(ds.out, slab, threadIdx.x);
+  if (threadIdx.x == 0) {
+    dabx_chunk_data t;
+    t.first_item = g.first; t.n_items = g.n; t.items_lost = (int)(g.first - g.done); t.rec_off = ds.out.dl_rec_off; t.bytes_off = ds.out.dl_bytes_off; t.n_bytes = g.n_bytes;
+    t.groups = ds.groups; t.items = ds.out.count; t.bytes = ds.out.n_bytes;
+    for (int i = 0; i < 8; i++) t.reserved[i] = 0;
+    reinterpret_cast<dabx_chunk_data *>(slab + off_data)[(size_t)ds.s * dd.max_subch + ds.j] = t;
+    ds.out.dl_done = ds.out.count;
+  }
+}
+int launch_deliver_data(const EngineDev &e, const DeliverDev &dv, const DataDev &dd, unsigned long long off_data, hipStream_t st)
+{
+  if (!off_data || dd.n <= 0) return 0;
+  DABX_HIP(hipMemsetAsync(dv.slab + off_data, 0, sizeof(dabx_chunk_data) * (size_t)e.n_streams * e.max_subch, st));
+  hipLaunchKernelGGL(k_deliver_data, dim3(dd.n), dim3(64), 0, st, dd, dv.slab, off_data);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+
+// The second extension of a slab that carries DABX_DELIVER_DATA, at byte 192
+__global__ void k_deliver_ext2(dabx_chunk_header_ext2 ext2, uint8_t *slab)
+{
+  if (blockIdx.x == 0 && threadIdx.x == 0) *reinterpret_cast<dabx_chunk_header_ext2 *>(slab + sizeof(dabx_chunk_header) + sizeof(dabx_chunk_header_ext)) = ext2;
+}
+int launch_deliver_ext2(const dabx_chunk_header_ext2 &ext2, uint8_t *slab, hipStream_t st)
+{
+  hipLaunchKernelGGL(k_deliver_ext2, dim3(1), dim3(64), 0, st, ext2, slab);
   DABX_HIP(hipGetLastError());
   return 0;
 }

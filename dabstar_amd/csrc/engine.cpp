@@ -384,6 +384,8 @@ void dabx_destroy(dabx_engine *e)
   e->aac.destroy();
   e->mot.destroy();
   e->car.destroy();
+  e->dat.destroy();
+  for (hipEvent_t ev : e->dat_ctl.timed) (void)hipEventDestroy(ev);
   for (void *p : e->allocs) (void)hipFree(p);
   if (e->locked_host) (void)hipHostFree(e->locked_host);
   if (e->seq_timeouts_host) (void)hipHostFree(e->seq_timeouts_host);
@@ -417,6 +419,7 @@ static int set_subchannels_impl(dabx_engine *e, int stream, const dabx_subch_des
   if ((rc = e->pad.download(d.max_subch))) return rc;
   if ((rc = e->mot.download(d.max_subch))) return rc;
   if ((rc = e->car.download(d.max_subch))) return rc;
+  if ((rc = e->dat.download(d.max_subch))) return rc;
   if ((rc = e->mpa.download(d.max_subch))) return rc;
   if ((rc = e->aac.download(d.max_subch))) return rc;
   int max_kbps = e->max_kbps;
@@ -515,6 +518,10 @@ static int set_subchannels_impl(dabx_engine *e, int stream, const dabx_subch_des
   if (!e->car.host.empty()) {           // ... and the carousel decoding behind it
     for (size_t sj : restarted) e->car.drop(sj);
     if ((rc = carousel_follow_packet(e))) return rc;
+  }
+  if (!e->dat.host.empty()) {           // ... and the data handler behind it, in the same way
+    for (size_t sj : restarted) e->dat.drop(sj);
+    if ((rc = data_follow_packet(e))) return rc;
   }
   if (!e->pad.host.empty()) {           // ... and so does PAD decoding
     for (size_t sj : restarted) e->pad.drop(sj);
@@ -848,7 +855,7 @@ int dabx_process(dabx_engine *e, int max_frames, int sync)
       rc = launch_msc_batch(e->dev, 4 * e->pending_frames, e->have_fast ? &e->fast : nullptr, e->ss, e->mk, e->dl.open ? &dv : nullptr, &tail,
                             e->pkt.dev.n > 0 ? &e->pkt.dev : nullptr, e->pad.dev.n > 0 ? &e->pad.dev : nullptr, e->mot.dev.n > 0 ? &e->mot.dev : nullptr,
                             e->car.dev.n > 0 ? &e->car.dev : nullptr, with_eti ? &eti : nullptr, e->mpa.dev.n > 0 ? &e->mpa.dev : nullptr, &e->mpa_launches,
-                            e->aac.dev.n > 0 ? &e->aac.dev : nullptr, &e->aac_launches);
+                            e->aac.dev.n > 0 ? &e->aac.dev : nullptr, &e->aac_launches, e->dat.dev.n > 0 ? &e->dat.dev : nullptr, &e->dat_ctl);
       if (rc) {
         if (e->dl.open) e->delivery_abort(dl_slot, dl_dev);          // the slabs of the chunk that was begun: never left IN_FLIGHT without a copy job
         e->pending_frames = 0;

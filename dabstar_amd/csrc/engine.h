@@ -5,6 +5,7 @@
 #include "pad_core.h"
 #include "mot_core.h"
 #include "carousel_core.h"
+#include "data_core.h"
 #include "mp2_core.h"
 #include "aac_core.h"
 #include "tii_core.h"
@@ -91,6 +92,8 @@ struct Delivery {
   bool mp2_audio() const { return (what & DABX_DELIVER_MP2_AUDIO) != 0; }      // the MP2 audio section (deliver.hip, k_deliver_mp2_audio), while a slot has the mode on
   bool aac() const { return (what & DABX_DELIVER_AAC) != 0; }      // the AAC section (deliver.hip, k_deliver_aac), while a slot has the mode on
   bool eti() const { return (what & DABX_DELIVER_ETI) != 0; }
+  bool data() const { return (what & DABX_DELIVER_DATA) != 0; }    // the data section (deliver.hip, k_deliver_data), while a slot has a handler on
+  dabx_chunk_header_ext2 ext2{};                 // the second extension as it goes into a slab; zeros without DABX_DELIVER_DATA
   EtiDev eti_dev(int devslab) const
   {
     return EtiDev{eti_front, eti_next, eti_stage[devslab], dev[devslab], subch_id, hdr.off_eti, eti_rows_off, hdr.max_frames, 0};
@@ -126,7 +129,7 @@ struct Ingest {
   int16_t *tab_int = nullptr; float *tab_frac = nullptr;
 };
 
-// The job table of a stage that runs on some slots only (k_packet: PacketSlot / PacketDev, k_pad: PadSlot / PadDev, k_mot: MotSlot / MotDev, k_carousel: CarouselSlot / CarouselDev).  Nothing of it exists
+// The job table of a stage that runs on some slots only (k_packet: PacketSlot / PacketDev, k_pad: PadSlot / PadDev, k_mot: MotSlot / MotDev, k_carousel: CarouselSlot / CarouselDev, k_data_handler: DataSlot / DataDev).  Nothing of it exists
 // until the stage's dabx_set_*_mode first switches a slot on: host stays empty, dev.n stays 0 and no batch launches the kernel.
 // host[sj].st mirrors the device's table entry of the slot; the device owns it between download and upload (both with the engine drained).
 template <class Slot, class Dev> struct JobTable {
@@ -349,6 +352,8 @@ struct dabx_engine : dabx::EngineHead {         // (iqfile.h: the ring format, w
   long long mpa_launches = 0;                  // k_mp2_audio launches (dabx_mp2_audio_stats.launches)
   JobTable<AacStreamSlot, AacStreamDev> aac;   // AAC stream slots (include/dabx.h "AAC stream", k_aac_stream): DAB+ slots all of them
   long long aac_launches = 0;                  // k_aac_stream launches (dabx_aac_stream_stats.launches)
+  JobTable<DataSlot, DataDev> dat;             // slots with a data handler (include/dabx.h "The data handlers of a packet-mode slot", k_data_handler): packet-mode slots all of them
+  DataStageCtl dat_ctl;                        // k_data_handler launches (dabx_data_stats.launches) and their timing events
   int build_msc_classes();
   int delivery_layout();                       // offsets of every slot's bytes in a slab for the sub-channels configured now
   int delivery_begin(DeliverDev *dv, int *slot, int *devslab);     // a chunk closes: host + device slab, front gather on stream a
@@ -402,6 +407,7 @@ void spectrum_stage_free(dabx_engine *e);
 void pad_count_sources(dabx_engine *e);
 int mot_follow_pad(dabx_engine *e);
 int carousel_follow_packet(dabx_engine *e);
+int data_follow_packet(dabx_engine *e);
 
 // How the dabx_read_* and dabx_get_*_stats entries of a ListedStage begin: the engine drained, the stream's state record read from the
 // device.  0: *c holds it; 1: the stage does not exist (nothing to read: the entry returns 0); < 0: the error to return.

@@ -14,7 +14,8 @@ static_assert(sizeof(dabx_chunk_header) == 128 && sizeof(dabx_chunk_stream) == 7
               sizeof(dabx_superframe_info) == 32 && sizeof(dabx_chunk_eti) == 64 && offsetof(dabx_chunk_header, off_eti) == 120 &&
               sizeof(dabx_chunk_header_ext) == 64 && sizeof(dabx_chunk_tii) == 32 && sizeof(dabx_tii_event) == 32 && sizeof(dabx_tii_result) == 16 &&
               sizeof(dabx_chunk_mp2_audio) == 128 && offsetof(dabx_chunk_header_ext, off_mp2_audio) == 16 &&
-              sizeof(dabx_chunk_aac) == 128 && offsetof(dabx_chunk_header_ext, off_aac) == 24,
+              sizeof(dabx_chunk_aac) == 128 && offsetof(dabx_chunk_header_ext, off_aac) == 24 &&
+              sizeof(dabx_chunk_header_ext2) == 64 && sizeof(dabx_chunk_data) == 128 && offsetof(dabx_chunk_data, groups) == 40,
               "include/dabx.h: chunk record layout");
 static constexpr int DL_SF_CAP = (4 * DL_FRAMES + 4) / 5;          // super frames one chunk can complete (4 CIFs may be waiting from before)
 #if DABX_MSC_BATCH == 7
@@ -95,6 +96,8 @@ int dabx_engine::delivery_layout()
   size_t off = sizeof(dabx_chunk_header);
   dabx_chunk_header_ext x{};
   if (D.what & ~255) { x.magic = DABX_CHUNK_EXT_MAGIC; x.bytes = sizeof(x); off += sizeof(x); }     // a bit the header has no word for: its extension follows it
+  dabx_chunk_header_ext2 x2{};
+  if (D.data()) { x2.magic = DABX_CHUNK_EXT2_MAGIC; x2.bytes = sizeof(x2); off += sizeof(x2); }     // the first extension is full: a second one behind it, at byte 192
   h.off_stream = off; off = align_up(off + S * sizeof(dabx_chunk_stream), 16);
   h.off_subch = off; off = align_up(off + S * M * sizeof(dabx_chunk_subch), 16);
   const bool fib = (D.what & DABX_DELIVER_FIB) != 0;
@@ -139,6 +142,8 @@ int dabx_engine::delivery_layout()
   off = layout_section(mpa, D.mp2_audio() && !d.fic_only, off, S * M * sizeof(dabx_chunk_mp2_audio), &x.off_mp2_audio);
   // ... and the AAC section (dabx_chunk_aac), in the same way
   off = layout_section(aac, D.aac() && !d.fic_only, off, S * M * sizeof(dabx_chunk_aac), &x.off_aac);
+  // ... and the data section (dabx_chunk_data), announced by the second extension
+  off = layout_section(dat, D.data() && !d.fic_only, off, S * M * sizeof(dabx_chunk_data), &x2.off_data);
   for (int i = REC_SCOPE; i < N_REC_SECTIONS; i++) if (int rc = layout_records(D.rec[i])) return rc;
   off = align_up(off, 256);
   h.off_msc = off;
@@ -159,6 +164,8 @@ int dabx_engine::delivery_layout()
   }
   D.hdr = h;
   D.ext = x;
+  D.ext2 = x2;
+  dat_ctl.off_data = x2.off_data;
   D.bytes = off;
   if (!pkt.host.empty()) if (int rc = pkt.upload()) return rc;
   if (!pad.host.empty()) if (int rc = pad.upload()) return rc;
@@ -166,6 +173,7 @@ int dabx_engine::delivery_layout()
   if (!car.host.empty()) if (int rc = car.upload()) return rc;
   if (!mpa.host.empty()) if (int rc = mpa.upload()) return rc;
   if (!aac.host.empty()) if (int rc = aac.upload()) return rc;
+  if (!dat.host.empty()) if (int rc = dat.upload()) return rc;
   if (S * M) {
     DABX_HIP(hipMemcpy(D.layout_off, lo.data(), sizeof(unsigned long long) * 3 * S * M, hipMemcpyHostToDevice));
     std::vector<int32_t> ids(subch_id_host.begin(), subch_id_host.begin() + S * M);
@@ -219,7 +227,8 @@ int dabx_engine::delivery_begin(DeliverDev *dv, int *slot, int *devslab)
   int rc = launch_deliver_front(dev, *dv, stream);
   // the ETI stage's front half: the FIB ring is the front end's, which rewrites it while the chunk's MSC batch is decoded
   if (!rc && D.eti()) rc = launch_eti_front(dev, D.eti_dev(*devslab), stream, mk);
-  if (!rc && D.ext.magic && !D.tii()) rc = launch_deliver_ext(D.ext, D.dev[*devslab], stream);      // (k_deliver_tii writes the header's extension otherwise)
+  if (!rc && D.ext.magic && !D.tii()) rc = launch_deliver_ext(D.ext, D.dev[*devslab], stream);
+  if (!rc && D.ext2.magic) rc = launch_deliver_ext2(D.ext2, D.dev[*devslab], stream);      // (k_deliver_tii writes the header's extension otherwise)
   // the record sections: behind the stages' kernels of the chunk's last frame, which the front-end stream has run by now
   for (int i = 0; i < N_REC_SECTIONS && !rc; i++) {
     const Delivery::RecSection &r = D.rec[i];
@@ -367,6 +376,8 @@ void delivery_free(dabx_engine *e)
   hip_free_all({D.layout_off, D.subch_id, D.frames_done, D.cif_done, D.sf_done, D.eti_front, D.eti_next, D.eti_stage[0], D.eti_stage[1], D.eti_stage[2]});
   for (Delivery::RecSection &r : D.rec) { hip_free_all({r.done, r.off}); r.done = nullptr; r.off = nullptr; r.room.clear(); }
   D.ext = dabx_chunk_header_ext{};
+  D.ext2 = dabx_chunk_header_ext2{};
+  e->dat_ctl.off_data = 0;
   D.layout_off = nullptr; D.subch_id = nullptr; D.frames_done = D.cif_done = D.sf_done = nullptr;
   D.eti_front = nullptr; D.eti_next = nullptr; D.eti_rows_off = 0;
   for (int k = 0; k < Delivery::NDEV; k++) D.eti_stage[k] = nullptr;
@@ -383,7 +394,7 @@ extern "C" {
 
 int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
 {
-  if (!e || (cfg && (cfg->host_slabs < 0 || cfg->host_slabs == 1 || cfg->host_slabs > 64 || (cfg->what & ~(1023 | DABX_DELIVER_AAC | DABX_DELIVER_SCOPE | DABX_DELIVER_CIR | DABX_DELIVER_SPECTRUM | DABX_DELIVER_FIG)) || cfg->copy_engine < 0 || cfg->copy_engine > 1))) {
+  if (!e || (cfg && (cfg->host_slabs < 0 || cfg->host_slabs == 1 || cfg->host_slabs > 64 || (cfg->what & ~(1023 | DABX_DELIVER_AAC | DABX_DELIVER_SCOPE | DABX_DELIVER_CIR | DABX_DELIVER_SPECTRUM | DABX_DELIVER_FIG | DABX_DELIVER_DATA)) || cfg->copy_engine < 0 || cfg->copy_engine > 1))) {
     set_error("dabx_delivery_open: bad argument");
     return DABX_E_ARG;
   }
@@ -427,6 +438,13 @@ int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
     set_error("dabx_delivery_open: DABX_DELIVER_FIG needs at least one DABX_DELIVER_* bit below 128 beside it");
     return DABX_E_ARG;
   }
+  // ... and DABX_DELIVER_DATA, in the same way
+  if (cfg && (cfg->what & DABX_DELIVER_DATA) &&
+      !(cfg->what & ~(DABX_DELIVER_DATA | DABX_DELIVER_FIG | DABX_DELIVER_SPECTRUM | DABX_DELIVER_CIR | DABX_DELIVER_SCOPE | DABX_DELIVER_AAC | DABX_DELIVER_MP2_AUDIO |
+                      DABX_DELIVER_TII | DABX_DELIVER_ETI))) {
+    set_error("dabx_delivery_open: DABX_DELIVER_DATA needs at least one DABX_DELIVER_* bit below 128 beside it");
+    return DABX_E_ARG;
+  }
   if (e->dl.open) { set_error("dabx_delivery_open: already open"); return DABX_E_STATE; }
   int rc = sync_all(e);
   if (rc) return rc;
@@ -458,13 +476,14 @@ int dabx_delivery_open(dabx_engine *e, const dabx_delivery_config *cfg)
   if (M && !d.fic_only) cap += S * ((size_t)4 * F * per_cif + (size_t)DL_SF_CAP * 5 * per_cif + 2 * 16 * M + M * DL_SF_CAP * sizeof(dabx_superframe_info));
   // ... and the data-group, the PAD and the MOT section
   if ((rc = e->pkt.download(d.max_subch)) || (rc = e->pad.download(d.max_subch)) || (rc = e->mot.download(d.max_subch)) ||
-      (rc = e->car.download(d.max_subch)) || (rc = e->mpa.download(d.max_subch)) || (rc = e->aac.download(d.max_subch))) return rc;
+      (rc = e->car.download(d.max_subch)) || (rc = e->mpa.download(d.max_subch)) || (rc = e->aac.download(d.max_subch)) || (rc = e->dat.download(d.max_subch))) return rc;
   cap += section_capacity(e->pkt, S * M * sizeof(dabx_chunk_dg)) + section_capacity(e->pad, S * M * sizeof(dabx_chunk_pad)) +
          section_capacity(e->mot, S * M * sizeof(dabx_chunk_mot)) + section_capacity(e->car, S * M * sizeof(dabx_chunk_mot));
   if (D.eti()) cap += 16 + S * sizeof(dabx_chunk_eti) + 256 + S * 4 * F * DABX_ETI_FRAME_BYTES;      // ... and the ETI section: its table and 4 F rows per stream
   if (D.what & ~255) cap += sizeof(dabx_chunk_header_ext);          // ... and the header's extension, where delivery_layout puts one
   if (D.mp2_audio()) cap += section_capacity(e->mpa, S * M * sizeof(dabx_chunk_mp2_audio));   // ... and the MP2 audio section
   if (D.aac()) cap += section_capacity(e->aac, S * M * sizeof(dabx_chunk_aac));               // ... and the AAC section
+  if (D.data()) cap += sizeof(dabx_chunk_header_ext2) + section_capacity(e->dat, S * M * sizeof(dabx_chunk_data));      // ... the second extension and the data section
   for (int i = 0; i < N_REC_SECTIONS; i++) {                        // ... and the record sections: a table and chunk_records slots per stream with room
     Delivery::RecSection &r = D.rec[i];
     const bool want = (D.what & r.bit) != 0;

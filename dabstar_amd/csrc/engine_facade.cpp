@@ -242,7 +242,8 @@ int dabx_internal_msc_decode(dabx_engine *e, const int32_t *cifs_per_stream, int
     e->dev.snap = e->snap_buf[e->ss.batch_parity];
     rc = launch_msc_batch(e->dev, batch_cifs, e->have_fast ? &e->fast : nullptr, e->ss, e->mk, nullptr, nullptr, e->pkt.dev.n > 0 ? &e->pkt.dev : nullptr,
                           e->pad.dev.n > 0 ? &e->pad.dev : nullptr, e->mot.dev.n > 0 ? &e->mot.dev : nullptr, e->car.dev.n > 0 ? &e->car.dev : nullptr,
-                          nullptr, e->mpa.dev.n > 0 ? &e->mpa.dev : nullptr, &e->mpa_launches, e->aac.dev.n > 0 ? &e->aac.dev : nullptr, &e->aac_launches);
+                          nullptr, e->mpa.dev.n > 0 ? &e->mpa.dev : nullptr, &e->mpa_launches, e->aac.dev.n > 0 ? &e->aac.dev : nullptr, &e->aac_launches,
+                          e->dat.dev.n > 0 ? &e->dat.dev : nullptr, &e->dat_ctl);
   }
   const int rc2 = sync_all(e);
   (void)hipFree(counts_dev);

@@ -45,6 +45,19 @@ int carousel_follow_packet(dabx_engine *e)
   return tab.upload();
 }
 
+// ... and the data-handler job table, likewise
+int data_follow_packet(dabx_engine *e)
+{
+  auto &tab = e->dat;
+  if (tab.host.empty()) return 0;
+  for (size_t sj = 0; sj < tab.host.size(); sj++) {
+    if (!tab.host[sj].on) continue;
+    if (!e->pkt.on(sj)) tab.drop(sj);
+    else tab.host[sj].st.pkt_index = e->pkt.index[sj];
+  }
+  return tab.upload();
+}
+
 }  // namespace dabx
 
 // ---- slots with output rings (out_ring.h): what the packet-mode and the PAD entry points below share -------------------------------------
@@ -141,6 +154,8 @@ static_assert(sizeof(dabx_chunk_dg) == 128 && sizeof(dabx_datagroup_info) == 32 
 static_assert(sizeof(dabx_chunk_pad) == 128 && sizeof(dabx_pad_item) == 32 && sizeof(dabx_pad_stats) == 128 && sizeof(dabx_pad_config) == 32, "include/dabx.h: PAD records");
 static_assert(sizeof(dabx_chunk_mot) == 128 && sizeof(dabx_mot_object) == 32 && sizeof(dabx_mot_stats) == 128 && sizeof(dabx_mot_config) == 32, "include/dabx.h: MOT records");
 static_assert(sizeof(dabx_carousel_stats) == 128 && sizeof(dabx_carousel_config) == 32, "include/dabx.h: carousel records");
+static_assert(sizeof(dabx_data_item) == 32 && sizeof(dabx_data_stats) == 256 && sizeof(dabx_data_config) == 32 && offsetof(dabx_data_item, group) == 24 &&
+              offsetof(dabx_data_stats, launches) == 232, "include/dabx.h: data-handler records");
 static_assert(sizeof(dabx_mp2_sync_stats) == 64 && offsetof(dabx_pad_config, source) == 4, "include/dabx.h: PAD of MP2 frames");
 static_assert(sizeof(dabx_mp2_audio_frame) == 32 && sizeof(dabx_mp2_audio_stats) == 64 && sizeof(dabx_mp2_audio_config) == 32 && offsetof(dabx_mp2_audio_frame, flags) == 28,
               "include/dabx.h: MP2 audio records");
@@ -174,9 +189,10 @@ int dabx_set_packet_mode(dabx_engine *e, int stream, int j, const dabx_packet_co
     tab.host.resize((size_t)e->dev.n_streams * e->dev.max_subch);
     tab.index.assign(tab.host.size(), -1);
   }
-  if ((rc = tab.download(e->dev.max_subch)) || (rc = e->car.download(e->dev.max_subch))) return rc;
+  if ((rc = tab.download(e->dev.max_subch)) || (rc = e->car.download(e->dev.max_subch)) || (rc = e->dat.download(e->dev.max_subch))) return rc;
   tab.drop(sj);
   e->car.drop(sj);                                                     // the packet stage restarts with empty rings: nothing for k_carousel to follow
+  e->dat.drop(sj);                                                     // ... or for k_data_handler
   if (cfg) {
     // two full batches (56 logical frames) of single-packet groups: a record per 24-byte packet, their payloads, and room for the series
     // under assembly, which lives in the byte ring in front of the completed groups (packet_core.h); a chunk: one batch of them
@@ -189,13 +205,15 @@ int dabx_set_packet_mode(dabx_engine *e, int stream, int j, const dabx_packet_co
       set_error("dabx_set_packet_mode: out of device memory");
       (void)tab.upload();
       (void)carousel_follow_packet(e);
+      (void)data_follow_packet(e);
       return DABX_E_NOMEM;
     }
     tab.host[sj] = h;
   }
   if ((rc = tab.upload())) return rc;
   if ((rc = carousel_follow_packet(e))) return rc;
-  return relayout_open_delivery(e, sj, sc, e->pad, e->mot, e->car, e->mpa, e->aac);
+  if ((rc = data_follow_packet(e))) return rc;
+  return relayout_open_delivery(e, sj, sc, e->pad, e->mot, e->car, e->mpa, e->aac, e->dat);
 }
 
 int dabx_read_datagroups(dabx_engine *e, int stream, int j, int n, dabx_datagroup_info *info, uint8_t *bytes, size_t max_bytes)
@@ -269,7 +287,7 @@ int dabx_set_pad_mode(dabx_engine *e, int stream, int j, const dabx_pad_config *
   if ((rc = tab.upload())) return rc;
   pad_count_sources(e);
   if ((rc = mot_follow_pad(e))) return rc;
-  return relayout_open_delivery(e, sj, sc, e->pkt, e->mot, e->car, e->mpa, e->aac);
+  return relayout_open_delivery(e, sj, sc, e->pkt, e->mot, e->car, e->mpa, e->aac, e->dat);
 }
 
 int dabx_get_mp2_sync_stats(dabx_engine *e, int stream, int j, dabx_mp2_sync_stats *out)
@@ -357,7 +375,7 @@ int dabx_set_mp2_audio_mode(dabx_engine *e, int stream, int j, const dabx_mp2_au
     }
   }
   if ((rc = tab.upload())) return rc;
-  return relayout_open_delivery(e, sj, sc, e->pkt, e->pad, e->mot, e->car, e->aac);
+  return relayout_open_delivery(e, sj, sc, e->pkt, e->pad, e->mot, e->car, e->aac, e->dat);
 }
 
 int dabx_read_mp2_audio(dabx_engine *e, int stream, int j, int n, dabx_mp2_audio_frame *recs, uint8_t *pcm, size_t max_bytes)
@@ -420,7 +438,7 @@ int dabx_set_aac_stream_mode(dabx_engine *e, int stream, int j, const dabx_aac_s
     tab.host[sj] = h;
   }
   if ((rc = tab.upload())) return rc;
-  return relayout_open_delivery(e, sj, sc, e->pkt, e->pad, e->mot, e->car, e->mpa);
+  return relayout_open_delivery(e, sj, sc, e->pkt, e->pad, e->mot, e->car, e->mpa, e->dat);
 }
 
 int dabx_read_aac_frames(dabx_engine *e, int stream, int j, int n, dabx_aac_frame *recs, uint8_t *bytes, size_t max_bytes)
@@ -494,7 +512,7 @@ int dabx_set_mot_mode(dabx_engine *e, int stream, int j, const dabx_mot_config *
     }
   }
   if ((rc = tab.upload())) return rc;
-  return relayout_open_delivery(e, sj, sc, e->pkt, e->pad, e->car, e->mpa, e->aac);
+  return relayout_open_delivery(e, sj, sc, e->pkt, e->pad, e->car, e->mpa, e->aac, e->dat);
 }
 
 int dabx_read_mot_objects(dabx_engine *e, int stream, int j, int n, dabx_mot_object *info, uint8_t *bytes, size_t max_bytes)
@@ -591,7 +609,7 @@ int dabx_set_carousel_mode(dabx_engine *e, int stream, int j, const dabx_carouse
     }
   }
   if ((rc = tab.upload())) return rc;
-  return relayout_open_delivery(e, sj, sc, e->pkt, e->pad, e->mot, e->mpa, e->aac);
+  return relayout_open_delivery(e, sj, sc, e->pkt, e->pad, e->mot, e->mpa, e->aac, e->dat);
 }
 
 int dabx_get_carousel_stats(dabx_engine *e, int stream, int j, dabx_carousel_stats *out)
@@ -615,6 +633,105 @@ int dabx_get_carousel_stats(dabx_engine *e, int stream, int j, dabx_carousel_sta
   out->dir_segments = i32(x.dir_segments); out->dir_objects = i32(x.dir_objects); out->dir_short = i32(x.dir_short); out->dir_seg_bad = i32(x.dir_seg_bad);
   out->dir_cut = i32(x.dir_cut); out->dg_overrun = i32(x.dg_overrun); out->active = 1;
   return 0;
+}
+
+// ---- the data handlers of a packet-mode slot (data_core.h, k_data_handler) ----------------------------------------------------------------
+int dabx_set_data_mode(dabx_engine *e, int stream, int j, const dabx_data_config *cfg)
+{
+  if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch) { set_error("dabx_set_data_mode: bad argument"); return DABX_E_ARG; }
+  if (cfg && (cfg->size < 2 * sizeof(uint32_t) || cfg->handler < DABX_DATA_HANDLER_TDC || cfg->handler > DABX_DATA_HANDLER_JOURNALINE)) {
+    set_error("dabx_set_data_mode: bad configuration (size %u, handler %d)", cfg->size, cfg->size >= 2 * sizeof(uint32_t) ? (int)cfg->handler : 0);
+    return DABX_E_ARG;
+  }
+  if (cfg && cfg->size >= sizeof(dabx_data_config)) for (int r : cfg->reserved) if (r) { set_error("dabx_set_data_mode: a reserved word is not 0"); return DABX_E_ARG; }
+  const int only_new = cfg && cfg->size >= 3 * sizeof(uint32_t) && cfg->only_new_revisions ? 1 : 0;
+  int rc;
+  if ((rc = sync_all(e))) return rc;
+  const size_t sj = (size_t)stream * e->dev.max_subch + j;
+  if (cfg && !e->pkt.on(sj)) { set_error("dabx_set_data_mode: stream %d slot %d is not in packet mode (dabx_set_packet_mode)", stream, j); return DABX_E_ARG; }
+  auto &tab = e->dat;
+  if (tab.host.empty()) {
+    if (!cfg) return 0;
+    tab.host.resize((size_t)e->dev.n_streams * e->dev.max_subch);
+    tab.index.assign(tab.host.size(), -1);
+  }
+  PacketSlot ps{};                                                     // the walk starts with the next data group completed (read before
+  if (cfg) DABX_HIP(hipMemcpy(&ps, e->pkt.dev.slots + e->pkt.index[sj], sizeof(PacketSlot), hipMemcpyDeviceToHost));      // anything is dropped)
+  if ((rc = tab.download(e->dev.max_subch))) return rc;
+  tab.drop(sj);
+  if (cfg) {
+    decltype(e->dat)::Host h;
+    h.on = true;
+    DataSlot &st = h.st;
+    st.s = stream; st.j = j; st.pkt_index = e->pkt.index[sj]; st.handler = cfg->handler; st.only_new = only_new;
+    st.groups_seen = ps.out.count;
+    // a handler's output is never longer than the groups it reads: the packet slot's byte ring, and in a chunk of the delivery the packet
+    // slot's room; nothing is written beyond n_bytes before an item is complete
+    const bool jl = cfg->handler == DABX_DATA_HANDLER_JOURNALINE;
+    if (!out_ring_create(&st.out, ps.out.bytes_mask + 1, DATA_REC_RING, 0, DATA_REC_RING, ps.out.dl_bytes_cap, jl ? DATA_JL_TABLE : 0)) {
+      set_error("dabx_set_data_mode: out of device memory");
+      (void)tab.upload();
+      return DABX_E_NOMEM;
+    }
+    tab.host[sj] = h;
+    if (jl) {
+      tab.host[sj].st.jl = st.out.bytes + (size_t)st.out.bytes_mask + 1;
+      if (hipMemset(tab.host[sj].st.jl, DATA_JL_NONE, DATA_JL_TABLE) != hipSuccess) {      // no object id filed
+        tab.drop(sj);
+        (void)tab.upload();
+        set_error("dabx_set_data_mode: clearing the Journaline table failed");
+        return DABX_E_HIP;
+      }
+    }
+  }
+  if ((rc = tab.upload())) return rc;
+  SubchDev sc;
+  DABX_HIP(hipMemcpy(&sc, e->dev.subch + sj, sizeof(SubchDev), hipMemcpyDeviceToHost));
+  return relayout_open_delivery(e, sj, sc, e->pkt, e->pad, e->mot, e->car, e->mpa, e->aac);
+}
+
+int dabx_read_data_items(dabx_engine *e, int stream, int j, int n, dabx_data_item *info, uint8_t *bytes, size_t max_bytes)
+{
+  if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch || n <= 0 || !info) { set_error("dabx_read_data_items: bad argument"); return DABX_E_ARG; }
+  return ring_read(e, e->dat, (size_t)stream * e->dev.max_subch + j, n, info, bytes, max_bytes);
+}
+
+int dabx_get_data_stats(dabx_engine *e, int stream, int j, dabx_data_stats *out)
+{
+  if (!e || stream < 0 || stream >= e->dev.n_streams || j < 0 || j >= e->dev.max_subch || !out) { set_error("dabx_get_data_stats: bad argument"); return DABX_E_ARG; }
+  memset(out, 0, sizeof(*out));
+  out->launches = e->dat_ctl.launches;
+  const size_t sj = (size_t)stream * e->dev.max_subch + j;
+  if (!e->dat.on(sj)) return sync_all(e);
+  DataSlot st;
+  long long lo = 0;
+  if (int rc = ring_window(e, e->dat, sj, &st, &lo)) return rc;
+  out->groups = st.groups; out->items = st.out.count; out->bytes = st.out.n_bytes; out->lost = e->dat.host[sj].lost;
+  memcpy(&out->dg_overrun, &st.c, sizeof(DataCounters));
+  out->active = 1; out->handler = st.handler;
+  return 0;
+}
+
+int dabx_data_handler_for(int dscty, int app_type) { return data_handler_for(dscty, app_type); }
+
+// Measuring entry (tools/bench_data_handlers.py; not part of include/dabx.h), as dabx_internal_fig_timing: on = 1, every k_data_handler launch
+// from now on lies between two events of its own; on = 0, the engine is drained, the launches' times go to ms[0 .. max), oldest first, and the
+// events are freed.  Returns the number of launches that were timed.
+int dabx_internal_data_timing(dabx_engine *e, int on, float *ms, int max)
+{
+  if (!e || (max > 0 && !ms) || max < 0) { set_error("dabx_internal_data_timing: bad argument"); return DABX_E_ARG; }
+  if (int rc = sync_all(e)) return rc;
+  DataStageCtl &T = e->dat_ctl;
+  const int n = (int)(T.timed.size() / 2);
+  for (int i = 0; i < n; i++) {
+    float v = 0.f;
+    if (i < max && hipEventElapsedTime(&v, T.timed[2 * (size_t)i], T.timed[2 * (size_t)i + 1]) == hipSuccess) ms[i] = v;
+    (void)hipEventDestroy(T.timed[2 * (size_t)i]);
+    (void)hipEventDestroy(T.timed[2 * (size_t)i + 1]);
+  }
+  T.timed.clear();
+  T.timing = on != 0;
+  return n;
 }
 
 }  // extern "C"

@@ -10,6 +10,8 @@
 //   k_mot          MOT objects out of the X-PAD data groups the two PAD kernels have just emitted (pad_handler.cpp:553-622, mot_object.cpp:71-323)
 //   k_carousel     MOT objects out of the MSC data groups k_packet has just completed: MotHandler and MotDirectory (mot_handler.cpp:69-259,
 //                  mot_dir.cpp:28-156); launched right behind k_packet
+//   k_data_handler TDC frames, UDP payloads and NML objects out of the MSC data groups k_packet has just completed: tdc_dataHandler, IpDataHandler
+//                  and JournalineDataHandler (data_core.h); launched behind k_packet too, beside k_carousel
 //
 // Which logical frames of a slot are new in a batch is msc_new_frames (pipeline.h), for every stage and for the delivery (deliver.hip).
 #include "pipeline.h"
@@ -17,6 +19,7 @@
 #include "pad_core.h"
 #include "mot_core.h"
 #include "carousel_core.h"
+#include "data_core.h"
 #include "mp2_core.h"
 #include "aac_core.h"
 #include "fec_core.h"
@@ -860,6 +863,101 @@ __global__ __launch_bounds__(64) void k_carousel(CarouselDev cd)
   if (lane == 0) { cs.d = cw.d; cs.c = w.c; cs.x = cw.x; cs.out.count = w.n_recs; cs.out.n_bytes = w.n_bytes; cs.groups_seen = count; }
 }
 
+// ----------------------------------------------------------------------------------------- data handlers
+// One wave per packet-mode slot with a data handler on (DataDev::slots: those slots only), behind k_packet: walks the data groups k_packet
+// has completed since this slot's last visit as k_carousel does (PacketSlot::out.count against DataSlot::groups_seen; out_ring_oldest and
+// out_ring_intact are checked and a violation is counted in dg_overrun instead of read) and hands each to the slot's handler
+// (data_core.h: tdc_datahandler.cpp:52-193, ip_datahandler.cpp:44-148, dabdgdec_impl.c:130-296 with journaline_datahandler.cpp:38-132,
+// line by line).  The group is staged in LDS with dword loads -- at the byte offset it has in its first ring word, so ring words and LDS
+// words line up; a ring of a power of two never splits a word at its end -- and a handler reads nothing but those N bytes.
+// LDS: the group (DABX_DG_MAX_BYTES + 8), the two CRC tables (2 560) and the counters (200).  include/dabx.h "The data handlers of a packet-mode slot" states the semantics and the guards T1..T3, I1, J1.
+struct DataLds {
+  __attribute__((aligned(16))) uint8_t g[DABX_DG_MAX_BYTES + 8];
+  uint16_t crc[256], xpow[DATA_XPOW];        // the CCITT table and x^(8 m) mod P (serial look-up chains: in LDS, as k_packet keeps them)
+  DataCounters c;                              // the slot's counters for the launch: lane 0 counts
+};
+
+// the group at ring bytes [pos, pos + N), N <= DABX_DG_MAX_BYTES, into lds.g; returns where its byte 0 lies.  The barrier in front says the
+// previous group is done with, the one behind that this one is there.
+__device__ __forceinline__ const uint8_t *data_stage(DataLds &lds, const uint8_t *ring, unsigned long long mask, long long pos, int N, int lane)
+{
+  const int skew = (int)(pos & 3);
+  __syncthreads();
+  for (int k = lane; 4 * k < skew + N; k += 64)
+    reinterpret_cast<uint32_t *>(lds.g)[k] = *reinterpret_cast<const uint32_t *>(ring + (size_t)((unsigned long long)(pos - skew + 4 * k) & mask));
+  __syncthreads();
+  return lds.g + skew;
+}
+
+__device__ __forceinline__ void data_wave_open(DataWave &w, DataLds &lds, const DataSlot &ds, const uint16_t *crc, const uint16_t *xpow, int lane)
+{
+  for (int i = lane; i < 256; i += 64) lds.crc[i] = crc[i];
+  for (int i = lane; i < DATA_XPOW; i += 64) lds.xpow[i] = xpow[i];
+  if (lane == 0) lds.c = ds.c;               // (data_stage's barrier in front of the first group says all of it is there)
+  w.recs = ds.out.recs; w.ring = ds.out.bytes; w.rec_mask = ds.out.rec_mask; w.bytes_mask = ds.out.bytes_mask;
+  w.n_recs = ds.out.count; w.n_bytes = ds.out.n_bytes; w.groups = ds.groups;
+  w.jl = ds.jl; w.crc = lds.crc; w.xpow = lds.xpow; w.only_new = ds.only_new; w.lane = lane; w.c = &lds.c;
+}
+
+// the records [seen, count) of a ring of data groups (recs, rec_mask; their bytes in ring, mask) through the slot's handler
+__device__ __forceinline__ void data_walk(DataWave &w, DataLds &lds, int handler, const dabx_datagroup_info *recs, unsigned long long rec_mask, const uint8_t *ring,
+                                          unsigned long long mask, const OutRing<dabx_datagroup_info> *intact, long long seen, long long count, int lane)
+{
+  for (long long i = seen; i < count; i++) {
+    const unsigned long long *r = reinterpret_cast<const unsigned long long *>(recs + (size_t)((unsigned long long)i & rec_mask));
+    const long long pos = (long long)(((unsigned long long)pad_u((unsigned)(r[0] >> 32)) << 32) | pad_u((unsigned)r[0]));
+    if (intact && !out_ring_intact(*intact, pos)) { data_count(w, &DataCounters::dg_overrun); continue; }
+    const long long frame = (long long)(((unsigned long long)pad_u((unsigned)(r[2] >> 32)) << 32) | pad_u((unsigned)r[2]));      // last_frame
+    const unsigned lo = pad_u((unsigned)r[3]);                   // length, crc_flag, crc_ok
+    const int N = (int)(lo & 0xFFFFu);
+    if (N > DABX_DG_MAX_BYTES) { data_count(w, &DataCounters::dg_overrun); continue; }   // (cannot happen: k_packet bounds a series there)
+    const uint8_t *g = data_stage(lds, ring, mask, pos, N, lane);
+    data_group(w, handler, g, N, ((lo >> 16) & 0xFFu) != 0, ((lo >> 24) & 0xFFu) != 0, frame, (unsigned)i);
+  }
+}
+
+__global__ __launch_bounds__(64) void k_data_handler(DataDev dd)
+{
+  const int lane = threadIdx.x;
+  DataSlot &ds = dd.slots[blockIdx.x];
+  if (ds.pkt_index < 0 || ds.pkt_index >= dd.n_pkt) return;
+  const PacketSlot &ps = dd.pkt_slots[ds.pkt_index];
+  const long long count = ps.out.count;
+  long long seen = ds.groups_seen;
+  if (count <= seen) return;
+  __shared__ DataLds lds;
+  DataWave w;
+  data_wave_open(w, lds, ds, dd.crc_ccitt, dd.crc_xpow, lane);
+  const long long oldest = out_ring_oldest(ps.out);
+  if (seen < oldest) { if (lane == 0) lds.c.dg_overrun += oldest - seen; seen = oldest; }      // (cannot happen: the stage runs behind every batch)
+  data_walk(w, lds, ds.handler, ps.out.recs, ps.out.rec_mask, ps.out.bytes, ps.out.bytes_mask, &ps.out, seen, count, lane);
+  if (lane == 0) { ds.c = lds.c; ds.groups = w.groups; ds.out.count = w.n_recs; ds.out.n_bytes = w.n_bytes; ds.groups_seen = count; }
+}
+
+// ... and the same walk over crafted groups without an engine (dabx_internal_data_walk_device): slot b's n_groups records, byte_pos counted
+// in a ring of bytes_mask + 1 bytes that all slots share
+__global__ __launch_bounds__(64) void k_data_batch(DataBatchSlot *slots, const uint8_t *bytes, unsigned long long bytes_mask, const uint16_t *crc, const uint16_t *xpow)
+{
+  const int lane = threadIdx.x;
+  DataBatchSlot &bs = slots[blockIdx.x];
+  DataSlot &ds = bs.st;
+  __shared__ DataLds lds;
+  DataWave w;
+  data_wave_open(w, lds, ds, crc, xpow, lane);
+  data_walk(w, lds, ds.handler, bs.groups, ~0ull, bytes, bytes_mask, nullptr, 0, bs.n_groups, lane);
+  if (lane == 0) { ds.c = lds.c; ds.groups = w.groups; ds.out.count = w.n_recs; ds.out.n_bytes = w.n_bytes; ds.groups_seen = bs.n_groups; }
+}
+
+int launch_data_batch(DataBatchSlot *slots, int n_slots, const uint8_t *bytes, unsigned long long bytes_mask, hipStream_t st)
+{
+  const DevTables *t;
+  int rc = get_tables(&t);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_data_batch, dim3(n_slots), dim3(64), 0, st, slots, bytes, bytes_mask, t->crc_ccitt, t->crc_xpow);
+  DABX_HIP(hipGetLastError());
+  return 0;
+}
+
 // ---------------------------------------------------------------------------------------------- launchers
 // One per stage, on the stream launch_msc_batch gives them.  The packet and PAD launchers take the engine's job table (null or n = 0: the
 // engine has no such slot, no launch), fill in what the kernel reads of the engine and leave the argument they launched with in *used for
@@ -913,6 +1011,35 @@ int launch_carousel_stage(const EngineDev &e, const CarouselDev *car, const Pack
   mk.begin(14, st);
   hipLaunchKernelGGL(k_carousel, dim3(q.n), dim3(64), 0, st, q);
   mk.end(14, st);
+  DABX_HIP(hipGetLastError());
+  *used = q;
+  return 0;
+}
+
+// behind k_packet, as k_carousel: k_data_handler reads the packet rings as that launch left them.  No marker: the profile table has no row
+// for it (ctl->launches counts for dabx_data_stats; tools/bench_data_handlers.py times it through dabx_internal_data_timing)
+int launch_data_stage(const EngineDev &e, const DataDev *data, const PacketDev &pk, hipStream_t st, DataStageCtl *ctl, DataDev *used)
+{
+  *used = DataDev{};
+  if (!data || data->n <= 0 || pk.n <= 0) return 0;
+  DataDev q = *data;
+  q.max_subch = e.max_subch; q.pkt_slots = pk.slots; q.n_pkt = pk.n; q.crc_ccitt = pk.crc_ccitt; q.crc_xpow = pk.crc_xpow;
+  hipEvent_t ev[2] = {nullptr, nullptr};     // dabx_internal_data_timing: the launch between two events of its own
+  if (ctl && ctl->timing && (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess || hipEventRecord(ev[0], st) != hipSuccess)) {
+    for (hipEvent_t v : ev) if (v) (void)hipEventDestroy(v);
+    set_error("launch_data_stage: no event pair for the launch");
+    return DABX_E_HIP;
+  }
+  hipLaunchKernelGGL(k_data_handler, dim3(q.n), dim3(64), 0, st, q);
+  if (ev[1]) {                               // the pair is kept only once both events are recorded
+    if (hipEventRecord(ev[1], st) != hipSuccess) {
+      for (hipEvent_t v : ev) (void)hipEventDestroy(v);
+      set_error("launch_data_stage: the event behind the launch was not recorded");
+      return DABX_E_HIP;
+    }
+    ctl->timed.push_back(ev[0]); ctl->timed.push_back(ev[1]);
+  }
+  if (ctl) ctl->launches++;
   DABX_HIP(hipGetLastError());
   *used = q;
   return 0;

@@ -3,6 +3,8 @@
 #include "dabx_internal.h"
 #include "ring_fmt.h"
 #include <cstddef>
+#include <vector>
+#include <hip/hip_runtime.h>
 
 namespace dabx {
 
@@ -401,6 +403,14 @@ struct MotDev;                    // mot_core.h
 struct CarouselDev;               // carousel_core.h
 struct Mp2AudioDev;               // mp2_core.h
 struct AacStreamDev;              // aac_core.h
+struct DataDev;                   // data_core.h
+// what the engine keeps of k_data_handler beside its job table: the launches so far (dabx_data_stats.launches) and, while `timing` is on
+// (dabx_internal_data_timing), a pair of events around every launch -- two more per launch for as long as it is on, without a bound: a
+// measuring entry, switched on for a run and read out behind it
+struct DataStageCtl {
+  long long launches = 0; bool timing = false; std::vector<hipEvent_t> timed;
+  unsigned long long off_data = 0;        // dabx_chunk_header_ext2.off_data of the chunk being packed (0: the slab has no data section)
+};
 struct ScopeDev;                  // scope_core.h
 struct CirDev;                    // cir_core.h
 struct SpecDev;                   // spectrum_core.h
@@ -411,7 +421,8 @@ int launch_front_step(const EngineDev &e, EngineStreams &ss, Marker &mk, bool as
 int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineStreams &ss, Marker &mk, const DeliverDev *dv = nullptr,
                      hipStream_t *tail = nullptr, const PacketDev *pk = nullptr, const PadDev *pad = nullptr, const MotDev *mot = nullptr,
                      const CarouselDev *car = nullptr, const EtiDev *eti = nullptr, const Mp2AudioDev *mp2a = nullptr, long long *mp2a_launches = nullptr,
-                     const AacStreamDev *aac = nullptr, long long *aac_launches = nullptr);
+                     const AacStreamDev *aac = nullptr, long long *aac_launches = nullptr,
+                     const DataDev *data = nullptr, DataStageCtl *data_ctl = nullptr);
 int launch_dciq(const EngineDev &e, int mode, hipStream_t st);
 int launch_level_exact(const EngineDev &e, hipStream_t st);
 int launch_commit(const EngineDev &e, int stream, unsigned long long n, hipStream_t st);
@@ -436,6 +447,8 @@ int launch_deliver_pad(const EngineDev &e, const DeliverDev &dv, const PadDev &p
 int launch_deliver_mot(const EngineDev &e, const DeliverDev &dv, const MotDev &md, hipStream_t st);
 int launch_deliver_carousel(const EngineDev &e, const DeliverDev &dv, const CarouselDev &cd, hipStream_t st, bool clear_table);
 int launch_deliver_mp2_audio(const EngineDev &e, const DeliverDev &dv, const Mp2AudioDev &ad, unsigned long long off_mp2_audio, hipStream_t st);
+int launch_deliver_data(const EngineDev &e, const DeliverDev &dv, const DataDev &dd, unsigned long long off_data, hipStream_t st);
+int launch_deliver_ext2(const dabx_chunk_header_ext2 &ext2, uint8_t *slab, hipStream_t st);
 int launch_deliver_aac(const EngineDev &e, const DeliverDev &dv, const AacStreamDev &ad, unsigned long long off_aac, hipStream_t st);
 int launch_deliver_ext(const dabx_chunk_header_ext &ext, uint8_t *slab, hipStream_t st);           // at chunk close, front-end stream: the header's extension of a slab without a TII section
 // at chunk close, front-end stream, behind launch_deliver_front: record section `section` (REC_*); REC_TII writes the header's extension too
@@ -449,6 +462,7 @@ int launch_pad_stage(const EngineDev &e, const PadDev *pad, hipStream_t st, Mark
 int launch_mot_stage(const EngineDev &e, const MotDev *mot, const PadDev &pad, hipStream_t st, Marker &mk, MotDev *used);
 int launch_mp2_audio_stage(const EngineDev &e, const Mp2AudioDev *ma, hipStream_t st, Mp2AudioDev *used);
 int launch_aac_stream_stage(const EngineDev &e, const AacStreamDev *aa, hipStream_t st, AacStreamDev *used);
+int launch_data_stage(const EngineDev &e, const DataDev *data, const PacketDev &pk, hipStream_t st, DataStageCtl *ctl, DataDev *used);
 int launch_carousel_stage(const EngineDev &e, const CarouselDev *car, const PacketDev &pk, hipStream_t st, Marker &mk, CarouselDev *used);
 // fib.cpp
 void dabx_internal_fibdec_skip(dabx_fibdec *d, long long n_fibs);     // FIBs the decoder never saw (they had left the ring)

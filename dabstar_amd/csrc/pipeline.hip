@@ -23,6 +23,7 @@
 #include "carousel_core.h"
 #include "mp2_core.h"
 #include "aac_core.h"
+#include "data_core.h"
 #include <algorithm>
 #include "ofdm_core.h"
 #include "scope_core.h"
@@ -2403,11 +2404,11 @@ int launch_front_step(const EngineDev &e_in, EngineStreams &ss, Marker &mk, bool
 // `e.snap` must point at the snapshot buffer of this batch.
 // `dv` (optional): the chunk's slot gather (deliver.hip) goes behind the DAB+ stage on the stream that ran it, before the batch's
 // completion event; *tail (optional) = the stream whose work completes the batch.
-// `pk`, `pad`, `mot`, `car` (optional): the engine's packet-mode / PAD / MOT / carousel slots, for the slot stages (msc_stages.hip) and the gathers of what
+// `pk`, `pad`, `mot`, `car`, `data` (optional): the engine's packet-mode / PAD / MOT / carousel / data-handler slots, for the slot stages (msc_stages.hip) and the gathers of what
 // they emitted.
 int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineStreams &ss, Marker &mk, const DeliverDev *dv, hipStream_t *tail,
                      const PacketDev *pk, const PadDev *pad, const MotDev *mot, const CarouselDev *car, const EtiDev *eti, const Mp2AudioDev *mp2a,
-                     long long *mp2a_launches, const AacStreamDev *aac, long long *aac_launches)
+                     long long *mp2a_launches, const AacStreamDev *aac, long long *aac_launches, const DataDev *data, DataStageCtl *data_ctl)
 {
   const DevTables *t;
   int rc = get_tables(&t);
@@ -2500,8 +2501,10 @@ int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineSt
   CarouselDev c;
   Mp2AudioDev au;
   AacStreamDev ac;
+  DataDev dh;
   if ((rc = launch_packet_stage(e, pk, sb, mk, &p))) return rc;
   if ((rc = launch_carousel_stage(e, car, p, sb, mk, &c))) return rc;
+  if ((rc = launch_data_stage(e, data, p, sb, data_ctl, &dh))) return rc;       // TDC / IP / Journaline handlers of the slots that have one: launched only when there is one
   if ((rc = launch_dabplus_stage(e, sb, mk))) return rc;
   if ((rc = launch_pad_stage(e, pad, sb, mk, &q))) return rc;
   if ((rc = launch_mot_stage(e, mot, q, sb, mk, &m))) return rc;
@@ -2517,6 +2520,7 @@ int launch_msc_batch(const EngineDev &e, int cifs, const MscFast *fast, EngineSt
   if (dv && c.n > 0 && (rc = launch_deliver_carousel(e, *dv, c, sb, m.n <= 0))) return rc;      // ... the carousel slots' rows of it
   if (dv && au.n > 0 && (rc = launch_deliver_mp2_audio(e, *dv, au, dv->off_mp2_audio, sb))) return rc;      // ... and its MP2 audio section
   if (dv && ac.n > 0 && (rc = launch_deliver_aac(e, *dv, ac, dv->off_aac, sb))) return rc;      // ... and its AAC section
+  if (dv && dh.n > 0 && data_ctl && (rc = launch_deliver_data(e, *dv, dh, data_ctl->off_data, sb))) return rc;      // ... and its data section
   if (tail) *tail = sb;
   if (ss.b) {
     DABX_HIP(hipEventRecord(ss.msc_done, ss.b));

@@ -76,6 +76,10 @@ def load(build_if_missing=True):
     if hasattr(L, "dabx_set_carousel_mode"):         # MOT objects of a packet-mode carousel
         L.dabx_set_carousel_mode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.dabx_get_carousel_stats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    if hasattr(L, "dabx_set_data_mode"):             # TDC / IP / Journaline handlers of a packet-mode slot
+        L.dabx_set_data_mode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.dabx_read_data_items.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.dabx_get_data_stats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     if hasattr(L, "dabx_get_mp2_sync_stats"):        # ... and of DAB (MP2) audio slots
         L.dabx_get_mp2_sync_stats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     if hasattr(L, "dabx_set_mp2_audio_mode"):        # MP2 audio of DAB audio slots
@@ -1043,6 +1047,66 @@ class CarouselConfig(C.Structure):
                 ("reserved", C.c_int32 * 4)]
 
 
+# The data handlers of a packet-mode slot (include/dabx.h): dabx_data_item, one record per TDC frame, UDP payload or NML object, and
+# dabx_data_stats: one int64 per decision and guard
+DATA_HANDLERS = {"tdc": 1, "ip": 2, "journaline": 3}
+DATA_HANDLER_MOT = 4
+DATA_TDC_0, DATA_TDC_1, DATA_UDP, DATA_NML = 1, 2, 3, 4
+DATA_CRC_OK, DATA_NEW_REVISION = 1, 2
+DATA_ITEM = np.dtype([("byte_pos", "<i8"), ("frame", "<i8"), ("length", "<u2"), ("kind", "u1"), ("flags", "u1"), ("a", "<u2"), ("b", "<u2"),
+                      ("group", "<u4"), ("reserved", "<u4")])
+DATA_COUNTERS = ("groups", "items", "bytes", "dg_overrun", "walk_end", "tdc_cut", "tdc_len_bad", "tdc_hdr_crc_bad", "tdc_crc0_bad", "tdc_crc0_short",
+                 "tdc_type_other", "ip_dg_crc_bad", "ip_len_bad", "ip_not_v4", "ip_checksum_bad", "ip_proto_other", "ip_short", "jl_hdr_short",
+                 "jl_segmented", "jl_empty", "jl_len_bad", "jl_crc_bad", "jl_no_crc", "jl_type_other", "nml_too_long", "nml_short", "nml_type_bad",
+                 "nml_repeat")
+DATA_STATS = np.dtype([(k, "<i8") for k in DATA_COUNTERS[:3] + ("lost",) + DATA_COUNTERS[3:] + ("launches", "active", "handler")])
+# ... in bulk: DELIVER_DATA = 524288 (opt-in like DELIVER_FIG; 1024, 4096, 16384 and 131072 stay refused), announced by a SECOND extension of
+# the header at byte 192 (CHUNK_HEADER_EXT2; off_stream is then 256), one CHUNK_DATA per (stream, slot)
+DELIVER_DATA = 524288
+CHUNK_EXT2_MAGIC = 0x32584244                    # "DBX2"
+CHUNK_HEADER_EXT2 = np.dtype([("magic", "<u4"), ("bytes", "<u4"), ("off_data", "<u8"), ("reserved", "<u8", 6)])
+CHUNK_DATA = np.dtype([("first_item", "<i8"), ("n_items", "<i4"), ("items_lost", "<i4"), ("rec_off", "<u8"), ("bytes_off", "<u8"), ("n_bytes", "<i8")] +
+                      [(k, "<i8") for k in ("groups", "items", "bytes")] + [("reserved", "<i8", 8)])
+assert DATA_ITEM.itemsize == 32 and DATA_STATS.itemsize == 256 and CHUNK_HEADER_EXT2.itemsize == 64 and CHUNK_DATA.itemsize == 128
+
+
+class DataConfig(C.Structure):
+    """dabx_data_config."""
+    _fields_ = [("size", C.c_uint32), ("handler", C.c_int32), ("only_new_revisions", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+def data_handler_for(dscty, app_type):
+    """dabx_data_handler_for: DATA_HANDLERS' value, DATA_HANDLER_MOT or 0 for a packet-mode component (data_processor.cpp:53-101)."""
+    return int(load().dabx_data_handler_for(int(dscty), int(app_type)))
+
+
+def data_walk(handler, records, group_bytes, only_new_revisions=False, device=False, max_items=4096, out_cap=1 << 20):
+    """One slot's crafted data groups through a handler without an engine (dabx_internal_data_walk_host / _device: test entries, not part of
+    include/dabx.h): records [n] DATAGROUP_INFO with byte_pos into group_bytes.  device = False: the host build of the handlers, needs no
+    device; True: k_data_batch, the body of the engine's k_data_handler.  Returns (items [k] DATA_ITEM, their bytes, stats dict)."""
+    L = load()
+    call = L.dabx_internal_data_walk_device if device else L.dabx_internal_data_walk_host
+    call.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    records = np.ascontiguousarray(records, DATAGROUP_INFO)
+    group_bytes = np.ascontiguousarray(group_bytes, np.uint8)
+    items, out, st = np.zeros(max_items, DATA_ITEM), np.zeros(out_cap, np.uint8), np.zeros(1, DATA_STATS)
+    k = check(call(DATA_HANDLERS[handler] if isinstance(handler, str) else int(handler), int(bool(only_new_revisions)), len(records),
+                   _p(records) if len(records) else None, _p(group_bytes) if len(group_bytes) else None, len(group_bytes), max_items, _p(items), _p(out), out_cap,
+                   _p(st)))
+    items = items[:k].copy()
+    return items, out[:int(items["length"].sum())].copy(), {n: int(st[0][n]) for n in DATA_STATS.names}
+
+
+def data_timing(engine, on, max_launches=4096):
+    """Measuring entry (dabx_internal_data_timing; not part of include/dabx.h): on = True, every k_data_handler launch from now on lies between
+    two HIP events of its own; on = False: the times (ms, float32) of the launches made since, oldest first."""
+    ms = np.zeros(max_launches, np.float32)
+    L = load()
+    L.dabx_internal_data_timing.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    n = check(L.dabx_internal_data_timing(engine._h, int(bool(on)), _p(ms), max_launches))
+    return ms[:min(n, max_launches)].copy()
+
+
 class MotConfig(C.Structure):
     """dabx_mot_config."""
     _fields_ = [("size", C.c_uint32), ("max_object_bytes", C.c_uint32), ("reserved", C.c_int32 * 6)]
@@ -1135,6 +1199,15 @@ class Chunk:
             if int(self.header_ext["off_fig"]):
                 o = int(self.header_ext["off_fig"])
                 self.fig_table = self.raw[o:o + S * 32].view(CHUNK_FIG)
+        self.header_ext2 = None                 # the second extension (CHUNK_HEADER_EXT2) when `what` has DELIVER_DATA, else None
+        self.data_table = None                  # the data section: [S, M] CHUNK_DATA, or None when the slab has none
+        if int(h["what"]) & DELIVER_DATA:
+            self.header_ext2 = self.raw[192:256].view(CHUNK_HEADER_EXT2)[0]
+            if int(self.header_ext2["magic"]) != CHUNK_EXT2_MAGIC or int(self.header_ext2["bytes"]) < 64:
+                raise DabxError("chunk %d: bad second header extension" % self.seq)
+            if int(self.header_ext2["off_data"]):
+                o = int(self.header_ext2["off_data"])
+                self.data_table = self.raw[o:o + S * M * 128].view(CHUNK_DATA).reshape(S, M)
         self.eti_table = None                  # the ETI section: [S] CHUNK_ETI, or None when the slab has none
         if int(h["off_eti"]):
             self.eti_table = self.raw[int(h["off_eti"]):int(h["off_eti"]) + S * 64].view(CHUNK_ETI)
@@ -1254,6 +1327,13 @@ class Chunk:
         the slab has no AAC section or the slot has not the mode on."""
         rec, by = self._ring_items(self.aac_table, "rec_off", "n_frames", AAC_FRAME, s, j)
         return (self.aac_table[s, j] if self.aac_table is not None and int(self.aac_table[s, j]["rec_off"]) else None), rec, by
+
+    def data(self, s, j):
+        """The handler items of slot (s, j) in this chunk: (its CHUNK_DATA record or None, [n_items] DATA_ITEM, their n_bytes bytes), views;
+        item i is bytes[byte_pos[i] : byte_pos[i] + length[i]].  None and empty when the slab has no data section or the slot has no
+        handler on."""
+        rec, by = self._ring_items(self.data_table, "rec_off", "n_items", DATA_ITEM, s, j)
+        return (self.data_table[s, j] if self.data_table is not None and int(self.data_table[s, j]["rec_off"]) else None), rec, by
 
     def release(self):
         if self._eng is not None:
@@ -1792,6 +1872,29 @@ class Engine:
         out = np.zeros(1, CAROUSEL_STATS)
         check(load().dabx_get_carousel_stats(self._h, int(stream), int(j), _p(out)))
         return {k: int(out[0][k]) for k in CAROUSEL_STATS.names}
+
+    def set_data_mode(self, stream, j, handler="tdc", only_new_revisions=False, on=True):
+        """Switches a data handler of packet-mode slot j of `stream` on (restarting it when one is on already) or off (dabx_set_data_mode).
+        handler: "tdc", "ip" or "journaline" (an integer is passed on as it is); only_new_revisions: Journaline objects whose revision
+        is the one filed are not emitted.  The items are read with read_data_items."""
+        L = load()
+        if not on:
+            check(L.dabx_set_data_mode(self._h, int(stream), int(j), None))
+        else:
+            cfg = DataConfig(size=C.sizeof(DataConfig), handler=DATA_HANDLERS[handler] if isinstance(handler, str) else int(handler),
+                             only_new_revisions=int(bool(only_new_revisions)))
+            check(L.dabx_set_data_mode(self._h, int(stream), int(j), C.byref(cfg)))
+
+    def read_data_items(self, stream, j, n=256, max_bytes=None, with_bytes=True):
+        """(records [k] DATA_ITEM, bytes uint8) of the newest k <= n items of slot j that are still in its rings, oldest first; item i is
+        bytes[byte_pos[i] : byte_pos[i] + length[i]].  with_bytes = False: the records alone."""
+        return self._read_ring(load().dabx_read_data_items, DATA_ITEM, DG_RING_MAX_BYTES, stream, j, n, max_bytes, with_bytes)
+
+    def data_stats(self, stream, j):
+        """dabx_data_stats of slot j as a dict (all zero but `launches` unless a handler is on for the slot)."""
+        out = np.zeros(1, DATA_STATS)
+        check(load().dabx_get_data_stats(self._h, int(stream), int(j), _p(out)))
+        return {k: int(out[0][k]) for k in DATA_STATS.names}
 
     def set_mp2_audio_mode(self, stream, j, on=True):
         """Switches the MP2 audio decoding of DAB audio slot j of `stream` on (restarting it, as a fresh Mp2Processor, when it is on already)

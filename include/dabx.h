@@ -856,8 +856,8 @@ int  dabx_get_mot_stats(dabx_engine *e, int stream, int subch_idx, dabx_mot_stat
  * segment-number range is kept whole.  The defaults take 9.3 MB.
  * Parity of this path with the reference's object code is unpinned: mot_handler.cpp cannot be compiled without the GUI's headers
  * (dabradio.h), so the tests compare the device with a line-by-line restatement (tests/carousel_cases.py).
- * Out of scope: the SPI/EPG decoders, image decoding, the charset of the object name, the default name "trid_<n>", the Journaline, TDC
- * and IP handlers, packet-mode FEC. */
+ * Out of scope: the SPI/EPG decoders, image decoding, the charset of the object name, the default name "trid_<n>", packet-mode FEC.  The
+ * Journaline, TDC and IP handlers: the next section. */
 #define DABX_MOT_FLAG_DIR_ELEMENT 1   /* dabx_mot_object.au of a carousel slot, bit 0: the dirElement argument of signal_new_mot_object */
 typedef struct {
   uint32_t size;             /* sizeof(dabx_carousel_config) of the caller */
@@ -906,6 +906,149 @@ typedef struct {
  * flags: DABX_MOT_FLAG_DIR_ELEMENT.  An engine without a carousel slot allocates and launches nothing for this stage.  Drains the engine. */
 int  dabx_set_carousel_mode(dabx_engine *e, int stream, int subch_idx, const dabx_carousel_config *cfg);
 int  dabx_get_carousel_stats(dabx_engine *e, int stream, int subch_idx, dabx_carousel_stats *out);
+/* ------------------------------------------------------------------------------------------------------------
+ * The data handlers of a packet-mode slot: what DataProcessor does with the MSC data groups of a packet-mode sub-channel whose handler is
+ * not MotHandler (data_processor.cpp:53-101, :208, :236) behind the hand-over of dabx_datagroup_info -- tdc_dataHandler (TPEG; DSCTy 5
+ * with application type 4), IpDataHandler (DSCTy 59) and JournalineDataHandler (DSCTy 44, or DSCTy 5 with application type 0x44a) -- on
+ * the device (k_data_handler, behind k_packet on the MSC batch's stream, one wave per slot with the mode on), down to the bytes a TPEG
+ * decoder, a UDP socket or an NML parser is fed: every put_data_into_ring_buffer / callback is one dabx_data_item plus its bytes.
+ * dabx_data_handler_for says which handler a component needs.  N is the group's length in bytes; the reference's bit offsets are restated
+ * in bytes; every name in the right-hand column of dabx_data_stats is a counter of the decision it stands beside.
+ *
+ * TDC (base/backend/data/tdc_datahandler.cpp:52-193, tdc:).  The whole group is searched, header and CRC included, and the group's own CRC
+ * verdict is not looked at.  From o = 0, while o < N:
+ *   1 o advances byte by byte while o + 2 < N and bytes o, o + 1 are not FF 0F (tdc:62-72); o + 2 >= N: return (tdc:73-76, walk_end).  A
+ *     sync word in the last two bytes is therefore never found.  Kept.
+ *   2 length = bytes o + 2, o + 3 as a SIGNED 16-bit value; length < 0 or length >= N - o: return (tdc:85-88, tdc_len_bad).
+ *   3 the header check (tdc:91-113): bytes o .. o + 3, byte o + 6 and min(length, 11) bytes from o + 7; its CCITT CRC (start 0xFFFF,
+ *     complemented) against bytes o + 4, o + 5; a mismatch: return (tdc_hdr_crc_bad).
+ *   4 type (byte o + 6) 0 (tdc:130-151): the item is `length` bytes from o + 7, DABX_DATA_CRC_OK when check_crc_bytes(frame, length - 2)
+ *     holds; a failure is only counted (tdc_crc0_bad) and the frame goes out all the same.  Type 1 (tdc:153-193): the item is `length`
+ *     bytes from o + 7; the component walk of tdc:171-190 changes nothing observable and reads outside the frame: it is not performed.
+ *     Any other type: return (tdc:123-126, tdc_type_other).
+ *   5 o = o + 7 + length, and the loop goes on.
+ * IP (base/backend/data/ip_datahandler.cpp:44-148, ip:):
+ *   1 crc_flag && !crc_ok of the record: return (ip:59, ip_dg_crc_bad; the CRC is not run again).
+ *   2 next = 2, + 2 with the extension flag, + 2 with the segment flag, whose fields are not used (ip:64-74); with the user-access flag
+ *     lengthInd = the low nibble of the byte at next, next += 1 + lengthInd (ip:78-88; the transport id is not used).
+ *   3 ipLength = bytes next + 2, next + 3, accepted only if ipLength < N (ip:95, else ip_len_bad).  Version nibble != 4: return (ip:103,
+ *     ip_not_v4).
+ *   4 h = low nibble of byte 0 of the datagram; the sum of its 2 h big-endian half-words, folded ONCE, is accepted when the low 16 bits of
+ *     its complement are 0 (ip:121-129, else ip_checksum_bad).  The single fold is kept.  Protocol (byte 9) != 17: return (ip_proto_other).
+ *   5 the item is bytes [4 h + 8, ipLength) of the datagram (ip:134, :145-147); zero bytes is a legal item.
+ * Journaline (base/backend/data/journaline/dabdgdec_impl.c:130-296, dg:; journaline_datahandler.cpp:38-132, jl:; NML.cpp:363-385, nml:),
+ * a counter per return code of DAB_DATAGROUP_DECODER_putData:
+ *   1 N < 2, or the extension flag and N < 4: jl_hdr_short (code 2).  Segment flag: jl_segmented (3).  data_len = N - 2 - 2 ext; 0: jl_empty
+ *     (4).  With the CRC flag: data_len < 2: jl_len_bad (5), then data_len -= 2, and crc_ok == 0 of the record: jl_crc_bad (6; the CRC is
+ *     not run again).  Without the CRC flag: jl_no_crc (7).  Group type != 0: silently ignored (dg:227-235, jl_type_other).  The
+ *     user-access flag is ignored: its field stays in the object.  Kept.
+ *   2 the object is data_len bytes behind the header.  nml_len < 4: nml_short (nml:363-368).  Type bits (byte 2 >> 5) 0 or above 4: the
+ *     reference makes these INVALID and drops them (jl:105-106), so does the device (nml_type_bad).
+ *   3 otherwise one item, DABX_DATA_NEW_REVISION set when the object id was never filed or its revision index differs from the one filed
+ *     (jl:113-125); the table (64 KiB per slot: id -> revision, 0xFF = none) is updated either way.  With only_new_revisions an object
+ *     without the flag is counted (nml_repeat) and not emitted.
+ *   Stated deviation: the device files every object that passes 2; the reference files only what its parser (inflate, item walk) accepted.
+ * Guards, where the reference reads outside the group or its buffer; each is counted and the handler returns:
+ *   T1 (tdc:80-84): o + 7 > N, length, CRC and type lie beyond the group.  tdc_cut.
+ *   T2 (tdc:103-108, :136-139, :166-169): o + 7 + length > N, the check vector and the copy read up to six bytes beyond the group.  tdc_cut.
+ *   T3 (tdc:140): length < 2, check_crc_bytes reads bytes -2 and -1 of its buffer.  The flag stays clear, tdc_crc0_short, the frame goes out.
+ *   I1 (ip:47-50, :81, :94, :99-103, :114-123, :134, :146), counted once as ip_short and the group dropped: a header field or the length
+ *      word beyond the group; ipLength < 10 (0 included: ipVector[0], data[9]); next + ipLength > N; 4 h > ipLength; ipLength - 4 h - 8 < 0.
+ *      In the order of the reference's reads: flags, lengthInd, length word, then ip:95, then ipLength < 10 and next + ipLength > N, the
+ *      version, 4 h > ipLength, the checksum, the protocol, the negative payload.
+ *   J1 (jl:48): data_len > 4096, the memcpy into nml[4096].  nml_too_long, in front of nml_short.
+ * Memory per slot: a byte ring of the size of the packet slot's byte ring (a handler's output is never longer than the groups it reads), 256
+ * records, and 64 KiB for a Journaline slot.
+ * Parity of this path with the reference's object code is unpinned, as for every DataProcessor path: the handlers cannot be compiled
+ * without the GUI's headers (dabradio.h), so the tests compare the device with a line-by-line restatement (tests/data_handler_cases.py).
+ * Out of scope: NML parsing and inflate, TPEG decoding, sending datagrams, _handle_TDC_async_stream (which does nothing observable),
+ * packet-mode FEC.  In bulk the items travel in the data section of the slab (DABX_DELIVER_DATA, dabx_chunk_data below). */
+#define DABX_DATA_HANDLER_TDC 1
+#define DABX_DATA_HANDLER_IP 2
+#define DABX_DATA_HANDLER_JOURNALINE 3
+#define DABX_DATA_HANDLER_MOT 4       /* dabx_data_handler_for only: use dabx_set_carousel_mode */
+#define DABX_DATA_TDC_0 1             /* dabx_data_item.kind: a TDC frame of type 0, ... */
+#define DABX_DATA_TDC_1 2             /* ... of type 1, */
+#define DABX_DATA_UDP 3               /* the payload of a UDP datagram, */
+#define DABX_DATA_NML 4               /* an NML object */
+#define DABX_DATA_CRC_OK 1            /* dabx_data_item.flags, TDC type 0: the frame's own CRC holds */
+#define DABX_DATA_NEW_REVISION 2      /* ... NML: the object id was never filed or its revision index has changed */
+typedef struct {
+  uint32_t size;             /* sizeof(dabx_data_config) of the caller */
+  int32_t  handler;          /* DABX_DATA_HANDLER_TDC, _IP or _JOURNALINE; anything else: DABX_E_ARG */
+  int32_t  only_new_revisions; /* Journaline: objects without DABX_DATA_NEW_REVISION are not emitted.  Read only when size >= 12 */
+  int32_t  reserved[5];      /* zero */
+} dabx_data_config;          /* 32 bytes */
+typedef struct {
+  int64_t  byte_pos;         /* of the item's first byte in the bytes returned with it */
+  int64_t  frame;            /* dabx_datagroup_info.last_frame of the group */
+  uint16_t length;           /* bytes */
+  uint8_t  kind;             /* DABX_DATA_TDC_0, _TDC_1, _UDP, _NML */
+  uint8_t  flags;            /* DABX_DATA_CRC_OK, DABX_DATA_NEW_REVISION */
+  uint16_t a;                /* TDC: the byte offset of the sync word in the group; UDP: the first 16-bit word of the UDP header (source port); NML: the object id */
+  uint16_t b;                /* UDP: the second word (destination port); NML: object byte 2 (type / static / compressed / revision) in the
+                                low byte, byte 1 of the group (continuity / repetition index) in the high byte; TDC: 0 */
+  uint32_t group;            /* the group's index in the slot's sequence of data groups (dabx_packet_stats.dg_count counts them) */
+  uint32_t reserved;
+} dabx_data_item;            /* 32 bytes */
+typedef struct {
+  int64_t groups;            /* data groups handed to the handler */
+  int64_t items, bytes;      /* dabx_data_item records emitted and their bytes */
+  int64_t lost;              /* items that had left the rings before a dabx_read_data_items call could return them */
+  int64_t dg_overrun;        /* data groups that had left the packet rings before k_data_handler reached them (the rings hold two batches: always 0) */
+  int64_t walk_end;          /* TDC 1 */
+  int64_t tdc_cut;           /* guards T1, T2 */
+  int64_t tdc_len_bad;       /* TDC 2 */
+  int64_t tdc_hdr_crc_bad;   /* TDC 3 */
+  int64_t tdc_crc0_bad;      /* TDC 4: a type-0 frame emitted without DABX_DATA_CRC_OK */
+  int64_t tdc_crc0_short;    /* guard T3 */
+  int64_t tdc_type_other;    /* TDC 4 */
+  int64_t ip_dg_crc_bad;     /* IP 1 */
+  int64_t ip_len_bad;        /* IP 3 */
+  int64_t ip_not_v4;         /* IP 3 */
+  int64_t ip_checksum_bad;   /* IP 4 */
+  int64_t ip_proto_other;    /* IP 4 */
+  int64_t ip_short;          /* guard I1 */
+  int64_t jl_hdr_short, jl_segmented, jl_empty, jl_len_bad, jl_crc_bad, jl_no_crc;      /* Journaline 1: return codes 2 .. 7 */
+  int64_t jl_type_other;     /* Journaline 1 */
+  int64_t nml_too_long;      /* guard J1 */
+  int64_t nml_short;         /* Journaline 2 */
+  int64_t nml_type_bad;      /* Journaline 2 */
+  int64_t nml_repeat;        /* Journaline 3: objects held back by only_new_revisions */
+  int64_t launches;          /* k_data_handler launches of the engine (whatever the slot) */
+  int64_t active;            /* 1: a handler is on for the slot (all else but launches is zero otherwise) */
+  int64_t handler;           /* DABX_DATA_HANDLER_* of the slot */
+} dabx_data_stats;           /* 256 bytes */
+/* Switches a data handler of slot subch_idx of `stream` on (cfg != NULL) or off (NULL).  On only for a slot in packet mode
+ * (dabx_set_packet_mode); DABX_E_ARG otherwise, and for an unknown handler or a reserved word that is not 0.  It starts with empty rings
+ * (and an empty Journaline table) at the next data group completed; calling it again restarts it.  Calling dabx_set_packet_mode for the
+ * slot, on or off, ends it: the packet stage restarts with empty rings.  The setting and the state stay with the slot wherever
+ * dabx_set_subchannels says it "keeps decoding without interruption", a move to other capacity units included; a new or changed slot loses
+ * them.  Independent of the carousel mode: both may read the same groups.  The data groups of the slot are produced and delivered exactly
+ * as before.  An engine without such a slot allocates and launches nothing for this stage.  Drains the engine. */
+int  dabx_set_data_mode(dabx_engine *e, int stream, int subch_idx, const dabx_data_config *cfg);
+/* The newest k <= n items of the slot that are still in its rings, oldest first, with exactly the contract of dabx_read_mot_objects: info
+ * [n]; bytes (NULL: the records alone) receives the items' bytes back to back, byte_pos counted from the first returned; of the newest n
+ * only the newest that fit max_bytes are returned.  Returns k; 0 for a slot without a handler.  Drains the engine. */
+int  dabx_read_data_items(dabx_engine *e, int stream, int subch_idx, int n, dabx_data_item *info, uint8_t *bytes, size_t max_bytes);
+int  dabx_get_data_stats(dabx_engine *e, int stream, int subch_idx, dabx_data_stats *out);
+/* The switch of data_processor.cpp:53-101, a pure function: the handler of a packet-mode component with this DSCTy and (first) user
+ * application type (dabx_packet_component; dabx_fig_user_apps_entry).  DABX_DATA_HANDLER_TDC, _IP, _JOURNALINE, DABX_DATA_HANDLER_MOT (use
+ * the carousel mode) or 0: the reference installs an empty handler. */
+int  dabx_data_handler_for(int dscty, int app_type);
+/* The data section (DABX_DELIVER_DATA): one dabx_chunk_data per (stream, slot) from dabx_chunk_header_ext2.off_data, all zero for a slot
+ * without a handler; behind the table every such slot has room for 256 records and for what the slot's data-group room holds (4 * 7
+ * logical frames and DABX_DG_MAX_BYTES: a handler's output is never longer than the groups it read) -- of more the newest that fit are
+ * delivered and the rest counted in items_lost.  Record i's item is the `length` bytes at bytes_off + byte_pos.  Gathered behind the
+ * batch's stages (k_deliver_data) like the AAC section; the section exists while at least one slot has a handler on. */
+typedef struct {
+  int64_t  first_item;       /* number, since the handler was switched on, of the first record in the chunk */
+  int32_t  n_items, items_lost;        /* records in the chunk; records between the previous chunk's and these that were not delivered */
+  uint64_t rec_off, bytes_off;
+  int64_t  n_bytes;
+  int64_t  groups, items, bytes;       /* dabx_data_stats after the chunk's batch */
+  int64_t  reserved[8];
+} dabx_chunk_data;           /* 128 bytes */
 /* ------------------------------------------------------------------------------------------------------------
  * Bulk delivery of the results to the host.  The reference hands every FIB to IFibDecoder::process_FIB
  * (base/decoder/fib_decoder_if.h:81, called from fic_decoder.cpp:234-261) and every logical frame to
@@ -1000,7 +1143,14 @@ enum { DABX_DELIVER_FIB = 1, DABX_DELIVER_MSC = 2, DABX_DELIVER_SF = 4,
           kernels launched are exactly what they are without it.  With the bit the header is followed by a dabx_chunk_header_ext.  The value
           is 262144, not 131072: the mask 131072 has always been refused with DABX_E_ARG, alone and beside other bits, and callers rely on
           that (tests/test_gpu_spectrum_delivery.py), so 131072 stays refused, as 1024, 4096 and 16384 do */
-       DABX_DELIVER_FIG = 262144 };
+       DABX_DELIVER_FIG = 262144,
+       /* the items of every packet-mode slot that has a data handler on (dabx_set_data_mode; the data section, dabx_chunk_data below).
+          Opt-in exactly like the eight bits above: what == 0 does NOT include it, the bit alone or with only DABX_DELIVER_ETI, _TII,
+          _MP2_AUDIO, _AAC, _SCOPE, _CIR, _SPECTRUM and _FIG beside it is DABX_E_ARG, and without the bit a slab, dabx_delivery_slab_bytes and
+          the kernels launched are exactly what they are without it.  dabx_chunk_header_ext is full: with this bit a second extension,
+          dabx_chunk_header_ext2, follows it at byte 192 and announces the section, and off_stream is 256.  1024, 4096, 16384 and 131072
+          stay refused */
+       DABX_DELIVER_DATA = 524288 };
 typedef struct {
   int32_t host_slabs;       /* page-locked host slabs, >= 2 (0 = default 4) */
   int32_t what;             /* DABX_DELIVER_* mask, 0 = everything */
@@ -1039,6 +1189,15 @@ typedef struct {
 #endif
   union { uint64_t off_fig; uint64_t reserved[1]; };
 } dabx_chunk_header_ext;    /* 64 bytes */
+/* The second extension: present when, and only when, dabx_chunk_header.what carries DABX_DELIVER_DATA.  It follows the first at byte 192,
+ * and the stream table then starts at 256 (off_stream says so). */
+#define DABX_CHUNK_EXT2_MAGIC 0x32584244u  /* "DBX2" */
+typedef struct {
+  uint32_t magic;           /* DABX_CHUNK_EXT2_MAGIC */
+  uint32_t bytes;           /* 64 */
+  uint64_t off_data;        /* the data section: dabx_chunk_data[n_streams * max_subch]; 0 = the slab has none */
+  uint64_t reserved[6];     /* zero */
+} dabx_chunk_header_ext2;   /* 64 bytes */
 typedef struct {
   int64_t first_frame;      /* index, since the stream was opened, of the first frame in the chunk */
   int32_t n_frames;         /* frames of this stream in the chunk, 0..max_frames (a stream out of lock delivers none) */
